@@ -2,11 +2,19 @@
 """MHLA operator bench: fwd+bwd tokens/s at (B, N, H, D) on MI355X, with roofline and CPU baseline.
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+  python bench.py ... --full                           (everything else the bench measures, see below)
+  python bench.py ... --dump-outputs DIR               (what the last timed step computed, as DIR/<name>.npy)
 
 A "step" is one forward + backward of the block-mixing MHLA operator over one synthetic batch
 resident in HBM.  Workload at every N (weak scaling, per GPU): BASELINE.json configs[1]
 "Synthetic MHLA op micro-bench B=8 N=4096 H=16 D=64 bf16" with M = 64 blocks of S = 64 tokens.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (headline figure and the roofline
+fraction that follows from it by arithmetic).  `--full` adds every other measurement after the timed
+steps: GPU-event time of the step, per-kernel durations, PMC traffic and MFMA figures, the reduced-precision
+step, the measured peaks, the CPU baselines, the other BASELINE.json shapes, the DiT / GPT / Wan step
+benches and the `targets` block, with the full record written to bench_full.json.
 """
 import argparse
 import json
@@ -55,6 +63,12 @@ def parse():
     p.add_argument("--dit-step-timeout", type=float, default=240.0, help="seconds after which the DiT training-step measurement is abandoned")
     p.add_argument("--no-dit-step", action="store_true",
                    help="skip the second measurement: the DiT-XL/2 256^2 training step of the thin host (DDP over RCCL when N > 1)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, run every other measurement and check of the bench (see the module docstring; the --no-* "
+                        "options trim it) and write the full record to bench_full.json; off by default")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed (out, dq, dk, dv, dW; rank 0) as DIR/<name>.npy "
+                        "in float32: token tensors larger than 2^21 values as a fixed, seeded sample of their (b, n) token rows")
     return p.parse_args()
 
 
@@ -70,6 +84,31 @@ def make_inputs(a, device, seed):
     side = int(round(a.M ** 0.5))
     W = block_distance_weights((side, side) if side * side == a.M else (a.M,), "linear").to(device)
     return q, k, v, W, do
+
+
+DUMP_VALUES_PER_TENSOR = 1 << 21   # 8 MiB of float32 per token tensor: the four of them and dW stay well under 64 MB
+
+
+def dump_outputs(d, outs):
+    """Write one step's results (out, dq, dk, dv: [B, N, H, D]; dW: [M, M]) to d/<name>.npy as float32.  A token tensor of more
+    than DUMP_VALUES_PER_TENSOR values is written as a sample of its B*N token rows, [rows, H, D]: the same rows for every tensor,
+    drawn from a fixed seed, so two runs with the same arguments write the same positions."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    rows = None
+    total = 0
+    for name, t in zip(("out", "dq", "dk", "dv", "dW"), outs):
+        t = t.detach()
+        if t.dim() == 4 and t.numel() > DUMP_VALUES_PER_TENSOR:
+            t = t.reshape(-1, t.shape[2], t.shape[3])
+            if rows is None:
+                n = max(1, DUMP_VALUES_PER_TENSOR // t[0].numel())
+                rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values.to(t.device)
+            t = t.index_select(0, rows)
+        arr = t.float().cpu().numpy()
+        total += arr.nbytes
+        assert total <= 64_000_000, f"--dump-outputs: {total} bytes"
+        np.save(os.path.join(d, name + ".npy"), arr)
 
 
 def cpu_baseline(a, budget_s=15.0, Bs=None):
@@ -336,9 +375,17 @@ def main():
 
     reducer = mdist.OverlappedGradAllReduce()
 
-    def step():
+    def fwd_bwd(keep=False):
+        """One forward + backward; keep=True returns what it computed: (out, dq, dk, dv, dW)."""
         out = mhla_amd.mhla_blockmix(q, k, v, W, eps=1e-6, summaries=a.summaries)
         out.backward(do)
+        return (out, q.grad, k.grad, v.grad, W.grad) if keep else None
+
+    eager_outs = [None]
+
+    def step():
+        eager_outs[0] = None   # the previous step's results go back to the allocator before this step allocates
+        eager_outs[0] = fwd_bwd(keep=True)
         # the one real exchange of a data-parallel step on this path: the mean all-reduce of dW, scheduled like DDP's
         # reducer (asynchronous, consumed at the next step / the closing synchronisation of the timed region)
         reducer.issue(W.grad)
@@ -348,6 +395,8 @@ def main():
     eager_step = step
     step_group, group = None, 1
     launch_mode = "eager (Python autograd)"
+    # the results of the last single step and of the last step of a `step_group` call (for --dump-outputs)
+    step_outs, group_outs = (lambda: eager_outs[0]), None
     if a.graph:
         # Whole-step capture: the forward + backward (both autograd calls, their workspace allocations, every launch) is
         # recorded once in a HIP graph and replayed -- the same work with no Python on the launch path, so the number does
@@ -362,27 +411,29 @@ def main():
             q.grad = k.grad = v.grad = W.grad = None
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                mhla_amd.mhla_blockmix(q, k, v, W, eps=1e-6, summaries=a.summaries).backward(do)
+                graph_outs = fwd_bwd(keep=True)
 
             def step():   # noqa: F811
                 graph.replay()
                 reducer.issue(W.grad)
 
             launch_mode = "hipGraph replay of the captured fwd+bwd step"
+            step_outs = lambda: graph_outs   # noqa: E731
             if world > 1:
                 # N ranks: every step is one replay followed by the all-reduce of its dW.  The gradient lives in the graph's static
                 # buffer, so two graphs alternate, each ending with "its" copy of dW / N: the collective of step k runs while
                 # graph (k + 1) % 2 computes, and a buffer is rewritten only after its previous collective was waited for
                 q.grad = k.grad = v.grad = W.grad = None
                 gbufs = [torch.empty_like(W, dtype=torch.float32) for _ in range(2)]
-                graphs = []
+                graphs, alt_outs = [], []
                 for gb_ in gbufs:
                     g_ = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g_):
-                        mhla_amd.mhla_blockmix(q, k, v, W, eps=1e-6, summaries=a.summaries).backward(do)
+                        o_ = fwd_bwd(keep=True)
                         gb_.copy_(W.grad).div_(world)
                         q.grad = k.grad = v.grad = W.grad = None
                     graphs.append(g_)
+                    alt_outs.append(o_[:4] + (gb_,))   # dW: the all-reduced mean, once the step's collective was waited for
                 phase = [0]
 
                 def step():   # noqa: F811
@@ -392,14 +443,15 @@ def main():
                     reducer.issue(gbufs[i], prescaled=True)
 
                 launch_mode = "hipGraph replay of the captured fwd+bwd step (+ dW / N), then its all-reduce; two graphs alternate"
+                step_outs = lambda: alt_outs[phase[0] ^ 1]   # noqa: E731
             if world == 1 and a.graph_steps > 1:
                 # one GPU: no per-step exchange, so several whole steps go into one graph (each replay costs ~15 us of device-side
                 # start-up whatever it holds); every captured step is the complete forward + backward on the same inputs
                 q.grad = k.grad = v.grad = W.grad = None
                 graph_g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph_g):
-                    for _ in range(a.graph_steps):
-                        mhla_amd.mhla_blockmix(q, k, v, W, eps=1e-6, summaries=a.summaries).backward(do)
+                    for i_ in range(a.graph_steps):
+                        group_outs = fwd_bwd(keep=i_ == a.graph_steps - 1)
                         q.grad = k.grad = v.grad = W.grad = None
                 # the first launch of an instantiated graph uploads it to the device (~0.5 ms, seen as +10 % on a 20-step run): one
                 # untimed replay right after the capture, besides the W warm-up steps (which use the one-step graph when W is
@@ -416,6 +468,7 @@ def main():
                 print(f"[bench] graph capture failed ({type(e).__name__}: {e}); eager launches", file=sys.stderr)
             q.grad = k.grad = v.grad = W.grad = None
             step, step_group, group = eager_step, None, 1
+            step_outs, group_outs = (lambda: eager_outs[0]), None
 
     def sync_all():
         reducer.wait()
@@ -425,6 +478,43 @@ def main():
     ms_per_step = el / a.steps * 1e3
     tokens_per_step = a.B * a.N * world
     value = tokens_per_step / (el / a.steps)
+    if a.dump_outputs and rank == 0:
+        # the last timed step was a `step_group` call when K is a multiple of the group, else a single step
+        dump_outputs(a.dump_outputs, group_outs if step_group is not None and group > 1 and a.steps % group == 0 else step_outs())
+
+    esz = {"bf16": 2, "f16": 2, "f32": 4}[a.dtype]
+    nde = a.B * a.H * a.N * a.D * esz                         # one token tensor of this rank's batch
+    alg_bytes = 12 * nde                                      # SURVEY.md 8(d): fwd 4 NDe + bwd 8 NDe per (b, h)
+    # the roofline figure of the line comes from the ONE timed number, ms_per_step (wall clock of the timed region, launch
+    # overheads included); with --full the GPU-time bracket of the second pass is listed beside it
+    achieved = alg_bytes / (ms_per_step * 1e-3) / 1e9
+    res = None
+    if rank == 0:
+        res = {
+            "metric": "MHLA fwd+bwd tokens/sec at (B,N,H,D)",
+            "value": value, "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": a.dtype, "data": "synthetic",
+            "config": {"workload": f"block-mix MHLA op fwd+bwd, per GPU B={a.B} N={a.N} H={a.H} D={a.D} "
+                                   f"M={a.M} S={a.N // a.M} {a.dtype} ({_config_name(a)})",
+                       "global_batch": a.B * world, "parallelism": f"dp{world} (batch shards, dW all-reduce only)",
+                       "launch": launch_mode,
+                       "arithmetic": {"tf32": "library default: bf16 hi + lo operands, fp32 accumulation, block summaries stored as fp16 payload x a power-of-two "
+                                              "multiplier per block row (11 significand bits, 2 bytes) = the precision the reference's matmul / 1x1 conv run at "
+                                              "(mhla_dit/mhla/mhla.py:262-263 under allow_tf32, mhla_dit/train.py:12-13); within 1e-3 of the fp32 result (observed 3e-4)",
+                                      "split": "block summaries as 24-bit floats (>= 16 significand bits; opt-in MHLA_FLAG_FP32_GRADE_SUMMARIES, round 5's default)",
+                                      "bf16": "REDUCED PRECISION (--summaries bf16, opt-in MHLA_FLAG_BF16_SUMMARIES): single-bf16 block summaries"}[a.summaries if a.dtype != "f32" else "split"],
+                       "autograd_nodes": "C++ (libmhla_torch.so)" if mhla_amd.ops._native_nodes() else "Python (ops.py)",
+                       **({"shared_gpu_harness": f"{world} ranks on {torch.cuda.device_count()} GPU(s), gloo: harness test, "
+                                                  "not a scaling measurement"} if shared else {})},
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS if achieved else None, "algorithmic_bytes_per_step": alg_bytes},
+        }
+    if not a.full:
+        if rank == 0:
+            print(compact_line(res), flush=True)
+        _close(world)
+        return
 
     # ---- GPU time of the whole step: HIP events on the launch stream around K more steps (the library's side-stream work
     # is joined back into this stream before each backward returns, so the bracket covers it) ----
@@ -452,9 +542,6 @@ def main():
         kernels[name] = {"launches_per_step": int(cnt) / a.steps, "avg_us": float(tot) / int(cnt) * 1e3,
                          "us_per_step": float(tot) / a.steps * 1e3}
     gpu_us = sum(kv["us_per_step"] for kv in kernels.values())
-    esz = {"bf16": 2, "f16": 2, "f32": 4}[a.dtype]
-    nde = a.B * a.H * a.N * a.D * esz                         # one token tensor of this rank's batch
-    alg_bytes = 12 * nde                                      # SURVEY.md 8(d): fwd 4 NDe + bwd 8 NDe per (b, h)
     # share of the algorithmic token traffic each kernel is responsible for: the dominant kernel's own
     # roofline fraction is its share / its duration
     share = {"k_t16_bwd": 7, "k_t16_bwd_dkv": 4, "k_t16_bwd_dq": 3, "k_t16_out": 2,
@@ -496,32 +583,11 @@ def main():
     dit_step = None
     run_dit = not a.no_dit_step and _config_name(a) == "BASELINE.json configs[1]" and not shared
     alg_flops = a.B * a.H * (12 * a.N * a.D * a.D + 6 * a.M * a.M * a.D * a.D)
-    # the roofline figure of the line comes from the ONE timed number, ms_per_step (wall clock of the timed region, launch
-    # overheads included); the GPU-time bracket of the second pass is listed beside it
-    achieved = alg_bytes / (ms_per_step * 1e-3) / 1e9
     achieved_gpu = alg_bytes / (step_gpu_us * 1e-6) / 1e9 if step_gpu_us else None
 
     if rank == 0:
-        res = {
-            "metric": "MHLA fwd+bwd tokens/sec at (B,N,H,D)",
-            "value": value, "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": a.dtype, "data": "synthetic",
-            "config": {"workload": f"block-mix MHLA op fwd+bwd, per GPU B={a.B} N={a.N} H={a.H} D={a.D} "
-                                   f"M={a.M} S={a.N // a.M} {a.dtype} ({_config_name(a)})",
-                       "global_batch": a.B * world, "parallelism": f"dp{world} (batch shards, dW all-reduce only)",
-                       "launch": launch_mode,
-                       "arithmetic": {"tf32": "library default: bf16 hi + lo operands, fp32 accumulation, block summaries stored as fp16 payload x a power-of-two "
-                                              "multiplier per block row (11 significand bits, 2 bytes) = the precision the reference's matmul / 1x1 conv run at "
-                                              "(mhla_dit/mhla/mhla.py:262-263 under allow_tf32, mhla_dit/train.py:12-13); within 1e-3 of the fp32 result (observed 3e-4)",
-                                      "split": "block summaries as 24-bit floats (>= 16 significand bits; opt-in MHLA_FLAG_FP32_GRADE_SUMMARIES, round 5's default)",
-                                      "bf16": "REDUCED PRECISION (--summaries bf16, opt-in MHLA_FLAG_BF16_SUMMARIES): single-bf16 block summaries"}[a.summaries if a.dtype != "f32" else "split"],
-                       "autograd_nodes": "C++ (libmhla_torch.so)" if mhla_amd.ops._native_nodes() else "Python (ops.py)",
-                       **({"shared_gpu_harness": f"{world} ranks on {torch.cuda.device_count()} GPU(s), gloo: harness test, "
-                                                  "not a scaling measurement"} if shared else {})},
-            "roofline": {
-                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS if achieved else None, "traffic": traffic,
+        res["roofline"].update({
+                "traffic": traffic,
                 "traffic_over_algorithmic": traffic / alg_bytes if traffic else None,
                 "frac_from_gpu_events": achieved_gpu / HBM_PEAK_GBS if achieved_gpu else None,
                 "mfma_busy_frac_pmc": mfma_busy,
@@ -539,8 +605,7 @@ def main():
                     "frac": (share.get(dom, 0) * nde / (kernels[dom]["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS) if share.get(dom) else None},
                 "kernels": kernels,
                 "mfma_frac_of_bf16_peak": alg_flops / (step_gpu_us * 1e-6) / 1e12 / MFMA_BF16_PEAK_TFLOPS if step_gpu_us else None,
-            },
-        }
+        })
         if world == 1 and a.summaries == "tf32" and a.dtype == "bf16" and not a.no_extra_configs:
             # the opt-in reduced-precision form of the same step (single-bf16 block summaries: rounds 1-4's arithmetic and kernels),
             # for comparison only -- `value` above is the number of record
@@ -603,8 +668,6 @@ def main():
                         "target": ">= 10x the CPU-eager reference on DiT-XL/2 256^2 tokens at 1 GPU"}
             except Exception as e:   # noqa: BLE001
                 res["extra_configs"] = {"error": f"{type(e).__name__}: {e}"}
-    else:
-        res = None
     if run_dit:
         # Every rank takes part (DDP collectives).  The operator line must survive whatever happens here: a watchdog on every
         # rank prints the line without this measurement (rank 0) and leaves the process if the step has not finished in time.
@@ -656,6 +719,10 @@ def main():
     if rank == 0:
         res["targets"] = targets_block(res, world)
         emit(res)
+    _close(world)
+
+
+def _close(world):
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

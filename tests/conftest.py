@@ -16,10 +16,16 @@ def pytest_configure(config):
 
 
 def load_golden(name):
+    """tests/golden/<name>.npz and, for a fixture too large for one committed file, its parts <name>.part1.npz, .part2.npz, ..."""
     import torch
 
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))
-    return {k: (z[k] if k == "meta" else torch.from_numpy(z[k])) for k in z.files}
+    out, i, path = {}, 0, os.path.join(GOLDEN, name + ".npz")
+    while i == 0 or os.path.exists(path):
+        z = np.load(path)
+        out.update({k: (z[k] if k == "meta" else torch.from_numpy(z[k])) for k in z.files})
+        i += 1
+        path = os.path.join(GOLDEN, f"{name}.part{i}.npz")
+    return out
 
 
 def rel_err(a, b):

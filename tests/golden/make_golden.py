@@ -37,10 +37,34 @@ def np32(t):
     return t.detach().to(torch.float32).cpu().numpy().copy()
 
 
+PART_BYTES = 960 << 10   # a committed file stays under 1 MiB: a larger fixture continues in <name>.part1.npz, .part2.npz, ...
+
+
+def _npz_bytes(**arrs):
+    import io
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrs)
+    return buf.getbuffer().nbytes
+
+
+def split_parts(arrs):
+    """The arrays in their order, cut into consecutive groups whose compressed .npz stays under PART_BYTES
+    (conftest.load_golden joins them back in this order)."""
+    parts, cur = [], {}
+    for k, a in arrs.items():
+        if cur and _npz_bytes(**cur, **{k: a}) > PART_BYTES:
+            parts.append(cur)
+            cur = {}
+        cur[k] = a
+    parts.append(cur)
+    return parts
+
+
 def save(name, **arrs):
-    path = os.path.join(OUT, name + ".npz")
-    np.savez_compressed(path, **arrs)
-    print(f"wrote {path}: {os.path.getsize(path) / 1024:.1f} KiB, keys={sorted(arrs)}")
+    for i, part in enumerate(split_parts(arrs)):
+        path = os.path.join(OUT, name + (f".part{i}" if i else "") + ".npz")
+        np.savez_compressed(path, **part)
+        print(f"wrote {path}: {os.path.getsize(path) / 1024:.1f} KiB, keys={sorted(part)}")
 
 
 # ---------------------------------------------------------------------------

@@ -65,7 +65,7 @@ def test_bench_two_rank_launch_path_in_shared_gpu_mode():
     on 127.0.0.1 (gloo: two ranks share the device), run the two-alternating-graphs launch mode with the asynchronous dW
     all-reduce and rank 0 prints ONE line with n_gpus = 2 -- the code the driver's scaling run executes with RCCL."""
     env = dict(os.environ, MASTER_PORT="29611")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full",
                         "--no-dit-step", "--no-extra-configs", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -85,7 +85,7 @@ def test_bench_eight_rank_launch_path_in_shared_gpu_mode():
     alternating-graphs launch mode with the asynchronous dW all-reduce, ONE line from rank 0 with n_gpus = 8 and the one-line
     contract's fields.  A harness test (8-GPU readiness on paper), not a scaling measurement."""
     env = dict(os.environ, MASTER_PORT="29631")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--full",
                         "--no-dit-step", "--no-extra-configs", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -369,6 +369,32 @@ def test_bench_line_is_small_strict_json():
     assert got["roofline"]["traffic"] is None and got["value"] == pytest.approx(full["value"], rel=1e-5)
 
 
+def test_bench_dump_outputs_is_a_fixed_float32_sample(tmp_path):
+    """`bench.py --dump-outputs DIR`: out / dq / dk / dv / dW as float32 .npy, under 64 MB in all.  A C2-sized token tensor is written
+    as 2048 of its B*N token rows, drawn from a fixed seed (the same rows for every tensor and every run); small tensors whole."""
+    import numpy as np
+    import bench
+    B, N, H, D, M = 8, 4096, 16, 64, 64
+    x = torch.randn(B, N, H, D, generator=torch.Generator().manual_seed(1)).bfloat16()
+    W = torch.randn(M, M, generator=torch.Generator().manual_seed(2))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), (x, 2 * x, -x, x, W))
+    names = ("out", "dq", "dk", "dv", "dW")
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert all(got[n].dtype == np.float32 for n in names)
+    assert sum(got[n].nbytes for n in names) <= 64_000_000
+    rows = torch.randperm(B * N, generator=torch.Generator().manual_seed(0))[:2048].sort().values
+    assert got["out"].shape == (2048, H, D)
+    assert np.array_equal(got["out"], x.reshape(-1, H, D)[rows].float().numpy())
+    assert np.array_equal(got["dq"], 2 * got["out"]) and np.array_equal(got["dk"], -got["out"])
+    assert np.array_equal(got["dW"], W.numpy())
+    for n in names:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))
+    small = torch.randn(2, 64, 4, 16)
+    bench.dump_outputs(str(tmp_path / "s"), (small, small, small, small, W))
+    assert np.array_equal(np.load(tmp_path / "s" / "out.npy"), small.numpy())
+
+
 def test_describe_dispatch_names_the_path_of_every_baseline_config():
     """mhla_describe_dispatch / mhla_causal_describe_dispatch (pure host logic): the kernel family and block-summary format a
     BASELINE.json configuration takes, asserted instead of inferred from timings."""

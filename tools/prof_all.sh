@@ -12,8 +12,8 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for s in ${SHAPES:-c2 c3 c3f c4b c5 c5b c2b c2c}; do
   if [ "$s" = c2 ]; then
-    rocprofv3 --kernel-trace --stats -d "$OUT/$s.trace" -o res -- python3 "$ROOT/bench.py" --steps 20 --warmup 3 --no-cpu-baseline --no-extra-configs --no-dit-step --no-step-benches > "$OUT/$s.trace.log" 2>&1
-    title="bench.py --steps 20 --warmup 3 (C2: B=8 N=4096 H=16 D=64 bf16 M=64)"
+    rocprofv3 --kernel-trace --stats -d "$OUT/$s.trace" -o res -- python3 "$ROOT/bench.py" --steps 20 --warmup 3 --full --no-cpu-baseline --no-extra-configs --no-dit-step --no-step-benches > "$OUT/$s.trace.log" 2>&1
+    title="bench.py --steps 20 --warmup 3 --full (C2: B=8 N=4096 H=16 D=64 bf16 M=64)"
     bash "$ROOT/tools/pmc_run.sh" "$OUT/$s.pmc" --no-dit-step --no-step-benches > /dev/null 2>&1
   else
     rocprofv3 --kernel-trace --stats -d "$OUT/$s.trace" -o res -- python3 "$ROOT/tools/run_shape.py" $s 10 > "$OUT/$s.trace.log" 2>&1
