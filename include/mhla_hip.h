@@ -309,6 +309,29 @@ int mhla_causal_bwd(mhla_view q, mhla_view k, mhla_view v, const float* mix, int
                     int B, int T, int H, int K, int V, int chunk,
                     float scale, int dtype, unsigned flags, void* stream);
 
+/* Decoding (generation): the state of a sequence and the single-token step.  Row t of the forward above depends on the
+ * tokens <= t only, so a step reproduces it from, per (b, h), in fp32 whatever the tensor dtype:
+ *   S   [B][H][cap_chunks][K][V]  K_j^T V_j of every finished chunk j (mix[i][j] differs per row i: all are kept --
+ *                                 4 K V bytes per chunk and head, 128 KB at K = 128, V = 256)
+ *   P   [B][H][K][V]              the prefix mix sum_{j<i} mix[i][j] S[j] of the open chunk i
+ *   Cur [B][H][K][V]              the open chunk's running K^T V
+ * all dense and 16-byte aligned; an empty state (no token seen) is P = Cur = 0.
+ * mhla_causal_state_init: the state after the T tokens of k, v ([B,T,H,K], [B,T,H,V]); needs ceil(T / chunk) <= cap_chunks and,
+ * unless the state is then full, ldmix > T / chunk.  Rows of S beyond the finished chunks are neither read nor written.
+ * mhla_causal_step: one token (q, k: [B,1,H,K]; v, out, y, gate: [B,1,H,V]) at position `pos` = tokens seen so far, with
+ * i = pos / chunk:  Cur += k (x) v;  out = scale q^T (P + mix[i][i] Cur);  at pos % chunk == chunk - 1 the chunk closes:
+ * S[i] = Cur, Cur = 0, P = sum_{j<=i} mix[i+1][j] S[j] (P = 0 when i + 1 == cap_chunks: the state is full).  The caller
+ * advances pos.  `y` non-NULL: the epilogue of mhla_causal_normgate_fwd on this token (`gate` ptr NULL: no gate, `norm_w`
+ * NULL: no weight), and `out` may then be a NULL ptr.  MHLA_EINVAL when pos / chunk >= cap_chunks, when ldmix does not cover
+ * the row of mix the call reads, or when ws_bytes < mhla_causal_step_ws_bytes (pure host arithmetic).  K, V multiples of 4,
+ * chunk 64, B*H <= 65535.  No atomics: results repeat bit for bit. */
+size_t mhla_causal_step_ws_bytes(int B, int H, int K, int V, int dtype);
+int mhla_causal_state_init(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                           int B, int T, int H, int K, int V, int chunk, int dtype, void* stream);
+int mhla_causal_step(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                     float* Cur, int64_t pos, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y,
+                     void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype, void* stream);
+
 /* ---- prologue: q / k of the Wan host -------------------------------------- */
 
 /*

@@ -1,0 +1,125 @@
+// C ABI, causal operator: the decode state of a sequence and the single-token step (mhla_causal_state_init, mhla_causal_step;
+// kernels: causal_step.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
+#include "capi_common.hpp"
+#include "blockmix.hpp"
+#include "causal.hpp"
+#include "causal_step.hpp"
+
+using namespace mhla;
+using namespace mhla::capi;
+
+namespace {
+
+int cst_check(int B, int H, int K, int V, int chunk, int dtype) {
+    if (B <= 0 || H <= 0 || K <= 0 || V <= 0) return fail(MHLA_EINVAL, "non-positive dimension B=%d H=%d K=%d V=%d", B, H, K, V);
+    if (chunk != 64) return fail(MHLA_ENOTSUP, "chunk=%d: only 64 is supported", chunk);
+    if ((K | V) & 3) return fail(MHLA_EINVAL, "K=%d and V=%d must be multiples of 4", K, V);
+    if (dtype < 0 || dtype > 2) return fail(MHLA_EINVAL, "unknown dtype %d", dtype);
+    if ((size_t)B * H > 65535) return fail(MHLA_ENOTSUP, "B*H=%zu exceeds grid limit 65535", (size_t)B * H);
+    return MHLA_OK;
+}
+int cst_check_state(const float* S, int cap, const float* P, const float* Cur) {
+    if (cap <= 0) return fail(MHLA_EINVAL, "cap_chunks=%d must be positive", cap);
+    if (!S || !P || !Cur) return fail(MHLA_EINVAL, "state: S, P or Cur null");
+    if (((uintptr_t)S | (uintptr_t)P | (uintptr_t)Cur) % 16) return fail(MHLA_EINVAL, "state: S, P and Cur must be 16-byte aligned");
+    return MHLA_OK;
+}
+// K rows per workgroup of k_cs_step (a multiple of 16): the whole of K where (b, h) x V tiles already give every CU four
+// workgroups, otherwise halved down to 16 rows -- B H = 4 at K = 128, V = 256 runs 128 workgroups instead of 16
+int cst_rows(size_t bh, int K, int V) {
+    const long vt = (V + CST_VT - 1) / CST_VT, groups = (K + CST_RG - 1) / CST_RG;
+    long g = groups;
+    while (g > 1 && (long)bh * vt * ((groups + g - 1) / g) < 1024) g = (g + 1) / 2;
+    return (int)g * CST_RG;
+}
+size_t cst_ws_bytes(int B, int H, int K, int V) {   // the most splits any plan uses: 16 rows each
+    return al4((size_t)B * H * ((K + CST_RG - 1) / CST_RG) * V) * 4;
+}
+
+int cst_roll(float* S, int cap, float* P, float* Cur, const float* mixrow, int nj, int commit, int BH, long E, hipStream_t st) {
+    const CsRollArgs r{S, P, Cur, mixrow, E, cap, nj, commit};
+    return launch(k_cs_roll, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll", r);
+}
+
+template <typename T>
+int cst_xty(const mhla_view& k, const mhla_view& v, long tok0, long ntok, float* out, int stride_chunks, int B, int H, int K, int V,
+            hipStream_t st) {
+    StateArgs a{};
+    a.x = cv(k); a.y = cv(v);
+    a.x.ptr = (const T*)k.ptr + tok0 * k.sn;
+    a.y.ptr = (const T*)v.ptr + tok0 * v.sn;
+    a.out = out; a.H = H; a.M = stride_chunks; a.S = CS; a.D = 64; a.DX = K; a.DY = V; a.T = ntok; a.alpha = 1.f;
+    const int strips = ((K + 63) / 64) * ((V + 63) / 64);
+    return launch(k_bm_state<T, 4, 2>, dim3((unsigned)((ntok + CS - 1) / CS), B * H, strips), dim3(NTHREADS), state_smem_floats<4>() * 4, st,
+                  "k_bm_state<2>", a);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mhla_causal_step_ws_bytes(int B, int H, int K, int V, int dtype) {
+    (void)dtype;
+    if (B <= 0 || H <= 0 || K <= 0 || V <= 0) return 0;
+    return cst_ws_bytes(B, H, K, V);
+}
+
+int mhla_causal_state_init(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                           int B, int T, int H, int K, int V, int chunk, int dtype, void* stream) {
+    RC(cst_check(B, H, K, V, chunk, dtype));
+    if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive (an empty state is all zeros)", T);
+    CHECK_VIEW(k); CHECK_VIEW(v);
+    RC(cst_check_state(S, cap_chunks, P, Cur));
+    const int nfull = T / chunk, tail = T - nfull * chunk;
+    if (nfull + (tail ? 1 : 0) > cap_chunks) return fail(MHLA_EINVAL, "T=%d tokens need %d chunks, the state holds %d", T, nfull + (tail ? 1 : 0), cap_chunks);
+    // the open chunk i = nfull reads mix[i][0 .. i]; a state that is full (nfull == cap_chunks) has no open chunk
+    const bool open = nfull < cap_chunks;
+    if (open && (!mix || ldmix < nfull + 1)) return fail(MHLA_EINVAL, "mix null or ldmix=%d < %d (row %d of mix is read)", ldmix, nfull + 1, nfull);
+    hipStream_t st = (hipStream_t)stream;
+    const long E = (long)K * V;
+    DISPATCH_T(dtype, {
+        if (nfull) RC(cst_xty<ET>(k, v, 0, (long)nfull * chunk, S, cap_chunks, B, H, K, V, st));
+        if (tail)  RC(cst_xty<ET>(k, v, (long)nfull * chunk, tail, Cur, 1, B, H, K, V, st));
+    });
+    if (!tail) {
+        hipError_t e = hipMemsetAsync(Cur, 0, (size_t)B * H * E * 4, st);
+        if (e != hipSuccess) return fail(MHLA_ELAUNCH, "hipMemsetAsync(Cur): %s", hipGetErrorString(e));
+    }
+    return cst_roll(S, cap_chunks, P, Cur, open ? mix + (long)nfull * ldmix : nullptr, nfull, 0, B * H, E, st);
+}
+
+int mhla_causal_step(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                     int64_t pos, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws,
+                     size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check(B, H, K, V, chunk, dtype));
+    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(v);
+    if (!out.ptr && !y.ptr) return fail(MHLA_EINVAL, "out and y both null");
+    if (out.ptr) CHECK_VIEW(out);
+    if (y.ptr) CHECK_VIEW(y);
+    if (gate.ptr) CHECK_VIEW(gate);
+    if ((gate.ptr || norm_w) && !y.ptr) return fail(MHLA_EINVAL, "gate / norm_w given without y");
+    RC(cst_check_state(S, cap_chunks, P, Cur));
+    if (pos < 0) return fail(MHLA_EINVAL, "pos=%lld is negative", (long long)pos);
+    const int64_t i = pos / chunk;
+    const int r = (int)(pos - i * chunk);
+    if (i >= cap_chunks) return fail(MHLA_EINVAL, "pos=%lld is in chunk %lld, the state holds %d", (long long)pos, (long long)i, cap_chunks);
+    const bool roll = r == chunk - 1, next = roll && i + 1 < cap_chunks;
+    if (!mix || ldmix < i + 1 + (next ? 1 : 0))
+        return fail(MHLA_EINVAL, "mix null or ldmix=%d < %lld (row %lld of mix is read)", ldmix, (long long)(i + 1 + (next ? 1 : 0)), (long long)(i + (next ? 1 : 0)));
+    const size_t need = cst_ws_bytes(B, H, K, V);
+    if (!ws || ws_bytes < need) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+    if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int BH = B * H, kr = cst_rows((size_t)BH, K, V), nsplit = (K + kr - 1) / kr;
+    DISPATCH_T(dtype, {
+        const CsStepArgs s{cv(q), cv(k), cv(v), mix + i * ldmix + i, P, Cur, (float*)ws, H, K, V, kr, nsplit};
+        RC(launch(k_cs_step<ET>, dim3((V + CST_VT - 1) / CST_VT, nsplit, BH), dim3(CST_THREADS), 0, st, "k_cs_step", s));
+        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, nsplit};
+        RC(launch(k_cs_step_finish<ET>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
+    });
+    if (roll) RC(cst_roll(S, cap_chunks, P, Cur, next ? mix + (i + 1) * ldmix : nullptr, (int)i + 1, 1, BH, (long)K * V, st));
+    return MHLA_OK;
+}
+
+}  // extern "C"

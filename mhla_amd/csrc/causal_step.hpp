@@ -1,0 +1,224 @@
+// Causal chunk-mixing MHLA, token-by-token decoding (generation): the decode state of a sequence and the kernels of one step.
+//
+// Row t of the chunk operator (causal.hpp: naive_chunk_simple_mhla_fixed) depends on the tokens <= t only, so a step that
+// reproduces row t needs, per (batch, head), in fp32:
+//   S[j]  [K][V]  K_j^T V_j of every FINISHED chunk j  (mix[i][j] differs for every row i: no S[j] can be folded away)
+//   P     [K][V]  the prefix mix of the open chunk i:  sum_{j<i} mix[i][j] S[j]
+//   Cur   [K][V]  the open chunk's running K^T V
+// With pos tokens seen, i = pos / 64, r = pos % 64, the step on the new token's (q, k, v) is
+//   Cur += k (x) v ;  o = scale q^T (P + mix[i][i] Cur) ;  r == 63: S[i] = Cur, Cur = 0, P = sum_{j<=i} mix[i+1][j] S[j].
+//   k_cs_step        : the rank-1 update and the mat-vec, tiled over V (64 columns) and split over K (16 rows x `kr / 16` per
+//                      workgroup) so that B H = 4 still fills the machine; per-split partial sums of o -> fp32 workspace
+//   k_cs_step_finish : partials summed in split order, scale, one rounding; optional RMSNorm x swish gate over the head's V channels
+//   k_cs_roll        : the chunk boundary (and the prefix mix of a prefilled state)
+// Memory-bound (P and Cur read, Cur written: 12 K V bytes per (b, h) and token); plain fp32 FMA, no MFMA, no atomics: every
+// sum has a fixed order, so results repeat bit for bit.  The state is fp32 whatever the tensor dtype: Cur takes up to 64
+// rank-1 updates and P sums up to L chunks -- a 16-bit state would round at every token.
+#pragma once
+#include "common.hpp"
+
+namespace mhla {
+
+constexpr int CST_THREADS = 256;
+constexpr int CST_VT = 64;        // V columns per workgroup: 16 lanes x 4
+constexpr int CST_RG = 16;        // row groups per workgroup: thread (rg, c4) walks rows rg, rg + 16, ...
+
+struct CsStepArgs {
+    View q, k, v;          // [B][1][H][K / V]
+    const float* mix;      // &mix[i][i]
+    float* P;              // [bh][K][V]
+    float* Cur;            // [bh][K][V]
+    float* part;           // [bh][nsplit][V]
+    int H, K, V, kr, nsplit;
+};
+
+template <typename T> __device__ __forceinline__ float cst_ld1(const T* p);
+template <> __device__ __forceinline__ float cst_ld1<float>(const float* p) { return *p; }
+template <> __device__ __forceinline__ float cst_ld1<bf16_t>(const bf16_t* p) { return bf16_to_f32(p->v); }
+template <> __device__ __forceinline__ float cst_ld1<f16_t>(const f16_t* p) { return (float)p->v; }
+template <typename T> __device__ __forceinline__ void cst_st1(T* p, float x);
+template <> __device__ __forceinline__ void cst_st1<float>(float* p, float x) { *p = x; }
+template <> __device__ __forceinline__ void cst_st1<bf16_t>(bf16_t* p, float x) { p->v = cvt_bf16(x); }
+template <> __device__ __forceinline__ void cst_st1<f16_t>(f16_t* p, float x) { p->v = (_Float16)x; }
+
+// grid (ceil(V / 64), nsplit, B H)
+template <typename T>
+__global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
+    __shared__ __attribute__((aligned(16))) float red[CST_RG][CST_VT];
+    const int tid = threadIdx.x, c4 = (tid & 15) * 4, rg = tid >> 4;
+    const int bh = blockIdx.z, b = bh / a.H, h = bh - b * a.H;
+    const int col = blockIdx.x * CST_VT + c4;
+    const int k0 = blockIdx.y * a.kr, k1 = min(a.K, k0 + a.kr);
+    const bool live = col < a.V;   // (V % 4 == 0: a thread's four columns are inside or outside together)
+    const T* qb = (const T*)a.q.ptr + b * a.q.sb + h * a.q.sh;
+    const T* kb = (const T*)a.k.ptr + b * a.k.sb + h * a.k.sh;
+    const T* vb = (const T*)a.v.ptr + b * a.v.sb + h * a.v.sh;
+    const float mii = *a.mix;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (live) {
+        const f32x4 vv = Io<T>::ld4(vb + col);
+        const long base = (long)bh * a.K * a.V + col;
+        constexpr int U = 4;   // rows in flight per thread: 2 U 16-byte loads
+        for (int r0 = k0 + rg; r0 < k1; r0 += CST_RG * U) {
+            f32x4 p[U], c[U];
+            float qv[U], kv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int r = r0 + u * CST_RG;
+                if (r < k1) {
+                    p[u] = gld<f32x4>(a.P + base + (long)r * a.V);
+                    c[u] = gld<f32x4>(a.Cur + base + (long)r * a.V);
+                    qv[u] = cst_ld1(qb + r);
+                    kv[u] = cst_ld1(kb + r);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int r = r0 + u * CST_RG;
+                if (r < k1) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        c[u][t] = fmaf(kv[u], vv[t], c[u][t]);
+                        acc[t] = fmaf(qv[u], fmaf(mii, c[u][t], p[u][t]), acc[t]);
+                    }
+                    gst<f32x4>(a.Cur + base + (long)r * a.V, c[u]);
+                }
+            }
+        }
+    }
+    *reinterpret_cast<f32x4*>(&red[rg][c4]) = acc;
+    __syncthreads();
+    if (tid < CST_VT) {
+        const int cc = blockIdx.x * CST_VT + tid;
+        if (cc < a.V) {
+            float s = 0.f;
+#pragma unroll
+            for (int g = 0; g < CST_RG; ++g) s += red[g][tid];
+            a.part[((long)bh * a.nsplit + blockIdx.y) * a.V + cc] = s;
+        }
+    }
+}
+
+struct CsFinishArgs {
+    const float* part;     // [bh][nsplit][V]
+    MView out, y;          // [B][1][H][V]; either ptr may be null
+    View gate;             // ptr null: no gate
+    const float* nw;       // [V] or null
+    float neps, scale;
+    int H, V, nsplit;
+};
+
+// grid (B H): o = scale * (partials in split order); y = o rsqrt(mean(o^2 over V) + neps) nw g sigmoid(g), from the fp32 o
+template <typename T>
+__global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishArgs a) {
+    __shared__ float red[CST_THREADS / 64];
+    const int tid = threadIdx.x, bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
+    const float* pb = a.part + (long)bh * a.nsplit * a.V;
+    T* ob = a.out.ptr ? (T*)a.out.ptr + b * a.out.sb + h * a.out.sh : nullptr;
+    auto o_at = [&](int c) {   // one accumulator, split order; the loads of a batch of eight issued together
+        float s = 0.f;
+        int j = 0;
+        for (; j + 8 <= a.nsplit; j += 8) {
+            float t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) t[u] = pb[(long)(j + u) * a.V + c];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += t[u];
+        }
+        for (; j < a.nsplit; ++j) s += pb[(long)j * a.V + c];
+        return a.scale * s;
+    };
+    constexpr int NC = 4;   // columns a thread keeps in registers between the two passes (V <= 1024); beyond: summed again
+    float oreg[NC];
+    float ss = 0.f;
+#pragma unroll
+    for (int u = 0; u < NC; ++u) {
+        const int c = tid + u * CST_THREADS;
+        oreg[u] = c < a.V ? o_at(c) : 0.f;
+        ss = fmaf(oreg[u], oreg[u], ss);
+        if (ob && c < a.V) cst_st1(ob + c, oreg[u]);
+    }
+    for (int c = tid + NC * CST_THREADS; c < a.V; c += CST_THREADS) {
+        const float o = o_at(c);
+        ss = fmaf(o, o, ss);
+        if (ob) cst_st1(ob + c, o);
+    }
+    if (!a.y.ptr) return;
+    ss = wave_sum(ss);
+    if ((tid & 63) == 0) red[tid >> 6] = ss;
+    __syncthreads();
+    const float rstd = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)a.V + a.neps);
+    T* yb = (T*)a.y.ptr + b * a.y.sb + h * a.y.sh;
+    const T* gb = a.gate.ptr ? (const T*)a.gate.ptr + b * a.gate.sb + h * a.gate.sh : nullptr;
+    auto put = [&](int c, float o) {
+        float yv = o * rstd;
+        if (a.nw) yv *= a.nw[c];
+        if (gb) {
+            const float g = cst_ld1(gb + c);
+            yv *= g / (1.f + __expf(-g));
+        }
+        cst_st1(yb + c, yv);
+    };
+#pragma unroll
+    for (int u = 0; u < NC; ++u) {
+        const int c = tid + u * CST_THREADS;
+        if (c < a.V) put(c, oreg[u]);
+    }
+    for (int c = tid + NC * CST_THREADS; c < a.V; c += CST_THREADS) put(c, o_at(c));   // (the same sum in the same order as above)
+}
+
+struct CsRollArgs {
+    float* S;              // [bh][cap][K][V]
+    float* P;              // [bh][K][V]
+    float* Cur;            // [bh][K][V]
+    const float* mixrow;   // row of mix the new P is formed with (nj entries read), or null: P = 0
+    long E;                // K V
+    int cap, nj, commit;   // commit: S[nj - 1] = Cur, Cur = 0 first (the boundary); else S[0 .. nj) as they are (prefill)
+};
+
+// grid (ceil(E / 4 / 64), B H), one wave per workgroup: P = sum_{j < nj} mixrow[j] S[j], ascending j
+__global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
+    const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
+    if (e >= a.E) return;   // (E % 4 == 0)
+    const long bh = blockIdx.y;
+    float* Sb = a.S + bh * a.cap * a.E + e;
+    const long pe = bh * a.E + e;
+    int n = a.nj;
+    f32x4 last = {0.f, 0.f, 0.f, 0.f};
+    if (a.commit) {
+        last = gld<f32x4>(a.Cur + pe);
+        gst<f32x4>(Sb + (long)(a.nj - 1) * a.E, last);
+        gst<f32x4>(a.Cur + pe, f32x4{0.f, 0.f, 0.f, 0.f});
+        n = a.nj - 1;
+    }
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (a.mixrow) {
+        constexpr int U = 8;
+        int j = 0;
+        for (; j + U <= n; j += U) {
+            f32x4 s[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) s[u] = gld<f32x4>(Sb + (long)(j + u) * a.E);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const float w = a.mixrow[j + u];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc[t] = fmaf(w, s[u][t], acc[t]);
+            }
+        }
+        for (; j < n; ++j) {
+            const f32x4 s = gld<f32x4>(Sb + (long)j * a.E);
+            const float w = a.mixrow[j];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] = fmaf(w, s[t], acc[t]);
+        }
+        if (a.commit) {
+            const float w = a.mixrow[n];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] = fmaf(w, last[t], acc[t]);
+        }
+    }
+    gst<f32x4>(a.P + pe, acc);
+}
+
+}  // namespace mhla

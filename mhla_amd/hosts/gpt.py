@@ -3,12 +3,14 @@
 reference's GLA-family language model (mhla_nlp/fla/models/gla/modeling_gla.py:83-100 builds the attention the same way).
 Plumbing for step-level numbers; stock PyTorch besides the attention layer.  The reference layer's mixing matrix has 32 chunks
 (layers/mhla.py:196-200: 2048 tokens at chunk 64); `max_seq_len` sizes it for longer sequences (8192 -> 128 chunks, the
-BASELINE.json configs[4] sequence length, through the drop-in layer's `max_chunks`)."""
+BASELINE.json configs[4] sequence length, through the drop-in layer's `max_chunks`).  With `exact_decoding=True` the layers
+keep a decode state in a cache (`forward(..., cache=DecodeCache())`: prefill on the first call, one exact step per later
+token) and `generate` decodes greedily on top of it."""
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..modules import MHLA
+from ..modules import MHLA, DecodeCache
 
 
 class RMSNorm(nn.Module):
@@ -35,40 +37,60 @@ class GatedMLP(nn.Module):
 
 
 class Block(nn.Module):
-    def __init__(self, dim, heads, expand_k, expand_v, layer_idx, max_chunks=32):
+    def __init__(self, dim, heads, expand_k, expand_v, layer_idx, max_chunks=32, exact_decoding=False):
         super().__init__()
         self.attn_norm = RMSNorm(dim)
         self.attn = MHLA(mode="chunk", hidden_size=dim, expand_k=expand_k, expand_v=expand_v, num_heads=heads,
-                         feature_map="relu", layer_idx=layer_idx, max_chunks=max_chunks)
+                         feature_map="relu", layer_idx=layer_idx, max_chunks=max_chunks, exact_decoding=exact_decoding)
         self.mlp_norm = RMSNorm(dim)
         self.mlp = GatedMLP(dim)
 
-    def forward(self, x):
-        x = x + self.attn(self.attn_norm(x))[0]
+    def forward(self, x, cache=None):
+        if cache is None:
+            x = x + self.attn(self.attn_norm(x))[0]
+        else:
+            x = x + self.attn(self.attn_norm(x), past_key_values=cache, use_cache=True)[0]
         return x + self.mlp(self.mlp_norm(x))
 
 
 class GPT_MHLA(nn.Module):
     def __init__(self, vocab_size=32000, hidden_size=1024, num_layers=24, num_heads=4, expand_k=0.5, expand_v=1.0,
-                 max_seq_len=2048):
+                 max_seq_len=2048, exact_decoding=False):
         super().__init__()
+        self.exact_decoding = bool(exact_decoding)
         self.embeddings = nn.Embedding(vocab_size, hidden_size)
         max_chunks = max(32, (max_seq_len + 63) // 64)     # 32 = the reference layer's matrix; 128 for seq_len 8192 (config 5)
-        self.layers = nn.ModuleList([Block(hidden_size, num_heads, expand_k, expand_v, i, max_chunks) for i in range(num_layers)])
+        self.layers = nn.ModuleList([Block(hidden_size, num_heads, expand_k, expand_v, i, max_chunks, exact_decoding) for i in range(num_layers)])
         self.norm = RMSNorm(hidden_size)
         self.lm_head = nn.Linear(hidden_size, vocab_size, bias=False)
         for m in self.modules():
             if isinstance(m, (nn.Linear, nn.Embedding)):
                 nn.init.normal_(m.weight, std=0.02)
 
-    def forward(self, input_ids, labels=None):
+    def forward(self, input_ids, labels=None, cache=None):
+        """`cache` (a `DecodeCache`, model built with `exact_decoding=True`): `input_ids` are the tokens AFTER the ones the cache
+        has seen -- the whole prompt on an empty cache, then one token per call."""
+        if cache is not None and not self.exact_decoding:
+            raise ValueError("GPT_MHLA.forward(cache=...) needs a model built with exact_decoding=True")
         x = self.embeddings(input_ids)
         for blk in self.layers:
-            x = blk(x)
+            x = blk(x, cache)
         logits = self.lm_head(self.norm(x))
         if labels is None:
             return logits
         return F.cross_entropy(logits[:, :-1].reshape(-1, logits.shape[-1]).float(), labels[:, 1:].reshape(-1))
+
+    @torch.no_grad()
+    def generate(self, input_ids, max_new_tokens):
+        """Greedy decoding: one prefill over `input_ids` [B, T], then one cached step per new token.  Returns the
+        `max_new_tokens` new ids [B, max_new_tokens]; T + max_new_tokens must fit the mixing matrix (`max_seq_len`)."""
+        cache = DecodeCache()
+        new = []
+        ids = input_ids
+        for _ in range(int(max_new_tokens)):
+            ids = self.forward(ids, cache=cache)[:, -1:].argmax(-1)
+            new.append(ids)
+        return torch.cat(new, dim=1) if new else input_ids[:, :0]
 
 
 def GPT_configs():

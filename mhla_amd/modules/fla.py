@@ -8,7 +8,8 @@ kernels; rotary is plain tensor math (NeoX half rotation, rotary.py:20-32) -- no
 
 Deviations, all documented in SURVEY.md: sequences of <= 64 tokens use the single-chunk case of the
 chunk operator (the reference's token-recurrent form equals it only on the first chunk and ignores
-its initial state).  `use_short_conv=True` (off in the shipped configuration; the reference's
+its initial state); `exact_decoding=True` (not in the reference) replaces that branch, under `use_cache`, by a prefill that
+keeps a `CausalState` and exact single-token steps.  `use_short_conv=True` (off in the shipped configuration; the reference's
 ShortConvolution is a sibling fla module outside the MHLA hot path) is served by a plain-PyTorch
 `ShortConvolution` with the reference's parameters and cache protocol (no HIP kernel: not on the path).
 """
@@ -19,7 +20,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops import featmap_rotary, mhla_causal, mhla_causal_normgate, naive_recurrent_mhla, rmsnorm_gate
+from ..ops import (CausalState, featmap_rotary, mhla_causal, mhla_causal_normgate, mhla_causal_state, mhla_causal_step,
+                   naive_recurrent_mhla, rmsnorm_gate)
 from ..weights import causal_mixing_init
 
 
@@ -146,6 +148,34 @@ class ShortConvolution(nn.Conv1d):
         return self.hidden_size * self.kernel_size[0]
 
 
+class DecodeCache:
+    """Minimal list-backed cache with the protocol the layer uses (`fla.models.utils.Cache` has the same one): `len(cache)`
+    layers hold a state, `cache[i]` is layer i's `{"recurrent_state", "conv_state"}`, `get_seq_length(i)` the tokens layer i
+    has seen, `update(...)` stores a layer's state and adds `offset` tokens to its count."""
+
+    def __init__(self):
+        self.states, self._seen = [], []
+
+    def __len__(self):
+        return len(self.states)
+
+    def __getitem__(self, layer_idx):
+        return self.states[layer_idx]
+
+    def get_seq_length(self, layer_idx=0):
+        layer_idx = layer_idx or 0
+        return self._seen[layer_idx] if layer_idx < len(self._seen) else 0
+
+    def update(self, recurrent_state=None, conv_state=None, layer_idx=0, offset=1, **kwargs):
+        layer_idx = layer_idx or 0
+        while len(self.states) <= layer_idx:
+            self.states.append(dict(recurrent_state=None, conv_state=None))
+            self._seen.append(0)
+        self.states[layer_idx] = dict(recurrent_state=recurrent_state, conv_state=conv_state)
+        self._seen[layer_idx] += int(offset)
+        return self.states[layer_idx]
+
+
 def _elu1(x):
     return F.elu(x) + 1
 
@@ -157,13 +187,21 @@ class MHLA(nn.Module):
                  use_output_gate: bool = True, gate_fn: str = "swish", elementwise_affine: Optional[bool] = True,
                  norm_eps: float = 1e-5, gate_logit_normalizer: int = 16, gate_low_rank_dim: int = 16,
                  clamp_min: Optional[float] = None, fuse_norm: bool = True, layer_idx: int = None, max_chunks: int = 32,
-                 summaries: str = "tf32"):
+                 summaries: str = "tf32", exact_decoding: bool = False):
         """`max_chunks` (not in the reference, default = its hard-coded 32): side of the mixing matrix, i.e. the longest
         sequence is 64 * max_chunks tokens -- 128 for the 8192-token configuration of BASELINE.json configs[4], which the
         reference layer itself cannot run (layers/mhla.py:196-200); the operator accepts any [n, n] matrix (naive.py:55).
         `summaries` (not in the reference): "tf32" (default) stores the operator's chunk summaries with 11 significand bits in 2
         bytes (the precision of the reference's TF32 matmuls), "split" with >= 16 bits in 4 bytes (bf16 hi + lo pairs, naive.py:39);
-        "bf16" opts into the reduced-precision variant (2-3e-3 of the output's maximum) -- see mhla_amd.mhla_causal."""
+        "bf16" opts into the reduced-precision variant (2-3e-3 of the output's maximum) -- see mhla_amd.mhla_causal.
+        `exact_decoding` (not in the reference, default off: nothing changes): with `use_cache=True` and a cache
+        (`past_key_values`, e.g. `DecodeCache`; `layer_idx` set), a call on an empty cache -- of any length -- is a prefill: the
+        chunk operator as otherwise, plus a `CausalState` (ops.py: 4 K V bytes per finished chunk and head, fp32) stored as the
+        cache's `recurrent_state`; a later call of one token runs `mhla_causal_step` (norm x gate fused when
+        `fuse_norm_and_gate`) and returns exactly the row the chunk operator over the whole sequence would.  A later call of
+        several tokens runs the step once per token: correct, not optimised.  All sequences of the batch share one length: a
+        padding `attention_mask` raises NotImplementedError (an all-ones mask is ignored).  Steps are inference only (call
+        under `torch.no_grad()`).  Adds no parameters."""
         super().__init__()
         self.mode = mode
         self.hidden_size = hidden_size
@@ -181,6 +219,7 @@ class MHLA(nn.Module):
         if summaries not in ("tf32", "split", "bf16"):
             raise ValueError(f"summaries={summaries!r}: 'tf32', 'split' or 'bf16'")
         self.summaries = summaries
+        self.exact_decoding = bool(exact_decoding)
         self.use_output_gate = use_output_gate
         assert mode in ["chunk", "fused_recurrent", "fused_chunk"], f"Not supported mode `{mode}`."
         assert self.key_dim % num_heads == 0, f"key dim must be divisible by num_heads of {num_heads}"
@@ -237,6 +276,15 @@ class MHLA(nn.Module):
         last_state = None
         if past_key_values is not None and self.layer_idx is not None and len(past_key_values) > self.layer_idx:
             last_state = past_key_values[self.layer_idx]                      # :249-251
+        exact = self.exact_decoding and bool(use_cache) and past_key_values is not None and hasattr(past_key_values, "update")
+        if exact:
+            if self.layer_idx is None:
+                raise ValueError("MHLA(exact_decoding=True): the cache is indexed by layer_idx, which is None")
+            if attention_mask is not None:
+                if not bool(attention_mask.all()):
+                    raise NotImplementedError("MHLA(exact_decoding=True): all sequences of a batch share one length; a padding "
+                                              "attention_mask is not supported with the decode state")
+                attention_mask = None
         indices = None
         cu_seqlens = kwargs.get("cu_seqlens", None)
         if attention_mask is not None:                                       # layers/mhla.py:253-256 (get_unpad_data)
@@ -297,7 +345,30 @@ class MHLA(nn.Module):
             q, k = self.rotary(q, k, seqlen_offset=seqlen_offset, max_seqlen=table_len, positions=positions)   # :311
         recurrent_state = last_state["recurrent_state"] if last_state is not None else None
         fused_epilogue = self.use_output_gate and self.fuse_norm_and_gate and q_len > 64
-        if fused_epilogue:
+        if exact and isinstance(recurrent_state, CausalState):
+            # decoding: one exact step per token on the state the prefill (or the steps before) left
+            g = gn = None
+            if self.fuse_norm_and_gate:
+                g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
+                gn = self.g_norm_swish_gate
+            fused_epilogue = gn is not None
+            o = torch.cat([mhla_causal_step(q[:, t:t + 1], k[:, t:t + 1], v[:, t:t + 1], self.mixing_matrix, recurrent_state,
+                                            gate=g[:, t:t + 1] if gn is not None else None,
+                                            norm_weight=gn.weight if gn is not None else None,
+                                            norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None)
+                           for t in range(T)], dim=1)
+            if fused_epilogue:
+                o = o.reshape(B, T, self.value_dim)
+        elif exact:
+            # prefill: the chunk operator for the output (any length: the single-chunk case for <= 64 tokens), and the decode state
+            if fused_epilogue:
+                g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
+                gn = self.g_norm_swish_gate
+                o = mhla_causal_normgate(q, k, v, self.mixing_matrix, g, gn.weight, gn.eps, summaries=self.summaries).reshape(B, T, self.value_dim)
+            else:
+                o = mhla_causal(q, k, v, self.mixing_matrix, summaries=self.summaries)
+            recurrent_state = mhla_causal_state(k, v, self.mixing_matrix)
+        elif fused_epilogue:
             # operator + per-head RMSNorm x swish gate (:330-337 + :351-355) as one node: the epilogue runs in the operator's
             # output kernel where the shape allows, otherwise as the separate HIP kernel (mhla_causal_normgate decides)
             g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)

@@ -1190,6 +1190,190 @@ def naive_recurrent_mhla(q, k, v, mixing_matrix, chunk_size: int = 64, scale: Op
 
 
 # ------------------------------------------------------------------------------------------
+# causal operator, decoding: prefill state + single-token step
+# ------------------------------------------------------------------------------------------
+class CausalState:
+    """Decode state of the causal operator, fp32 whatever the tensor dtype: `S [B, H, cap, K, V]` (K_j^T V_j of every finished
+    chunk), `P [B, H, K, V]` (prefix mix of the open chunk), `Cur [B, H, K, V]` (the open chunk's running K^T V), `seen` tokens
+    so far.  Every row of the mixing matrix weighs the finished chunks differently, so all of them are kept: 4 K V bytes per
+    chunk and head (128 KB at K = 128, V = 256) -- `nbytes` reports the total.  All sequences of the batch share `seen`."""
+
+    __slots__ = ("S", "P", "Cur", "seen", "chunk_size")
+
+    def __init__(self, S: torch.Tensor, P: torch.Tensor, Cur: torch.Tensor, seen: int = 0, chunk_size: int = 64):
+        self.S, self.P, self.Cur, self.seen, self.chunk_size = S, P, Cur, int(seen), int(chunk_size)
+
+    @classmethod
+    def empty(cls, B: int, H: int, K: int, V: int, capacity_chunks: int, device="cuda", chunk_size: int = 64) -> "CausalState":
+        if min(B, H, K, V, capacity_chunks) <= 0:
+            raise ValueError(f"CausalState.empty: non-positive size B={B} H={H} K={K} V={V} capacity_chunks={capacity_chunks}")
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
+        return cls(z(B, H, capacity_chunks, K, V), z(B, H, K, V), z(B, H, K, V), 0, chunk_size)
+
+    @property
+    def capacity_chunks(self) -> int:
+        return self.S.shape[2]
+
+    @property
+    def nbytes(self) -> int:
+        return 4 * (self.S.numel() + self.P.numel() + self.Cur.numel())
+
+    def clone(self) -> "CausalState":
+        return CausalState(self.S.clone(), self.P.clone(), self.Cur.clone(), self.seen, self.chunk_size)
+
+    def __repr__(self):
+        B, H, cap, K, V = self.S.shape
+        return f"CausalState(B={B}, H={H}, K={K}, V={V}, capacity_chunks={cap}, seen={self.seen}, device={self.S.device})"
+
+
+def _mix2d(mix: torch.Tensor) -> torch.Tensor:
+    return mix.detach().reshape(mix.shape[0], mix.shape[1]).to(torch.float32).contiguous()
+
+
+@functools.lru_cache(maxsize=64)
+def _step_ws_bytes(B, H, K, V, dt):
+    return _lib.load().mhla_causal_step_ws_bytes(B, H, K, V, dt)
+
+
+@_device_guard
+def _causal_state_init(k, v, mix, state: CausalState):
+    lib = _lib.load()
+    B, T, H, K = k.shape
+    k, v = _prep(k), _prep(v)
+    mixf = _mix2d(mix)
+    rc = lib.mhla_causal_state_init(_view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+                                    state.P.data_ptr(), state.Cur.data_ptr(), B, T, H, K, v.shape[-1], state.chunk_size,
+                                    _dtype_code(k), _stream())
+    _lib.check(rc, "mhla_causal_state_init")
+    state.seen = T
+
+
+def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, chunk_size: int = 64,
+                        scale: Optional[float] = None, *, summaries: str = "tf32", capacity_chunks: Optional[int] = None):
+    """`(o, state)`: `o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries)` and the `CausalState`
+    after these T tokens, from which `mhla_causal_step` continues one token at a time (T = 0: an empty state).  The state is
+    built from k, v in exact fp32 products, independently of `summaries`; no autograd passes through it.
+    capacity_chunks: chunks the state can hold (64 tokens each), default and at most the rows L of the mixing matrix."""
+    if q.dim() != 4 or v.dim() != 4:
+        raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
+    if int(chunk_size) != 64:
+        raise ValueError(f"mhla_causal_prefill: chunk_size={chunk_size}, the decode state supports 64 only")
+    o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries)
+    return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks)
+
+
+def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, *, capacity_chunks: Optional[int] = None) -> CausalState:
+    """The `CausalState` after the T tokens of k `[B, T, H, K]`, v `[B, T, H, V]` (the state half of `mhla_causal_prefill`;
+    chunk 64).  T = 0: an empty state."""
+    if k.dim() != 4 or v.dim() != 4:
+        raise ValueError("k: [B, T, H, K], v: [B, T, H, V]")
+    B, T, H, K = k.shape
+    V = v.shape[-1]
+    _check_like(k, "mhla_causal_state", v=(v, (B, T, H, V)))
+    L = mixing_matrix.shape[0]
+    cap = L if capacity_chunks is None else int(capacity_chunks)
+    if not 0 < cap <= L:
+        raise ValueError(f"capacity_chunks={cap} must be in 1 .. {L} (rows of mixing_matrix)")
+    if (T + 63) // 64 > cap:
+        raise IndexError(f"sequence of {T} tokens needs {(T + 63) // 64} chunks but the state holds only {cap}")
+    if mixing_matrix.device != k.device or mixing_matrix.dim() < 2 or mixing_matrix.shape[1] < cap:
+        raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)] with L >= {cap} on {k.device}")
+    _require_gpu(k, v, mixing_matrix)
+    nb = _MAX_GRID_BH // H
+    with torch.no_grad():
+        state = CausalState.empty(B, H, K, V, cap, k.device, 64)
+        for i in range(0, B if T else 0, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
+            part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], 0, 64)
+            _causal_state_init(k[i:i + nb].detach(), v[i:i + nb].detach(), mixing_matrix, part)
+        state.seen = T
+    return state
+
+
+@_device_guard
+def _causal_step(q, k, v, mixf, state, pos, scale, gate, wf, norm_eps, want_y):
+    lib = _lib.load()
+    B, _, H, K = q.shape
+    V = v.shape[-1]
+    dt = _dtype_code(q)
+    res = torch.empty((B, 1, H, V), dtype=q.dtype, device=q.device)
+    ws = _ws(_step_ws_bytes(B, H, K, V, dt), q.device)
+    rc = lib.mhla_causal_step(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+                              state.P.data_ptr(), state.Cur.data_ptr(), pos, NULL_VIEW if want_y else _view(res),
+                              _view(gate) if gate is not None else NULL_VIEW, wf.data_ptr() if wf is not None else None,
+                              float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K, V,
+                              state.chunk_size, float(scale), dt, _stream())
+    _lib.check(rc, "mhla_causal_step")
+    return res
+
+
+def _step_view_ok(t: torch.Tensor) -> bool:
+    # what the step kernels address in place: 4-element pieces (8 bytes for 16-bit types, 16 for fp32)
+    return t.stride(3) == 1 and all(s % 4 == 0 for s in t.stride()[:3]) and t.data_ptr() % (4 * t.element_size()) == 0
+
+
+def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
+                     scale: Optional[float] = None, gate: Optional[torch.Tensor] = None, norm_weight: Optional[torch.Tensor] = None,
+                     norm_eps: float = 1e-5, epilogue: Optional[bool] = None) -> torch.Tensor:
+    """One decoding step of the causal operator: q, k `[B, 1, H, K]`, v `[B, 1, H, V]` of the token at position `state.seen`;
+    returns row `state.seen` of `mhla_causal` over the whole sequence, `[B, 1, H, V]`, updates `state` in place and advances
+    `state.seen`.  Strided views (slices of a packed projection) are read in place.  With `gate` and / or `norm_weight` (or
+    `epilogue=True` for the bare norm) the result is `rmsnorm_gate(o, gate, norm_weight, norm_eps)` applied in the same
+    launch chain.  Inference only: nothing is recorded for autograd, and an input that requires grad while grad mode is on
+    raises.  The step that would open chunk L of an [L, L] matrix (or exceed the state's capacity) raises IndexError and
+    leaves the state untouched.  Cost per token: P and Cur read, Cur written (12 K V bytes per (b, h)); every 64th step also
+    closes the chunk and re-mixes the finished ones (4 K V bytes per finished chunk)."""
+    if not isinstance(state, CausalState):
+        raise TypeError(f"mhla_causal_step: state must be a CausalState, got {type(state).__name__}")
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("q, k: [B, 1, H, K], v: [B, 1, H, V]")
+    B, T, H, K = q.shape
+    V = v.shape[-1]
+    if T != 1:
+        raise ValueError(f"mhla_causal_step takes one token per call (T = 1), got T = {T}")
+    try:
+        _check_like(q, "mhla_causal_step", k=(k, q.shape), v=(v, (B, 1, H, V)), gate=(gate, (B, 1, H, V)))
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+    if q.dtype not in _DTYPES:
+        raise ValueError(f"mhla_causal_step: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
+    if tuple(state.S.shape) != (B, H, state.capacity_chunks, K, V) or tuple(state.P.shape) != (B, H, K, V) or tuple(state.Cur.shape) != (B, H, K, V):
+        raise ValueError(f"mhla_causal_step: state is {state!r}, the token has B={B} H={H} K={K} V={V}")
+    for name, t in (("state.S", state.S), ("state.P", state.P), ("state.Cur", state.Cur), ("mixing_matrix", mixing_matrix), ("norm_weight", norm_weight)):
+        if t is not None and t.device != q.device:
+            raise ValueError(f"mhla_causal_step: {name} is on {t.device}, expected {q.device}")
+    if norm_weight is not None and norm_weight.numel() != V:
+        raise ValueError(f"mhla_causal_step: norm_weight has {norm_weight.numel()} entries, expected V={V}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, gate)):
+        raise RuntimeError("mhla_causal_step is inference only: call it under torch.no_grad() (an input requires grad)")
+    _require_gpu(q, k, v, mixing_matrix)
+    L = mixing_matrix.shape[0]
+    if mixing_matrix.dim() < 2 or mixing_matrix.shape[1] < min(L, state.capacity_chunks):
+        raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
+    pos = state.seen
+    n = pos // state.chunk_size + 1
+    if n > L:
+        raise IndexError(f"sequence of {pos + 1} tokens needs {n} chunks but mixing_matrix has only {L} rows")
+    if n > state.capacity_chunks:
+        raise IndexError(f"sequence of {pos + 1} tokens needs {n} chunks but the state holds only {state.capacity_chunks}")
+    if scale is None:
+        scale = K ** -0.5
+    want_y = bool(epilogue) if epilogue is not None else (gate is not None or norm_weight is not None)
+    if not want_y and (gate is not None or norm_weight is not None):
+        raise ValueError("mhla_causal_step: gate / norm_weight given with epilogue=False")
+    with torch.no_grad():
+        q, k, v = (t if _step_view_ok(t) else t.contiguous() for t in (q, k, v))
+        if gate is not None and not _step_view_ok(gate):
+            gate = gate.contiguous()
+        mixf = _mix2d(mixing_matrix)
+        wf = norm_weight.detach().reshape(V).to(torch.float32).contiguous() if norm_weight is not None else None
+        if not (state.S.is_contiguous() and state.P.is_contiguous() and state.Cur.is_contiguous()):
+            raise ValueError("mhla_causal_step: state tensors must be contiguous")
+        res = _causal_step(q, k, v, mixf, state, pos, scale, gate, wf, norm_eps, want_y)
+    state.seen = pos + 1
+    return res
+
+
+# ------------------------------------------------------------------------------------------
 # per-head RMSNorm x swish gate
 # ------------------------------------------------------------------------------------------
 class _RmsNormGate(torch.autograd.Function):

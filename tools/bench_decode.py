@@ -1,0 +1,149 @@
+#!/usr/bin/env python
+"""Per-token latency of the causal operator's decoding step (mhla_causal_step) at the two C5 head shapes of bench_configs.py
+(H = 4, K = 128, V = 256 and H = 4, K = 256, V = 512; bf16 tokens, fp32 state, L = 128 chunks), B = 1 and 32, early (pos ~ 100)
+and late (pos ~ 8000) in the sequence.  Per configuration, alternating within one run and repeated `--reps` times:
+  * `--steps` (>= 200) ordinary steps at a fixed position (the state's `seen` is put back before every call, so every call is the
+    same step: no chunk boundary), HIP events around the batch, ending in a synchronise;
+  * the same number of BOUNDARY steps (pos % 64 == 63: the step plus k_cs_roll over the i + 1 finished chunks), separately;
+  * what the token costs without a decode state: `mhla_causal` forward over all pos + 1 tokens.
+Each JSON line carries the median and the min / max over the repetitions (us per token), the device time of each kernel from the
+library's per-launch event hook (the event-timed batch includes the Python host path of a call, which at B = 1 is the larger
+part), the bytes a step must move -- 3 B H K V 4 (P and Cur read, Cur written) plus the token rows -- and the resulting GB/s.
+
+`--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
+after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from bench_configs import kernel_times  # noqa: E402
+import mhla_amd  # noqa: E402
+from mhla_amd import causal_mixing_init  # noqa: E402
+
+DEV = "cuda"
+L = 128
+
+
+def batch_us(fn, iters, warm=10):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3
+
+
+def spread(xs):
+    return {"median": round(statistics.median(xs), 2), "min": round(min(xs), 2), "max": round(max(xs), 2)}
+
+
+def token(B, H, K, V, g):
+    mk = lambda D: torch.randn(B, 1, H, D, generator=g).to(torch.bfloat16).to(DEV)
+    return mk(K), mk(K), mk(V)
+
+
+def config(B, H, K, V, pos, steps, reps, parent_iters):
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    q, k, v = token(B, H, K, V, g)
+    i = pos // 64
+    state = mhla_amd.CausalState.empty(B, H, K, V, L, DEV)
+    state.S[:, :, :i + 1].normal_(0, 0.1)        # finished chunks the boundary step reads
+    state.P.normal_(0, 0.1)
+    T = pos + 1
+    qT, kT = (torch.randn(B, T, H, K, generator=g).to(torch.bfloat16).to(DEV) for _ in range(2))
+    vT = torch.randn(B, T, H, V, generator=g).to(torch.bfloat16).to(DEV)
+    roll_pos = i * 64 + 63
+
+    def step():
+        state.seen = pos
+        mhla_amd.mhla_causal_step(q, k, v, mix, state)
+
+    def roll():
+        state.seen = roll_pos
+        mhla_amd.mhla_causal_step(q, k, v, mix, state)
+
+    def parent():
+        mhla_amd.mhla_causal(qT, kT, vT, mix)
+
+    t_step, t_roll, t_parent = [], [], []
+    with torch.no_grad():
+        for _ in range(reps):
+            t_step.append(batch_us(step, steps))
+            t_roll.append(batch_us(roll, steps))
+            t_parent.append(batch_us(parent, parent_iters, warm=2))
+            state.Cur.zero_()                     # (the repeated step keeps adding the same k (x) v: keep it small)
+        ks = {n: round(us, 2) for n, us in kernel_times(step, iters=20).items()}
+        kr = {n: round(us, 2) for n, us in kernel_times(roll, iters=20).items()}
+    nbytes = 3 * B * H * K * V * 4 + B * H * (2 * K + 2 * V) * 2
+    dev_step = ks.get("k_cs_step", 0.0) + ks.get("k_cs_step_finish", 0.0)
+    rec = {"B": B, "H": H, "K": K, "V": V, "pos": pos, "chunk": i, "steps_per_batch": steps, "reps": reps,
+           "step_us": spread(t_step), "roll_step_us": spread(t_roll), "roll_pos": roll_pos,
+           "parent_fwd_us": spread(t_parent), "parent_tokens": T,
+           "step_kernels_us": ks, "roll_step_kernels_us": kr,
+           "step_bytes": nbytes, "step_GBps_wall": round(nbytes / (statistics.median(t_step) * 1e-6) / 1e9, 1),
+           "step_GBps_device": round(nbytes / (dev_step * 1e-6) / 1e9, 1) if dev_step else None,
+           "roll_bytes": (i + 1) * B * H * K * V * 4 + 3 * B * H * K * V * 4,
+           "state_MB": round(state.nbytes / 2 ** 20, 1)}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def roll_sweep(B, H, K, V, steps):
+    """How the boundary step grows with the number of finished chunks: k_cs_roll reads (i + 1) K V 4 bytes per (b, h)."""
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    q, k, v = token(B, H, K, V, g)
+    state = mhla_amd.CausalState.empty(B, H, K, V, L, DEV)
+    state.S.normal_(0, 0.1)
+    out = {}
+    with torch.no_grad():
+        for i in (0, 1, 7, 15, 31, 63, 95, 125):
+            def roll():
+                state.seen = i * 64 + 63
+                mhla_amd.mhla_causal_step(q, k, v, mix, state)
+            wall = batch_us(roll, steps)
+            out[i] = {"wall_us": round(wall, 2), "k_cs_roll_us": round(kernel_times(roll, iters=20).get("k_cs_roll", 0.0), 2),
+                      "roll_bytes": (i + 1) * B * H * K * V * 4 + 3 * B * H * K * V * 4}
+    print(json.dumps({"roll_sweep": {"B": B, "H": H, "K": K, "V": V}, "by_chunk": out}), flush=True)
+
+
+def workload():
+    B, H, K, V, T0, n = 1, 4, 128, 256, 8000, 192
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    q, k = (torch.randn(B, T0 + n, H, K, generator=g).to(torch.bfloat16).to(DEV) for _ in range(2))
+    v = torch.randn(B, T0 + n, H, V, generator=g).to(torch.bfloat16).to(DEV)
+    with torch.no_grad():
+        _, state = mhla_amd.mhla_causal_prefill(q[:, :T0], k[:, :T0], v[:, :T0], mix)
+        for t in range(T0, T0 + n):
+            mhla_amd.mhla_causal_step(q[:, t:t + 1], k[:, t:t + 1], v[:, t:t + 1], mix, state)
+    torch.cuda.synchronize()
+    print(json.dumps({"workload": "prefill + steps", "B": B, "H": H, "K": K, "V": V, "prefill": T0, "steps": n, "seen": state.seen}))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--parent-iters", type=int, default=5)
+    ap.add_argument("--workload", action="store_true")
+    a = ap.parse_args()
+    if a.workload:
+        workload()
+    else:
+        for H, K, V in ((4, 128, 256), (4, 256, 512)):
+            for B in (1, 32):
+                for pos in (100, 8000):
+                    config(B, H, K, V, pos, max(200, a.steps), a.reps, a.parent_iters)
+        roll_sweep(1, 4, 128, 256, max(200, a.steps))
+        roll_sweep(32, 4, 128, 256, max(200, a.steps))
