@@ -205,7 +205,7 @@ def blockmix_bwd(
 # ----------------------------------------------------------------------------
 # A10  causal chunk-mixing forward
 # ----------------------------------------------------------------------------
-def causal_fwd(q, k, v, mix, chunk_size: int = 64, return_aux: bool = False):
+def causal_fwd(q, k, v, mix, chunk_size: int = 64, return_aux: bool = False, scale: Optional[float] = None):
     """Causal chunk-mixing MHLA operator, forward.
 
     Restates ``naive_chunk_simple_mhla_fixed``
@@ -213,12 +213,14 @@ def causal_fwd(q, k, v, mix, chunk_size: int = 64, return_aux: bool = False):
     right-pad T to a multiple of ``chunk_size``, ``S_j = K_j^T V_j``,
     ``O_i = Q_i (sum_{j<i} m_ij S_j) + m_ii tril(Q_i K_i^T) V_i``; cast back.
     ``q, k: [B, T, H, K]``, ``v: [B, T, H, V]``, ``mix: [L, L]`` (or
-    ``[L, L, 1, 1, 1, 1]``) with ``L >= ceil(T / chunk_size)``.
+    ``[L, L, 1, 1, 1, 1]``) with ``L >= ceil(T / chunk_size)``.  ``scale`` replaces
+    the reference's ``K**-0.5`` (the default) when given.
     """
     dtype = q.dtype
     mix = mix.reshape(mix.shape[0], mix.shape[1]).float()
     qf, kf, vf = (t.permute(0, 2, 1, 3).float() for t in (q, k, v))     # naive.py:39
-    scale = qf.shape[-1] ** -0.5                                        # naive.py:42
+    if scale is None:
+        scale = qf.shape[-1] ** -0.5                                    # naive.py:42
     T = qf.shape[-2]
     C = chunk_size
     pad = (C - T % C) % C                                               # naive.py:46-51
@@ -241,11 +243,12 @@ def causal_fwd(q, k, v, mix, chunk_size: int = 64, return_aux: bool = False):
     return o
 
 
-def causal_bwd(q, k, v, mix, dout, chunk_size: int = 64) -> dict:
+def causal_bwd(q, k, v, mix, dout, chunk_size: int = 64, scale: Optional[float] = None) -> dict:
     """Closed-form gradients of :func:`causal_fwd`."""
     mix2 = mix.reshape(mix.shape[0], mix.shape[1]).float()
     qf, kf, vf, dof = (t.permute(0, 2, 1, 3).float() for t in (q, k, v, dout))
-    scale = qf.shape[-1] ** -0.5
+    if scale is None:
+        scale = qf.shape[-1] ** -0.5
     T = qf.shape[-2]
     C = chunk_size
     pad = (C - T % C) % C

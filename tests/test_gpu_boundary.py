@@ -202,14 +202,21 @@ def test_cpp_and_python_autograd_nodes_are_the_same_operator(monkeypatch):
             o.backward(torch.randn(B, N, H, D, generator=g).to(dt).to(DEV))
             out += [o.detach(), q.grad, k.grad, v.grad, W.grad] + ([qd.grad, kd.grad] if split else [])
         # causal: 16-bit pipeline and generic kernels, [L, L, 1, 1, 1, 1] parameter with L > n
-        for (T, K, V, dt) in ((300, 64, 128, torch.bfloat16), (100, 16, 24, torch.float32)):
+        # (the last case: a `scale` argument, which each node hands to the C ABI itself; same seed, so same tensors as the first)
+        o_at = {}
+        for (T, K, V, dt, scale) in ((300, 64, 128, torch.bfloat16, None), (100, 16, 24, torch.float32, None), (300, 64, 128, torch.bfloat16, 0.37)):
             g.manual_seed(T)
             mk = lambda d: torch.randn(2, T, 2, d, generator=g).to(dt).to(DEV).requires_grad_(True)
             q, k, v = mk(K), mk(K), mk(V)
             mix = torch.tril(torch.rand(8, 8, generator=g)).reshape(8, 8, 1, 1, 1, 1).to(DEV).requires_grad_(True)
-            o = mhla_amd.mhla_causal(q, k, v, mix)
+            o = mhla_amd.mhla_causal(q, k, v, mix, scale=scale)
             o.backward(torch.randn(2, T, 2, V, generator=g).to(dt).to(DEV))
             out += [o.detach(), q.grad, k.grad, v.grad, mix.grad]
+            if (T, K, V, dt) == (300, 64, 128, torch.bfloat16):
+                o_at[scale] = o.detach()
+        # the scaled case is another result than the default one on the same tensors (both nodes read the argument), and linear in it
+        assert not torch.equal(o_at[0.37], o_at[None])
+        check("out at scale 0.37 vs 0.37 / 0.125 x the default's", o_at[0.37], (o_at[None].float() * (0.37 / 0.125)).cpu(), 3 * 2.0 ** -8)   # two bf16 roundings + slack
         res[native] = out
         x = torch.rand(2, 64, 2, 16, device=DEV)
         with pytest.raises(ValueError):

@@ -3,7 +3,7 @@ import pytest
 import torch
 
 from conftest import load_golden
-from gpu_util import poison, DEV, GTOL_BF16SUM, TOL_BF16SUM, CAUSAL_TOL, CAUSAL_DMIX_TOL, check
+from gpu_util import poison, DEV, GTOL_BF16SUM, TOL_BF16SUM, CAUSAL_TOL, CAUSAL_CHUNK_TOL_H16, CAUSAL_DMIX_TOL, check, check_chunks
 from oracle import mhla_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -27,26 +27,47 @@ def causal_tols(dtype, summaries="tf32"):
     return CAUSAL_TOL[dtype], CAUSAL_TOL[dtype], CAUSAL_DMIX_TOL[dtype]
 
 
-def run_causal(B, T, H, K, V, L, dtype, seed=1234, summaries="tf32"):
+def causal_chunk_tols(dtype, summaries="tf32"):
+    """(out, dq / dk / dv) tolerances of the PER-CHUNK check (gpu_util.check_chunks): every summary tile belongs to one chunk and is
+    rounded relative to itself, so the derivations hold chunk by chunk -- the bf16-summaries bounds for summaries="bf16", one
+    final rounding + 1e-3 otherwise; for the default 11-bit stored summaries the bound derived from the fp64 model of the format
+    (gpu_util.CAUSAL_CHUNK_TOL_H16; shapes that the default arithmetic serves with wider summaries are held to it as well)."""
+    if summaries == "bf16":
+        return TOL_BF16SUM[dtype], GTOL_BF16SUM[dtype]
+    if summaries == "tf32":
+        return CAUSAL_CHUNK_TOL_H16[dtype], CAUSAL_CHUNK_TOL_H16[dtype]
+    return CAUSAL_TOL[dtype], CAUSAL_TOL[dtype]
+
+
+def check_both(name, got, want, tol, chunk_tol=None):
+    """The globally normalised check and the per-chunk one (token axis 1, 64-token chunks)."""
+    check(name, got, want, tol)
+    check_chunks(name, got, want, tol if chunk_tol is None else chunk_tol)
+
+
+def run_causal(B, T, H, K, V, L, dtype, seed=1234, summaries="tf32", inputs=None, scale=None, force_generic=False):
+    """Forward and backward against the oracle: out, dq, dk, dv under the global and the per-chunk check, dmix under the global
+    one.  `inputs`: (q, k, v, mix, do) instead of causal_inputs(..., seed); `scale`: passed to the operator and the oracle."""
     import mhla_amd
-    q, k, v, mix, do = causal_inputs(B, T, H, K, V, L, dtype, seed)
-    want = orc.causal_fwd(q.float(), k.float(), v.float(), mix)
-    wg = orc.causal_bwd(q.float(), k.float(), v.float(), mix, do.float())
+    q, k, v, mix, do = causal_inputs(B, T, H, K, V, L, dtype, seed) if inputs is None else inputs
+    want = orc.causal_fwd(q.float(), k.float(), v.float(), mix, scale=scale)
+    wg = orc.causal_bwd(q.float(), k.float(), v.float(), mix, do.float(), scale=scale)
     dq, dk, dv, dm = (t.to(DEV).requires_grad_(True) for t in (q, k, v, mix.view(L, L, 1, 1, 1, 1)))
     poison()
-    if summaries == "tf32":   # the reference's own call form (the library's default arithmetic)
+    if summaries == "tf32" and scale is None and not force_generic:   # the reference's own call form (the library's default arithmetic)
         out = mhla_amd.naive_chunk_simple_mhla_fixed(q=dq, k=dk, v=dv, mixing_matrix=dm)
     else:
-        out = mhla_amd.mhla_causal(dq, dk, dv, dm, summaries=summaries)
+        out = mhla_amd.mhla_causal(dq, dk, dv, dm, scale=scale, summaries=summaries, force_generic=force_generic)
     assert out.dtype == dtype and out.shape == (B, T, H, V)
     dod = do.to(DEV)
     poison()
     out.backward(dod)
     otol, gtol, mtol = causal_tols(dtype, summaries)
-    check("out", out, want, otol)
-    check("dq", dq.grad, wg["dq"], gtol)
-    check("dk", dk.grad, wg["dk"], gtol)
-    check("dv", dv.grad, wg["dv"], gtol)
+    cotol, cgtol = causal_chunk_tols(dtype, "split" if force_generic else summaries)
+    check_both("out", out, want, otol, cotol)
+    check_both("dq", dq.grad, wg["dq"], gtol, cgtol)
+    check_both("dk", dk.grad, wg["dk"], gtol, cgtol)
+    check_both("dv", dv.grad, wg["dv"], gtol, cgtol)
     check("dmix", dm.grad.reshape(L, L), wg["dmix"], mtol)
 
 
@@ -66,9 +87,10 @@ def test_golden_causal(tag):
     # (2u + 1e-3), and the rms-relative error -- which counts how OFTEN that happens -- under north_star's 1e-3 (observed 1.5e-4;
     # single-bf16 summaries flip 40 % of the elements: 3e-3).
     tol = 2 * 2.0 ** -8 + 1e-3 if bf16 else 1e-4
-    check("out", out, g["out"], tol)
+    # per chunk: a one-ulp flip is 2u of ITS element, so fixture d keeps its bound chunk by chunk; fp32 fixtures: CAUSAL_TOL
+    check_both("out", out, g["out"], tol, tol if bf16 else CAUSAL_TOL[torch.float32])
     for n, t in (("dq", q), ("dk", k), ("dv", v)):
-        check(n, t.grad, g[n], tol if bf16 else 2e-4)
+        check_both(n, t.grad, g[n], tol if bf16 else 2e-4)
     check("dmix", mix.grad, g["dmix"], CAUSAL_DMIX_TOL[torch.bfloat16] if bf16 else 2e-4)
     if bf16:
         from conftest import rms_ratio
@@ -96,13 +118,16 @@ def test_causal_lowp(dtype):
 BF16_SHAPES = [(256, 64, 64), (200, 64, 128), (50, 128, 64), (1000, 128, 256), (129, 256, 512),
                (320, 64, 48), (320, 48, 64), (200, 192, 192), (130, 192, 320), (200, 64, 384),
                # chunk walks of the output / summaries kernels (four chunks per workgroup): a full group followed by a partial
-               # one, ragged and one-token last chunks
+               # one, ragged and one-token last chunks -- held to their OWN magnitude by the per-chunk check of run_causal (against
+               # the tensor's maximum a one-token last chunk of dk is 1 .. 6 % and may be anything); the tails and walk boundaries
+               # one by one: test_causal_tails_and_walk_boundaries
                (330, 128, 256), (449, 128, 256), (321, 64, 64), (8192, 64, 64), (2100, 256, 256),
                # 129..256 chunks: the sixteen-wave mixing kernels (dS and dmix as two launches)
                (8256, 64, 64), (16384, 64, 64), (10000, 128, 128),
                # the token-gradient kernel's chunk walk (k_csf_bwd_tok4: with B H = 4 here, two chunks per workgroup from 128 chunks on and
                # four at 256 -- the shapes above cover K = 64 / 128 with an odd chunk count and a ragged tail; the full-size C5 test walks
-               # eight): K = 192, an odd count and a 8-token last chunk
+               # eight): K = 192, an odd count and a 8-token last chunk (dk / dv there are 0.6 % of the tensor's maximum: it is the
+               # per-chunk check that sees them)
                (8200, 192, 192)]
 
 
@@ -133,7 +158,9 @@ def test_causal_shapes_bf16_hi_lo_summaries(T, K, V):
 
 @pytest.mark.parametrize("vscale,doscale", [(1e-18, 1e12), (3e14, 1e-25)])
 def test_causal_h16_summaries_at_extreme_scales(vscale, doscale):
-    """The chunk summaries' strip multipliers absorb the scale of v and dO (1e-18 .. 3e14); a zero chunk and one 2^40 above the rest included."""
+    """The chunk summaries' strip multipliers absorb the scale of v and dO (1e-18 .. 3e14); a zero chunk and one 2^40 above the rest
+    included.  The per-chunk check holds the chunks in front of the large one (out, dq) and every other chunk's dk to their own
+    magnitude; dk of the zeroed v chunk (both of its terms carry v_j) is exactly zero."""
     import mhla_amd
     B, T, H, K, V, L = 1, 512, 2, 64, 128, 8
     q, k, v, mix, do = causal_inputs(B, T, H, K, V, L, torch.float32, seed=21)
@@ -149,11 +176,14 @@ def test_causal_h16_summaries_at_extreme_scales(vscale, doscale):
     out = mhla_amd.mhla_causal(dq, dk, dv, dm)
     out.backward(do.to(DEV))
     otol, gtol, mtol = causal_tols(torch.bfloat16)
-    check("out", out, want, otol)
-    check("dq", dq.grad, wg["dq"], gtol)
-    check("dk", dk.grad, wg["dk"], gtol)
-    check("dv", dv.grad, wg["dv"], gtol)
+    cotol, cgtol = causal_chunk_tols(torch.bfloat16)
+    check_both("out", out, want, otol, cotol)
+    check_both("dq", dq.grad, wg["dq"], gtol, cgtol)
+    check_both("dk", dk.grad, wg["dk"], gtol, cgtol)
+    check_both("dv", dv.grad, wg["dv"], gtol, cgtol)
     check("dmix", dm.grad, wg["dmix"], mtol)
+    assert float(wg["dk"][:, 64:128].abs().max()) == 0.0 and float(wg["dk"][:, 128:192].abs().max()) > 0.0
+    assert torch.equal(dk.grad[:, 64:128].cpu(), torch.zeros(B, 64, H, K, dtype=torch.bfloat16)), "dk of the zeroed v chunk"
 
 
 @pytest.mark.parametrize("T,K,V", [(16400, 64, 64), (300, 320, 64)])
@@ -174,8 +204,80 @@ def test_causal_bf16_pipeline_vs_generic():
         out.backward(do.to(DEV))
         res[tag] = (out, dq.grad, dk.grad, dv.grad, dm.grad)
     for name, a, b in zip(("out", "dq", "dk", "dv"), res["fast"], res["generic"]):
-        check(name, a, b.float().cpu(), 2 * 2.0 ** -8 + 1e-3)
+        check_both(name, a, b.float().cpu(), 2 * 2.0 ** -8 + 1e-3)
     check("dmix", res["fast"][4], res["generic"][4].float().cpu(), 1e-3)
+
+
+# ---- the smallest shapes at which a chunk can be wrong locally: every case forward + backward vs the oracle, global and per-chunk ----
+ARITH = [(torch.bfloat16, 64, 64, "tf32"), (torch.bfloat16, 64, 64, "split"), (torch.bfloat16, 192, 192, "tf32"),
+         (torch.bfloat16, 192, 192, "split"), (torch.float32, 32, 16, "tf32")]
+ARITH_IDS = [f"{str(d).split('.')[-1]}-K{K}-V{V}-{s}" for d, K, V, s in ARITH]
+
+
+@pytest.mark.parametrize("B,H", [(2, 2), (1, 3)], ids=["B2H2", "B1H3"])
+@pytest.mark.parametrize("arith", ARITH, ids=ARITH_IDS)
+@pytest.mark.parametrize("r", [1, 8, 17, 63])
+@pytest.mark.parametrize("n", [1, 4, 5, 8])
+def test_causal_tails_and_walk_boundaries(n, r, arith, B, H):
+    """T = 64 n + r: the kernels walk four chunks per workgroup, so n = 4, 8 put the ragged tail behind full groups and n = 1, 5
+    inside one; bf16 pipeline (K / 64 = 1 and 3) with 11-bit and hi + lo summaries, and the generic fp32 kernels.  B = 1, H = 3:
+    the rows behind a ragged tail belong to another head's valid, finite data, which poison() cannot flag -- the tail's own
+    magnitude does."""
+    dtype, K, V, summaries = arith
+    T = 64 * n + r
+    run_causal(B, T, H, K, V, n + 1, dtype, seed=1000 * n + r + K, summaries=summaries)
+
+
+def positive_inputs(B, T, H, K, V, L, dtype, seed):
+    """q, k = relu(randn): the layer's feature map before rotary -- every chunk summary adds with one sign, so out and dq grow along
+    the sequence (the first chunk is about 1/16 of the last at T = 1024) and dk, dv shrink."""
+    g = torch.Generator().manual_seed(seed)
+    q = torch.relu(torch.randn(B, T, H, K, generator=g)).to(dtype)
+    k = torch.relu(torch.randn(B, T, H, K, generator=g)).to(dtype)
+    v = torch.randn(B, T, H, V, generator=g).to(dtype)
+    do = torch.randn(B, T, H, V, generator=g).to(dtype)
+    return q, k, v, torch.tril(torch.rand(L, L, generator=g).clamp(1e-5, 1)), do
+
+
+@pytest.mark.parametrize("dtype,summaries", [(torch.bfloat16, "tf32"), (torch.bfloat16, "split"), (torch.float32, "tf32")], ids=["bf16", "bf16-split", "fp32"])
+@pytest.mark.parametrize("K,V", [(64, 64), (128, 256)])
+def test_causal_growth_along_the_sequence(K, V, dtype, summaries):
+    B, T, H, L = 2, 1024, 2, 16
+    run_causal(B, T, H, K, V, L, dtype, summaries=summaries, inputs=positive_inputs(B, T, H, K, V, L, dtype, seed=K + V))
+
+
+def log_uniform_mix(L, seed, small_diagonal=False):
+    """The mixing parameter over its legal range [1e-5, 1] (the layer clamps there): log-uniform entries, which make whole chunks of
+    out small; optionally m_ii = 1e-5 (the clamp's lower end) on every other diagonal entry, chunk 0 included."""
+    g = torch.Generator().manual_seed(seed)
+    mix = torch.tril(10.0 ** (-5.0 * torch.rand(L, L, generator=g)))
+    if small_diagonal:
+        mix.diagonal()[0::2] = 1e-5
+    assert float(mix.max()) <= 1.0 and float(mix[mix > 0].min()) >= float(torch.tensor(1e-5))   # (1e-5 as fp32 stores it)
+    return mix
+
+
+@pytest.mark.parametrize("small_diagonal", [False, True], ids=["loguniform", "loguniform-diag1e-5"])
+@pytest.mark.parametrize("T,K,V,dtype,summaries", [(449, 128, 256, torch.bfloat16, "tf32"), (449, 128, 256, torch.bfloat16, "split"),
+                                                    (200, 32, 16, torch.float32, "tf32")], ids=["bf16", "bf16-split", "fp32"])
+def test_causal_mixing_weights_over_their_legal_range(T, K, V, dtype, summaries, small_diagonal):
+    B, H, L = 2, 2, (T + 63) // 64
+    q, k, v, _, do = causal_inputs(B, T, H, K, V, L, dtype, seed=T + K)
+    run_causal(B, T, H, K, V, L, dtype, summaries=summaries, inputs=(q, k, v, log_uniform_mix(L, T, small_diagonal), do))
+
+
+@pytest.mark.parametrize("scale", [1.0, 0.37])
+@pytest.mark.parametrize("T,K,V,dtype,summaries,generic", [(330, 128, 256, torch.bfloat16, "tf32", False), (330, 128, 256, torch.bfloat16, "split", False),
+                                                            (330, 128, 256, torch.bfloat16, "tf32", True), (200, 32, 16, torch.float32, "tf32", False)],
+                         ids=["bf16", "bf16-split", "bf16-generic", "fp32"])
+def test_causal_scale_argument(T, K, V, dtype, summaries, generic, scale):
+    """`scale` other than the default K ** -0.5 (0.088 / 0.177 here) and other than each other: every kernel that applies it -- score
+    tile, dmix diagonal, dQ, dK, output, the dP summaries -- reads the argument; the oracle gets the same one."""
+    import mhla_amd
+    assert abs(scale - K ** -0.5) > 0.1
+    if dtype == torch.bfloat16:
+        assert mhla_amd.describe_causal_dispatch(T, K, V, dtype, summaries=summaries, force_generic=generic)["family"].startswith("generic") == generic
+    run_causal(2, T, 2, K, V, 8, dtype, seed=T + K, summaries=summaries, scale=scale, force_generic=generic)
 
 
 @pytest.mark.parametrize("summaries", ["tf32", "split"])
@@ -216,10 +318,11 @@ def test_causal_more_than_2_31_elements():
         want = orc.causal_fwd(sl(q), sl(k), sl(v), mix)
         wg = orc.causal_bwd(sl(q), sl(k), sl(v), mix, sl(do))
         s16 = lambda t: t.detach()[b:b + 1, :, h:h + 1].cpu()   # (bf16: check() charges the final rounding per element)
-        check("out", s16(out), want, CAUSAL_TOL[torch.bfloat16])
-        check("dq", s16(q.grad), wg["dq"], CAUSAL_TOL[torch.bfloat16])
-        check("dk", s16(k.grad), wg["dk"], CAUSAL_TOL[torch.bfloat16])
-        check("dv", s16(v.grad), wg["dv"], CAUSAL_TOL[torch.bfloat16])
+        ctol = causal_chunk_tols(torch.bfloat16)[1]
+        check_both("out", s16(out), want, CAUSAL_TOL[torch.bfloat16], ctol)
+        check_both("dq", s16(q.grad), wg["dq"], CAUSAL_TOL[torch.bfloat16], ctol)
+        check_both("dk", s16(k.grad), wg["dk"], CAUSAL_TOL[torch.bfloat16], ctol)
+        check_both("dv", s16(v.grad), wg["dv"], CAUSAL_TOL[torch.bfloat16], ctol)
     # dmix of the whole batch = sum over batch chunks (size-independent), first samples anchored on the oracle
     full = md.grad.detach().double().cpu()
     acc = torch.zeros_like(full)
@@ -253,9 +356,10 @@ def test_causal_bf16_strided_views():
     dm = mix.view(L, L, 1, 1, 1, 1).to(DEV).requires_grad_(True)
     out = mhla_amd.naive_chunk_simple_mhla_fixed(q=dqkv[:, :, 0], k=dqkv[:, :, 1], v=dqkv[:, :, 2], mixing_matrix=dm)
     out.backward(do.to(DEV))
-    check("out", out, want, CAUSAL_TOL[torch.bfloat16])
+    ctol = causal_chunk_tols(torch.bfloat16)[1]
+    check_both("out", out, want, CAUSAL_TOL[torch.bfloat16], ctol)
     for i, n in enumerate(("dq", "dk", "dv")):
-        check(n, dqkv.grad[:, :, i], wg[n], CAUSAL_TOL[torch.bfloat16])
+        check_both(n, dqkv.grad[:, :, i], wg[n], CAUSAL_TOL[torch.bfloat16], ctol)
     check("dmix", dm.grad.reshape(L, L), wg["dmix"], CAUSAL_DMIX_TOL[torch.bfloat16])
 
 
@@ -341,6 +445,21 @@ def test_rmsnorm_gate(D, dtype, gate):
 def test_causal_normgate_fused_epilogue(T, K, V, gate, affine, summaries):
     """N1: per-head RMSNorm x swish gate inside the causal operator's output kernel (mhla_causal_normgate_fwd) vs the oracle's
     composition (causal_fwd -> rms_norm_swish_gate), forward and every gradient; and vs the unfused HIP composition."""
+    run_normgate(T, K, V, gate, affine, summaries)
+
+
+@pytest.mark.parametrize("scale", [1.0, 0.37])
+@pytest.mark.parametrize("summaries", ["tf32", "split"])
+def test_causal_normgate_fused_epilogue_scale(summaries, scale):
+    """The same with a `scale` argument other than the default K ** -0.5 = 0.088.  Behind an RMSNorm with eps = 1e-5 << mean(o^2)
+    nothing depends on the scale of o (y moves by 4e-4, the gradients by at most 3e-3: inside the bounds), so these cases take a
+    norm_eps of the size of mean(o^2) at the tested scale (227 at 0.37, 1657 at 1.0): y and every gradient of the oracle
+    composition then differ from those at the default scale by 1.7 .. 7 times their maximum, which run_normgate asserts on the
+    CPU before it compares -- an operator that dropped the argument, or applied it in one direction only, fails every check."""
+    run_normgate(300, 128, 256, True, True, summaries, scale=scale, norm_eps={0.37: 230.0, 1.0: 1660.0}[scale])
+
+
+def run_normgate(T, K, V, gate, affine, summaries, scale=None, norm_eps=1e-5):
     import mhla_amd
     from mhla_amd import ops
     B, H, L = 2, 2, 8
@@ -361,20 +480,32 @@ def test_causal_normgate_fused_epilogue(T, K, V, gate, affine, summaries):
         def backward(ctx, g):
             return g.bfloat16().float()
 
-    ref = [t.float().clone().requires_grad_(True) for t in (q, k, v, mix)]
-    gr = g.float().clone().requires_grad_(True) if gate else None
-    wr = w.clone().requires_grad_(True) if affine else None
-    o_exact = orc.causal_fwd(ref[0], ref[1], ref[2], ref[3])
-    o_ref = _R16.apply(o_exact)
-    norm = lambda o: (orc.rms_norm_swish_gate(o, gr, wr if affine else torch.ones(V), 1e-5) if gate else
-                      o * torch.rsqrt(o.pow(2).mean(-1, keepdim=True) + 1e-5) * (wr if affine else 1.0))
-    y_ref = norm(o_ref)
-    (y_ref * do.float()).sum().backward()
+    def oracle_flow(scale):
+        ref = [t.float().clone().requires_grad_(True) for t in (q, k, v, mix)]
+        gr = g.float().clone().requires_grad_(True) if gate else None
+        wr = w.clone().requires_grad_(True) if affine else None
+        o_exact = orc.causal_fwd(ref[0], ref[1], ref[2], ref[3], scale=scale)
+        o_ref = _R16.apply(o_exact)
+        norm = lambda o: (orc.rms_norm_swish_gate(o, gr, wr if affine else torch.ones(V), norm_eps) if gate else
+                          o * torch.rsqrt(o.pow(2).mean(-1, keepdim=True) + norm_eps) * (wr if affine else 1.0))
+        y_ref = norm(o_ref)
+        (y_ref * do.float()).sum().backward()
+        return ref, gr, wr, o_exact, y_ref, norm
+
+    ref, gr, wr, o_exact, y_ref, norm = oracle_flow(scale)
+    if scale is not None:   # the comparison must be able to see the argument: at the default scale the oracle gives other results
+        from conftest import rel_err
+        ref0, gr0, wr0, _, y0, _ = oracle_flow(None)
+        pairs = [("y", y_ref.detach(), y0.detach())] + [(n, a.grad, b.grad) for n, a, b in zip(("dq", "dk", "dv", "dmix"), ref, ref0)]
+        pairs += [("dgate", gr.grad, gr0.grad)] if gate else []
+        pairs += [("dweight", wr.grad, wr0.grad)] if affine else []
+        for n, a, b in pairs:
+            assert rel_err(b, a) > 0.5, f"{n} does not depend on scale at norm_eps = {norm_eps} ({rel_err(b, a):.2e}): the case proves nothing"
     dev = [t.to(DEV).requires_grad_(True) for t in (q, k, v, mix)]
     gd = g.to(DEV).requires_grad_(True) if gate else None
     wd = w.to(DEV).requires_grad_(True) if affine else None
     poison()
-    y = mhla_amd.mhla_causal_normgate(dev[0], dev[1], dev[2], dev[3], gd, wd, 1e-5, summaries=summaries)
+    y = mhla_amd.mhla_causal_normgate(dev[0], dev[1], dev[2], dev[3], gd, wd, norm_eps, scale=scale, summaries=summaries)
     assert y.dtype == torch.bfloat16
     poison()
     y.backward(do.to(DEV))
@@ -407,8 +538,8 @@ def test_causal_normgate_fused_epilogue(T, K, V, gate, affine, summaries):
         check("dweight", wd.grad, wr.grad, 2e-3 + extra)
     # the unfused composition of the two HIP operators agrees (same kernels downstream, one more bf16 rounding of o)
     with torch.no_grad():
-        y2 = mhla_amd.rmsnorm_gate(mhla_amd.mhla_causal(dev[0], dev[1], dev[2], dev[3], summaries=summaries), gd, wd, 1e-5)
-        y3 = mhla_amd.mhla_causal_normgate(dev[0], dev[1], dev[2], dev[3], gd, wd, 1e-5, summaries=summaries)   # inference: o is not stored
+        y2 = mhla_amd.rmsnorm_gate(mhla_amd.mhla_causal(dev[0], dev[1], dev[2], dev[3], scale=scale, summaries=summaries), gd, wd, norm_eps)
+        y3 = mhla_amd.mhla_causal_normgate(dev[0], dev[1], dev[2], dev[3], gd, wd, norm_eps, scale=scale, summaries=summaries)   # inference: o is not stored
     check("fused vs unfused", y3, y2.float().cpu(), 3 * u + 1e-3)
     check("inference vs training path", y3, y.detach().float().cpu(), 1e-6)
 
@@ -435,10 +566,11 @@ def test_full_size_c5_sampled_head(summaries):
     s16 = lambda t: t.detach()[b:b + 1, :, h:h + 1]   # (bf16: check() charges the final rounding per element)
     want = orc.causal_fwd(sl(q), sl(k), sl(v), mix)
     wg = orc.causal_bwd(sl(q), sl(k), sl(v), mix, sl(do))
-    check("out", s16(out), want, CAUSAL_TOL[torch.bfloat16])
-    check("dq", s16(dq.grad), wg["dq"], CAUSAL_TOL[torch.bfloat16])
-    check("dk", s16(dk.grad), wg["dk"], CAUSAL_TOL[torch.bfloat16])
-    check("dv", s16(dv.grad), wg["dv"], CAUSAL_TOL[torch.bfloat16])
+    ctol = causal_chunk_tols(torch.bfloat16, summaries)[1]
+    check_both("out", s16(out), want, CAUSAL_TOL[torch.bfloat16], ctol)
+    check_both("dq", s16(dq.grad), wg["dq"], CAUSAL_TOL[torch.bfloat16], ctol)
+    check_both("dk", s16(dk.grad), wg["dk"], CAUSAL_TOL[torch.bfloat16], ctol)
+    check_both("dv", s16(dv.grad), wg["dv"], CAUSAL_TOL[torch.bfloat16], ctol)
     # dmix sums over every (b, h): the whole batch through the oracle
     wg_all = orc.causal_bwd(q.float(), k.float(), v.float(), mix, do.float())
     check("dmix (all heads)", dm.grad, wg_all["dmix"], CAUSAL_DMIX_TOL[torch.bfloat16])
@@ -458,8 +590,9 @@ def test_full_size_c5_1p3b_like_shape(summaries):
     out.backward(do.to(DEV))
     want = orc.causal_fwd(q.float(), k.float(), v.float(), mix)
     wg = orc.causal_bwd(q.float(), k.float(), v.float(), mix, do.float())
-    check("out", out, want, CAUSAL_TOL[torch.bfloat16])
-    check("dq", dq.grad, wg["dq"], CAUSAL_TOL[torch.bfloat16])
-    check("dk", dk.grad, wg["dk"], CAUSAL_TOL[torch.bfloat16])
-    check("dv", dv.grad, wg["dv"], CAUSAL_TOL[torch.bfloat16])
+    ctol = causal_chunk_tols(torch.bfloat16, summaries)[1]
+    check_both("out", out, want, CAUSAL_TOL[torch.bfloat16], ctol)
+    check_both("dq", dq.grad, wg["dq"], CAUSAL_TOL[torch.bfloat16], ctol)
+    check_both("dk", dk.grad, wg["dk"], CAUSAL_TOL[torch.bfloat16], ctol)
+    check_both("dv", dv.grad, wg["dv"], CAUSAL_TOL[torch.bfloat16], ctol)
     check("dmix", dm.grad, wg["dmix"], CAUSAL_DMIX_TOL[torch.bfloat16])

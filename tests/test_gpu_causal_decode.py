@@ -6,15 +6,15 @@ import functools
 import pytest
 import torch
 
-from conftest import load_golden, rms_ratio
-from gpu_util import DEV, CAUSAL_TOL, TOL, check, poison
+from conftest import load_golden, rel_err, rms_ratio
+from gpu_util import DEV, CAUSAL_CHUNK_TOL_H16, CAUSAL_TOL, TOL, check, check_chunks, poison
 from oracle import mhla_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 
 @functools.lru_cache(maxsize=None)
-def _inputs(B, T, H, K, V, L, dtype, seed=1234):
+def _inputs(B, T, H, K, V, L, dtype, seed=1234, scale=None):
     """q, k with signs as roped feature maps have them, random lower-triangular mix; the fp32 oracle (output and summaries) of
     the dtype-rounded tensors, computed once per case."""
     g = torch.Generator().manual_seed(seed)
@@ -22,16 +22,28 @@ def _inputs(B, T, H, K, V, L, dtype, seed=1234):
     k = (torch.relu(torch.randn(B, T, H, K, generator=g)) * torch.sign(torch.randn(B, T, H, K, generator=g))).to(dtype)
     v = torch.randn(B, T, H, V, generator=g).to(dtype)
     mix = torch.tril(torch.rand(L, L, generator=g).clamp(1e-5, 1))
-    want = orc.causal_fwd(q.float(), k.float(), v.float(), mix)
+    want = orc.causal_fwd(q.float(), k.float(), v.float(), mix, scale=scale)
     return q, k, v, mix, want
 
 
-def _decode(q, k, v, mix, T0, n, state=None, views=None, **kw):
+def _check_rows(name, o0, o1, want):
+    """Prefill and step rows together, from token 0 so that the 64-token chunks of the per-chunk check are the operator's: each
+    chunk of rows (a partly decoded one included) within the bound of its own maximum.  A chunk may hold rows of both kinds, so
+    it gets the wider of the two per-chunk bounds: prefill rows come from the operator's default arithmetic (11-bit stored
+    summaries for 16-bit tensors: CAUSAL_CHUNK_TOL_H16), step rows from the fp32 state (CAUSAL_TOL)."""
+    got = o1 if o0 is None or o0.shape[1] == 0 else torch.cat([o0, o1], dim=1)
+    assert got.shape[1] == want.shape[1]
+    check_chunks(name, got, want, max(CAUSAL_CHUNK_TOL_H16[got.dtype], CAUSAL_TOL[got.dtype]))
+
+
+def _decode(q, k, v, mix, T0, n, state=None, views=None, scale=None, **kw):
     """Prefill the first T0 tokens (unless a state is given), then n steps; returns (prefill output, stacked step outputs, state)."""
     import mhla_amd
     o0 = None
+    if scale is not None:
+        kw["scale"] = scale
     if state is None:
-        o0, state = mhla_amd.mhla_causal_prefill(q[:, :T0], k[:, :T0], v[:, :T0], mix)
+        o0, state = mhla_amd.mhla_causal_prefill(q[:, :T0], k[:, :T0], v[:, :T0], mix, scale=scale)
         assert state.seen == T0
     outs = []
     for t in range(state.seen, state.seen + n):
@@ -81,6 +93,7 @@ def test_steps_are_rows_of_the_full_operator(case):
     else:
         assert o0.shape == (B, 0, H, V)
     check("step rows", o1, want[:, T0:], CAUSAL_TOL[dtype])
+    _check_rows("rows", o0, o1, want)
 
 
 @pytest.mark.parametrize("tag,T0,T1", [("b", 190, 200), ("a", 64, 256), ("d", 130, 320)])
@@ -95,6 +108,7 @@ def test_steps_match_reference_fixtures(tag, T0, T1):
     want = g["out"][:, :T1]
     tol = 2 * 2.0 ** -8 + 1e-3 if bf16 else 1e-4    # the bounds test_golden_causal holds the operator to on these fixtures
     check("out rows", got, want, tol)
+    check_chunks("out rows", got, want, tol if bf16 else CAUSAL_TOL[torch.float32])
     if bf16:
         r = rms_ratio(got.float().cpu(), want.float())
         assert r < 1e-3, f"rms-relative error {r:.2e} vs the reference's own bf16 result"
@@ -110,6 +124,7 @@ def test_steps_match_the_reference_recurrent_form_on_the_first_chunk():
     assert o0.shape[1] == 0 and state.seen == 50
     check("vs out", o1, g["out"][:, :50], 1e-4)
     check("vs out_recurrent", o1, g["out_recurrent"][:, :50], 1e-4)
+    check_chunks("vs out", o1, g["out"][:, :50], 1e-4)
 
 
 def _check_state(state, q, k, v, mix, name):
@@ -184,6 +199,47 @@ def test_step_fused_norm_gate_epilogue(dtype, gate, affine):
     check("y", y, y_ref, CAUSAL_TOL[dtype])
 
 
+@pytest.mark.parametrize("scale", [1.0, 0.37])
+@pytest.mark.parametrize("epilogue", [False, True], ids=["o", "fused-norm-gate"])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+def test_scale_argument_across_a_chunk_boundary(dtype, epilogue, scale):
+    """`scale` other than the default K ** -0.5 = 0.125 through mhla_causal_prefill (60 tokens) and ten mhla_causal_step calls, the
+    fourth of which closes the chunk: rows of the oracle at the same scale, with and without the step's fused norm x gate
+    epilogue.  Behind a norm with eps << mean(o^2) y does not depend on the scale of o (2e-6 here), so the epilogue cases take
+    a norm_eps of the size of mean(o^2) at the tested scale (72 / 529): the oracle's y at the default scale is then 0.5 .. 0.8 of
+    the maximum away, asserted below.  mhla_causal_state takes no `scale` (the state S = k^T v does not contain it): a state
+    built by it alone continues, under the same `scale`, to the same bits."""
+    import mhla_amd
+    B, H, K, V, T0, n = 1, 2, 64, 128, 60, 10
+    assert abs(scale - K ** -0.5) > 0.1
+    q, k, v, mix, want = _inputs(B, T0 + n, H, K, V, 3, dtype, 1234, scale)
+    qd, kd, vd, md = (t.to(DEV) for t in (q, k, v, mix))
+    kw = {}
+    if epilogue:
+        gen = torch.Generator().manual_seed(7)
+        g = torch.randn(B, T0 + n, H, V, generator=gen).to(dtype)
+        w = torch.rand(V, generator=gen) + 0.5
+        eps = {0.37: 72.0, 1.0: 530.0}[scale]
+        kw = dict(gate=g.to(DEV), norm_weight=w.to(DEV), norm_eps=eps)
+        y_ref = orc.rms_norm_swish_gate(want[:, T0:], g[:, T0:].float(), w, eps)
+        y_default = orc.rms_norm_swish_gate(_inputs(B, T0 + n, H, K, V, 3, dtype)[4][:, T0:], g[:, T0:].float(), w, eps)
+        assert rel_err(y_default, y_ref) > 0.25   # the comparison can see the argument: 50 times the widest bound below
+    poison()
+    o0, o1, state = _decode(qd, kd, vd, md, T0, n, scale=scale, **kw)
+    assert state.seen == T0 + n and o1.dtype == dtype
+    check("prefill rows", o0, want[:, :T0], CAUSAL_TOL[dtype])
+    check_chunks("prefill rows", o0, want[:, :T0], CAUSAL_CHUNK_TOL_H16[dtype])
+    if epilogue:
+        check("y", o1, y_ref, CAUSAL_TOL[dtype])
+    else:
+        check("step rows", o1, want[:, T0:], CAUSAL_TOL[dtype])
+        _check_rows("rows", o0, o1, want)
+    s2 = mhla_amd.mhla_causal_state(kd[:, :T0], vd[:, :T0], md)
+    assert s2.seen == T0
+    _, o2, s2 = _decode(qd, kd, vd, md, T0, n, state=s2, scale=scale, **kw)
+    assert torch.equal(o2, o1) and torch.equal(s2.P, state.P) and torch.equal(s2.Cur, state.Cur) and torch.equal(s2.S[:, :, :1], state.S[:, :, :1])
+
+
 def test_steps_are_deterministic():
     dtype, B, H, K, V, T0, n, _ = C5
     (q, k, v, mix), _ = _case(C5)
@@ -226,6 +282,7 @@ def test_full_state_and_errors():
     # an [L, L] = [2, 2] matrix serves 128 tokens: the last step closes chunk 1 without a next row of mix
     o0, o1, state = _decode(q, k, v, mix, 120, 8)
     check("rows up to the capacity", torch.cat([o0, o1], 1), want[:, :128], CAUSAL_TOL[torch.float32])
+    _check_rows("rows up to the capacity", o0, o1, want[:, :128])
     assert state.seen == 128 and state.capacity_chunks == 2 and state.nbytes == 4 * B * H * K * V * 4
     keep = state.clone()
     with pytest.raises(IndexError, match="needs 3 chunks but mixing_matrix has only 2 rows"):

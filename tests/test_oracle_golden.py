@@ -150,6 +150,22 @@ def test_causal_closed_form_matches_autograd_fp64():
     grads = orc.causal_bwd(qf.detach(), kf.detach(), vf.detach(), mf.detach(), g["dout"])
     for name, t in (("dq", qf), ("dk", kf), ("dv", vf), ("dmix", mf)):
         assert rel_err(grads[name], t.grad) < 2e-5, name
+    # a non-default `scale`: the output is linear in it (q is scaled, nothing else), the closed form follows autograd, and
+    # the default is K ** -0.5 written out
+    K = qf.shape[-1]
+    assert torch.equal(orc.causal_fwd(qf.detach(), kf.detach(), vf.detach(), mf.detach(), scale=K ** -0.5), out.detach())
+    for name in ("dq", "dk", "dv", "dmix"):
+        assert torch.equal(orc.causal_bwd(qf.detach(), kf.detach(), vf.detach(), mf.detach(), g["dout"], scale=K ** -0.5)[name], grads[name]), name
+    for scale in (1.0, 0.37):
+        assert abs(scale - K ** -0.5) > 0.05
+        qs, ks, vs, ms = (t.detach().clone().requires_grad_(True) for t in (qf, kf, vf, mf))
+        out_s = orc.causal_fwd(qs, ks, vs, ms, scale=scale)
+        assert rel_err(out_s.detach(), out.detach() * (scale / K ** -0.5)) < 2e-6
+        (out_s * g["dout"]).sum().backward()
+        grads_s = orc.causal_bwd(qs.detach(), ks.detach(), vs.detach(), ms.detach(), g["dout"], scale=scale)
+        for name, t in (("dq", qs), ("dk", ks), ("dv", vs), ("dmix", ms)):
+            assert rel_err(grads_s[name], t.grad) < 2e-5, (name, scale)
+            assert rel_err(grads_s[name], grads[name]) > 0.05, (name, scale)   # (and it is not the default's gradient)
 
 
 def test_fla_neighbours():
