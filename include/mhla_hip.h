@@ -332,6 +332,28 @@ int mhla_causal_step(mhla_view q, mhla_view k, mhla_view v, const float* mix, in
                      float* Cur, int64_t pos, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y,
                      void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype, void* stream);
 
+/* mhla_causal_extend: T >= 1 new tokens (q, k: [B,T,H,K]; v, out, y, gate: [B,T,H,V]) on a state with `pos` tokens seen, in a
+ * number of launches that does not depend on T.  out = rows pos .. pos + T - 1 of the forward over the whole sequence, the
+ * state afterwards is what T steps leave (the caller advances pos by T).  With i = pos / chunk, r = pos % chunk the tokens
+ * fall into segments that never cross a chunk boundary -- min(T, chunk - r) rows of the open chunk i, whole chunks, a tail --
+ * and for a segment in chunk c with rows Q, K, V:
+ *   O   = scale (Q (P_c + mix[c][c] Cur_before) + mix[c][c] tril(Q K^T) V)        tril over the segment's own rows
+ *   Cur = Cur_before + K^T V ;  chunk full: S[c] = Cur, Cur = 0, P_{c+1} = sum_{j<=c} mix[c+1][j] S[j]  (0 when c + 1 == cap_chunks)
+ * Cur_before is the state's Cur for the first segment and zero afterwards, P_c the state's P for the first segment.  Exact
+ * fp32 products with fp32 accumulation (never the stored 11-bit summaries), no atomics.  `y`, `gate`, `norm_w`, `out`: as
+ * mhla_causal_step, the epilogue applied to the fp32 rows before their one rounding.  An empty state (pos = 0, P = Cur = 0)
+ * makes it a prefill.  Rows of S beyond the finished chunks are neither read nor written.
+ * Workspace (mhla_causal_extend_ws_bytes, pure host arithmetic, independent of dtype): one fp32 [K][V] tile per (b, h) and
+ * chunk touched after the first -- (pos + T - 1) / chunk - pos / chunk of them -- plus the T fp32 rows [V] per (b, h) the
+ * epilogue reads.  MHLA_EINVAL before any launch, the message naming the value: pos + T needs more chunks than cap_chunks;
+ * ldmix does not cover the last row of mix read (row (pos + T) / chunk when a chunk closes and the state is not full then,
+ * else row (pos + T - 1) / chunk); ws_bytes short.  T <= 65535 per call; K, V multiples of 4, chunk 64, B*H <= 65535. */
+size_t mhla_causal_extend_ws_bytes(int B, int T, int H, int K, int V, int64_t pos, int dtype);
+int mhla_causal_extend(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                       float* Cur, int64_t pos, int T, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                       mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
+                       void* stream);
+
 /* ---- prologue: q / k of the Wan host -------------------------------------- */
 
 /*

@@ -1,10 +1,11 @@
-// C ABI, causal operator: the decode state of a sequence and the single-token step (mhla_causal_state_init, mhla_causal_step;
-// kernels: causal_step.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
+// (mhla_causal_state_init, mhla_causal_step, mhla_causal_extend; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
 #include "causal.hpp"
 #include "causal_step.hpp"
+#include "causal_extend.hpp"
 
 using namespace mhla;
 using namespace mhla::capi;
@@ -53,6 +54,24 @@ int cst_xty(const mhla_view& k, const mhla_view& v, long tok0, long ntok, float*
     const int strips = ((K + 63) / 64) * ((V + 63) / 64);
     return launch(k_bm_state<T, 4, 2>, dim3((unsigned)((ntok + CS - 1) / CS), B * H, strips), dim3(NTHREADS), state_smem_floats<4>() * 4, st,
                   "k_bm_state<2>", a);
+}
+
+// the extension's workspace, in floats: P_c of every chunk touched after the first, then the fp32 rows the epilogue reads
+struct CxPlan {
+    int64_t i, ilast, iend;   // chunk of the first / last new token, chunk open after the extension
+    int r, a, nws;            // tokens in the open chunk, rows of the first segment, chunks touched after the first
+    size_t tiles, stage, total;
+};
+CxPlan cx_plan(int B, int T, int H, int K, int V, int64_t pos) {
+    CxPlan p{};
+    p.i = pos / CS; p.r = (int)(pos - p.i * CS);
+    p.a = T < CS - p.r ? T : CS - p.r;
+    p.ilast = (pos + T - 1) / CS; p.iend = (pos + T) / CS;
+    p.nws = (int)(p.ilast - p.i);
+    p.tiles = al4((size_t)B * H * p.nws * K * V);
+    p.stage = al4((size_t)B * H * T * V);
+    p.total = p.tiles + p.stage;
+    return p;
 }
 
 }  // namespace
@@ -119,6 +138,79 @@ int mhla_causal_step(mhla_view q, mhla_view k, mhla_view v, const float* mix, in
         RC(launch(k_cs_step_finish<ET>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
     });
     if (roll) RC(cst_roll(S, cap_chunks, P, Cur, next ? mix + (i + 1) * ldmix : nullptr, (int)i + 1, 1, BH, (long)K * V, st));
+    return MHLA_OK;
+}
+
+size_t mhla_causal_extend_ws_bytes(int B, int T, int H, int K, int V, int64_t pos, int dtype) {
+    (void)dtype;
+    if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || V <= 0 || pos < 0) return 0;
+    return cx_plan(B, T, H, K, V, pos).total * 4;
+}
+
+int mhla_causal_extend(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                       int64_t pos, int T, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws,
+                       size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check(B, H, K, V, chunk, dtype));
+    if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive", T);
+    if (T > 65535) return fail(MHLA_ENOTSUP, "T=%d exceeds 65535 tokens per call", T);
+    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(v);
+    if (!out.ptr && !y.ptr) return fail(MHLA_EINVAL, "out and y both null");
+    if (out.ptr) CHECK_VIEW(out);
+    if (y.ptr) CHECK_VIEW(y);
+    if (gate.ptr) CHECK_VIEW(gate);
+    if ((gate.ptr || norm_w) && !y.ptr) return fail(MHLA_EINVAL, "gate / norm_w given without y");
+    RC(cst_check_state(S, cap_chunks, P, Cur));
+    if (pos < 0) return fail(MHLA_EINVAL, "pos=%lld is negative", (long long)pos);
+    const CxPlan p = cx_plan(B, T, H, K, V, pos);
+    if (p.ilast >= cap_chunks)
+        return fail(MHLA_EINVAL, "pos=%lld + T=%d tokens need %lld chunks, the state holds %d", (long long)pos, T, (long long)(p.ilast + 1), cap_chunks);
+    // rows of mix read: the diagonal of chunks i .. ilast, and row iend (the chunk open afterwards) when a chunk closed and the state is not full
+    const bool closing = p.iend > p.i, full = p.iend >= cap_chunks;
+    const int64_t lastrow = closing && !full ? p.iend : p.ilast;
+    if (!mix || ldmix < lastrow + 1)
+        return fail(MHLA_EINVAL, "mix null or ldmix=%d < %lld (row %lld of mix is read)", ldmix, (long long)(lastrow + 1), (long long)lastrow);
+    if (!ws || ws_bytes < p.total * 4) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, p.total * 4);
+    if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int BH = B * H, nvt = (V + 63) / 64;
+    const long E = (long)K * V;
+    float* tiles = (float*)ws;
+    float* stage = tiles + p.tiles;
+    const int rest = T - p.a, nwhole = rest / CS, tail = rest - nwhole * CS;
+    DISPATCH_T(dtype, {
+        CxOutArgs o{};
+        o.q = cv(q); o.k = cv(k); o.v = cv(v);
+        if (!y.ptr) o.o = cmv(out);
+        o.stage = stage; o.H = H; o.K = K; o.V = V; o.T = T; o.scale = scale; o.mstep = (long)ldmix + 1;
+        // the first segment reads the state's P and Cur before its own product is added to Cur
+        o.P = P; o.p_bh = E; o.p_seg = 0; o.Cur = Cur; o.mdiag = mix + p.i * o.mstep; o.tok0 = 0; o.tend = p.a;
+        RC(launch(k_cx_out<ET>, dim3(1, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out", o));
+        const bool closes = p.r + p.a == CS;
+        const CxAccArgs c{cv(k), cv(v), Cur, closes ? S + p.i * E : Cur, closes ? (long)cap_chunks * E : E, H, p.a, K, V};
+        RC(launch(k_cx_xty_acc<ET>, dim3(1, BH, ((K + 63) / 64) * nvt), dim3(NTHREADS), 0, st, "k_cx_xty_acc", c));
+        if (closes) {
+            if (nwhole) RC(cst_xty<ET>(k, v, p.a, (long)nwhole * CS, S + (p.i + 1) * E, cap_chunks, B, H, K, V, st));
+            if (tail) {
+                RC(cst_xty<ET>(k, v, p.a + (long)nwhole * CS, tail, Cur, 1, B, H, K, V, st));
+            } else {
+                hipError_t e = hipMemsetAsync(Cur, 0, (size_t)BH * E * 4, st);
+                if (e != hipSuccess) return fail(MHLA_ELAUNCH, "hipMemsetAsync(Cur): %s", hipGetErrorString(e));
+            }
+            CxMixArgs m{S, tiles, P, mix, E, ldmix, cap_chunks, (int)p.i + 1, p.nws, 0, full ? -1 : (int)p.iend};
+            m.nc = (int)((full ? p.ilast : p.iend) - p.i);
+            const int groups = std::max(1, (m.nc + CX_MIX_NC - 1) / CX_MIX_NC);   // (a full state forms no P: one group writes the zeros)
+            RC(launch(k_cx_mix, dim3((unsigned)((E / 4 + 63) / 64), BH, groups), dim3(64), 0, st, "k_cx_mix", m));
+            if (rest) {
+                o.P = tiles; o.p_bh = (long)p.nws * E; o.p_seg = E; o.Cur = nullptr; o.mdiag = mix + (p.i + 1) * o.mstep;
+                o.tok0 = p.a; o.tend = T;
+                RC(launch(k_cx_out<ET>, dim3(p.nws, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out", o));
+            }
+        }
+        if (y.ptr) {
+            const CsFinishArgs f{stage, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, 1};
+            RC(launch(k_cs_step_finish<ET>, dim3(BH, T), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
+        }
+    });
     return MHLA_OK;
 }
 

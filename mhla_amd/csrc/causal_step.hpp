@@ -100,21 +100,22 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
 }
 
 struct CsFinishArgs {
-    const float* part;     // [bh][nsplit][V]
-    MView out, y;          // [B][1][H][V]; either ptr may be null
+    const float* part;     // [bh][T][nsplit][V]
+    MView out, y;          // [B][T][H][V], T = gridDim.y (the step: 1); either ptr may be null
     View gate;             // ptr null: no gate
     const float* nw;       // [V] or null
     float neps, scale;
     int H, V, nsplit;
 };
 
-// grid (B H): o = scale * (partials in split order); y = o rsqrt(mean(o^2 over V) + neps) nw g sigmoid(g), from the fp32 o
+// grid (B H, T tokens): o = scale * (partials in split order); y = o rsqrt(mean(o^2 over V) + neps) nw g sigmoid(g), from the fp32 o
 template <typename T>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishArgs a) {
     __shared__ float red[CST_THREADS / 64];
     const int tid = threadIdx.x, bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
-    const float* pb = a.part + (long)bh * a.nsplit * a.V;
-    T* ob = a.out.ptr ? (T*)a.out.ptr + b * a.out.sb + h * a.out.sh : nullptr;
+    const long tok = blockIdx.y;
+    const float* pb = a.part + ((long)bh * gridDim.y + tok) * a.nsplit * a.V;
+    T* ob = a.out.ptr ? (T*)a.out.ptr + b * a.out.sb + tok * a.out.sn + h * a.out.sh : nullptr;
     auto o_at = [&](int c) {   // one accumulator, split order; the loads of a batch of eight issued together
         float s = 0.f;
         int j = 0;
@@ -148,8 +149,8 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishAr
     if ((tid & 63) == 0) red[tid >> 6] = ss;
     __syncthreads();
     const float rstd = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)a.V + a.neps);
-    T* yb = (T*)a.y.ptr + b * a.y.sb + h * a.y.sh;
-    const T* gb = a.gate.ptr ? (const T*)a.gate.ptr + b * a.gate.sb + h * a.gate.sh : nullptr;
+    T* yb = (T*)a.y.ptr + b * a.y.sb + tok * a.y.sn + h * a.y.sh;
+    const T* gb = a.gate.ptr ? (const T*)a.gate.ptr + b * a.gate.sb + tok * a.gate.sn + h * a.gate.sh : nullptr;
     auto put = [&](int c, float o) {
         float yv = o * rstd;
         if (a.nw) yv *= a.nw[c];

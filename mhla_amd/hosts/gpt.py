@@ -5,7 +5,7 @@ Plumbing for step-level numbers; stock PyTorch besides the attention layer.  The
 (layers/mhla.py:196-200: 2048 tokens at chunk 64); `max_seq_len` sizes it for longer sequences (8192 -> 128 chunks, the
 BASELINE.json configs[4] sequence length, through the drop-in layer's `max_chunks`).  With `exact_decoding=True` the layers
 keep a decode state in a cache (`forward(..., cache=DecodeCache())`: prefill on the first call, one exact step per later
-token) and `generate` decodes greedily on top of it."""
+token, one extension per later call of several tokens) and `generate` decodes greedily on top of it."""
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -69,7 +69,9 @@ class GPT_MHLA(nn.Module):
 
     def forward(self, input_ids, labels=None, cache=None):
         """`cache` (a `DecodeCache`, model built with `exact_decoding=True`): `input_ids` are the tokens AFTER the ones the cache
-        has seen -- the whole prompt on an empty cache, then one token per call."""
+        has seen -- the whole prompt on an empty cache, then one token per call, or several (the next turn, a piece of a long
+        prompt, a draft to verify): on a non-empty cache those take the layer's `mhla_causal_extend` path, one launch chain per
+        layer whatever their number."""
         if cache is not None and not self.exact_decoding:
             raise ValueError("GPT_MHLA.forward(cache=...) needs a model built with exact_decoding=True")
         x = self.embeddings(input_ids)

@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops import (CausalState, featmap_rotary, mhla_causal, mhla_causal_normgate, mhla_causal_state, mhla_causal_step,
+from ..ops import (CausalState, featmap_rotary, mhla_causal, mhla_causal_extend, mhla_causal_normgate, mhla_causal_state, mhla_causal_step,
                    naive_recurrent_mhla, rmsnorm_gate)
 from ..weights import causal_mixing_init
 
@@ -199,9 +199,9 @@ class MHLA(nn.Module):
         chunk operator as otherwise, plus a `CausalState` (ops.py: 4 K V bytes per finished chunk and head, fp32) stored as the
         cache's `recurrent_state`; a later call of one token runs `mhla_causal_step` (norm x gate fused when
         `fuse_norm_and_gate`) and returns exactly the row the chunk operator over the whole sequence would.  A later call of
-        several tokens runs the step once per token: correct, not optimised.  All sequences of the batch share one length: a
-        padding `attention_mask` raises NotImplementedError (an all-ones mask is ignored).  Steps are inference only (call
-        under `torch.no_grad()`).  Adds no parameters."""
+        several tokens runs `mhla_causal_extend` once (the same epilogue; launches independent of the token count).  All
+        sequences of the batch share one length: a padding `attention_mask` raises NotImplementedError (an all-ones mask is
+        ignored).  Steps and extensions are inference only (call under `torch.no_grad()`).  Adds no parameters."""
         super().__init__()
         self.mode = mode
         self.hidden_size = hidden_size
@@ -346,17 +346,15 @@ class MHLA(nn.Module):
         recurrent_state = last_state["recurrent_state"] if last_state is not None else None
         fused_epilogue = self.use_output_gate and self.fuse_norm_and_gate and q_len > 64
         if exact and isinstance(recurrent_state, CausalState):
-            # decoding: one exact step per token on the state the prefill (or the steps before) left
+            # decoding on the state the prefill (or the calls before) left: one exact step for one token, one extension for several
             g = gn = None
             if self.fuse_norm_and_gate:
                 g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
                 gn = self.g_norm_swish_gate
             fused_epilogue = gn is not None
-            o = torch.cat([mhla_causal_step(q[:, t:t + 1], k[:, t:t + 1], v[:, t:t + 1], self.mixing_matrix, recurrent_state,
-                                            gate=g[:, t:t + 1] if gn is not None else None,
-                                            norm_weight=gn.weight if gn is not None else None,
-                                            norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None)
-                           for t in range(T)], dim=1)
+            advance = mhla_causal_step if T == 1 else mhla_causal_extend
+            o = advance(q, k, v, self.mixing_matrix, recurrent_state, gate=g, norm_weight=gn.weight if gn is not None else None,
+                        norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None)
             if fused_epilogue:
                 o = o.reshape(B, T, self.value_dim)
         elif exact:

@@ -1373,6 +1373,108 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
     return res
 
 
+# Largest workspace one launch chain of `mhla_causal_extend` takes: a longer extension is cut into consecutive calls.  Per (b, h)
+# the chain needs 4 K V bytes per chunk touched after the first and 4 V bytes per token (mhla_hip.h).
+EXTEND_WS_CAP_BYTES = 256 << 20
+
+
+@_device_guard
+def _causal_extend(q, k, v, mixf, state, pos, scale, gate, wf, norm_eps, want_y, res):
+    lib = _lib.load()
+    B, T, H, K = q.shape
+    V = v.shape[-1]
+    dt = _dtype_code(q)
+    ws = _ws(lib.mhla_causal_extend_ws_bytes(B, T, H, K, V, pos, dt), q.device)
+    rc = lib.mhla_causal_extend(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+                                state.P.data_ptr(), state.Cur.data_ptr(), pos, T, NULL_VIEW if want_y else _view(res),
+                                _view(gate) if gate is not None else NULL_VIEW, wf.data_ptr() if wf is not None else None,
+                                float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K, V,
+                                state.chunk_size, float(scale), dt, _stream())
+    _lib.check(rc, "mhla_causal_extend")
+
+
+def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
+                       scale: Optional[float] = None, gate: Optional[torch.Tensor] = None, norm_weight: Optional[torch.Tensor] = None,
+                       norm_eps: float = 1e-5, epilogue: Optional[bool] = None) -> torch.Tensor:
+    """T >= 1 new tokens on an existing decode state in one call: q, k `[B, T, H, K]`, v (and `gate`) `[B, T, H, V]` of the tokens
+    at positions `state.seen .. state.seen + T - 1`; returns those rows of `mhla_causal` over the whole sequence, `[B, T, H, V]`,
+    updates `state` in place as T calls of `mhla_causal_step` would and adds T to `state.seen` -- the next turn of a
+    conversation, a chunk of a long prompt, a draft to verify, in a number of launches that does not depend on T (at most seven).
+    Exact fp32 products on the fp32 state (rows of the step's grade, never the stored 11-bit summaries), so `extend` and `step`
+    may alternate freely; an empty state makes it a prefill in exact fp32.  T = 1 is `mhla_causal_step` itself (the same bits).
+    Epilogue arguments, strided views, inference only and the IndexError of a sequence beyond the mixing matrix or the state's
+    capacity (raised before anything is launched, the state untouched): as `mhla_causal_step`.  The workspace holds one fp32
+    [K, V] tile per (b, h) and chunk touched after the first, plus the T fp32 output rows; an extension that would need more than
+    `EXTEND_WS_CAP_BYTES` (256 MiB) is cut into consecutive calls at chunk boundaries."""
+    if not isinstance(state, CausalState):
+        raise TypeError(f"mhla_causal_extend: state must be a CausalState, got {type(state).__name__}")
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
+    B, T, H, K = q.shape
+    V = v.shape[-1]
+    if T < 1:
+        raise ValueError(f"mhla_causal_extend takes at least one token per call, got T = {T}")
+    if T == 1:
+        return mhla_causal_step(q, k, v, mixing_matrix, state, scale=scale, gate=gate, norm_weight=norm_weight, norm_eps=norm_eps,
+                                epilogue=epilogue)
+    try:
+        _check_like(q, "mhla_causal_extend", k=(k, q.shape), v=(v, (B, T, H, V)), gate=(gate, (B, T, H, V)))
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+    if q.dtype not in _DTYPES:
+        raise ValueError(f"mhla_causal_extend: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
+    if tuple(state.S.shape) != (B, H, state.capacity_chunks, K, V) or tuple(state.P.shape) != (B, H, K, V) or tuple(state.Cur.shape) != (B, H, K, V):
+        raise ValueError(f"mhla_causal_extend: state is {state!r}, the tokens have B={B} H={H} K={K} V={V}")
+    for name, t in (("state.S", state.S), ("state.P", state.P), ("state.Cur", state.Cur), ("mixing_matrix", mixing_matrix), ("norm_weight", norm_weight)):
+        if t is not None and t.device != q.device:
+            raise ValueError(f"mhla_causal_extend: {name} is on {t.device}, expected {q.device}")
+    if norm_weight is not None and norm_weight.numel() != V:
+        raise ValueError(f"mhla_causal_extend: norm_weight has {norm_weight.numel()} entries, expected V={V}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, gate)):
+        raise RuntimeError("mhla_causal_extend is inference only: call it under torch.no_grad() (an input requires grad)")
+    _require_gpu(q, k, v, mixing_matrix)
+    L = mixing_matrix.shape[0]
+    if mixing_matrix.dim() < 2 or mixing_matrix.shape[1] < min(L, state.capacity_chunks):
+        raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
+    if int(state.chunk_size) != 64:
+        raise ValueError(f"mhla_causal_extend: chunk_size={state.chunk_size}, the decode state supports 64 only")
+    pos = state.seen
+    n = (pos + T + 63) // 64
+    if n > L:
+        raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but mixing_matrix has only {L} rows")
+    if n > state.capacity_chunks:
+        raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but the state holds only {state.capacity_chunks}")
+    if scale is None:
+        scale = K ** -0.5
+    want_y = bool(epilogue) if epilogue is not None else (gate is not None or norm_weight is not None)
+    if not want_y and (gate is not None or norm_weight is not None):
+        raise ValueError("mhla_causal_extend: gate / norm_weight given with epilogue=False")
+    if not (state.S.is_contiguous() and state.P.is_contiguous() and state.Cur.is_contiguous()):
+        raise ValueError("mhla_causal_extend: state tensors must be contiguous")
+    with torch.no_grad():
+        q, k, v = (t if _step_view_ok(t) else t.contiguous() for t in (q, k, v))
+        if gate is not None and not _step_view_ok(gate):
+            gate = gate.contiguous()
+        mixf = _mix2d(mixing_matrix)
+        wf = norm_weight.detach().reshape(V).to(torch.float32).contiguous() if norm_weight is not None else None
+        res = torch.empty((B, T, H, V), dtype=q.dtype, device=q.device)
+        nb = min(B, _MAX_GRID_BH // H)
+        # tokens per call: whole chunks, so that nb H (K V / 64 + V) 4 bytes per token stay under the cap (and under the C ABI's 65535)
+        per_tok = nb * H * (K * V // 64 + V) * 4
+        step_t = min(max(64, EXTEND_WS_CAP_BYTES // per_tok // 64 * 64), 65472)
+        for i in range(0, B, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
+            part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], pos, 64)
+            t0 = 0
+            while t0 < T:
+                # the first piece fills the open chunk, so that every later one starts on a boundary
+                t1 = min(T, t0 + step_t - (pos + t0) % 64)
+                sl = lambda x: None if x is None else x[i:i + nb, t0:t1]
+                _causal_extend(sl(q), sl(k), sl(v), mixf, part, pos + t0, scale, sl(gate), wf, norm_eps, want_y, sl(res))
+                t0 = t1
+    state.seen = pos + T
+    return res
+
+
 # ------------------------------------------------------------------------------------------
 # per-head RMSNorm x swish gate
 # ------------------------------------------------------------------------------------------

@@ -10,6 +10,12 @@ Each JSON line carries the median and the min / max over the repetitions (us per
 library's per-launch event hook (the event-timed batch includes the Python host path of a call, which at B = 1 is the larger
 part), the bytes a step must move -- 3 B H K V 4 (P and Cur read, Cur written) plus the token rows -- and the resulting GB/s.
 
+`--extend`: an extension of T in {16, 64, 256, 1024} tokens by ONE `mhla_causal_extend` call at pos 100 and pos 8000, for the same
+configurations, against (a) the same T tokens as single steps (real ones: the boundaries they cross included) and (b) a full
+`mhla_causal` forward over pos + T tokens -- all three timed in the same run, alternating, `--reps` times; us per token, the
+ratios and the device time of each kernel of the extension.  `--extend --workload`: a prefill of 8000 tokens and one extension
+of 1024 at B = 1, H = 4, K = 128, V = 256, for a trace of its own.
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -117,6 +123,71 @@ def roll_sweep(B, H, K, V, steps):
     print(json.dumps({"roll_sweep": {"B": B, "H": H, "K": K, "V": V}, "by_chunk": out}), flush=True)
 
 
+def extend_config(B, H, K, V, pos, T, reps, parent_iters):
+    g = torch.Generator().manual_seed(1)
+    Lx = L + 16                                   # pos 8000 + 1024 tokens: 141 chunks
+    mix = causal_mixing_init(Lx).reshape(Lx, Lx).to(DEV)
+    i = pos // 64
+    state = mhla_amd.CausalState.empty(B, H, K, V, Lx, DEV)
+    state.S[:, :, :i].normal_(0, 0.1)
+    state.P.normal_(0, 0.1)
+    n = pos + T
+    qT, kT = (torch.randn(B, n, H, K, generator=g).to(torch.bfloat16).to(DEV) for _ in range(2))
+    vT = torch.randn(B, n, H, V, generator=g).to(torch.bfloat16).to(DEV)
+    qe, ke, ve = qT[:, pos:], kT[:, pos:], vT[:, pos:]
+
+    def reset():
+        state.seen = pos
+        state.Cur.zero_()
+
+    def extend():
+        reset()
+        mhla_amd.mhla_causal_extend(qe, ke, ve, mix, state)
+
+    def steps():
+        reset()
+        for t in range(T):
+            mhla_amd.mhla_causal_step(qe[:, t:t + 1], ke[:, t:t + 1], ve[:, t:t + 1], mix, state)
+
+    def parent():
+        mhla_amd.mhla_causal(qT, kT, vT, mix)
+
+    t_ext, t_step, t_parent = [], [], []
+    with torch.no_grad():
+        for _ in range(reps):
+            t_ext.append(batch_us(extend, 20, warm=3))
+            t_step.append(batch_us(steps, max(1, 256 // T), warm=1))
+            t_parent.append(batch_us(parent, parent_iters, warm=2))
+        ks = {nm: round(us, 2) for nm, us in kernel_times(extend, iters=10).items()}
+    ext, stp, par = (statistics.median(x) for x in (t_ext, t_step, t_parent))
+    touched = (pos + T - 1) // 64 - i
+    rec = {"extend": {"B": B, "H": H, "K": K, "V": V, "pos": pos, "T": T}, "reps": reps,
+           "extend_us": spread(t_ext), "steps_us": spread(t_step), "parent_fwd_us": spread(t_parent),
+           "extend_us_per_token": round(ext / T, 3), "steps_us_per_token": round(stp / T, 3), "parent_us_per_token": round(par / T, 3),
+           "steps_over_extend": round(stp / ext, 2), "parent_over_extend": round(par / ext, 2),
+           "extend_kernels_us": ks, "extend_device_us": round(sum(ks.values()), 2),
+           # P, Cur read, Cur / S written, the prefix tiles written and read back, S[0 .. ] read once per eight new chunks, token rows
+           "extend_bytes": B * H * (K * V * 4 * (3 + 3 * touched + (i + touched) * ((touched + 7) // 8)) + T * (2 * K + 2 * V) * 2)}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def extend_workload():
+    B, H, K, V, T0, n = 1, 4, 128, 256, 8000, 1024
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L + 16).reshape(L + 16, L + 16).to(DEV)
+    q, k = (torch.randn(B, T0 + n, H, K, generator=g).to(torch.bfloat16).to(DEV) for _ in range(2))
+    v = torch.randn(B, T0 + n, H, V, generator=g).to(torch.bfloat16).to(DEV)
+    with torch.no_grad():
+        _, state = mhla_amd.mhla_causal_prefill(q[:, :T0], k[:, :T0], v[:, :T0], mix)
+        for _ in range(10):
+            state.seen = T0
+            state.Cur.zero_()
+            mhla_amd.mhla_causal_extend(q[:, T0:], k[:, T0:], v[:, T0:], mix, state)
+    torch.cuda.synchronize()
+    print(json.dumps({"workload": "prefill + 10 x extend", "B": B, "H": H, "K": K, "V": V, "prefill": T0, "extend": n, "seen": state.seen}))
+
+
 def workload():
     B, H, K, V, T0, n = 1, 4, 128, 256, 8000, 192
     g = torch.Generator().manual_seed(1)
@@ -137,8 +208,17 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--parent-iters", type=int, default=5)
     ap.add_argument("--workload", action="store_true")
+    ap.add_argument("--extend", action="store_true")
     a = ap.parse_args()
-    if a.workload:
+    if a.extend and a.workload:
+        extend_workload()
+    elif a.extend:
+        for H, K, V in ((4, 128, 256), (4, 256, 512)):
+            for B in (1, 32):
+                for pos in (100, 8000):
+                    for T in (16, 64, 256, 1024):
+                        extend_config(B, H, K, V, pos, T, a.reps, a.parent_iters)
+    elif a.workload:
         workload()
     else:
         for H, K, V in ((4, 128, 256), (4, 256, 512)):
