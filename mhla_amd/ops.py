@@ -146,6 +146,38 @@ def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(nbytes, 16) // 4 + 4, dtype=torch.float32, device=device)
 
 
+# An optional tensor as the C ABI takes it: a null pointer / null view when it is absent.
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _view_or_null(t: Optional[torch.Tensor]) -> View:
+    return _view(t) if t is not None else NULL_VIEW
+
+
+def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """A norm weight / bias as the kernels read it: detached, fp32, contiguous."""
+    return t.detach().to(torch.float32).contiguous() if t is not None else None
+
+
+def _mix2d(mix: torch.Tensor, cols: Optional[int] = None) -> torch.Tensor:
+    """A mixing matrix [L, L(, 1, ...)] or a block-mix W [M, M(, 1, 1)] as the kernels read it: detached, fp32, contiguous
+    [rows, cols] (`cols`: what the caller will tell the library, so that a matrix of another width fails here)."""
+    return mix.detach().reshape(mix.shape[0], mix.shape[1] if cols is None else cols).to(torch.float32).contiguous()
+
+
+def _block_len(N: int, M: int) -> int:
+    if N % M:
+        raise ValueError(f"N={N} tokens not divisible into M={M} blocks")
+    return N // M
+
+
+def _rope_tables(cos: torch.Tensor, sin: torch.Tensor, N: int, D: int):
+    if cos.shape != (N, D // 2) or sin.shape != (N, D // 2) or cos.dtype != torch.float32 or sin.dtype != torch.float32:
+        raise ValueError(f"rope tables must be fp32 [N={N}, D/2={D // 2}]")
+    return cos.contiguous(), sin.contiguous()
+
+
 # Workspace sizes are pure functions of the problem: one ctypes round trip per distinct problem, not per call (the eager path of a
 # small operator -- the DiT shape -- is bound by the host, tools/host_overhead.py).
 @functools.lru_cache(maxsize=512)
@@ -189,27 +221,21 @@ def describe_dispatch(B: int, H: int, M: int, S: int, D: int, dtype, *, split: b
                       force_generic: bool = False, no_smalln: bool = False) -> dict:
     """Which kernel family, summary format and launches serve a block-mix problem (mhla_describe_dispatch; no GPU needed):
     {"family": ..., "summaries": ..., "fwd": [...], "bwd": [...]}.  dtype: a torch dtype."""
-    import ctypes
-    lib = _lib.load()
-    buf = ctypes.create_string_buffer(1024)
-    rc = lib.mhla_describe_dispatch(B, H, M, S, D, _DTYPES[dtype], int(split), _bm_flags(relu_eps, force_generic, no_smalln, summaries), buf, len(buf))
-    if rc < 0:
-        _lib.check(rc, "mhla_describe_dispatch")
-    return _parse_dispatch(buf.value.decode())
+    return _describe("mhla_describe_dispatch", B, H, M, S, D, _DTYPES[dtype], int(split), _bm_flags(relu_eps, force_generic, no_smalln, summaries))
 
 
 def describe_causal_dispatch(T: int, K: int, V: int, dtype, *, chunk_size: int = 64, summaries: str = "tf32", force_generic: bool = False) -> dict:
     """The same for the causal operator (mhla_causal_describe_dispatch)."""
+    return _describe("mhla_causal_describe_dispatch", T, K, V, chunk_size, _DTYPES[dtype], _causal_flags(summaries, force_generic))
+
+
+def _describe(fn: str, *problem) -> dict:
     import ctypes
-    lib = _lib.load()
     buf = ctypes.create_string_buffer(1024)
-    rc = lib.mhla_causal_describe_dispatch(T, K, V, chunk_size, _DTYPES[dtype], _causal_flags(summaries, force_generic), buf, len(buf))
+    rc = getattr(_lib.load(), fn)(*problem, buf, len(buf))
     if rc < 0:
-        _lib.check(rc, "mhla_causal_describe_dispatch")
-    return _parse_dispatch(buf.value.decode())
-
-
-def _parse_dispatch(txt: str) -> dict:
+        _lib.check(rc, fn)
+    txt = buf.value.decode()
     d = dict(part.split("=", 1) for part in txt.split("; "))
     d["fwd"], d["bwd"] = d["fwd"].split(" "), d["bwd"].split(" ")
     d["text"] = txt
@@ -227,6 +253,16 @@ def set_option(name: str, value: int) -> int:
     return rc
 
 
+def _den_views(normalize, q_den, k_den, qv, kv):
+    """The pair the normaliser reads: q_den / k_den where they are given (Wan: the un-roped q, k), otherwise q / k themselves
+    (`qv`, `kv`: their views); null views without normalisation."""
+    if not normalize:
+        return NULL_VIEW, NULL_VIEW
+    if q_den is not None:
+        return _view(q_den), _view(k_den)
+    return qv, kv
+
+
 class _BlockMix(torch.autograd.Function):
     @staticmethod
     @_device_guard
@@ -235,9 +271,7 @@ class _BlockMix(torch.autograd.Function):
         _require_gpu(q, k, v, W, q_den, k_den, block_index)
         B, N, H, D = q.shape
         M = W.shape[0]
-        if N % M:
-            raise ValueError(f"N={N} tokens not divisible into M={M} blocks")
-        S = N // M
+        S = _block_len(N, M)
         split = q_den is not None
         if split and not normalize:
             raise ValueError("q_den/k_den given but normalize=False")
@@ -248,18 +282,14 @@ class _BlockMix(torch.autograd.Function):
         q, k, v = _prep(q), _prep(k), _prep(v)
         if split:
             q_den, k_den = _prep(q_den), _prep(k_den)
-        Wf = W.detach().reshape(M, M).to(torch.float32).contiguous()
+        Wf = _mix2d(W, M)
         out = _alloc_like_tokens(B, N, H, D, q)
         dt = _dtype_code(q)
         fwd_bytes, _, keeps = _bm_plan(B, H, M, S, D, dt, int(split), flags)
         ws = _ws(fwd_bytes, q.device)
         qv, kv = _view(q), _view(k)
-        if normalize:
-            qd, kd = (_view(q_den), _view(k_den)) if split else (qv, kv)
-        else:
-            qd, kd = NULL_VIEW, NULL_VIEW
-        idx_ptr = block_index.data_ptr() if block_index is not None else None
-        rc = lib.mhla_blockmix_fwd(qv, kv, _view(v), qd, kd, Wf.data_ptr(), M, _view(out), idx_ptr,
+        qd, kd = _den_views(normalize, q_den, k_den, qv, kv)
+        rc = lib.mhla_blockmix_fwd(qv, kv, _view(v), qd, kd, Wf.data_ptr(), M, _view(out), _ptr(block_index),
                                    ws.data_ptr(), ws.numel() * 4, B, H, M, S, D, dt, float(eps), flags, _stream())
         if rc:
             _lib.check(rc, "mhla_blockmix_fwd")
@@ -293,16 +323,10 @@ class _BlockMix(torch.autograd.Function):
         dt = _dtype_code(q)
         ws = _ws(_bm_plan(B, H, M, S, D, dt, int(split), flags)[1], q.device)
         qv, kv = _view(q), _view(k)
-        if normalize:
-            qd, kd = (_view(q_den), _view(k_den)) if split else (qv, kv)
-        else:
-            qd, kd = NULL_VIEW, NULL_VIEW
-        idx_ptr = block_index.data_ptr() if block_index is not None else None
+        qd, kd = _den_views(normalize, q_den, k_den, qv, kv)
         rc = lib.mhla_blockmix_bwd(qv, kv, _view(v), qd, kd, Wf.data_ptr(), M, _view(out), _view(dout),
-                                   _view(dq), _view(dk), _view(dv),
-                                   _view(dqd) if split else NULL_VIEW, _view(dkd) if split else NULL_VIEW,
-                                   dW.data_ptr(), idx_ptr, ws.data_ptr(), ws.numel() * 4,
-                                   fwd_ws.data_ptr() if fwd_ws is not None else None, B, H, M, S, D,
+                                   _view(dq), _view(dk), _view(dv), _view_or_null(dqd), _view_or_null(dkd),
+                                   dW.data_ptr(), _ptr(block_index), ws.data_ptr(), ws.numel() * 4, _ptr(fwd_ws), B, H, M, S, D,
                                    dt, eps, flags, _stream())
         _lib.check(rc, "mhla_blockmix_bwd")
         _check_handover(lib, ws, B, H, M, S, D, dt, int(split), flags)
@@ -383,9 +407,7 @@ def _blockmix_wide_head(q, k, v, W, eps, q_den, k_den, normalize, block_index, r
     c = _wide_head_chunk(D)
     Wm = W.reshape(W.shape[0], W.shape[1]) if W.dim() == 4 else W
     M = Wm.shape[0]
-    if N % M:
-        raise ValueError(f"N={N} tokens not divisible into M={M} blocks")
-    S = N // M
+    S = _block_len(N, M)
     # (16-bit tensors: everything below runs on ONE fp32 copy of each tensor -- the partial products O_ab and the gradient pieces of the
     # slices would otherwise each carry their own 16-bit rounding into their sums -- and results / gradients are rounded once)
     q, k, v = q.float(), k.float(), v.float()
@@ -433,13 +455,12 @@ class _BlockMixRope(torch.autograd.Function):
         M = W.shape[0]
         S = N // M
         q, k, v = _prep(q.detach()), _prep(k.detach()), _prep(v.detach())
-        Wf = W.detach().reshape(M, M).to(torch.float32).contiguous()
-        out = torch.empty((B, N, H, D), dtype=q.dtype, device=q.device)
+        Wf = _mix2d(W, M)
+        out = _alloc_like_tokens(B, N, H, D, q)
         dt = _dtype_code(q)
         ws = _ws(_bm_plan(B, H, M, S, D, dt, 0, 0)[0], q.device)
         rc = lib.mhla_blockmix_rope_fwd(_view(q), _view(k), _view(v), int(bool(normalize)), Wf.data_ptr(), M, cos.data_ptr(),
-                                        sin.data_ptr(), cos.stride(0), _view(out),
-                                        block_index.data_ptr() if block_index is not None else None, ws.data_ptr(),
+                                        sin.data_ptr(), cos.stride(0), _view(out), _ptr(block_index), ws.data_ptr(),
                                         ws.numel() * 4, B, H, M, S, D, dt, float(eps), 0, _stream())
         _lib.check(rc, "mhla_blockmix_rope_fwd")
         keep = any(ctx.needs_input_grad[:4]) and ws.numel() * 4 <= KEEP_STATE_LIMIT_BYTES   # KV, G, z, ksum, 1/n for the backward
@@ -465,8 +486,7 @@ class _BlockMixRope(torch.autograd.Function):
         ws = _ws(_bm_plan(B, H, M, S, D, dt, 0, 0)[1], q.device)
         rc = lib.mhla_blockmix_rope_bwd(_view(q), _view(k), _view(v), int(normalize), Wf.data_ptr(), M, cos.data_ptr(),
                                         sin.data_ptr(), cos.stride(0), _view(out), _view(dout), _view(dq), _view(dk), _view(dv),
-                                        dW.data_ptr(), block_index.data_ptr() if block_index is not None else None,
-                                        ws.data_ptr(), ws.numel() * 4, fwd_ws.data_ptr() if fwd_ws is not None else None,
+                                        dW.data_ptr(), _ptr(block_index), ws.data_ptr(), ws.numel() * 4, _ptr(fwd_ws),
                                         B, H, M, S, D, dt, eps, 0, _stream())
         _lib.check(rc, "mhla_blockmix_rope_bwd")
         return dq, dk, dv, dW.reshape(w_shape).to(w_dtype), None, None, None, None, None
@@ -482,20 +502,15 @@ def mhla_blockmix_rope(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, W: tor
     tensors are materialised, in either direction: the backward rotates q and k again where the rotated ones are needed and
     returns the gradients w.r.t. the un-rotated tensors (fp32 tensors, D % 8 == 0 for the backward)."""
     _require_gpu(q, k, v, W, rope_cos, rope_sin, block_index)
-    if block_index is not None and (block_index.dtype != torch.int32 or not block_index.is_contiguous()):
-        raise TypeError("block_index must be a contiguous int32 tensor")
-    B, N, H, D = q.shape
-    M = W.shape[0]
-    if N % M:
-        raise ValueError(f"N={N} tokens not divisible into M={M} blocks")
+    _, N, _, D = q.shape
+    _block_len(N, W.shape[0])
     _check_like(q, "mhla_blockmix_rope", k=(k, q.shape), v=(v, q.shape))
     _check_block_index(block_index, N, q)
-    if rope_cos.shape != (N, D // 2) or rope_sin.shape != (N, D // 2) or rope_cos.dtype != torch.float32 or rope_sin.dtype != torch.float32:
-        raise ValueError(f"rope tables must be fp32 [N={N}, D/2={D // 2}]")
+    cos, sin = _rope_tables(rope_cos, rope_sin, N, D)
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, W)) and (q.dtype != torch.float32 or D % 8):
         raise RuntimeError("the backward of mhla_blockmix_rope needs fp32 tensors with D % 8 == 0; rotate in the host and call "
                            "mhla_blockmix(q_rope, k_rope, v, W, q_den=q, k_den=k) otherwise")
-    return _BlockMixRope.apply(q, k, v, W, rope_cos.contiguous(), rope_sin.contiguous(), eps, normalize, block_index)
+    return _BlockMixRope.apply(q, k, v, W, cos, sin, eps, normalize, block_index)
 
 
 # ------------------------------------------------------------------------------------------
@@ -506,53 +521,70 @@ def _tok3(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(-1) == 1 else t.contiguous()
 
 
-class _Lepe2d(torch.autograd.Function):
+def _lepe_taps(weight, bias, C, taps):
+    """A depthwise conv's weight [C, 1, k, k(, k)] as fp32 [taps, C], the layout the kernels read, and its bias in fp32 (or None)."""
+    return weight.detach().reshape(C, taps).t().to(torch.float32).contiguous(), _f32(bias)
+
+
+def _lepe_conv(dims, x, w_taps, bias, add, y, geom, transposed):
+    """mhla_lepe2d / mhla_lepe3d (`dims`): y = conv(x) (+ bias) (+ add), or with `transposed` the flipped-kernel correlation that is
+    the gradient w.r.t. the conv's input.  x, add, y: [B, N, C] with contiguous channels (or contiguous [B, N, H, D]: the same batch
+    and token strides); `geom`: the library's geometry arguments, (pieces_len, block_len, C, K) in 2-D and (F, H, W, C) in 3-D."""
+    lib = _lib.load()
+    fn = lib.mhla_lepe3d if dims == 3 else lib.mhla_lepe2d
+    rc = fn(x.data_ptr(), x.stride(0), x.stride(1), w_taps.data_ptr(), _ptr(bias), _ptr(add),
+            add.stride(0) if add is not None else 0, add.stride(1) if add is not None else 0,
+            y.data_ptr(), y.stride(0), y.stride(1), x.shape[0], *geom, int(transposed), _dtype_code(x), _stream())
+    if rc:
+        _lib.check(rc, f"mhla_lepe{dims}d (input gradient)" if transposed else f"mhla_lepe{dims}d")
+
+
+def _lepe_wgrad(dims, v, dy, geom, w_shape, w_dtype, b_dtype):
+    """mhla_lepe2d_wgrad / mhla_lepe3d_wgrad: the gradients of the conv's weight and bias in the parameters' shapes and dtypes
+    (`b_dtype` None: no bias, no gradient).  v, dy: [B, N, C] with contiguous channels."""
+    lib = _lib.load()
+    C = v.shape[2]
+    taps = w_shape.numel() // C
+    dwb = torch.empty((taps + 1, C), dtype=torch.float32, device=v.device)   # one row per tap, then the bias row
+    if dims == 3:
+        fn, nbytes = lib.mhla_lepe3d_wgrad, lib.mhla_lepe3d_wgrad_ws_bytes(C)
+    else:
+        fn, nbytes = lib.mhla_lepe2d_wgrad, lib.mhla_lepe2d_wgrad_ws_bytes(C, geom[3])
+    ws = _ws(nbytes, v.device)
+    rc = fn(v.data_ptr(), v.stride(0), v.stride(1), dy.data_ptr(), dy.stride(0), dy.stride(1), dwb.data_ptr(),
+            ws.data_ptr(), ws.numel() * 4, v.shape[0], *geom, _dtype_code(v), _stream())
+    _lib.check(rc, f"mhla_lepe{dims}d_wgrad")
+    return dwb[:taps].t().reshape(w_shape).to(w_dtype), (dwb[taps].to(b_dtype) if b_dtype is not None else None)
+
+
+class _Lepe(torch.autograd.Function):
+    """`lepe2d` (dims = 2) and `lepe3d` (dims = 3): the same node over the two kernel sets; `geom` as in `_lepe_conv`."""
+
     @staticmethod
     @_device_guard
-    def forward(ctx, v, weight, bias, add, pieces_len, block_len):
-        lib = _lib.load()
+    def forward(ctx, v, weight, bias, add, dims, geom):
         _require_gpu(v, weight, bias, add)
         B, N, C = v.shape
-        K = weight.shape[-1]
         v = _tok3(v)
-        w_taps = weight.detach().reshape(C, K * K).t().to(torch.float32).contiguous()
-        b32 = bias.detach().to(torch.float32).contiguous() if bias is not None else None
-        addc = _tok3(add) if add is not None else None
+        w_taps, b32 = _lepe_taps(weight, bias, C, 27 if dims == 3 else geom[3] ** 2)
         y = torch.empty((B, N, C), dtype=v.dtype, device=v.device)
-        rc = lib.mhla_lepe2d(v.data_ptr(), v.stride(0), v.stride(1), w_taps.data_ptr(),
-                             b32.data_ptr() if b32 is not None else None,
-                             addc.data_ptr() if addc is not None else None,
-                             addc.stride(0) if addc is not None else 0, addc.stride(1) if addc is not None else 0,
-                             y.data_ptr(), y.stride(0), y.stride(1), B, pieces_len, block_len, C, K, 0, _dtype_code(v), _stream())
-        _lib.check(rc, "mhla_lepe2d")
+        _lepe_conv(dims, v, w_taps, b32, _tok3(add) if add is not None else None, y, geom, False)
         ctx.save_for_backward(v, w_taps)
-        ctx.cfg = (pieces_len, block_len, K, weight.shape, weight.dtype, bias is not None, bias.dtype if bias is not None else None,
-                   add is not None)
+        ctx.cfg = (dims, geom, weight.shape, weight.dtype, bias.dtype if bias is not None else None, add is not None)
         return y
 
     @staticmethod
     @_device_guard
     def backward(ctx, dy):
-        lib = _lib.load()
         v, w_taps = ctx.saved_tensors
-        pl, bl, K, w_shape, w_dtype, has_bias, b_dtype, has_add = ctx.cfg
-        B, N, C = v.shape
+        dims, geom, w_shape, w_dtype, b_dtype, has_add = ctx.cfg
         dy = _tok3(dy.to(v.dtype))
         dv = dw = db = None
         if ctx.needs_input_grad[0]:
-            dv = torch.empty((B, N, C), dtype=v.dtype, device=v.device)
-            rc = lib.mhla_lepe2d(dy.data_ptr(), dy.stride(0), dy.stride(1), w_taps.data_ptr(), None, None, 0, 0,
-                                 dv.data_ptr(), dv.stride(0), dv.stride(1), B, pl, bl, C, K, 1, _dtype_code(v), _stream())
-            _lib.check(rc, "mhla_lepe2d (input gradient)")
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            dwb = torch.empty((K * K + 1, C), dtype=torch.float32, device=v.device)
-            ws = _ws(lib.mhla_lepe2d_wgrad_ws_bytes(C, K), v.device)
-            rc = lib.mhla_lepe2d_wgrad(v.data_ptr(), v.stride(0), v.stride(1), dy.data_ptr(), dy.stride(0), dy.stride(1),
-                                       dwb.data_ptr(), ws.data_ptr(), ws.numel() * 4, B, pl, bl, C, K, _dtype_code(v), _stream())
-            _lib.check(rc, "mhla_lepe2d_wgrad")
-            dw = dwb[:K * K].t().reshape(w_shape).to(w_dtype)
-            if has_bias:
-                db = dwb[K * K].to(b_dtype)
+            dv = torch.empty(v.shape, dtype=v.dtype, device=v.device)
+            _lepe_conv(dims, dy, w_taps, None, None, dv, geom, True)
+        if ctx.needs_input_grad[1] or (b_dtype is not None and ctx.needs_input_grad[2]):
+            dw, db = _lepe_wgrad(dims, v, dy, geom, w_shape, w_dtype, b_dtype)
         return dv, dw, db, (dy if has_add else None), None, None
 
 
@@ -566,56 +598,7 @@ def lepe2d(v: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
         raise ValueError("v: [B, N, C]; weight: [C, 1, K, K]")
     if v.shape[1] != (pieces_len * block_len) ** 2 or weight.shape[0] != v.shape[2]:
         raise ValueError(f"N={v.shape[1]} != (pieces_len*block_len)^2 or channel mismatch")
-    return _Lepe2d.apply(v, weight, bias, add, int(pieces_len), int(block_len))
-
-
-class _Lepe3d(torch.autograd.Function):
-    @staticmethod
-    @_device_guard
-    def forward(ctx, v, weight, bias, add, grid):
-        lib = _lib.load()
-        _require_gpu(v, weight, bias, add)
-        B, N, C = v.shape
-        F_, H_, W_ = grid
-        v = _tok3(v)
-        w_taps = weight.detach().reshape(C, 27).t().to(torch.float32).contiguous()
-        b32 = bias.detach().to(torch.float32).contiguous() if bias is not None else None
-        addc = _tok3(add) if add is not None else None
-        y = torch.empty((B, N, C), dtype=v.dtype, device=v.device)
-        rc = lib.mhla_lepe3d(v.data_ptr(), v.stride(0), v.stride(1), w_taps.data_ptr(),
-                             b32.data_ptr() if b32 is not None else None,
-                             addc.data_ptr() if addc is not None else None,
-                             addc.stride(0) if addc is not None else 0, addc.stride(1) if addc is not None else 0,
-                             y.data_ptr(), y.stride(0), y.stride(1), B, F_, H_, W_, C, 0, _dtype_code(v), _stream())
-        _lib.check(rc, "mhla_lepe3d")
-        ctx.save_for_backward(v, w_taps)
-        ctx.cfg = (grid, weight.shape, weight.dtype, bias is not None, bias.dtype if bias is not None else None, add is not None)
-        return y
-
-    @staticmethod
-    @_device_guard
-    def backward(ctx, dy):
-        lib = _lib.load()
-        v, w_taps = ctx.saved_tensors
-        (F_, H_, W_), w_shape, w_dtype, has_bias, b_dtype, has_add = ctx.cfg
-        B, N, C = v.shape
-        dy = _tok3(dy.to(v.dtype))
-        dv = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dv = torch.empty((B, N, C), dtype=v.dtype, device=v.device)
-            rc = lib.mhla_lepe3d(dy.data_ptr(), dy.stride(0), dy.stride(1), w_taps.data_ptr(), None, None, 0, 0,
-                                 dv.data_ptr(), dv.stride(0), dv.stride(1), B, F_, H_, W_, C, 1, _dtype_code(v), _stream())
-            _lib.check(rc, "mhla_lepe3d (input gradient)")
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            dwb = torch.empty((28, C), dtype=torch.float32, device=v.device)
-            ws = _ws(lib.mhla_lepe3d_wgrad_ws_bytes(C), v.device)
-            rc = lib.mhla_lepe3d_wgrad(v.data_ptr(), v.stride(0), v.stride(1), dy.data_ptr(), dy.stride(0), dy.stride(1),
-                                       dwb.data_ptr(), ws.data_ptr(), ws.numel() * 4, B, F_, H_, W_, C, _dtype_code(v), _stream())
-            _lib.check(rc, "mhla_lepe3d_wgrad")
-            dw = dwb[:27].t().reshape(w_shape).to(w_dtype)
-            if has_bias:
-                db = dwb[27].to(b_dtype)
-        return dv, dw, db, (dy if has_add else None), None
+    return _Lepe.apply(v, weight, bias, add, 2, (int(pieces_len), int(block_len), v.shape[2], weight.shape[-1]))
 
 
 def lepe3d(v: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], grid, add: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -628,7 +611,7 @@ def lepe3d(v: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
         raise ValueError("v: [B, N, C]; weight: [C, 1, 3, 3, 3]")
     if v.shape[1] != F_ * H_ * W_ or weight.shape[0] != v.shape[2]:
         raise ValueError(f"N={v.shape[1]} != F*H*W={F_ * H_ * W_} or channel mismatch")
-    return _Lepe3d.apply(v, weight, bias, add, (F_, H_, W_))
+    return _Lepe.apply(v, weight, bias, add, 3, (F_, H_, W_, v.shape[2]))
 
 
 @_device_guard
@@ -645,35 +628,27 @@ def mhla_blockmix_wan(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, W: torc
     _require_gpu(q, k, v, W, rope_cos, rope_sin, norm_weight, gate, block_index)
     if q.dtype != torch.float32:
         raise TypeError("mhla_blockmix_wan takes fp32 q, k, v (the host's .float())")
-    if block_index is not None and (block_index.dtype != torch.int32 or not block_index.is_contiguous()):
-        raise TypeError("block_index must be a contiguous int32 tensor")
     B, N, H, D = q.shape
     M = W.shape[0]
-    if N % M:
-        raise ValueError(f"N={N} tokens not divisible into M={M} blocks")
-    S = N // M
+    S = _block_len(N, M)
     _check_like(q, "mhla_blockmix_wan", k=(k, q.shape), v=(v, q.shape))
     _check_block_index(block_index, N, q)
     q, k, v = _prep(q.detach()), _prep(k.detach()), _prep(v.detach())
     cos = sin = None
     if rope_cos is not None:
-        if rope_cos.shape != (N, D // 2) or rope_cos.dtype != torch.float32 or rope_sin.shape != (N, D // 2) or rope_sin.dtype != torch.float32:
-            raise ValueError(f"rope tables must be fp32 [N={N}, D/2={D // 2}]")
-        cos, sin = rope_cos.contiguous(), rope_sin.contiguous()
+        cos, sin = _rope_tables(rope_cos, rope_sin, N, D)
     if gate is not None:
         if gate.shape != (B, N, H, D) or gate.dtype != out_dtype:
             raise ValueError("gate: [B, N, H, D] in out_dtype")
         gate = _prep(gate.detach())
-    nw = norm_weight.detach().to(torch.float32).contiguous() if norm_weight is not None else None
-    Wf = W.detach().reshape(M, M).to(torch.float32).contiguous()
+    nw = _f32(norm_weight)
+    Wf = _mix2d(W, M)
     out = torch.empty((B, N, H, D), dtype=out_dtype, device=q.device)
     ws = _ws(_bm_plan(B, H, M, S, D, _lib.F32, 0, 0)[0], q.device)
-    rc = lib.mhla_blockmix_wan_fwd(_view(q), _view(k), _view(v), int(bool(normalize)), Wf.data_ptr(), M,
-                                   cos.data_ptr() if cos is not None else None, sin.data_ptr() if sin is not None else None,
-                                   cos.stride(0) if cos is not None else 0, nw.data_ptr() if nw is not None else None,
-                                   float(norm_eps), _view(gate) if gate is not None else NULL_VIEW, _view(out),
-                                   _DTYPES[out_dtype], block_index.data_ptr() if block_index is not None else None,
-                                   ws.data_ptr(), ws.numel() * 4, B, H, M, S, D, _lib.F32, float(eps), 0, _stream())
+    rc = lib.mhla_blockmix_wan_fwd(_view(q), _view(k), _view(v), int(bool(normalize)), Wf.data_ptr(), M, _ptr(cos), _ptr(sin),
+                                   cos.stride(0) if cos is not None else 0, _ptr(nw), float(norm_eps), _view_or_null(gate), _view(out),
+                                   _DTYPES[out_dtype], _ptr(block_index), ws.data_ptr(), ws.numel() * 4,
+                                   B, H, M, S, D, _lib.F32, float(eps), 0, _stream())
     _lib.check(rc, "mhla_blockmix_wan_fwd")
     return out
 
@@ -701,16 +676,13 @@ def mhla_blockmix_wan_pro(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, wq:
     _require_gpu(q, k, v, W, wq, wk, rope_cos, rope_sin, norm_weight, gate, block_index)
     B, N, H, D = q.shape
     M = W.shape[0]
-    if N % M:
-        raise ValueError(f"N={N} tokens not divisible into M={M} blocks")
-    S = N // M
+    S = _block_len(N, M)
     _check_like(q, "mhla_blockmix_wan_pro", k=(k, q.shape), v=(v, q.shape))
     _check_block_index(block_index, N, q)
     q, k, v = _prep(q.detach()), _prep(k.detach()), _prep(v.detach())
     dt = _dtype_code(q)
     C = H * D
-    f32 = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
-    wq, wk, nw = f32(wq), f32(wk), f32(norm_weight)
+    wq, wk, nw = _f32(wq), _f32(wk), _f32(norm_weight)
     rq = rk = None
     if qk_norm:
         if not (q.stride(2) == D and k.stride(2) == D):
@@ -723,22 +695,18 @@ def mhla_blockmix_wan_pro(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, wq:
             _lib.check(lib.mhla_rms_rstd(x.data_ptr(), x.stride(1), r.data_ptr(), B * N, C, float(qk_norm_eps), dt, _stream()), "mhla_rms_rstd")
     cos = sin = None
     if rope_cos is not None:
-        if rope_cos.shape != (N, D // 2) or rope_cos.dtype != torch.float32 or rope_sin.shape != (N, D // 2) or rope_sin.dtype != torch.float32:
-            raise ValueError(f"rope tables must be fp32 [N={N}, D/2={D // 2}]")
-        cos, sin = rope_cos.contiguous(), rope_sin.contiguous()
+        cos, sin = _rope_tables(rope_cos, rope_sin, N, D)
     if gate is not None:
         if gate.shape != (B, N, H, D) or gate.dtype != q.dtype:
             raise ValueError("gate: [B, N, H, D] in the dtype of q")
         gate = _prep(gate.detach())
-    Wf = W.detach().reshape(M, M).to(torch.float32).contiguous()
-    out = torch.empty((B, N, H, D), dtype=q.dtype, device=q.device)
+    Wf = _mix2d(W, M)
+    out = _alloc_like_tokens(B, N, H, D, q)
     ws = _ws(_bm_plan(B, H, M, S, D, _lib.F32, 0, 0)[0], q.device)
-    p = lambda t: t.data_ptr() if t is not None else None
-    rc = lib.mhla_blockmix_wan_pro_fwd(_view(q), _view(k), _view(v), p(rq), p(rk), p(wq), p(wk), int(bool(normalize)), Wf.data_ptr(), M,
-                                       p(cos), p(sin), cos.stride(0) if cos is not None else 0, p(nw), float(norm_eps),
-                                       _view(gate) if gate is not None else NULL_VIEW, _view(out), dt,
-                                       block_index.data_ptr() if block_index is not None else None, ws.data_ptr(), ws.numel() * 4,
-                                       B, H, M, S, D, dt, float(eps), 0, _stream())
+    rc = lib.mhla_blockmix_wan_pro_fwd(_view(q), _view(k), _view(v), _ptr(rq), _ptr(rk), _ptr(wq), _ptr(wk), int(bool(normalize)),
+                                       Wf.data_ptr(), M, _ptr(cos), _ptr(sin), cos.stride(0) if cos is not None else 0, _ptr(nw),
+                                       float(norm_eps), _view_or_null(gate), _view(out), dt, _ptr(block_index),
+                                       ws.data_ptr(), ws.numel() * 4, B, H, M, S, D, dt, float(eps), 0, _stream())
     _lib.check(rc, "mhla_blockmix_wan_pro_fwd")
     return out
 
@@ -759,21 +727,18 @@ class _DitCore(torch.autograd.Function):
         S = N // M
         qkv = qkv if (qkv.is_contiguous() and _strided_ok(qkv[:, :, 0])) else qkv.contiguous()
         q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
-        Wf = W.detach().reshape(M, M).to(torch.float32).contiguous()
+        Wf = _mix2d(W, M)
         dt = _dtype_code(qkv)
-        attn = torch.empty((B, N, H, D), dtype=qkv.dtype, device=qkv.device)
+        attn = _alloc_like_tokens(B, N, H, D, qkv)
         ws = _ws(_bm_plan(B, H, M, S, D, dt, 0, flags)[0], qkv.device)
         qv, kv = _view(q), _view(k)
         rc = lib.mhla_blockmix_fwd(qv, kv, _view(v), qv, kv, Wf.data_ptr(), M, _view(attn), None, ws.data_ptr(), ws.numel() * 4,
                                    B, H, M, S, D, dt, float(eps), flags, _stream())
         _lib.check(rc, "mhla_blockmix_fwd")
-        w_taps = lepe_w.detach().reshape(C, K * K).t().to(torch.float32).contiguous()
-        b32 = lepe_b.detach().to(torch.float32).contiguous() if lepe_b is not None else None
+        w_taps, b32 = _lepe_taps(lepe_w, lepe_b, C, K * K)
         y = torch.empty((B, N, C), dtype=qkv.dtype, device=qkv.device)
         v3 = v.reshape(B, N, C)          # view: H and D are adjacent in the packed buffer
-        rc = lib.mhla_lepe2d(v3.data_ptr(), v3.stride(0), v3.stride(1), w_taps.data_ptr(), b32.data_ptr() if b32 is not None else None,
-                             attn.data_ptr(), N * C, C, y.data_ptr(), N * C, C, B, pieces_len, block_len, C, K, 0, dt, _stream())
-        _lib.check(rc, "mhla_lepe2d")
+        _lepe_conv(2, v3, w_taps, b32, attn, y, (pieces_len, block_len, C, K), False)
         keep = _bm_plan(B, H, M, S, D, dt, 0, flags)[2] and ws.numel() * 4 <= KEEP_STATE_LIMIT_BYTES
         ctx.save_for_backward(qkv, Wf, attn, w_taps, ws if keep else None)
         ctx.cfg = (pieces_len, block_len, float(eps), flags, W.shape, W.dtype, lepe_w.shape, lepe_w.dtype,
@@ -794,29 +759,19 @@ class _DitCore(torch.autograd.Function):
         dy4 = dy.reshape(B, N, H, D)
         q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
         dqkv = torch.empty_like(qkv)
-        dv_attn = torch.empty((B, N, H, D), dtype=qkv.dtype, device=qkv.device)
+        dv_attn = _alloc_like_tokens(B, N, H, D, qkv)
         dW = torch.empty((M, M), dtype=torch.float32, device=qkv.device)
         ws = _ws(_bm_plan(B, H, M, S, D, dt, 0, flags)[1], qkv.device)
         qv, kv = _view(q), _view(k)
         rc = lib.mhla_blockmix_bwd(qv, kv, _view(v), qv, kv, Wf.data_ptr(), M, _view(attn), _view(dy4),
                                    _view(dqkv[:, :, 0]), _view(dqkv[:, :, 1]), _view(dv_attn), NULL_VIEW, NULL_VIEW,
-                                   dW.data_ptr(), None, ws.data_ptr(), ws.numel() * 4,
-                                   fwd_ws.data_ptr() if fwd_ws is not None else None, B, H, M, S, D, dt, eps, flags, _stream())
+                                   dW.data_ptr(), None, ws.data_ptr(), ws.numel() * 4, _ptr(fwd_ws), B, H, M, S, D, dt, eps, flags, _stream())
         _lib.check(rc, "mhla_blockmix_bwd")
         _check_handover(lib, ws, B, H, M, S, D, dt, 0, flags)
         # dv = operator part + LePE part (flipped-kernel correlation of dy), written into the V slice of the packed gradient
-        dv3 = dqkv[:, :, 2].reshape(B, N, C)
-        rc = lib.mhla_lepe2d(dy.data_ptr(), N * C, C, w_taps.data_ptr(), None, dv_attn.data_ptr(), N * C, C,
-                             dv3.data_ptr(), dv3.stride(0), dv3.stride(1), B, pl, bl, C, K, 1, dt, _stream())
-        _lib.check(rc, "mhla_lepe2d (input gradient)")
-        dwb = torch.empty((K * K + 1, C), dtype=torch.float32, device=qkv.device)
-        ws2 = _ws(lib.mhla_lepe2d_wgrad_ws_bytes(C, K), qkv.device)
-        v3 = v.reshape(B, N, C)
-        rc = lib.mhla_lepe2d_wgrad(v3.data_ptr(), v3.stride(0), v3.stride(1), dy.data_ptr(), N * C, C, dwb.data_ptr(),
-                                   ws2.data_ptr(), ws2.numel() * 4, B, pl, bl, C, K, dt, _stream())
-        _lib.check(rc, "mhla_lepe2d_wgrad")
-        dlw = dwb[:K * K].t().reshape(lw_shape).to(lw_dtype)
-        dlb = dwb[K * K].to(lb_dtype) if lb_dtype is not None else None
+        geom = (pl, bl, C, K)
+        _lepe_conv(2, dy, w_taps, None, dv_attn, dqkv[:, :, 2].reshape(B, N, C), geom, True)
+        dlw, dlb = _lepe_wgrad(2, v.reshape(B, N, C), dy, geom, lw_shape, lw_dtype, lb_dtype)
         return dqkv, dW.reshape(w_shape).to(w_dtype), dlw, dlb, None, None, None, None
 
 
@@ -846,7 +801,7 @@ class _FmapRotary(torch.autograd.Function):
         _require_gpu(x, cos, sin)
         B, T, H, K = x.shape
         x = _prep(x)
-        y = torch.empty((B, T, H, K), dtype=x.dtype, device=x.device)
+        y = _alloc_like_tokens(B, T, H, K, x)
         rc = lib.mhla_featmap_rotary(_view(x), NULL_VIEW, cos.data_ptr(), sin.data_ptr(), cos.stride(0), t_offset, _view(y),
                                      B, T, H, K, fmap, 0, _dtype_code(x), _stream())
         _lib.check(rc, "mhla_featmap_rotary")
@@ -862,7 +817,7 @@ class _FmapRotary(torch.autograd.Function):
         fmap, t_offset = ctx.cfg
         B, T, H, K = x.shape
         dy = _prep(dy.to(x.dtype))
-        dx = torch.empty((B, T, H, K), dtype=x.dtype, device=x.device)
+        dx = _alloc_like_tokens(B, T, H, K, x)
         rc = lib.mhla_featmap_rotary(_view(dy), _view(x), cos.data_ptr(), sin.data_ptr(), cos.stride(0), t_offset, _view(dx),
                                      B, T, H, K, fmap, 1, _dtype_code(x), _stream())
         _lib.check(rc, "mhla_featmap_rotary (backward)")
@@ -896,11 +851,11 @@ class _QkPrologue(torch.autograd.Function):
             x2 = x2.contiguous()
         rows = x2.shape[0]
         y = torch.empty((rows, C), dtype=torch.float32, device=x.device)
-        w = weight.detach().to(torch.float32).contiguous() if weight is not None else None
+        w = _f32(weight)
         rope = cos is not None
         yr = torch.empty_like(y) if rope else None
         ntok = cos.shape[0] if rope else 0
-        rc = lib.mhla_qk_prologue_rope(x2.data_ptr(), x2.stride(0), w.data_ptr() if w is not None else None, y.data_ptr(), C,
+        rc = lib.mhla_qk_prologue_rope(x2.data_ptr(), x2.stride(0), _ptr(w), y.data_ptr(), C,
                                        yr.data_ptr() if rope else None, C, cos.data_ptr() if rope else None,
                                        sin.data_ptr() if rope else None, cos.stride(0) if rope else 0, ntok,
                                        int(head_dim) if rope else 0, rows, C, int(weight is not None), float(norm_eps),
@@ -928,11 +883,10 @@ class _QkPrologue(torch.autograd.Function):
         if w is not None:
             dwp = torch.empty((lib.mhla_qk_prologue_dw_rows(rows), C), dtype=torch.float32, device=x2.device)
         rope = dyr is not None
-        rc = lib.mhla_qk_prologue_bwd(x2.data_ptr(), x2.stride(0), w.data_ptr() if w is not None else None,
-                                      dy.data_ptr() if dy is not None else None, C, dyr.data_ptr() if rope else None, C,
+        rc = lib.mhla_qk_prologue_bwd(x2.data_ptr(), x2.stride(0), _ptr(w), _ptr(dy), C, dyr.data_ptr() if rope else None, C,
                                       cos.data_ptr() if rope else None, sin.data_ptr() if rope else None,
                                       cos.stride(0) if rope else 0, cos.shape[0] if rope else 0, head_dim if rope else 0,
-                                      dx.data_ptr(), C, dwp.data_ptr() if dwp is not None else None, rows, C,
+                                      dx.data_ptr(), C, _ptr(dwp), rows, C,
                                       int(w is not None), norm_eps, _dtype_code(x2), _stream())
         _lib.check(rc, "mhla_qk_prologue_bwd")
         dw = dwp.sum(0).to(w_dtype) if dwp is not None else None
@@ -960,6 +914,39 @@ def qk_prologue(x: torch.Tensor, weight: Optional[torch.Tensor], norm_eps: float
 # ------------------------------------------------------------------------------------------
 # causal chunk-mixing MHLA (fla)
 # ------------------------------------------------------------------------------------------
+def _causal_check(what, q, k, v, mix, chunk_size, gate=None):
+    """The forward checks of the causal nodes: a row of the mixing matrix for every chunk of the sequence; k, v, gate like q.
+    Returns the number of chunks."""
+    B, T, H, _ = q.shape
+    n = (T + chunk_size - 1) // chunk_size
+    L = mix.shape[0]
+    if n > L:
+        raise IndexError(f"sequence of {T} tokens needs {n} chunks but mixing_matrix has only {L} rows")
+    _check_like(q, what, k=(k, q.shape), v=(v, (B, T, H, v.shape[-1])), gate=(gate, (B, T, H, v.shape[-1])))
+    return n
+
+
+def _causal_bwd(q, k, v, mixf, dout, fwd_ws, chunk_size, scale, flags):
+    """mhla_causal_bwd on a node's saved tensors (`fwd_ws`: the forward's chunk summaries, None to recompute them):
+    (dq, dk, dv, dmix), dmix fp32 in the shape of mixf."""
+    lib = _lib.load()
+    B, T, H, K = q.shape
+    V = v.shape[-1]
+    dq = _alloc_like_tokens(B, T, H, K, q)
+    dk = _alloc_like_tokens(B, T, H, K, q)
+    dv = _alloc_like_tokens(B, T, H, V, q)
+    # the library writes every entry of the leading [n, n] block (zeros above the diagonal)
+    n_chunks = (T + chunk_size - 1) // chunk_size
+    dmix = (torch.empty if tuple(mixf.shape) == (n_chunks, n_chunks) else torch.zeros)(mixf.shape, dtype=torch.float32, device=q.device)
+    dt = _dtype_code(q)
+    ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, dt, flags)[1], q.device)
+    rc = lib.mhla_causal_bwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(dout),
+                             _view(dq), _view(dk), _view(dv), dmix.data_ptr(), dmix.shape[1],
+                             ws.data_ptr(), ws.numel() * 4, _ptr(fwd_ws), B, T, H, K, V, chunk_size, scale, dt, flags, _stream())
+    _lib.check(rc, "mhla_causal_bwd")
+    return dq, dk, dv, dmix
+
+
 class _Causal(torch.autograd.Function):
     @staticmethod
     @_device_guard
@@ -968,16 +955,12 @@ class _Causal(torch.autograd.Function):
         _require_gpu(q, k, v, mix)
         B, T, H, K = q.shape
         V = v.shape[-1]
-        n = (T + chunk_size - 1) // chunk_size
-        L = mix.shape[0]
-        if n > L:
-            raise IndexError(f"sequence of {T} tokens needs {n} chunks but mixing_matrix has only {L} rows")
-        _check_like(q, "mhla_causal", k=(k, q.shape), v=(v, (B, T, H, V)))
+        n = _causal_check("mhla_causal", q, k, v, mix, chunk_size)
         if mix.device != q.device or mix.dim() < 2 or mix.shape[1] < n:
             raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)] with L >= {n} on {q.device}")
         q, k, v = _prep(q), _prep(k), _prep(v)
-        mixf = mix.detach().reshape(L, mix.shape[1]).to(torch.float32).contiguous()
-        out = torch.empty((B, T, H, V), dtype=q.dtype, device=q.device)
+        mixf = _mix2d(mix)
+        out = _alloc_like_tokens(B, T, H, V, q)
         ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, _dtype_code(q), flags)[0], q.device)
         rc = lib.mhla_causal_fwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(out),
                                  ws.data_ptr(), ws.numel() * 4, B, T, H, K, V, chunk_size, float(scale),
@@ -992,25 +975,14 @@ class _Causal(torch.autograd.Function):
     @staticmethod
     @_device_guard
     def backward(ctx, dout):
-        lib = _lib.load()
         q, k, v, mixf, fwd_ws = ctx.saved_tensors
         chunk_size, scale, mix_shape, mix_dtype, flags = ctx.cfg
-        B, T, H, K = q.shape
-        V = v.shape[-1]
-        dout = _prep(dout.to(q.dtype))
-        dk = torch.empty((B, T, H, K), dtype=q.dtype, device=q.device)
-        dv = torch.empty((B, T, H, V), dtype=q.dtype, device=q.device)
-        dq = torch.empty((B, T, H, K), dtype=q.dtype, device=q.device)
-        # the library writes every entry of the leading [n, n] block (zeros above the diagonal)
-        n_chunks = (T + chunk_size - 1) // chunk_size
-        dmix = (torch.empty if tuple(mixf.shape) == (n_chunks, n_chunks) else torch.zeros)(mixf.shape, dtype=torch.float32, device=q.device)
-        ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, _dtype_code(q), flags)[1], q.device)
-        rc = lib.mhla_causal_bwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(dout),
-                                 _view(dq), _view(dk), _view(dv), dmix.data_ptr(), dmix.shape[1],
-                                 ws.data_ptr(), ws.numel() * 4, fwd_ws.data_ptr() if fwd_ws is not None else None,
-                                 B, T, H, K, V, chunk_size, scale, _dtype_code(q), flags, _stream())
-        _lib.check(rc, "mhla_causal_bwd")
+        dq, dk, dv, dmix = _causal_bwd(q, k, v, mixf, _prep(dout.to(q.dtype)), fwd_ws, chunk_size, scale, flags)
         return dq, dk, dv, dmix.reshape(mix_shape).to(mix_dtype), None, None, None, None
+
+
+def _causal_keep_limit(keep_state_limit: Optional[int]) -> int:
+    return CAUSAL_KEEP_STATE_LIMIT_BYTES if keep_state_limit is None else int(keep_state_limit)
 
 
 def _causal_flags(summaries: str, force_generic: bool) -> int:
@@ -1041,7 +1013,7 @@ def mhla_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix
         raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
     if int(chunk_size) <= 0:
         raise ValueError(f"chunk_size must be positive, got {chunk_size}")
-    keep_limit = CAUSAL_KEEP_STATE_LIMIT_BYTES if keep_state_limit is None else int(keep_state_limit)
+    keep_limit = _causal_keep_limit(keep_state_limit)
     flags = _causal_flags(summaries, force_generic)
     if scale is None:
         scale = q.shape[-1] ** -0.5
@@ -1074,23 +1046,17 @@ class _CausalNormGate(torch.autograd.Function):
         _require_gpu(q, k, v, mix, gate, weight)
         B, T, H, K = q.shape
         V = v.shape[-1]
-        n = (T + chunk_size - 1) // chunk_size
-        L = mix.shape[0]
-        if n > L:
-            raise IndexError(f"sequence of {T} tokens needs {n} chunks but mixing_matrix has only {L} rows")
-        _check_like(q, "mhla_causal_normgate", k=(k, q.shape), v=(v, (B, T, H, V)), gate=(gate, (B, T, H, V)))
+        _causal_check("mhla_causal_normgate", q, k, v, mix, chunk_size, gate)
         q, k, v = _prep(q), _prep(k), _prep(v)
         gate = _prep(gate) if gate is not None else None
-        mixf = mix.detach().reshape(L, mix.shape[1]).to(torch.float32).contiguous()
-        wf = weight.detach().to(torch.float32).contiguous() if weight is not None else None
+        mixf = _mix2d(mix)
+        wf = _f32(weight)
         need_grad = any(ctx.needs_input_grad[:6])
-        out = torch.empty((B, T, H, V), dtype=q.dtype, device=q.device) if need_grad else None
-        y = torch.empty((B, T, H, V), dtype=q.dtype, device=q.device)
+        out = _alloc_like_tokens(B, T, H, V, q) if need_grad else None
+        y = _alloc_like_tokens(B, T, H, V, q)
         ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, _dtype_code(q), flags)[0], q.device)
-        rc = lib.mhla_causal_normgate_fwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1],
-                                          _view(out) if out is not None else NULL_VIEW,
-                                          _view(gate) if gate is not None else NULL_VIEW,
-                                          wf.data_ptr() if wf is not None else None, float(norm_eps), _view(y),
+        rc = lib.mhla_causal_normgate_fwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view_or_null(out),
+                                          _view_or_null(gate), _ptr(wf), float(norm_eps), _view(y),
                                           ws.data_ptr(), ws.numel() * 4, B, T, H, K, V, chunk_size, float(scale),
                                           _dtype_code(q), flags, _stream())
         _lib.check(rc, "mhla_causal_normgate_fwd")
@@ -1102,35 +1068,10 @@ class _CausalNormGate(torch.autograd.Function):
     @staticmethod
     @_device_guard
     def backward(ctx, dy):
-        lib = _lib.load()
         q, k, v, mixf, out, gate, wf, fwd_ws = ctx.saved_tensors
         chunk_size, scale, norm_eps, mix_shape, mix_dtype, w_dtype, flags = ctx.cfg
-        B, T, H, K = q.shape
-        V = v.shape[-1]
-        rows = B * T * H
-        dyc = dy.contiguous().to(q.dtype)
-        do = torch.empty_like(out)
-        dg = torch.empty_like(out) if gate is not None else None
-        gc = gate.contiguous() if gate is not None else None
-        dwp = torch.empty((lib.mhla_rmsnorm_gate_dw_rows(rows), V), dtype=torch.float32, device=q.device)
-        rc = lib.mhla_rmsnorm_gate_bwd(out.data_ptr(), V, gc.data_ptr() if gc is not None else None, V,
-                                       wf.data_ptr() if wf is not None else None, dyc.data_ptr(), V, do.data_ptr(), V,
-                                       dg.data_ptr() if dg is not None else None, V, dwp.data_ptr(), rows, V, norm_eps,
-                                       _dtype_code(q), _stream())
-        _lib.check(rc, "mhla_rmsnorm_gate_bwd")
-        dq = torch.empty((B, T, H, K), dtype=q.dtype, device=q.device)
-        dk = torch.empty((B, T, H, K), dtype=q.dtype, device=q.device)
-        dv = torch.empty((B, T, H, V), dtype=q.dtype, device=q.device)
-        # the library writes every entry of the leading [n, n] block (zeros above the diagonal)
-        n_chunks = (T + chunk_size - 1) // chunk_size
-        dmix = (torch.empty if tuple(mixf.shape) == (n_chunks, n_chunks) else torch.zeros)(mixf.shape, dtype=torch.float32, device=q.device)
-        ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, _dtype_code(q), flags)[1], q.device)
-        rc = lib.mhla_causal_bwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(do),
-                                 _view(dq), _view(dk), _view(dv), dmix.data_ptr(), dmix.shape[1],
-                                 ws.data_ptr(), ws.numel() * 4, fwd_ws.data_ptr() if fwd_ws is not None else None,
-                                 B, T, H, K, V, chunk_size, scale, _dtype_code(q), flags, _stream())
-        _lib.check(rc, "mhla_causal_bwd")
-        dw = dwp.sum(0).to(w_dtype) if wf is not None else None
+        do, dg, dw = _rmsnorm_gate_bwd(out, gate.contiguous() if gate is not None else None, wf, dy, norm_eps, w_dtype)
+        dq, dk, dv, dmix = _causal_bwd(q, k, v, mixf, do, fwd_ws, chunk_size, scale, flags)
         return dq, dk, dv, dmix.reshape(mix_shape).to(mix_dtype), dg, dw, None, None, None, None, None
 
 
@@ -1158,8 +1099,8 @@ def mhla_causal_normgate(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixi
     if not causal_normgate_fusable(q, v, chunk_size, flags):
         return rmsnorm_gate(mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries, keep_state_limit=keep_state_limit),
                             gate, weight, norm_eps)
-    keep_limit = CAUSAL_KEEP_STATE_LIMIT_BYTES if keep_state_limit is None else int(keep_state_limit)
-    return _CausalNormGate.apply(q, k, v, mixing_matrix, gate, weight, int(chunk_size), scale, norm_eps, flags, keep_limit)
+    return _CausalNormGate.apply(q, k, v, mixing_matrix, gate, weight, int(chunk_size), scale, norm_eps, flags,
+                                 _causal_keep_limit(keep_state_limit))
 
 
 def naive_recurrent_mhla(q, k, v, mixing_matrix, chunk_size: int = 64, scale: Optional[float] = None,
@@ -1226,10 +1167,6 @@ class CausalState:
         return f"CausalState(B={B}, H={H}, K={K}, V={V}, capacity_chunks={cap}, seen={self.seen}, device={self.S.device})"
 
 
-def _mix2d(mix: torch.Tensor) -> torch.Tensor:
-    return mix.detach().reshape(mix.shape[0], mix.shape[1]).to(torch.float32).contiguous()
-
-
 @functools.lru_cache(maxsize=64)
 def _step_ws_bytes(B, H, K, V, dt):
     return _lib.load().mhla_causal_step_ws_bytes(B, H, K, V, dt)
@@ -1289,26 +1226,83 @@ def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Ten
     return state
 
 
-@_device_guard
-def _causal_step(q, k, v, mixf, state, pos, scale, gate, wf, norm_eps, want_y):
-    lib = _lib.load()
-    B, _, H, K = q.shape
-    V = v.shape[-1]
-    dt = _dtype_code(q)
-    res = torch.empty((B, 1, H, V), dtype=q.dtype, device=q.device)
-    ws = _ws(_step_ws_bytes(B, H, K, V, dt), q.device)
-    rc = lib.mhla_causal_step(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-                              state.P.data_ptr(), state.Cur.data_ptr(), pos, NULL_VIEW if want_y else _view(res),
-                              _view(gate) if gate is not None else NULL_VIEW, wf.data_ptr() if wf is not None else None,
-                              float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K, V,
-                              state.chunk_size, float(scale), dt, _stream())
-    _lib.check(rc, "mhla_causal_step")
-    return res
-
-
 def _step_view_ok(t: torch.Tensor) -> bool:
     # what the step kernels address in place: 4-element pieces (8 bytes for 16-bit types, 16 for fp32)
     return t.stride(3) == 1 and all(s % 4 == 0 for s in t.stride()[:3]) and t.data_ptr() % (4 * t.element_size()) == 0
+
+
+def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue):
+    """What `mhla_causal_step` and `mhla_causal_extend` (`fn`: the one called, for the messages) check after their own tests of
+    the state's type, the tensors' rank and T, and the tensors they launch with.  The C ABI receives raw pointers, so everything
+    is refused here, in an order callers rely on -- tensors like q, dtype, state shapes, devices, norm_weight, requires-grad, GPU,
+    matrix shape, chunk size, rows / capacity (IndexError), epilogue arguments, state contiguity -- before anything is launched
+    or `state` is touched.  Returns (q, k, v, gate, mixf, wf, pos, scale, want_y): the token tensors addressable in place or as
+    contiguous copies, the mixing matrix and the norm weight in fp32, the position of the first token."""
+    B, T, H, K = q.shape
+    V = v.shape[-1]
+    try:
+        _check_like(q, fn, k=(k, (B, T, H, K)), v=(v, (B, T, H, V)), gate=(gate, (B, T, H, V)))
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+    if q.dtype not in _DTYPES:
+        raise ValueError(f"{fn}: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
+    if tuple(state.S.shape) != (B, H, state.capacity_chunks, K, V) or tuple(state.P.shape) != (B, H, K, V) or tuple(state.Cur.shape) != (B, H, K, V):
+        raise ValueError(f"{fn}: state is {state!r}, the {'token has' if T == 1 else 'tokens have'} B={B} H={H} K={K} V={V}")
+    dev = q.device
+    for name, t in (("state.S", state.S), ("state.P", state.P), ("state.Cur", state.Cur), ("mixing_matrix", mixing_matrix), ("norm_weight", norm_weight)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{fn}: {name} is on {t.device}, expected {dev}")
+    if norm_weight is not None and norm_weight.numel() != V:
+        raise ValueError(f"{fn}: norm_weight has {norm_weight.numel()} entries, expected V={V}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, gate)):
+        raise RuntimeError(f"{fn} is inference only: call it under torch.no_grad() (an input requires grad)")
+    _require_gpu(q, k, v, mixing_matrix)
+    L = mixing_matrix.shape[0]
+    if mixing_matrix.dim() < 2 or mixing_matrix.shape[1] < min(L, state.capacity_chunks):
+        raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
+    if int(state.chunk_size) != 64:
+        raise ValueError(f"{fn}: chunk_size={state.chunk_size}, the decode state supports 64 only")
+    pos = state.seen
+    n = (pos + T + 63) // 64
+    if n > L:
+        raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but mixing_matrix has only {L} rows")
+    if n > state.capacity_chunks:
+        raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but the state holds only {state.capacity_chunks}")
+    if scale is None:
+        scale = K ** -0.5
+    want_y = bool(epilogue) if epilogue is not None else (gate is not None or norm_weight is not None)
+    if not want_y and (gate is not None or norm_weight is not None):
+        raise ValueError(f"{fn}: gate / norm_weight given with epilogue=False")
+    if not (state.S.is_contiguous() and state.P.is_contiguous() and state.Cur.is_contiguous()):
+        raise ValueError(f"{fn}: state tensors must be contiguous")
+    # (nothing from here to the end of the call is recorded for autograd, with or without torch.no_grad(): grad mode is off or no
+    # token tensor requires grad, both matrices are detached, and the launch reads and writes through raw pointers)
+    q, k, v = (t if _step_view_ok(t) else t.contiguous() for t in (q, k, v))
+    if gate is not None and not _step_view_ok(gate):
+        gate = gate.contiguous()
+    wf = norm_weight.detach().reshape(V).to(torch.float32).contiguous() if norm_weight is not None else None
+    return q, k, v, gate, _mix2d(mixing_matrix), wf, pos, scale, want_y
+
+
+@_device_guard
+def _causal_decode(q, k, v, gate, mixf, wf, pos, scale, want_y, fn, state, res, norm_eps):
+    """One launch chain of the library's `fn` ("mhla_causal_step": one token; "mhla_causal_extend": T) on what `_decode_prepare`
+    returned (the first nine arguments): the tokens at positions pos .. of `state`, the rows (after the epilogue with `want_y`)
+    into `res`."""
+    lib = _lib.load()
+    B, T, H, K = q.shape
+    V = v.shape[-1]
+    dt = _dtype_code(q)
+    if fn == "mhla_causal_step":
+        call, ntok, ws_bytes = lib.mhla_causal_step, (), _step_ws_bytes(B, H, K, V, dt)
+    else:
+        call, ntok, ws_bytes = lib.mhla_causal_extend, (T,), lib.mhla_causal_extend_ws_bytes(B, T, H, K, V, pos, dt)
+    ws = _ws(ws_bytes, q.device)
+    rc = call(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+              state.P.data_ptr(), state.Cur.data_ptr(), pos, *ntok, NULL_VIEW if want_y else _view(res), _view_or_null(gate),
+              _ptr(wf), float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K, V,
+              state.chunk_size, float(scale), dt, _stream())
+    _lib.check(rc, fn)
 
 
 def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
@@ -1326,71 +1320,19 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
         raise TypeError(f"mhla_causal_step: state must be a CausalState, got {type(state).__name__}")
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k: [B, 1, H, K], v: [B, 1, H, V]")
-    B, T, H, K = q.shape
-    V = v.shape[-1]
+    B, T, H, _ = q.shape
     if T != 1:
         raise ValueError(f"mhla_causal_step takes one token per call (T = 1), got T = {T}")
-    try:
-        _check_like(q, "mhla_causal_step", k=(k, q.shape), v=(v, (B, 1, H, V)), gate=(gate, (B, 1, H, V)))
-    except TypeError as e:
-        raise ValueError(str(e)) from None
-    if q.dtype not in _DTYPES:
-        raise ValueError(f"mhla_causal_step: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
-    if tuple(state.S.shape) != (B, H, state.capacity_chunks, K, V) or tuple(state.P.shape) != (B, H, K, V) or tuple(state.Cur.shape) != (B, H, K, V):
-        raise ValueError(f"mhla_causal_step: state is {state!r}, the token has B={B} H={H} K={K} V={V}")
-    for name, t in (("state.S", state.S), ("state.P", state.P), ("state.Cur", state.Cur), ("mixing_matrix", mixing_matrix), ("norm_weight", norm_weight)):
-        if t is not None and t.device != q.device:
-            raise ValueError(f"mhla_causal_step: {name} is on {t.device}, expected {q.device}")
-    if norm_weight is not None and norm_weight.numel() != V:
-        raise ValueError(f"mhla_causal_step: norm_weight has {norm_weight.numel()} entries, expected V={V}")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, gate)):
-        raise RuntimeError("mhla_causal_step is inference only: call it under torch.no_grad() (an input requires grad)")
-    _require_gpu(q, k, v, mixing_matrix)
-    L = mixing_matrix.shape[0]
-    if mixing_matrix.dim() < 2 or mixing_matrix.shape[1] < min(L, state.capacity_chunks):
-        raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
-    pos = state.seen
-    n = pos // state.chunk_size + 1
-    if n > L:
-        raise IndexError(f"sequence of {pos + 1} tokens needs {n} chunks but mixing_matrix has only {L} rows")
-    if n > state.capacity_chunks:
-        raise IndexError(f"sequence of {pos + 1} tokens needs {n} chunks but the state holds only {state.capacity_chunks}")
-    if scale is None:
-        scale = K ** -0.5
-    want_y = bool(epilogue) if epilogue is not None else (gate is not None or norm_weight is not None)
-    if not want_y and (gate is not None or norm_weight is not None):
-        raise ValueError("mhla_causal_step: gate / norm_weight given with epilogue=False")
-    with torch.no_grad():
-        q, k, v = (t if _step_view_ok(t) else t.contiguous() for t in (q, k, v))
-        if gate is not None and not _step_view_ok(gate):
-            gate = gate.contiguous()
-        mixf = _mix2d(mixing_matrix)
-        wf = norm_weight.detach().reshape(V).to(torch.float32).contiguous() if norm_weight is not None else None
-        if not (state.S.is_contiguous() and state.P.is_contiguous() and state.Cur.is_contiguous()):
-            raise ValueError("mhla_causal_step: state tensors must be contiguous")
-        res = _causal_step(q, k, v, mixf, state, pos, scale, gate, wf, norm_eps, want_y)
-    state.seen = pos + 1
+    prepared = _decode_prepare("mhla_causal_step", q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue)
+    res = _alloc_like_tokens(B, 1, H, v.shape[-1], q)
+    _causal_decode(*prepared, "mhla_causal_step", state, res, norm_eps)
+    state.seen += 1
     return res
 
 
 # Largest workspace one launch chain of `mhla_causal_extend` takes: a longer extension is cut into consecutive calls.  Per (b, h)
 # the chain needs 4 K V bytes per chunk touched after the first and 4 V bytes per token (mhla_hip.h).
 EXTEND_WS_CAP_BYTES = 256 << 20
-
-
-@_device_guard
-def _causal_extend(q, k, v, mixf, state, pos, scale, gate, wf, norm_eps, want_y, res):
-    lib = _lib.load()
-    B, T, H, K = q.shape
-    V = v.shape[-1]
-    dt = _dtype_code(q)
-    ws = _ws(lib.mhla_causal_extend_ws_bytes(B, T, H, K, V, pos, dt), q.device)
-    rc = lib.mhla_causal_extend(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-                                state.P.data_ptr(), state.Cur.data_ptr(), pos, T, NULL_VIEW if want_y else _view(res),
-                                _view(gate) if gate is not None else NULL_VIEW, wf.data_ptr() if wf is not None else None,
-                                float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K, V,
-                                state.chunk_size, float(scale), dt, _stream())
-    _lib.check(rc, "mhla_causal_extend")
 
 
 def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
@@ -1417,60 +1359,22 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     if T == 1:
         return mhla_causal_step(q, k, v, mixing_matrix, state, scale=scale, gate=gate, norm_weight=norm_weight, norm_eps=norm_eps,
                                 epilogue=epilogue)
-    try:
-        _check_like(q, "mhla_causal_extend", k=(k, q.shape), v=(v, (B, T, H, V)), gate=(gate, (B, T, H, V)))
-    except TypeError as e:
-        raise ValueError(str(e)) from None
-    if q.dtype not in _DTYPES:
-        raise ValueError(f"mhla_causal_extend: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
-    if tuple(state.S.shape) != (B, H, state.capacity_chunks, K, V) or tuple(state.P.shape) != (B, H, K, V) or tuple(state.Cur.shape) != (B, H, K, V):
-        raise ValueError(f"mhla_causal_extend: state is {state!r}, the tokens have B={B} H={H} K={K} V={V}")
-    for name, t in (("state.S", state.S), ("state.P", state.P), ("state.Cur", state.Cur), ("mixing_matrix", mixing_matrix), ("norm_weight", norm_weight)):
-        if t is not None and t.device != q.device:
-            raise ValueError(f"mhla_causal_extend: {name} is on {t.device}, expected {q.device}")
-    if norm_weight is not None and norm_weight.numel() != V:
-        raise ValueError(f"mhla_causal_extend: norm_weight has {norm_weight.numel()} entries, expected V={V}")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, gate)):
-        raise RuntimeError("mhla_causal_extend is inference only: call it under torch.no_grad() (an input requires grad)")
-    _require_gpu(q, k, v, mixing_matrix)
-    L = mixing_matrix.shape[0]
-    if mixing_matrix.dim() < 2 or mixing_matrix.shape[1] < min(L, state.capacity_chunks):
-        raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
-    if int(state.chunk_size) != 64:
-        raise ValueError(f"mhla_causal_extend: chunk_size={state.chunk_size}, the decode state supports 64 only")
-    pos = state.seen
-    n = (pos + T + 63) // 64
-    if n > L:
-        raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but mixing_matrix has only {L} rows")
-    if n > state.capacity_chunks:
-        raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but the state holds only {state.capacity_chunks}")
-    if scale is None:
-        scale = K ** -0.5
-    want_y = bool(epilogue) if epilogue is not None else (gate is not None or norm_weight is not None)
-    if not want_y and (gate is not None or norm_weight is not None):
-        raise ValueError("mhla_causal_extend: gate / norm_weight given with epilogue=False")
-    if not (state.S.is_contiguous() and state.P.is_contiguous() and state.Cur.is_contiguous()):
-        raise ValueError("mhla_causal_extend: state tensors must be contiguous")
-    with torch.no_grad():
-        q, k, v = (t if _step_view_ok(t) else t.contiguous() for t in (q, k, v))
-        if gate is not None and not _step_view_ok(gate):
-            gate = gate.contiguous()
-        mixf = _mix2d(mixing_matrix)
-        wf = norm_weight.detach().reshape(V).to(torch.float32).contiguous() if norm_weight is not None else None
-        res = torch.empty((B, T, H, V), dtype=q.dtype, device=q.device)
-        nb = min(B, _MAX_GRID_BH // H)
-        # tokens per call: whole chunks, so that nb H (K V / 64 + V) 4 bytes per token stay under the cap (and under the C ABI's 65535)
-        per_tok = nb * H * (K * V // 64 + V) * 4
-        step_t = min(max(64, EXTEND_WS_CAP_BYTES // per_tok // 64 * 64), 65472)
-        for i in range(0, B, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
-            part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], pos, 64)
-            t0 = 0
-            while t0 < T:
-                # the first piece fills the open chunk, so that every later one starts on a boundary
-                t1 = min(T, t0 + step_t - (pos + t0) % 64)
-                sl = lambda x: None if x is None else x[i:i + nb, t0:t1]
-                _causal_extend(sl(q), sl(k), sl(v), mixf, part, pos + t0, scale, sl(gate), wf, norm_eps, want_y, sl(res))
-                t0 = t1
+    q, k, v, gate, mixf, wf, pos, scale, want_y = _decode_prepare("mhla_causal_extend", q, k, v, mixing_matrix, state, scale, gate,
+                                                                  norm_weight, epilogue)
+    res = _alloc_like_tokens(B, T, H, V, q)
+    nb = min(B, _MAX_GRID_BH // H)
+    # tokens per call: whole chunks, so that nb H (K V / 64 + V) 4 bytes per token stay under the cap (and under the C ABI's 65535)
+    per_tok = nb * H * (K * V // 64 + V) * 4
+    step_t = min(max(64, EXTEND_WS_CAP_BYTES // per_tok // 64 * 64), 65472)
+    for i in range(0, B, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
+        part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], pos, 64)
+        t0 = 0
+        while t0 < T:
+            # the first piece fills the open chunk, so that every later one starts on a boundary
+            t1 = min(T, t0 + step_t - (pos + t0) % 64)
+            sl = lambda x: None if x is None else x[i:i + nb, t0:t1]
+            _causal_decode(sl(q), sl(k), sl(v), sl(gate), mixf, wf, pos + t0, scale, want_y, "mhla_causal_extend", part, sl(res), norm_eps)
+            t0 = t1
     state.seen = pos + T
     return res
 
@@ -1478,6 +1382,22 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
 # ------------------------------------------------------------------------------------------
 # per-head RMSNorm x swish gate
 # ------------------------------------------------------------------------------------------
+def _rmsnorm_gate_bwd(x, g, wf, dy, eps, w_dtype):
+    """mhla_rmsnorm_gate_bwd over the rows of x [..., D] (x and the gate g contiguous, g / the fp32 weight wf may be None):
+    (dx, dg, dw), dw summed from the kernel's fp32 partial rows and cast to the weight's dtype."""
+    lib = _lib.load()
+    D = x.shape[-1]
+    rows = x.numel() // D
+    dyc = dy.contiguous().to(x.dtype)
+    dx = torch.empty_like(x)
+    dg = torch.empty_like(x) if g is not None else None
+    dwp = torch.empty((lib.mhla_rmsnorm_gate_dw_rows(rows), D), dtype=torch.float32, device=x.device)
+    rc = lib.mhla_rmsnorm_gate_bwd(x.data_ptr(), D, _ptr(g), D, _ptr(wf), dyc.data_ptr(), D, dx.data_ptr(), D, _ptr(dg), D,
+                                   dwp.data_ptr(), rows, D, eps, _dtype_code(x), _stream())
+    _lib.check(rc, "mhla_rmsnorm_gate_bwd")
+    return dx, dg, (dwp.sum(0).to(w_dtype) if wf is not None else None)
+
+
 class _RmsNormGate(torch.autograd.Function):
     @staticmethod
     @_device_guard
@@ -1487,11 +1407,10 @@ class _RmsNormGate(torch.autograd.Function):
         D = x.shape[-1]
         xc = x.contiguous()
         gc = g.contiguous().to(x.dtype) if g is not None else None
-        wf = weight.detach().to(torch.float32).contiguous() if weight is not None else None
+        wf = _f32(weight)
         rows = xc.numel() // D
         y = torch.empty_like(xc)
-        rc = lib.mhla_rmsnorm_gate_fwd(xc.data_ptr(), D, gc.data_ptr() if gc is not None else None, D,
-                                       wf.data_ptr() if wf is not None else None, y.data_ptr(), D, None, rows, D,
+        rc = lib.mhla_rmsnorm_gate_fwd(xc.data_ptr(), D, _ptr(gc), D, _ptr(wf), y.data_ptr(), D, None, rows, D,
                                        float(eps), _dtype_code(xc), _stream())
         _lib.check(rc, "mhla_rmsnorm_gate_fwd")
         ctx.save_for_backward(xc, gc, wf)
@@ -1501,23 +1420,9 @@ class _RmsNormGate(torch.autograd.Function):
     @staticmethod
     @_device_guard
     def backward(ctx, dy):
-        lib = _lib.load()
         xc, gc, wf = ctx.saved_tensors
-        eps, wdtype = ctx.cfg
-        D = xc.shape[-1]
-        rows = xc.numel() // D
-        dyc = dy.contiguous().to(xc.dtype)
-        dx = torch.empty_like(xc)
-        dg = torch.empty_like(xc) if gc is not None else None
-        nrows = lib.mhla_rmsnorm_gate_dw_rows(rows)
-        dwp = torch.empty((nrows, D), dtype=torch.float32, device=xc.device)
-        rc = lib.mhla_rmsnorm_gate_bwd(xc.data_ptr(), D, gc.data_ptr() if gc is not None else None, D,
-                                       wf.data_ptr() if wf is not None else None, dyc.data_ptr(), D, dx.data_ptr(), D,
-                                       dg.data_ptr() if dg is not None else None, D, dwp.data_ptr(), rows, D, eps,
-                                       _dtype_code(xc), _stream())
-        _lib.check(rc, "mhla_rmsnorm_gate_bwd")
-        dw = dwp.sum(0).to(wdtype) if wf is not None else None
-        return dx, dg, dw, None
+        eps, w_dtype = ctx.cfg
+        return (*_rmsnorm_gate_bwd(xc, gc, wf, dy, eps, w_dtype), None)
 
 
 def rmsnorm_gate(x: torch.Tensor, g: Optional[torch.Tensor], weight: Optional[torch.Tensor],

@@ -407,6 +407,38 @@ def test_full_state_and_errors():
     assert torch.equal(st.S, snap.S) and torch.equal(st.Cur, snap.Cur) and torch.equal(st.P, snap.P)
 
 
+@pytest.mark.parametrize("name,T", [("mhla_causal_step", 1), ("mhla_causal_extend", 5)])
+def test_checks_behind_the_device_check_refuse_before_launch(name, T):
+    """The argument checks of step and extend that only GPU tensors reach (tests/test_decode_validation_cpu.py holds the others):
+    epilogue arguments with epilogue=False, a state that is not contiguous, a state of another chunk size.  Each is a ValueError
+    naming the function called -- for the chunk size too, which the step used to leave to the library (RuntimeError) -- and
+    leaves the state as it was; nothing is launched."""
+    import mhla_amd
+    fn = getattr(mhla_amd, name)
+    B, H, K, V, cap = 1, 2, 16, 24, 3
+    q, k, v = torch.zeros(B, T, H, K, device=DEV), torch.zeros(B, T, H, K, device=DEV), torch.ones(B, T, H, V, device=DEV)
+    mix = torch.ones(cap, cap, device=DEV)
+
+    def refused(state, match, **kw):
+        before = [t.clone() for t in (state.S, state.P, state.Cur)]
+        with pytest.raises(ValueError, match=match):
+            fn(q, k, v, mix, state, **kw)
+        assert state.seen == 7 and all(torch.equal(a, b) for a, b in zip(before, (state.S, state.P, state.Cur)))
+
+    def fresh(chunk_size=64):
+        s = mhla_amd.CausalState.empty(B, H, K, V, cap, DEV, chunk_size=chunk_size)
+        s.seen = 7
+        s.Cur.fill_(0.5)
+        return s
+
+    refused(fresh(), f"{name}: gate / norm_weight given with epilogue=False", gate=torch.ones_like(v), epilogue=False)
+    strided = fresh()
+    strided.S = torch.full((B, H, cap, K, 2 * V), 0.25, device=DEV)[..., ::2]
+    assert strided.S.shape == (B, H, cap, K, V) and not strided.S.is_contiguous()
+    refused(strided, f"{name}: state tensors must be contiguous")
+    refused(fresh(chunk_size=32), f"{name}: chunk_size=32, the decode state supports 64 only")
+
+
 def _launches(fn):
     """Kernel launches of the library while `fn` runs: {name: count} (mhla_prof_*)."""
     from mhla_amd import _lib

@@ -1,6 +1,9 @@
 #!/usr/bin/env python
 """Where the host time of an eager operator call goes (cProfile over many un-synchronised fwd+bwd calls of the C3 shape):
-python tools/host_overhead.py [iters]"""
+python tools/host_overhead.py [iters] [--python-nodes] [--causal]
+--python-nodes: the autograd nodes of ops.py (ops.USE_NATIVE_NODES = False) instead of the C++ ones, where those are built.
+--causal: the same loop on mhla_causal (B = 2, T = 512, H = 2, K = 64, V = 128, bf16) instead of mhla_blockmix."""
+import argparse
 import cProfile
 import os
 import pstats
@@ -11,19 +14,37 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import mhla_amd  # noqa: E402
+from mhla_amd import ops  # noqa: E402
 from mhla_amd.weights import block_distance_weights  # noqa: E402
 
-iters = int(sys.argv[1]) if len(sys.argv) > 1 else 300
-B, N, H, D, M = 32, 256, 16, 72, 16
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("iters", nargs="?", type=int, default=300)
+ap.add_argument("--python-nodes", action="store_true")
+ap.add_argument("--causal", action="store_true")
+a = ap.parse_args()
+iters = a.iters
+if a.python_nodes:
+    ops.USE_NATIVE_NODES = False
 g = torch.Generator().manual_seed(0)
-mk = lambda: (torch.rand(B, N, H, D, generator=g) + 0.01).to(torch.bfloat16).cuda().requires_grad_(True)
-q, k, v = mk(), mk(), mk()
-W = block_distance_weights((4, 4), "linear").cuda().requires_grad_(True)
-do = torch.randn(B, N, H, D, generator=g).to(torch.bfloat16).cuda()
+if a.causal:
+    B, T, H, K, V = 2, 512, 2, 64, 128
+    mk = lambda D: torch.randn(B, T, H, D, generator=g).to(torch.bfloat16).cuda().requires_grad_(True)
+    q, k, v = mk(K), mk(K), mk(V)
+    W = mhla_amd.causal_mixing_init(T // 64).reshape(T // 64, T // 64).cuda().requires_grad_(True)
+    do = torch.randn(B, T, H, V, generator=g).to(torch.bfloat16).cuda()
+    op = mhla_amd.mhla_causal
+else:
+    B, N, H, D, M = 32, 256, 16, 72, 16
+    mk = lambda: (torch.rand(B, N, H, D, generator=g) + 0.01).to(torch.bfloat16).cuda().requires_grad_(True)
+    q, k, v = mk(), mk(), mk()
+    W = block_distance_weights((4, 4), "linear").cuda().requires_grad_(True)
+    do = torch.randn(B, N, H, D, generator=g).to(torch.bfloat16).cuda()
+    op = mhla_amd.mhla_blockmix
+print(f"{op.__name__}, {'C++' if ops._native_nodes() else 'Python'} autograd nodes")
 
 
 def step():
-    out = mhla_amd.mhla_blockmix(q, k, v, W)
+    out = op(q, k, v, W)
     out.backward(do)
 
 
