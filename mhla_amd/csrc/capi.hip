@@ -166,9 +166,8 @@ HandoverWatch g_watch;
 // rotary prologue) the dispatcher clears it with a 4-byte memset -- so mhla_blockmix_bwd_status never reads an unrelated word
 // (round-3 ADVICE: it used to infer the path from the shape alone).
 size_t bwd_ws_body_bytes(int B, int H, int M, int S, int D, int dtype, int split, unsigned flags) {
-    const size_t gen = bm_carve(nullptr, B, H, M, S, D, bm_sumfmt(M, S, D, dtype, flags), sp_shape_ok(D, flags), bm_olo(M, S, D, dtype, flags)).total_bwd;
-    const bool fast = fast_shape_ok(M, D, dtype, split != 0, flags) && !(flags & MHLA_FLAG_FORCE_GENERIC);
-    return (std::max(gen, fast ? fast_carve(nullptr, B, H, M, S).total_bwd : (size_t)0) + 15) & ~(size_t)15;
+    const size_t gen = bm_carve_for(nullptr, B, H, M, S, D, dtype, flags, false).total_bwd;
+    return (std::max(gen, bm_fast_layout(M, S, D, dtype, split != 0, flags) ? fast_carve(nullptr, B, H, M, S).total_bwd : (size_t)0) + 15) & ~(size_t)15;
 }
 int* bwd_err_word(void* ws, int B, int H, int M, int S, int D, int dtype, int split, unsigned flags) {
     return (int*)((char*)ws + bwd_ws_body_bytes(B, H, M, S, D, dtype, split, flags));
@@ -247,24 +246,161 @@ void mhla_debug_set_trace(void* buf) { g_trace = (unsigned long long*)buf; }
 // backward), 0 when the forward is stateless (generic recompute / small-sequence path).
 int mhla_blockmix_fwd_keeps_state(int B, int H, int M, int S, int D, int dtype, int split, unsigned flags) {
     (void)B; (void)H;
-    if (flags & MHLA_FLAG_FORCE_GENERIC) return 0;
-    if ((sn_shape_ok(M, S, D, dtype, split != 0) || snf_shape_ok(M, S, D, dtype, split != 0)) && !(flags & MHLA_FLAG_NO_SMALLN)) return 0;
-    if (fast_shape_ok(M, D, dtype, split != 0, flags)) return 1;
-    return sp_shape_ok(D, flags) ? 1 : 0;   // split-operand path: KV, G, z, ksum, 1/n (fp32)
+    switch (bm_route(M, S, D, dtype, split != 0, flags)) {
+        case BM_SNF: case BM_SN: return 0;
+        case BM_FAST: return 1;
+        default: return sp_shape_ok(D, flags) ? 1 : 0;   // split-operand path: KV, G, z, ksum, 1/n (fp32)
+    }
 }
 
 // Upper bound over the paths the library may take for this problem (the fast path needs less).
 // (the fast path needs less than the split-operand path, but which one runs also depends on the alignment of the views, which
 // these queries do not see: the bound covers both)
-// (MHLA_FLAG_NO_BWD_STATE: the forward neither writes nor carves the O-residual region)
-static bool fwd_olo(int M, int S, int D, int dtype, unsigned flags) { return bm_olo(M, S, D, dtype, flags) && !(flags & MHLA_FLAG_NO_BWD_STATE); }
 size_t mhla_blockmix_fwd_ws_bytes(int B, int H, int M, int S, int D, int dtype, int split, unsigned flags) {
-    const size_t gen = bm_carve(nullptr, B, H, M, S, D, bm_sumfmt(M, S, D, dtype, flags), sp_shape_ok(D, flags), fwd_olo(M, S, D, dtype, flags)).total_fwd;
-    if (fast_shape_ok(M, D, dtype, split != 0, flags) && !(flags & MHLA_FLAG_FORCE_GENERIC)) return std::max(gen, fast_carve(nullptr, B, H, M, S).total_fwd);
-    return gen;
+    const size_t gen = bm_carve_for(nullptr, B, H, M, S, D, dtype, flags, true).total_fwd;
+    return bm_fast_layout(M, S, D, dtype, split != 0, flags) ? std::max(gen, fast_carve(nullptr, B, H, M, S).total_fwd) : gen;
 }
 size_t mhla_blockmix_bwd_ws_bytes(int B, int H, int M, int S, int D, int dtype, int split, unsigned flags) {
     return bwd_ws_body_bytes(B, H, M, S, D, dtype, split, flags) + 16;   // + the error word of the fused token-gradient launch
+}
+
+// what every block-mix entry point hands on: the call as validated so far (c.w: carved by the family that runs)
+static BmCall bm_call(mhla_view q_num, mhla_view k_num, mhla_view v, mhla_view q_den, mhla_view k_den, const float* W, int ldw, const int32_t* block_index,
+                      int B, int H, int M, int S, int D, int dtype, float eps, unsigned flags, void* stream, const float* rcos, const float* rsin, long ldr) {
+    BmCall c{};
+    c.normalize = q_den.ptr != nullptr;
+    c.split = c.normalize && (q_den.ptr != q_num.ptr || k_den.ptr != k_num.ptr);
+    c.q_num = q_num; c.k_num = k_num; c.v = v; c.q_den = c.normalize ? q_den : q_num; c.k_den = c.normalize ? k_den : k_num;
+    c.W = W; c.ldw = ldw; c.block_index = block_index; c.B = B; c.H = H; c.M = M; c.S = S; c.D = D; c.dtype = dtype; c.eps = eps; c.flags = flags;
+    c.st = (hipStream_t)stream; c.rcos = rcos; c.rsin = rsin; c.ldr = ldr;
+    return c;
+}
+static int bm_typed(const BmCall& c, const bool FWD) {
+    switch (c.dtype) {
+        case MHLA_F32: return FWD ? bm_fwd_typed<float, false>(c) : bm_bwd_typed<float, false>(c);
+        case MHLA_BF16:
+            if (bm_sum16(c.D, c.dtype, c.flags)) return FWD ? bm_fwd_typed<bf16_t, true>(c) : bm_bwd_typed<bf16_t, true>(c);
+            return FWD ? bm_fwd_typed<bf16_t, false>(c) : bm_bwd_typed<bf16_t, false>(c);
+        case MHLA_F16: return FWD ? bm_fwd_typed<f16_t, false>(c) : bm_bwd_typed<f16_t, false>(c);
+        default: return fail(MHLA_EINVAL, "unknown dtype %d", c.dtype);
+    }
+}
+
+// ---- small-sequence families (smalln.hpp, smalln_f32.hpp): one launch per direction, dW partials [bh][M][M] in `dwp` (backward) ----
+static fast::SnArgs sn_args(const BmCall& c, void* dwp) {
+    fast::SnArgs sa{};
+    sa.q = cv(c.q_num); sa.k = cv(c.k_num); sa.v = cv(c.v); sa.idx = c.block_index; sa.W = c.W; sa.ldw = c.ldw;
+    sa.H = c.H; sa.M = c.M; sa.D = c.D; sa.eps = c.eps; sa.relu = c.relu(); sa.normalize = c.normalize;
+    if (!dwp) { sa.out = cmv(c.out); return sa; }
+    sa.o = c.normalize ? cv(c.outv) : cv(c.q_num); sa.dout = cv(c.dout); sa.dq = cmv(c.dq_num); sa.dk = cmv(c.dk_num); sa.dv = cmv(c.dv); sa.dwp = (float*)dwp;
+    return sa;
+}
+static int sn_fwd(const BmCall& c, BmRoute r) {
+    const fast::SnArgs sa = sn_args(c, nullptr);
+    const int M = c.M;
+    const bool hl = !(c.flags & MHLA_FLAG_BF16_SUMMARIES), g = sa.idx != nullptr, d4 = c.D <= 64;
+    const char* name = bm_sn_name(r, false, c.D, hl);
+    const dim3 grid(c.B * c.H);
+    if (r == BM_SN) {
+        if (d4) return launch(hl ? sn_fwd_kernel<4, true>(g, M) : sn_fwd_kernel<4, false>(g, M), grid, dim3(fast::SN_T), fast::sn_fwd_smem<4>(), c.st, name, sa);
+        return launch(hl ? sn_fwd_kernel<5, true>(g, M) : sn_fwd_kernel<5, false>(g, M), grid, dim3(fast::SN_T), fast::sn_fwd_smem<5>(), c.st, name, sa);
+    }
+    // fp32 tensors in the DiT / ViT regime: the attention-form kernels with hi + lo bf16 operands (smalln_f32.hpp)
+    if (d4) return launch(g ? fast::k_snf_fwd<4, true> : (M == 16 ? fast::k_snf_fwd<4, false, true> : fast::k_snf_fwd<4, false>), grid, dim3(fast::SNF_T), fast::snf_smem<4>(), c.st, name, sa);
+    return launch(g ? fast::k_snf_fwd<5, true> : (M == 16 ? fast::k_snf_fwd<5, false, true> : fast::k_snf_fwd<5, false>), grid, dim3(fast::SNF_T), fast::snf_smem<5>(), c.st, name, sa);
+}
+static int sn_bwd(const BmCall& c, BmRoute r, void* ws, size_t ws_bytes) {
+    const int M = c.M, BH = c.B * c.H;
+    const size_t need = (size_t)BH * M * M * 4;
+    if (ws_bytes < need) return ws_too_small(ws_bytes, need);
+    fast::SnArgs sa = sn_args(c, ws);
+    const bool hl = !(c.flags & MHLA_FLAG_BF16_SUMMARIES), g = sa.idx != nullptr, d4 = c.D <= 64;
+    const char* name = bm_sn_name(r, true, c.D, hl);
+    if (r == BM_SN) {
+        sa.trace = g_trace.load();
+        const int nth = hl ? fast::SN_TB * (3 - SN_BWD_NB) : fast::SN_TB;
+        if (d4) RC(launch(hl ? sn_bwd_kernel<4, true>(g, M) : sn_bwd_kernel<4, false>(g, M), dim3(BH), dim3(nth), hl ? fast::sn_bwd_smem<4, SN_BWD_NB>() : fast::sn_bwd_smem<4>(), c.st, name, sa));
+        else    RC(launch(hl ? sn_bwd_kernel<5, true>(g, M) : sn_bwd_kernel<5, false>(g, M), dim3(BH), dim3(nth), hl ? fast::sn_bwd_smem<5, SN_BWD_NB>() : fast::sn_bwd_smem<5>(), c.st, name, sa));
+    } else if (d4) RC(launch(g ? fast::k_snf_bwd<4, true> : (M == 16 ? fast::k_snf_bwd<4, false, true> : fast::k_snf_bwd<4, false>), dim3(BH), dim3(fast::SNF_T), fast::snf_smem<4>(), c.st, name, sa));
+    else           RC(launch(g ? fast::k_snf_bwd<5, true> : (M == 16 ? fast::k_snf_bwd<5, false, true> : fast::k_snf_bwd<5, false>), dim3(BH), dim3(fast::SNF_T), fast::snf_smem<5>(), c.st, name, sa));
+    return launch(fast::k_sn_dw_reduce, dim3(M * M), dim3(256), 0, c.st, N_SN_DW_REDUCE, (const float*)ws, c.dW, M * M, BH);
+}
+
+// ---- bf16 fast path (fused.hpp, fused_tile16.hpp) ----
+// its summaries KV^T, ksum, z and 1 / n: the forward, and the recompute leg of a backward that was handed no forward workspace
+static int fast_summaries(const BmCall& c, const FastWs& f) {
+    const int BH = c.B * c.H, S = c.S;
+    fast::FsStateArgs sa{};
+    sa.x = cv(c.k_num); sa.y = cv(c.v); sa.t = cv(c.q_num); sa.idx = c.block_index; sa.state = f.state; sa.ksum = f.ksum;
+    sa.z_out = f.z; sa.H = c.H; sa.M = c.M; sa.S = S; sa.eps = c.eps; sa.relu = c.relu(); sa.normalize = c.normalize;
+    if (S <= 64) RC(launch_state1c<0>(sa, f.njg, BH, c.st, N_FS_STATE[0]));
+    else RC(launch(fast::k_fs_state_fwd<0>, dim3(f.njg, BH), dim3(fast::FT8), fast::FS_STATE_FWD_SMEM, c.st, N_FS_STATE[0], sa));
+    if (c.normalize)
+        RC(launch(fast::k_fs_wz<0>, dim3((S + fast::WZ_C - 1) / fast::WZ_C, BH), dim3(fast::FT), 0, c.st, N_FS_WZ, c.W, c.ldw, (const float*)f.z, f.ninv, c.M, S, c.eps));
+    return MHLA_OK;
+}
+static int fast_fwd(const BmCall& c, void* ws, size_t ws_bytes) {
+    const int B = c.B, H = c.H, M = c.M, S = c.S;
+    const FastWs f = fast_carve(ws, B, H, M, S);
+    if (ws_bytes < f.total_fwd) return ws_too_small(ws_bytes, f.total_fwd);
+    RC(fast_summaries(c, f));
+    fast::FsOutArgs oa{};
+    oa.q = cv(c.q_num); oa.o = cmv(c.out); oa.idx = c.block_index; oa.W = c.W; oa.ldw = c.ldw; oa.state = f.state; oa.ninv = f.ninv;
+    oa.H = H; oa.M = M; oa.S = S; oa.njg = f.njg; oa.eps = c.eps; oa.relu = c.relu(); oa.normalize = c.normalize;
+    oa.trace = g_trace.load();
+    oa.cs = f.cs;
+    if (f.cs > 1) return launch(fast::k_tile_out<16, true>, dim3(fast::tiles_per_bh(f.njg, 16) * B * H * f.cs), dim3(fast::FT8), fast::tile_smem<16>(), c.st, N_T16_OUT, oa);
+    return launch(fast::k_tile_out<16>, dim3(fast::tiles_per_bh(f.njg, 16) * B * H), dim3(fast::FT8), fast::tile_smem<16>(), c.st, N_T16_OUT, oa);
+}
+static int fast_bwd(const BmCall& c, void* ws, size_t ws_bytes, const void* fwd_ws, int* err_word) {
+    const int B = c.B, H = c.H, M = c.M, S = c.S;
+    const bool normalize = c.normalize;
+    hipStream_t st = c.st;
+    FastWs f = fast_carve(ws, B, H, M, S);
+    const size_t need = mhla_blockmix_bwd_ws_bytes(B, H, M, S, c.D, c.dtype, c.split, c.flags);
+    if (ws_bytes < need) return ws_too_small(ws_bytes, need);
+    f.err = err_word;
+    const fast::u16* state = f.state;
+    const float *z = f.z, *ksum = f.ksum, *ninv = f.ninv;
+    if (fwd_ws) {   // forward workspace retained by the caller: reuse KV^T, z, ksum, 1/n
+        const FastWs ff = fast_carve(const_cast<void*>(fwd_ws), B, H, M, S);
+        state = ff.state; z = ff.z; ksum = ff.ksum; ninv = ff.ninv;
+    } else {
+        RC(fast_summaries(c, f));
+    }
+    fast::FsStateArgs ga{};
+    ga.x = cv(c.q_num); ga.y = cv(c.dout); ga.t = cv(c.outv); ga.idx = c.block_index; ga.W = c.W; ga.ldw = c.ldw; ga.ninv = ninv;
+    ga.state = f.dstate; ga.dn = f.dn; ga.H = H; ga.M = M; ga.S = S; ga.eps = c.eps; ga.relu = c.relu(); ga.normalize = normalize;
+    if (S <= 64) RC(launch_state1c<1>(ga, f.njg, B * H, st, N_FS_STATE[1]));
+    else RC(launch(fast::k_fs_state<1>, dim3(f.njg, B * H), dim3(fast::FT8), fast::FS_STATE_SMEM, st, N_FS_STATE[1], ga));
+    // dW needs only dG^T, KV^T, dn and z, all complete here; dz = W^T dn (needed by the token-gradient kernels) rides in
+    // the same launch as extra workgroups
+    fast::FsDwArgs da{f.dstate, state, normalize ? f.dn : nullptr, z, f.dwp, M, S, f.njg, c.W, c.ldw, f.dz, f.done, f.err, f.ntt * f.cs};
+    const int nwz = normalize ? (S + fast::WZ_C - 1) / fast::WZ_C : 0;
+    RC(launch(fast::k_fs_dw<>, dim3(fast::DW_SPLIT + nwz, B * H), dim3(fast::FT8), fast::FS_DW_SMEM, st, N_FS_DW, da));
+    fast::FsTokArgs ta{};
+    ta.q = cv(c.q_num); ta.k = cv(c.k_num); ta.v = cv(c.v); ta.dout = cv(c.dout); ta.dq = cmv(c.dq_num); ta.dk = cmv(c.dk_num);
+    ta.dv = cmv(c.dv); ta.idx = c.block_index; ta.W = c.W; ta.ldw = c.ldw; ta.state = state; ta.dstate = f.dstate; ta.ninv = ninv;
+    ta.dz = f.dz; ta.ksum = ksum; ta.H = H; ta.M = M; ta.S = S; ta.njg = f.njg; ta.eps = c.eps; ta.relu = c.relu();
+    ta.normalize = normalize;
+    ta.dksum = f.dksum;
+    const long ntile_wgs = (long)f.ntt * B * H * f.cs;
+    ta.cs = f.cs; ta.dks_part = (long)al4((size_t)B * H * M * 64);
+    unsigned long long* tr = g_trace.load();   // regions: [0] k_t16_out, [1] dQ role, [2] dK/dV role (record = ntiles + blockIdx.x)
+    ta.trace = tr ? tr + ntile_wgs * fast::TRACE_SLOTS : nullptr;
+    ta.dwp = f.dwp; ta.dW = c.dW; ta.nparts = B * H * fast::DW_SPLIT; ta.ntiles = (int)ntile_wgs; ta.done = f.done;
+    ta.err = f.err;
+    ta.drop_signal = g_drop_signal.load();   // testing aid for the bounded wait (mhla_set_option)
+    g_watch.check(st);                        // did an earlier fused launch of this process report an expired hand-over?
+    const auto tile_bwd = f.cs > 1 ? fast::k_tile_bwd<16, true> : fast::k_tile_bwd<16, false>;   // (multi-chunk blocks: cs workgroups per tile)
+    if (g_two_launches.load()) {   // (the kernel boundary orders dksum and the flags: the wait returns at its first poll)
+        RC(launch(tile_bwd, dim3((unsigned)ntile_wgs), dim3(fast::FT8), fast::tile_smem<16>(), st, "k_t16_bwd_dq", ta));
+        ta.x0 = (int)ntile_wgs;
+        return launch(tile_bwd, dim3((unsigned)ntile_wgs + fast::DWR_WGS), dim3(fast::FT8), fast::tile_smem<16>(), st, "k_t16_bwd_dkv", ta);
+    }
+    RC(launch(tile_bwd, dim3((unsigned)(2 * ntile_wgs) + fast::DWR_WGS), dim3(fast::FT8), fast::tile_smem<16>(), st, N_T16_BWD, ta));
+    if (normalize) g_watch.watch(f.err, st);
+    return MHLA_OK;
 }
 
 static int bm_fwd_impl(mhla_view q_num, mhla_view k_num, mhla_view v, mhla_view q_den, mhla_view k_den, const float* W,
@@ -272,73 +408,24 @@ static int bm_fwd_impl(mhla_view q_num, mhla_view k_num, mhla_view v, mhla_view 
                        int M, int S, int D, int dtype, float eps, unsigned flags, void* stream, const float* rcos,
                        const float* rsin, long ldr, bool epi = false, const float* nw = nullptr, float neps = 0.f,
                        mhla_view gate = mhla_view{nullptr, 0, 0, 0}, int out_dtype = 0) {
-    const bool normalize = q_den.ptr != nullptr;
-    const bool split = normalize && (q_den.ptr != q_num.ptr || k_den.ptr != k_num.ptr);
-    RC(bm_check(B, H, M, S, D, dtype, flags, normalize, split));
+    BmCall c = bm_call(q_num, k_num, v, q_den, k_den, W, ldw, block_index, B, H, M, S, D, dtype, eps, flags, stream, rcos, rsin, ldr);
+    RC(bm_check(B, H, M, S, D, dtype, flags, c.split));
     CHECK_VIEW(q_num); CHECK_VIEW(k_num); CHECK_VIEW(v); CHECK_VIEW(out);
-    if (normalize) { CHECK_VIEW(q_den); CHECK_VIEW(k_den); }
+    if (c.normalize) { CHECK_VIEW(q_den); CHECK_VIEW(k_den); }
     if (!W || ldw < M) return fail(MHLA_EINVAL, "W null or ldw=%d < M=%d", ldw, M);
     if (!ws || ((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace null or not 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (!normalize) { q_den = q_num; k_den = k_num; }
-    const int relu = (flags & MHLA_FLAG_RELU_EPS) ? 1 : 0;
-    const mhla_view outv{out.ptr, out.sb, out.sn, out.sh};
     if (epi && (!sp_shape_ok(D, flags) || dtype != MHLA_F32))
         return fail(MHLA_ENOTSUP, "fused norm/gate epilogue needs fp32 q, k, v, D %% 8 == 0 and the split-operand kernels (D=%d, dtype=%d)", D, dtype);
     if (rcos && !sp_shape_ok(D, flags)) return fail(MHLA_ENOTSUP, "fused rotary prologue needs D %% 8 == 0 and the split-operand kernels (D=%d, flags=%u)", D, flags);
-    if (!rcos && !epi && sn_shape_ok(M, S, D, dtype, split) && !(flags & (MHLA_FLAG_FORCE_GENERIC | MHLA_FLAG_NO_SMALLN)) && view_ok16(q_num) &&
-        view_ok16(k_num) && view_ok16(v) && view_ok16(outv)) {
-        fast::SnArgs sa{};
-        sa.q = cv(q_num); sa.k = cv(k_num); sa.v = cv(v); sa.out = cmv(out); sa.idx = block_index; sa.W = W; sa.ldw = ldw;
-        sa.H = H; sa.M = M; sa.D = D; sa.eps = eps; sa.relu = relu; sa.normalize = normalize;
-        const bool hl = !(flags & MHLA_FLAG_BF16_SUMMARIES), g = sa.idx != nullptr;
-        if (D <= 64) RC(launch(hl ? sn_fwd_kernel<4, true>(g, M) : sn_fwd_kernel<4, false>(g, M), dim3(B * H), dim3(fast::SN_T), fast::sn_fwd_smem<4>(), st, hl ? "k_sn_fwd<4,hl>" : "k_sn_fwd<4>", sa));
-        else         RC(launch(hl ? sn_fwd_kernel<5, true>(g, M) : sn_fwd_kernel<5, false>(g, M), dim3(B * H), dim3(fast::SN_T), fast::sn_fwd_smem<5>(), st, hl ? "k_sn_fwd<5,hl>" : "k_sn_fwd<5>", sa));
-        return MHLA_OK;
+    c.out = out; c.epi = epi; c.gate = gate; c.nw = nw; c.neps = neps; c.out_dtype = out_dtype;
+    switch (const BmRoute r = bm_call_route(c, false)) {
+        case BM_SN: case BM_SNF: return sn_fwd(c, r);
+        case BM_FAST: return fast_fwd(c, ws, ws_bytes);
+        default: break;
     }
-    if (!rcos && !epi && snf_shape_ok(M, S, D, dtype, split) && !(flags & (MHLA_FLAG_FORCE_GENERIC | MHLA_FLAG_NO_SMALLN)) && view_ok16(q_num) &&
-        view_ok16(k_num) && view_ok16(v) && view_ok16(outv)) {
-        // fp32 tensors in the DiT / ViT regime: the attention-form kernels with hi + lo bf16 operands (smalln_f32.hpp)
-        fast::SnArgs sa{};
-        sa.q = cv(q_num); sa.k = cv(k_num); sa.v = cv(v); sa.out = cmv(out); sa.idx = block_index; sa.W = W; sa.ldw = ldw;
-        sa.H = H; sa.M = M; sa.D = D; sa.eps = eps; sa.relu = relu; sa.normalize = normalize;
-        if (D <= 64) RC(launch(sa.idx ? fast::k_snf_fwd<4, true> : (M == 16 ? fast::k_snf_fwd<4, false, true> : fast::k_snf_fwd<4, false>), dim3(B * H), dim3(fast::SNF_T), fast::snf_smem<4>(), st, "k_snf_fwd<4>", sa));
-        else         RC(launch(sa.idx ? fast::k_snf_fwd<5, true> : (M == 16 ? fast::k_snf_fwd<5, false, true> : fast::k_snf_fwd<5, false>), dim3(B * H), dim3(fast::SNF_T), fast::snf_smem<5>(), st, "k_snf_fwd<5>", sa));
-        return MHLA_OK;
-    }
-    if (!rcos && !epi && fast_shape_ok(M, D, dtype, split, flags) && !(flags & MHLA_FLAG_FORCE_GENERIC) && view_ok16(q_num) && view_ok16(k_num) &&
-        view_ok16(v) && view_ok16(outv)) {
-        const FastWs f = fast_carve(ws, B, H, M, S);
-        if (ws_bytes < f.total_fwd) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, f.total_fwd);
-        fast::FsStateArgs sa{};
-        sa.x = cv(k_num); sa.y = cv(v); sa.t = cv(q_num); sa.idx = block_index; sa.state = f.state; sa.ksum = f.ksum;
-        sa.z_out = f.z; sa.H = H; sa.M = M; sa.S = S; sa.eps = eps; sa.relu = relu; sa.normalize = normalize;
-        if (S <= 64) RC(launch_state1c<0>(sa, f.njg, B * H, st, "k_fs_state_fwd"));
-        else RC(launch(fast::k_fs_state_fwd<0>, dim3(f.njg, B * H), dim3(fast::FT8), fast::FS_STATE_FWD_SMEM, st, "k_fs_state_fwd", sa));
-        if (normalize)
-            RC(launch(fast::k_fs_wz<0>, dim3((S + fast::WZ_C - 1) / fast::WZ_C, B * H), dim3(fast::FT), 0, st, "k_fs_wz<0>", W, ldw, (const float*)f.z, f.ninv, M, S, eps));
-        fast::FsOutArgs oa{};
-        oa.q = cv(q_num); oa.o = cmv(out); oa.idx = block_index; oa.W = W; oa.ldw = ldw; oa.state = f.state; oa.ninv = f.ninv;
-        oa.H = H; oa.M = M; oa.S = S; oa.njg = f.njg; oa.eps = eps; oa.relu = relu; oa.normalize = normalize;
-        oa.trace = g_trace.load();
-        oa.cs = f.cs;
-        if (f.cs > 1) RC(launch(fast::k_tile_out<16, true>, dim3(fast::tiles_per_bh(f.njg, 16) * B * H * f.cs), dim3(fast::FT8), fast::tile_smem<16>(), st, "k_t16_out", oa));
-        else          RC(launch(fast::k_tile_out<16>, dim3(fast::tiles_per_bh(f.njg, 16) * B * H), dim3(fast::FT8), fast::tile_smem<16>(), st, "k_t16_out", oa));
-        return MHLA_OK;
-    }
-    const BmWs w = bm_carve(ws, B, H, M, S, D, bm_sumfmt(M, S, D, dtype, flags), sp_shape_ok(D, flags), fwd_olo(M, S, D, dtype, flags));
-    if (ws_bytes < w.total_fwd) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, w.total_fwd);
-    BmCall c{};
-    c.q_num = q_num; c.k_num = k_num; c.v = v; c.q_den = q_den; c.k_den = k_den; c.out = out; c.gate = gate;
-    c.W = W; c.ldw = ldw; c.block_index = block_index; c.w = w; c.B = B; c.H = H; c.M = M; c.S = S; c.D = D; c.eps = eps; c.flags = flags;
-    c.normalize = normalize; c.split = split; c.epi = epi; c.st = st; c.rcos = rcos; c.rsin = rsin; c.ldr = ldr;
-    c.nw = nw; c.neps = neps; c.out_dtype = out_dtype;
-    switch (dtype) {
-        case MHLA_F32: return bm_fwd_typed<float, false>(c);
-        case MHLA_BF16: return bm_sum16(D, dtype, flags) ? bm_fwd_typed<bf16_t, true>(c) : bm_fwd_typed<bf16_t, false>(c);
-        case MHLA_F16: return bm_fwd_typed<f16_t, false>(c);
-        default: return fail(MHLA_EINVAL, "unknown dtype %d", dtype);
-    }
+    c.w = bm_carve_for(ws, B, H, M, S, D, dtype, flags, true);
+    if (ws_bytes < c.w.total_fwd) return ws_too_small(ws_bytes, c.w.total_fwd);
+    return bm_typed(c, true);
 }
 
 int mhla_blockmix_fwd(mhla_view q_num, mhla_view k_num, mhla_view v, mhla_view q_den, mhla_view k_den, const float* W,
@@ -352,9 +439,7 @@ int mhla_blockmix_rope_fwd(mhla_view q, mhla_view k, mhla_view v, int normalize,
                            const float* rope_cos, const float* rope_sin, int64_t ld_rope, mhla_mview out,
                            const int32_t* block_index, void* ws, size_t ws_bytes, int B, int H, int M, int S, int D,
                            int dtype, float eps, unsigned flags, void* stream) {
-    if (!rope_cos || !rope_sin) return fail(MHLA_EINVAL, "rope tables null");
-    if (ld_rope < D / 2 || (ld_rope & 3) || ((uintptr_t)rope_cos | (uintptr_t)rope_sin) % 16)
-        return fail(MHLA_EINVAL, "rope tables: ld=%lld must be >= D/2, a multiple of 4, and the tables 16-byte aligned", (long long)ld_rope);
+    RC(check_rope(rope_cos, rope_sin, ld_rope, D, true));
     if (flags & MHLA_FLAG_RELU_EPS) return fail(MHLA_ENOTSUP, "relu prologue and rotary prologue are not combined (Wan applies relu before the norm output is roped: use mhla_qk_prologue)");
     const mhla_view none{nullptr, 0, 0, 0};
     return bm_fwd_impl(q, k, v, normalize ? q : none, normalize ? k : none, W, ldw, out, block_index, ws, ws_bytes, B, H, M, S, D,
@@ -366,14 +451,10 @@ int mhla_blockmix_wan_fwd(mhla_view q, mhla_view k, mhla_view v, int normalize, 
                           mhla_view gate, mhla_mview out, int out_dtype, const int32_t* block_index, void* ws,
                           size_t ws_bytes, int B, int H, int M, int S, int D, int dtype, float eps, unsigned flags,
                           void* stream) {
-    if ((rope_cos == nullptr) != (rope_sin == nullptr)) return fail(MHLA_EINVAL, "rope_cos and rope_sin must be given together");
-    if (rope_cos && (ld_rope < D / 2 || (ld_rope & 3) || ((uintptr_t)rope_cos | (uintptr_t)rope_sin) % 16))
-        return fail(MHLA_EINVAL, "rope tables: ld=%lld must be >= D/2, a multiple of 4, and the tables 16-byte aligned", (long long)ld_rope);
+    RC(check_rope(rope_cos, rope_sin, ld_rope, D, false));
     if (out_dtype < 0 || out_dtype > 2) return fail(MHLA_EINVAL, "unknown out_dtype %d", out_dtype);
     if (flags & MHLA_FLAG_RELU_EPS) return fail(MHLA_ENOTSUP, "relu prologue is not combined with the Wan prologue / epilogue (use mhla_qk_prologue)");
-    if (gate.ptr) {
-        if (((uintptr_t)gate.ptr) % 8 || ((gate.sb | gate.sn | gate.sh) & 3)) return fail(MHLA_EINVAL, "gate: pointer must be 8-byte aligned, strides multiples of 4");
-    }
+    RC(check_gate(gate));
     if (norm_w && ((uintptr_t)norm_w) % 16) return fail(MHLA_EINVAL, "norm_w must be 16-byte aligned");
     const mhla_view none{nullptr, 0, 0, 0};
     return bm_fwd_impl(q, k, v, normalize ? q : none, normalize ? k : none, W, ldw, out, block_index, ws, ws_bytes, B, H, M, S, D,
@@ -385,140 +466,41 @@ static int bm_bwd_impl(mhla_view q_num, mhla_view k_num, mhla_view v, mhla_view 
                        mhla_mview dq_den, mhla_mview dk_den, float* dW, const int32_t* block_index, void* ws,
                        size_t ws_bytes, const void* fwd_ws, int B, int H, int M, int S, int D, int dtype, float eps,
                        unsigned flags, void* stream, const float* rcos = nullptr, const float* rsin = nullptr, long ldr = 0) {
-    const bool normalize = q_den.ptr != nullptr;
-    const bool split = normalize && (q_den.ptr != q_num.ptr || k_den.ptr != k_num.ptr);
-    RC(bm_check(B, H, M, S, D, dtype, flags, normalize, split));
+    BmCall c = bm_call(q_num, k_num, v, q_den, k_den, W, ldw, block_index, B, H, M, S, D, dtype, eps, flags, stream, rcos, rsin, ldr);
+    RC(bm_check(B, H, M, S, D, dtype, flags, c.split));
     CHECK_VIEW(q_num); CHECK_VIEW(k_num); CHECK_VIEW(v); CHECK_VIEW(dout);
     CHECK_VIEW(dq_num); CHECK_VIEW(dk_num); CHECK_VIEW(dv);
-    if (normalize) { CHECK_VIEW(q_den); CHECK_VIEW(k_den); CHECK_VIEW(out); }
-    if (split) { CHECK_VIEW(dq_den); CHECK_VIEW(dk_den); }
+    if (c.normalize) { CHECK_VIEW(q_den); CHECK_VIEW(k_den); CHECK_VIEW(out); }
+    if (c.split) { CHECK_VIEW(dq_den); CHECK_VIEW(dk_den); }
     if (!W || ldw < M || !dW) return fail(MHLA_EINVAL, "W/dW null or ldw=%d < M=%d", ldw, M);
     if (!ws || ((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace null or not 16-byte aligned");
     if (fwd_ws && ((uintptr_t)fwd_ws) % 16) return fail(MHLA_EINVAL, "fwd_ws not 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (!normalize) { q_den = q_num; k_den = k_num; }
-    const int relu = (flags & MHLA_FLAG_RELU_EPS) ? 1 : 0;
-    {
-        const mhla_view dqv{dq_num.ptr, dq_num.sb, dq_num.sn, dq_num.sh}, dkv_{dk_num.ptr, dk_num.sb, dk_num.sn, dk_num.sh},
-            dvv{dv.ptr, dv.sb, dv.sn, dv.sh};
-        if (!rcos && snf_shape_ok(M, S, D, dtype, split) && !(flags & (MHLA_FLAG_FORCE_GENERIC | MHLA_FLAG_NO_SMALLN)) && view_ok16(q_num) &&
-            view_ok16(k_num) && view_ok16(v) && view_ok16(dout) && (!normalize || view_ok16(out)) && view_ok16(dqv) &&
-            view_ok16(dkv_) && view_ok16(dvv)) {
-            const size_t need = (size_t)B * H * M * M * 4;
-            if (ws_bytes < need) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-            fast::SnArgs sa{};
-            sa.q = cv(q_num); sa.k = cv(k_num); sa.v = cv(v); sa.o = normalize ? cv(out) : cv(q_num); sa.dout = cv(dout);
-            sa.dq = cmv(dq_num); sa.dk = cmv(dk_num); sa.dv = cmv(dv); sa.idx = block_index; sa.W = W; sa.ldw = ldw;
-            sa.dwp = (float*)ws; sa.H = H; sa.M = M; sa.D = D; sa.eps = eps; sa.relu = relu; sa.normalize = normalize;
-            if (D <= 64) RC(launch(sa.idx ? fast::k_snf_bwd<4, true> : (M == 16 ? fast::k_snf_bwd<4, false, true> : fast::k_snf_bwd<4, false>), dim3(B * H), dim3(fast::SNF_T), fast::snf_smem<4>(), st, "k_snf_bwd<4>", sa));
-            else         RC(launch(sa.idx ? fast::k_snf_bwd<5, true> : (M == 16 ? fast::k_snf_bwd<5, false, true> : fast::k_snf_bwd<5, false>), dim3(B * H), dim3(fast::SNF_T), fast::snf_smem<5>(), st, "k_snf_bwd<5>", sa));
-            RC(launch(fast::k_sn_dw_reduce, dim3(M * M), dim3(256), 0, st, "k_sn_dw_reduce", (const float*)ws, dW, M * M, B * H));
-            return MHLA_OK;
-        }
-        if (!rcos && sn_shape_ok(M, S, D, dtype, split) && !(flags & (MHLA_FLAG_FORCE_GENERIC | MHLA_FLAG_NO_SMALLN)) && view_ok16(q_num) &&
-            view_ok16(k_num) && view_ok16(v) && view_ok16(dout) && (!normalize || view_ok16(out)) && view_ok16(dqv) &&
-            view_ok16(dkv_) && view_ok16(dvv)) {
-            const size_t need = (size_t)B * H * M * M * 4;
-            if (ws_bytes < need) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-            fast::SnArgs sa{};
-            sa.q = cv(q_num); sa.k = cv(k_num); sa.v = cv(v); sa.o = normalize ? cv(out) : cv(q_num); sa.dout = cv(dout);
-            sa.dq = cmv(dq_num); sa.dk = cmv(dk_num); sa.dv = cmv(dv); sa.idx = block_index; sa.W = W; sa.ldw = ldw;
-            sa.dwp = (float*)ws; sa.H = H; sa.M = M; sa.D = D; sa.eps = eps; sa.relu = relu; sa.normalize = normalize;
-            sa.trace = g_trace.load();
-            const bool hl = !(flags & MHLA_FLAG_BF16_SUMMARIES), g = sa.idx != nullptr;
-            const int nth = hl ? fast::SN_TB * (3 - SN_BWD_NB) : fast::SN_TB;
-            if (D <= 64) RC(launch(hl ? sn_bwd_kernel<4, true>(g, M) : sn_bwd_kernel<4, false>(g, M), dim3(B * H), dim3(nth), hl ? fast::sn_bwd_smem<4, SN_BWD_NB>() : fast::sn_bwd_smem<4>(), st, hl ? "k_sn_bwd<4,hl>" : "k_sn_bwd<4>", sa));
-            else         RC(launch(hl ? sn_bwd_kernel<5, true>(g, M) : sn_bwd_kernel<5, false>(g, M), dim3(B * H), dim3(nth), hl ? fast::sn_bwd_smem<5, SN_BWD_NB>() : fast::sn_bwd_smem<5>(), st, hl ? "k_sn_bwd<5,hl>" : "k_sn_bwd<5>", sa));
-            RC(launch(fast::k_sn_dw_reduce, dim3(M * M), dim3(256), 0, st, "k_sn_dw_reduce", (const float*)ws, dW, M * M, B * H));
-            return MHLA_OK;
-        }
-        if (!rcos && fast_shape_ok(M, D, dtype, split, flags) && !(flags & MHLA_FLAG_FORCE_GENERIC) && view_ok16(q_num) && view_ok16(k_num) &&
-            view_ok16(v) && view_ok16(dout) && (!normalize || view_ok16(out)) && view_ok16(dqv) && view_ok16(dkv_) && view_ok16(dvv)) {
-            FastWs f = fast_carve(ws, B, H, M, S);
-            const size_t need = mhla_blockmix_bwd_ws_bytes(B, H, M, S, D, dtype, split, flags);
-            if (ws_bytes < need) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-            f.err = bwd_err_word(ws, B, H, M, S, D, dtype, split, flags);
-            const fast::u16* state = f.state;
-            const float *z = f.z, *ksum = f.ksum, *ninv = f.ninv;
-            if (fwd_ws) {   // forward workspace retained by the caller: reuse KV^T, z, ksum, 1/n
-                const FastWs ff = fast_carve(const_cast<void*>(fwd_ws), B, H, M, S);
-                state = ff.state; z = ff.z; ksum = ff.ksum; ninv = ff.ninv;
-            } else {
-                fast::FsStateArgs sa{};
-                sa.x = cv(k_num); sa.y = cv(v); sa.t = cv(q_num); sa.idx = block_index; sa.state = f.state; sa.ksum = f.ksum;
-                sa.z_out = f.z; sa.H = H; sa.M = M; sa.S = S; sa.eps = eps; sa.relu = relu; sa.normalize = normalize;
-                if (S <= 64) RC(launch_state1c<0>(sa, f.njg, B * H, st, "k_fs_state_fwd"));
-        else RC(launch(fast::k_fs_state_fwd<0>, dim3(f.njg, B * H), dim3(fast::FT8), fast::FS_STATE_FWD_SMEM, st, "k_fs_state_fwd", sa));
-                if (normalize)
-                    RC(launch(fast::k_fs_wz<0>, dim3((S + fast::WZ_C - 1) / fast::WZ_C, B * H), dim3(fast::FT), 0, st, "k_fs_wz<0>", W, ldw, (const float*)f.z, f.ninv, M, S, eps));
-            }
-            fast::FsStateArgs ga{};
-            ga.x = cv(q_num); ga.y = cv(dout); ga.t = cv(out); ga.idx = block_index; ga.W = W; ga.ldw = ldw; ga.ninv = ninv;
-            ga.state = f.dstate; ga.dn = f.dn; ga.H = H; ga.M = M; ga.S = S; ga.eps = eps; ga.relu = relu; ga.normalize = normalize;
-            if (S <= 64) RC(launch_state1c<1>(ga, f.njg, B * H, st, "k_fs_state<1>"));
-            else RC(launch(fast::k_fs_state<1>, dim3(f.njg, B * H), dim3(fast::FT8), fast::FS_STATE_SMEM, st, "k_fs_state<1>", ga));
-            // dW needs only dG^T, KV^T, dn and z, all complete here; dz = W^T dn (needed by the token-gradient kernels) rides in
-            // the same launch as extra workgroups
-            fast::FsDwArgs da{f.dstate, state, normalize ? f.dn : nullptr, z, f.dwp, M, S, f.njg, W, ldw, f.dz, f.done, f.err, f.ntt * f.cs};
-            hipStream_t sd = st;
-            const int nwz = normalize ? (S + fast::WZ_C - 1) / fast::WZ_C : 0;
-            RC(launch(fast::k_fs_dw<>, dim3(fast::DW_SPLIT + nwz, B * H), dim3(fast::FT8), fast::FS_DW_SMEM, sd, "k_fs_dw", da));
-            fast::FsTokArgs ta{};
-            ta.q = cv(q_num); ta.k = cv(k_num); ta.v = cv(v); ta.dout = cv(dout); ta.dq = cmv(dq_num); ta.dk = cmv(dk_num);
-            ta.dv = cmv(dv); ta.idx = block_index; ta.W = W; ta.ldw = ldw; ta.state = state; ta.dstate = f.dstate; ta.ninv = ninv;
-            ta.dz = f.dz; ta.ksum = ksum; ta.H = H; ta.M = M; ta.S = S; ta.njg = f.njg; ta.eps = eps; ta.relu = relu;
-            ta.normalize = normalize;
-            ta.dksum = f.dksum;
-            const long ntile_wgs = (long)f.ntt * B * H * f.cs;
-            ta.cs = f.cs; ta.dks_part = (long)al4((size_t)B * H * M * 64);
-            unsigned long long* tr = g_trace.load();   // regions: [0] k_t16_out, [1] dQ role, [2] dK/dV role (record = ntiles + blockIdx.x)
-            ta.trace = tr ? tr + ntile_wgs * fast::TRACE_SLOTS : nullptr;
-            ta.dwp = f.dwp; ta.dW = dW; ta.nparts = B * H * fast::DW_SPLIT; ta.ntiles = (int)ntile_wgs; ta.done = f.done;
-            ta.err = f.err;
-            ta.drop_signal = g_drop_signal.load();   // testing aid for the bounded wait (mhla_set_option)
-            g_watch.check(st);                        // did an earlier fused launch of this process report an expired hand-over?
-            const auto tile_bwd = f.cs > 1 ? fast::k_tile_bwd<16, true> : fast::k_tile_bwd<16, false>;   // (multi-chunk blocks: cs workgroups per tile)
-            if (g_two_launches.load()) {   // (the kernel boundary orders dksum and the flags: the wait returns at its first poll)
-                RC(launch(tile_bwd, dim3((unsigned)ntile_wgs), dim3(fast::FT8), fast::tile_smem<16>(), st, "k_t16_bwd_dq", ta));
-                ta.x0 = (int)ntile_wgs;
-                RC(launch(tile_bwd, dim3((unsigned)ntile_wgs + fast::DWR_WGS), dim3(fast::FT8), fast::tile_smem<16>(), st, "k_t16_bwd_dkv", ta));
-                return MHLA_OK;
-            }
-            RC(launch(tile_bwd, dim3((unsigned)(2 * ntile_wgs) + fast::DWR_WGS), dim3(fast::FT8), fast::tile_smem<16>(), st, "k_t16_bwd", ta));
-            if (normalize) g_watch.watch(f.err, st);
-            return MHLA_OK;
-        }
+    c.outv = out; c.dout = dout; c.dq_num = dq_num; c.dk_num = dk_num; c.dv = dv; c.dq_den = dq_den; c.dk_den = dk_den; c.dW = dW;
+    const bool fast_layout = bm_fast_layout(M, S, D, dtype, c.split, flags);
+    switch (const BmRoute r = bm_call_route(c, true)) {
+        case BM_SN: case BM_SNF: return sn_bwd(c, r, ws, ws_bytes);
+        case BM_FAST: return fast_bwd(c, ws, ws_bytes, fwd_ws, bwd_err_word(ws, B, H, M, S, D, dtype, c.split, flags));
+        default: break;
     }
-    BmWs w = bm_carve(ws, B, H, M, S, D, bm_sumfmt(M, S, D, dtype, flags), sp_shape_ok(D, flags), bm_olo(M, S, D, dtype, flags));
-    if (ws_bytes < w.total_bwd) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, w.total_bwd);
-    if (fast_shape_ok(M, D, dtype, split, flags) && !(flags & MHLA_FLAG_FORCE_GENERIC)) {
+    c.w = bm_carve_for(ws, B, H, M, S, D, dtype, flags, false);
+    if (ws_bytes < c.w.total_bwd) return ws_too_small(ws_bytes, c.w.total_bwd);
+    if (fast_layout) {
         // a fast-path shape on another path (misaligned views, rotary prologue): leave a defined error word for the status call
-        if (ws_bytes < mhla_blockmix_bwd_ws_bytes(B, H, M, S, D, dtype, split, flags))
-            return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, mhla_blockmix_bwd_ws_bytes(B, H, M, S, D, dtype, split, flags));
-        if (hipMemsetAsync(bwd_err_word(ws, B, H, M, S, D, dtype, split, flags), 0, 4, st) != hipSuccess)
+        const size_t need = mhla_blockmix_bwd_ws_bytes(B, H, M, S, D, dtype, c.split, flags);
+        if (ws_bytes < need) return ws_too_small(ws_bytes, need);
+        if (hipMemsetAsync(bwd_err_word(ws, B, H, M, S, D, dtype, c.split, flags), 0, 4, c.st) != hipSuccess)
             return fail(MHLA_ELAUNCH, "hipMemsetAsync of the error word failed");
     }
     // the forward's KV, G, z, ksum, 1/n are still in its workspace (only when the shape cannot have taken the bf16 fast path,
     // whose workspace has another layout)
-    const bool reuse = fwd_ws && sp_shape_ok(D, flags) && (rcos || !fast_shape_ok(M, D, dtype, split, flags));
-    unsigned short* const olo_own = w.olo;
-    if (reuse) {
-        const BmWs f = bm_carve(const_cast<void*>(fwd_ws), B, H, M, S, D, bm_sumfmt(M, S, D, dtype, flags), sp_shape_ok(D, flags), fwd_olo(M, S, D, dtype, flags));
-        w.kv = f.kv; w.g = f.g; w.z = f.z; w.ksum = f.ksum; w.ninv = f.ninv;
-        if (f.olo) w.olo = f.olo;   // (a forward given MHLA_FLAG_NO_BWD_STATE has no residual region: the backward recomputes it into its own)
+    c.reuse = fwd_ws && sp_shape_ok(D, flags) && (rcos || !fast_layout);
+    c.olo_own = c.w.olo;
+    if (c.reuse) {
+        const BmWs f = bm_carve_for(const_cast<void*>(fwd_ws), B, H, M, S, D, dtype, flags, true);
+        c.w.kv = f.kv; c.w.g = f.g; c.w.z = f.z; c.w.ksum = f.ksum; c.w.ninv = f.ninv;
+        if (f.olo) c.w.olo = f.olo;   // (a forward given MHLA_FLAG_NO_BWD_STATE has no residual region: the backward recomputes it into its own)
     }
-    BmCall c{};
-    c.olo_own = olo_own;
-    c.q_num = q_num; c.k_num = k_num; c.v = v; c.q_den = q_den; c.k_den = k_den; c.outv = out; c.dout = dout;
-    c.dq_num = dq_num; c.dk_num = dk_num; c.dv = dv; c.dq_den = dq_den; c.dk_den = dk_den; c.dW = dW;
-    c.W = W; c.ldw = ldw; c.block_index = block_index; c.w = w; c.B = B; c.H = H; c.M = M; c.S = S; c.D = D; c.eps = eps; c.flags = flags;
-    c.normalize = normalize; c.split = split; c.reuse = reuse; c.st = st; c.rcos = rcos; c.rsin = rsin; c.ldr = ldr;
-    switch (dtype) {
-        case MHLA_F32: return bm_bwd_typed<float, false>(c);
-        case MHLA_BF16: return bm_sum16(D, dtype, flags) ? bm_bwd_typed<bf16_t, true>(c) : bm_bwd_typed<bf16_t, false>(c);
-        case MHLA_F16: return bm_bwd_typed<f16_t, false>(c);
-        default: return fail(MHLA_EINVAL, "unknown dtype %d", dtype);
-    }
+    return bm_typed(c, false);
 }
 
 int mhla_blockmix_bwd(mhla_view q_num, mhla_view k_num, mhla_view v, mhla_view q_den, mhla_view k_den, const float* W,
@@ -539,9 +521,7 @@ int mhla_blockmix_rope_bwd(mhla_view q, mhla_view k, mhla_view v, int normalize,
                            mhla_mview dq, mhla_mview dk, mhla_mview dv, float* dW, const int32_t* block_index, void* ws,
                            size_t ws_bytes, const void* fwd_ws, int B, int H, int M, int S, int D, int dtype, float eps,
                            unsigned flags, void* stream) {
-    if (!rope_cos || !rope_sin) return fail(MHLA_EINVAL, "rope tables null");
-    if (ld_rope < D / 2 || (ld_rope & 3) || ((uintptr_t)rope_cos | (uintptr_t)rope_sin) % 16)
-        return fail(MHLA_EINVAL, "rope tables: ld=%lld must be >= D/2, a multiple of 4, and the tables 16-byte aligned", (long long)ld_rope);
+    RC(check_rope(rope_cos, rope_sin, ld_rope, D, true));
     if (dtype != MHLA_F32 || !sp_shape_ok(D, flags))
         return fail(MHLA_ENOTSUP, "rotary backward needs fp32 tensors and D %% 8 == 0 (D=%d, dtype=%d, flags=%u)", D, dtype, flags);
     if (flags & MHLA_FLAG_RELU_EPS) return fail(MHLA_ENOTSUP, "relu prologue and rotary prologue are not combined");
@@ -556,52 +536,29 @@ int mhla_blockmix_rope_bwd(mhla_view q, mhla_view k, mhla_view v, int normalize,
 // "family=...; summaries=...; fwd=k1,k2,...; bwd=k1,k2,..." -- so that tests and tools can assert the path a BASELINE configuration
 // takes instead of inferring it from timings (DESIGN.md section 0a is the same table).  Returns the length written (without the NUL).
 int mhla_describe_dispatch(int B, int H, int M, int S, int D, int dtype, int split, unsigned flags, char* buf, size_t cap) {
-    RC(bm_check(B, H, M, S, D, dtype, flags, true, split != 0));
+    RC(bm_check(B, H, M, S, D, dtype, flags, split != 0));
     std::string fam, sum, fwd, bwd;
-    const bool gen = (flags & MHLA_FLAG_FORCE_GENERIC) != 0, nosn = gen || (flags & MHLA_FLAG_NO_SMALLN);
-    if (!nosn && snf_shape_ok(M, S, D, dtype, split != 0)) {
-        fam = "small-sequence fp32 (attention form, one launch per direction)";
-        sum = "none (score tiles in LDS as bf16 hi + lo pairs)";
-        fwd = D <= 64 ? "k_snf_fwd<4>" : "k_snf_fwd<5>"; bwd = std::string(D <= 64 ? "k_snf_bwd<4>" : "k_snf_bwd<5>") + " k_sn_dw_reduce";
-    } else if (!nosn && sn_shape_ok(M, S, D, dtype, split != 0)) {
-        fam = "small-sequence bf16 (attention form, one launch per direction)";
-        const bool hl = !(flags & MHLA_FLAG_BF16_SUMMARIES);
-        sum = hl ? "none (score tiles in LDS as bf16 hi + lo pairs)" : "none (score tiles as single bf16: reduced precision)";
-        const std::string dt = D <= 64 ? "4" : "5";
-        fwd = "k_sn_fwd<" + dt + (hl ? ",hl>" : ">"); bwd = "k_sn_bwd<" + dt + (hl ? ",hl>" : ">") + " k_sn_dw_reduce";
-    } else if (!gen && fast_shape_ok(M, D, dtype, split != 0, flags)) {
+    const BmRoute r = bm_route(M, S, D, dtype, split != 0, flags);
+    const bool hl = !(flags & MHLA_FLAG_BF16_SUMMARIES);
+    if (r == BM_SNF || r == BM_SN) {
+        fam = r == BM_SNF ? "small-sequence fp32 (attention form, one launch per direction)" : "small-sequence bf16 (attention form, one launch per direction)";
+        sum = hl || r == BM_SNF ? "none (score tiles in LDS as bf16 hi + lo pairs)" : "none (score tiles as single bf16: reduced precision)";
+        fwd = bm_sn_name(r, false, D, hl); bwd = std::string(bm_sn_name(r, true, D, hl)) + " " + N_SN_DW_REDUCE;
+    } else if (r == BM_FAST) {
         fam = "bf16 fast path (fused mixing + token tiles)";
         sum = "bf16 (single bf16 values, 8-block interleaved: reduced precision, opt-in)";
-        fwd = "k_fs_state_fwd k_fs_wz<0> k_t16_out"; bwd = "k_fs_state<1> k_fs_dw k_t16_bwd";
-    } else if (sp_shape_ok(D, flags)) {
-        const int fmt = bm_sumfmt(M, S, D, dtype, flags);
-        const long E = (long)D * D;
-        const bool s16 = fmt == SF_BF16, mixr = (M > 32 || !s16) && M <= 256 && E % (s16 ? 128 : 64) == 0, evenS = (S % 2) == 0;
-        fam = "split-operand (bf16 hi + lo MFMA operands)";
-        sum = fmt == SF_H16 ? "h16 (fp16 payload x row multiplier: 11 significand bits, 2 bytes)" : fmt == SF_P24 ? "p24 (24-bit floats: 16 significand bits, 3 bytes)"
-              : fmt == SF_BF16 ? "bf16 (single bf16 values: reduced precision, opt-in)" : "fp32 words";
-        const bool wave16 = s16 && S == 16 && D == 64 && !split;
-        const std::string st0 = wave16 ? "k_s16_state<0>" : "k_sp_state", out = wave16 ? "k_s16_out" : "k_sp_out";
-        std::string mix0, mix1, dw;
-        const std::string dwr = std::string("k_sp_dwr<") + (M <= 128 ? "2" : M <= 192 ? "3" : "4") + (fmt == SF_H16 ? ",h16>" : ">");   // whole-matrix dW kernel (incl. the <dn, z> term)
-        if (fmt == SF_H16) {
-            const bool m2 = sp_mixh2_applies(M, E, (long)B * H, S);
-            mix0 = m2 ? "k_sp_mixh2<0>" : "k_sp_mixh<0>"; mix1 = M <= 128 ? "k_sp_mixh<1,dw>" : (m2 ? "k_sp_mixh2<1>" : "k_sp_mixh<1>"); dw = M <= 128 ? "" : dwr;
-        }
-        else if (s16 && M > 192 && mixr) { mix0 = "k_sp_mixr_dma<0>"; mix1 = "k_sp_mixr_dma<1>"; dw = dwr; }
-        else if (mixr) {
-            mix0 = "k_sp_mixr<0>";
-            if (!s16 && M <= 128) { mix1 = "k_sp_mixr<1,dw>"; dw = ""; }
-            else { mix1 = "k_sp_mixr<1>"; dw = s16 ? (M > 64 ? dwr : (M <= 16 ? "k_sp_dw<16>" : M <= 32 ? "k_sp_dw<32>" : "k_sp_dw")) : (fmt == SF_P24 ? "k_sp_dwt" : "k_sp_dw"); }
-        } else { mix0 = "k_sp_mix<0>"; mix1 = "k_sp_mix<1>"; dw = s16 && M > 64 && M <= 256 && E % 64 == 0 ? dwr : (M <= 16 ? "k_sp_dw<16>" : M <= 32 ? "k_sp_dw<32>" : "k_sp_dw"); }
-        const bool wzf = fmt == SF_BF16 ? (M > 192 && M <= 256 && S <= 16 && mixr) : (mixr && evenS);   // the normaliser's product rides in the mixing kernel
-        fwd = st0 + " " + mix0 + (wzf ? "" : " k_wz<0>") + " " + out;
-        bwd = std::string(wave16 ? "k_s16_state<1>" : "k_sp_state<1>") + " " + mix1 + (wzf ? "" : " k_wz<1>") + (dw.empty() ? "" : " " + dw) +
-              ((dw.empty() && wzf) || dw == dwr ? "" : " k_dw") + " k_dw_reduce " + (wave16 ? "k_s16_bwd_dq k_s16_bwd_dkv" : "k_sp_bwd_dq k_sp_bwd_dkv");
-    } else {
-        fam = "generic (exact fp32 MFMA)";
-        sum = "fp32 words (dense rows)";
-        fwd = "k_bm_state<0> k_mix<0,0> k_wz<0> k_bm_out"; bwd = "k_bm_state<0> k_mix<0,0> k_wz<0> k_bm_state<1> k_wz<1> k_mix<1,0> k_dw k_dw_reduce k_bm_bwd_tok";   // (no state is kept: the backward recomputes KV, G, 1 / n)
+        fwd = std::string(N_FS_STATE[0]) + " " + N_FS_WZ + " " + N_T16_OUT; bwd = std::string(N_FS_STATE[1]) + " " + N_FS_DW + " " + N_T16_BWD;
+    } else {   // the plan of a call with the normaliser, aligned views, no rotary tables or epilogue, the forward's workspace kept
+        const BmPlan p = bm_plan((long)B * H, M, S, D, dtype, flags, true, split != 0, false, false, true);
+        fam = p.sp ? "split-operand (bf16 hi + lo MFMA operands)" : "generic (exact fp32 MFMA)";
+        sum = !p.sp ? "fp32 words (dense rows)" : p.fmt == SF_H16 ? "h16 (fp16 payload x row multiplier: 11 significand bits, 2 bytes)"
+              : p.fmt == SF_P24 ? "p24 (24-bit floats: 16 significand bits, 3 bytes)" : p.fmt == SF_BF16 ? "bf16 (single bf16 values: reduced precision, opt-in)" : "fp32 words";
+        const std::string wz0 = p.wz_kernel ? std::string(" ") + N_WZ[0] : "", wz1 = p.wz_kernel ? std::string(" ") + N_WZ[1] : "";
+        const std::string summaries = std::string(p.n_state[0]) + " " + p.n_mix[0] + wz0;
+        fwd = summaries + " " + p.n_out;
+        // (the split-operand rows name k_wz<1> behind the mixing, wherever the plan launches it; the generic backward recomputes the forward's summaries)
+        bwd = (p.sp ? "" : summaries + " ") + p.n_state[1] + (p.sp ? std::string(" ") + p.n_mix[1] + wz1 : wz1 + " " + p.n_mix[1]) + (p.n_dw ? std::string(" ") + p.n_dw : "") +
+              (p.dnz ? std::string(" ") + N_DNZ : "") + " " + N_DW_REDUCE + " " + p.n_tok[0] + (p.n_tok[1] ? std::string(" ") + p.n_tok[1] : "");
     }
     const std::string txt = "family=" + fam + "; summaries=" + sum + "; fwd=" + fwd + "; bwd=" + bwd;
     if (buf && cap) {
@@ -617,11 +574,9 @@ int mhla_describe_dispatch(int B, int H, int M, int S, int D, int dtype, int spl
 int mhla_blockmix_bwd_status(const void* ws, size_t ws_bytes, int B, int H, int M, int S, int D, int dtype, int split, unsigned flags,
                              void* stream) {
     if (!ws) return fail(MHLA_EINVAL, "workspace null");
-    if (!fast_shape_ok(M, D, dtype, split != 0, flags) || (flags & MHLA_FLAG_FORCE_GENERIC) ||
-        (sn_shape_ok(M, S, D, dtype, split != 0) && !(flags & MHLA_FLAG_NO_SMALLN)))
-        return MHLA_OK;
+    if (bm_route(M, S, D, dtype, split != 0, flags) != BM_FAST) return MHLA_OK;
     const size_t need = mhla_blockmix_bwd_ws_bytes(B, H, M, S, D, dtype, split, flags);
-    if (ws_bytes < need) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+    if (ws_bytes < need) return ws_too_small(ws_bytes, need);
     int word = 0;
     hipError_t e = hipMemcpyAsync(&word, bwd_err_word(const_cast<void*>(ws), B, H, M, S, D, dtype, split, flags), sizeof(int),
                                   hipMemcpyDeviceToHost, (hipStream_t)stream);

@@ -276,7 +276,8 @@ def test_bwd_status_after_a_fast_shape_fell_back_to_another_path():
     check("dW", dW, Wd.grad.float().cpu(), 2 * 3 * 2.0 ** -8)
 
 
-@pytest.mark.parametrize("case", ["c2", "c2_split", "c2_256x16", "odd_s", "c4_small", "fp32_64", "generic", "c3", "causal", "causal_129"])
+@pytest.mark.parametrize("case", ["c2", "c2_split", "c2_256x16", "odd_s", "c4_small", "fp32_64", "generic", "c3", "causal", "causal_129",
+                                  "fast", "s16_256x16", "s16_tiled", "s16_dw16", "split_160", "over_256", "fp32_2waves", "h16_160", "snf"])
 def test_described_dispatch_is_the_dispatch_that_runs(case):
     """mhla_describe_dispatch against the library's own per-launch hook: the kernels it names are the kernels a forward + backward of the
     problem launches, in order (block-mix shapes of every family and summary format, the causal pipeline with one and two mixing launches)."""
@@ -296,7 +297,16 @@ def test_described_dispatch_is_the_dispatch_that_runs(case):
     else:
         B, H, M, S, D, dt, kw = {"c2": (1, 2, 64, 64, 64, bf, {}), "c2_split": (1, 2, 64, 64, 64, bf, {"summaries": "split"}),
                                  "c2_256x16": (1, 2, 256, 16, 64, bf, {}), "odd_s": (1, 2, 40, 21, 64, bf, {}), "c4_small": (1, 2, 150, 6, 128, f32, {}),
-                                 "fp32_64": (1, 2, 64, 32, 64, f32, {}), "generic": (1, 2, 16, 16, 36, f32, {}), "c3": (2, 2, 16, 16, 72, bf, {})}[case]
+                                 "fp32_64": (1, 2, 64, 32, 64, f32, {}), "generic": (1, 2, 16, 16, 36, f32, {}), "c3": (2, 2, 16, 16, 72, bf, {}),
+                                 "fast": (1, 2, 64, 64, 64, bf, {"summaries": "bf16"}),            # the bf16 fast path
+                                 "s16_256x16": (1, 2, 256, 16, 64, bf, {"summaries": "bf16"}),    # wave-per-block kernels, k_sp_mixr_dma, k_sp_dwr
+                                 "s16_tiled": (1, 2, 40, 21, 72, bf, {"summaries": "bf16"}),      # bf16 summaries on the tiled k_sp_mix
+                                 "s16_dw16": (1, 2, 16, 32, 96, bf, {"summaries": "bf16"}),       # k_sp_dw<16>
+                                 "split_160": (1, 2, 160, 16, 64, bf, {"summaries": "split"}),    # fp32 words, twelve-wave k_sp_mixr, k_sp_dw
+                                 "over_256": (1, 2, 300, 16, 64, bf, {}),                         # more than 256 blocks
+                                 "fp32_2waves": (1, 2, 16, 32, 64, f32, {}),                      # two-wave mixing with dW fused
+                                 "h16_160": (1, 2, 160, 16, 64, bf, {}),                          # h16 beyond 128 blocks without the re-cut kernel
+                                 "snf": (2, 2, 16, 16, 72, f32, {})}[case]                        # small-sequence fp32
         want = mhla_amd.describe_dispatch(B, H, M, S, D, dt, **kw)
         q, k, v, W, do, _, _ = make_blockmix_inputs(B, H, M, S, D, dt, 1, "rand", False)
         t = [x.requires_grad_(True) for x in to_dev(q, k, v, W)]

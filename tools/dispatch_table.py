@@ -1,6 +1,11 @@
 #!/usr/bin/env python
 """The dispatch table of DESIGN.md section 0a, printed from the library's own predicates (mhla_describe_dispatch /
-mhla_causal_describe_dispatch: pure host logic, no GPU needed):  python tools/dispatch_table.py"""
+mhla_causal_describe_dispatch: pure host logic, no GPU needed):  python tools/dispatch_table.py
+--sweep: one line per problem of a grid across every dispatch boundary -- arguments -> the description (or the refusal's code and
+message), both workspace sizes and keeps_state -- under the default options, recut_kernels = 0 and fp32_summaries = 1.  Two builds of the
+library (MHLA_LIB_PATH) dispatch alike exactly when their sweeps are byte-identical."""
+import ctypes
+import itertools
 import os
 import sys
 
@@ -33,11 +38,41 @@ CAUSAL = [
     ("129 .. 256 chunks", "default", (16384, 64, 64, bf), {}),
     ("fp32 / fp16 tensors; K or V not multiples of 64; K > 256; more than 256 chunks", "any", (8192, 128, 256, f32), {}),
 ]
-arrow = lambda ks: " → ".join("`" + k + "`" for k in ks)
-print("| configuration | tensors | flags | kernel family | block / chunk summaries in HBM | forward launches | backward launches |\n|---|---|---|---|---|---|---|")
-for name, dt, fl, a, kw in ROWS:
-    d = mhla_amd.describe_dispatch(*a, **kw)
-    print(f"| {name} | {dt} | {fl} | {d['family']} | {d['summaries']} | {arrow(d['fwd'])} | {arrow(d['bwd'])} |")
-for name, fl, a, kw in CAUSAL:
-    d = mhla_amd.describe_causal_dispatch(*a, **kw)
-    print(f"| causal: {name} | {'bf16' if a[3] is bf else 'fp32'} | {fl} | {d['family']} | {d['summaries']} | {arrow(d['fwd'])} | {arrow(d['bwd'])} |")
+
+
+def sweep_line(lib, B, H, M, S, D, dt, split, flags, buf=ctypes.create_string_buffer(2048)):
+    rc = lib.mhla_describe_dispatch(B, H, M, S, D, dt, split, flags, buf, len(buf))
+    said = buf.value.decode() if rc >= 0 else f"rc={rc} {lib.mhla_last_error().decode()}"
+    sizes = [getattr(lib, "mhla_blockmix_" + q)(B, H, M, S, D, dt, split, flags) for q in ("fwd_ws_bytes", "bwd_ws_bytes", "fwd_keeps_state")]
+    return f"B={B} H={H} M={M} S={S} D={D} dtype={dt} split={split} flags={flags} -> {said} | fwd_ws={sizes[0]} bwd_ws={sizes[1]} keeps_state={sizes[2]}"
+
+
+def sweep(out=sys.stdout):
+    lib = mhla_amd._lib.load()
+    L = mhla_amd._lib
+    grid = list(itertools.product((2, 128), (2, 4, 16, 17, 32, 33, 64, 65, 128, 129, 192, 193, 256, 257), (8, 16, 21, 64), (32, 36, 64, 72, 96, 104, 128),
+                                  (L.F32, L.BF16, L.F16), (0, L.FLAG_FP32_GRADE_SUMMARIES, L.FLAG_BF16_SUMMARIES), (0, 1), (0, L.FLAG_NO_SMALLN), (0, L.FLAG_FORCE_GENERIC)))
+    for option, value in ((None, 0), ("recut_kernels", 0), ("fp32_summaries", 1)):
+        before = lib.mhla_set_option(option.encode(), value) if option else None
+        try:
+            print(f"# {option or 'default options'}{'' if option is None else ' = ' + str(value)}", file=out)
+            for BH, M, S, D, dt, summ, split, nosn, gen in grid:
+                print(sweep_line(lib, 1, BH, M, S, D, dt, split, summ | nosn | gen), file=out)
+        finally:
+            if option:
+                lib.mhla_set_option(option.encode(), before)
+
+
+def table():
+    arrow = lambda ks: " → ".join("`" + k + "`" for k in ks)
+    print("| configuration | tensors | flags | kernel family | block / chunk summaries in HBM | forward launches | backward launches |\n|---|---|---|---|---|---|---|")
+    for name, dt, fl, a, kw in ROWS:
+        d = mhla_amd.describe_dispatch(*a, **kw)
+        print(f"| {name} | {dt} | {fl} | {d['family']} | {d['summaries']} | {arrow(d['fwd'])} | {arrow(d['bwd'])} |")
+    for name, fl, a, kw in CAUSAL:
+        d = mhla_amd.describe_causal_dispatch(*a, **kw)
+        print(f"| causal: {name} | {'bf16' if a[3] is bf else 'fp32'} | {fl} | {d['family']} | {d['summaries']} | {arrow(d['fwd'])} | {arrow(d['bwd'])} |")
+
+
+if __name__ == "__main__":
+    sweep() if "--sweep" in sys.argv else table()
