@@ -332,6 +332,26 @@ int mhla_causal_step(mhla_view q, mhla_view k, mhla_view v, const float* mix, in
                      float* Cur, int64_t pos, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y,
                      void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype, void* stream);
 
+/* mhla_causal_step_ragged: mhla_causal_step for a batch whose sequences are at positions of their own (added without a change of
+ * any existing signature or behaviour: MHLA_ABI_VERSION stays 9).  `pos_dev`: device int32 [B], tokens seen by each sequence.
+ * Sequence b behaves as in a batch of one: i = pos_dev[b] / chunk, its out row uses mix[i][i], and it closes its chunk -- S[i] = Cur,
+ * Cur = 0, P from row i + 1 of mix, or P = 0 when i + 1 == cap_chunks -- only if pos_dev[b] % chunk == chunk - 1.  The call itself
+ * adds one to every pos_dev[b], in its last launch and in stream order (no copy, no synchronisation; the earlier launches of
+ * the chain address by pos_dev, the last does not), so the array is the caller's to keep in step with, not to advance.
+ * The library cannot read device memory to validate, hence two host values: `max_pos`, the largest entry of pos_dev, which
+ * takes the place of `pos` in the MHLA_EINVAL checks of mhla_causal_step (cap_chunks, ldmix, the rows of mix read); and
+ * `any_boundary`, non-zero when at least one sequence is at pos % chunk == chunk - 1 (zero: the boundary kernel is not
+ * launched, and no chunk closes).  Restriction: with any_boundary the row after chunk max_pos / chunk must be covered by ldmix
+ * unless that chunk is the state's last, whichever sequence is the one on the boundary (MHLA_EINVAL otherwise, before any
+ * launch).  pos_dev must hold what max_pos and any_boundary were computed from; an array that disagrees is the caller's
+ * error and gives wrong rows.  As a defence only, an entry outside 0 .. max_pos is never used to address: the step clamps
+ * it, the boundary kernel skips that sequence.  Tiling and the order of every sum are those of mhla_causal_step: equal
+ * positions give the same bits.  Workspace: mhla_causal_step_ws_bytes. */
+int mhla_causal_step_ragged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                            float* Cur, int32_t* pos_dev, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate,
+                            const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V,
+                            int chunk, float scale, int dtype, void* stream);
+
 /* mhla_causal_extend: T >= 1 new tokens (q, k: [B,T,H,K]; v, out, y, gate: [B,T,H,V]) on a state with `pos` tokens seen, in a
  * number of launches that does not depend on T.  out = rows pos .. pos + T - 1 of the forward over the whole sequence, the
  * state afterwards is what T steps leave (the caller advances pos by T).  With i = pos / chunk, r = pos % chunk the tokens

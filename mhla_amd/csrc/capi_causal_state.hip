@@ -1,5 +1,5 @@
 // C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
-// (mhla_causal_state_init, mhla_causal_step, mhla_causal_extend; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// (mhla_causal_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_extend; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
@@ -40,7 +40,7 @@ size_t cst_ws_bytes(int B, int H, int K, int V) {   // the most splits any plan 
 
 int cst_roll(float* S, int cap, float* P, float* Cur, const float* mixrow, int nj, int commit, int BH, long E, hipStream_t st) {
     const CsRollArgs r{S, P, Cur, mixrow, E, cap, nj, commit};
-    return launch(k_cs_roll, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll", r);
+    return launch(k_cs_roll<false>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll", r);
 }
 
 template <typename T>
@@ -138,6 +138,48 @@ int mhla_causal_step(mhla_view q, mhla_view k, mhla_view v, const float* mix, in
         RC(launch(k_cs_step_finish<ET>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
     });
     if (roll) RC(cst_roll(S, cap_chunks, P, Cur, next ? mix + (i + 1) * ldmix : nullptr, (int)i + 1, 1, BH, (long)K * V, st));
+    return MHLA_OK;
+}
+
+int mhla_causal_step_ragged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                            float* Cur, int32_t* pos_dev, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate,
+                            const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V,
+                            int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check(B, H, K, V, chunk, dtype));
+    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(v);
+    if (!out.ptr && !y.ptr) return fail(MHLA_EINVAL, "out and y both null");
+    if (out.ptr) CHECK_VIEW(out);
+    if (y.ptr) CHECK_VIEW(y);
+    if (gate.ptr) CHECK_VIEW(gate);
+    if ((gate.ptr || norm_w) && !y.ptr) return fail(MHLA_EINVAL, "gate / norm_w given without y");
+    RC(cst_check_state(S, cap_chunks, P, Cur));
+    if (!pos_dev || ((uintptr_t)pos_dev) % 4) return fail(MHLA_EINVAL, "pos_dev null or not 4-byte aligned");
+    if (max_pos < 0 || max_pos >= INT32_MAX) return fail(MHLA_EINVAL, "max_pos=%lld is negative or beyond int32", (long long)max_pos);
+    const int64_t i = max_pos / chunk;
+    if (i >= cap_chunks) return fail(MHLA_EINVAL, "max_pos=%lld is in chunk %lld, the state holds %d", (long long)max_pos, (long long)i, cap_chunks);
+    // which sequence is on a boundary is known on the device only: with any_boundary the row after the furthest sequence's chunk
+    // must be covered (unless that chunk is the state's last), as if that sequence were the one -- a restriction (mhla_hip.h):
+    // the matrix passed with a boundary step reaches one row past the furthest sequence, or the state's capacity
+    const bool next = any_boundary && i + 1 < cap_chunks;
+    if (!mix || ldmix < i + 1 + (next ? 1 : 0))
+        return fail(MHLA_EINVAL, "mix null or ldmix=%d < %lld (row %lld of mix is read)", ldmix, (long long)(i + 1 + (next ? 1 : 0)), (long long)(i + (next ? 1 : 0)));
+    const size_t need = cst_ws_bytes(B, H, K, V);
+    if (!ws || ws_bytes < need) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+    if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int BH = B * H, kr = cst_rows((size_t)BH, K, V), nsplit = (K + kr - 1) / kr;
+    const long E = (long)K * V;
+    // step and roll address by pos_dev; the finish, which does not, advances it: last in the chain
+    DISPATCH_T(dtype, {
+        const CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, H, K, V, kr, nsplit, pos_dev, ldmix, (int)max_pos};
+        RC(launch(k_cs_step<ET, true>, dim3((V + CST_VT - 1) / CST_VT, nsplit, BH), dim3(CST_THREADS), 0, st, "k_cs_step_ragged", s));
+        if (any_boundary) {
+            const CsRollArgs r{S, P, Cur, nullptr, E, cap_chunks, 0, 0, pos_dev, mix, ldmix, (int)max_pos, H};
+            RC(launch(k_cs_roll<true>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll_ragged", r));
+        }
+        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, nsplit, pos_dev};
+        RC(launch(k_cs_step_finish<ET>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
+    });
     return MHLA_OK;
 }
 

@@ -11,11 +11,17 @@
 //                      workgroup) so that B H = 4 still fills the machine; per-split partial sums of o -> fp32 workspace
 //   k_cs_step_finish : partials summed in split order, scale, one rounding; optional RMSNorm x swish gate over the head's V channels
 //   k_cs_roll        : the chunk boundary (and the prefix mix of a prefilled state)
+// Ragged batches (every sequence at a position of its own): the same kernels, instantiated with RAGGED, read pos[b] from a device
+// int32 [B] array and derive i, r per (b, h) workgroup -- the step its mix[i][i], the roll whether this sequence is on a boundary
+// at all.  Tiling, K split, row walk and the order of every sum are the uniform ones, so equal positions give the uniform bits.
+// pos[b] advances in k_cs_step_finish, the last launch of the ragged chain (step, roll, finish) and the only one that does not
+// address by it: no workgroup writes pos[b] in a launch in which another reads it.
 // Memory-bound (P and Cur read, Cur written: 12 K V bytes per (b, h) and token); plain fp32 FMA, no MFMA, no atomics: every
 // sum has a fixed order, so results repeat bit for bit.  The state is fp32 whatever the tensor dtype: Cur takes up to 64
 // rank-1 updates and P sums up to L chunks -- a 16-bit state would round at every token.
 #pragma once
 #include "common.hpp"
+#include "causal.hpp"   // CS, the chunk length
 
 namespace mhla {
 
@@ -25,12 +31,20 @@ constexpr int CST_RG = 16;        // row groups per workgroup: thread (rg, c4) w
 
 struct CsStepArgs {
     View q, k, v;          // [B][1][H][K / V]
-    const float* mix;      // &mix[i][i]
+    const float* mix;      // &mix[i][i]; RAGGED: &mix[0][0]
     float* P;              // [bh][K][V]
     float* Cur;            // [bh][K][V]
     float* part;           // [bh][nsplit][V]
     int H, K, V, kr, nsplit;
+    // RAGGED only
+    const int* pos;        // [B] tokens seen per sequence
+    int ldmix, max_pos;    // row stride of mix; the largest position the host vouches for (a pos[b] outside 0 .. max_pos is clamped)
 };
+
+// pos[b] as the ragged step addresses by it.  Defence only: the caller keeps the array equal to its host mirror, and then the clamp
+// changes nothing.  An array that disagrees with the mirror is a caller's error that gives wrong rows (another mix[i][i]); what the
+// clamp -- and the roll's skip of such a sequence -- guarantee is that it cannot address outside what the host checked.
+__device__ __forceinline__ int cst_pos(const int* pos, int b, int max_pos) { return min(max(pos[b], 0), max_pos); }
 
 template <typename T> __device__ __forceinline__ float cst_ld1(const T* p);
 template <> __device__ __forceinline__ float cst_ld1<float>(const float* p) { return *p; }
@@ -42,7 +56,7 @@ template <> __device__ __forceinline__ void cst_st1<bf16_t>(bf16_t* p, float x) 
 template <> __device__ __forceinline__ void cst_st1<f16_t>(f16_t* p, float x) { p->v = (_Float16)x; }
 
 // grid (ceil(V / 64), nsplit, B H)
-template <typename T>
+template <typename T, bool RAGGED = false>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
     __shared__ __attribute__((aligned(16))) float red[CST_RG][CST_VT];
     const int tid = threadIdx.x, c4 = (tid & 15) * 4, rg = tid >> 4;
@@ -53,7 +67,13 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
     const T* qb = (const T*)a.q.ptr + b * a.q.sb + h * a.q.sh;
     const T* kb = (const T*)a.k.ptr + b * a.k.sb + h * a.k.sh;
     const T* vb = (const T*)a.v.ptr + b * a.v.sb + h * a.v.sh;
-    const float mii = *a.mix;
+    float mii;
+    if constexpr (RAGGED) {
+        const long i = cst_pos(a.pos, b, a.max_pos) / CS;
+        mii = a.mix[i * a.ldmix + i];
+    } else {
+        mii = *a.mix;
+    }
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     if (live) {
         const f32x4 vv = Io<T>::ld4(vb + col);
@@ -106,6 +126,7 @@ struct CsFinishArgs {
     const float* nw;       // [V] or null
     float neps, scale;
     int H, V, nsplit;
+    int* advance;          // [B] or null: positions of a ragged state, each incremented once (by the workgroup of head 0, token 0)
 };
 
 // grid (B H, T tokens): o = scale * (partials in split order); y = o rsqrt(mean(o^2 over V) + neps) nw g sigmoid(g), from the fp32 o
@@ -114,6 +135,7 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishAr
     __shared__ float red[CST_THREADS / 64];
     const int tid = threadIdx.x, bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
     const long tok = blockIdx.y;
+    if (a.advance && h == 0 && tok == 0 && tid == 0) a.advance[b] += 1;   // (nothing in this launch reads it)
     const float* pb = a.part + ((long)bh * gridDim.y + tok) * a.nsplit * a.V;
     T* ob = a.out.ptr ? (T*)a.out.ptr + b * a.out.sb + tok * a.out.sn + h * a.out.sh : nullptr;
     auto o_at = [&](int c) {   // one accumulator, split order; the loads of a batch of eight issued together
@@ -175,25 +197,41 @@ struct CsRollArgs {
     const float* mixrow;   // row of mix the new P is formed with (nj entries read), or null: P = 0
     long E;                // K V
     int cap, nj, commit;   // commit: S[nj - 1] = Cur, Cur = 0 first (the boundary); else S[0 .. nj) as they are (prefill)
+    // RAGGED only: nj, commit and mixrow are derived per sequence from pos[b], the position of the token the step just took
+    const int* pos;        // [B]
+    const float* mix;      // &mix[0][0]
+    int ldmix, max_pos, H;
 };
 
 // grid (ceil(E / 4 / 64), B H), one wave per workgroup: P = sum_{j < nj} mixrow[j] S[j], ascending j
+// RAGGED: each (b, h) for itself -- not on a boundary (pos[b] % 64 != 63): nothing; else the commit with nj = i + 1 and the new P
+// from row i + 1 of mix, or P = 0 when i + 1 == cap (this sequence's state is full)
+template <bool RAGGED = false>
 __global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
     const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
     if (e >= a.E) return;   // (E % 4 == 0)
     const long bh = blockIdx.y;
+    int nj = a.nj, commit = a.commit;
+    const float* mixrow = a.mixrow;
+    if constexpr (RAGGED) {
+        const int p = a.pos[bh / a.H];
+        if (p < 0 || p > a.max_pos || p % CS != CS - 1) return;   // (outside 0 .. max_pos: defence only, see cst_pos)
+        nj = p / CS + 1;   // (<= cap: the host checked max_pos / 64 < cap)
+        commit = 1;
+        mixrow = nj < a.cap ? a.mix + (long)nj * a.ldmix : nullptr;
+    }
     float* Sb = a.S + bh * a.cap * a.E + e;
     const long pe = bh * a.E + e;
-    int n = a.nj;
+    int n = nj;
     f32x4 last = {0.f, 0.f, 0.f, 0.f};
-    if (a.commit) {
+    if (commit) {
         last = gld<f32x4>(a.Cur + pe);
-        gst<f32x4>(Sb + (long)(a.nj - 1) * a.E, last);
+        gst<f32x4>(Sb + (long)(nj - 1) * a.E, last);
         gst<f32x4>(a.Cur + pe, f32x4{0.f, 0.f, 0.f, 0.f});
-        n = a.nj - 1;
+        n = nj - 1;
     }
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (a.mixrow) {
+    if (mixrow) {
         constexpr int U = 8;
         int j = 0;
         for (; j + U <= n; j += U) {
@@ -202,19 +240,19 @@ __global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
             for (int u = 0; u < U; ++u) s[u] = gld<f32x4>(Sb + (long)(j + u) * a.E);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const float w = a.mixrow[j + u];
+                const float w = mixrow[j + u];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) acc[t] = fmaf(w, s[u][t], acc[t]);
             }
         }
         for (; j < n; ++j) {
             const f32x4 s = gld<f32x4>(Sb + (long)j * a.E);
-            const float w = a.mixrow[j];
+            const float w = mixrow[j];
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[t] = fmaf(w, s[t], acc[t]);
         }
-        if (a.commit) {
-            const float w = a.mixrow[n];
+        if (commit) {
+            const float w = mixrow[n];
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[t] = fmaf(w, last[t], acc[t]);
         }

@@ -45,11 +45,11 @@ class Block(nn.Module):
         self.mlp_norm = RMSNorm(dim)
         self.mlp = GatedMLP(dim)
 
-    def forward(self, x, cache=None):
+    def forward(self, x, cache=None, attention_mask=None):
         if cache is None:
-            x = x + self.attn(self.attn_norm(x))[0]
+            x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask)[0]
         else:
-            x = x + self.attn(self.attn_norm(x), past_key_values=cache, use_cache=True)[0]
+            x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask, past_key_values=cache, use_cache=True)[0]
         return x + self.mlp(self.mlp_norm(x))
 
 
@@ -67,30 +67,36 @@ class GPT_MHLA(nn.Module):
             if isinstance(m, (nn.Linear, nn.Embedding)):
                 nn.init.normal_(m.weight, std=0.02)
 
-    def forward(self, input_ids, labels=None, cache=None):
+    def forward(self, input_ids, labels=None, cache=None, attention_mask=None):
         """`cache` (a `DecodeCache`, model built with `exact_decoding=True`): `input_ids` are the tokens AFTER the ones the cache
         has seen -- the whole prompt on an empty cache, then one token per call, or several (the next turn, a piece of a long
         prompt, a draft to verify): on a non-empty cache those take the layer's `mhla_causal_extend` path, one launch chain per
-        layer whatever their number."""
+        layer whatever their number.
+        `attention_mask` [B, T] (0 = padding) is handed to every layer.  With a cache it belongs to the prefill and must be
+        left-padded: every sequence is then decoded as if alone in the batch, at its own position (the layer's ragged decode
+        state), and later calls need no mask.  Logits at padding rows are unspecified."""
         if cache is not None and not self.exact_decoding:
             raise ValueError("GPT_MHLA.forward(cache=...) needs a model built with exact_decoding=True")
         x = self.embeddings(input_ids)
         for blk in self.layers:
-            x = blk(x, cache)
+            x = blk(x, cache, attention_mask)
         logits = self.lm_head(self.norm(x))
         if labels is None:
             return logits
         return F.cross_entropy(logits[:, :-1].reshape(-1, logits.shape[-1]).float(), labels[:, 1:].reshape(-1))
 
     @torch.no_grad()
-    def generate(self, input_ids, max_new_tokens):
+    def generate(self, input_ids, max_new_tokens, attention_mask=None):
         """Greedy decoding: one prefill over `input_ids` [B, T], then one cached step per new token.  Returns the
-        `max_new_tokens` new ids [B, max_new_tokens]; T + max_new_tokens must fit the mixing matrix (`max_seq_len`)."""
+        `max_new_tokens` new ids [B, max_new_tokens]; T + max_new_tokens must fit the mixing matrix (`max_seq_len`).
+        `attention_mask` [B, T]: prompts of different lengths, left-padded to T (0 = padding); every sequence continues from
+        its own length."""
         cache = DecodeCache()
         new = []
         ids = input_ids
         for _ in range(int(max_new_tokens)):
-            ids = self.forward(ids, cache=cache)[:, -1:].argmax(-1)
+            ids = self.forward(ids, cache=cache, attention_mask=attention_mask)[:, -1:].argmax(-1)
+            attention_mask = None   # (the prefill's: the decode state carries the lengths from here on)
             new.append(ids)
         return torch.cat(new, dim=1) if new else input_ids[:, :0]
 

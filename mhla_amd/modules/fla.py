@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops import (CausalState, featmap_rotary, mhla_causal, mhla_causal_extend, mhla_causal_normgate, mhla_causal_state, mhla_causal_step,
+from ..ops import (CausalState, _runs, mhla_causal_prefill, featmap_rotary, mhla_causal, mhla_causal_extend, mhla_causal_normgate, mhla_causal_state, mhla_causal_step,
                    naive_recurrent_mhla, rmsnorm_gate)
 from ..weights import causal_mixing_init
 
@@ -199,9 +199,14 @@ class MHLA(nn.Module):
         chunk operator as otherwise, plus a `CausalState` (ops.py: 4 K V bytes per finished chunk and head, fp32) stored as the
         cache's `recurrent_state`; a later call of one token runs `mhla_causal_step` (norm x gate fused when
         `fuse_norm_and_gate`) and returns exactly the row the chunk operator over the whole sequence would.  A later call of
-        several tokens runs `mhla_causal_extend` once (the same epilogue; launches independent of the token count).  All
-        sequences of the batch share one length: a padding `attention_mask` raises NotImplementedError (an all-ones mask is
-        ignored).  Steps and extensions are inference only (call under `torch.no_grad()`).  Adds no parameters."""
+        several tokens runs `mhla_causal_extend` once (the same epilogue; launches independent of the token count).
+        Padding: the prefill (the call on an empty cache) may carry a LEFT-padded `attention_mask` (each row zeros, then ones;
+        anything else, or `use_short_conv`, raises NotImplementedError).  Every sequence then runs alone -- its own rotary
+        positions, the operator over its real tokens only, zeros at the padding rows of the output; sequences never mix, unlike
+        the packed batch of the non-exact path -- and the state is ragged (`CausalState.lengths`): later calls step all sequences
+        together, each at its own position, and do not read the mask beyond its shape.  An all-ones mask gives a uniform state,
+        and a padding mask on a call whose cached state is uniform raises NotImplementedError.  Steps and extensions are
+        inference only (call under `torch.no_grad()`).  Adds no parameters."""
         super().__init__()
         self.mode = mode
         self.hidden_size = hidden_size
@@ -277,14 +282,26 @@ class MHLA(nn.Module):
         if past_key_values is not None and self.layer_idx is not None and len(past_key_values) > self.layer_idx:
             last_state = past_key_values[self.layer_idx]                      # :249-251
         exact = self.exact_decoding and bool(use_cache) and past_key_values is not None and hasattr(past_key_values, "update")
+        ragged_lengths = None     # a padded prefill: tokens per sequence (left-padded); `ragged`: this call is one, or continues one
+        cached = last_state["recurrent_state"] if last_state is not None else None
+        ragged = exact and isinstance(cached, CausalState) and cached.lengths is not None
         if exact:
             if self.layer_idx is None:
                 raise ValueError("MHLA(exact_decoding=True): the cache is indexed by layer_idx, which is None")
-            if attention_mask is not None:
+            if attention_mask is not None and not ragged:   # (a ragged state carries the lengths: the mask is not read)
                 if not bool(attention_mask.all()):
-                    raise NotImplementedError("MHLA(exact_decoding=True): all sequences of a batch share one length; a padding "
-                                              "attention_mask is not supported with the decode state")
-                attention_mask = None
+                    if isinstance(cached, CausalState):
+                        raise NotImplementedError("MHLA(exact_decoding=True): the cached decode state is uniform (all sequences share "
+                                                  "one length); a padding attention_mask goes with the prefill")
+                    m = attention_mask[:, -q_len:].to(hidden_states.device) != 0
+                    if self.use_short_conv:
+                        raise NotImplementedError("MHLA(exact_decoding=True): use_short_conv with a padding attention_mask")
+                    if m.shape != (batch_size, q_len) or bool((m[:, :-1] & ~m[:, 1:]).any()):
+                        raise NotImplementedError("MHLA(exact_decoding=True): a padding attention_mask must be left-padded, each row "
+                                                  f"zeros then ones over the {q_len} tokens of the call")
+                    ragged_lengths = m.sum(-1).tolist()
+                    ragged = True
+            attention_mask = None
         indices = None
         cu_seqlens = kwargs.get("cu_seqlens", None)
         if attention_mask is not None:                                       # layers/mhla.py:253-256 (get_unpad_data)
@@ -318,7 +335,19 @@ class MHLA(nn.Module):
         # rotary position of every token row: packed sequences restart at every sequence start (rotary.py:68-72 with cu_seqlens);
         # with a padding mask AND a cache offset every sequence continues from its own length (prepare_lens_from_mask, :305-309)
         positions = None
-        if cu_seqlens is not None:
+        if ragged:
+            # every sequence at positions of its own, in the [B, T] layout: row (b, t) is token t - pad_b of a padded prefill (padding
+            # rows: position 0, their output is dropped), token pos_b + t of a later call (the state's device positions: no sync).
+            # The tables are gathered per row, so q and k go through the rotary as one sequence of B T rows.
+            tpos = torch.arange(T, device=q.device)
+            if ragged_lengths is not None:
+                pads = T - torch.tensor(ragged_lengths, device=q.device)
+                positions, table_len = (tpos[None, :] - pads[:, None]).clamp_(min=0).flatten(), T
+            else:
+                positions, table_len = (cached.pos.long()[:, None] + tpos[None, :]).flatten(), cached.seen + T
+            q, k = q.reshape(1, B * T, self.num_heads, self.head_k_dim), k.reshape(1, B * T, self.num_heads, self.head_k_dim)
+            seqlen_offset = 0
+        elif cu_seqlens is not None:
             tpos = torch.arange(T, device=q.device)
             cu = cu_seqlens.to(q.device).long()
             seq = torch.searchsorted(cu, tpos, right=True) - 1
@@ -326,8 +355,9 @@ class MHLA(nn.Module):
             if attention_mask is not None and seqlen_offset > 0:
                 offs = (attention_mask.sum(-1).to(q.device).long() - q_len)[seq]
             positions = tpos - cu[seq] + offs
-        table_len = T + seqlen_offset if positions is None else (
-            (int(attention_mask.shape[1]) if attention_mask is not None and seqlen_offset > 0 else T + seqlen_offset))
+        if not ragged:
+            table_len = T + seqlen_offset if positions is None else (
+                (int(attention_mask.shape[1]) if attention_mask is not None and seqlen_offset > 0 else T + seqlen_offset))
         if self.head_k_dim % 8 == 0:
             # feature map (:297-299) + rotary (:311) in one HIP kernel per tensor and direction
             cos, sin = self.rotary._tables(table_len, q.device, q.dtype)
@@ -343,7 +373,9 @@ class MHLA(nn.Module):
                 self._warned_eager_rotary = True
             q, k = self.feature_map_q(q), self.feature_map_k(k)              # :297-299
             q, k = self.rotary(q, k, seqlen_offset=seqlen_offset, max_seqlen=table_len, positions=positions)   # :311
-        recurrent_state = last_state["recurrent_state"] if last_state is not None else None
+        if ragged:
+            q, k = q.reshape(B, T, self.num_heads, self.head_k_dim), k.reshape(B, T, self.num_heads, self.head_k_dim)
+        recurrent_state = cached
         fused_epilogue = self.use_output_gate and self.fuse_norm_and_gate and q_len > 64
         if exact and isinstance(recurrent_state, CausalState):
             # decoding on the state the prefill (or the calls before) left: one exact step for one token, one extension for several
@@ -357,6 +389,22 @@ class MHLA(nn.Module):
                         norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None)
             if fused_epilogue:
                 o = o.reshape(B, T, self.value_dim)
+        elif ragged_lengths is not None:
+            # padded prefill: the operator (and the fused epilogue) over every sequence's real tokens alone, zeros elsewhere -- run by
+            # run of adjacent sequences of equal length, as mhla_causal_prefill(lengths=, left_padded=True) does
+            if fused_epilogue:
+                g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
+                gn = self.g_norm_swish_gate
+                o = q.new_zeros(B, T, self.num_heads, self.head_v_dim)
+                for i, j, n in _runs(ragged_lengths, B):
+                    if n:
+                        o[i:j, T - n:] = mhla_causal_normgate(q[i:j, T - n:], k[i:j, T - n:], v[i:j, T - n:], self.mixing_matrix, g[i:j, T - n:],
+                                                              gn.weight, gn.eps, summaries=self.summaries)
+                o = o.reshape(B, T, self.value_dim)
+                recurrent_state = mhla_causal_state(k, v, self.mixing_matrix, lengths=ragged_lengths, left_padded=True)
+            else:
+                o, recurrent_state = mhla_causal_prefill(q, k, v, self.mixing_matrix, summaries=self.summaries, lengths=ragged_lengths,
+                                                         left_padded=True)
         elif exact:
             # prefill: the chunk operator for the output (any length: the single-chunk case for <= 64 tokens), and the decode state
             if fused_epilogue:
@@ -399,6 +447,8 @@ class MHLA(nn.Module):
         else:
             o = self.g_norm(o, None).reshape(B, T, self.value_dim)
         o = self.o_proj(o)
+        if ragged_lengths is not None:                                       # zeros at padding rows, as pad_input leaves them
+            o = o.masked_fill(~m.unsqueeze(-1), 0)
         if indices is not None:                                              # pad_input, :362-363
             full = o.new_zeros(batch_size * q_len, o.shape[-1])
             full.index_copy_(0, indices, o.squeeze(0))

@@ -1137,12 +1137,27 @@ class CausalState:
     """Decode state of the causal operator, fp32 whatever the tensor dtype: `S [B, H, cap, K, V]` (K_j^T V_j of every finished
     chunk), `P [B, H, K, V]` (prefix mix of the open chunk), `Cur [B, H, K, V]` (the open chunk's running K^T V), `seen` tokens
     so far.  Every row of the mixing matrix weighs the finished chunks differently, so all of them are kept: 4 K V bytes per
-    chunk and head (128 KB at K = 128, V = 256) -- `nbytes` reports the total.  All sequences of the batch share `seen`."""
+    chunk and head (128 KB at K = 128, V = 256) -- `nbytes` reports the total.  A UNIFORM state (`lengths is None`): all sequences
+    of the batch share `seen`.  A RAGGED state (built with `lengths=`, and ragged from then on even if the lengths are equal): sequence
+    b has seen `lengths[b]` tokens and behaves exactly as if it lived alone in a batch of one.  `lengths` (a tuple of B ints) is the
+    host mirror every check and the boundary decision read; `pos` (int32 [B] on the state's device) holds the same numbers for the
+    kernels, which advance it themselves -- a step costs no copy and no synchronisation; `seen` is kept equal to `max(lengths)`."""
 
-    __slots__ = ("S", "P", "Cur", "seen", "chunk_size")
+    __slots__ = ("S", "P", "Cur", "seen", "chunk_size", "lengths", "pos")
 
-    def __init__(self, S: torch.Tensor, P: torch.Tensor, Cur: torch.Tensor, seen: int = 0, chunk_size: int = 64):
+    def __init__(self, S: torch.Tensor, P: torch.Tensor, Cur: torch.Tensor, seen: int = 0, chunk_size: int = 64, *, lengths=None,
+                 pos: Optional[torch.Tensor] = None):
         self.S, self.P, self.Cur, self.seen, self.chunk_size = S, P, Cur, int(seen), int(chunk_size)
+        self.lengths = self.pos = None
+        if lengths is not None:
+            lengths = _lengths_tuple("CausalState", lengths, S.shape[0], None)
+            if pos is None:
+                pos = torch.tensor(lengths, dtype=torch.int32, device=S.device)
+            elif pos.dtype != torch.int32 or tuple(pos.shape) != (len(lengths),):
+                raise ValueError(f"CausalState: pos must be an int32 tensor of shape ({len(lengths)},), got {pos.dtype} {tuple(pos.shape)}")
+            self.lengths, self.pos, self.seen = lengths, pos, max(lengths)
+        elif pos is not None:
+            raise ValueError("CausalState: pos given without lengths")
 
     @classmethod
     def empty(cls, B: int, H: int, K: int, V: int, capacity_chunks: int, device="cuda", chunk_size: int = 64) -> "CausalState":
@@ -1157,14 +1172,55 @@ class CausalState:
 
     @property
     def nbytes(self) -> int:
-        return 4 * (self.S.numel() + self.P.numel() + self.Cur.numel())
+        return 4 * (self.S.numel() + self.P.numel() + self.Cur.numel() + (self.pos.numel() if self.pos is not None else 0))
 
     def clone(self) -> "CausalState":
-        return CausalState(self.S.clone(), self.P.clone(), self.Cur.clone(), self.seen, self.chunk_size)
+        return CausalState(self.S.clone(), self.P.clone(), self.Cur.clone(), self.seen, self.chunk_size, lengths=self.lengths,
+                           pos=self.pos.clone() if self.pos is not None else None)
+
+    @classmethod
+    def cat(cls, states) -> "CausalState":
+        """The states of separately prefilled requests as one batch (copies; the inputs stay usable).  Uniform inputs that have all
+        seen the same number of tokens give a uniform state; differing lengths, or any ragged input, give a ragged one.  ValueError
+        when H, K, V, capacity, chunk size or device differ."""
+        states = list(states)
+        if not states or not all(isinstance(s, CausalState) for s in states):
+            raise ValueError("CausalState.cat: a non-empty sequence of CausalState")
+        a = states[0]
+        for s in states[1:]:
+            if tuple(s.S.shape[1:]) != tuple(a.S.shape[1:]) or s.chunk_size != a.chunk_size or s.S.device != a.S.device:
+                raise ValueError(f"CausalState.cat: {s!r} does not go with {a!r} (H, K, V, capacity, chunk size and device must agree)")
+        S, P, Cur = (torch.cat([getattr(s, n) for s in states], dim=0) for n in ("S", "P", "Cur"))
+        if all(s.lengths is None and s.seen == a.seen for s in states):
+            return cls(S, P, Cur, a.seen, a.chunk_size)
+        lengths = [n for s in states for n in (s.lengths if s.lengths is not None else (s.seen,) * s.S.shape[0])]
+        return cls(S, P, Cur, 0, a.chunk_size, lengths=lengths)
 
     def __repr__(self):
         B, H, cap, K, V = self.S.shape
-        return f"CausalState(B={B}, H={H}, K={K}, V={V}, capacity_chunks={cap}, seen={self.seen}, device={self.S.device})"
+        seen = f"seen={self.seen}" if self.lengths is None else f"lengths={self.lengths}"
+        return f"CausalState(B={B}, H={H}, K={K}, V={V}, capacity_chunks={cap}, {seen}, device={self.S.device})"
+
+
+def _lengths_tuple(fn, lengths, B, T):
+    """`lengths` (a list or a tensor; reading a device tensor synchronises) as the host mirror of a ragged state: B ints in 0 .. T."""
+    lengths = tuple(int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths))
+    if len(lengths) != B:
+        raise ValueError(f"{fn}: lengths has {len(lengths)} entries, expected B={B}")
+    if any(n < 0 or (T is not None and n > T) for n in lengths):
+        raise ValueError(f"{fn}: lengths={lengths} must be in 0 .." + (f" T={T}" if T is not None else ""))
+    return lengths
+
+
+def _runs(lengths, nb):
+    """(first, end, length) of every run of adjacent sequences with equal length, none longer than `nb` sequences."""
+    i = 0
+    while i < len(lengths):
+        j = i + 1
+        while j < len(lengths) and j - i < nb and lengths[j] == lengths[i]:
+            j += 1
+        yield i, j, lengths[i]
+        i = j
 
 
 @functools.lru_cache(maxsize=64)
@@ -1186,27 +1242,48 @@ def _causal_state_init(k, v, mix, state: CausalState):
 
 
 def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, chunk_size: int = 64,
-                        scale: Optional[float] = None, *, summaries: str = "tf32", capacity_chunks: Optional[int] = None):
+                        scale: Optional[float] = None, *, summaries: str = "tf32", capacity_chunks: Optional[int] = None,
+                        lengths=None, left_padded: bool = False):
     """`(o, state)`: `o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries)` and the `CausalState`
     after these T tokens, from which `mhla_causal_step` continues one token at a time (T = 0: an empty state).  The state is
     built from k, v in exact fp32 products, independently of `summaries`; no autograd passes through it.
-    capacity_chunks: chunks the state can hold (64 tokens each), default and at most the rows L of the mixing matrix."""
+    capacity_chunks: chunks the state can hold (64 tokens each), default and at most the rows L of the mixing matrix.
+    lengths, left_padded: a padded batch, as `mhla_causal_state` takes it -- the state is ragged, every sequence's rows of `o` are
+    those of `mhla_causal` over that sequence alone (one call per run of adjacent sequences of equal length), padding rows zero."""
     if q.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
     if int(chunk_size) != 64:
         raise ValueError(f"mhla_causal_prefill: chunk_size={chunk_size}, the decode state supports 64 only")
-    o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries)
-    return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks)
+    if lengths is None:
+        o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries)
+        return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks)
+    B, T, H, _ = q.shape
+    lengths = _lengths_tuple("mhla_causal_prefill", lengths, B, T)
+    state = mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks, lengths=lengths, left_padded=left_padded)
+    o = torch.zeros((B, T, H, v.shape[-1]), dtype=q.dtype, device=q.device)
+    for i, j, n in _runs(lengths, B):
+        if n:
+            t0 = T - n if left_padded else 0
+            o[i:j, t0:t0 + n] = mhla_causal(q[i:j, t0:t0 + n], k[i:j, t0:t0 + n], v[i:j, t0:t0 + n], mixing_matrix, chunk_size, scale,
+                                            summaries=summaries)
+    return o, state
 
 
-def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, *, capacity_chunks: Optional[int] = None) -> CausalState:
+def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, *, lengths=None, left_padded: bool = False,
+                      capacity_chunks: Optional[int] = None) -> CausalState:
     """The `CausalState` after the T tokens of k `[B, T, H, K]`, v `[B, T, H, V]` (the state half of `mhla_causal_prefill`;
-    chunk 64).  T = 0: an empty state."""
+    chunk 64).  T = 0: an empty state.
+    lengths (a list or a tensor of B ints in 0 .. T; a device tensor is read once, which synchronises): a padded batch -- the tokens
+    of sequence b are rows `[0, lengths[b])`, or `[T - lengths[b], T)` with `left_padded`, and the state is ragged (`CausalState`):
+    every sequence as if prefilled alone, `lengths[b] = 0` an empty one.  Built run by run of adjacent sequences of equal length."""
     if k.dim() != 4 or v.dim() != 4:
         raise ValueError("k: [B, T, H, K], v: [B, T, H, V]")
     B, T, H, K = k.shape
     V = v.shape[-1]
     _check_like(k, "mhla_causal_state", v=(v, (B, T, H, V)))
+    if lengths is not None:
+        lengths = _lengths_tuple("mhla_causal_state", lengths, B, T)
+        T = max(lengths)
     L = mixing_matrix.shape[0]
     cap = L if capacity_chunks is None else int(capacity_chunks)
     if not 0 < cap <= L:
@@ -1219,6 +1296,13 @@ def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Ten
     nb = _MAX_GRID_BH // H
     with torch.no_grad():
         state = CausalState.empty(B, H, K, V, cap, k.device, 64)
+        if lengths is not None:
+            for i, j, n in _runs(lengths, nb):
+                if n:
+                    t0 = k.shape[1] - n if left_padded else 0
+                    part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], 0, 64)
+                    _causal_state_init(k[i:j, t0:t0 + n].detach(), v[i:j, t0:t0 + n].detach(), mixing_matrix, part)
+            return CausalState(state.S, state.P, state.Cur, 0, 64, lengths=lengths)
         for i in range(0, B if T else 0, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
             part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], 0, 64)
             _causal_state_init(k[i:i + nb].detach(), v[i:i + nb].detach(), mixing_matrix, part)
@@ -1237,7 +1321,8 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
     is refused here, in an order callers rely on -- tensors like q, dtype, state shapes, devices, norm_weight, requires-grad, GPU,
     matrix shape, chunk size, rows / capacity (IndexError), epilogue arguments, state contiguity -- before anything is launched
     or `state` is touched.  Returns (q, k, v, gate, mixf, wf, pos, scale, want_y): the token tensors addressable in place or as
-    contiguous copies, the mixing matrix and the norm weight in fp32, the position of the first token."""
+    contiguous copies, the mixing matrix and the norm weight in fp32, the position of the first token (of the furthest sequence
+    of a ragged state, whose `seen` is `max(lengths)`: rows and capacity are checked against it)."""
     B, T, H, K = q.shape
     V = v.shape[-1]
     try:
@@ -1275,6 +1360,9 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
         raise ValueError(f"{fn}: gate / norm_weight given with epilogue=False")
     if not (state.S.is_contiguous() and state.P.is_contiguous() and state.Cur.is_contiguous()):
         raise ValueError(f"{fn}: state tensors must be contiguous")
+    if state.lengths is not None and (len(state.lengths) != B or state.pos is None or state.pos.device != dev or state.pos.dtype != torch.int32
+                                      or tuple(state.pos.shape) != (B,) or not state.pos.is_contiguous()):
+        raise ValueError(f"{fn}: a ragged state carries B={B} lengths and `pos`, a contiguous int32 [B] tensor on {dev}")
     # (nothing from here to the end of the call is recorded for autograd, with or without torch.no_grad(): grad mode is off or no
     # token tensor requires grad, both matrices are detached, and the launch reads and writes through raw pointers)
     q, k, v = (t if _step_view_ok(t) else t.contiguous() for t in (q, k, v))
@@ -1305,6 +1393,23 @@ def _causal_decode(q, k, v, gate, mixf, wf, pos, scale, want_y, fn, state, res, 
     _lib.check(rc, fn)
 
 
+@_device_guard
+def _causal_step_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, pos, lengths, res, norm_eps):
+    """One launch chain of `mhla_causal_step_ragged` on what `_decode_prepare` returned, for the sequences `state` (a batch slice)
+    holds: `pos` their device positions, which the chain advances, `lengths` the host mirror of the same numbers."""
+    lib = _lib.load()
+    B, _, H, K = q.shape
+    V = v.shape[-1]
+    dt = _dtype_code(q)
+    ws = _ws(_step_ws_bytes(B, H, K, V, dt), q.device)
+    rc = lib.mhla_causal_step_ragged(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+                                     state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), max(lengths), int(any(n % 64 == 63 for n in lengths)),
+                                     NULL_VIEW if want_y else _view(res), _view_or_null(gate), _ptr(wf), float(norm_eps),
+                                     _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K, V, state.chunk_size,
+                                     float(scale), dt, _stream())
+    _lib.check(rc, "mhla_causal_step_ragged")
+
+
 def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
                      scale: Optional[float] = None, gate: Optional[torch.Tensor] = None, norm_weight: Optional[torch.Tensor] = None,
                      norm_eps: float = 1e-5, epilogue: Optional[bool] = None) -> torch.Tensor:
@@ -1315,7 +1420,11 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
     launch chain.  Inference only: nothing is recorded for autograd, and an input that requires grad while grad mode is on
     raises.  The step that would open chunk L of an [L, L] matrix (or exceed the state's capacity) raises IndexError and
     leaves the state untouched.  Cost per token: P and Cur read, Cur written (12 K V bytes per (b, h)); every 64th step also
-    closes the chunk and re-mixes the finished ones (4 K V bytes per finished chunk)."""
+    closes the chunk and re-mixes the finished ones (4 K V bytes per finished chunk).
+    On a ragged state (`state.lengths`) the token of sequence b is at position `lengths[b]`, the row returned is that of
+    `mhla_causal` over that sequence's own tokens, and each sequence closes its chunk where its own position says so -- one
+    launch chain for the batch, the positions advanced on the device (no copy, no synchronisation); every entry of `lengths`
+    and `seen` grow by one.  The IndexError is raised when the longest sequence would not fit."""
     if not isinstance(state, CausalState):
         raise TypeError(f"mhla_causal_step: state must be a CausalState, got {type(state).__name__}")
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
@@ -1325,7 +1434,29 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
         raise ValueError(f"mhla_causal_step takes one token per call (T = 1), got T = {T}")
     prepared = _decode_prepare("mhla_causal_step", q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue)
     res = _alloc_like_tokens(B, 1, H, v.shape[-1], q)
-    _causal_decode(*prepared, "mhla_causal_step", state, res, norm_eps)
+    if state.lengths is None:
+        _causal_decode(*prepared, "mhla_causal_step", state, res, norm_eps)
+        state.seen += 1
+        return res
+    q, k, v, gate, mixf, wf, _, scale, want_y = prepared
+    nb = _MAX_GRID_BH // H
+    # What the library checks per launch, for every slice before the first launch (a refusal after an earlier slice had run would
+    # leave its device positions ahead of `lengths`): a slice with a sequence on a boundary needs the row after its furthest
+    # sequence's chunk, unless that chunk is the state's last.
+    for i in range(0, B, nb):
+        part = state.lengths[i:i + nb]
+        need = max(part) // 64 + 1 + (any(n % 64 == 63 for n in part) and max(part) // 64 + 1 < state.capacity_chunks)
+        if mixf.shape[1] < need:
+            raise IndexError(f"mhla_causal_step: a sequence of lengths {part} closes its chunk: row {need - 1} of mixing_matrix is read, "
+                             f"which has only {mixf.shape[1]} columns")
+    if B <= nb:   # the usual case, one launch chain: no views to build
+        _causal_step_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, state.pos, state.lengths, res, norm_eps)
+    for i in range(0, B if B > nb else 0, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
+        sl = lambda x: None if x is None else x[i:i + nb]
+        part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], 0, 64)
+        _causal_step_ragged(sl(q), sl(k), sl(v), sl(gate), mixf, wf, scale, want_y, part, state.pos[i:i + nb], state.lengths[i:i + nb],
+                            sl(res), norm_eps)
+    state.lengths = tuple(n + 1 for n in state.lengths)
     state.seen += 1
     return res
 
@@ -1347,7 +1478,10 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     Epilogue arguments, strided views, inference only and the IndexError of a sequence beyond the mixing matrix or the state's
     capacity (raised before anything is launched, the state untouched): as `mhla_causal_step`.  The workspace holds one fp32
     [K, V] tile per (b, h) and chunk touched after the first, plus the T fp32 output rows; an extension that would need more than
-    `EXTEND_WS_CAP_BYTES` (256 MiB) is cut into consecutive calls at chunk boundaries."""
+    `EXTEND_WS_CAP_BYTES` (256 MiB) is cut into consecutive calls at chunk boundaries.
+    On a ragged state every sequence gets T new tokens, at positions `lengths[b] ..`: the same launch chain runs once per run of
+    adjacent sequences of equal length (correct, but not launch-optimal across differing lengths: there is no ragged extend
+    kernel), then T is added to the device positions and to `lengths`."""
     if not isinstance(state, CausalState):
         raise TypeError(f"mhla_causal_extend: state must be a CausalState, got {type(state).__name__}")
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
@@ -1366,15 +1500,20 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     # tokens per call: whole chunks, so that nb H (K V / 64 + V) 4 bytes per token stay under the cap (and under the C ABI's 65535)
     per_tok = nb * H * (K * V // 64 + V) * 4
     step_t = min(max(64, EXTEND_WS_CAP_BYTES // per_tok // 64 * 64), 65472)
-    for i in range(0, B, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
-        part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], pos, 64)
+    # (batches beyond one launch's (b, h) range: see mhla_blockmix)
+    runs = ((i, min(B, i + nb), pos) for i in range(0, B, nb)) if state.lengths is None else _runs(state.lengths, nb)
+    for i, j, p in runs:
+        part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], p, 64)
         t0 = 0
         while t0 < T:
             # the first piece fills the open chunk, so that every later one starts on a boundary
-            t1 = min(T, t0 + step_t - (pos + t0) % 64)
-            sl = lambda x: None if x is None else x[i:i + nb, t0:t1]
-            _causal_decode(sl(q), sl(k), sl(v), sl(gate), mixf, wf, pos + t0, scale, want_y, "mhla_causal_extend", part, sl(res), norm_eps)
+            t1 = min(T, t0 + step_t - (p + t0) % 64)
+            sl = lambda x: None if x is None else x[i:j, t0:t1]
+            _causal_decode(sl(q), sl(k), sl(v), sl(gate), mixf, wf, p + t0, scale, want_y, "mhla_causal_extend", part, sl(res), norm_eps)
             t0 = t1
+    if state.lengths is not None:
+        state.pos += T
+        state.lengths = tuple(n + T for n in state.lengths)
     state.seen = pos + T
     return res
 

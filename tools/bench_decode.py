@@ -16,6 +16,17 @@ configurations, against (a) the same T tokens as single steps (real ones: the bo
 ratios and the device time of each kernel of the extension.  `--extend --workload`: a prefill of 8000 tokens and one extension
 of 1024 at B = 1, H = 4, K = 128, V = 256, for a trace of its own.
 
+`--ragged`: the step on a RAGGED state (one position per sequence, `mhla_causal_step_ragged`) against the uniform step at the same B, at
+the C5 head (H = 4, K = 128, V = 256), B = 8 and 32: the ragged lengths lie in four different chunks around chunk 15 (offsets -2, -1,
++1, +2, so that the boundary kernel reads as many finished chunks on average as the uniform one at chunk 15), every sequence at another
+place in its chunk.  Alternating in the same run, `--reps` times, non-boundary and boundary steps separately; per variant the wall time
+of a call (events around `--steps` calls) and the DEVICE time of its kernels (the per-launch event hook, 20 calls per repetition), each
+with median, min and max.  Every call must be the same step, so the host side of the state (`seen`, `lengths`) is put back before
+every call as above, and so are the device positions of the ragged state, which the launch chain itself advances: a 4 B-byte device
+copy before every call, so that host mirror and device array agree at every launch, as they do in use.  The uniform variants are given
+the same copy (into a spare tensor), so that all four wall times include that one extra launch; the device times count the library's
+kernels only.  The ragged step moves the uniform step's bytes plus 4 B.
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -123,6 +134,71 @@ def roll_sweep(B, H, K, V, steps):
     print(json.dumps({"roll_sweep": {"B": B, "H": H, "K": K, "V": V}, "by_chunk": out}), flush=True)
 
 
+def ragged_config(B, H, K, V, steps, reps):
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    q, k, v = token(B, H, K, V, g)
+    i0 = 15
+    chunks = [i0 + (-2, -1, 1, 2)[b % 4] for b in range(B)]
+
+    def make(lengths):
+        st = mhla_amd.CausalState.empty(B, H, K, V, L, DEV)
+        st.S[:, :, :i0 + 3].normal_(0, 0.1)
+        st.P.normal_(0, 0.1)
+        return st if lengths is None else mhla_amd.CausalState(st.S, st.P, st.Cur, lengths=lengths)
+
+    len_step = tuple(c * 64 + (7 * b) % 63 for b, c in enumerate(chunks))
+    len_roll = tuple(c * 64 + 63 for c in chunks)
+    uni, rag = make(None), make(len_step)
+    pos_step, pos_roll = (torch.tensor(x, dtype=torch.int32, device=DEV) for x in (len_step, len_roll))
+    spare = torch.empty_like(pos_roll)
+
+    def put_back(lengths):
+        rag.lengths, rag.seen = lengths, max(lengths)
+
+    def u_step():
+        uni.seen = i0 * 64 + 36
+        spare.copy_(pos_step)
+        mhla_amd.mhla_causal_step(q, k, v, mix, uni)
+
+    def r_step():
+        put_back(len_step)
+        rag.pos.copy_(pos_step)
+        mhla_amd.mhla_causal_step(q, k, v, mix, rag)
+
+    def u_roll():
+        uni.seen = i0 * 64 + 63
+        spare.copy_(pos_roll)
+        mhla_amd.mhla_causal_step(q, k, v, mix, uni)
+
+    def r_roll():
+        put_back(len_roll)
+        rag.pos.copy_(pos_roll)
+        mhla_amd.mhla_causal_step(q, k, v, mix, rag)
+
+    wall = {n: [] for n in ("uniform_step", "ragged_step", "uniform_roll", "ragged_roll")}
+    dev = {n: [] for n in wall}
+    kern = {}
+    fns = {"uniform_step": u_step, "ragged_step": r_step, "uniform_roll": u_roll, "ragged_roll": r_roll}
+    with torch.no_grad():
+        for _ in range(reps):
+            for n, fn in fns.items():
+                wall[n].append(batch_us(fn, steps))
+            for n, fn in fns.items():
+                kern[n] = kernel_times(fn, iters=20)
+                dev[n].append(sum(kern[n].values()))
+            uni.Cur.zero_()
+            rag.Cur.zero_()
+    nbytes = 3 * B * H * K * V * 4 + B * H * (2 * K + 2 * V) * 2
+    rec = {"ragged": {"B": B, "H": H, "K": K, "V": V, "chunks": sorted(set(chunks)), "uniform_chunk": i0}, "steps_per_batch": steps, "reps": reps,
+           "wall_us": {n: spread(x) for n, x in wall.items()}, "device_us": {n: spread(x) for n, x in dev.items()},
+           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()},
+           "step_bytes": {"uniform": nbytes, "ragged": nbytes + 4 * B},
+           "ragged_step_device_within_uniform_spread": min(dev["uniform_step"]) <= statistics.median(dev["ragged_step"]) <= max(dev["uniform_step"])}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def extend_config(B, H, K, V, pos, T, reps, parent_iters):
     g = torch.Generator().manual_seed(1)
     Lx = L + 16                                   # pos 8000 + 1024 tokens: 141 chunks
@@ -209,8 +285,12 @@ if __name__ == "__main__":
     ap.add_argument("--parent-iters", type=int, default=5)
     ap.add_argument("--workload", action="store_true")
     ap.add_argument("--extend", action="store_true")
+    ap.add_argument("--ragged", action="store_true")
     a = ap.parse_args()
-    if a.extend and a.workload:
+    if a.ragged:
+        for B in (8, 32):
+            ragged_config(B, 4, 128, 256, max(200, a.steps), a.reps)
+    elif a.extend and a.workload:
         extend_workload()
     elif a.extend:
         for H, K, V in ((4, 128, 256), (4, 256, 512)):
