@@ -352,6 +352,30 @@ int mhla_causal_step_ragged(mhla_view q, mhla_view k, mhla_view v, const float* 
                             const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V,
                             int chunk, float scale, int dtype, void* stream);
 
+/* mhla_causal_step_dev: the device-positioned step -- mhla_causal_step_ragged whose launch chain and arguments depend on no
+ * position, so that one captured graph (hipGraph) replays it token after token (added without a change of any existing signature
+ * or behaviour: MHLA_ABI_VERSION stays 9).  No `max_pos`, no `any_boundary`: every call enqueues the same three launches (step,
+ * boundary, finish), and the bound on pos_dev[b] is the state's capacity.  Per sequence b, with p = pos_dev[b] read on the device:
+ *   LIVE   (0 <= p < chunk * cap_chunks): exactly the ragged step (the same bits); the chunk closes only if p % chunk == chunk - 1
+ *          (P from row p / chunk + 1 of mix, or P = 0 when that chunk was the state's last); pos_dev[b] = p + 1.
+ *   FROZEN (any other p -- a sequence whose state is full, or a caller's mark such as -1): a defined branch, not an error: S, P,
+ *          Cur and pos_dev[b] are untouched, the sequence's row of `out` / `y` is written as zeros (o = 0 through the epilogue: y
+ *          is zero for finite gate and weight), and full_dev[b] = 1.  full_dev (device int32 [B]) is never cleared by the library.
+ * No content of pos_dev can address outside S, the matrix or the tables: chunk index and matrix row are < cap_chunks, the table
+ * row < tab_rows.  Hence the static checks, all MHLA_EINVAL before any launch: ldmix >= cap_chunks (the matrix has at least
+ * cap_chunks rows, any of which may be read); workspace as mhla_causal_step_ws_bytes; the others as mhla_causal_step.
+ * Fused q / k prologue of the fla layer (the call then takes the projections' q and k): `feature_map` (0 identity, 1 relu,
+ * 2 elu + 1) and then, with `rope_cos` / `rope_sin` (given together or both NULL), the NeoX rotary at row p of the tables --
+ * [tab_rows][K/2] in the tensor dtype with row stride ld_tab, as mhla_featmap_rotary takes them (ld_tab >= K / 2, a multiple of 4,
+ * bases aligned to 4 elements) and tab_rows >= chunk * cap_chunks.  Needs K % 8 == 0.  The fp32 arithmetic is that of
+ * mhla_featmap_rotary and the result is rounded to the tensor dtype where that call stores it, so a state advanced by fused
+ * steps is the state mhla_featmap_rotary + mhla_causal_step(_ragged) leave, bit for bit. */
+int mhla_causal_step_dev(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                         float* Cur, int32_t* pos_dev, int32_t* full_dev, const void* rope_cos, const void* rope_sin, int64_t ld_tab,
+                         int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                         mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
+                         void* stream);
+
 /* mhla_causal_extend: T >= 1 new tokens (q, k: [B,T,H,K]; v, out, y, gate: [B,T,H,V]) on a state with `pos` tokens seen, in a
  * number of launches that does not depend on T.  out = rows pos .. pos + T - 1 of the forward over the whole sequence, the
  * state afterwards is what T steps leave (the caller advances pos by T).  With i = pos / chunk, r = pos % chunk the tokens

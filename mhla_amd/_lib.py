@@ -80,6 +80,9 @@ SIGNATURES = {
     "mhla_causal_step_ragged": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                         View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int,
                                         c_float, c_int, c_void_p]),
+    "mhla_causal_step_dev": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int64, c_int64, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int,
+                                     c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "mhla_causal_extend_ws_bytes": (c_size_t, [c_int] * 5 + [c_int64, c_int]),
     "mhla_causal_extend": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, View, View,
                                    c_void_p, c_float, View, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_float, c_int,

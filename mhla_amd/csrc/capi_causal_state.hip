@@ -1,5 +1,5 @@
 // C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
-// (mhla_causal_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_extend; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// (mhla_causal_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
@@ -179,6 +179,58 @@ int mhla_causal_step_ragged(mhla_view q, mhla_view k, mhla_view v, const float* 
         }
         const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, nsplit, pos_dev};
         RC(launch(k_cs_step_finish<ET>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
+    });
+    return MHLA_OK;
+}
+
+int mhla_causal_step_dev(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                         float* Cur, int32_t* pos_dev, int32_t* full_dev, const void* rope_cos, const void* rope_sin, int64_t ld_tab,
+                         int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                         mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
+                         void* stream) {
+    RC(cst_check(B, H, K, V, chunk, dtype));
+    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(v);
+    if (!out.ptr && !y.ptr) return fail(MHLA_EINVAL, "out and y both null");
+    if (out.ptr) CHECK_VIEW(out);
+    if (y.ptr) CHECK_VIEW(y);
+    if (gate.ptr) CHECK_VIEW(gate);
+    if ((gate.ptr || norm_w) && !y.ptr) return fail(MHLA_EINVAL, "gate / norm_w given without y");
+    RC(cst_check_state(S, cap_chunks, P, Cur));
+    if (cap_chunks > INT32_MAX / 64) return fail(MHLA_ENOTSUP, "cap_chunks=%d: positions beyond int32", cap_chunks);
+    if (!pos_dev || ((uintptr_t)pos_dev) % 4) return fail(MHLA_EINVAL, "pos_dev null or not 4-byte aligned");
+    if (!full_dev || ((uintptr_t)full_dev) % 4) return fail(MHLA_EINVAL, "full_dev null or not 4-byte aligned");
+    // every bound is the capacity: whichever chunk a sequence is in, rows and columns 0 .. cap_chunks - 1 of mix may be read
+    if (!mix || ldmix < cap_chunks)
+        return fail(MHLA_EINVAL, "mix null or ldmix=%d < cap_chunks=%d (the matrix is read up to row %d)", ldmix, cap_chunks, cap_chunks - 1);
+    if (feature_map < 0 || feature_map > 2) return fail(MHLA_EINVAL, "feature_map %d: 0 identity, 1 relu, 2 elu+1", feature_map);
+    if (!rope_cos != !rope_sin) return fail(MHLA_EINVAL, "rope_cos and rope_sin must be given together");
+    const bool pro = rope_cos || feature_map;
+    if (pro && (K & 7)) return fail(MHLA_EINVAL, "K=%d: the fused prologue needs K %% 8 == 0", K);
+    if (rope_cos) {
+        if (ld_tab < K / 2 || (ld_tab & 3)) return fail(MHLA_EINVAL, "cos/sin tables: ld_tab=%lld < K/2 or not a multiple of 4", (long long)ld_tab);
+        const size_t al = dtype == MHLA_F32 ? 16 : 8;
+        if (((uintptr_t)rope_cos | (uintptr_t)rope_sin) % al) return fail(MHLA_EINVAL, "cos/sin tables must be %zu-byte aligned", al);
+        if (tab_rows < (int64_t)64 * cap_chunks || tab_rows > INT32_MAX)
+            return fail(MHLA_EINVAL, "tab_rows=%lld: the tables need a row per position, %lld (64 cap_chunks)", (long long)tab_rows, (long long)64 * cap_chunks);
+    }
+    const size_t need = cst_ws_bytes(B, H, K, V);
+    if (!ws || ws_bytes < need) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+    if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int BH = B * H, kr = cst_rows((size_t)BH, K, V), nsplit = (K + kr - 1) / kr, max_pos = 64 * cap_chunks - 1;
+    const long E = (long)K * V;
+    // always the same three launches, none of whose arguments depends on a position: step and roll address by pos_dev, the
+    // finish -- one thread per sequence reads it, none else -- advances it or sets full_dev
+    DISPATCH_T(dtype, {
+        const CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, H, K, V, kr, nsplit, pos_dev, ldmix, max_pos,
+                           rope_cos, rope_sin, (long)ld_tab, (int)tab_rows, feature_map};
+        const dim3 grid((V + CST_VT - 1) / CST_VT, nsplit, BH);
+        if (pro) RC(launch(k_cs_step<ET, true, true, true>, grid, dim3(CST_THREADS), 0, st, "k_cs_step_dev<pro>", s));
+        else     RC(launch(k_cs_step<ET, true, true, false>, grid, dim3(CST_THREADS), 0, st, "k_cs_step_dev", s));
+        const CsRollArgs r{S, P, Cur, nullptr, E, cap_chunks, 0, 0, pos_dev, mix, ldmix, max_pos, H};
+        RC(launch(k_cs_roll<true>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll_ragged", r));
+        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, nsplit, pos_dev, max_pos, full_dev};
+        RC(launch(k_cs_step_finish<ET, true>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish_dev", f));
     });
     return MHLA_OK;
 }

@@ -16,6 +16,16 @@
 // at all.  Tiling, K split, row walk and the order of every sum are the uniform ones, so equal positions give the uniform bits.
 // pos[b] advances in k_cs_step_finish, the last launch of the ragged chain (step, roll, finish) and the only one that does not
 // address by it: no workgroup writes pos[b] in a launch in which another reads it.
+// Device-positioned steps (DEV; mhla_causal_step_dev): a launch chain whose shape and arguments do not depend on the positions
+// at all, so that a captured graph can replay it token after token.  Always step, roll, finish; the bound on pos[b] is the
+// state's capacity instead of a number the host vouches for per call.  A sequence with 0 <= pos[b] < 64 cap is LIVE and takes
+// the ragged step (the same tiling, K split, row walk and order of every sum: the same bits).  Any other pos[b] makes it FROZEN,
+// a defined branch: its workgroups touch neither P, Cur nor S, write zeros as their partial sums (so the finish really writes
+// the row: o = 0, and y = 0 through the epilogue), pos[b] stays, and the finish sets full[b] = 1.  The roll is the ragged one
+// with max_pos = 64 cap - 1: it returns after reading pos[b] unless that sequence is live and on a boundary.  The finish reads
+// and writes pos[b] in ONE thread per sequence and nowhere else, so the rule above holds.  With PRO the step applies the fla
+// layer's q / k prologue itself (feature map, then the NeoX rotary at row pos[b] of the cos / sin tables) where it loads q[r]
+// and k[r]: fmrot_* (common.hpp), the arithmetic k_fmap_rotary runs, rounded to the tensor dtype where that kernel stores.
 // Memory-bound (P and Cur read, Cur written: 12 K V bytes per (b, h) and token); plain fp32 FMA, no MFMA, no atomics: every
 // sum has a fixed order, so results repeat bit for bit.  The state is fp32 whatever the tensor dtype: Cur takes up to 64
 // rank-1 updates and P sums up to L chunks -- a 16-bit state would round at every token.
@@ -39,6 +49,11 @@ struct CsStepArgs {
     // RAGGED only
     const int* pos;        // [B] tokens seen per sequence
     int ldmix, max_pos;    // row stride of mix; the largest position the host vouches for (a pos[b] outside 0 .. max_pos is clamped)
+    // DEV only (max_pos = 64 cap - 1: a pos[b] outside 0 .. max_pos is a frozen sequence)
+    const void* cos;       // PRO: [tab_rows][ldt] rotary tables in the tensor dtype, K / 2 columns read
+    const void* sin;
+    long ldt;
+    int tab_rows, fmap;    // tab_rows >= 64 cap (the host checked); feature map: 0 identity, 1 relu, 2 elu + 1
 };
 
 // pos[b] as the ragged step addresses by it.  Defence only: the caller keeps the array equal to its host mirror, and then the clamp
@@ -55,20 +70,51 @@ template <> __device__ __forceinline__ void cst_st1<float>(float* p, float x) { 
 template <> __device__ __forceinline__ void cst_st1<bf16_t>(bf16_t* p, float x) { p->v = cvt_bf16(x); }
 template <> __device__ __forceinline__ void cst_st1<f16_t>(f16_t* p, float x) { p->v = (_Float16)x; }
 
+// element r of a token's q or k row x [K] after the layer's prologue, as the tensor would hold it: f(x[r]) rotated with its
+// partner f(x[r +- K / 2]) by the angle in row `cosr` / `sinr` of the tables (null: no rotation), rounded to T
+template <typename T>
+__device__ __forceinline__ float cst_pro1(const T* x, int r, int half, const T* cosr, const T* sinr, int fmap) {
+    if (!cosr) return stored_value<T>(fmrot_map(cst_ld1(x + r), fmap));   // (a feature map without rotary)
+    const bool lo = r < half;
+    const int j = lo ? r : r - half;
+    const float x0 = fmrot_map(cst_ld1(x + j), fmap), x1 = fmrot_map(cst_ld1(x + j + half), fmap);
+    const float c = cst_ld1(cosr + j), s = cst_ld1(sinr + j);
+    return stored_value<T>(lo ? fmrot_lo(x0, x1, c, s) : fmrot_hi(x0, x1, c, s));
+}
+
 // grid (ceil(V / 64), nsplit, B H)
-template <typename T, bool RAGGED = false>
+template <typename T, bool RAGGED = false, bool DEV = false, bool PRO = false>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
+    static_assert(!DEV || RAGGED, "DEV is the ragged step, bounded by the capacity");
+    static_assert(!PRO || DEV, "the fused prologue goes with the device-positioned step");
     __shared__ __attribute__((aligned(16))) float red[CST_RG][CST_VT];
     const int tid = threadIdx.x, c4 = (tid & 15) * 4, rg = tid >> 4;
     const int bh = blockIdx.z, b = bh / a.H, h = bh - b * a.H;
     const int col = blockIdx.x * CST_VT + c4;
     const int k0 = blockIdx.y * a.kr, k1 = min(a.K, k0 + a.kr);
-    const bool live = col < a.V;   // (V % 4 == 0: a thread's four columns are inside or outside together)
+    bool live = col < a.V;   // (V % 4 == 0: a thread's four columns are inside or outside together)
     const T* qb = (const T*)a.q.ptr + b * a.q.sb + h * a.q.sh;
     const T* kb = (const T*)a.k.ptr + b * a.k.sb + h * a.k.sh;
     const T* vb = (const T*)a.v.ptr + b * a.v.sb + h * a.v.sh;
     float mii;
-    if constexpr (RAGGED) {
+    [[maybe_unused]] const T* cosr = nullptr;
+    [[maybe_unused]] const T* sinr = nullptr;
+    if constexpr (DEV) {
+        int p = a.pos[b];
+        if (p < 0 || p > a.max_pos) {   // frozen: zeros as partial sums, the state untouched
+            live = false;
+            p = 0;
+        }
+        const long i = p / CS;          // (< cap <= ldmix and the rows of mix: the host checked)
+        mii = a.mix[i * a.ldmix + i];
+        if constexpr (PRO) {
+            if (a.cos) {
+                const long row = min(p, a.tab_rows - 1);
+                cosr = (const T*)a.cos + row * a.ldt;
+                sinr = (const T*)a.sin + row * a.ldt;
+            }
+        }
+    } else if constexpr (RAGGED) {
         const long i = cst_pos(a.pos, b, a.max_pos) / CS;
         mii = a.mix[i * a.ldmix + i];
     } else {
@@ -88,8 +134,13 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
                 if (r < k1) {
                     p[u] = gld<f32x4>(a.P + base + (long)r * a.V);
                     c[u] = gld<f32x4>(a.Cur + base + (long)r * a.V);
-                    qv[u] = cst_ld1(qb + r);
-                    kv[u] = cst_ld1(kb + r);
+                    if constexpr (PRO) {
+                        qv[u] = cst_pro1(qb, r, a.K / 2, cosr, sinr, a.fmap);
+                        kv[u] = cst_pro1(kb, r, a.K / 2, cosr, sinr, a.fmap);
+                    } else {
+                        qv[u] = cst_ld1(qb + r);
+                        kv[u] = cst_ld1(kb + r);
+                    }
                 }
             }
 #pragma unroll
@@ -127,15 +178,28 @@ struct CsFinishArgs {
     float neps, scale;
     int H, V, nsplit;
     int* advance;          // [B] or null: positions of a ragged state, each incremented once (by the workgroup of head 0, token 0)
+    // DEV only: a position outside 0 .. max_pos (64 cap - 1) stays, and full[b] = 1 instead
+    int max_pos;
+    int* full;             // [B], never cleared here
 };
 
 // grid (B H, T tokens): o = scale * (partials in split order); y = o rsqrt(mean(o^2 over V) + neps) nw g sigmoid(g), from the fp32 o
-template <typename T>
+// DEV: the one thread that advances pos[b] is the only one of the launch to read it; a frozen sequence's partial sums are the zeros
+// its step wrote, so its row needs no branch here
+template <typename T, bool DEV = false>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishArgs a) {
     __shared__ float red[CST_THREADS / 64];
     const int tid = threadIdx.x, bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
     const long tok = blockIdx.y;
-    if (a.advance && h == 0 && tok == 0 && tid == 0) a.advance[b] += 1;   // (nothing in this launch reads it)
+    if constexpr (DEV) {
+        if (h == 0 && tok == 0 && tid == 0) {
+            const int p = a.advance[b];
+            if (p < 0 || p > a.max_pos) a.full[b] = 1;
+            else a.advance[b] = p + 1;
+        }
+    } else {
+        if (a.advance && h == 0 && tok == 0 && tid == 0) a.advance[b] += 1;   // (nothing in this launch reads it)
+    }
     const float* pb = a.part + ((long)bh * gridDim.y + tok) * a.nsplit * a.V;
     T* ob = a.out.ptr ? (T*)a.out.ptr + b * a.out.sb + tok * a.out.sn + h * a.out.sh : nullptr;
     auto o_at = [&](int c) {   // one accumulator, split order; the loads of a batch of eight issued together

@@ -145,6 +145,18 @@ template <typename T> __device__ __forceinline__ uint2 store_residual4(f32x4 x) 
                       pack_bf16x2(x[2] - stored_value<T>(x[2]), x[3] - stored_value<T>(x[3])));
 }
 
+// q / k prologue of the fla layer, per element in fp32 (k_fmap_rotary, epilogue.hpp; the fused prologue of the device-positioned decode
+// step, causal_step.hpp): the feature map (0 identity, 1 relu, 2 elu + 1), then the NeoX half rotation of the pair (x0, x1) =
+// (x[i], x[i + K/2]) by the angle (c, s).  One copy, with the fused multiply-adds written out so that no caller's contraction can
+// choose another rounding: both kernels round the same fp32 value.
+__device__ __forceinline__ float fmrot_map(float x, int fmap) {
+    if (fmap == 1) return fmaxf(x, 0.f);
+    if (fmap == 2) return x > 0.f ? x + 1.f : __expf(x);
+    return x;
+}
+__device__ __forceinline__ float fmrot_lo(float x0, float x1, float c, float s) { return fmaf(x0, c, -(x1 * s)); }   // y[i]
+__device__ __forceinline__ float fmrot_hi(float x0, float x1, float c, float s) { return fmaf(x1, c, x0 * s); }      // y[i + K/2]
+
 // h16: a 2-byte storage format of block / chunk summaries -- an fp16 payload x one power-of-two multiplier per group (a block row of
 // the block-mixing operator, split.hpp; a 16 x 64 strip of a chunk tile of the causal operator, causal_bf16.hpp): 11 significand bits.
 // decode multiplier of a row whose largest magnitude is mx: 2^(floor(log2 mx) - 14), exponent field clamped to [1, 240]

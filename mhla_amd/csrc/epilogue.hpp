@@ -481,12 +481,12 @@ __global__ __launch_bounds__(256) void k_fmap_rotary(const FmRotArgs a) {
     f32x4 y0, y1;
     if (!BWD) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (a.fmap == 1) { x0[u] = fmaxf(x0[u], 0.f); x1[u] = fmaxf(x1[u], 0.f); }
-            else if (a.fmap == 2) { x0[u] = x0[u] > 0.f ? x0[u] + 1.f : __expf(x0[u]); x1[u] = x1[u] > 0.f ? x1[u] + 1.f : __expf(x1[u]); }
+        for (int u = 0; u < 4; ++u) {   // (fmrot_*: common.hpp, shared with the decode step's fused prologue)
+            x0[u] = fmrot_map(x0[u], a.fmap);
+            x1[u] = fmrot_map(x1[u], a.fmap);
+            y0[u] = fmrot_lo(x0[u], x1[u], c[u], s[u]);
+            y1[u] = fmrot_hi(x0[u], x1[u], c[u], s[u]);
         }
-        y0 = x0 * c - x1 * s;
-        y1 = x1 * c + x0 * s;
     } else {
         y0 = x0 * c + x1 * s;
         y1 = x1 * c - x0 * s;

@@ -5,7 +5,8 @@ Plumbing for step-level numbers; stock PyTorch besides the attention layer.  The
 (layers/mhla.py:196-200: 2048 tokens at chunk 64); `max_seq_len` sizes it for longer sequences (8192 -> 128 chunks, the
 BASELINE.json configs[4] sequence length, through the drop-in layer's `max_chunks`).  With `exact_decoding=True` the layers
 keep a decode state in a cache (`forward(..., cache=DecodeCache())`: prefill on the first call, one exact step per later
-token, one extension per later call of several tokens) and `generate` decodes greedily on top of it."""
+token, one extension per later call of several tokens) and `generate` decodes greedily on top of it -- with `graph=True` by
+replaying one captured whole-model step per token (device-positioned steps: `DecodeCache(device_positions=True)`)."""
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -86,19 +87,49 @@ class GPT_MHLA(nn.Module):
         return F.cross_entropy(logits[:, :-1].reshape(-1, logits.shape[-1]).float(), labels[:, 1:].reshape(-1))
 
     @torch.no_grad()
-    def generate(self, input_ids, max_new_tokens, attention_mask=None):
+    def generate(self, input_ids, max_new_tokens, attention_mask=None, graph=False, return_logits=False):
         """Greedy decoding: one prefill over `input_ids` [B, T], then one cached step per new token.  Returns the
         `max_new_tokens` new ids [B, max_new_tokens]; T + max_new_tokens must fit the mixing matrix (`max_seq_len`).
         `attention_mask` [B, T]: prompts of different lengths, left-padded to T (0 = padding); every sequence continues from
-        its own length."""
-        cache = DecodeCache()
-        new = []
+        its own length.
+        `graph=True`: the steps are device-positioned (`DecodeCache(device_positions=True)`) -- an eager prefill, one eager step
+        that loads every kernel, then ONE whole-model step captured in a graph (static id and logits buffers, a single stream: a
+        linear graph without parallel branches) and replayed once per token, and one `cache.sync()` at the end, which raises
+        IndexError if a sequence was stepped beyond `max_seq_len` (its logits from there on came from zero attention rows).
+        `return_logits=True`: `(ids, logits [B, max_new_tokens, vocab])`, the logits every id was picked from."""
+        n = int(max_new_tokens)
+        cache = DecodeCache(device_positions=bool(graph))
+        new, kept = [], []
+
+        def pick(logits):
+            kept.append(logits[:, -1:]) if return_logits else None
+            new.append(logits[:, -1:].argmax(-1))
+            return new[-1]
+
         ids = input_ids
-        for _ in range(int(max_new_tokens)):
-            ids = self.forward(ids, cache=cache, attention_mask=attention_mask)[:, -1:].argmax(-1)
+        for _ in range(min(n, 1) if graph else n):   # (graph: the prefill alone)
+            ids = pick(self.forward(ids, cache=cache, attention_mask=attention_mask))
             attention_mask = None   # (the prefill's: the decode state carries the lengths from here on)
-            new.append(ids)
-        return torch.cat(new, dim=1) if new else input_ids[:, :0]
+        if graph and n > 1:
+            # the warm-up step (a real token) on a side stream, as a capture wants it: kernel code objects and the GEMM library's
+            # per-stream workspaces exist before anything is recorded
+            side = torch.cuda.Stream(device=ids.device)
+            side.wait_stream(torch.cuda.current_stream(ids.device))
+            with torch.cuda.stream(side):
+                ids = pick(self.forward(ids, cache=cache))
+            torch.cuda.current_stream(ids.device).wait_stream(side)
+        if graph and n > 2:
+            static_ids = ids.clone()
+            step = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(step):   # (one capture stream, nothing forks from it: a linear graph)
+                static_logits = self.forward(static_ids, cache=cache)
+            for _ in range(n - 2):
+                step.replay()
+                static_ids.copy_(pick(static_logits.clone()))
+        if graph:
+            cache.sync()
+        ids = torch.cat(new, dim=1) if new else input_ids[:, :0]
+        return (ids, torch.cat(kept, dim=1) if kept else None) if return_logits else ids
 
 
 def GPT_configs():

@@ -20,8 +20,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops import (CausalState, _runs, mhla_causal_prefill, featmap_rotary, mhla_causal, mhla_causal_extend, mhla_causal_normgate, mhla_causal_state, mhla_causal_step,
-                   naive_recurrent_mhla, rmsnorm_gate)
+from ..ops import (CausalState, _mix2d, _runs, mhla_causal_prefill, featmap_rotary, mhla_causal, mhla_causal_extend, mhla_causal_normgate, mhla_causal_state, mhla_causal_step,
+                   mhla_causal_step_dev, naive_recurrent_mhla, rmsnorm_gate)
 from ..weights import causal_mixing_init
 
 
@@ -151,10 +151,35 @@ class ShortConvolution(nn.Conv1d):
 class DecodeCache:
     """Minimal list-backed cache with the protocol the layer uses (`fla.models.utils.Cache` has the same one): `len(cache)`
     layers hold a state, `cache[i]` is layer i's `{"recurrent_state", "conv_state"}`, `get_seq_length(i)` the tokens layer i
-    has seen, `update(...)` stores a layer's state and adds `offset` tokens to its count."""
+    has seen, `update(...)` stores a layer's state and adds `offset` tokens to its count.
+    `device_positions=True` (layers built with `exact_decoding=True`): after the prefill every one-token call is a
+    device-positioned step (`mhla_causal_step_dev`: the q / k prologue and the norm x gate epilogue inside its three launches) that
+    reads no host position and never synchronises, so a whole decode step can be captured in `torch.cuda.graph` and replayed
+    once per token.  The prefill leaves a ragged state plus, in the layer's entry, what the steps read: the clamped,
+    lower-triangular fp32 mixing matrix and the rotary tables of 64 x capacity rows.  Neither the states' host mirrors nor this
+    cache's token counts move during such steps (a replay runs no Python): `sync()` brings both up, with the one device-to-host
+    copy per layer of the whole generation."""
 
-    def __init__(self):
+    def __init__(self, device_positions: bool = False):
         self.states, self._seen = [], []
+        self.device_positions = bool(device_positions)
+
+    def sync(self):
+        """After device-positioned steps: `CausalState.sync()` on every layer's state and the tokens they advanced by added to
+        this cache's counts.  Raises the first IndexError of a state that was stepped beyond its capacity, after all are synced."""
+        err = None
+        for i, entry in enumerate(self.states):
+            st = entry.get("recurrent_state")
+            if isinstance(st, CausalState) and st.stale:
+                before = st.seen
+                try:
+                    st.sync()
+                except IndexError as e:
+                    err = err or e
+                self._seen[i] += st.seen - before
+        if err is not None:
+            raise err
+        return self
 
     def __len__(self):
         return len(self.states)
@@ -206,7 +231,10 @@ class MHLA(nn.Module):
         the packed batch of the non-exact path -- and the state is ragged (`CausalState.lengths`): later calls step all sequences
         together, each at its own position, and do not read the mask beyond its shape.  An all-ones mask gives a uniform state,
         and a padding mask on a call whose cached state is uniform raises NotImplementedError.  Steps and extensions are
-        inference only (call under `torch.no_grad()`).  Adds no parameters."""
+        inference only (call under `torch.no_grad()`).  Adds no parameters.
+        With a `DecodeCache(device_positions=True)` the one-token calls after the prefill are device-positioned steps (see
+        `DecodeCache`; capturable in a graph); they do not reassign `mixing_matrix.data` -- generation does not change the weights
+        -- and calls of several tokens on such a cache, `use_short_conv` and `head_k_dim % 8 != 0` raise NotImplementedError."""
         super().__init__()
         self.mode = mode
         self.hidden_size = hidden_size
@@ -271,6 +299,11 @@ class MHLA(nn.Module):
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 past_key_values=None, use_cache: Optional[bool] = False, output_attentions: Optional[bool] = False,
                 **kwargs: Dict):
+        dev_mode = self.exact_decoding and bool(use_cache) and getattr(past_key_values, "device_positions", False)
+        if dev_mode:
+            entry = self._device_positioned_entry(hidden_states, past_key_values)
+            if entry is not None:
+                return self._device_positioned_step(hidden_states, entry), None, past_key_values
         # clamp + tril of the mixing weights at the start of every forward, on .data (layers/mhla.py:237)
         self.mixing_matrix.data = torch.clamp(self.mixing_matrix.data, 1e-5, 1).tril()
         if attention_mask is not None:
@@ -432,9 +465,31 @@ class MHLA(nn.Module):
         else:                                                                # :330-337
             o = mhla_causal(q, k, v, self.mixing_matrix, summaries=self.summaries)
             recurrent_state = None
+        if dev_mode and isinstance(recurrent_state, CausalState):
+            recurrent_state = recurrent_state.to_ragged()
         if past_key_values is not None and hasattr(past_key_values, "update"):   # :339-345
-            past_key_values.update(recurrent_state=recurrent_state, conv_state=conv_states if self.use_short_conv else None,
-                                   layer_idx=self.layer_idx, offset=q_len)
+            entry = past_key_values.update(recurrent_state=recurrent_state, conv_state=conv_states if self.use_short_conv else None,
+                                           layer_idx=self.layer_idx, offset=q_len)
+            if dev_mode and isinstance(recurrent_state, CausalState):
+                # what the device-positioned steps read, made once: the matrix as this forward clamped it (generation does not change
+                # the weights), the tables of a row per position the state can reach, the norm weight in fp32
+                cap = recurrent_state.capacity_chunks
+                cos, sin = self.rotary._tables(64 * cap, q.device, q.dtype)
+                gn = self.g_norm_swish_gate if self.fuse_norm_and_gate else None
+                entry.update(dev_mix=_mix2d(self.mixing_matrix), dev_cos=cos[:64 * cap], dev_sin=sin[:64 * cap],
+                             dev_norm_weight=gn.weight.detach().float().contiguous() if gn is not None and gn.weight is not None else None)
+        o = self._gate_and_project(o, hidden_states, fused_epilogue)
+        if ragged_lengths is not None:                                       # zeros at padding rows, as pad_input leaves them
+            o = o.masked_fill(~m.unsqueeze(-1), 0)
+        if indices is not None:                                              # pad_input, :362-363
+            full = o.new_zeros(batch_size * q_len, o.shape[-1])
+            full.index_copy_(0, indices, o.squeeze(0))
+            o = full.reshape(batch_size, q_len, -1)
+        return o, None, past_key_values
+
+    def _gate_and_project(self, o, hidden_states, fused_epilogue):
+        """Norm and output gate (unless the operator's launch chain applied them already: `fused_epilogue`), then o_proj."""
+        B, T, _ = hidden_states.shape
         if fused_epilogue:
             pass
         elif self.use_output_gate:
@@ -446,11 +501,46 @@ class MHLA(nn.Module):
                 o = self.g_norm(o, None).reshape(B, T, self.value_dim) * self.gate_fn(g)
         else:
             o = self.g_norm(o, None).reshape(B, T, self.value_dim)
-        o = self.o_proj(o)
-        if ragged_lengths is not None:                                       # zeros at padding rows, as pad_input leaves them
-            o = o.masked_fill(~m.unsqueeze(-1), 0)
-        if indices is not None:                                              # pad_input, :362-363
-            full = o.new_zeros(batch_size * q_len, o.shape[-1])
-            full.index_copy_(0, indices, o.squeeze(0))
-            o = full.reshape(batch_size, q_len, -1)
-        return o, None, past_key_values
+        return self.o_proj(o)
+
+    def _device_positioned_entry(self, hidden_states, cache):
+        """`DecodeCache(device_positions=True)`: what the configuration cannot do is refused on every call, the prefill included;
+        returns this layer's cache entry once the prefill has left a state (None before: the call is the prefill)."""
+        if self.layer_idx is None:
+            raise ValueError("MHLA(exact_decoding=True): the cache is indexed by layer_idx, which is None")
+        if self.use_short_conv:
+            raise NotImplementedError("MHLA: DecodeCache(device_positions=True) with use_short_conv (the convolution's state is host-positioned)")
+        if self.head_k_dim % 8:
+            raise NotImplementedError(f"MHLA: DecodeCache(device_positions=True) needs head_k_dim % 8 == 0 (the fused q / k prologue), got {self.head_k_dim}")
+        entry = cache[self.layer_idx] if len(cache) > self.layer_idx else None
+        if entry is None or not isinstance(entry.get("recurrent_state"), CausalState):
+            return None
+        if hidden_states.shape[1] != 1:
+            raise NotImplementedError(f"MHLA: a call of {hidden_states.shape[1]} tokens on a DecodeCache(device_positions=True) that holds a "
+                                      "state: device-positioned decoding takes one token per call (there is no device-positioned extend)")
+        return entry
+
+    def _device_positioned_step(self, hidden_states, entry):
+        """One token on a `DecodeCache(device_positions=True)`: projections, `mhla_causal_step_dev` (feature map, rotary at each
+        sequence's device position, the step, and norm x gate when `fuse_norm_and_gate`, in three launches), output projection.
+        Nothing here depends on a position or synchronises, the cache is not updated (the state advances in place, on the device),
+        and `mixing_matrix.data` is NOT reassigned: the matrix the prefill clamped is read, since generation does not change the
+        weights.  The whole call may be captured in a graph."""
+        B, T, _ = hidden_states.shape
+        q = self.q_proj(hidden_states).reshape(B, T, self.num_heads, self.head_k_dim)
+        k, v = self.k_proj(hidden_states), self.v_proj(hidden_states)
+        if self.num_kv_groups > 1:
+            k = k.reshape(B, T, self.num_kv_heads, 1, self.head_k_dim).expand(-1, -1, -1, self.num_kv_groups, -1)
+            v = v.reshape(B, T, self.num_kv_heads, 1, self.head_v_dim).expand(-1, -1, -1, self.num_kv_groups, -1)
+        k = k.reshape(B, T, self.num_heads, self.head_k_dim)
+        v = v.reshape(B, T, self.num_heads, self.head_v_dim)
+        g = gn = None
+        if self.fuse_norm_and_gate:
+            g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
+            gn = self.g_norm_swish_gate
+        o = mhla_causal_step_dev(q, k, v, entry["dev_mix"], entry["recurrent_state"], feature_map=self._fmap_name,
+                                 rotary=(entry["dev_cos"], entry["dev_sin"]), gate=g, norm_weight=entry["dev_norm_weight"],
+                                 norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None)
+        if gn is not None:
+            o = o.reshape(B, T, self.value_dim)
+        return self._gate_and_project(o, hidden_states, gn is not None)

@@ -1141,14 +1141,18 @@ class CausalState:
     of the batch share `seen`.  A RAGGED state (built with `lengths=`, and ragged from then on even if the lengths are equal): sequence
     b has seen `lengths[b]` tokens and behaves exactly as if it lived alone in a batch of one.  `lengths` (a tuple of B ints) is the
     host mirror every check and the boundary decision read; `pos` (int32 [B] on the state's device) holds the same numbers for the
-    kernels, which advance it themselves -- a step costs no copy and no synchronisation; `seen` is kept equal to `max(lengths)`."""
+    kernels, which advance it themselves -- a step costs no copy and no synchronisation; `seen` is kept equal to `max(lengths)`.
+    Device-positioned steps (`mhla_causal_step_dev`) move `pos` alone and leave the mirror behind: the state is then `stale`, every
+    call that reads the mirror refuses it, and `sync()` reads `pos` back.  `full` (int32 [B] on the state's device, zeros, created on
+    first use) is where those steps flag a sequence they found beyond the capacity."""
 
-    __slots__ = ("S", "P", "Cur", "seen", "chunk_size", "lengths", "pos")
+    __slots__ = ("S", "P", "Cur", "seen", "chunk_size", "lengths", "pos", "stale", "_full")
 
     def __init__(self, S: torch.Tensor, P: torch.Tensor, Cur: torch.Tensor, seen: int = 0, chunk_size: int = 64, *, lengths=None,
                  pos: Optional[torch.Tensor] = None):
         self.S, self.P, self.Cur, self.seen, self.chunk_size = S, P, Cur, int(seen), int(chunk_size)
-        self.lengths = self.pos = None
+        self.lengths = self.pos = self._full = None
+        self.stale = False
         if lengths is not None:
             lengths = _lengths_tuple("CausalState", lengths, S.shape[0], None)
             if pos is None:
@@ -1172,11 +1176,52 @@ class CausalState:
 
     @property
     def nbytes(self) -> int:
-        return 4 * (self.S.numel() + self.P.numel() + self.Cur.numel() + (self.pos.numel() if self.pos is not None else 0))
+        return 4 * (self.S.numel() + self.P.numel() + self.Cur.numel() + sum(t.numel() for t in (self.pos, self._full) if t is not None))
+
+    @property
+    def full(self) -> torch.Tensor:
+        """int32 [B] zeros on the state's device, created on first use: a device-positioned step sets `full[b] = 1` when it finds
+        sequence b beyond the capacity (and leaves that sequence as it is); nothing but the caller clears it."""
+        if self._full is None:
+            self._full = torch.zeros(self.S.shape[0], dtype=torch.int32, device=self.S.device)
+        return self._full
+
+    def to_ragged(self) -> "CausalState":
+        """A ragged state on the SAME storage (S, P, Cur are shared, not copied), every length equal to `seen` -- what
+        `mhla_causal_step_dev` takes.  A ragged state returns itself."""
+        if self.lengths is not None:
+            return self
+        return CausalState(self.S, self.P, self.Cur, 0, self.chunk_size, lengths=(self.seen,) * self.S.shape[0])
+
+    def sync(self) -> "CausalState":
+        """Bring the host mirror up to the device after device-positioned steps: `pos` and `full` are read back in one copy --
+        the one device-to-host copy of that path, and it synchronises --, `lengths` and `seen` are refreshed and the state is no
+        longer stale.  Then, if any `full` flag is set, IndexError naming those sequences: they were stepped beyond the
+        capacity, their rows from then on were zeros and their state stopped at the capacity.  A uniform state has nothing on
+        the device to read."""
+        if self.lengths is None:
+            return self
+        host = (self.pos if self._full is None else torch.stack((self.pos, self._full))).tolist()
+        pos, full = (host, ()) if self._full is None else host
+        self.lengths, self.seen, self.stale = tuple(int(n) for n in pos), max(int(n) for n in pos), False
+        over = [b for b, f in enumerate(full) if f]
+        if over:
+            raise IndexError(f"CausalState.sync: sequences {over} were stepped beyond the capacity of {self.capacity_chunks} chunks "
+                             f"({64 * self.capacity_chunks} tokens): their rows from there on are zeros (lengths={self.lengths})")
+        return self
+
+    def _refuse_stale(self, fn: str):
+        if self.stale:
+            raise ValueError(f"{fn}: the state was advanced by mhla_causal_step_dev and its host mirror (lengths, seen) is stale: "
+                             "call state.sync() first")
 
     def clone(self) -> "CausalState":
-        return CausalState(self.S.clone(), self.P.clone(), self.Cur.clone(), self.seen, self.chunk_size, lengths=self.lengths,
-                           pos=self.pos.clone() if self.pos is not None else None)
+        c = CausalState(self.S.clone(), self.P.clone(), self.Cur.clone(), self.seen, self.chunk_size, lengths=self.lengths,
+                        pos=self.pos.clone() if self.pos is not None else None)
+        c.stale = self.stale
+        if self._full is not None:
+            c._full = self._full.clone()
+        return c
 
     @classmethod
     def cat(cls, states) -> "CausalState":
@@ -1190,11 +1235,16 @@ class CausalState:
         for s in states[1:]:
             if tuple(s.S.shape[1:]) != tuple(a.S.shape[1:]) or s.chunk_size != a.chunk_size or s.S.device != a.S.device:
                 raise ValueError(f"CausalState.cat: {s!r} does not go with {a!r} (H, K, V, capacity, chunk size and device must agree)")
+        for s in states:
+            s._refuse_stale("CausalState.cat")
         S, P, Cur = (torch.cat([getattr(s, n) for s in states], dim=0) for n in ("S", "P", "Cur"))
         if all(s.lengths is None and s.seen == a.seen for s in states):
             return cls(S, P, Cur, a.seen, a.chunk_size)
         lengths = [n for s in states for n in (s.lengths if s.lengths is not None else (s.seen,) * s.S.shape[0])]
-        return cls(S, P, Cur, 0, a.chunk_size, lengths=lengths)
+        out = cls(S, P, Cur, 0, a.chunk_size, lengths=lengths)
+        if any(s._full is not None for s in states):
+            out._full = torch.cat([s.full for s in states])
+        return out
 
     def __repr__(self):
         B, H, cap, K, V = self.S.shape
@@ -1315,14 +1365,16 @@ def _step_view_ok(t: torch.Tensor) -> bool:
     return t.stride(3) == 1 and all(s % 4 == 0 for s in t.stride()[:3]) and t.data_ptr() % (4 * t.element_size()) == 0
 
 
-def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue):
+def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=True):
     """What `mhla_causal_step` and `mhla_causal_extend` (`fn`: the one called, for the messages) check after their own tests of
     the state's type, the tensors' rank and T, and the tensors they launch with.  The C ABI receives raw pointers, so everything
     is refused here, in an order callers rely on -- tensors like q, dtype, state shapes, devices, norm_weight, requires-grad, GPU,
     matrix shape, chunk size, rows / capacity (IndexError), epilogue arguments, state contiguity -- before anything is launched
     or `state` is touched.  Returns (q, k, v, gate, mixf, wf, pos, scale, want_y): the token tensors addressable in place or as
     contiguous copies, the mixing matrix and the norm weight in fp32, the position of the first token (of the furthest sequence
-    of a ragged state, whose `seen` is `max(lengths)`: rows and capacity are checked against it)."""
+    of a ragged state, whose `seen` is `max(lengths)`: rows and capacity are checked against it).  `positioned=False`
+    (`mhla_causal_step_dev`, which made its own check of the matrix against the capacity): the host position is neither read nor
+    checked -- a stale mirror is fine -- and the position returned is None."""
     B, T, H, K = q.shape
     V = v.shape[-1]
     try:
@@ -1347,12 +1399,14 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
         raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
     if int(state.chunk_size) != 64:
         raise ValueError(f"{fn}: chunk_size={state.chunk_size}, the decode state supports 64 only")
-    pos = state.seen
-    n = (pos + T + 63) // 64
-    if n > L:
-        raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but mixing_matrix has only {L} rows")
-    if n > state.capacity_chunks:
-        raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but the state holds only {state.capacity_chunks}")
+    pos = None
+    if positioned:
+        pos = state.seen
+        n = (pos + T + 63) // 64
+        if n > L:
+            raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but mixing_matrix has only {L} rows")
+        if n > state.capacity_chunks:
+            raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but the state holds only {state.capacity_chunks}")
     if scale is None:
         scale = K ** -0.5
     want_y = bool(epilogue) if epilogue is not None else (gate is not None or norm_weight is not None)
@@ -1427,6 +1481,7 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
     and `seen` grow by one.  The IndexError is raised when the longest sequence would not fit."""
     if not isinstance(state, CausalState):
         raise TypeError(f"mhla_causal_step: state must be a CausalState, got {type(state).__name__}")
+    state._refuse_stale("mhla_causal_step")
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k: [B, 1, H, K], v: [B, 1, H, V]")
     B, T, H, _ = q.shape
@@ -1461,6 +1516,94 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
     return res
 
 
+@_device_guard
+def _causal_step_dev(q, k, v, gate, mixf, wf, scale, want_y, state, pos, full, cos, sin, fmap, res, norm_eps):
+    """One launch chain of `mhla_causal_step_dev` on what `_decode_prepare` returned, for the sequences `state` (a batch slice)
+    holds.  Nothing here reads a position or synchronises: legal under stream capture."""
+    lib = _lib.load()
+    B, _, H, K = q.shape
+    V = v.shape[-1]
+    dt = _dtype_code(q)
+    ws = _ws(_step_ws_bytes(B, H, K, V, dt), q.device)
+    rc = lib.mhla_causal_step_dev(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+                                  state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), full.data_ptr(), _ptr(cos), _ptr(sin),
+                                  cos.stride(0) if cos is not None else 0, cos.shape[0] if cos is not None else 0, fmap,
+                                  NULL_VIEW if want_y else _view(res), _view_or_null(gate), _ptr(wf), float(norm_eps),
+                                  _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K, V, state.chunk_size,
+                                  float(scale), dt, _stream())
+    _lib.check(rc, "mhla_causal_step_dev")
+
+
+def mhla_causal_step_dev(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
+                         feature_map: Optional[str] = None, rotary=None, scale: Optional[float] = None,
+                         gate: Optional[torch.Tensor] = None, norm_weight: Optional[torch.Tensor] = None, norm_eps: float = 1e-5,
+                         epilogue: Optional[bool] = None) -> torch.Tensor:
+    """`mhla_causal_step` on a ragged state with the positions on the device only: the same rows and the same state, bit for bit,
+    from a call that reads no host position, advances none and never synchronises -- the launch chain (always three launches) and
+    every argument are the same token after token, so the call may be captured in `torch.cuda.graph` and replayed once per token
+    with new q, k, v (and gate) copied into the captured tensors.  It marks the state `stale`: `state.lengths` / `seen` stay where
+    they were until `state.sync()`, and `mhla_causal_step`, `mhla_causal_extend` and `CausalState.cat` refuse the state until then.
+    state: a ragged one (ValueError otherwise: `state.to_ragged()` makes one on the same storage).  mixing_matrix: at least
+    `capacity_chunks` rows and columns (IndexError otherwise) -- the bound is the capacity, not the current length.
+    A sequence at or beyond the capacity (64 capacity_chunks tokens) is FROZEN, not an error: its state and position stay, its row
+    of the result is zeros, and `state.full[b]` becomes 1 -- `state.sync()` raises the IndexError the host-positioned step
+    would have raised, after the fact.
+    feature_map (None / "identity", "relu", "elu") and rotary = (cos, sin) -- tables `[>= 64 capacity_chunks, K/2]` in the dtype
+    of q -- fuse the fla layer's q / k prologue into the step: q and k are then the projections' outputs, and sequence b is
+    rotated by row `pos[b]` of the tables, with the arithmetic and the rounding of `featmap_rotary` (K % 8 == 0).
+    scale, gate, norm_weight, norm_eps, epilogue, strided views, inference only: as `mhla_causal_step`."""
+    fn = "mhla_causal_step_dev"
+    if not isinstance(state, CausalState):
+        raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("q, k: [B, 1, H, K], v: [B, 1, H, V]")
+    B, T, H, K = q.shape
+    if T != 1:
+        raise ValueError(f"{fn} takes one token per call (T = 1), got T = {T}")
+    if state.lengths is None:
+        raise ValueError(f"{fn}: the state is uniform ({state!r}); the positions must live on the device: pass state.to_ragged()")
+    cap = state.capacity_chunks
+    if mixing_matrix.dim() < 2 or mixing_matrix.shape[0] < cap or mixing_matrix.shape[1] < cap:
+        raise IndexError(f"{fn}: mixing_matrix {tuple(mixing_matrix.shape)} has fewer rows or columns than the state's capacity of "
+                         f"{cap} chunks, which bounds what a step may read")
+    cos = sin = None
+    if rotary is not None:
+        cos, sin = rotary
+        for name, t in (("cos", cos), ("sin", sin)):
+            if t.dim() != 2 or t.shape[0] < 64 * cap:
+                raise ValueError(f"{fn}: rotary {name} has shape {tuple(t.shape)}, expected at least {64 * cap} rows (64 per chunk of "
+                                 f"capacity) of K/2={K // 2} entries")
+            if t.dtype != q.dtype or t.device != q.device:
+                raise ValueError(f"{fn}: rotary {name} is {t.dtype} on {t.device}, expected {q.dtype} on {q.device}")
+            if t.shape[1] != K // 2:
+                raise ValueError(f"{fn}: rotary {name} has shape {tuple(t.shape)}, expected K/2={K // 2} entries per row")
+    if (rotary is not None or feature_map is not None) and K % 8:
+        raise ValueError(f"{fn}: K={K}: the fused prologue (feature_map / rotary) needs K % 8 == 0")
+    if feature_map not in _FMAPS:
+        raise ValueError(f"{fn}: feature_map {feature_map!r}: one of {sorted(k for k in _FMAPS if k)} or None")
+    q, k, v, gate, mixf, wf, _, scale, want_y = _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue,
+                                                                positioned=False)
+    if cos is not None and (cos.stride(1) != 1 or sin.stride(1) != 1 or cos.stride(0) != sin.stride(0) or cos.stride(0) % 4
+                            or (cos.data_ptr() | sin.data_ptr()) % (4 * cos.element_size())):
+        cos, sin = cos.contiguous(), sin.contiguous()
+    if state._full is None and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{fn}: state.full does not exist yet and a tensor created while capturing would belong to the graph "
+                           "(cleared by every replay): run one eager step first, or touch state.full before the capture")
+    full = state.full
+    res = _alloc_like_tokens(B, 1, H, v.shape[-1], q)
+    nb = _MAX_GRID_BH // H
+    state.stale = True
+    for i in range(0, B, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
+        if B <= nb:
+            _causal_step_dev(q, k, v, gate, mixf, wf, scale, want_y, state, state.pos, full, cos, sin, _FMAPS[feature_map], res, norm_eps)
+            break
+        sl = lambda x: None if x is None else x[i:i + nb]
+        part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], 0, 64)
+        _causal_step_dev(sl(q), sl(k), sl(v), sl(gate), mixf, wf, scale, want_y, part, state.pos[i:i + nb], full[i:i + nb], cos, sin,
+                         _FMAPS[feature_map], sl(res), norm_eps)
+    return res
+
+
 # Largest workspace one launch chain of `mhla_causal_extend` takes: a longer extension is cut into consecutive calls.  Per (b, h)
 # the chain needs 4 K V bytes per chunk touched after the first and 4 V bytes per token (mhla_hip.h).
 EXTEND_WS_CAP_BYTES = 256 << 20
@@ -1484,6 +1627,7 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     kernel), then T is added to the device positions and to `lengths`."""
     if not isinstance(state, CausalState):
         raise TypeError(f"mhla_causal_extend: state must be a CausalState, got {type(state).__name__}")
+    state._refuse_stale("mhla_causal_extend")
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
     B, T, H, K = q.shape

@@ -27,6 +27,18 @@ copy before every call, so that host mirror and device array agree at every laun
 the same copy (into a spare tensor), so that all four wall times include that one extra launch; the device times count the library's
 kernels only.  The ragged step moves the uniform step's bytes plus 4 B.
 
+`--graph`: the device-positioned step (`mhla_causal_step_dev`: positions on the device only, a launch chain that depends on none of
+them) at the C5 head (H = 4, K = 128, V = 256, bf16, L = 128), B = 8 and 32, lengths as for `--ragged`, non-boundary steps: (a) the eager
+ragged step, (b) the eager device-positioned step, (c) ONE captured device-positioned step replayed (`torch.cuda.graph`); then the same
+three with the fla layer's q / k prologue (relu + rotary) -- for (a) the chain the layer runs today: two `index_select`s of the tables
+at the device positions, two `featmap_rotary` launches, the ragged step; for (b), (c) the prologue fused into the step.  Every variant
+(the graph too) starts with the 4 B-byte copy that puts the device positions back, so that every call is the same step.  Alternating in
+one run, `--reps` times: wall time per call (events around `--steps` calls or replays) with median, min, max; device time of the
+library's kernels for the eager variants (the per-launch event hook cannot see inside a replay, whose wall time is GPU-side).
+Then a GPT 340M decode step (24 layers, bf16, B = 8, prompt 100): eager on an ordinary cache, eager device-positioned, and the captured
+whole-model step replayed; the positions advance (a boundary every 64th step is part of the average).  Last line: the GPU kernels one
+layer's decode step launches before and after (torch.profiler; null where the profiler gives no device events).
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -199,6 +211,132 @@ def ragged_config(B, H, K, V, steps, reps):
     return rec
 
 
+def graph_config(B, H, K, V, steps, reps):
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    q, k, v = token(B, H, K, V, g)
+    i0 = 15
+    chunks = [i0 + (-2, -1, 1, 2)[b % 4] for b in range(B)]
+    lengths = tuple(c * 64 + (7 * b) % 63 for b, c in enumerate(chunks))
+    pos0 = torch.tensor(lengths, dtype=torch.int32, device=DEV)
+    inv = 1.0 / (10000.0 ** (torch.arange(0, K, 2, dtype=torch.float32) / K))
+    fr = torch.outer(torch.arange(64 * L, dtype=torch.float32), inv)
+    cos, sin = torch.cos(fr).to(torch.bfloat16).to(DEV), torch.sin(fr).to(torch.bfloat16).to(DEV)
+
+    def make():
+        st = mhla_amd.CausalState.empty(B, H, K, V, L, DEV)
+        st.S[:, :, :i0 + 3].normal_(0, 0.1)
+        st.P.normal_(0, 0.1)
+        st = mhla_amd.CausalState(st.S, st.P, st.Cur, lengths=lengths)
+        st.full
+        return st
+
+    rag, dev, rep, rep_pro = make(), make(), make(), make()
+
+    def ragged():
+        rag.lengths, rag.seen = lengths, max(lengths)
+        rag.pos.copy_(pos0)
+        mhla_amd.mhla_causal_step(q, k, v, mix, rag)
+
+    def ragged_pro():   # the layer's chain today: tables gathered at the device positions, two prologue launches, the ragged step
+        rag.lengths, rag.seen = lengths, max(lengths)
+        rag.pos.copy_(pos0)
+        p = rag.pos.long()
+        c, s = cos.index_select(0, p), sin.index_select(0, p)
+        qq = mhla_amd.featmap_rotary(q.reshape(1, B, H, K), c, s, "relu", 0).reshape(B, 1, H, K)
+        kk = mhla_amd.featmap_rotary(k.reshape(1, B, H, K), c, s, "relu", 0).reshape(B, 1, H, K)
+        mhla_amd.mhla_causal_step(qq, kk, v, mix, rag)
+
+    def dev_step(st=dev, **kw):
+        st.pos.copy_(pos0)
+        return mhla_amd.mhla_causal_step_dev(q, k, v, mix, st, **kw)
+
+    dev_pro = lambda st=dev: dev_step(st, feature_map="relu", rotary=(cos, sin))
+    graphs = {}
+    with torch.no_grad():
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            dev_step(rep), dev_pro(rep_pro)
+        torch.cuda.current_stream().wait_stream(side)
+        for name, fn, st in (("replay", dev_step, rep), ("replay_pro", dev_pro, rep_pro)):
+            graphs[name] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[name]):
+                fn(st)
+    fns = {"ragged": ragged, "dev": dev_step, "replay": graphs["replay"].replay,
+           "ragged_pro": ragged_pro, "dev_pro": dev_pro, "replay_pro": graphs["replay_pro"].replay}
+    wall = {n: [] for n in fns}
+    devt = {n: [] for n in fns if not n.startswith("replay")}
+    kern = {}
+    with torch.no_grad():
+        for _ in range(reps):
+            for n, fn in fns.items():
+                wall[n].append(batch_us(fn, steps))
+            for n in devt:
+                kern[n] = kernel_times(fns[n], iters=20)
+                devt[n].append(sum(kern[n].values()))
+            for st in (rag, dev, rep, rep_pro):
+                st.Cur.zero_()
+    rec = {"graph": {"B": B, "H": H, "K": K, "V": V, "chunks": sorted(set(chunks))}, "steps_per_batch": steps, "reps": reps,
+           "wall_us": {n: spread(x) for n, x in wall.items()}, "device_us": {n: spread(x) for n, x in devt.items()},
+           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()},
+           "replay_median_below_min_eager_ragged": statistics.median(wall["replay"]) < min(wall["ragged"]),
+           "replay_pro_median_below_min_eager_ragged_pro": statistics.median(wall["replay_pro"]) < min(wall["ragged_pro"])}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def gpu_kernel_count(fn):
+    """GPU kernels one call of `fn` launches, or None where the profiler reports no device events."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if getattr(e, "device_type", None) is not None and "cuda" in str(e.device_type).lower())
+        return n or None
+    except Exception:   # noqa: BLE001
+        return None
+
+
+def gpt_graph(steps, reps, B=8, T0=100):
+    from mhla_amd.hosts.gpt import GPT_MHLA, GPT_configs
+    from mhla_amd.modules import DecodeCache
+    torch.manual_seed(0)
+    model = GPT_MHLA(**GPT_configs()["340M"], exact_decoding=True).to(DEV).to(torch.bfloat16).eval()
+    prompt = torch.randint(0, 32000, (B, T0), device=DEV)
+    steps = min(steps, (2048 - T0 - 8) // (reps + 1))   # every cache stays inside the matrix (2048 tokens) over all repetitions
+    ids = torch.randint(0, 32000, (B, 1), device=DEV)
+    with torch.no_grad():
+        caches = {n: DecodeCache(device_positions=n != "eager") for n in ("eager", "dev", "replay")}
+        for c in caches.values():
+            model(prompt, cache=c)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            model(ids, cache=caches["replay"])
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            model(ids, cache=caches["replay"])
+        fns = {"eager": lambda: model(ids, cache=caches["eager"]), "dev": lambda: model(ids, cache=caches["dev"]), "replay": graph.replay}
+        wall = {n: [] for n in fns}
+        for _ in range(reps):
+            for n, fn in fns.items():
+                wall[n].append(batch_us(fn, steps, warm=2))
+        layer, x = model.layers[0].attn, torch.randn(B, 1, 1024, device=DEV, dtype=torch.bfloat16)
+        counts = {n: gpu_kernel_count(lambda n=n: layer(x, past_key_values=caches[n], use_cache=True)) for n in ("eager", "dev")}
+        for n in ("dev", "replay"):
+            caches[n].sync()
+    rec = {"gpt_340M_decode_step": {"B": B, "prompt": T0, "layers": 24, "dtype": "bf16"}, "steps_per_batch": steps, "reps": reps,
+           "wall_us": {n: spread(x) for n, x in wall.items()}, "layer_step_gpu_kernels": counts,
+           "tokens_seen": {n: c.get_seq_length(0) for n, c in caches.items()}}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def extend_config(B, H, K, V, pos, T, reps, parent_iters):
     g = torch.Generator().manual_seed(1)
     Lx = L + 16                                   # pos 8000 + 1024 tokens: 141 chunks
@@ -286,8 +424,13 @@ if __name__ == "__main__":
     ap.add_argument("--workload", action="store_true")
     ap.add_argument("--extend", action="store_true")
     ap.add_argument("--ragged", action="store_true")
+    ap.add_argument("--graph", action="store_true")
     a = ap.parse_args()
-    if a.ragged:
+    if a.graph:
+        for B in (8, 32):
+            graph_config(B, 4, 128, 256, max(200, a.steps), a.reps)
+        gpt_graph(a.steps, a.reps)
+    elif a.ragged:
         for B in (8, 32):
             ragged_config(B, 4, 128, 256, max(200, a.steps), a.reps)
     elif a.extend and a.workload:
