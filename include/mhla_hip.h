@@ -398,6 +398,40 @@ int mhla_causal_extend(mhla_view q, mhla_view k, mhla_view v, const float* mix, 
                        mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                        void* stream);
 
+/* mhla_causal_extend_ragged: mhla_causal_extend for a batch whose sequence b is at a position of its own, pos_dev[b], and takes a
+ * token count of its own, ntok_dev[b] in 0 .. T (added without a change of any existing signature or behaviour: MHLA_ABI_VERSION
+ * stays 9).  pos_dev, ntok_dev: device int32 [B].  q, k, v, gate, out, y are padded to T rows per sequence: the tokens of sequence b
+ * are rows [0, ntok_dev[b]), or [T - ntok_dev[b], T) with `left_padded`.  Sequence b behaves as in mhla_causal_extend alone in a
+ * batch of one at pos = pos_dev[b], T = ntok_dev[b] (the same tiles and order of every sum: the same bits; one token: the bits of
+ * mhla_causal_step for a batch of one); ntok_dev[b] = 0 leaves its state untouched.  Rows outside a sequence's window are never read
+ * into anything (q, k, v, gate) and are WRITTEN as zeros (out, y): the caller clears nothing.  At most six launches whatever B,
+ * the counts and the positions; the last adds ntok_dev[b] to pos_dev[b] in stream order (the earlier launches address by
+ * pos_dev, the last does not), so the array is the caller's to keep in step with, not to advance.
+ * The library cannot read device memory to validate, hence host values that vouch for the arrays:
+ *   T           the padded width, 1 .. 65535
+ *   max_end     the largest pos_dev[b] + ntok_dev[b] over the sequences with ntok_dev[b] > 0 (0: none has): takes the place of
+ *               pos + T in the capacity and ldmix checks of mhla_causal_extend
+ *   max_later   the largest number of chunks a sequence touches after its first, (pos + n - 1) / chunk - pos / chunk: sizes the grid
+ *               of the later segments and the workspace stride per (b, h)
+ *   any_close   non-zero when at least one sequence closes a chunk (pos % chunk + n >= chunk); zero: the three launches that form
+ *               later chunks and prefix mixes are not made.  Restriction, as mhla_causal_step_ragged: with any_close row
+ *               max_end / chunk of mix must be covered by ldmix unless max_end fills the state, whichever sequence closes
+ *   left_padded non-zero: windows are right-aligned, [T - n, T)
+ * pos_dev / ntok_dev must hold what these were computed from; arrays that disagree are the caller's error.  As a defence only, no
+ * content of the arrays addresses outside S, the matrix, the workspace or the token tensors: a sequence with pos < 0, n > T,
+ * pos + n > max_end, more later chunks than max_later, or a closing chunk without any_close is SKIPPED -- its state and position
+ * stay untouched and its rows are zeros.
+ * Workspace (mhla_causal_extend_ragged_ws_bytes, pure host arithmetic, independent of dtype), in 4-byte words, each term rounded
+ * up to a multiple of 4:  B H max_later K V  +  B H T V  +  B.  MHLA_EINVAL before any launch, the message naming the value:
+ * T outside 1 .. 65535; max_end beyond 64 cap_chunks; max_later beyond what T tokens can touch, or given without any_close; ldmix
+ * short of the row above; ws_bytes short or ws misaligned; pos_dev / ntok_dev null or misaligned.  Others as mhla_causal_extend. */
+size_t mhla_causal_extend_ragged_ws_bytes(int B, int T, int H, int K, int V, int max_later, int dtype);
+int mhla_causal_extend_ragged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                              float* Cur, int32_t* pos_dev, const int32_t* ntok_dev, int T, int64_t max_end, int max_later,
+                              int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                              mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
+                              void* stream);
+
 /* ---- prologue: q / k of the Wan host -------------------------------------- */
 
 /*

@@ -1,5 +1,5 @@
 // C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
-// (mhla_causal_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// (mhla_causal_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
@@ -71,6 +71,20 @@ CxPlan cx_plan(int B, int T, int H, int K, int V, int64_t pos) {
     p.tiles = al4((size_t)B * H * p.nws * K * V);
     p.stage = al4((size_t)B * H * T * V);
     p.total = p.tiles + p.stage;
+    return p;
+}
+
+// the ragged extension's workspace, in floats: P_c tiles with the batch maximum of later chunks as the stride per (b, h), the fp32
+// rows of every padded token, and nval[B] (int32)
+struct CxRagPlan {
+    size_t tiles, stage, nval, total;
+};
+CxRagPlan cx_rag_plan(int B, int T, int H, int K, int V, int max_later) {
+    CxRagPlan p{};
+    p.tiles = al4((size_t)B * H * max_later * K * V);
+    p.stage = al4((size_t)B * H * T * V);
+    p.nval = al4((size_t)B);
+    p.total = p.tiles + p.stage + p.nval;
     return p;
 }
 
@@ -304,6 +318,83 @@ int mhla_causal_extend(mhla_view q, mhla_view k, mhla_view v, const float* mix, 
             const CsFinishArgs f{stage, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, 1};
             RC(launch(k_cs_step_finish<ET>, dim3(BH, T), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
         }
+    });
+    return MHLA_OK;
+}
+
+size_t mhla_causal_extend_ragged_ws_bytes(int B, int T, int H, int K, int V, int max_later, int dtype) {
+    (void)dtype;
+    if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || V <= 0 || max_later < 0) return 0;
+    return cx_rag_plan(B, T, H, K, V, max_later).total * 4;
+}
+
+int mhla_causal_extend_ragged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                              float* Cur, int32_t* pos_dev, const int32_t* ntok_dev, int T, int64_t max_end, int max_later,
+                              int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                              mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
+                              void* stream) {
+    RC(cst_check(B, H, K, V, chunk, dtype));
+    if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive", T);
+    if (T > 65535) return fail(MHLA_EINVAL, "T=%d exceeds 65535 tokens per call", T);
+    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(v);
+    if (!out.ptr && !y.ptr) return fail(MHLA_EINVAL, "out and y both null");
+    if (out.ptr) CHECK_VIEW(out);
+    if (y.ptr) CHECK_VIEW(y);
+    if (gate.ptr) CHECK_VIEW(gate);
+    if ((gate.ptr || norm_w) && !y.ptr) return fail(MHLA_EINVAL, "gate / norm_w given without y");
+    RC(cst_check_state(S, cap_chunks, P, Cur));
+    if (cap_chunks > INT32_MAX / 64) return fail(MHLA_ENOTSUP, "cap_chunks=%d: positions beyond int32", cap_chunks);
+    if (!pos_dev || ((uintptr_t)pos_dev) % 4) return fail(MHLA_EINVAL, "pos_dev null or not 4-byte aligned");
+    if (!ntok_dev || ((uintptr_t)ntok_dev) % 4) return fail(MHLA_EINVAL, "ntok_dev null or not 4-byte aligned");
+    if (max_end < 0) return fail(MHLA_EINVAL, "max_end=%lld is negative", (long long)max_end);
+    if (max_end > (int64_t)64 * cap_chunks)
+        return fail(MHLA_EINVAL, "max_end=%lld tokens need %lld chunks, the state holds %d", (long long)max_end, (long long)((max_end + 63) / 64), cap_chunks);
+    if (max_later < 0 || max_later > (T + 62) / 64)
+        return fail(MHLA_EINVAL, "max_later=%d: T=%d tokens touch at most %d chunks after the first", max_later, T, (T + 62) / 64);
+    if (max_later && !any_close) return fail(MHLA_EINVAL, "max_later=%d without any_close", max_later);
+    // rows of mix read: every sequence's diagonal up to chunk (its end - 1) / 64 and, where it closes a chunk and is not full then, row
+    // (its end) / 64.  Which sequence closes is known on the device only: with any_close row max_end / 64 must be covered (or
+    // the state's last), as if the furthest sequence were the one -- the restriction of mhla_causal_step_ragged
+    const int64_t lastrow = any_close ? std::min<int64_t>(max_end / 64, cap_chunks - 1) : (max_end > 0 ? (max_end - 1) / 64 : 0);
+    if (!mix || ldmix < lastrow + 1)
+        return fail(MHLA_EINVAL, "mix null or ldmix=%d < %lld (row %lld of mix is read)", ldmix, (long long)(lastrow + 1), (long long)lastrow);
+    const CxRagPlan p = cx_rag_plan(B, T, H, K, V, max_later);
+    if (!ws || ws_bytes < p.total * 4) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, p.total * 4);
+    if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int BH = B * H, nvt = (V + 63) / 64, strips = ((K + 63) / 64) * nvt;
+    const long E = (long)K * V;
+    float* tiles = (float*)ws;
+    float* stage = tiles + p.tiles;
+    int* nval = (int*)(stage + p.stage);
+    const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0};
+    const int kr = cst_rows((size_t)H, K, V);   // a one-token sequence: the step's K split for a batch of one
+    // every launch but the last addresses by pos_dev; the last, which does not, advances it
+    DISPATCH_T(dtype, {
+        CxOutArgs o{};
+        o.q = cv(q); o.k = cv(k); o.v = cv(v);
+        o.stage = stage; o.H = H; o.K = K; o.V = V; o.T = T; o.scale = scale; o.mstep = (long)ldmix + 1;
+        o.P = P; o.Cur = Cur; o.mdiag = mix; o.rag = g; o.later = 0; o.nval = nval; o.kr = kr; o.nsplit = (K + kr - 1) / kr;
+        RC(launch(k_cx_out<ET, true>, dim3(1, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out_ragged", o));
+        CxAccArgs c{};
+        c.x = cv(k); c.y = cv(v); c.H = H; c.DX = K; c.DY = V; c.rag = g; c.later = 0; c.S = S; c.Cur = Cur;
+        RC(launch(k_cx_xty_acc<ET, true>, dim3(1, BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+        if (any_close) {
+            c.later = 1;
+            RC(launch(k_cx_xty_acc<ET, true>, dim3(std::max(1, max_later), BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+            CxMixRagArgs m{};
+            m.m.S = S; m.m.ws = tiles; m.m.P = P; m.m.mix = mix; m.m.E = E; m.m.ldmix = ldmix; m.m.cap = cap_chunks;
+            m.rag = g; m.H = H;
+            const int groups = (max_later + 1 + CX_MIX_NC - 1) / CX_MIX_NC;   // (the largest nc is max_later + 1)
+            RC(launch(k_cx_mix_ragged, dim3((unsigned)((E / 4 + 63) / 64), BH, groups), dim3(64), 0, st, "k_cx_mix_ragged", m));
+            if (max_later) {
+                o.P = tiles; o.Cur = nullptr; o.later = 1;
+                RC(launch(k_cx_out<ET, true>, dim3(max_later, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out_ragged", o));
+            }
+        }
+        CsFinishArgs f{stage, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, 1, pos_dev};
+        f.nval = nval; f.left = left_padded ? 1 : 0;
+        RC(launch(k_cs_step_finish<ET, false, true>, dim3(BH, T), dim3(CST_THREADS), 0, st, "k_cs_step_finish_ragged", f));
     });
     return MHLA_OK;
 }

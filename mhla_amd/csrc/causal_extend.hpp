@@ -15,11 +15,60 @@
 //   k_cs_step_finish over the token rows (fp32 rows staged by k_cx_out): scale, norm x gate, ONE rounding
 // Every product is an exact fp32 MFMA tile product with fp32 accumulation (k_cs_out's machinery), never the 11-bit stored
 // summaries: the rows are of the same grade as the step's.  No atomics, every sum in a fixed order.
+// Ragged extend (RAGGED; mhla_causal_extend_ragged): ONE chain for a batch whose sequence b takes ntok[b] tokens (0 .. T) at its
+// own position pos[b], the tokens padded to [B][T][...] (rows [0, n), or [T - n, T) left-padded).  Every (b, h) workgroup reads
+// pos[b] and ntok[b] (device int32 [B]) and derives the plan the host derives above (cx_seq): i, r, the first segment's rows a, the
+// chunks touched after the first, whether the first segment closes chunk i, whether the state is full afterwards.  The later
+// segments are a grid dimension sized by the batch maximum the host vouches for; a workgroup whose sequence has no such segment
+// (or no token at all) returns after those two loads, before any LDS or other global traffic.  Six launches, whatever B, ntok, pos:
+//   k_cx_out<RAGGED>     first segment (also: nval[b] = the tokens the chain accepts for b, which the finish reads instead of pos)
+//   k_cx_xty_acc<RAGGED> first segment: Cur, or S[i_b] where that sequence's chunk closes
+//   k_cx_xty_acc<RAGGED> later segments (src null): whole chunks -> S[i_b + 1 + s], the tail -> Cur, no tail -> Cur = 0.  A launch
+//                        of its own: the one before READS Cur, this one WRITES it
+//   k_cx_mix_ragged      c0 = i_b + 1, nc and cP per sequence; workspace stride = the batch maximum of later chunks
+//   k_cx_out<RAGGED>     later segments, P from the workspace
+//   k_cs_step_finish<WIN> every row of [B][T]: rows of the window from the staged fp32 rows, rows outside it written as ZEROS;
+//                        pos[b] += nval[b] -- the last launch, the only one that does not address by pos
+// (the middle three only when the host says some sequence closes a chunk).  Tiling and the order of every sum are the uniform
+// chain's, so a sequence gets the bits mhla_causal_extend gives it alone in a batch of one; a sequence with ONE token gets the
+// step's arithmetic (k_cs_step's row walk and K split of a batch of one, fmaf for fmaf), as T = 1 of the uniform call is the step.
+// Defence only: a sequence whose pos / ntok fall outside what the host vouched for is skipped (state untouched, rows zeros).
 #pragma once
 #include "causal.hpp"
 #include "causal_step.hpp"
 
 namespace mhla {
+
+// RAGGED: what every kernel of the ragged chain derives its sequence's plan from
+struct CxRag {
+    const int* pos;        // [B] tokens seen per sequence
+    const int* ntok;       // [B] new tokens per sequence, 0 .. T
+    int T, cap;            // padded width; chunks the state holds
+    int max_end;           // host-vouched: the largest pos[b] + ntok[b] over sequences with tokens (<= 64 cap)
+    int max_later;         // host-vouched: the largest number of chunks touched after the first
+    int any_close;         // host-vouched: some sequence closes a chunk (the later-segment launches exist)
+    int left;              // left-padded: sequence b's tokens are rows [T - n, T)
+};
+struct CxSeq {
+    int n, i, r, a;        // tokens; chunk and fill of the open chunk; rows of the first segment
+    int later;             // chunks touched after the first
+    int iend;              // chunk open after the extension
+    int shift;             // first token row inside [0, T)
+    bool closes, full;     // the first segment closes chunk i; the state is full afterwards
+};
+// false: no token, or (defence only) entries outside what the host vouched for -- the caller returns at once
+__device__ __forceinline__ bool cx_seq(const CxRag& g, int b, CxSeq& s) {
+    const int p = g.pos[b], n = g.ntok[b];
+    if (p < 0 || n < 1 || n > g.T || (long)p + n > (long)g.max_end) return false;
+    s.n = n; s.i = p / CS; s.r = p - s.i * CS;
+    s.a = min(n, CS - s.r);
+    s.later = (p + n - 1) / CS - s.i;
+    s.iend = (p + n) / CS;
+    s.closes = s.iend > s.i;
+    s.full = s.iend >= g.cap;
+    s.shift = g.left ? g.T - n : 0;
+    return s.later <= g.max_later && (!s.closes || g.any_close);
+}
 
 struct CxOutArgs {
     View q, k, v;          // [B][T][H][K / V]: the extension's tokens
@@ -34,6 +83,11 @@ struct CxOutArgs {
     int H, K, V;
     long T;
     float scale;
+    // RAGGED only: P is the state's (later = 0) or the workspace (later = 1), Cur the state's, mdiag = &mix[0][0]
+    CxRag rag;
+    int later;             // 0: the first segment of every sequence; 1: segment blockIdx.x of the later ones
+    int* nval;             // [B] (later = 0 writes it) tokens the chain accepts for sequence b: what the finish reads
+    int kr, nsplit;        // the K split of k_cs_step for a batch of one: the sums of a one-token sequence
 };
 
 // [64 kk][64 cols] slice of P + mii Cur (Cur null: P alone) -> LDS, zero padded; V % 4 == 0
@@ -63,8 +117,47 @@ __device__ __forceinline__ void cx_load_pc(float* __restrict__ dst, int ld, cons
     }
 }
 
-// grid (segments, B H, ceil(V / 64)): k_cs_out on a run of <= 64 token rows of one chunk
+// One token of sequence (b, h) with the arithmetic of k_cs_step + k_cs_step_finish for a batch of one (RAGGED, n = 1): per K split
+// thread (rg, c4) walks rows rg, rg + 16, ... with c = fmaf(k, v, Cur), acc = fmaf(q, fmaf(mii, c, P), acc); the 16 row groups are
+// summed in order, then the splits in order.  Cur is NOT written here (k_cx_xty_acc forms the same fmaf).  red: [16][64] floats
 template <typename T>
+__device__ __forceinline__ void cx_one_token(const CxOutArgs& a, float* red, const T* qr, const T* kr, const T* vr, const float* Pi,
+                                             const float* Ci, float mii, int v0, float* srow, int tid) {
+    const int c4 = (tid & 15) * 4, rg = tid >> 4, col = v0 + c4;
+    const bool live = col < a.V;
+    f32x4 vv = {0.f, 0.f, 0.f, 0.f};
+    if (live) vv = Io<T>::ld4(vr + col);
+    float tot = 0.f;
+    for (int sp = 0; sp < a.nsplit; ++sp) {
+        const int k0 = sp * a.kr, k1 = min(a.K, k0 + a.kr);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        if (live) {
+            for (int r = k0 + rg; r < k1; r += CST_RG) {
+                const f32x4 p = gld<f32x4>(Pi + (long)r * a.V + col);
+                f32x4 c = gld<f32x4>(Ci + (long)r * a.V + col);
+                const float qv = cst_ld1(qr + r), kv = cst_ld1(kr + r);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    c[t] = fmaf(kv, vv[t], c[t]);
+                    acc[t] = fmaf(qv, fmaf(mii, c[t], p[t]), acc[t]);
+                }
+            }
+        }
+        *reinterpret_cast<f32x4*>(red + rg * CST_VT + c4) = acc;
+        __syncthreads();
+        if (tid < CST_VT) {
+            float s = 0.f;
+#pragma unroll
+            for (int g = 0; g < CST_RG; ++g) s += red[g * CST_VT + tid];
+            tot += s;
+        }
+        __syncthreads();
+    }
+    if (tid < CST_VT && v0 + tid < a.V) srow[tid] = tot;
+}
+
+// grid (segments, B H, ceil(V / 64)): k_cs_out on a run of <= 64 token rows of one chunk
+template <typename T, bool RAGGED = false>
 __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Qs = smem;                  // [64 c][66]
@@ -75,14 +168,50 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
     const int seg = blockIdx.x, bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H;
     const int v0 = blockIdx.z * 64, vv = min(64, a.V - v0);
-    const long p0 = a.tok0 + (long)seg * CS;
-    const int rv = (int)min((long)CS, a.tend - p0);
+    long p0;
+    int rv;
+    const float* Pi;
+    const float* Ci;
+    float mii;
+    [[maybe_unused]] bool one = false;
+    if constexpr (RAGGED) {
+        CxSeq s;
+        const bool ok = cx_seq(a.rag, b, s);
+        if (!a.later && h == 0 && blockIdx.z == 0 && tid == 0) a.nval[b] = ok ? s.n : 0;
+        if (!ok || (a.later && seg >= s.later)) return;   // ahead of any LDS or further global traffic
+        const long E = (long)a.K * a.V;
+        if (a.later) {
+            const int tok = s.a + seg * CS;
+            p0 = s.shift + tok;
+            rv = min(CS, s.n - tok);
+            Pi = a.P + ((long)bh * a.rag.max_later + seg) * E;
+            Ci = nullptr;
+            mii = a.mdiag[(long)(s.i + 1 + seg) * a.mstep];
+        } else {
+            p0 = s.shift;
+            rv = s.a;
+            Pi = a.P + (long)bh * E;
+            Ci = a.Cur + (long)bh * E;
+            mii = a.mdiag[(long)s.i * a.mstep];
+            one = s.n == 1;
+        }
+    } else {
+        p0 = a.tok0 + (long)seg * CS;
+        rv = (int)min((long)CS, a.tend - p0);
+        Pi = a.P + (long)bh * a.p_bh + (long)seg * a.p_seg;
+        Ci = a.Cur ? a.Cur + (long)bh * a.K * a.V : nullptr;
+        mii = a.mdiag[(long)seg * a.mstep];
+    }
     const T* qb = (const T*)a.q.ptr + b * a.q.sb + h * a.q.sh;
     const T* kb = (const T*)a.k.ptr + b * a.k.sb + h * a.k.sh;
     const T* vb = (const T*)a.v.ptr + b * a.v.sb + h * a.v.sh;
-    const float* Pi = a.P + (long)bh * a.p_bh + (long)seg * a.p_seg;
-    const float* Ci = a.Cur ? a.Cur + (long)bh * a.K * a.V : nullptr;
-    const float mii = a.mdiag[(long)seg * a.mstep];
+    if constexpr (RAGGED) {
+        if (one) {
+            cx_one_token<T>(a, smem, qb + p0 * a.q.sn, kb + p0 * a.k.sn, vb + p0 * a.v.sn, Pi, Ci, mii, v0,
+                            a.stage + ((long)bh * a.T + p0) * a.V + v0, tid);
+            return;
+        }
+    }
 
     f32x4 accO[4], accA[4];
 #pragma unroll
@@ -136,10 +265,19 @@ struct CxAccArgs {
     float* dst;            // Cur, or S[i] when the segment closes the chunk
     long dst_bh;           // floats from one (b, h) to the next in dst
     int H, rows, DX, DY;
+    // RAGGED only: rows, src and dst are derived per sequence
+    CxRag rag;
+    int later;             // 0: the first segment (src = Cur); 1: segment blockIdx.x of the later ones (src null)
+    float* S;              // [bh][cap][K][V]
+    float* Cur;            // [bh][K][V]
 };
 
 // grid (1, B H, strips of 64 x 64): dst = src + X^T Y over the segment's rows -- the accumulating form of k_bm_state<MODE 2>
-template <typename T>
+// RAGGED, grid (segments, B H, strips): each (b, h) for itself.  later = 0: the first segment, dst = S[i_b] where that sequence's chunk
+// closes, else Cur; one token: fmaf(k, v, Cur), the step's rank-1 update.  later = 1: K^T V alone (k_bm_state<2>'s tiles, loads and
+// kend: the same sums) of later segment blockIdx.x -- 64 rows -> S[i_b + 1 + s], fewer (the tail) -> Cur -- and segment 0's workgroups
+// write Cur = 0 for a sequence that closed its chunk and has no tail.  The two are separate launches: the first reads Cur.
+template <typename T, bool RAGGED = false>
 __global__ __launch_bounds__(NTHREADS) void k_cx_xty_acc(const CxAccArgs a) {
     constexpr int LD = ld_kmajor(64);
     __shared__ __attribute__((aligned(16))) float Xs[CS * LD];
@@ -148,18 +286,46 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_xty_acc(const CxAccArgs a) {
     const int bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H;
     const int nsy = (a.DY + 63) / 64;
     const int x0 = (blockIdx.z / nsy) * 64, y0 = (blockIdx.z % nsy) * 64;
+    int rows = a.rows;
+    long tok0 = 0;
+    const float* sb = nullptr;
+    float* db = nullptr;
+    [[maybe_unused]] bool one = false, zero_cur = false;
+    if constexpr (RAGGED) {
+        CxSeq s;
+        if (!cx_seq(a.rag, b, s)) return;   // ahead of any LDS or further global traffic
+        const long E = (long)a.DX * a.DY;
+        if (a.later) {
+            const int seg = blockIdx.x, rest = s.n - s.a;
+            if (!s.closes) return;
+            zero_cur = seg == 0 && rest % CS == 0;
+            rows = seg < s.later ? min(CS, rest - seg * CS) : 0;
+            if (!rows && !zero_cur) return;
+            tok0 = s.shift + s.a + (long)seg * CS;
+            db = rows == CS ? a.S + ((long)bh * a.rag.cap + s.i + 1 + seg) * E : a.Cur + (long)bh * E;
+        } else {
+            rows = s.a;
+            tok0 = s.shift;
+            sb = a.Cur + (long)bh * E;
+            db = s.closes ? a.S + ((long)bh * a.rag.cap + s.i) * E : a.Cur + (long)bh * E;
+            one = s.n == 1;
+        }
+    } else {
+        sb = a.src + (long)bh * a.DX * a.DY;
+        db = a.dst + (long)bh * a.dst_bh;
+    }
     const T* xb = (const T*)a.x.ptr + b * a.x.sb + h * a.x.sh;
     const T* yb = (const T*)a.y.ptr + b * a.y.sb + h * a.y.sh;
-    const int kend = (a.rows + 3) & ~3;
+    const int kend = (rows + 3) & ~3;
     f32x4 acc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    load_tile<T, 64, false>(Xs, LD, xb + x0, a.x.sn, nullptr, 0, a.rows, kend, a.DX - x0, 0.f, tid, NTHREADS);
-    load_tile<T, 64, false>(Ys, LD, yb + y0, a.y.sn, nullptr, 0, a.rows, kend, a.DY - y0, 0.f, tid, NTHREADS);
-    __syncthreads();
-    xty_accum<4, 4>(acc, Xs, Ys, LD, kend, wave, lane);
-    const float* sb = a.src + (long)bh * a.DX * a.DY;
-    float* db = a.dst + (long)bh * a.dst_bh;
+    if (!RAGGED || rows) {
+        load_tile<T, 64, false>(Xs, LD, xb + x0, a.x.sn, nullptr, tok0, rows, kend, a.DX - x0, 0.f, tid, NTHREADS);
+        load_tile<T, 64, false>(Ys, LD, yb + y0, a.y.sn, nullptr, tok0, rows, kend, a.DY - y0, 0.f, tid, NTHREADS);
+        __syncthreads();
+        xty_accum<4, 4>(acc, Xs, Ys, LD, kend, wave, lane);
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int t = wave + 4 * i, tm = t >> 2, tn = t & 3;
@@ -167,7 +333,20 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_xty_acc(const CxAccArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = x0 + tm * 16 + kq * 4 + r;
-            if (row < a.DX && col < a.DY) db[(long)row * a.DY + col] = sb[(long)row * a.DY + col] + acc[i][r];
+            if (row < a.DX && col < a.DY) {
+                if constexpr (RAGGED) {
+                    const long at = (long)row * a.DY + col;
+                    if (rows) {
+                        float val = acc[i][r];
+                        if (one) val = fmaf(Xs[row - x0], Ys[col - y0], sb[at]);
+                        else if (sb) val = sb[at] + val;
+                        db[at] = val;
+                    }
+                    if (zero_cur) a.Cur[(long)bh * a.DX * a.DY + at] = 0.f;
+                } else {
+                    db[(long)row * a.DY + col] = sb[(long)row * a.DY + col] + acc[i][r];
+                }
+            }
         }
     }
 }
@@ -184,17 +363,15 @@ struct CxMixArgs {
     int cP;                // chunk whose prefix mix is the state's P (c0 <= cP < c0 + nc), or -1: the state is full, P = 0
 };
 
-// grid (ceil(E / 4 / 64), B H, ceil(nc / 8)), one wave per workgroup: P_c = sum_{j < c} mix[c][j] S[j], ascending j (k_cs_roll's sum)
-__global__ __launch_bounds__(64) void k_cx_mix(const CxMixArgs a) {
-    const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
-    if (e >= a.E) return;   // (E % 4 == 0)
-    const long bh = blockIdx.y;
+// P_c of the chunks c0 + u0 .. of one (b, h), elements e .. e + 3: ascending j with fmaf (k_cs_roll's sum).  `nws` of them go to the
+// workspace, whose stride per (b, h) is `ws_bh` tiles
+__device__ __forceinline__ void cx_mix_sums(const CxMixArgs& a, long bh, long e, int c0, int nws, int ws_bh, int nc, int cP) {
     const float* Sb = a.S + bh * a.cap * a.E + e;
-    const int u0 = blockIdx.z * CX_MIX_NC, nu = min(CX_MIX_NC, a.nc - u0);
+    const int u0 = blockIdx.z * CX_MIX_NC, nu = min(CX_MIX_NC, nc - u0);
     f32x4 acc[CX_MIX_NC];
 #pragma unroll
     for (int u = 0; u < CX_MIX_NC; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int cbase = a.c0 + u0, jend = nu > 0 ? cbase + nu - 1 : 0;   // the last chunk of the group sums j < jend
+    const int cbase = c0 + u0, jend = nu > 0 ? cbase + nu - 1 : 0;   // the last chunk of the group sums j < jend
     // j < cbase: a term of every chunk of the group (eight tiles in flight, no per-chunk test); cbase <= j < jend: of the chunks behind j
     constexpr int U = 8;
     const int jall = nu > 0 ? cbase : 0;
@@ -230,11 +407,37 @@ __global__ __launch_bounds__(64) void k_cx_mix(const CxMixArgs a) {
 #pragma unroll
     for (int u = 0; u < CX_MIX_NC; ++u) {
         if (u < nu) {
-            if (u0 + u < a.nws) gst<f32x4>(a.ws + (bh * a.nws + u0 + u) * a.E + e, acc[u]);
-            if (cbase + u == a.cP) gst<f32x4>(a.P + bh * a.E + e, acc[u]);
+            if (u0 + u < nws) gst<f32x4>(a.ws + (bh * ws_bh + u0 + u) * a.E + e, acc[u]);
+            if (cbase + u == cP) gst<f32x4>(a.P + bh * a.E + e, acc[u]);
         }
     }
-    if (a.cP < 0 && blockIdx.z == 0) gst<f32x4>(a.P + bh * a.E + e, f32x4{0.f, 0.f, 0.f, 0.f});
+    if (cP < 0 && blockIdx.z == 0) gst<f32x4>(a.P + bh * a.E + e, f32x4{0.f, 0.f, 0.f, 0.f});
+}
+
+// grid (ceil(E / 4 / 64), B H, ceil(nc / 8)), one wave per workgroup: P_c = sum_{j < c} mix[c][j] S[j], ascending j (k_cs_roll's sum)
+__global__ __launch_bounds__(64) void k_cx_mix(const CxMixArgs a) {
+    const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
+    if (e >= a.E) return;   // (E % 4 == 0)
+    cx_mix_sums(a, blockIdx.y, e, a.c0, a.nws, a.nws, a.nc, a.cP);
+}
+
+struct CxMixRagArgs {
+    CxMixArgs m;           // c0, nws, nc and cP unused: per sequence
+    CxRag rag;
+    int H;
+};
+
+// grid (ceil(E / 4 / 64), B H, groups of the largest nc): each (b, h) for itself -- a sequence that closes no chunk returns; else
+// c0 = i_b + 1, its own later chunks to the workspace (stride rag.max_later), P of the chunk open afterwards to the state's P, or P = 0
+// where that sequence's state is then full
+__global__ __launch_bounds__(64) void k_cx_mix_ragged(const CxMixRagArgs a) {
+    const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
+    if (e >= a.m.E) return;   // (E % 4 == 0)
+    const long bh = blockIdx.y;
+    CxSeq s;
+    if (!cx_seq(a.rag, (int)(bh / a.H), s) || !s.closes) return;
+    const int nc = (s.full ? s.i + s.later : s.iend) - s.i;
+    cx_mix_sums(a.m, bh, e, s.i + 1, s.later, a.rag.max_later, nc, s.full ? -1 : s.iend);
 }
 
 }  // namespace mhla

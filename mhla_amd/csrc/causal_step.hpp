@@ -16,6 +16,8 @@
 // at all.  Tiling, K split, row walk and the order of every sum are the uniform ones, so equal positions give the uniform bits.
 // pos[b] advances in k_cs_step_finish, the last launch of the ragged chain (step, roll, finish) and the only one that does not
 // address by it: no workgroup writes pos[b] in a launch in which another reads it.
+// The finish is also the last launch of the ragged extend (WIN; causal_extend.hpp): over all B T padded rows it writes the rows outside a
+// sequence's window as zeros and adds that sequence's token count to pos[b].
 // Device-positioned steps (DEV; mhla_causal_step_dev): a launch chain whose shape and arguments do not depend on the positions
 // at all, so that a captured graph can replay it token after token.  Always step, roll, finish; the bound on pos[b] is the
 // state's capacity instead of a number the host vouches for per call.  A sequence with 0 <= pos[b] < 64 cap is LIVE and takes
@@ -181,17 +183,35 @@ struct CsFinishArgs {
     // DEV only: a position outside 0 .. max_pos (64 cap - 1) stays, and full[b] = 1 instead
     int max_pos;
     int* full;             // [B], never cleared here
+    // WIN only (the ragged extend, causal_extend.hpp): sequence b's rows are nval[b] <= T of the T padded ones
+    const int* nval;       // [B] tokens the chain accepted per sequence
+    int left;              // the window is rows [T - nval[b], T) instead of [0, nval[b])
 };
 
 // grid (B H, T tokens): o = scale * (partials in split order); y = o rsqrt(mean(o^2 over V) + neps) nw g sigmoid(g), from the fp32 o
 // DEV: the one thread that advances pos[b] is the only one of the launch to read it; a frozen sequence's partial sums are the zeros
 // its step wrote, so its row needs no branch here
-template <typename T, bool DEV = false>
+// WIN: a row outside its sequence's window is written as zeros (out and y) and reads nothing else; advance[b] += nval[b].  pos is
+// not read by any other thread of this launch: the window comes from nval, which an earlier launch of the chain wrote
+template <typename T, bool DEV = false, bool WIN = false>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishArgs a) {
+    static_assert(!(DEV && WIN), "the device-positioned step has one row per sequence");
     __shared__ float red[CST_THREADS / 64];
     const int tid = threadIdx.x, bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
     const long tok = blockIdx.y;
-    if constexpr (DEV) {
+    if constexpr (WIN) {
+        const int n = a.nval[b], t0 = a.left ? (int)gridDim.y - n : 0;
+        if (h == 0 && tok == 0 && tid == 0) a.advance[b] += n;   // (nothing in this launch reads it)
+        if (tok < t0 || tok >= t0 + n) {
+            T* ob = a.out.ptr ? (T*)a.out.ptr + b * a.out.sb + tok * a.out.sn + h * a.out.sh : nullptr;
+            T* yb = a.y.ptr ? (T*)a.y.ptr + b * a.y.sb + tok * a.y.sn + h * a.y.sh : nullptr;
+            for (int c = tid; c < a.V; c += CST_THREADS) {
+                if (ob) cst_st1(ob + c, 0.f);
+                if (yb) cst_st1(yb + c, 0.f);
+            }
+            return;
+        }
+    } else if constexpr (DEV) {
         if (h == 0 && tok == 0 && tid == 0) {
             const int p = a.advance[b];
             if (p < 0 || p > a.max_pos) a.full[b] = 1;

@@ -46,11 +46,14 @@ class Block(nn.Module):
         self.mlp_norm = RMSNorm(dim)
         self.mlp = GatedMLP(dim)
 
-    def forward(self, x, cache=None, attention_mask=None):
+    def forward(self, x, cache=None, attention_mask=None, token_counts=None):
         if cache is None:
             x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask)[0]
-        else:
+        elif token_counts is None:
             x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask, past_key_values=cache, use_cache=True)[0]
+        else:
+            x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask, past_key_values=cache, use_cache=True,
+                              token_counts=token_counts)[0]
         return x + self.mlp(self.mlp_norm(x))
 
 
@@ -68,19 +71,25 @@ class GPT_MHLA(nn.Module):
             if isinstance(m, (nn.Linear, nn.Embedding)):
                 nn.init.normal_(m.weight, std=0.02)
 
-    def forward(self, input_ids, labels=None, cache=None, attention_mask=None):
+    def forward(self, input_ids, labels=None, cache=None, attention_mask=None, token_counts=None):
         """`cache` (a `DecodeCache`, model built with `exact_decoding=True`): `input_ids` are the tokens AFTER the ones the cache
         has seen -- the whole prompt on an empty cache, then one token per call, or several (the next turn, a piece of a long
         prompt, a draft to verify): on a non-empty cache those take the layer's `mhla_causal_extend` path, one launch chain per
         layer whatever their number.
         `attention_mask` [B, T] (0 = padding) is handed to every layer.  With a cache it belongs to the prefill and must be
         left-padded: every sequence is then decoded as if alone in the batch, at its own position (the layer's ragged decode
-        state), and later calls need no mask.  Logits at padding rows are unspecified."""
+        state), and later calls need no mask.  Logits at padding rows are unspecified.
+        `token_counts` (B ints in 0 .. T, a list or a tensor; with a cache whose decode state is ragged, i.e. after a masked
+        prefill): sequence b takes only the LAST `token_counts[b]` tokens of `input_ids[b]` (right-aligned, as the prefill's
+        padding) -- one slot decoding a token beside another taking a slice of a long prompt, a slot that sits the call out (0) -- in
+        one launch chain per layer; handed to every layer.  The layers' outputs at padding rows are zeros, the logits there unspecified."""
         if cache is not None and not self.exact_decoding:
             raise ValueError("GPT_MHLA.forward(cache=...) needs a model built with exact_decoding=True")
+        if token_counts is not None and isinstance(token_counts, torch.Tensor):
+            token_counts = token_counts.tolist()   # (read once for all layers)
         x = self.embeddings(input_ids)
         for blk in self.layers:
-            x = blk(x, cache, attention_mask)
+            x = blk(x, cache, attention_mask) if token_counts is None else blk(x, cache, attention_mask, token_counts)
         logits = self.lm_head(self.norm(x))
         if labels is None:
             return logits

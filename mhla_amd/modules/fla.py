@@ -232,6 +232,11 @@ class MHLA(nn.Module):
         together, each at its own position, and do not read the mask beyond its shape.  An all-ones mask gives a uniform state,
         and a padding mask on a call whose cached state is uniform raises NotImplementedError.  Steps and extensions are
         inference only (call under `torch.no_grad()`).  Adds no parameters.
+        On a cached ragged state `forward(..., token_counts=[n_0, ...])` (through `**kwargs`; B ints in 0 .. T, ignored anywhere
+        else) gives every sequence its own number of the call's tokens, RIGHT-aligned as the left-padded prefill: sequence b takes
+        rows `[T - n_b, T)` at positions `pos_b ..` (its own rotary rows), in one `mhla_causal_extend(counts=, left_padded=True)`
+        launch chain whatever the counts; the output is zero at padding rows, n_b = 0 leaves that sequence's state untouched, and
+        the cache's token count grows by what the longest sequence grew.  `use_short_conv` raises NotImplementedError.
         With a `DecodeCache(device_positions=True)` the one-token calls after the prefill are device-positioned steps (see
         `DecodeCache`; capturable in a graph); they do not reassign `mixing_matrix.data` -- generation does not change the weights
         -- and calls of several tokens on such a cache, `use_short_conv` and `head_k_dim % 8 != 0` raise NotImplementedError."""
@@ -337,6 +342,16 @@ class MHLA(nn.Module):
             attention_mask = None
         indices = None
         cu_seqlens = kwargs.get("cu_seqlens", None)
+        # token_counts (not in the reference; through **kwargs, so its signature is kept): B ints in 0 .. q_len, honoured only on a
+        # cached ragged decode state -- sequence b takes the LAST token_counts[b] rows of the call (right-aligned, as the left-padded
+        # prefill), through mhla_causal_extend(counts=, left_padded=True): one launch chain whatever the counts
+        token_counts = kwargs.get("token_counts", None) if ragged and isinstance(cached, CausalState) else None
+        if token_counts is not None:
+            if self.use_short_conv:
+                raise NotImplementedError("MHLA(exact_decoding=True): use_short_conv with token_counts")
+            token_counts = tuple(int(n) for n in (token_counts.tolist() if isinstance(token_counts, torch.Tensor) else token_counts))
+            if len(token_counts) != batch_size or any(n < 0 or n > q_len for n in token_counts):
+                raise ValueError(f"MHLA: token_counts={token_counts} must be {batch_size} ints in 0 .. {q_len}")
         if attention_mask is not None:                                       # layers/mhla.py:253-256 (get_unpad_data)
             m = attention_mask[:, -q_len:]
             indices = torch.nonzero(m.flatten(), as_tuple=False).flatten()
@@ -376,6 +391,12 @@ class MHLA(nn.Module):
             if ragged_lengths is not None:
                 pads = T - torch.tensor(ragged_lengths, device=q.device)
                 positions, table_len = (tpos[None, :] - pads[:, None]).clamp_(min=0).flatten(), T
+            elif token_counts is not None:
+                # row t of sequence b is its token pos_b + (t - (T - n_b)); padding rows (t < T - n_b) are clamped: their output is dropped
+                pads = T - torch.tensor(token_counts, device=q.device)
+                count_mask = tpos[None, :] >= pads[:, None]
+                rel = (tpos[None, :] - pads[:, None]).clamp_(min=0)
+                positions, table_len = (cached.pos.long()[:, None] + rel).flatten(), cached.seen + T
             else:
                 positions, table_len = (cached.pos.long()[:, None] + tpos[None, :]).flatten(), cached.seen + T
             q, k = q.reshape(1, B * T, self.num_heads, self.head_k_dim), k.reshape(1, B * T, self.num_heads, self.head_k_dim)
@@ -417,9 +438,11 @@ class MHLA(nn.Module):
                 g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
                 gn = self.g_norm_swish_gate
             fused_epilogue = gn is not None
-            advance = mhla_causal_step if T == 1 else mhla_causal_extend
+            seen_before = recurrent_state.seen
+            advance = mhla_causal_step if T == 1 and token_counts is None else mhla_causal_extend
+            counted = {} if token_counts is None else {"counts": token_counts, "left_padded": True}
             o = advance(q, k, v, self.mixing_matrix, recurrent_state, gate=g, norm_weight=gn.weight if gn is not None else None,
-                        norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None)
+                        norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None, **counted)
             if fused_epilogue:
                 o = o.reshape(B, T, self.value_dim)
         elif ragged_lengths is not None:
@@ -468,8 +491,9 @@ class MHLA(nn.Module):
         if dev_mode and isinstance(recurrent_state, CausalState):
             recurrent_state = recurrent_state.to_ragged()
         if past_key_values is not None and hasattr(past_key_values, "update"):   # :339-345
+            # (with token_counts the furthest sequence may have grown by fewer than q_len tokens: the cache counts what the state does)
             entry = past_key_values.update(recurrent_state=recurrent_state, conv_state=conv_states if self.use_short_conv else None,
-                                           layer_idx=self.layer_idx, offset=q_len)
+                                           layer_idx=self.layer_idx, offset=q_len if token_counts is None else recurrent_state.seen - seen_before)
             if dev_mode and isinstance(recurrent_state, CausalState):
                 # what the device-positioned steps read, made once: the matrix as this forward clamped it (generation does not change
                 # the weights), the tables of a row per position the state can reach, the norm weight in fp32
@@ -481,6 +505,8 @@ class MHLA(nn.Module):
         o = self._gate_and_project(o, hidden_states, fused_epilogue)
         if ragged_lengths is not None:                                       # zeros at padding rows, as pad_input leaves them
             o = o.masked_fill(~m.unsqueeze(-1), 0)
+        if token_counts is not None:
+            o = o.masked_fill(~count_mask.unsqueeze(-1), 0)
         if indices is not None:                                              # pad_input, :362-363
             full = o.new_zeros(batch_size * q_len, o.shape[-1])
             full.index_copy_(0, indices, o.squeeze(0))

@@ -1609,9 +1609,110 @@ def mhla_causal_step_dev(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixi
 EXTEND_WS_CAP_BYTES = 256 << 20
 
 
+def _counts_tuple(fn, counts, B, T):
+    """`counts` (a list or a tensor; reading a device tensor synchronises) as B ints in 0 .. T."""
+    counts = tuple(int(n) for n in (counts.tolist() if isinstance(counts, torch.Tensor) else counts))
+    if len(counts) != B:
+        raise ValueError(f"{fn}: counts has {len(counts)} entries, expected B={B}")
+    if any(n < 0 or n > T for n in counts):
+        raise ValueError(f"{fn}: counts={counts} must be in 0 .. T={T}")
+    return counts
+
+
+def _ragged_plan(lengths, counts, cap):
+    """What `mhla_causal_extend_ragged` is told about the device arrays of one batch slice: (max_end, max_later, any_close, the
+    last row of the mixing matrix it may read)."""
+    live = [(p, n) for p, n in zip(lengths, counts) if n]
+    if not live:
+        return 0, 0, False, 0
+    max_end = max(p + n for p, n in live)
+    max_later = max((p + n - 1) // 64 - p // 64 for p, n in live)
+    any_close = any(p % 64 + n >= 64 for p, n in live)
+    return max_end, max_later, any_close, (min(max_end // 64, cap - 1) if any_close else (max_end - 1) // 64)
+
+
+@_device_guard
+def _causal_extend_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, pos, ntok, plan, left_padded, res, norm_eps):
+    """One launch chain of `mhla_causal_extend_ragged` on what `_decode_prepare` returned, for the sequences `state` (a batch slice)
+    holds: `pos` their device positions, which the chain advances, `ntok` their token counts on the device, `plan` the host
+    values of `_ragged_plan`."""
+    lib = _lib.load()
+    B, T, H, K = q.shape
+    V = v.shape[-1]
+    dt = _dtype_code(q)
+    max_end, max_later, any_close, _ = plan
+    ws = _ws(lib.mhla_causal_extend_ragged_ws_bytes(B, T, H, K, V, max_later, dt), q.device)
+    rc = lib.mhla_causal_extend_ragged(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+                                       state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), ntok.data_ptr(), T, max_end, max_later,
+                                       int(any_close), int(bool(left_padded)), NULL_VIEW if want_y else _view(res), _view_or_null(gate),
+                                       _ptr(wf), float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K,
+                                       V, state.chunk_size, float(scale), dt, _stream())
+    _lib.check(rc, "mhla_causal_extend_ragged")
+
+
+def _extend_run(prepared, state, res, norm_eps, i, j, p, t_lo, t_hi, step_t):
+    """Tokens [t_lo, t_hi) of the padded tensors as the next tokens of sequences i .. j - 1, all at position p: the uniform launch
+    chain, cut into consecutive calls of at most `step_t` tokens at chunk boundaries."""
+    q, k, v, gate, mixf, wf, _, scale, want_y = prepared
+    part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], p, 64)
+    t0 = t_lo
+    while t0 < t_hi:
+        # the first piece fills the open chunk, so that every later one starts on a boundary
+        t1 = min(t_hi, t0 + step_t - (p + t0 - t_lo) % 64)
+        sl = lambda x: None if x is None else x[i:j, t0:t1]
+        _causal_decode(sl(q), sl(k), sl(v), sl(gate), mixf, wf, p + t0 - t_lo, scale, want_y, "mhla_causal_extend", part, sl(res), norm_eps)
+        t0 = t1
+
+
+def _extend_step_t(nb, H, K, V):
+    # tokens per call: whole chunks, so that nb H (K V / 64 + V) 4 bytes per token stay under the cap (and under the C ABI's 65535)
+    per_tok = nb * H * (K * V // 64 + V) * 4
+    return min(max(64, EXTEND_WS_CAP_BYTES // per_tok // 64 * 64), 65472)
+
+
+def _extend_counts(fn, prepared, state, counts, left_padded, res, norm_eps):
+    """Sequence b of a ragged state takes `counts[b]` of the T padded tokens: one ragged launch chain per batch slice.  A slice whose
+    workspace would exceed `EXTEND_WS_CAP_BYTES` is not cut per sequence: the whole call then runs the uniform chain sequence by
+    sequence (which cuts at chunk boundaries), and writes the padding rows itself."""
+    q, k, v, gate, mixf, wf, _, scale, want_y = prepared
+    B, T, H, K = q.shape
+    V = v.shape[-1]
+    nb = min(B, _MAX_GRID_BH // H)
+    cap = state.capacity_chunks
+    slices = [(i, min(B, i + nb), _ragged_plan(state.lengths[i:i + nb], counts[i:i + nb], cap)) for i in range(0, B, nb)]
+    # what the library checks per launch, for every slice before the first launch (see mhla_causal_step)
+    for i, j, plan in slices:
+        if plan[0] and mixf.shape[1] < plan[3] + 1:
+            raise IndexError(f"{fn}: sequences {list(range(i, j))} (lengths {state.lengths[i:j]}, counts {counts[i:j]}): row {plan[3]} of "
+                             f"mixing_matrix is read, which has only {mixf.shape[1]} columns")
+    lib = _lib.load()
+    dt = _dtype_code(q)
+    if any(lib.mhla_causal_extend_ragged_ws_bytes(j - i, T, H, K, V, plan[1], dt) > EXTEND_WS_CAP_BYTES for i, j, plan in slices):
+        res.zero_()
+        step_t = _extend_step_t(1, H, K, V)
+        for b, (p, n) in enumerate(zip(state.lengths, counts)):
+            if n:
+                t_lo = T - n if left_padded else 0
+                _extend_run(prepared, state, res, norm_eps, b, b + 1, p, t_lo, t_lo + n, step_t)
+        state.pos += torch.tensor(counts, dtype=torch.int32).to(state.pos.device, non_blocking=False)
+    else:
+        ntok = torch.tensor(counts, dtype=torch.int32).to(q.device)   # the one small copy of the call
+        for i, j, plan in slices:
+            if B <= nb:   # the usual case, one launch chain: no views to build
+                _causal_extend_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, state.pos, ntok, plan, left_padded, res, norm_eps)
+                break
+            sl = lambda x: None if x is None else x[i:j]
+            part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], 0, 64)
+            _causal_extend_ragged(sl(q), sl(k), sl(v), sl(gate), mixf, wf, scale, want_y, part, state.pos[i:j], ntok[i:j], plan, left_padded,
+                                  sl(res), norm_eps)
+    state.lengths = tuple(p + n for p, n in zip(state.lengths, counts))
+    state.seen = max(state.lengths)
+    return res
+
+
 def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
                        scale: Optional[float] = None, gate: Optional[torch.Tensor] = None, norm_weight: Optional[torch.Tensor] = None,
-                       norm_eps: float = 1e-5, epilogue: Optional[bool] = None) -> torch.Tensor:
+                       norm_eps: float = 1e-5, epilogue: Optional[bool] = None, counts=None, left_padded: bool = False) -> torch.Tensor:
     """T >= 1 new tokens on an existing decode state in one call: q, k `[B, T, H, K]`, v (and `gate`) `[B, T, H, V]` of the tokens
     at positions `state.seen .. state.seen + T - 1`; returns those rows of `mhla_causal` over the whole sequence, `[B, T, H, V]`,
     updates `state` in place as T calls of `mhla_causal_step` would and adds T to `state.seen` -- the next turn of a
@@ -1622,9 +1723,22 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     capacity (raised before anything is launched, the state untouched): as `mhla_causal_step`.  The workspace holds one fp32
     [K, V] tile per (b, h) and chunk touched after the first, plus the T fp32 output rows; an extension that would need more than
     `EXTEND_WS_CAP_BYTES` (256 MiB) is cut into consecutive calls at chunk boundaries.
-    On a ragged state every sequence gets T new tokens, at positions `lengths[b] ..`: the same launch chain runs once per run of
-    adjacent sequences of equal length (correct, but not launch-optimal across differing lengths: there is no ragged extend
-    kernel), then T is added to the device positions and to `lengths`."""
+    On a ragged state every sequence gets T new tokens, at positions `lengths[b] ..`.  Equal lengths: the uniform launch chain.
+    Differing lengths: ONE ragged launch chain (at most six launches whatever B and the lengths), whose kernels read every
+    sequence's position from `state.pos` and give each sequence the bits it would get alone in a batch of one; then T is added to the
+    device positions (by the chain) and to `lengths`.
+    counts (a list or a tensor of B ints in 0 .. T; a device tensor is read once, which synchronises; needs a ragged state --
+    `state.to_ragged()` makes one -- that is not stale): sequence b takes `counts[b]` tokens only, rows `[0, counts[b])` of the
+    padded tensors, or `[T - counts[b], T)` with `left_padded` -- a decoding slot beside a 256-token slice of a long prompt, drafts of
+    different lengths, a slot that sits this call out (0: its state stays bit for bit).  The same single ragged chain, whatever
+    the counts; one small host-to-device copy (the counts).  Rows outside a sequence's window are never read and come back as
+    zeros; `state.pos` advances on the device, `lengths` by `counts`, `seen` to `max(lengths)`.  A count of 1 is that sequence's
+    `mhla_causal_step` (the same bits as in a batch of one).  IndexError, before anything is launched and naming the
+    sequences, when one would exceed the mixing matrix or the capacity.  All counts 0: nothing is launched, zeros are returned.
+    Batches beyond one launch's (b, h) range are sliced; a ragged call whose workspace would exceed `EXTEND_WS_CAP_BYTES` is not cut
+    per sequence but falls back to the uniform chain sequence by sequence (which cuts at chunk boundaries): the same rows and
+    state within fp32 rounding, more launches."""
+    fn = "mhla_causal_extend"
     if not isinstance(state, CausalState):
         raise TypeError(f"mhla_causal_extend: state must be a CausalState, got {type(state).__name__}")
     state._refuse_stale("mhla_causal_extend")
@@ -1634,27 +1748,40 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     V = v.shape[-1]
     if T < 1:
         raise ValueError(f"mhla_causal_extend takes at least one token per call, got T = {T}")
+    if counts is not None:
+        counts = _counts_tuple(fn, counts, B, T)
+        if state.lengths is None:
+            raise ValueError(f"{fn}: counts needs a ragged state and this one is uniform ({state!r}); the positions must live on the "
+                             "device: pass state.to_ragged()")
+        if len(state.lengths) != B:
+            raise ValueError(f"{fn}: the state holds {len(state.lengths)} sequences, the tokens B={B}")
+        if mixing_matrix.dim() < 2:
+            raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
+        L, cap = mixing_matrix.shape[0], state.capacity_chunks
+        need = [(p + n + 63) // 64 if n else 0 for p, n in zip(state.lengths, counts)]
+        for limit, what in ((L, f"mixing_matrix has only {L} rows"), (cap, f"the state holds only {cap}")):
+            over = [b for b, c in enumerate(need) if c > limit]
+            if over:
+                raise IndexError(f"{fn}: sequences {over} (lengths {tuple(state.lengths[b] for b in over)} + counts "
+                                 f"{tuple(counts[b] for b in over)}) need up to {max(need)} chunks but {what}")
+        prepared = _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=False)
+        if not any(counts):
+            return torch.zeros((B, T, H, V), dtype=q.dtype, device=q.device)
+        return _extend_counts(fn, prepared, state, counts, left_padded, _alloc_like_tokens(B, T, H, V, q), norm_eps)
     if T == 1:
         return mhla_causal_step(q, k, v, mixing_matrix, state, scale=scale, gate=gate, norm_weight=norm_weight, norm_eps=norm_eps,
                                 epilogue=epilogue)
-    q, k, v, gate, mixf, wf, pos, scale, want_y = _decode_prepare("mhla_causal_extend", q, k, v, mixing_matrix, state, scale, gate,
-                                                                  norm_weight, epilogue)
+    prepared = _decode_prepare("mhla_causal_extend", q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue)
+    pos = prepared[6]
     res = _alloc_like_tokens(B, T, H, V, q)
+    if state.lengths is not None and any(n != state.lengths[0] for n in state.lengths):
+        return _extend_counts(fn, prepared, state, (T,) * B, False, res, norm_eps)
     nb = min(B, _MAX_GRID_BH // H)
-    # tokens per call: whole chunks, so that nb H (K V / 64 + V) 4 bytes per token stay under the cap (and under the C ABI's 65535)
-    per_tok = nb * H * (K * V // 64 + V) * 4
-    step_t = min(max(64, EXTEND_WS_CAP_BYTES // per_tok // 64 * 64), 65472)
+    step_t = _extend_step_t(nb, H, K, V)
     # (batches beyond one launch's (b, h) range: see mhla_blockmix)
     runs = ((i, min(B, i + nb), pos) for i in range(0, B, nb)) if state.lengths is None else _runs(state.lengths, nb)
     for i, j, p in runs:
-        part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], p, 64)
-        t0 = 0
-        while t0 < T:
-            # the first piece fills the open chunk, so that every later one starts on a boundary
-            t1 = min(T, t0 + step_t - (p + t0) % 64)
-            sl = lambda x: None if x is None else x[i:j, t0:t1]
-            _causal_decode(sl(q), sl(k), sl(v), sl(gate), mixf, wf, p + t0, scale, want_y, "mhla_causal_extend", part, sl(res), norm_eps)
-            t0 = t1
+        _extend_run(prepared, state, res, norm_eps, i, j, p, 0, T, step_t)
     if state.lengths is not None:
         state.pos += T
         state.lengths = tuple(n + T for n in state.lengths)

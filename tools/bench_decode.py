@@ -39,6 +39,15 @@ Then a GPT 340M decode step (24 layers, bf16, B = 8, prompt 100): eager on an or
 whole-model step replayed; the positions advance (a boundary every 64th step is part of the average).  Last line: the GPU kernels one
 layer's decode step launches before and after (torch.profiler; null where the profiler gives no device events).
 
+`--mixed`: a mixed serving batch at the C5 head (H = 4, K = 128, V = 256, bf16, L = 128), B = 8: seven sequences at positions of their
+own (chunks 13 .. 17, every one at another place in its chunk, none on a boundary) decode ONE token each while the eighth takes a
+256-token slice of a long prompt (from position 1000: it closes four chunks).  (a) ONE `mhla_causal_extend(counts=, left_padded=True)`
+call -- the ragged launch chain -- against (b) what such a batch costs without it: one `mhla_causal_extend` per sequence on its B = 1
+slice of the same state (for one token that is the step).  Alternating in one run, `--reps` times, `--steps` calls each: wall time per
+call with median, min and max, the device time of the library's kernels and the launches per call (the per-launch event hook).  The
+state is put back before every call -- host mirror and a 32-byte device copy of the positions, given to both variants -- so that every
+call is the same work.
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -286,6 +295,75 @@ def graph_config(B, H, K, V, steps, reps):
     return rec
 
 
+def launch_counts(fn):
+    """{kernel: launches} of one call of `fn` (the library's per-launch hook)."""
+    import ctypes
+    lib = mhla_amd._lib.load()
+    buf = ctypes.create_string_buffer(1 << 14)
+    torch.cuda.synchronize()
+    lib.mhla_prof_report(buf, len(buf))
+    lib.mhla_prof_enable(1)
+    fn()
+    torch.cuda.synchronize()
+    lib.mhla_prof_enable(0)
+    lib.mhla_prof_report(buf, len(buf))
+    return {ln.rsplit(" ", 2)[0]: int(ln.rsplit(" ", 2)[1]) for ln in buf.value.decode().splitlines() if ln.strip()}
+
+
+def mixed_config(H, K, V, steps, reps, slice_tokens=256):
+    B = 8
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    lengths = tuple((13 + b % 5) * 64 + 5 + (9 * b) % 50 for b in range(B - 1)) + (1000,)
+    counts = (1,) * (B - 1) + (slice_tokens,)
+    T = slice_tokens
+    q, k = (torch.randn(B, T, H, K, generator=g).to(torch.bfloat16).to(DEV) for _ in range(2))
+    v = torch.randn(B, T, H, V, generator=g).to(torch.bfloat16).to(DEV)
+    st = mhla_amd.CausalState.empty(B, H, K, V, L, DEV)
+    st.S[:, :, :24].normal_(0, 0.1)
+    st.P.normal_(0, 0.1)
+    rag = mhla_amd.CausalState(st.S, st.P, st.Cur, lengths=lengths)
+    ones = [mhla_amd.CausalState(st.S[b:b + 1], st.P[b:b + 1], st.Cur[b:b + 1], lengths[b]) for b in range(B)]
+    pos0 = torch.tensor(lengths, dtype=torch.int32, device=DEV)
+    spare = torch.empty_like(pos0)
+    toks = [tuple(t[b:b + 1, T - n:] for t in (q, k, v)) for b, n in enumerate(counts)]   # right-aligned, as the ragged call reads them
+
+    def ragged():
+        rag.lengths, rag.seen = lengths, max(lengths)
+        rag.pos.copy_(pos0)
+        mhla_amd.mhla_causal_extend(q, k, v, mix, rag, counts=counts, left_padded=True)
+
+    def per_sequence():
+        spare.copy_(pos0)
+        for b in range(B):
+            ones[b].seen = lengths[b]
+            mhla_amd.mhla_causal_extend(*toks[b], mix, ones[b])
+
+    fns = {"ragged_chain": ragged, "per_sequence": per_sequence}
+    wall = {n: [] for n in fns}
+    dev = {n: [] for n in fns}
+    kern = {}
+    with torch.no_grad():
+        for _ in range(reps):
+            for n, fn in fns.items():
+                wall[n].append(batch_us(fn, steps))
+            for n, fn in fns.items():
+                kern[n] = kernel_times(fn, iters=20)
+                dev[n].append(sum(kern[n].values()))
+            st.Cur.zero_()
+        launches = {n: launch_counts(fn) for n, fn in fns.items()}
+    med = {n: statistics.median(x) for n, x in wall.items()}
+    rec = {"mixed": {"B": B, "H": H, "K": K, "V": V, "lengths": lengths, "counts": counts}, "steps_per_batch": steps, "reps": reps,
+           "wall_us": {n: spread(x) for n, x in wall.items()}, "device_us": {n: spread(x) for n, x in dev.items()},
+           "per_sequence_over_ragged_wall": round(med["per_sequence"] / med["ragged_chain"], 2),
+           "per_sequence_over_ragged_device": round(statistics.median(dev["per_sequence"]) / statistics.median(dev["ragged_chain"]), 2),
+           "launches": {n: {"total": sum(c.values()), "by_kernel": c} for n, c in launches.items()},
+           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()},
+           "ragged_wall_median_below_per_sequence_min": med["ragged_chain"] < min(wall["per_sequence"])}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def gpu_kernel_count(fn):
     """GPU kernels one call of `fn` launches, or None where the profiler reports no device events."""
     try:
@@ -425,8 +503,11 @@ if __name__ == "__main__":
     ap.add_argument("--extend", action="store_true")
     ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--graph", action="store_true")
+    ap.add_argument("--mixed", action="store_true")
     a = ap.parse_args()
-    if a.graph:
+    if a.mixed:
+        mixed_config(4, 128, 256, max(100, a.steps), a.reps)
+    elif a.graph:
         for B in (8, 32):
             graph_config(B, 4, 128, 256, max(200, a.steps), a.reps)
         gpt_graph(a.steps, a.reps)
