@@ -188,6 +188,11 @@ int bm_state(const BmPlan& p, const BmCall& c, const StateArgs& a) {
             return launch(sp::k_sp_state<ET, DT, TRANS, true, SNT, S16>, g, dim3(SNT), sp::sp_state_smem<DT>(), c.st, name, a);
         return MHLA_OK;
     }
+    // (forward on h16 summaries without a split normaliser pair: the instantiation that has no third row stream)
+    if constexpr (TRANS == 0 && bm_h16_built<ET, DT, S16>()) {
+        if (p.fmt == SF_H16 && !(c.normalize && c.split) && g_recut.load())
+            return launch(sp::k_sp_state<ET, DT, 0, false, SNT, S16, 2, false, false>, g, dim3(SNT), sp::sp_state_smem<DT>(), c.st, name, a);
+    }
     // (backward on h16 / p24, 16-bit tensors, D <= 64: the row dots come from G_i; two more LDS tiles)
     WITH_PF(p.fmt, return launch(sp::k_sp_state<ET, DT, TRANS, false, SNT, S16, PF>, g, dim3(SNT),
                                  (PF && TRANS && sizeof(ET) == 2 && DT <= 4) ? sp::sp_state_rd_smem<DT>() : sp::sp_state_smem<DT>(), c.st, name, a));
@@ -211,6 +216,11 @@ int bm_state_and_mix(const BmPlan& p, const BmCall& c) {
 // ---- output O_i = Q_i G_i / n_i: the forward's, and the backward's recompute of what the forward's 16-bit store of O rounded away ----
 template <typename ET, int DT, bool S16, typename TO = ET, bool EPI = false>
 int sp_out(const BmPlan& p, const BmCall& c, const OutArgs& o, const char* name) {
+    // (16-bit tensors on h16 summaries, D <= 64, blocks of at most 64 tokens: the instantiation of one tile per wave)
+    if constexpr (!EPI && bm_h16_built<ET, DT, S16>() && DT <= 4) {
+        if (p.fmt == SF_H16 && bm_one_tile(c.S))
+            return launch(sp::k_sp_out<ET, DT, TO, false, S16, 2, false, false, true>, dim3(c.M, c.B * c.H), dim3(sp::SP_OUT_T), sp::sp_out_smem<DT, S16>(), c.st, name, o);
+    }
     WITH_PF(p.fmt, return launch(sp::k_sp_out<ET, DT, TO, EPI, S16, PF>, dim3(c.M, c.B * c.H), dim3(sp::SP_OUT_T), sp::sp_out_smem<DT, S16>(), c.st, name, o));
     return MHLA_OK;
 }
@@ -316,7 +326,12 @@ int bm_tok(const BmPlan& p, const BmCall& c, const TokArgs& t) {
         return MHLA_OK;
     }
     // (16-bit tensors: q_den in 16-byte pieces when it only feeds dksum; not at D = 72 / 80, where the wider rows cost a wave of occupancy)
-    if (c.normalize && !c.relu() && sizeof(ET) == 2 && DT != 5) WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, true, PF>, g, blk, sp::sp_tok_smem<DT, S16>(), c.st, p.n_tok[0], t)));
+    const bool wq = c.normalize && !c.relu() && sizeof(ET) == 2 && DT != 5;
+    // (h16 summaries, D <= 64, blocks of at most 64 tokens: a wave has one tile at the most -- the loop-free instantiation)
+    constexpr bool ONE_BUILT = bm_h16_built<ET, DT, S16>() && DT <= 4;
+    if (wq && ONE_BUILT && p.fmt == SF_H16 && bm_one_tile(c.S)) {
+        if constexpr (ONE_BUILT) RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, true, 2, true>, g, blk, sp::sp_tok_smem<DT, S16>(), c.st, p.n_tok[0], t));
+    } else if (wq) WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, true, PF>, g, blk, sp::sp_tok_smem<DT, S16>(), c.st, p.n_tok[0], t)));
     else WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, false, PF>, g, blk, sp::sp_tok_smem<DT, S16>(), c.st, p.n_tok[0], t)));
     WITH_PF(p.fmt, return launch(sp::k_sp_bwd_dkv<ET, DT, false, S16, PF>, g, blk, sp::sp_tok_smem<DT, S16>(), c.st, p.n_tok[1], t));
     return MHLA_OK;

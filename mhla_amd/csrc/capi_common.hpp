@@ -87,7 +87,7 @@ inline std::atomic<unsigned long long*> g_trace{nullptr};
 #define SP_MIXH2_TE 64   // slice width of k_sp_mixh2 in summary elements
 #endif
 // (mhla_set_option("recut_kernels", 0): the kernels they replaced -- k_sp_mixh at twelve / sixteen waves, the block-per-workgroup Wan output
-// kernel -- for A/B timing and for the bit-equality tests; MHLA_WAN_FLAT=0 / MHLA_RECUT=0 in the environment set the start value)
+// kernel, the loop forms of the one-tile token kernels (bm_one_tile below), k_sp_state with the stand-in third stream -- for A/B timing and for the bit-equality tests; MHLA_WAN_FLAT=0 / MHLA_RECUT=0 in the environment set the start value)
 inline std::atomic<int> g_recut{[] { const char* e = getenv("MHLA_RECUT"); const char* f = getenv("MHLA_WAN_FLAT"); return ((e && e[0] == '0') || (f && f[0] == '0')) ? 0 : 1; }()};
 inline bool sp_mixh2_applies(int M, long E, long BH, long S = 0) {
     if (M <= 128 || M > 256 || !g_recut.load()) return false;
@@ -96,6 +96,9 @@ inline bool sp_mixh2_applies(int M, long E, long BH, long S = 0) {
     const long total = BH * ((E + SP_MIXH2_TE - 1) / SP_MIXH2_TE), wgs = std::min<long>(total, 256);
     return wgs > 0 && (total + wgs - 1) / wgs >= SP_MIXH2_MIN_SLICES;
 }
+// The split-operand token kernels walk a block's 16-token tiles four waves abreast: with at most 64 tokens per block a wave has one tile
+// at the most, and the instantiations without the tile loop and its look-ahead serve the launch ("recut_kernels" 0: the loop kernels)
+inline bool bm_one_tile(int S) { return S <= 64 && g_recut.load(); }
 // mhla_set_option("fp32_summaries") / MHLA_FP32_SUMMARIES=1 (read once): the resident-mixing pipeline keeps its summaries as fp32 instead of 24-bit floats
 inline std::atomic<int> g_no_p24{[] { const char* e = getenv("MHLA_FP32_SUMMARIES"); return (e && e[0] == '1') ? 1 : 0; }()};
 

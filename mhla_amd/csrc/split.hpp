@@ -340,13 +340,18 @@ template <int DT> __host__ __device__ constexpr int sp_state_rd_smem() {   // (i
 // one operand that is an INTERMEDIATE (dP = dO / n, MODE 1) is split into hi + lo parts whatever the tensor type
 // PRO (MODE 0, Wan inference): x and qd are 16-bit projection outputs; relu(x * rstd[token] * w[channel]) + eps is applied on load
 // (StateArgs::pro_*), the values then carry a lo part like fp32 tensors
-template <typename T, int DT, int MODE, bool ROPE = false, int NT = NTHREADS, bool S16 = Sum16<T>::value, int P24 = 0, bool PRO = false>
+// TS: the call may have a third token tensor (MODE 0: the split pair's k_den, MODE 1: the forward output).  false (MODE 0, picked by the
+// launch when the call has no split normaliser pair): no third row stream -- it was pointed at the key rows again and its values zeroed,
+// half as many requests again in the chunk loop -- and no registers for it
+template <typename T, int DT, int MODE, bool ROPE = false, int NT = NTHREADS, bool S16 = Sum16<T>::value, int P24 = 0, bool PRO = false, bool TS = true>
 __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state(const StateArgs a) {
+    static_assert(TS || MODE == 0, "the backward's third tensor is a property of its arithmetic (RD), not of the call");
     static_assert(!PRO || (MODE == 0 && !S16), "the prologue on load serves the forward's summary kernel");
     static_assert(!P24 || !S16, "p24 is a format of the fp32-grade summaries");
     // RD: the row dots dO . O = dO' . (Q G_i) are formed from the mixed summary G_i (staged as hi / lo tiles beside the operand tiles): the
     // stored output and its residual are not read, and the forward does not write the residual (capi_common.hpp bm_rowdots_from_g)
     constexpr bool RD = MODE == 1 && P24 && sizeof(T) == 2 && DT <= 4 && !ROPE;
+    constexpr bool THIRD = TS && !RD;   // a third row stream exists
     constexpr bool TN = !RD;   // the token tiles in the conflict-free layout (Geo::LD, mat_row)
     constexpr int DW = Geo<DT>::DW, LD = TN ? Geo<DT>::LD : Geo<DT>::LDR, CGS = Geo<DT>::CGS, RPP = NT / CGS, IT = 32 / RPP, NWV = NT / 64,
                   RT = (DT + NWV - 1) / NWV, TILE = 32 * LD;
@@ -372,14 +377,14 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
     const T* vb = (const T*)a.y.ptr + b * a.y.sb + h * a.y.sh;
     const View& third = MODE == 0 ? a.kd : a.o;   // MODE 0: the normaliser's keys; MODE 1: the forward output
     const T* kdb = (const T*)third.ptr + b * third.sb + h * third.sh;
-    const bool den = a.normalize && ((MODE == 1 && !RD) || (MODE == 0 && a.split));   // a third tensor is read
+    const bool den = THIRD && a.normalize && ((MODE == 1 && !RD) || (MODE == 0 && a.split));   // a third tensor is read
     const int r0 = tid / CGS, cg = (tid % CGS) * 8;
     const float* ninvb = a.ninv + ((long)bh * a.M + blk) * S;   // MODE 1
 
     // the chunk's rows AS LOADED (kr, vr, dr): converted in `settle`, at the commit -- `ld8` converted them as they arrived, i.e. the wait for
     // the next chunk sat right behind its request, in front of this chunk's products (tools/isa_waits.py: `L L L L W3 W2` at the loop top)
-    typename Raw4<T>::type kr[IT][2], vr[IT][2], dr[IT][2];
-    f32x4 kx[IT][2], vx[IT][2], dx[IT][2], rc[ROPE ? IT : 1], rs[ROPE ? IT : 1];
+    typename Raw4<T>::type kr[IT][2], vr[IT][2], dr[THIRD ? IT : 1][2];
+    f32x4 kx[IT][2], vx[IT][2], dx[THIRD ? IT : 1][2], rc[ROPE ? IT : 1], rs[ROPE ? IT : 1];
     float nv[IT];
     float prr[PRO ? IT : 1];   // PRO: the rows' rstd
     f32x4 pw[PRO ? 2 : 1];     // ... and the norm weights of the thread's 8 channels
@@ -431,8 +436,10 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
             kr[it][1] = gld<typename Raw4<T>::type>(kb + row * a.x.sn + cgc + 4);
             vr[it][0] = gld<typename Raw4<T>::type>(vb + row * a.y.sn + cgc);
             vr[it][1] = gld<typename Raw4<T>::type>(vb + row * a.y.sn + cgc + 4);
-            dr[it][0] = gld<typename Raw4<T>::type>(kdq + row * kdsn + cgc);
-            dr[it][1] = gld<typename Raw4<T>::type>(kdq + row * kdsn + cgc + 4);
+            if constexpr (THIRD) {
+                dr[it][0] = gld<typename Raw4<T>::type>(kdq + row * kdsn + cgc);
+                dr[it][1] = gld<typename Raw4<T>::type>(kdq + row * kdsn + cgc + 4);
+            }
             nv[it] = gld<float>(nvp + ((MODE == 1 && a.normalize) ? rcl : 0));
             if constexpr (PRO) prr[it] = gld<float>(a.pro_rk ? a.pro_rk + b * a.pro_n + row : reinterpret_cast<const float*>(a.x.ptr));
             if constexpr (OLO) ox[it] = gld<uint4>(olop + (olo_on ? (long)rcl * D : 0));
@@ -454,7 +461,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
             for (int hf = 0; hf < 2; ++hf) {
                 kx[it][hf] = raw4_to_f32(T{}, kr[it][hf]);
                 vx[it][hf] = raw4_to_f32(T{}, vr[it][hf]);
-                dx[it][hf] = raw4_to_f32(T{}, dr[it][hf]);
+                if constexpr (THIRD) dx[it][hf] = raw4_to_f32(T{}, dr[it][hf]);
             }
             if constexpr (PRO) {
                 const float r = a.pro_rk ? prr[it] : 1.f;   // ((x rstd) w: the order of k_qk_prologue, so that the two paths agree bit for bit)
@@ -464,7 +471,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
             if (a.relu) relu8(kx[it][0], kx[it][1], a.eps);
             kx[it][0] = valid ? kx[it][0] : z4; kx[it][1] = valid ? kx[it][1] : z4;
             vx[it][0] = valid ? vx[it][0] : z4; vx[it][1] = valid ? vx[it][1] : z4;
-            dx[it][0] = (valid && den) ? dx[it][0] : z4; dx[it][1] = (valid && den) ? dx[it][1] : z4;
+            if constexpr (THIRD) { dx[it][0] = (valid && den) ? dx[it][0] : z4; dx[it][1] = (valid && den) ? dx[it][1] : z4; }
             if constexpr (OLO) {   // O = stored value + what the store rounded away
                 const unsigned w[4] = {ox[it].x, ox[it].y, ox[it].z, ox[it].w};
                 const bool on = valid && olo_on;
@@ -494,7 +501,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
             const int off = mat_row<TN>(r0 + RPP * it) * LD + cg;
             uint4 hi, lo;
             if (MODE == 1 && a.normalize) {   // dn[s] and the 1/n scaling of dO
-                if constexpr (!RD) {
+                if constexpr (THIRD) {
                     float d = 0.f;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) d += vx[it][0][i] * dx[it][0][i] + vx[it][1][i] * dx[it][1][i];
@@ -522,7 +529,8 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
             *reinterpret_cast<uint4*>(Vh + off) = hi;
             if (LOY) *reinterpret_cast<uint4*>(Vl + off) = lo;
             if (MODE == 0) {
-                const f32x4* s = den ? dx[it] : kx[it];
+                const f32x4* s = kx[it];
+                if constexpr (THIRD) s = den ? dx[it] : kx[it];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     ksp[i] += s[0][i];
@@ -1660,7 +1668,9 @@ constexpr int SP_OUT_T = 512;   // 8 waves share the staged G_i: twice the loads
 // quantises twice at the Wan shape -- 14 tiles on 8 waves are two rounds (87.5 %), 1 800 workgroups on 256 CUs are eight waves of
 // workgroups for 7.03 (88 %) -- 77 % together; the flat list leaves the last round of a range (98.4 tiles in 13 rounds: 94.6 %).
 // OutArgs::nbh = B H; needs at least 8 tiles per block (a round then spans at most two blocks, the next round at most one more).
-template <typename T, int DT, typename TO = T, bool EPI = false, bool S16 = Sum16<T>::value, int P24 = 0, bool PRO = false, bool FLAT = false>   // PRO: the q prologue on load (OutArgs::pro_*)
+// ONE: the launch has S <= 64 -- a wave has its one tile `wave` at the most: no loop, no second row set, no fetch of a next tile (it was
+// clamped onto the block's last row and dropped) and no map look-ahead
+template <typename T, int DT, typename TO = T, bool EPI = false, bool S16 = Sum16<T>::value, int P24 = 0, bool PRO = false, bool FLAT = false, bool ONE = false>   // PRO: the q prologue on load (OutArgs::pro_*)
 #ifndef SP_OUT_EPI_WAVES
 #define SP_OUT_EPI_WAVES 2   // the fused-epilogue variant takes 142 VGPRs: one workgroup per CU without spills (157 us at C4) beats two with 28 spilled registers (163 us)
 #endif
@@ -1669,6 +1679,7 @@ __global__ __launch_bounds__(SP_OUT_T, EPI ? SP_OUT_EPI_WAVES : 2) void k_sp_out
     constexpr bool LO = !std::is_same<T, bf16_t>::value || PRO;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     static_assert(!FLAT || (P24 == 1 && sizeof(T) == 2 && !S16), "the flat tile list serves 16-bit tensors with 24-bit summaries");
+    static_assert(!ONE || (!FLAT && SP_OUT_T / 64 >= 4), "one tile per wave: blocks of at most 64 tokens, one block per workgroup");
     u16* Gh = reinterpret_cast<u16*>(smem_raw);   // [d1][d2], rows >= D and columns >= D zero   (FLAT: two (hi, lo) pairs, block parity)
     u16* Gl = Gh + TILE;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nl = lane & 15, kg = lane >> 4;
@@ -1978,10 +1989,17 @@ __global__ __launch_bounds__(SP_OUT_T, EPI ? SP_OUT_EPI_WAVES : 2) void k_sp_out
         int lk = 0;
         if (a.idx) lk = gld<int>(a.idx + p0 + min(wave * 16 + nl, S - 1));   // (uniform branch; nothing is in flight yet)
         fetch(wave, cur, lk);
-        lk = look(wave + NWV);   // (for the next fetch)
+        if constexpr (!ONE) lk = look(wave + NWV);   // (for the next fetch)
         // (S16: G_i stored as bf16: no lo tile)
         stage_mat_split<DT, S16, SP_OUT_T, P24>(Gh, Gl, a.g, ((long)bh * a.M + blk) * a.es, D, tid);
         __syncthreads();
+        if constexpr (ONE) {
+            if (wave * 16 < S) {   // (uniform)
+                early();
+                tile(wave, true);
+            }
+            return;
+        }
         for (int tt = wave; tt * 16 < S; tt += NWV) {
             if constexpr (DBL) {
                 early();
@@ -2359,7 +2377,9 @@ __device__ __forceinline__ bf16x8 row_read8(const u16* tile, int ld, int c0, int
 // transposed rotation before dz ksum^T is added, so the one stored tensor is the gradient of the un-rotated q
 // WQ: q_den enters only dksum (normaliser on, no relu prologue) and is fetched in 16-byte pieces in the operand layout; otherwise in
 // the output layout, where the relu gradient mask needs it (a template flag: both register sets at once cost the occupancy)
-template <typename T, int DT, bool ROPE = false, bool S16 = Sum16<T>::value, bool WQ = false, int P24 = 0>
+// ONE: the launch has S <= 64, so a wave has at most its one tile `wave`: no loop, no second row set and no look-ahead -- the loop's
+// unconditional prefetch asked for the wave's own rows a second time there (every dO and q_den piece, 1 / n, dz and a map entry)
+template <typename T, int DT, bool ROPE = false, bool S16 = Sum16<T>::value, bool WQ = false, int P24 = 0, bool ONE = false>
 __global__ __launch_bounds__(NTHREADS, (DT <= 4 && WQ) ? 4 : 2) void k_sp_bwd_dq(const TokArgs a) {
     constexpr int LD = mat_ld<DT>(), DW = Geo<DT>::DW, KST = Geo<DT>::KST, TILE = KST * 32 * LD;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -2425,7 +2445,7 @@ __global__ __launch_bounds__(NTHREADS, (DT <= 4 && WQ) ? 4 : 2) void k_sp_bwd_dq
     int lk = 0;
     if (a.idx) lk = gld<int>(a.idx + p0 + min(wave * 16 + nl, S - 1));   // (uniform branch; nothing is in flight yet)
     fetch(wave, cur, lk);   // in flight while G_i is staged
-    lk = look(wave + 4);
+    if constexpr (!ONE) lk = look(wave + 4);
     const float ksum_v = gld<float>(a.normalize ? a.ksum + ((long)bh * M + blk) * D + min(tid, D - 1) : standin);
     stage_mat_split<DT, S16, NTHREADS, P24>(Gh, Gl, a.g, ((long)bh * M + blk) * a.es, D, tid);
     if (tid < DW) ksum[tid] = (a.normalize && tid < D) ? ksum_v : 0.f;
@@ -2513,11 +2533,15 @@ __global__ __launch_bounds__(NTHREADS, (DT <= 4 && WQ) ? 4 : 2) void k_sp_bwd_dq
             }
         }
     };
-    for (int tt = wave; tt * 16 < S; tt += 4) {
-        fetch((tt + 4) * 16 < S ? tt + 4 : tt, nxt, lk);   // (unconditional; the wave's last tile: itself again -- lines it has just read)
-        lk = look(tt + 8);
-        tile();
-        cur = nxt;
+    if constexpr (ONE) {
+        if (wave * 16 < S) tile();   // (uniform)
+    } else {
+        for (int tt = wave; tt * 16 < S; tt += 4) {
+            fetch((tt + 4) * 16 < S ? tt + 4 : tt, nxt, lk);   // (unconditional; the wave's last tile: itself again -- lines it has just read)
+            lk = look(tt + 8);
+            tile();
+            cur = nxt;
+        }
     }
     if (a.normalize) {   // dksum[d] = sum_s dz[s] qden[s][d]: over the 16 token lanes, then over the waves
         if constexpr (WQ) {   // the lane's features 32 ks + 8 kg + 0..7
@@ -2574,7 +2598,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_bwd_dkv(const TokArgs a) {  
     // the gather map's entry of the lane's row, looked up one fetch ahead (without a map: the summaries' first word, dropped)
     // (a wave whose tile is the block's last prefetches ITS OWN tile again -- lines it has just read; re-reading the block's last tile cost
     // the L2 a second pass over K and V, and a stand-in address selected by `has a next tile` became a branch around the loads.  A loop-free
-    // second copy of the tile body for blocks of one tile per wave cost 30 registers and the fourth workgroup per CU)
+    // second copy of the tile body for blocks of one tile per wave cost 30 registers and the fourth workgroup per CU; as an instantiation of
+    // its own -- the form k_sp_bwd_dq and k_sp_out run at S <= 64 -- it took 78 registers for 126 and measured 61.9 -> 61.4, 61.9 -> 61.4 and
+    // 62.2 -> 62.4 us at C2: this kernel's branch already keeps the second request away, so there was nothing to remove)
     auto look = [&](int tt) { return gld<int>(a.idx ? a.idx + p0 + min(tt * 16 + nl, S - 1) : reinterpret_cast<const int*>(a.dkv)); };
     auto fetch = [&](int tt, Rows& R, int looked) __attribute__((always_inline)) {
         const int s = tt * 16 + nl, sv = min(s, S - 1);
