@@ -310,6 +310,35 @@ int mhla_causal_bwd(mhla_view q, mhla_view k, mhla_view v, const float* mix, int
                     int B, int T, int H, int K, int V, int chunk,
                     float scale, int dtype, unsigned flags, void* stream);
 
+/* Packed sequences (cu_seqlens): one row of T tokens (B = 1 by convention; B > 1 applies the same table to every batch row) holds
+ * several sequences, and each is computed exactly as if it were alone in a call of its own (added without a change of any
+ * existing signature or behaviour: MHLA_ABI_VERSION stays 9).  The caller cuts every sequence into its own 64-token chunks
+ * (ragged last chunk, none for an empty sequence), numbers them c = 0 .. n_chunks - 1 along the pack and passes
+ *   chunk_tab_dev  device int32 [n_chunks][2]: {first token row, rows in 1 .. 64} of chunk c, 8-byte aligned
+ *   mix            fp32 [n_chunks, n_chunks]: mix_eff[c][c'] = mix[loc(c)][loc(c')] where c, c' belong to the same sequence
+ *                  and c' <= c (loc: the chunk's index within its sequence), 0 elsewhere.
+ * The calls are then the uniform calls above over n_chunks chunks: the same kernels (the token-facing ones take a chunk's rows
+ * from the table instead of from its index), grids, dispatch -- the 16-bit pipeline serves bf16 with K, V multiples of 64,
+ * K <= 256 and n_chunks <= 256 -- and workspace layout, all by n_chunks; T stays the token count of the views.  dmix is the
+ * gradient of mix_eff, [n_chunks, n_chunks].  The table lives on the device and is NOT read by the validation, which checks
+ * n_chunks in ceil(T / 64) .. T and what the uniform calls check: its contents are the caller's contract -- rows
+ * start .. start + count - 1 inside 0 .. T - 1 and disjoint between chunks (rows that no chunk covers are not written).
+ * mhla_causal_varlen_normgate_fusable: mhla_causal_normgate_fusable by n_chunks. */
+size_t mhla_causal_varlen_fwd_ws_bytes(int B, int T, int H, int K, int V, int chunk, int n_chunks, int dtype, unsigned flags);
+size_t mhla_causal_varlen_bwd_ws_bytes(int B, int T, int H, int K, int V, int chunk, int n_chunks, int dtype, unsigned flags);
+int mhla_causal_varlen_normgate_fusable(int T, int K, int V, int chunk, int n_chunks, int dtype, unsigned flags);
+int mhla_causal_varlen_fwd(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out, void* ws,
+                           size_t ws_bytes, int B, int T, int H, int K, int V, int chunk, int n_chunks, const int* chunk_tab_dev,
+                           float scale, int dtype, unsigned flags, void* stream);
+int mhla_causal_varlen_normgate_fwd(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out, mhla_view gate,
+                                    const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int T, int H,
+                                    int K, int V, int chunk, int n_chunks, const int* chunk_tab_dev, float scale, int dtype,
+                                    unsigned flags, void* stream);
+int mhla_causal_varlen_bwd(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_view dout, mhla_mview dq,
+                           mhla_mview dk, mhla_mview dv, float* dmix, int lddmix, void* ws, size_t ws_bytes, const void* fwd_ws,
+                           int B, int T, int H, int K, int V, int chunk, int n_chunks, const int* chunk_tab_dev, float scale, int dtype,
+                           unsigned flags, void* stream);
+
 /* Decoding (generation): the state of a sequence and the single-token step.  Row t of the forward above depends on the
  * tokens <= t only, so a step reproduces it from, per (b, h), in fp32 whatever the tensor dtype:
  *   S   [B][H][cap_chunks][K][V]  K_j^T V_j of every finished chunk j (mix[i][j] differs per row i: all are kept --

@@ -71,6 +71,17 @@ SIGNATURES = {
                                          c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_uint, c_void_p]),
     "mhla_causal_bwd": (c_int, [View, View, View, c_void_p, c_int, View, View, View, View, c_void_p, c_int, c_void_p,
                                 c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_uint, c_void_p]),
+    "mhla_causal_varlen_fwd_ws_bytes": (c_size_t, [c_int] * 8 + [c_uint]),
+    "mhla_causal_varlen_bwd_ws_bytes": (c_size_t, [c_int] * 8 + [c_uint]),
+    "mhla_causal_varlen_normgate_fusable": (c_int, [c_int] * 6 + [c_uint]),
+    "mhla_causal_varlen_fwd": (c_int, [View, View, View, c_void_p, c_int, View, c_void_p, c_size_t, c_int, c_int, c_int,
+                                       c_int, c_int, c_int, c_int, c_void_p, c_float, c_int, c_uint, c_void_p]),
+    "mhla_causal_varlen_normgate_fwd": (c_int, [View, View, View, c_void_p, c_int, View, View, c_void_p, c_float, View, c_void_p,
+                                                c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_float, c_int,
+                                                c_uint, c_void_p]),
+    "mhla_causal_varlen_bwd": (c_int, [View, View, View, c_void_p, c_int, View, View, View, View, c_void_p, c_int, c_void_p,
+                                       c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_float, c_int,
+                                       c_uint, c_void_p]),
     "mhla_causal_step_ws_bytes": (c_size_t, [c_int] * 5),
     "mhla_causal_state_init": (c_int, [View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                        c_int, c_int, c_int, c_int, c_void_p]),

@@ -12,6 +12,7 @@
 // same kernels serve fp32, bf16 and fp16 tensors (converted while staging tiles into LDS).
 #pragma once
 #include "common.hpp"
+#include <type_traits>
 
 namespace mhla {
 
@@ -105,6 +106,15 @@ struct StateArgs {
     const float *pro_rk, *pro_wk, *pro_rq, *pro_wq;
     long pro_n;
 };
+// MODE 2 over packed sequences: block `blk` covers the rows tab[blk] = {first row, rows <= S} instead of rows blk S .. of the T
+// tokens.  The entry is workgroup-uniform and read through the constant address space: a scalar load.  These three belong to the
+// causal operator (causal.hpp names the type cs_tab_t; capi_causal.hip is the only caller) and live here only because k_bm_state,
+// whose MODE 2 reads the table, does; StateArgs and the block-mix modes know nothing of them.
+typedef int tab2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ tab2_t ld_tab(const tab2_t* tab, int i) { return *(const __attribute__((address_space(4))) tab2_t*)(tab + i); }
+struct StateArgsVar : StateArgs {
+    const tab2_t* tab;
+};
 
 template <int DT>
 __host__ __device__ constexpr int state_smem_floats() {
@@ -130,8 +140,8 @@ __device__ __forceinline__ void xty_accum(f32x4 (&acc)[NT], const float* __restr
     }
 }
 
-template <typename T, int DT, int MODE>
-__global__ __launch_bounds__(NTHREADS) void k_bm_state(const StateArgs a) {
+template <typename T, int DT, int MODE, typename A = StateArgs>
+__global__ __launch_bounds__(NTHREADS) void k_bm_state(const A a) {
     constexpr int DP = DT * 16, CH = bm_chunk(DT), LD = ld_kmajor(DP), NT = (DT * DT + 3) / 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Xs = smem;
@@ -143,7 +153,7 @@ __global__ __launch_bounds__(NTHREADS) void k_bm_state(const StateArgs a) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int blk = blockIdx.x, bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H;
     const int D = a.D;
-    const long p0 = (long)blk * a.S;
+    long p0 = (long)blk * a.S;
     const T* xb = (const T*)a.x.ptr + b * a.x.sb + h * a.x.sh;
     const T* yb = (const T*)a.y.ptr + b * a.y.sb + h * a.y.sh;
     // MODE 2: strips and token tail
@@ -152,7 +162,13 @@ __global__ __launch_bounds__(NTHREADS) void k_bm_state(const StateArgs a) {
         const int nsy = (a.DY + DP - 1) / DP;
         x0 = (blockIdx.z / nsy) * DP;
         y0 = (blockIdx.z % nsy) * DP;
-        S = (int)max(0L, min((long)a.S, a.T - p0));
+        if constexpr (std::is_same_v<A, StateArgsVar>) {   // packed sequences: the block's rows from the table
+            const tab2_t e = ld_tab(a.tab, blk);
+            p0 = e.x;
+            S = e.y;
+        } else {
+            S = (int)max(0L, min((long)a.S, a.T - p0));
+        }
     }
 
     f32x4 acc[NT];

@@ -16,7 +16,25 @@ constexpr int CS_LDX = 66;           // x-major tiles [64][66]
 constexpr int CS_LDK = 80;           // k-major tiles [64][80]
 constexpr int CS_LDO = 68;           // staging
 
+// First token row and valid rows of chunk ci.  Uniform call: the chunks are cut at multiples of 64 of the T tokens.  Packed
+// sequences (the *Var args below): row `ci` of a device table {start, count} -- every sequence of the pack cut into its own
+// chunks, numbered along the pack.  The entry is workgroup-uniform and read through the constant address space: a scalar
+// load, counted on lgkmcnt, so the vector-load rings of the 16-bit token kernels (vmcnt) keep their counts.
+struct CsRows { long p0; int rv; };
+using cs_tab_t = tab2_t;   // (blockmix.hpp: ld_tab)
+template <typename A>
+__device__ __forceinline__ CsRows cs_rows(const A& a, int ci) {
+    if constexpr (A::VARLEN) {
+        const cs_tab_t e = ld_tab(a.tab, ci);
+        return CsRows{(long)e.x, e.y};
+    } else {
+        const long p0 = (long)ci * 64;
+        return CsRows{p0, (int)min((long)64, a.T - p0)};
+    }
+}
+
 struct CsOutArgs {
+    static constexpr bool VARLEN = false;
     View q, k, v;
     MView o;
     const float* mix;
@@ -32,10 +50,14 @@ struct CsOutArgs {
     const float* nw;    // [V] or null
     float neps;
 };
+struct CsOutArgsVar : CsOutArgs {   // packed sequences: n chunks of 1 .. 64 rows each, anywhere in the T rows
+    static constexpr bool VARLEN = true;
+    const cs_tab_t* tab;   // [n] {first row, rows}
+};
 constexpr int CS_OUT_SMEM_FLOATS = 3 * CS * CS_LDX + CS * CS_LDK + CS * CS_LDO;
 
-template <typename T>
-__global__ __launch_bounds__(NTHREADS) void k_cs_out(const CsOutArgs a) {
+template <typename T, typename A = CsOutArgs>
+__global__ __launch_bounds__(NTHREADS) void k_cs_out(const A a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Qs = smem;                  // [64 c][66]
     float* Ks = Qs + CS * CS_LDX;      // [64 c'][66]
@@ -45,8 +67,13 @@ __global__ __launch_bounds__(NTHREADS) void k_cs_out(const CsOutArgs a) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
     const int ci = blockIdx.x, bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H;
     const int v0 = blockIdx.z * 64, vv = min(64, a.V - v0);
-    const long p0 = (long)ci * CS;
-    const int rv = (int)min((long)CS, a.T - p0);
+    long p0 = (long)ci * CS;
+    int rv = (int)min((long)CS, a.T - p0);
+    if constexpr (A::VARLEN) {   // (written out: through cs_rows the uniform instantiation was scheduled differently)
+        const cs_tab_t e = ld_tab(a.tab, ci);
+        p0 = e.x;
+        rv = e.y;
+    }
     const T* qb = (const T*)a.q.ptr + b * a.q.sb + h * a.q.sh;
     const T* kb = (const T*)a.k.ptr + b * a.k.sb + h * a.k.sh;
     const T* vb = (const T*)a.v.ptr + b * a.v.sb + h * a.v.sh;
@@ -92,6 +119,7 @@ __global__ __launch_bounds__(NTHREADS) void k_cs_out(const CsOutArgs a) {
 }
 
 struct CsTokArgs {
+    static constexpr bool VARLEN = false;
     View q, k, v, dout;
     MView dq, dk, dv;
     const float* mix;
@@ -104,10 +132,14 @@ struct CsTokArgs {
     float scale;
     int cpw = 1;       // k_csf_bwd_tok4: consecutive chunks per workgroup (its grid is ceil(n / cpw) x bh)
 };
+struct CsTokArgsVar : CsTokArgs {   // packed sequences (see CsOutArgsVar)
+    static constexpr bool VARLEN = true;
+    const cs_tab_t* tab;
+};
 constexpr int CS_TOK_SMEM_FLOATS = 6 * CS * CS_LDX + CS * CS_LDO + 8;
 
-template <typename T>
-__global__ __launch_bounds__(NTHREADS) void k_cs_bwd_tok(const CsTokArgs a) {
+template <typename T, typename A = CsTokArgs>
+__global__ __launch_bounds__(NTHREADS) void k_cs_bwd_tok(const A a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                  // m_ii scale tril(Q K^T)   [c][c']
     float* dAs = As + CS * CS_LDX;     // m_ii tril(dO V^T)        [c][c']
@@ -119,8 +151,9 @@ __global__ __launch_bounds__(NTHREADS) void k_cs_bwd_tok(const CsTokArgs a) {
     float* red = Os + CS * CS_LDO;     // [8]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
     const int ci = blockIdx.x, bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H;
-    const long p0 = (long)ci * CS;
-    const int rv = (int)min((long)CS, a.T - p0);
+    const CsRows cr = cs_rows(a, ci);
+    const long p0 = cr.p0;
+    const int rv = cr.rv;
     const int K = a.K, V = a.V;
     auto base = [&](const View& w) { return (const T*)w.ptr + b * w.sb + h * w.sh; };
     auto mbase = [&](const MView& w) { return (T*)w.ptr + b * w.sb + h * w.sh; };

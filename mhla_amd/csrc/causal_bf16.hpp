@@ -212,8 +212,8 @@ __host__ __device__ constexpr int csf_tok4_smem() {
 // register slots per summary set (and plane) keeps NK rounds of P / dS tiles in flight, the same slots carry the Q / K tiles
 // before step 1 and the Q tiles again for step 3.  DBUF (K > 128, or HL: one workgroup per CU whatever the LDS use): a second
 // set of P / dS buffers and a dV staging tile of its own, so that a round is commit -> ONE barrier -> refill -> multiply.
-template <int NK, int HL>
-__global__ __launch_bounds__(NT4, (NK <= 2 && !HL) ? 4 : 2) void k_csf_bwd_tok4(const CsTokArgs a) {
+template <int NK, int HL, typename A = CsTokArgs>
+__global__ __launch_bounds__(NT4, (NK <= 2 && !HL) ? 4 : 2) void k_csf_bwd_tok4(const A a) {
     constexpr int P = HL ? 2 : 1, MP = cs_mplanes(HL), LD = csf_tok4_ld<NK, HL>(), CT = tile_elems<LD>();   // P: LDS planes, MP: planes in memory
     constexpr bool H16 = HL == 2;
     constexpr bool DBUF = NK > 2 || HL;
@@ -253,8 +253,9 @@ __global__ __launch_bounds__(NT4, (NK <= 2 && !HL) ? 4 : 2) void k_csf_bwd_tok4(
         }
     };
     {   // the first chunk's Q / K tiles and first dO / V slices; every later chunk's travel during the chunk before it
-        const long p0 = (long)c_first * CS;
-        const int rv = (int)min((long)CS, a.T - p0);
+        const CsRows cr = cs_rows(a, c_first);
+        const long p0 = cr.p0;
+        const int rv = cr.rv;
 #pragma unroll
         for (int kk = 0; kk < NK; ++kk) {
             cs8_issue_tok(rP[kk][0], qb + kk * 64, a.q.sn, p0, rv, tid);
@@ -264,12 +265,14 @@ __global__ __launch_bounds__(NT4, (NK <= 2 && !HL) ? 4 : 2) void k_csf_bwd_tok4(
         cs8_issue_tok(nV, vb, a.v.sn, p0, rv, tid);
     }
     for (int ci = c_first; ci <= c_last; ++ci) {
-    const long p0 = (long)ci * CS;
-    const int rv = (int)min((long)CS, a.T - p0);
+    const CsRows cr = cs_rows(a, ci);
+    const long p0 = cr.p0;
+    const int rv = cr.rv;
     // the chunk whose first tiles are requested while this one is worked on (the workgroup's last chunk: itself again, dropped --
     // no load behind a branch)
-    const long p0n = (long)min(ci + 1, c_last) * CS;
-    const int rvn = (int)min((long)CS, a.T - p0n);
+    const CsRows crn = cs_rows(a, min(ci + 1, c_last));
+    const long p0n = crn.p0;
+    const int rvn = crn.rv;
     const u16* Pb = reinterpret_cast<const u16*>(a.P) + bh * L.bhs + ci * L.cst;
     const u16* dSb = reinterpret_cast<const u16*>(a.dS) + bh * L.bhs + ci * L.cst;
     const float mii = a.mix[(long)ci * a.ldmix + ci];
@@ -454,11 +457,11 @@ __host__ __device__ constexpr int csf_out4_smem() {
 
 // (HL with four V slices per workgroup -- the fused epilogue at V = 256 -- holds 32 ring and 32 accumulator registers beside the
 //  operands: one workgroup per CU on 256 VGPRs instead of 20 spilled registers at 128)
-template <int NV, bool EPI, int HL, int NH = 1>
+template <int NV, bool EPI, int HL, int NH = 1, typename A = CsOutArgs>
 #ifndef CSF_OUT4_NV4_WAVES
 #define CSF_OUT4_NV4_WAVES 4   // four slices with hi + lo pairs: two workgroups per CU at 128 VGPRs and 4 spilled registers (98 us at C5)
 #endif                         // beat one workgroup at 134 (107 us) and two slices per workgroup, which read Q and K twice (108-112 us)
-__global__ __launch_bounds__(NT4, NH > 1 ? 2 : (HL && NV == 4) ? (EPI ? 2 : CSF_OUT4_NV4_WAVES) : 4) void k_csf_out4(const CsOutArgs a) {   // (NH > 1: 138 KB of LDS, one workgroup per CU anyway)
+__global__ __launch_bounds__(NT4, NH > 1 ? 2 : (HL && NV == 4) ? (EPI ? 2 : CSF_OUT4_NV4_WAVES) : 4) void k_csf_out4(const A a) {   // (NH > 1: 138 KB of LDS, one workgroup per CU anyway)
     constexpr int P = HL ? 2 : 1, MP = cs_mplanes(HL), LD = CSF_OUT4_LD, CT = tile_elems<LD>();   // P: LDS planes, MP: planes in memory
     constexpr bool H16 = HL == 2;
     static_assert(NH == 1 || EPI, "only the fused-epilogue variant walks several halves of the head");
@@ -483,7 +486,7 @@ __global__ __launch_bounds__(NT4, NH > 1 ? 2 : (HL && NV == 4) ? (EPI ? 2 : CSF_
     if (hv > 0) __syncthreads();   // the previous half's V tiles and score tile are dead
     const int tr = tid >> 3, tc = (tid & 7) * 8;
     // the thread's token row in chunk c (rows past the sequence: the chunk's first row, zeroed on commit)
-    auto row_of = [&](int c) { const long p = (long)c * CS; return p + (tr < (int)min((long)CS, a.T - p) ? tr : 0); };
+    auto row_of = [&](int c) { const CsRows w = cs_rows(a, c); return w.p0 + (tr < w.rv ? tr : 0); };
     // the score tile's buffer: the P buffer that the last round (nks NV - 1) does not read
     u16* Ao = Ps + ((((nks * NV - 1) & 1) ^ 1)) * P * CT;
 
@@ -506,10 +509,11 @@ __global__ __launch_bounds__(NT4, NH > 1 ? 2 : (HL && NV == 4) ? (EPI ? 2 : CSF_
         __builtin_amdgcn_sched_barrier(0);
     }
     for (int ci = c0; ci < c1; ++ci) {
-    const long p0 = (long)ci * CS;
-    const int rv = (int)min((long)CS, a.T - p0);
+    const CsRows cr = cs_rows(a, ci);
+    const long p0 = cr.p0;
+    const int rv = cr.rv;
     const u16* Pb = reinterpret_cast<const u16*>(a.P) + bh * L.bhs + ci * L.cst;
-    const long trow = row_of(ci);
+    const long trow = p0 + (tr < rv ? tr : 0);
     const int cn = ci + 1 < c1 ? ci + 1 : ci;   // next chunk (behind the last one: this chunk again -- hot lines, never used)
     const long trown = row_of(cn);
     const u16* Pbn = reinterpret_cast<const u16*>(a.P) + bh * L.bhs + cn * L.cst;
@@ -681,11 +685,16 @@ __global__ __launch_bounds__(NT4, NH > 1 ? 2 : (HL && NV == 4) ? (EPI ? 2 : CSF_
 // staging strip, eight full 128-byte rows per store instruction.
 // -------------------------------------------------------------------------------------------------
 struct CsfStateArgs {
+    static constexpr bool VARLEN = false;
     View x, y;
     u16* out;
     int H, n, K, V;
     long T;
     float mul;
+};
+struct CsfStateArgsVar : CsfStateArgs {   // packed sequences (see CsOutArgsVar)
+    static constexpr bool VARLEN = true;
+    const cs_tab_t* tab;
 };
 constexpr int ST2_KW = 128, ST2_VW = 256, ST2_LDX = ST2_KW + 8, ST2_LDY = ST2_VW + 8;
 #ifndef ST2_T
@@ -698,8 +707,8 @@ constexpr int ST2_KW = 128, ST2_VW = 256, ST2_LDX = ST2_KW + 8, ST2_LDY = ST2_VW
 template <int HL> __host__ __device__ constexpr int csf_state2_smem() { return (CS * ST2_LDX + CS * ST2_LDY + (ST2_T / 64) * cs_mplanes(HL) * 16 * CLD) * 2; }
 constexpr int ST2_CPW = ST2_CPW_;
 
-template <int HL>
-__global__ __launch_bounds__(ST2_T, 2) void k_csf_state2(const CsfStateArgs a) {
+template <int HL, typename A = CsfStateArgs>
+__global__ __launch_bounds__(ST2_T, 2) void k_csf_state2(const A a) {
     constexpr int P = cs_mplanes(HL);   // planes written
     constexpr int XP = 4 * 256 / ST2_T, YP = 8 * 256 / ST2_T, XR = 64 / XP, YR = 64 / YP, RRS = 8 / (ST2_T / 64);   // staging passes, rows per pass, strips per wave
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -719,8 +728,9 @@ __global__ __launch_bounds__(ST2_T, 2) void k_csf_state2(const CsfStateArgs a) {
     const bool xok = xc < kw, yok = yc < vw;
     uint4 xr[XP], yr[YP];
     auto issue = [&](int ci, bool filler) {   // (no load behind a branch: rows past the sequence's end read the chunk's first row;
-        const long p0 = (long)ci * CS;        //  the filler behind the last chunk reads that one row with every pass)
-        const int rv = filler ? 0 : (int)min((long)CS, a.T - p0);
+        const CsRows cr = cs_rows(a, ci);     //  the filler behind the last chunk reads that one row with every pass)
+        const long p0 = cr.p0;
+        const int rv = filler ? 0 : cr.rv;
 #pragma unroll
         for (int p = 0; p < XP; ++p) {
             const int row = (tid >> 4) + XR * p;
@@ -734,7 +744,7 @@ __global__ __launch_bounds__(ST2_T, 2) void k_csf_state2(const CsfStateArgs a) {
     };
     issue(c0, false);
     for (int ci = c0; ci < c1; ++ci) {
-        const int rv = (int)min((long)CS, a.T - (long)ci * CS);
+        const int rv = cs_rows(a, ci).rv;
         u16* ob = a.out + bh * L.bhs + ci * L.cst;
         if (ci > c0) __syncthreads();   // the previous chunk's tiles are dead
 #pragma unroll

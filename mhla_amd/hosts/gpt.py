@@ -12,6 +12,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..modules import MHLA, DecodeCache
+from ..ops import causal_varlen_plan
 
 
 class RMSNorm(nn.Module):
@@ -38,16 +39,19 @@ class GatedMLP(nn.Module):
 
 
 class Block(nn.Module):
-    def __init__(self, dim, heads, expand_k, expand_v, layer_idx, max_chunks=32, exact_decoding=False):
+    def __init__(self, dim, heads, expand_k, expand_v, layer_idx, max_chunks=32, exact_decoding=False, isolate_sequences=False):
         super().__init__()
         self.attn_norm = RMSNorm(dim)
         self.attn = MHLA(mode="chunk", hidden_size=dim, expand_k=expand_k, expand_v=expand_v, num_heads=heads,
-                         feature_map="relu", layer_idx=layer_idx, max_chunks=max_chunks, exact_decoding=exact_decoding)
+                         feature_map="relu", layer_idx=layer_idx, max_chunks=max_chunks, exact_decoding=exact_decoding,
+                         isolate_sequences=isolate_sequences)
         self.mlp_norm = RMSNorm(dim)
         self.mlp = GatedMLP(dim)
 
-    def forward(self, x, cache=None, attention_mask=None, token_counts=None):
-        if cache is None:
+    def forward(self, x, cache=None, attention_mask=None, token_counts=None, cu_seqlens=None, varlen_plan=None):
+        if cu_seqlens is not None or varlen_plan is not None:   # packed sequences (training): no cache
+            x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask, cu_seqlens=cu_seqlens, varlen_plan=varlen_plan)[0]
+        elif cache is None:
             x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask)[0]
         elif token_counts is None:
             x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask, past_key_values=cache, use_cache=True)[0]
@@ -59,19 +63,20 @@ class Block(nn.Module):
 
 class GPT_MHLA(nn.Module):
     def __init__(self, vocab_size=32000, hidden_size=1024, num_layers=24, num_heads=4, expand_k=0.5, expand_v=1.0,
-                 max_seq_len=2048, exact_decoding=False):
+                 max_seq_len=2048, exact_decoding=False, isolate_sequences=False):
         super().__init__()
         self.exact_decoding = bool(exact_decoding)
+        self.isolate_sequences = bool(isolate_sequences)
         self.embeddings = nn.Embedding(vocab_size, hidden_size)
         max_chunks = max(32, (max_seq_len + 63) // 64)     # 32 = the reference layer's matrix; 128 for seq_len 8192 (config 5)
-        self.layers = nn.ModuleList([Block(hidden_size, num_heads, expand_k, expand_v, i, max_chunks, exact_decoding) for i in range(num_layers)])
+        self.layers = nn.ModuleList([Block(hidden_size, num_heads, expand_k, expand_v, i, max_chunks, exact_decoding, isolate_sequences) for i in range(num_layers)])
         self.norm = RMSNorm(hidden_size)
         self.lm_head = nn.Linear(hidden_size, vocab_size, bias=False)
         for m in self.modules():
             if isinstance(m, (nn.Linear, nn.Embedding)):
                 nn.init.normal_(m.weight, std=0.02)
 
-    def forward(self, input_ids, labels=None, cache=None, attention_mask=None, token_counts=None):
+    def forward(self, input_ids, labels=None, cache=None, attention_mask=None, token_counts=None, cu_seqlens=None):
         """`cache` (a `DecodeCache`, model built with `exact_decoding=True`): `input_ids` are the tokens AFTER the ones the cache
         has seen -- the whole prompt on an empty cache, then one token per call, or several (the next turn, a piece of a long
         prompt, a draft to verify): on a non-empty cache those take the layer's `mhla_causal_extend` path, one launch chain per
@@ -82,13 +87,26 @@ class GPT_MHLA(nn.Module):
         `token_counts` (B ints in 0 .. T, a list or a tensor; with a cache whose decode state is ragged, i.e. after a masked
         prefill): sequence b takes only the LAST `token_counts[b]` tokens of `input_ids[b]` (right-aligned, as the prefill's
         padding) -- one slot decoding a token beside another taking a slice of a long prompt, a slot that sits the call out (0) -- in
-        one launch chain per layer; handed to every layer.  The layers' outputs at padding rows are zeros, the logits there unspecified."""
+        one launch chain per layer; handed to every layer.  The layers' outputs at padding rows are zeros, the logits there unspecified.
+        `cu_seqlens` (no cache; `input_ids` [1, T]): packed sequences, handed to every layer.  A model built with
+        `isolate_sequences=True` runs every sequence of the pack (or of a padded batch with `attention_mask`) alone; the
+        operator's chunk table (`causal_varlen_plan`, one host read of the lengths) is built here once for all layers."""
         if cache is not None and not self.exact_decoding:
             raise ValueError("GPT_MHLA.forward(cache=...) needs a model built with exact_decoding=True")
+        if cu_seqlens is not None and cache is not None:
+            raise NotImplementedError("GPT_MHLA.forward: cu_seqlens with a cache")
+        plan = None
+        if self.isolate_sequences and cache is None and (cu_seqlens is not None or attention_mask is not None):
+            lens = cu_seqlens if cu_seqlens is not None else F.pad(
+                attention_mask[:, -input_ids.shape[1]:].sum(-1, dtype=torch.int32).cumsum(0, dtype=torch.int32), (1, 0))
+            plan = causal_varlen_plan(lens, input_ids.device)
         if token_counts is not None and isinstance(token_counts, torch.Tensor):
             token_counts = token_counts.tolist()   # (read once for all layers)
         x = self.embeddings(input_ids)
         for blk in self.layers:
+            if cu_seqlens is not None or plan is not None:
+                x = blk(x, cache, attention_mask, cu_seqlens=cu_seqlens, varlen_plan=plan)
+                continue
             x = blk(x, cache, attention_mask) if token_counts is None else blk(x, cache, attention_mask, token_counts)
         logits = self.lm_head(self.norm(x))
         if labels is None:

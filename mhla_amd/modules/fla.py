@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops import (CausalState, _mix2d, _runs, mhla_causal_prefill, featmap_rotary, mhla_causal, mhla_causal_extend, mhla_causal_normgate, mhla_causal_state, mhla_causal_step,
+from ..ops import (CausalState, _mix2d, _runs, causal_varlen_plan, mhla_causal_prefill, featmap_rotary, mhla_causal, mhla_causal_extend, mhla_causal_normgate, mhla_causal_state, mhla_causal_step,
                    mhla_causal_step_dev, naive_recurrent_mhla, rmsnorm_gate)
 from ..weights import causal_mixing_init
 
@@ -212,7 +212,7 @@ class MHLA(nn.Module):
                  use_output_gate: bool = True, gate_fn: str = "swish", elementwise_affine: Optional[bool] = True,
                  norm_eps: float = 1e-5, gate_logit_normalizer: int = 16, gate_low_rank_dim: int = 16,
                  clamp_min: Optional[float] = None, fuse_norm: bool = True, layer_idx: int = None, max_chunks: int = 32,
-                 summaries: str = "tf32", exact_decoding: bool = False):
+                 summaries: str = "tf32", exact_decoding: bool = False, isolate_sequences: bool = False):
         """`max_chunks` (not in the reference, default = its hard-coded 32): side of the mixing matrix, i.e. the longest
         sequence is 64 * max_chunks tokens -- 128 for the 8192-token configuration of BASELINE.json configs[4], which the
         reference layer itself cannot run (layers/mhla.py:196-200); the operator accepts any [n, n] matrix (naive.py:55).
@@ -239,7 +239,14 @@ class MHLA(nn.Module):
         the cache's token count grows by what the longest sequence grew.  `use_short_conv` raises NotImplementedError.
         With a `DecodeCache(device_positions=True)` the one-token calls after the prefill are device-positioned steps (see
         `DecodeCache`; capturable in a graph); they do not reassign `mixing_matrix.data` -- generation does not change the weights
-        -- and calls of several tokens on such a cache, `use_short_conv` and `head_k_dim % 8 != 0` raise NotImplementedError."""
+        -- and calls of several tokens on such a cache, `use_short_conv` and `head_k_dim % 8 != 0` raise NotImplementedError.
+        `isolate_sequences` (not in the reference, default off: nothing changes): a call with `cu_seqlens`, given or made by
+        unpadding an `attention_mask`, runs the operator over every sequence of the pack alone (`mhla_causal(cu_seqlens=)`:
+        each sequence's chunks cut from its own start, rows 0.. of the mixing matrix, nothing of its neighbours -- what
+        `exact_decoding` evaluates) instead of over the pack as one sequence; calls of <= 64 tokens then use the chunk operator
+        too and return no recurrent state.  `varlen_plan=` (through `**kwargs`): a `CausalVarlenPlan` built once for all layers.
+        With `use_cache` a call that carries an `attention_mask` or `cu_seqlens` raises NotImplementedError -- the `exact_decoding`
+        prefill of a padded batch included."""
         super().__init__()
         self.mode = mode
         self.hidden_size = hidden_size
@@ -258,6 +265,7 @@ class MHLA(nn.Module):
             raise ValueError(f"summaries={summaries!r}: 'tf32', 'split' or 'bf16'")
         self.summaries = summaries
         self.exact_decoding = bool(exact_decoding)
+        self.isolate_sequences = bool(isolate_sequences)
         self.use_output_gate = use_output_gate
         assert mode in ["chunk", "fused_recurrent", "fused_chunk"], f"Not supported mode `{mode}`."
         assert self.key_dim % num_heads == 0, f"key dim must be divisible by num_heads of {num_heads}"
@@ -315,6 +323,10 @@ class MHLA(nn.Module):
             assert len(attention_mask.shape) == 2, (
                 "Expected attention_mask as a 0-1 matrix with shape [batch_size, seq_len] for padding purposes "
                 "(0 indicating padding). Arbitrary attention masks of shape [batch_size, seq_len, seq_len] are not allowed.")
+        if self.isolate_sequences and use_cache and (attention_mask is not None or kwargs.get("cu_seqlens", None) is not None):
+            # (before the exact_decoding prefill drops the mask: that path is refused too, not taken silently)
+            raise NotImplementedError("MHLA(isolate_sequences=True): an attention_mask or cu_seqlens with use_cache -- a decode state per "
+                                      "packed sequence, and the exact_decoding prefill of a padded batch, are not implemented for it")
         batch_size, q_len, _ = hidden_states.shape
         last_state = None
         if past_key_values is not None and self.layer_idx is not None and len(past_key_values) > self.layer_idx:
@@ -358,6 +370,11 @@ class MHLA(nn.Module):
             cu_seqlens = F.pad(m.sum(-1, dtype=torch.int32).cumsum(0, dtype=torch.int32), (1, 0))
             hidden_states = hidden_states.reshape(batch_size * q_len, -1).index_select(0, indices).unsqueeze(0)
         B, T, _ = hidden_states.shape
+        plan = None               # isolate_sequences: the pack's chunk table, handed to the operator as cu_seqlens=
+        if self.isolate_sequences and cu_seqlens is not None:
+            plan = kwargs.get("varlen_plan", None)
+            if plan is None:
+                plan = causal_varlen_plan(cu_seqlens, hidden_states.device)
         conv_states = None
         if self.use_short_conv:                                              # :258-279
             cq = ck = cv = None
@@ -475,7 +492,11 @@ class MHLA(nn.Module):
             # output kernel where the shape allows, otherwise as the separate HIP kernel (mhla_causal_normgate decides)
             g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
             gn = self.g_norm_swish_gate
-            o = mhla_causal_normgate(q, k, v, self.mixing_matrix, g, gn.weight, gn.eps, summaries=self.summaries).reshape(B, T, self.value_dim)
+            o = mhla_causal_normgate(q, k, v, self.mixing_matrix, g, gn.weight, gn.eps, summaries=self.summaries,
+                                     cu_seqlens=plan).reshape(B, T, self.value_dim)
+            recurrent_state = None
+        elif plan is not None:                                               # (isolate_sequences: the chunk operator whatever q_len)
+            o = mhla_causal(q, k, v, self.mixing_matrix, summaries=self.summaries, cu_seqlens=plan)
             recurrent_state = None
         elif q_len <= 64:                                                    # :247, :318-327: the token-recurrent form
             if T > 64 and not getattr(self, "_warned_recurrent_packed", False):

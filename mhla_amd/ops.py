@@ -193,6 +193,13 @@ def _cs_plan(B, T, H, K, V, chunk, dt, flags):
     return (lib.mhla_causal_fwd_ws_bytes(B, T, H, K, V, chunk, dt, flags), lib.mhla_causal_bwd_ws_bytes(B, T, H, K, V, chunk, dt, flags))
 
 
+@functools.lru_cache(maxsize=512)
+def _cs_varlen_plan(B, T, H, K, V, chunk, n_chunks, dt, flags):
+    lib = _lib.load()
+    return (lib.mhla_causal_varlen_fwd_ws_bytes(B, T, H, K, V, chunk, n_chunks, dt, flags),
+            lib.mhla_causal_varlen_bwd_ws_bytes(B, T, H, K, V, chunk, n_chunks, dt, flags))
+
+
 # ------------------------------------------------------------------------------------------
 # block-mixing MHLA (DiT / ViT / Wan)
 # ------------------------------------------------------------------------------------------
@@ -926,9 +933,10 @@ def _causal_check(what, q, k, v, mix, chunk_size, gate=None):
     return n
 
 
-def _causal_bwd(q, k, v, mixf, dout, fwd_ws, chunk_size, scale, flags):
+def _causal_bwd(q, k, v, mixf, dout, fwd_ws, chunk_size, scale, flags, plan=None):
     """mhla_causal_bwd on a node's saved tensors (`fwd_ws`: the forward's chunk summaries, None to recompute them):
-    (dq, dk, dv, dmix), dmix fp32 in the shape of mixf."""
+    (dq, dk, dv, dmix), dmix fp32 in the shape of mixf.  `plan`: packed sequences -- mhla_causal_varlen_bwd over the plan's chunk
+    table, mixf the plan's effective matrix [n, n]."""
     lib = _lib.load()
     B, T, H, K = q.shape
     V = v.shape[-1]
@@ -936,9 +944,17 @@ def _causal_bwd(q, k, v, mixf, dout, fwd_ws, chunk_size, scale, flags):
     dk = _alloc_like_tokens(B, T, H, K, q)
     dv = _alloc_like_tokens(B, T, H, V, q)
     # the library writes every entry of the leading [n, n] block (zeros above the diagonal)
-    n_chunks = (T + chunk_size - 1) // chunk_size
+    n_chunks = (T + chunk_size - 1) // chunk_size if plan is None else plan.n_chunks
     dmix = (torch.empty if tuple(mixf.shape) == (n_chunks, n_chunks) else torch.zeros)(mixf.shape, dtype=torch.float32, device=q.device)
     dt = _dtype_code(q)
+    if plan is not None:
+        ws = _ws(_cs_varlen_plan(B, T, H, K, V, chunk_size, n_chunks, dt, flags)[1], q.device)
+        rc = lib.mhla_causal_varlen_bwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(dout),
+                                        _view(dq), _view(dk), _view(dv), dmix.data_ptr(), dmix.shape[1],
+                                        ws.data_ptr(), ws.numel() * 4, _ptr(fwd_ws), B, T, H, K, V, chunk_size, n_chunks,
+                                        plan.table.data_ptr(), scale, dt, flags, _stream())
+        _lib.check(rc, "mhla_causal_varlen_bwd")
+        return dq, dk, dv, dmix
     ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, dt, flags)[1], q.device)
     rc = lib.mhla_causal_bwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(dout),
                              _view(dq), _view(dk), _view(dv), dmix.data_ptr(), dmix.shape[1],
@@ -981,6 +997,129 @@ class _Causal(torch.autograd.Function):
         return dq, dk, dv, dmix.reshape(mix_shape).to(mix_dtype), None, None, None, None
 
 
+class CausalVarlenPlan:
+    """Packed sequences for the causal operator: every sequence of `cu` (cumulative lengths, as fla's `cu_seqlens`) cut into
+    its own chunks -- a ragged last chunk per sequence, none for an empty one -- numbered c = 0 .. n_chunks - 1 along the pack.
+    Built once per batch (`causal_varlen_plan`) and shared by every layer.
+
+    cu        host tuple of the cumulative lengths
+    n_chunks  chunks of the pack; max_chunks: of its longest sequence (rows of the mixing matrix it reads)
+    table     device int32 [n_chunks, 2]: first token row and rows (1 .. chunk_size) of every chunk -- what the kernels read
+    loc, seq  device int64 [n_chunks]: the chunk's index within its sequence, and its sequence"""
+
+    def __init__(self, cu, device, chunk_size: int = 64):
+        self.cu = tuple(cu)
+        self.chunk_size = int(chunk_size)
+        starts, counts, loc, seq = [], [], [], []
+        for s in range(len(self.cu) - 1):
+            for j, p in enumerate(range(self.cu[s], self.cu[s + 1], self.chunk_size)):
+                starts.append(p)
+                counts.append(min(self.chunk_size, self.cu[s + 1] - p))
+                loc.append(j)
+                seq.append(s)
+        self.n_chunks = len(starts)
+        self.max_chunks = max(loc) + 1 if loc else 0
+        self.table = torch.tensor([starts, counts], dtype=torch.int32).t().contiguous().to(device)
+        self.loc = torch.tensor(loc, dtype=torch.int64).to(device)
+        self.seq = torch.tensor(seq, dtype=torch.int64).to(device)
+        c = torch.arange(self.n_chunks, device=self.table.device)
+        self._mask = ((self.seq[:, None] == self.seq[None, :]) & (c[None, :] <= c[:, None])).to(torch.float32)
+
+    @property
+    def lengths(self):
+        return tuple(b - a for a, b in zip(self.cu, self.cu[1:]))
+
+    def mix_eff(self, mixing_matrix: torch.Tensor) -> torch.Tensor:
+        """fp32 [n_chunks, n_chunks]: mix_eff[c, c'] = mixing_matrix[loc[c], loc[c']] where c and c' belong to the same sequence
+        and c' <= c, exact zeros elsewhere -- the operator over the pack's chunks with this matrix is the operator over every
+        sequence alone.  Differentiable: autograd's index backward sums a gradient of it into `mixing_matrix`."""
+        if mixing_matrix.device != self.table.device:
+            raise ValueError(f"mixing_matrix is on {mixing_matrix.device}, the plan on {self.table.device}")
+        m = mixing_matrix.reshape(mixing_matrix.shape[0], mixing_matrix.shape[1]).to(torch.float32)
+        return m[self.loc[:, None], self.loc[None, :]] * self._mask
+
+    def __repr__(self):
+        return f"CausalVarlenPlan(sequences={len(self.cu) - 1}, tokens={self.cu[-1]}, n_chunks={self.n_chunks}, device={self.table.device})"
+
+
+def causal_varlen_plan(cu_seqlens, device=None, chunk_size: int = 64) -> CausalVarlenPlan:
+    """The `CausalVarlenPlan` of `cu_seqlens` (a sequence of ints or a 1-D integer tensor; reading a device tensor synchronises,
+    once -- build the plan once per batch and pass it to every layer as `cu_seqlens=`).  ValueError unless cu_seqlens is 1-D,
+    starts at 0 and never decreases; empty sequences are allowed.  `device` defaults to the tensor's."""
+    if isinstance(cu_seqlens, torch.Tensor):
+        if cu_seqlens.dim() != 1 or cu_seqlens.is_floating_point() or cu_seqlens.is_complex():
+            raise ValueError(f"cu_seqlens must be a 1-D integer tensor, got shape {tuple(cu_seqlens.shape)} of {cu_seqlens.dtype}")
+        if device is None:
+            device = cu_seqlens.device
+        cu = cu_seqlens.tolist()
+    else:
+        cu = list(cu_seqlens)
+        if any(isinstance(x, (list, tuple, torch.Tensor)) or int(x) != x for x in cu):
+            raise ValueError(f"cu_seqlens must be a 1-D sequence of ints, got {cu_seqlens!r}")
+    cu = tuple(int(x) for x in cu)
+    if int(chunk_size) <= 0:
+        raise ValueError(f"chunk_size must be positive, got {chunk_size}")
+    if len(cu) < 1 or cu[0] != 0:
+        raise ValueError(f"cu_seqlens must start at 0, got {cu}")
+    if any(b < a for a, b in zip(cu, cu[1:])):
+        raise ValueError(f"cu_seqlens must be non-decreasing, got {cu}")
+    return CausalVarlenPlan(cu, device if device is not None else "cpu", chunk_size)
+
+
+def _causal_varlen_args(what, q, mixing_matrix, cu_seqlens, chunk_size) -> CausalVarlenPlan:
+    """The checks of a packed call, all before the library is loaded or anything is launched; returns the plan."""
+    if q.shape[0] != 1:
+        raise ValueError(f"{what}: cu_seqlens takes one packed row (B = 1), got B = {q.shape[0]}")
+    plan = cu_seqlens if isinstance(cu_seqlens, CausalVarlenPlan) else causal_varlen_plan(cu_seqlens, q.device, chunk_size)
+    if plan.chunk_size != int(chunk_size):
+        raise ValueError(f"{what}: the plan was built for chunk_size={plan.chunk_size}, the call has chunk_size={chunk_size}")
+    if plan.cu[-1] != q.shape[1]:
+        raise ValueError(f"{what}: cu_seqlens ends at {plan.cu[-1]}, the pack has T = {q.shape[1]} tokens")
+    if plan.table.device != q.device:
+        raise ValueError(f"{what}: the plan is on {plan.table.device}, expected {q.device}")
+    L = mixing_matrix.shape[0]
+    if plan.max_chunks > L:
+        long = [i for i, n in enumerate(plan.lengths) if n > chunk_size * L]
+        raise IndexError(f"{what}: sequences {long} of lengths {[plan.lengths[i] for i in long]} need more than the {L} rows of "
+                         f"mixing_matrix ({chunk_size * L} tokens)")
+    return plan
+
+
+class _CausalVarlen(torch.autograd.Function):
+    """_Causal over a pack: `mix` is the plan's effective matrix [n, n] (a differentiable function of the mixing matrix), the
+    gradient returned for it is the library's dmix_eff."""
+
+    @staticmethod
+    @_device_guard
+    def forward(ctx, q, k, v, mix, plan, scale, flags, keep_limit):
+        lib = _lib.load()
+        _require_gpu(q, k, v, mix, plan.table)
+        B, T, H, K = q.shape
+        V = v.shape[-1]
+        n, chunk_size = plan.n_chunks, plan.chunk_size
+        _causal_check("mhla_causal", q, k, v, mix, chunk_size)
+        q, k, v = _prep(q), _prep(k), _prep(v)
+        mixf = _mix2d(mix, n)
+        out = _alloc_like_tokens(B, T, H, V, q)
+        ws = _ws(_cs_varlen_plan(B, T, H, K, V, chunk_size, n, _dtype_code(q), flags)[0], q.device)
+        rc = lib.mhla_causal_varlen_fwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(out),
+                                        ws.data_ptr(), ws.numel() * 4, B, T, H, K, V, chunk_size, n, plan.table.data_ptr(),
+                                        float(scale), _dtype_code(q), flags, _stream())
+        _lib.check(rc, "mhla_causal_varlen_fwd")
+        keep = ws.numel() * 4 <= keep_limit and any(ctx.needs_input_grad[:4])
+        ctx.save_for_backward(q, k, v, mixf, ws if keep else None)
+        ctx.cfg = (plan, float(scale), flags)
+        return out
+
+    @staticmethod
+    @_device_guard
+    def backward(ctx, dout):
+        q, k, v, mixf, fwd_ws = ctx.saved_tensors
+        plan, scale, flags = ctx.cfg
+        dq, dk, dv, dmix = _causal_bwd(q, k, v, mixf, _prep(dout.to(q.dtype)), fwd_ws, plan.chunk_size, scale, flags, plan)
+        return dq, dk, dv, dmix, None, None, None, None
+
+
 def _causal_keep_limit(keep_state_limit: Optional[int]) -> int:
     return CAUSAL_KEEP_STATE_LIMIT_BYTES if keep_state_limit is None else int(keep_state_limit)
 
@@ -994,7 +1133,7 @@ def _causal_flags(summaries: str, force_generic: bool) -> int:
 
 def mhla_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor,
                 chunk_size: int = 64, scale: Optional[float] = None, *, summaries: str = "tf32",
-                force_generic: bool = False, keep_state_limit: Optional[int] = None) -> torch.Tensor:
+                force_generic: bool = False, keep_state_limit: Optional[int] = None, cu_seqlens=None) -> torch.Tensor:
     """Causal chunk-mixing MHLA operator (naive_chunk_simple_mhla_fixed,
     mhla_nlp/fla/ops/mhla/naive.py:10-83).  q, k: [B, T, H, K]; v: [B, T, H, V];
     mixing_matrix: [L, L] or [L, L, 1, 1, 1, 1], L >= ceil(T / chunk_size).  fp32 compute, output in
@@ -1008,7 +1147,12 @@ def mhla_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix
     force_generic: testing aid -- the generic fp32-MFMA kernels for every shape.
     keep_state_limit: largest forward workspace (bytes: the chunk summaries S, P -- 4 B T H K V / 64 bytes at the default, 8 with hi + lo pairs)
     kept alive for the backward; above it the backward recomputes them.  Default: ops.CAUSAL_KEEP_STATE_LIMIT_BYTES
-    (set_keep_state_limits)."""
+    (set_keep_state_limits).
+    cu_seqlens: packed sequences, the fla convention (B = 1) -- a `CausalVarlenPlan` (`causal_varlen_plan`: build it once per
+    batch), a sequence of ints or a 1-D tensor (read once: a device tensor synchronises), starting at 0, non-decreasing, ending at
+    T.  Every sequence is computed exactly as if it were alone in a call of its own: its chunks are cut from its own first token
+    and see rows 0.. of the mixing matrix and nothing of their neighbours.  Empty sequences are allowed; IndexError, before
+    anything is launched, names the sequences longer than 64 L tokens."""
     if q.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
     if int(chunk_size) <= 0:
@@ -1017,6 +1161,9 @@ def mhla_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix
     flags = _causal_flags(summaries, force_generic)
     if scale is None:
         scale = q.shape[-1] ** -0.5
+    plan = _causal_varlen_args("mhla_causal", q, mixing_matrix, cu_seqlens, chunk_size) if cu_seqlens is not None else None
+    if plan is not None and q.shape[1] > 0:
+        return _CausalVarlen.apply(q, k, v, plan.mix_eff(mixing_matrix), plan, scale, flags, keep_limit)
     if q.shape[0] == 0 or q.shape[1] == 0:   # empty batch / sequence
         return torch.zeros_like(v) + 0 * (q.sum() + k.sum() + mixing_matrix.sum()).to(v.dtype)
     nb = _MAX_GRID_BH // q.shape[2]
@@ -1075,27 +1222,81 @@ class _CausalNormGate(torch.autograd.Function):
         return dq, dk, dv, dmix.reshape(mix_shape).to(mix_dtype), dg, dw, None, None, None, None, None
 
 
-def causal_normgate_fusable(q: torch.Tensor, v: torch.Tensor, chunk_size: int = 64, flags: int = 0) -> bool:
+class _CausalNormGateVarlen(torch.autograd.Function):
+    """_CausalNormGate over a pack (see _CausalVarlen)."""
+
+    @staticmethod
+    @_device_guard
+    def forward(ctx, q, k, v, mix, gate, weight, plan, scale, norm_eps, flags, keep_limit):
+        lib = _lib.load()
+        _require_gpu(q, k, v, mix, gate, weight, plan.table)
+        B, T, H, K = q.shape
+        V = v.shape[-1]
+        n, chunk_size = plan.n_chunks, plan.chunk_size
+        _causal_check("mhla_causal_normgate", q, k, v, mix, chunk_size, gate)
+        q, k, v = _prep(q), _prep(k), _prep(v)
+        gate = _prep(gate) if gate is not None else None
+        mixf = _mix2d(mix, n)
+        wf = _f32(weight)
+        need_grad = any(ctx.needs_input_grad[:6])
+        out = _alloc_like_tokens(B, T, H, V, q) if need_grad else None
+        y = _alloc_like_tokens(B, T, H, V, q)
+        ws = _ws(_cs_varlen_plan(B, T, H, K, V, chunk_size, n, _dtype_code(q), flags)[0], q.device)
+        rc = lib.mhla_causal_varlen_normgate_fwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view_or_null(out),
+                                                 _view_or_null(gate), _ptr(wf), float(norm_eps), _view(y),
+                                                 ws.data_ptr(), ws.numel() * 4, B, T, H, K, V, chunk_size, n, plan.table.data_ptr(),
+                                                 float(scale), _dtype_code(q), flags, _stream())
+        _lib.check(rc, "mhla_causal_varlen_normgate_fwd")
+        keep = ws.numel() * 4 <= keep_limit and need_grad
+        ctx.save_for_backward(q, k, v, mixf, out, gate, wf, ws if keep else None)
+        ctx.cfg = (plan, float(scale), float(norm_eps), weight.dtype if weight is not None else None, flags)
+        return y
+
+    @staticmethod
+    @_device_guard
+    def backward(ctx, dy):
+        q, k, v, mixf, out, gate, wf, fwd_ws = ctx.saved_tensors
+        plan, scale, norm_eps, w_dtype, flags = ctx.cfg
+        do, dg, dw = _rmsnorm_gate_bwd(out, gate.contiguous() if gate is not None else None, wf, dy, norm_eps, w_dtype)
+        dq, dk, dv, dmix = _causal_bwd(q, k, v, mixf, do, fwd_ws, plan.chunk_size, scale, flags, plan)
+        return dq, dk, dv, dmix, dg, dw, None, None, None, None, None
+
+
+def causal_normgate_fusable(q: torch.Tensor, v: torch.Tensor, chunk_size: int = 64, flags: int = 0, cu_seqlens=None) -> bool:
     """Shapes the fused epilogue covers (the library's own answer, mhla_causal_normgate_fusable: bf16, K % 64 == 0, K <= 256,
-    V % 64 == 0, V <= 256 or V = 384 / 512, at most 256 chunks) within one launch's (batch, head) range."""
+    V % 64 == 0, V <= 256 or V = 384 / 512, at most 256 chunks) within one launch's (batch, head) range.  cu_seqlens (as
+    mhla_causal takes it): the answer for the pack, by its chunk count."""
     if q.dtype not in _DTYPES or not (q.shape[0] > 0 and q.shape[1] > 0 and q.shape[0] * q.shape[2] <= _MAX_GRID_BH):
         return False
+    if cu_seqlens is not None:
+        plan = cu_seqlens if isinstance(cu_seqlens, CausalVarlenPlan) else causal_varlen_plan(cu_seqlens, q.device, chunk_size)
+        return _lib.load().mhla_causal_varlen_normgate_fusable(q.shape[1], q.shape[-1], v.shape[-1], chunk_size, plan.n_chunks,
+                                                               _DTYPES[q.dtype], flags) == 1
     return _lib.load().mhla_causal_normgate_fusable(q.shape[1], q.shape[-1], v.shape[-1], chunk_size, _DTYPES[q.dtype], flags) == 1
 
 
 def mhla_causal_normgate(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor,
                          gate: Optional[torch.Tensor], weight: Optional[torch.Tensor], norm_eps: float = 1e-5,
                          chunk_size: int = 64, scale: Optional[float] = None, *, summaries: str = "tf32",
-                         keep_state_limit: Optional[int] = None) -> torch.Tensor:
+                         keep_state_limit: Optional[int] = None, cu_seqlens=None) -> torch.Tensor:
     """`rmsnorm_gate(mhla_causal(q, k, v, mix), gate, weight, norm_eps)` -- the fla layer's operator + FusedRMSNormGated
     (mhla_nlp/fla/layers/mhla.py:330-355).  Where the fused epilogue applies (bf16, K, V multiples of 64, K <= 256, V <= 256 or
     384 / 512, at most 256 chunks) the norm x gate runs inside the operator's output kernel; other shapes compose the two HIP operators.
-    `summaries`, `keep_state_limit`: see mhla_causal."""
+    `summaries`, `keep_state_limit`, `cu_seqlens`: see mhla_causal."""
     if int(chunk_size) <= 0:
         raise ValueError(f"chunk_size must be positive, got {chunk_size}")
     flags = _causal_flags(summaries, False)
     if scale is None:
         scale = q.shape[-1] ** -0.5
+    if cu_seqlens is not None:
+        if q.dim() != 4 or v.dim() != 4:
+            raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
+        plan = _causal_varlen_args("mhla_causal_normgate", q, mixing_matrix, cu_seqlens, chunk_size)
+        if not causal_normgate_fusable(q, v, chunk_size, flags, plan):
+            return rmsnorm_gate(mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries, keep_state_limit=keep_state_limit,
+                                            cu_seqlens=plan), gate, weight, norm_eps)
+        return _CausalNormGateVarlen.apply(q, k, v, plan.mix_eff(mixing_matrix), gate, weight, plan, scale, norm_eps, flags,
+                                           _causal_keep_limit(keep_state_limit))
     if not causal_normgate_fusable(q, v, chunk_size, flags):
         return rmsnorm_gate(mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries, keep_state_limit=keep_state_limit),
                             gate, weight, norm_eps)
