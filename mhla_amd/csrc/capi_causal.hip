@@ -92,32 +92,42 @@ int cs_check_tab(int T, int chunk, int n, const void* tab) {
     return MHLA_OK;
 }
 
+// the size and capability queries, by the number of chunks n (as cs_path takes it)
+CsWs cs_sizes(int B, int n, int H, int K, int V, int chunk, int dtype, unsigned flags) {
+    return cs_carve(nullptr, B, n, H, K, V, chunk, cs_path(n, K, V, chunk, dtype, flags));
+}
+int cs_fusable(int n, int K, int V, int chunk, int dtype, unsigned flags) { return cs_epi_ok(cs_path(n, K, V, chunk, dtype, flags), V) ? 1 : 0; }
+
+// Packed sequences take the same launch, at the same geometry, through the kernel's table instantiation, whose arguments are the plain
+// ones followed by the chunk table: the one place that picks between the two
+template <typename Args, typename ArgsVar>
+int launch_tab(void (*plain)(Args), void (*table)(ArgsVar), dim3 grid, dim3 block, size_t smem, hipStream_t st, const char* name,
+               const char* name_tab, const Args& a, const cs_tab_t* tab) {
+    if (!tab) return launch(plain, grid, block, smem, st, name, a);
+    const ArgsVar av{a, tab};
+    return launch(table, grid, block, smem, st, name_tab, av);
+}
+
 // S_j (or dP_i) = alpha X_j^T Y_j with 64x64 strips (generic path)
 template <typename T>
 int cs_xty(const mhla_view& x, const mhla_view& y, float* out, float alpha, int B, int T_, int H, int n, int DX,
                   int DY, hipStream_t st, const cs_tab_t* tab) {
-    StateArgsVar a{};
+    StateArgs a{};
     a.x = cv(x); a.y = cv(y); a.out = out; a.H = H; a.M = n; a.S = CS; a.D = 64; a.DX = DX; a.DY = DY; a.T = T_;
     a.alpha = alpha;
-    a.tab = tab;
     const int strips = ((DX + 63) / 64) * ((DY + 63) / 64);
-    if (tab) return launch(k_bm_state<T, 4, 2, StateArgsVar>, dim3(n, B * H, strips), dim3(NTHREADS), state_smem_floats<4>() * 4, st, "k_bm_state<2,tab>", a);
-    return launch(k_bm_state<T, 4, 2>, dim3(n, B * H, strips), dim3(NTHREADS), state_smem_floats<4>() * 4, st, "k_bm_state<2>", (const StateArgs&)a);
+    return launch_tab(k_bm_state<T, 4, 2>, k_bm_state<T, 4, 2, StateArgsVar>, dim3(n, B * H, strips), dim3(NTHREADS), state_smem_floats<4>() * 4, st,
+                      "k_bm_state<2>", "k_bm_state<2,tab>", a, tab);
 }
 
 // chunk summaries X^T Y of the 16-bit pipeline (S = K^T V, dP = scale Q^T dO)
 template <int HL>
 int cs_state16(const mhla_view& x, const mhla_view& y, uint16_t* out, float mul, int B, int T, int H, int n, int K, int V, hipStream_t st,
                const cs_tab_t* tab) {
-    fast::CsfStateArgs s{cv(x), cv(y), out, H, n, K, V, (long)T, mul};
+    const fast::CsfStateArgs s{cv(x), cv(y), out, H, n, K, V, (long)T, mul};
     const int blocks = ((K + fast::ST2_KW - 1) / fast::ST2_KW) * ((V + fast::ST2_VW - 1) / fast::ST2_VW);
-    if (tab) {
-        fast::CsfStateArgsVar sv{s, tab};
-        return launch(fast::k_csf_state2<HL, fast::CsfStateArgsVar>, dim3((n + fast::ST2_CPW - 1) / fast::ST2_CPW, B * H, blocks), dim3(ST2_T),
-                      fast::csf_state2_smem<HL>(), st, "k_csf_state<tab>", sv);
-    }
-    return launch(fast::k_csf_state2<HL>, dim3((n + fast::ST2_CPW - 1) / fast::ST2_CPW, B * H, blocks), dim3(ST2_T),
-                  fast::csf_state2_smem<HL>(), st, "k_csf_state", s);
+    return launch_tab(fast::k_csf_state2<HL>, fast::k_csf_state2<HL, fast::CsfStateArgsVar>, dim3((n + fast::ST2_CPW - 1) / fast::ST2_CPW, B * H, blocks),
+                      dim3(ST2_T), fast::csf_state2_smem<HL>(), st, "k_csf_state", "k_csf_state<tab>", s, tab);
 }
 
 // P = strictly-lower mix of S
@@ -141,11 +151,12 @@ int cs_fwd16(const mhla_view& q, const mhla_view& k, const mhla_view& v, const f
     // V slices per workgroup: the largest of 4, 3, 2, 1 that divides V / 64 (the fused epilogue owns the head: V / 64 <= 4); the
     // more slices, the fewer times a chunk's Q and K rows and its score tile are fetched / formed
     const int nvs = V / 64, nv = nvs % 4 == 0 ? 4 : nvs % 3 == 0 ? 3 : nvs % 2 == 0 ? 2 : 1;
-    const CsOutArgsVar ov{o, tab};   // (packed sequences: the same grids and launches, the kernels' table variants)
-#define OUT4(NV, EPI) (tab ? launch(fast::k_csf_out4<NV, EPI, HL, 1, CsOutArgsVar>, dim3(EPI ? n : (n + fast::CSF_OUT4_CPW - 1) / fast::CSF_OUT4_CPW, B * H, nvs / NV), dim3(fast::NT4), fast::csf_out4_smem<NV, EPI, HL>(), st, EPI ? "k_csf_out4<norm,tab>" : "k_csf_out4<tab>", ov) \
-                           : launch(fast::k_csf_out4<NV, EPI, HL>, dim3(EPI ? n : (n + fast::CSF_OUT4_CPW - 1) / fast::CSF_OUT4_CPW, B * H, nvs / NV), dim3(fast::NT4), fast::csf_out4_smem<NV, EPI, HL>(), st, EPI ? "k_csf_out4<norm>" : "k_csf_out4", o))
-#define OUT4H2(NV) (tab ? launch(fast::k_csf_out4<NV, true, HL, 2, CsOutArgsVar>, dim3(n, B * H, 1), dim3(fast::NT4), fast::csf_out4_smem<NV, true, HL, 2>(), st, "k_csf_out4<norm,2,tab>", ov) \
-                        : launch(fast::k_csf_out4<NV, true, HL, 2>, dim3(n, B * H, 1), dim3(fast::NT4), fast::csf_out4_smem<NV, true, HL, 2>(), st, "k_csf_out4<norm,2>", o))
+#define OUT4(NV, EPI) launch_tab(fast::k_csf_out4<NV, EPI, HL>, fast::k_csf_out4<NV, EPI, HL, 1, CsOutArgsVar>,                                \
+                                 dim3(EPI ? n : (n + fast::CSF_OUT4_CPW - 1) / fast::CSF_OUT4_CPW, B * H, nvs / NV), dim3(fast::NT4),           \
+                                 fast::csf_out4_smem<NV, EPI, HL>(), st, EPI ? "k_csf_out4<norm>" : "k_csf_out4",                               \
+                                 EPI ? "k_csf_out4<norm,tab>" : "k_csf_out4<tab>", o, tab)
+#define OUT4H2(NV) launch_tab(fast::k_csf_out4<NV, true, HL, 2>, fast::k_csf_out4<NV, true, HL, 2, CsOutArgsVar>, dim3(n, B * H, 1), dim3(fast::NT4), \
+                              fast::csf_out4_smem<NV, true, HL, 2>(), st, "k_csf_out4<norm,2>", "k_csf_out4<norm,2,tab>", o, tab)
     if (epi && nvs > 4) RC(nvs == 6 ? OUT4H2(3) : OUT4H2(4));   // V = 384, 512: the head in two halves (cs_epi_ok)
     else if (epi) RC(nvs == 1 ? OUT4(1, true) : nvs == 2 ? OUT4(2, true) : nvs == 3 ? OUT4(3, true) : OUT4(4, true));
     else     RC(nv == 1 ? OUT4(1, false) : nv == 2 ? OUT4(2, false) : nv == 3 ? OUT4(3, false) : OUT4(4, false));
@@ -183,11 +194,9 @@ int cs_bwd16(const mhla_view& q, const mhla_view& k, const mhla_view& v, const f
 #undef MIXB
     CsTokArgs t{cv(q), cv(k), cv(v), cv(dout), cmv(dq), cmv(dk), cmv(dv), mix, ldmix, w.P, w.dS, w.diag, H, n, K, V, (long)T, scale};
     // chunks per workgroup: the largest power of two (<= the variant's limit) that still leaves every CU a workgroup
-    CsTokArgsVar tv{};
-    tv.tab = tab;
-#define TOK4(NK) (t.cpw = csf_tok4_walk(fast::csf_tok4_cpw<NK, HL>(), n, B * H), (CsTokArgs&)tv = t, \
-                  tab ? launch(fast::k_csf_bwd_tok4<NK, HL, CsTokArgsVar>, dim3((n + t.cpw - 1) / t.cpw, B * H), dim3(fast::NT4), fast::csf_tok4_smem<NK, HL>(), st, "k_csf_bwd_tok4<tab>", tv) \
-                      : launch(fast::k_csf_bwd_tok4<NK, HL>, dim3((n + t.cpw - 1) / t.cpw, B * H), dim3(fast::NT4), fast::csf_tok4_smem<NK, HL>(), st, "k_csf_bwd_tok4", t))
+#define TOK4(NK) (t.cpw = csf_tok4_walk(fast::csf_tok4_cpw<NK, HL>(), n, B * H),                                                          \
+                  launch_tab(fast::k_csf_bwd_tok4<NK, HL>, fast::k_csf_bwd_tok4<NK, HL, CsTokArgsVar>, dim3((n + t.cpw - 1) / t.cpw, B * H), \
+                             dim3(fast::NT4), fast::csf_tok4_smem<NK, HL>(), st, "k_csf_bwd_tok4", "k_csf_bwd_tok4<tab>", t, tab))
     RC(K == 64 ? TOK4(1) : K == 128 ? TOK4(2) : K == 192 ? TOK4(3) : TOK4(4));
 #undef TOK4
     // up to 128 chunks: 16 part-lanes per element instead of 4 -- a thread's chain of dependent load batches is what the kernel takes
@@ -239,8 +248,8 @@ int cs_fwd_impl(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldm
         dim3 mgrid((unsigned)((m.E + MIX_TE - 1) / MIX_TE), (n + MIX_TI - 1) / MIX_TI, B * H);
         RC(launch(k_mix<0, 1>, mgrid, dim3(NTHREADS), MIX_SMEM_FLOATS * 4, st, "k_mix<0,1>", m));
         CsOutArgs o{cv(q), cv(k), cv(v), cmv(out), mix, ldmix, w.P, H, n, K, V, (long)T, scale, cmv(out), cv(mhla_view{nullptr, 0, 0, 0}), nullptr, 0.f};
-        if (tab) RC(launch(k_cs_out<ET, CsOutArgsVar>, dim3(n, B * H, (V + 63) / 64), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cs_out<tab>", CsOutArgsVar{o, tab}));
-        else     RC(launch(k_cs_out<ET>, dim3(n, B * H, (V + 63) / 64), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cs_out", o));
+        RC(launch_tab(k_cs_out<ET>, k_cs_out<ET, CsOutArgsVar>, dim3(n, B * H, (V + 63) / 64), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cs_out",
+                      "k_cs_out<tab>", o, tab));
     });
     return MHLA_OK;
 }
@@ -285,14 +294,8 @@ int cs_bwd_impl(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldm
         MixArgs mt{mix, ldmix, w.dP, w.dS, n, E};
         RC(launch(k_mix<1, 1>, mgrid, dim3(NTHREADS), MIX_SMEM_FLOATS * 4, st, "k_mix<1,1>", mt));
         CsTokArgs t{cv(q), cv(k), cv(v), cv(dout), cmv(dq), cmv(dk), cmv(dv), mix, ldmix, w.P, w.dS, w.diag, H, n, K, V, (long)T, scale};
-        if (tab) {
-            CsTokArgsVar tv{};
-            (CsTokArgs&)tv = t;
-            tv.tab = tab;
-            RC(launch(k_cs_bwd_tok<ET, CsTokArgsVar>, dim3(n, B * H), dim3(NTHREADS), CS_TOK_SMEM_FLOATS * 4, st, "k_cs_bwd_tok<tab>", tv));
-        } else {
-            RC(launch(k_cs_bwd_tok<ET>, dim3(n, B * H), dim3(NTHREADS), CS_TOK_SMEM_FLOATS * 4, st, "k_cs_bwd_tok", t));
-        }
+        RC(launch_tab(k_cs_bwd_tok<ET>, k_cs_bwd_tok<ET, CsTokArgsVar>, dim3(n, B * H), dim3(NTHREADS), CS_TOK_SMEM_FLOATS * 4, st, "k_cs_bwd_tok",
+                      "k_cs_bwd_tok<tab>", t, tab));
         DwArgs d{w.dP, w.S, E, nullptr, nullptr, 0, w.dwp, n, tiles, nsplit};
         RC(launch(k_dw<1>, dim3(tiles * tiles, B * H, nsplit), dim3(NTHREADS), DW_SMEM_FLOATS * 4, st, "k_dw<1>", d));
         RC(launch(k_dw_reduce<1>, dim3((n * n + 63) / 64), dim3(256), 0, st, "k_dw_reduce<1>", (const float*)w.dwp,
@@ -309,13 +312,13 @@ extern "C" {
 // causal
 // ---------------------------------------------------------------------------------------------
 size_t mhla_causal_fwd_ws_bytes(int B, int T, int H, int K, int V, int chunk, int dtype, unsigned flags) {
-    return cs_carve(nullptr, B, cs_chunks(T, chunk), H, K, V, chunk, cs_path(cs_chunks(T, chunk), K, V, chunk, dtype, flags)).total_fwd;
+    return cs_sizes(B, cs_chunks(T, chunk), H, K, V, chunk, dtype, flags).total_fwd;
 }
 size_t mhla_causal_bwd_ws_bytes(int B, int T, int H, int K, int V, int chunk, int dtype, unsigned flags) {
-    return cs_carve(nullptr, B, cs_chunks(T, chunk), H, K, V, chunk, cs_path(cs_chunks(T, chunk), K, V, chunk, dtype, flags)).total_bwd;
+    return cs_sizes(B, cs_chunks(T, chunk), H, K, V, chunk, dtype, flags).total_bwd;
 }
 int mhla_causal_normgate_fusable(int T, int K, int V, int chunk, int dtype, unsigned flags) {
-    return cs_epi_ok(cs_path(cs_chunks(T, chunk), K, V, chunk, dtype, flags), V) ? 1 : 0;
+    return cs_fusable(cs_chunks(T, chunk), K, V, chunk, dtype, flags);
 }
 
 // The causal operator's kernel family and summary format as text (see mhla_describe_dispatch).
@@ -361,16 +364,13 @@ int mhla_causal_bwd(mhla_view q, mhla_view k, mhla_view v, const float* mix, int
 
 // ---- packed sequences: the same launch chains over a caller-built chunk table (mhla_hip.h) ----
 size_t mhla_causal_varlen_fwd_ws_bytes(int B, int T, int H, int K, int V, int chunk, int n_chunks, int dtype, unsigned flags) {
-    (void)T;
-    return cs_carve(nullptr, B, n_chunks, H, K, V, chunk, cs_path(n_chunks, K, V, chunk, dtype, flags)).total_fwd;
+    return (void)T, cs_sizes(B, n_chunks, H, K, V, chunk, dtype, flags).total_fwd;
 }
 size_t mhla_causal_varlen_bwd_ws_bytes(int B, int T, int H, int K, int V, int chunk, int n_chunks, int dtype, unsigned flags) {
-    (void)T;
-    return cs_carve(nullptr, B, n_chunks, H, K, V, chunk, cs_path(n_chunks, K, V, chunk, dtype, flags)).total_bwd;
+    return (void)T, cs_sizes(B, n_chunks, H, K, V, chunk, dtype, flags).total_bwd;
 }
 int mhla_causal_varlen_normgate_fusable(int T, int K, int V, int chunk, int n_chunks, int dtype, unsigned flags) {
-    (void)T;
-    return cs_epi_ok(cs_path(n_chunks, K, V, chunk, dtype, flags), V) ? 1 : 0;
+    return (void)T, cs_fusable(n_chunks, K, V, chunk, dtype, flags);
 }
 int mhla_causal_varlen_fwd(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out, void* ws,
                            size_t ws_bytes, int B, int T, int H, int K, int V, int chunk, int n_chunks, const int* chunk_tab_dev,

@@ -26,6 +26,31 @@ int cst_check_state(const float* S, int cap, const float* P, const float* Cur) {
     if (((uintptr_t)S | (uintptr_t)P | (uintptr_t)Cur) % 16) return fail(MHLA_EINVAL, "state: S, P and Cur must be 16-byte aligned");
     return MHLA_OK;
 }
+// what every step and extend entry point checks of its tokens, outputs and state, in this order (the parameter names are the messages')
+int cst_check_io(const mhla_view& q, const mhla_view& k, const mhla_view& v, const mhla_mview& out, const mhla_mview& y, const mhla_view& gate,
+                 const float* norm_w, int dtype, const float* S, int cap, const float* P, const float* Cur) {
+    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(v);
+    if (!out.ptr && !y.ptr) return fail(MHLA_EINVAL, "out and y both null");
+    if (out.ptr) CHECK_VIEW(out);
+    if (y.ptr) CHECK_VIEW(y);
+    if (gate.ptr) CHECK_VIEW(gate);
+    if ((gate.ptr || norm_w) && !y.ptr) return fail(MHLA_EINVAL, "gate / norm_w given without y");
+    return cst_check_state(S, cap, P, Cur);
+}
+int cst_check_ws(const void* ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need) return ws_too_small(ws_bytes, need);
+    if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
+    return MHLA_OK;
+}
+int cst_check_dev(const char* name, const void* p) {   // an int32 array on the device
+    if (!p || ((uintptr_t)p) % 4) return fail(MHLA_EINVAL, "%s null or not 4-byte aligned", name);
+    return MHLA_OK;
+}
+int cst_check_mix(const float* mix, int ldmix, int64_t lastrow) {   // lastrow: the last row of mix the call reads, up to its diagonal
+    if (!mix || ldmix < lastrow + 1)
+        return fail(MHLA_EINVAL, "mix null or ldmix=%d < %lld (row %lld of mix is read)", ldmix, (long long)(lastrow + 1), (long long)lastrow);
+    return MHLA_OK;
+}
 // K rows per workgroup of k_cs_step (a multiple of 16): the whole of K where (b, h) x V tiles already give every CU four
 // workgroups, otherwise halved down to 16 rows -- B H = 4 at K = 128, V = 256 runs 128 workgroups instead of 16
 int cst_rows(size_t bh, int K, int V) {
@@ -41,6 +66,24 @@ size_t cst_ws_bytes(int B, int H, int K, int V) {   // the most splits any plan 
 int cst_roll(float* S, int cap, float* P, float* Cur, const float* mixrow, int nj, int commit, int BH, long E, hipStream_t st) {
     const CsRollArgs r{S, P, Cur, mixrow, E, cap, nj, commit};
     return launch(k_cs_roll<false>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll", r);
+}
+// the roll of a ragged state: each sequence for itself, by pos_dev (the position of the token its step just took)
+int cst_roll_ragged(float* S, int cap, float* P, float* Cur, const int32_t* pos_dev, const float* mix, int ldmix, int max_pos, int H, int BH,
+                    long E, hipStream_t st) {
+    const CsRollArgs r{S, P, Cur, nullptr, E, cap, 0, 0, pos_dev, mix, ldmix, max_pos, H};
+    return launch(k_cs_roll<true>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll_ragged", r);
+}
+int cst_zero_cur(float* Cur, int BH, long E, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(Cur, 0, (size_t)BH * E * 4, st);
+    if (e != hipSuccess) return fail(MHLA_ELAUNCH, "hipMemsetAsync(Cur): %s", hipGetErrorString(e));
+    return MHLA_OK;
+}
+// one launch of a k_cs_step variant: fills in the K split (s.kr rows per workgroup, s.nsplit partial sums per output, which the finish adds)
+template <typename KERN>
+int cst_step(KERN kernel, const char* name, CsStepArgs& s, int BH, hipStream_t st) {
+    s.kr = cst_rows((size_t)BH, s.K, s.V);
+    s.nsplit = (s.K + s.kr - 1) / s.kr;
+    return launch(kernel, dim3((s.V + CST_VT - 1) / CST_VT, s.nsplit, BH), dim3(CST_THREADS), 0, st, name, s);
 }
 
 template <typename T>
@@ -108,17 +151,14 @@ int mhla_causal_state_init(mhla_view k, mhla_view v, const float* mix, int ldmix
     if (nfull + (tail ? 1 : 0) > cap_chunks) return fail(MHLA_EINVAL, "T=%d tokens need %d chunks, the state holds %d", T, nfull + (tail ? 1 : 0), cap_chunks);
     // the open chunk i = nfull reads mix[i][0 .. i]; a state that is full (nfull == cap_chunks) has no open chunk
     const bool open = nfull < cap_chunks;
-    if (open && (!mix || ldmix < nfull + 1)) return fail(MHLA_EINVAL, "mix null or ldmix=%d < %d (row %d of mix is read)", ldmix, nfull + 1, nfull);
+    if (open) RC(cst_check_mix(mix, ldmix, nfull));
     hipStream_t st = (hipStream_t)stream;
     const long E = (long)K * V;
     DISPATCH_T(dtype, {
         if (nfull) RC(cst_xty<ET>(k, v, 0, (long)nfull * chunk, S, cap_chunks, B, H, K, V, st));
         if (tail)  RC(cst_xty<ET>(k, v, (long)nfull * chunk, tail, Cur, 1, B, H, K, V, st));
     });
-    if (!tail) {
-        hipError_t e = hipMemsetAsync(Cur, 0, (size_t)B * H * E * 4, st);
-        if (e != hipSuccess) return fail(MHLA_ELAUNCH, "hipMemsetAsync(Cur): %s", hipGetErrorString(e));
-    }
+    if (!tail) RC(cst_zero_cur(Cur, B * H, E, st));
     return cst_roll(S, cap_chunks, P, Cur, open ? mix + (long)nfull * ldmix : nullptr, nfull, 0, B * H, E, st);
 }
 
@@ -126,29 +166,20 @@ int mhla_causal_step(mhla_view q, mhla_view k, mhla_view v, const float* mix, in
                      int64_t pos, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws,
                      size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype, void* stream) {
     RC(cst_check(B, H, K, V, chunk, dtype));
-    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(v);
-    if (!out.ptr && !y.ptr) return fail(MHLA_EINVAL, "out and y both null");
-    if (out.ptr) CHECK_VIEW(out);
-    if (y.ptr) CHECK_VIEW(y);
-    if (gate.ptr) CHECK_VIEW(gate);
-    if ((gate.ptr || norm_w) && !y.ptr) return fail(MHLA_EINVAL, "gate / norm_w given without y");
-    RC(cst_check_state(S, cap_chunks, P, Cur));
+    RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
     if (pos < 0) return fail(MHLA_EINVAL, "pos=%lld is negative", (long long)pos);
     const int64_t i = pos / chunk;
     const int r = (int)(pos - i * chunk);
     if (i >= cap_chunks) return fail(MHLA_EINVAL, "pos=%lld is in chunk %lld, the state holds %d", (long long)pos, (long long)i, cap_chunks);
     const bool roll = r == chunk - 1, next = roll && i + 1 < cap_chunks;
-    if (!mix || ldmix < i + 1 + (next ? 1 : 0))
-        return fail(MHLA_EINVAL, "mix null or ldmix=%d < %lld (row %lld of mix is read)", ldmix, (long long)(i + 1 + (next ? 1 : 0)), (long long)(i + (next ? 1 : 0)));
-    const size_t need = cst_ws_bytes(B, H, K, V);
-    if (!ws || ws_bytes < need) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-    if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
+    RC(cst_check_mix(mix, ldmix, i + (next ? 1 : 0)));
+    RC(cst_check_ws(ws, ws_bytes, cst_ws_bytes(B, H, K, V)));
     hipStream_t st = (hipStream_t)stream;
-    const int BH = B * H, kr = cst_rows((size_t)BH, K, V), nsplit = (K + kr - 1) / kr;
+    const int BH = B * H;
     DISPATCH_T(dtype, {
-        const CsStepArgs s{cv(q), cv(k), cv(v), mix + i * ldmix + i, P, Cur, (float*)ws, H, K, V, kr, nsplit};
-        RC(launch(k_cs_step<ET>, dim3((V + CST_VT - 1) / CST_VT, nsplit, BH), dim3(CST_THREADS), 0, st, "k_cs_step", s));
-        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, nsplit};
+        CsStepArgs s{cv(q), cv(k), cv(v), mix + i * ldmix + i, P, Cur, (float*)ws, H, K, V};
+        RC(cst_step(k_cs_step<ET>, "k_cs_step", s, BH, st));
+        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit};
         RC(launch(k_cs_step_finish<ET>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
     });
     if (roll) RC(cst_roll(S, cap_chunks, P, Cur, next ? mix + (i + 1) * ldmix : nullptr, (int)i + 1, 1, BH, (long)K * V, st));
@@ -160,14 +191,8 @@ int mhla_causal_step_ragged(mhla_view q, mhla_view k, mhla_view v, const float* 
                             const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V,
                             int chunk, float scale, int dtype, void* stream) {
     RC(cst_check(B, H, K, V, chunk, dtype));
-    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(v);
-    if (!out.ptr && !y.ptr) return fail(MHLA_EINVAL, "out and y both null");
-    if (out.ptr) CHECK_VIEW(out);
-    if (y.ptr) CHECK_VIEW(y);
-    if (gate.ptr) CHECK_VIEW(gate);
-    if ((gate.ptr || norm_w) && !y.ptr) return fail(MHLA_EINVAL, "gate / norm_w given without y");
-    RC(cst_check_state(S, cap_chunks, P, Cur));
-    if (!pos_dev || ((uintptr_t)pos_dev) % 4) return fail(MHLA_EINVAL, "pos_dev null or not 4-byte aligned");
+    RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
+    RC(cst_check_dev("pos_dev", pos_dev));
     if (max_pos < 0 || max_pos >= INT32_MAX) return fail(MHLA_EINVAL, "max_pos=%lld is negative or beyond int32", (long long)max_pos);
     const int64_t i = max_pos / chunk;
     if (i >= cap_chunks) return fail(MHLA_EINVAL, "max_pos=%lld is in chunk %lld, the state holds %d", (long long)max_pos, (long long)i, cap_chunks);
@@ -175,23 +200,16 @@ int mhla_causal_step_ragged(mhla_view q, mhla_view k, mhla_view v, const float* 
     // must be covered (unless that chunk is the state's last), as if that sequence were the one -- a restriction (mhla_hip.h):
     // the matrix passed with a boundary step reaches one row past the furthest sequence, or the state's capacity
     const bool next = any_boundary && i + 1 < cap_chunks;
-    if (!mix || ldmix < i + 1 + (next ? 1 : 0))
-        return fail(MHLA_EINVAL, "mix null or ldmix=%d < %lld (row %lld of mix is read)", ldmix, (long long)(i + 1 + (next ? 1 : 0)), (long long)(i + (next ? 1 : 0)));
-    const size_t need = cst_ws_bytes(B, H, K, V);
-    if (!ws || ws_bytes < need) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-    if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
+    RC(cst_check_mix(mix, ldmix, i + (next ? 1 : 0)));
+    RC(cst_check_ws(ws, ws_bytes, cst_ws_bytes(B, H, K, V)));
     hipStream_t st = (hipStream_t)stream;
-    const int BH = B * H, kr = cst_rows((size_t)BH, K, V), nsplit = (K + kr - 1) / kr;
-    const long E = (long)K * V;
+    const int BH = B * H;
     // step and roll address by pos_dev; the finish, which does not, advances it: last in the chain
     DISPATCH_T(dtype, {
-        const CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, H, K, V, kr, nsplit, pos_dev, ldmix, (int)max_pos};
-        RC(launch(k_cs_step<ET, true>, dim3((V + CST_VT - 1) / CST_VT, nsplit, BH), dim3(CST_THREADS), 0, st, "k_cs_step_ragged", s));
-        if (any_boundary) {
-            const CsRollArgs r{S, P, Cur, nullptr, E, cap_chunks, 0, 0, pos_dev, mix, ldmix, (int)max_pos, H};
-            RC(launch(k_cs_roll<true>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll_ragged", r));
-        }
-        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, nsplit, pos_dev};
+        CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, H, K, V, 0, 0, pos_dev, ldmix, (int)max_pos};
+        RC(cst_step(k_cs_step<ET, true>, "k_cs_step_ragged", s, BH, st));
+        if (any_boundary) RC(cst_roll_ragged(S, cap_chunks, P, Cur, pos_dev, mix, ldmix, (int)max_pos, H, BH, (long)K * V, st));
+        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit, pos_dev};
         RC(launch(k_cs_step_finish<ET>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
     });
     return MHLA_OK;
@@ -203,16 +221,10 @@ int mhla_causal_step_dev(mhla_view q, mhla_view k, mhla_view v, const float* mix
                          mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                          void* stream) {
     RC(cst_check(B, H, K, V, chunk, dtype));
-    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(v);
-    if (!out.ptr && !y.ptr) return fail(MHLA_EINVAL, "out and y both null");
-    if (out.ptr) CHECK_VIEW(out);
-    if (y.ptr) CHECK_VIEW(y);
-    if (gate.ptr) CHECK_VIEW(gate);
-    if ((gate.ptr || norm_w) && !y.ptr) return fail(MHLA_EINVAL, "gate / norm_w given without y");
-    RC(cst_check_state(S, cap_chunks, P, Cur));
+    RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
     if (cap_chunks > INT32_MAX / 64) return fail(MHLA_ENOTSUP, "cap_chunks=%d: positions beyond int32", cap_chunks);
-    if (!pos_dev || ((uintptr_t)pos_dev) % 4) return fail(MHLA_EINVAL, "pos_dev null or not 4-byte aligned");
-    if (!full_dev || ((uintptr_t)full_dev) % 4) return fail(MHLA_EINVAL, "full_dev null or not 4-byte aligned");
+    RC(cst_check_dev("pos_dev", pos_dev));
+    RC(cst_check_dev("full_dev", full_dev));
     // every bound is the capacity: whichever chunk a sequence is in, rows and columns 0 .. cap_chunks - 1 of mix may be read
     if (!mix || ldmix < cap_chunks)
         return fail(MHLA_EINVAL, "mix null or ldmix=%d < cap_chunks=%d (the matrix is read up to row %d)", ldmix, cap_chunks, cap_chunks - 1);
@@ -227,23 +239,18 @@ int mhla_causal_step_dev(mhla_view q, mhla_view k, mhla_view v, const float* mix
         if (tab_rows < (int64_t)64 * cap_chunks || tab_rows > INT32_MAX)
             return fail(MHLA_EINVAL, "tab_rows=%lld: the tables need a row per position, %lld (64 cap_chunks)", (long long)tab_rows, (long long)64 * cap_chunks);
     }
-    const size_t need = cst_ws_bytes(B, H, K, V);
-    if (!ws || ws_bytes < need) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-    if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
+    RC(cst_check_ws(ws, ws_bytes, cst_ws_bytes(B, H, K, V)));
     hipStream_t st = (hipStream_t)stream;
-    const int BH = B * H, kr = cst_rows((size_t)BH, K, V), nsplit = (K + kr - 1) / kr, max_pos = 64 * cap_chunks - 1;
-    const long E = (long)K * V;
+    const int BH = B * H, max_pos = 64 * cap_chunks - 1;
     // always the same three launches, none of whose arguments depends on a position: step and roll address by pos_dev, the
     // finish -- one thread per sequence reads it, none else -- advances it or sets full_dev
     DISPATCH_T(dtype, {
-        const CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, H, K, V, kr, nsplit, pos_dev, ldmix, max_pos,
-                           rope_cos, rope_sin, (long)ld_tab, (int)tab_rows, feature_map};
-        const dim3 grid((V + CST_VT - 1) / CST_VT, nsplit, BH);
-        if (pro) RC(launch(k_cs_step<ET, true, true, true>, grid, dim3(CST_THREADS), 0, st, "k_cs_step_dev<pro>", s));
-        else     RC(launch(k_cs_step<ET, true, true, false>, grid, dim3(CST_THREADS), 0, st, "k_cs_step_dev", s));
-        const CsRollArgs r{S, P, Cur, nullptr, E, cap_chunks, 0, 0, pos_dev, mix, ldmix, max_pos, H};
-        RC(launch(k_cs_roll<true>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll_ragged", r));
-        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, nsplit, pos_dev, max_pos, full_dev};
+        CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, H, K, V, 0, 0, pos_dev, ldmix, max_pos,
+                     rope_cos, rope_sin, (long)ld_tab, (int)tab_rows, feature_map};
+        if (pro) RC(cst_step(k_cs_step<ET, true, true, true>, "k_cs_step_dev<pro>", s, BH, st));
+        else     RC(cst_step(k_cs_step<ET, true, true, false>, "k_cs_step_dev", s, BH, st));
+        RC(cst_roll_ragged(S, cap_chunks, P, Cur, pos_dev, mix, ldmix, max_pos, H, BH, (long)K * V, st));
+        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit, pos_dev, max_pos, full_dev};
         RC(launch(k_cs_step_finish<ET, true>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish_dev", f));
     });
     return MHLA_OK;
@@ -261,13 +268,7 @@ int mhla_causal_extend(mhla_view q, mhla_view k, mhla_view v, const float* mix, 
     RC(cst_check(B, H, K, V, chunk, dtype));
     if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive", T);
     if (T > 65535) return fail(MHLA_ENOTSUP, "T=%d exceeds 65535 tokens per call", T);
-    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(v);
-    if (!out.ptr && !y.ptr) return fail(MHLA_EINVAL, "out and y both null");
-    if (out.ptr) CHECK_VIEW(out);
-    if (y.ptr) CHECK_VIEW(y);
-    if (gate.ptr) CHECK_VIEW(gate);
-    if ((gate.ptr || norm_w) && !y.ptr) return fail(MHLA_EINVAL, "gate / norm_w given without y");
-    RC(cst_check_state(S, cap_chunks, P, Cur));
+    RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
     if (pos < 0) return fail(MHLA_EINVAL, "pos=%lld is negative", (long long)pos);
     const CxPlan p = cx_plan(B, T, H, K, V, pos);
     if (p.ilast >= cap_chunks)
@@ -275,10 +276,8 @@ int mhla_causal_extend(mhla_view q, mhla_view k, mhla_view v, const float* mix, 
     // rows of mix read: the diagonal of chunks i .. ilast, and row iend (the chunk open afterwards) when a chunk closed and the state is not full
     const bool closing = p.iend > p.i, full = p.iend >= cap_chunks;
     const int64_t lastrow = closing && !full ? p.iend : p.ilast;
-    if (!mix || ldmix < lastrow + 1)
-        return fail(MHLA_EINVAL, "mix null or ldmix=%d < %lld (row %lld of mix is read)", ldmix, (long long)(lastrow + 1), (long long)lastrow);
-    if (!ws || ws_bytes < p.total * 4) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, p.total * 4);
-    if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
+    RC(cst_check_mix(mix, ldmix, lastrow));
+    RC(cst_check_ws(ws, ws_bytes, p.total * 4));
     hipStream_t st = (hipStream_t)stream;
     const int BH = B * H, nvt = (V + 63) / 64;
     const long E = (long)K * V;
@@ -298,12 +297,8 @@ int mhla_causal_extend(mhla_view q, mhla_view k, mhla_view v, const float* mix, 
         RC(launch(k_cx_xty_acc<ET>, dim3(1, BH, ((K + 63) / 64) * nvt), dim3(NTHREADS), 0, st, "k_cx_xty_acc", c));
         if (closes) {
             if (nwhole) RC(cst_xty<ET>(k, v, p.a, (long)nwhole * CS, S + (p.i + 1) * E, cap_chunks, B, H, K, V, st));
-            if (tail) {
-                RC(cst_xty<ET>(k, v, p.a + (long)nwhole * CS, tail, Cur, 1, B, H, K, V, st));
-            } else {
-                hipError_t e = hipMemsetAsync(Cur, 0, (size_t)BH * E * 4, st);
-                if (e != hipSuccess) return fail(MHLA_ELAUNCH, "hipMemsetAsync(Cur): %s", hipGetErrorString(e));
-            }
+            if (tail) RC(cst_xty<ET>(k, v, p.a + (long)nwhole * CS, tail, Cur, 1, B, H, K, V, st));
+            else      RC(cst_zero_cur(Cur, BH, E, st));
             CxMixArgs m{S, tiles, P, mix, E, ldmix, cap_chunks, (int)p.i + 1, p.nws, 0, full ? -1 : (int)p.iend};
             m.nc = (int)((full ? p.ilast : p.iend) - p.i);
             const int groups = std::max(1, (m.nc + CX_MIX_NC - 1) / CX_MIX_NC);   // (a full state forms no P: one group writes the zeros)
@@ -335,17 +330,11 @@ int mhla_causal_extend_ragged(mhla_view q, mhla_view k, mhla_view v, const float
                               void* stream) {
     RC(cst_check(B, H, K, V, chunk, dtype));
     if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive", T);
-    if (T > 65535) return fail(MHLA_EINVAL, "T=%d exceeds 65535 tokens per call", T);
-    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(v);
-    if (!out.ptr && !y.ptr) return fail(MHLA_EINVAL, "out and y both null");
-    if (out.ptr) CHECK_VIEW(out);
-    if (y.ptr) CHECK_VIEW(y);
-    if (gate.ptr) CHECK_VIEW(gate);
-    if ((gate.ptr || norm_w) && !y.ptr) return fail(MHLA_EINVAL, "gate / norm_w given without y");
-    RC(cst_check_state(S, cap_chunks, P, Cur));
+    if (T > 65535) return fail(MHLA_EINVAL, "T=%d exceeds 65535 tokens per call", T);   // (mhla_causal_extend answers MHLA_ENOTSUP here: kept, a caller may test the code)
+    RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
     if (cap_chunks > INT32_MAX / 64) return fail(MHLA_ENOTSUP, "cap_chunks=%d: positions beyond int32", cap_chunks);
-    if (!pos_dev || ((uintptr_t)pos_dev) % 4) return fail(MHLA_EINVAL, "pos_dev null or not 4-byte aligned");
-    if (!ntok_dev || ((uintptr_t)ntok_dev) % 4) return fail(MHLA_EINVAL, "ntok_dev null or not 4-byte aligned");
+    RC(cst_check_dev("pos_dev", pos_dev));
+    RC(cst_check_dev("ntok_dev", ntok_dev));
     if (max_end < 0) return fail(MHLA_EINVAL, "max_end=%lld is negative", (long long)max_end);
     if (max_end > (int64_t)64 * cap_chunks)
         return fail(MHLA_EINVAL, "max_end=%lld tokens need %lld chunks, the state holds %d", (long long)max_end, (long long)((max_end + 63) / 64), cap_chunks);
@@ -356,11 +345,9 @@ int mhla_causal_extend_ragged(mhla_view q, mhla_view k, mhla_view v, const float
     // (its end) / 64.  Which sequence closes is known on the device only: with any_close row max_end / 64 must be covered (or
     // the state's last), as if the furthest sequence were the one -- the restriction of mhla_causal_step_ragged
     const int64_t lastrow = any_close ? std::min<int64_t>(max_end / 64, cap_chunks - 1) : (max_end > 0 ? (max_end - 1) / 64 : 0);
-    if (!mix || ldmix < lastrow + 1)
-        return fail(MHLA_EINVAL, "mix null or ldmix=%d < %lld (row %lld of mix is read)", ldmix, (long long)(lastrow + 1), (long long)lastrow);
+    RC(cst_check_mix(mix, ldmix, lastrow));
     const CxRagPlan p = cx_rag_plan(B, T, H, K, V, max_later);
-    if (!ws || ws_bytes < p.total * 4) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, p.total * 4);
-    if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
+    RC(cst_check_ws(ws, ws_bytes, p.total * 4));
     hipStream_t st = (hipStream_t)stream;
     const int BH = B * H, nvt = (V + 63) / 64, strips = ((K + 63) / 64) * nvt;
     const long E = (long)K * V;

@@ -188,14 +188,11 @@ def _bm_plan(B, H, M, S, D, dt, split, flags):
 
 
 @functools.lru_cache(maxsize=512)
-def _cs_plan(B, T, H, K, V, chunk, dt, flags):
+def _cs_plan(B, T, H, K, V, chunk, dt, flags, n_chunks=None):
+    """(forward, backward) workspace bytes of a causal call; `n_chunks`: the chunks of a pack (None: the uniform call)."""
     lib = _lib.load()
-    return (lib.mhla_causal_fwd_ws_bytes(B, T, H, K, V, chunk, dt, flags), lib.mhla_causal_bwd_ws_bytes(B, T, H, K, V, chunk, dt, flags))
-
-
-@functools.lru_cache(maxsize=512)
-def _cs_varlen_plan(B, T, H, K, V, chunk, n_chunks, dt, flags):
-    lib = _lib.load()
+    if n_chunks is None:
+        return (lib.mhla_causal_fwd_ws_bytes(B, T, H, K, V, chunk, dt, flags), lib.mhla_causal_bwd_ws_bytes(B, T, H, K, V, chunk, dt, flags))
     return (lib.mhla_causal_varlen_fwd_ws_bytes(B, T, H, K, V, chunk, n_chunks, dt, flags),
             lib.mhla_causal_varlen_bwd_ws_bytes(B, T, H, K, V, chunk, n_chunks, dt, flags))
 
@@ -933,11 +930,18 @@ def _causal_check(what, q, k, v, mix, chunk_size, gate=None):
     return n
 
 
+def _causal_call(name, plan, *args):
+    """mhla_causal_<name>(*args), checked; for a pack mhla_causal_varlen_<name>, whose two extra arguments -- the pack's chunk count
+    and chunk table -- stand before the last four (scale, dtype, flags, stream)."""
+    if plan is not None:
+        name, args = "varlen_" + name, args[:-4] + (plan.n_chunks, plan.table.data_ptr()) + args[-4:]
+    _lib.check(getattr(_lib.load(), "mhla_causal_" + name)(*args), "mhla_causal_" + name)
+
+
 def _causal_bwd(q, k, v, mixf, dout, fwd_ws, chunk_size, scale, flags, plan=None):
     """mhla_causal_bwd on a node's saved tensors (`fwd_ws`: the forward's chunk summaries, None to recompute them):
     (dq, dk, dv, dmix), dmix fp32 in the shape of mixf.  `plan`: packed sequences -- mhla_causal_varlen_bwd over the plan's chunk
     table, mixf the plan's effective matrix [n, n]."""
-    lib = _lib.load()
     B, T, H, K = q.shape
     V = v.shape[-1]
     dq = _alloc_like_tokens(B, T, H, K, q)
@@ -947,54 +951,47 @@ def _causal_bwd(q, k, v, mixf, dout, fwd_ws, chunk_size, scale, flags, plan=None
     n_chunks = (T + chunk_size - 1) // chunk_size if plan is None else plan.n_chunks
     dmix = (torch.empty if tuple(mixf.shape) == (n_chunks, n_chunks) else torch.zeros)(mixf.shape, dtype=torch.float32, device=q.device)
     dt = _dtype_code(q)
-    if plan is not None:
-        ws = _ws(_cs_varlen_plan(B, T, H, K, V, chunk_size, n_chunks, dt, flags)[1], q.device)
-        rc = lib.mhla_causal_varlen_bwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(dout),
-                                        _view(dq), _view(dk), _view(dv), dmix.data_ptr(), dmix.shape[1],
-                                        ws.data_ptr(), ws.numel() * 4, _ptr(fwd_ws), B, T, H, K, V, chunk_size, n_chunks,
-                                        plan.table.data_ptr(), scale, dt, flags, _stream())
-        _lib.check(rc, "mhla_causal_varlen_bwd")
-        return dq, dk, dv, dmix
-    ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, dt, flags)[1], q.device)
-    rc = lib.mhla_causal_bwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(dout),
-                             _view(dq), _view(dk), _view(dv), dmix.data_ptr(), dmix.shape[1],
-                             ws.data_ptr(), ws.numel() * 4, _ptr(fwd_ws), B, T, H, K, V, chunk_size, scale, dt, flags, _stream())
-    _lib.check(rc, "mhla_causal_bwd")
+    ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, dt, flags, None if plan is None else n_chunks)[1], q.device)
+    _causal_call("bwd", plan, _view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(dout), _view(dq), _view(dk), _view(dv),
+                 dmix.data_ptr(), dmix.shape[1], ws.data_ptr(), ws.numel() * 4, _ptr(fwd_ws), B, T, H, K, V, chunk_size, scale, dt, flags,
+                 _stream())
     return dq, dk, dv, dmix
 
 
 class _Causal(torch.autograd.Function):
+    """`plan`: None, or the CausalVarlenPlan of a pack -- `mix` is then the plan's effective matrix [n, n] (a differentiable function
+    of the mixing matrix) and the gradient returned for it is the library's dmix_eff."""
+
     @staticmethod
     @_device_guard
-    def forward(ctx, q, k, v, mix, chunk_size, scale, flags, keep_limit):
-        lib = _lib.load()
-        _require_gpu(q, k, v, mix)
+    def forward(ctx, q, k, v, mix, chunk_size, scale, flags, keep_limit, plan):
+        _lib.load()   # (a missing library is reported before anything else)
+        table, n_chunks = (None, None) if plan is None else (plan.table, plan.n_chunks)
+        _require_gpu(q, k, v, mix, table)
         B, T, H, K = q.shape
         V = v.shape[-1]
         n = _causal_check("mhla_causal", q, k, v, mix, chunk_size)
-        if mix.device != q.device or mix.dim() < 2 or mix.shape[1] < n:
+        if plan is None and (mix.device != q.device or mix.dim() < 2 or mix.shape[1] < n):
             raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)] with L >= {n} on {q.device}")
         q, k, v = _prep(q), _prep(k), _prep(v)
-        mixf = _mix2d(mix)
+        mixf = _mix2d(mix, n_chunks)
         out = _alloc_like_tokens(B, T, H, V, q)
-        ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, _dtype_code(q), flags)[0], q.device)
-        rc = lib.mhla_causal_fwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(out),
-                                 ws.data_ptr(), ws.numel() * 4, B, T, H, K, V, chunk_size, float(scale),
-                                 _dtype_code(q), flags, _stream())
-        _lib.check(rc, "mhla_causal_fwd")
+        ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, _dtype_code(q), flags, n_chunks)[0], q.device)
+        _causal_call("fwd", plan, _view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(out), ws.data_ptr(), ws.numel() * 4,
+                     B, T, H, K, V, chunk_size, float(scale), _dtype_code(q), flags, _stream())
         # keep the chunk summaries (S_j and their prefix mixes) for the backward unless they are very large
         keep = ws.numel() * 4 <= keep_limit and any(ctx.needs_input_grad[:4])
         ctx.save_for_backward(q, k, v, mixf, ws if keep else None)
-        ctx.cfg = (chunk_size, float(scale), mix.shape, mix.dtype, flags)
+        ctx.cfg = (chunk_size, float(scale), mix.shape, mix.dtype, flags, plan)
         return out
 
     @staticmethod
     @_device_guard
     def backward(ctx, dout):
         q, k, v, mixf, fwd_ws = ctx.saved_tensors
-        chunk_size, scale, mix_shape, mix_dtype, flags = ctx.cfg
-        dq, dk, dv, dmix = _causal_bwd(q, k, v, mixf, _prep(dout.to(q.dtype)), fwd_ws, chunk_size, scale, flags)
-        return dq, dk, dv, dmix.reshape(mix_shape).to(mix_dtype), None, None, None, None
+        chunk_size, scale, mix_shape, mix_dtype, flags, plan = ctx.cfg
+        dq, dk, dv, dmix = _causal_bwd(q, k, v, mixf, _prep(dout.to(q.dtype)), fwd_ws, chunk_size, scale, flags, plan)
+        return dq, dk, dv, dmix if plan is not None else dmix.reshape(mix_shape).to(mix_dtype), None, None, None, None, None
 
 
 class CausalVarlenPlan:
@@ -1085,41 +1082,6 @@ def _causal_varlen_args(what, q, mixing_matrix, cu_seqlens, chunk_size) -> Causa
     return plan
 
 
-class _CausalVarlen(torch.autograd.Function):
-    """_Causal over a pack: `mix` is the plan's effective matrix [n, n] (a differentiable function of the mixing matrix), the
-    gradient returned for it is the library's dmix_eff."""
-
-    @staticmethod
-    @_device_guard
-    def forward(ctx, q, k, v, mix, plan, scale, flags, keep_limit):
-        lib = _lib.load()
-        _require_gpu(q, k, v, mix, plan.table)
-        B, T, H, K = q.shape
-        V = v.shape[-1]
-        n, chunk_size = plan.n_chunks, plan.chunk_size
-        _causal_check("mhla_causal", q, k, v, mix, chunk_size)
-        q, k, v = _prep(q), _prep(k), _prep(v)
-        mixf = _mix2d(mix, n)
-        out = _alloc_like_tokens(B, T, H, V, q)
-        ws = _ws(_cs_varlen_plan(B, T, H, K, V, chunk_size, n, _dtype_code(q), flags)[0], q.device)
-        rc = lib.mhla_causal_varlen_fwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(out),
-                                        ws.data_ptr(), ws.numel() * 4, B, T, H, K, V, chunk_size, n, plan.table.data_ptr(),
-                                        float(scale), _dtype_code(q), flags, _stream())
-        _lib.check(rc, "mhla_causal_varlen_fwd")
-        keep = ws.numel() * 4 <= keep_limit and any(ctx.needs_input_grad[:4])
-        ctx.save_for_backward(q, k, v, mixf, ws if keep else None)
-        ctx.cfg = (plan, float(scale), flags)
-        return out
-
-    @staticmethod
-    @_device_guard
-    def backward(ctx, dout):
-        q, k, v, mixf, fwd_ws = ctx.saved_tensors
-        plan, scale, flags = ctx.cfg
-        dq, dk, dv, dmix = _causal_bwd(q, k, v, mixf, _prep(dout.to(q.dtype)), fwd_ws, plan.chunk_size, scale, flags, plan)
-        return dq, dk, dv, dmix, None, None, None, None
-
-
 def _causal_keep_limit(keep_state_limit: Optional[int]) -> int:
     return CAUSAL_KEEP_STATE_LIMIT_BYTES if keep_state_limit is None else int(keep_state_limit)
 
@@ -1163,16 +1125,16 @@ def mhla_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix
         scale = q.shape[-1] ** -0.5
     plan = _causal_varlen_args("mhla_causal", q, mixing_matrix, cu_seqlens, chunk_size) if cu_seqlens is not None else None
     if plan is not None and q.shape[1] > 0:
-        return _CausalVarlen.apply(q, k, v, plan.mix_eff(mixing_matrix), plan, scale, flags, keep_limit)
+        return _Causal.apply(q, k, v, plan.mix_eff(mixing_matrix), int(chunk_size), scale, flags, keep_limit, plan)
     if q.shape[0] == 0 or q.shape[1] == 0:   # empty batch / sequence
         return torch.zeros_like(v) + 0 * (q.sum() + k.sum() + mixing_matrix.sum()).to(v.dtype)
     nb = _MAX_GRID_BH // q.shape[2]
     if q.shape[0] > nb:   # see mhla_blockmix
-        return torch.cat([_Causal.apply(q[i:i + nb], k[i:i + nb], v[i:i + nb], mixing_matrix, int(chunk_size), scale, flags, keep_limit)
+        return torch.cat([_Causal.apply(q[i:i + nb], k[i:i + nb], v[i:i + nb], mixing_matrix, int(chunk_size), scale, flags, keep_limit, None)
                           for i in range(0, q.shape[0], nb)], dim=0)
     if _native_nodes():
         return torch.ops.mhla_amd.causal(q, k, v, mixing_matrix, int(chunk_size), float(scale), flags, keep_limit)
-    return _Causal.apply(q, k, v, mixing_matrix, int(chunk_size), scale, flags, keep_limit)
+    return _Causal.apply(q, k, v, mixing_matrix, int(chunk_size), scale, flags, keep_limit, None)
 
 
 def naive_chunk_simple_mhla_fixed(q, k, v, mixing_matrix, output_final_state: bool = False, chunk_size: int = 64,
@@ -1184,82 +1146,42 @@ def naive_chunk_simple_mhla_fixed(q, k, v, mixing_matrix, output_final_state: bo
 
 class _CausalNormGate(torch.autograd.Function):
     """Causal operator + per-head RMSNorm x swish gate as ONE node: the forward applies the epilogue inside the operator's
-    output kernel (mhla_causal_normgate_fwd); the backward is the norm's backward kernel followed by the operator's backward."""
+    output kernel (mhla_causal_normgate_fwd); the backward is the norm's backward kernel followed by the operator's backward.
+    `plan`: as _Causal takes it."""
 
     @staticmethod
     @_device_guard
-    def forward(ctx, q, k, v, mix, gate, weight, chunk_size, scale, norm_eps, flags, keep_limit):
-        lib = _lib.load()
-        _require_gpu(q, k, v, mix, gate, weight)
+    def forward(ctx, q, k, v, mix, gate, weight, chunk_size, scale, norm_eps, flags, keep_limit, plan):
+        _lib.load()
+        table, n_chunks = (None, None) if plan is None else (plan.table, plan.n_chunks)
+        _require_gpu(q, k, v, mix, gate, weight, table)
         B, T, H, K = q.shape
         V = v.shape[-1]
         _causal_check("mhla_causal_normgate", q, k, v, mix, chunk_size, gate)
         q, k, v = _prep(q), _prep(k), _prep(v)
         gate = _prep(gate) if gate is not None else None
-        mixf = _mix2d(mix)
+        mixf = _mix2d(mix, n_chunks)
         wf = _f32(weight)
         need_grad = any(ctx.needs_input_grad[:6])
         out = _alloc_like_tokens(B, T, H, V, q) if need_grad else None
         y = _alloc_like_tokens(B, T, H, V, q)
-        ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, _dtype_code(q), flags)[0], q.device)
-        rc = lib.mhla_causal_normgate_fwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view_or_null(out),
-                                          _view_or_null(gate), _ptr(wf), float(norm_eps), _view(y),
-                                          ws.data_ptr(), ws.numel() * 4, B, T, H, K, V, chunk_size, float(scale),
-                                          _dtype_code(q), flags, _stream())
-        _lib.check(rc, "mhla_causal_normgate_fwd")
+        ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, _dtype_code(q), flags, n_chunks)[0], q.device)
+        _causal_call("normgate_fwd", plan, _view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view_or_null(out),
+                     _view_or_null(gate), _ptr(wf), float(norm_eps), _view(y), ws.data_ptr(), ws.numel() * 4, B, T, H, K, V, chunk_size,
+                     float(scale), _dtype_code(q), flags, _stream())
         keep = ws.numel() * 4 <= keep_limit and need_grad
         ctx.save_for_backward(q, k, v, mixf, out, gate, wf, ws if keep else None)
-        ctx.cfg = (chunk_size, float(scale), float(norm_eps), mix.shape, mix.dtype, weight.dtype if weight is not None else None, flags)
+        ctx.cfg = (chunk_size, float(scale), float(norm_eps), mix.shape, mix.dtype, weight.dtype if weight is not None else None, flags, plan)
         return y
 
     @staticmethod
     @_device_guard
     def backward(ctx, dy):
         q, k, v, mixf, out, gate, wf, fwd_ws = ctx.saved_tensors
-        chunk_size, scale, norm_eps, mix_shape, mix_dtype, w_dtype, flags = ctx.cfg
+        chunk_size, scale, norm_eps, mix_shape, mix_dtype, w_dtype, flags, plan = ctx.cfg
         do, dg, dw = _rmsnorm_gate_bwd(out, gate.contiguous() if gate is not None else None, wf, dy, norm_eps, w_dtype)
-        dq, dk, dv, dmix = _causal_bwd(q, k, v, mixf, do, fwd_ws, chunk_size, scale, flags)
-        return dq, dk, dv, dmix.reshape(mix_shape).to(mix_dtype), dg, dw, None, None, None, None, None
-
-
-class _CausalNormGateVarlen(torch.autograd.Function):
-    """_CausalNormGate over a pack (see _CausalVarlen)."""
-
-    @staticmethod
-    @_device_guard
-    def forward(ctx, q, k, v, mix, gate, weight, plan, scale, norm_eps, flags, keep_limit):
-        lib = _lib.load()
-        _require_gpu(q, k, v, mix, gate, weight, plan.table)
-        B, T, H, K = q.shape
-        V = v.shape[-1]
-        n, chunk_size = plan.n_chunks, plan.chunk_size
-        _causal_check("mhla_causal_normgate", q, k, v, mix, chunk_size, gate)
-        q, k, v = _prep(q), _prep(k), _prep(v)
-        gate = _prep(gate) if gate is not None else None
-        mixf = _mix2d(mix, n)
-        wf = _f32(weight)
-        need_grad = any(ctx.needs_input_grad[:6])
-        out = _alloc_like_tokens(B, T, H, V, q) if need_grad else None
-        y = _alloc_like_tokens(B, T, H, V, q)
-        ws = _ws(_cs_varlen_plan(B, T, H, K, V, chunk_size, n, _dtype_code(q), flags)[0], q.device)
-        rc = lib.mhla_causal_varlen_normgate_fwd(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view_or_null(out),
-                                                 _view_or_null(gate), _ptr(wf), float(norm_eps), _view(y),
-                                                 ws.data_ptr(), ws.numel() * 4, B, T, H, K, V, chunk_size, n, plan.table.data_ptr(),
-                                                 float(scale), _dtype_code(q), flags, _stream())
-        _lib.check(rc, "mhla_causal_varlen_normgate_fwd")
-        keep = ws.numel() * 4 <= keep_limit and need_grad
-        ctx.save_for_backward(q, k, v, mixf, out, gate, wf, ws if keep else None)
-        ctx.cfg = (plan, float(scale), float(norm_eps), weight.dtype if weight is not None else None, flags)
-        return y
-
-    @staticmethod
-    @_device_guard
-    def backward(ctx, dy):
-        q, k, v, mixf, out, gate, wf, fwd_ws = ctx.saved_tensors
-        plan, scale, norm_eps, w_dtype, flags = ctx.cfg
-        do, dg, dw = _rmsnorm_gate_bwd(out, gate.contiguous() if gate is not None else None, wf, dy, norm_eps, w_dtype)
-        dq, dk, dv, dmix = _causal_bwd(q, k, v, mixf, do, fwd_ws, plan.chunk_size, scale, flags, plan)
-        return dq, dk, dv, dmix, dg, dw, None, None, None, None, None
+        dq, dk, dv, dmix = _causal_bwd(q, k, v, mixf, do, fwd_ws, chunk_size, scale, flags, plan)
+        return dq, dk, dv, dmix if plan is not None else dmix.reshape(mix_shape).to(mix_dtype), dg, dw, None, None, None, None, None, None
 
 
 def causal_normgate_fusable(q: torch.Tensor, v: torch.Tensor, chunk_size: int = 64, flags: int = 0, cu_seqlens=None) -> bool:
@@ -1268,11 +1190,11 @@ def causal_normgate_fusable(q: torch.Tensor, v: torch.Tensor, chunk_size: int = 
     mhla_causal takes it): the answer for the pack, by its chunk count."""
     if q.dtype not in _DTYPES or not (q.shape[0] > 0 and q.shape[1] > 0 and q.shape[0] * q.shape[2] <= _MAX_GRID_BH):
         return False
+    fn, pack = "mhla_causal_normgate_fusable", ()
     if cu_seqlens is not None:
         plan = cu_seqlens if isinstance(cu_seqlens, CausalVarlenPlan) else causal_varlen_plan(cu_seqlens, q.device, chunk_size)
-        return _lib.load().mhla_causal_varlen_normgate_fusable(q.shape[1], q.shape[-1], v.shape[-1], chunk_size, plan.n_chunks,
-                                                               _DTYPES[q.dtype], flags) == 1
-    return _lib.load().mhla_causal_normgate_fusable(q.shape[1], q.shape[-1], v.shape[-1], chunk_size, _DTYPES[q.dtype], flags) == 1
+        fn, pack = "mhla_causal_varlen_normgate_fusable", (plan.n_chunks,)
+    return getattr(_lib.load(), fn)(q.shape[1], q.shape[-1], v.shape[-1], chunk_size, *pack, _DTYPES[q.dtype], flags) == 1
 
 
 def mhla_causal_normgate(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor,
@@ -1288,20 +1210,16 @@ def mhla_causal_normgate(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixi
     flags = _causal_flags(summaries, False)
     if scale is None:
         scale = q.shape[-1] ** -0.5
+    plan = None
     if cu_seqlens is not None:
         if q.dim() != 4 or v.dim() != 4:
             raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
         plan = _causal_varlen_args("mhla_causal_normgate", q, mixing_matrix, cu_seqlens, chunk_size)
-        if not causal_normgate_fusable(q, v, chunk_size, flags, plan):
-            return rmsnorm_gate(mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries, keep_state_limit=keep_state_limit,
-                                            cu_seqlens=plan), gate, weight, norm_eps)
-        return _CausalNormGateVarlen.apply(q, k, v, plan.mix_eff(mixing_matrix), gate, weight, plan, scale, norm_eps, flags,
-                                           _causal_keep_limit(keep_state_limit))
-    if not causal_normgate_fusable(q, v, chunk_size, flags):
-        return rmsnorm_gate(mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries, keep_state_limit=keep_state_limit),
-                            gate, weight, norm_eps)
-    return _CausalNormGate.apply(q, k, v, mixing_matrix, gate, weight, int(chunk_size), scale, norm_eps, flags,
-                                 _causal_keep_limit(keep_state_limit))
+    if not causal_normgate_fusable(q, v, chunk_size, flags, plan):
+        return rmsnorm_gate(mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries, keep_state_limit=keep_state_limit,
+                                        cu_seqlens=plan), gate, weight, norm_eps)
+    return _CausalNormGate.apply(q, k, v, mixing_matrix if plan is None else plan.mix_eff(mixing_matrix), gate, weight, int(chunk_size), scale,
+                                 norm_eps, flags, _causal_keep_limit(keep_state_limit), plan)
 
 
 def naive_recurrent_mhla(q, k, v, mixing_matrix, chunk_size: int = 64, scale: Optional[float] = None,

@@ -354,7 +354,7 @@ def test_layer_isolates_sequences():
 
 
 def test_layer_bf16_takes_the_fused_varlen_node(monkeypatch):
-    """A bf16 layer with isolate_sequences hands the pack to the fused norm x gate node (_CausalNormGateVarlen), padded batch and
+    """A bf16 layer with isolate_sequences hands the pack to the fused norm x gate node (_CausalNormGate with the pack's plan), padded batch and
     explicit cu_seqlens alike.  What the layer passed to the operator is recorded, and the operator's y is held to
     oracle.rms_norm_swish_gate of the per-sequence oracle on exactly those tensors, with the reference layer's rounding of o:
     3u + 1e-3, the bound of test_fused_normgate / test_gpu_causal.run_normgate for this quantity."""
@@ -373,7 +373,7 @@ def test_layer_bf16_takes_the_fused_varlen_node(monkeypatch):
     for b, n in enumerate(lens):
         mask[b, T - n:] = 1
     seen, nodes = [], []
-    real_op, real_apply = fla.mhla_causal_normgate, ops._CausalNormGateVarlen.apply
+    real_op, real_apply = fla.mhla_causal_normgate, ops._CausalNormGate.apply
 
     def recording_op(q, k, v, mix, g, w, eps, **kw):
         y = real_op(q, k, v, mix, g, w, eps, **kw)
@@ -381,10 +381,10 @@ def test_layer_bf16_takes_the_fused_varlen_node(monkeypatch):
         return y
 
     def counting_apply(*a):
-        nodes.append(1)
+        nodes.extend(1 for x in a if isinstance(x, ops.CausalVarlenPlan))   # (the node's plan argument: None for a uniform call)
         return real_apply(*a)
     monkeypatch.setattr(fla, "mhla_causal_normgate", recording_op)
-    monkeypatch.setattr(ops._CausalNormGateVarlen, "apply", counting_apply)
+    monkeypatch.setattr(ops._CausalNormGate, "apply", counting_apply)
     packed_x = torch.cat([x[b, T - n:] for b, n in enumerate(lens)], 0).unsqueeze(0)
     cu = torch.tensor([0, lens[0], lens[0] + lens[1]], dtype=torch.int32, device=DEV)
     with torch.no_grad():

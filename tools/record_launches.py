@@ -1,13 +1,16 @@
 #!/usr/bin/env python
-"""Record the launch sequences of the block-mix C ABI on the host, without a GPU, to compare two trees (a refactor of the host layer
-must leave them identical):
+"""Record the launch sequences of the block-mix and causal C ABI on the host, without a GPU, to compare two trees (a refactor of the host
+layer must leave them identical):
   python tools/record_launches.py build TREE OUT_DIR   # copies TREE's csrc + include to OUT_DIR, replaces capi_common.hpp's launch() by a
-                                                       # logger that returns MHLA_OK, builds OUT_DIR/librec.so from the block-mix units
-  python tools/record_launches.py run OUT_DIR/librec.so 2> log   # drives the entry points with never-dereferenced aligned pointers
+                                                       # logger that returns MHLA_OK, builds OUT_DIR/librec.so from the block-mix and causal units
+  python tools/record_launches.py run OUT_DIR/librec.so [blockmix|causal|decode ...] 2> log   # drives the entry points (default: all three
+                                                       # sections) with never-dereferenced aligned pointers
 Every launch is one line on stderr: name string, the kernel's own symbol (dladdr: the exact template instantiation), grid, block, dynamic
-LDS size, stream and a hash of the argument bytes; every call's return code and message too.  `diff` the logs of the two trees.  The
-argument hash covers struct padding: build with RECORD_ZERO_INIT=1 (host pass with -ftrivial-auto-var-init=zero, which reaches named
-locals only) to compare it."""
+LDS size, stream and a hash of the argument bytes; every call's return code and message and every size / capability query's answer too.
+In the two causal units (the operator: the twelve mhla_causal_* / mhla_causal_varlen_* calls and queries; the decode state: its six entry
+points and three size queries) hipMemsetAsync is a logger as well -- one MEMSET line -- so the launches behind a memset are recorded.
+`diff` the logs of the two trees.  The argument hash covers struct padding: build with RECORD_ZERO_INIT=1 (host pass with
+-ftrivial-auto-var-init=zero, which reaches named locals only) to compare it."""
 import ctypes
 import itertools
 import os
@@ -27,9 +30,21 @@ int launch(K kernel, dim3 grid, dim3 block, size_t smem, hipStream_t stream, con
             block.x, block.y, block.z, smem, (void*)stream, h);
     return MHLA_OK;
 }
+inline hipError_t rec_memset(void* p, int value, size_t bytes, hipStream_t stream) {
+    fprintf(stderr, "MEMSET %p value=%d bytes=%zu st=%p\\n", p, value, bytes, (void*)stream);
+    return hipSuccess;
+}
+#ifdef RECORD_MEMSET
+#define hipMemsetAsync rec_memset
+#endif
 
 '''
-UNITS = ["capi", "capi_bm_f32", "capi_bm_bf16", "capi_bm_bf16hl", "capi_bm_f16", "capi_bm_wanpro"]
+UNITS = ["capi", "capi_bm_f32", "capi_bm_bf16", "capi_bm_bf16hl", "capi_bm_f16", "capi_bm_wanpro", "capi_causal", "capi_causal_state"]
+CAUSAL_ENTRIES = ("mhla_causal_fwd_ws_bytes", "mhla_causal_bwd_ws_bytes", "mhla_causal_normgate_fusable", "mhla_causal_fwd", "mhla_causal_normgate_fwd",
+                  "mhla_causal_bwd", "mhla_causal_varlen_fwd_ws_bytes", "mhla_causal_varlen_bwd_ws_bytes", "mhla_causal_varlen_normgate_fusable",
+                  "mhla_causal_varlen_fwd", "mhla_causal_varlen_normgate_fwd", "mhla_causal_varlen_bwd")
+DECODE_ENTRIES = ("mhla_causal_step_ws_bytes", "mhla_causal_state_init", "mhla_causal_step", "mhla_causal_step_ragged", "mhla_causal_step_dev",
+                  "mhla_causal_extend_ws_bytes", "mhla_causal_extend", "mhla_causal_extend_ragged_ws_bytes", "mhla_causal_extend_ragged")
 
 
 def build(tree, out):
@@ -43,22 +58,36 @@ def build(tree, out):
     base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++20", "-fPIC", '-DMHLA_BUILD_FLAGS="rec"', "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] + zero
     objs = [os.path.join(out, u + ".o") for u in UNITS]
     with ThreadPoolExecutor(len(UNITS)) as ex:
-        list(ex.map(lambda u: subprocess.run(base + ["-c", os.path.join(out, "mhla_amd", "csrc", u + ".hip"), "-o", os.path.join(out, u + ".o")], check=True, capture_output=True), UNITS))
+        list(ex.map(lambda u: subprocess.run(base + (["-DRECORD_MEMSET"] if u.startswith("capi_causal") else []) + ["-c", os.path.join(out, "mhla_amd", "csrc", u + ".hip"), "-o", os.path.join(out, u + ".o")],
+                                             check=True, capture_output=True), UNITS))
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", os.path.join(out, "librec.so"), "-ldl"], check=True)
 
 
-def run(path):
+def say(s):
+    sys.stderr.write(s + "\n"); sys.stderr.flush()
+
+
+def run(path, sections):
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     from mhla_amd import _lib as L
     lib = ctypes.CDLL(path)
     for name in ("mhla_last_error", "mhla_blockmix_fwd_ws_bytes", "mhla_blockmix_bwd_ws_bytes", "mhla_blockmix_fwd", "mhla_blockmix_bwd",
-                 "mhla_blockmix_rope_fwd", "mhla_blockmix_rope_bwd", "mhla_blockmix_wan_fwd", "mhla_blockmix_wan_pro_fwd"):
+                 "mhla_blockmix_rope_fwd", "mhla_blockmix_rope_bwd", "mhla_blockmix_wan_fwd", "mhla_blockmix_wan_pro_fwd") + CAUSAL_ENTRIES + DECODE_ENTRIES:
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = L.SIGNATURES[name]
+    for sec in sections or ("blockmix", "causal", "decode"):
+        print(sec, "calls", {"blockmix": run_blockmix, "causal": run_causal, "decode": run_decode}[sec](lib, L))
+
+
+P = 1 << 32   # fake device addresses: region i is P + (i << 28), 16-byte aligned, never dereferenced
+
+
+def at(i, off=0):
+    return P + (i << 28) + off
+
+
+def run_blockmix(lib, L):
     V = L.View
-    P = 1 << 32
-    def say(s):
-        sys.stderr.write(s + "\n"); sys.stderr.flush()
     def view(base, H, D, off=0):
         return V(base + off, 1 << 24, H * D, D)
     n = 0
@@ -106,8 +135,119 @@ def run(path):
                         rc = lib.mhla_blockmix_wan_pro_fwd(q, k, v, P + (17 << 28), P + (18 << 28), P + (19 << 28), P + (24 << 28), norm, W, M, c, s, 64, P + (15 << 28), 1e-6,
                                                            view(P + (16 << 28), 64, D), o, od, None, ws, f32ws, 1, 64, M, S2, D, dt, 1e-6, 0, 0x1000)
                         say(f"WAN_PRO rc={rc} {lib.mhla_last_error().decode() if rc else ''}")
-    print("calls", n)
+    return n
+
+
+class Calls:
+    """Calls an entry point and logs `TAG rc=... message`; counts the calls."""
+    def __init__(self, lib):
+        self.lib, self.n = lib, 0
+
+    def __call__(self, tag, fn, *args):
+        rc = getattr(self.lib, fn)(*args)
+        say(f"{tag} rc={rc} {self.lib.mhla_last_error().decode() if rc else ''}")
+        self.n += 1
+
+
+def run_causal(lib, L):
+    """The causal operator: uniform and packed forward, fused norm x gate forward and backward, with their size / capability queries."""
+    call = Calls(lib)
+    def view(i, H, D, off=0):
+        return L.View(at(i, off), 1 << 24, H * D, D)
+    NV = L.NULL_VIEW
+    FG, BF, FP = L.CAUSAL_FORCE_GENERIC, L.CAUSAL_BF16_SUMMARIES, L.CAUSAL_FP32_GRADE_SUMMARIES
+    mix, dmix, ws, bws, tab, nw = at(20), at(22), at(21), at(23), at(24), at(25)
+    grid = itertools.product((2, 256), (1, 63, 64, 65, 321, 8200, 16448), (4, 64, 128, 192, 256, 320), (4, 64, 192, 256, 384, 512, 576),
+                             (L.F32, L.BF16, L.F16), (0, FG, BF, FP, BF | FP, 64), (64, 32))
+    for H, T, K, Vd, dt, fl, chunk in grid:
+        n = (T + chunk - 1) // chunk
+        thin = H == 2 and chunk == 64 and fl in (0, FG)   # (the variants of a call on a thinner grid)
+        for mode in ("plain", "misaligned", "shortws", "smallld") if thin else ("plain",):
+            off = 8 if mode == "misaligned" else 0
+            q, k, do, dq, dk = (view(i, H, K, off) for i in (0, 1, 4, 5, 6))
+            v, o, y, g, dv = (view(i, H, Vd, off) for i in (2, 3, 8, 9, 7))
+            short, ld = int(mode == "shortws"), n - int(mode == "smallld")
+            fws, bwsz = lib.mhla_causal_fwd_ws_bytes(1, T, H, K, Vd, chunk, dt, fl), lib.mhla_causal_bwd_ws_bytes(1, T, H, K, Vd, chunk, dt, fl)
+            say(f"CAUSAL H={H} T={T} K={K} V={Vd} dt={dt} flags={fl} chunk={chunk} mode={mode} fws={fws} bws={bwsz} "
+                f"fusable={lib.mhla_causal_normgate_fusable(T, K, Vd, chunk, dt, fl)}")
+            tail = (1, T, H, K, Vd, chunk, 0.125, dt, fl, 0x1000)
+            call("FWD", "mhla_causal_fwd", q, k, v, mix, ld, o, ws, fws - short, *tail)
+            for gate, out in ((g, o), (g, NV), (NV, o), (NV, NV)):
+                call("NORMGATE", "mhla_causal_normgate_fwd", q, k, v, mix, ld, out, gate, nw, 1e-6, y, ws, fws - short, *tail)
+            call("NORMGATE_NOY", "mhla_causal_normgate_fwd", q, k, v, mix, ld, o, g, nw, 1e-6, NV, ws, fws, *tail)
+            for fw in (ws, None):
+                call("BWD", "mhla_causal_bwd", q, k, v, mix, ld, do, dq, dk, dv, dmix, ld, bws, bwsz - short, fw, *tail)
+            # packed sequences: the table's row count at, inside and outside its bounds; tables that are refused on the thinner grid
+            for nc in (n, n + 3, T, n - 1, T + 1) if thin else (n, n + 3):
+                for tb in (tab, None, tab + 4) if thin and mode == "plain" else (tab,):
+                    ld = nc - int(mode == "smallld")
+                    fws = lib.mhla_causal_varlen_fwd_ws_bytes(1, T, H, K, Vd, chunk, nc, dt, fl)
+                    bwsz = lib.mhla_causal_varlen_bwd_ws_bytes(1, T, H, K, Vd, chunk, nc, dt, fl)
+                    say(f"PACKED nc={nc} tab={tb and hex(tb)} fws={fws} bws={bwsz} fusable={lib.mhla_causal_varlen_normgate_fusable(T, K, Vd, chunk, nc, dt, fl)}")
+                    tail = (1, T, H, K, Vd, chunk, nc, tb, 0.125, dt, fl, 0x1000)
+                    call("VFWD", "mhla_causal_varlen_fwd", q, k, v, mix, ld, o, ws, fws - short, *tail)
+                    for gate, out in ((g, o), (NV, NV)):
+                        call("VNORMGATE", "mhla_causal_varlen_normgate_fwd", q, k, v, mix, ld, out, gate, nw, 1e-6, y, ws, fws - short, *tail)
+                    for fw in (ws, None):
+                        call("VBWD", "mhla_causal_varlen_bwd", q, k, v, mix, ld, do, dq, dk, dv, dmix, ld, bws, bwsz - short, fw, *tail)
+    return call.n
+
+
+def run_decode(lib, L):
+    """The decode state: init, the three steps and the two extensions.  Every call is made from one dict of arguments; a variant
+    overrides some of them (a null or misaligned pointer, a short workspace, every ldmix from 0 to past the capacity)."""
+    call = Calls(lib)
+    NV = L.NULL_VIEW
+    for (B, H), K, Vd, dt, cap in itertools.product(((2, 2), (4, 64)), (64, 128, 100, 6), (64, 192), (L.F32, L.BF16, L.F16), (1, 3, 5)):
+        def view(i, D, off=0):
+            return L.View(at(i, off), 1 << 24, H * D, D)
+        say(f"DECODE B={B} H={H} K={K} V={Vd} dt={dt} cap={cap} step_ws={lib.mhla_causal_step_ws_bytes(B, H, K, Vd, dt)}")
+        base = dict(q=view(0, K), k=view(1, K), v=view(2, Vd), out=view(3, Vd), y=view(8, Vd), gate=view(9, Vd), nw=at(25), mix=at(20), ld=cap + 1,
+                    S=at(10), P=at(11), Cur=at(12), pos_dev=at(13), full_dev=at(14), ntok_dev=at(15), cos=None, sin=None, ld_tab=K // 2, rows=64 * cap,
+                    fmap=0, ws=at(21), short=0, chunk=64)
+        variants = [("", {})]
+        if H == 2:   # (the variants on the smaller batch)
+            variants += [(f"{name}={'null' if o is None else 'off' + str(o)}", {name: None if o is None else base[name] + o})
+                         for name, offs in (("S", (None, 8)), ("P", (None, 8)), ("Cur", (None, 8)), ("pos_dev", (None, 2)), ("full_dev", (None, 2)),
+                                            ("ntok_dev", (None, 2)), ("ws", (None, 8)), ("mix", (None,))) for o in offs]
+            variants += [(f"out={int(o)} y={int(y)} gate={int(g)} nw={int(w)}", dict(out=base["out"] if o else NV, y=base["y"] if y else NV,
+                                                                                     gate=base["gate"] if g else NV, nw=base["nw"] if w else None))
+                         for o, y, g, w in itertools.product((0, 1), repeat=4) if not (o and y and g and w)]
+            variants += [("views+8", {n_: view(i, D, 8) for n_, i, D in (("q", 0, K), ("k", 1, K), ("v", 2, Vd), ("out", 3, Vd), ("y", 8, Vd), ("gate", 9, Vd))}),
+                         ("ws-1", dict(short=1)), ("chunk=32", dict(chunk=32))]
+            variants += [(f"ldmix={ld}", dict(ld=ld)) for ld in range(cap + 1)]
+        positions = sorted({-1, 0, 62, 63, 64, 127, 64 * cap - 1, 64 * cap})
+        for vname, over in variants:
+            a = dict(base, **over)
+            say(f"VARIANT {vname}")
+            state, epi = (a["mix"], a["ld"], a["S"], cap, a["P"], a["Cur"]), (a["out"], a["gate"], a["nw"], 1e-6, a["y"], a["ws"])
+            dims, step_ws = (B, H, K, Vd, a["chunk"], 0.125, dt, 0x1000), lib.mhla_causal_step_ws_bytes(B, H, K, Vd, dt) - a["short"]
+            for T in (0, 1, 63, 64, 65, 130, 64 * cap, 64 * cap + 1):
+                call(f"INIT T={T}", "mhla_causal_state_init", a["k"], a["v"], *state, B, T, H, K, Vd, a["chunk"], dt, 0x1000)
+            for pos in positions:
+                call(f"STEP pos={pos}", "mhla_causal_step", a["q"], a["k"], a["v"], *state, pos, *epi, step_ws, *dims)
+                for anyb in (0, 1):
+                    call(f"STEP_RAGGED max_pos={pos} any_boundary={anyb}", "mhla_causal_step_ragged", a["q"], a["k"], a["v"], *state, a["pos_dev"], pos, anyb,
+                         *epi, step_ws, *dims)
+            cs = at(16), at(17)
+            ropes = [("none", None, None, K // 2, 64 * cap), ("both", *cs, K // 2, 64 * cap), ("cos only", cs[0], None, K // 2, 64 * cap),
+                     ("sin only", None, cs[1], K // 2, 64 * cap), ("off8", cs[0] + 8, cs[1], K // 2, 64 * cap), ("off4", cs[0], cs[1] + 4, K // 2, 64 * cap),
+                     ("ld short", *cs, K // 2 - 4, 64 * cap), ("ld odd", *cs, K // 2 + 2, 64 * cap), ("rows short", *cs, K // 2, 64 * cap - 1),
+                     ("rows wide", *cs, K // 2 + 4, 1 << 31)]
+            for fmap, (rname, cos, sin, ldt, rows) in itertools.product((0, 1, 2, 3), ropes):
+                call(f"STEP_DEV fmap={fmap} rope={rname}", "mhla_causal_step_dev", a["q"], a["k"], a["v"], *state, a["pos_dev"], a["full_dev"], cos, sin, ldt, rows,
+                     fmap, *epi, step_ws, *dims)
+            for T in (1, 2, 63, 64, 65, 130, 65536):
+                for pos in positions:
+                    xws = lib.mhla_causal_extend_ws_bytes(B, T, H, K, Vd, pos, dt)
+                    call(f"EXTEND pos={pos} T={T} ws={xws}", "mhla_causal_extend", a["q"], a["k"], a["v"], *state, pos, T, *epi, xws - a["short"], *dims)
+                most = (T + 62) // 64
+                for max_end, later, close, left in itertools.product((-1, 0, 1, 63, 64, 65, 64 * cap, 64 * cap + 1), sorted({0, 1, most, most + 1}), (0, 1), (0, 1)):
+                    xws = lib.mhla_causal_extend_ragged_ws_bytes(B, T, H, K, Vd, later, dt)
+                    call(f"EXTEND_RAGGED T={T} max_end={max_end} max_later={later} any_close={close} left={left} ws={xws}", "mhla_causal_extend_ragged",
+                         a["q"], a["k"], a["v"], *state, a["pos_dev"], a["ntok_dev"], T, max_end, later, close, left, *epi, xws - a["short"], *dims)
+    return call.n
 
 
 if __name__ == "__main__":
-    build(sys.argv[2], sys.argv[3]) if sys.argv[1] == "build" else run(sys.argv[2])
+    build(sys.argv[2], sys.argv[3]) if sys.argv[1] == "build" else run(sys.argv[2], sys.argv[3:])
