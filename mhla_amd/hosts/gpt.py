@@ -49,15 +49,14 @@ class Block(nn.Module):
         self.mlp = GatedMLP(dim)
 
     def forward(self, x, cache=None, attention_mask=None, token_counts=None, cu_seqlens=None, varlen_plan=None):
+        kw = {}
         if cu_seqlens is not None or varlen_plan is not None:   # packed sequences (training): no cache
-            x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask, cu_seqlens=cu_seqlens, varlen_plan=varlen_plan)[0]
-        elif cache is None:
-            x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask)[0]
-        elif token_counts is None:
-            x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask, past_key_values=cache, use_cache=True)[0]
-        else:
-            x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask, past_key_values=cache, use_cache=True,
-                              token_counts=token_counts)[0]
+            kw = dict(cu_seqlens=cu_seqlens, varlen_plan=varlen_plan)
+        elif cache is not None:
+            kw = dict(past_key_values=cache, use_cache=True)
+            if token_counts is not None:
+                kw["token_counts"] = token_counts
+        x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask, **kw)[0]
         return x + self.mlp(self.mlp_norm(x))
 
 
@@ -104,10 +103,7 @@ class GPT_MHLA(nn.Module):
             token_counts = token_counts.tolist()   # (read once for all layers)
         x = self.embeddings(input_ids)
         for blk in self.layers:
-            if cu_seqlens is not None or plan is not None:
-                x = blk(x, cache, attention_mask, cu_seqlens=cu_seqlens, varlen_plan=plan)
-                continue
-            x = blk(x, cache, attention_mask) if token_counts is None else blk(x, cache, attention_mask, token_counts)
+            x = blk(x, cache, attention_mask, token_counts, cu_seqlens, plan)
         logits = self.lm_head(self.norm(x))
         if labels is None:
             return logits

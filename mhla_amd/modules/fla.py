@@ -14,7 +14,7 @@ ShortConvolution is a sibling fla module outside the MHLA hot path) is served by
 `ShortConvolution` with the reference's parameters and cache protocol (no HIP kernel: not on the path).
 """
 import warnings
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -205,6 +205,25 @@ def _elu1(x):
     return F.elu(x) + 1
 
 
+class _Call(NamedTuple):
+    """The kind of a `MHLA.forward` call, as `_classify_call` finds it."""
+    exact: bool                          # exact_decoding with use_cache and a cache: a prefill, or a step / extension on `state`
+    state: Optional[CausalState]         # the decode state this layer's cache entry holds (exact calls only)
+    ragged: bool                         # a left-padded prefill, or a call on a ragged state: every sequence at positions of its own
+    lengths: Optional[list]              # the left-padded prefill: tokens per sequence ...
+    keep: Optional[torch.Tensor]         # ... and its [B, T] mask of real tokens
+    token_counts: Optional[Tuple[int, ...]]   # validated; only on a cached ragged state
+    seen: int                            # tokens `state` held before the call
+
+
+class _RotaryRows(NamedTuple):
+    """Where `MHLA._rotary_rows` puts every token row of a call."""
+    positions: Optional[torch.Tensor]    # the rotary position of every row (long, flattened), None: seqlen_offset .. seqlen_offset + T
+    table_len: int                       # rows of the cos / sin tables the call needs
+    seqlen_offset: int
+    keep: Optional[torch.Tensor]         # token_counts: [B, T] mask of the rows each sequence takes
+
+
 class MHLA(nn.Module):
     def __init__(self, mode: str = "chunk", hidden_size: int = 1024, expand_k: float = 0.5, expand_v: float = 1.0,
                  num_heads: int = 4, num_kv_heads: Optional[int] = None, feature_map: Optional[str] = None,
@@ -312,8 +331,7 @@ class MHLA(nn.Module):
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 past_key_values=None, use_cache: Optional[bool] = False, output_attentions: Optional[bool] = False,
                 **kwargs: Dict):
-        dev_mode = self.exact_decoding and bool(use_cache) and getattr(past_key_values, "device_positions", False)
-        if dev_mode:
+        if self.exact_decoding and bool(use_cache) and getattr(past_key_values, "device_positions", False):
             entry = self._device_positioned_entry(hidden_states, past_key_values)
             if entry is not None:
                 return self._device_positioned_step(hidden_states, entry), None, past_key_values
@@ -331,52 +349,91 @@ class MHLA(nn.Module):
         last_state = None
         if past_key_values is not None and self.layer_idx is not None and len(past_key_values) > self.layer_idx:
             last_state = past_key_values[self.layer_idx]                      # :249-251
+        call = self._classify_call(hidden_states, attention_mask, past_key_values, use_cache, last_state, kwargs)
+        # (an exact call's mask has become the prefill's lengths, or is not read: a ragged state carries them)
+        attention_mask = None if call.exact else attention_mask
+        indices, cu_seqlens = None, kwargs.get("cu_seqlens", None)
+        if attention_mask is not None:
+            hidden_states, indices, cu_seqlens = self._unpad(hidden_states, attention_mask)
+        plan = None               # isolate_sequences: the pack's chunk table, handed to the operator as cu_seqlens=
+        if self.isolate_sequences and cu_seqlens is not None:
+            plan = kwargs.get("varlen_plan", None)
+            if plan is None:
+                plan = causal_varlen_plan(cu_seqlens, hidden_states.device)
+        q, k, v, conv_states = self._project(hidden_states, last_state, use_cache, cu_seqlens)
+        rows = self._rotary_rows(call, q, q_len, cu_seqlens, attention_mask, past_key_values)
+        q, k = self._featmap_rotary(q, k, rows, flat=call.ragged)
+        fused = self.use_output_gate and self.fuse_norm_and_gate and q_len > 64
+        if call.state is not None:
+            o, recurrent_state, fused = self._decode(q, k, v, hidden_states, call.state, call.token_counts)
+        elif call.exact:
+            o, recurrent_state, fused = self._exact_prefill(q, k, v, hidden_states, call.lengths, fused)
+        else:
+            initial_state = last_state["recurrent_state"] if last_state is not None else None
+            o, recurrent_state, fused = self._reference_operator(q, k, v, hidden_states, plan, fused, (batch_size, q_len), initial_state, use_cache)
+        self._update_cache(past_key_values, use_cache, call, recurrent_state, conv_states, q_len, q)
+        o = self._gate_and_project(o, hidden_states, fused)
+        if call.keep is not None:                                            # zeros at padding rows, as pad_input leaves them
+            o = o.masked_fill(~call.keep.unsqueeze(-1), 0)
+        if rows.keep is not None:
+            o = o.masked_fill(~rows.keep.unsqueeze(-1), 0)
+        if indices is not None:                                              # pad_input, :362-363
+            full = o.new_zeros(batch_size * q_len, o.shape[-1])
+            full.index_copy_(0, indices, o.squeeze(0))
+            o = full.reshape(batch_size, q_len, -1)
+        return o, None, past_key_values
+
+    def _classify_call(self, hidden_states, attention_mask, past_key_values, use_cache, last_state, kwargs) -> _Call:
+        """Which kind of call this is (see `_Call`), and every refusal that depends on the kind."""
+        batch_size, q_len, _ = hidden_states.shape
         exact = self.exact_decoding and bool(use_cache) and past_key_values is not None and hasattr(past_key_values, "update")
-        ragged_lengths = None     # a padded prefill: tokens per sequence (left-padded); `ragged`: this call is one, or continues one
         cached = last_state["recurrent_state"] if last_state is not None else None
-        ragged = exact and isinstance(cached, CausalState) and cached.lengths is not None
+        state = cached if exact and isinstance(cached, CausalState) else None
+        ragged = state is not None and state.lengths is not None
+        lengths = keep = None
         if exact:
             if self.layer_idx is None:
                 raise ValueError("MHLA(exact_decoding=True): the cache is indexed by layer_idx, which is None")
-            if attention_mask is not None and not ragged:   # (a ragged state carries the lengths: the mask is not read)
-                if not bool(attention_mask.all()):
-                    if isinstance(cached, CausalState):
-                        raise NotImplementedError("MHLA(exact_decoding=True): the cached decode state is uniform (all sequences share "
-                                                  "one length); a padding attention_mask goes with the prefill")
-                    m = attention_mask[:, -q_len:].to(hidden_states.device) != 0
-                    if self.use_short_conv:
-                        raise NotImplementedError("MHLA(exact_decoding=True): use_short_conv with a padding attention_mask")
-                    if m.shape != (batch_size, q_len) or bool((m[:, :-1] & ~m[:, 1:]).any()):
-                        raise NotImplementedError("MHLA(exact_decoding=True): a padding attention_mask must be left-padded, each row "
-                                                  f"zeros then ones over the {q_len} tokens of the call")
-                    ragged_lengths = m.sum(-1).tolist()
-                    ragged = True
-            attention_mask = None
-        indices = None
-        cu_seqlens = kwargs.get("cu_seqlens", None)
+            # (a ragged state carries the lengths: the mask is not read)
+            if attention_mask is not None and not ragged and not bool(attention_mask.all()):
+                if state is not None:
+                    raise NotImplementedError("MHLA(exact_decoding=True): the cached decode state is uniform (all sequences share "
+                                              "one length); a padding attention_mask goes with the prefill")
+                keep = attention_mask[:, -q_len:].to(hidden_states.device) != 0
+                if self.use_short_conv:
+                    raise NotImplementedError("MHLA(exact_decoding=True): use_short_conv with a padding attention_mask")
+                if keep.shape != (batch_size, q_len) or bool((keep[:, :-1] & ~keep[:, 1:]).any()):
+                    raise NotImplementedError("MHLA(exact_decoding=True): a padding attention_mask must be left-padded, each row "
+                                              f"zeros then ones over the {q_len} tokens of the call")
+                lengths, ragged = keep.sum(-1).tolist(), True
         # token_counts (not in the reference; through **kwargs, so its signature is kept): B ints in 0 .. q_len, honoured only on a
         # cached ragged decode state -- sequence b takes the LAST token_counts[b] rows of the call (right-aligned, as the left-padded
         # prefill), through mhla_causal_extend(counts=, left_padded=True): one launch chain whatever the counts
-        token_counts = kwargs.get("token_counts", None) if ragged and isinstance(cached, CausalState) else None
+        token_counts = kwargs.get("token_counts", None) if ragged and state is not None else None
         if token_counts is not None:
             if self.use_short_conv:
                 raise NotImplementedError("MHLA(exact_decoding=True): use_short_conv with token_counts")
             token_counts = tuple(int(n) for n in (token_counts.tolist() if isinstance(token_counts, torch.Tensor) else token_counts))
             if len(token_counts) != batch_size or any(n < 0 or n > q_len for n in token_counts):
                 raise ValueError(f"MHLA: token_counts={token_counts} must be {batch_size} ints in 0 .. {q_len}")
-        if attention_mask is not None:                                       # layers/mhla.py:253-256 (get_unpad_data)
-            m = attention_mask[:, -q_len:]
-            indices = torch.nonzero(m.flatten(), as_tuple=False).flatten()
-            cu_seqlens = F.pad(m.sum(-1, dtype=torch.int32).cumsum(0, dtype=torch.int32), (1, 0))
-            hidden_states = hidden_states.reshape(batch_size * q_len, -1).index_select(0, indices).unsqueeze(0)
+        return _Call(exact, state, ragged, lengths, keep, token_counts, state.seen if state is not None else 0)
+
+    @staticmethod
+    def _unpad(hidden_states, attention_mask):
+        """layers/mhla.py:253-256 (get_unpad_data): the real tokens of a padded batch as one packed sequence `[1, tokens, D]`, their
+        rows in the `[B * T]` layout and the pack's `cu_seqlens`."""
+        batch_size, q_len, _ = hidden_states.shape
+        m = attention_mask[:, -q_len:]
+        indices = torch.nonzero(m.flatten(), as_tuple=False).flatten()
+        cu_seqlens = F.pad(m.sum(-1, dtype=torch.int32).cumsum(0, dtype=torch.int32), (1, 0))
+        return hidden_states.reshape(batch_size * q_len, -1).index_select(0, indices).unsqueeze(0), indices, cu_seqlens
+
+    def _project(self, hidden_states, last_state=None, use_cache=False, cu_seqlens=None):
+        """q, k, v as `[B, T, H, .]` (through the short convolutions with `use_short_conv`, :258-279; grouped k / v heads
+        expanded, :290-292) and the convolutions' states (None without them)."""
         B, T, _ = hidden_states.shape
-        plan = None               # isolate_sequences: the pack's chunk table, handed to the operator as cu_seqlens=
-        if self.isolate_sequences and cu_seqlens is not None:
-            plan = kwargs.get("varlen_plan", None)
-            if plan is None:
-                plan = causal_varlen_plan(cu_seqlens, hidden_states.device)
         conv_states = None
-        if self.use_short_conv:                                              # :258-279
+        if self.use_short_conv:
             cq = ck = cv = None
             if last_state is not None and last_state.get("conv_state") is not None:
                 cq, ck, cv = last_state["conv_state"]
@@ -384,155 +441,142 @@ class MHLA(nn.Module):
             k, ck = self.k_conv1d(x=self.k_proj(hidden_states), cache=ck, output_final_state=use_cache, cu_seqlens=cu_seqlens)
             v, cv = self.v_conv1d(x=self.v_proj(hidden_states), cache=cv, output_final_state=use_cache, cu_seqlens=cu_seqlens)
             conv_states = (cq, ck, cv)
-            q = q.reshape(B, T, self.num_heads, self.head_k_dim)
         else:
-            q = self.q_proj(hidden_states).reshape(B, T, self.num_heads, self.head_k_dim)
-            k = self.k_proj(hidden_states)
-            v = self.v_proj(hidden_states)
-        if self.num_kv_groups > 1:                                           # :290-292 (repeat '(h g) d')
+            q, k, v = self.q_proj(hidden_states), self.k_proj(hidden_states), self.v_proj(hidden_states)
+        q = q.reshape(B, T, self.num_heads, self.head_k_dim)
+        if self.num_kv_groups > 1:                                           # (repeat '(h g) d')
             k = k.reshape(B, T, self.num_kv_heads, 1, self.head_k_dim).expand(-1, -1, -1, self.num_kv_groups, -1)
             v = v.reshape(B, T, self.num_kv_heads, 1, self.head_v_dim).expand(-1, -1, -1, self.num_kv_groups, -1)
-        k = k.reshape(B, T, self.num_heads, self.head_k_dim)
-        v = v.reshape(B, T, self.num_heads, self.head_v_dim)
+        return q, k.reshape(B, T, self.num_heads, self.head_k_dim), v.reshape(B, T, self.num_heads, self.head_v_dim), conv_states
+
+    def _rotary_rows(self, call, q, q_len, cu_seqlens, attention_mask, past_key_values) -> _RotaryRows:
+        """The rotary position of every token row (see `_RotaryRows`): packed sequences restart at every sequence start
+        (rotary.py:68-72 with cu_seqlens); with a padding mask AND a cache offset every sequence continues from its own length
+        (prepare_lens_from_mask, :305-309)."""
+        B, T = q.shape[:2]
         seqlen_offset = 0
         if past_key_values is not None and hasattr(past_key_values, "get_seq_length"):
             seqlen_offset = past_key_values.get_seq_length(self.layer_idx)    # :301-303
-        # rotary position of every token row: packed sequences restart at every sequence start (rotary.py:68-72 with cu_seqlens);
-        # with a padding mask AND a cache offset every sequence continues from its own length (prepare_lens_from_mask, :305-309)
-        positions = None
-        if ragged:
+        if cu_seqlens is None and not call.ragged:
+            return _RotaryRows(None, T + seqlen_offset, seqlen_offset, None)
+        tpos = torch.arange(T, device=q.device)
+        if call.ragged:
             # every sequence at positions of its own, in the [B, T] layout: row (b, t) is token t - pad_b of a padded prefill (padding
             # rows: position 0, their output is dropped), token pos_b + t of a later call (the state's device positions: no sync).
             # The tables are gathered per row, so q and k go through the rotary as one sequence of B T rows.
-            tpos = torch.arange(T, device=q.device)
-            if ragged_lengths is not None:
-                pads = T - torch.tensor(ragged_lengths, device=q.device)
-                positions, table_len = (tpos[None, :] - pads[:, None]).clamp_(min=0).flatten(), T
-            elif token_counts is not None:
-                # row t of sequence b is its token pos_b + (t - (T - n_b)); padding rows (t < T - n_b) are clamped: their output is dropped
-                pads = T - torch.tensor(token_counts, device=q.device)
-                count_mask = tpos[None, :] >= pads[:, None]
-                rel = (tpos[None, :] - pads[:, None]).clamp_(min=0)
-                positions, table_len = (cached.pos.long()[:, None] + rel).flatten(), cached.seen + T
-            else:
-                positions, table_len = (cached.pos.long()[:, None] + tpos[None, :]).flatten(), cached.seen + T
-            q, k = q.reshape(1, B * T, self.num_heads, self.head_k_dim), k.reshape(1, B * T, self.num_heads, self.head_k_dim)
-            seqlen_offset = 0
-        elif cu_seqlens is not None:
-            tpos = torch.arange(T, device=q.device)
-            cu = cu_seqlens.to(q.device).long()
-            seq = torch.searchsorted(cu, tpos, right=True) - 1
-            offs = seqlen_offset
-            if attention_mask is not None and seqlen_offset > 0:
-                offs = (attention_mask.sum(-1).to(q.device).long() - q_len)[seq]
-            positions = tpos - cu[seq] + offs
-        if not ragged:
-            table_len = T + seqlen_offset if positions is None else (
-                (int(attention_mask.shape[1]) if attention_mask is not None and seqlen_offset > 0 else T + seqlen_offset))
+            if call.lengths is not None:
+                pads = T - torch.tensor(call.lengths, device=q.device)
+                return _RotaryRows((tpos[None, :] - pads[:, None]).clamp_(min=0).flatten(), T, 0, None)
+            if call.token_counts is None:
+                return _RotaryRows((call.state.pos.long()[:, None] + tpos[None, :]).flatten(), call.state.seen + T, 0, None)
+            # row t of sequence b is its token pos_b + (t - (T - n_b)); padding rows (t < T - n_b) are clamped: their output is dropped
+            pads = T - torch.tensor(call.token_counts, device=q.device)
+            rel = (tpos[None, :] - pads[:, None]).clamp_(min=0)
+            return _RotaryRows((call.state.pos.long()[:, None] + rel).flatten(), call.state.seen + T, 0, tpos[None, :] >= pads[:, None])
+        cu = cu_seqlens.to(q.device).long()
+        seq = torch.searchsorted(cu, tpos, right=True) - 1
+        if attention_mask is None or seqlen_offset <= 0:
+            return _RotaryRows(tpos - cu[seq] + seqlen_offset, T + seqlen_offset, seqlen_offset, None)
+        offs = (attention_mask.sum(-1).to(q.device).long() - q_len)[seq]
+        return _RotaryRows(tpos - cu[seq] + offs, int(attention_mask.shape[1]), seqlen_offset, None)
+
+    def _featmap_rotary(self, q, k, rows, flat):
+        """Feature map (:297-299) and rotary (:311) of q and k at `rows`; `flat`: as one sequence of B T rows (ragged calls)."""
+        shape = q.shape
+        if flat:
+            q, k = q.reshape(1, shape[0] * shape[1], *shape[2:]), k.reshape(1, shape[0] * shape[1], *shape[2:])
         if self.head_k_dim % 8 == 0:
-            # feature map (:297-299) + rotary (:311) in one HIP kernel per tensor and direction
-            cos, sin = self.rotary._tables(table_len, q.device, q.dtype)
-            t_off = seqlen_offset
-            if positions is not None:   # per-token rows of the tables, gathered once
-                cos, sin, t_off = cos.index_select(0, positions), sin.index_select(0, positions), 0
-            q = featmap_rotary(q, cos, sin, self._fmap_name, t_off)
-            k = featmap_rotary(k, cos, sin, self._fmap_name, t_off)
+            # feature map + rotary in one HIP kernel per tensor and direction
+            cos, sin = self.rotary._tables(rows.table_len, q.device, q.dtype)
+            t_off = rows.seqlen_offset
+            if rows.positions is not None:   # per-token rows of the tables, gathered once
+                cos, sin, t_off = cos.index_select(0, rows.positions), sin.index_select(0, rows.positions), 0
+            q, k = featmap_rotary(q, cos, sin, self._fmap_name, t_off), featmap_rotary(k, cos, sin, self._fmap_name, t_off)
         else:
             if not getattr(self, "_warned_eager_rotary", False):
                 warnings.warn(f"MHLA: head_k_dim={self.head_k_dim} is not a multiple of 8: feature map and rotary run as eager "
-                              "PyTorch ops (about ten elementwise passes per tensor) instead of the fused HIP kernel", stacklevel=2)
+                              "PyTorch ops (about ten elementwise passes per tensor) instead of the fused HIP kernel", stacklevel=3)
                 self._warned_eager_rotary = True
             q, k = self.feature_map_q(q), self.feature_map_k(k)              # :297-299
-            q, k = self.rotary(q, k, seqlen_offset=seqlen_offset, max_seqlen=table_len, positions=positions)   # :311
-        if ragged:
-            q, k = q.reshape(B, T, self.num_heads, self.head_k_dim), k.reshape(B, T, self.num_heads, self.head_k_dim)
-        recurrent_state = cached
-        fused_epilogue = self.use_output_gate and self.fuse_norm_and_gate and q_len > 64
-        if exact and isinstance(recurrent_state, CausalState):
-            # decoding on the state the prefill (or the calls before) left: one exact step for one token, one extension for several
-            g = gn = None
-            if self.fuse_norm_and_gate:
-                g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
-                gn = self.g_norm_swish_gate
-            fused_epilogue = gn is not None
-            seen_before = recurrent_state.seen
-            advance = mhla_causal_step if T == 1 and token_counts is None else mhla_causal_extend
-            counted = {} if token_counts is None else {"counts": token_counts, "left_padded": True}
-            o = advance(q, k, v, self.mixing_matrix, recurrent_state, gate=g, norm_weight=gn.weight if gn is not None else None,
-                        norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None, **counted)
-            if fused_epilogue:
-                o = o.reshape(B, T, self.value_dim)
-        elif ragged_lengths is not None:
-            # padded prefill: the operator (and the fused epilogue) over every sequence's real tokens alone, zeros elsewhere -- run by
-            # run of adjacent sequences of equal length, as mhla_causal_prefill(lengths=, left_padded=True) does
-            if fused_epilogue:
-                g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
-                gn = self.g_norm_swish_gate
-                o = q.new_zeros(B, T, self.num_heads, self.head_v_dim)
-                for i, j, n in _runs(ragged_lengths, B):
-                    if n:
-                        o[i:j, T - n:] = mhla_causal_normgate(q[i:j, T - n:], k[i:j, T - n:], v[i:j, T - n:], self.mixing_matrix, g[i:j, T - n:],
-                                                              gn.weight, gn.eps, summaries=self.summaries)
-                o = o.reshape(B, T, self.value_dim)
-                recurrent_state = mhla_causal_state(k, v, self.mixing_matrix, lengths=ragged_lengths, left_padded=True)
-            else:
-                o, recurrent_state = mhla_causal_prefill(q, k, v, self.mixing_matrix, summaries=self.summaries, lengths=ragged_lengths,
-                                                         left_padded=True)
-        elif exact:
-            # prefill: the chunk operator for the output (any length: the single-chunk case for <= 64 tokens), and the decode state
-            if fused_epilogue:
-                g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
-                gn = self.g_norm_swish_gate
-                o = mhla_causal_normgate(q, k, v, self.mixing_matrix, g, gn.weight, gn.eps, summaries=self.summaries).reshape(B, T, self.value_dim)
-            else:
-                o = mhla_causal(q, k, v, self.mixing_matrix, summaries=self.summaries)
-            recurrent_state = mhla_causal_state(k, v, self.mixing_matrix)
-        elif fused_epilogue:
+            q, k = self.rotary(q, k, seqlen_offset=rows.seqlen_offset, max_seqlen=rows.table_len, positions=rows.positions)   # :311
+        return (q.reshape(shape), k.reshape(shape)) if flat else (q, k)
+
+    def _fused_gate(self, hidden_states):
+        """`(g [B, T, H, V], the norm module)` for an operator that applies norm x gate itself; `(None, None)` unless `fuse_norm_and_gate`."""
+        if not self.fuse_norm_and_gate:
+            return None, None
+        return self.g_proj(hidden_states).reshape(*hidden_states.shape[:2], self.num_heads, self.head_v_dim), self.g_norm_swish_gate
+
+    def _decode(self, q, k, v, hidden_states, state, token_counts):
+        """Decoding on the state the prefill (or the calls before) left: one exact step for one token, one extension for several."""
+        B, T = q.shape[:2]
+        g, gn = self._fused_gate(hidden_states)
+        advance = mhla_causal_step if T == 1 and token_counts is None else mhla_causal_extend
+        counted = {} if token_counts is None else {"counts": token_counts, "left_padded": True}
+        o = advance(q, k, v, self.mixing_matrix, state, gate=g, norm_weight=gn.weight if gn is not None else None,
+                    norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None, **counted)
+        return (o.reshape(B, T, self.value_dim) if gn is not None else o), state, gn is not None
+
+    def _exact_prefill(self, q, k, v, hidden_states, lengths, fused):
+        """Prefill: the chunk operator for the output (any length: the single-chunk case for <= 64 tokens), and the decode state.
+        `lengths` (a left-padded batch): the operator (and the fused epilogue) over every sequence's real tokens alone, zeros
+        elsewhere -- run by run of adjacent sequences of equal length, as mhla_causal_prefill(lengths=, left_padded=True) does."""
+        B, T = q.shape[:2]
+        mix = self.mixing_matrix
+        if not fused and lengths is not None:
+            return (*mhla_causal_prefill(q, k, v, mix, summaries=self.summaries, lengths=lengths, left_padded=True), False)
+        if not fused:
+            return mhla_causal(q, k, v, mix, summaries=self.summaries), mhla_causal_state(k, v, mix), False
+        g, gn = self._fused_gate(hidden_states)
+        if lengths is None:
+            o = mhla_causal_normgate(q, k, v, mix, g, gn.weight, gn.eps, summaries=self.summaries)
+            return o.reshape(B, T, self.value_dim), mhla_causal_state(k, v, mix), True
+        o = q.new_zeros(B, T, self.num_heads, self.head_v_dim)
+        for i, j, n in _runs(lengths, B):
+            if n:
+                o[i:j, T - n:] = mhla_causal_normgate(q[i:j, T - n:], k[i:j, T - n:], v[i:j, T - n:], mix, g[i:j, T - n:],
+                                                      gn.weight, gn.eps, summaries=self.summaries)
+        return o.reshape(B, T, self.value_dim), mhla_causal_state(k, v, mix, lengths=lengths, left_padded=True), True
+
+    def _reference_operator(self, q, k, v, hidden_states, plan, fused, padded_shape, initial_state, use_cache):
+        """The reference layer's operator call, and the `isolate_sequences` one (`plan`): a recurrent state only from the
+        token-recurrent form."""
+        B, T = q.shape[:2]
+        if fused:
             # operator + per-head RMSNorm x swish gate (:330-337 + :351-355) as one node: the epilogue runs in the operator's
             # output kernel where the shape allows, otherwise as the separate HIP kernel (mhla_causal_normgate decides)
-            g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
-            gn = self.g_norm_swish_gate
-            o = mhla_causal_normgate(q, k, v, self.mixing_matrix, g, gn.weight, gn.eps, summaries=self.summaries,
-                                     cu_seqlens=plan).reshape(B, T, self.value_dim)
-            recurrent_state = None
-        elif plan is not None:                                               # (isolate_sequences: the chunk operator whatever q_len)
-            o = mhla_causal(q, k, v, self.mixing_matrix, summaries=self.summaries, cu_seqlens=plan)
-            recurrent_state = None
-        elif q_len <= 64:                                                    # :247, :318-327: the token-recurrent form
-            if T > 64 and not getattr(self, "_warned_recurrent_packed", False):
-                warnings.warn(f"MHLA: a padded batch of {batch_size} x {q_len} tokens unpads to one packed sequence of {T} > 64 tokens; "
-                              "the recurrent branch then runs the multi-chunk chunk operator (the reference's recurrent form reads "
-                              "shifted states beyond the first chunk -- not replicated, see naive_recurrent_mhla)", stacklevel=2)
-                self._warned_recurrent_packed = True
-            o, recurrent_state = naive_recurrent_mhla(q, k, v, self.mixing_matrix, initial_state=recurrent_state,
-                                                      output_final_state=bool(use_cache))
-        else:                                                                # :330-337
-            o = mhla_causal(q, k, v, self.mixing_matrix, summaries=self.summaries)
-            recurrent_state = None
-        if dev_mode and isinstance(recurrent_state, CausalState):
-            recurrent_state = recurrent_state.to_ragged()
-        if past_key_values is not None and hasattr(past_key_values, "update"):   # :339-345
-            # (with token_counts the furthest sequence may have grown by fewer than q_len tokens: the cache counts what the state does)
-            entry = past_key_values.update(recurrent_state=recurrent_state, conv_state=conv_states if self.use_short_conv else None,
-                                           layer_idx=self.layer_idx, offset=q_len if token_counts is None else recurrent_state.seen - seen_before)
-            if dev_mode and isinstance(recurrent_state, CausalState):
-                # what the device-positioned steps read, made once: the matrix as this forward clamped it (generation does not change
-                # the weights), the tables of a row per position the state can reach, the norm weight in fp32
-                cap = recurrent_state.capacity_chunks
-                cos, sin = self.rotary._tables(64 * cap, q.device, q.dtype)
-                gn = self.g_norm_swish_gate if self.fuse_norm_and_gate else None
-                entry.update(dev_mix=_mix2d(self.mixing_matrix), dev_cos=cos[:64 * cap], dev_sin=sin[:64 * cap],
-                             dev_norm_weight=gn.weight.detach().float().contiguous() if gn is not None and gn.weight is not None else None)
-        o = self._gate_and_project(o, hidden_states, fused_epilogue)
-        if ragged_lengths is not None:                                       # zeros at padding rows, as pad_input leaves them
-            o = o.masked_fill(~m.unsqueeze(-1), 0)
-        if token_counts is not None:
-            o = o.masked_fill(~count_mask.unsqueeze(-1), 0)
-        if indices is not None:                                              # pad_input, :362-363
-            full = o.new_zeros(batch_size * q_len, o.shape[-1])
-            full.index_copy_(0, indices, o.squeeze(0))
-            o = full.reshape(batch_size, q_len, -1)
-        return o, None, past_key_values
+            g, gn = self._fused_gate(hidden_states)
+            o = mhla_causal_normgate(q, k, v, self.mixing_matrix, g, gn.weight, gn.eps, summaries=self.summaries, cu_seqlens=plan)
+            return o.reshape(B, T, self.value_dim), None, True
+        if plan is not None:                                                 # (isolate_sequences: the chunk operator whatever q_len)
+            return mhla_causal(q, k, v, self.mixing_matrix, summaries=self.summaries, cu_seqlens=plan), None, False
+        batch_size, q_len = padded_shape
+        if q_len > 64:                                                       # :330-337
+            return mhla_causal(q, k, v, self.mixing_matrix, summaries=self.summaries), None, False
+        if T > 64 and not getattr(self, "_warned_recurrent_packed", False):   # :247, :318-327: the token-recurrent form
+            warnings.warn(f"MHLA: a padded batch of {batch_size} x {q_len} tokens unpads to one packed sequence of {T} > 64 tokens; "
+                          "the recurrent branch then runs the multi-chunk chunk operator (the reference's recurrent form reads "
+                          "shifted states beyond the first chunk -- not replicated, see naive_recurrent_mhla)", stacklevel=3)
+            self._warned_recurrent_packed = True
+        return (*naive_recurrent_mhla(q, k, v, self.mixing_matrix, initial_state=initial_state, output_final_state=bool(use_cache)), False)
+
+    def _update_cache(self, cache, use_cache, call, recurrent_state, conv_states, q_len, like):
+        """:339-345; on a `DecodeCache(device_positions=True)` the state is stored ragged, with what the device-positioned steps read."""
+        if cache is None or not hasattr(cache, "update"):
+            return
+        dev = self.exact_decoding and bool(use_cache) and getattr(cache, "device_positions", False) and isinstance(recurrent_state, CausalState)
+        recurrent_state = recurrent_state.to_ragged() if dev else recurrent_state
+        # (with token_counts the furthest sequence may have grown by fewer than q_len tokens: the cache counts what the state does)
+        entry = cache.update(recurrent_state=recurrent_state, conv_state=conv_states, layer_idx=self.layer_idx,
+                             offset=q_len if call.token_counts is None else recurrent_state.seen - call.seen)
+        if dev:
+            # what the device-positioned steps read, made once: the matrix as this forward clamped it (generation does not change
+            # the weights), the tables of a row per position the state can reach, the norm weight in fp32
+            cap = recurrent_state.capacity_chunks
+            cos, sin = self.rotary._tables(64 * cap, like.device, like.dtype)
+            gn = self.g_norm_swish_gate if self.fuse_norm_and_gate else None
+            entry.update(dev_mix=_mix2d(self.mixing_matrix), dev_cos=cos[:64 * cap], dev_sin=sin[:64 * cap],
+                         dev_norm_weight=gn.weight.detach().float().contiguous() if gn is not None and gn.weight is not None else None)
 
     def _gate_and_project(self, o, hidden_states, fused_epilogue):
         """Norm and output gate (unless the operator's launch chain applied them already: `fused_epilogue`), then o_proj."""
@@ -573,21 +617,9 @@ class MHLA(nn.Module):
         Nothing here depends on a position or synchronises, the cache is not updated (the state advances in place, on the device),
         and `mixing_matrix.data` is NOT reassigned: the matrix the prefill clamped is read, since generation does not change the
         weights.  The whole call may be captured in a graph."""
-        B, T, _ = hidden_states.shape
-        q = self.q_proj(hidden_states).reshape(B, T, self.num_heads, self.head_k_dim)
-        k, v = self.k_proj(hidden_states), self.v_proj(hidden_states)
-        if self.num_kv_groups > 1:
-            k = k.reshape(B, T, self.num_kv_heads, 1, self.head_k_dim).expand(-1, -1, -1, self.num_kv_groups, -1)
-            v = v.reshape(B, T, self.num_kv_heads, 1, self.head_v_dim).expand(-1, -1, -1, self.num_kv_groups, -1)
-        k = k.reshape(B, T, self.num_heads, self.head_k_dim)
-        v = v.reshape(B, T, self.num_heads, self.head_v_dim)
-        g = gn = None
-        if self.fuse_norm_and_gate:
-            g = self.g_proj(hidden_states).reshape(B, T, self.num_heads, self.head_v_dim)
-            gn = self.g_norm_swish_gate
+        q, k, v, _ = self._project(hidden_states)
+        g, gn = self._fused_gate(hidden_states)
         o = mhla_causal_step_dev(q, k, v, entry["dev_mix"], entry["recurrent_state"], feature_map=self._fmap_name,
                                  rotary=(entry["dev_cos"], entry["dev_sin"]), gate=g, norm_weight=entry["dev_norm_weight"],
                                  norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None)
-        if gn is not None:
-            o = o.reshape(B, T, self.value_dim)
-        return self._gate_and_project(o, hidden_states, gn is not None)
+        return self._gate_and_project(o.reshape(*hidden_states.shape[:2], self.value_dim) if gn is not None else o, hidden_states, gn is not None)

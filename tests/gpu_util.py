@@ -225,6 +225,18 @@ def chunk_errors(got, want, chunk=64, dim=1):
     return per, ((g - w).abs().max() / w.abs().max()).item()
 
 
+def _fla_layer(**kw):
+    """The fla layer the decoding tests share: hidden 256, 2 heads (K = 64, V = 128), exact_decoding, seeded norm weight and mixing matrix."""
+    from mhla_amd import modules
+    torch.manual_seed(3)
+    m = modules.MHLA(mode="chunk", hidden_size=256, expand_k=0.5, expand_v=1.0, num_heads=2, feature_map="relu", norm_eps=1e-6,
+                     layer_idx=0, exact_decoding=True, **kw)
+    with torch.no_grad():
+        (m.g_norm_swish_gate if m.fuse_norm_and_gate else m.g_norm).weight.uniform_(0.5, 1.5)
+        m.mixing_matrix.copy_(torch.rand(32, 32).view(32, 32, 1, 1, 1, 1))
+    return m
+
+
 def poison():
     """Fill ~350 MB of device memory with NaN and free it again: the next torch.empty() calls of the ops (workspaces,
     outputs, gradients) start as NaN, and the registers of idle CUs hold NaN -- reads of memory or registers that were never

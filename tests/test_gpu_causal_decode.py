@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import load_golden, rel_err, rms_ratio
-from gpu_util import DEV, CAUSAL_CHUNK_TOL_H16, CAUSAL_TOL, TOL, check, check_chunks, poison
+from gpu_util import DEV, CAUSAL_CHUNK_TOL_H16, CAUSAL_TOL, TOL, check, check_chunks, poison, _fla_layer
 from oracle import mhla_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -334,17 +334,6 @@ def test_full_state_and_errors():
     assert raw(128, need) == EINVAL and b"the state holds 2" in lib.mhla_last_error()
     torch.cuda.synchronize()
     assert torch.equal(st.Cur, snap.Cur) and torch.equal(st.P, snap.P)
-
-
-def _fla_layer(**kw):
-    from mhla_amd import modules
-    torch.manual_seed(3)
-    m = modules.MHLA(mode="chunk", hidden_size=256, expand_k=0.5, expand_v=1.0, num_heads=2, feature_map="relu", norm_eps=1e-6,
-                     layer_idx=0, exact_decoding=True, **kw)
-    with torch.no_grad():
-        (m.g_norm_swish_gate if m.fuse_norm_and_gate else m.g_norm).weight.uniform_(0.5, 1.5)
-        m.mixing_matrix.copy_(torch.rand(32, 32).view(32, 32, 1, 1, 1, 1))
-    return m
 
 
 @pytest.mark.parametrize("opts", [{}, {"num_kv_heads": 1}, {"use_output_gate": False}], ids=["default", "gqa", "no-output-gate"])

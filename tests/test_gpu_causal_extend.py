@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from conftest import load_golden, rel_err, rms_ratio
-from gpu_util import DEV, CAUSAL_CHUNK_TOL_H16, CAUSAL_TOL, TOL, check, check_chunks, poison
+from gpu_util import DEV, CAUSAL_CHUNK_TOL_H16, CAUSAL_TOL, TOL, check, check_chunks, poison, _fla_layer
 from oracle import mhla_oracle as orc
 from test_extend_cpu import extend_ref
 
@@ -465,17 +465,6 @@ def test_launch_count_does_not_depend_on_the_tokens():
     _, s2 = _start(q, k, v, mix, 100)
     stepped = _launches(lambda: _steps(q, k, v, mix, s2, 3))
     assert stepped.get("k_cs_step") == 3 and sum(stepped.values()) >= 6, stepped   # at least two per token
-
-
-def _fla_layer(**kw):
-    from mhla_amd import modules
-    torch.manual_seed(3)
-    m = modules.MHLA(mode="chunk", hidden_size=256, expand_k=0.5, expand_v=1.0, num_heads=2, feature_map="relu", norm_eps=1e-6,
-                     layer_idx=0, exact_decoding=True, **kw)
-    with torch.no_grad():
-        (m.g_norm_swish_gate if m.fuse_norm_and_gate else m.g_norm).weight.uniform_(0.5, 1.5)
-        m.mixing_matrix.copy_(torch.rand(32, 32).view(32, 32, 1, 1, 1, 1))
-    return m
 
 
 def test_fla_layer_launch_count():

@@ -8,11 +8,11 @@ import functools
 import pytest
 import torch
 
-from gpu_util import DEV, CAUSAL_TOL, TOL, check, poison
+from gpu_util import DEV, CAUSAL_TOL, TOL, check, poison, _fla_layer
 from oracle import mhla_oracle as orc
 from test_extend_cpu import oracle_state
 from test_extend_ragged_cpu import TABLE, TABLE_CAP, TABLE_T, extend_ragged_ref, table_inputs, window
-from test_gpu_causal_extend import _close, _fla_layer, _launches
+from test_gpu_causal_extend import _close, _launches
 
 pytestmark = pytest.mark.gpu
 

@@ -11,7 +11,7 @@ import functools
 import pytest
 import torch
 
-from gpu_util import DEV, CAUSAL_TOL, TOL, check, poison
+from gpu_util import DEV, CAUSAL_TOL, TOL, check, poison, _fla_layer
 from neighbour_refs import featmap_rotary_ref
 from oracle import mhla_oracle as orc
 from test_gpu_causal_ragged import _check_state, _check_step_rows, _prefill, _seqs, _window
@@ -238,7 +238,6 @@ def test_fla_layer_device_positions_and_graph_replay():
     calls), and a captured layer step replayed against the eager device-positioned bits."""
     import mhla_amd
     from mhla_amd import modules
-    from test_gpu_causal_ragged import _fla_layer
     m = _fla_layer().to(DEV).to(torch.bfloat16).eval()
     lens, T0, n = (70, 33), 70, 3
     gen = torch.Generator().manual_seed(21)
