@@ -195,7 +195,7 @@ int bm_state(const BmPlan& p, const BmCall& c, const StateArgs& a) {
     }
     // (backward on h16 / p24, 16-bit tensors, D <= 64: the row dots come from G_i; two more LDS tiles)
     WITH_PF(p.fmt, return launch(sp::k_sp_state<ET, DT, TRANS, false, SNT, S16, PF>, g, dim3(SNT),
-                                 (PF && TRANS && sizeof(ET) == 2 && DT <= 4) ? sp::sp_state_rd_smem<DT>() : sp::sp_state_smem<DT>(), c.st, name, a));
+                                 (PF && TRANS && sizeof(ET) == 2 && DT <= 4) ? sp::sp_state_rd_smem<DT, sp::sp_payrd<ET, DT, PF>()>() : sp::sp_state_smem<DT>(), c.st, name, a));
     return MHLA_OK;
 }
 // KV / ksum / z, G and 1 / n: the forward, and the recompute leg of a backward that was handed no forward workspace
@@ -320,7 +320,7 @@ int bm_tok(const BmPlan& p, const BmCall& c, const TokArgs& t) {
     }
     if (p.rope) {
         if constexpr (std::is_same<ET, float>::value) {
-            WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, true, false, false, PF>, g, blk, sp::sp_tok_smem<DT, false>(), c.st, p.n_tok[0], t));
+            WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, true, false, false, PF>, g, blk, sp::sp_dq_smem<DT, false, sp::sp_payop<ET, DT, PF, true>()>(), c.st, p.n_tok[0], t));
                            return launch(sp::k_sp_bwd_dkv<ET, DT, true, false, PF>, g, blk, sp::sp_tok_smem<DT, false>(), c.st, p.n_tok[1], t));
         }
         return MHLA_OK;
@@ -330,9 +330,9 @@ int bm_tok(const BmPlan& p, const BmCall& c, const TokArgs& t) {
     // (h16 summaries, D <= 64, blocks of at most 64 tokens: a wave has one tile at the most -- the loop-free instantiation)
     constexpr bool ONE_BUILT = bm_h16_built<ET, DT, S16>() && DT <= 4;
     if (wq && ONE_BUILT && p.fmt == SF_H16 && bm_one_tile(c.S)) {
-        if constexpr (ONE_BUILT) RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, true, 2, true>, g, blk, sp::sp_tok_smem<DT, S16>(), c.st, p.n_tok[0], t));
-    } else if (wq) WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, true, PF>, g, blk, sp::sp_tok_smem<DT, S16>(), c.st, p.n_tok[0], t)));
-    else WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, false, PF>, g, blk, sp::sp_tok_smem<DT, S16>(), c.st, p.n_tok[0], t)));
+        if constexpr (ONE_BUILT) RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, true, 2, true>, g, blk, sp::sp_dq_smem<DT, S16, sp::sp_payop<ET, DT, 2>()>(), c.st, p.n_tok[0], t));
+    } else if (wq) WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, true, PF>, g, blk, sp::sp_dq_smem<DT, S16, sp::sp_payop<ET, DT, PF>()>(), c.st, p.n_tok[0], t)));
+    else WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, false, PF>, g, blk, sp::sp_dq_smem<DT, S16, sp::sp_payop<ET, DT, PF>()>(), c.st, p.n_tok[0], t)));
     WITH_PF(p.fmt, return launch(sp::k_sp_bwd_dkv<ET, DT, false, S16, PF>, g, blk, sp::sp_tok_smem<DT, S16>(), c.st, p.n_tok[1], t));
     return MHLA_OK;
 }

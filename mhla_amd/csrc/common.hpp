@@ -197,6 +197,41 @@ __device__ __forceinline__ void h16_split8(const uint4& pay, float m, uint4& hi,
     lo = make_uint4(l[0], l[1], l[2], l[3]);
 }
 
+// A token row of a 16-bit tensor as the fp16 MFMA operand that meets an h16 PAYLOAD (the payload is an fp16 matrix already; decoding
+// payload * m into bf16 hi + lo planes is work the product does not need).  A bf16 or fp16 element times a power of two is an fp16
+// value, so (payload, scaled row) in ONE v_mfma_f32_16x16x32_f16 forms the same exact products as the bf16 hi / lo MFMAs did; the result
+// is accumulator * m / u, applied in fp32.  The row's up-scale u = 2^e puts its largest magnitude into [2^14, 2^15) -- the payload's own
+// range, so 64 products of a head dim sum to < 2^36 -- with the exponent field clamped to [1, 253] (u and h16_inv(u) both normal: rows
+// below 2^-112 keep fewer bits, nothing overflows); a zero row has u = 1.  Elements more than ~2^29 below the row's maximum lose bits
+// or flush in fp16: far below the fp32 accumulation noise of the row's product.  The maximum is taken over the lanes that share the
+// token with shuffles -- the operand layout's kg = lane >> 4 groups (lanes nl, nl + 16, nl + 32, nl + 48: FIRST = 16, LANES = 4) or the
+// LANES neighbouring lanes of a staging pass (FIRST = 1): EVERY lane of the wave must call this.
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+template <int FIRST = 16, int LANES = 4>
+__device__ __forceinline__ float tok16_scale(float lane_max) {   // lane_max: max |x| over the features of the row this lane holds
+    float mx = lane_max;
+#pragma unroll
+    for (int o = FIRST; o < FIRST * LANES; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    const unsigned e = (__float_as_uint(mx) >> 23) & 0xffu;
+    unsigned f = 268u - e;   // 127 + 14 - (e - 127)
+    f = f > 253u ? 253u : f;
+    return __uint_as_float((mx == 0.f ? 127u : f) << 23);
+}
+// NP pieces of 8 consecutive features of the lane's token row (padding -- rows past the block, features past D -- already zero) -> the
+// operands; returns u
+template <int NP>
+__device__ __forceinline__ float tok16_operands(const f32x4 (&x)[NP][2], f16x8 (&op)[NP]) {
+    float mx = 0.f;
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mx = fmaxf(mx, fmaxf(fabsf(x[p][0][i]), fabsf(x[p][1][i])));
+    const float u = tok16_scale(mx);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) op[p] = __builtin_bit_cast(f16x8, h16_pack8(x[p][0], x[p][1], u));
+    return u;
+}
+
 // Token-major view [B, N, H, D]; element strides; D contiguous.
 struct View {
     const void* ptr;

@@ -277,6 +277,42 @@ __device__ __forceinline__ void stage_mat_split(u16* __restrict__ Gh, u16* __res
     }
 }
 
+// Payload operands (common.hpp tok16_operands): where the summary is h16, the tensors are 16-bit, D <= 64 and the token operand of a
+// product is an exact tensor element, the staged matrix is ONE plane of the payload as stored and the token row a scaled fp16 operand --
+// one fp16 MFMA per step for the two or three bf16 ones, half the LDS, no decode.  -DSP_PAYLOAD_OPERANDS=0 (MHLA_BUILD_DEFINES) builds
+// the hi + lo form for A/B timing.  Used by k_sp_bwd_dq (its dO rows) and by the row dots of k_sp_state<1> (sp_payrd).  Not by k_sp_bwd_dkv:
+// built and measured (profiles/payload_operands.md) -- 126 -> 113 VGPRs still leave it four workgroups per CU, 61.7 -> 62.8 us at C2.  Not
+// by k_sp_out: its q rows may be relu'd or rotated by a run-time flag of the call, and it holds the most workgroups a CU takes already.
+#ifndef SP_PAYLOAD_OPERANDS
+#define SP_PAYLOAD_OPERANDS 1
+#endif
+template <typename T, int DT, int P24, bool ROPE = false>
+__host__ __device__ constexpr bool sp_payop() { return SP_PAYLOAD_OPERANDS && P24 == 2 && sizeof(T) == 2 && DT <= 4 && !ROPE; }
+// h16 row of a D x D summary -> ONE LDS plane [KP][mat_ld] of its payload, undecoded, in the mat_row layout (mat_row_read8 /
+// mat_tr_read8 then deliver fp16 operands: as_f16x8); rows and columns >= D zero.  Returns the row's multiplier m.  Through registers,
+// not global_load_lds_dwordx4: the LDS-DMA writes a wave's 64 pieces back to back, which allows neither the padded row stride nor
+// the zero rows and columns of a D < KP matrix, and the matrix is one round trip per workgroup that the token rows' loads already cover.
+template <int DT, int NT = NTHREADS>
+__device__ __forceinline__ float stage_mat_payload(u16* __restrict__ G, const float* __restrict__ base, long elem_off, int D, int tid) {
+    constexpr int LD = mat_ld<DT>(), CGS = Geo<DT>::CGS, RPP = NT / CGS, KP = Geo<DT>::KST * 32;
+    const int r0 = tid / CGS, cg = (tid % CGS) * 8;
+    constexpr int PASSES = (KP + RPP - 1) / RPP;
+    const char* rowp = reinterpret_cast<const char*>(base + elem_off);   // (elem_off counts floats: the row's start)
+    const float hm = gld<float>(rowp + 2 * D * D);
+    uint4 x16[PASSES];
+#pragma unroll
+    for (int u = 0; u < PASSES; ++u) {   // (every load unconditional, from a clamped position: see stage_mat_split)
+        const int r = min(r0 + RPP * u, D - 1), c = min(cg, D - 8);
+        x16[u] = gld<uint4>(rowp + 2 * (r * D + c));
+    }
+#pragma unroll
+    for (int u = 0; u < PASSES; ++u) {
+        const int r = r0 + RPP * u;
+        if (r < KP && cg < KP) *reinterpret_cast<uint4*>(G + mat_row<mat_new<DT>()>(r) * LD + cg) = (r < D && cg < D) ? x16[u] : make_uint4(0, 0, 0, 0);
+    }
+    return hm;
+}
+
 // stage_mat_split in two halves for 24-bit summaries staged in ONE batch (D = 128 by 512 threads: four passes): the loads are requested,
 // the workgroup multiplies a round of token tiles, then the pieces are committed (k_sp_out<.., FLAT>)
 template <int DT, int NT>
@@ -324,9 +360,15 @@ __host__ __device__ constexpr int sp_state_smem() {
 
 // MODE 1 on 16-bit tensors with 24-bit summaries and D <= 64 (RD): the row dots dO . O come from G_i -- two more tiles (G_i as hi / lo,
 // [64][72] bf16 each) and the partial dots of a 32-token chunk
-template <int DT> __host__ __device__ constexpr int sp_state_rd_smem() {   // (its token tiles keep the rows of DW + 8: four workgroups per CU)
-    return 4 * 32 * Geo<DT>::LDR * 2 + Geo<DT>::DW * 4 + 2 * Geo<DT>::KST * 32 * mat_ld<DT>() * 2 + 2 * 32 * 4;
+// ONEP (sp_payrd: h16 summaries, bf16 tensors): G_i is one plane of its payload and dO travels as fp16 rows in the Kl tile, which bf16
+// tensors leave unused -- the 10 KB pay for the conflict-free token layout (Geo::LD) and a fifth workgroup per CU
+template <int DT, bool ONEP = false> __host__ __device__ constexpr int sp_state_rd_smem() {   // (!ONEP: its token tiles keep the rows of DW + 8: four workgroups per CU)
+    return 4 * 32 * (ONEP ? Geo<DT>::LD : Geo<DT>::LDR) * 2 + Geo<DT>::DW * 4 + (ONEP ? 1 : 2) * Geo<DT>::KST * 32 * mat_ld<DT>() * 2 + 2 * 32 * 4;
 }
+// fp16 tensors keep the hi + lo form: their Kl tile holds q's lo part, and a fifth tile would cost the form its gain
+template <typename T, int DT, int P24>
+__host__ __device__ constexpr bool sp_payrd() { return sp_payop<T, DT, P24>() && std::is_same<T, bf16_t>::value; }
+static_assert(!SP_PAYLOAD_OPERANDS || 5 * sp_state_rd_smem<4, true>() <= 160 * 1024, "five k_sp_state<1> (row dots from G) workgroups per CU at D = 64");
 
 // MODE 0 (forward):  out = KV_j = K_j^T V_j; ksum_j; z_j                      x = k_num, y = v, kd = k_den, qd = q_den
 // MODE 1 (backward): out = dG_i = Q_i^T (dO_i / n_i); dn_i[s] = -(dO_i[s] . O_i[s]) / n_i[s]     x = q_num, y = dout, o = out
@@ -352,7 +394,8 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
     // stored output and its residual are not read, and the forward does not write the residual (capi_common.hpp bm_rowdots_from_g)
     constexpr bool RD = MODE == 1 && P24 && sizeof(T) == 2 && DT <= 4 && !ROPE;
     constexpr bool THIRD = TS && !RD;   // a third row stream exists
-    constexpr bool TN = !RD;   // the token tiles in the conflict-free layout (Geo::LD, mat_row)
+    constexpr bool PAYRD = RD && sp_payrd<T, DT, P24>();   // the row dots on G_i's payload and fp16 dO rows (kept in the Kl tile)
+    constexpr bool TN = !RD || PAYRD;   // the token tiles in the conflict-free layout (Geo::LD, mat_row)
     constexpr int DW = Geo<DT>::DW, LD = TN ? Geo<DT>::LD : Geo<DT>::LDR, CGS = Geo<DT>::CGS, RPP = NT / CGS, IT = 32 / RPP, NWV = NT / 64,
                   RT = (DT + NWV - 1) / NWV, TILE = 32 * LD;
     static_assert(IT >= 1 && RPP * IT == 32, "a 32-row chunk must be whole staging passes");
@@ -368,8 +411,8 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
     float* cs = reinterpret_cast<float*>(smem_raw);    // [RPP][DW] column-sum partials: over the tiles, after the last product
     float* vecd = reinterpret_cast<float*>(Vl + TILE); // [DW] ksum
     u16* Gh = reinterpret_cast<u16*>(vecd + DW);       // RD: G_i [d1][d2] hi, lo ([KST * 32][GLD] each), then the chunk's partial row dots [2][32]
-    u16* Gl = Gh + GT;
-    float* rdp = reinterpret_cast<float*>(Gl + GT);
+    u16* Gl = Gh + GT;                                 // (PAYRD: one plane)
+    float* rdp = reinterpret_cast<float*>(Gh + (PAYRD ? 1 : 2) * GT);
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nl = lane & 15, kg = lane >> 4;
     const int blk = blockIdx.x, bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H, S = a.S, D = a.D;
     const long p0 = (long)blk * S;
@@ -491,8 +534,9 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
         }
     };
     float ksp[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float nvc[IT];   // RD: 1 / n and the first row of the chunk whose row dots are in flight
+    float nvc[IT];   // RD: 1 / n (PAYRD: m 2^-e / n^2, the row's whole factor) and the first row of the chunk whose row dots are in flight
     int crowc = 0;
+    float gm = 1.f;  // PAYRD: the multiplier of G_i's payload
     auto commit = [&]() __attribute__((always_inline)) {
         __builtin_amdgcn_sched_barrier(0);   // (the fetched values are not touched before this point: hipcc would hoist `settle` above the products and wait there)
         settle();
@@ -512,6 +556,14 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
                 } else {
                     nvc[it] = nv[it];   // (the next fetch overwrites nv and crow before this chunk's dots are complete)
                     crowc = crow;
+                    if constexpr (PAYRD) {   // the dO row itself, scaled into fp16, for the row dots: the CGS threads of a row share its maximum
+                        float mx = 0.f;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) mx = fmaxf(mx, fmaxf(fabsf(vx[it][0][i]), fabsf(vx[it][1][i])));
+                        const float u = tok16_scale<1, CGS>(mx);
+                        *reinterpret_cast<uint4*>(Kl + off) = h16_pack8(vx[it][0], vx[it][1], u);
+                        nvc[it] = ((gm * nv[it]) * h16_inv(u)) * nv[it];   // dO . O = (dO . q G) / n, and dn = -(dO . O) / n
+                    }
                 }
                 vx[it][0] *= nv[it];
                 vx[it][1] *= nv[it];
@@ -548,7 +600,10 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
 
     fetch(0);
     if constexpr (RD) {   // (its loads travel with the first chunk's; the loop's first barrier covers the tiles)
-        if (a.normalize) stage_mat_split<DT, false, NT, P24>(Gh, Gl, a.g, ((long)bh * a.M + blk) * a.es, D, tid);
+        if (a.normalize) {
+            if constexpr (PAYRD) gm = stage_mat_payload<DT, NT>(Gh, a.g, ((long)bh * a.M + blk) * a.es, D, tid);
+            else stage_mat_split<DT, false, NT, P24>(Gh, Gl, a.g, ((long)bh * a.M + blk) * a.es, D, tid);
+        }
     }
     // one 32-token chunk: commit, request the next one (PF: there is one -- a compile-time fact of the call site, so that no branch sits
     // around the request: where such a branch joins hipcc waits for the loads in it), products
@@ -562,11 +617,11 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
             if (a.normalize) {
                 constexpr int KSTG = Geo<DT>::KST, CTH = (DT + 1) / 2;
                 const int tt = wave & 1, hf = wave >> 1;
-                bf16x8 bh_[KSTG], bl_[KSTG];
+                bf16x8 bh_[KSTG], bl_[KSTG];   // dO / n as hi + lo; PAYRD: bh_ = the fp16 dO rows
 #pragma unroll
                 for (int ks = 0; ks < KSTG; ++ks) {
-                    bh_[ks] = mat_row_read8<TN>(Vh, LD, tt * 16, ks * 32, lane);
-                    bl_[ks] = mat_row_read8<TN>(Vl, LD, tt * 16, ks * 32, lane);
+                    bh_[ks] = mat_row_read8<TN>(PAYRD ? Kl : Vh, LD, tt * 16, ks * 32, lane);
+                    if constexpr (!PAYRD) bl_[ks] = mat_row_read8<TN>(Vl, LD, tt * 16, ks * 32, lane);
                 }
                 float dot = 0.f;
 #pragma unroll
@@ -576,10 +631,15 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
                         f32x4 t4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                         for (int ks = 0; ks < KSTG; ++ks) {
-                            const bf16x8 gh = mat_row_read8<mat_new<DT>()>(Gh, GLD, ct * 16, ks * 32, lane), gl = mat_row_read8<mat_new<DT>()>(Gl, GLD, ct * 16, ks * 32, lane);
-                            t4 = mfma_bf16(gh, bh_[ks], t4);
-                            t4 = mfma_bf16(gl, bh_[ks], t4);
-                            t4 = mfma_bf16(gh, bl_[ks], t4);
+                            const bf16x8 gh = mat_row_read8<mat_new<DT>()>(Gh, GLD, ct * 16, ks * 32, lane);
+                            if constexpr (PAYRD) {
+                                t4 = fast::mfma_f16(fast::as_f16x8(gh), fast::as_f16x8(bh_[ks]), t4);
+                            } else {
+                                const bf16x8 gl = mat_row_read8<mat_new<DT>()>(Gl, GLD, ct * 16, ks * 32, lane);
+                                t4 = mfma_bf16(gh, bh_[ks], t4);
+                                t4 = mfma_bf16(gl, bh_[ks], t4);
+                                t4 = mfma_bf16(gh, bl_[ks], t4);
+                            }
                         }
                         const uint2 qr = *reinterpret_cast<const uint2*>(Kh + (tt * 16 + mat_row<TN>(nl)) * LD + ct * 16 + kg * 4);   // q[s][16 ct + 4 kg ..]: hi part
                         f32x4 q4 = {__uint_as_float(qr.x << 16), __uint_as_float(qr.x & 0xffff0000u), __uint_as_float(qr.y << 16), __uint_as_float(qr.y & 0xffff0000u)};
@@ -2362,10 +2422,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_dwt(const DwArgs a) {
 //   k_sp_bwd_dq : dQ_i = (dO_i / n_i) G_i^T (+ dz_i ksum_i^T) ; dksum_i = Qden_i^T dz_i ; dQden_i = dz_i ksum_i^T (split)
 //   k_sp_bwd_dkv: dK_j = V_j dKV_j^T (+ dksum_j) ; dV_j = K_j dKV_j ; dKden_j = 1 dksum_j^T (split)
 // -------------------------------------------------------------------------------------------------
+// k_sp_bwd_dq: the staged G_i (ONEP: one payload plane, sp_payop), the waves' dksum partials [4][DW] and ksum [DW] -- not the store
+// strips of k_sp_bwd_dkv below, which cost it a third of its workgroups per CU while it was launched with sp_tok_smem
+template <int DT, bool S16 = false, bool ONEP = false>
+__host__ __device__ constexpr int sp_dq_smem() {
+    return ((S16 || ONEP) ? 1 : 2) * Geo<DT>::KST * 32 * mat_ld<DT>() * 2 + Geo<DT>::DW * 4 * 4 + Geo<DT>::DW * 4;
+}
+static_assert(6 * sp_dq_smem<4, false, false>() <= 160 * 1024 && 6 * sp_dq_smem<4, false, true>() <= 160 * 1024, "six k_sp_bwd_dq workgroups per CU at D = 64");
 template <int DT, bool S16 = false>
 __host__ __device__ constexpr int sp_tok_smem() {
     // (+ k_sp_bwd_dkv's row staging for 16-bit tensors with rows of up to 128 bytes: [4 waves][dK, dV][16 tokens][DW + 8] 16-bit values)
-    return sp_out_smem<DT, S16>() + Geo<DT>::DW * 4 * 4 + Geo<DT>::DW * 4 + (DT <= 4 ? 4 * 2 * 16 * (Geo<DT>::DW + 8) * 2 : 0);
+    return sp_dq_smem<DT, S16>() + (DT <= 4 ? 4 * 2 * 16 * (Geo<DT>::DW + 8) * 2 : 0);
 }
 
 // A operand with the reduction index along the rows' columns: A[m][k] = T[c0 + m][k0 + 8 kg .. + 7]
@@ -2383,9 +2450,10 @@ template <typename T, int DT, bool ROPE = false, bool S16 = Sum16<T>::value, boo
 __global__ __launch_bounds__(NTHREADS, (DT <= 4 && WQ) ? 4 : 2) void k_sp_bwd_dq(const TokArgs a) {
     constexpr int LD = mat_ld<DT>(), DW = Geo<DT>::DW, KST = Geo<DT>::KST, TILE = KST * 32 * LD;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    constexpr bool PAYOP = sp_payop<T, DT, P24, ROPE>();   // G_i as ONE plane of its h16 payload, dO rows as scaled fp16 operands
     u16* Gh = reinterpret_cast<u16*>(smem_raw);
-    u16* Gl = Gh + TILE;                                  // not allocated for bf16 summaries
-    float* dksw = reinterpret_cast<float*>(Gh + (S16 ? 1 : 2) * TILE);   // [4 waves][DW]
+    u16* Gl = Gh + TILE;                                  // not allocated for bf16 summaries (or PAYOP)
+    float* dksw = reinterpret_cast<float*>(Gh + ((S16 || PAYOP) ? 1 : 2) * TILE);   // [4 waves][DW]
     float* ksum = dksw + 4 * DW;                          // [DW]
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nl = lane & 15, kg = lane >> 4;
     const int blk = blockIdx.x, bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H, S = a.S, D = a.D, M = a.M;
@@ -2447,7 +2515,9 @@ __global__ __launch_bounds__(NTHREADS, (DT <= 4 && WQ) ? 4 : 2) void k_sp_bwd_dq
     fetch(wave, cur, lk);   // in flight while G_i is staged
     if constexpr (!ONE) lk = look(wave + 4);
     const float ksum_v = gld<float>(a.normalize ? a.ksum + ((long)bh * M + blk) * D + min(tid, D - 1) : standin);
-    stage_mat_split<DT, S16, NTHREADS, P24>(Gh, Gl, a.g, ((long)bh * M + blk) * a.es, D, tid);
+    float gm = 1.f;   // PAYOP: the multiplier of G_i's payload
+    if constexpr (PAYOP) gm = stage_mat_payload<DT>(Gh, a.g, ((long)bh * M + blk) * a.es, D, tid);
+    else stage_mat_split<DT, S16, NTHREADS, P24>(Gh, Gl, a.g, ((long)bh * M + blk) * a.es, D, tid);
     if (tid < DW) ksum[tid] = (a.normalize && tid < D) ? ksum_v : 0.f;
     __syncthreads();
     f32x4 dksp[WQ ? 1 : DT], dksw8[WQ ? KST : 1][2];   // per-lane dksum partials: output layout / operand layout (WQ)
@@ -2459,14 +2529,28 @@ __global__ __launch_bounds__(NTHREADS, (DT <= 4 && WQ) ? 4 : 2) void k_sp_bwd_dq
     auto tile = [&]() __attribute__((always_inline)) {
         const float cninv = a.normalize ? cur.ninv : 1.f, cdz = (a.normalize && cur.live) ? cur.dz : 0.f;
         bf16x8 gh[KST], gl[KST];   // dO / n : B[k = d2][n = s]
+        f16x8 g16[KST];            // PAYOP: dO 2^e, and m 2^-e / n for the accumulators (1 / n in fp32: dO / n is not rounded to 16 bits)
+        float cscale = 1.f;
+        if constexpr (PAYOP) {
+            f32x4 x[KST][2];
 #pragma unroll
-        for (int ks = 0; ks < KST; ++ks) {
-            uint4 hi, lo;
-            const bool in = ks * 32 + kg * 8 < D;
-            const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-            split8((in ? raw4_to_f32(T{}, cur.g[ks][0]) : z4) * cninv, (in ? raw4_to_f32(T{}, cur.g[ks][1]) : z4) * cninv, hi, lo);
-            gh[ks] = as_bf16x8(hi);
-            gl[ks] = as_bf16x8(lo);
+            for (int ks = 0; ks < KST; ++ks) {
+                const bool in = ks * 32 + kg * 8 < D;
+                const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+                x[ks][0] = in ? raw4_to_f32(T{}, cur.g[ks][0]) : z4;
+                x[ks][1] = in ? raw4_to_f32(T{}, cur.g[ks][1]) : z4;
+            }
+            cscale = (gm * cninv) * h16_inv(tok16_operands<KST>(x, g16));
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < KST; ++ks) {
+                uint4 hi, lo;
+                const bool in = ks * 32 + kg * 8 < D;
+                const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+                split8((in ? raw4_to_f32(T{}, cur.g[ks][0]) : z4) * cninv, (in ? raw4_to_f32(T{}, cur.g[ks][1]) : z4) * cninv, hi, lo);
+                gh[ks] = as_bf16x8(hi);
+                gl[ks] = as_bf16x8(lo);
+            }
         }
         // gradient of one feature tile in output layout (4 features of the lane's token) and its q_den companion
         auto epilogue = [&](int ct, f32x4& c, f32x4& cd, const f32x2& rc, const f32x2& rs) {
@@ -2504,15 +2588,24 @@ __global__ __launch_bounds__(NTHREADS, (DT <= 4 && WQ) ? 4 : 2) void k_sp_bwd_dq
 #pragma unroll
             for (int ks = 0; ks < KST; ++ks) {
                 const bf16x8 a0h = mat_row_read8<mat_new<DT>()>(Gh, LD, ct * 16, ks * 32, lane), a1h = mat_row_read8<mat_new<DT>()>(Gh, LD, c1t * 16, ks * 32, lane);
-                c0 = mfma_bf16(a0h, gh[ks], c0);
-                c1 = mfma_bf16(a1h, gh[ks], c1);
-                if (!S16) {
-                    const bf16x8 a0l = mat_row_read8<mat_new<DT>()>(Gl, LD, ct * 16, ks * 32, lane), a1l = mat_row_read8<mat_new<DT>()>(Gl, LD, c1t * 16, ks * 32, lane);
-                    c0 = mfma_bf16(a0l, gh[ks], c0);
-                    c1 = mfma_bf16(a1l, gh[ks], c1);
+                if constexpr (PAYOP) {
+                    c0 = fast::mfma_f16(fast::as_f16x8(a0h), g16[ks], c0);
+                    c1 = fast::mfma_f16(fast::as_f16x8(a1h), g16[ks], c1);
+                } else {
+                    c0 = mfma_bf16(a0h, gh[ks], c0);
+                    c1 = mfma_bf16(a1h, gh[ks], c1);
+                    if (!S16) {
+                        const bf16x8 a0l = mat_row_read8<mat_new<DT>()>(Gl, LD, ct * 16, ks * 32, lane), a1l = mat_row_read8<mat_new<DT>()>(Gl, LD, c1t * 16, ks * 32, lane);
+                        c0 = mfma_bf16(a0l, gh[ks], c0);
+                        c1 = mfma_bf16(a1l, gh[ks], c1);
+                    }
+                    c0 = mfma_bf16(a0h, gl[ks], c0);
+                    c1 = mfma_bf16(a1h, gl[ks], c1);
                 }
-                c0 = mfma_bf16(a0h, gl[ks], c0);
-                c1 = mfma_bf16(a1h, gl[ks], c1);
+            }
+            if constexpr (PAYOP) {
+                c0 *= cscale;
+                c1 *= cscale;
             }
             f32x4 e0, e1 = {0.f, 0.f, 0.f, 0.f};
             epilogue(ct, c0, e0, rc0, rs0);
