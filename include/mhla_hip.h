@@ -362,6 +362,30 @@ int mhla_causal_step(mhla_view q, mhla_view k, mhla_view v, const float* mix, in
                      float* Cur, int64_t pos, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y,
                      void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype, void* stream);
 
+/* mhla_causal_varlen_state_init: mhla_causal_state_init for a pack (cu_seqlens) -- the ragged decode state of every sequence of
+ * one packed row k [1,T,H,K], v [1,T,H,V] in one launch chain (two launches, whatever n_seqs; added without a change of any existing
+ * signature or behaviour: MHLA_ABI_VERSION stays 9).  S [n_seqs][H][cap_chunks][K][V], P and Cur [n_seqs][H][K][V] as above.
+ *   chunk_tab_dev  the table of mhla_causal_varlen_fwd: device int32 [n_chunks][2] {first token row, rows in 1 .. 64}, 8-byte aligned
+ *   chunk_dst_dev  device int32 [n_chunks][2]: {sequence, index of the chunk within its sequence} of chunk c
+ *   seq_len_dev    device int32 [n_seqs]: the tokens of every sequence -- the ragged state's position array
+ *   max_len        host value: the longest sequence
+ * Per sequence s of n = seq_len_dev[s] tokens and per head, with nfull = n / 64: S[s][h][j] = K_j^T V_j of every finished chunk
+ * j < nfull (a last chunk of exactly 64 rows is finished); Cur[s][h] the K^T V of the ragged last chunk, zeros when n % 64 == 0
+ * (an empty sequence included); P[s][h] = sum_{j<nfull} mix[nfull][j] S[j] in ascending j, zeros when nfull == 0 or
+ * nfull == cap_chunks (the state is full).  P and Cur of every sequence are written by the call itself; rows of S beyond the
+ * finished chunks are neither read nor written.  Exact fp32 products, the kernels and the order of every sum of
+ * mhla_causal_state_init: the result is bit for bit what that call leaves for the sequence alone.  No atomics.
+ * The three arrays live on the device and are NOT read by the validation (host arithmetic only, before any launch): what
+ * mhla_causal_state_init checks of dimensions, views and state; n_seqs > 0; n_seqs * H <= 65535 (MHLA_ENOTSUP); T > 0 and
+ * n_chunks in ceil(T / 64) .. T (an all-empty pack is an all-zero state, the caller's to make); 0 <= max_len <= T;
+ * ceil(max_len / 64) <= cap_chunks; ldmix covers row min(max_len / 64, cap_chunks - 1) of mix; the arrays non-null and 4-byte
+ * aligned, the chunk table 8-byte.  Their contents are the caller's contract (the table as for mhla_causal_varlen_fwd; the
+ * destinations distinct); as a defence only, a seq_len_dev[s] outside 0 .. max_len leaves P and Cur of that sequence untouched,
+ * and a destination outside n_seqs / cap_chunks is not written. */
+int mhla_causal_varlen_state_init(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                                  int n_seqs, const int32_t* seq_len_dev, int max_len, int T, int H, int K, int V, int chunk,
+                                  int n_chunks, const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, int dtype, void* stream);
+
 /* mhla_causal_step_ragged: mhla_causal_step for a batch whose sequences are at positions of their own (added without a change of
  * any existing signature or behaviour: MHLA_ABI_VERSION stays 9).  `pos_dev`: device int32 [B], tokens seen by each sequence.
  * Sequence b behaves as in a batch of one: i = pos_dev[b] / chunk, its out row uses mix[i][i], and it closes its chunk -- S[i] = Cur,

@@ -85,6 +85,8 @@ SIGNATURES = {
     "mhla_causal_step_ws_bytes": (c_size_t, [c_int] * 5),
     "mhla_causal_state_init": (c_int, [View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                        c_int, c_int, c_int, c_int, c_void_p]),
+    "mhla_causal_varlen_state_init": (c_int, [View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                              c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "mhla_causal_step": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, View, View,
                                  c_void_p, c_float, View, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
                                  c_void_p]),

@@ -112,8 +112,20 @@ struct StateArgs {
 // whose MODE 2 reads the table, does; StateArgs and the block-mix modes know nothing of them.
 typedef int tab2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ tab2_t ld_tab(const tab2_t* tab, int i) { return *(const __attribute__((address_space(4))) tab2_t*)(tab + i); }
+__device__ __forceinline__ int ld_tab1(const int* tab, int i) { return *(const __attribute__((address_space(4))) int*)(tab + i); }   // (4-byte aligned tables)
 struct StateArgsVar : StateArgs {
     const tab2_t* tab;
+};
+// MODE 2 over packed sequences, each tile written straight into the decode state of its sequence (mhla_causal_varlen_state_init;
+// B = 1, so blockIdx.y is the head): dst[blk] = {sequence, index of the chunk within its sequence}, workgroup-uniform and read as
+// the table is.  A whole block (S rows) is a finished chunk and goes to Sq[seq][h][loc] (`cap` tiles per (seq, h)), a shorter one is
+// the sequence's open chunk and goes to Cur[seq][h].  An entry outside 0 .. nseq - 1 / 0 .. cap - 1 writes nothing (defence only:
+// the table is the caller's contract).  `out` and M are unused.
+struct StateArgsDst : StateArgsVar {
+    const int* dst;   // [blocks][2], 4-byte aligned
+    float* Sq;     // [nseq][H][cap][DX][DY]
+    float* Cur;    // [nseq][H][DX][DY]
+    int nseq, cap;
 };
 
 template <int DT>
@@ -162,7 +174,7 @@ __global__ __launch_bounds__(NTHREADS) void k_bm_state(const A a) {
         const int nsy = (a.DY + DP - 1) / DP;
         x0 = (blockIdx.z / nsy) * DP;
         y0 = (blockIdx.z % nsy) * DP;
-        if constexpr (std::is_same_v<A, StateArgsVar>) {   // packed sequences: the block's rows from the table
+        if constexpr (std::is_base_of_v<StateArgsVar, A>) {   // packed sequences: the block's rows from the table
             const tab2_t e = ld_tab(a.tab, blk);
             p0 = e.x;
             S = e.y;
@@ -236,7 +248,16 @@ __global__ __launch_bounds__(NTHREADS) void k_bm_state(const A a) {
     // KV_j / dG_i -> ws : C layout col = lane & 15, row = (lane >> 4) * 4 + r
     const int DX = MODE == 2 ? a.DX : D, DY = MODE == 2 ? a.DY : D;
     const float alpha = MODE == 2 ? a.alpha : 1.f;
-    float* ob = a.out + ((long)bh * a.M + blk) * DX * DY;
+    float* ob;
+    if constexpr (std::is_same_v<A, StateArgsDst>) {   // (MODE 2) the tile's place in its sequence's decode state
+        const tab2_t d = {ld_tab1(a.dst, 2 * blk), ld_tab1(a.dst, 2 * blk + 1)};
+        const bool whole = S == a.S;
+        if ((unsigned)d.x >= (unsigned)a.nseq || (whole && (unsigned)d.y >= (unsigned)a.cap)) return;   // (workgroup-uniform)
+        const long sh = (long)d.x * a.H + h;
+        ob = whole ? a.Sq + (sh * a.cap + d.y) * DX * DY : a.Cur + sh * DX * DY;
+    } else {
+        ob = a.out + ((long)bh * a.M + blk) * DX * DY;
+    }
     const int r16 = lane & 15, kq = lane >> 4;
 #pragma unroll
     for (int i = 0; i < NT; ++i) {

@@ -1,5 +1,5 @@
 // C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
-// (mhla_causal_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
@@ -99,6 +99,19 @@ int cst_xty(const mhla_view& k, const mhla_view& v, long tok0, long ntok, float*
                   "k_bm_state<2>", a);
 }
 
+// the chunks of a pack (B = 1), each tile into its sequence's state: a whole chunk to S[seq][h][loc], a ragged one to Cur[seq][h]
+template <typename T>
+int cst_xty_pack(const mhla_view& k, const mhla_view& v, float* S, int cap, float* Cur, int n_seqs, int n_chunks, const int* tab, const int* dst,
+                 int T_, int H, int K, int V, hipStream_t st) {
+    StateArgsDst a{};
+    a.x = cv(k); a.y = cv(v);
+    a.H = H; a.M = 0; a.S = CS; a.D = 64; a.DX = K; a.DY = V; a.T = T_; a.alpha = 1.f;
+    a.tab = (const tab2_t*)tab; a.dst = dst; a.Sq = S; a.Cur = Cur; a.nseq = n_seqs; a.cap = cap;
+    const int strips = ((K + 63) / 64) * ((V + 63) / 64);
+    return launch(k_bm_state<T, 4, 2, StateArgsDst>, dim3((unsigned)n_chunks, H, strips), dim3(NTHREADS), state_smem_floats<4>() * 4, st,
+                  "k_bm_state<2,dst>", a);
+}
+
 // the extension's workspace, in floats: P_c of every chunk touched after the first, then the fp32 rows the epilogue reads
 struct CxPlan {
     int64_t i, ilast, iend;   // chunk of the first / last new token, chunk open after the extension
@@ -160,6 +173,32 @@ int mhla_causal_state_init(mhla_view k, mhla_view v, const float* mix, int ldmix
     });
     if (!tail) RC(cst_zero_cur(Cur, B * H, E, st));
     return cst_roll(S, cap_chunks, P, Cur, open ? mix + (long)nfull * ldmix : nullptr, nfull, 0, B * H, E, st);
+}
+
+int mhla_causal_varlen_state_init(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                                  int n_seqs, const int32_t* seq_len_dev, int max_len, int T, int H, int K, int V, int chunk, int n_chunks,
+                                  const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, int dtype, void* stream) {
+    RC(cst_check(1, H, K, V, chunk, dtype));
+    if (n_seqs <= 0) return fail(MHLA_EINVAL, "n_seqs=%d must be positive", n_seqs);
+    if ((size_t)n_seqs * H > 65535) return fail(MHLA_ENOTSUP, "n_seqs*H=%zu exceeds grid limit 65535", (size_t)n_seqs * H);
+    if (T <= 0 || n_chunks <= 0) return fail(MHLA_EINVAL, "T=%d n_chunks=%d must be positive (an all-empty pack is an all-zero state)", T, n_chunks);
+    CHECK_VIEW(k); CHECK_VIEW(v);
+    RC(cst_check_state(S, cap_chunks, P, Cur));
+    if (n_chunks < (T + chunk - 1) / chunk || n_chunks > T)
+        return fail(MHLA_EINVAL, "n_chunks=%d outside ceil(T / %d)=%d .. T=%d", n_chunks, chunk, (T + chunk - 1) / chunk, T);
+    if (max_len < 0 || max_len > T) return fail(MHLA_EINVAL, "max_len=%d outside 0 .. T=%d", max_len, T);
+    if ((max_len + chunk - 1) / chunk > cap_chunks)
+        return fail(MHLA_EINVAL, "max_len=%d tokens need %d chunks, the state holds %d", max_len, (max_len + chunk - 1) / chunk, cap_chunks);
+    // sequence s reads row len[s] / 64 of mix up to its diagonal unless its state is then full: the longest one's row covers all
+    RC(cst_check_mix(mix, ldmix, std::min(max_len / chunk, cap_chunks - 1)));
+    RC(cst_check_dev("seq_len_dev", seq_len_dev));
+    RC(cst_check_dev("chunk_dst_dev", chunk_dst_dev));
+    if (!chunk_tab_dev || ((uintptr_t)chunk_tab_dev) % 8) return fail(MHLA_EINVAL, "chunk_tab_dev null or not 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_T(dtype, { RC(cst_xty_pack<ET>(k, v, S, cap_chunks, Cur, n_seqs, n_chunks, chunk_tab_dev, chunk_dst_dev, T, H, K, V, st)); });
+    const long E = (long)K * V;
+    const CsRollArgs r{S, P, Cur, nullptr, E, cap_chunks, 0, 0, seq_len_dev, mix, ldmix, max_len, H};
+    return launch(k_cs_roll<false, true>, dim3((unsigned)((E / 4 + 63) / 64), n_seqs * H), dim3(64), 0, st, "k_cs_roll_pack", r);
 }
 
 int mhla_causal_step(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,

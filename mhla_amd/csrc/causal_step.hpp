@@ -10,7 +10,7 @@
 //   k_cs_step        : the rank-1 update and the mat-vec, tiled over V (64 columns) and split over K (16 rows x `kr / 16` per
 //                      workgroup) so that B H = 4 still fills the machine; per-split partial sums of o -> fp32 workspace
 //   k_cs_step_finish : partials summed in split order, scale, one rounding; optional RMSNorm x swish gate over the head's V channels
-//   k_cs_roll        : the chunk boundary (and the prefix mix of a prefilled state)
+//   k_cs_roll        : the chunk boundary (and the prefix mix of a prefilled state; PACK: of every sequence of a prefilled pack)
 // Ragged batches (every sequence at a position of its own): the same kernels, instantiated with RAGGED, read pos[b] from a device
 // int32 [B] array and derive i, r per (b, h) workgroup -- the step its mix[i][i], the roll whether this sequence is on a boundary
 // at all.  Tiling, K split, row walk and the order of every sum are the uniform ones, so equal positions give the uniform bits.
@@ -282,6 +282,7 @@ struct CsRollArgs {
     long E;                // K V
     int cap, nj, commit;   // commit: S[nj - 1] = Cur, Cur = 0 first (the boundary); else S[0 .. nj) as they are (prefill)
     // RAGGED only: nj, commit and mixrow are derived per sequence from pos[b], the position of the token the step just took
+    // PACK only (the prefill of a pack, mhla_causal_varlen_state_init): from pos[b], the tokens of sequence b; max_pos: the longest
     const int* pos;        // [B]
     const float* mix;      // &mix[0][0]
     int ldmix, max_pos, H;
@@ -290,13 +291,25 @@ struct CsRollArgs {
 // grid (ceil(E / 4 / 64), B H), one wave per workgroup: P = sum_{j < nj} mixrow[j] S[j], ascending j
 // RAGGED: each (b, h) for itself -- not on a boundary (pos[b] % 64 != 63): nothing; else the commit with nj = i + 1 and the new P
 // from row i + 1 of mix, or P = 0 when i + 1 == cap (this sequence's state is full)
-template <bool RAGGED = false>
+// PACK: each (b, h) for itself, the prefix mix of a state whose finished chunks S[0 .. nj) were just written, nj = pos[b] / 64 --
+// no commit; P from row nj of mix, or P = 0 when nj == cap; Cur = 0 where the sequence has no open chunk (pos[b] % 64 == 0, an
+// empty sequence included: P = Cur = 0).  A pos[b] outside 0 .. max_pos leaves the sequence untouched (defence only, as RAGGED)
+template <bool RAGGED = false, bool PACK = false>
 __global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
+    static_assert(!(RAGGED && PACK), "one addressing mode");
     const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
     if (e >= a.E) return;   // (E % 4 == 0)
     const long bh = blockIdx.y;
     int nj = a.nj, commit = a.commit;
     const float* mixrow = a.mixrow;
+    if constexpr (PACK) {
+        const int p = a.pos[bh / a.H];
+        if (p < 0 || p > a.max_pos) return;
+        nj = p / CS;   // (<= cap: the host checked ceil(max_pos / 64) <= cap)
+        commit = 0;
+        mixrow = nj < a.cap ? a.mix + (long)nj * a.ldmix : nullptr;
+        if (p % CS == 0) gst<f32x4>(a.Cur + bh * a.E + e, f32x4{0.f, 0.f, 0.f, 0.f});
+    }
     if constexpr (RAGGED) {
         const int p = a.pos[bh / a.H];
         if (p < 0 || p > a.max_pos || p % CS != CS - 1) return;   // (outside 0 .. max_pos: defence only, see cst_pos)

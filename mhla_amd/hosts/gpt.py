@@ -50,10 +50,10 @@ class Block(nn.Module):
 
     def forward(self, x, cache=None, attention_mask=None, token_counts=None, cu_seqlens=None, varlen_plan=None):
         kw = {}
-        if cu_seqlens is not None or varlen_plan is not None:   # packed sequences (training): no cache
+        if cu_seqlens is not None or varlen_plan is not None:   # packed sequences: training (no cache), or the packed prefill
             kw = dict(cu_seqlens=cu_seqlens, varlen_plan=varlen_plan)
-        elif cache is not None:
-            kw = dict(past_key_values=cache, use_cache=True)
+        if cache is not None:
+            kw.update(past_key_values=cache, use_cache=True)
             if token_counts is not None:
                 kw["token_counts"] = token_counts
         x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask, **kw)[0]
@@ -87,15 +87,24 @@ class GPT_MHLA(nn.Module):
         prefill): sequence b takes only the LAST `token_counts[b]` tokens of `input_ids[b]` (right-aligned, as the prefill's
         padding) -- one slot decoding a token beside another taking a slice of a long prompt, a slot that sits the call out (0) -- in
         one launch chain per layer; handed to every layer.  The layers' outputs at padding rows are zeros, the logits there unspecified.
-        `cu_seqlens` (no cache; `input_ids` [1, T]): packed sequences, handed to every layer.  A model built with
+        `cu_seqlens` (`input_ids` [1, T]): packed sequences, handed to every layer.  A model built with
         `isolate_sequences=True` runs every sequence of the pack (or of a padded batch with `attention_mask`) alone; the
-        operator's chunk table (`causal_varlen_plan`, one host read of the lengths) is built here once for all layers."""
+        operator's chunk table (`causal_varlen_plan`, one host read of the lengths) is built here once for all layers.  With a
+        cache, `cu_seqlens` is the packed prefill: a model built with both `exact_decoding` and `isolate_sequences`, an EMPTY
+        `DecodeCache(packed_prefill=True)`; the logits are the pack's, [1, T], and later calls are [sequences, T'] on the ragged
+        state.  On a cache that holds a state it raises NotImplementedError."""
         if cache is not None and not self.exact_decoding:
             raise ValueError("GPT_MHLA.forward(cache=...) needs a model built with exact_decoding=True")
-        if cu_seqlens is not None and cache is not None:
-            raise NotImplementedError("GPT_MHLA.forward: cu_seqlens with a cache")
+        # a model built with exact_decoding and isolate_sequences prefills a pack into an EMPTY DecodeCache(packed_prefill=True):
+        # the layers' packed exact prefill (`input_ids` [1, T] with cu_seqlens, or a padded batch with attention_mask)
+        prefill = cache is not None and len(cache) == 0
+        packed = prefill and self.isolate_sequences and getattr(cache, "packed_prefill", False)
+        if cu_seqlens is not None and cache is not None and not packed:
+            raise NotImplementedError("GPT_MHLA.forward: cu_seqlens with a cache" + (
+                " that already holds a state" if not prefill else
+                " needs a model built with exact_decoding and isolate_sequences and a DecodeCache(packed_prefill=True)"))
         plan = None
-        if self.isolate_sequences and cache is None and (cu_seqlens is not None or attention_mask is not None):
+        if self.isolate_sequences and (cache is None or packed) and (cu_seqlens is not None or attention_mask is not None):
             lens = cu_seqlens if cu_seqlens is not None else F.pad(
                 attention_mask[:, -input_ids.shape[1]:].sum(-1, dtype=torch.int32).cumsum(0, dtype=torch.int32), (1, 0))
             plan = causal_varlen_plan(lens, input_ids.device)
@@ -114,14 +123,16 @@ class GPT_MHLA(nn.Module):
         """Greedy decoding: one prefill over `input_ids` [B, T], then one cached step per new token.  Returns the
         `max_new_tokens` new ids [B, max_new_tokens]; T + max_new_tokens must fit the mixing matrix (`max_seq_len`).
         `attention_mask` [B, T]: prompts of different lengths, left-padded to T (0 = padding); every sequence continues from
-        its own length.
+        its own length.  A model built with `exact_decoding` and `isolate_sequences` prefills them as a pack
+        (`DecodeCache(packed_prefill=True)`); the prompts stay left-padded, since the next token is read from `logits[:, -1]`.
         `graph=True`: the steps are device-positioned (`DecodeCache(device_positions=True)`) -- an eager prefill, one eager step
         that loads every kernel, then ONE whole-model step captured in a graph (static id and logits buffers, a single stream: a
         linear graph without parallel branches) and replayed once per token, and one `cache.sync()` at the end, which raises
         IndexError if a sequence was stepped beyond `max_seq_len` (its logits from there on came from zero attention rows).
         `return_logits=True`: `(ids, logits [B, max_new_tokens, vocab])`, the logits every id was picked from."""
         n = int(max_new_tokens)
-        cache = DecodeCache(device_positions=bool(graph))
+        # (both flags: a padded batch is prefilled as a pack -- no padding row through the operator, one state chain per layer)
+        cache = DecodeCache(device_positions=bool(graph), packed_prefill=self.exact_decoding and self.isolate_sequences)
         new, kept = [], []
 
         def pick(logits):

@@ -158,11 +158,17 @@ class DecodeCache:
     once per token.  The prefill leaves a ragged state plus, in the layer's entry, what the steps read: the clamped,
     lower-triangular fp32 mixing matrix and the rotary tables of 64 x capacity rows.  Neither the states' host mirrors nor this
     cache's token counts move during such steps (a replay runs no Python): `sync()` brings both up, with the one device-to-host
-    copy per layer of the whole generation."""
+    copy per layer of the whole generation.
+    `packed_prefill=True` (layers built with `exact_decoding=True` and `isolate_sequences=True`): the call on the empty cache may
+    carry `cu_seqlens` (B = 1) or an `attention_mask`, which the layer unpads to a pack -- a packed exact prefill: the operator
+    over the pack, every sequence alone, and the ragged decode state of all of them from one launch chain
+    (`mhla_causal_state(cu_seqlens=)`); later calls are `[sequences, T', D]` on that state.  Off (the default), such a call is
+    refused as before."""
 
-    def __init__(self, device_positions: bool = False):
+    def __init__(self, device_positions: bool = False, packed_prefill: bool = False):
         self.states, self._seen = [], []
         self.device_positions = bool(device_positions)
+        self.packed_prefill = bool(packed_prefill)
 
     def sync(self):
         """After device-positioned steps: `CausalState.sync()` on every layer's state and the tokens they advanced by added to
@@ -214,6 +220,7 @@ class _Call(NamedTuple):
     keep: Optional[torch.Tensor]         # ... and its [B, T] mask of real tokens
     token_counts: Optional[Tuple[int, ...]]   # validated; only on a cached ragged state
     seen: int                            # tokens `state` held before the call
+    packed: bool = False                 # the packed exact prefill (DecodeCache(packed_prefill=True)): a pack in, a ragged state out
 
 
 class _RotaryRows(NamedTuple):
@@ -265,7 +272,12 @@ class MHLA(nn.Module):
         `exact_decoding` evaluates) instead of over the pack as one sequence; calls of <= 64 tokens then use the chunk operator
         too and return no recurrent state.  `varlen_plan=` (through `**kwargs`): a `CausalVarlenPlan` built once for all layers.
         With `use_cache` a call that carries an `attention_mask` or `cu_seqlens` raises NotImplementedError -- the `exact_decoding`
-        prefill of a padded batch included."""
+        prefill of a padded batch included -- unless the layer has `exact_decoding` too and the cache is a
+        `DecodeCache(packed_prefill=True)`: the call on the empty cache is then a packed exact prefill (`cu_seqlens` with B = 1, or
+        an `attention_mask`, unpadded to a pack and re-padded on the way out): the operator over the pack, the ragged decode state
+        of every sequence from one launch chain, rotary rows per sequence, and the cache counts the longest sequence; later calls
+        are `[sequences, T', D]` on that state and read no mask.  `use_short_conv` there, and `cu_seqlens` on a cache that already
+        holds a state, raise NotImplementedError."""
         super().__init__()
         self.mode = mode
         self.hidden_size = hidden_size
@@ -341,7 +353,8 @@ class MHLA(nn.Module):
             assert len(attention_mask.shape) == 2, (
                 "Expected attention_mask as a 0-1 matrix with shape [batch_size, seq_len] for padding purposes "
                 "(0 indicating padding). Arbitrary attention masks of shape [batch_size, seq_len, seq_len] are not allowed.")
-        if self.isolate_sequences and use_cache and (attention_mask is not None or kwargs.get("cu_seqlens", None) is not None):
+        if (self.isolate_sequences and use_cache and (attention_mask is not None or kwargs.get("cu_seqlens", None) is not None)
+                and not (self.exact_decoding and getattr(past_key_values, "packed_prefill", False))):
             # (before the exact_decoding prefill drops the mask: that path is refused too, not taken silently)
             raise NotImplementedError("MHLA(isolate_sequences=True): an attention_mask or cu_seqlens with use_cache -- a decode state per "
                                       "packed sequence, and the exact_decoding prefill of a padded batch, are not implemented for it")
@@ -351,7 +364,7 @@ class MHLA(nn.Module):
             last_state = past_key_values[self.layer_idx]                      # :249-251
         call = self._classify_call(hidden_states, attention_mask, past_key_values, use_cache, last_state, kwargs)
         # (an exact call's mask has become the prefill's lengths, or is not read: a ragged state carries them)
-        attention_mask = None if call.exact else attention_mask
+        attention_mask = None if call.exact and not call.packed else attention_mask
         indices, cu_seqlens = None, kwargs.get("cu_seqlens", None)
         if attention_mask is not None:
             hidden_states, indices, cu_seqlens = self._unpad(hidden_states, attention_mask)
@@ -363,11 +376,11 @@ class MHLA(nn.Module):
         q, k, v, conv_states = self._project(hidden_states, last_state, use_cache, cu_seqlens)
         rows = self._rotary_rows(call, q, q_len, cu_seqlens, attention_mask, past_key_values)
         q, k = self._featmap_rotary(q, k, rows, flat=call.ragged)
-        fused = self.use_output_gate and self.fuse_norm_and_gate and q_len > 64
+        fused = self.use_output_gate and self.fuse_norm_and_gate and (q_len > 64 or call.packed)
         if call.state is not None:
             o, recurrent_state, fused = self._decode(q, k, v, hidden_states, call.state, call.token_counts)
         elif call.exact:
-            o, recurrent_state, fused = self._exact_prefill(q, k, v, hidden_states, call.lengths, fused)
+            o, recurrent_state, fused = self._exact_prefill(q, k, v, hidden_states, call.lengths, fused, plan if call.packed else None)
         else:
             initial_state = last_state["recurrent_state"] if last_state is not None else None
             o, recurrent_state, fused = self._reference_operator(q, k, v, hidden_states, plan, fused, (batch_size, q_len), initial_state, use_cache)
@@ -394,6 +407,20 @@ class MHLA(nn.Module):
         if exact:
             if self.layer_idx is None:
                 raise ValueError("MHLA(exact_decoding=True): the cache is indexed by layer_idx, which is None")
+            cu_seqlens = kwargs.get("cu_seqlens", None)
+            if self.isolate_sequences and getattr(past_key_values, "packed_prefill", False):
+                # DecodeCache(packed_prefill=True): the call on the empty cache that carries a pack (or a mask, unpadded to one) is the
+                # packed exact prefill; on a state, a mask is not read (as on any ragged state) and a pack is refused
+                if state is not None and cu_seqlens is not None:
+                    raise NotImplementedError("MHLA(isolate_sequences=True): cu_seqlens on a cache that already holds a decode state -- "
+                                              "packed new tokens are not implemented: pass them padded, [sequences, T, D], with token_counts=")
+                if state is None and (cu_seqlens is not None or attention_mask is not None):
+                    if self.use_short_conv:
+                        raise NotImplementedError("MHLA(isolate_sequences=True): use_short_conv with a packed exact prefill (a convolution "
+                                                  "state per packed sequence is not implemented)")
+                    if cu_seqlens is not None and batch_size != 1:
+                        raise ValueError(f"MHLA: cu_seqlens takes one packed row (B = 1), got B = {batch_size}")
+                    return _Call(True, None, False, None, None, None, 0, True)
             # (a ragged state carries the lengths: the mask is not read)
             if attention_mask is not None and not ragged and not bool(attention_mask.all()):
                 if state is not None:
@@ -517,12 +544,17 @@ class MHLA(nn.Module):
                     norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None, **counted)
         return (o.reshape(B, T, self.value_dim) if gn is not None else o), state, gn is not None
 
-    def _exact_prefill(self, q, k, v, hidden_states, lengths, fused):
+    def _exact_prefill(self, q, k, v, hidden_states, lengths, fused, plan=None):
         """Prefill: the chunk operator for the output (any length: the single-chunk case for <= 64 tokens), and the decode state.
         `lengths` (a left-padded batch): the operator (and the fused epilogue) over every sequence's real tokens alone, zeros
-        elsewhere -- run by run of adjacent sequences of equal length, as mhla_causal_prefill(lengths=, left_padded=True) does."""
+        elsewhere -- run by run of adjacent sequences of equal length, as mhla_causal_prefill(lengths=, left_padded=True) does.
+        `plan` (the packed exact prefill): the `isolate_sequences` operator over the pack, and the ragged state of every sequence
+        of it from one launch chain."""
         B, T = q.shape[:2]
         mix = self.mixing_matrix
+        if plan is not None:
+            o, _, fused = self._reference_operator(q, k, v, hidden_states, plan, fused, (B, T), None, True)
+            return o, mhla_causal_state(k, v, mix, cu_seqlens=plan), fused
         if not fused and lengths is not None:
             return (*mhla_causal_prefill(q, k, v, mix, summaries=self.summaries, lengths=lengths, left_padded=True), False)
         if not fused:
@@ -566,9 +598,10 @@ class MHLA(nn.Module):
             return
         dev = self.exact_decoding and bool(use_cache) and getattr(cache, "device_positions", False) and isinstance(recurrent_state, CausalState)
         recurrent_state = recurrent_state.to_ragged() if dev else recurrent_state
-        # (with token_counts the furthest sequence may have grown by fewer than q_len tokens: the cache counts what the state does)
+        # (with token_counts the furthest sequence may have grown by fewer than q_len tokens, and a packed prefill's q_len is the
+        # pack's: the cache counts what the state does -- after a packed prefill, the longest sequence)
         entry = cache.update(recurrent_state=recurrent_state, conv_state=conv_states, layer_idx=self.layer_idx,
-                             offset=q_len if call.token_counts is None else recurrent_state.seen - call.seen)
+                             offset=q_len if call.token_counts is None and not call.packed else recurrent_state.seen - call.seen)
         if dev:
             # what the device-positioned steps read, made once: the matrix as this forward clamped it (generation does not change
             # the weights), the tables of a row per position the state can reach, the norm weight in fp32

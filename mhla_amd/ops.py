@@ -1002,7 +1002,9 @@ class CausalVarlenPlan:
     cu        host tuple of the cumulative lengths
     n_chunks  chunks of the pack; max_chunks: of its longest sequence (rows of the mixing matrix it reads)
     table     device int32 [n_chunks, 2]: first token row and rows (1 .. chunk_size) of every chunk -- what the kernels read
-    loc, seq  device int64 [n_chunks]: the chunk's index within its sequence, and its sequence"""
+    loc, seq  device int64 [n_chunks]: the chunk's index within its sequence, and its sequence
+    dst       device int32 [n_chunks, 2]: (seq, loc) of every chunk -- where the packed prefill puts the chunk's K^T V in the ragged
+              decode state (`mhla_causal_state(cu_seqlens=)`)"""
 
     def __init__(self, cu, device, chunk_size: int = 64):
         self.cu = tuple(cu)
@@ -1019,6 +1021,7 @@ class CausalVarlenPlan:
         self.table = torch.tensor([starts, counts], dtype=torch.int32).t().contiguous().to(device)
         self.loc = torch.tensor(loc, dtype=torch.int64).to(device)
         self.seq = torch.tensor(seq, dtype=torch.int64).to(device)
+        self.dst = torch.tensor([seq, loc], dtype=torch.int32).t().contiguous().to(device)
         c = torch.arange(self.n_chunks, device=self.table.device)
         self._mask = ((self.seq[:, None] == self.seq[None, :]) & (c[None, :] <= c[:, None])).to(torch.float32)
 
@@ -1412,17 +1415,24 @@ def _causal_state_init(k, v, mix, state: CausalState):
 
 def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, chunk_size: int = 64,
                         scale: Optional[float] = None, *, summaries: str = "tf32", capacity_chunks: Optional[int] = None,
-                        lengths=None, left_padded: bool = False):
+                        lengths=None, left_padded: bool = False, cu_seqlens=None):
     """`(o, state)`: `o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries)` and the `CausalState`
     after these T tokens, from which `mhla_causal_step` continues one token at a time (T = 0: an empty state).  The state is
     built from k, v in exact fp32 products, independently of `summaries`; no autograd passes through it.
     capacity_chunks: chunks the state can hold (64 tokens each), default and at most the rows L of the mixing matrix.
     lengths, left_padded: a padded batch, as `mhla_causal_state` takes it -- the state is ragged, every sequence's rows of `o` are
-    those of `mhla_causal` over that sequence alone (one call per run of adjacent sequences of equal length), padding rows zero."""
+    those of `mhla_causal` over that sequence alone (one call per run of adjacent sequences of equal length), padding rows zero.
+    cu_seqlens: a pack (B = 1), as `mhla_causal` takes it -- `o` is the packed output `mhla_causal(..., cu_seqlens=)`, the state
+    the ragged one of `mhla_causal_state(..., cu_seqlens=)`, one sequence of the pack per batch entry; one plan serves both."""
     if q.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
     if int(chunk_size) != 64:
         raise ValueError(f"mhla_causal_prefill: chunk_size={chunk_size}, the decode state supports 64 only")
+    if cu_seqlens is not None:
+        # every refusal of the state half first, so that nothing is launched for a call that is refused
+        plan = _causal_state_pack_args("mhla_causal_prefill", k, v, mixing_matrix, cu_seqlens, lengths, left_padded, capacity_chunks)[0]
+        o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries, cu_seqlens=plan)
+        return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks, cu_seqlens=plan)
     if lengths is None:
         o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries)
         return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks)
@@ -1438,13 +1448,72 @@ def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixin
     return o, state
 
 
+def _causal_state_pack_args(fn, k, v, mixing_matrix, cu_seqlens, lengths, left_padded, capacity_chunks):
+    """The checks of a packed prefill state, all before the library is loaded or anything is launched; returns (plan, capacity)."""
+    if k.dim() != 4 or v.dim() != 4:
+        raise ValueError("k: [B, T, H, K], v: [B, T, H, V]")
+    if lengths is not None or left_padded:
+        raise ValueError(f"{fn}: cu_seqlens (a pack) excludes lengths= and left_padded= (a padded batch)")
+    B, T, H, K = k.shape
+    _check_like(k, fn, v=(v, (B, T, H, v.shape[-1])))
+    plan = _causal_varlen_args(fn, k, mixing_matrix, cu_seqlens, 64)
+    L = mixing_matrix.shape[0]
+    cap = L if capacity_chunks is None else int(capacity_chunks)
+    if not 0 < cap <= L:
+        raise ValueError(f"capacity_chunks={cap} must be in 1 .. {L} (rows of mixing_matrix)")
+    n_seqs = len(plan.cu) - 1
+    if n_seqs < 1:
+        raise ValueError(f"{fn}: cu_seqlens holds no sequence")
+    if n_seqs * H > _MAX_GRID_BH:
+        raise ValueError(f"{fn}: {n_seqs} sequences x H={H} heads exceed one launch's range of {_MAX_GRID_BH} (sequence, head) pairs: "
+                         "split the pack")
+    if plan.max_chunks > cap:
+        long = [i for i, n in enumerate(plan.lengths) if n > 64 * cap]
+        raise IndexError(f"{fn}: sequences {long} of lengths {[plan.lengths[i] for i in long]} need more than the {cap} chunks the "
+                         f"state holds ({64 * cap} tokens)")
+    if mixing_matrix.device != k.device or mixing_matrix.dim() < 2 or mixing_matrix.shape[1] < cap:
+        raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)] with L >= {cap} on {k.device}")
+    return plan, cap
+
+
+@_device_guard
+def _causal_state_init_pack(k, v, mix, state: CausalState, plan: CausalVarlenPlan):
+    """One launch chain of `mhla_causal_varlen_state_init`: the state of every sequence of the pack k, v into the ragged `state`."""
+    lib = _lib.load()
+    _, T, H, K = k.shape
+    k, v = _prep(k), _prep(v)
+    mixf = _mix2d(mix)
+    rc = lib.mhla_causal_varlen_state_init(_view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+                                           state.P.data_ptr(), state.Cur.data_ptr(), len(state.lengths), state.pos.data_ptr(),
+                                           max(state.lengths), T, H, K, v.shape[-1], state.chunk_size, plan.n_chunks,
+                                           plan.table.data_ptr(), plan.dst.data_ptr(), _dtype_code(k), _stream())
+    _lib.check(rc, "mhla_causal_varlen_state_init")
+
+
 def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, *, lengths=None, left_padded: bool = False,
-                      capacity_chunks: Optional[int] = None) -> CausalState:
+                      capacity_chunks: Optional[int] = None, cu_seqlens=None) -> CausalState:
     """The `CausalState` after the T tokens of k `[B, T, H, K]`, v `[B, T, H, V]` (the state half of `mhla_causal_prefill`;
     chunk 64).  T = 0: an empty state.
     lengths (a list or a tensor of B ints in 0 .. T; a device tensor is read once, which synchronises): a padded batch -- the tokens
     of sequence b are rows `[0, lengths[b])`, or `[T - lengths[b], T)` with `left_padded`, and the state is ragged (`CausalState`):
-    every sequence as if prefilled alone, `lengths[b] = 0` an empty one.  Built run by run of adjacent sequences of equal length."""
+    every sequence as if prefilled alone, `lengths[b] = 0` an empty one.  Built run by run of adjacent sequences of equal length.
+    cu_seqlens (a `CausalVarlenPlan`, a list or a tensor, as `mhla_causal` takes it; B = 1): a pack -- the ragged state of B =
+    number of sequences, in `cu` order, empty ones included, bit for bit what every sequence prefilled alone gives, in ONE launch
+    chain whatever their number (`mhla_causal_varlen_state_init`).  Excludes `lengths` / `left_padded` (ValueError); IndexError
+    names the sequences longer than `64 capacity_chunks` tokens; ValueError when sequences x heads exceed 65535."""
+    if cu_seqlens is not None:
+        plan, cap = _causal_state_pack_args("mhla_causal_state", k, v, mixing_matrix, cu_seqlens, lengths, left_padded, capacity_chunks)
+        _, T, H, K = k.shape
+        if T:
+            _require_gpu(k, v, mixing_matrix, plan.table)
+        with torch.no_grad():
+            state = CausalState.empty(len(plan.lengths), H, K, v.shape[-1], cap, k.device, 64)
+            # (the launch chain writes P and Cur of every sequence, the empty ones included: nothing to zero first)
+            P, Cur = (state.P, state.Cur) if not T else (torch.empty_like(state.P), torch.empty_like(state.Cur))
+            state = CausalState(state.S, P, Cur, 0, 64, lengths=plan.lengths)
+            if T:
+                _causal_state_init_pack(k.detach(), v.detach(), mixing_matrix, state, plan)
+        return state
     if k.dim() != 4 or v.dim() != 4:
         raise ValueError("k: [B, T, H, K], v: [B, T, H, V]")
     B, T, H, K = k.shape

@@ -48,6 +48,14 @@ call with median, min and max, the device time of the library's kernels and the 
 state is put back before every call -- host mirror and a 32-byte device copy of the positions, given to both variants -- so that every
 call is the same work.
 
+`--packed-prefill`: the same eight prompts (100 .. 2048 tokens, all different) prefilled two ways at the C5 head (H = 4, K = 128,
+V = 256, bf16, L = 128, a state of 40 chunks per sequence): (a) left-padded to [8, 2048] through `mhla_causal_prefill(lengths=,
+left_padded=True)` -- one operator call and one state chain per run of equal lengths, here per prompt -- and (b) packed to [1, sum]
+through `mhla_causal_prefill(cu_seqlens=plan)` -- one operator call over the pack, one state chain (`mhla_causal_varlen_state_init`).
+Alternating in one run, `--reps` times, `--steps` calls each (at most 20): wall time per call with median, min and max, the device time
+of the library's kernels and its launches per call (the per-launch event hook); the same for the state half alone
+(`mhla_causal_state`).  The plan is built once, outside the timed calls, as a server builds it once per batch for all layers.
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -364,6 +372,52 @@ def mixed_config(H, K, V, steps, reps, slice_tokens=256):
     return rec
 
 
+def packed_prefill_config(H, K, V, iters, reps, cap=40):
+    lengths = (100, 333, 517, 777, 1024, 1300, 1701, 2048)
+    B, T = len(lengths), max(lengths)
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    mk = lambda n, D: torch.randn(1, n, H, D, generator=g).to(torch.bfloat16)
+    seqs = [(mk(n, K), mk(n, K), mk(n, V)) for n in lengths]
+    pad = [torch.zeros(B, T, H, D, dtype=torch.bfloat16) for D in (K, K, V)]
+    for b, n in enumerate(lengths):
+        for dst, src in zip(pad, seqs[b]):
+            dst[b, T - n:] = src[0]
+    qp, kp, vp = (t.to(DEV) for t in pad)
+    qc, kc, vc = (torch.cat([s[i] for s in seqs], dim=1).to(DEV) for i in range(3))
+    cu = [0]
+    for n in lengths:
+        cu.append(cu[-1] + n)
+    plan = mhla_amd.causal_varlen_plan(cu, DEV)
+    fns = {"padded_prefill": lambda: mhla_amd.mhla_causal_prefill(qp, kp, vp, mix, lengths=lengths, left_padded=True, capacity_chunks=cap),
+           "packed_prefill": lambda: mhla_amd.mhla_causal_prefill(qc, kc, vc, mix, cu_seqlens=plan, capacity_chunks=cap),
+           "padded_state": lambda: mhla_amd.mhla_causal_state(kp, vp, mix, lengths=lengths, left_padded=True, capacity_chunks=cap),
+           "packed_state": lambda: mhla_amd.mhla_causal_state(kc, vc, mix, cu_seqlens=plan, capacity_chunks=cap)}
+    wall = {n: [] for n in fns}
+    dev = {n: [] for n in fns}
+    kern = {}
+    with torch.no_grad():
+        for _ in range(reps):
+            for n, fn in fns.items():
+                wall[n].append(batch_us(fn, iters, warm=2))
+            for n, fn in fns.items():
+                kern[n] = kernel_times(fn, iters=5)
+                dev[n].append(sum(kern[n].values()))
+        launches = {n: launch_counts(fn) for n, fn in fns.items()}
+    med = {n: statistics.median(x) for n, x in wall.items()}
+    rec = {"packed_prefill": {"H": H, "K": K, "V": V, "lengths": lengths, "tokens": cu[-1], "padded_rows": B * T, "capacity_chunks": cap,
+                              "pack_chunks": plan.n_chunks},
+           "calls_per_batch": iters, "reps": reps,
+           "wall_us": {n: spread(x) for n, x in wall.items()}, "device_us": {n: spread(x) for n, x in dev.items()},
+           "launches": {n: {"total": sum(c.values()), "by_kernel": c} for n, c in launches.items()},
+           "padded_over_packed_wall": {h: round(med["padded_" + h] / med["packed_" + h], 2) for h in ("prefill", "state")},
+           "padded_over_packed_device": {h: round(statistics.median(dev["padded_" + h]) / statistics.median(dev["packed_" + h]), 2)
+                                         for h in ("prefill", "state")},
+           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()}}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def gpu_kernel_count(fn):
     """GPU kernels one call of `fn` launches, or None where the profiler reports no device events."""
     try:
@@ -504,8 +558,11 @@ if __name__ == "__main__":
     ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--mixed", action="store_true")
+    ap.add_argument("--packed-prefill", action="store_true")
     a = ap.parse_args()
-    if a.mixed:
+    if a.packed_prefill:
+        packed_prefill_config(4, 128, 256, min(20, a.steps), a.reps)
+    elif a.mixed:
         mixed_config(4, 128, 256, max(100, a.steps), a.reps)
     elif a.graph:
         for B in (8, 32):
