@@ -168,6 +168,10 @@ int mhla_blockmix_fwd(mhla_view q_num, mhla_view k_num, mhla_view v,
  * [rows of one batch item][D/2] fp32, indexed by the token's memory row (the same index
  * block_index maps to), shared by all heads and batch items.  No q_rope / k_rope tensors exist.
  * Workspace: mhla_blockmix_fwd_ws_bytes(..., split = 0, flags).  Needs D % 8 == 0.
+ * fp32 tensors; 16-bit tensors only where their summaries are fp32 words or bf16 (head dims above 96, MHLA_FLAG_BF16_SUMMARIES, the
+ * "fp32_summaries" option).  On h16 / p24 summaries a 16-bit call is refused with MHLA_ENOTSUP during argument validation -- no
+ * rotary summary kernel is built for it: pass fp32 tensors, or rotate on the host and call mhla_blockmix_fwd(q_rope, k_rope, v,
+ * q_den = q, k_den = k).
  */
 int mhla_blockmix_rope_fwd(mhla_view q, mhla_view k, mhla_view v, int normalize,
                            const float* W, int ldw,

@@ -417,6 +417,9 @@ static int bm_fwd_impl(mhla_view q_num, mhla_view k_num, mhla_view v, mhla_view 
     if (epi && (!sp_shape_ok(D, flags) || dtype != MHLA_F32))
         return fail(MHLA_ENOTSUP, "fused norm/gate epilogue needs fp32 q, k, v, D %% 8 == 0 and the split-operand kernels (D=%d, dtype=%d)", D, dtype);
     if (rcos && !sp_shape_ok(D, flags)) return fail(MHLA_ENOTSUP, "fused rotary prologue needs D %% 8 == 0 and the split-operand kernels (D=%d, flags=%u)", D, flags);
+    if (rcos && dtype != MHLA_F32 && sf_packed(bm_sumfmt(M, S, D, dtype, flags)))   // (no rotary summary kernel is built for 16-bit tensors on h16 / p24)
+        return fail(MHLA_ENOTSUP, "rotary forward on 16-bit tensors with h16 / p24 summaries is not built (M=%d S=%d D=%d dtype=%d): use fp32 tensors, or rotate "
+                                  "on the host and call mhla_blockmix(q_rope, k_rope, v, W, q_den=q, k_den=k)", M, S, D, dtype);
     c.out = out; c.epi = epi; c.gate = gate; c.nw = nw; c.neps = neps; c.out_dtype = out_dtype;
     switch (const BmRoute r = bm_call_route(c, false)) {
         case BM_SN: case BM_SNF: return sn_fwd(c, r);

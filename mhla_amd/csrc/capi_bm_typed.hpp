@@ -11,7 +11,7 @@
 namespace mhla {
 namespace capi {
 
-static_assert(sp::mixr_te<4, true>() == mixr_slice(true) && sp::mixr_te<4, false>() == mixr_slice(false), "bm_plan's resident-mixing rule");
+static_assert(sp::mixr_te<4, SF_BF16>() == mixr_slice(true) && sp::mixr_te<4, SF_F32>() == mixr_slice(false) && sp::mixr_te<4, SF_P24>() == mixr_slice(false), "bm_plan's resident-mixing rule");
 template <int DT> constexpr int sp_state_threads() {   // eight waves at D = 128 (split.hpp)
 #ifdef MHLA_SP_STATE_4WAVES
     return NTHREADS;
@@ -26,20 +26,39 @@ template <int DT> constexpr int sp_state_threads() {   // eight waves at D = 128
 #define SP_MIXH2_RT 1   // 16-row output tiles per wave of k_sp_mixh2 (1: twelve / sixteen waves, 2: six / eight)
 #endif
 
-// p24 summaries (split.hpp: 24-bit floats, 3 / 4 of the bytes of every summary transfer) on the resident-mixing pipeline: 16-bit tensors
-// with head dims up to 96 and up to 128 blocks (the fused dW), and fp32 tensors at head dims 113 .. 128 with 33 .. 192 blocks (the Wan
-// shape, rotary tables and fused epilogue included: the operands are bf16 hi + lo pairs there too, 16 significand bits either way).
-template <typename ET, int DT, bool S16>
-constexpr bool bm_p24_built() { return !S16 && ((sizeof(ET) == 2 && DT <= 6) || (std::is_same<ET, float>::value && DT == 8)); }
-// h16 (2-byte summaries, the default on 16-bit tensors): the same pipeline, instantiated for 16-bit element types (capi_common.hpp bm_sumfmt decides per call)
-template <typename ET, int DT, bool S16>
-constexpr bool bm_h16_built() { return !S16 && sizeof(ET) == 2 && DT <= 6; }
-// Run `...` with PF = the kernels' summary-format template value of this call (0: fp32 words, or bf16 when S16; 1: p24; 2: h16), where <ET, DT, S16> build it
-#define WITH_PF(fmt, ...) do { \
-        if ((fmt) == SF_H16) { if constexpr (bm_h16_built<ET, DT, S16>()) { constexpr int PF = 2; __VA_ARGS__; } else return fail(MHLA_EINVAL, "h16 summaries are not built for this type / head dim"); } \
-        else if ((fmt) == SF_P24) { if constexpr (bm_p24_built<ET, DT, S16>()) { constexpr int PF = 1; __VA_ARGS__; } else return fail(MHLA_EINVAL, "p24 summaries are not built for this type / head dim"); } \
-        else { constexpr int PF = 0; __VA_ARGS__; } \
-    } while (0)
+// The summary formats (common.hpp SF_*) a unit builds its split-operand kernels for; capi_common.hpp bm_sumfmt decides per call.  S16 (the
+// unit of bf16 tensors with MHLA_FLAG_BF16_SUMMARIES) builds bf16 summaries and nothing else; the other units build fp32 words and
+//   p24 (split.hpp: 24-bit floats, 3 / 4 of the bytes of every summary transfer) on the resident-mixing pipeline: 16-bit tensors with head
+//       dims up to 96 and up to 128 blocks (the fused dW), and fp32 tensors at head dims 113 .. 128 with 33 .. 192 blocks (the Wan shape,
+//       rotary tables and fused epilogue included: the operands are bf16 hi + lo pairs there too, 16 significand bits either way);
+//   h16 (2-byte summaries, the default on 16-bit tensors): the same pipeline, for 16-bit element types.
+template <typename ET, int DT, bool S16, int FMT>
+constexpr bool bm_fmt_built() {
+    if (S16 || FMT == SF_BF16) return S16 && FMT == SF_BF16;
+    if (FMT == SF_P24) return (sizeof(ET) == 2 && DT <= 6) || (std::is_same<ET, float>::value && DT == 8);
+    if (FMT == SF_H16) return sizeof(ET) == 2 && DT <= 6;
+    return true;
+}
+template <bool S16> constexpr int sf_plain() { return S16 ? SF_BF16 : SF_F32; }   // the unit's format of one stored value per element
+// the plan names a kernel this unit has no instantiation of: nothing is launched
+template <typename ET, int DT>
+int not_built(const char* kernel, int fmt) {
+    static const char* const fmts[] = {"fp32-word", "p24", "h16", "bf16"};
+    return fail(MHLA_ENOTSUP, "%s is not built for %s tensors with %s summaries at head dims up to %d", kernel,
+                std::is_same<ET, float>::value ? "fp32" : std::is_same<ET, bf16_t>::value ? "bf16" : "fp16", fmts[fmt & 3], 16 * DT);
+}
+// run launch_fmt.operator()<FMT>() with FMT = the call's summary format, where <ET, DT, S16> build it  (the cases' order is the order in
+// which a unit instantiates, and lays out, the kernels of one launch site)
+template <typename ET, int DT, bool S16, typename F>
+int with_fmt(int fmt, const char* kernel, F&& launch_fmt) {
+    switch (fmt) {
+        case SF_H16: if constexpr (bm_fmt_built<ET, DT, S16, SF_H16>()) return launch_fmt.template operator()<SF_H16>(); break;
+        case SF_P24: if constexpr (bm_fmt_built<ET, DT, S16, SF_P24>()) return launch_fmt.template operator()<SF_P24>(); break;
+        case SF_F32: if constexpr (bm_fmt_built<ET, DT, S16, SF_F32>()) return launch_fmt.template operator()<SF_F32>(); break;
+        case SF_BF16: if constexpr (bm_fmt_built<ET, DT, S16, SF_BF16>()) return launch_fmt.template operator()<SF_BF16>(); break;
+    }
+    return not_built<ET, DT>(kernel, fmt);
+}
 
 // ---- mixing: Out_i = sum_j Wm(i, j) In_j over the block summaries ----
 struct MixOp {
@@ -72,22 +91,22 @@ inline sp::MixrArgs mixr_args(const MixOp& o, const MixSlices& s, bool wz, bool 
 }
 // sp::k_sp_mixr (split.hpp).  DW: the backward's dKV = W^T dG with the dW products riding along (fp32 / 24-bit summaries, up to 128 blocks): one
 // [M][M] partial per workgroup (`*parts`); with `wz`, dz = W^T dn and the <dn_i, z_j> term of dW ride along too
-template <int NW, int TRANS, bool S16, bool DW, int P24>   // P24: 0 fp32 words (bf16 when S16), 1 24-bit floats
+template <int NW, int TRANS, int FMT, bool DW>
 int sp_mixr_nw(const MixOp& o, bool wz, const char* name, int* parts) {
     // persistent workgroups: as many as fit a CU beside each other (35 KB of LDS at four waves, 70 KB at eight)
     // DW: 54 KB of LDS at four waves: two per CU; 27 KB at two waves
-    const MixSlices s = mix_slices(o, sp::mixr_te<NW, S16>(), sp::mixr_te<NW, S16>(), wz, DW ? 256 * (NW <= 2 ? 4 : NW <= 4 ? 2 : 1) : 256 * (NW <= 2 ? 8 : NW <= 4 ? 4 : NW <= 8 ? 2 : 1));
+    const MixSlices s = mix_slices(o, sp::mixr_te<NW, FMT>(), sp::mixr_te<NW, FMT>(), wz, DW ? 256 * (NW <= 2 ? 4 : NW <= 4 ? 2 : 1) : 256 * (NW <= 2 ? 8 : NW <= 4 ? 4 : NW <= 8 ? 2 : 1));
     if (parts) *parts = s.gw;
-    return launch(sp::k_sp_mixr<NW, TRANS, S16, DW, P24>, dim3(s.gw), dim3(64 * NW), sp::sp_mixr_smem<NW, S16, DW>(), o.st, name, mixr_args(o, s, wz, !DW));
+    return launch(sp::k_sp_mixr<NW, TRANS, FMT, DW>, dim3(s.gw), dim3(64 * NW), sp::sp_mixr_smem<NW, FMT, DW>(), o.st, name, mixr_args(o, s, wz, !DW));
 }
-template <int TRANS, bool S16, bool DW, int P24>
+template <int TRANS, int FMT, bool DW>
 int sp_mixr(const MixOp& o, int nw, bool wz, const char* name, int* parts = nullptr) {
     switch (nw) {
-        case 2: if constexpr (!S16) return sp_mixr_nw<2, TRANS, S16, DW, P24>(o, wz, name, parts); break;
-        case 4: return sp_mixr_nw<4, TRANS, S16, DW, P24>(o, wz, name, parts);
-        case 8: return sp_mixr_nw<8, TRANS, S16, DW, P24>(o, wz, name, parts);
-        case 12: if constexpr (!DW) return sp_mixr_nw<12, TRANS, S16, DW, P24>(o, wz, name, parts); break;   // (twelve waves have no registers for the dW tiles)
-        case 16: if constexpr (!DW && !P24 && !S16) return sp_mixr_nw<16, TRANS, S16, DW, P24>(o, wz, name, parts); break;   // (p24: bm_sumfmt admits up to 192 blocks; bf16: k_sp_mixr_dma)
+        case 2: if constexpr (FMT != SF_BF16) return sp_mixr_nw<2, TRANS, FMT, DW>(o, wz, name, parts); break;
+        case 4: return sp_mixr_nw<4, TRANS, FMT, DW>(o, wz, name, parts);
+        case 8: return sp_mixr_nw<8, TRANS, FMT, DW>(o, wz, name, parts);
+        case 12: if constexpr (!DW) return sp_mixr_nw<12, TRANS, FMT, DW>(o, wz, name, parts); break;   // (twelve waves have no registers for the dW tiles)
+        case 16: if constexpr (!DW && FMT == SF_F32) return sp_mixr_nw<16, TRANS, FMT, DW>(o, wz, name, parts); break;   // (p24: bm_sumfmt admits up to 192 blocks; bf16: k_sp_mixr_dma)
     }
     return fail(MHLA_EINVAL, "sp_mixr: M=%d out of range", o.M);
 }
@@ -137,8 +156,10 @@ int sp_mixh(const MixOp& o, BmKern kind, int nw, bool dw, bool wz, const char* n
     return fail(MHLA_EINVAL, "sp_mixh: M=%d out of range", o.M);
 }
 // the plan's mixing kernel of direction TRANS; `*parts`: the [M][M] dW partials it left, where dW rode along
-template <int TRANS, bool S16, bool P24OK>
+template <typename ET, int DT, int TRANS, bool S16>
 int bm_mix(const BmPlan& p, const BmCall& c, int* parts = nullptr) {
+    constexpr int PLAIN = sf_plain<S16>();
+    constexpr bool PACKED = bm_fmt_built<ET, DT, S16, SF_P24>();   // the unit has the p24 mixing kernels and, with them, the h16 ones (mixh.hpp)
     const MixOp o = mix_op(p, c, TRANS);
     const bool wz = c.normalize && p.wz_fused;
     const char* name = p.n_mix[TRANS];
@@ -147,24 +168,26 @@ int bm_mix(const BmPlan& p, const BmCall& c, int* parts = nullptr) {
         case K_MIX:
             return launch(k_mix<TRANS, 0>, dim3((unsigned)((o.E + MIX_TE - 1) / MIX_TE), (o.M + MIX_TI - 1) / MIX_TI, o.BH), dim3(NTHREADS), MIX_SMEM_FLOATS * 4, o.st, name, dense);
         case K_SP_MIX:
-            return launch(sp::k_sp_mix<TRANS, S16>, dim3((unsigned)((o.E + sp::SPM_TE - 1) / sp::SPM_TE), (o.M + 63) / 64, o.BH), dim3(NTHREADS), sp::sp_mix_smem<S16>(), o.st, name, tiled);
+            if (p.fmt == PLAIN) return launch(sp::k_sp_mix<TRANS, PLAIN>, dim3((unsigned)((o.E + sp::SPM_TE - 1) / sp::SPM_TE), (o.M + 63) / 64, o.BH), dim3(NTHREADS), sp::sp_mix_smem<PLAIN>(), o.st, name, tiled);
+            break;
         case K_SP_MIXR_DMA:
             if constexpr (S16) return sp_mixr_dma<TRANS>(o, wz, name);
             break;
         case K_SP_MIXR:
-            if constexpr (TRANS == 1) {
-                if (p.dw_fused && p.fmt == SF_P24) { if constexpr (P24OK) return sp_mixr<1, false, true, 1>(o, p.nw, wz, name, parts); }
-                else if (p.dw_fused) return sp_mixr<1, false, true, 0>(o, p.nw, wz, name, parts);
-            }
-            if (p.fmt == SF_P24) { if constexpr (P24OK) return sp_mixr<TRANS, false, false, 1>(o, p.nw, wz, name); }
-            else return sp_mixr<TRANS, S16, false, 0>(o, p.nw, wz, name);
+            if (TRANS == 1 && p.dw_fused) {   // (the plan lets dW ride on fp32 words and p24 only)
+                if constexpr (TRANS == 1) {
+                    if (p.fmt == SF_P24) { if constexpr (PACKED) return sp_mixr<1, SF_P24, true>(o, p.nw, wz, name, parts); }
+                    else if (p.fmt == SF_F32) return sp_mixr<1, SF_F32, true>(o, p.nw, wz, name, parts);
+                }
+            } else if (p.fmt == SF_P24) { if constexpr (PACKED) return sp_mixr<TRANS, SF_P24, false>(o, p.nw, wz, name); }
+            else if (p.fmt == PLAIN) return sp_mixr<TRANS, PLAIN, false>(o, p.nw, wz, name);
             break;
         case K_SP_MIXH: case K_SP_MIXH2:
-            if constexpr (P24OK) return sp_mixh<TRANS>(o, p.mix[TRANS], p.nw, TRANS && p.dw_fused, wz, name, parts);
+            if constexpr (PACKED) return sp_mixh<TRANS>(o, p.mix[TRANS], p.nw, TRANS && p.dw_fused, wz, name, parts);
             break;
         default: break;
     }
-    return fail(MHLA_EINVAL, "%s is not built for this type / head dim", name);
+    return not_built<ET, DT>(name, p.fmt);
 }
 // the normaliser's product as a launch of its own: 1 / n = 1 / (eps + W z) (TRANS 0), dz = W^T dn (TRANS 1)
 template <int TRANS>
@@ -182,21 +205,24 @@ int bm_state(const BmPlan& p, const BmCall& c, const StateArgs& a) {
     if (p.state == K_BM_STATE) return launch(k_bm_state<ET, DT, TRANS>, g, dim3(NTHREADS), state_smem_floats<DT>() * 4, c.st, name, a);
     if (p.state == K_S16_STATE) return launch(s16::k_s16_state<TRANS>, dim3((c.M + s16::WPB - 1) / s16::WPB, c.B * c.H), dim3(64 * s16::WPB), s16::state_smem(), c.st, name, a);
     if (p.rope) {   // (the rotary backward serves fp32 tensors; 24-bit summaries with rotary tables likewise)
-        if (p.fmt == SF_P24 || p.fmt == SF_H16) {
-            if constexpr (F32 && bm_p24_built<ET, DT, S16>()) return launch(sp::k_sp_state<ET, DT, TRANS, true, SNT, false, 1>, g, dim3(SNT), sp::sp_state_smem<DT>(), c.st, name, a);
-        } else if constexpr (F32 || TRANS == 0)
-            return launch(sp::k_sp_state<ET, DT, TRANS, true, SNT, S16>, g, dim3(SNT), sp::sp_state_smem<DT>(), c.st, name, a);
-        return MHLA_OK;
+        constexpr sp::StateVar ROPE{.rope = true};
+        if (p.fmt == SF_P24) {
+            if constexpr (F32 && bm_fmt_built<ET, DT, S16, SF_P24>()) return launch(sp::k_sp_state<ET, DT, TRANS, SNT, SF_P24, ROPE>, g, dim3(SNT), sp::sp_state_smem<DT>(), c.st, name, a);
+        } else if (p.fmt == sf_plain<S16>()) {
+            if constexpr (F32 || TRANS == 0) return launch(sp::k_sp_state<ET, DT, TRANS, SNT, sf_plain<S16>(), ROPE>, g, dim3(SNT), sp::sp_state_smem<DT>(), c.st, name, a);
+        }
+        return not_built<ET, DT>(name, p.fmt);
     }
     // (forward on h16 summaries without a split normaliser pair: the instantiation that has no third row stream)
-    if constexpr (TRANS == 0 && bm_h16_built<ET, DT, S16>()) {
+    if constexpr (TRANS == 0 && bm_fmt_built<ET, DT, S16, SF_H16>()) {
         if (p.fmt == SF_H16 && !(c.normalize && c.split) && g_recut.load())
-            return launch(sp::k_sp_state<ET, DT, 0, false, SNT, S16, 2, false, false>, g, dim3(SNT), sp::sp_state_smem<DT>(), c.st, name, a);
+            return launch(sp::k_sp_state<ET, DT, 0, SNT, SF_H16, sp::StateVar{.ts = false}>, g, dim3(SNT), sp::sp_state_smem<DT>(), c.st, name, a);
     }
     // (backward on h16 / p24, 16-bit tensors, D <= 64: the row dots come from G_i; two more LDS tiles)
-    WITH_PF(p.fmt, return launch(sp::k_sp_state<ET, DT, TRANS, false, SNT, S16, PF>, g, dim3(SNT),
-                                 (PF && TRANS && sizeof(ET) == 2 && DT <= 4) ? sp::sp_state_rd_smem<DT, sp::sp_payrd<ET, DT, PF>()>() : sp::sp_state_smem<DT>(), c.st, name, a));
-    return MHLA_OK;
+    return with_fmt<ET, DT, S16>(p.fmt, name, [&]<int FMT>() {
+        constexpr int smem = (sf_packed(FMT) && TRANS && sizeof(ET) == 2 && DT <= 4) ? sp::sp_state_rd_smem<DT, sp::sp_payrd<ET, DT, FMT>()>() : sp::sp_state_smem<DT>();
+        return launch(sp::k_sp_state<ET, DT, TRANS, SNT, FMT>, g, dim3(SNT), smem, c.st, name, a);
+    });
 }
 // KV / ksum / z, G and 1 / n: the forward, and the recompute leg of a backward that was handed no forward workspace
 template <typename ET, int DT, bool S16>
@@ -208,7 +234,7 @@ int bm_state_and_mix(const BmPlan& p, const BmCall& c) {
     a.out = w.kv; a.ksum = w.ksum; a.zo = w.z; a.es = w.es;
     a.H = c.H; a.M = c.M; a.S = c.S; a.D = c.D; a.eps = c.eps; a.relu = c.relu(); a.normalize = c.normalize; a.split = c.split;
     RC((bm_state<ET, DT, 0, S16>(p, c, a)));
-    RC((bm_mix<0, S16, bm_p24_built<ET, DT, S16>()>(p, c)));
+    RC((bm_mix<ET, DT, 0, S16>(p, c)));
     if (p.wz_kernel) RC(launch_wz<0>(c.W, c.ldw, w.z, w.ninv, c.B * c.H, c.M, c.S, c.eps, c.st));
     return MHLA_OK;
 }
@@ -216,13 +242,15 @@ int bm_state_and_mix(const BmPlan& p, const BmCall& c) {
 // ---- output O_i = Q_i G_i / n_i: the forward's, and the backward's recompute of what the forward's 16-bit store of O rounded away ----
 template <typename ET, int DT, bool S16, typename TO = ET, bool EPI = false>
 int sp_out(const BmPlan& p, const BmCall& c, const OutArgs& o, const char* name) {
+    const dim3 g(c.M, c.B * c.H), blk(sp::SP_OUT_T);
     // (16-bit tensors on h16 summaries, D <= 64, blocks of at most 64 tokens: the instantiation of one tile per wave)
-    if constexpr (!EPI && bm_h16_built<ET, DT, S16>() && DT <= 4) {
+    if constexpr (!EPI && bm_fmt_built<ET, DT, S16, SF_H16>() && DT <= 4) {
         if (p.fmt == SF_H16 && bm_one_tile(c.S))
-            return launch(sp::k_sp_out<ET, DT, TO, false, S16, 2, false, false, true>, dim3(c.M, c.B * c.H), dim3(sp::SP_OUT_T), sp::sp_out_smem<DT, S16>(), c.st, name, o);
+            return launch(sp::k_sp_out<ET, DT, TO, SF_H16, sp::OutVar{.one = true}>, g, blk, sp::sp_out_smem<DT, SF_H16>(), c.st, name, o);
     }
-    WITH_PF(p.fmt, return launch(sp::k_sp_out<ET, DT, TO, EPI, S16, PF>, dim3(c.M, c.B * c.H), dim3(sp::SP_OUT_T), sp::sp_out_smem<DT, S16>(), c.st, name, o));
-    return MHLA_OK;
+    return with_fmt<ET, DT, S16>(p.fmt, name, [&]<int FMT>() {
+        return launch(sp::k_sp_out<ET, DT, TO, FMT, sp::OutVar{.epi = EPI}>, g, blk, sp::sp_out_smem<DT, FMT>(), c.st, name, o);
+    });
 }
 inline OutArgs out_args(const BmCall& c) {
     OutArgs o{};
@@ -242,7 +270,7 @@ int bm_out(const BmPlan& p, const BmCall& c, OutArgs& o, const char* name) {
         if (c.out_dtype == MHLA_F16) return sp_out<float, DT, S16, f16_t, true>(p, c, o, name);
         return sp_out<float, DT, S16, float, true>(p, c, o, name);
     }
-    return MHLA_OK;
+    return not_built<ET, DT>(name, p.fmt);
 }
 
 // ---- dW = sum_bh (<dG_i, KV_j> + <dn_i, z_j>): partials in w.dwp, `*parts` of them, then k_dw_reduce ----
@@ -265,7 +293,7 @@ inline int sp_dwr(const s16::DwrArgs& d, int tiles, bool h16, int BH, hipStream_
     if (tiles == 3) return launch(s16::k_sp_dwr<3>, g, dim3(576), s16::dwr_smem<3>(), st, name, d);
     return launch(s16::k_sp_dwr<4>, g, dim3(1024), s16::dwr_smem<4>(), st, name, d);
 }
-template <bool S16, bool P24OK>
+template <typename ET, int DT, bool S16>
 int bm_dw(const BmPlan& p, const BmCall& c, int tiles, int* parts) {
     const BmWs& w = c.w;
     const int BH = c.B * c.H, M = c.M;
@@ -275,24 +303,28 @@ int bm_dw(const BmPlan& p, const BmCall& c, int tiles, int* parts) {
     if (p.dw == K_SP_DWR) {   // whole-matrix workgroups: the <dn_i, z_j> term is one of their stages
         const int nsplit = sp_dwr_splits(BH, E);
         *parts = BH * nsplit;
-        return sp_dwr(s16::DwrArgs{(const sp::u16*)w.dg, (const sp::u16*)w.kv, E, p.fmt == SF_H16 ? 2 * w.es : w.es, dn, z, c.S, w.dwp, M, nsplit}, p.dw_v, p.fmt == SF_H16, BH, c.st, p.n_dw);
+        const s16::DwrArgs d{(const sp::u16*)w.dg, (const sp::u16*)w.kv, E, p.fmt == SF_H16 ? 2 * w.es : w.es, dn, z, c.S, w.dwp, M, nsplit};   // (named: tools/record_launches.py hashes the padding too)
+        return sp_dwr(d, p.dw_v, p.fmt == SF_H16, BH, c.st, p.n_dw);
     }
     int nsplit = dw_splits(tiles * tiles * BH, E);
     if (p.dw == K_DW) {
         *parts = BH * nsplit;
-        return launch(k_dw<0>, dim3(tiles * tiles, BH, nsplit), dim3(NTHREADS), DW_SMEM_FLOATS * 4, c.st, p.n_dw, DwArgs{w.dg, w.kv, E, dn, z, (long)c.S, w.dwp, M, tiles, nsplit});
+        const DwArgs d{w.dg, w.kv, E, dn, z, (long)c.S, w.dwp, M, tiles, nsplit};
+        return launch(k_dw<0>, dim3(tiles * tiles, BH, nsplit), dim3(NTHREADS), DW_SMEM_FLOATS * 4, c.st, p.n_dw, d);
     }
     if (nsplit > DW_MAX_SPLIT - 1) nsplit = DW_MAX_SPLIT - 1;   // one more part per (b, h) holds the <dn_i, z_j> term
     *parts = BH * nsplit;
     const DwArgs d{w.dg, w.kv, E, nullptr, nullptr, 0, w.dwp, M, tiles, nsplit, w.es};
     const dim3 g(p.dw_v ? 1 : tiles * tiles, BH, nsplit);
     if (p.dw == K_SP_DWT) {   // 24-bit summaries of 129 .. 192 blocks: k_sp_dwt reads dG and KV again
-        if constexpr (P24OK) return launch(sp::k_sp_dwt<true>, g, dim3(NTHREADS), sp::SP_DWT_SMEM, c.st, p.n_dw, d);
-        return fail(MHLA_EINVAL, "%s is not built for this type / head dim", p.n_dw);
+        if constexpr (bm_fmt_built<ET, DT, S16, SF_P24>()) { if (p.fmt == SF_P24) return launch(sp::k_sp_dwt<SF_P24>, g, dim3(NTHREADS), sp::SP_DWT_SMEM, c.st, p.n_dw, d); }
+        return not_built<ET, DT>(p.n_dw, p.fmt);
     }
-    if (p.dw_v == 16) return launch(sp::k_sp_dw<S16, 1>, g, dim3(NTHREADS), sp::SP_DW_SMEM, c.st, p.n_dw, d);
-    if (p.dw_v == 32) return launch(sp::k_sp_dw<S16, 2>, g, dim3(NTHREADS), sp::SP_DW_SMEM, c.st, p.n_dw, d);
-    return launch(sp::k_sp_dw<S16>, g, dim3(NTHREADS), sp::SP_DW_SMEM, c.st, p.n_dw, d);
+    constexpr int PLAIN = sf_plain<S16>();
+    if (p.fmt != PLAIN) return not_built<ET, DT>(p.n_dw, p.fmt);
+    if (p.dw_v == 16) return launch(sp::k_sp_dw<PLAIN, 1>, g, dim3(NTHREADS), sp::SP_DW_SMEM, c.st, p.n_dw, d);
+    if (p.dw_v == 32) return launch(sp::k_sp_dw<PLAIN, 2>, g, dim3(NTHREADS), sp::SP_DW_SMEM, c.st, p.n_dw, d);
+    return launch(sp::k_sp_dw<PLAIN>, g, dim3(NTHREADS), sp::SP_DW_SMEM, c.st, p.n_dw, d);
 }
 // the <dn_i, z_j> term as one more part per (b, h), behind the `parts` there are
 template <int MASK = 0>   // (templates: instantiated only in the units that launch them)
@@ -309,6 +341,14 @@ int launch_dw_reduce(const float* dwp, float* dW, int M, int parts, int BH, bool
 }
 
 // ---- token gradients dQ, dK, dV ----
+template <typename ET, int DT, int FMT, sp::DqVar V = sp::DqVar{}>
+int sp_dq(const BmPlan& p, const BmCall& c, const TokArgs& t) {
+    return launch(sp::k_sp_bwd_dq<ET, DT, FMT, V>, dim3(c.M, c.B * c.H), dim3(NTHREADS), sp::sp_dq_smem<DT, FMT, sp::sp_payop<ET, DT, FMT, V.rope>()>(), c.st, p.n_tok[0], t);
+}
+template <typename ET, int DT, int FMT, sp::DkvVar V = sp::DkvVar{}>
+int sp_dkv(const BmPlan& p, const BmCall& c, const TokArgs& t) {
+    return launch(sp::k_sp_bwd_dkv<ET, DT, FMT, V>, dim3(c.M, c.B * c.H), dim3(NTHREADS), sp::sp_tok_smem<DT, FMT>(), c.st, p.n_tok[1], t);
+}
 template <typename ET, int DT, bool S16>
 int bm_tok(const BmPlan& p, const BmCall& c, const TokArgs& t) {
     const dim3 g(c.M, c.B * c.H), blk(NTHREADS);
@@ -319,25 +359,24 @@ int bm_tok(const BmPlan& p, const BmCall& c, const TokArgs& t) {
         return launch(s16::k_s16_bwd_dkv<0>, g16, b16, s16::dkv_smem(), c.st, p.n_tok[1], t);
     }
     if (p.rope) {
-        if constexpr (std::is_same<ET, float>::value) {
-            WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, true, false, false, PF>, g, blk, sp::sp_dq_smem<DT, false, sp::sp_payop<ET, DT, PF, true>()>(), c.st, p.n_tok[0], t));
-                           return launch(sp::k_sp_bwd_dkv<ET, DT, true, false, PF>, g, blk, sp::sp_tok_smem<DT, false>(), c.st, p.n_tok[1], t));
-        }
-        return MHLA_OK;
+        if constexpr (std::is_same<ET, float>::value) return with_fmt<ET, DT, S16>(p.fmt, p.n_tok[0], [&]<int FMT>() {
+            RC((sp_dq<ET, DT, FMT, sp::DqVar{.rope = true}>(p, c, t)));
+            return sp_dkv<ET, DT, FMT, sp::DkvVar{.rope = true}>(p, c, t);
+        });
+        return not_built<ET, DT>(p.n_tok[0], p.fmt);
     }
     // (16-bit tensors: q_den in 16-byte pieces when it only feeds dksum; not at D = 72 / 80, where the wider rows cost a wave of occupancy)
     const bool wq = c.normalize && !c.relu() && sizeof(ET) == 2 && DT != 5;
     // (h16 summaries, D <= 64, blocks of at most 64 tokens: a wave has one tile at the most -- the loop-free instantiation)
-    constexpr bool ONE_BUILT = bm_h16_built<ET, DT, S16>() && DT <= 4;
+    constexpr bool ONE_BUILT = bm_fmt_built<ET, DT, S16, SF_H16>() && DT <= 4;
     if (wq && ONE_BUILT && p.fmt == SF_H16 && bm_one_tile(c.S)) {
-        if constexpr (ONE_BUILT) RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, true, 2, true>, g, blk, sp::sp_dq_smem<DT, S16, sp::sp_payop<ET, DT, 2>()>(), c.st, p.n_tok[0], t));
-    } else if (wq) WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, true, PF>, g, blk, sp::sp_dq_smem<DT, S16, sp::sp_payop<ET, DT, PF>()>(), c.st, p.n_tok[0], t)));
-    else WITH_PF(p.fmt, RC(launch(sp::k_sp_bwd_dq<ET, DT, false, S16, false, PF>, g, blk, sp::sp_dq_smem<DT, S16, sp::sp_payop<ET, DT, PF>()>(), c.st, p.n_tok[0], t)));
-    WITH_PF(p.fmt, return launch(sp::k_sp_bwd_dkv<ET, DT, false, S16, PF>, g, blk, sp::sp_tok_smem<DT, S16>(), c.st, p.n_tok[1], t));
-    return MHLA_OK;
+        if constexpr (ONE_BUILT) RC((sp_dq<ET, DT, SF_H16, sp::DqVar{.wq = true, .one = true}>(p, c, t)));
+    } else if (wq) RC((with_fmt<ET, DT, S16>(p.fmt, p.n_tok[0], [&]<int FMT>() { return sp_dq<ET, DT, FMT, sp::DqVar{.wq = true}>(p, c, t); })));
+    else RC((with_fmt<ET, DT, S16>(p.fmt, p.n_tok[0], [&]<int FMT>() { return sp_dq<ET, DT, FMT>(p, c, t); })));
+    return with_fmt<ET, DT, S16>(p.fmt, p.n_tok[1], [&]<int FMT>() { return sp_dkv<ET, DT, FMT>(p, c, t); });
 }
 
-// S16: the block summaries are stored as bf16 (bf16 tensors with MHLA_FLAG_BF16_SUMMARIES); false: fp32 summaries, hi + lo operands
+// S16: the unit of bf16 block summaries (bf16 tensors with MHLA_FLAG_BF16_SUMMARIES); false: fp32-grade summaries, hi + lo operands (bm_fmt_built)
 template <typename ET, bool S16>
 int bm_fwd_typed(const BmCall& c) {
     const BmPlan p = bm_plan(c, false);
@@ -377,8 +416,8 @@ int bm_bwd_typed(const BmCall& c) {
         if (p.wz_kernel && p.wz1_first) RC(launch_wz<1>(c.W, c.ldw, w.dn, w.dz, BH, M, S, 0.f, c.st));
         // dKV = W^T dG, dz = W^T dn, dW
         int parts = 0;
-        RC((bm_mix<1, S16, bm_p24_built<ET, DT, S16>()>(p, c, &parts)));
-        RC((bm_dw<S16, bm_p24_built<ET, DT, S16>()>(p, c, tiles, &parts)));
+        RC((bm_mix<ET, DT, 1, S16>(p, c, &parts)));
+        RC((bm_dw<ET, DT, S16>(p, c, tiles, &parts)));
         if (p.wz_kernel && !p.wz1_first) RC(launch_wz<1>(c.W, c.ldw, w.dn, w.dz, BH, M, S, 0.f, c.st));
         if (p.dnz) {
             RC(launch_dnz(c, tiles, parts));

@@ -23,11 +23,11 @@ int wan_pro_fwd(const mhla_view& q, const mhla_view& k, const mhla_view& v, cons
     a.out = w.kv; a.ksum = w.ksum; a.zo = w.z; a.es = es;
     a.H = H; a.M = M; a.S = S; a.D = D; a.eps = eps; a.relu = 1; a.normalize = normalize; a.split = 0;
     a.pro_rk = rstd_k; a.pro_wk = wk; a.pro_rq = rstd_q; a.pro_wq = wq; a.pro_n = (long)M * S;
-    if (rcos) RC(launch(sp::k_sp_state<ET, DT, 0, true, SNT, false, 1, true>, dim3(M, B * H), dim3(SNT), sp::sp_state_smem<DT>(), st, "k_sp_state<rope,pro>", a));
-    else      RC(launch(sp::k_sp_state<ET, DT, 0, false, SNT, false, 1, true>, dim3(M, B * H), dim3(SNT), sp::sp_state_smem<DT>(), st, "k_sp_state<pro>", a));
+    if (rcos) RC(launch(sp::k_sp_state<ET, DT, 0, SNT, SF_P24, sp::StateVar{.rope = true, .pro = true}>, dim3(M, B * H), dim3(SNT), sp::sp_state_smem<DT>(), st, "k_sp_state<rope,pro>", a));
+    else      RC(launch(sp::k_sp_state<ET, DT, 0, SNT, SF_P24, sp::StateVar{.pro = true}>, dim3(M, B * H), dim3(SNT), sp::sp_state_smem<DT>(), st, "k_sp_state<pro>", a));
     const BmPlan p = bm_plan((long)B * H, M, S, D, MHLA_F32, 0, normalize, false, rcos != nullptr, true, false);   // (the fp32-tensor operator's plan: mhla_blockmix_wan_pro_ok)
     const MixOp m{W, ldw, w.kv, w.g, M, E, es, B * H, st, w.z, w.ninv, S, eps, nullptr, nullptr, nullptr};
-    RC((sp_mixr<0, false, false, 1>(m, p.nw, normalize && p.wz_fused, p.n_mix[0])));
+    RC((sp_mixr<0, SF_P24, false>(m, p.nw, normalize && p.wz_fused, p.n_mix[0])));
     if (p.wz_kernel) RC(launch_wz<0>(W, ldw, w.z, w.ninv, B * H, M, S, eps, st));
     OutArgs o{};
     o.rcos = rcos; o.rsin = rsin; o.ldr = ldr;
@@ -36,20 +36,21 @@ int wan_pro_fwd(const mhla_view& q, const mhla_view& k, const mhla_view& v, cons
     o.nw = nw; o.neps = neps; o.gate = cv(gate);
     o.pro_rq = rstd_q; o.pro_wq = wq; o.pro_n = (long)M * S;
     const dim3 g(M, B * H), blk(sp::SP_OUT_T);
+    constexpr sp::OutVar BLOCK{.epi = true, .pro = true}, FLAT{.epi = true, .pro = true, .flat = true};
     // the flat tile list (split.hpp k_sp_out<.., FLAT>): one persistent workgroup per CU, when the blocks are long enough for its rounds and
     // there are enough tiles to cut (mhla_set_option("recut_kernels", 0) / MHLA_WAN_FLAT=0: the block-per-workgroup launch, for A/B)
     o.nbh = B * H;
     const int tpi = (S + 15) / 16;
     if (g_recut.load() && tpi >= 8 && (long)B * H * M * tpi >= 256L * 32) {
         const dim3 gf(256);
-        if (out_dtype == MHLA_BF16)     RC(launch(sp::k_sp_out<ET, DT, bf16_t, true, false, 1, true, true>, gf, blk, 2 * sp::sp_out_smem<DT>(), st, "k_sp_out<norm,pro,flat>", o));
-        else if (out_dtype == MHLA_F16) RC(launch(sp::k_sp_out<ET, DT, f16_t, true, false, 1, true, true>, gf, blk, 2 * sp::sp_out_smem<DT>(), st, "k_sp_out<norm,pro,flat>", o));
-        else                            RC(launch(sp::k_sp_out<ET, DT, float, true, false, 1, true, true>, gf, blk, 2 * sp::sp_out_smem<DT>(), st, "k_sp_out<norm,pro,flat>", o));
+        if (out_dtype == MHLA_BF16)     RC(launch(sp::k_sp_out<ET, DT, bf16_t, SF_P24, FLAT>, gf, blk, 2 * sp::sp_out_smem<DT, SF_P24>(), st, "k_sp_out<norm,pro,flat>", o));
+        else if (out_dtype == MHLA_F16) RC(launch(sp::k_sp_out<ET, DT, f16_t, SF_P24, FLAT>, gf, blk, 2 * sp::sp_out_smem<DT, SF_P24>(), st, "k_sp_out<norm,pro,flat>", o));
+        else                            RC(launch(sp::k_sp_out<ET, DT, float, SF_P24, FLAT>, gf, blk, 2 * sp::sp_out_smem<DT, SF_P24>(), st, "k_sp_out<norm,pro,flat>", o));
         return MHLA_OK;
     }
-    if (out_dtype == MHLA_BF16)     RC(launch(sp::k_sp_out<ET, DT, bf16_t, true, false, 1, true>, g, blk, sp::sp_out_smem<DT>(), st, "k_sp_out<norm,pro>", o));
-    else if (out_dtype == MHLA_F16) RC(launch(sp::k_sp_out<ET, DT, f16_t, true, false, 1, true>, g, blk, sp::sp_out_smem<DT>(), st, "k_sp_out<norm,pro>", o));
-    else                            RC(launch(sp::k_sp_out<ET, DT, float, true, false, 1, true>, g, blk, sp::sp_out_smem<DT>(), st, "k_sp_out<norm,pro>", o));
+    if (out_dtype == MHLA_BF16)     RC(launch(sp::k_sp_out<ET, DT, bf16_t, SF_P24, BLOCK>, g, blk, sp::sp_out_smem<DT, SF_P24>(), st, "k_sp_out<norm,pro>", o));
+    else if (out_dtype == MHLA_F16) RC(launch(sp::k_sp_out<ET, DT, f16_t, SF_P24, BLOCK>, g, blk, sp::sp_out_smem<DT, SF_P24>(), st, "k_sp_out<norm,pro>", o));
+    else                            RC(launch(sp::k_sp_out<ET, DT, float, SF_P24, BLOCK>, g, blk, sp::sp_out_smem<DT, SF_P24>(), st, "k_sp_out<norm,pro>", o));
     return MHLA_OK;
 }
 

@@ -145,12 +145,7 @@ inline int dt_for(int D) { return D <= 32 ? 2 : D <= 64 ? 4 : D <= 80 ? 5 : D <=
         default: return fail(MHLA_ENOTSUP, "head dim tile %d not supported", dt);\
     }
 
-// Storage format of the D x D block summaries KV, G, dG, dKV in the workspace (bm_sumfmt: a function of the call's shape, dtype and
-// flags -- and of the process-wide "fp32_summaries" option -- so that a forward and the backward that reuses its state agree)
-enum { SF_F32 = 0,    // fp32 words
-       SF_P24 = 1,    // 24-bit floats in two planes per row (split.hpp p24): 16 significand bits, 3 bytes
-       SF_H16 = 2,    // fp16 payload x one power-of-two multiplier per row (split.hpp h16): 11 significand bits, 2 bytes -- the default for 16-bit tensors
-       SF_BF16 = 3 }; // single bf16 values (MHLA_FLAG_BF16_SUMMARIES: reduced precision, opt-in)
+// (the summary format of a call: the SF_* values of common.hpp, picked by bm_sumfmt below)
 struct BmWs {
     float *kv, *g, *z, *ksum, *ninv, *dg, *dkv, *dn, *dz, *dks, *dwp;
     unsigned short* olo;   // forward region: O - fl(O) as bf16 [bh][M S][D] (16-bit tensors at the default arithmetic), or null
@@ -336,7 +331,7 @@ constexpr const char* N_DW_REDUCE = "k_dw_reduce";
 // branching is plan field -> template instantiation -- and mhla_describe_dispatch prints it, names included.
 enum BmKern { K_NONE, K_BM_STATE, K_SP_STATE, K_S16_STATE, K_MIX, K_SP_MIX, K_SP_MIXR, K_SP_MIXR_DMA, K_SP_MIXH, K_SP_MIXH2,
               K_SP_DWR, K_SP_DW, K_SP_DWT, K_DW, K_BM_OUT, K_SP_OUT, K_S16_OUT, K_BM_TOK, K_SP_TOK, K_S16_TOK };
-constexpr int mixr_slice(bool s16) { return s16 ? 128 : 64; }   // sp::mixr_te<4, S16>() (asserted in capi_bm_typed.hpp): the slice the resident mixing needs whole
+constexpr int mixr_slice(bool s16) { return s16 ? 128 : 64; }   // sp::mixr_te<4, FMT>() (asserted in capi_bm_typed.hpp): the slice the resident mixing needs whole
 struct BmPlan {
     int fmt;             // SF_*
     bool sp;             // split-operand kernels (false: the generic fp32-MFMA ones, dense rows, nothing kept for the backward)

@@ -157,6 +157,18 @@ __device__ __forceinline__ float fmrot_map(float x, int fmap) {
 __device__ __forceinline__ float fmrot_lo(float x0, float x1, float c, float s) { return fmaf(x0, c, -(x1 * s)); }   // y[i]
 __device__ __forceinline__ float fmrot_hi(float x0, float x1, float c, float s) { return fmaf(x1, c, x0 * s); }      // y[i + K/2]
 
+// Storage format of the D x D block summaries KV, G, dG, dKV of the block-mixing operator in its workspace.  The host picks it per call
+// (capi_common.hpp bm_sumfmt: a function of the call's shape, dtype and flags -- and of the process-wide "fp32_summaries" option -- so
+// that a forward and the backward that reuses its state agree); the split-operand kernels (split.hpp) take it as their FMT parameter.
+enum { SF_F32 = 0,    // fp32 words
+       SF_P24 = 1,    // 24-bit floats in two planes per row (split.hpp p24): 16 significand bits, 3 bytes
+       SF_H16 = 2,    // fp16 payload x one power-of-two multiplier per row (split.hpp h16): 11 significand bits, 2 bytes -- the default for 16-bit tensors
+       SF_BF16 = 3 }; // single bf16 values (MHLA_FLAG_BF16_SUMMARIES: reduced precision, opt-in)
+// the format's products take a bf16 hi + lo operand pair (SF_BF16: the stored value is the one operand, no lo tile)
+__host__ __device__ constexpr bool sf_has_lo(int fmt) { return fmt != SF_BF16; }
+// a reader's unit is 8 elements of a packed row: a 16-byte piece of the 2-byte plane (and, p24, an 8-byte piece of the third-byte plane)
+__host__ __device__ constexpr bool sf_packed(int fmt) { return fmt == SF_P24 || fmt == SF_H16; }
+
 // h16: a 2-byte storage format of block / chunk summaries -- an fp16 payload x one power-of-two multiplier per group (a block row of
 // the block-mixing operator, split.hpp; a 16 x 64 strip of a chunk tile of the causal operator, causal_bf16.hpp): 11 significand bits.
 // decode multiplier of a row whose largest magnitude is mx: 2^(floor(log2 mx) - 14), exponent field clamped to [1, 240]

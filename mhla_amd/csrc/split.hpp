@@ -27,7 +27,10 @@ using fast::s16x4;
 using fast::s16x8;
 using fast::u16;
 
-__device__ __forceinline__ bf16x8 row_read8(const u16* tile, int ld, int c0, int k0, int lane);   // (defined with the token-gradient kernels)
+// A operand with the reduction index along the rows' columns: A[m][k] = T[c0 + m][k0 + 8 kg .. + 7]
+__device__ __forceinline__ bf16x8 row_read8(const u16* tile, int ld, int c0, int k0, int lane) {
+    return *reinterpret_cast<const bf16x8*>(tile + (c0 + (lane & 15)) * ld + k0 + (lane >> 4) * 8);
+}
 
 template <typename T>
 __device__ __forceinline__ void ld8(const T* p, f32x4& a, f32x4& b) {
@@ -151,10 +154,6 @@ __device__ __forceinline__ void p24_unpack8(const uint4& hi, const uint2& lo, f3
 // -------------------------------------------------------------------------------------------------
 // (the format's helpers -- h16_mult_from_max / _from_bound, h16_inv, h16_pack2 / _pack8, h16_split8 -- are in common.hpp: the causal pipeline uses them too)
 
-// Block summaries (KV, G, dG, dKV) are fp32 in the workspace, except for bf16 tensors: there they are stored as bf16 (as on
-// the bf16 fast path), which halves the summary traffic -- the larger share of the bytes when S is small -- and needs no lo part.
-template <typename T> struct Sum16 { static constexpr bool value = std::is_same<T, bf16_t>::value; };
-
 template <int DT> struct Geo {
     static constexpr int CGS = DT > 4 ? 16 : 8;        // column groups of 8 per tile row
     static constexpr int DW = CGS * 8;                 // tile width (columns), >= 16 DT
@@ -205,14 +204,14 @@ template <bool NEW = true>
 __device__ __forceinline__ bf16x8 mat_row_read8(const u16* tile, int ld, int c0, int k0, int lane) {
     return *reinterpret_cast<const bf16x8*>(tile + (c0 + mat_row<NEW>(lane & 15)) * ld + k0 + (lane >> 4) * 8);
 }
-template <int DT, bool S16 = false>   // bf16 summaries: no lo tile
-__host__ __device__ constexpr int sp_out_smem() { return (S16 ? 1 : 2) * Geo<DT>::KST * 32 * mat_ld<DT>() * 2; }
+template <int DT, int FMT>
+__host__ __device__ constexpr int sp_out_smem() { return (sf_has_lo(FMT) ? 2 : 1) * Geo<DT>::KST * 32 * mat_ld<DT>() * 2; }
 
 // EPI: the per-head RMSNorm (x SiLU gate) that follows the operator in the Wan host (wan/mhla_utils.py:356-362) is applied
 // to the token's D outputs before they are stored, in the dtype TO of the host's activations: O is rounded to TO (the
 // `.to(dtype)` at :356), normalised over the head dim in fp32, scaled by the norm weight and the gate, stored once.
-// D x D summary matrix (fp32, or bf16 when S16) -> LDS [KP][LD] hi (/ lo) tiles; rows and columns >= D zero.  NT threads.
-template <int DT, bool S16, int NT = NTHREADS, int P24 = 0>   // P24: 0 fp32 words (or bf16 when S16), 1 24-bit floats, 2 h16
+// D x D summary matrix in the format FMT -> LDS [KP][LD] hi (/ lo) tiles; rows and columns >= D zero.  NT threads.
+template <int DT, int FMT, int NT = NTHREADS>
 __device__ __forceinline__ void stage_mat_split(u16* __restrict__ Gh, u16* __restrict__ Gl, const float* __restrict__ base, long elem_off, int D, int tid) {
     constexpr int LD = mat_ld<DT>(), CGS = Geo<DT>::CGS, RPP = NT / CGS, KP = Geo<DT>::KST * 32;
     const int r0 = tid / CGS, cg = (tid % CGS) * 8;
@@ -221,7 +220,7 @@ __device__ __forceinline__ void stage_mat_split(u16* __restrict__ Gh, u16* __res
     const float* g = base + elem_off;
     const u16* g16 = reinterpret_cast<const u16*>(base) + elem_off;
     float hm = 0.f;   // h16: the row's multiplier
-    if constexpr (P24 == 2) hm = gld<float>(reinterpret_cast<const char*>(base + elem_off) + 2 * D * D);
+    if constexpr (FMT == SF_H16) hm = gld<float>(reinterpret_cast<const char*>(base + elem_off) + 2 * D * D);
     for (int pb = 0; pb < PASSES; pb += UB) {
         f32x4 x[UB][2];
         uint4 x16[UB];
@@ -234,12 +233,12 @@ __device__ __forceinline__ void stage_mat_split(u16* __restrict__ Gh, u16* __res
             x[u][0] = x[u][1] = f32x4{0.f, 0.f, 0.f, 0.f};
             x16[u] = make_uint4(0, 0, 0, 0);
             xl[u] = make_uint2(0, 0);
-            if (P24) {   // 8 elements: a piece of the hi plane and one of the lo plane (elem_off counts floats: the row's start)
+            if (sf_packed(FMT)) {   // 8 elements: a piece of the hi plane and one of the lo plane (elem_off counts floats: the row's start)
                 const int e = r * D + c;
                 const char* rowp = reinterpret_cast<const char*>(base + elem_off);
                 x16[u] = gld<uint4>(rowp + 2 * e);
-                if constexpr (P24 == 1) xl[u] = gld<uint2>(rowp + 2 * D * D + e);
-            } else if (S16) {
+                if constexpr (FMT == SF_P24) xl[u] = gld<uint2>(rowp + 2 * D * D + e);
+            } else if (FMT == SF_BF16) {
                 x16[u] = gld<uint4>(g16 + (long)r * D + c);
             } else {
                 const float* src = g + (long)r * D + c;
@@ -256,15 +255,15 @@ __device__ __forceinline__ void stage_mat_split(u16* __restrict__ Gh, u16* __res
                 xl[u] = make_uint2(0, 0);
             }
             if (r < KP && cg < KP) {
-                if (P24 == 2) {
+                if (FMT == SF_H16) {
                     uint4 hi, lo;
                     h16_split8(x16[u], hm, hi, lo);
                     *reinterpret_cast<uint4*>(Gh + off) = hi;
                     *reinterpret_cast<uint4*>(Gl + off) = lo;
-                } else if (P24) {
+                } else if (FMT == SF_P24) {
                     *reinterpret_cast<uint4*>(Gh + off) = x16[u];
                     *reinterpret_cast<uint4*>(Gl + off) = p24_lo8(x16[u], xl[u]);
-                } else if (S16) {
+                } else if (FMT == SF_BF16) {
                     *reinterpret_cast<uint4*>(Gh + off) = x16[u];
                 } else {
                     uint4 hi, lo;
@@ -286,8 +285,8 @@ __device__ __forceinline__ void stage_mat_split(u16* __restrict__ Gh, u16* __res
 #ifndef SP_PAYLOAD_OPERANDS
 #define SP_PAYLOAD_OPERANDS 1
 #endif
-template <typename T, int DT, int P24, bool ROPE = false>
-__host__ __device__ constexpr bool sp_payop() { return SP_PAYLOAD_OPERANDS && P24 == 2 && sizeof(T) == 2 && DT <= 4 && !ROPE; }
+template <typename T, int DT, int FMT, bool ROPE = false>
+__host__ __device__ constexpr bool sp_payop() { return SP_PAYLOAD_OPERANDS && FMT == SF_H16 && sizeof(T) == 2 && DT <= 4 && !ROPE; }
 // h16 row of a D x D summary -> ONE LDS plane [KP][mat_ld] of its payload, undecoded, in the mat_row layout (mat_row_read8 /
 // mat_tr_read8 then deliver fp16 operands: as_f16x8); rows and columns >= D zero.  Returns the row's multiplier m.  Through registers,
 // not global_load_lds_dwordx4: the LDS-DMA writes a wave's 64 pieces back to back, which allows neither the padded row stride nor
@@ -366,8 +365,8 @@ template <int DT, bool ONEP = false> __host__ __device__ constexpr int sp_state_
     return 4 * 32 * (ONEP ? Geo<DT>::LD : Geo<DT>::LDR) * 2 + Geo<DT>::DW * 4 + (ONEP ? 1 : 2) * Geo<DT>::KST * 32 * mat_ld<DT>() * 2 + 2 * 32 * 4;
 }
 // fp16 tensors keep the hi + lo form: their Kl tile holds q's lo part, and a fifth tile would cost the form its gain
-template <typename T, int DT, int P24>
-__host__ __device__ constexpr bool sp_payrd() { return sp_payop<T, DT, P24>() && std::is_same<T, bf16_t>::value; }
+template <typename T, int DT, int FMT>
+__host__ __device__ constexpr bool sp_payrd() { return sp_payop<T, DT, FMT>() && std::is_same<T, bf16_t>::value; }
 static_assert(!SP_PAYLOAD_OPERANDS || 5 * sp_state_rd_smem<4, true>() <= 160 * 1024, "five k_sp_state<1> (row dots from G) workgroups per CU at D = 64");
 
 // MODE 0 (forward):  out = KV_j = K_j^T V_j; ksum_j; z_j                      x = k_num, y = v, kd = k_den, qd = q_den
@@ -378,30 +377,32 @@ static_assert(!SP_PAYLOAD_OPERANDS || 5 * sp_state_rd_smem<4, true>() <= 160 * 1
 // the staging and accumulator registers per thread (<= 128 VGPRs: two workgroups = 16 waves per CU) and half the time per block,
 // which matters at the Wan shape for a second reason: 1 800 blocks on 768 four-wave slots are 2.3 rounds that cost 3, on 512
 // eight-wave slots of half the duration 3.5 rounds that cost 4 (of half the length).
-// S16: the summary is stored as bf16 (the opt-in MHLA_FLAG_BF16_SUMMARIES arithmetic on bf16 tensors); otherwise fp32, and the
-// one operand that is an INTERMEDIATE (dP = dO / n, MODE 1) is split into hi + lo parts whatever the tensor type
+// FMT: the format `out` is stored in (and G_i read in, where the row dots come from it).  SF_BF16 is the opt-in MHLA_FLAG_BF16_SUMMARIES
+// arithmetic on bf16 tensors; otherwise the one operand that is an INTERMEDIATE (dP = dO / n, MODE 1) is split into hi + lo parts
+// whatever the tensor type
 // PRO (MODE 0, Wan inference): x and qd are 16-bit projection outputs; relu(x * rstd[token] * w[channel]) + eps is applied on load
 // (StateArgs::pro_*), the values then carry a lo part like fp32 tensors
 // TS: the call may have a third token tensor (MODE 0: the split pair's k_den, MODE 1: the forward output).  false (MODE 0, picked by the
 // launch when the call has no split normaliser pair): no third row stream -- it was pointed at the key rows again and its values zeroed,
 // half as many requests again in the chunk loop -- and no registers for it
-template <typename T, int DT, int MODE, bool ROPE = false, int NT = NTHREADS, bool S16 = Sum16<T>::value, int P24 = 0, bool PRO = false, bool TS = true>
-__global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state(const StateArgs a) {
+struct StateVar { bool rope = false, pro = false, ts = true; };
+template <typename T, int DT, int MODE, int NT, int FMT, StateVar V = StateVar{}>
+__global__ __launch_bounds__(NT, NT == 512 ? 4 : (V.rope ? 2 : 3)) void k_sp_state(const StateArgs a) {
+    constexpr bool ROPE = V.rope, PRO = V.pro, TS = V.ts;
     static_assert(TS || MODE == 0, "the backward's third tensor is a property of its arithmetic (RD), not of the call");
-    static_assert(!PRO || (MODE == 0 && !S16), "the prologue on load serves the forward's summary kernel");
-    static_assert(!P24 || !S16, "p24 is a format of the fp32-grade summaries");
+    static_assert(!PRO || (MODE == 0 && FMT != SF_BF16), "the prologue on load serves the forward's summary kernel on fp32-grade summaries");
     // RD: the row dots dO . O = dO' . (Q G_i) are formed from the mixed summary G_i (staged as hi / lo tiles beside the operand tiles): the
     // stored output and its residual are not read, and the forward does not write the residual (capi_common.hpp bm_rowdots_from_g)
-    constexpr bool RD = MODE == 1 && P24 && sizeof(T) == 2 && DT <= 4 && !ROPE;
+    constexpr bool RD = MODE == 1 && sf_packed(FMT) && sizeof(T) == 2 && DT <= 4 && !ROPE;
     constexpr bool THIRD = TS && !RD;   // a third row stream exists
-    constexpr bool PAYRD = RD && sp_payrd<T, DT, P24>();   // the row dots on G_i's payload and fp16 dO rows (kept in the Kl tile)
+    constexpr bool PAYRD = RD && sp_payrd<T, DT, FMT>();   // the row dots on G_i's payload and fp16 dO rows (kept in the Kl tile)
     constexpr bool TN = !RD || PAYRD;   // the token tiles in the conflict-free layout (Geo::LD, mat_row)
     constexpr int DW = Geo<DT>::DW, LD = TN ? Geo<DT>::LD : Geo<DT>::LDR, CGS = Geo<DT>::CGS, RPP = NT / CGS, IT = 32 / RPP, NWV = NT / 64,
                   RT = (DT + NWV - 1) / NWV, TILE = 32 * LD;
     static_assert(IT >= 1 && RPP * IT == 32, "a 32-row chunk must be whole staging passes");
     static_assert(RPP * DW * 4 <= 4 * 32 * LD * 2, "column-sum partials must fit in the tiles");
     constexpr bool LO = !std::is_same<T, bf16_t>::value || PRO;   // the token operands carry a lo part
-    constexpr bool LOY = !std::is_same<T, bf16_t>::value || (MODE == 1 && !S16);   // ... and so does y = dO / n, unless the reduced-precision form was asked for
+    constexpr bool LOY = !std::is_same<T, bf16_t>::value || (MODE == 1 && sf_has_lo(FMT));   // ... and so does y = dO / n, unless the reduced-precision form was asked for
     constexpr int GLD = mat_ld<DT>(), GT = Geo<DT>::KST * 32 * GLD;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u16* Kh = reinterpret_cast<u16*>(smem_raw);
@@ -465,7 +466,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
     const float* nvp = (MODE == 1 && a.normalize) ? ninvb : reinterpret_cast<const float*>(a.x.ptr);
     // MODE 1, 16-bit tensors at the default arithmetic: the residual of the forward's store of O (StateArgs::olo), fetched with
     // the rows (unconditionally: without it, the first bytes of x, dropped in `settle`)
-    constexpr bool OLO = MODE == 1 && !S16 && sizeof(T) == 2 && !RD;
+    constexpr bool OLO = MODE == 1 && sf_has_lo(FMT) && sizeof(T) == 2 && !RD;
     const bool olo_on = OLO && a.normalize && a.olo != nullptr;
     const u16* olop = olo_on ? a.olo + ((long)bh * a.M * S + p0) * D + cgc : reinterpret_cast<const u16*>(a.x.ptr);
     uint4 ox[OLO ? IT : 1];
@@ -602,7 +603,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
     if constexpr (RD) {   // (its loads travel with the first chunk's; the loop's first barrier covers the tiles)
         if (a.normalize) {
             if constexpr (PAYRD) gm = stage_mat_payload<DT, NT>(Gh, a.g, ((long)bh * a.M + blk) * a.es, D, tid);
-            else stage_mat_split<DT, false, NT, P24>(Gh, Gl, a.g, ((long)bh * a.M + blk) * a.es, D, tid);
+            else stage_mat_split<DT, FMT, NT>(Gh, Gl, a.g, ((long)bh * a.M + blk) * a.es, D, tid);
         }
     }
     // one 32-token chunk: commit, request the next one (PF: there is one -- a compile-time fact of the call site, so that no branch sits
@@ -699,9 +700,9 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
     // segments (k_sp_state ran at 3.9 TB/s of its bytes at C2)
     constexpr int CW = (DW > 64 && NWV == 8) ? 64 : DW, LDO = CW + 4, PPRO = CW / 4;
     static_assert(NWV * 16 * LDO * 4 <= 4 * 32 * LD * 2, "the staging tiles of all waves must fit in the operand tiles");
-    const bool staged = !S16 && (P24 || ((D & 3) == 0 && (a.es & 3) == 0));   // (uniform; p24: D % 8 == 0 by the path's shape test)
+    const bool staged = sf_has_lo(FMT) && (sf_packed(FMT) || ((D & 3) == 0 && (a.es & 3) == 0));   // (uniform; p24: D % 8 == 0 by the path's shape test)
     float hinv = 0.f;   // h16: 1 / the row's multiplier
-    if constexpr (P24 == 2) {
+    if constexpr (FMT == SF_H16) {
         // the row's multiplier from the summary's largest magnitude: lane -> wave (shuffles) -> workgroup (NWV floats in `vecd`, free until
         // the column sums); padded rows / columns are zero products and do not matter
         float mx = 0.f;
@@ -735,7 +736,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
 #pragma unroll
                             for (int r = 0; r < 4; ++r) Os[(kg * 4 + r) * LDO + ct * 16 - c0 + nl] = acc[rt][ct][r];
                     __builtin_amdgcn_wave_barrier();
-                    if constexpr (P24) {   // units of 8 elements: a 16-byte piece of the hi plane and an 8-byte piece of the lo plane
+                    if constexpr (sf_packed(FMT)) {   // units of 8 elements: a 16-byte piece of the hi plane and an 8-byte piece of the lo plane
 #pragma unroll
                         for (int p = 0; p < CW / 32; ++p) {
                             const int v = lane + 64 * p, row = v / (CW / 8), c8 = v % (CW / 8);
@@ -743,7 +744,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
                             if (grow < D && gcol < D) {
                                 const float* src = Os + row * LDO + c8 * 8;
                                 const int e = grow * D + gcol;
-                                if constexpr (P24 == 2) {
+                                if constexpr (FMT == SF_H16) {
                                     gst<uint4>(reinterpret_cast<char*>(ob) + 2 * e, h16_pack8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), hinv));
                                 } else {
                                 uint4 hi;
@@ -776,7 +777,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (ROPE ? 2 : 3)) void k_sp_state
             for (int r = 0; r < 4; ++r) {
                 const int row = (wave * RT + rt) * 16 + kg * 4 + r, col = ct * 16 + nl;
                 if (row < D && col < D) {
-                    if (S16) reinterpret_cast<u16*>(a.out)[((long)bh * a.M + blk) * a.es + (long)row * D + col] = cvt_bf16(acc[rt][ct][r]);
+                    if (FMT == SF_BF16) reinterpret_cast<u16*>(a.out)[((long)bh * a.M + blk) * a.es + (long)row * D + col] = cvt_bf16(acc[rt][ct][r]);
                     else                 ob[(long)row * D + col] = acc[rt][ct][r];
                 }
             }
@@ -853,9 +854,9 @@ static_assert(64 * (SPM_TE + 4) * 4 <= SP_MIX_SMEM, "output staging must fit in 
 // bf16 summaries: no lo tiles and a bf16 output staging [64][SPM_LD]: half the LDS, twice the resident workgroups
 constexpr int SP_MIX_SMEM16 = 2 * SPM_TILE * 2;
 static_assert(64 * SPM_LD * 2 <= SP_MIX_SMEM16, "bf16 output staging must fit in the input tiles");
-template <bool S16> constexpr int sp_mix_smem() { return S16 ? SP_MIX_SMEM16 : SP_MIX_SMEM; }
+template <int FMT> constexpr int sp_mix_smem() { return FMT == SF_BF16 ? SP_MIX_SMEM16 : SP_MIX_SMEM; }
 
-template <int TRANS, bool S16 = false>   // S16: summaries stored as bf16 (no lo part)
+template <int TRANS, int FMT>   // FMT: fp32 words, or SF_BF16 (no lo part)
 __global__ __launch_bounds__(NTHREADS, 2) void k_sp_mix(const MixArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u16* Xs = reinterpret_cast<u16*>(smem_raw);
@@ -882,7 +883,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_mix(const MixArgs a) {
 #pragma unroll
             for (int u = 0; u < 2; ++u)
                 if (e0 + sc + 64 * u < a.E) {   // E is a multiple of 8
-                    if (S16) {
+                    if (FMT == SF_BF16) {
                         pre16[u] = *reinterpret_cast<const uint4*>(inb16 + (long)row * a.es + sc + 64 * u);
                     } else {
                         const float* src = inb + (long)row * a.es + sc;
@@ -893,10 +894,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_mix(const MixArgs a) {
         }
     };
     auto commit = [&](int buf) {
-        u16* th = Xs + buf * (S16 ? 1 : 2) * SPM_TILE + sr * SPM_LD + sc;
+        u16* th = Xs + buf * (sf_has_lo(FMT) ? 2 : 1) * SPM_TILE + sr * SPM_LD + sc;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            if (S16) {
+            if (FMT == SF_BF16) {
                 *reinterpret_cast<uint4*>(th + 64 * u) = pre16[u];
             } else {
                 uint4 hi, lo;
@@ -957,18 +958,18 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_mix(const MixArgs a) {
             ah[t] = hi;
             al[t] = (__bf16)(wc[t] - (float)hi);
         }
-        const u16* th = Xs + buf * (S16 ? 1 : 2) * SPM_TILE;
+        const u16* th = Xs + buf * (sf_has_lo(FMT) ? 2 : 1) * SPM_TILE;
 #pragma unroll
         for (int t4 = 0; t4 < 8; t4 += 4) {
             bf16x8 bh_[4], bl_[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 bh_[t] = tr_read8(th, SPM_LD, 0, (t4 + t) * 16, lane);
-                if (!S16) bl_[t] = tr_read8(th + SPM_TILE, SPM_LD, 0, (t4 + t) * 16, lane);
+                if (sf_has_lo(FMT)) bl_[t] = tr_read8(th + SPM_TILE, SPM_LD, 0, (t4 + t) * 16, lane);
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[t4 + t] = mfma_bf16(ah, bh_[t], acc[t4 + t]);
-            if (!S16)
+            if (sf_has_lo(FMT))
 #pragma unroll
                 for (int t = 0; t < 4; ++t) acc[t4 + t] = mfma_bf16(ah, bl_[t], acc[t4 + t]);
 #pragma unroll
@@ -981,7 +982,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_mix(const MixArgs a) {
         }
     }
     __syncthreads();
-    if constexpr (S16) {
+    if constexpr (FMT == SF_BF16) {
         u16* Os = Xs;   // [64][SPM_LD] bf16
 #pragma unroll
         for (int t = 0; t < 8; ++t)
@@ -1011,7 +1012,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_mix(const MixArgs a) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// k_sp_mixr<NW, TRANS, S16>: the same mixing with EVERY block of the (b,h) resident in the workgroup (M <= 16 NW <= 256), the
+// k_sp_mixr<NW, TRANS, FMT>: the same mixing with EVERY block of the (b,h) resident in the workgroup (M <= 16 NW <= 256), the
 // causal path's k_csf_mixf for a full matrix.  A workgroup owns slices of 256-byte row pieces (TE = 64 fp32 or 128 bf16 elements):
 // the slice's rows of all blocks sit in LDS (fp32 summaries as bf16 hi + lo tiles), so every summary byte is read from HBM once
 // (k_sp_mix re-reads a slice per 64-row output tile: 1.5x at M = 150, 4x at M = 256) and the mixing weights of a wave's 16 output
@@ -1112,50 +1113,50 @@ struct MixrArgs {
     const float* zin2;
 };
 // slice width: 256-byte row pieces; 128-byte ones for 16 waves (1024 threads on 128 VGPRs: half the accumulators and staging registers)
-template <int NW, bool S16> __host__ __device__ constexpr int mixr_te() { return (S16 ? 128 : 64) / (NW > 12 ? 2 : 1); }
-template <int NW, bool S16, bool DW = false>
+template <int NW, int FMT> __host__ __device__ constexpr int mixr_te() { return (FMT == SF_BF16 ? 128 : 64) / (NW > 12 ? 2 : 1); }
+template <int NW, int FMT, bool DW = false>
 __host__ __device__ constexpr int sp_mixr_smem() {
-    constexpr int TE = mixr_te<NW, S16>(), ROWS = 16 * NW;
-    return (S16 ? 1 : (DW ? 4 : 2)) * ROWS * (TE + 8) * 2 + (S16 ? ROWS * (TE + 8) * 2 : ROWS * (TE + 4) * 4);
+    constexpr int TE = mixr_te<NW, FMT>(), ROWS = 16 * NW;
+    return (FMT == SF_BF16 ? 1 : (DW ? 4 : 2)) * ROWS * (TE + 8) * 2 + (FMT == SF_BF16 ? ROWS * (TE + 8) * 2 : ROWS * (TE + 4) * 4);
 }
 
 // DW (TRANS 1, fp32 summaries, M <= 128): the kernel also stages the KV rows of every slice (hi + lo, two more tiles) and accumulates
 // dW[i][j] += sum_{e in slice} dG[i][e] KV[j][e] over ALL its slices -- every (b,h) it meets: dW is their sum anyway -- in
 // registers (wave w owns rows i = 16 w .. 16 w + 15, all columns: NW tiles); one [M][M] partial per workgroup at the end, summed in a
 // fixed order by k_dw_reduce.  Replaces k_sp_dw, which read dG and KV a second time (C2 at the default arithmetic: 81 us).
-// P24: the summaries (in, in2, out) are stored as 24-bit floats in two planes per row (p24_pack8).  A thread's unit is then 8 elements
+// p24: the summaries (in, in2, out) are stored as 24-bit floats in two planes per row (p24_pack8).  A thread's unit is then 8 elements
 // of a row -- one 16-byte piece of the hi plane and one 8-byte piece of the lo plane -- instead of a 16-byte piece of 4 floats.
 // (h16 summaries are mixed by k_sp_mixh, mixh.hpp: on the payload, with the fp16 MFMA.  A decode-at-the-commit variant of THIS kernel was
 // built first in round 6 and was no faster than p24: 2-byte rows in 64-element slices put fewer bytes in flight per workgroup.)
-template <int NW, int TRANS, bool S16, bool DW = false, int P24 = 0>
-__global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3) / 4) void k_sp_mixr(const MixrArgs a) {   // (eight waves on 24-bit summaries without dW: 128 VGPRs, two workgroups per CU instead of one at 136)
-    static_assert(!DW || (TRANS == 1 && !S16 && NW <= 8), "dW rides in the backward's fp32 mixing kernel, M <= 128 (twelve waves: 77 spilled registers)");
-    static_assert(P24 == 0 || (P24 == 1 && !S16 && NW <= 12), "p24: fp32-grade summaries, slices of 64 elements");
-    constexpr int TE = mixr_te<NW, S16>(), ROWS = 16 * NW, LD = TE + 8, LDO = TE + 4, NK = (NW + 1) / 2, NT = TE / 16;
-    constexpr int PPR = TE * (S16 ? 2 : 4) / 16;          // 16-byte pieces per row of the slice (16, or 8 with 16 waves)
-    constexpr int NTH = 64 * NW, NP = P24 ? ROWS * 8 / NTH : ROWS * PPR / NTH;   // pieces (P24: units of 8 elements) per thread and slice
-    constexpr int UPR = P24 ? 8 : PPR;                    // ... per row
+template <int NW, int TRANS, int FMT, bool DW = false>   // FMT: fp32 words, p24 or bf16
+__global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && FMT == SF_P24) ? 4 : (NW + 3) / 4) void k_sp_mixr(const MixrArgs a) {   // (eight waves on 24-bit summaries without dW: 128 VGPRs, two workgroups per CU instead of one at 136)
+    static_assert(!DW || (TRANS == 1 && sf_has_lo(FMT) && NW <= 8), "dW rides in the backward's fp32 mixing kernel, M <= 128 (twelve waves: 77 spilled registers)");
+    static_assert(FMT != SF_H16 && (FMT != SF_P24 || NW <= 12), "h16 is mixed by k_sp_mixh; p24: up to twelve waves");
+    constexpr int TE = mixr_te<NW, FMT>(), ROWS = 16 * NW, LD = TE + 8, LDO = TE + 4, NK = (NW + 1) / 2, NT = TE / 16;
+    constexpr int PPR = TE * (FMT == SF_BF16 ? 2 : 4) / 16;          // 16-byte pieces per row of the slice (16, or 8 with 16 waves)
+    constexpr int NTH = 64 * NW, NP = FMT == SF_P24 ? ROWS * 8 / NTH : ROWS * PPR / NTH;   // pieces (p24: units of 8 elements) per thread and slice
+    constexpr int UPR = FMT == SF_P24 ? 8 : PPR;                    // ... per row
     static_assert(NP * NTH == ROWS * UPR, "pieces must tile the slice");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u16* Th = reinterpret_cast<u16*>(smem_raw);
     u16* Tl = Th + ROWS * LD;                                        // (fp32 summaries only)
     u16* Kh = Tl + ROWS * LD;                                        // (DW only: the KV rows of the slice)
     u16* Kl = Kh + ROWS * LD;
-    unsigned char* Os = smem_raw + (S16 ? 1 : (DW ? 4 : 2)) * ROWS * LD * 2;     // bf16 [ROWS][LD] or fp32 [ROWS][LDO]
+    unsigned char* Os = smem_raw + (FMT == SF_BF16 ? 1 : (DW ? 4 : 2)) * ROWS * LD * 2;     // bf16 [ROWS][LD] or fp32 [ROWS][LDO]
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nl = lane & 15, kg = lane >> 4;
     const int M = a.M;
     const long nsl = a.E / TE;
     const long s0 = (long)blockIdx.x * a.spw;
     const int cnt_s = (int)max(0L, min((long)a.spw, a.total - s0));   // this workgroup's summary slices: a consecutive range
     const int nzs = (a.S + TE - 1) / TE;                              // normaliser slices per (b, h): dealt round-robin, see the loops
-    if (cnt_s <= 0 && (S16 || (long)blockIdx.x >= a.ztotal)) return;
+    if (cnt_s <= 0 && (FMT == SF_BF16 || (long)blockIdx.x >= a.ztotal)) return;
     // B operand: B[k = r][n = o] = weight of input block r in output block o = 16 wave + nl, r = 32 ks + 8 kg + t
     bf16x8 wh[NK][1], wl[NK][1];
-    static_assert((TRANS ? 64 * (ROWS + 4) : ROWS * 68) * 4 <= sp_mixr_smem<NW, S16, DW>(), "weight chunk must fit in the tiles");
+    static_assert((TRANS ? 64 * (ROWS + 4) : ROWS * 68) * 4 <= sp_mixr_smem<NW, FMT, DW>(), "weight chunk must fit in the tiles");
     mixr_weights<TRANS, 64 * NW, ROWS, NK, 1>(wh, wl, reinterpret_cast<float*>(smem_raw), a.W, a.ldw, M, wave * 16, tid);
-    constexpr int ESZ = S16 ? 2 : 4;
-    constexpr int SLB = P24 ? 128 : TE * ESZ;             // bytes of a slice in a summary row (P24: of its hi plane)
-    // P24: the lo piece of a unit relative to its hi piece (goff + 16 c of slice es): lo plane at 2 E, slice at 64 es, piece at 8 c
+    constexpr int ESZ = FMT == SF_BF16 ? 2 : 4;
+    constexpr int SLB = FMT == SF_P24 ? 128 : TE * ESZ;             // bytes of a slice in a summary row (p24: of its hi plane)
+    // p24: the lo piece of a unit relative to its hi piece (goff + 16 c of slice es): lo plane at 2 E, slice at 64 es, piece at 8 c
     auto lo_rel = [&](int es, int c) { return (long)2 * a.E - 64 * es - 8 * c; };
     // byte offset of slice (bh, es); a workgroup's slices are consecutive, so the pair is advanced rather than divided out per
     // slice (the 64-bit division was 150 instructions with branches between the barrier and the next slice's loads)
@@ -1167,20 +1168,19 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
         const int v = tid + p * NTH, row = v / UPR, c = v % UPR;
-        goff[p] = (unsigned)((long)(row < M ? row : M - 1) * a.es * ESZ + c * 16);   // (P24: the unit's hi piece; its lo piece: lo_rel)
+        goff[p] = (unsigned)((long)(row < M ? row : M - 1) * a.es * ESZ + c * 16);   // (p24: the unit's hi piece; its lo piece: lo_rel)
     }
-    // staging registers.  P24: pre = hi piece, prl = lo piece; a normaliser slice (plain floats) takes the unit's 8 floats in pre + prz
+    // staging registers.  p24: pre = hi piece, prl = lo piece; a normaliser slice (plain floats) takes the unit's 8 floats in pre + prz
     struct Stage {
-        uint4 pre[NP], pre2[DW ? NP : 1], prz[P24 ? NP : 1], prz2[(P24 && DW) ? NP : 1];
-        u32x2_t prl[P24 ? NP : 1], prl2[(P24 && DW) ? NP : 1];   // (native vectors: an array of uint2 in here stays in scratch)
+        uint4 pre[NP], pre2[DW ? NP : 1], prz[FMT == SF_P24 ? NP : 1], prz2[(FMT == SF_P24 && DW) ? NP : 1];
+        u32x2_t prl[FMT == SF_P24 ? NP : 1], prl2[(FMT == SF_P24 && DW) ? NP : 1];   // (native vectors: an array of uint2 in here stays in scratch)
     };
     // (A second slice in flight per workgroup -- two Stage objects, the loop unrolled by two -- gained nothing: hipcc's wait in front of
     // the commit is vmcnt(0), i.e. for both.  Nor did starting the workgroups of a CU a fraction of an iteration apart, or fetching and
     // storing the lo pieces of an even / odd slice pair together, whole 128-byte lines at a time.)
-    constexpr int NBUF = 1;
     Stage sga;
     // a normaliser slice: rows of S floats, pieces past the row's end are not touched (zeros)
-    constexpr int ZPB = P24 ? 32 : 16, ZPF = ZPB / 4;   // bytes / floats of a thread's piece of a normaliser row
+    constexpr int ZPB = FMT == SF_P24 ? 32 : 16, ZPF = ZPB / 4;   // bytes / floats of a thread's piece of a normaliser row
     auto zoff = [&](int p) { const int v = tid + p * NTH, row = v / UPR, c = v % UPR; return (unsigned)((row < M ? row : M - 1) * a.S * 4 + c * ZPB); };
     auto zlive = [&](int p, int es, int half = 0) { return ((tid + p * NTH) % UPR) * ZPF + half * 4 + es * TE < a.S; };
     const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
@@ -1212,14 +1212,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 g.pre[p] = zld(base, p, es, 0);
-                if constexpr (P24) g.prz[p] = zld(base, p, es, 1);
+                if constexpr (FMT == SF_P24) g.prz[p] = zld(base, p, es, 1);
             }
             if constexpr (DW) {
                 const char* base2 = reinterpret_cast<const char*>(a.zin2) + boff;
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
                     g.pre2[p] = zld(base2, p, es, 0);
-                    if constexpr (P24) g.prz2[p] = zld(base2, p, es, 1);
+                    if constexpr (FMT == SF_P24) g.prz2[p] = zld(base2, p, es, 1);
                 }
             }
             return;
@@ -1228,14 +1228,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             g.pre[p] = gld_stream16(base + goff[p]);
-            if constexpr (P24) g.prl[p] = *(const MHLA_GLOBAL_AS u32x2_t*)(base + goff[p] + lo_rel(es, (tid + p * NTH) % UPR));
+            if constexpr (FMT == SF_P24) g.prl[p] = *(const MHLA_GLOBAL_AS u32x2_t*)(base + goff[p] + lo_rel(es, (tid + p * NTH) % UPR));
         }
         if constexpr (DW) {
             const char* base2 = reinterpret_cast<const char*>(a.in2) + boff;
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 g.pre2[p] = gld_stream16(base2 + goff[p]);
-                if constexpr (P24) g.prl2[p] = *(const MHLA_GLOBAL_AS u32x2_t*)(base2 + goff[p] + lo_rel(es, (tid + p * NTH) % UPR));
+                if constexpr (FMT == SF_P24) g.prl2[p] = *(const MHLA_GLOBAL_AS u32x2_t*)(base2 + goff[p] + lo_rel(es, (tid + p * NTH) % UPR));
             }
         }
     };
@@ -1263,7 +1263,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3
     bool pz = false;
     int pzes = 0;
     auto store_slice = [&](long off, bool zslice, int zes) __attribute__((always_inline)) {
-        if constexpr (!S16) {
+        if constexpr (sf_has_lo(FMT)) {
             if (zslice) {   // the normaliser's rows: 1 / (eps + .) in the forward, as they are in the backward
                 char* zb = reinterpret_cast<char*>(a.zout) + off;
 #pragma unroll
@@ -1292,7 +1292,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             const int v = tid + p * NTH, row = v / UPR, c = v % UPR;
-            if constexpr (P24) {
+            if constexpr (FMT == SF_P24) {
                 if (row < M) {
                     const float* src = reinterpret_cast<const float*>(Os) + row * LDO + c * 8;
                     uint4 hi;
@@ -1304,7 +1304,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3
                 continue;
             }
             if (row < M) {
-                const uint4 x = S16 ? *reinterpret_cast<const uint4*>(reinterpret_cast<const u16*>(Os) + row * LD + c * 8)
+                const uint4 x = FMT == SF_BF16 ? *reinterpret_cast<const uint4*>(reinterpret_cast<const u16*>(Os) + row * LD + c * 8)
                                     : *reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(Os) + row * LDO + c * 4);
                 gst<uint4>(ob + goff[p], x);
             }
@@ -1323,7 +1323,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3
             const int v = tid + p * NTH, row = v / UPR, c = v % UPR;
             const bool ok = row < M;   // rows past the last block: zeros (their weights are zero too, but 0 x NaN is not)
             const uint4 x = make_uint4(ok ? g.pre[p].x : 0u, ok ? g.pre[p].y : 0u, ok ? g.pre[p].z : 0u, ok ? g.pre[p].w : 0u);
-            if constexpr (P24) {
+            if constexpr (FMT == SF_P24) {
                 if (zslice) {   // 8 plain floats
                     commit_hl(Th, Tl, zmask(g.pre[p], ok, p, zes, 0), row, 2 * c);
                     commit_hl(Th, Tl, zmask(g.prz[p], ok, p, zes, 1), row, 2 * c + 1);
@@ -1342,7 +1342,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3
                         *reinterpret_cast<uint4*>(Kl + row * LD + c * 8) = p24_lo8(y, yl);
                     }
                 }
-            } else if constexpr (S16) {
+            } else if constexpr (FMT == SF_BF16) {
                 *reinterpret_cast<uint4*>(Th + row * LD + c * 8) = x;
             } else if (zslice) {   // (fp32 summaries: the unit is the 16-byte piece)
                 commit_hl(Th, Tl, zmask(g.pre[p], ok, p, zes, 0), row, c);
@@ -1375,15 +1375,15 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3
                 constexpr int TB = NT < 4 ? NT : 4;   // operand tiles per batch
 #pragma unroll
                 for (int t4 = 0; t4 < NT; t4 += TB) {
-                    bf16x8 sv[TB], sl[S16 ? 1 : TB];
+                    bf16x8 sv[TB], sl[FMT == SF_BF16 ? 1 : TB];
 #pragma unroll
                     for (int t = 0; t < TB; ++t) {
                         sv[t] = tr_read8(Th, LD, ks * 32, (t4 + t) * 16, lane);
-                        if constexpr (!S16) sl[t] = tr_read8(Tl, LD, ks * 32, (t4 + t) * 16, lane);
+                        if constexpr (sf_has_lo(FMT)) sl[t] = tr_read8(Tl, LD, ks * 32, (t4 + t) * 16, lane);
                     }
 #pragma unroll
                     for (int t = 0; t < TB; ++t) acc[t4 + t] = mfma_bf16(sv[t], wh[ks][0], acc[t4 + t]);
-                    if constexpr (!S16) {
+                    if constexpr (sf_has_lo(FMT)) {
 #pragma unroll
                         for (int t = 0; t < TB; ++t) acc[t4 + t] = mfma_bf16(sl[t], wh[ks][0], acc[t4 + t]);
                     }
@@ -1413,7 +1413,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3
         // lane: elements 16 t + 4 kg .. + 3 of output block 16 wave + nl -> staging tile [block][element]
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-            if constexpr (S16)
+            if constexpr (FMT == SF_BF16)
                 *reinterpret_cast<uint2*>(reinterpret_cast<u16*>(Os) + (wave * 16 + nl) * LD + t * 16 + kg * 4) =
                     make_uint2(pack_bf16x2(acc[t][0], acc[t][1]), pack_bf16x2(acc[t][2], acc[t][3]));
             else
@@ -1438,7 +1438,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && !DW && P24 == 1) ? 4 : (NW + 3
             es = ne;
         }
     }
-    if constexpr (!S16) {
+    if constexpr (sf_has_lo(FMT)) {
         bool firstz = cnt_s <= 0;
         for (long zi = blockIdx.x; zi < a.ztotal; zi += gridDim.x) {   // (the first one is not prefetched under the last summary slice)
             const long nzi = zi + gridDim.x;
@@ -1730,15 +1730,17 @@ constexpr int SP_OUT_T = 512;   // 8 waves share the staged G_i: twice the loads
 // OutArgs::nbh = B H; needs at least 8 tiles per block (a round then spans at most two blocks, the next round at most one more).
 // ONE: the launch has S <= 64 -- a wave has its one tile `wave` at the most: no loop, no second row set, no fetch of a next tile (it was
 // clamped onto the block's last row and dropped) and no map look-ahead
-template <typename T, int DT, typename TO = T, bool EPI = false, bool S16 = Sum16<T>::value, int P24 = 0, bool PRO = false, bool FLAT = false, bool ONE = false>   // PRO: the q prologue on load (OutArgs::pro_*)
+struct OutVar { bool epi = false, pro = false, flat = false, one = false; };   // pro: the q prologue on load (OutArgs::pro_*)
+template <typename T, int DT, typename TO, int FMT, OutVar V = OutVar{}>
 #ifndef SP_OUT_EPI_WAVES
 #define SP_OUT_EPI_WAVES 2   // the fused-epilogue variant takes 142 VGPRs: one workgroup per CU without spills (157 us at C4) beats two with 28 spilled registers (163 us)
 #endif
-__global__ __launch_bounds__(SP_OUT_T, EPI ? SP_OUT_EPI_WAVES : 2) void k_sp_out(const OutArgs a) {
+__global__ __launch_bounds__(SP_OUT_T, V.epi ? SP_OUT_EPI_WAVES : 2) void k_sp_out(const OutArgs a) {
+    constexpr bool EPI = V.epi, PRO = V.pro, FLAT = V.flat, ONE = V.one;
     constexpr int LD = mat_ld<DT>(), KST = Geo<DT>::KST, KP = KST * 32, TILE = KP * LD;
     constexpr bool LO = !std::is_same<T, bf16_t>::value || PRO;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    static_assert(!FLAT || (P24 == 1 && sizeof(T) == 2 && !S16), "the flat tile list serves 16-bit tensors with 24-bit summaries");
+    static_assert(!FLAT || (FMT == SF_P24 && sizeof(T) == 2), "the flat tile list serves 16-bit tensors with 24-bit summaries");
     static_assert(!ONE || (!FLAT && SP_OUT_T / 64 >= 4), "one tile per wave: blocks of at most 64 tokens, one block per workgroup");
     u16* Gh = reinterpret_cast<u16*>(smem_raw);   // [d1][d2], rows >= D and columns >= D zero   (FLAT: two (hi, lo) pairs, block parity)
     u16* Gl = Gh + TILE;
@@ -1931,7 +1933,7 @@ __global__ __launch_bounds__(SP_OUT_T, EPI ? SP_OUT_EPI_WAVES : 2) void k_sp_out
                 const bf16x8 a0h = mat_tr_read8<mat_new<DT>()>(Gh, LD, ks * 32, ct * 16, lane), a1h = mat_tr_read8<mat_new<DT>()>(Gh, LD, ks * 32, ct * 16 + 16, lane);
                 c0 = mfma_bf16(a0h, qh[ks], c0);
                 c1 = mfma_bf16(a1h, qh[ks], c1);
-                if (!S16) {
+                if (sf_has_lo(FMT)) {
                     const bf16x8 a0l = mat_tr_read8<mat_new<DT>()>(Gl, LD, ks * 32, ct * 16, lane), a1l = mat_tr_read8<mat_new<DT>()>(Gl, LD, ks * 32, ct * 16 + 16, lane);
                     c0 = mfma_bf16(a0l, qh[ks], c0);
                     c1 = mfma_bf16(a1l, qh[ks], c1);
@@ -2050,8 +2052,8 @@ __global__ __launch_bounds__(SP_OUT_T, EPI ? SP_OUT_EPI_WAVES : 2) void k_sp_out
         if (a.idx) lk = gld<int>(a.idx + p0 + min(wave * 16 + nl, S - 1));   // (uniform branch; nothing is in flight yet)
         fetch(wave, cur, lk);
         if constexpr (!ONE) lk = look(wave + NWV);   // (for the next fetch)
-        // (S16: G_i stored as bf16: no lo tile)
-        stage_mat_split<DT, S16, SP_OUT_T, P24>(Gh, Gl, a.g, ((long)bh * a.M + blk) * a.es, D, tid);
+        // (SF_BF16: no lo tile)
+        stage_mat_split<DT, FMT, SP_OUT_T>(Gh, Gl, a.g, ((long)bh * a.M + blk) * a.es, D, tid);
         __syncthreads();
         if constexpr (ONE) {
             if (wave * 16 < S) {   // (uniform)
@@ -2138,8 +2140,8 @@ constexpr int SP_DW_SMEM = 64 * SP_DW_LD * 4;
 
 // NT: 16-row tiles per side of the output tile (4: 64 x 64; 1 / 2 when M <= 16 / 32, where the full tile would spend 15/16 or 3/4 of
 // its loads and MFMAs on clamped rows); UE = 4 / NT reduction steps per loop iteration keep the same number of loads in flight.
-// P24: both summary sets are 24-bit floats in two planes per row (the hi plane is the hi operand; the lo operand is rebuilt, p24_lo8)
-template <bool S16, int NT = 4, bool P24 = false>
+// FMT: fp32 words, or SF_BF16 (24-bit summaries: dW rides in k_sp_mixr, or k_sp_dwt below)
+template <int FMT, int NT = 4>
 __global__ __launch_bounds__(NTHREADS) void k_sp_dw(const DwArgs a) {
     constexpr int UE = 4 / NT;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -2176,7 +2178,7 @@ __global__ __launch_bounds__(NTHREADS) void k_sp_dw(const DwArgs a) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (long e0 = wbeg; e0 < wend; e0 += 32 * UE) {
-        if constexpr (S16) {   // bf16 summaries: operands as stored
+        if constexpr (FMT == SF_BF16) {   // operands as stored
             bf16x8 xa[UE][NT], ya[UE][NT];
 #pragma unroll
             for (int u = 0; u < UE; ++u) {
@@ -2199,34 +2201,6 @@ __global__ __launch_bounds__(NTHREADS) void k_sp_dw(const DwArgs a) {
             continue;
         }
         uint4 xh[UE][NT], xl[UE][NT], yh[UE][NT], yl[UE][NT];
-        if constexpr (P24) {   // 8 elements: 16 bytes of the hi plane at 2 e, 8 bytes of the lo plane at 2 E + e
-            uint2 xb[UE][NT], yb[UE][NT];
-#pragma unroll
-            for (int u = 0; u < UE; ++u) {
-                const long e = e0 + 32 * u;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    xh[u][t] = yh[u][t] = make_uint4(0, 0, 0, 0);
-                    xb[u][t] = yb[u][t] = make_uint2(0, 0);
-                    if (e < wend) {
-                        const char* xr = reinterpret_cast<const char*>(xp[t] - kg * 8);   // (the row's first byte)
-                        const char* yr = reinterpret_cast<const char*>(yp[t] - kg * 8);
-                        const long ee = e + kg * 8;
-                        xh[u][t] = gld<uint4>(xr + 2 * ee);
-                        xb[u][t] = gld<uint2>(xr + 2 * E + ee);
-                        yh[u][t] = gld<uint4>(yr + 2 * ee);
-                        yb[u][t] = gld<uint2>(yr + 2 * E + ee);
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UE; ++u)
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    xl[u][t] = p24_lo8(xh[u][t], xb[u][t]);
-                    yl[u][t] = p24_lo8(yh[u][t], yb[u][t]);
-                }
-        } else {
         f32x4 raw[UE][2 * NT][2];
 #pragma unroll
         for (int u = 0; u < UE; ++u) {
@@ -2249,7 +2223,6 @@ __global__ __launch_bounds__(NTHREADS) void k_sp_dw(const DwArgs a) {
                 split8(raw[u][t][0], raw[u][t][1], xh[u][t], xl[u][t]);
                 split8(raw[u][NT + t][0], raw[u][NT + t][1], yh[u][t], yl[u][t]);
             }
-        }
 #pragma unroll
         for (int u = 0; u < UE; ++u) {
 #pragma unroll
@@ -2288,7 +2261,8 @@ __global__ __launch_bounds__(NTHREADS) void k_sp_dw(const DwArgs a) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// k_sp_dwt<P24>: the same partials as k_sp_dw for fp32-grade summaries (fp32 words or 24-bit floats) and more than 128 blocks, with the
+// k_sp_dwt: the same partials as k_sp_dw for 24-bit summaries (two planes per row: the hi plane is the hi operand, the lo operand is
+// rebuilt, p24_lo8) and more than 128 blocks, with the
 // operand rows STAGED THROUGH LDS: k_sp_dw's lanes fetch their MFMA operands straight from memory -- 16 rows x 64 bytes (32 for the lo
 // plane) per load instruction -- and ran at 2.1-2.6 TB/s of its bytes (C4: 127 us, the 256 x 16 variant: 490 us).  Here a workgroup walks
 // its E-slice in chunks of 64 elements: 64 rows of dG and 64 rows of KV as 256-byte (128 + 64) row pieces, 16 or 8 lanes per row, the
@@ -2299,8 +2273,9 @@ __global__ __launch_bounds__(NTHREADS) void k_sp_dw(const DwArgs a) {
 // shape keeps k_sp_dw, whose waves multiply whole 64 x 64 tiles from registers.
 // -------------------------------------------------------------------------------------------------
 constexpr int SP_DWT_LD = 72, SP_DWT_SMEM = 4 * 64 * SP_DWT_LD * 2;
-template <bool P24>
+template <int FMT>   // (a template so that only the units that launch it carry it: a plain kernel in this header is emitted by every unit)
 __global__ __launch_bounds__(NTHREADS, 2) void k_sp_dwt(const DwArgs a) {
+    static_assert(FMT == SF_P24, "fp32 words keep k_sp_dw (above)");
     constexpr int LD = SP_DWT_LD, CE = 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u16* Xh = reinterpret_cast<u16*>(smem_raw);
@@ -2328,23 +2303,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_dwt(const DwArgs a) {
         xr[p] = reinterpret_cast<const char*>(a.x + ((long)bh * M + min(i0 + urow[p], M - 1)) * a.es);
         yr[p] = reinterpret_cast<const char*>(a.y + ((long)bh * M + min(j0 + urow[p], M - 1)) * a.es);
     }
-    uint4 xa[2], xb[2], ya[2], yb[2];   // fp32: the unit's 8 floats; P24: xa = hi piece, xb.xy = lo piece
+    uint4 xa[2], xb[2], ya[2], yb[2];   // xa = hi piece, xb.xy = lo piece
     auto issue = [&](long e0) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             const long e = e0 + ucol[p];
-            if constexpr (P24) {
-                xa[p] = gld_stream16(xr[p] + 2 * e);
-                ya[p] = gld_stream16(yr[p] + 2 * e);
-                const uint2 lx = gld<uint2>(xr[p] + 2 * E + e), ly = gld<uint2>(yr[p] + 2 * E + e);
-                xb[p] = make_uint4(lx.x, lx.y, 0u, 0u);
-                yb[p] = make_uint4(ly.x, ly.y, 0u, 0u);
-            } else {
-                xa[p] = gld_stream16(xr[p] + 4 * e);
-                xb[p] = gld_stream16(xr[p] + 4 * e + 16);
-                ya[p] = gld_stream16(yr[p] + 4 * e);
-                yb[p] = gld_stream16(yr[p] + 4 * e + 16);
-            }
+            xa[p] = gld_stream16(xr[p] + 2 * e);
+            ya[p] = gld_stream16(yr[p] + 2 * e);
+            const uint2 lx = gld<uint2>(xr[p] + 2 * E + e), ly = gld<uint2>(yr[p] + 2 * E + e);
+            xb[p] = make_uint4(lx.x, lx.y, 0u, 0u);
+            yb[p] = make_uint4(ly.x, ly.y, 0u, 0u);
         }
     };
     auto commit = [&]() __attribute__((always_inline)) {
@@ -2352,16 +2320,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_dwt(const DwArgs a) {
         for (int p = 0; p < 2; ++p) {
             const bool okx = i0 + urow[p] < M, oky = j0 + urow[p] < M;   // rows past the last block: zeros
             const int off = urow[p] * LD + ucol[p];
-            uint4 hx, lx, hy, ly;
-            if constexpr (P24) {
-                hx = xa[p];
-                lx = p24_lo8(xa[p], make_uint2(xb[p].x, xb[p].y));
-                hy = ya[p];
-                ly = p24_lo8(ya[p], make_uint2(yb[p].x, yb[p].y));
-            } else {
-                split8(__builtin_bit_cast(f32x4, xa[p]), __builtin_bit_cast(f32x4, xb[p]), hx, lx);
-                split8(__builtin_bit_cast(f32x4, ya[p]), __builtin_bit_cast(f32x4, yb[p]), hy, ly);
-            }
+            const uint4 hx = xa[p], lx = p24_lo8(xa[p], make_uint2(xb[p].x, xb[p].y));
+            const uint4 hy = ya[p], ly = p24_lo8(ya[p], make_uint2(yb[p].x, yb[p].y));
             // (component-wise: a select of whole uint4 structs goes through the stack)
             auto sel = [](bool ok, const uint4& v) { return make_uint4(ok ? v.x : 0u, ok ? v.y : 0u, ok ? v.z : 0u, ok ? v.w : 0u); };
             *reinterpret_cast<uint4*>(Xh + off) = sel(okx, hx);
@@ -2424,20 +2384,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_dwt(const DwArgs a) {
 // -------------------------------------------------------------------------------------------------
 // k_sp_bwd_dq: the staged G_i (ONEP: one payload plane, sp_payop), the waves' dksum partials [4][DW] and ksum [DW] -- not the store
 // strips of k_sp_bwd_dkv below, which cost it a third of its workgroups per CU while it was launched with sp_tok_smem
-template <int DT, bool S16 = false, bool ONEP = false>
+template <int DT, int FMT, bool ONEP = false>
 __host__ __device__ constexpr int sp_dq_smem() {
-    return ((S16 || ONEP) ? 1 : 2) * Geo<DT>::KST * 32 * mat_ld<DT>() * 2 + Geo<DT>::DW * 4 * 4 + Geo<DT>::DW * 4;
+    return ((sf_has_lo(FMT) && !ONEP) ? 2 : 1) * Geo<DT>::KST * 32 * mat_ld<DT>() * 2 + Geo<DT>::DW * 4 * 4 + Geo<DT>::DW * 4;
 }
-static_assert(6 * sp_dq_smem<4, false, false>() <= 160 * 1024 && 6 * sp_dq_smem<4, false, true>() <= 160 * 1024, "six k_sp_bwd_dq workgroups per CU at D = 64");
-template <int DT, bool S16 = false>
+static_assert(6 * sp_dq_smem<4, SF_F32>() <= 160 * 1024 && 6 * sp_dq_smem<4, SF_H16, true>() <= 160 * 1024, "six k_sp_bwd_dq workgroups per CU at D = 64");
+template <int DT, int FMT>
 __host__ __device__ constexpr int sp_tok_smem() {
     // (+ k_sp_bwd_dkv's row staging for 16-bit tensors with rows of up to 128 bytes: [4 waves][dK, dV][16 tokens][DW + 8] 16-bit values)
-    return sp_dq_smem<DT, S16>() + (DT <= 4 ? 4 * 2 * 16 * (Geo<DT>::DW + 8) * 2 : 0);
-}
-
-// A operand with the reduction index along the rows' columns: A[m][k] = T[c0 + m][k0 + 8 kg .. + 7]
-__device__ __forceinline__ bf16x8 row_read8(const u16* tile, int ld, int c0, int k0, int lane) {
-    return *reinterpret_cast<const bf16x8*>(tile + (c0 + (lane & 15)) * ld + k0 + (lane >> 4) * 8);
+    return sp_dq_smem<DT, FMT>() + (DT <= 4 ? 4 * 2 * 16 * (Geo<DT>::DW + 8) * 2 : 0);
 }
 
 // ROPE: the numerator pair was rotated inside the forward (q_den aliases the un-rotated q): dQ_rot is turned back by the
@@ -2446,14 +2401,16 @@ __device__ __forceinline__ bf16x8 row_read8(const u16* tile, int ld, int c0, int
 // the output layout, where the relu gradient mask needs it (a template flag: both register sets at once cost the occupancy)
 // ONE: the launch has S <= 64, so a wave has at most its one tile `wave`: no loop, no second row set and no look-ahead -- the loop's
 // unconditional prefetch asked for the wave's own rows a second time there (every dO and q_den piece, 1 / n, dz and a map entry)
-template <typename T, int DT, bool ROPE = false, bool S16 = Sum16<T>::value, bool WQ = false, int P24 = 0, bool ONE = false>
-__global__ __launch_bounds__(NTHREADS, (DT <= 4 && WQ) ? 4 : 2) void k_sp_bwd_dq(const TokArgs a) {
+struct DqVar { bool rope = false, wq = false, one = false; };
+template <typename T, int DT, int FMT, DqVar V = DqVar{}>
+__global__ __launch_bounds__(NTHREADS, (DT <= 4 && V.wq) ? 4 : 2) void k_sp_bwd_dq(const TokArgs a) {
+    constexpr bool ROPE = V.rope, WQ = V.wq, ONE = V.one;
     constexpr int LD = mat_ld<DT>(), DW = Geo<DT>::DW, KST = Geo<DT>::KST, TILE = KST * 32 * LD;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr bool PAYOP = sp_payop<T, DT, P24, ROPE>();   // G_i as ONE plane of its h16 payload, dO rows as scaled fp16 operands
+    constexpr bool PAYOP = sp_payop<T, DT, FMT, ROPE>();   // G_i as ONE plane of its h16 payload, dO rows as scaled fp16 operands
     u16* Gh = reinterpret_cast<u16*>(smem_raw);
     u16* Gl = Gh + TILE;                                  // not allocated for bf16 summaries (or PAYOP)
-    float* dksw = reinterpret_cast<float*>(Gh + ((S16 || PAYOP) ? 1 : 2) * TILE);   // [4 waves][DW]
+    float* dksw = reinterpret_cast<float*>(Gh + ((sf_has_lo(FMT) && !PAYOP) ? 2 : 1) * TILE);   // [4 waves][DW]
     float* ksum = dksw + 4 * DW;                          // [DW]
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nl = lane & 15, kg = lane >> 4;
     const int blk = blockIdx.x, bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H, S = a.S, D = a.D, M = a.M;
@@ -2517,7 +2474,7 @@ __global__ __launch_bounds__(NTHREADS, (DT <= 4 && WQ) ? 4 : 2) void k_sp_bwd_dq
     const float ksum_v = gld<float>(a.normalize ? a.ksum + ((long)bh * M + blk) * D + min(tid, D - 1) : standin);
     float gm = 1.f;   // PAYOP: the multiplier of G_i's payload
     if constexpr (PAYOP) gm = stage_mat_payload<DT>(Gh, a.g, ((long)bh * M + blk) * a.es, D, tid);
-    else stage_mat_split<DT, S16, NTHREADS, P24>(Gh, Gl, a.g, ((long)bh * M + blk) * a.es, D, tid);
+    else stage_mat_split<DT, FMT>(Gh, Gl, a.g, ((long)bh * M + blk) * a.es, D, tid);
     if (tid < DW) ksum[tid] = (a.normalize && tid < D) ? ksum_v : 0.f;
     __syncthreads();
     f32x4 dksp[WQ ? 1 : DT], dksw8[WQ ? KST : 1][2];   // per-lane dksum partials: output layout / operand layout (WQ)
@@ -2594,7 +2551,7 @@ __global__ __launch_bounds__(NTHREADS, (DT <= 4 && WQ) ? 4 : 2) void k_sp_bwd_dq
                 } else {
                     c0 = mfma_bf16(a0h, gh[ks], c0);
                     c1 = mfma_bf16(a1h, gh[ks], c1);
-                    if (!S16) {
+                    if (sf_has_lo(FMT)) {
                         const bf16x8 a0l = mat_row_read8<mat_new<DT>()>(Gl, LD, ct * 16, ks * 32, lane), a1l = mat_row_read8<mat_new<DT>()>(Gl, LD, c1t * 16, ks * 32, lane);
                         c0 = mfma_bf16(a0l, gh[ks], c0);
                         c1 = mfma_bf16(a1l, gh[ks], c1);
@@ -2661,14 +2618,16 @@ __global__ __launch_bounds__(NTHREADS, (DT <= 4 && WQ) ? 4 : 2) void k_sp_bwd_dq
 
 // ROPE: k is the un-rotated tensor: it is rotated on its way into the dV product (KV was formed from the rotated keys), and
 // dK_rot is turned back before dksum is added
-template <typename T, int DT, bool ROPE = false, bool S16 = Sum16<T>::value, int P24 = 0>
+struct DkvVar { bool rope = false; };
+template <typename T, int DT, int FMT, DkvVar V = DkvVar{}>
 __global__ __launch_bounds__(NTHREADS, 2) void k_sp_bwd_dkv(const TokArgs a) {   // (a bound of 4 -- 128 VGPRs, four workgroups per CU at D <= 64 -- measured: C2 +-0, blocks of 256 tokens 85 -> 94 us)
+    constexpr bool ROPE = V.rope;
     constexpr int LD = mat_ld<DT>(), DW = Geo<DT>::DW, KST = Geo<DT>::KST, TILE = KST * 32 * LD;
     constexpr bool LO = !std::is_same<T, bf16_t>::value;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u16* Gh = reinterpret_cast<u16*>(smem_raw);   // dKV_j [d1][d2]
     u16* Gl = Gh + TILE;                          // not allocated for bf16 summaries
-    float* dks = reinterpret_cast<float*>(Gh + (S16 ? 1 : 2) * TILE);   // [DW]
+    float* dks = reinterpret_cast<float*>(Gh + (sf_has_lo(FMT) ? 2 : 1) * TILE);   // [DW]
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nl = lane & 15, kg = lane >> 4;
     const int blk = blockIdx.x, bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H, S = a.S, D = a.D, M = a.M;
     const long p0 = (long)blk * S;
@@ -2727,7 +2686,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_bwd_dkv(const TokArgs a) {  
     fetch(wave, cur, lk);
     lk = look(wave + 4);
     const float dks_v = gld<float>(a.normalize ? a.dks + ((long)bh * M + blk) * D + min(tid, D - 1) : reinterpret_cast<const float*>(a.dkv));
-    stage_mat_split<DT, S16, NTHREADS, P24>(Gh, Gl, a.dkv, ((long)bh * M + blk) * a.es, D, tid);
+    stage_mat_split<DT, FMT>(Gh, Gl, a.dkv, ((long)bh * M + blk) * a.es, D, tid);
     if (tid < DW) dks[tid] = (a.normalize && tid < D) ? dks_v : 0.f;
     __syncthreads();
 
@@ -2742,8 +2701,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_bwd_dkv(const TokArgs a) {  
         constexpr bool ROWST = sizeof(T) == 2 && DT <= 4;
         constexpr int SLD = DW + 8;
         u16* stk = reinterpret_cast<u16*>(dks + DW) + wave * 2 * 16 * SLD;   // [dK, dV][16][SLD]
-        constexpr bool LATE = false;
-        f32x4 dkall[LATE ? DT : 1], dvall[LATE ? DT : 1];
 #pragma unroll
         for (int ks = 0; ks < KST; ++ks) {
             uint4 hi, lo;
@@ -2777,7 +2734,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_bwd_dkv(const TokArgs a) {  
                 const bf16x8 th = mat_tr_read8<mat_new<DT>()>(Gh, LD, ks * 32, ct * 16, lane);
                 ck = mfma_bf16(ah, vh[ks], ck);
                 cv = mfma_bf16(th, kh[ks], cv);
-                if (!S16) {
+                if (sf_has_lo(FMT)) {
                     const bf16x8 al = mat_row_read8<mat_new<DT>()>(Gl, LD, ct * 16, ks * 32, lane), tl = mat_tr_read8<mat_new<DT>()>(Gl, LD, ks * 32, ct * 16, lane);
                     ck = mfma_bf16(al, vh[ks], ck);
                     cv = mfma_bf16(tl, kh[ks], cv);
@@ -2803,9 +2760,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_bwd_dkv(const TokArgs a) {  
                 const uint2 pv = std::is_same<T, bf16_t>::value ? make_uint2(pack_bf16x2(cv[0], cv[1]), pack_bf16x2(cv[2], cv[3])) : make_uint2(h16_pack2(cv[0], cv[1]), h16_pack2(cv[2], cv[3]));
                 *reinterpret_cast<uint2*>(stk + nl * SLD + ct * 16 + kg * 4) = pk;
                 *reinterpret_cast<uint2*>(stk + 16 * SLD + nl * SLD + ct * 16 + kg * 4) = pv;
-            } else if constexpr (LATE) {
-                dkall[ct] = ck;
-                dvall[ct] = cv;
             } else {
             dkst[ct & 1] = ck;
             dvst[ct & 1] = cv;
@@ -2853,21 +2807,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sp_bwd_dkv(const TokArgs a) {  
                 }
             }
             __builtin_amdgcn_wave_barrier();
-        } else if constexpr (LATE) {
-            // 16-bit rows of up to 128 bytes: all of a token's dK pieces, then all of its dV pieces, in consecutive store instructions -- the
-            // two 64-byte halves of a line written with the other tensor's store and two tiles of products between them left the L2 as
-            // partial lines (WRITE_SIZE 154 MB for 134 MB of results, and the fill reads on top)
-#pragma unroll
-            for (int cta = 0; cta < DT; cta += 2) store_tile_pair<T>(dkb + cur.row * a.dk.sn, cta, DT, D, kg, dkall[cta], dkall[cta + 1 < DT ? cta + 1 : cta], cur.live, wide_dk);
-#pragma unroll
-            for (int cta = 0; cta < DT; cta += 2) store_tile_pair<T>(dvb + cur.row * a.dv.sn, cta, DT, D, kg, dvall[cta], dvall[cta + 1 < DT ? cta + 1 : cta], cur.live, wide_dv);
-            if (a.normalize && a.split && cur.live) {
-#pragma unroll
-                for (int ct = 0; ct < DT; ++ct) {
-                    const int da = ct * 16 + kg * 4;
-                    if (da < D) Io<T>::st4(dkdb + cur.row * a.dkd.sn + da, *reinterpret_cast<const f32x4*>(dks + da));
-                }
-            }
         }
     };
     for (int tt = wave; tt * 16 < S; tt += 4) {

@@ -504,7 +504,12 @@ def mhla_blockmix_rope(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, W: tor
     q, k are the un-rotated tensors ([B, N, H, D]); rope_cos / rope_sin are fp32 [N, D/2] (the multiplier of `rope_apply`
     per token row).  Rotated k feeds KV, rotated q the numerator, plain q / k the normaliser -- no q_rope / k_rope
     tensors are materialised, in either direction: the backward rotates q and k again where the rotated ones are needed and
-    returns the gradients w.r.t. the un-rotated tensors (fp32 tensors, D % 8 == 0 for the backward)."""
+    returns the gradients w.r.t. the un-rotated tensors (fp32 tensors, D % 8 == 0 for the backward).
+
+    The forward serves fp32 tensors.  16-bit tensors are served only where their block summaries are fp32 words or bf16 (head dims
+    above 96, summaries='bf16', the "fp32_summaries" option); on the h16 / p24 summaries that are their default the library refuses
+    the call (no rotary summary kernel is built for them) and this raises: use fp32 tensors, or rotate on the host and call
+    mhla_blockmix(q_rope, k_rope, v, W, q_den=q, k_den=k)."""
     _require_gpu(q, k, v, W, rope_cos, rope_sin, block_index)
     _, N, _, D = q.shape
     _block_len(N, W.shape[0])

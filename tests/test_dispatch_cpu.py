@@ -212,6 +212,19 @@ def test_rope_table_checks_are_shared_by_the_four_entry_points(entry):
         assert call(cos, sin, ld, none) == -22 and lib.mhla_last_error() == ROPE_MSG % ld, (cos, sin, ld, lib.mhla_last_error())
 
 
+def test_rope_fwd_refuses_16bit_tensors_on_h16_or_p24_summaries():
+    """No rotary summary kernel is built for 16-bit tensors on h16 / p24 summaries: bf16 at D = 64 (h16) is refused while the arguments are
+    checked; at D = 128 (fp32 words) the same call passes this check and fails the next one, the workspace size."""
+    from mhla_amd import _lib
+    lib = _lib.load()
+    call = lambda D, ws_bytes: lib.mhla_blockmix_rope_fwd(*(_lib.View(P, D * 16, D, D),) * 3, 1, P, 16, P, P, D // 2, _lib.View(P, D * 16, D, D), None, P, ws_bytes,
+                                                          1, 1, 16, 16, D, _lib.BF16, 1e-6, 0, None)
+    assert call(64, 1 << 30) == -95, lib.mhla_last_error()   # MHLA_ENOTSUP
+    assert lib.mhla_last_error() == (b"rotary forward on 16-bit tensors with h16 / p24 summaries is not built (M=16 S=16 D=64 dtype=1): use fp32 tensors, or "
+                                     b"rotate on the host and call mhla_blockmix(q_rope, k_rope, v, W, q_den=q, k_den=k)")
+    assert call(128, 16) == -22 and lib.mhla_last_error().startswith(b"workspace too small"), lib.mhla_last_error()
+
+
 @pytest.mark.parametrize("entry", ["wan_fwd", "wan_pro_fwd"])
 def test_gate_check_is_shared_by_the_two_entry_points(entry):
     from mhla_amd import _lib

@@ -471,6 +471,12 @@ def test_qk_prologue_and_rope_op():
             check(f"rope op {name} normalize={normalize}", a_.grad, b_.grad, 2e-4)
     with pytest.raises(RuntimeError):   # the rotary backward is built for fp32 tensors
         mhla_amd.mhla_blockmix_rope(q.to(DEV).bfloat16().requires_grad_(True), k.to(DEV).bfloat16(), v.to(DEV).bfloat16(), W.to(DEV), cos, sin)
+    # the rotary forward is not built for 16-bit tensors on h16 / p24 summaries: refused before anything is launched
+    with torch.no_grad():
+        q16, k16, v16 = (torch.rand(1, 4 * 16, 2, 64, generator=g).to(DEV).bfloat16() for _ in range(3))
+        tab = torch.ones(4 * 16, 32, device=DEV)
+        with pytest.raises(RuntimeError, match="rotary forward on 16-bit tensors with h16 / p24 summaries is not built.*use fp32 tensors, or rotate on the host"):
+            mhla_amd.mhla_blockmix_rope(q16, k16, v16, torch.eye(4, device=DEV), tab, torch.zeros_like(tab))
     # prologue + epilogue fused: rotary inside, per-head RMSNorm x SiLU gate before the store, output in the host dtype
     nw = torch.rand(D, generator=g) + 0.5
     for odt in (torch.bfloat16, torch.float32):
