@@ -125,9 +125,10 @@ BF16_SHAPES = [(256, 64, 64), (200, 64, 128), (50, 128, 64), (1000, 128, 256), (
                # 129..256 chunks: the sixteen-wave mixing kernels (dS and dmix as two launches)
                (8256, 64, 64), (16384, 64, 64), (10000, 128, 128),
                # the token-gradient kernel's chunk walk (k_csf_bwd_tok4: with B H = 4 here, two chunks per workgroup from 128 chunks on and
-               # four at 256 -- the shapes above cover K = 64 / 128 with an odd chunk count and a ragged tail; the full-size C5 test walks
-               # eight): K = 192, an odd count and a 8-token last chunk (dk / dv there are 0.6 % of the tensor's maximum: it is the
-               # per-chunk check that sees them)
+               # four at 256 -- the shapes above cover K = 64 / 128 with an odd chunk count and a ragged tail; the full-size C5 test, with
+               # B H = 8 and 128 chunks, walks four as well; eight, the benchmark's C5 value, and every walking instantiation at 2, 4
+               # and 8: test_gpu_causal_walk.py): K = 192, an odd count and a 8-token last chunk (dk / dv there are 0.6 % of the
+               # tensor's maximum: it is the per-chunk check that sees them)
                (8200, 192, 192)]
 
 
