@@ -490,6 +490,41 @@ int mhla_causal_extend_ragged(mhla_view q, mhla_view k, mhla_view v, const float
                               mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                               void* stream);
 
+/* mhla_causal_verify_ragged: the rows of mhla_causal_extend_ragged WITHOUT committing a token -- a draft to verify (added without a
+ * change of any existing signature or behaviour: MHLA_ABI_VERSION stays 9).  Arguments, workspace
+ * (mhla_causal_extend_ragged_ws_bytes), checks, the six launches, the tiles and the order of every sum are those of
+ * mhla_causal_extend_ragged, and out / y hold the same bits; pos_dev is const.  After the call P, Cur, pos_dev and the FINISHED rows of
+ * S -- S[b][h][0 .. pos_dev[b] / chunk) -- hold their previous bits: the state still describes pos_dev[b] tokens, and any call that
+ * takes such a state gives what it would have given without the verify.  Rows pos_dev[b] / chunk .. of S are UNSPECIFIED afterwards:
+ * the chain scribbles the draft's K^T V sums on them (the prefix mixes of the draft's later chunks are formed from them).  That is
+ * within the state's contract -- rows of S beyond the finished chunks are neither read nor relied on by any call before a later
+ * call finishes them, which overwrites them -- so undoing a draft needs no copy of S. */
+int mhla_causal_verify_ragged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                              float* Cur, const int32_t* pos_dev, const int32_t* ntok_dev, int T, int64_t max_end, int max_later,
+                              int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                              mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
+                              void* stream);
+
+/* mhla_causal_commit_ragged: advance a ragged state by the first accept_dev[b] tokens of sequence b's draft window, no rows computed
+ * (added without a change of any existing signature or behaviour: MHLA_ABI_VERSION stays 9).  k, v, ntok_dev, T and left_padded
+ * are those of the verify: the window of sequence b is placed by ntok_dev[b] -- rows [0, ntok_dev[b]), or [T - ntok_dev[b], T) with
+ * `left_padded` -- and its first min(accept_dev[b], ntok_dev[b]) rows are taken; accept_dev: device int32 [B].  The state afterwards,
+ * pos_dev included, is bit for bit the one mhla_causal_extend_ragged leaves with those rows as the sequence's tokens (the same
+ * tiles and order of every sum; one accepted token: the step's rank-1 fmaf); accept_dev[b] = 0 leaves the sequence untouched.
+ * At most four launches whatever B, the counts and the positions, none of which touches q, out, y or gate: the first segment's
+ * K^T V, then -- only with any_close -- the later segments' and the prefix mix of the chunk open afterwards, then pos_dev[b] +=
+ * the accepted count in stream order (the earlier launches address by pos_dev, the last does not).
+ * max_end, max_later and any_close vouch for the ACCEPTED counts -- the values of mhla_causal_extend_ragged computed from pos_dev and
+ * min(accept_dev, ntok_dev) -- with the same restriction on ldmix and the same defence: a sequence outside what they vouch for is
+ * skipped, state and position untouched.  Workspace (mhla_causal_commit_ragged_ws_bytes, pure host arithmetic): B 4-byte words
+ * rounded up to a multiple of 4.  MHLA_EINVAL before any launch: what mhla_causal_extend_ragged checks of T, the views k and v, the
+ * state, the three device arrays, the host values, ldmix and the workspace. */
+size_t mhla_causal_commit_ragged_ws_bytes(int B, int dtype);
+int mhla_causal_commit_ragged(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                              int32_t* pos_dev, const int32_t* ntok_dev, const int32_t* accept_dev, int T, int64_t max_end,
+                              int max_later, int any_close, int left_padded, void* ws, size_t ws_bytes, int B, int H, int K, int V,
+                              int chunk, int dtype, void* stream);
+
 /* ---- prologue: q / k of the Wan host -------------------------------------- */
 
 /*

@@ -104,7 +104,14 @@ SIGNATURES = {
     "mhla_causal_extend_ragged": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                           c_int64, c_int, c_int, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int,
                                           c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
-    "mhla_featmap_rotary": (c_int, [View, View, c_void_p, c_void_p, c_int64, c_int64, View, c_int, c_int, c_int, c_int, c_int,
+    "mhla_causal_verify_ragged": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                          c_int64, c_int, c_int, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int,
+                                          c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "mhla_causal_commit_ragged_ws_bytes": (c_size_t, [c_int] * 2),
+    "mhla_causal_commit_ragged": (c_int, [View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_int, c_int64, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int,
+                                          c_int, c_void_p]),
+    "mhla_featmap_rotary": (c_int, [View,View, c_void_p, c_void_p, c_int64, c_int64, View, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_void_p]),
     "mhla_lepe2d": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                             c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -1,5 +1,5 @@
 // C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
-// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
@@ -142,6 +142,75 @@ CxRagPlan cx_rag_plan(int B, int T, int H, int K, int V, int max_later) {
     p.nval = al4((size_t)B);
     p.total = p.tiles + p.stage + p.nval;
     return p;
+}
+
+// what the ragged entry points check of the host values that vouch for the device arrays, and of the rows of mix they let be read
+int cx_rag_check(int T, int cap_chunks, const int32_t* pos_dev, const int32_t* ntok_dev, int64_t max_end, int max_later, int any_close,
+                 const float* mix, int ldmix) {
+    if (cap_chunks > INT32_MAX / 64) return fail(MHLA_ENOTSUP, "cap_chunks=%d: positions beyond int32", cap_chunks);
+    RC(cst_check_dev("pos_dev", pos_dev));
+    RC(cst_check_dev("ntok_dev", ntok_dev));
+    if (max_end < 0) return fail(MHLA_EINVAL, "max_end=%lld is negative", (long long)max_end);
+    if (max_end > (int64_t)64 * cap_chunks)
+        return fail(MHLA_EINVAL, "max_end=%lld tokens need %lld chunks, the state holds %d", (long long)max_end, (long long)((max_end + 63) / 64), cap_chunks);
+    if (max_later < 0 || max_later > (T + 62) / 64)
+        return fail(MHLA_EINVAL, "max_later=%d: T=%d tokens touch at most %d chunks after the first", max_later, T, (T + 62) / 64);
+    if (max_later && !any_close) return fail(MHLA_EINVAL, "max_later=%d without any_close", max_later);
+    // rows of mix read: every sequence's diagonal up to chunk (its end - 1) / 64 and, where it closes a chunk and is not full then, row
+    // (its end) / 64.  Which sequence closes is known on the device only: with any_close row max_end / 64 must be covered (or
+    // the state's last), as if the furthest sequence were the one -- the restriction of mhla_causal_step_ragged
+    const int64_t lastrow = any_close ? std::min<int64_t>(max_end / 64, cap_chunks - 1) : (max_end > 0 ? (max_end - 1) / 64 : 0);
+    return cst_check_mix(mix, ldmix, lastrow);
+}
+
+// the ragged extend chain; dry (the verify): the same launches, nothing of the committed state -- Cur, P, pos_dev -- written
+int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                    float* Cur, int32_t* pos_dev, const int32_t* ntok_dev, int T, int64_t max_end, int max_later, int any_close,
+                    int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws,
+                    size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check(B, H, K, V, chunk, dtype));
+    if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive", T);
+    if (T > 65535) return fail(MHLA_EINVAL, "T=%d exceeds 65535 tokens per call", T);   // (mhla_causal_extend answers MHLA_ENOTSUP here: kept, a caller may test the code)
+    RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
+    RC(cx_rag_check(T, cap_chunks, pos_dev, ntok_dev, max_end, max_later, any_close, mix, ldmix));
+    const CxRagPlan p = cx_rag_plan(B, T, H, K, V, max_later);
+    RC(cst_check_ws(ws, ws_bytes, p.total * 4));
+    hipStream_t st = (hipStream_t)stream;
+    const int BH = B * H, nvt = (V + 63) / 64, strips = ((K + 63) / 64) * nvt;
+    const long E = (long)K * V;
+    float* tiles = (float*)ws;
+    float* stage = tiles + p.tiles;
+    int* nval = (int*)(stage + p.stage);
+    const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0, dry ? 1 : 0};
+    const int kr = cst_rows((size_t)H, K, V);   // a one-token sequence: the step's K split for a batch of one
+    // every launch but the last addresses by pos_dev; the last, which does not, advances it (dry: does not)
+    DISPATCH_T(dtype, {
+        CxOutArgs o{};
+        o.q = cv(q); o.k = cv(k); o.v = cv(v);
+        o.stage = stage; o.H = H; o.K = K; o.V = V; o.T = T; o.scale = scale; o.mstep = (long)ldmix + 1;
+        o.P = P; o.Cur = Cur; o.mdiag = mix; o.rag = g; o.later = 0; o.nval = nval; o.kr = kr; o.nsplit = (K + kr - 1) / kr;
+        RC(launch(k_cx_out<ET, true>, dim3(1, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out_ragged", o));
+        CxAccArgs c{};
+        c.x = cv(k); c.y = cv(v); c.H = H; c.DX = K; c.DY = V; c.rag = g; c.later = 0; c.S = S; c.Cur = Cur;
+        RC(launch(k_cx_xty_acc<ET, true>, dim3(1, BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+        if (any_close) {
+            c.later = 1;
+            RC(launch(k_cx_xty_acc<ET, true>, dim3(std::max(1, max_later), BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+            CxMixRagArgs m{};
+            m.m.S = S; m.m.ws = tiles; m.m.P = P; m.m.mix = mix; m.m.E = E; m.m.ldmix = ldmix; m.m.cap = cap_chunks;
+            m.rag = g; m.H = H;
+            const int groups = (max_later + 1 + CX_MIX_NC - 1) / CX_MIX_NC;   // (the largest nc is max_later + 1)
+            RC(launch(k_cx_mix_ragged, dim3((unsigned)((E / 4 + 63) / 64), BH, groups), dim3(64), 0, st, "k_cx_mix_ragged", m));
+            if (max_later) {
+                o.P = tiles; o.Cur = nullptr; o.later = 1;
+                RC(launch(k_cx_out<ET, true>, dim3(max_later, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out_ragged", o));
+            }
+        }
+        CsFinishArgs f{stage, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, 1, dry ? nullptr : pos_dev};
+        f.nval = nval; f.left = left_padded ? 1 : 0;
+        RC(launch(k_cs_step_finish<ET, false, true>, dim3(BH, T), dim3(CST_THREADS), 0, st, "k_cs_step_finish_ragged", f));
+    });
+    return MHLA_OK;
 }
 
 }  // namespace
@@ -367,62 +436,56 @@ int mhla_causal_extend_ragged(mhla_view q, mhla_view k, mhla_view v, const float
                               int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                               mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                               void* stream) {
+    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, ntok_dev, T, max_end, max_later, any_close, left_padded,
+                           out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_verify_ragged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                              float* Cur, const int32_t* pos_dev, const int32_t* ntok_dev, int T, int64_t max_end, int max_later,
+                              int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                              mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
+                              void* stream) {
+    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), ntok_dev, T, max_end, max_later, any_close, left_padded, out, gate, norm_w,
+                           norm_eps, y, ws, ws_bytes, B, H, K, V, chunk, scale, dtype, stream);
+}
+
+size_t mhla_causal_commit_ragged_ws_bytes(int B, int dtype) {
+    (void)dtype;
+    return B > 0 ? al4((size_t)B) * 4 : 0;
+}
+
+int mhla_causal_commit_ragged(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                              int32_t* pos_dev, const int32_t* ntok_dev, const int32_t* accept_dev, int T, int64_t max_end,
+                              int max_later, int any_close, int left_padded, void* ws, size_t ws_bytes, int B, int H, int K, int V,
+                              int chunk, int dtype, void* stream) {
     RC(cst_check(B, H, K, V, chunk, dtype));
     if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive", T);
-    if (T > 65535) return fail(MHLA_EINVAL, "T=%d exceeds 65535 tokens per call", T);   // (mhla_causal_extend answers MHLA_ENOTSUP here: kept, a caller may test the code)
-    RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
-    if (cap_chunks > INT32_MAX / 64) return fail(MHLA_ENOTSUP, "cap_chunks=%d: positions beyond int32", cap_chunks);
-    RC(cst_check_dev("pos_dev", pos_dev));
-    RC(cst_check_dev("ntok_dev", ntok_dev));
-    if (max_end < 0) return fail(MHLA_EINVAL, "max_end=%lld is negative", (long long)max_end);
-    if (max_end > (int64_t)64 * cap_chunks)
-        return fail(MHLA_EINVAL, "max_end=%lld tokens need %lld chunks, the state holds %d", (long long)max_end, (long long)((max_end + 63) / 64), cap_chunks);
-    if (max_later < 0 || max_later > (T + 62) / 64)
-        return fail(MHLA_EINVAL, "max_later=%d: T=%d tokens touch at most %d chunks after the first", max_later, T, (T + 62) / 64);
-    if (max_later && !any_close) return fail(MHLA_EINVAL, "max_later=%d without any_close", max_later);
-    // rows of mix read: every sequence's diagonal up to chunk (its end - 1) / 64 and, where it closes a chunk and is not full then, row
-    // (its end) / 64.  Which sequence closes is known on the device only: with any_close row max_end / 64 must be covered (or
-    // the state's last), as if the furthest sequence were the one -- the restriction of mhla_causal_step_ragged
-    const int64_t lastrow = any_close ? std::min<int64_t>(max_end / 64, cap_chunks - 1) : (max_end > 0 ? (max_end - 1) / 64 : 0);
-    RC(cst_check_mix(mix, ldmix, lastrow));
-    const CxRagPlan p = cx_rag_plan(B, T, H, K, V, max_later);
-    RC(cst_check_ws(ws, ws_bytes, p.total * 4));
+    if (T > 65535) return fail(MHLA_EINVAL, "T=%d exceeds 65535 tokens per call", T);
+    CHECK_VIEW(k); CHECK_VIEW(v);
+    RC(cst_check_state(S, cap_chunks, P, Cur));
+    RC(cst_check_dev("accept_dev", accept_dev));
+    RC(cx_rag_check(T, cap_chunks, pos_dev, ntok_dev, max_end, max_later, any_close, mix, ldmix));
+    RC(cst_check_ws(ws, ws_bytes, al4((size_t)B) * 4));
     hipStream_t st = (hipStream_t)stream;
-    const int BH = B * H, nvt = (V + 63) / 64, strips = ((K + 63) / 64) * nvt;
+    const int BH = B * H, strips = ((K + 63) / 64) * ((V + 63) / 64);
     const long E = (long)K * V;
-    float* tiles = (float*)ws;
-    float* stage = tiles + p.tiles;
-    int* nval = (int*)(stage + p.stage);
-    const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0};
-    const int kr = cst_rows((size_t)H, K, V);   // a one-token sequence: the step's K split for a batch of one
+    int* nval = (int*)ws;
+    const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0, 0, accept_dev};
     // every launch but the last addresses by pos_dev; the last, which does not, advances it
     DISPATCH_T(dtype, {
-        CxOutArgs o{};
-        o.q = cv(q); o.k = cv(k); o.v = cv(v);
-        o.stage = stage; o.H = H; o.K = K; o.V = V; o.T = T; o.scale = scale; o.mstep = (long)ldmix + 1;
-        o.P = P; o.Cur = Cur; o.mdiag = mix; o.rag = g; o.later = 0; o.nval = nval; o.kr = kr; o.nsplit = (K + kr - 1) / kr;
-        RC(launch(k_cx_out<ET, true>, dim3(1, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out_ragged", o));
         CxAccArgs c{};
-        c.x = cv(k); c.y = cv(v); c.H = H; c.DX = K; c.DY = V; c.rag = g; c.later = 0; c.S = S; c.Cur = Cur;
+        c.x = cv(k); c.y = cv(v); c.H = H; c.DX = K; c.DY = V; c.rag = g; c.later = 0; c.S = S; c.Cur = Cur; c.nval = nval;
         RC(launch(k_cx_xty_acc<ET, true>, dim3(1, BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
         if (any_close) {
             c.later = 1;
             RC(launch(k_cx_xty_acc<ET, true>, dim3(std::max(1, max_later), BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
             CxMixRagArgs m{};
-            m.m.S = S; m.m.ws = tiles; m.m.P = P; m.m.mix = mix; m.m.E = E; m.m.ldmix = ldmix; m.m.cap = cap_chunks;
+            m.m.S = S; m.m.ws = nullptr; m.m.P = P; m.m.mix = mix; m.m.E = E; m.m.ldmix = ldmix; m.m.cap = cap_chunks;
             m.rag = g; m.H = H;
-            const int groups = (max_later + 1 + CX_MIX_NC - 1) / CX_MIX_NC;   // (the largest nc is max_later + 1)
-            RC(launch(k_cx_mix_ragged, dim3((unsigned)((E / 4 + 63) / 64), BH, groups), dim3(64), 0, st, "k_cx_mix_ragged", m));
-            if (max_later) {
-                o.P = tiles; o.Cur = nullptr; o.later = 1;
-                RC(launch(k_cx_out<ET, true>, dim3(max_later, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out_ragged", o));
-            }
+            RC(launch(k_cx_mix_ragged, dim3((unsigned)((E / 4 + 63) / 64), BH, 1), dim3(64), 0, st, "k_cx_mix_ragged", m));
         }
-        CsFinishArgs f{stage, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, 1, pos_dev};
-        f.nval = nval; f.left = left_padded ? 1 : 0;
-        RC(launch(k_cs_step_finish<ET, false, true>, dim3(BH, T), dim3(CST_THREADS), 0, st, "k_cs_step_finish_ragged", f));
     });
-    return MHLA_OK;
+    return launch(k_cx_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, "k_cx_advance", pos_dev, (const int*)nval, B);
 }
 
 }  // extern "C"

@@ -33,6 +33,15 @@
 // chain's, so a sequence gets the bits mhla_causal_extend gives it alone in a batch of one; a sequence with ONE token gets the
 // step's arithmetic (k_cs_step's row walk and K split of a batch of one, fmaf for fmaf), as T = 1 of the uniform call is the step.
 // Defence only: a sequence whose pos / ntok fall outside what the host vouched for is skipped (state untouched, rows zeros).
+// Verify (CxRag::dry; mhla_causal_verify_ragged): the same six launches, tiles and sums, minus every write to the committed state --
+// Cur, P and pos.  S[i_b] and S[i_b + 1 ...] are still written: those rows are unfinished at pos[b], nothing reads them before a later
+// call finishes them, and the later segments' prefix mixes are formed from them.  The rows are the ragged extend's, bit for bit.
+// Commit (CxRag::acc; mhla_causal_commit_ragged): the state half of the chain alone, on the first min(acc[b], ntok[b]) tokens of each
+// window (the window still placed by ntok[b]), no q and no output -- at most four launches:
+//   k_cx_xty_acc<RAGGED> first segment (also nval[b]), k_cx_xty_acc<RAGGED> later segments, k_cx_mix_ragged with no workspace (only
+//   the P of the chunk open afterwards is formed), k_cx_advance: pos[b] += nval[b] -- the last, the only one not addressing by pos
+// (the middle two only when some sequence closes a chunk).  The same tiles and sums again: the state is the one the ragged extend
+// leaves after acc[b] tokens, bit for bit; one accepted token takes the step's fmaf.
 #pragma once
 #include "causal.hpp"
 #include "causal_step.hpp"
@@ -48,6 +57,8 @@ struct CxRag {
     int max_later;         // host-vouched: the largest number of chunks touched after the first
     int any_close;         // host-vouched: some sequence closes a chunk (the later-segment launches exist)
     int left;              // left-padded: sequence b's tokens are rows [T - n, T)
+    int dry;               // verify: Cur, P and pos are not written (S rows at and beyond pos[b] / 64 still are)
+    const int* acc;        // [B] or null; commit: sequence b takes the first min(acc[b], ntok[b]) tokens of its ntok[b]-token window
 };
 struct CxSeq {
     int n, i, r, a;        // tokens; chunk and fill of the open chunk; rows of the first segment
@@ -58,15 +69,16 @@ struct CxSeq {
 };
 // false: no token, or (defence only) entries outside what the host vouched for -- the caller returns at once
 __device__ __forceinline__ bool cx_seq(const CxRag& g, int b, CxSeq& s) {
-    const int p = g.pos[b], n = g.ntok[b];
-    if (p < 0 || n < 1 || n > g.T || (long)p + n > (long)g.max_end) return false;
+    const int p = g.pos[b], w = g.ntok[b];
+    const int n = g.acc ? min(g.acc[b], w) : w;
+    if (p < 0 || n < 1 || w > g.T || (long)p + n > (long)g.max_end) return false;
     s.n = n; s.i = p / CS; s.r = p - s.i * CS;
     s.a = min(n, CS - s.r);
     s.later = (p + n - 1) / CS - s.i;
     s.iend = (p + n) / CS;
     s.closes = s.iend > s.i;
     s.full = s.iend >= g.cap;
-    s.shift = g.left ? g.T - n : 0;
+    s.shift = g.left ? g.T - w : 0;
     return s.later <= g.max_later && (!s.closes || g.any_close);
 }
 
@@ -270,6 +282,7 @@ struct CxAccArgs {
     int later;             // 0: the first segment (src = Cur); 1: segment blockIdx.x of the later ones (src null)
     float* S;              // [bh][cap][K][V]
     float* Cur;            // [bh][K][V]
+    int* nval;             // [B] or null (later = 0 writes it): the tokens the chain accepts for sequence b, as k_cx_out's
 };
 
 // grid (1, B H, strips of 64 x 64): dst = src + X^T Y over the segment's rows -- the accumulating form of k_bm_state<MODE 2>
@@ -293,17 +306,21 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_xty_acc(const CxAccArgs a) {
     [[maybe_unused]] bool one = false, zero_cur = false;
     if constexpr (RAGGED) {
         CxSeq s;
-        if (!cx_seq(a.rag, b, s)) return;   // ahead of any LDS or further global traffic
+        const bool ok = cx_seq(a.rag, b, s);
+        if (a.nval && !a.later && h == 0 && blockIdx.z == 0 && tid == 0) a.nval[b] = ok ? s.n : 0;
+        if (!ok) return;   // ahead of any LDS or further global traffic
         const long E = (long)a.DX * a.DY;
         if (a.later) {
             const int seg = blockIdx.x, rest = s.n - s.a;
             if (!s.closes) return;
-            zero_cur = seg == 0 && rest % CS == 0;
+            zero_cur = seg == 0 && rest % CS == 0 && !a.rag.dry;
             rows = seg < s.later ? min(CS, rest - seg * CS) : 0;
+            if (a.rag.dry && rows < CS) return;   // (the tail would go to Cur)
             if (!rows && !zero_cur) return;
             tok0 = s.shift + s.a + (long)seg * CS;
             db = rows == CS ? a.S + ((long)bh * a.rag.cap + s.i + 1 + seg) * E : a.Cur + (long)bh * E;
         } else {
+            if (a.rag.dry && !s.closes) return;   // (the sum would go to Cur)
             rows = s.a;
             tok0 = s.shift;
             sb = a.Cur + (long)bh * E;
@@ -422,7 +439,7 @@ __global__ __launch_bounds__(64) void k_cx_mix(const CxMixArgs a) {
 }
 
 struct CxMixRagArgs {
-    CxMixArgs m;           // c0, nws, nc and cP unused: per sequence
+    CxMixArgs m;           // c0, nws, nc and cP unused: per sequence; ws null (commit): only the state's P is formed
     CxRag rag;
     int H;
 };
@@ -436,8 +453,22 @@ __global__ __launch_bounds__(64) void k_cx_mix_ragged(const CxMixRagArgs a) {
     const long bh = blockIdx.y;
     CxSeq s;
     if (!cx_seq(a.rag, (int)(bh / a.H), s) || !s.closes) return;
+    if (a.rag.dry) {   // the workspace tiles alone: no cP matches and none is negative
+        if (s.later) cx_mix_sums(a.m, bh, e, s.i + 1, s.later, a.rag.max_later, s.later, 0x7fffffff);
+        return;
+    }
+    if (!a.m.ws) {     // chunk iend alone (every accumulator sums ascending j by itself: the group does not change its bits), or P = 0
+        cx_mix_sums(a.m, bh, e, s.iend, 0, 0, s.full ? 0 : 1, s.full ? -1 : s.iend);
+        return;
+    }
     const int nc = (s.full ? s.i + s.later : s.iend) - s.i;
     cx_mix_sums(a.m, bh, e, s.i + 1, s.later, a.rag.max_later, nc, s.full ? -1 : s.iend);
+}
+
+// grid (ceil(B / 64)): the last launch of the commit chain, pos[b] += nval[b] (nval: what the first launch of the chain accepted)
+__global__ __launch_bounds__(64) void k_cx_advance(int* pos, const int* nval, int B) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b < B) pos[b] += nval[b];
 }
 
 }  // namespace mhla

@@ -179,7 +179,7 @@ struct CsFinishArgs {
     const float* nw;       // [V] or null
     float neps, scale;
     int H, V, nsplit;
-    int* advance;          // [B] or null: positions of a ragged state, each incremented once (by the workgroup of head 0, token 0)
+    int* advance;          // [B] or null: positions of a ragged state, each advanced once (by the workgroup of head 0, token 0)
     // DEV only: a position outside 0 .. max_pos (64 cap - 1) stays, and full[b] = 1 instead
     int max_pos;
     int* full;             // [B], never cleared here
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishAr
     const long tok = blockIdx.y;
     if constexpr (WIN) {
         const int n = a.nval[b], t0 = a.left ? (int)gridDim.y - n : 0;
-        if (h == 0 && tok == 0 && tid == 0) a.advance[b] += n;   // (nothing in this launch reads it)
+        if (a.advance && h == 0 && tok == 0 && tid == 0) a.advance[b] += n;   // (nothing in this launch reads it; null: a verify)
         if (tok < t0 || tok >= t0 + n) {
             T* ob = a.out.ptr ? (T*)a.out.ptr + b * a.out.sb + tok * a.out.sn + h * a.out.sh : nullptr;
             T* yb = a.y.ptr ? (T*)a.y.ptr + b * a.y.sb + tok * a.y.sn + h * a.y.sh : nullptr;

@@ -48,7 +48,7 @@ class Block(nn.Module):
         self.mlp_norm = RMSNorm(dim)
         self.mlp = GatedMLP(dim)
 
-    def forward(self, x, cache=None, attention_mask=None, token_counts=None, cu_seqlens=None, varlen_plan=None):
+    def forward(self, x, cache=None, attention_mask=None, token_counts=None, cu_seqlens=None, varlen_plan=None, speculative=False):
         kw = {}
         if cu_seqlens is not None or varlen_plan is not None:   # packed sequences: training (no cache), or the packed prefill
             kw = dict(cu_seqlens=cu_seqlens, varlen_plan=varlen_plan)
@@ -56,6 +56,8 @@ class Block(nn.Module):
             kw.update(past_key_values=cache, use_cache=True)
             if token_counts is not None:
                 kw["token_counts"] = token_counts
+            if speculative:
+                kw["speculative"] = True
         x = x + self.attn(self.attn_norm(x), attention_mask=attention_mask, **kw)[0]
         return x + self.mlp(self.mlp_norm(x))
 
@@ -75,7 +77,7 @@ class GPT_MHLA(nn.Module):
             if isinstance(m, (nn.Linear, nn.Embedding)):
                 nn.init.normal_(m.weight, std=0.02)
 
-    def forward(self, input_ids, labels=None, cache=None, attention_mask=None, token_counts=None, cu_seqlens=None):
+    def forward(self, input_ids, labels=None, cache=None, attention_mask=None, token_counts=None, cu_seqlens=None, speculative=False):
         """`cache` (a `DecodeCache`, model built with `exact_decoding=True`): `input_ids` are the tokens AFTER the ones the cache
         has seen -- the whole prompt on an empty cache, then one token per call, or several (the next turn, a piece of a long
         prompt, a draft to verify): on a non-empty cache those take the layer's `mhla_causal_extend` path, one launch chain per
@@ -92,7 +94,10 @@ class GPT_MHLA(nn.Module):
         operator's chunk table (`causal_varlen_plan`, one host read of the lengths) is built here once for all layers.  With a
         cache, `cu_seqlens` is the packed prefill: a model built with both `exact_decoding` and `isolate_sequences`, an EMPTY
         `DecodeCache(packed_prefill=True)`; the logits are the pack's, [1, T], and later calls are [sequences, T'] on the ragged
-        state.  On a cache that holds a state it raises NotImplementedError."""
+        state.  On a cache that holds a state it raises NotImplementedError.
+        `speculative=True` (a cache that holds a state): `input_ids` are a draft to VERIFY -- the logits of the same call without
+        the flag, but no layer's state and no token count moves; `cache.commit(accept)` then advances every layer by the first
+        `accept[b]` tokens of sequence b's window, `cache.discard()` by none.  Handed to every layer."""
         if cache is not None and not self.exact_decoding:
             raise ValueError("GPT_MHLA.forward(cache=...) needs a model built with exact_decoding=True")
         # a model built with exact_decoding and isolate_sequences prefills a pack into an EMPTY DecodeCache(packed_prefill=True):
@@ -112,14 +117,14 @@ class GPT_MHLA(nn.Module):
             token_counts = token_counts.tolist()   # (read once for all layers)
         x = self.embeddings(input_ids)
         for blk in self.layers:
-            x = blk(x, cache, attention_mask, token_counts, cu_seqlens, plan)
+            x = blk(x, cache, attention_mask, token_counts, cu_seqlens, plan, speculative)
         logits = self.lm_head(self.norm(x))
         if labels is None:
             return logits
         return F.cross_entropy(logits[:, :-1].reshape(-1, logits.shape[-1]).float(), labels[:, 1:].reshape(-1))
 
     @torch.no_grad()
-    def generate(self, input_ids, max_new_tokens, attention_mask=None, graph=False, return_logits=False):
+    def generate(self, input_ids, max_new_tokens, attention_mask=None, graph=False, return_logits=False, draft=None, draft_len=4):
         """Greedy decoding: one prefill over `input_ids` [B, T], then one cached step per new token.  Returns the
         `max_new_tokens` new ids [B, max_new_tokens]; T + max_new_tokens must fit the mixing matrix (`max_seq_len`).
         `attention_mask` [B, T]: prompts of different lengths, left-padded to T (0 = padding); every sequence continues from
@@ -129,8 +134,19 @@ class GPT_MHLA(nn.Module):
         that loads every kernel, then ONE whole-model step captured in a graph (static id and logits buffers, a single stream: a
         linear graph without parallel branches) and replayed once per token, and one `cache.sync()` at the end, which raises
         IndexError if a sequence was stepped beyond `max_seq_len` (its logits from there on came from zero attention rows).
-        `return_logits=True`: `(ids, logits [B, max_new_tokens, vocab])`, the logits every id was picked from."""
+        `return_logits=True`: `(ids, logits [B, max_new_tokens, vocab])`, the logits every id was picked from.
+        `draft=fn, draft_len=k`: greedy SPECULATIVE decoding, the same ids in fewer model calls.  `fn(histories)` takes the list of B
+        1-D id tensors (every prompt without its padding, plus the tokens emitted so far) and returns `[B, k]` proposed ids.  Per
+        round ONE model call verifies `[last token, d_1 .. d_k]` (`speculative=True`: no state moves), sequence b accepts the
+        longest prefix with `d_j == argmax(logits_{j-1})`, emits those m_b drafts plus the bonus token `argmax(logits_{m_b})`, and
+        `cache.commit(m_b + 1)` advances every layer -- one host read of the acceptance per round for all of them.  A sequence that
+        has its `max_new_tokens` sits the later rounds out (`token_counts` 0); near the end the window is clipped so that nothing is
+        verified beyond `T + max_new_tokens`.  `graph=True` with it raises NotImplementedError."""
         n = int(max_new_tokens)
+        if draft is not None:
+            if graph:
+                raise NotImplementedError("GPT_MHLA.generate: draft= with graph=True (a verify reads the host positions)")
+            return self._generate_speculative(input_ids, n, attention_mask, return_logits, draft, int(draft_len))
         # (both flags: a padded batch is prefilled as a pack -- no padding row through the operator, one state chain per layer)
         cache = DecodeCache(device_positions=bool(graph), packed_prefill=self.exact_decoding and self.isolate_sequences)
         new, kept = [], []
@@ -164,6 +180,58 @@ class GPT_MHLA(nn.Module):
             cache.sync()
         ids = torch.cat(new, dim=1) if new else input_ids[:, :0]
         return (ids, torch.cat(kept, dim=1) if kept else None) if return_logits else ids
+
+    def _generate_speculative(self, input_ids, n, attention_mask, return_logits, draft, k):
+        """`generate(draft=, draft_len=k)`: the prefill, then rounds of draft, verify, accept, commit (see `generate`)."""
+        if k < 1:
+            raise ValueError(f"GPT_MHLA.generate: draft_len={k} must be at least 1")
+        B, T = input_ids.shape
+        dev = input_ids.device
+        empty = input_ids[:, :0]
+        if n < 1:
+            return (empty, None) if return_logits else empty
+        cache = DecodeCache(packed_prefill=self.exact_decoding and self.isolate_sequences)
+        logits = self.forward(input_ids, cache=cache, attention_mask=attention_mask)[:, -1]
+        keep = attention_mask[:, -T:].to(dev) != 0 if attention_mask is not None else None
+        hist = [input_ids[b, keep[b]] if keep is not None else input_ids[b] for b in range(B)]
+        out = [[t] for t in logits.argmax(-1).tolist()]          # emitted ids per sequence
+        kept = [[logits[b]] for b in range(B)]                    # the logits each was picked from
+        last = logits.argmax(-1)
+        hist = [torch.cat([h, last[b:b + 1]]) for b, h in enumerate(hist)]
+        while any(len(o) < n for o in out):
+            # sequence b verifies [last, d_1 .. d_kb], kb = min(k, what it may still emit - 1): right-aligned in k + 1 columns
+            room = [n - len(o) for o in out]
+            counts = [min(k, r - 1) + 1 if r > 0 else 0 for r in room]
+            d = draft(hist).to(dev)
+            if tuple(d.shape) != (B, k):
+                raise ValueError(f"GPT_MHLA.generate: draft returned {tuple(d.shape)}, expected [B, draft_len] = {(B, k)}")
+            window = torch.zeros(B, k + 1, dtype=input_ids.dtype, device=dev)
+            for b, c in enumerate(counts):
+                if c:
+                    window[b, k + 1 - c] = last[b]
+                    window[b, k + 2 - c:] = d[b, :c - 1]
+            logits = self.forward(window, cache=cache, token_counts=counts, speculative=True)
+            # column j + 1 of the window is checked against the argmax at column j; the one host read of the round
+            top_host, win_host = torch.stack([logits.argmax(-1), window]).tolist()
+            agree = [[t == w for t, w in zip(tr[:-1], wr[1:])] for tr, wr in zip(top_host, win_host)]
+            accept = []
+            for b, c in enumerate(counts):
+                if not c:
+                    accept.append(0)
+                    continue
+                c0, m = k + 1 - c, 0
+                while m < c - 1 and agree[b][c0 + m]:
+                    m += 1
+                accept.append(m + 1)
+                new = top_host[b][c0:c0 + m + 1]                  # the m accepted drafts (equal to the argmax) and the bonus token
+                out[b].extend(new)
+                kept[b].extend(logits[b, c0:c0 + m + 1]) if return_logits else None
+                add = torch.tensor(new, dtype=input_ids.dtype, device=dev)
+                hist[b] = torch.cat([hist[b], add])
+                last[b] = add[-1]
+            cache.commit(accept)
+        ids = torch.tensor(out, dtype=torch.long, device=dev)
+        return (ids, torch.stack([torch.stack(r) for r in kept])) if return_logits else ids
 
 
 def GPT_configs():

@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops import (CausalState, _mix2d, _runs, causal_varlen_plan, mhla_causal_prefill, featmap_rotary, mhla_causal, mhla_causal_extend, mhla_causal_normgate, mhla_causal_state, mhla_causal_step,
+from ..ops import (CausalState, _mix2d, _runs, causal_varlen_plan, mhla_causal_prefill, featmap_rotary, mhla_causal, mhla_causal_commit, mhla_causal_extend, mhla_causal_normgate, mhla_causal_state, mhla_causal_step, mhla_causal_verify,
                    mhla_causal_step_dev, naive_recurrent_mhla, rmsnorm_gate)
 from ..weights import causal_mixing_init
 
@@ -163,7 +163,10 @@ class DecodeCache:
     carry `cu_seqlens` (B = 1) or an `attention_mask`, which the layer unpads to a pack -- a packed exact prefill: the operator
     over the pack, every sequence alone, and the ragged decode state of all of them from one launch chain
     (`mhla_causal_state(cu_seqlens=)`); later calls are `[sequences, T', D]` on that state.  Off (the default), such a call is
-    refused as before."""
+    refused as before.
+    Speculative calls (`MHLA.forward(..., speculative=True)`) leave a verified draft in every layer's entry (`"draft"`) and move
+    neither the states nor the token counts: `commit(accept)` advances every layer by the accepted prefix, `discard()` drops the
+    drafts; until one of them, any other call on those layers is refused."""
 
     def __init__(self, device_positions: bool = False, packed_prefill: bool = False):
         self.states, self._seen = [], []
@@ -185,6 +188,26 @@ class DecodeCache:
                 self._seen[i] += st.seen - before
         if err is not None:
             raise err
+        return self
+
+    def commit(self, accept):
+        """After a speculative call: `mhla_causal_commit` of every layer that holds a draft with the first `accept[b]` tokens of
+        sequence b's draft (B ints, or a tensor read once here for all layers), what the furthest sequence grew added to the
+        layer's token count, and the drafts dropped."""
+        accept = tuple(int(n) for n in (accept.tolist() if isinstance(accept, torch.Tensor) else accept))
+        for i, entry in enumerate(self.states):
+            if entry.get("draft") is not None:
+                st = entry["recurrent_state"]
+                before = st.seen
+                mhla_causal_commit(entry["draft"], entry["draft_mix"], st, accept)
+                self._seen[i] += st.seen - before
+        return self.discard()
+
+    def discard(self):
+        """Drop every layer's pending draft: the states are as they were before the speculative call."""
+        for entry in self.states:
+            entry.pop("draft", None)
+            entry.pop("draft_mix", None)
         return self
 
     def __len__(self):
@@ -263,6 +286,13 @@ class MHLA(nn.Module):
         rows `[T - n_b, T)` at positions `pos_b ..` (its own rotary rows), in one `mhla_causal_extend(counts=, left_padded=True)`
         launch chain whatever the counts; the output is zero at padding rows, n_b = 0 leaves that sequence's state untouched, and
         the cache's token count grows by what the longest sequence grew.  `use_short_conv` raises NotImplementedError.
+        On a cached decode state `forward(..., speculative=True)` (through `**kwargs`; ignored without `exact_decoding`) is a VERIFY
+        of a draft: the output of the same call without the flag (rotary rows and `token_counts` handled alike), from
+        `mhla_causal_verify` -- neither the state nor the cache's token count moves, and the draft stays in the layer's cache entry
+        until `DecodeCache.commit(accept)` advances the state by each sequence's accepted prefix or `DecodeCache.discard()` drops
+        it.  A uniform cached state is replaced by `state.to_ragged()` (the same storage).  A new speculative call replaces a
+        pending draft; any other call on an entry with one raises ValueError.  `use_short_conv`, a
+        `DecodeCache(device_positions=True)` and an empty cache raise NotImplementedError.
         With a `DecodeCache(device_positions=True)` the one-token calls after the prefill are device-positioned steps (see
         `DecodeCache`; capturable in a graph); they do not reassign `mixing_matrix.data` -- generation does not change the weights
         -- and calls of several tokens on such a cache, `use_short_conv` and `head_k_dim % 8 != 0` raise NotImplementedError.
@@ -344,6 +374,8 @@ class MHLA(nn.Module):
                 past_key_values=None, use_cache: Optional[bool] = False, output_attentions: Optional[bool] = False,
                 **kwargs: Dict):
         if self.exact_decoding and bool(use_cache) and getattr(past_key_values, "device_positions", False):
+            if kwargs.get("speculative", False):
+                raise NotImplementedError("MHLA: speculative=True on a DecodeCache(device_positions=True) (a verify reads the host positions)")
             entry = self._device_positioned_entry(hidden_states, past_key_values)
             if entry is not None:
                 return self._device_positioned_step(hidden_states, entry), None, past_key_values
@@ -362,6 +394,7 @@ class MHLA(nn.Module):
         last_state = None
         if past_key_values is not None and self.layer_idx is not None and len(past_key_values) > self.layer_idx:
             last_state = past_key_values[self.layer_idx]                      # :249-251
+        speculative = self._speculative_call(past_key_values, use_cache, last_state, kwargs)
         call = self._classify_call(hidden_states, attention_mask, past_key_values, use_cache, last_state, kwargs)
         # (an exact call's mask has become the prefill's lengths, or is not read: a ragged state carries them)
         attention_mask = None if call.exact and not call.packed else attention_mask
@@ -378,13 +411,16 @@ class MHLA(nn.Module):
         q, k = self._featmap_rotary(q, k, rows, flat=call.ragged)
         fused = self.use_output_gate and self.fuse_norm_and_gate and (q_len > 64 or call.packed)
         if call.state is not None:
-            o, recurrent_state, fused = self._decode(q, k, v, hidden_states, call.state, call.token_counts)
+            o, recurrent_state, fused = self._decode(q, k, v, hidden_states, call.state, call.token_counts, speculative)
         elif call.exact:
             o, recurrent_state, fused = self._exact_prefill(q, k, v, hidden_states, call.lengths, fused, plan if call.packed else None)
         else:
             initial_state = last_state["recurrent_state"] if last_state is not None else None
             o, recurrent_state, fused = self._reference_operator(q, k, v, hidden_states, plan, fused, (batch_size, q_len), initial_state, use_cache)
-        self._update_cache(past_key_values, use_cache, call, recurrent_state, conv_states, q_len, q)
+        if speculative:   # (the verified draft, not a state: neither the state nor the cache's token count moves)
+            last_state.update(draft=recurrent_state, draft_mix=self.mixing_matrix.detach())
+        else:
+            self._update_cache(past_key_values, use_cache, call, recurrent_state, conv_states, q_len, q)
         o = self._gate_and_project(o, hidden_states, fused)
         if call.keep is not None:                                            # zeros at padding rows, as pad_input leaves them
             o = o.masked_fill(~call.keep.unsqueeze(-1), 0)
@@ -395,6 +431,26 @@ class MHLA(nn.Module):
             full.index_copy_(0, indices, o.squeeze(0))
             o = full.reshape(batch_size, q_len, -1)
         return o, None, past_key_values
+
+    def _speculative_call(self, past_key_values, use_cache, last_state, kwargs) -> bool:
+        """Whether the call is a speculative one (`speculative=True` through **kwargs; ignored without `exact_decoding`, `use_cache` and
+        a cache) -- a verify on the cached decode state, which must exist and is made ragged on the same storage -- and the refusals
+        around a pending draft: a new speculative call replaces it, any other call is refused until `commit` or `discard`."""
+        exact = self.exact_decoding and bool(use_cache) and past_key_values is not None and hasattr(past_key_values, "update")
+        speculative = exact and bool(kwargs.get("speculative", False))
+        if not speculative:
+            if exact and last_state is not None and last_state.get("draft") is not None:
+                raise ValueError("MHLA(exact_decoding=True): the cache holds a pending draft of a speculative call: commit or discard first "
+                                 "(DecodeCache.commit(accept) / DecodeCache.discard())")
+            return False
+        if self.use_short_conv:
+            raise NotImplementedError("MHLA(exact_decoding=True): use_short_conv with speculative=True (the convolution's state has no verify)")
+        state = last_state["recurrent_state"] if last_state is not None else None
+        if not isinstance(state, CausalState):
+            raise NotImplementedError("MHLA(exact_decoding=True): speculative=True on an empty cache: a draft is verified on the decode state "
+                                      "a prefill left")
+        last_state["recurrent_state"] = state.to_ragged()   # (shares storage; a ragged state returns itself)
+        return True
 
     def _classify_call(self, hidden_states, attention_mask, past_key_values, use_cache, last_state, kwargs) -> _Call:
         """Which kind of call this is (see `_Call`), and every refusal that depends on the kind."""
@@ -534,14 +590,17 @@ class MHLA(nn.Module):
             return None, None
         return self.g_proj(hidden_states).reshape(*hidden_states.shape[:2], self.num_heads, self.head_v_dim), self.g_norm_swish_gate
 
-    def _decode(self, q, k, v, hidden_states, state, token_counts):
-        """Decoding on the state the prefill (or the calls before) left: one exact step for one token, one extension for several."""
+    def _decode(self, q, k, v, hidden_states, state, token_counts, speculative=False):
+        """Decoding on the state the prefill (or the calls before) left: one exact step for one token, one extension for several.
+        `speculative`: a verify -- the same rows, the state untouched, and the `CausalDraft` returned in the state's place."""
         B, T = q.shape[:2]
         g, gn = self._fused_gate(hidden_states)
-        advance = mhla_causal_step if T == 1 and token_counts is None else mhla_causal_extend
+        advance = mhla_causal_verify if speculative else mhla_causal_step if T == 1 and token_counts is None else mhla_causal_extend
         counted = {} if token_counts is None else {"counts": token_counts, "left_padded": True}
         o = advance(q, k, v, self.mixing_matrix, state, gate=g, norm_weight=gn.weight if gn is not None else None,
                     norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None, **counted)
+        if speculative:
+            o, state = o
         return (o.reshape(B, T, self.value_dim) if gn is not None else o), state, gn is not None
 
     def _exact_prefill(self, q, k, v, hidden_states, lengths, fused, plan=None):

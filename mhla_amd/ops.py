@@ -1812,6 +1812,28 @@ def _counts_tuple(fn, counts, B, T):
     return counts
 
 
+def _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, scale, gate, norm_weight, epilogue):
+    """What a call with per-sequence `counts` (`mhla_causal_extend(counts=)`, `mhla_causal_verify`) checks, in the order callers rely
+    on, before anything is launched or `state` is touched; returns (counts as a tuple, what `_decode_prepare` returns)."""
+    B, T = q.shape[:2]
+    counts = _counts_tuple(fn, counts, B, T)
+    if state.lengths is None:
+        raise ValueError(f"{fn}: counts needs a ragged state and this one is uniform ({state!r}); the positions must live on the "
+                         "device: pass state.to_ragged()")
+    if len(state.lengths) != B:
+        raise ValueError(f"{fn}: the state holds {len(state.lengths)} sequences, the tokens B={B}")
+    if mixing_matrix.dim() < 2:
+        raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
+    L, cap = mixing_matrix.shape[0], state.capacity_chunks
+    need = [(p + n + 63) // 64 if n else 0 for p, n in zip(state.lengths, counts)]
+    for limit, what in ((L, f"mixing_matrix has only {L} rows"), (cap, f"the state holds only {cap}")):
+        over = [b for b, c in enumerate(need) if c > limit]
+        if over:
+            raise IndexError(f"{fn}: sequences {over} (lengths {tuple(state.lengths[b] for b in over)} + counts "
+                             f"{tuple(counts[b] for b in over)}) need up to {max(need)} chunks but {what}")
+    return counts, _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=False)
+
+
 def _ragged_plan(lengths, counts, cap):
     """What `mhla_causal_extend_ragged` is told about the device arrays of one batch slice: (max_end, max_later, any_close, the
     last row of the mixing matrix it may read)."""
@@ -1824,23 +1846,37 @@ def _ragged_plan(lengths, counts, cap):
     return max_end, max_later, any_close, (min(max_end // 64, cap - 1) if any_close else (max_end - 1) // 64)
 
 
+def _ragged_slices(fn, state, counts, H, mixf):
+    """The batch slices of one ragged call, (first, end, `_ragged_plan`) each, after what the library checks per launch was checked
+    for every slice before the first launch (see mhla_causal_step)."""
+    B = len(counts)
+    nb = min(B, _MAX_GRID_BH // H)
+    slices = [(i, min(B, i + nb), _ragged_plan(state.lengths[i:i + nb], counts[i:i + nb], state.capacity_chunks)) for i in range(0, B, nb)]
+    for i, j, plan in slices:
+        if plan[0] and mixf.shape[1] < plan[3] + 1:
+            raise IndexError(f"{fn}: sequences {list(range(i, j))} (lengths {state.lengths[i:j]}, counts {counts[i:j]}): row {plan[3]} of "
+                             f"mixing_matrix is read, which has only {mixf.shape[1]} columns")
+    return slices
+
+
 @_device_guard
-def _causal_extend_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, pos, ntok, plan, left_padded, res, norm_eps):
+def _causal_extend_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, pos, ntok, plan, left_padded, res, norm_eps,
+                          fn="mhla_causal_extend_ragged"):
     """One launch chain of `mhla_causal_extend_ragged` on what `_decode_prepare` returned, for the sequences `state` (a batch slice)
     holds: `pos` their device positions, which the chain advances, `ntok` their token counts on the device, `plan` the host
-    values of `_ragged_plan`."""
+    values of `_ragged_plan`.  fn="mhla_causal_verify_ragged": the same arguments and rows, nothing committed."""
     lib = _lib.load()
     B, T, H, K = q.shape
     V = v.shape[-1]
     dt = _dtype_code(q)
     max_end, max_later, any_close, _ = plan
     ws = _ws(lib.mhla_causal_extend_ragged_ws_bytes(B, T, H, K, V, max_later, dt), q.device)
-    rc = lib.mhla_causal_extend_ragged(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-                                       state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), ntok.data_ptr(), T, max_end, max_later,
-                                       int(any_close), int(bool(left_padded)), NULL_VIEW if want_y else _view(res), _view_or_null(gate),
-                                       _ptr(wf), float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K,
-                                       V, state.chunk_size, float(scale), dt, _stream())
-    _lib.check(rc, "mhla_causal_extend_ragged")
+    rc = getattr(lib, fn)(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+                          state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), ntok.data_ptr(), T, max_end, max_later,
+                          int(any_close), int(bool(left_padded)), NULL_VIEW if want_y else _view(res), _view_or_null(gate),
+                          _ptr(wf), float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K,
+                          V, state.chunk_size, float(scale), dt, _stream())
+    _lib.check(rc, fn)
 
 
 def _extend_run(prepared, state, res, norm_eps, i, j, p, t_lo, t_hi, step_t):
@@ -1871,13 +1907,7 @@ def _extend_counts(fn, prepared, state, counts, left_padded, res, norm_eps):
     B, T, H, K = q.shape
     V = v.shape[-1]
     nb = min(B, _MAX_GRID_BH // H)
-    cap = state.capacity_chunks
-    slices = [(i, min(B, i + nb), _ragged_plan(state.lengths[i:i + nb], counts[i:i + nb], cap)) for i in range(0, B, nb)]
-    # what the library checks per launch, for every slice before the first launch (see mhla_causal_step)
-    for i, j, plan in slices:
-        if plan[0] and mixf.shape[1] < plan[3] + 1:
-            raise IndexError(f"{fn}: sequences {list(range(i, j))} (lengths {state.lengths[i:j]}, counts {counts[i:j]}): row {plan[3]} of "
-                             f"mixing_matrix is read, which has only {mixf.shape[1]} columns")
+    slices = _ragged_slices(fn, state, counts, H, mixf)
     lib = _lib.load()
     dt = _dtype_code(q)
     if any(lib.mhla_causal_extend_ragged_ws_bytes(j - i, T, H, K, V, plan[1], dt) > EXTEND_WS_CAP_BYTES for i, j, plan in slices):
@@ -1942,22 +1972,7 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     if T < 1:
         raise ValueError(f"mhla_causal_extend takes at least one token per call, got T = {T}")
     if counts is not None:
-        counts = _counts_tuple(fn, counts, B, T)
-        if state.lengths is None:
-            raise ValueError(f"{fn}: counts needs a ragged state and this one is uniform ({state!r}); the positions must live on the "
-                             "device: pass state.to_ragged()")
-        if len(state.lengths) != B:
-            raise ValueError(f"{fn}: the state holds {len(state.lengths)} sequences, the tokens B={B}")
-        if mixing_matrix.dim() < 2:
-            raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
-        L, cap = mixing_matrix.shape[0], state.capacity_chunks
-        need = [(p + n + 63) // 64 if n else 0 for p, n in zip(state.lengths, counts)]
-        for limit, what in ((L, f"mixing_matrix has only {L} rows"), (cap, f"the state holds only {cap}")):
-            over = [b for b, c in enumerate(need) if c > limit]
-            if over:
-                raise IndexError(f"{fn}: sequences {over} (lengths {tuple(state.lengths[b] for b in over)} + counts "
-                                 f"{tuple(counts[b] for b in over)}) need up to {max(need)} chunks but {what}")
-        prepared = _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=False)
+        counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, scale, gate, norm_weight, epilogue)
         if not any(counts):
             return torch.zeros((B, T, H, V), dtype=q.dtype, device=q.device)
         return _extend_counts(fn, prepared, state, counts, left_padded, _alloc_like_tokens(B, T, H, V, q), norm_eps)
@@ -1980,6 +1995,145 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
         state.lengths = tuple(n + T for n in state.lengths)
     state.seen = pos + T
     return res
+
+
+class CausalDraft:
+    """What `mhla_causal_verify` hands to `mhla_causal_commit`: the draft's prepared `k`, `v` (REFERENCES to the tensors the verify
+    read, or to their contiguous copies -- not copies of their own), `counts` (B ints), `left_padded`, and `lengths`, the state's
+    lengths when the draft was verified, which a commit holds the state to."""
+
+    __slots__ = ("k", "v", "counts", "left_padded", "lengths")
+
+    def __init__(self, k, v, counts, left_padded, lengths):
+        self.k, self.v, self.counts, self.left_padded, self.lengths = k, v, tuple(counts), bool(left_padded), tuple(lengths)
+
+    def __repr__(self):
+        return f"CausalDraft(counts={self.counts}, left_padded={self.left_padded}, lengths={self.lengths})"
+
+
+def mhla_causal_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
+                       counts=None, left_padded: bool = False, scale: Optional[float] = None, gate: Optional[torch.Tensor] = None,
+                       norm_weight: Optional[torch.Tensor] = None, norm_eps: float = 1e-5, epilogue: Optional[bool] = None):
+    """`(o, draft)`: the rows `mhla_causal_extend(q, k, v, mixing_matrix, state, counts=counts, left_padded=left_padded, ...)` would
+    return, bit for bit, WITHOUT committing a token -- a draft of speculative, lookup or multi-token-prediction decoding to verify.
+    `state` is untouched: `P`, `Cur`, `pos`, the finished chunks of `S`, `lengths` and `seen` are as before, so any call on it gives
+    what it would have given (rows of `S` beyond a sequence's finished chunks are scribbled on; they are outside the state's
+    contract, nothing reads them before a later call finishes them).  No copy of the state is made.
+    state: a ragged one that is not stale (ValueError otherwise: `state.to_ragged()` makes one on the same storage).  counts (B ints
+    in 0 .. T, default T for every sequence), left_padded, the epilogue arguments, strided views, inference only and the
+    IndexErrors: as `mhla_causal_extend(counts=)` -- the WHOLE draft must fit the mixing matrix and the capacity.  The same six
+    launches at most; all counts 0: nothing is launched.  Batches beyond one launch's (b, h) range are sliced; a call whose workspace
+    would exceed `EXTEND_WS_CAP_BYTES` raises ValueError (drafts are short: there is no sequential fallback).
+    `draft` (a `CausalDraft`) is what `mhla_causal_commit` takes to advance the state by an accepted prefix.  It holds references to
+    k and v (or to the contiguous copies the call made), not copies: the caller must not overwrite k, v before the commit."""
+    fn = "mhla_causal_verify"
+    if not isinstance(state, CausalState):
+        raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
+    state._refuse_stale(fn)
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
+    B, T, H, K = q.shape
+    V = v.shape[-1]
+    if T < 1:
+        raise ValueError(f"{fn} takes at least one token per call, got T = {T}")
+    counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, (T,) * B if counts is None else counts, scale, gate,
+                                       norm_weight, epilogue)
+    q, k, v, gate, mixf, wf, _, scale, want_y = prepared
+    draft = CausalDraft(k, v, counts, left_padded, state.lengths)
+    if not any(counts):
+        return torch.zeros((B, T, H, V), dtype=q.dtype, device=q.device), draft
+    slices = _ragged_slices(fn, state, counts, H, mixf)
+    lib = _lib.load()
+    dt = _dtype_code(q)
+    need = max(lib.mhla_causal_extend_ragged_ws_bytes(j - i, T, H, K, V, plan[1], dt) for i, j, plan in slices)
+    if need > EXTEND_WS_CAP_BYTES:
+        raise ValueError(f"{fn}: a draft of T={T} tokens for {B} sequences needs a workspace of {need} bytes, more than "
+                         f"EXTEND_WS_CAP_BYTES={EXTEND_WS_CAP_BYTES}: verify fewer tokens or sequences per call")
+    res = _alloc_like_tokens(B, T, H, V, q)
+    ntok = torch.tensor(counts, dtype=torch.int32).to(q.device)   # the one small copy of the call
+    for i, j, plan in slices:
+        if len(slices) == 1:   # the usual case, one launch chain: no views to build
+            _causal_extend_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, state.pos, ntok, plan, left_padded, res, norm_eps,
+                                  "mhla_causal_verify_ragged")
+            break
+        sl = lambda x: None if x is None else x[i:j]
+        part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], 0, 64)
+        _causal_extend_ragged(sl(q), sl(k), sl(v), sl(gate), mixf, wf, scale, want_y, part, state.pos[i:j], ntok[i:j], plan, left_padded,
+                              sl(res), norm_eps, "mhla_causal_verify_ragged")
+    return res, draft
+
+
+@_device_guard
+def _causal_commit_ragged(k, v, mixf, state, pos, ntok, acc, plan, left_padded):
+    """One launch chain of `mhla_causal_commit_ragged` for the sequences `state` (a batch slice) holds: `pos` their device positions,
+    which the chain advances, `ntok` / `acc` the draft's and the accepted counts on the device, `plan` the host values of
+    `_ragged_plan` for the accepted counts."""
+    lib = _lib.load()
+    B, T, H, K = k.shape
+    V = v.shape[-1]
+    dt = _dtype_code(k)
+    max_end, max_later, any_close, _ = plan
+    ws = _ws(lib.mhla_causal_commit_ragged_ws_bytes(B, dt), k.device)
+    rc = lib.mhla_causal_commit_ragged(_view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+                                       state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), ntok.data_ptr(), acc.data_ptr(), T, max_end,
+                                       max_later, int(any_close), int(bool(left_padded)), ws.data_ptr(), ws.numel() * 4, B, H, K, V,
+                                       state.chunk_size, dt, _stream())
+    _lib.check(rc, "mhla_causal_commit_ragged")
+
+
+def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: CausalState, accept) -> CausalState:
+    """Advance `state` by the first `accept[b]` tokens of every sequence's verified draft (`draft`: what `mhla_causal_verify`
+    returned for this state); returns `state`.  Afterwards the state -- every sequence's finished chunks, `P`, `Cur`, `pos`, `lengths`,
+    `seen` -- is bit for bit the one `mhla_causal_extend(..., counts=accept)` leaves when called instead of the verify.  At most four
+    launches, which read the draft's k and v only; no rows are computed.
+    accept: B ints, or a tensor (read once, which synchronises a device tensor), 0 <= accept[b] <= draft.counts[b]; anything else is
+    a ValueError, as is a state that moved since the verify (`state.lengths != draft.lengths`), a uniform or a stale state.  All
+    zeros (every draft rejected): nothing is launched and the state is bit for bit as before."""
+    fn = "mhla_causal_commit"
+    if not isinstance(draft, CausalDraft):
+        raise TypeError(f"{fn}: draft must be a CausalDraft (what mhla_causal_verify returns), got {type(draft).__name__}")
+    if not isinstance(state, CausalState):
+        raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
+    state._refuse_stale(fn)
+    if state.lengths is None:
+        raise ValueError(f"{fn}: the state is uniform ({state!r}); a draft is verified on, and committed to, a ragged state")
+    B = len(draft.counts)
+    accept = tuple(int(n) for n in (accept.tolist() if isinstance(accept, torch.Tensor) else accept))
+    if len(accept) != B:
+        raise ValueError(f"{fn}: accept has {len(accept)} entries, the draft B={B}")
+    if any(a < 0 or a > n for a, n in zip(accept, draft.counts)):
+        raise ValueError(f"{fn}: accept={accept} must be in 0 .. counts={draft.counts} of the draft")
+    if tuple(state.lengths) != draft.lengths:
+        raise ValueError(f"{fn}: the state moved since the verify: lengths {state.lengths}, the draft was verified at {draft.lengths}")
+    if not any(accept):
+        return state
+    k, v = draft.k, draft.v
+    _, T, H, K = k.shape
+    if tuple(state.S.shape) != (B, H, state.capacity_chunks, K, v.shape[-1]) or state.S.device != k.device:
+        raise ValueError(f"{fn}: state is {state!r}, the draft has B={B} H={H} K={K} V={v.shape[-1]} on {k.device}")
+    if mixing_matrix.dim() < 2 or mixing_matrix.device != k.device:
+        raise ValueError(f"{fn}: mixing_matrix must be [L, L(, 1, 1, 1, 1)] on {k.device}, got {tuple(mixing_matrix.shape)} on "
+                         f"{mixing_matrix.device}")
+    _require_gpu(k, v, mixing_matrix)
+    mixf = _mix2d(mixing_matrix)
+    slices = _ragged_slices(fn, state, accept, H, mixf)
+    if any(plan[0] and mixf.shape[0] < plan[3] + 1 for _, _, plan in slices):
+        raise IndexError(f"{fn}: mixing_matrix has only {mixf.shape[0]} rows, fewer than the accepted tokens read (lengths "
+                         f"{state.lengths}, accept {accept})")
+    dev = k.device
+    both = torch.tensor((draft.counts, accept), dtype=torch.int32).to(dev)   # the one small copy of the call
+    ntok, acc = both[0], both[1]
+    for i, j, plan in slices:
+        if not plan[0]:
+            continue
+        if len(slices) == 1:
+            _causal_commit_ragged(k, v, mixf, state, state.pos, ntok, acc, plan, draft.left_padded)
+            break
+        part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], 0, 64)
+        _causal_commit_ragged(k[i:j], v[i:j], mixf, part, state.pos[i:j], ntok[i:j], acc[i:j], plan, draft.left_padded)
+    state.lengths = tuple(p + a for p, a in zip(state.lengths, accept))
+    state.seen = max(state.lengths)
+    return state
 
 
 # ------------------------------------------------------------------------------------------

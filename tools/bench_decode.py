@@ -56,6 +56,14 @@ Alternating in one run, `--reps` times, `--steps` calls each (at most 20): wall 
 of the library's kernels and its launches per call (the per-launch event hook); the same for the state half alone
 (`mhla_causal_state`).  The plan is built once, outside the timed calls, as a server builds it once per batch for all layers.
 
+`--speculative`: one round of speculative decoding at the 340M layer shape (H = 4, K = 128, V = 256, bf16, L = 128), a history of 2048
+tokens, a draft of k = 4 (the verify sees 5 tokens: the last one and the draft), B = 1 and 8: (a) `mhla_causal_verify` + `mhla_causal_commit`
+of all 5, (b) the same with 2 of 5 accepted, (c) the round without them -- `CausalState.clone()` (4 K V bytes per chunk and head of S),
+`mhla_causal_extend(counts=)` on the clone -- and (d) five exact steps (`mhla_causal_step` on the uniform state; 2048 .. 2052: no
+boundary).  Alternating in one run, `--reps` times, `--steps` calls each: wall time per call with median, min and max, the device time of
+the library's kernels and its launches per call (the per-launch event hook).  The state is put back before every call -- host mirror and
+a 4 B-byte device copy of the positions, given to every variant -- so that every call is the same work.
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -372,6 +380,69 @@ def mixed_config(H, K, V, steps, reps, slice_tokens=256):
     return rec
 
 
+def speculative_config(B, H, K, V, steps, reps, pos=2048, k=4):
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    T = k + 1
+    q, kk = (torch.randn(B, T, H, K, generator=g).to(torch.bfloat16).to(DEV) for _ in range(2))
+    v = torch.randn(B, T, H, V, generator=g).to(torch.bfloat16).to(DEV)
+    st = mhla_amd.CausalState.empty(B, H, K, V, L, DEV)
+    st.S[:, :, :pos // 64].normal_(0, 0.1)
+    st.P.normal_(0, 0.1)
+    lengths = (pos,) * B
+    rag = mhla_amd.CausalState(st.S, st.P, st.Cur, lengths=lengths)
+    uni = mhla_amd.CausalState(st.S, st.P, st.Cur, pos)
+    pos0 = torch.tensor(lengths, dtype=torch.int32, device=DEV)
+    spare = torch.empty_like(pos0)
+    counts = (T,) * B
+
+    def put_back():
+        rag.lengths, rag.seen = lengths, pos
+        rag.pos.copy_(pos0)
+
+    def round_of(accept):
+        def fn():
+            put_back()
+            _, draft = mhla_amd.mhla_causal_verify(q, kk, v, mix, rag, counts=counts)
+            mhla_amd.mhla_causal_commit(draft, mix, rag, accept)
+        return fn
+
+    def clone_extend():
+        put_back()
+        mhla_amd.mhla_causal_extend(q, kk, v, mix, rag.clone(), counts=counts)
+
+    def five_steps():
+        spare.copy_(pos0)
+        uni.seen = pos
+        for t in range(T):
+            mhla_amd.mhla_causal_step(q[:, t:t + 1], kk[:, t:t + 1], v[:, t:t + 1], mix, uni)
+
+    fns = {"verify_commit_all": round_of((T,) * B), "verify_commit_2_of_5": round_of((2,) * B), "clone_extend": clone_extend,
+           "five_steps": five_steps}
+    wall = {n: [] for n in fns}
+    dev = {n: [] for n in fns}
+    kern = {}
+    with torch.no_grad():
+        for _ in range(reps):
+            for n, fn in fns.items():
+                wall[n].append(batch_us(fn, steps))
+            for n, fn in fns.items():
+                kern[n] = kernel_times(fn, iters=20)
+                dev[n].append(sum(kern[n].values()))
+            st.Cur.zero_()
+        launches = {n: launch_counts(fn) for n, fn in fns.items()}
+    med = {n: statistics.median(x) for n, x in wall.items()}
+    rec = {"speculative": {"B": B, "H": H, "K": K, "V": V, "pos": pos, "draft_len": k, "verify_tokens": T}, "steps_per_batch": steps, "reps": reps,
+           "wall_us": {n: spread(x) for n, x in wall.items()}, "device_us": {n: spread(x) for n, x in dev.items()},
+           "launches": {n: {"total": sum(c.values()), "by_kernel": c} for n, c in launches.items()},
+           "five_steps_over_round_wall": round(med["five_steps"] / med["verify_commit_all"], 2),
+           "clone_extend_over_round_wall": round(med["clone_extend"] / med["verify_commit_all"], 2),
+           "state_MB": round(rag.nbytes / 2 ** 20, 1),
+           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()}}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def packed_prefill_config(H, K, V, iters, reps, cap=40):
     lengths = (100, 333, 517, 777, 1024, 1300, 1701, 2048)
     B, T = len(lengths), max(lengths)
@@ -559,8 +630,12 @@ if __name__ == "__main__":
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--mixed", action="store_true")
     ap.add_argument("--packed-prefill", action="store_true")
+    ap.add_argument("--speculative", action="store_true")
     a = ap.parse_args()
-    if a.packed_prefill:
+    if a.speculative:
+        for B in (1, 8):
+            speculative_config(B, 4, 128, 256, max(100, a.steps), a.reps)
+    elif a.packed_prefill:
         packed_prefill_config(4, 128, 256, min(20, a.steps), a.reps)
     elif a.mixed:
         mixed_config(4, 128, 256, max(100, a.steps), a.reps)
