@@ -525,6 +525,40 @@ int mhla_causal_commit_ragged(mhla_view k, mhla_view v, const float* mix, int ld
                               int max_later, int any_close, int left_padded, void* ws, size_t ws_bytes, int B, int H, int K, int V,
                               int chunk, int dtype, void* stream);
 
+/* Grouped-query heads (added without a change of any existing signature or behaviour: MHLA_ABI_VERSION stays 9).  S, P and Cur are
+ * functions of k and v alone, so with Hkv k/v heads serving H = G Hkv query heads (query head h uses k/v head h / G) the G heads of
+ * a group share one state.  The four calls below are their namesakes with one more integer, `Hkv`, after `H`: q, gate, out, y have H
+ * heads; k, v have Hkv heads; S is [B][Hkv][cap_chunks][K][V], P and Cur [B][Hkv][K][V].  Rows, state and pos_dev afterwards are bit for
+ * bit those of the namesake on k, v repeated G times per head with a state of H heads (every head of a group then holding the same
+ * state): each sum has the same terms in the same order -- the K split of the step is chosen from the query head count for that
+ * reason -- while P and Cur are read, and Cur written, once per k/v head: 1 / G of the state, of the per-token traffic and of the
+ * chunk-boundary re-mix.  Hkv = H is the namesake itself (the same launches).  mhla_causal_state_init, mhla_causal_varlen_state_init
+ * and mhla_causal_commit_ragged touch no q: they serve a grouped state as they are, given the un-repeated k, v and H = Hkv.
+ * Checks, before any launch: MHLA_EINVAL for Hkv < 1 or H % Hkv != 0, MHLA_ENOTSUP for H / Hkv > 8; everything else as the namesake
+ * (B*H <= 65535 counts query heads).  Workspace of the steps: mhla_causal_step_ws_bytes(B, H, ...), the query head count; of the extend
+ * and the verify (mhla_causal_extend_ragged_gqa_ws_bytes), in 4-byte words, each term rounded up to a multiple of 4:
+ * B Hkv max_later K V  +  B H T V  +  B. */
+int mhla_causal_step_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                                float* Cur, int32_t* pos_dev, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate,
+                                const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K,
+                                int V, int chunk, float scale, int dtype, void* stream);
+int mhla_causal_step_dev_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                             float* Cur, int32_t* pos_dev, int32_t* full_dev, const void* rope_cos, const void* rope_sin, int64_t ld_tab,
+                             int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                             mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
+                             int dtype, void* stream);
+size_t mhla_causal_extend_ragged_gqa_ws_bytes(int B, int T, int H, int Hkv, int K, int V, int max_later, int dtype);
+int mhla_causal_extend_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                                  float* Cur, int32_t* pos_dev, const int32_t* ntok_dev, int T, int64_t max_end, int max_later,
+                                  int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                                  mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
+                                  int dtype, void* stream);
+int mhla_causal_verify_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                                  float* Cur, const int32_t* pos_dev, const int32_t* ntok_dev, int T, int64_t max_end, int max_later,
+                                  int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                                  mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
+                                  int dtype, void* stream);
+
 /* ---- prologue: q / k of the Wan host -------------------------------------- */
 
 /*

@@ -111,6 +111,20 @@ SIGNATURES = {
     "mhla_causal_commit_ragged": (c_int, [View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_int, c_int64, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_void_p]),
+    # grouped-query heads: the namesakes with Hkv after H
+    "mhla_causal_step_ragged_gqa": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                            View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_float, c_int, c_void_p]),
+    "mhla_causal_step_dev_gqa": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_int64, c_int64, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int,
+                                         c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "mhla_causal_extend_ragged_gqa_ws_bytes": (c_size_t, [c_int] * 8),
+    "mhla_causal_extend_ragged_gqa": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                              c_int64, c_int, c_int, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int,
+                                              c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "mhla_causal_verify_ragged_gqa": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                              c_int64, c_int, c_int, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int,
+                                              c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "mhla_featmap_rotary": (c_int, [View,View, c_void_p, c_void_p, c_int64, c_int64, View, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_void_p]),
     "mhla_lepe2d": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,

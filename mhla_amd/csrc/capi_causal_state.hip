@@ -1,5 +1,5 @@
 // C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
-// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged, and the grouped-query forms mhla_causal_*_gqa of the ragged entry points; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
@@ -18,6 +18,12 @@ int cst_check(int B, int H, int K, int V, int chunk, int dtype) {
     if ((K | V) & 3) return fail(MHLA_EINVAL, "K=%d and V=%d must be multiples of 4", K, V);
     if (dtype < 0 || dtype > 2) return fail(MHLA_EINVAL, "unknown dtype %d", dtype);
     if ((size_t)B * H > 65535) return fail(MHLA_ENOTSUP, "B*H=%zu exceeds grid limit 65535", (size_t)B * H);
+    return MHLA_OK;
+}
+// grouped-query heads: the state, k and v have Hkv heads, each shared by G = H / Hkv query heads (Hkv = H: the ungrouped call)
+int cst_check_group(int H, int Hkv) {
+    if (Hkv < 1 || H % Hkv) return fail(MHLA_EINVAL, "Hkv=%d must be positive and divide H=%d", Hkv, H);
+    if (H / Hkv > CST_GMAX) return fail(MHLA_ENOTSUP, "H=%d query heads on Hkv=%d k/v heads: at most %d per k/v head are supported", H, Hkv, CST_GMAX);
     return MHLA_OK;
 }
 int cst_check_state(const float* S, int cap, const float* P, const float* Cur) {
@@ -79,11 +85,14 @@ int cst_zero_cur(float* Cur, int BH, long E, hipStream_t st) {
     return MHLA_OK;
 }
 // one launch of a k_cs_step variant: fills in the K split (s.kr rows per workgroup, s.nsplit partial sums per output, which the finish adds)
+// BH counts the query heads, G of which share a workgroup (s.H: the k/v heads): the split is the one of the ungrouped call on
+// repeated heads, so that every sum has its terms and its order
 template <typename KERN>
-int cst_step(KERN kernel, const char* name, CsStepArgs& s, int BH, hipStream_t st) {
+int cst_step(KERN kernel, const char* name, CsStepArgs& s, int BH, hipStream_t st, int G = 1) {
+    s.G = G;
     s.kr = cst_rows((size_t)BH, s.K, s.V);
     s.nsplit = (s.K + s.kr - 1) / s.kr;
-    return launch(kernel, dim3((s.V + CST_VT - 1) / CST_VT, s.nsplit, BH), dim3(CST_THREADS), 0, st, name, s);
+    return launch(kernel, dim3((s.V + CST_VT - 1) / CST_VT, s.nsplit, BH / G), dim3(CST_THREADS), 0, st, name, s);
 }
 
 template <typename T>
@@ -135,9 +144,9 @@ CxPlan cx_plan(int B, int T, int H, int K, int V, int64_t pos) {
 struct CxRagPlan {
     size_t tiles, stage, nval, total;
 };
-CxRagPlan cx_rag_plan(int B, int T, int H, int K, int V, int max_later) {
+CxRagPlan cx_rag_plan(int B, int T, int H, int Hkv, int K, int V, int max_later) {   // (tiles per k/v head, rows per query head)
     CxRagPlan p{};
-    p.tiles = al4((size_t)B * H * max_later * K * V);
+    p.tiles = al4((size_t)B * Hkv * max_later * K * V);
     p.stage = al4((size_t)B * H * T * V);
     p.nval = al4((size_t)B);
     p.total = p.tiles + p.stage + p.nval;
@@ -164,19 +173,22 @@ int cx_rag_check(int T, int cap_chunks, const int32_t* pos_dev, const int32_t* n
 }
 
 // the ragged extend chain; dry (the verify): the same launches, nothing of the committed state -- Cur, P, pos_dev -- written
+// Hkv < H (grouped-query heads): the launches that form or move state run over the B Hkv k/v heads, the two that compute rows
+// (k_cx_out, the finish) over the B H query heads
 int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
                     float* Cur, int32_t* pos_dev, const int32_t* ntok_dev, int T, int64_t max_end, int max_later, int any_close,
                     int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws,
-                    size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype, void* stream) {
+                    size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream) {
     RC(cst_check(B, H, K, V, chunk, dtype));
+    RC(cst_check_group(H, Hkv));
     if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive", T);
     if (T > 65535) return fail(MHLA_EINVAL, "T=%d exceeds 65535 tokens per call", T);   // (mhla_causal_extend answers MHLA_ENOTSUP here: kept, a caller may test the code)
     RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
     RC(cx_rag_check(T, cap_chunks, pos_dev, ntok_dev, max_end, max_later, any_close, mix, ldmix));
-    const CxRagPlan p = cx_rag_plan(B, T, H, K, V, max_later);
+    const CxRagPlan p = cx_rag_plan(B, T, H, Hkv, K, V, max_later);
     RC(cst_check_ws(ws, ws_bytes, p.total * 4));
     hipStream_t st = (hipStream_t)stream;
-    const int BH = B * H, nvt = (V + 63) / 64, strips = ((K + 63) / 64) * nvt;
+    const int BH = B * H, BHk = B * Hkv, nvt = (V + 63) / 64, strips = ((K + 63) / 64) * nvt;
     const long E = (long)K * V;
     float* tiles = (float*)ws;
     float* stage = tiles + p.tiles;
@@ -189,18 +201,19 @@ int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float
         o.q = cv(q); o.k = cv(k); o.v = cv(v);
         o.stage = stage; o.H = H; o.K = K; o.V = V; o.T = T; o.scale = scale; o.mstep = (long)ldmix + 1;
         o.P = P; o.Cur = Cur; o.mdiag = mix; o.rag = g; o.later = 0; o.nval = nval; o.kr = kr; o.nsplit = (K + kr - 1) / kr;
+        o.G = H / Hkv;
         RC(launch(k_cx_out<ET, true>, dim3(1, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out_ragged", o));
         CxAccArgs c{};
-        c.x = cv(k); c.y = cv(v); c.H = H; c.DX = K; c.DY = V; c.rag = g; c.later = 0; c.S = S; c.Cur = Cur;
-        RC(launch(k_cx_xty_acc<ET, true>, dim3(1, BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+        c.x = cv(k); c.y = cv(v); c.H = Hkv; c.DX = K; c.DY = V; c.rag = g; c.later = 0; c.S = S; c.Cur = Cur;
+        RC(launch(k_cx_xty_acc<ET, true>, dim3(1, BHk, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
         if (any_close) {
             c.later = 1;
-            RC(launch(k_cx_xty_acc<ET, true>, dim3(std::max(1, max_later), BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+            RC(launch(k_cx_xty_acc<ET, true>, dim3(std::max(1, max_later), BHk, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
             CxMixRagArgs m{};
             m.m.S = S; m.m.ws = tiles; m.m.P = P; m.m.mix = mix; m.m.E = E; m.m.ldmix = ldmix; m.m.cap = cap_chunks;
-            m.rag = g; m.H = H;
+            m.rag = g; m.H = Hkv;
             const int groups = (max_later + 1 + CX_MIX_NC - 1) / CX_MIX_NC;   // (the largest nc is max_later + 1)
-            RC(launch(k_cx_mix_ragged, dim3((unsigned)((E / 4 + 63) / 64), BH, groups), dim3(64), 0, st, "k_cx_mix_ragged", m));
+            RC(launch(k_cx_mix_ragged, dim3((unsigned)((E / 4 + 63) / 64), BHk, groups), dim3(64), 0, st, "k_cx_mix_ragged", m));
             if (max_later) {
                 o.P = tiles; o.Cur = nullptr; o.later = 1;
                 RC(launch(k_cx_out<ET, true>, dim3(max_later, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out_ragged", o));
@@ -209,6 +222,87 @@ int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float
         CsFinishArgs f{stage, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, 1, dry ? nullptr : pos_dev};
         f.nval = nval; f.left = left_padded ? 1 : 0;
         RC(launch(k_cs_step_finish<ET, false, true>, dim3(BH, T), dim3(CST_THREADS), 0, st, "k_cs_step_finish_ragged", f));
+    });
+    return MHLA_OK;
+}
+
+// the ragged step chain (step, roll, finish); Hkv < H (grouped-query heads): step and roll run over the B Hkv k/v heads, the step
+// writing the partial sums of all B H query heads, which the finish reads as ever
+int cs_step_ragged_chain(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                         float* Cur, int32_t* pos_dev, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate,
+                         const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V,
+                         int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check(B, H, K, V, chunk, dtype));
+    RC(cst_check_group(H, Hkv));
+    RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
+    RC(cst_check_dev("pos_dev", pos_dev));
+    if (max_pos < 0 || max_pos >= INT32_MAX) return fail(MHLA_EINVAL, "max_pos=%lld is negative or beyond int32", (long long)max_pos);
+    const int64_t i = max_pos / chunk;
+    if (i >= cap_chunks) return fail(MHLA_EINVAL, "max_pos=%lld is in chunk %lld, the state holds %d", (long long)max_pos, (long long)i, cap_chunks);
+    // which sequence is on a boundary is known on the device only: with any_boundary the row after the furthest sequence's chunk
+    // must be covered (unless that chunk is the state's last), as if that sequence were the one -- a restriction (mhla_hip.h):
+    // the matrix passed with a boundary step reaches one row past the furthest sequence, or the state's capacity
+    const bool next = any_boundary && i + 1 < cap_chunks;
+    RC(cst_check_mix(mix, ldmix, i + (next ? 1 : 0)));
+    RC(cst_check_ws(ws, ws_bytes, cst_ws_bytes(B, H, K, V)));
+    hipStream_t st = (hipStream_t)stream;
+    const int BH = B * H, G = H / Hkv;
+    // step and roll address by pos_dev; the finish, which does not, advances it: last in the chain
+    DISPATCH_T(dtype, {
+        CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, Hkv, K, V, 0, 0, pos_dev, ldmix, (int)max_pos};
+        if (G == 1) RC(cst_step(k_cs_step<ET, true>, "k_cs_step_ragged", s, BH, st));
+        else        RC(cst_step(k_cs_step<ET, true, false, false, CST_GMAX>, "k_cs_step_ragged<gqa>", s, BH, st, G));
+        if (any_boundary) RC(cst_roll_ragged(S, cap_chunks, P, Cur, pos_dev, mix, ldmix, (int)max_pos, Hkv, B * Hkv, (long)K * V, st));
+        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit, pos_dev};
+        RC(launch(k_cs_step_finish<ET>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
+    });
+    return MHLA_OK;
+}
+
+// the device-positioned step chain; Hkv < H as in cs_step_ragged_chain (the fused prologue: k once per k/v head, q per query head)
+int cs_step_dev_chain(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                      float* Cur, int32_t* pos_dev, int32_t* full_dev, const void* rope_cos, const void* rope_sin, int64_t ld_tab,
+                      int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                      mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale, int dtype,
+                      void* stream) {
+    RC(cst_check(B, H, K, V, chunk, dtype));
+    RC(cst_check_group(H, Hkv));
+    RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
+    if (cap_chunks > INT32_MAX / 64) return fail(MHLA_ENOTSUP, "cap_chunks=%d: positions beyond int32", cap_chunks);
+    RC(cst_check_dev("pos_dev", pos_dev));
+    RC(cst_check_dev("full_dev", full_dev));
+    // every bound is the capacity: whichever chunk a sequence is in, rows and columns 0 .. cap_chunks - 1 of mix may be read
+    if (!mix || ldmix < cap_chunks)
+        return fail(MHLA_EINVAL, "mix null or ldmix=%d < cap_chunks=%d (the matrix is read up to row %d)", ldmix, cap_chunks, cap_chunks - 1);
+    if (feature_map < 0 || feature_map > 2) return fail(MHLA_EINVAL, "feature_map %d: 0 identity, 1 relu, 2 elu+1", feature_map);
+    if (!rope_cos != !rope_sin) return fail(MHLA_EINVAL, "rope_cos and rope_sin must be given together");
+    const bool pro = rope_cos || feature_map;
+    if (pro && (K & 7)) return fail(MHLA_EINVAL, "K=%d: the fused prologue needs K %% 8 == 0", K);
+    if (rope_cos) {
+        if (ld_tab < K / 2 || (ld_tab & 3)) return fail(MHLA_EINVAL, "cos/sin tables: ld_tab=%lld < K/2 or not a multiple of 4", (long long)ld_tab);
+        const size_t al = dtype == MHLA_F32 ? 16 : 8;
+        if (((uintptr_t)rope_cos | (uintptr_t)rope_sin) % al) return fail(MHLA_EINVAL, "cos/sin tables must be %zu-byte aligned", al);
+        if (tab_rows < (int64_t)64 * cap_chunks || tab_rows > INT32_MAX)
+            return fail(MHLA_EINVAL, "tab_rows=%lld: the tables need a row per position, %lld (64 cap_chunks)", (long long)tab_rows, (long long)64 * cap_chunks);
+    }
+    RC(cst_check_ws(ws, ws_bytes, cst_ws_bytes(B, H, K, V)));
+    hipStream_t st = (hipStream_t)stream;
+    const int BH = B * H, G = H / Hkv, max_pos = 64 * cap_chunks - 1;
+    // always the same three launches, none of whose arguments depends on a position: step and roll address by pos_dev, the
+    // finish -- one thread per sequence reads it, none else -- advances it or sets full_dev
+    DISPATCH_T(dtype, {
+        CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, Hkv, K, V, 0, 0, pos_dev, ldmix, max_pos,
+                     rope_cos, rope_sin, (long)ld_tab, (int)tab_rows, feature_map};
+        if (G == 1) {
+            if (pro) RC(cst_step(k_cs_step<ET, true, true, true>, "k_cs_step_dev<pro>", s, BH, st));
+            else     RC(cst_step(k_cs_step<ET, true, true, false>, "k_cs_step_dev", s, BH, st));
+        } else {
+            if (pro) RC(cst_step(k_cs_step<ET, true, true, true, CST_GMAX>, "k_cs_step_dev<pro,gqa>", s, BH, st, G));
+            else     RC(cst_step(k_cs_step<ET, true, true, false, CST_GMAX>, "k_cs_step_dev<gqa>", s, BH, st, G));
+        }
+        RC(cst_roll_ragged(S, cap_chunks, P, Cur, pos_dev, mix, ldmix, max_pos, Hkv, B * Hkv, (long)K * V, st));
+        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit, pos_dev, max_pos, full_dev};
+        RC(launch(k_cs_step_finish<ET, true>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish_dev", f));
     });
     return MHLA_OK;
 }
@@ -298,29 +392,16 @@ int mhla_causal_step_ragged(mhla_view q, mhla_view k, mhla_view v, const float* 
                             float* Cur, int32_t* pos_dev, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate,
                             const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V,
                             int chunk, float scale, int dtype, void* stream) {
-    RC(cst_check(B, H, K, V, chunk, dtype));
-    RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
-    RC(cst_check_dev("pos_dev", pos_dev));
-    if (max_pos < 0 || max_pos >= INT32_MAX) return fail(MHLA_EINVAL, "max_pos=%lld is negative or beyond int32", (long long)max_pos);
-    const int64_t i = max_pos / chunk;
-    if (i >= cap_chunks) return fail(MHLA_EINVAL, "max_pos=%lld is in chunk %lld, the state holds %d", (long long)max_pos, (long long)i, cap_chunks);
-    // which sequence is on a boundary is known on the device only: with any_boundary the row after the furthest sequence's chunk
-    // must be covered (unless that chunk is the state's last), as if that sequence were the one -- a restriction (mhla_hip.h):
-    // the matrix passed with a boundary step reaches one row past the furthest sequence, or the state's capacity
-    const bool next = any_boundary && i + 1 < cap_chunks;
-    RC(cst_check_mix(mix, ldmix, i + (next ? 1 : 0)));
-    RC(cst_check_ws(ws, ws_bytes, cst_ws_bytes(B, H, K, V)));
-    hipStream_t st = (hipStream_t)stream;
-    const int BH = B * H;
-    // step and roll address by pos_dev; the finish, which does not, advances it: last in the chain
-    DISPATCH_T(dtype, {
-        CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, H, K, V, 0, 0, pos_dev, ldmix, (int)max_pos};
-        RC(cst_step(k_cs_step<ET, true>, "k_cs_step_ragged", s, BH, st));
-        if (any_boundary) RC(cst_roll_ragged(S, cap_chunks, P, Cur, pos_dev, mix, ldmix, (int)max_pos, H, BH, (long)K * V, st));
-        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit, pos_dev};
-        RC(launch(k_cs_step_finish<ET>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
-    });
-    return MHLA_OK;
+    return cs_step_ragged_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, max_pos, any_boundary, out, gate, norm_w, norm_eps, y, ws,
+                                ws_bytes, B, H, H, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_step_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                                float* Cur, int32_t* pos_dev, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate,
+                                const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K,
+                                int V, int chunk, float scale, int dtype, void* stream) {
+    return cs_step_ragged_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, max_pos, any_boundary, out, gate, norm_w, norm_eps, y, ws,
+                                ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
 int mhla_causal_step_dev(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
@@ -328,40 +409,17 @@ int mhla_causal_step_dev(mhla_view q, mhla_view k, mhla_view v, const float* mix
                          int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                          mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                          void* stream) {
-    RC(cst_check(B, H, K, V, chunk, dtype));
-    RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
-    if (cap_chunks > INT32_MAX / 64) return fail(MHLA_ENOTSUP, "cap_chunks=%d: positions beyond int32", cap_chunks);
-    RC(cst_check_dev("pos_dev", pos_dev));
-    RC(cst_check_dev("full_dev", full_dev));
-    // every bound is the capacity: whichever chunk a sequence is in, rows and columns 0 .. cap_chunks - 1 of mix may be read
-    if (!mix || ldmix < cap_chunks)
-        return fail(MHLA_EINVAL, "mix null or ldmix=%d < cap_chunks=%d (the matrix is read up to row %d)", ldmix, cap_chunks, cap_chunks - 1);
-    if (feature_map < 0 || feature_map > 2) return fail(MHLA_EINVAL, "feature_map %d: 0 identity, 1 relu, 2 elu+1", feature_map);
-    if (!rope_cos != !rope_sin) return fail(MHLA_EINVAL, "rope_cos and rope_sin must be given together");
-    const bool pro = rope_cos || feature_map;
-    if (pro && (K & 7)) return fail(MHLA_EINVAL, "K=%d: the fused prologue needs K %% 8 == 0", K);
-    if (rope_cos) {
-        if (ld_tab < K / 2 || (ld_tab & 3)) return fail(MHLA_EINVAL, "cos/sin tables: ld_tab=%lld < K/2 or not a multiple of 4", (long long)ld_tab);
-        const size_t al = dtype == MHLA_F32 ? 16 : 8;
-        if (((uintptr_t)rope_cos | (uintptr_t)rope_sin) % al) return fail(MHLA_EINVAL, "cos/sin tables must be %zu-byte aligned", al);
-        if (tab_rows < (int64_t)64 * cap_chunks || tab_rows > INT32_MAX)
-            return fail(MHLA_EINVAL, "tab_rows=%lld: the tables need a row per position, %lld (64 cap_chunks)", (long long)tab_rows, (long long)64 * cap_chunks);
-    }
-    RC(cst_check_ws(ws, ws_bytes, cst_ws_bytes(B, H, K, V)));
-    hipStream_t st = (hipStream_t)stream;
-    const int BH = B * H, max_pos = 64 * cap_chunks - 1;
-    // always the same three launches, none of whose arguments depends on a position: step and roll address by pos_dev, the
-    // finish -- one thread per sequence reads it, none else -- advances it or sets full_dev
-    DISPATCH_T(dtype, {
-        CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, H, K, V, 0, 0, pos_dev, ldmix, max_pos,
-                     rope_cos, rope_sin, (long)ld_tab, (int)tab_rows, feature_map};
-        if (pro) RC(cst_step(k_cs_step<ET, true, true, true>, "k_cs_step_dev<pro>", s, BH, st));
-        else     RC(cst_step(k_cs_step<ET, true, true, false>, "k_cs_step_dev", s, BH, st));
-        RC(cst_roll_ragged(S, cap_chunks, P, Cur, pos_dev, mix, ldmix, max_pos, H, BH, (long)K * V, st));
-        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit, pos_dev, max_pos, full_dev};
-        RC(launch(k_cs_step_finish<ET, true>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish_dev", f));
-    });
-    return MHLA_OK;
+    return cs_step_dev_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, full_dev, rope_cos, rope_sin, ld_tab, tab_rows, feature_map,
+                             out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, H, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_step_dev_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                             float* Cur, int32_t* pos_dev, int32_t* full_dev, const void* rope_cos, const void* rope_sin, int64_t ld_tab,
+                             int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                             mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
+                             int dtype, void* stream) {
+    return cs_step_dev_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, full_dev, rope_cos, rope_sin, ld_tab, tab_rows, feature_map,
+                             out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
 size_t mhla_causal_extend_ws_bytes(int B, int T, int H, int K, int V, int64_t pos, int dtype) {
@@ -396,7 +454,7 @@ int mhla_causal_extend(mhla_view q, mhla_view k, mhla_view v, const float* mix, 
         CxOutArgs o{};
         o.q = cv(q); o.k = cv(k); o.v = cv(v);
         if (!y.ptr) o.o = cmv(out);
-        o.stage = stage; o.H = H; o.K = K; o.V = V; o.T = T; o.scale = scale; o.mstep = (long)ldmix + 1;
+        o.stage = stage; o.H = H; o.K = K; o.V = V; o.T = T; o.scale = scale; o.mstep = (long)ldmix + 1; o.G = 1;
         // the first segment reads the state's P and Cur before its own product is added to Cur
         o.P = P; o.p_bh = E; o.p_seg = 0; o.Cur = Cur; o.mdiag = mix + p.i * o.mstep; o.tok0 = 0; o.tend = p.a;
         RC(launch(k_cx_out<ET>, dim3(1, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out", o));
@@ -428,7 +486,13 @@ int mhla_causal_extend(mhla_view q, mhla_view k, mhla_view v, const float* mix, 
 size_t mhla_causal_extend_ragged_ws_bytes(int B, int T, int H, int K, int V, int max_later, int dtype) {
     (void)dtype;
     if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || V <= 0 || max_later < 0) return 0;
-    return cx_rag_plan(B, T, H, K, V, max_later).total * 4;
+    return cx_rag_plan(B, T, H, H, K, V, max_later).total * 4;
+}
+
+size_t mhla_causal_extend_ragged_gqa_ws_bytes(int B, int T, int H, int Hkv, int K, int V, int max_later, int dtype) {
+    (void)dtype;
+    if (B <= 0 || T <= 0 || H <= 0 || Hkv <= 0 || H % Hkv || K <= 0 || V <= 0 || max_later < 0) return 0;
+    return cx_rag_plan(B, T, H, Hkv, K, V, max_later).total * 4;
 }
 
 int mhla_causal_extend_ragged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
@@ -437,7 +501,16 @@ int mhla_causal_extend_ragged(mhla_view q, mhla_view k, mhla_view v, const float
                               mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                               void* stream) {
     return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, ntok_dev, T, max_end, max_later, any_close, left_padded,
-                           out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, K, V, chunk, scale, dtype, stream);
+                           out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, H, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_extend_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                                  float* Cur, int32_t* pos_dev, const int32_t* ntok_dev, int T, int64_t max_end, int max_later,
+                                  int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                                  mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
+                                  int dtype, void* stream) {
+    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, ntok_dev, T, max_end, max_later, any_close, left_padded,
+                           out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
 int mhla_causal_verify_ragged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
@@ -446,7 +519,16 @@ int mhla_causal_verify_ragged(mhla_view q, mhla_view k, mhla_view v, const float
                               mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                               void* stream) {
     return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), ntok_dev, T, max_end, max_later, any_close, left_padded, out, gate, norm_w,
-                           norm_eps, y, ws, ws_bytes, B, H, K, V, chunk, scale, dtype, stream);
+                           norm_eps, y, ws, ws_bytes, B, H, H, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_verify_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                                  float* Cur, const int32_t* pos_dev, const int32_t* ntok_dev, int T, int64_t max_end, int max_later,
+                                  int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                                  mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
+                                  int dtype, void* stream) {
+    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), ntok_dev, T, max_end, max_later,
+                           any_close, left_padded, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
 size_t mhla_causal_commit_ragged_ws_bytes(int B, int dtype) {

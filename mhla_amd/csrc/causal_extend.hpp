@@ -100,6 +100,8 @@ struct CxOutArgs {
     int later;             // 0: the first segment of every sequence; 1: segment blockIdx.x of the later ones
     int* nval;             // [B] (later = 0 writes it) tokens the chain accepts for sequence b: what the finish reads
     int kr, nsplit;        // the K split of k_cs_step for a batch of one: the sums of a one-token sequence
+    // grouped-query heads: q, o and stage have H heads, k, v, P, Cur and the workspace tiles H / G -- query head h reads k/v head h / G
+    int G;                 // >= 1
 };
 
 // [64 kk][64 cols] slice of P + mii Cur (Cur null: P alone) -> LDS, zero padded; V % 4 == 0
@@ -168,7 +170,8 @@ __device__ __forceinline__ void cx_one_token(const CxOutArgs& a, float* red, con
     if (tid < CST_VT && v0 + tid < a.V) srow[tid] = tot;
 }
 
-// grid (segments, B H, ceil(V / 64)): k_cs_out on a run of <= 64 token rows of one chunk
+// grid (segments, B H, ceil(V / 64)): k_cs_out on a run of <= 64 token rows of one chunk.  It only reads the state: with a.G > 1 the G
+// query heads of a group read the one state of their k/v head (causal_step.hpp), each with the tiles and sums of the ungrouped call
 template <typename T, bool RAGGED = false>
 __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -179,6 +182,8 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
     float* Os = Ps + CS * CS_LDK;      // [64][68]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
     const int seg = blockIdx.x, bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H;
+    const int hk = h / a.G;
+    const long bhk = (long)b * (a.H / a.G) + hk;   // the state's (b, k/v head); G = 1: bh
     const int v0 = blockIdx.z * 64, vv = min(64, a.V - v0);
     long p0;
     int rv;
@@ -196,27 +201,27 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
             const int tok = s.a + seg * CS;
             p0 = s.shift + tok;
             rv = min(CS, s.n - tok);
-            Pi = a.P + ((long)bh * a.rag.max_later + seg) * E;
+            Pi = a.P + (bhk * a.rag.max_later + seg) * E;
             Ci = nullptr;
             mii = a.mdiag[(long)(s.i + 1 + seg) * a.mstep];
         } else {
             p0 = s.shift;
             rv = s.a;
-            Pi = a.P + (long)bh * E;
-            Ci = a.Cur + (long)bh * E;
+            Pi = a.P + bhk * E;
+            Ci = a.Cur + bhk * E;
             mii = a.mdiag[(long)s.i * a.mstep];
             one = s.n == 1;
         }
     } else {
         p0 = a.tok0 + (long)seg * CS;
         rv = (int)min((long)CS, a.tend - p0);
-        Pi = a.P + (long)bh * a.p_bh + (long)seg * a.p_seg;
-        Ci = a.Cur ? a.Cur + (long)bh * a.K * a.V : nullptr;
+        Pi = a.P + bhk * a.p_bh + (long)seg * a.p_seg;
+        Ci = a.Cur ? a.Cur + bhk * a.K * a.V : nullptr;
         mii = a.mdiag[(long)seg * a.mstep];
     }
     const T* qb = (const T*)a.q.ptr + b * a.q.sb + h * a.q.sh;
-    const T* kb = (const T*)a.k.ptr + b * a.k.sb + h * a.k.sh;
-    const T* vb = (const T*)a.v.ptr + b * a.v.sb + h * a.v.sh;
+    const T* kb = (const T*)a.k.ptr + b * a.k.sb + hk * a.k.sh;
+    const T* vb = (const T*)a.v.ptr + b * a.v.sb + hk * a.v.sh;
     if constexpr (RAGGED) {
         if (one) {
             cx_one_token<T>(a, smem, qb + p0 * a.q.sn, kb + p0 * a.k.sn, vb + p0 * a.v.sn, Pi, Ci, mii, v0,

@@ -28,6 +28,11 @@
 // and writes pos[b] in ONE thread per sequence and nowhere else, so the rule above holds.  With PRO the step applies the fla
 // layer's q / k prologue itself (feature map, then the NeoX rotary at row pos[b] of the cos / sin tables) where it loads q[r]
 // and k[r]: fmrot_* (common.hpp), the arithmetic k_fmap_rotary runs, rounded to the tensor dtype where that kernel stores.
+// Grouped-query heads (GMAX > 1; the *_gqa entry points): S, P and Cur depend on k and v alone, so the G = H / Hkv query heads of a
+// group share ONE state, [B][Hkv][...].  A workgroup of the grouped step belongs to a k/v head: it loads its P / Cur rows, forms
+// c = fmaf(k, v, Cur) and stores Cur once, and keeps one accumulator per query head of the group, acc[g] = fmaf(q_g, fmaf(mii, c, p),
+// acc[g]) -- the sums of the ungrouped step on repeated heads, term for term and in order (the K split is chosen from the QUERY
+// head count for that reason), at 1 / G of its state traffic.  The finish runs unchanged over the B H query heads.
 // Memory-bound (P and Cur read, Cur written: 12 K V bytes per (b, h) and token); plain fp32 FMA, no MFMA, no atomics: every
 // sum has a fixed order, so results repeat bit for bit.  The state is fp32 whatever the tensor dtype: Cur takes up to 64
 // rank-1 updates and P sums up to L chunks -- a 16-bit state would round at every token.
@@ -56,6 +61,8 @@ struct CsStepArgs {
     const void* sin;
     long ldt;
     int tab_rows, fmap;    // tab_rows >= 64 cap (the host checked); feature map: 0 identity, 1 relu, 2 elu + 1
+    // GMAX > 1 only: H counts the k/v heads (k, v, P, Cur and the grid), q and part have G H heads, head hk G + g in group hk
+    int G;                 // 1 .. GMAX
 };
 
 // pos[b] as the ragged step addresses by it.  Defence only: the caller keeps the array equal to its host mirror, and then the clamp
@@ -84,18 +91,23 @@ __device__ __forceinline__ float cst_pro1(const T* x, int r, int half, const T* 
     return stored_value<T>(lo ? fmrot_lo(x0, x1, c, s) : fmrot_hi(x0, x1, c, s));
 }
 
-// grid (ceil(V / 64), nsplit, B H)
-template <typename T, bool RAGGED = false, bool DEV = false, bool PRO = false>
+constexpr int CST_GMAX = 8;       // query heads per k/v head the grouped step serves
+
+// grid (ceil(V / 64), nsplit, B H); GMAX > 1 (grouped-query heads, a.H = Hkv): one accumulator per query head g < a.G of the group,
+// the loop over g fully unrolled and predicated by a.G alone (uniform over the launch)
+template <typename T, bool RAGGED = false, bool DEV = false, bool PRO = false, int GMAX = 1>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
     static_assert(!DEV || RAGGED, "DEV is the ragged step, bounded by the capacity");
     static_assert(!PRO || DEV, "the fused prologue goes with the device-positioned step");
-    __shared__ __attribute__((aligned(16))) float red[CST_RG][CST_VT];
+    static_assert(GMAX == 1 || RAGGED, "grouped heads: the ragged and device-positioned steps only");
+    __shared__ __attribute__((aligned(16))) float red[GMAX][CST_RG][CST_VT];
     const int tid = threadIdx.x, c4 = (tid & 15) * 4, rg = tid >> 4;
     const int bh = blockIdx.z, b = bh / a.H, h = bh - b * a.H;
+    const int G = GMAX > 1 ? a.G : 1;
     const int col = blockIdx.x * CST_VT + c4;
     const int k0 = blockIdx.y * a.kr, k1 = min(a.K, k0 + a.kr);
     bool live = col < a.V;   // (V % 4 == 0: a thread's four columns are inside or outside together)
-    const T* qb = (const T*)a.q.ptr + b * a.q.sb + h * a.q.sh;
+    const T* qb = (const T*)a.q.ptr + b * a.q.sb + (long)h * G * a.q.sh;   // (query head h G of the group)
     const T* kb = (const T*)a.k.ptr + b * a.k.sb + h * a.k.sh;
     const T* vb = (const T*)a.v.ptr + b * a.v.sb + h * a.v.sh;
     float mii;
@@ -122,26 +134,30 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
     } else {
         mii = *a.mix;
     }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[GMAX];
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (live) {
         const f32x4 vv = Io<T>::ld4(vb + col);
         const long base = (long)bh * a.K * a.V + col;
         constexpr int U = 4;   // rows in flight per thread: 2 U 16-byte loads
         for (int r0 = k0 + rg; r0 < k1; r0 += CST_RG * U) {
             f32x4 p[U], c[U];
-            float qv[U], kv[U];
+            float qv[GMAX][U], kv[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int r = r0 + u * CST_RG;
                 if (r < k1) {
                     p[u] = gld<f32x4>(a.P + base + (long)r * a.V);
                     c[u] = gld<f32x4>(a.Cur + base + (long)r * a.V);
-                    if constexpr (PRO) {
-                        qv[u] = cst_pro1(qb, r, a.K / 2, cosr, sinr, a.fmap);
-                        kv[u] = cst_pro1(kb, r, a.K / 2, cosr, sinr, a.fmap);
-                    } else {
-                        qv[u] = cst_ld1(qb + r);
-                        kv[u] = cst_ld1(kb + r);
+                    if constexpr (PRO) kv[u] = cst_pro1(kb, r, a.K / 2, cosr, sinr, a.fmap);
+                    else               kv[u] = cst_ld1(kb + r);
+#pragma unroll
+                    for (int g = 0; g < GMAX; ++g) {
+                        if (g < G) {
+                            if constexpr (PRO) qv[g][u] = cst_pro1(qb + g * a.q.sh, r, a.K / 2, cosr, sinr, a.fmap);
+                            else               qv[g][u] = cst_ld1(qb + g * a.q.sh + r);
+                        }
                     }
                 }
             }
@@ -150,24 +166,35 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
                 const int r = r0 + u * CST_RG;
                 if (r < k1) {
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        c[u][t] = fmaf(kv[u], vv[t], c[u][t]);
-                        acc[t] = fmaf(qv[u], fmaf(mii, c[u][t], p[u][t]), acc[t]);
+                    for (int t = 0; t < 4; ++t) c[u][t] = fmaf(kv[u], vv[t], c[u][t]);
+#pragma unroll
+                    for (int g = 0; g < GMAX; ++g) {
+                        if (g < G) {
+#pragma unroll
+                            for (int t = 0; t < 4; ++t) acc[g][t] = fmaf(qv[g][u], fmaf(mii, c[u][t], p[u][t]), acc[g][t]);
+                        }
                     }
                     gst<f32x4>(a.Cur + base + (long)r * a.V, c[u]);
                 }
             }
         }
     }
-    *reinterpret_cast<f32x4*>(&red[rg][c4]) = acc;
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g)
+        if (g < G) *reinterpret_cast<f32x4*>(&red[g][rg][c4]) = acc[g];
     __syncthreads();
     if (tid < CST_VT) {
         const int cc = blockIdx.x * CST_VT + tid;
         if (cc < a.V) {
-            float s = 0.f;
 #pragma unroll
-            for (int g = 0; g < CST_RG; ++g) s += red[g][tid];
-            a.part[((long)bh * a.nsplit + blockIdx.y) * a.V + cc] = s;
+            for (int g = 0; g < GMAX; ++g) {
+                if (g < G) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int j = 0; j < CST_RG; ++j) s += red[g][j][tid];
+                    a.part[(((long)bh * G + g) * a.nsplit + blockIdx.y) * a.V + cc] = s;
+                }
+            }
         }
     }
 }

@@ -39,12 +39,13 @@ class GatedMLP(nn.Module):
 
 
 class Block(nn.Module):
-    def __init__(self, dim, heads, expand_k, expand_v, layer_idx, max_chunks=32, exact_decoding=False, isolate_sequences=False):
+    def __init__(self, dim, heads, expand_k, expand_v, layer_idx, max_chunks=32, exact_decoding=False, isolate_sequences=False,
+                 num_kv_heads=None, grouped_state=False):
         super().__init__()
         self.attn_norm = RMSNorm(dim)
         self.attn = MHLA(mode="chunk", hidden_size=dim, expand_k=expand_k, expand_v=expand_v, num_heads=heads,
                          feature_map="relu", layer_idx=layer_idx, max_chunks=max_chunks, exact_decoding=exact_decoding,
-                         isolate_sequences=isolate_sequences)
+                         isolate_sequences=isolate_sequences, num_kv_heads=num_kv_heads, grouped_state=grouped_state)
         self.mlp_norm = RMSNorm(dim)
         self.mlp = GatedMLP(dim)
 
@@ -64,13 +65,16 @@ class Block(nn.Module):
 
 class GPT_MHLA(nn.Module):
     def __init__(self, vocab_size=32000, hidden_size=1024, num_layers=24, num_heads=4, expand_k=0.5, expand_v=1.0,
-                 max_seq_len=2048, exact_decoding=False, isolate_sequences=False):
+                 max_seq_len=2048, exact_decoding=False, isolate_sequences=False, num_kv_heads=None, grouped_state=False):
+        """`num_kv_heads`, `grouped_state`: passed to every layer (`MHLA`): grouped-query heads, and -- with `exact_decoding` -- decode
+        states of `num_kv_heads` heads instead of `num_heads` equal copies per group."""
         super().__init__()
         self.exact_decoding = bool(exact_decoding)
         self.isolate_sequences = bool(isolate_sequences)
         self.embeddings = nn.Embedding(vocab_size, hidden_size)
         max_chunks = max(32, (max_seq_len + 63) // 64)     # 32 = the reference layer's matrix; 128 for seq_len 8192 (config 5)
-        self.layers = nn.ModuleList([Block(hidden_size, num_heads, expand_k, expand_v, i, max_chunks, exact_decoding, isolate_sequences) for i in range(num_layers)])
+        self.layers = nn.ModuleList([Block(hidden_size, num_heads, expand_k, expand_v, i, max_chunks, exact_decoding, isolate_sequences, num_kv_heads, grouped_state)
+                                     for i in range(num_layers)])
         self.norm = RMSNorm(hidden_size)
         self.lm_head = nn.Linear(hidden_size, vocab_size, bias=False)
         for m in self.modules():

@@ -261,7 +261,8 @@ class MHLA(nn.Module):
                  use_output_gate: bool = True, gate_fn: str = "swish", elementwise_affine: Optional[bool] = True,
                  norm_eps: float = 1e-5, gate_logit_normalizer: int = 16, gate_low_rank_dim: int = 16,
                  clamp_min: Optional[float] = None, fuse_norm: bool = True, layer_idx: int = None, max_chunks: int = 32,
-                 summaries: str = "tf32", exact_decoding: bool = False, isolate_sequences: bool = False):
+                 summaries: str = "tf32", exact_decoding: bool = False, isolate_sequences: bool = False,
+                 grouped_state: bool = False):
         """`max_chunks` (not in the reference, default = its hard-coded 32): side of the mixing matrix, i.e. the longest
         sequence is 64 * max_chunks tokens -- 128 for the 8192-token configuration of BASELINE.json configs[4], which the
         reference layer itself cannot run (layers/mhla.py:196-200); the operator accepts any [n, n] matrix (naive.py:55).
@@ -307,7 +308,14 @@ class MHLA(nn.Module):
         an `attention_mask`, unpadded to a pack and re-padded on the way out): the operator over the pack, the ragged decode state
         of every sequence from one launch chain, rotary rows per sequence, and the cache counts the longest sequence; later calls
         are `[sequences, T', D]` on that state and read no mask.  `use_short_conv` there, and `cu_seqlens` on a cache that already
-        holds a state, raise NotImplementedError."""
+        holds a state, raise NotImplementedError.
+        `grouped_state` (not in the reference, default off: nothing changes; needs `exact_decoding`, ValueError otherwise): with
+        `num_kv_heads < num_heads` every exact call -- the prefill's state, steps, extensions with or without `token_counts`,
+        speculative verify / commit, device-positioned steps, the packed exact prefill -- keeps k and v un-repeated: feature map and
+        rotary run on `num_kv_heads` heads, and the cached `CausalState` has `num_kv_heads` heads, 1 / `num_kv_groups` of the memory
+        and of the per-token state traffic (the state is a function of k and v alone, so the repeated heads of a group held equal
+        copies).  The outputs are bit for bit those of `grouped_state=False`; only the operator of the prefill's output still takes
+        repeated heads."""
         super().__init__()
         self.mode = mode
         self.hidden_size = hidden_size
@@ -327,6 +335,9 @@ class MHLA(nn.Module):
         self.summaries = summaries
         self.exact_decoding = bool(exact_decoding)
         self.isolate_sequences = bool(isolate_sequences)
+        if grouped_state and not exact_decoding:
+            raise ValueError("MHLA(grouped_state=True) needs exact_decoding=True: the grouped state is the exact decode state")
+        self.grouped_state = bool(grouped_state)
         self.use_output_gate = use_output_gate
         assert mode in ["chunk", "fused_recurrent", "fused_chunk"], f"Not supported mode `{mode}`."
         assert self.key_dim % num_heads == 0, f"key dim must be divisible by num_heads of {num_heads}"
@@ -406,7 +417,9 @@ class MHLA(nn.Module):
             plan = kwargs.get("varlen_plan", None)
             if plan is None:
                 plan = causal_varlen_plan(cu_seqlens, hidden_states.device)
-        q, k, v, conv_states = self._project(hidden_states, last_state, use_cache, cu_seqlens)
+        # (grouped_state: the exact paths keep the k/v heads un-repeated; the prefill repeats them for its operator alone)
+        grouped = self.grouped_state and call.exact and self.num_kv_groups > 1
+        q, k, v, conv_states = self._project(hidden_states, last_state, use_cache, cu_seqlens, repeat=not grouped)
         rows = self._rotary_rows(call, q, q_len, cu_seqlens, attention_mask, past_key_values)
         q, k = self._featmap_rotary(q, k, rows, flat=call.ragged)
         fused = self.use_output_gate and self.fuse_norm_and_gate and (q_len > 64 or call.packed)
@@ -511,9 +524,16 @@ class MHLA(nn.Module):
         cu_seqlens = F.pad(m.sum(-1, dtype=torch.int32).cumsum(0, dtype=torch.int32), (1, 0))
         return hidden_states.reshape(batch_size * q_len, -1).index_select(0, indices).unsqueeze(0), indices, cu_seqlens
 
-    def _project(self, hidden_states, last_state=None, use_cache=False, cu_seqlens=None):
+    def _repeat_kv(self, k, v):
+        """k, v of `num_kv_heads` heads with every head repeated `num_kv_groups` times (repeat '(h g) d', :290-292)."""
+        B, T = k.shape[:2]
+        k = k.unsqueeze(3).expand(-1, -1, -1, self.num_kv_groups, -1).reshape(B, T, self.num_heads, self.head_k_dim)
+        v = v.unsqueeze(3).expand(-1, -1, -1, self.num_kv_groups, -1).reshape(B, T, self.num_heads, self.head_v_dim)
+        return k, v
+
+    def _project(self, hidden_states, last_state=None, use_cache=False, cu_seqlens=None, repeat=True):
         """q, k, v as `[B, T, H, .]` (through the short convolutions with `use_short_conv`, :258-279; grouped k / v heads
-        expanded, :290-292) and the convolutions' states (None without them)."""
+        expanded, :290-292 -- `repeat=False`: left as `[B, T, num_kv_heads, .]`) and the convolutions' states (None without them)."""
         B, T, _ = hidden_states.shape
         conv_states = None
         if self.use_short_conv:
@@ -527,10 +547,10 @@ class MHLA(nn.Module):
         else:
             q, k, v = self.q_proj(hidden_states), self.k_proj(hidden_states), self.v_proj(hidden_states)
         q = q.reshape(B, T, self.num_heads, self.head_k_dim)
-        if self.num_kv_groups > 1:                                           # (repeat '(h g) d')
-            k = k.reshape(B, T, self.num_kv_heads, 1, self.head_k_dim).expand(-1, -1, -1, self.num_kv_groups, -1)
-            v = v.reshape(B, T, self.num_kv_heads, 1, self.head_v_dim).expand(-1, -1, -1, self.num_kv_groups, -1)
-        return q, k.reshape(B, T, self.num_heads, self.head_k_dim), v.reshape(B, T, self.num_heads, self.head_v_dim), conv_states
+        k, v = k.reshape(B, T, self.num_kv_heads, self.head_k_dim), v.reshape(B, T, self.num_kv_heads, self.head_v_dim)
+        if self.num_kv_groups > 1 and repeat:
+            k, v = self._repeat_kv(k, v)
+        return q, k, v, conv_states
 
     def _rotary_rows(self, call, q, q_len, cu_seqlens, attention_mask, past_key_values) -> _RotaryRows:
         """The rotary position of every token row (see `_RotaryRows`): packed sequences restart at every sequence start
@@ -565,9 +585,9 @@ class MHLA(nn.Module):
 
     def _featmap_rotary(self, q, k, rows, flat):
         """Feature map (:297-299) and rotary (:311) of q and k at `rows`; `flat`: as one sequence of B T rows (ragged calls)."""
-        shape = q.shape
+        shape, kshape = q.shape, k.shape   # (grouped_state: k has the k/v heads)
         if flat:
-            q, k = q.reshape(1, shape[0] * shape[1], *shape[2:]), k.reshape(1, shape[0] * shape[1], *shape[2:])
+            q, k = q.reshape(1, shape[0] * shape[1], *shape[2:]), k.reshape(1, shape[0] * shape[1], *kshape[2:])
         if self.head_k_dim % 8 == 0:
             # feature map + rotary in one HIP kernel per tensor and direction
             cos, sin = self.rotary._tables(rows.table_len, q.device, q.dtype)
@@ -582,7 +602,7 @@ class MHLA(nn.Module):
                 self._warned_eager_rotary = True
             q, k = self.feature_map_q(q), self.feature_map_k(k)              # :297-299
             q, k = self.rotary(q, k, seqlen_offset=rows.seqlen_offset, max_seqlen=rows.table_len, positions=rows.positions)   # :311
-        return (q.reshape(shape), k.reshape(shape)) if flat else (q, k)
+        return (q.reshape(shape), k.reshape(kshape)) if flat else (q, k)
 
     def _fused_gate(self, hidden_states):
         """`(g [B, T, H, V], the norm module)` for an operator that applies norm x gate itself; `(None, None)` unless `fuse_norm_and_gate`."""
@@ -611,21 +631,23 @@ class MHLA(nn.Module):
         of it from one launch chain."""
         B, T = q.shape[:2]
         mix = self.mixing_matrix
+        # (grouped_state: the state from the k/v heads as they are, the operator on repeated heads)
+        ko, vo = self._repeat_kv(k, v) if k.shape[2] != self.num_heads else (k, v)
         if plan is not None:
-            o, _, fused = self._reference_operator(q, k, v, hidden_states, plan, fused, (B, T), None, True)
+            o, _, fused = self._reference_operator(q, ko, vo, hidden_states, plan, fused, (B, T), None, True)
             return o, mhla_causal_state(k, v, mix, cu_seqlens=plan), fused
         if not fused and lengths is not None:
             return (*mhla_causal_prefill(q, k, v, mix, summaries=self.summaries, lengths=lengths, left_padded=True), False)
         if not fused:
-            return mhla_causal(q, k, v, mix, summaries=self.summaries), mhla_causal_state(k, v, mix), False
+            return mhla_causal(q, ko, vo, mix, summaries=self.summaries), mhla_causal_state(k, v, mix), False
         g, gn = self._fused_gate(hidden_states)
         if lengths is None:
-            o = mhla_causal_normgate(q, k, v, mix, g, gn.weight, gn.eps, summaries=self.summaries)
+            o = mhla_causal_normgate(q, ko, vo, mix, g, gn.weight, gn.eps, summaries=self.summaries)
             return o.reshape(B, T, self.value_dim), mhla_causal_state(k, v, mix), True
         o = q.new_zeros(B, T, self.num_heads, self.head_v_dim)
         for i, j, n in _runs(lengths, B):
             if n:
-                o[i:j, T - n:] = mhla_causal_normgate(q[i:j, T - n:], k[i:j, T - n:], v[i:j, T - n:], mix, g[i:j, T - n:],
+                o[i:j, T - n:] = mhla_causal_normgate(q[i:j, T - n:], ko[i:j, T - n:], vo[i:j, T - n:], mix, g[i:j, T - n:],
                                                       gn.weight, gn.eps, summaries=self.summaries)
         return o.reshape(B, T, self.value_dim), mhla_causal_state(k, v, mix, lengths=lengths, left_padded=True), True
 
@@ -709,7 +731,7 @@ class MHLA(nn.Module):
         Nothing here depends on a position or synchronises, the cache is not updated (the state advances in place, on the device),
         and `mixing_matrix.data` is NOT reassigned: the matrix the prefill clamped is read, since generation does not change the
         weights.  The whole call may be captured in a graph."""
-        q, k, v, _ = self._project(hidden_states)
+        q, k, v, _ = self._project(hidden_states, repeat=not self.grouped_state)
         g, gn = self._fused_gate(hidden_states)
         o = mhla_causal_step_dev(q, k, v, entry["dev_mix"], entry["recurrent_state"], feature_map=self._fmap_name,
                                  rotary=(entry["dev_cos"], entry["dev_sin"]), gate=g, norm_weight=entry["dev_norm_weight"],

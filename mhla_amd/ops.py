@@ -28,6 +28,21 @@ def _native_nodes() -> bool:
 # (batch, head) pairs one launch of the library addresses (grid.y); larger batches are sliced by the operators below
 _MAX_GRID_BH = 65535
 
+# query heads one k/v head serves in the grouped decode calls (the library's CST_GMAX)
+_MAX_KV_GROUP = 8
+
+
+def _kv_group(fn: str, H: int, Hkv: int) -> int:
+    """G = H / Hkv of a decode call whose k, v have Hkv heads and q has H (query head h uses k/v head h // G, the layer's repeat
+    order); host arithmetic, raised before the library is loaded or a state is touched."""
+    if Hkv == H:
+        return 1
+    if Hkv < 1 or H % Hkv:
+        raise ValueError(f"{fn}: q has H={H} heads and k, v have Hkv={Hkv}: H must be a multiple of Hkv (grouped-query heads)")
+    if H // Hkv > _MAX_KV_GROUP:
+        raise NotImplementedError(f"{fn}: H={H} query heads on Hkv={Hkv} k/v heads: at most {_MAX_KV_GROUP} per k/v head are supported")
+    return H // Hkv
+
 # Forward workspaces up to these sizes are kept alive for the backward (block / chunk summaries); beyond the limit the backward
 # recomputes them.  The memory is held per LAYER between its forward and its backward: the causal pipeline's hi + lo chunk
 # summaries are 0.54 GB per layer at the 340M fla shape (B = 4, T = 8192) and 1.07 GB at the 1.3B-like one (B = 2) -- 13 / 26 GB
@@ -1271,7 +1286,9 @@ class CausalState:
     kernels, which advance it themselves -- a step costs no copy and no synchronisation; `seen` is kept equal to `max(lengths)`.
     Device-positioned steps (`mhla_causal_step_dev`) move `pos` alone and leave the mirror behind: the state is then `stale`, every
     call that reads the mirror refuses it, and `sync()` reads `pos` back.  `full` (int32 [B] on the state's device, zeros, created on
-    first use) is where those steps flag a sequence they found beyond the capacity."""
+    first use) is where those steps flag a sequence they found beyond the capacity.
+    Grouped-query heads: the state is a function of k and v alone, so its head count is that of k and v (Hkv), whatever the number
+    of query heads -- every decode call takes q `[B, T, H, K]` with k, v `[B, T, Hkv, .]` and a state of Hkv heads, H = G Hkv, G <= 8."""
 
     __slots__ = ("S", "P", "Cur", "seen", "chunk_size", "lengths", "pos", "stale", "_full")
 
@@ -1405,6 +1422,18 @@ def _step_ws_bytes(B, H, K, V, dt):
     return _lib.load().mhla_causal_step_ws_bytes(B, H, K, V, dt)
 
 
+def _gqa_call(lib, name, H, Hkv):
+    """(entry point, its head arguments) of a ragged decode call: `name` itself with H, or -- k, v and the state having fewer heads
+    than q -- its grouped form `name_gqa` with H, Hkv."""
+    return (getattr(lib, name), (H,)) if Hkv == H else (getattr(lib, name + "_gqa"), (H, Hkv))
+
+
+def _extend_ragged_ws_bytes(lib, B, T, H, Hkv, K, V, max_later, dt):
+    if Hkv == H:
+        return lib.mhla_causal_extend_ragged_ws_bytes(B, T, H, K, V, max_later, dt)
+    return lib.mhla_causal_extend_ragged_gqa_ws_bytes(B, T, H, Hkv, K, V, max_later, dt)
+
+
 @_device_guard
 def _causal_state_init(k, v, mix, state: CausalState):
     lib = _lib.load()
@@ -1428,18 +1457,23 @@ def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixin
     lengths, left_padded: a padded batch, as `mhla_causal_state` takes it -- the state is ragged, every sequence's rows of `o` are
     those of `mhla_causal` over that sequence alone (one call per run of adjacent sequences of equal length), padding rows zero.
     cu_seqlens: a pack (B = 1), as `mhla_causal` takes it -- `o` is the packed output `mhla_causal(..., cu_seqlens=)`, the state
-    the ragged one of `mhla_causal_state(..., cu_seqlens=)`, one sequence of the pack per batch entry; one plan serves both."""
+    the ragged one of `mhla_causal_state(..., cu_seqlens=)`, one sequence of the pack per batch entry; one plan serves both.
+    Grouped-query heads (k, v `[B, T, Hkv, .]`, H = G Hkv, G <= 8): `o` is computed on k, v repeated G times per head, as the fla
+    layer does; the state is built from the un-repeated k, v and has Hkv heads (`CausalState`)."""
     if q.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
     if int(chunk_size) != 64:
         raise ValueError(f"mhla_causal_prefill: chunk_size={chunk_size}, the decode state supports 64 only")
+    # grouped-query heads: the state from the un-repeated k, v; the operator that computes `o` takes repeated heads
+    G = _kv_group("mhla_causal_prefill", q.shape[2], k.shape[2]) if k.dim() == 4 else 1
+    ko, vo = (k, v) if G == 1 else (k.repeat_interleave(G, 2), v.repeat_interleave(G, 2))
     if cu_seqlens is not None:
         # every refusal of the state half first, so that nothing is launched for a call that is refused
         plan = _causal_state_pack_args("mhla_causal_prefill", k, v, mixing_matrix, cu_seqlens, lengths, left_padded, capacity_chunks)[0]
-        o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries, cu_seqlens=plan)
+        o = mhla_causal(q, ko, vo, mixing_matrix, chunk_size, scale, summaries=summaries, cu_seqlens=plan)
         return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks, cu_seqlens=plan)
     if lengths is None:
-        o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries)
+        o = mhla_causal(q, ko, vo, mixing_matrix, chunk_size, scale, summaries=summaries)
         return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks)
     B, T, H, _ = q.shape
     lengths = _lengths_tuple("mhla_causal_prefill", lengths, B, T)
@@ -1448,7 +1482,7 @@ def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixin
     for i, j, n in _runs(lengths, B):
         if n:
             t0 = T - n if left_padded else 0
-            o[i:j, t0:t0 + n] = mhla_causal(q[i:j, t0:t0 + n], k[i:j, t0:t0 + n], v[i:j, t0:t0 + n], mixing_matrix, chunk_size, scale,
+            o[i:j, t0:t0 + n] = mhla_causal(q[i:j, t0:t0 + n], ko[i:j, t0:t0 + n], vo[i:j, t0:t0 + n], mixing_matrix, chunk_size, scale,
                                             summaries=summaries)
     return o, state
 
@@ -1561,7 +1595,8 @@ def _step_view_ok(t: torch.Tensor) -> bool:
 def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=True):
     """What `mhla_causal_step` and `mhla_causal_extend` (`fn`: the one called, for the messages) check after their own tests of
     the state's type, the tensors' rank and T, and the tensors they launch with.  The C ABI receives raw pointers, so everything
-    is refused here, in an order callers rely on -- tensors like q, dtype, state shapes, devices, norm_weight, requires-grad, GPU,
+    is refused here, in an order callers rely on -- the head counts (k, v and the state may have Hkv heads that divide q's H:
+    `_kv_group`), tensors like q, dtype, state shapes, devices, norm_weight, requires-grad, GPU,
     matrix shape, chunk size, rows / capacity (IndexError), epilogue arguments, state contiguity -- before anything is launched
     or `state` is touched.  Returns (q, k, v, gate, mixf, wf, pos, scale, want_y): the token tensors addressable in place or as
     contiguous copies, the mixing matrix and the norm weight in fp32, the position of the first token (of the furthest sequence
@@ -1570,14 +1605,17 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
     checked -- a stale mirror is fine -- and the position returned is None."""
     B, T, H, K = q.shape
     V = v.shape[-1]
+    Hk = k.shape[2]   # grouped-query heads: k, v and the state have Hkv heads, q, gate and the rows H = G Hkv
+    _kv_group(fn, H, Hk)
     try:
-        _check_like(q, fn, k=(k, (B, T, H, K)), v=(v, (B, T, H, V)), gate=(gate, (B, T, H, V)))
+        _check_like(q, fn, k=(k, (B, T, Hk, K)), v=(v, (B, T, Hk, V)), gate=(gate, (B, T, H, V)))
     except TypeError as e:
         raise ValueError(str(e)) from None
     if q.dtype not in _DTYPES:
         raise ValueError(f"{fn}: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
-    if tuple(state.S.shape) != (B, H, state.capacity_chunks, K, V) or tuple(state.P.shape) != (B, H, K, V) or tuple(state.Cur.shape) != (B, H, K, V):
-        raise ValueError(f"{fn}: state is {state!r}, the {'token has' if T == 1 else 'tokens have'} B={B} H={H} K={K} V={V}")
+    if tuple(state.S.shape) != (B, Hk, state.capacity_chunks, K, V) or tuple(state.P.shape) != (B, Hk, K, V) or tuple(state.Cur.shape) != (B, Hk, K, V):
+        raise ValueError(f"{fn}: state is {state!r}, the {'token has' if T == 1 else 'tokens have'} B={B} H={H if Hk == H else Hk} K={K} V={V}"
+                         + ("" if Hk == H else f" (k/v heads; q has {H})"))
     dev = q.device
     for name, t in (("state.S", state.S), ("state.P", state.P), ("state.Cur", state.Cur), ("mixing_matrix", mixing_matrix), ("norm_weight", norm_weight)):
         if t is not None and t.device != dev:
@@ -1649,11 +1687,12 @@ def _causal_step_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, pos, leng
     V = v.shape[-1]
     dt = _dtype_code(q)
     ws = _ws(_step_ws_bytes(B, H, K, V, dt), q.device)
-    rc = lib.mhla_causal_step_ragged(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-                                     state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), max(lengths), int(any(n % 64 == 63 for n in lengths)),
-                                     NULL_VIEW if want_y else _view(res), _view_or_null(gate), _ptr(wf), float(norm_eps),
-                                     _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K, V, state.chunk_size,
-                                     float(scale), dt, _stream())
+    call, heads = _gqa_call(lib, "mhla_causal_step_ragged", H, k.shape[2])
+    rc = call(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+              state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), max(lengths), int(any(n % 64 == 63 for n in lengths)),
+              NULL_VIEW if want_y else _view(res), _view_or_null(gate), _ptr(wf), float(norm_eps),
+              _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, *heads, K, V, state.chunk_size,
+              float(scale), dt, _stream())
     _lib.check(rc, "mhla_causal_step_ragged")
 
 
@@ -1671,7 +1710,11 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
     On a ragged state (`state.lengths`) the token of sequence b is at position `lengths[b]`, the row returned is that of
     `mhla_causal` over that sequence's own tokens, and each sequence closes its chunk where its own position says so -- one
     launch chain for the batch, the positions advanced on the device (no copy, no synchronisation); every entry of `lengths`
-    and `seen` grow by one.  The IndexError is raised when the longest sequence would not fit."""
+    and `seen` grow by one.  The IndexError is raised when the longest sequence would not fit.
+    Grouped-query heads: k, v `[B, 1, Hkv, .]` with a state of Hkv heads and q of H = G Hkv (G <= 8; query head h uses k/v head
+    h // G): the bits of this call on k, v repeated G times and a state of H heads, with P and Cur moved once per k/v head.  A
+    uniform grouped state takes the ragged launch chain, its positions filled on the device; `step_dev`, `extend`, `verify` and
+    `commit` take the same shapes."""
     if not isinstance(state, CausalState):
         raise TypeError(f"mhla_causal_step: state must be a CausalState, got {type(state).__name__}")
     state._refuse_stale("mhla_causal_step")
@@ -1682,29 +1725,33 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
         raise ValueError(f"mhla_causal_step takes one token per call (T = 1), got T = {T}")
     prepared = _decode_prepare("mhla_causal_step", q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue)
     res = _alloc_like_tokens(B, 1, H, v.shape[-1], q)
-    if state.lengths is None:
+    if state.lengths is None and k.shape[2] == H:
         _causal_decode(*prepared, "mhla_causal_step", state, res, norm_eps)
         state.seen += 1
         return res
     q, k, v, gate, mixf, wf, _, scale, want_y = prepared
+    lengths, pos = state.lengths, state.pos
+    if lengths is None:   # grouped heads have no uniform kernels: the ragged chain, its positions filled on the device (no copy, no synchronisation)
+        lengths, pos = (state.seen,) * B, torch.full((B,), state.seen, dtype=torch.int32, device=q.device)
     nb = _MAX_GRID_BH // H
     # What the library checks per launch, for every slice before the first launch (a refusal after an earlier slice had run would
     # leave its device positions ahead of `lengths`): a slice with a sequence on a boundary needs the row after its furthest
     # sequence's chunk, unless that chunk is the state's last.
     for i in range(0, B, nb):
-        part = state.lengths[i:i + nb]
+        part = lengths[i:i + nb]
         need = max(part) // 64 + 1 + (any(n % 64 == 63 for n in part) and max(part) // 64 + 1 < state.capacity_chunks)
         if mixf.shape[1] < need:
             raise IndexError(f"mhla_causal_step: a sequence of lengths {part} closes its chunk: row {need - 1} of mixing_matrix is read, "
                              f"which has only {mixf.shape[1]} columns")
     if B <= nb:   # the usual case, one launch chain: no views to build
-        _causal_step_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, state.pos, state.lengths, res, norm_eps)
+        _causal_step_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, pos, lengths, res, norm_eps)
     for i in range(0, B if B > nb else 0, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
         sl = lambda x: None if x is None else x[i:i + nb]
         part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], 0, 64)
-        _causal_step_ragged(sl(q), sl(k), sl(v), sl(gate), mixf, wf, scale, want_y, part, state.pos[i:i + nb], state.lengths[i:i + nb],
+        _causal_step_ragged(sl(q), sl(k), sl(v), sl(gate), mixf, wf, scale, want_y, part, pos[i:i + nb], lengths[i:i + nb],
                             sl(res), norm_eps)
-    state.lengths = tuple(n + 1 for n in state.lengths)
+    if state.lengths is not None:
+        state.lengths = tuple(n + 1 for n in state.lengths)
     state.seen += 1
     return res
 
@@ -1718,12 +1765,13 @@ def _causal_step_dev(q, k, v, gate, mixf, wf, scale, want_y, state, pos, full, c
     V = v.shape[-1]
     dt = _dtype_code(q)
     ws = _ws(_step_ws_bytes(B, H, K, V, dt), q.device)
-    rc = lib.mhla_causal_step_dev(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-                                  state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), full.data_ptr(), _ptr(cos), _ptr(sin),
-                                  cos.stride(0) if cos is not None else 0, cos.shape[0] if cos is not None else 0, fmap,
-                                  NULL_VIEW if want_y else _view(res), _view_or_null(gate), _ptr(wf), float(norm_eps),
-                                  _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K, V, state.chunk_size,
-                                  float(scale), dt, _stream())
+    call, heads = _gqa_call(lib, "mhla_causal_step_dev", H, k.shape[2])
+    rc = call(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+              state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), full.data_ptr(), _ptr(cos), _ptr(sin),
+              cos.stride(0) if cos is not None else 0, cos.shape[0] if cos is not None else 0, fmap,
+              NULL_VIEW if want_y else _view(res), _view_or_null(gate), _ptr(wf), float(norm_eps),
+              _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, *heads, K, V, state.chunk_size,
+              float(scale), dt, _stream())
     _lib.check(rc, "mhla_causal_step_dev")
 
 
@@ -1870,12 +1918,13 @@ def _causal_extend_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, pos, nt
     V = v.shape[-1]
     dt = _dtype_code(q)
     max_end, max_later, any_close, _ = plan
-    ws = _ws(lib.mhla_causal_extend_ragged_ws_bytes(B, T, H, K, V, max_later, dt), q.device)
-    rc = getattr(lib, fn)(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-                          state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), ntok.data_ptr(), T, max_end, max_later,
-                          int(any_close), int(bool(left_padded)), NULL_VIEW if want_y else _view(res), _view_or_null(gate),
-                          _ptr(wf), float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K,
-                          V, state.chunk_size, float(scale), dt, _stream())
+    ws = _ws(_extend_ragged_ws_bytes(lib, B, T, H, k.shape[2], K, V, max_later, dt), q.device)
+    call, heads = _gqa_call(lib, fn, H, k.shape[2])
+    rc = call(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
+              state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), ntok.data_ptr(), T, max_end, max_later,
+              int(any_close), int(bool(left_padded)), NULL_VIEW if want_y else _view(res), _view_or_null(gate),
+              _ptr(wf), float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, *heads, K,
+              V, state.chunk_size, float(scale), dt, _stream())
     _lib.check(rc, fn)
 
 
@@ -1906,11 +1955,30 @@ def _extend_counts(fn, prepared, state, counts, left_padded, res, norm_eps):
     q, k, v, gate, mixf, wf, _, scale, want_y = prepared
     B, T, H, K = q.shape
     V = v.shape[-1]
+    Hk = k.shape[2]
     nb = min(B, _MAX_GRID_BH // H)
     slices = _ragged_slices(fn, state, counts, H, mixf)
     lib = _lib.load()
     dt = _dtype_code(q)
-    if any(lib.mhla_causal_extend_ragged_ws_bytes(j - i, T, H, K, V, plan[1], dt) > EXTEND_WS_CAP_BYTES for i, j, plan in slices):
+    over = any(_extend_ragged_ws_bytes(lib, j - i, T, H, Hk, K, V, plan[1], dt) > EXTEND_WS_CAP_BYTES for i, j, plan in slices)
+    if over and Hk != H:
+        # grouped heads have no uniform chain to fall back to: the ragged chain window by window of whole chunks of tokens, every
+        # sequence taking what it has in the window (this function again, on views; each window fits the cap)
+        step_t = _extend_step_t(nb, H, K, V)
+        if T <= step_t:
+            raise ValueError(f"{fn}: {nb} sequences x {T} tokens need a workspace beyond EXTEND_WS_CAP_BYTES={EXTEND_WS_CAP_BYTES} with "
+                             "grouped heads: extend fewer sequences per call")
+        for t0 in range(0, T, step_t):
+            t1 = min(T, t0 + step_t)
+            lo = [T - n if left_padded else 0 for n in counts]
+            part = tuple(max(0, min(t1, a + n) - max(t0, a)) for a, n in zip(lo, counts))
+            sl = lambda x: None if x is None else x[:, t0:t1]
+            if any(part):
+                _extend_counts(fn, (sl(q), sl(k), sl(v), sl(gate), mixf, wf, None, scale, want_y), state, part, left_padded, sl(res), norm_eps)
+            else:
+                res[:, t0:t1].zero_()
+        return res
+    if over:
         res.zero_()
         step_t = _extend_step_t(1, H, K, V)
         for b, (p, n) in enumerate(zip(state.lengths, counts)):
@@ -1960,7 +2028,9 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     sequences, when one would exceed the mixing matrix or the capacity.  All counts 0: nothing is launched, zeros are returned.
     Batches beyond one launch's (b, h) range are sliced; a ragged call whose workspace would exceed `EXTEND_WS_CAP_BYTES` is not cut
     per sequence but falls back to the uniform chain sequence by sequence (which cuts at chunk boundaries): the same rows and
-    state within fp32 rounding, more launches."""
+    state within fp32 rounding, more launches.
+    Grouped-query heads (k, v and the state on Hkv heads, as `mhla_causal_step`): always the ragged chain, on a uniform state too;
+    beyond `EXTEND_WS_CAP_BYTES` it runs window by window of whole chunks of tokens instead of sequence by sequence."""
     fn = "mhla_causal_extend"
     if not isinstance(state, CausalState):
         raise TypeError(f"mhla_causal_extend: state must be a CausalState, got {type(state).__name__}")
@@ -1982,8 +2052,14 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     prepared = _decode_prepare("mhla_causal_extend", q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue)
     pos = prepared[6]
     res = _alloc_like_tokens(B, T, H, V, q)
-    if state.lengths is not None and any(n != state.lengths[0] for n in state.lengths):
+    if state.lengths is not None and (k.shape[2] != H or any(n != state.lengths[0] for n in state.lengths)):
         return _extend_counts(fn, prepared, state, (T,) * B, False, res, norm_eps)
+    if k.shape[2] != H:   # grouped heads have no uniform kernels: the ragged chain on the same storage, its positions filled on the device
+        rag = CausalState(state.S, state.P, state.Cur, 0, 64, lengths=(pos,) * B,
+                          pos=torch.full((B,), pos, dtype=torch.int32, device=q.device))
+        _extend_counts(fn, prepared, rag, (T,) * B, False, res, norm_eps)
+        state.seen = pos + T
+        return res
     nb = min(B, _MAX_GRID_BH // H)
     step_t = _extend_step_t(nb, H, K, V)
     # (batches beyond one launch's (b, h) range: see mhla_blockmix)
@@ -2045,7 +2121,7 @@ def mhla_causal_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     slices = _ragged_slices(fn, state, counts, H, mixf)
     lib = _lib.load()
     dt = _dtype_code(q)
-    need = max(lib.mhla_causal_extend_ragged_ws_bytes(j - i, T, H, K, V, plan[1], dt) for i, j, plan in slices)
+    need = max(_extend_ragged_ws_bytes(lib, j - i, T, H, k.shape[2], K, V, plan[1], dt) for i, j, plan in slices)
     if need > EXTEND_WS_CAP_BYTES:
         raise ValueError(f"{fn}: a draft of T={T} tokens for {B} sequences needs a workspace of {need} bytes, more than "
                          f"EXTEND_WS_CAP_BYTES={EXTEND_WS_CAP_BYTES}: verify fewer tokens or sequences per call")

@@ -64,6 +64,11 @@ boundary).  Alternating in one run, `--reps` times, `--steps` calls each: wall t
 the library's kernels and its launches per call (the per-launch event hook).  The state is put back before every call -- host mirror and
 a 4 B-byte device copy of the positions, given to every variant -- so that every call is the same work.
 
+`--gqa`: grouped-query heads (`mhla_causal_step` with k, v and the state on Hkv heads, q on H) beside the repeated-head step on a
+state of H heads, at B = 8, H = 16, Hkv = 4 and 2, K = 128, V = 256, 32 chunks seen: the ordinary step and the one that closes a chunk,
+alternating in one run, `--reps` times, `--steps` calls each -- wall and device time per call (median, min, max), the kernels' device
+times, the bytes of state a step moves and the state's size.
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -232,6 +237,59 @@ def ragged_config(B, H, K, V, steps, reps):
            "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()},
            "step_bytes": {"uniform": nbytes, "ragged": nbytes + 4 * B},
            "ragged_step_device_within_uniform_spread": min(dev["uniform_step"]) <= statistics.median(dev["ragged_step"]) <= max(dev["uniform_step"])}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def gqa_config(B, H, Hkv, K, V, steps, reps, chunks_seen=32):
+    """Grouped-query heads: the ragged step on a state of Hkv heads (k, v un-repeated) beside the repeated-head step on a state of H
+    heads (what a layer without `grouped_state` runs), every sequence `chunks_seen` chunks in; the ordinary step and the one that
+    closes a chunk, alternating in one run."""
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    G = H // Hkv
+    q = torch.randn(B, 1, H, K, generator=g).to(torch.bfloat16).to(DEV)
+    k = torch.randn(B, 1, Hkv, K, generator=g).to(torch.bfloat16).to(DEV)
+    v = torch.randn(B, 1, Hkv, V, generator=g).to(torch.bfloat16).to(DEV)
+    kr, vr = k.repeat_interleave(G, 2), v.repeat_interleave(G, 2)
+    len_step, len_roll = (chunks_seen * 64 + 36,) * B, (chunks_seen * 64 + 63,) * B
+    pos_step, pos_roll = (torch.tensor(x, dtype=torch.int32, device=DEV) for x in (len_step, len_roll))
+
+    def make(heads):
+        st = mhla_amd.CausalState.empty(B, heads, K, V, L, DEV)
+        st.S[:, :, :chunks_seen + 1].normal_(0, 0.1)
+        st.P.normal_(0, 0.1)
+        return mhla_amd.CausalState(st.S, st.P, st.Cur, lengths=len_step)
+
+    grouped, repeated = make(Hkv), make(H)
+
+    def run(state, kk, vv, lengths, pos):
+        def fn():
+            state.lengths, state.seen = lengths, max(lengths)
+            state.pos.copy_(pos)
+            mhla_amd.mhla_causal_step(q, kk, vv, mix, state)
+        return fn
+
+    fns = {"repeated_step": run(repeated, kr, vr, len_step, pos_step), "grouped_step": run(grouped, k, v, len_step, pos_step),
+           "repeated_roll": run(repeated, kr, vr, len_roll, pos_roll), "grouped_roll": run(grouped, k, v, len_roll, pos_roll)}
+    wall, dev, kern = {n: [] for n in fns}, {n: [] for n in fns}, {}
+    with torch.no_grad():
+        for _ in range(reps):
+            for n, fn in fns.items():
+                wall[n].append(batch_us(fn, steps))
+            for n, fn in fns.items():
+                kern[n] = kernel_times(fn, iters=20)
+                dev[n].append(sum(kern[n].values()))
+            grouped.Cur.zero_()
+            repeated.Cur.zero_()
+    state_bytes = lambda heads: 3 * B * heads * K * V * 4
+    rec = {"gqa": {"B": B, "H": H, "Hkv": Hkv, "G": G, "K": K, "V": V, "chunks_seen": chunks_seen}, "steps_per_batch": steps, "reps": reps,
+           "wall_us": {n: spread(x) for n, x in wall.items()}, "device_us": {n: spread(x) for n, x in dev.items()},
+           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()},
+           "step_state_traffic_bytes": {"repeated": state_bytes(H), "grouped": state_bytes(Hkv)},
+           "state_MB_at_chunks_seen": {"repeated": round((chunks_seen + 2) * B * H * K * V * 4 / 2 ** 20, 1),
+                                       "grouped": round((chunks_seen + 2) * B * Hkv * K * V * 4 / 2 ** 20, 1)},
+           "state_MB_allocated": {"repeated": round(repeated.nbytes / 2 ** 20, 1), "grouped": round(grouped.nbytes / 2 ** 20, 1)}}
     print(json.dumps(rec), flush=True)
     return rec
 
@@ -631,8 +689,12 @@ if __name__ == "__main__":
     ap.add_argument("--mixed", action="store_true")
     ap.add_argument("--packed-prefill", action="store_true")
     ap.add_argument("--speculative", action="store_true")
+    ap.add_argument("--gqa", action="store_true")
     a = ap.parse_args()
-    if a.speculative:
+    if a.gqa:
+        for Hkv in (4, 2):
+            gqa_config(8, 16, Hkv, 128, 256, max(200, a.steps), a.reps)
+    elif a.speculative:
         for B in (1, 8):
             speculative_config(B, 4, 128, 256, max(100, a.steps), a.reps)
     elif a.packed_prefill:
