@@ -9,7 +9,7 @@ from __future__ import annotations
 import functools
 import os
 import warnings
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -126,11 +126,12 @@ def _check_block_index(block_index: Optional[torch.Tensor], N: int, ref: torch.T
 
 def _view(t: torch.Tensor) -> View:
     """[B, N, H, D] tensor -> mhla_view (element strides; D must be contiguous)."""
-    if t.dim() != 4:
+    s = t.stride()   # (read once: four or five views per call add up on the host-bound decode step)
+    if len(s) != 4:
         raise ValueError(f"expected a [B, N, H, D] tensor, got shape {tuple(t.shape)}")
-    if t.stride(3) != 1:
+    if s[3] != 1:
         raise ValueError("last dim must be contiguous")
-    return View(t.data_ptr(), t.stride(0), t.stride(1), t.stride(2))
+    return View(t.data_ptr(), s[0], s[1], s[2])
 
 
 def _strided_ok(t: torch.Tensor) -> bool:
@@ -966,7 +967,7 @@ def _causal_bwd(q, k, v, mixf, dout, fwd_ws, chunk_size, scale, flags, plan=None
     V = v.shape[-1]
     dq = _alloc_like_tokens(B, T, H, K, q)
     dk = _alloc_like_tokens(B, T, H, K, q)
-    dv = _alloc_like_tokens(B, T, H, V, q)
+    dv = q.new_empty((B, T, H, V))
     # the library writes every entry of the leading [n, n] block (zeros above the diagonal)
     n_chunks = (T + chunk_size - 1) // chunk_size if plan is None else plan.n_chunks
     dmix = (torch.empty if tuple(mixf.shape) == (n_chunks, n_chunks) else torch.zeros)(mixf.shape, dtype=torch.float32, device=q.device)
@@ -995,7 +996,7 @@ class _Causal(torch.autograd.Function):
             raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)] with L >= {n} on {q.device}")
         q, k, v = _prep(q), _prep(k), _prep(v)
         mixf = _mix2d(mix, n_chunks)
-        out = _alloc_like_tokens(B, T, H, V, q)
+        out = q.new_empty((B, T, H, V))
         ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, _dtype_code(q), flags, n_chunks)[0], q.device)
         _causal_call("fwd", plan, _view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(out), ws.data_ptr(), ws.numel() * 4,
                      B, T, H, K, V, chunk_size, float(scale), _dtype_code(q), flags, _stream())
@@ -1186,8 +1187,8 @@ class _CausalNormGate(torch.autograd.Function):
         mixf = _mix2d(mix, n_chunks)
         wf = _f32(weight)
         need_grad = any(ctx.needs_input_grad[:6])
-        out = _alloc_like_tokens(B, T, H, V, q) if need_grad else None
-        y = _alloc_like_tokens(B, T, H, V, q)
+        out = q.new_empty((B, T, H, V)) if need_grad else None
+        y = q.new_empty((B, T, H, V))
         ws = _ws(_cs_plan(B, T, H, K, V, chunk_size, _dtype_code(q), flags, n_chunks)[0], q.device)
         _causal_call("normgate_fwd", plan, _view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view_or_null(out),
                      _view_or_null(gate), _ptr(wf), float(norm_eps), _view(y), ws.data_ptr(), ws.numel() * 4, B, T, H, K, V, chunk_size,
@@ -1298,7 +1299,7 @@ class CausalState:
         self.lengths = self.pos = self._full = None
         self.stale = False
         if lengths is not None:
-            lengths = _lengths_tuple("CausalState", lengths, S.shape[0], None)
+            lengths = _int_tuple("CausalState", "lengths", lengths, S.shape[0], None)
             if pos is None:
                 pos = torch.tensor(lengths, dtype=torch.int32, device=S.device)
             elif pos.dtype != torch.int32 or tuple(pos.shape) != (len(lengths),):
@@ -1396,14 +1397,17 @@ class CausalState:
         return f"CausalState(B={B}, H={H}, K={K}, V={V}, capacity_chunks={cap}, {seen}, device={self.S.device})"
 
 
-def _lengths_tuple(fn, lengths, B, T):
-    """`lengths` (a list or a tensor; reading a device tensor synchronises) as the host mirror of a ragged state: B ints in 0 .. T."""
-    lengths = tuple(int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths))
-    if len(lengths) != B:
-        raise ValueError(f"{fn}: lengths has {len(lengths)} entries, expected B={B}")
-    if any(n < 0 or (T is not None and n > T) for n in lengths):
-        raise ValueError(f"{fn}: lengths={lengths} must be in 0 .." + (f" T={T}" if T is not None else ""))
-    return lengths
+def _int_tuple(fn, name, xs, B, hi):
+    """`xs` (a list or a tensor; reading a device tensor synchronises) as B ints in 0 .. hi: the `lengths` of a ragged state (its
+    host mirror; `hi` = T, or None for no upper bound), the `counts` of a call (T), the `accept` of a commit (`hi`: the draft's
+    counts, a tuple -- one bound per sequence)."""
+    xs = tuple(int(n) for n in (xs.tolist() if isinstance(xs, torch.Tensor) else xs))
+    per_seq = isinstance(hi, tuple)
+    if len(xs) != B:
+        raise ValueError(f"{fn}: {name} has {len(xs)} entries, " + (f"the draft B={B}" if per_seq else f"expected B={B}"))
+    if any(n < 0 or n > h for n, h in zip(xs, hi)) if per_seq else B and (min(xs) < 0 or (hi is not None and max(xs) > hi)):
+        raise ValueError(f"{fn}: {name}={xs} must be in 0 .." + ("" if hi is None else f" counts={hi} of the draft" if per_seq else f" T={hi}"))
+    return xs
 
 
 def _runs(lengths, nb):
@@ -1415,6 +1419,39 @@ def _runs(lengths, nb):
             j += 1
         yield i, j, lengths[i]
         i = j
+
+
+def _state_slice(state: CausalState, i, j) -> CausalState:
+    """`state` for its sequences [i, j): views of S, P, Cur (what a launch reads of a state besides its sizes), or -- all of them,
+    the usual case -- the state itself, with no views to build."""
+    if i == 0 and j == state.S.shape[0]:
+        return state
+    return CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], 0, 64)
+
+
+def _batch_slices(state: CausalState, nb, prepared=None, *along):
+    """One launch addresses `nb` sequences (`_MAX_GRID_BH // H`; batches beyond that range: see mhla_blockmix).  Yields, for every
+    batch slice [i, j) of at most `nb`: (`_state_slice`, `prepared.part(i, j)`, x[i:j] for every x of `along`).  B <= nb, the usual
+    case, is one launch chain on the objects themselves."""
+    B = state.S.shape[0]
+    if B <= nb:
+        yield (state, prepared) + along
+        return
+    for i in range(0, B, nb):
+        j = min(B, i + nb)
+        yield (_state_slice(state, i, j), prepared.part(i, j) if prepared is not None else None) + tuple(x[i:j] for x in along)
+
+
+def _run_slices(state: CausalState, lengths, nb):
+    """`_batch_slices` cut further where adjacent lengths differ: (i, j, the length, `_state_slice`) of every run of `_runs`."""
+    for i, j, n in _runs(lengths, nb):
+        yield i, j, n, _state_slice(state, i, j)
+
+
+def _state_head(mixf, state: CausalState):
+    """The arguments every decode entry point of the library takes after its token views: the mixing matrix with its leading
+    dimension, then S with the capacity, P, Cur."""
+    return mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.S.shape[2], state.P.data_ptr(), state.Cur.data_ptr()
 
 
 @functools.lru_cache(maxsize=64)
@@ -1440,11 +1477,9 @@ def _causal_state_init(k, v, mix, state: CausalState):
     B, T, H, K = k.shape
     k, v = _prep(k), _prep(v)
     mixf = _mix2d(mix)
-    rc = lib.mhla_causal_state_init(_view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-                                    state.P.data_ptr(), state.Cur.data_ptr(), B, T, H, K, v.shape[-1], state.chunk_size,
+    rc = lib.mhla_causal_state_init(_view(k), _view(v), *_state_head(mixf, state), B, T, H, K, v.shape[-1], state.chunk_size,
                                     _dtype_code(k), _stream())
     _lib.check(rc, "mhla_causal_state_init")
-    state.seen = T
 
 
 def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, chunk_size: int = 64,
@@ -1476,7 +1511,7 @@ def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixin
         o = mhla_causal(q, ko, vo, mixing_matrix, chunk_size, scale, summaries=summaries)
         return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks)
     B, T, H, _ = q.shape
-    lengths = _lengths_tuple("mhla_causal_prefill", lengths, B, T)
+    lengths = _int_tuple("mhla_causal_prefill", "lengths", lengths, B, T)
     state = mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks, lengths=lengths, left_padded=left_padded)
     o = torch.zeros((B, T, H, v.shape[-1]), dtype=q.dtype, device=q.device)
     for i, j, n in _runs(lengths, B):
@@ -1522,8 +1557,7 @@ def _causal_state_init_pack(k, v, mix, state: CausalState, plan: CausalVarlenPla
     _, T, H, K = k.shape
     k, v = _prep(k), _prep(v)
     mixf = _mix2d(mix)
-    rc = lib.mhla_causal_varlen_state_init(_view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-                                           state.P.data_ptr(), state.Cur.data_ptr(), len(state.lengths), state.pos.data_ptr(),
+    rc = lib.mhla_causal_varlen_state_init(_view(k), _view(v), *_state_head(mixf, state), len(state.lengths), state.pos.data_ptr(),
                                            max(state.lengths), T, H, K, v.shape[-1], state.chunk_size, plan.n_chunks,
                                            plan.table.data_ptr(), plan.dst.data_ptr(), _dtype_code(k), _stream())
     _lib.check(rc, "mhla_causal_varlen_state_init")
@@ -1559,7 +1593,7 @@ def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Ten
     V = v.shape[-1]
     _check_like(k, "mhla_causal_state", v=(v, (B, T, H, V)))
     if lengths is not None:
-        lengths = _lengths_tuple("mhla_causal_state", lengths, B, T)
+        lengths = _int_tuple("mhla_causal_state", "lengths", lengths, B, T)
         T = max(lengths)
     L = mixing_matrix.shape[0]
     cap = L if capacity_chunks is None else int(capacity_chunks)
@@ -1573,39 +1607,76 @@ def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Ten
     nb = _MAX_GRID_BH // H
     with torch.no_grad():
         state = CausalState.empty(B, H, K, V, cap, k.device, 64)
+        # a uniform batch is one run of T tokens per slice; T = 0 launches nothing
+        t_pad = k.shape[1]
+        for i, j, n, part in _run_slices(state, lengths if lengths is not None else (T,) * B, nb):
+            if n:
+                t0 = t_pad - n if left_padded and lengths is not None else 0
+                _causal_state_init(k[i:j, t0:t0 + n].detach(), v[i:j, t0:t0 + n].detach(), mixing_matrix, part)
         if lengths is not None:
-            for i, j, n in _runs(lengths, nb):
-                if n:
-                    t0 = k.shape[1] - n if left_padded else 0
-                    part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], 0, 64)
-                    _causal_state_init(k[i:j, t0:t0 + n].detach(), v[i:j, t0:t0 + n].detach(), mixing_matrix, part)
             return CausalState(state.S, state.P, state.Cur, 0, 64, lengths=lengths)
-        for i in range(0, B if T else 0, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
-            part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], 0, 64)
-            _causal_state_init(k[i:i + nb].detach(), v[i:i + nb].detach(), mixing_matrix, part)
         state.seen = T
     return state
 
 
 def _step_view_ok(t: torch.Tensor) -> bool:
     # what the step kernels address in place: 4-element pieces (8 bytes for 16-bit types, 16 for fp32)
-    return t.stride(3) == 1 and all(s % 4 == 0 for s in t.stride()[:3]) and t.data_ptr() % (4 * t.element_size()) == 0
+    sb, sn, sh, sd = t.stride()
+    return sd == 1 and (sb | sn | sh) % 4 == 0 and t.data_ptr() % (4 * t.element_size()) == 0
 
 
-def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=True):
-    """What `mhla_causal_step` and `mhla_causal_extend` (`fn`: the one called, for the messages) check after their own tests of
-    the state's type, the tensors' rank and T, and the tensors they launch with.  The C ABI receives raw pointers, so everything
-    is refused here, in an order callers rely on -- the head counts (k, v and the state may have Hkv heads that divide q's H:
-    `_kv_group`), tensors like q, dtype, state shapes, devices, norm_weight, requires-grad, GPU,
+class _Prepared(NamedTuple):
+    """What `_decode_prepare` returns and every launcher below takes as its first nine arguments (`*prepared`): the token tensors
+    addressable in place or as contiguous copies, the mixing matrix and the norm weight in fp32, the position of the first token
+    (None when the call is not host-positioned), the scale, and whether the rows go through the norm x gate epilogue."""
+    q: torch.Tensor
+    k: torch.Tensor
+    v: torch.Tensor
+    gate: Optional[torch.Tensor]
+    mixf: torch.Tensor
+    wf: Optional[torch.Tensor]
+    pos: Optional[int]
+    scale: float
+    want_y: bool
+
+    def part(self, i, j, t0=None, t1=None, pos=None) -> "_Prepared":
+        """The same call for sequences [i, j) and tokens [t0, t1) (None: no bound) only; `pos`: the position of its first token,
+        where that is another."""
+        q, k, v, gate = (x if x is None else x[i:j, t0:t1] for x in self[:4])
+        return self._replace(q=q, k=k, v=v, gate=gate, pos=self.pos if pos is None else pos)
+
+
+def _decode_entry(fn, state, q, k, v, one_token, refuse_stale):
+    """The first refusals of every decode call, in this order: the state's type, a stale host mirror (not for
+    `mhla_causal_step_dev`, which never reads it), the tensors' rank, the token count."""
+    if not isinstance(state, CausalState):
+        raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
+    if refuse_stale and state.stale:
+        state._refuse_stale(fn)
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        t = "1" if one_token else "T"
+        raise ValueError(f"q, k: [B, {t}, H, K], v: [B, {t}, H, V]")
+    T = q.shape[1]
+    if one_token and T != 1:
+        raise ValueError(f"{fn} takes one token per call (T = 1), got T = {T}")
+    if T < 1:
+        raise ValueError(f"{fn} takes at least one token per call, got T = {T}")
+
+
+def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=True) -> _Prepared:
+    """What `mhla_causal_step` and `mhla_causal_extend` (`fn`: the one called, for the messages) check after `_decode_entry`'s
+    tests of the state's type, the tensors' rank and T, and the tensors they launch with.  The C ABI receives raw pointers, so
+    everything is refused here, in an order callers rely on -- the head counts (k, v and the state may have Hkv heads that divide
+    q's H: `_kv_group`), tensors like q, dtype, state shapes, devices, norm_weight, requires-grad, GPU,
     matrix shape, chunk size, rows / capacity (IndexError), epilogue arguments, state contiguity -- before anything is launched
-    or `state` is touched.  Returns (q, k, v, gate, mixf, wf, pos, scale, want_y): the token tensors addressable in place or as
-    contiguous copies, the mixing matrix and the norm weight in fp32, the position of the first token (of the furthest sequence
+    or `state` is touched.  Returns a `_Prepared`; its position is that of the first token (of the furthest sequence
     of a ragged state, whose `seen` is `max(lengths)`: rows and capacity are checked against it).  `positioned=False`
     (`mhla_causal_step_dev`, which made its own check of the matrix against the capacity): the host position is neither read nor
     checked -- a stale mirror is fine -- and the position returned is None."""
     B, T, H, K = q.shape
     V = v.shape[-1]
     Hk = k.shape[2]   # grouped-query heads: k, v and the state have Hkv heads, q, gate and the rows H = G Hkv
+    cap = state.capacity_chunks
     _kv_group(fn, H, Hk)
     try:
         _check_like(q, fn, k=(k, (B, T, Hk, K)), v=(v, (B, T, Hk, V)), gate=(gate, (B, T, H, V)))
@@ -1613,7 +1684,7 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
         raise ValueError(str(e)) from None
     if q.dtype not in _DTYPES:
         raise ValueError(f"{fn}: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
-    if tuple(state.S.shape) != (B, Hk, state.capacity_chunks, K, V) or tuple(state.P.shape) != (B, Hk, K, V) or tuple(state.Cur.shape) != (B, Hk, K, V):
+    if tuple(state.S.shape) != (B, Hk, cap, K, V) or tuple(state.P.shape) != (B, Hk, K, V) or tuple(state.Cur.shape) != (B, Hk, K, V):
         raise ValueError(f"{fn}: state is {state!r}, the {'token has' if T == 1 else 'tokens have'} B={B} H={H if Hk == H else Hk} K={K} V={V}"
                          + ("" if Hk == H else f" (k/v heads; q has {H})"))
     dev = q.device
@@ -1626,7 +1697,7 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
         raise RuntimeError(f"{fn} is inference only: call it under torch.no_grad() (an input requires grad)")
     _require_gpu(q, k, v, mixing_matrix)
     L = mixing_matrix.shape[0]
-    if mixing_matrix.dim() < 2 or mixing_matrix.shape[1] < min(L, state.capacity_chunks):
+    if mixing_matrix.dim() < 2 or mixing_matrix.shape[1] < min(L, cap):
         raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
     if int(state.chunk_size) != 64:
         raise ValueError(f"{fn}: chunk_size={state.chunk_size}, the decode state supports 64 only")
@@ -1636,8 +1707,8 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
         n = (pos + T + 63) // 64
         if n > L:
             raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but mixing_matrix has only {L} rows")
-        if n > state.capacity_chunks:
-            raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but the state holds only {state.capacity_chunks}")
+        if n > cap:
+            raise IndexError(f"sequence of {pos + T} tokens needs {n} chunks but the state holds only {cap}")
     if scale is None:
         scale = K ** -0.5
     want_y = bool(epilogue) if epilogue is not None else (gate is not None or norm_weight is not None)
@@ -1654,46 +1725,48 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
     if gate is not None and not _step_view_ok(gate):
         gate = gate.contiguous()
     wf = norm_weight.detach().reshape(V).to(torch.float32).contiguous() if norm_weight is not None else None
-    return q, k, v, gate, _mix2d(mixing_matrix), wf, pos, scale, want_y
+    # (built without the generated `__new__`: one Python call less on a path that is bound by the host)
+    return tuple.__new__(_Prepared, (q, k, v, gate, _mix2d(mixing_matrix), wf, pos, scale, want_y))
 
 
 @_device_guard
-def _causal_decode(q, k, v, gate, mixf, wf, pos, scale, want_y, fn, state, res, norm_eps):
-    """One launch chain of the library's `fn` ("mhla_causal_step": one token; "mhla_causal_extend": T) on what `_decode_prepare`
-    returned (the first nine arguments): the tokens at positions pos .. of `state`, the rows (after the epilogue with `want_y`)
-    into `res`."""
-    lib = _lib.load()
-    B, T, H, K = q.shape
-    V = v.shape[-1]
-    dt = _dtype_code(q)
-    if fn == "mhla_causal_step":
-        call, ntok, ws_bytes = lib.mhla_causal_step, (), _step_ws_bytes(B, H, K, V, dt)
-    else:
-        call, ntok, ws_bytes = lib.mhla_causal_extend, (T,), lib.mhla_causal_extend_ws_bytes(B, T, H, K, V, pos, dt)
-    ws = _ws(ws_bytes, q.device)
-    rc = call(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-              state.P.data_ptr(), state.Cur.data_ptr(), pos, *ntok, NULL_VIEW if want_y else _view(res), _view_or_null(gate),
-              _ptr(wf), float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, H, K, V,
-              state.chunk_size, float(scale), dt, _stream())
-    _lib.check(rc, fn)
-
-
-@_device_guard
-def _causal_step_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, pos, lengths, res, norm_eps):
-    """One launch chain of `mhla_causal_step_ragged` on what `_decode_prepare` returned, for the sequences `state` (a batch slice)
-    holds: `pos` their device positions, which the chain advances, `lengths` the host mirror of the same numbers."""
+def _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, name, twin, state, middle, ws_bytes, res, norm_eps):
+    """The one library call of the decode entry points that compute rows: `name` on what `_decode_prepare` returned (the first
+    eight arguments; the guard finds its tensor at once), for the sequences `state` -- the batch or a slice of it -- holds.  All
+    of them take the token views and `_state_head`, then arguments of their own (`middle`), then one tail: the rows into `res` (through the norm x gate epilogue with `want_y`), a
+    workspace of `ws_bytes`, the sizes, scale, dtype and stream.  `twin`: the entry point has a grouped-query form, which
+    `_gqa_call` picks when k, v and the state have fewer heads than q."""
     lib = _lib.load()
     B, _, H, K = q.shape
-    V = v.shape[-1]
-    dt = _dtype_code(q)
-    ws = _ws(_step_ws_bytes(B, H, K, V, dt), q.device)
-    call, heads = _gqa_call(lib, "mhla_causal_step_ragged", H, k.shape[2])
-    rc = call(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-              state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), max(lengths), int(any(n % 64 == 63 for n in lengths)),
-              NULL_VIEW if want_y else _view(res), _view_or_null(gate), _ptr(wf), float(norm_eps),
-              _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, *heads, K, V, state.chunk_size,
-              float(scale), dt, _stream())
-    _lib.check(rc, "mhla_causal_step_ragged")
+    call, heads = _gqa_call(lib, name, H, k.shape[2]) if twin else (getattr(lib, name), (H,))
+    ws = _ws(ws_bytes, q.device)
+    # (the two optional arguments spelt out, not through `_view_or_null` / `_ptr`: two Python calls on a host-bound path)
+    rc = call(_view(q), _view(k), _view(v), *_state_head(mixf, state), *middle, NULL_VIEW if want_y else _view(res),
+              _view(gate) if gate is not None else NULL_VIEW, wf.data_ptr() if wf is not None else None, float(norm_eps),
+              _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, *heads, K, v.shape[-1], state.chunk_size,
+              float(scale), _DTYPES[q.dtype], _stream())
+    _lib.check(rc, name)
+
+
+def _causal_decode(q, k, v, gate, mixf, wf, pos, scale, want_y, state, res, norm_eps, extend=False):
+    """One launch chain of `mhla_causal_step` (one token) or, with `extend`, of `mhla_causal_extend` (T tokens) on what
+    `_decode_prepare` returned (the first nine arguments): the tokens at positions pos .. of the uniform `state`, the rows into `res`."""
+    B, T, H, K = q.shape
+    V, dt = v.shape[-1], _DTYPES[q.dtype]
+    if extend:
+        name, middle, ws_bytes = "mhla_causal_extend", (pos, T), _lib.load().mhla_causal_extend_ws_bytes(B, T, H, K, V, pos, dt)
+    else:
+        name, middle, ws_bytes = "mhla_causal_step", (pos,), _step_ws_bytes(B, H, K, V, dt)
+    _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, name, False, state, middle, ws_bytes, res, norm_eps)
+
+
+def _causal_step_ragged(q, k, v, gate, mixf, wf, _, scale, want_y, state, pos, lengths, res, norm_eps):
+    """One launch chain of `mhla_causal_step_ragged` on what `_decode_prepare` returned, for the sequences `state` (a batch slice)
+    holds: `pos` their device positions, which the chain advances, `lengths` the host mirror of the same numbers."""
+    B, _, H, K = q.shape
+    _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, "mhla_causal_step_ragged", True, state,
+                   (pos.data_ptr(), max(lengths), int(any(n % 64 == 63 for n in lengths))),
+                   _step_ws_bytes(B, H, K, v.shape[-1], _DTYPES[q.dtype]), res, norm_eps)
 
 
 def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
@@ -1715,64 +1788,43 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
     h // G): the bits of this call on k, v repeated G times and a state of H heads, with P and Cur moved once per k/v head.  A
     uniform grouped state takes the ragged launch chain, its positions filled on the device; `step_dev`, `extend`, `verify` and
     `commit` take the same shapes."""
-    if not isinstance(state, CausalState):
-        raise TypeError(f"mhla_causal_step: state must be a CausalState, got {type(state).__name__}")
-    state._refuse_stale("mhla_causal_step")
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError("q, k: [B, 1, H, K], v: [B, 1, H, V]")
-    B, T, H, _ = q.shape
-    if T != 1:
-        raise ValueError(f"mhla_causal_step takes one token per call (T = 1), got T = {T}")
+    _decode_entry("mhla_causal_step", state, q, k, v, True, True)
     prepared = _decode_prepare("mhla_causal_step", q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue)
-    res = _alloc_like_tokens(B, 1, H, v.shape[-1], q)
+    B, _, H, _ = q.shape
+    res = q.new_empty((B, 1, H, v.shape[-1]))
     if state.lengths is None and k.shape[2] == H:
-        _causal_decode(*prepared, "mhla_causal_step", state, res, norm_eps)
+        _causal_decode(*prepared, state, res, norm_eps)
         state.seen += 1
         return res
-    q, k, v, gate, mixf, wf, _, scale, want_y = prepared
     lengths, pos = state.lengths, state.pos
     if lengths is None:   # grouped heads have no uniform kernels: the ragged chain, its positions filled on the device (no copy, no synchronisation)
         lengths, pos = (state.seen,) * B, torch.full((B,), state.seen, dtype=torch.int32, device=q.device)
     nb = _MAX_GRID_BH // H
     # What the library checks per launch, for every slice before the first launch (a refusal after an earlier slice had run would
     # leave its device positions ahead of `lengths`): a slice with a sequence on a boundary needs the row after its furthest
-    # sequence's chunk, unless that chunk is the state's last.
+    # sequence's chunk, unless that chunk is the state's last.  (Not `_ragged_slices` with counts of one, which asks for less.)
+    cols = prepared.mixf.shape[1]
     for i in range(0, B, nb):
         part = lengths[i:i + nb]
         need = max(part) // 64 + 1 + (any(n % 64 == 63 for n in part) and max(part) // 64 + 1 < state.capacity_chunks)
-        if mixf.shape[1] < need:
+        if cols < need:
             raise IndexError(f"mhla_causal_step: a sequence of lengths {part} closes its chunk: row {need - 1} of mixing_matrix is read, "
-                             f"which has only {mixf.shape[1]} columns")
-    if B <= nb:   # the usual case, one launch chain: no views to build
-        _causal_step_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, pos, lengths, res, norm_eps)
-    for i in range(0, B if B > nb else 0, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
-        sl = lambda x: None if x is None else x[i:i + nb]
-        part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], 0, 64)
-        _causal_step_ragged(sl(q), sl(k), sl(v), sl(gate), mixf, wf, scale, want_y, part, pos[i:i + nb], lengths[i:i + nb],
-                            sl(res), norm_eps)
+                             f"which has only {cols} columns")
+    for part, p, pos_, lengths_, out in _batch_slices(state, nb, prepared, pos, lengths, res):
+        _causal_step_ragged(*p, part, pos_, lengths_, out, norm_eps)
     if state.lengths is not None:
         state.lengths = tuple(n + 1 for n in state.lengths)
     state.seen += 1
     return res
 
 
-@_device_guard
-def _causal_step_dev(q, k, v, gate, mixf, wf, scale, want_y, state, pos, full, cos, sin, fmap, res, norm_eps):
+def _causal_step_dev(q, k, v, gate, mixf, wf, _, scale, want_y, state, pos, full, rotary, fmap, res, norm_eps):
     """One launch chain of `mhla_causal_step_dev` on what `_decode_prepare` returned, for the sequences `state` (a batch slice)
-    holds.  Nothing here reads a position or synchronises: legal under stream capture."""
-    lib = _lib.load()
+    holds; `rotary`: the tables as the library takes them, (cos, sin, row stride, rows), nulls and zeros without.  Nothing here reads
+    a position or synchronises: legal under stream capture."""
     B, _, H, K = q.shape
-    V = v.shape[-1]
-    dt = _dtype_code(q)
-    ws = _ws(_step_ws_bytes(B, H, K, V, dt), q.device)
-    call, heads = _gqa_call(lib, "mhla_causal_step_dev", H, k.shape[2])
-    rc = call(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-              state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), full.data_ptr(), _ptr(cos), _ptr(sin),
-              cos.stride(0) if cos is not None else 0, cos.shape[0] if cos is not None else 0, fmap,
-              NULL_VIEW if want_y else _view(res), _view_or_null(gate), _ptr(wf), float(norm_eps),
-              _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, *heads, K, V, state.chunk_size,
-              float(scale), dt, _stream())
-    _lib.check(rc, "mhla_causal_step_dev")
+    _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, "mhla_causal_step_dev", True, state,
+                   (pos.data_ptr(), full.data_ptr(), *rotary, fmap), _step_ws_bytes(B, H, K, v.shape[-1], _DTYPES[q.dtype]), res, norm_eps)
 
 
 def mhla_causal_step_dev(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
@@ -1794,13 +1846,8 @@ def mhla_causal_step_dev(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixi
     rotated by row `pos[b]` of the tables, with the arithmetic and the rounding of `featmap_rotary` (K % 8 == 0).
     scale, gate, norm_weight, norm_eps, epilogue, strided views, inference only: as `mhla_causal_step`."""
     fn = "mhla_causal_step_dev"
-    if not isinstance(state, CausalState):
-        raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError("q, k: [B, 1, H, K], v: [B, 1, H, V]")
-    B, T, H, K = q.shape
-    if T != 1:
-        raise ValueError(f"{fn} takes one token per call (T = 1), got T = {T}")
+    _decode_entry(fn, state, q, k, v, True, False)   # (a stale mirror is what this call leaves: not refused)
+    B, _, H, K = q.shape
     if state.lengths is None:
         raise ValueError(f"{fn}: the state is uniform ({state!r}); the positions must live on the device: pass state.to_ragged()")
     cap = state.capacity_chunks
@@ -1822,26 +1869,21 @@ def mhla_causal_step_dev(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixi
         raise ValueError(f"{fn}: K={K}: the fused prologue (feature_map / rotary) needs K % 8 == 0")
     if feature_map not in _FMAPS:
         raise ValueError(f"{fn}: feature_map {feature_map!r}: one of {sorted(k for k in _FMAPS if k)} or None")
-    q, k, v, gate, mixf, wf, _, scale, want_y = _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue,
-                                                                positioned=False)
-    if cos is not None and (cos.stride(1) != 1 or sin.stride(1) != 1 or cos.stride(0) != sin.stride(0) or cos.stride(0) % 4
-                            or (cos.data_ptr() | sin.data_ptr()) % (4 * cos.element_size())):
-        cos, sin = cos.contiguous(), sin.contiguous()
+    prepared = _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=False)
+    rot = (None, None, 0, 0)
+    if cos is not None:
+        if (cos.stride(1) != 1 or sin.stride(1) != 1 or cos.stride(0) != sin.stride(0) or cos.stride(0) % 4
+                or (cos.data_ptr() | sin.data_ptr()) % (4 * cos.element_size())):
+            cos, sin = cos.contiguous(), sin.contiguous()
+        rot = (cos.data_ptr(), sin.data_ptr(), cos.stride(0), cos.shape[0])
     if state._full is None and torch.cuda.is_current_stream_capturing():
         raise RuntimeError(f"{fn}: state.full does not exist yet and a tensor created while capturing would belong to the graph "
                            "(cleared by every replay): run one eager step first, or touch state.full before the capture")
     full = state.full
-    res = _alloc_like_tokens(B, 1, H, v.shape[-1], q)
-    nb = _MAX_GRID_BH // H
+    res = q.new_empty((B, 1, H, v.shape[-1]))
     state.stale = True
-    for i in range(0, B, nb):   # (batches beyond one launch's (b, h) range: see mhla_blockmix)
-        if B <= nb:
-            _causal_step_dev(q, k, v, gate, mixf, wf, scale, want_y, state, state.pos, full, cos, sin, _FMAPS[feature_map], res, norm_eps)
-            break
-        sl = lambda x: None if x is None else x[i:i + nb]
-        part = CausalState(state.S[i:i + nb], state.P[i:i + nb], state.Cur[i:i + nb], 0, 64)
-        _causal_step_dev(sl(q), sl(k), sl(v), sl(gate), mixf, wf, scale, want_y, part, state.pos[i:i + nb], full[i:i + nb], cos, sin,
-                         _FMAPS[feature_map], sl(res), norm_eps)
+    for part, p, pos, full_, out in _batch_slices(state, _MAX_GRID_BH // H, prepared, state.pos, full, res):
+        _causal_step_dev(*p, part, pos, full_, rot, _FMAPS[feature_map], out, norm_eps)
     return res
 
 
@@ -1850,21 +1892,11 @@ def mhla_causal_step_dev(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixi
 EXTEND_WS_CAP_BYTES = 256 << 20
 
 
-def _counts_tuple(fn, counts, B, T):
-    """`counts` (a list or a tensor; reading a device tensor synchronises) as B ints in 0 .. T."""
-    counts = tuple(int(n) for n in (counts.tolist() if isinstance(counts, torch.Tensor) else counts))
-    if len(counts) != B:
-        raise ValueError(f"{fn}: counts has {len(counts)} entries, expected B={B}")
-    if any(n < 0 or n > T for n in counts):
-        raise ValueError(f"{fn}: counts={counts} must be in 0 .. T={T}")
-    return counts
-
-
 def _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, scale, gate, norm_weight, epilogue):
     """What a call with per-sequence `counts` (`mhla_causal_extend(counts=)`, `mhla_causal_verify`) checks, in the order callers rely
     on, before anything is launched or `state` is touched; returns (counts as a tuple, what `_decode_prepare` returns)."""
     B, T = q.shape[:2]
-    counts = _counts_tuple(fn, counts, B, T)
+    counts = _int_tuple(fn, "counts", counts, B, T)
     if state.lengths is None:
         raise ValueError(f"{fn}: counts needs a ragged state and this one is uniform ({state!r}); the positions must live on the "
                          "device: pass state.to_ragged()")
@@ -1907,38 +1939,34 @@ def _ragged_slices(fn, state, counts, H, mixf):
     return slices
 
 
-@_device_guard
-def _causal_extend_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, pos, ntok, plan, left_padded, res, norm_eps,
+def _causal_extend_ragged(q, k, v, gate, mixf, wf, _, scale, want_y, state, pos, ntok, plan, left_padded, res, norm_eps,
                           fn="mhla_causal_extend_ragged"):
     """One launch chain of `mhla_causal_extend_ragged` on what `_decode_prepare` returned, for the sequences `state` (a batch slice)
     holds: `pos` their device positions, which the chain advances, `ntok` their token counts on the device, `plan` the host
     values of `_ragged_plan`.  fn="mhla_causal_verify_ragged": the same arguments and rows, nothing committed."""
-    lib = _lib.load()
     B, T, H, K = q.shape
-    V = v.shape[-1]
-    dt = _dtype_code(q)
     max_end, max_later, any_close, _ = plan
-    ws = _ws(_extend_ragged_ws_bytes(lib, B, T, H, k.shape[2], K, V, max_later, dt), q.device)
-    call, heads = _gqa_call(lib, fn, H, k.shape[2])
-    rc = call(_view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-              state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), ntok.data_ptr(), T, max_end, max_later,
-              int(any_close), int(bool(left_padded)), NULL_VIEW if want_y else _view(res), _view_or_null(gate),
-              _ptr(wf), float(norm_eps), _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, *heads, K,
-              V, state.chunk_size, float(scale), dt, _stream())
-    _lib.check(rc, fn)
+    ws_bytes = _extend_ragged_ws_bytes(_lib.load(), B, T, H, k.shape[2], K, v.shape[-1], max_later, _DTYPES[q.dtype])
+    _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, fn, True, state,
+                   (pos.data_ptr(), ntok.data_ptr(), T, max_end, max_later, int(any_close), int(bool(left_padded))), ws_bytes, res, norm_eps)
 
 
-def _extend_run(prepared, state, res, norm_eps, i, j, p, t_lo, t_hi, step_t):
-    """Tokens [t_lo, t_hi) of the padded tensors as the next tokens of sequences i .. j - 1, all at position p: the uniform launch
-    chain, cut into consecutive calls of at most `step_t` tokens at chunk boundaries."""
-    q, k, v, gate, mixf, wf, _, scale, want_y = prepared
-    part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], p, 64)
+def _ragged_chains(fn, prepared, state, slices, counts, left_padded, res, norm_eps):
+    """`_causal_extend_ragged` (`fn`: the entry point, extend or verify) once per batch slice of `_ragged_slices`."""
+    ntok = torch.tensor(counts, dtype=torch.int32).to(res.device)   # the one small copy of the call
+    # (`slices[0][1]`, the first slice's end, is the width `_ragged_slices` cut at)
+    for (_, _, plan), (part, p, pos, ntok_, out) in zip(slices, _batch_slices(state, slices[0][1], prepared, state.pos, ntok, res)):
+        _causal_extend_ragged(*p, part, pos, ntok_, plan, left_padded, out, norm_eps, fn)
+
+
+def _extend_run(prepared, part, res, norm_eps, i, j, p, t_lo, t_hi, step_t):
+    """Tokens [t_lo, t_hi) of the padded tensors as the next tokens of sequences i .. j - 1 (whose state `part` is), all at position
+    p: the uniform launch chain, cut into consecutive calls of at most `step_t` tokens at chunk boundaries."""
     t0 = t_lo
     while t0 < t_hi:
         # the first piece fills the open chunk, so that every later one starts on a boundary
         t1 = min(t_hi, t0 + step_t - (p + t0 - t_lo) % 64)
-        sl = lambda x: None if x is None else x[i:j, t0:t1]
-        _causal_decode(sl(q), sl(k), sl(v), sl(gate), mixf, wf, p + t0 - t_lo, scale, want_y, "mhla_causal_extend", part, sl(res), norm_eps)
+        _causal_decode(*prepared.part(i, j, t0, t1, p + t0 - t_lo), part, res[i:j, t0:t1], norm_eps, True)
         t0 = t1
 
 
@@ -1952,18 +1980,17 @@ def _extend_counts(fn, prepared, state, counts, left_padded, res, norm_eps):
     """Sequence b of a ragged state takes `counts[b]` of the T padded tokens: one ragged launch chain per batch slice.  A slice whose
     workspace would exceed `EXTEND_WS_CAP_BYTES` is not cut per sequence: the whole call then runs the uniform chain sequence by
     sequence (which cuts at chunk boundaries), and writes the padding rows itself."""
-    q, k, v, gate, mixf, wf, _, scale, want_y = prepared
-    B, T, H, K = q.shape
-    V = v.shape[-1]
-    Hk = k.shape[2]
-    nb = min(B, _MAX_GRID_BH // H)
-    slices = _ragged_slices(fn, state, counts, H, mixf)
+    B, T, H, K = prepared.q.shape
+    V = prepared.v.shape[-1]
+    Hk = prepared.k.shape[2]
+    slices = _ragged_slices(fn, state, counts, H, prepared.mixf)
     lib = _lib.load()
-    dt = _dtype_code(q)
+    dt = _DTYPES[prepared.q.dtype]
     over = any(_extend_ragged_ws_bytes(lib, j - i, T, H, Hk, K, V, plan[1], dt) > EXTEND_WS_CAP_BYTES for i, j, plan in slices)
     if over and Hk != H:
         # grouped heads have no uniform chain to fall back to: the ragged chain window by window of whole chunks of tokens, every
         # sequence taking what it has in the window (this function again, on views; each window fits the cap)
+        nb = min(B, _MAX_GRID_BH // H)
         step_t = _extend_step_t(nb, H, K, V)
         if T <= step_t:
             raise ValueError(f"{fn}: {nb} sequences x {T} tokens need a workspace beyond EXTEND_WS_CAP_BYTES={EXTEND_WS_CAP_BYTES} with "
@@ -1972,30 +1999,22 @@ def _extend_counts(fn, prepared, state, counts, left_padded, res, norm_eps):
             t1 = min(T, t0 + step_t)
             lo = [T - n if left_padded else 0 for n in counts]
             part = tuple(max(0, min(t1, a + n) - max(t0, a)) for a, n in zip(lo, counts))
-            sl = lambda x: None if x is None else x[:, t0:t1]
             if any(part):
-                _extend_counts(fn, (sl(q), sl(k), sl(v), sl(gate), mixf, wf, None, scale, want_y), state, part, left_padded, sl(res), norm_eps)
+                _extend_counts(fn, prepared.part(None, None, t0, t1), state, part, left_padded, res[:, t0:t1], norm_eps)
             else:
                 res[:, t0:t1].zero_()
         return res
     if over:
         res.zero_()
         step_t = _extend_step_t(1, H, K, V)
-        for b, (p, n) in enumerate(zip(state.lengths, counts)):
+        for b, _, p, part in _run_slices(state, state.lengths, 1):   # (sequence by sequence)
+            n = counts[b]
             if n:
                 t_lo = T - n if left_padded else 0
-                _extend_run(prepared, state, res, norm_eps, b, b + 1, p, t_lo, t_lo + n, step_t)
+                _extend_run(prepared, part, res, norm_eps, b, b + 1, p, t_lo, t_lo + n, step_t)
         state.pos += torch.tensor(counts, dtype=torch.int32).to(state.pos.device, non_blocking=False)
     else:
-        ntok = torch.tensor(counts, dtype=torch.int32).to(q.device)   # the one small copy of the call
-        for i, j, plan in slices:
-            if B <= nb:   # the usual case, one launch chain: no views to build
-                _causal_extend_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, state.pos, ntok, plan, left_padded, res, norm_eps)
-                break
-            sl = lambda x: None if x is None else x[i:j]
-            part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], 0, 64)
-            _causal_extend_ragged(sl(q), sl(k), sl(v), sl(gate), mixf, wf, scale, want_y, part, state.pos[i:j], ntok[i:j], plan, left_padded,
-                                  sl(res), norm_eps)
+        _ragged_chains("mhla_causal_extend_ragged", prepared, state, slices, counts, left_padded, res, norm_eps)
     state.lengths = tuple(p + n for p, n in zip(state.lengths, counts))
     state.seen = max(state.lengths)
     return res
@@ -2032,26 +2051,20 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     Grouped-query heads (k, v and the state on Hkv heads, as `mhla_causal_step`): always the ragged chain, on a uniform state too;
     beyond `EXTEND_WS_CAP_BYTES` it runs window by window of whole chunks of tokens instead of sequence by sequence."""
     fn = "mhla_causal_extend"
-    if not isinstance(state, CausalState):
-        raise TypeError(f"mhla_causal_extend: state must be a CausalState, got {type(state).__name__}")
-    state._refuse_stale("mhla_causal_extend")
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
+    _decode_entry(fn, state, q, k, v, False, True)
     B, T, H, K = q.shape
     V = v.shape[-1]
-    if T < 1:
-        raise ValueError(f"mhla_causal_extend takes at least one token per call, got T = {T}")
     if counts is not None:
         counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, scale, gate, norm_weight, epilogue)
         if not any(counts):
             return torch.zeros((B, T, H, V), dtype=q.dtype, device=q.device)
-        return _extend_counts(fn, prepared, state, counts, left_padded, _alloc_like_tokens(B, T, H, V, q), norm_eps)
+        return _extend_counts(fn, prepared, state, counts, left_padded, q.new_empty((B, T, H, V)), norm_eps)
     if T == 1:
         return mhla_causal_step(q, k, v, mixing_matrix, state, scale=scale, gate=gate, norm_weight=norm_weight, norm_eps=norm_eps,
                                 epilogue=epilogue)
-    prepared = _decode_prepare("mhla_causal_extend", q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue)
-    pos = prepared[6]
-    res = _alloc_like_tokens(B, T, H, V, q)
+    prepared = _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue)
+    pos = prepared.pos
+    res = q.new_empty((B, T, H, V))
     if state.lengths is not None and (k.shape[2] != H or any(n != state.lengths[0] for n in state.lengths)):
         return _extend_counts(fn, prepared, state, (T,) * B, False, res, norm_eps)
     if k.shape[2] != H:   # grouped heads have no uniform kernels: the ragged chain on the same storage, its positions filled on the device
@@ -2062,10 +2075,9 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
         return res
     nb = min(B, _MAX_GRID_BH // H)
     step_t = _extend_step_t(nb, H, K, V)
-    # (batches beyond one launch's (b, h) range: see mhla_blockmix)
-    runs = ((i, min(B, i + nb), pos) for i in range(0, B, nb)) if state.lengths is None else _runs(state.lengths, nb)
-    for i, j, p in runs:
-        _extend_run(prepared, state, res, norm_eps, i, j, p, 0, T, step_t)
+    # (a uniform state: runs of the one length, `nb` sequences each)
+    for i, j, p, part in _run_slices(state, state.lengths if state.lengths is not None else (pos,) * B, nb):
+        _extend_run(prepared, part, res, norm_eps, i, j, p, 0, T, step_t)
     if state.lengths is not None:
         state.pos += T
         state.lengths = tuple(n + T for n in state.lengths)
@@ -2103,39 +2115,22 @@ def mhla_causal_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     `draft` (a `CausalDraft`) is what `mhla_causal_commit` takes to advance the state by an accepted prefix.  It holds references to
     k and v (or to the contiguous copies the call made), not copies: the caller must not overwrite k, v before the commit."""
     fn = "mhla_causal_verify"
-    if not isinstance(state, CausalState):
-        raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
-    state._refuse_stale(fn)
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
+    _decode_entry(fn, state, q, k, v, False, True)
     B, T, H, K = q.shape
     V = v.shape[-1]
-    if T < 1:
-        raise ValueError(f"{fn} takes at least one token per call, got T = {T}")
     counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, (T,) * B if counts is None else counts, scale, gate,
                                        norm_weight, epilogue)
-    q, k, v, gate, mixf, wf, _, scale, want_y = prepared
-    draft = CausalDraft(k, v, counts, left_padded, state.lengths)
+    draft = CausalDraft(prepared.k, prepared.v, counts, left_padded, state.lengths)
     if not any(counts):
         return torch.zeros((B, T, H, V), dtype=q.dtype, device=q.device), draft
-    slices = _ragged_slices(fn, state, counts, H, mixf)
+    slices = _ragged_slices(fn, state, counts, H, prepared.mixf)
     lib = _lib.load()
-    dt = _dtype_code(q)
-    need = max(_extend_ragged_ws_bytes(lib, j - i, T, H, k.shape[2], K, V, plan[1], dt) for i, j, plan in slices)
+    need = max(_extend_ragged_ws_bytes(lib, j - i, T, H, k.shape[2], K, V, plan[1], _DTYPES[q.dtype]) for i, j, plan in slices)
     if need > EXTEND_WS_CAP_BYTES:
         raise ValueError(f"{fn}: a draft of T={T} tokens for {B} sequences needs a workspace of {need} bytes, more than "
                          f"EXTEND_WS_CAP_BYTES={EXTEND_WS_CAP_BYTES}: verify fewer tokens or sequences per call")
-    res = _alloc_like_tokens(B, T, H, V, q)
-    ntok = torch.tensor(counts, dtype=torch.int32).to(q.device)   # the one small copy of the call
-    for i, j, plan in slices:
-        if len(slices) == 1:   # the usual case, one launch chain: no views to build
-            _causal_extend_ragged(q, k, v, gate, mixf, wf, scale, want_y, state, state.pos, ntok, plan, left_padded, res, norm_eps,
-                                  "mhla_causal_verify_ragged")
-            break
-        sl = lambda x: None if x is None else x[i:j]
-        part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], 0, 64)
-        _causal_extend_ragged(sl(q), sl(k), sl(v), sl(gate), mixf, wf, scale, want_y, part, state.pos[i:j], ntok[i:j], plan, left_padded,
-                              sl(res), norm_eps, "mhla_causal_verify_ragged")
+    res = q.new_empty((B, T, H, V))
+    _ragged_chains("mhla_causal_verify_ragged", prepared, state, slices, counts, left_padded, res, norm_eps)
     return res, draft
 
 
@@ -2150,9 +2145,8 @@ def _causal_commit_ragged(k, v, mixf, state, pos, ntok, acc, plan, left_padded):
     dt = _dtype_code(k)
     max_end, max_later, any_close, _ = plan
     ws = _ws(lib.mhla_causal_commit_ragged_ws_bytes(B, dt), k.device)
-    rc = lib.mhla_causal_commit_ragged(_view(k), _view(v), mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.capacity_chunks,
-                                       state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(), ntok.data_ptr(), acc.data_ptr(), T, max_end,
-                                       max_later, int(any_close), int(bool(left_padded)), ws.data_ptr(), ws.numel() * 4, B, H, K, V,
+    rc = lib.mhla_causal_commit_ragged(_view(k), _view(v), *_state_head(mixf, state), pos.data_ptr(), ntok.data_ptr(), acc.data_ptr(), T,
+                                       max_end, max_later, int(any_close), int(bool(left_padded)), ws.data_ptr(), ws.numel() * 4, B, H, K, V,
                                        state.chunk_size, dt, _stream())
     _lib.check(rc, "mhla_causal_commit_ragged")
 
@@ -2174,11 +2168,7 @@ def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: C
     if state.lengths is None:
         raise ValueError(f"{fn}: the state is uniform ({state!r}); a draft is verified on, and committed to, a ragged state")
     B = len(draft.counts)
-    accept = tuple(int(n) for n in (accept.tolist() if isinstance(accept, torch.Tensor) else accept))
-    if len(accept) != B:
-        raise ValueError(f"{fn}: accept has {len(accept)} entries, the draft B={B}")
-    if any(a < 0 or a > n for a, n in zip(accept, draft.counts)):
-        raise ValueError(f"{fn}: accept={accept} must be in 0 .. counts={draft.counts} of the draft")
+    accept = _int_tuple(fn, "accept", accept, B, draft.counts)
     if tuple(state.lengths) != draft.lengths:
         raise ValueError(f"{fn}: the state moved since the verify: lengths {state.lengths}, the draft was verified at {draft.lengths}")
     if not any(accept):
@@ -2199,14 +2189,9 @@ def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: C
     dev = k.device
     both = torch.tensor((draft.counts, accept), dtype=torch.int32).to(dev)   # the one small copy of the call
     ntok, acc = both[0], both[1]
-    for i, j, plan in slices:
-        if not plan[0]:
-            continue
-        if len(slices) == 1:
-            _causal_commit_ragged(k, v, mixf, state, state.pos, ntok, acc, plan, draft.left_padded)
-            break
-        part = CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], 0, 64)
-        _causal_commit_ragged(k[i:j], v[i:j], mixf, part, state.pos[i:j], ntok[i:j], acc[i:j], plan, draft.left_padded)
+    for (_, _, plan), (part, _, k_, v_, pos, ntok_, acc_) in zip(slices, _batch_slices(state, slices[0][1], None, k, v, state.pos, ntok, acc)):
+        if plan[0]:   # (a slice of which nothing was accepted is left alone)
+            _causal_commit_ragged(k_, v_, mixf, part, pos, ntok_, acc_, plan, draft.left_padded)
     state.lengths = tuple(p + a for p, a in zip(state.lengths, accept))
     state.seen = max(state.lengths)
     return state
