@@ -243,6 +243,13 @@ int bm_state_and_mix(const BmPlan& p, const BmCall& c) {
 template <typename ET, int DT, bool S16, typename TO = ET, bool EPI = false>
 int sp_out(const BmPlan& p, const BmCall& c, const OutArgs& o, const char* name) {
     const dim3 g(c.M, c.B * c.H), blk(sp::SP_OUT_T);
+    // (bf16 tensors with rotary tables, served on fp32-word summaries only: the instantiation that keeps the lo part of the rotated q)
+    if constexpr (!EPI && !S16 && std::is_same<ET, bf16_t>::value) {
+        if (c.rcos) {
+            if (p.fmt != SF_F32) return not_built<ET, DT>(name, p.fmt);
+            return launch(sp::k_sp_out<ET, DT, TO, SF_F32, sp::OutVar{.rope = true}>, g, blk, sp::sp_out_smem<DT, SF_F32>(), c.st, name, o);
+        }
+    }
     // (16-bit tensors on h16 summaries, D <= 64, blocks of at most 64 tokens: the instantiation of one tile per wave)
     if constexpr (!EPI && bm_fmt_built<ET, DT, S16, SF_H16>() && DT <= 4) {
         if (p.fmt == SF_H16 && bm_one_tile(c.S))

@@ -401,7 +401,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (V.rope ? 2 : 3)) void k_sp_sta
                   RT = (DT + NWV - 1) / NWV, TILE = 32 * LD;
     static_assert(IT >= 1 && RPP * IT == 32, "a 32-row chunk must be whole staging passes");
     static_assert(RPP * DW * 4 <= 4 * 32 * LD * 2, "column-sum partials must fit in the tiles");
-    constexpr bool LO = !std::is_same<T, bf16_t>::value || PRO;   // the token operands carry a lo part
+    constexpr bool LO = !std::is_same<T, bf16_t>::value || PRO || (ROPE && sf_has_lo(FMT));   // the token operands carry a lo part (a rotated bf16 value is an fp32 one)
     constexpr bool LOY = !std::is_same<T, bf16_t>::value || (MODE == 1 && sf_has_lo(FMT));   // ... and so does y = dO / n, unless the reduced-precision form was asked for
     constexpr int GLD = mat_ld<DT>(), GT = Geo<DT>::KST * 32 * GLD;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -1730,7 +1730,9 @@ constexpr int SP_OUT_T = 512;   // 8 waves share the staged G_i: twice the loads
 // OutArgs::nbh = B H; needs at least 8 tiles per block (a round then spans at most two blocks, the next round at most one more).
 // ONE: the launch has S <= 64 -- a wave has its one tile `wave` at the most: no loop, no second row set, no fetch of a next tile (it was
 // clamped onto the block's last row and dropped) and no map look-ahead
-struct OutVar { bool epi = false, pro = false, flat = false, one = false; };   // pro: the q prologue on load (OutArgs::pro_*)
+// ROPE (bf16 tensors): the launch has rotary tables -- the rotated q is an fp32 value and keeps its lo part, like fp32 / fp16 tensors and the
+// prologue's values do (without it the variant of calls without tables, where a bf16 q is its own hi part, is unchanged)
+struct OutVar { bool epi = false, pro = false, flat = false, one = false, rope = false; };   // pro: the q prologue on load (OutArgs::pro_*)
 template <typename T, int DT, typename TO, int FMT, OutVar V = OutVar{}>
 #ifndef SP_OUT_EPI_WAVES
 #define SP_OUT_EPI_WAVES 2   // the fused-epilogue variant takes 142 VGPRs: one workgroup per CU without spills (157 us at C4) beats two with 28 spilled registers (163 us)
@@ -1738,8 +1740,9 @@ template <typename T, int DT, typename TO, int FMT, OutVar V = OutVar{}>
 __global__ __launch_bounds__(SP_OUT_T, V.epi ? SP_OUT_EPI_WAVES : 2) void k_sp_out(const OutArgs a) {
     constexpr bool EPI = V.epi, PRO = V.pro, FLAT = V.flat, ONE = V.one;
     constexpr int LD = mat_ld<DT>(), KST = Geo<DT>::KST, KP = KST * 32, TILE = KP * LD;
-    constexpr bool LO = !std::is_same<T, bf16_t>::value || PRO;
+    constexpr bool LO = !std::is_same<T, bf16_t>::value || PRO || V.rope;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    static_assert(!V.rope || (std::is_same<T, bf16_t>::value && sf_has_lo(FMT) && !PRO && !FLAT && !ONE), "the rotary flag marks the bf16 variant that keeps the lo part of the rotated q");
     static_assert(!FLAT || (FMT == SF_P24 && sizeof(T) == 2), "the flat tile list serves 16-bit tensors with 24-bit summaries");
     static_assert(!ONE || (!FLAT && SP_OUT_T / 64 >= 4), "one tile per wave: blocks of at most 64 tokens, one block per workgroup");
     u16* Gh = reinterpret_cast<u16*>(smem_raw);   // [d1][d2], rows >= D and columns >= D zero   (FLAT: two (hi, lo) pairs, block parity)

@@ -522,9 +522,12 @@ def mhla_blockmix_rope(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, W: tor
     tensors are materialised, in either direction: the backward rotates q and k again where the rotated ones are needed and
     returns the gradients w.r.t. the un-rotated tensors (fp32 tensors, D % 8 == 0 for the backward).
 
-    The forward serves fp32 tensors.  16-bit tensors are served only where their block summaries are fp32 words or bf16 (head dims
-    above 96, summaries='bf16', the "fp32_summaries" option); on the h16 / p24 summaries that are their default the library refuses
-    the call (no rotary summary kernel is built for them) and this raises: use fp32 tensors, or rotate on the host and call
+    The forward serves fp32 tensors.  16-bit tensors are served only where their block summaries are fp32 words: head dims above
+    96; head dims up to 96 where the format falls back to fp32 words (more than 128 blocks of fewer than 16 tokens or at head dims under
+    32, more than 256 blocks, D * D no multiple of 64); the "fp32_summaries" process option.  The rotated q and k are fp32 values there and enter the
+    products as bf16 hi + lo pairs whatever the tensor type: one final rounding + 1e-3, like the default arithmetic of
+    mhla_blockmix.  On the h16 / p24 summaries that are the 16-bit default elsewhere the library refuses the call (no rotary summary
+    kernel is built for them) and this raises: use fp32 tensors, or rotate on the host and call
     mhla_blockmix(q_rope, k_rope, v, W, q_den=q, k_den=k)."""
     _require_gpu(q, k, v, W, rope_cos, rope_sin, block_index)
     _, N, _, D = q.shape

@@ -88,6 +88,62 @@ def oracle_blockmix(q, k, v, W, do, qd, kd, eps, normalize):
     return out, grads
 
 
+# The launch shapes of the rotary operator (tests/test_gpu_blockmix_rope.py holds the kernels to fp64 at them, tests/test_rope_ref_cpu.py
+# the reference's own conditioning): (B, H, M, S, D, normalize, gather map).  What each one reaches is listed in the GPU test.
+ROPE_CASES = [
+    (2, 3, 5, 70, 72, True, True), (2, 2, 3, 40, 24, True, True), (2, 2, 9, 16, 8, True, False), (1, 2, 70, 20, 88, True, False),
+    (1, 3, 33, 24, 96, True, True), (2, 2, 40, 33, 128, True, False), (1, 2, 150, 17, 104, False, True), (2, 2, 200, 8, 128, True, True),
+    (1, 2, 260, 8, 64, True, False), (2, 2, 6, 210, 128, True, True), (1, 2, 1, 48, 64, True, False), (2, 2, 16, 16, 64, False, True),
+]
+
+
+def rope_case_seed(case):
+    return case[2] * 1000 + case[3]
+
+
+def rope_rotate(x, cos, sin):
+    """Wan's rotation of x [B, N, H, D] by the token's angles: consecutive channel pairs (x0, x1) -> (x0 c - x1 s, x0 s + x1 c);
+    cos / sin: [N, D/2] tables in any float dtype, taken to the dtype of x (fp32 tables are exact in fp64)."""
+    B, N, H, D = x.shape
+    xs = x.reshape(B, N, H, D // 2, 2)
+    c, s = cos[None, :, None, :].to(x.dtype), sin[None, :, None, :].to(x.dtype)
+    return torch.stack((xs[..., 0] * c - xs[..., 1] * s, xs[..., 0] * s + xs[..., 1] * c), dim=-1).reshape(B, N, H, D)
+
+
+def make_rope_inputs(B, H, M, S, D, dtype, seed=1234, gather=False):
+    """Seeded inputs of the rotary block-mix operator: q, k = relu(randn) + 1e-6, v, dO = randn (all in `dtype`), W = rand(M, M),
+    fp32 cos / sin tables [N, D/2] of angles uniform in [0, 2 pi), and with `gather` a random permutation as the gather map
+    (int32[N]: block-major position -> token row; None otherwise).  Returns q, k, v, W, do, cos, sin, perm."""
+    g = torch.Generator().manual_seed(seed)
+    N = M * S
+    q = (torch.relu(torch.randn(B, N, H, D, generator=g)) + 1e-6).to(dtype)
+    k = (torch.relu(torch.randn(B, N, H, D, generator=g)) + 1e-6).to(dtype)
+    v = torch.randn(B, N, H, D, generator=g).to(dtype)
+    do = torch.randn(B, N, H, D, generator=g).to(dtype)
+    W = torch.rand(M, M, generator=g)
+    ang = torch.rand(N, D // 2, generator=g) * (2 * torch.pi)
+    cos, sin = torch.cos(ang), torch.sin(ang)
+    perm = torch.randperm(N, generator=g).int() if gather else None
+    return q, k, v, W, do, cos, sin, perm
+
+
+def rope_blockmix_fp64(q, k, v, W, do, cos, sin, perm=None, normalize=True, eps=1e-6, dtype=torch.float64):
+    """The rotary block-mix operator on the given tensors in fp64 (`dtype`: the same function in another precision, to measure
+    the reference's own conditioning): the un-rotated q, k are rotated by the tables, everything is gathered to block-major order
+    (position p reads token row perm[p]), the oracle's operator runs on the rotated pair with the un-rotated pair as the
+    normaliser's, and the result is scattered back to token rows.  Gradients of <out, do> w.r.t. the UN-rotated q, k and v, W by
+    autograd (tests/test_rope_ref_cpu.py ties them to the oracle's closed form).  Returns out, dq, dk, dv, dW."""
+    t = [x.detach().to(dtype).clone().requires_grad_(True) for x in (q, k, v, W)]
+    rows = torch.arange(q.shape[1]) if perm is None else perm.long()
+    bm = lambda x: x[:, rows]
+    o = orc.blockmix_fwd(bm(rope_rotate(t[0], cos, sin)), bm(rope_rotate(t[1], cos, sin)), bm(t[2]), t[3], eps,
+                         bm(t[0]) if normalize else None, bm(t[1]) if normalize else None, normalize)
+    (o * bm(do.to(dtype))).sum().backward()
+    out = torch.empty_like(o)
+    out[:, rows] = o.detach()
+    return out, t[0].grad, t[1].grad, t[2].grad, t[3].grad
+
+
 def to_dev(*ts):
     return [None if t is None else t.to(DEV) for t in ts]
 
