@@ -1,4 +1,6 @@
 """Shared helpers for the -m gpu parity tests: seeded inputs and oracle calls."""
+import ctypes
+
 import torch
 
 from conftest import rel_err, rms_ratio
@@ -291,6 +293,23 @@ def _fla_layer(**kw):
         (m.g_norm_swish_gate if m.fuse_norm_and_gate else m.g_norm).weight.uniform_(0.5, 1.5)
         m.mixing_matrix.copy_(torch.rand(32, 32).view(32, 32, 1, 1, 1, 1))
     return m
+
+
+def launches(fn):
+    """Kernel launches of the library while `fn` runs: {name: count} (mhla_prof_*)."""
+    from mhla_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(1 << 14)
+    torch.cuda.synchronize()
+    lib.mhla_prof_report(buf, len(buf))   # (clears records an earlier user may have left)
+    lib.mhla_prof_enable(1)
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        lib.mhla_prof_enable(0)
+        lib.mhla_prof_report(buf, len(buf))
+    return {ln.rsplit(" ", 2)[0]: int(ln.rsplit(" ", 2)[1]) for ln in buf.value.decode().splitlines() if ln.strip()}
 
 
 def poison():

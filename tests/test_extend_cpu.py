@@ -1,60 +1,12 @@
 """Extending a decode state by several tokens (mhla_causal_extend), the parts that need no GPU: an fp64 restatement of the
-formula (`extend_ref`, which the GPU tests import for their state comparisons) held to the oracle, the workspace arithmetic and
-the validation that runs before anything is launched."""
+formula (`decode_util.extend_ref`, which the GPU tests use for their state comparisons) held to the oracle, the workspace
+arithmetic and the validation that runs before anything is launched."""
 import pytest
 import torch
 
 from conftest import rel_err
+from decode_util import extend_ref, oracle_state
 from oracle import mhla_oracle as orc
-
-
-def extend_ref(state, q, k, v, mix, scale=None):
-    """`state` = (S [B, H, cap, K, V], P [B, H, K, V], Cur [B, H, K, V], seen); q, k [B, T, H, K], v [B, T, H, V]; chunk 64.
-    Returns (o [B, T, H, V], (S, P, Cur, seen) after the T tokens), all fp64, by the segment formula: with i = seen / 64,
-    r = seen % 64 a segment is a run of new tokens inside one chunk c,
-        O = scale (Q (P_c + m_cc Cur_before) + m_cc tril(Q K^T) V),  Cur = Cur_before + K^T V,
-        chunk full: S[c] = Cur, Cur = 0, P_{c+1} = sum_{j<=c} mix[c+1][j] S[j]  (0 when c + 1 == capacity)."""
-    S, P, Cur, seen = state
-    S, P, Cur = S.double().clone(), P.double().clone(), Cur.double().clone()
-    m = mix.reshape(mix.shape[0], mix.shape[1]).double()
-    cap = S.shape[2]
-    qh, kh, vh = (t.double().permute(0, 2, 1, 3) for t in (q, k, v))
-    T, K = qh.shape[2], qh.shape[3]
-    scale = K ** -0.5 if scale is None else scale
-    outs, t = [], 0
-    while t < T:
-        c, r = divmod(seen, 64)
-        assert c < cap, "the state is full"
-        a = min(T - t, 64 - r)
-        Q, Kc, Vc = qh[:, :, t:t + a], kh[:, :, t:t + a], vh[:, :, t:t + a]
-        A = torch.tril(Q @ Kc.transpose(-1, -2))
-        outs.append(scale * (Q @ (P + m[c, c] * Cur) + m[c, c] * (A @ Vc)))
-        Cur = Cur + Kc.transpose(-1, -2) @ Vc
-        t, seen = t + a, seen + a
-        if seen % 64 == 0:
-            S[:, :, c] = Cur
-            Cur = torch.zeros_like(Cur)
-            P = torch.einsum("j,bhjkv->bhkv", m[c + 1, :c + 1], S[:, :, :c + 1]) if c + 1 < cap else torch.zeros_like(P)
-    return torch.cat(outs, dim=2).permute(0, 2, 1, 3), (S, P, Cur, seen)
-
-
-def oracle_state(k, v, mix, seen, cap):
-    """The state after `seen` tokens from the oracle's chunk summaries (fp32)."""
-    B, _, H, K = k.shape
-    V = v.shape[-1]
-    S = torch.zeros(B, H, cap, K, V)
-    P, Cur = torch.zeros(B, H, K, V), torch.zeros(B, H, K, V)
-    if seen:
-        # (one more token than `seen` on a boundary, so that the oracle forms the open chunk's prefix mix)
-        n = seen + (1 if seen % 64 == 0 else 0)
-        z, kk, vv = torch.zeros(B, n, H, K), torch.zeros(B, n, H, K), torch.zeros(B, n, H, V)
-        kk[:, :seen], vv[:, :seen] = k[:, :seen].float(), v[:, :seen].float()
-        _, aux = orc.causal_fwd(z, kk, vv, mix, return_aux=True)
-        nfull = seen // 64
-        S[:, :, :nfull] = aux["S"][:, :, :nfull]
-        if nfull < cap:
-            Cur, P = aux["S"][:, :, nfull].clone(), aux["P"][:, :, nfull].clone()
-    return S, P, Cur, seen
 
 
 RUNS = [(0, (70,)), (60, (10, 1, 57, 64, 3)), (64, (65, 130)), (37, (27, 200, 64, 1, 63))]

@@ -1,77 +1,13 @@
 """Extending a ragged decode state by a token count per sequence (mhla_causal_extend(..., counts=)), the parts that need no
-GPU: a per-sequence restatement (`extend_ragged_ref`, test_extend_cpu.extend_ref applied to every sequence's own window, which
-the GPU tests import) held to the oracle, the workspace arithmetic of the ragged entry point and the validation that runs before
+GPU: a per-sequence restatement (`decode_util.extend_ragged_ref`, `extend_ref` applied to every sequence's own window, which
+the GPU tests use) held to the oracle, the workspace arithmetic of the ragged entry point and the validation that runs before
 the device check."""
 import pytest
 import torch
 
 from conftest import rel_err
+from decode_util import TABLE, TABLE_CAP, TABLE_T, extend_ragged_ref, oracle_state, start_state, table_inputs, window
 from oracle import mhla_oracle as orc
-from test_extend_cpu import extend_ref, oracle_state
-
-# (pos, n) of one batch, capacity 4 chunks, padded width 130: every branch of the per-sequence plan beside every other
-TABLE = [(60, 10),    # crosses a boundary
-         (0, 0),      # an idle slot
-         (63, 1),     # closes on its only row
-         (64, 130),   # starts on a boundary, then two whole chunks and a tail
-         (37, 27),    # lands exactly on a boundary: Cur = 0, P the next chunk's
-         (5, 3),      # stays inside its chunk
-         (0, 70),     # an empty state used as a prefill
-         (192, 64)]   # fills the state: P = Cur = 0
-TABLE_T, TABLE_CAP, TABLE_L = 130, 4, 5   # (one row of the matrix more than the capacity: the oracle opens chunk 4 for its summaries)
-
-
-def window(T, n, left_padded):
-    """Rows of the padded [B, T, ...] tensors that hold a sequence's n tokens."""
-    t0 = T - n if left_padded else 0
-    return slice(t0, t0 + n)
-
-
-def extend_ragged_ref(state, q, k, v, mix, counts, left_padded=False, scale=None):
-    """`state` = (S [B, H, cap, K, V], P, Cur [B, H, K, V], lengths); q, k [B, T, H, K], v [B, T, H, V] padded; sequence b takes
-    `counts[b]` tokens -- rows [0, n) or, left-padded, [T - n, T) -- at position lengths[b]: `extend_ref` on every sequence alone.
-    Returns (o [B, T, H, V] fp64, zeros outside every window, (S, P, Cur, lengths) afterwards, fp64).  Padding rows are never read."""
-    S, P, Cur, lengths = state
-    S, P, Cur = S.double().clone(), P.double().clone(), Cur.double().clone()
-    B, T, H, _ = q.shape
-    o = torch.zeros(B, T, H, v.shape[-1], dtype=torch.float64)
-    out_len = []
-    for b, (p, n) in enumerate(zip(lengths, counts)):
-        out_len.append(p + n)
-        if not n:
-            continue
-        w = window(T, n, left_padded)
-        ob, (Sb, Pb, Cb, seen) = extend_ref((S[b:b + 1], P[b:b + 1], Cur[b:b + 1], p), q[b:b + 1, w], k[b:b + 1, w], v[b:b + 1, w], mix, scale)
-        assert seen == p + n
-        o[b:b + 1, w], S[b:b + 1], P[b:b + 1], Cur[b:b + 1] = ob, Sb, Pb, Cb
-    return o, (S, P, Cur, tuple(out_len))
-
-
-def table_inputs(H, K, V, dtype=torch.float32, table=TABLE, T=TABLE_T, L=TABLE_L, seed=77, left_padded=False):
-    """Per sequence of `table` its whole history of pos + n tokens (q, k with signs as roped feature maps have them, rounded to
-    `dtype`), the padded tensors of the extension with NaN in every padding row, and a random lower-triangular mix [L, L]."""
-    g = torch.Generator().manual_seed(seed)
-    mix = torch.tril(torch.rand(L, L, generator=g).clamp(1e-5, 1))
-    hist = []
-    B = len(table)
-    q, k = (torch.full((B, T, H, K), float("nan")).to(dtype) for _ in range(2))
-    v = torch.full((B, T, H, V), float("nan")).to(dtype)
-    for b, (p, n) in enumerate(table):
-        m = max(p + n, 1)
-        qs = (torch.relu(torch.randn(1, m, H, K, generator=g)) * torch.sign(torch.randn(1, m, H, K, generator=g))).to(dtype)
-        ks = (torch.relu(torch.randn(1, m, H, K, generator=g)) * torch.sign(torch.randn(1, m, H, K, generator=g))).to(dtype)
-        vs = torch.randn(1, m, H, V, generator=g).to(dtype)
-        hist.append((qs, ks, vs))
-        w = window(T, n, left_padded)
-        q[b, w], k[b, w], v[b, w] = qs[0, p:p + n], ks[0, p:p + n], vs[0, p:p + n]
-    return hist, q, k, v, mix
-
-
-def start_state(hist, table, mix, cap):
-    """The batch's state before the extension, sequence by sequence from the oracle's summaries (fp32)."""
-    parts = [oracle_state(ks.float(), vs.float(), mix, p, cap) for (_, ks, vs), (p, _) in zip(hist, table)]
-    return tuple(torch.cat([x[i] for x in parts]) for i in range(3)) + (tuple(p for p, _ in table),)
-
 
 @pytest.mark.parametrize("left_padded", [False, True], ids=["right-padded", "left-padded"])
 @pytest.mark.parametrize("scale", [None, 0.37])

@@ -1,29 +1,15 @@
 """GPU parity: decoding with the causal operator -- prefill state + single-token steps (mhla_causal_prefill / mhla_causal_step),
 the fla layer's `exact_decoding` and the GPT host's cache / generate.  The reference is the chunk operator itself: it is causal,
 so row t of `orc.causal_fwd` over the whole sequence is what step t must return."""
-import functools
-
 import pytest
 import torch
 
 from conftest import load_golden, rel_err, rms_ratio
+from decode_util import check_state, decode_inputs, packed_views
 from gpu_util import DEV, CAUSAL_CHUNK_TOL_H16, CAUSAL_TOL, TOL, check, check_chunks, poison, _fla_layer
 from oracle import mhla_oracle as orc
 
 pytestmark = pytest.mark.gpu
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(B, T, H, K, V, L, dtype, seed=1234, scale=None):
-    """q, k with signs as roped feature maps have them, random lower-triangular mix; the fp32 oracle (output and summaries) of
-    the dtype-rounded tensors, computed once per case."""
-    g = torch.Generator().manual_seed(seed)
-    q = (torch.relu(torch.randn(B, T, H, K, generator=g)) * torch.sign(torch.randn(B, T, H, K, generator=g))).to(dtype)
-    k = (torch.relu(torch.randn(B, T, H, K, generator=g)) * torch.sign(torch.randn(B, T, H, K, generator=g))).to(dtype)
-    v = torch.randn(B, T, H, V, generator=g).to(dtype)
-    mix = torch.tril(torch.rand(L, L, generator=g).clamp(1e-5, 1))
-    want = orc.causal_fwd(q.float(), k.float(), v.float(), mix, scale=scale)
-    return q, k, v, mix, want
 
 
 def _check_rows(name, o0, o1, want):
@@ -52,16 +38,6 @@ def _decode(q, k, v, mix, T0, n, state=None, views=None, scale=None, **kw):
     return o0, (torch.cat(outs, dim=1) if outs else None), state
 
 
-def _packed_views(qt, kt, vt):
-    """q, k, v of one token as strided slices of ONE packed projection output [B, 1, H * (2 K + V)]."""
-    B, _, H, K = qt.shape
-    V = vt.shape[-1]
-    packed = torch.cat([qt, kt, vt], dim=-1).reshape(B, 1, H * (2 * K + V)).contiguous().view(B, 1, H, 2 * K + V)
-    views = packed[..., :K], packed[..., K:2 * K], packed[..., 2 * K:]
-    assert not views[1].is_contiguous() and views[1].data_ptr() != packed.data_ptr()
-    return views
-
-
 CASES = [  # dtype, B, H, K, V, T0, n, packed
     (torch.float32, 2, 2, 16, 24, 0, 70, False),       # empty state, first roll
     (torch.float32, 1, 2, 32, 16, 60, 10, False),      # partial tail then roll
@@ -77,7 +53,7 @@ C5 = CASES[3]
 def _case(case):
     dtype, B, H, K, V, T0, n, packed = case
     L = (T0 + n + 63) // 64 + 1
-    q, k, v, mix, want = _inputs(B, T0 + n, H, K, V, L, dtype)
+    q, k, v, mix, want = decode_inputs(B, T0 + n, H, K, V, L, dtype)
     return [t.to(DEV) for t in (q, k, v, mix)], want
 
 
@@ -86,7 +62,7 @@ def test_steps_are_rows_of_the_full_operator(case):
     dtype, B, H, K, V, T0, n, packed = case
     (q, k, v, mix), want = _case(case)
     poison()
-    o0, o1, state = _decode(q, k, v, mix, T0, n, views=_packed_views if packed else None)
+    o0, o1, state = _decode(q, k, v, mix, T0, n, views=packed_views if packed else None)
     assert state.seen == T0 + n and o1.dtype == dtype and o1.shape == (B, n, H, V)
     if T0:
         check("prefill rows", o0, want[:, :T0], CAUSAL_TOL[dtype])
@@ -127,39 +103,16 @@ def test_steps_match_the_reference_recurrent_form_on_the_first_chunk():
     check_chunks("vs out", o1, g["out"][:, :50], 1e-4)
 
 
-def _check_state(state, q, k, v, mix, name):
-    """S, P, Cur against the oracle's summaries of the tokens seen so far (fp32 state whatever the tensor dtype)."""
-    s = state.seen
-    nfull, tail = s // 64, s % 64
-    f = lambda t, n: t[:, :n].float().cpu()
-    tol = TOL[torch.float32]
-    assert state.S.dtype == state.P.dtype == state.Cur.dtype == torch.float32
-    _, aux = orc.causal_fwd(f(q, s), f(k, s), f(v, s), mix.cpu(), return_aux=True)
-    if nfull:
-        check(f"{name}: S", state.S[:, :, :nfull], aux["S"][:, :, :nfull], tol)
-    if tail:
-        check(f"{name}: Cur", state.Cur, aux["S"][:, :, nfull], tol)
-        if nfull:
-            check(f"{name}: P", state.P, aux["P"][:, :, nfull], tol)
-        else:
-            assert float(state.P.abs().max()) == 0.0
-    else:
-        assert float(state.Cur.abs().max()) == 0.0
-        if s + 1 <= q.shape[1]:   # on a boundary: the prefix mix the NEXT token will read
-            _, aux1 = orc.causal_fwd(f(q, s + 1), f(k, s + 1), f(v, s + 1), mix.cpu(), return_aux=True)
-            check(f"{name}: P (boundary)", state.P, aux1["P"][:, :, nfull], tol, atol=1e-30 if nfull == 0 else 0.0)
-
-
 def test_state_contents():
     import mhla_amd
     dtype, B, H, K, V, T0, n, _ = C5
     (q, k, v, mix), _ = _case(C5)
     _, _, state = _decode(q, k, v, mix, T0, 0)
-    _check_state(state, q, k, v, mix, "after prefill(120)")
+    check_state(state, q, k, v, mix, "after prefill(120)")
     _decode(q, k, v, mix, T0, 8, state=state)
-    _check_state(state, q, k, v, mix, "on the boundary 128")
+    check_state(state, q, k, v, mix, "on the boundary 128")
     _decode(q, k, v, mix, T0, n - 8, state=state)
-    _check_state(state, q, k, v, mix, "after 80 steps")
+    check_state(state, q, k, v, mix, "after 80 steps")
     # prefill(T0) + n steps == prefill(T0 + n)
     _, ref = mhla_amd.mhla_causal_prefill(q, k, v, mix)
     assert ref.seen == state.seen == T0 + n
@@ -170,14 +123,14 @@ def test_state_contents():
     check("Cur: steps vs prefill", state.Cur, ref.Cur.cpu(), tol)
     # a prefill that ends on a boundary
     _, _, sb = _decode(q, k, v, mix, 128, 0)
-    _check_state(sb, q, k, v, mix, "after prefill(128)")
+    check_state(sb, q, k, v, mix, "after prefill(128)")
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
 @pytest.mark.parametrize("gate,affine", [(True, True), (True, False), (False, True)])
 def test_step_fused_norm_gate_epilogue(dtype, gate, affine):
     B, H, K, V, T0, n = 1, 2, 64, 128, 60, 6
-    q, k, v, mix, want = _inputs(B, T0 + n, H, K, V, 3, dtype)
+    q, k, v, mix, want = decode_inputs(B, T0 + n, H, K, V, 3, dtype)
     gen = torch.Generator().manual_seed(7)
     g = torch.randn(B, T0 + n, H, V, generator=gen).to(dtype)
     w = torch.rand(V, generator=gen) + 0.5
@@ -212,7 +165,7 @@ def test_scale_argument_across_a_chunk_boundary(dtype, epilogue, scale):
     import mhla_amd
     B, H, K, V, T0, n = 1, 2, 64, 128, 60, 10
     assert abs(scale - K ** -0.5) > 0.1
-    q, k, v, mix, want = _inputs(B, T0 + n, H, K, V, 3, dtype, 1234, scale)
+    q, k, v, mix, want = decode_inputs(B, T0 + n, H, K, V, 3, dtype, 1234, scale)
     qd, kd, vd, md = (t.to(DEV) for t in (q, k, v, mix))
     kw = {}
     if epilogue:
@@ -222,7 +175,7 @@ def test_scale_argument_across_a_chunk_boundary(dtype, epilogue, scale):
         eps = {0.37: 72.0, 1.0: 530.0}[scale]
         kw = dict(gate=g.to(DEV), norm_weight=w.to(DEV), norm_eps=eps)
         y_ref = orc.rms_norm_swish_gate(want[:, T0:], g[:, T0:].float(), w, eps)
-        y_default = orc.rms_norm_swish_gate(_inputs(B, T0 + n, H, K, V, 3, dtype)[4][:, T0:], g[:, T0:].float(), w, eps)
+        y_default = orc.rms_norm_swish_gate(decode_inputs(B, T0 + n, H, K, V, 3, dtype)[4][:, T0:], g[:, T0:].float(), w, eps)
         assert rel_err(y_default, y_ref) > 0.25   # the comparison can see the argument: 50 times the widest bound below
     poison()
     o0, o1, state = _decode(qd, kd, vd, md, T0, n, scale=scale, **kw)
@@ -277,7 +230,7 @@ def test_full_state_and_errors():
     import mhla_amd
     from mhla_amd import _lib, ops
     B, H, K, V = 1, 2, 16, 24
-    q, k, v, mix3, want = _inputs(B, 130, H, K, V, 3, torch.float32, seed=5)
+    q, k, v, mix3, want = decode_inputs(B, 130, H, K, V, 3, torch.float32, seed=5)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix3[:2, :2].contiguous()))   # (rows 0, 1 of the operator read mix[:2, :2] only)
     # an [L, L] = [2, 2] matrix serves 128 tokens: the last step closes chunk 1 without a next row of mix
     o0, o1, state = _decode(q, k, v, mix, 120, 8)

@@ -1,33 +1,17 @@
 """GPU parity: extending a decode state of the causal operator by several tokens in one call (mhla_causal_extend), through the
 fla layer's `exact_decoding` and the GPT host's cache.  The reference is the chunk operator itself, as in
 test_gpu_causal_decode.py: rows state.seen .. state.seen + T - 1 of `orc.causal_fwd` over the whole sequence; states are
-compared with the oracle's summaries, with the fp64 restatement of the segment formula (test_extend_cpu.extend_ref) and with
+compared with the oracle's summaries, with the fp64 restatement of the segment formula (decode_util.extend_ref) and with
 the same state advanced by single steps."""
-import ctypes
-import functools
-
 import pytest
 import torch
 
 from conftest import load_golden, rel_err, rms_ratio
-from gpu_util import DEV, CAUSAL_CHUNK_TOL_H16, CAUSAL_TOL, TOL, check, check_chunks, poison, _fla_layer
+from decode_util import check_state, cpu_state, decode_inputs, extend_ref, packed_views, same_state
+from gpu_util import DEV, CAUSAL_CHUNK_TOL_H16, CAUSAL_TOL, TOL, check, check_chunks, launches, poison, _fla_layer
 from oracle import mhla_oracle as orc
-from test_extend_cpu import extend_ref
 
 pytestmark = pytest.mark.gpu
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(B, T, H, K, V, L, dtype, seed=1234, scale=None):
-    """As test_gpu_causal_decode._inputs: q, k with signs as roped feature maps have them, random lower-triangular mix; the fp32
-    oracle of the dtype-rounded tensors, computed once per case."""
-    g = torch.Generator().manual_seed(seed)
-    q = (torch.relu(torch.randn(B, T, H, K, generator=g)) * torch.sign(torch.randn(B, T, H, K, generator=g))).to(dtype)
-    k = (torch.relu(torch.randn(B, T, H, K, generator=g)) * torch.sign(torch.randn(B, T, H, K, generator=g))).to(dtype)
-    v = torch.randn(B, T, H, V, generator=g).to(dtype)
-    mix = torch.tril(torch.rand(L, L, generator=g).clamp(1e-5, 1))
-    want = orc.causal_fwd(q.float(), k.float(), v.float(), mix, scale=scale)
-    return q, k, v, mix, want
 
 
 def _start(q, k, v, mix, T0, scale=None, **kw):
@@ -58,16 +42,6 @@ def _steps(q, k, v, mix, state, n, **kw):
     return torch.cat(outs, dim=1)
 
 
-def _packed_views(qt, kt, vt):
-    """q, k, v of the T tokens as strided slices of ONE packed projection output [B, T, H * (2 K + V)]."""
-    B, T, H, K = qt.shape
-    V = vt.shape[-1]
-    packed = torch.cat([qt, kt, vt], dim=-1).reshape(B, T, H * (2 * K + V)).contiguous().view(B, T, H, 2 * K + V)
-    views = packed[..., :K], packed[..., K:2 * K], packed[..., 2 * K:]
-    assert not views[1].is_contiguous() and views[1].data_ptr() != packed.data_ptr()
-    return views
-
-
 def _check_rows(name, o0, ext, want):
     """All rows from token 0, so that the 64-token chunks of the per-chunk check are the operator's.  Chunks that hold prefill rows
     of the default operator (11-bit stored summaries for 16-bit tensors) get the wider of the two per-chunk bounds; every chunk
@@ -82,56 +56,6 @@ def _check_rows(name, o0, ext, want):
         check_chunks(f"{name}: chunks with prefill rows", got[:, :n0], want[:, :n0], max(CAUSAL_CHUNK_TOL_H16[dt], CAUSAL_TOL[dt]))
     if got.shape[1] > n0:
         check_chunks(f"{name}: chunks from the state alone", got[:, n0:], want[:, n0:], CAUSAL_TOL[dt])
-
-
-def _close(name, got, want, tol):
-    w = want.float().cpu()
-    if w.numel() == 0:
-        return
-    if float(w.abs().max()) == 0.0:
-        assert float(got.abs().max()) == 0.0, f"{name} must be exactly zero"
-    else:
-        check(name, got, w, tol)
-
-
-def _check_state(state, q, k, v, mix, name):
-    """S, P, Cur against the oracle's summaries of the tokens seen so far (the logic of test_gpu_causal_decode._check_state)."""
-    s = state.seen
-    nfull, tail = s // 64, s % 64
-    f = lambda t, n: t[:, :n].float().cpu()
-    tol = TOL[torch.float32]
-    assert state.S.dtype == state.P.dtype == state.Cur.dtype == torch.float32
-    _, aux = orc.causal_fwd(f(q, s), f(k, s), f(v, s), mix.cpu(), return_aux=True)
-    if nfull:
-        check(f"{name}: S", state.S[:, :, :nfull], aux["S"][:, :, :nfull], tol)
-    if tail:
-        check(f"{name}: Cur", state.Cur, aux["S"][:, :, nfull], tol)
-        if nfull:
-            check(f"{name}: P", state.P, aux["P"][:, :, nfull], tol)
-        else:
-            assert float(state.P.abs().max()) == 0.0
-    else:
-        assert float(state.Cur.abs().max()) == 0.0, f"{name}: Cur on a boundary must be exactly 0"
-        if s + 1 <= q.shape[1] and nfull < state.capacity_chunks:   # on a boundary: the prefix mix the NEXT token will read
-            _, aux1 = orc.causal_fwd(f(q, s + 1), f(k, s + 1), f(v, s + 1), mix.cpu(), return_aux=True)
-            check(f"{name}: P (boundary)", state.P, aux1["P"][:, :, nfull], tol, atol=1e-30 if nfull == 0 else 0.0)
-
-
-def _same_state(name, a, b, tol=None):
-    """States a, b (a CausalState, or extend_ref's tuple): finished chunks, P and Cur equal (tol None: bit for bit)."""
-    ta = (a.S, a.P, a.Cur, a.seen) if hasattr(a, "seen") else a
-    tb = (b.S, b.P, b.Cur, b.seen) if hasattr(b, "seen") else b
-    assert ta[3] == tb[3]
-    nfull = ta[3] // 64
-    for part, x, y in (("S", ta[0][:, :, :nfull], tb[0][:, :, :nfull]), ("P", ta[1], tb[1]), ("Cur", ta[2], tb[2])):
-        if tol is None:
-            assert torch.equal(x, y), f"{name}: {part} differs"
-        else:
-            _close(f"{name}: {part}", x, y, tol)
-
-
-def _cpu_state(state):
-    return state.S.cpu(), state.P.cpu(), state.Cur.cpu(), state.seen
 
 
 CASES = [  # dtype, B, H, K, V, T0 (prefill), extensions, packed, state checks
@@ -153,7 +77,7 @@ C5 = CASES[4]
 def _case(case):
     dtype, B, H, K, V, T0, exts = case[:7]
     T = T0 + sum(exts)
-    q, k, v, mix, want = _inputs(B, T, H, K, V, (T + 63) // 64 + 1, dtype)
+    q, k, v, mix, want = decode_inputs(B, T, H, K, V, (T + 63) // 64 + 1, dtype)
     return [t.to(DEV) for t in (q, k, v, mix)], want
 
 
@@ -170,16 +94,16 @@ def test_extensions_are_rows_of_the_full_operator(case):
     outs = []
     for n in exts:
         before = state.clone()
-        outs.append(_extend(q, k, v, mix, state, n, views=_packed_views if packed else None))
+        outs.append(_extend(q, k, v, mix, state, n, views=packed_views if packed else None))
         if states:
             name = f"after {state.seen} tokens"
-            _check_state(state, q, k, v, mix, name)
+            check_state(state, q, k, v, mix, name)
             sl = slice(before.seen, state.seen)
-            o_ref, ref = extend_ref(_cpu_state(before), q[:, sl].cpu(), k[:, sl].cpu(), v[:, sl].cpu(), mix.cpu())
+            o_ref, ref = extend_ref(cpu_state(before), q[:, sl].cpu(), k[:, sl].cpu(), v[:, sl].cpu(), mix.cpu())
             check(f"{name}: rows vs extend_ref", outs[-1], o_ref.float(), CAUSAL_TOL[dtype])
-            _same_state(f"{name}: vs extend_ref", _cpu_state(state), ref, TOL[torch.float32])
+            same_state(f"{name}: vs extend_ref", cpu_state(state), ref, TOL[torch.float32])
             _steps(q, k, v, mix, before, n)
-            _same_state(f"{name}: vs single steps", _cpu_state(state), _cpu_state(before), TOL[torch.float32])
+            same_state(f"{name}: vs single steps", cpu_state(state), cpu_state(before), TOL[torch.float32])
     assert state.seen == T0 + sum(exts)
     _check_rows("rows", o0, torch.cat(outs, dim=1), want)
 
@@ -187,7 +111,7 @@ def test_extensions_are_rows_of_the_full_operator(case):
 def test_interleaved_extensions_and_steps():
     import mhla_amd
     dtype, B, H, K, V = torch.bfloat16, 1, 2, 64, 64
-    q, k, v, mix, want = _inputs(B, 205, H, K, V, 5, dtype)
+    q, k, v, mix, want = decode_inputs(B, 205, H, K, V, 5, dtype)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
     poison()
     o0, state = _start(q, k, v, mix, 50)
@@ -196,15 +120,15 @@ def test_interleaved_extensions_and_steps():
     assert state.seen == 205
     _check_rows("rows", o0, torch.cat(outs, dim=1), want)
     ref = mhla_amd.mhla_causal_state(k, v, mix)
-    _same_state("vs one prefill of the whole sequence", _cpu_state(state), _cpu_state(ref), TOL[torch.float32])
-    _check_state(state, q, k, v, mix, "after 205 tokens")
+    same_state("vs one prefill of the whole sequence", cpu_state(state), cpu_state(ref), TOL[torch.float32])
+    check_state(state, q, k, v, mix, "after 205 tokens")
 
 
 @pytest.mark.parametrize("T0", [10, 63, 64], ids=["inside", "closes-the-chunk", "on-a-boundary"])
 def test_one_token_is_the_step(T0):
     import mhla_amd
     dtype, B, H, K, V = torch.bfloat16, 1, 2, 64, 128
-    q, k, v, mix, _ = _inputs(B, 70, H, K, V, 3, dtype)
+    q, k, v, mix, _ = decode_inputs(B, 70, H, K, V, 3, dtype)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
     _, sa = _start(q, k, v, mix, T0)
     sb = sa.clone()
@@ -243,7 +167,7 @@ def test_extend_fused_norm_gate_epilogue(dtype, gate, affine, scale):
     values test_scale_argument_across_a_chunk_boundary derives for these inputs): the oracle's y at the default scale is then far
     outside the bound, asserted below."""
     B, H, K, V, T0, n = 1, 2, 64, 128, 20, 50
-    q, k, v, mix, want = _inputs(B, T0 + n, H, K, V, 3, dtype, 1234, scale)
+    q, k, v, mix, want = decode_inputs(B, T0 + n, H, K, V, 3, dtype, 1234, scale)
     gen = torch.Generator().manual_seed(7)
     g = torch.randn(B, T0 + n, H, V, generator=gen).to(dtype)
     w = torch.rand(V, generator=gen) + 0.5
@@ -254,7 +178,7 @@ def test_extend_fused_norm_gate_epilogue(dtype, gate, affine, scale):
             return orc.rms_norm_swish_gate(o, g[:, T0:].float(), w if affine else None, eps)
         return o * torch.rsqrt(o.pow(2).mean(-1, keepdim=True) + eps) * w
     y_ref = y_of(want[:, T0:])
-    assert rel_err(y_of(_inputs(B, T0 + n, H, K, V, 3, dtype)[4][:, T0:]), y_ref) > 0.25   # the comparison can see `scale`
+    assert rel_err(y_of(decode_inputs(B, T0 + n, H, K, V, 3, dtype)[4][:, T0:]), y_ref) > 0.25   # the comparison can see `scale`
     qd, kd, vd, md = (t.to(DEV) for t in (q, k, v, mix))
     kw = {"norm_eps": eps, "scale": scale}
     if gate:
@@ -269,7 +193,7 @@ def test_extend_fused_norm_gate_epilogue(dtype, gate, affine, scale):
     _, s2 = _start(qd, kd, vd, md, T0, scale=scale)
     o = _extend(qd, kd, vd, md, s2, n, scale=scale)
     check("o", o, want[:, T0:], CAUSAL_TOL[dtype])
-    _same_state("epilogue or not", state, s2)
+    same_state("epilogue or not", state, s2)
 
 
 def test_extensions_are_deterministic():
@@ -282,7 +206,7 @@ def test_extensions_are_deterministic():
         runs.append((_extend(q, k, v, mix, st, 200), st))
     (oa, sa), (ob, sb) = runs
     assert torch.equal(oa, ob)
-    _same_state("two runs", sa, sb)
+    same_state("two runs", sa, sb)
 
 
 def test_long_extensions_and_large_batches_are_cut(monkeypatch):
@@ -290,7 +214,7 @@ def test_long_extensions_and_large_batches_are_cut(monkeypatch):
     of one batch entry slices the batch: the same segments through the same kernels, so the same bits as one call."""
     from mhla_amd import ops
     dtype, B, H, K, V, T0, n = torch.bfloat16, 2, 2, 64, 64, 40, 230
-    q, k, v, mix, want = _inputs(B, T0 + n, H, K, V, 6, dtype)
+    q, k, v, mix, want = decode_inputs(B, T0 + n, H, K, V, 6, dtype)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
     o0, s0 = _start(q, k, v, mix, T0)
     whole = s0.clone()
@@ -298,14 +222,14 @@ def test_long_extensions_and_large_batches_are_cut(monkeypatch):
     monkeypatch.setattr(ops, "EXTEND_WS_CAP_BYTES", 1)
     monkeypatch.setattr(ops, "_MAX_GRID_BH", H)
     cut = s0.clone()
-    ran = _launches(lambda: _extend(q, k, v, mix, cut, n))
+    ran = launches(lambda: _extend(q, k, v, mix, cut, n))
     assert ran["k_cx_xty_acc"] == 2 * 5, ran      # per batch entry: 24 tokens to the boundary, 64, 64, 64, 14
     _check_rows("rows", o0, o_whole, want)
     cut2 = s0.clone()
     o_cut = _extend(q, k, v, mix, cut2, n)
     assert torch.equal(o_cut, o_whole)
-    _same_state("cut vs one call", cut2, whole)
-    _same_state("cut, run twice", cut2, cut)
+    same_state("cut vs one call", cut2, whole)
+    same_state("cut, run twice", cut2, cut)
 
 
 def test_uninitialised_memory_is_never_read():
@@ -322,7 +246,7 @@ def test_uninitialised_memory_is_never_read():
     s2.S[:, :, 1:] = float("nan")
     o2 = _extend(q, k, v, mix, s2, 150)
     assert torch.equal(o2, o1)
-    _same_state("NaN beyond the finished chunks", s2, state)
+    same_state("NaN beyond the finished chunks", s2, state)
     assert bool(torch.isnan(s2.S[:, :, nfull:]).all())
 
 
@@ -330,7 +254,7 @@ def test_full_state_and_errors():
     import mhla_amd
     from mhla_amd import _lib, ops
     B, H, K, V = 1, 2, 16, 24
-    q, k, v, mix3, want = _inputs(B, 130, H, K, V, 3, torch.float32, seed=5)
+    q, k, v, mix3, want = decode_inputs(B, 130, H, K, V, 3, torch.float32, seed=5)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix3[:2, :2].contiguous()))   # (rows 0, 1 of the operator read mix[:2, :2] only)
     # an [L, L] = [2, 2] matrix serves 128 tokens: the extension closes chunk 1 without a next row of mix
     o0, state = _start(q, k, v, mix, 120)
@@ -338,14 +262,14 @@ def test_full_state_and_errors():
     _check_rows("rows up to the capacity", o0, o1, want[:, :128])
     assert state.seen == 128 and state.capacity_chunks == 2
     assert float(state.P.abs().max()) == 0.0 and float(state.Cur.abs().max()) == 0.0     # the state is full
-    _check_state(state, q, k, v, mix, "full state")
+    check_state(state, q, k, v, mix, "full state")
     keep = state.clone()
     with pytest.raises(IndexError, match="needs 3 chunks but mixing_matrix has only 2 rows"):
         _extend(q, k, v, mix, state, 2)
     with pytest.raises(IndexError):
         _extend(q, k, v, mix, state, 1)
     assert state.seen == 128
-    _same_state("after the refused calls", state, keep)
+    same_state("after the refused calls", state, keep)
     _, fresh = _start(q, k, v, mix, 120)
     keep = fresh.clone()
     with pytest.raises(IndexError, match="sequence of 129 tokens needs 3 chunks"):
@@ -379,7 +303,7 @@ def test_full_state_and_errors():
     with pytest.raises(RuntimeError, match="inference only"):
         ext(some(q).clone().requires_grad_(True), some(k), some(v))
     assert st.seen == 10
-    _same_state("after the refused calls", st, before)
+    same_state("after the refused calls", st, before)
     with torch.no_grad():   # the same input under no_grad is fine
         o = ext(some(q).clone().requires_grad_(True), some(k), some(v))
     assert not o.requires_grad and st.seen == 15
@@ -439,31 +363,14 @@ def test_checks_behind_the_device_check_refuse_before_launch(name, T):
     refused(fresh(chunk_size=32), f"{name}: chunk_size=32, the decode state supports 64 only")
 
 
-def _launches(fn):
-    """Kernel launches of the library while `fn` runs: {name: count} (mhla_prof_*)."""
-    from mhla_amd import _lib
-    lib = _lib.load()
-    buf = ctypes.create_string_buffer(1 << 14)
-    torch.cuda.synchronize()
-    lib.mhla_prof_report(buf, len(buf))   # (clears records an earlier user may have left)
-    lib.mhla_prof_enable(1)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        lib.mhla_prof_enable(0)
-        lib.mhla_prof_report(buf, len(buf))
-    return {ln.rsplit(" ", 2)[0]: int(ln.rsplit(" ", 2)[1]) for ln in buf.value.decode().splitlines() if ln.strip()}
-
-
 def test_launch_count_does_not_depend_on_the_tokens():
     (q, k, v, mix), want = _case(C5)
     _, state = _start(q, k, v, mix, 100)
-    ran = _launches(lambda: _extend(q, k, v, mix, state, 200))
+    ran = launches(lambda: _extend(q, k, v, mix, state, 200))
     assert ran and "k_cs_step" not in ran and "k_cx_out" in ran, ran
     assert sum(ran.values()) <= 8 < 200, ran
     _, s2 = _start(q, k, v, mix, 100)
-    stepped = _launches(lambda: _steps(q, k, v, mix, s2, 3))
+    stepped = launches(lambda: _steps(q, k, v, mix, s2, 3))
     assert stepped.get("k_cs_step") == 3 and sum(stepped.values()) >= 6, stepped   # at least two per token
 
 
@@ -474,7 +381,7 @@ def test_fla_layer_launch_count():
     cache = modules.DecodeCache()
     with torch.no_grad():
         m(x[:, :100], past_key_values=cache, use_cache=True)
-        ran = _launches(lambda: m(x[:, 100:300], past_key_values=cache, use_cache=True))
+        ran = launches(lambda: m(x[:, 100:300], past_key_values=cache, use_cache=True))
     assert ran and "k_cs_step" not in ran and "k_cx_out" in ran, ran
     assert sum(ran.values()) < 200, ran
     assert cache.get_seq_length() == 300 and cache[0]["recurrent_state"].seen == 300

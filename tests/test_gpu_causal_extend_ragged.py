@@ -8,22 +8,15 @@ import functools
 import pytest
 import torch
 
-from gpu_util import DEV, CAUSAL_TOL, TOL, check, poison, _fla_layer
+from decode_util import (NAN, SHAPE_IDS, SHAPES, TABLE, TABLE_CAP, TABLE_T, close_or_zero, cpu_state, extend_ragged_ref, layer_inputs,
+                         one_sequence, oracle_state, padding_is_zero, ragged_start, same_seq_state, table_inputs, unchanged, window)
+from gpu_util import DEV, CAUSAL_TOL, TOL, check, launches, poison, _fla_layer
 from oracle import mhla_oracle as orc
-from test_extend_cpu import oracle_state
-from test_extend_ragged_cpu import TABLE, TABLE_CAP, TABLE_T, extend_ragged_ref, table_inputs, window
-from test_gpu_causal_extend import _close, _launches
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(torch.float32, 2, 16, 24),      # below one tile
-          (torch.float32, 2, 80, 72),      # not multiples of 64
-          (torch.bfloat16, 2, 64, 128),
-          (torch.float16, 2, 64, 64)]
-SHAPE_IDS = ["fp32-K16V24", "fp32-K80V72", "bf16-K64V128", "fp16-K64V64"]
 # a batch twice as large, with other counts (capacity 4 as well)
 TABLE2 = TABLE + [(10, 5), (100, 130), (63, 2), (0, 1), (128, 64), (200, 7), (1, 0), (64, 64)]
-NAN = float("nan")
 
 
 @functools.lru_cache(maxsize=None)
@@ -33,30 +26,6 @@ def _batch(dtype, H, K, V, left_padded, big=False):
     hist, q, k, v, mix = table_inputs(H, K, V, dtype, table=tuple(table), left_padded=left_padded)
     want = [orc.causal_fwd(qs.float(), ks.float(), vs.float(), mix)[:, p:p + n] if n else None for (qs, ks, vs), (p, n) in zip(hist, table)]
     return table, hist, q, k, v, mix, want
-
-
-def _start(table, hist, mix, cap=TABLE_CAP):
-    """The ragged state of the batch before the extension: `mhla_causal_state(lengths=)` over the right-padded histories."""
-    import mhla_amd
-    B, T0 = len(table), max(max(p for p, _ in table), 1)
-    _, k0, v0 = hist[0]
-    k = torch.zeros(B, T0, *k0.shape[2:], dtype=k0.dtype)
-    v = torch.zeros(B, T0, *v0.shape[2:], dtype=v0.dtype)
-    for b, (p, _) in enumerate(table):
-        k[b, :p], v[b, :p] = hist[b][1][0, :p], hist[b][2][0, :p]
-    state = mhla_amd.mhla_causal_state(k.to(DEV), v.to(DEV), mix.to(DEV), lengths=[p for p, _ in table], capacity_chunks=cap)
-    assert state.lengths == tuple(p for p, _ in table)
-    return state
-
-
-def _cpu(state):
-    return state.S.cpu(), state.P.cpu(), state.Cur.cpu(), state.lengths
-
-
-def _one(state, b):
-    """Sequence b of a ragged state as a uniform state of a batch of one (a copy)."""
-    import mhla_amd
-    return mhla_amd.CausalState(state.S[b:b + 1].clone(), state.P[b:b + 1].clone(), state.Cur[b:b + 1].clone(), state.lengths[b], 64)
 
 
 def _extend(q, k, v, mix, state, counts, left_padded, **kw):
@@ -69,25 +38,6 @@ def _extend(q, k, v, mix, state, counts, left_padded, **kw):
     return o
 
 
-def _padding_is_zero(o, counts, left_padded):
-    T = o.shape[1]
-    for b, n in enumerate(counts):
-        pad = torch.ones(T, dtype=torch.bool)
-        pad[window(T, n, left_padded)] = False
-        if bool(pad.any()):
-            assert float(o[b].cpu()[pad].float().abs().max()) == 0.0, f"sequence {b}: padding rows must be exactly zero"
-
-
-def _same_seq_state(name, a, ia, b, ib, seen):
-    """Sequence ia of state a and ib of b: finished chunks, P and Cur bit for bit."""
-    nfull = seen // 64
-    for part in ("S", "P", "Cur"):
-        x, y = getattr(a, part)[ia], getattr(b, part)[ib]
-        if part == "S":
-            x, y = x[:, :nfull], y[:, :nfull]
-        assert torch.equal(x, y), f"{name}: {part} differs"
-
-
 @pytest.mark.parametrize("left_padded", [False, True], ids=["right-padded", "left-padded"])
 @pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
 def test_rows_and_states_of_every_sequence(shape, left_padded):
@@ -95,17 +45,17 @@ def test_rows_and_states_of_every_sequence(shape, left_padded):
     table, hist, q, k, v, mix, want = _batch(dtype, H, K, V, left_padded)
     counts = tuple(n for _, n in table)
     poison()
-    state = _start(table, hist, mix)
+    state = ragged_start(table, hist, mix)
     before = state.clone()
     o = _extend(q.to(DEV), k.to(DEV), v.to(DEV), mix.to(DEV), state, counts, left_padded)
-    _padding_is_zero(o, counts, left_padded)
-    o_ref, ref = extend_ragged_ref(_cpu(before), q, k, v, mix, counts, left_padded)
+    padding_is_zero(o, counts, left_padded)
+    o_ref, ref = extend_ragged_ref(cpu_state(before), q, k, v, mix, counts, left_padded)
     tol = TOL[torch.float32]
     checked = 0
     for b, (p, n) in enumerate(table):
         name = f"sequence {b} (pos {p}, n {n})"
         if not n:
-            _same_seq_state(name + ": an idle slot keeps its state", state, b, before, b, 64 * TABLE_CAP)
+            same_seq_state(name + ": an idle slot keeps its state", state, b, before, b, 64 * TABLE_CAP)
             continue
         w = window(TABLE_T, n, left_padded)
         check(f"{name}: rows", o[b:b + 1, w], want[b], CAUSAL_TOL[dtype])
@@ -114,8 +64,8 @@ def test_rows_and_states_of_every_sequence(shape, left_padded):
         nfull = (p + n) // 64
         for part, got, a, r in (("S", state.S[b:b + 1, :, :nfull], orc_state[0][:, :, :nfull], ref[0][b:b + 1, :, :nfull]),
                                 ("P", state.P[b:b + 1], orc_state[1], ref[1][b:b + 1]), ("Cur", state.Cur[b:b + 1], orc_state[2], ref[2][b:b + 1])):
-            _close(f"{name}: {part} vs the oracle", got, a, tol)
-            _close(f"{name}: {part} vs extend_ref", got, r.float(), tol)
+            close_or_zero(f"{name}: {part} vs the oracle", got, a, tol)
+            close_or_zero(f"{name}: {part} vs extend_ref", got, r.float(), tol)
         if (p + n) % 64 == 0:
             assert float(state.Cur[b].abs().max()) == 0.0, f"{name}: Cur on a boundary must be exactly 0"
         if p + n == 64 * TABLE_CAP:
@@ -134,14 +84,14 @@ def test_same_bits_as_each_sequence_alone(shape, left_padded):
     table, hist, q, k, v, mix, _ = _batch(dtype, H, K, V, left_padded)
     counts = tuple(n for _, n in table)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
-    state = _start(table, hist, mix.cpu())
+    state = ragged_start(table, hist, mix.cpu())
     before = state.clone()
     o = _extend(q, k, v, mix, state, counts, left_padded)
     for b, (p, n) in enumerate(table):
         if not n:
             continue
         w = window(TABLE_T, n, left_padded)
-        alone = _one(before, b)
+        alone = one_sequence(before, b)
         fn = mhla_amd.mhla_causal_step if n == 1 else mhla_amd.mhla_causal_extend
         oa = fn(q[b:b + 1, w], k[b:b + 1, w], v[b:b + 1, w], mix, alone)
         assert alone.seen == p + n
@@ -149,7 +99,7 @@ def test_same_bits_as_each_sequence_alone(shape, left_padded):
         diff = (o[b:b + 1, w].float() - oa.float()).abs().max().item()
         print(f"{name}: max |batch - alone| = {diff:.3e}")
         assert torch.equal(o[b:b + 1, w], oa), f"{name}: rows differ from the sequence alone (max {diff:.3e})"
-        _same_seq_state(name, state, b, alone, 0, p + n)
+        same_seq_state(name, state, b, alone, 0, p + n)
 
 
 def test_padding_is_never_read_and_always_written():
@@ -164,7 +114,7 @@ def test_padding_is_never_read_and_always_written():
             g[b, window(TABLE_T, n, left_padded)] = torch.randn(n, H, V, generator=gen)
         wgt = torch.rand(V, generator=gen) + 0.5
         qd, kd, vd, md, gd = (t.to(DEV) for t in (q, k, v, mix, g.to(dtype)))
-        state = _start(table, hist, mix)
+        state = ragged_start(table, hist, mix)
         nanned = state.clone()
         for b, (p, n) in enumerate(table):
             nanned.S[b, :, (p + n) // 64:] = NAN        # rows of S beyond the chunks this sequence will have finished
@@ -173,18 +123,18 @@ def test_padding_is_never_read_and_always_written():
         o = _extend(qd, kd, vd, md, state, counts, left_padded)
         y = _extend(qd, kd, vd, md, before.clone(), counts, left_padded, gate=gd, norm_weight=wgt.to(DEV))
         for name, res in (("o", o), ("y", y)):
-            _padding_is_zero(res, counts, left_padded)
+            padding_is_zero(res, counts, left_padded)
             for b, n in enumerate(counts):
                 assert bool(torch.isfinite(res[b, window(TABLE_T, n, left_padded)]).all()), f"{name}: sequence {b} holds non-finite rows"
         for name, t in (("S", state.S), ("P", state.P), ("Cur", state.Cur)):
             assert bool(torch.isfinite(t).all()), f"{name} holds non-finite values"
-        _same_seq_state("an idle slot keeps its state", state, 1, before, 1, 64 * TABLE_CAP)
+        same_seq_state("an idle slot keeps its state", state, 1, before, 1, 64 * TABLE_CAP)
         assert torch.equal(state.S[1], before.S[1])
         o2 = _extend(qd, kd, vd, md, nanned, counts, left_padded)
         assert torch.equal(o2, o)
         for b, (p, n) in enumerate(table):
             nfull = (p + n) // 64
-            _same_seq_state(f"sequence {b}: NaN beyond the finished chunks", nanned, b, state, b, p + n)
+            same_seq_state(f"sequence {b}: NaN beyond the finished chunks", nanned, b, state, b, p + n)
             assert bool(torch.isnan(nanned.S[b, :, nfull:]).all()), f"sequence {b}: S beyond chunk {nfull} was written"
 
 
@@ -204,10 +154,10 @@ def test_epilogue_and_strided_views(dtype):
     qv, kv, vv = packed[..., :K], packed[..., K:2 * K], packed[..., 2 * K:]
     assert not kv.is_contiguous() and kv.data_ptr() != packed.data_ptr()
     poison()
-    state = _start(table, hist, mix)
+    state = ragged_start(table, hist, mix)
     plain = state.clone()
     y = _extend(qv, kv, vv, mix.to(DEV), state, counts, left_padded, gate=g.to(DEV), norm_weight=wgt.to(DEV), norm_eps=1e-5)
-    _padding_is_zero(y, counts, left_padded)
+    padding_is_zero(y, counts, left_padded)
     for b, (p, n) in enumerate(table):
         if n:
             w = window(TABLE_T, n, left_padded)
@@ -216,7 +166,7 @@ def test_epilogue_and_strided_views(dtype):
     # the state does not depend on the epilogue or on the views
     _extend(q.to(DEV), k.to(DEV), v.to(DEV), mix.to(DEV), plain, counts, left_padded)
     for b, (p, n) in enumerate(table):
-        _same_seq_state(f"sequence {b}: epilogue or not", state, b, plain, b, p + n)
+        same_seq_state(f"sequence {b}: epilogue or not", state, b, plain, b, p + n)
 
 
 def test_launch_count_depends_on_nothing():
@@ -227,17 +177,17 @@ def test_launch_count_depends_on_nothing():
         table, hist, q, k, v, mix, _ = _batch(dtype, H, K, V, False, big)
         counts = tuple(n for _, n in table)
         q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
-        state = _start(table, hist, mix.cpu())
+        state = ragged_start(table, hist, mix.cpu())
         loop = state.clone()
-        ran[big] = _launches(lambda: _extend(q, k, v, mix, state, counts, False))
+        ran[big] = launches(lambda: _extend(q, k, v, mix, state, counts, False))
         assert ran[big] and "k_cs_step" not in ran[big] and "k_cx_out_ragged" in ran[big], ran[big]
         assert sum(ran[big].values()) <= 8, ran[big]
 
         def per_sequence():
             for b, (p, n) in enumerate(table):
                 if n:
-                    mhla_amd.mhla_causal_extend(q[b:b + 1, :n], k[b:b + 1, :n], v[b:b + 1, :n], mix, _one(loop, b))
-        looped = _launches(per_sequence)
+                    mhla_amd.mhla_causal_extend(q[b:b + 1, :n], k[b:b + 1, :n], v[b:b + 1, :n], mix, one_sequence(loop, b))
+        looped = launches(per_sequence)
         assert sum(looped.values()) > sum(ran[big].values()), (looped, ran[big])
     assert sum(ran[True].values()) == sum(ran[False].values()), ran
 
@@ -247,7 +197,7 @@ def test_two_runs_give_equal_bits():
     table, hist, q, k, v, mix, _ = _batch(dtype, H, K, V, True)
     counts = tuple(n for _, n in table)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
-    s0 = _start(table, hist, mix.cpu())
+    s0 = ragged_start(table, hist, mix.cpu())
     runs = []
     for _ in range(2):
         st = s0.clone()
@@ -258,12 +208,6 @@ def test_two_runs_give_equal_bits():
     assert torch.equal(sa.pos, sb.pos)
 
 
-def _unchanged(state, keep):
-    torch.cuda.synchronize()
-    assert state.lengths == keep.lengths and state.seen == keep.seen and torch.equal(state.pos, keep.pos)
-    assert torch.equal(state.S, keep.S) and torch.equal(state.P, keep.P) and torch.equal(state.Cur, keep.Cur)
-
-
 def test_refusals_leave_the_state_untouched():
     import mhla_amd
     from mhla_amd import _lib, ops
@@ -271,15 +215,15 @@ def test_refusals_leave_the_state_untouched():
     table, hist, q, k, v, mix, _ = _batch(dtype, H, K, V, False)
     B = len(table)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
-    state = _start(table, hist, mix.cpu())
+    state = ragged_start(table, hist, mix.cpu())
     keep = state.clone()
     ext = lambda counts, m=mix: mhla_amd.mhla_causal_extend(q, k, v, m, state, counts=counts)
     with pytest.raises(IndexError, match=r"sequences \[7\].*the state holds only 4"):
         ext([0, 0, 0, 0, 0, 0, 0, 65])              # sequence 7 is at 192 of 256
-    _unchanged(state, keep)
+    unchanged(state, keep)
     with pytest.raises(IndexError, match=r"sequences \[3, 7\].*mixing_matrix has only 1 rows"):
         ext([1, 1, 1, 1, 1, 1, 1, 1], m=mix[:1, :1].contiguous())   # sequences 3 (at 64) and 7 (at 192) are beyond chunk 0
-    _unchanged(state, keep)
+    unchanged(state, keep)
 
     # the raw entry point
     lib = _lib.load()
@@ -304,7 +248,7 @@ def test_refusals_leave_the_state_untouched():
     assert raw(T=65536) == EINVAL and b"T=65536" in lib.mhla_last_error()
     assert raw(max_end=257) == EINVAL and b"max_end=257" in lib.mhla_last_error()
     assert raw(pos=None) == EINVAL and b"pos_dev" in lib.mhla_last_error()
-    _unchanged(state, keep)
+    unchanged(state, keep)
 
 
 def test_interleaved_with_ragged_steps():
@@ -318,7 +262,7 @@ def test_interleaved_with_ragged_steps():
     hist, _, _, _, mix = table_inputs(H, K, V, dtype, table=table, T=max(total), L=L, seed=5)
     want = [orc.causal_fwd(qs.float(), ks.float(), vs.float(), mix) for qs, ks, vs in hist]
     B = len(total)
-    state = _start(tuple((p, 0) for p in pos0), hist, mix, cap)
+    state = ragged_start(tuple((p, 0) for p in pos0), hist, mix, cap)
     md = mix.to(DEV)
 
     def padded(counts, T, left_padded):
@@ -350,7 +294,7 @@ def test_interleaved_with_ragged_steps():
     ref = mhla_amd.mhla_causal_state(k_all.to(DEV), v_all.to(DEV), md, lengths=total, capacity_chunks=cap)
     for b, n in enumerate(total):
         for part, x, y in (("S", state.S[b, :, :n // 64], ref.S[b, :, :n // 64]), ("P", state.P[b], ref.P[b]), ("Cur", state.Cur[b], ref.Cur[b])):
-            _close(f"sequence {b}: {part} vs one prefill of its whole history", x, y.cpu(), TOL[torch.float32])
+            close_or_zero(f"sequence {b}: {part} vs one prefill of its whole history", x, y.cpu(), TOL[torch.float32])
 
 
 def test_no_counts_on_differing_lengths_takes_the_ragged_chain():
@@ -361,18 +305,18 @@ def test_no_counts_on_differing_lengths_takes_the_ragged_chain():
     table = ((60, T), (0, T), (64, T))
     hist, q, k, v, mix = table_inputs(H, K, V, dtype, table=table, T=T, L=4, seed=11)
     q, k, v, md = (t.to(DEV) for t in (q, k, v, mix))
-    state = _start(table, hist, mix, 4)
+    state = ragged_start(table, hist, mix, 4)
     before = state.clone()
-    ran = _launches(lambda: mhla_amd.mhla_causal_extend(q, k, v, md, state))
+    ran = launches(lambda: mhla_amd.mhla_causal_extend(q, k, v, md, state))
     assert "k_cx_out_ragged" in ran and sum(ran.values()) <= 8, ran
     assert state.lengths == (130, 70, 134) and state.pos.tolist() == [130, 70, 134] and state.seen == 134
     o = mhla_amd.mhla_causal_extend(q, k, v, md, before.clone())
     for b, (p, n) in enumerate(table):
-        alone = _one(before, b)
+        alone = one_sequence(before, b)
         assert torch.equal(o[b:b + 1], mhla_amd.mhla_causal_extend(q[b:b + 1], k[b:b + 1], v[b:b + 1], md, alone))
-        _same_seq_state(f"sequence {b}", state, b, alone, 0, p + n)
-    same = _start(((60, T), (60, T)), hist[:1] * 2, mix, 4)
-    ran = _launches(lambda: mhla_amd.mhla_causal_extend(q[:2], k[:2], v[:2], md, same))
+        same_seq_state(f"sequence {b}", state, b, alone, 0, p + n)
+    same = ragged_start(((60, T), (60, T)), hist[:1] * 2, mix, 4)
+    ran = launches(lambda: mhla_amd.mhla_causal_extend(q[:2], k[:2], v[:2], md, same))
     assert "k_cx_out" in ran and "k_cx_out_ragged" not in ran, ran
 
 
@@ -385,44 +329,40 @@ def test_large_batches_are_sliced_and_a_workspace_over_the_cap_falls_back(monkey
     table, hist, q, k, v, mix, want = _batch(dtype, H, K, V, True)
     counts = tuple(n for _, n in table)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
-    s0 = _start(table, hist, mix.cpu())
+    s0 = ragged_start(table, hist, mix.cpu())
     whole = s0.clone()
     o_whole = _extend(q, k, v, mix, whole, counts, True)
     monkeypatch.setattr(ops, "_MAX_GRID_BH", 3 * H)
     sliced = s0.clone()
-    ran = _launches(lambda: _extend(q, k, v, mix, sliced, counts, True))
+    ran = launches(lambda: _extend(q, k, v, mix, sliced, counts, True))
     assert ran["k_cs_step_finish_ragged"] == 3 and "k_cx_out" not in ran, ran      # slices of 3, 3 and 2 sequences
     sliced = s0.clone()
     assert torch.equal(_extend(q, k, v, mix, sliced, counts, True), o_whole)
     for b, (p, n) in enumerate(table):
-        _same_seq_state(f"sequence {b}: sliced vs one chain", sliced, b, whole, b, p + n)
+        same_seq_state(f"sequence {b}: sliced vs one chain", sliced, b, whole, b, p + n)
     monkeypatch.setattr(ops, "EXTEND_WS_CAP_BYTES", 1)
     cut = s0.clone()
-    ran = _launches(lambda: _extend(q, k, v, mix, cut, counts, True))
+    ran = launches(lambda: _extend(q, k, v, mix, cut, counts, True))
     assert "k_cx_out" in ran and "k_cx_out_ragged" not in ran, ran
     cut = s0.clone()
     o_cut = _extend(q, k, v, mix, cut, counts, True)
-    _padding_is_zero(o_cut, counts, True)
+    padding_is_zero(o_cut, counts, True)
     for b, (p, n) in enumerate(table):
         if n:
             check(f"sequence {b}: rows of the fallback", o_cut[b:b + 1, window(TABLE_T, n, True)], want[b], CAUSAL_TOL[dtype])
         nfull = (p + n) // 64
         for part, x, y in (("S", cut.S[b, :, :nfull], whole.S[b, :, :nfull]), ("P", cut.P[b], whole.P[b]), ("Cur", cut.Cur[b], whole.Cur[b])):
-            _close(f"sequence {b}: {part} of the fallback vs the chain", x, y.cpu(), TOL[torch.float32])
+            close_or_zero(f"sequence {b}: {part} of the fallback vs the chain", x, y.cpu(), TOL[torch.float32])
 
 
 def test_all_counts_zero_is_a_no_op():
     dtype, H, K, V = SHAPES[0]
     table, hist, q, k, v, mix, _ = _batch(dtype, H, K, V, False)
-    state = _start(table, hist, mix)
+    state = ragged_start(table, hist, mix)
     keep = state.clone()
-    ran = _launches(lambda: _extend(q.to(DEV), k.to(DEV), v.to(DEV), mix.to(DEV), state, (0,) * len(table), False))
+    ran = launches(lambda: _extend(q.to(DEV), k.to(DEV), v.to(DEV), mix.to(DEV), state, (0,) * len(table), False))
     assert not ran, ran
-    _unchanged(state, keep)
-
-
-def _layer_inputs(B, T, seed):
-    return torch.randn(B, T, 256, generator=torch.Generator().manual_seed(seed))
+    unchanged(state, keep)
 
 
 @pytest.mark.parametrize("opts", [{}, {"use_output_gate": False}], ids=["default", "no-output-gate"])
@@ -431,8 +371,8 @@ def test_fla_layer_token_counts(opts):
     from mhla_amd import modules
     m = _fla_layer(**opts).to(DEV).eval()
     prompts, counts, T = (70, 20, 64), (3, 130, 0), 130
-    x0 = _layer_inputs(3, 70, 31).to(DEV)
-    x1 = _layer_inputs(3, T, 32).to(DEV)
+    x0 = layer_inputs(3, 70, 31).to(DEV)
+    x1 = layer_inputs(3, T, 32).to(DEV)
     mask = torch.zeros(3, 70, dtype=torch.long, device=DEV)
     for b, n in enumerate(prompts):
         mask[b, 70 - n:] = 1
@@ -454,7 +394,7 @@ def test_fla_layer_token_counts(opts):
 def test_fla_layer_token_counts_refusals():
     from mhla_amd import modules
     m = _fla_layer().to(DEV).eval()
-    x0, x1 = _layer_inputs(2, 10, 41).to(DEV), _layer_inputs(2, 4, 42).to(DEV)
+    x0, x1 = layer_inputs(2, 10, 41).to(DEV), layer_inputs(2, 4, 42).to(DEV)
     mask = torch.tensor([[0] * 5 + [1] * 5, [1] * 10], device=DEV)
     cache = modules.DecodeCache()
     with torch.no_grad():

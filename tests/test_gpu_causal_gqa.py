@@ -11,12 +11,12 @@ import functools
 import pytest
 import torch
 
+from decode_util import NAN, signed_features
 from gpu_util import DEV, CAUSAL_TOL, check, poison
 from oracle import mhla_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
 B, K, V, CAP, L = 3, 40, 72, 4, 5
 HEADS = [(4, 2), (6, 2), (8, 1)]
 DTYPES = [torch.bfloat16, torch.float32]
@@ -36,8 +36,7 @@ def rep(t, G):
 def _stream(dtype, H, Hk):
     """One stream of tokens per batch entry (q with H heads, k, v with Hk), gate, norm weight, the matrix -- on the device."""
     g = torch.Generator().manual_seed(97 + H + Hk)
-    sgn = lambda *s: torch.relu(torch.randn(*s, generator=g)) * torch.sign(torch.randn(*s, generator=g))
-    q, k = sgn(B, STREAM, H, K).to(dtype), sgn(B, STREAM, Hk, K).to(dtype)
+    q, k = signed_features(g, B, STREAM, H, K).to(dtype), signed_features(g, B, STREAM, Hk, K).to(dtype)
     v, gate = torch.randn(B, STREAM, Hk, V, generator=g).to(dtype), torch.randn(B, STREAM, H, V, generator=g).to(dtype)
     mix = torch.tril(torch.rand(L, L, generator=g).clamp(1e-5, 1))
     w = torch.rand(V, generator=g) + 0.5

@@ -23,11 +23,10 @@ Forward, u = 2^-8:
 import pytest
 import torch
 
-from gpu_util import DEV, check, poison
+from gpu_util import DEV, check, launches, poison
 from oracle import mhla_oracle as orc
 from test_gpu_causal import causal_inputs
 from test_gpu_causal_varlen import CU, seqs
-from test_gpu_neighbours import _launches
 
 pytestmark = pytest.mark.gpu
 
@@ -93,7 +92,7 @@ def run_fused(q, k, v, mix, do, g, w, summaries, norm_eps=1e-5, cu=None, keep_st
     assert ops.causal_normgate_fusable(fd[0], fd[2], cu_seqlens=plan, flags=ops._causal_flags(summaries, False)) == fusable
     dod, res = do.to(DEV), {}
     poison()
-    ran = _launches(lambda: res.__setitem__("y", mhla_amd.mhla_causal_normgate(fd[0], fd[1], fd[2], fd[3], fd[4], fd[5], norm_eps, **kw)))
+    ran = launches(lambda: res.__setitem__("y", mhla_amd.mhla_causal_normgate(fd[0], fd[1], fd[2], fd[3], fd[4], fd[5], norm_eps, **kw)))
     y = res["y"]
     assert y.dtype == dtype and y.shape == v.shape
     fused = [n for n in ran if n.startswith("k_csf_out4<norm")]
@@ -206,7 +205,7 @@ def test_strided_views(summaries):
     assert not gate.is_contiguous() and not dy.is_contiguous() and not dqkv[:, :, 0].is_contiguous()
     res = {}
     poison()
-    ran = _launches(lambda: res.__setitem__("y", mhla_amd.mhla_causal_normgate(dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2], dm, gate, dw, 1e-5,
+    ran = launches(lambda: res.__setitem__("y", mhla_amd.mhla_causal_normgate(dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2], dm, gate, dw, 1e-5,
                                                                               summaries=summaries)))
     assert ran.get(fused_kernel(D)) == 1, ran
     poison()

@@ -2,128 +2,36 @@
 step kernels, extend on a ragged state, the fla layer's left-padded prefill and the GPT host's `attention_mask`.  Sequence b must
 behave exactly as if it lived alone in a batch of one, so the reference is `orc.causal_fwd` (resp. the layer / the host's full
 forward) per sequence, on that sequence's own tokens."""
-import functools
-
 import pytest
 import torch
 
-from gpu_util import DEV, CAUSAL_TOL, TOL, check, check_chunks, poison, _fla_layer
+from decode_util import check_state, check_step_rows, packed_views, ragged_inputs, ragged_prefill, ragged_steps, window_rows
+from gpu_util import DEV, CAUSAL_TOL, check, poison, _fla_layer
 from oracle import mhla_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 
-@functools.lru_cache(maxsize=None)
-def _seqs(lengths, n, H, K, V, L, dtype, seed=1234):
-    """B sequences on timelines of their own: sequence b's tokens are rows [0, lengths[b] + n] of q[b], k[b], v[b] (one more than
-    the n decoded ones, for the state check on a boundary).  q, k with signs as roped feature maps have them, a random lower-
-    triangular mix; the fp32 oracle of every sequence alone over its lengths[b] + n tokens, computed once per case."""
-    B, T = len(lengths), max(lengths) + n + 1
-    g = torch.Generator().manual_seed(seed)
-    q = (torch.relu(torch.randn(B, T, H, K, generator=g)) * torch.sign(torch.randn(B, T, H, K, generator=g))).to(dtype)
-    k = (torch.relu(torch.randn(B, T, H, K, generator=g)) * torch.sign(torch.randn(B, T, H, K, generator=g))).to(dtype)
-    v = torch.randn(B, T, H, V, generator=g).to(dtype)
-    mix = torch.tril(torch.rand(L, L, generator=g).clamp(1e-5, 1))
-    want = tuple(orc.causal_fwd(q[b:b + 1, :m + n].float(), k[b:b + 1, :m + n].float(), v[b:b + 1, :m + n].float(), mix)
-                 for b, m in enumerate(lengths))
-    return q, k, v, mix, want
-
-
-def _left_padded(x, lengths):
-    """[B, max(lengths), ...]: sequence b's first lengths[b] rows at the END of row b, NaN (never to be read) before them."""
-    T = max(lengths)
-    out = torch.full((len(lengths), T) + tuple(x.shape[2:]), float("nan"), dtype=x.dtype, device=x.device)
-    for b, m in enumerate(lengths):
-        if m:
-            out[b, T - m:] = x[b, :m]
-    return out
-
-
-def _window(x, lengths, t0, n):
-    """[B, n, ...]: rows lengths[b] + t0 .. of every sequence (the tokens the next n steps take)."""
-    return torch.stack([x[b, m + t0:m + t0 + n] for b, m in enumerate(lengths)])
-
-
-def _prefill(q, k, v, mix, lengths, how, cap=None):
-    """(prefill rows per sequence, ragged state) through `lengths=` on a left-padded batch, or `CausalState.cat` of B = 1 prefills."""
-    import mhla_amd
-    if how == "left_padded":
-        T = max(lengths)
-        o, state = mhla_amd.mhla_causal_prefill(*(_left_padded(t, lengths) for t in (q, k, v)), mix, lengths=list(lengths), left_padded=True,
-                                                capacity_chunks=cap)
-        for b, m in enumerate(lengths):
-            assert float(o[b, :T - m].abs().max() if m < T else 0.0) == 0.0, f"padding rows of sequence {b} are not zero"
-        return [o[b:b + 1, T - m:] for b, m in enumerate(lengths)], state
-    parts = [mhla_amd.mhla_causal_prefill(q[b:b + 1, :m], k[b:b + 1, :m], v[b:b + 1, :m], mix, capacity_chunks=cap) for b, m in enumerate(lengths)]
-    return [o for o, _ in parts], mhla_amd.CausalState.cat([s for _, s in parts])
-
-
-def _steps(q, k, v, mix, state, lengths, t0, n, views=None, **kw):
-    import mhla_amd
-    qs, ks, vs = (_window(t, lengths, t0, n) for t in (q, k, v))
-    outs = []
-    for t in range(n):
-        qt, kt, vt = (views or (lambda *a: a))(qs[:, t:t + 1], ks[:, t:t + 1], vs[:, t:t + 1])
-        outs.append(mhla_amd.mhla_causal_step(qt, kt, vt, mix, state, **{a: (b[:, t:t + 1] if a == "gate" else b) for a, b in kw.items()}))
-    return torch.cat(outs, dim=1)
-
-
-def _check_step_rows(name, got, want, m, dtype):
-    """Rows m .. of one sequence: within CAUSAL_TOL of the sequence's maximum, and chunk by chunk of the sequence's OWN chunks (the
-    rows up to its next boundary, then whole chunks) within CAUSAL_TOL of each chunk's maximum: step rows come from the fp32 state."""
-    ref = want[:, m:]
-    check(name, got, ref, CAUSAL_TOL[dtype])
-    first = min(got.shape[1], 64 - m % 64)
-    check_chunks(f"{name} (open chunk)", got[:, :first], ref[:, :first], CAUSAL_TOL[dtype])
-    if first < got.shape[1]:
-        check_chunks(name, got[:, first:], ref[:, first:], CAUSAL_TOL[dtype])
-
-
-def _check_state(state, b, s, q, k, v, mix, name):
-    """S, P, Cur of sequence b against the oracle's summaries of its s tokens (as _check_state of test_gpu_causal_decode.py)."""
-    nfull, tail = s // 64, s % 64
-    f = lambda t, n: t[b:b + 1, :n].float().cpu()
-    tol = TOL[torch.float32]
-    S, P, Cur = state.S[b:b + 1], state.P[b:b + 1], state.Cur[b:b + 1]
-    assert S.dtype == P.dtype == Cur.dtype == torch.float32
-    _, aux = orc.causal_fwd(f(q, s), f(k, s), f(v, s), mix.cpu(), return_aux=True) if s else (None, None)
-    if nfull:
-        check(f"{name}: S", S[:, :, :nfull], aux["S"][:, :, :nfull], tol)
-    if tail:
-        check(f"{name}: Cur", Cur, aux["S"][:, :, nfull], tol)
-        if nfull:
-            check(f"{name}: P", P, aux["P"][:, :, nfull], tol)
-        else:
-            assert float(P.abs().max()) == 0.0
-    else:
-        assert float(Cur.abs().max()) == 0.0
-        if nfull == state.capacity_chunks:
-            assert float(P.abs().max()) == 0.0   # a full state has no open chunk
-        elif s + 1 <= q.shape[1]:   # on a boundary: the prefix mix the NEXT token will read
-            _, aux1 = orc.causal_fwd(f(q, s + 1), f(k, s + 1), f(v, s + 1), mix.cpu(), return_aux=True)
-            check(f"{name}: P (boundary)", P, aux1["P"][:, :, nfull], tol, atol=1e-30 if nfull == 0 else 0.0)
-
-
 def _run_rows(dtype, H, K, V, lengths, n, L, cap, how, state_checks=True):
-    q, k, v, mix, want = _seqs(lengths, n, H, K, V, L, dtype)
+    q, k, v, mix, want = ragged_inputs(lengths, n, H, K, V, L, dtype)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
     poison()
-    o0, state = _prefill(q, k, v, mix, lengths, how, cap)
+    o0, state = ragged_prefill(q, k, v, mix, lengths, how, cap)
     assert state.lengths == tuple(lengths) and state.seen == max(lengths) and state.pos.tolist() == list(lengths)
     assert state.capacity_chunks == (cap or L)
     for b, m in enumerate(lengths):
         if m:
             check(f"seq {b}: prefill rows", o0[b], want[b][:, :m], CAUSAL_TOL[dtype])
         if state_checks:
-            _check_state(state, b, m, q, k, v, mix, f"seq {b} after prefill({m})")
-    o1 = _steps(q, k, v, mix, state, lengths, 0, n)
+            check_state(state, q, k, v, mix, f"seq {b} after prefill({m})", b, m)
+    o1 = ragged_steps(q, k, v, mix, state, lengths, 0, n)
     assert o1.dtype == dtype and o1.shape == (len(lengths), n, H, V)
     assert state.lengths == tuple(m + n for m in lengths) and state.seen == max(lengths) + n
     assert state.pos.tolist() == list(state.lengths)
     for b, m in enumerate(lengths):
-        _check_step_rows(f"seq {b}: step rows", o1[b:b + 1], want[b], m, dtype)
+        check_step_rows(f"seq {b}: step rows", o1[b:b + 1], want[b], m, dtype)
         if state_checks:
-            _check_state(state, b, m + n, q, k, v, mix, f"seq {b} after {n} steps")
+            check_state(state, q, k, v, mix, f"seq {b} after {n} steps", b, m + n)
     return state
 
 
@@ -146,7 +54,7 @@ def test_dtypes_and_k_split(case):
 def test_equal_lengths_give_the_uniform_bits():
     import mhla_amd
     dtype, H, K, V, T0, n = torch.bfloat16, 2, 64, 128, 60, 10
-    q, k, v, mix, _ = _seqs((T0, T0), n, H, K, V, 3, dtype)
+    q, k, v, mix, _ = ragged_inputs((T0, T0), n, H, K, V, 3, dtype)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
     rag = mhla_amd.mhla_causal_state(k[:, :T0], v[:, :T0], mix, lengths=[T0, T0])
     uni = mhla_amd.mhla_causal_state(k[:, :T0], v[:, :T0], mix)
@@ -160,30 +68,20 @@ def test_equal_lengths_give_the_uniform_bits():
     assert float(rag.S[:, :, 0].abs().max()) > 0
 
 
-def _packed_views(qt, kt, vt):
-    """q, k, v of one token as strided slices of ONE packed projection output [B, 1, H * (2 K + V)]."""
-    B, _, H, K = qt.shape
-    V = vt.shape[-1]
-    packed = torch.cat([qt, kt, vt], dim=-1).reshape(B, 1, H * (2 * K + V)).contiguous().view(B, 1, H, 2 * K + V)
-    views = packed[..., :K], packed[..., K:2 * K], packed[..., 2 * K:]
-    assert not views[1].is_contiguous() and views[1].data_ptr() != packed.data_ptr()
-    return views
-
-
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
 def test_epilogue_and_strided_views(dtype):
     """The fused norm x gate epilogue on a ragged state, q, k, v read in place as slices of one packed projection: sequence 0 closes
     its chunk at the fourth step, sequence 1 is in its first chunk."""
     H, K, V, lengths, n = 2, 64, 128, (60, 5), 6
-    q, k, v, mix, want = _seqs(lengths, n, H, K, V, 3, dtype)
+    q, k, v, mix, want = ragged_inputs(lengths, n, H, K, V, 3, dtype)
     gen = torch.Generator().manual_seed(7)
     g = torch.randn(2, n, H, V, generator=gen).to(dtype)
     w = torch.rand(V, generator=gen) + 0.5
     eps = 1e-5
     qd, kd, vd, md = (t.to(DEV) for t in (q, k, v, mix))
     poison()
-    _, state = _prefill(qd, kd, vd, md, lengths, "left_padded")
-    y = _steps(qd, kd, vd, md, state, lengths, 0, n, views=_packed_views, gate=g.to(DEV), norm_weight=w.to(DEV), norm_eps=eps)
+    _, state = ragged_prefill(qd, kd, vd, md, lengths, "left_padded")
+    y = ragged_steps(qd, kd, vd, md, state, lengths, 0, n, views=packed_views, gate=g.to(DEV), norm_weight=w.to(DEV), norm_eps=eps)
     assert y.dtype == dtype and state.lengths == (66, 11)
     for b, m in enumerate(lengths):
         y_ref = orc.rms_norm_swish_gate(want[b][:, m:], g[b:b + 1].float(), w, eps)
@@ -195,14 +93,14 @@ def test_full_state_and_refusal():
     step after that would open chunk 2 of sequence 0 and is refused before anything is launched."""
     import mhla_amd
     dtype, H, K, V, lengths = torch.float32, 2, 16, 24, (127, 30)
-    q, k, v, mix, want = _seqs(lengths, 1, H, K, V, 2, dtype)
+    q, k, v, mix, want = ragged_inputs(lengths, 1, H, K, V, 2, dtype)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
     state = _run_rows(dtype, H, K, V, lengths, 1, 2, None, "left_padded")   # (checks rows and, per sequence, S, P, Cur)
     assert state.capacity_chunks == 2 and state.lengths == (128, 31)
     assert float(state.P[0].abs().max()) == 0.0 and float(state.Cur[0].abs().max()) == 0.0 and float(state.P[1].abs().max()) == 0.0
     assert float(state.Cur[1].abs().max()) > 0
     keep = state.clone()
-    qs, ks, vs = (_window(t, lengths, 1, 1) for t in (q, k, v))
+    qs, ks, vs = (window_rows(t, lengths, 1, 1) for t in (q, k, v))
     with pytest.raises(IndexError, match="needs 3 chunks"):
         mhla_amd.mhla_causal_step(qs, ks, vs, mix, state)
     with pytest.raises(IndexError, match="needs 3 chunks"):
@@ -215,18 +113,18 @@ def test_full_state_and_refusal():
 def test_extend_on_a_ragged_state():
     import mhla_amd
     dtype, H, K, V, lengths, T, n = torch.float32, 2, 32, 64, (10, 70), 130, 5
-    q, k, v, mix, want = _seqs(lengths, T + n, H, K, V, 5, dtype)
+    q, k, v, mix, want = ragged_inputs(lengths, T + n, H, K, V, 5, dtype)
     q, k, v, mix = (t.to(DEV) for t in (q, k, v, mix))
     poison()
-    _, state = _prefill(q, k, v, mix, lengths, "left_padded")
-    o = mhla_amd.mhla_causal_extend(*(_window(t, lengths, 0, T) for t in (q, k, v)), mix, state)
+    _, state = ragged_prefill(q, k, v, mix, lengths, "left_padded")
+    o = mhla_amd.mhla_causal_extend(*(window_rows(t, lengths, 0, T) for t in (q, k, v)), mix, state)
     assert o.shape == (2, T, H, V) and state.lengths == (140, 200) and state.seen == 200 and state.pos.tolist() == [140, 200]
     for b, m in enumerate(lengths):
-        _check_step_rows(f"seq {b}: extend rows", o[b:b + 1], want[b][:, :m + T], m, dtype)
-        _check_state(state, b, m + T, q, k, v, mix, f"seq {b} after extend({T})")
-    o1 = _steps(q, k, v, mix, state, lengths, T, n)
+        check_step_rows(f"seq {b}: extend rows", o[b:b + 1], want[b][:, :m + T], m, dtype)
+        check_state(state, q, k, v, mix, f"seq {b} after extend({T})", b, m + T)
+    o1 = ragged_steps(q, k, v, mix, state, lengths, T, n)
     for b, m in enumerate(lengths):
-        _check_step_rows(f"seq {b}: step rows after extend", o1[b:b + 1], want[b], m + T, dtype)
+        check_step_rows(f"seq {b}: step rows after extend", o1[b:b + 1], want[b], m + T, dtype)
     assert state.pos.tolist() == list(state.lengths) == [145, 205]
 
 

@@ -8,17 +8,13 @@ import functools
 import pytest
 import torch
 
-from gpu_util import DEV, CAUSAL_TOL, TOL, check, poison, _fla_layer
+from decode_util import (ACCEPT, COUNTS, DRAFTS, NAN, SHAPE_IDS, SHAPES, SPEC_CAP, SPEC_L, SPEC_T, SPEC_TABLE, close_or_zero, layer_inputs,
+                         oracle_state, padding_is_zero, ragged_start, same_seq_state, table_inputs, unchanged, window)
+from gpu_util import DEV, CAUSAL_TOL, TOL, check, launches, poison, _fla_layer
 from oracle import mhla_oracle as orc
-from test_extend_cpu import oracle_state
-from test_extend_ragged_cpu import table_inputs, window
-from test_gpu_causal_extend import _close, _launches
-from test_gpu_causal_extend_ragged import SHAPES, SHAPE_IDS, _padding_is_zero, _same_seq_state, _start, _unchanged
-from test_speculative_cpu import ACCEPT, COUNTS, DRAFTS, SPEC_CAP, SPEC_L, SPEC_T, SPEC_TABLE
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
 B = len(SPEC_TABLE)
 # other accepted counts with a chunk closing somewhere, as in ACCEPT: the commit's launches must not depend on the counts
 ACCEPT2 = (10, 0, 9, 1, 0, 0, 1, 130, 3, 1, 0, 64)
@@ -37,7 +33,7 @@ def _batch(dtype, H, K, V, left_padded):
 def _state(hist, mix, cap=SPEC_CAP, table=DRAFTS):
     """The ragged state before the verify, with NaN in every row of S at or beyond each sequence's finished chunks: a read of an
     unfinished row shows."""
-    state = _start(table, hist, mix, cap)
+    state = ragged_start(table, hist, mix, cap)
     for b, (p, _) in enumerate(table):
         state.S[b, :, p // 64:] = NAN
     return state
@@ -86,7 +82,7 @@ def _same_as_extended(state, ref, before, accept):
     assert state.seen == max(state.lengths) and not state.stale
     assert torch.equal(state.pos, ref.pos) and state.pos.tolist() == list(state.lengths)
     for b, n in enumerate(state.lengths):
-        _same_seq_state(f"sequence {b} (accepted {accept[b]})", state, b, ref, b, n)
+        same_seq_state(f"sequence {b} (accepted {accept[b]})", state, b, ref, b, n)
 
 
 @pytest.mark.parametrize("left_padded", [False, True], ids=["right-padded", "left-padded"])
@@ -105,7 +101,7 @@ def test_verify_rows_and_the_state_it_leaves(shape, left_padded):
     _verify_left_the_state(state, before)
     o_ext = mhla_amd.mhla_causal_extend(q, k, v, md, before.clone(), counts=COUNTS, left_padded=left_padded)
     assert torch.equal(o, o_ext), f"rows differ from mhla_causal_extend (max {(o.float() - o_ext.float()).abs().max().item():.3e})"
-    _padding_is_zero(o, COUNTS, left_padded)
+    padding_is_zero(o, COUNTS, left_padded)
     for b, (p, n) in enumerate(DRAFTS):
         if n:
             check(f"sequence {b} (pos {p}, n {n}): rows", o[b:b + 1, window(SPEC_T, n, left_padded)], want[b], CAUSAL_TOL[dtype])
@@ -130,7 +126,7 @@ def test_commit_is_the_extend_by_the_accepted_prefix(shape, left_padded):
         nfull = (p + a) // 64
         ref = oracle_state(hist[b][1].float(), hist[b][2].float(), mix, p + a, SPEC_CAP)
         for part, got, r in (("S", state.S[b:b + 1, :, :nfull], ref[0][:, :, :nfull]), ("P", state.P[b:b + 1], ref[1]), ("Cur", state.Cur[b:b + 1], ref[2])):
-            _close(f"{name}: {part} vs the oracle", got, r, tol)
+            close_or_zero(f"{name}: {part} vs the oracle", got, r, tol)
         if (p + a) % 64 == 0:
             assert float(state.Cur[b].abs().max()) == 0.0, f"{name}: Cur on a boundary must be exactly 0"
         if p + a == 64 * SPEC_CAP:
@@ -141,7 +137,7 @@ def test_commit_is_the_extend_by_the_accepted_prefix(shape, left_padded):
     # nothing accepted anywhere: nothing is launched, bit for bit as before
     again = before.clone()
     _, draft = _verify(q, k, v, md, again, COUNTS, left_padded)
-    ran = _launches(lambda: mhla_amd.mhla_causal_commit(draft, md, again, (0,) * B))
+    ran = launches(lambda: mhla_amd.mhla_causal_commit(draft, md, again, (0,) * B))
     assert not ran, ran
     _verify_left_the_state(again, before)
 
@@ -198,7 +194,7 @@ def test_scribbles_on_unfinished_rows_are_harmless():
     ref = mhla_amd.mhla_causal_state(k_all.to(DEV), v_all.to(DEV), md, lengths=total, capacity_chunks=cap)
     for b, n in enumerate(total):
         for part, x, y in (("S", state.S[b, :, :n // 64], ref.S[b, :, :n // 64]), ("P", state.P[b], ref.P[b]), ("Cur", state.Cur[b], ref.Cur[b])):
-            _close(f"sequence {b}: {part} vs one prefill of the sequence really taken", x, y.cpu(), TOL[torch.float32])
+            close_or_zero(f"sequence {b}: {part} vs one prefill of the sequence really taken", x, y.cpu(), TOL[torch.float32])
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
@@ -224,7 +220,7 @@ def test_epilogue_and_strided_views(dtype):
         _verify_left_the_state(state, before)
         y_ext = mhla_amd.mhla_causal_extend(qv, kv, vv, md, before.clone(), counts=COUNTS, left_padded=left_padded, **kw)
         assert torch.equal(y, y_ext), f"{sorted(kw)}: rows differ from mhla_causal_extend"
-        _padding_is_zero(y, COUNTS, left_padded)
+        padding_is_zero(y, COUNTS, left_padded)
     assert draft.k.data_ptr() == kv.data_ptr() and draft.v.data_ptr() == vv.data_ptr()      # references, not copies
     mhla_amd.mhla_causal_commit(draft, md, state, ACCEPT)
     _same_as_extended(state, _extended(q, k, v, md, before, COUNTS, ACCEPT, left_padded), before, ACCEPT)
@@ -240,20 +236,20 @@ def test_launch_counts():
     state = _state(hist, mix)
     before = state.clone()
     ext = before.clone()
-    ran_ext = _launches(lambda: mhla_amd.mhla_causal_extend(q, k, v, md, ext, counts=COUNTS))
+    ran_ext = launches(lambda: mhla_amd.mhla_causal_extend(q, k, v, md, ext, counts=COUNTS))
     drafts = []
-    ran = _launches(lambda: drafts.append(_verify(q, k, v, md, state, COUNTS, False)[1]))
+    ran = launches(lambda: drafts.append(_verify(q, k, v, md, state, COUNTS, False)[1]))
     assert ran == ran_ext and sum(ran.values()) == 6 and ran["k_cs_step_finish_ragged"] == 1, (ran, ran_ext)
     counts = {}
     for name, accept in (("table", ACCEPT), ("other", ACCEPT2), ("open", ACCEPT_OPEN)):
         st = before.clone()
-        counts[name] = _launches(lambda: mhla_amd.mhla_causal_commit(drafts[0], md, st, accept))
+        counts[name] = launches(lambda: mhla_amd.mhla_causal_commit(drafts[0], md, st, accept))
         assert not any(n.startswith(("k_cx_out", "k_cs_step")) for n in counts[name]), counts[name]
         assert counts[name]["k_cx_advance"] == 1 and sum(counts[name].values()) <= 4, counts[name]
         _same_as_extended(st, _extended(q, k, v, md, before, COUNTS, accept, False), before, accept)
     assert counts["table"] == counts["other"] and sum(counts["table"].values()) == 4, counts
     assert counts["open"] == {"k_cx_xty_acc_ragged": 1, "k_cx_advance": 1}, counts
-    idle = _launches(lambda: _verify(q, k, v, md, state, (0,) * B, False))
+    idle = launches(lambda: _verify(q, k, v, md, state, (0,) * B, False))
     assert not idle, idle
 
 
@@ -290,11 +286,11 @@ def test_large_batches_are_sliced(monkeypatch):
     monkeypatch.setattr(ops, "_MAX_GRID_BH", 5 * H)
     sliced = s0.clone()
     got = []
-    ran = _launches(lambda: got.extend(_verify(q, k, v, md, sliced, COUNTS, True)))
+    ran = launches(lambda: got.extend(_verify(q, k, v, md, sliced, COUNTS, True)))
     assert ran["k_cs_step_finish_ragged"] == 3, ran      # slices of 5, 5 and 2 sequences
     assert torch.equal(got[0], o_whole)
     _verify_left_the_state(sliced, s0)
-    ran = _launches(lambda: mhla_amd.mhla_causal_commit(got[1], md, sliced, ACCEPT))
+    ran = launches(lambda: mhla_amd.mhla_causal_commit(got[1], md, sliced, ACCEPT))
     assert ran["k_cx_advance"] == 3, ran
     _same_as_extended(sliced, whole, s0, ACCEPT)
 
@@ -305,19 +301,19 @@ def test_refusals_behind_the_device_check_leave_the_state_untouched(monkeypatch)
     dtype, H, K, V = SHAPES[0]
     hist, q, k, v, mix, _ = _batch(dtype, H, K, V, False)
     md = mix.to(DEV)
-    state = _start(DRAFTS, hist, mix, SPEC_CAP)
+    state = ragged_start(DRAFTS, hist, mix, SPEC_CAP)
     keep = state.clone()
     ver = lambda counts, m=md: mhla_amd.mhla_causal_verify(q, k, v, m, state, counts=counts)
     with pytest.raises(IndexError, match=r"sequences \[11\].*the state holds only 4"):
         ver([0] * 11 + [65])                           # sequence 11 is at 192 of 256: the whole draft must fit
     with pytest.raises(IndexError, match=r"mixing_matrix has only 1 rows"):
         ver([1] * B, m=md[:1, :1].contiguous())
-    _unchanged(state, keep)
+    unchanged(state, keep)
     monkeypatch.setattr(ops, "EXTEND_WS_CAP_BYTES", 1)
     with pytest.raises(ValueError, match="EXTEND_WS_CAP_BYTES"):
         ver(COUNTS)
     monkeypatch.undo()
-    _unchanged(state, keep)
+    unchanged(state, keep)
     _, draft = _verify(q, k, v, md, state, COUNTS, False)
     with pytest.raises(ValueError, match="must be in 0"):
         mhla_amd.mhla_causal_commit(draft, md, state, [11] + [0] * (B - 1))
@@ -333,7 +329,7 @@ def test_refusals_behind_the_device_check_leave_the_state_untouched(monkeypatch)
     after = moved.clone()
     with pytest.raises(ValueError, match="moved since the verify"):
         mhla_amd.mhla_causal_commit(draft, md, moved, ACCEPT)
-    _unchanged(moved, after)
+    unchanged(moved, after)
 
     # the raw entry points
     lib = _lib.load()
@@ -371,7 +367,7 @@ def test_refusals_behind_the_device_check_leave_the_state_untouched(monkeypatch)
     assert raw_commit(max_end=257) == EINVAL and b"max_end=257" in lib.mhla_last_error()
     assert raw_commit(max_later=1, any_close=0) == EINVAL and b"without any_close" in lib.mhla_last_error()
     assert raw_commit(accept=None) == EINVAL and b"accept_dev" in lib.mhla_last_error()
-    _unchanged(state, keep)
+    unchanged(state, keep)
     # defence: host values that vouch for less than the arrays hold skip those sequences -- state and position untouched
     assert raw_commit(max_end=100, max_later=0, any_close=0) == 0
     torch.cuda.synchronize()
@@ -383,10 +379,6 @@ def test_refusals_behind_the_device_check_leave_the_state_untouched(monkeypatch)
             assert torch.equal(state.P[b], keep.P[b]) and torch.equal(state.Cur[b], keep.Cur[b]) and torch.equal(state.S[b], keep.S[b])
 
 
-def _layer_inputs(nb, T, seed):
-    return torch.randn(nb, T, 256, generator=torch.Generator().manual_seed(seed))
-
-
 @pytest.mark.parametrize("opts", [{}, {"use_output_gate": False}], ids=["default", "no-output-gate"])
 def test_fla_layer_speculative_then_commit(opts):
     """A speculative call, `cache.commit(accept)`, a normal call: per sequence, that sequence alone fed its accepted tokens and then
@@ -394,7 +386,7 @@ def test_fla_layer_speculative_then_commit(opts):
     from mhla_amd import modules
     m = _fla_layer(**opts).to(DEV).eval()
     prompts, counts, accept, nxt, T, T2 = (70, 20, 64), (3, 70, 5), (2, 66, 0), (4, 1, 4), 70, 4
-    x0, x1, x2 = _layer_inputs(3, 70, 31).to(DEV), _layer_inputs(3, T, 32).to(DEV), _layer_inputs(3, T2, 33).to(DEV)
+    x0, x1, x2 = layer_inputs(3, 70, 31).to(DEV), layer_inputs(3, T, 32).to(DEV), layer_inputs(3, T2, 33).to(DEV)
     mask = torch.zeros(3, 70, dtype=torch.long, device=DEV)
     for b, n in enumerate(prompts):
         mask[b, 70 - n:] = 1
@@ -426,7 +418,7 @@ def test_fla_layer_speculative_then_commit(opts):
 def test_fla_layer_speculative_drafts_and_refusals():
     from mhla_amd import modules
     m = _fla_layer().to(DEV).eval()
-    x0, x1 = _layer_inputs(2, 10, 41).to(DEV), _layer_inputs(2, 4, 42).to(DEV)
+    x0, x1 = layer_inputs(2, 10, 41).to(DEV), layer_inputs(2, 4, 42).to(DEV)
     with torch.no_grad():
         with pytest.raises(NotImplementedError, match="empty cache"):
             m(x1, past_key_values=modules.DecodeCache(), use_cache=True, speculative=True)

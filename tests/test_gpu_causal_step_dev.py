@@ -11,10 +11,10 @@ import functools
 import pytest
 import torch
 
+from decode_util import check_state, check_step_rows, ragged_inputs, ragged_prefill, window_rows
 from gpu_util import DEV, CAUSAL_TOL, TOL, check, poison, _fla_layer
 from neighbour_refs import featmap_rotary_ref
 from oracle import mhla_oracle as orc
-from test_gpu_causal_ragged import _check_state, _check_step_rows, _prefill, _seqs, _window
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +32,7 @@ def _dev_and_ragged(dtype, K, V, epilogue):
     both states, the inputs, the per-sequence oracle, the epilogue's gate and weight).  Run once per case, shared by the tests."""
     import mhla_amd
     H = 2
-    q, k, v, mix, want = _seqs(LENGTHS, NSTEP, H, K, V, CAP, dtype)
+    q, k, v, mix, want = ragged_inputs(LENGTHS, NSTEP, H, K, V, CAP, dtype)
     qd, kd, vd, md = (t.to(DEV) for t in (q, k, v, mix))
     kw, g, w = {}, None, None
     if epilogue:
@@ -41,9 +41,9 @@ def _dev_and_ragged(dtype, K, V, epilogue):
         w = torch.rand(V, generator=gen) + 0.5
         kw = dict(norm_weight=w.to(DEV), norm_eps=1e-5)
     poison()
-    _, state = _prefill(qd, kd, vd, md, LENGTHS, "left_padded", CAP)
+    _, state = ragged_prefill(qd, kd, vd, md, LENGTHS, "left_padded", CAP)
     a, b = state.clone(), state.clone()
-    qs, ks, vs = (_window(t, LENGTHS, 0, NSTEP) for t in (qd, kd, vd))
+    qs, ks, vs = (window_rows(t, LENGTHS, 0, NSTEP) for t in (qd, kd, vd))
     rows_dev, rows_rag = [], []
     for t in range(NSTEP):
         tok = (qs[:, t:t + 1], ks[:, t:t + 1], vs[:, t:t + 1])
@@ -79,11 +79,11 @@ def test_rows_and_state_match_the_oracle(case):
     rows_dev, _, a, _, (qd, kd, vd, md), want, g, w = _dev_and_ragged(*case)
     for s, m in enumerate(LENGTHS):
         if g is None:
-            _check_step_rows(f"seq {s}: rows", rows_dev[s:s + 1], want[s], m, dtype)
+            check_step_rows(f"seq {s}: rows", rows_dev[s:s + 1], want[s], m, dtype)
         else:
             y_ref = orc.rms_norm_swish_gate(want[s][:, m:], g[s:s + 1].float(), w, 1e-5)
             check(f"seq {s}: y", rows_dev[s:s + 1], y_ref, CAUSAL_TOL[dtype])
-        _check_state(a, s, m + NSTEP, qd, kd, vd, md, f"seq {s} after {NSTEP} steps")
+        check_state(a, qd, kd, vd, md, f"seq {s} after {NSTEP} steps", s, m + NSTEP)
 
 
 def _tables(rows, K, dtype, seed=5):
@@ -130,9 +130,9 @@ def test_fused_prologue(fmap, K, V, dtype):
     xqd, xkd, vd, md, cd, sd, qd, kd = (t.to(DEV) for t in (xq, xk, v, mix, cos, sin, q, k))
     assert cd.shape == (64 * CAP, K // 2)
     poison()
-    _, state = _prefill(qd, kd, vd, md, LENGTHS, "left_padded", CAP)
+    _, state = ragged_prefill(qd, kd, vd, md, LENGTHS, "left_padded", CAP)
     a, b = state.clone(), state.clone()
-    xqs, xks, vs = (_window(t, LENGTHS, 0, NSTEP) for t in (xqd, xkd, vd))
+    xqs, xks, vs = (window_rows(t, LENGTHS, 0, NSTEP) for t in (xqd, xkd, vd))
     rows, rows_unfused = [], []
     for t in range(NSTEP):
         rows.append(mhla_amd.mhla_causal_step_dev(xqs[:, t:t + 1], xks[:, t:t + 1], vs[:, t:t + 1], md, a, feature_map=fmap, rotary=(cd, sd)))
@@ -142,7 +142,7 @@ def test_fused_prologue(fmap, K, V, dtype):
     print(f"prologue {fmap} K={K} {dtype}: rows bit-equal to the unfused chain: {torch.equal(rows, rows_unfused)}; state bit-equal: {same}")
     assert a.pos.tolist() == b.pos.tolist() == [m + NSTEP for m in LENGTHS]
     for s, m in enumerate(LENGTHS):
-        _check_step_rows(f"seq {s}: rows", rows[s:s + 1], want[s], m, dtype)
+        check_step_rows(f"seq {s}: rows", rows[s:s + 1], want[s], m, dtype)
     for n in ("S", "P", "Cur"):
         x, y = getattr(a, n), getattr(b, n)
         if float(y.abs().max()) == 0.0:
@@ -156,12 +156,12 @@ def test_capacity_freezes_a_sequence():
     step 2, `full` set -- while the others step on; `sync()` reports it after refreshing the mirror."""
     import mhla_amd
     dtype, H, K, V, lengths, cap, L, n = torch.float32, 2, 16, 24, (126, 120, 0), 2, 3, 4
-    q, k, v, mix, want = _seqs(lengths, n, H, K, V, L, dtype)
+    q, k, v, mix, want = ragged_inputs(lengths, n, H, K, V, L, dtype)
     qd, kd, vd, md = (t.to(DEV) for t in (q, k, v, mix))
     poison()
-    _, state = _prefill(qd, kd, vd, md, lengths, "left_padded", cap)
+    _, state = ragged_prefill(qd, kd, vd, md, lengths, "left_padded", cap)
     assert state.capacity_chunks == cap
-    qs, ks, vs = (_window(t, lengths, 0, n) for t in (qd, kd, vd))
+    qs, ks, vs = (window_rows(t, lengths, 0, n) for t in (qd, kd, vd))
     rows, snap = [], None
     for t in range(n):
         poison()
@@ -175,11 +175,11 @@ def test_capacity_freezes_a_sequence():
     for name in ("S", "P", "Cur"):
         assert torch.equal(getattr(state, name)[0], getattr(snap, name)[0]), f"{name} of the frozen sequence moved"
     assert state.pos.tolist() == [128, 124, 4] and state.full.tolist() == [1, 0, 0]
-    _check_step_rows("seq 0: rows before the capacity", rows[0:1, :2], want[0][:, :128], 126, dtype)
-    _check_state(state, 0, 128, qd, kd, vd, md, "seq 0 at the capacity")
+    check_step_rows("seq 0: rows before the capacity", rows[0:1, :2], want[0][:, :128], 126, dtype)
+    check_state(state, qd, kd, vd, md, "seq 0 at the capacity", 0, 128)
     for s in (1, 2):
-        _check_step_rows(f"seq {s}: rows", rows[s:s + 1], want[s], lengths[s], dtype)
-        _check_state(state, s, lengths[s] + n, qd, kd, vd, md, f"seq {s} after {n} steps")
+        check_step_rows(f"seq {s}: rows", rows[s:s + 1], want[s], lengths[s], dtype)
+        check_state(state, qd, kd, vd, md, f"seq {s} after {n} steps", s, lengths[s] + n)
     assert state.stale and state.lengths == lengths
     with pytest.raises(ValueError, match=r"sync\(\)"):
         mhla_amd.mhla_causal_step(qs[:, :1], ks[:, :1], vs[:, :1], md, state)
@@ -199,8 +199,8 @@ def test_graph_replay_gives_the_eager_bits():
     g = torch.randn(len(lengths), n, H, V, generator=gen).to(dtype)
     w = torch.rand(V, generator=gen) + 0.5
     gd, wd = g.to(DEV), w.to(DEV)
-    _, state = _prefill(qd, kd, vd, md, lengths, "left_padded", cap)
-    xqs, xks, vs = (_window(t, lengths, 0, n) for t in (xqd, xkd, vd))
+    _, state = ragged_prefill(qd, kd, vd, md, lengths, "left_padded", cap)
+    xqs, xks, vs = (window_rows(t, lengths, 0, n) for t in (xqd, xkd, vd))
     step = lambda tq, tk, tv, tg, st: mhla_amd.mhla_causal_step_dev(tq, tk, tv, md, st, feature_map=fmap, rotary=(cd, sd), gate=tg,
                                                                     norm_weight=wd, norm_eps=1e-5)
     eager, replayed = state.clone(), state.clone()

@@ -16,9 +16,9 @@ CAUSAL_CHUNK_TOL_H16 was derived with, so the constant holds here as it stands."
 import pytest
 import torch
 
+from gpu_util import launches
 from test_gpu_causal import run_causal
 from test_gpu_causal_varlen import run_varlen, tok4_walk
-from test_gpu_neighbours import _launches
 
 pytestmark = pytest.mark.gpu
 
@@ -63,7 +63,7 @@ def test_token_kernel_chunk_walk(B, cpw, groups, K, V, summaries):
     assert (T + 63) // 64 == N_CHUNKS and T % 64 == 5
     assert tok4_most(K, summaries) == 8 and tok4_walk(8, N_CHUNKS, B * H) == cpw, (tok4_most(K, summaries), tok4_walk(8, N_CHUNKS, B * H))
     assert walk_groups(N_CHUNKS, cpw) == groups
-    ran = _launches(lambda: run_causal(B, T, H, K, V, N_CHUNKS, torch.bfloat16, seed=T + K, summaries=summaries))
+    ran = launches(lambda: run_causal(B, T, H, K, V, N_CHUNKS, torch.bfloat16, seed=T + K, summaries=summaries))
     assert ran.get("k_csf_bwd_tok4") == 1, ran
 
 
@@ -71,7 +71,7 @@ def test_token_kernel_without_a_walk_at_the_same_shape():
     """K = 256 keeps one chunk per workgroup whatever B H is: the control of the cases above."""
     B, K, V, summaries = CONTROL
     assert tok4_most(K, summaries) == 1 and tok4_walk(tok4_most(K, summaries), N_CHUNKS, B * H) == 1
-    ran = _launches(lambda: run_causal(B, T, H, K, V, N_CHUNKS, torch.bfloat16, seed=T + K, summaries=summaries))
+    ran = launches(lambda: run_causal(B, T, H, K, V, N_CHUNKS, torch.bfloat16, seed=T + K, summaries=summaries))
     assert ran.get("k_csf_bwd_tok4") == 1, ran
 
 
@@ -82,5 +82,5 @@ def test_token_kernel_walks_eight_chunks_across_sequence_boundaries():
     cu, chunks = pack_cu()
     assert chunks == PACK_CHUNKS and mhla_amd.causal_varlen_plan(cu, "cpu").n_chunks == PACK_CHUNKS
     assert tok4_most(64, "tf32") == 8 and tok4_walk(8, PACK_CHUNKS, 1 * PACK_H) == 8
-    ran = _launches(lambda: run_varlen(cu, PACK_H, 64, 64, torch.bfloat16, seed=PACK_CHUNKS))
+    ran = launches(lambda: run_varlen(cu, PACK_H, 64, 64, torch.bfloat16, seed=PACK_CHUNKS))
     assert ran.get("k_csf_bwd_tok4<tab>") == 1, ran

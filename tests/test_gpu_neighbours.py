@@ -13,14 +13,13 @@ beyond the final rounding of fp64 at the largest row counts used here, so the re
 
 Not covered: the FORWARD grid caps of 2^20 workgroups (norm_fwd_grid) -- a second trip there needs over 4 M rows, too slow
 against a CPU reference."""
-import ctypes
 import functools
 
 import pytest
 import torch
 
 import neighbour_refs as nr
-from gpu_util import DEV, DW_TOL, TOL, check, poison
+from gpu_util import DEV, DW_TOL, TOL, check, launches, poison
 
 pytestmark = pytest.mark.gpu
 
@@ -48,22 +47,6 @@ def _f32tol(dtype):
 def _lib():
     from mhla_amd import _lib as L
     return L.load()
-
-
-def _launches(fn):
-    """Kernel launches of the library while `fn` runs: {name: count} (mhla_prof_*)."""
-    lib = _lib()
-    buf = ctypes.create_string_buffer(1 << 14)
-    torch.cuda.synchronize()
-    lib.mhla_prof_report(buf, len(buf))   # (clears records an earlier user may have left)
-    lib.mhla_prof_enable(1)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        lib.mhla_prof_enable(0)
-        lib.mhla_prof_report(buf, len(buf))
-    return {ln.rsplit(" ", 2)[0]: int(ln.rsplit(" ", 2)[1]) for ln in buf.value.decode().splitlines() if ln.strip()}
 
 
 # -------------------------------------------------------------------------------------------------
@@ -573,11 +556,11 @@ def _lepe_case(kind, geom, C, dtype, B=3, view="packed", seed=0, expect=None):
         dyd = _embed(dy, view)[0].detach()[sl]
     out = []
     poison()
-    ran = _launches(lambda: out.append(hip(buf[sl], wd, bd, ad)))
+    ran = launches(lambda: out.append(hip(buf[sl], wd, bd, ad)))
     got = out[0]
     assert got.dtype == dtype
     poison()
-    ran_b = _launches(lambda: got.backward(dyd))
+    ran_b = launches(lambda: got.backward(dyd))
     if expect:
         assert expect in ran and expect in ran_b, (expect, ran, ran_b)
         other = {"k_lepe2d": "k_lepe2d_run4", "k_lepe2d_run4": "k_lepe2d"}.get(expect)
@@ -673,9 +656,9 @@ def _nonfinite_case(kind, geom, C, dtype, marks, expect=None):
     for name, vv, dd in (("clean", v, dy), ("marked", vm, dym)):
         vd = _dev(vv)
         poison()
-        ran = _launches(lambda: res.__setitem__(name + " y", hip(vd, wd)))
+        ran = launches(lambda: res.__setitem__(name + " y", hip(vd, wd)))
         poison()
-        ran_b = _launches(lambda: res[name + " y"].backward(dd.to(DEV)))
+        ran_b = launches(lambda: res[name + " y"].backward(dd.to(DEV)))
         res[name + " dv"] = vd.grad
         if expect:
             assert expect in ran and expect in ran_b, (ran, ran_b)

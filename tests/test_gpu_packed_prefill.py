@@ -7,10 +7,9 @@ import functools
 import pytest
 import torch
 
-from gpu_util import DEV, CAUSAL_TOL, check, poison, _fla_layer
+from decode_util import check_state, check_step_rows, ragged_steps, signed_features
+from gpu_util import DEV, CAUSAL_TOL, check, launches, poison, _fla_layer
 from oracle import mhla_oracle as orc
-from test_gpu_causal_ragged import _steps, _check_state, _check_step_rows
-from test_gpu_neighbours import _launches
 
 pytestmark = pytest.mark.gpu
 
@@ -36,13 +35,13 @@ def _pack(x, lengths):
 
 @functools.lru_cache(maxsize=None)
 def _seqs(lengths, n, H, K, V, rows, dtype, seed=1234):
-    """As _seqs of test_gpu_causal_ragged.py makes them -- B sequences on timelines of their own, rows [0, lengths[b] + n] of q[b],
+    """As decode_util.ragged_inputs makes them -- B sequences on timelines of their own, rows [0, lengths[b] + n] of q[b],
     k[b], v[b], q and k with signs as roped feature maps have them, a random lower-triangular mix -- and the fp32 oracle of every
     sequence alone over its lengths[b] + n tokens (None for no token at all), computed once per case."""
     B, T = len(lengths), max(lengths) + n + 1
     g = torch.Generator().manual_seed(seed)
-    q = (torch.relu(torch.randn(B, T, H, K, generator=g)) * torch.sign(torch.randn(B, T, H, K, generator=g))).to(dtype)
-    k = (torch.relu(torch.randn(B, T, H, K, generator=g)) * torch.sign(torch.randn(B, T, H, K, generator=g))).to(dtype)
+    q = signed_features(g, B, T, H, K).to(dtype)
+    k = signed_features(g, B, T, H, K).to(dtype)
     v = torch.randn(B, T, H, V, generator=g).to(dtype)
     mix = torch.tril(torch.rand(rows, rows, generator=g).clamp(1e-5, 1))
     want = tuple(orc.causal_fwd(q[b:b + 1, :m + n].float(), k[b:b + 1, :m + n].float(), v[b:b + 1, :m + n].float(), mix) if m + n else None
@@ -101,7 +100,7 @@ def test_state_against_the_oracle(case):
     poison()
     state = mhla_amd.mhla_causal_state(_pack(k, PACK), _pack(v, PACK), mix, cu_seqlens=_cu(PACK), capacity_chunks=CAP)
     for b, m in enumerate(PACK):
-        _check_state(state, b, m, q, k, v, mix, f"seq {b} after the packed prefill({m})")
+        check_state(state, q, k, v, mix, f"seq {b} after the packed prefill({m})", b, m)
 
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
@@ -152,11 +151,11 @@ def test_prefill_rows_and_70_steps(case):
     for b, m in enumerate(lengths):
         if m:
             check(f"seq {b}: prefill rows", o[:, cu[b]:cu[b + 1]], want[b][:, :m], CAUSAL_TOL[dtype])
-    o1 = _steps(q, k, v, mix, state, lengths, 0, n)
-    o2 = _steps(q, k, v, mix, cat, lengths, 0, n)
+    o1 = ragged_steps(q, k, v, mix, state, lengths, 0, n)
+    o2 = ragged_steps(q, k, v, mix, cat, lengths, 0, n)
     assert state.lengths == tuple(m + n for m in lengths) and state.pos.tolist() == list(state.lengths)
     for b, m in enumerate(lengths):
-        _check_step_rows(f"seq {b}: step rows", o1[b:b + 1], want[b], m, dtype)
+        check_step_rows(f"seq {b}: step rows", o1[b:b + 1], want[b], m, dtype)
     assert torch.equal(o1, o2), "steps on the packed state differ from the steps on CausalState.cat of the prefills alone"
     assert torch.equal(state.P, cat.P) and torch.equal(state.Cur, cat.Cur)
     for b, m in enumerate(lengths):
@@ -168,7 +167,7 @@ def test_launches_do_not_grow_with_the_sequences():
     import mhla_amd
     dtype, H, K, V = CASES[1]
     q, k, v, mix, _ = _case(*CASES[1])
-    count = lambda fn: sum(_launches(fn).values())
+    count = lambda fn: sum(launches(fn).values())
     two = (65, 191)
     k2, v2 = _pack(k[[1, 4]], two), _pack(v[[1, 4]], two)
     p2, p6 = mhla_amd.causal_varlen_plan(_cu(two), DEV), mhla_amd.causal_varlen_plan(_cu(PACK), DEV)

@@ -1,51 +1,14 @@
 """Verifying a draft without committing it and committing an accepted prefix (mhla_causal_verify / mhla_causal_commit), the parts
-that need no GPU: the restatement the GPU tests import (`verify_ref`, `commit_ref`, built from test_extend_ragged_cpu.extend_ragged_ref)
-held to the oracle on the table of (pos, draft, accepted), the validation that runs before the device check, and the bookkeeping of
+that need no GPU: the restatement in decode_util (`verify_ref`, `commit_ref`, built from `extend_ragged_ref`) held to the oracle
+on the table of (pos, draft, accepted), the validation that runs before the device check, and the bookkeeping of
 `DecodeCache.commit` / `discard`."""
 import pytest
 import torch
 
 from conftest import rel_err
+from decode_util import (ACCEPT, COUNTS, DRAFTS, SPEC_CAP, SPEC_T, SPEC_L, SPEC_TABLE, commit_ref, oracle_state, start_state, table_inputs,
+                         verify_ref, window)
 from oracle import mhla_oracle as orc
-from test_extend_cpu import oracle_state
-from test_extend_ragged_cpu import extend_ragged_ref, start_state, table_inputs, window
-
-# (pos, n, accept) of one batch, capacity 4 chunks, padded width 130, a 5 x 5 matrix
-SPEC_TABLE = [(60, 10, 0),     # all rejected after the verify crossed a boundary
-              (60, 10, 3),     # accepted inside the open chunk
-              (60, 10, 4),     # accepted exactly closes the chunk
-              (60, 10, 10),
-              (0, 0, 0),       # idle
-              (63, 1, 1),
-              (63, 1, 0),
-              (64, 130, 70),   # whole chunks, ends inside a later one
-              (5, 3, 2),
-              (0, 70, 64),     # an empty state
-              (192, 64, 64),   # fills the state: P = Cur = 0
-              (192, 64, 63)]
-SPEC_T, SPEC_CAP, SPEC_L = 130, 4, 5
-DRAFTS = tuple((p, n) for p, n, _ in SPEC_TABLE)
-COUNTS = tuple(n for _, n, _ in SPEC_TABLE)
-ACCEPT = tuple(a for _, _, a in SPEC_TABLE)
-
-
-def verify_ref(state, q, k, v, mix, counts, left_padded=False, scale=None):
-    """(the rows `extend_ragged_ref` gives, the INPUT state): a verify commits nothing."""
-    return extend_ragged_ref(state, q, k, v, mix, counts, left_padded, scale)[0], state
-
-
-def commit_ref(state, k, v, mix, counts, accept, left_padded=False):
-    """The state after the first accept[b] rows of every sequence's counts[b]-row window: `extend_ragged_ref(counts=accept)` on the
-    accepted rows, moved to where a window of accept[b] rows lies."""
-    B, T = k.shape[:2]
-    ka, va = torch.zeros_like(k), torch.zeros_like(v)
-    for b, (n, a) in enumerate(zip(counts, accept)):
-        assert 0 <= a <= n
-        src = window(T, n, left_padded)
-        dst = window(T, a, left_padded)
-        ka[b, dst], va[b, dst] = k[b, src.start:src.start + a], v[b, src.start:src.start + a]
-    return extend_ragged_ref(state, torch.zeros_like(ka), ka, va, mix, accept, left_padded)[1]
-
 
 @pytest.mark.parametrize("left_padded", [False, True], ids=["right-padded", "left-padded"])
 def test_verify_and_commit_refs_reproduce_the_oracle(left_padded):
