@@ -343,6 +343,29 @@ int mhla_causal_varlen_bwd(mhla_view q, mhla_view k, mhla_view v, const float* m
                            int B, int T, int H, int K, int V, int chunk, int n_chunks, const int* chunk_tab_dev, float scale, int dtype,
                            unsigned flags, void* stream);
 
+/* Grouped-query heads in the forward (added without a change of any existing signature or behaviour: MHLA_ABI_VERSION stays 9).
+ * Each call is its namesake with one more integer, Hkv, after H: q, out, gate, y have H heads, k [B,T,Hkv,K] and v [B,T,Hkv,V] have
+ * Hkv, H = G Hkv, and query head h reads k/v head h / G (the layer's repeat order).  The result is, bit for bit, the namesake's on
+ * k, v repeated G times per head: the chunk summaries and their prefix mixes are formed once per k/v head -- the same sums in the
+ * same order -- and the output kernel's arithmetic per query head is the namesake's.  MHLA_EINVAL for Hkv < 1 or H % Hkv != 0,
+ * MHLA_ENOTSUP for G > 8; B * H <= 65535 counts query heads; every other check as the namesake.  Hkv == H makes the namesake's own
+ * launches.  Workspace: exactly mhla_causal_fwd_ws_bytes(B, T, Hkv, ...) / mhla_causal_varlen_fwd_ws_bytes(B, T, Hkv, ...) -- 1 / G
+ * of the namesake's -- and mhla_causal_normgate_fusable / mhla_causal_varlen_normgate_fusable answer unchanged (they take no head
+ * count).  There is no grouped backward: mhla_causal_bwd takes k, v on H heads, and a workspace these calls filled is not a
+ * `fwd_ws` for it. */
+int mhla_causal_fwd_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out, void* ws, size_t ws_bytes,
+                        int B, int T, int H, int Hkv, int K, int V, int chunk, float scale, int dtype, unsigned flags, void* stream);
+int mhla_causal_normgate_fwd_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out, mhla_view gate,
+                                 const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int T, int H,
+                                 int Hkv, int K, int V, int chunk, float scale, int dtype, unsigned flags, void* stream);
+int mhla_causal_varlen_fwd_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out, void* ws,
+                               size_t ws_bytes, int B, int T, int H, int Hkv, int K, int V, int chunk, int n_chunks,
+                               const int* chunk_tab_dev, float scale, int dtype, unsigned flags, void* stream);
+int mhla_causal_varlen_normgate_fwd_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out,
+                                        mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes,
+                                        int B, int T, int H, int Hkv, int K, int V, int chunk, int n_chunks, const int* chunk_tab_dev,
+                                        float scale, int dtype, unsigned flags, void* stream);
+
 /* Decoding (generation): the state of a sequence and the single-token step.  Row t of the forward above depends on the
  * tokens <= t only, so a step reproduces it from, per (b, h), in fp32 whatever the tensor dtype:
  *   S   [B][H][cap_chunks][K][V]  K_j^T V_j of every finished chunk j (mix[i][j] differs per row i: all are kept --

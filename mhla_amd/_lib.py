@@ -125,6 +125,15 @@ SIGNATURES = {
     "mhla_causal_verify_ragged_gqa": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                               c_int64, c_int, c_int, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int,
                                               c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "mhla_causal_fwd_gqa": (c_int, [View, View, View, c_void_p, c_int, View, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
+                                    c_int, c_int, c_int, c_float, c_int, c_uint, c_void_p]),
+    "mhla_causal_normgate_fwd_gqa": (c_int, [View, View, View, c_void_p, c_int, View, View, c_void_p, c_float, View, c_void_p,
+                                             c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_uint, c_void_p]),
+    "mhla_causal_varlen_fwd_gqa": (c_int, [View, View, View, c_void_p, c_int, View, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
+                                           c_int, c_int, c_int, c_int, c_void_p, c_float, c_int, c_uint, c_void_p]),
+    "mhla_causal_varlen_normgate_fwd_gqa": (c_int, [View, View, View, c_void_p, c_int, View, View, c_void_p, c_float, View, c_void_p,
+                                                    c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_float,
+                                                    c_int, c_uint, c_void_p]),
     "mhla_featmap_rotary": (c_int, [View,View, c_void_p, c_void_p, c_int64, c_int64, View, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_void_p]),
     "mhla_lepe2d": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,

@@ -6,6 +6,7 @@
 #include "causal.hpp"
 #include "causal_bf16.hpp"
 #include "causal_mix.hpp"
+#include "capi_causal_gqa.hpp"
 
 #include <string>
 
@@ -143,11 +144,13 @@ int cs_mix_fwd(const float* mix, int ldmix, const uint16_t* S, uint16_t* P, int 
 template <int HL>
 int cs_fwd16(const mhla_view& q, const mhla_view& k, const mhla_view& v, const float* mix, int ldmix, const mhla_mview& out,
              const CsWs& w, int B, int T, int H, int K, int V, int n, float scale, hipStream_t st, bool epi, const float* nw,
-             float neps, const mhla_view& gate, const mhla_mview& y, const cs_tab_t* tab) {
+             float neps, const mhla_view& gate, const mhla_mview& y, const cs_tab_t* tab, int Hkv) {
+    // Hkv: the heads of k and v (grouped-query heads: H = G Hkv) -- the summaries and their mixes exist once per k/v head
     const long E = (long)K * V;
-    RC(cs_state16<HL>(k, v, (uint16_t*)w.S, 1.f, B, T, H, n, K, V, st, tab));
-    RC(cs_mix_fwd<HL>(mix, ldmix, (const uint16_t*)w.S, (uint16_t*)w.P, B * H, n, E, st));
+    RC(cs_state16<HL>(k, v, (uint16_t*)w.S, 1.f, B, T, Hkv, n, K, V, st, tab));
+    RC(cs_mix_fwd<HL>(mix, ldmix, (const uint16_t*)w.S, (uint16_t*)w.P, B * Hkv, n, E, st));
     CsOutArgs o{cv(q), cv(k), cv(v), cmv(out), mix, ldmix, w.P, H, n, K, V, (long)T, scale, cmv(y), cv(gate), nw, neps};
+    if (Hkv != H) return cs_out16_gqa(HL, o, H / Hkv, B, epi, st, tab);
     // V slices per workgroup: the largest of 4, 3, 2, 1 that divides V / 64 (the fused epilogue owns the head: V / 64 <= 4); the
     // more slices, the fewer times a chunk's Q and K rows and its score tile are fetched / formed
     const int nvs = V / 64, nv = nvs % 4 == 0 ? 4 : nvs % 3 == 0 ? 3 : nvs % 2 == 0 ? 2 : 1;
@@ -213,9 +216,14 @@ int cs_bwd16(const mhla_view& q, const mhla_view& k, const mhla_view& v, const f
 
 int cs_fwd_impl(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out, void* ws,
                 size_t ws_bytes, int B, int T, int H, int K, int V, int chunk, float scale, int dtype, unsigned flags, void* stream,
-                bool epi, const float* nw, float neps, mhla_view gate, mhla_mview y, int n_chunks = 0, const int* chunk_tab = nullptr) {
+                bool epi, const float* nw, float neps, mhla_view gate, mhla_mview y, int n_chunks = 0, const int* chunk_tab = nullptr,
+                int Hkv = 0) {
     // chunk_tab non-null: packed sequences, n_chunks rows of the table; null: the uniform call, ceil(T / chunk) chunks
+    // Hkv: 0, or the heads of k and v of a grouped-query call (mhla_causal_*_fwd_gqa; Hkv == H: the plain launches)
     RC(cs_check(B, T, H, K, V, chunk, dtype, flags));
+    if (!Hkv) Hkv = H;
+    if (Hkv < 1 || H % Hkv) return fail(MHLA_EINVAL, "H=%d query heads must be a multiple of Hkv=%d k/v heads", H, Hkv);
+    if (H / Hkv > CS_GQA_MAX) return fail(MHLA_ENOTSUP, "H=%d query heads on Hkv=%d k/v heads: at most %d per k/v head", H, Hkv, CS_GQA_MAX);
     if (chunk_tab) RC(cs_check_tab(T, chunk, n_chunks, chunk_tab));
     const cs_tab_t* tab = (const cs_tab_t*)chunk_tab;
     const int n = tab ? n_chunks : cs_chunks(T, chunk);
@@ -233,21 +241,22 @@ int cs_fwd_impl(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldm
     if (!mix || ldmix < n) return fail(MHLA_EINVAL, "mix null or ldmix=%d < n=%d chunks (T=%d)", ldmix, n, T);
     if (path.pipe16 && !(view_ok16(q) && view_ok16(k) && view_ok16(v) && (epi || view_ok16m(out))))
         return fail(MHLA_EINVAL, "bf16 tensors with K, V multiples of 64 must be 16-byte aligned views (strides multiples of 8)");
-    const CsWs w = cs_carve(ws, B, n, H, K, V, chunk, path);
+    const CsWs w = cs_carve(ws, B, n, Hkv, K, V, chunk, path);
     if (!ws || ws_bytes < w.total_fwd) return fail(MHLA_EINVAL, "workspace too small: %zu < %zu bytes", ws_bytes, w.total_fwd);
     if (((uintptr_t)ws) % 16) return fail(MHLA_EINVAL, "workspace not 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if (path.pipe16)
-        return path.hl == 2 ? cs_fwd16<2>(q, k, v, mix, ldmix, out, w, B, T, H, K, V, n, scale, st, epi, nw, neps, gate, y, tab)
-             : path.hl == 1 ? cs_fwd16<1>(q, k, v, mix, ldmix, out, w, B, T, H, K, V, n, scale, st, epi, nw, neps, gate, y, tab)
-                            : cs_fwd16<0>(q, k, v, mix, ldmix, out, w, B, T, H, K, V, n, scale, st, epi, nw, neps, gate, y, tab);
+        return path.hl == 2 ? cs_fwd16<2>(q, k, v, mix, ldmix, out, w, B, T, H, K, V, n, scale, st, epi, nw, neps, gate, y, tab, Hkv)
+             : path.hl == 1 ? cs_fwd16<1>(q, k, v, mix, ldmix, out, w, B, T, H, K, V, n, scale, st, epi, nw, neps, gate, y, tab, Hkv)
+                            : cs_fwd16<0>(q, k, v, mix, ldmix, out, w, B, T, H, K, V, n, scale, st, epi, nw, neps, gate, y, tab, Hkv);
     const long E = (long)K * V;
     DISPATCH_T(dtype, {
-        RC(cs_xty<ET>(k, v, w.S, 1.f, B, T, H, n, K, V, st, tab));
+        RC(cs_xty<ET>(k, v, w.S, 1.f, B, T, Hkv, n, K, V, st, tab));
         MixArgs m{mix, ldmix, w.S, w.P, n, E};
-        dim3 mgrid((unsigned)((m.E + MIX_TE - 1) / MIX_TE), (n + MIX_TI - 1) / MIX_TI, B * H);
+        dim3 mgrid((unsigned)((m.E + MIX_TE - 1) / MIX_TE), (n + MIX_TI - 1) / MIX_TI, B * Hkv);
         RC(launch(k_mix<0, 1>, mgrid, dim3(NTHREADS), MIX_SMEM_FLOATS * 4, st, "k_mix<0,1>", m));
         CsOutArgs o{cv(q), cv(k), cv(v), cmv(out), mix, ldmix, w.P, H, n, K, V, (long)T, scale, cmv(out), cv(mhla_view{nullptr, 0, 0, 0}), nullptr, 0.f};
+        if (Hkv != H) return cs_out_gqa(dtype, o, H / Hkv, B, st, tab);
         RC(launch_tab(k_cs_out<ET>, k_cs_out<ET, CsOutArgsVar>, dim3(n, B * H, (V + 63) / 64), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cs_out",
                       "k_cs_out<tab>", o, tab));
     });
@@ -388,6 +397,41 @@ int mhla_causal_varlen_normgate_fwd(mhla_view q, mhla_view k, mhla_view v, const
     return cs_fwd_impl(q, k, v, mix, ldmix, out, ws, ws_bytes, B, T, H, K, V, chunk, scale, dtype, flags, stream, true, norm_w, norm_eps, gate, y,
                        n_chunks, chunk_tab_dev);
 }
+
+// ---- grouped-query heads in the forward: the namesakes with Hkv after H (mhla_hip.h) ----
+int mhla_causal_fwd_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out, void* ws, size_t ws_bytes,
+                        int B, int T, int H, int Hkv, int K, int V, int chunk, float scale, int dtype, unsigned flags, void* stream) {
+    if (Hkv < 1) return fail(MHLA_EINVAL, "Hkv=%d must be positive", Hkv);
+    return cs_fwd_impl(q, k, v, mix, ldmix, out, ws, ws_bytes, B, T, H, K, V, chunk, scale, dtype, flags, stream, false, nullptr, 0.f,
+                       mhla_view{nullptr, 0, 0, 0}, mhla_mview{nullptr, 0, 0, 0}, 0, nullptr, Hkv);
+}
+int mhla_causal_normgate_fwd_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out, mhla_view gate,
+                                 const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int T, int H,
+                                 int Hkv, int K, int V, int chunk, float scale, int dtype, unsigned flags, void* stream) {
+    if (Hkv < 1) return fail(MHLA_EINVAL, "Hkv=%d must be positive", Hkv);
+    if (!y.ptr) return fail(MHLA_EINVAL, "y null");
+    return cs_fwd_impl(q, k, v, mix, ldmix, out, ws, ws_bytes, B, T, H, K, V, chunk, scale, dtype, flags, stream, true, norm_w, norm_eps, gate, y,
+                       0, nullptr, Hkv);
+}
+int mhla_causal_varlen_fwd_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out, void* ws,
+                               size_t ws_bytes, int B, int T, int H, int Hkv, int K, int V, int chunk, int n_chunks,
+                               const int* chunk_tab_dev, float scale, int dtype, unsigned flags, void* stream) {
+    if (Hkv < 1) return fail(MHLA_EINVAL, "Hkv=%d must be positive", Hkv);
+    if (!chunk_tab_dev) return fail(MHLA_EINVAL, "chunk_tab_dev null");
+    return cs_fwd_impl(q, k, v, mix, ldmix, out, ws, ws_bytes, B, T, H, K, V, chunk, scale, dtype, flags, stream, false, nullptr, 0.f,
+                       mhla_view{nullptr, 0, 0, 0}, mhla_mview{nullptr, 0, 0, 0}, n_chunks, chunk_tab_dev, Hkv);
+}
+int mhla_causal_varlen_normgate_fwd_gqa(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_mview out,
+                                        mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes,
+                                        int B, int T, int H, int Hkv, int K, int V, int chunk, int n_chunks, const int* chunk_tab_dev,
+                                        float scale, int dtype, unsigned flags, void* stream) {
+    if (Hkv < 1) return fail(MHLA_EINVAL, "Hkv=%d must be positive", Hkv);
+    if (!y.ptr) return fail(MHLA_EINVAL, "y null");
+    if (!chunk_tab_dev) return fail(MHLA_EINVAL, "chunk_tab_dev null");
+    return cs_fwd_impl(q, k, v, mix, ldmix, out, ws, ws_bytes, B, T, H, K, V, chunk, scale, dtype, flags, stream, true, norm_w, norm_eps, gate, y,
+                       n_chunks, chunk_tab_dev, Hkv);
+}
+
 int mhla_causal_varlen_bwd(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, mhla_view dout, mhla_mview dq,
                            mhla_mview dk, mhla_mview dv, float* dmix, int lddmix, void* ws, size_t ws_bytes, const void* fwd_ws,
                            int B, int T, int H, int K, int V, int chunk, int n_chunks, const int* chunk_tab_dev, float scale, int dtype,

@@ -54,6 +54,19 @@ struct CsOutArgsVar : CsOutArgs {   // packed sequences: n chunks of 1 .. 64 row
     static constexpr bool VARLEN = true;
     const cs_tab_t* tab;   // [n] {first row, rows}
 };
+// Grouped-query heads in the forward's output kernels: q, o, y, gate have H heads, k, v and the summaries P have H / G, and query
+// head h reads k/v head h / G.  The group factor lives in argument types of its own, so that the plain instantiations keep their
+// arguments and their code: (b, h) = b H + h and H = G Hkv make (b, h) / G the k/v pair b Hkv + h / G -- one division per workgroup.
+struct CsOutArgsGqa : CsOutArgs {
+    static constexpr bool GQA = true;
+    int G, Hkv;   // query heads per k/v head (2 .. 8), k/v heads (H / G)
+};
+struct CsOutArgsVarGqa : CsOutArgsVar {
+    static constexpr bool GQA = true;
+    int G, Hkv;
+};
+template <typename A>
+constexpr bool cs_gqa = requires { A::GQA; };
 constexpr int CS_OUT_SMEM_FLOATS = 3 * CS * CS_LDX + CS * CS_LDK + CS * CS_LDO;
 
 template <typename T, typename A = CsOutArgs>
@@ -74,11 +87,16 @@ __global__ __launch_bounds__(NTHREADS) void k_cs_out(const A a) {
         p0 = e.x;
         rv = e.y;
     }
+    int hk = h, bhk = bh;   // the k/v head and its (b, head) pair
+    if constexpr (cs_gqa<A>) {
+        bhk = __builtin_amdgcn_readfirstlane((int)((unsigned)bh / (unsigned)a.G));
+        hk = bhk - b * a.Hkv;
+    }
     const T* qb = (const T*)a.q.ptr + b * a.q.sb + h * a.q.sh;
-    const T* kb = (const T*)a.k.ptr + b * a.k.sb + h * a.k.sh;
-    const T* vb = (const T*)a.v.ptr + b * a.v.sb + h * a.v.sh;
+    const T* kb = (const T*)a.k.ptr + b * a.k.sb + hk * a.k.sh;
+    const T* vb = (const T*)a.v.ptr + b * a.v.sb + hk * a.v.sh;
     T* ob = (T*)a.o.ptr + b * a.o.sb + h * a.o.sh;
-    const float* Pi = a.P + ((long)bh * a.n + ci) * a.K * a.V;
+    const float* Pi = a.P + ((long)bhk * a.n + ci) * a.K * a.V;
     const bool vec_ok = (a.V & 3) == 0;
 
     f32x4 accO[4], accA[4];

@@ -457,11 +457,16 @@ __host__ __device__ constexpr int csf_out4_smem() {
 
 // (HL with four V slices per workgroup -- the fused epilogue at V = 256 -- holds 32 ring and 32 accumulator registers beside the
 //  operands: one workgroup per CU on 256 VGPRs instead of 20 spilled registers at 128)
+// the grouped-query instantiation (CsOutArgsGqa, causal.hpp) that is held to five waves' registers, below
+template <int NV, bool EPI, int HL, int NH, typename A>
+__host__ __device__ constexpr bool csf_out4_gqa_tight() { return cs_gqa<A> && !A::VARLEN && NV == 2 && HL == 2 && !EPI && NH == 1; }
 template <int NV, bool EPI, int HL, int NH = 1, typename A = CsOutArgs>
 #ifndef CSF_OUT4_NV4_WAVES
 #define CSF_OUT4_NV4_WAVES 4   // four slices with hi + lo pairs: two workgroups per CU at 128 VGPRs and 4 spilled registers (98 us at C5)
 #endif                         // beat one workgroup at 134 (107 us) and two slices per workgroup, which read Q and K twice (108-112 us)
-__global__ __launch_bounds__(NT4, NH > 1 ? 2 : (HL && NV == 4) ? (EPI ? 2 : CSF_OUT4_NV4_WAVES) : 4) void k_csf_out4(const A a) {   // (NH > 1: 138 KB of LDS, one workgroup per CU anyway)
+// (grouped-query twin of the plain h16 kernel with two slices: within the 128 registers of four waves the compiler schedules it to 128
+//  with 2 spilled registers where the plain kernel takes 92; held to the budget of five waves it takes 94 and spills nothing)
+__global__ __launch_bounds__(NT4, (csf_out4_gqa_tight<NV, EPI, HL, NH, A>()) ? 5 : NH > 1 ? 2 : (HL && NV == 4) ? (EPI ? 2 : CSF_OUT4_NV4_WAVES) : 4) void k_csf_out4(const A a) {   // (NH > 1: 138 KB of LDS, one workgroup per CU anyway)
     constexpr int P = HL ? 2 : 1, MP = cs_mplanes(HL), LD = CSF_OUT4_LD, CT = tile_elems<LD>();   // P: LDS planes, MP: planes in memory
     constexpr bool H16 = HL == 2;
     static_assert(NH == 1 || EPI, "only the fused-epilogue variant walks several halves of the head");
@@ -473,15 +478,20 @@ __global__ __launch_bounds__(NT4, NH > 1 ? 2 : (HL && NV == 4) ? (EPI ? 2 : CSF_
     const int rt = wave & 3, ch = wave >> 2;
     constexpr int CPW = EPI ? 1 : CSF_OUT4_CPW;
     const int c0 = blockIdx.x * CPW, c1 = min(a.n, c0 + CPW), bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H;
+    int hk = h, bhk = bh;   // the k/v head and its (b, head) pair: k, v and the P tiles (grouped-query heads, CsOutArgsGqa)
+    if constexpr (cs_gqa<A>) {
+        bhk = __builtin_amdgcn_readfirstlane((int)((unsigned)bh / (unsigned)a.G));   // (workgroup-uniform: scalar registers)
+        hk = bhk - b * a.Hkv;
+    }
     const int V = a.V, nks = a.K / 64;
     const u16* qb = (const u16*)a.q.ptr + b * a.q.sb + h * a.q.sh;
-    const u16* kb = (const u16*)a.k.ptr + b * a.k.sb + h * a.k.sh;
+    const u16* kb = (const u16*)a.k.ptr + b * a.k.sb + hk * a.k.sh;
     const CsLayout L = cs_layout(a.n, (long)a.K * V, MP);
     float ss[4] = {0.f, 0.f, 0.f, 0.f};   // (EPI) row sums of squares over the halves walked so far
 #pragma unroll 1
     for (int hv = 0; hv < NH; ++hv) {
     const int vbase = (NH > 1 ? hv : (int)blockIdx.z) * 64 * NV;
-    const u16* vb = (const u16*)a.v.ptr + b * a.v.sb + h * a.v.sh + vbase;
+    const u16* vb = (const u16*)a.v.ptr + b * a.v.sb + hk * a.v.sh + vbase;
     u16* ob = (u16*)a.o.ptr + b * a.o.sb + h * a.o.sh + vbase;
     if (hv > 0) __syncthreads();   // the previous half's V tiles and score tile are dead
     const int tr = tid >> 3, tc = (tid & 7) * 8;
@@ -497,7 +507,7 @@ __global__ __launch_bounds__(NT4, NH > 1 ? 2 : (HL && NV == 4) ? (EPI ? 2 : CSF_
         rQ = gld<uint4>(qb + trow0 * a.q.sn + tc);
         rK = gld<uint4>(kb + trow0 * a.k.sn + tc);
         __builtin_amdgcn_sched_barrier(0);
-        const u16* Pb0 = reinterpret_cast<const u16*>(a.P) + bh * L.bhs + c0 * L.cst;
+        const u16* Pb0 = reinterpret_cast<const u16*>(a.P) + bhk * L.bhs + c0 * L.cst;
 #pragma unroll
         for (int j = 0; j < NV; ++j)
 #pragma unroll
@@ -512,11 +522,11 @@ __global__ __launch_bounds__(NT4, NH > 1 ? 2 : (HL && NV == 4) ? (EPI ? 2 : CSF_
     const CsRows cr = cs_rows(a, ci);
     const long p0 = cr.p0;
     const int rv = cr.rv;
-    const u16* Pb = reinterpret_cast<const u16*>(a.P) + bh * L.bhs + ci * L.cst;
+    const u16* Pb = reinterpret_cast<const u16*>(a.P) + bhk * L.bhs + ci * L.cst;
     const long trow = p0 + (tr < rv ? tr : 0);
     const int cn = ci + 1 < c1 ? ci + 1 : ci;   // next chunk (behind the last one: this chunk again -- hot lines, never used)
     const long trown = row_of(cn);
-    const u16* Pbn = reinterpret_cast<const u16*>(a.P) + bh * L.bhs + cn * L.cst;
+    const u16* Pbn = reinterpret_cast<const u16*>(a.P) + bhk * L.bhs + cn * L.cst;
     if (ci > c0) __syncthreads();   // the previous chunk's staging tiles are dead
     const float mii = gld<float>(a.mix + (long)ci * a.ldmix + ci);   // (requested here: a wait for it later would drain the ring)
     f32x4 accO[NV][2], accA[2];

@@ -314,8 +314,9 @@ class MHLA(nn.Module):
         speculative verify / commit, device-positioned steps, the packed exact prefill -- keeps k and v un-repeated: feature map and
         rotary run on `num_kv_heads` heads, and the cached `CausalState` has `num_kv_heads` heads, 1 / `num_kv_groups` of the memory
         and of the per-token state traffic (the state is a function of k and v alone, so the repeated heads of a group held equal
-        copies).  The outputs are bit for bit those of `grouped_state=False`; only the operator of the prefill's output still takes
-        repeated heads."""
+        copies).  The outputs are bit for bit those of `grouped_state=False`; the operator of the prefill's output takes the
+        un-repeated heads too (`mhla_causal`: natively when there is no gradient to compute).  Whatever `grouped_state`, a forward
+        without a cache under `torch.no_grad()` leaves k and v un-repeated as well."""
         super().__init__()
         self.mode = mode
         self.hidden_size = hidden_size
@@ -417,8 +418,11 @@ class MHLA(nn.Module):
             plan = kwargs.get("varlen_plan", None)
             if plan is None:
                 plan = causal_varlen_plan(cu_seqlens, hidden_states.device)
-        # (grouped_state: the exact paths keep the k/v heads un-repeated; the prefill repeats them for its operator alone)
-        grouped = self.grouped_state and call.exact and self.num_kv_groups > 1
+        # (grouped_state: the exact paths keep the k/v heads un-repeated.  So does, with grad mode off, every call whose operator is the
+        # reference protocol's -- mhla_causal / mhla_causal_normgate / naive_recurrent_mhla take grouped-query heads, and the state the
+        # last one returns has q's heads; an exact call without grouped_state keeps its repeated heads: its cached state has them)
+        reference = call.state is None and not call.exact
+        grouped = self.num_kv_groups > 1 and ((self.grouped_state and call.exact) or (reference and not torch.is_grad_enabled()))
         q, k, v, conv_states = self._project(hidden_states, last_state, use_cache, cu_seqlens, repeat=not grouped)
         rows = self._rotary_rows(call, q, q_len, cu_seqlens, attention_mask, past_key_values)
         q, k = self._featmap_rotary(q, k, rows, flat=call.ragged)
@@ -631,8 +635,8 @@ class MHLA(nn.Module):
         of it from one launch chain."""
         B, T = q.shape[:2]
         mix = self.mixing_matrix
-        # (grouped_state: the state from the k/v heads as they are, the operator on repeated heads)
-        ko, vo = self._repeat_kv(k, v) if k.shape[2] != self.num_heads else (k, v)
+        # (grouped_state: the state and the operator both take the k/v heads as they are)
+        ko, vo = k, v
         if plan is not None:
             o, _, fused = self._reference_operator(q, ko, vo, hidden_states, plan, fused, (B, T), None, True)
             return o, mhla_causal_state(k, v, mix, cu_seqlens=plan), fused

@@ -1109,6 +1109,61 @@ def _causal_varlen_args(what, q, mixing_matrix, cu_seqlens, chunk_size) -> Causa
     return plan
 
 
+def _causal_group(fn, q, k, v, gate=None) -> int:
+    """G = H / Hkv of an operator call whose k, v have fewer heads than q (grouped-query heads, the decode calls' convention:
+    `_kv_group`); with G > 1 also the shapes -- k, v on the same Hkv heads, gate on q's H.  Host arithmetic, raised before the
+    library is loaded."""
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        return 1   # (the operator's own shape errors)
+    B, T, H, K = q.shape
+    G = _kv_group(fn, H, k.shape[2])
+    if G > 1:
+        _check_like(q, fn, k=(k, (B, T, k.shape[2], K)), v=(v, (B, T, k.shape[2], v.shape[-1])), gate=(gate, (B, T, H, v.shape[-1])))
+    return G
+
+
+def _expand_kv(t: torch.Tensor, G: int) -> torch.Tensor:
+    """[B, T, Hkv, D] -> [B, T, Hkv G, D], every head G times in a row (the layer's '(h g)' order, `repeat_interleave(G, 2)`), as a
+    differentiable expand + reshape: autograd sums the G gradients of a head back onto it."""
+    B, T, Hkv, D = t.shape
+    return t[:, :, :, None, :].expand(B, T, Hkv, G, D).reshape(B, T, Hkv * G, D)
+
+
+def _wants_grad(*ts) -> bool:
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+@_device_guard
+def _causal_fwd_gqa(q, k, v, mix, gate, weight, chunk_size, scale, norm_eps, flags, plan, epi):
+    """The grouped-query forward without a graph (mhla_causal_fwd_gqa and its kin): q [B, T, H, K] on k, v of Hkv heads, un-repeated.
+    The chunk summaries, their mixes and the workspace exist once per k/v head; `epi`: the fused norm x gate output.  `plan`, `mix`:
+    as _Causal takes them."""
+    _lib.load()
+    table, n_chunks = (None, None) if plan is None else (plan.table, plan.n_chunks)
+    _require_gpu(q, k, v, mix, gate, weight, table)
+    B, T, H, K = q.shape
+    Hkv, V = k.shape[2], v.shape[-1]
+    n = (T + chunk_size - 1) // chunk_size
+    if n > mix.shape[0]:
+        raise IndexError(f"sequence of {T} tokens needs {n} chunks but mixing_matrix has only {mix.shape[0]} rows")
+    if plan is None and (mix.device != q.device or mix.dim() < 2 or mix.shape[1] < n):
+        raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)] with L >= {n} on {q.device}")
+    q, k, v = _prep(q.detach()), _prep(k.detach()), _prep(v.detach())
+    mixf = _mix2d(mix, n_chunks)
+    dt = _dtype_code(q)
+    out = q.new_empty((B, T, H, V))
+    ws = _ws(_cs_plan(B, T, Hkv, K, V, chunk_size, dt, flags, n_chunks)[0], q.device)   # (by the k/v heads: 1 / G of the repeated call's)
+    tail = (ws.data_ptr(), ws.numel() * 4, B, T, H, Hkv, K, V, chunk_size, float(scale), dt, flags, _stream())
+    if not epi:
+        _causal_call("fwd_gqa", plan, _view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], _view(out), *tail)
+    else:
+        gate = _prep(gate.detach()) if gate is not None else None
+        wf = _f32(weight)
+        _causal_call("normgate_fwd_gqa", plan, _view(q), _view(k), _view(v), mixf.data_ptr(), mixf.shape[1], NULL_VIEW, _view_or_null(gate),
+                     _ptr(wf), float(norm_eps), _view(out), *tail)
+    return out
+
+
 def _causal_keep_limit(keep_state_limit: Optional[int]) -> int:
     return CAUSAL_KEEP_STATE_LIMIT_BYTES if keep_state_limit is None else int(keep_state_limit)
 
@@ -1141,7 +1196,14 @@ def mhla_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix
     batch), a sequence of ints or a 1-D tensor (read once: a device tensor synchronises), starting at 0, non-decreasing, ending at
     T.  Every sequence is computed exactly as if it were alone in a call of its own: its chunks are cut from its own first token
     and see rows 0.. of the mixing matrix and nothing of their neighbours.  Empty sequences are allowed; IndexError, before
-    anything is launched, names the sequences longer than 64 L tokens."""
+    anything is launched, names the sequences longer than 64 L tokens.
+    Grouped-query heads: k [B, T, Hkv, K], v [B, T, Hkv, V] with H = G Hkv, G <= 8; query head h uses k/v head h // G.  The result
+    is, bit for bit, that of the call on `k.repeat_interleave(G, 2)`, `v.repeat_interleave(G, 2)`.  With no gradient to compute
+    (grad mode off, or nothing that requires one) the forward runs natively on the un-repeated heads: chunk summaries, their
+    mixes and the workspace once per k/v head, no copy of k or v.  When a gradient is needed, k and v are expanded to H heads
+    inside the graph and today's nodes run -- the backward still works on repeated heads, because the group sums of dk / dv
+    belong in a token kernel that has no registers left for them and the group-summed dP in the summary kernel -- and autograd
+    returns dk, dv on Hkv heads."""
     if q.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
     if int(chunk_size) <= 0:
@@ -1150,7 +1212,19 @@ def mhla_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix
     flags = _causal_flags(summaries, force_generic)
     if scale is None:
         scale = q.shape[-1] ** -0.5
+    G = _causal_group("mhla_causal", q, k, v)
     plan = _causal_varlen_args("mhla_causal", q, mixing_matrix, cu_seqlens, chunk_size) if cu_seqlens is not None else None
+    if G > 1 and _wants_grad(q, k, v, mixing_matrix):   # the backward's kernels take repeated heads: today's nodes on expanded k, v
+        k, v = _expand_kv(k, G), _expand_kv(v, G)
+    elif G > 1:
+        B, T, H, _ = q.shape
+        if B == 0 or T == 0:
+            return torch.zeros((B, T, H, v.shape[-1]), dtype=v.dtype, device=v.device)
+        mix = mixing_matrix if plan is None else plan.mix_eff(mixing_matrix)
+        nb = max(1, min(B, _MAX_GRID_BH // H))   # (slices sized by the query heads: they are what the output launch's grid counts)
+        outs = [_causal_fwd_gqa(q[i:i + nb], k[i:i + nb], v[i:i + nb], mix, None, None, int(chunk_size), scale, 0.0, flags, plan, False)
+                for i in range(0, B, nb)]
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
     if plan is not None and q.shape[1] > 0:
         return _Causal.apply(q, k, v, plan.mix_eff(mixing_matrix), int(chunk_size), scale, flags, keep_limit, plan)
     if q.shape[0] == 0 or q.shape[1] == 0:   # empty batch / sequence
@@ -1231,7 +1305,7 @@ def mhla_causal_normgate(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixi
     """`rmsnorm_gate(mhla_causal(q, k, v, mix), gate, weight, norm_eps)` -- the fla layer's operator + FusedRMSNormGated
     (mhla_nlp/fla/layers/mhla.py:330-355).  Where the fused epilogue applies (bf16, K, V multiples of 64, K <= 256, V <= 256 or
     384 / 512, at most 256 chunks) the norm x gate runs inside the operator's output kernel; other shapes compose the two HIP operators.
-    `summaries`, `keep_state_limit`, `cu_seqlens`: see mhla_causal."""
+    `summaries`, `keep_state_limit`, `cu_seqlens`, grouped-query heads (k, v on Hkv heads; gate, like q, on H): see mhla_causal."""
     if int(chunk_size) <= 0:
         raise ValueError(f"chunk_size must be positive, got {chunk_size}")
     flags = _causal_flags(summaries, False)
@@ -1242,9 +1316,15 @@ def mhla_causal_normgate(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixi
         if q.dim() != 4 or v.dim() != 4:
             raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
         plan = _causal_varlen_args("mhla_causal_normgate", q, mixing_matrix, cu_seqlens, chunk_size)
+    G = _causal_group("mhla_causal_normgate", q, k, v, gate)
     if not causal_normgate_fusable(q, v, chunk_size, flags, plan):
         return rmsnorm_gate(mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries, keep_state_limit=keep_state_limit,
                                         cu_seqlens=plan), gate, weight, norm_eps)
+    if G > 1 and _wants_grad(q, k, v, mixing_matrix, gate, weight):
+        k, v = _expand_kv(k, G), _expand_kv(v, G)
+    elif G > 1:
+        return _causal_fwd_gqa(q, k, v, mixing_matrix if plan is None else plan.mix_eff(mixing_matrix), gate, weight, int(chunk_size), scale,
+                               norm_eps, flags, plan, True)
     return _CausalNormGate.apply(q, k, v, mixing_matrix if plan is None else plan.mix_eff(mixing_matrix), gate, weight, int(chunk_size), scale,
                                  norm_eps, flags, _causal_keep_limit(keep_state_limit), plan)
 
@@ -1292,7 +1372,8 @@ class CausalState:
     call that reads the mirror refuses it, and `sync()` reads `pos` back.  `full` (int32 [B] on the state's device, zeros, created on
     first use) is where those steps flag a sequence they found beyond the capacity.
     Grouped-query heads: the state is a function of k and v alone, so its head count is that of k and v (Hkv), whatever the number
-    of query heads -- every decode call takes q `[B, T, H, K]` with k, v `[B, T, Hkv, .]` and a state of Hkv heads, H = G Hkv, G <= 8."""
+    of query heads -- every decode call, and the operator that computes a prefill's output rows (`mhla_causal`), takes q
+    `[B, T, H, K]` with k, v `[B, T, Hkv, .]` and a state of Hkv heads, H = G Hkv, G <= 8."""
 
     __slots__ = ("S", "P", "Cur", "seen", "chunk_size", "lengths", "pos", "stale", "_full")
 
@@ -1496,22 +1577,23 @@ def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixin
     those of `mhla_causal` over that sequence alone (one call per run of adjacent sequences of equal length), padding rows zero.
     cu_seqlens: a pack (B = 1), as `mhla_causal` takes it -- `o` is the packed output `mhla_causal(..., cu_seqlens=)`, the state
     the ragged one of `mhla_causal_state(..., cu_seqlens=)`, one sequence of the pack per batch entry; one plan serves both.
-    Grouped-query heads (k, v `[B, T, Hkv, .]`, H = G Hkv, G <= 8): `o` is computed on k, v repeated G times per head, as the fla
-    layer does; the state is built from the un-repeated k, v and has Hkv heads (`CausalState`)."""
+    Grouped-query heads (k, v `[B, T, Hkv, .]`, H = G Hkv, G <= 8): `o` is `mhla_causal` on the un-repeated k, v -- bit for bit the
+    output on k, v repeated G times per head, as the fla layer repeats them, without the copies; the state is built from the same
+    k, v and has Hkv heads (`CausalState`)."""
     if q.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
     if int(chunk_size) != 64:
         raise ValueError(f"mhla_causal_prefill: chunk_size={chunk_size}, the decode state supports 64 only")
-    # grouped-query heads: the state from the un-repeated k, v; the operator that computes `o` takes repeated heads
-    G = _kv_group("mhla_causal_prefill", q.shape[2], k.shape[2]) if k.dim() == 4 else 1
-    ko, vo = (k, v) if G == 1 else (k.repeat_interleave(G, 2), v.repeat_interleave(G, 2))
+    # grouped-query heads: the operator that computes `o` and the state both take the un-repeated k, v
+    if k.dim() == 4:
+        _kv_group("mhla_causal_prefill", q.shape[2], k.shape[2])
     if cu_seqlens is not None:
         # every refusal of the state half first, so that nothing is launched for a call that is refused
         plan = _causal_state_pack_args("mhla_causal_prefill", k, v, mixing_matrix, cu_seqlens, lengths, left_padded, capacity_chunks)[0]
-        o = mhla_causal(q, ko, vo, mixing_matrix, chunk_size, scale, summaries=summaries, cu_seqlens=plan)
+        o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries, cu_seqlens=plan)
         return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks, cu_seqlens=plan)
     if lengths is None:
-        o = mhla_causal(q, ko, vo, mixing_matrix, chunk_size, scale, summaries=summaries)
+        o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries)
         return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks)
     B, T, H, _ = q.shape
     lengths = _int_tuple("mhla_causal_prefill", "lengths", lengths, B, T)
@@ -1520,7 +1602,7 @@ def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixin
     for i, j, n in _runs(lengths, B):
         if n:
             t0 = T - n if left_padded else 0
-            o[i:j, t0:t0 + n] = mhla_causal(q[i:j, t0:t0 + n], ko[i:j, t0:t0 + n], vo[i:j, t0:t0 + n], mixing_matrix, chunk_size, scale,
+            o[i:j, t0:t0 + n] = mhla_causal(q[i:j, t0:t0 + n], k[i:j, t0:t0 + n], v[i:j, t0:t0 + n], mixing_matrix, chunk_size, scale,
                                             summaries=summaries)
     return o, state
 

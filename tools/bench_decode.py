@@ -69,6 +69,13 @@ state of H heads, at B = 8, H = 16, Hkv = 4 and 2, K = 128, V = 256, 32 chunks s
 alternating in one run, `--reps` times, `--steps` calls each -- wall and device time per call (median, min, max), the kernels' device
 times, the bytes of state a step moves and the state's size.
 
+`--gqa-prefill`: the grouped-query prefill operator (`mhla_causal` / `mhla_causal_normgate` on k, v of Hkv heads, no graph) beside the
+repeated-head path it replaces (`repeat_interleave` of k and v, then the operator on H heads) at B = 1, T = 8192, H = 16, Hkv = 8, 4, 2,
+K = 128, V = 256, bf16, `summaries="tf32"`, plain and with the fused norm x gate epilogue.  Both paths run in one process, alternating,
+`--reps` times, `--steps` calls each after a warm-up of both: device-event time per call (median, min, max: the spread of repeated
+identical runs), the kernels' device times, the workspace each path asks for and the peak of `torch.cuda.max_memory_allocated` over
+one call above what the inputs hold.
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -547,6 +554,44 @@ def packed_prefill_config(H, K, V, iters, reps, cap=40):
     return rec
 
 
+def gqa_prefill_config(H, Hkv, K, V, T, fused, iters, reps):
+    from mhla_amd import ops
+    G = H // Hkv
+    g = torch.Generator().manual_seed(1)
+    mk = lambda h, D: torch.randn(1, T, h, D, generator=g).to(torch.bfloat16).to(DEV)
+    q, k, v, gate = mk(H, K), mk(Hkv, K), mk(Hkv, V), mk(H, V)
+    w = torch.ones(V, device=DEV)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    op = (lambda kk, vv: mhla_amd.mhla_causal_normgate(q, kk, vv, mix, gate, w)) if fused else (lambda kk, vv: mhla_amd.mhla_causal(q, kk, vv, mix))
+    fns = {"grouped": lambda: op(k, v), "repeated": lambda: op(k.repeat_interleave(G, 2), v.repeat_interleave(G, 2))}
+    dev = {n: [] for n in fns}
+    kern, peak = {}, {}
+    with torch.no_grad():
+        for fn in fns.values():   # warm-up of both paths before either is timed
+            batch_us(fn, 3, warm=3)
+        for _ in range(reps):
+            for n, fn in fns.items():
+                dev[n].append(batch_us(fn, iters, warm=2))
+        for n, fn in fns.items():
+            kern[n] = kernel_times(fn, iters=5)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            fn()
+            torch.cuda.synchronize()
+            peak[n] = torch.cuda.max_memory_allocated() - base
+    dt = ops._dtype_code(q)
+    ws = {"grouped": ops._cs_plan(1, T, Hkv, K, V, 64, dt, 0)[0], "repeated": ops._cs_plan(1, T, H, K, V, 64, dt, 0)[0]}
+    med = {n: statistics.median(x) for n, x in dev.items()}
+    rec = {"gqa_prefill": {"B": 1, "T": T, "H": H, "Hkv": Hkv, "K": K, "V": V, "fused_epilogue": fused, "summaries": "tf32"},
+           "calls_per_batch": iters, "reps": reps, "event_us": {n: spread(x) for n, x in dev.items()},
+           "repeated_over_grouped": round(med["repeated"] / med["grouped"], 3),
+           "workspace_bytes": ws, "workspace_ratio": round(ws["repeated"] / ws["grouped"], 3), "peak_bytes_over_inputs": peak,
+           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()}}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def gpu_kernel_count(fn):
     """GPU kernels one call of `fn` launches, or None where the profiler reports no device events."""
     try:
@@ -690,8 +735,13 @@ if __name__ == "__main__":
     ap.add_argument("--packed-prefill", action="store_true")
     ap.add_argument("--speculative", action="store_true")
     ap.add_argument("--gqa", action="store_true")
+    ap.add_argument("--gqa-prefill", action="store_true")
     a = ap.parse_args()
-    if a.gqa:
+    if a.gqa_prefill:
+        for fused in (False, True):
+            for Hkv in (8, 4, 2):
+                gqa_prefill_config(16, Hkv, 128, 256, 8192, fused, min(20, a.steps), a.reps)
+    elif a.gqa:
         for Hkv in (4, 2):
             gqa_config(8, 16, Hkv, 128, 256, max(200, a.steps), a.reps)
     elif a.speculative:
