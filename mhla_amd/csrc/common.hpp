@@ -161,8 +161,8 @@ __device__ __forceinline__ float fmrot_hi(float x0, float x1, float c, float s) 
 // (capi_common.hpp bm_sumfmt: a function of the call's shape, dtype and flags -- and of the process-wide "fp32_summaries" option -- so
 // that a forward and the backward that reuses its state agree); the split-operand kernels (split.hpp) take it as their FMT parameter.
 enum { SF_F32 = 0,    // fp32 words
-       SF_P24 = 1,    // 24-bit floats in two planes per row (split.hpp p24): 16 significand bits, 3 bytes
-       SF_H16 = 2,    // fp16 payload x one power-of-two multiplier per row (split.hpp h16): 11 significand bits, 2 bytes -- the default for 16-bit tensors
+       SF_P24 = 1,    // 24-bit floats in two planes per row (split_operands.hpp p24): 16 significand bits, 3 bytes
+       SF_H16 = 2,    // fp16 payload x one power-of-two multiplier per row (split_operands.hpp h16): 11 significand bits, 2 bytes -- the default for 16-bit tensors
        SF_BF16 = 3 }; // single bf16 values (MHLA_FLAG_BF16_SUMMARIES: reduced precision, opt-in)
 // the format's products take a bf16 hi + lo operand pair (SF_BF16: the stored value is the one operand, no lo tile)
 __host__ __device__ constexpr bool sf_has_lo(int fmt) { return fmt != SF_BF16; }

@@ -1,5 +1,5 @@
-// k_sp_mixh: the resident-sequence mixing of split.hpp (k_sp_mixr) for block summaries in the h16 format -- an fp16 payload x one
-// power-of-two multiplier per block row (split.hpp, "h16") -- computed ON THE PAYLOAD with the fp16 MFMA:
+// k_sp_mixh: the resident-sequence mixing of split_mixr.hpp (k_sp_mixr) for block summaries in the h16 format -- an fp16 payload x one
+// power-of-two multiplier per block row (split_operands.hpp, "h16") -- computed ON THE PAYLOAD with the fp16 MFMA:
 //
 //     out_o[e] = sum_r Wm(o, r) m_r pay_r[e] = m_o * sum_r w'(o, r) pay_r[e],     w'(o, r) = Wm(o, r) m_r / m_o,  |w'| <= 1,
 //
@@ -30,52 +30,6 @@ template <int NW> __host__ __device__ constexpr int mixh_te() { return NW > 8 ? 
 template <int NW> __host__ __device__ constexpr int mixh_tez() { return mixh_te<NW>() / 2; }
 template <int NW, bool DW>
 __host__ __device__ constexpr int sp_mixh_smem() { return (DW ? 3 : 2) * 16 * NW * (mixh_te<NW>() + 8) * 2 + 3 * 16 * NW * 4; }
-
-// The workgroup's mixing weights as fp32 B-operand fragments: wf[ks][t] = weight of input block r = 32 ks + 8 kg + t in output block
-// o = obase + nl (TRANS: W[r][o], else W[o][r]); blocks past M: 0.  Fetched through LDS like mixr_weights.  Ends with a barrier.
-template <int TRANS, int NTH, int ROWS, int NK>
-__device__ __forceinline__ void mixh_weights(float (&wf)[NK][8], float* __restrict__ Tf, const float* __restrict__ W, int ldw, int M, int obase, int tid) {
-    constexpr int TR = TRANS ? 64 : ROWS, TC = TRANS ? ROWS : 64, LDT = TC + 4, PPRW = TC / 4, NCH = (NK + 1) / 2;
-    const int lane = tid & 63, nl = lane & 15, kg = lane >> 4;
-    const bool vec = ((reinterpret_cast<uintptr_t>(W) & 15) == 0) && (ldw & 3) == 0;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        __syncthreads();
-        for (int v = tid; v < TR * PPRW; v += NTH) {
-            const int row = v / PPRW, c4 = (v - row * PPRW) * 4;
-            const int gr = TRANS ? c * 64 + row : row, gc = TRANS ? c4 : c * 64 + c4;
-            f32x4 x = {0.f, 0.f, 0.f, 0.f};
-            if (gr < M) {
-                const float* src = W + (long)gr * ldw + gc;
-                if (vec && gc + 4 <= M) {
-                    x = gld<f32x4>(src);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (gc + i < M) x[i] = gld<float>(src + i);
-                }
-            }
-            *reinterpret_cast<f32x4*>(Tf + row * LDT + c4) = x;
-        }
-        __syncthreads();
-        const int o = obase + nl;
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-            if (2 * c + k2 < NK) {
-                if (TRANS) {
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) wf[2 * c + k2][t] = Tf[(k2 * 32 + kg * 8 + t) * LDT + o];
-                } else {
-                    const f32x4 lo4 = *reinterpret_cast<const f32x4*>(Tf + o * LDT + k2 * 32 + kg * 8);
-                    const f32x4 hi4 = *reinterpret_cast<const f32x4*>(Tf + o * LDT + k2 * 32 + kg * 8 + 4);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) { wf[2 * c + k2][t] = lo4[t]; wf[2 * c + k2][4 + t] = hi4[t]; }
-                }
-            }
-        }
-    }
-    __syncthreads();
-}
 
 // MixrArgs as for k_sp_mixr: total = bh * ceil(E / TE) summary slices, ztotal = bh * ceil(S / TEZ) normaliser slices.
 template <int NW, int TRANS, bool DW>
@@ -370,7 +324,10 @@ __global__ __launch_bounds__(64 * NW, DW ? (NW + 3) / 4 : (NW <= 4 ? 4 : (NW + 3
     // (the first slice's rows are requested before the weights are fetched through LDS: with four slices per workgroup at the C2 shape the
     // prologue's two round trips were a fifth of the kernel)
     if (cnt_s > 0) issue(std::false_type{}, sga, (int)(s0 / nsl), (int)(s0 - (long)(s0 / nsl) * nsl));
-    mixh_weights<TRANS, NTH, ROWS, NK>(wf, reinterpret_cast<float*>(smem_raw), a.W, a.ldw, M, wave * 16, tid);
+    mix_weights_each<TRANS, NTH, ROWS, NK>(reinterpret_cast<float*>(smem_raw), a.W, a.ldw, M, 0, wave * 16, tid, [&](int ks, const float (&w)[8]) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) wf[ks][t] = w[t];
+    });
     if (cnt_s > 0) {
         int bh = (int)(s0 / nsl), es = (int)(s0 - (long)bh * nsl);
         for (int it = 0; it < cnt_s; ++it) {

@@ -28,54 +28,6 @@ __host__ __device__ constexpr int sp_mixh2_smem() {
     return (tiles > chunk ? tiles : chunk) + (RI + RO) * 4;   // (the staged weight chunk of the rebuild lies over the tiles)
 }
 
-// mixh_weights, one reduction step at a time: f(ks, w) is called with the lane's eight fp32 weights of step ks (input blocks 32 ks + 8 kg ..,
-// output block o0 + obase + nl; ROWS output blocks from o0 are staged, NK steps of input blocks) while the chunk that holds them is staged -- the caller's temporaries are 8 registers, not 8 NK.  Ends with a barrier.
-template <int TRANS, int NTH, int ROWS, int NK, typename F>
-__device__ __forceinline__ void mixh_weights_ks(float* __restrict__ Tf, const float* __restrict__ W, int ldw, int M, int o0, int obase, int tid, F f) {
-    constexpr int TR = TRANS ? 64 : ROWS, TC = TRANS ? ROWS : 64, LDT = TC + 4, PPRW = TC / 4, NCH = (NK + 1) / 2;
-    const int lane = tid & 63, nl = lane & 15, kg = lane >> 4;
-    const bool vec = ((reinterpret_cast<uintptr_t>(W) & 15) == 0) && (ldw & 3) == 0;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        __syncthreads();
-        for (int v = tid; v < TR * PPRW; v += NTH) {
-            const int row = v / PPRW, c4 = (v - row * PPRW) * 4;
-            const int gr = TRANS ? c * 64 + row : o0 + row, gc = TRANS ? o0 + c4 : c * 64 + c4;   // (output blocks o0 .. o0 + ROWS - 1 of the matrix)
-            f32x4 x = {0.f, 0.f, 0.f, 0.f};
-            if (gr < M) {
-                const float* src = W + (long)gr * ldw + gc;
-                if (vec && gc + 4 <= M) {
-                    x = gld<f32x4>(src);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (gc + i < M) x[i] = gld<float>(src + i);
-                }
-            }
-            *reinterpret_cast<f32x4*>(Tf + row * LDT + c4) = x;
-        }
-        __syncthreads();
-        const int o = obase + nl;
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-            if (2 * c + k2 < NK) {
-                float w[8];
-                if (TRANS) {
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) w[t] = Tf[(k2 * 32 + kg * 8 + t) * LDT + o];
-                } else {
-                    const f32x4 lo4 = *reinterpret_cast<const f32x4*>(Tf + o * LDT + k2 * 32 + kg * 8);
-                    const f32x4 hi4 = *reinterpret_cast<const f32x4*>(Tf + o * LDT + k2 * 32 + kg * 8 + 4);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) { w[t] = lo4[t]; w[4 + t] = hi4[t]; }
-                }
-                f(2 * c + k2, w);
-            }
-        }
-    }
-    __syncthreads();
-}
-
 // NW waves with RT 16-row output tiles each, over IH times as many input rows: a workgroup forms output blocks blockIdx.y * RO .. + RO - 1 (RO =
 // 16 NW RT) from RI = IH RO input blocks.  IH = 2: the two halves of the output rows are two workgroups that each read the whole slice --
 // the weights a wave keeps are those of ITS output tiles only (8 RI / 32 x 2 registers per tile), which is what lets 256 blocks keep
@@ -216,7 +168,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sp_mixh2(const MixrAr
         }
     };
     // The (b, h)'s operand weights: w'(o, r) = w(o, r) m_r / m_o as fp16 hi + lo, m_o = the power of two >= beta_o = sum_r |w(o, r)| m_r (the
-    // expressions of k_sp_mixh, in its order).  The weights come through the tiles (mixh_weights, one output tile at a time: 8 NK
+    // expressions of k_sp_mixh, in its order).  The weights come through the tiles (mix_weights_each, one output tile at a time: 8 NK
     // temporaries), the input rows' multipliers straight from their rows into `ms`.  The caller has flushed the previous slice's stores and
     // passed a barrier; the first slice's commit follows the staging's last barrier.
     auto rebuild = [&](int bh) __attribute__((always_inline)) {
@@ -227,7 +179,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sp_mixh2(const MixrAr
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
             float beta = 0.f;
-            mixh_weights_ks<TRANS, NTH, RO, NK>(reinterpret_cast<float*>(smem_raw), a.W, a.ldw, M, o0, (wave * RT + rt) * 16, tid, [&](int ks, const float (&w)[8]) {
+            mix_weights_each<TRANS, NTH, RO, NK>(reinterpret_cast<float*>(smem_raw), a.W, a.ldw, M, o0, (wave * RT + rt) * 16, tid, [&](int ks, const float (&w)[8]) {
                 const f32x4 m0 = *reinterpret_cast<const f32x4*>(ms + ks * 32 + kg * 8), m1 = *reinterpret_cast<const f32x4*>(ms + ks * 32 + kg * 8 + 4);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) beta += fabsf(w[t] * m0[t]) + fabsf(w[4 + t] * m1[t]);
@@ -236,7 +188,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sp_mixh2(const MixrAr
             beta += __shfl_xor(beta, 32, 64);
             const float om = h16_mult_from_bound(beta), oinv = h16_inv(om);
             if (kg == 0) mo[(wave * RT + rt) * 16 + nl] = om;
-            mixh_weights_ks<TRANS, NTH, RO, NK>(reinterpret_cast<float*>(smem_raw), a.W, a.ldw, M, o0, (wave * RT + rt) * 16, tid, [&](int ks, const float (&w)[8]) {
+            mix_weights_each<TRANS, NTH, RO, NK>(reinterpret_cast<float*>(smem_raw), a.W, a.ldw, M, o0, (wave * RT + rt) * 16, tid, [&](int ks, const float (&w)[8]) {
                 const f32x4 m0 = *reinterpret_cast<const f32x4*>(ms + ks * 32 + kg * 8), m1 = *reinterpret_cast<const f32x4*>(ms + ks * 32 + kg * 8 + 4);
                 f16x8 wh, wl;
 #pragma unroll
@@ -255,7 +207,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sp_mixh2(const MixrAr
     auto rebuild_z = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
-            mixh_weights_ks<TRANS, NTH, RO, NK>(reinterpret_cast<float*>(smem_raw), a.W, a.ldw, M, o0, (wave * RT + rt) * 16, tid, [&](int ks, const float (&w)[8]) {
+            mix_weights_each<TRANS, NTH, RO, NK>(reinterpret_cast<float*>(smem_raw), a.W, a.ldw, M, o0, (wave * RT + rt) * 16, tid, [&](int ks, const float (&w)[8]) {
 #pragma unroll
                 for (int t = 0; t < 8; ++t) {
                     const __bf16 h = (__bf16)w[t];

@@ -382,7 +382,7 @@ template <int TT> __host__ __device__ constexpr int dwr_smem() { return DWR_NBUF
 
 using sp::wait_vmcnt;
 
-// H16: x and y are h16 payload rows (fp16, the row's fp32 multiplier right behind its E elements, split.hpp): the products run on the fp16
+// H16: x and y are h16 payload rows (fp16, the row's fp32 multiplier right behind its E elements, split_operands.hpp): the products run on the fp16
 // MFMA (exact in the fp32 accumulators) and the partial is scaled by mult_x[i] mult_y[j] once, before the fp32 stages of (x2, y2) join.
 template <int TT, bool H16 = false>
 __global__ __launch_bounds__(64 * TT * TT) void k_sp_dwr(const DwrArgs a) {

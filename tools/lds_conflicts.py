@@ -13,7 +13,7 @@ round-1 layout) and after (0.00) the round-4 layout change of the tile kernels (
 
   python tools/lds_conflicts.py            table of the layouts in use and of the ones they replaced
   python tools/lds_conflicts.py search     brute force over row strides / piece swizzles for a [64][64] bf16 tile
-  python tools/lds_conflicts.py split      the staged matrices / token tiles of the split kernels (split.hpp mat_ld, mat_row): round-1 vs round-6 layout
+  python tools/lds_conflicts.py split      the staged matrices / token tiles of the split kernels (split_operands.hpp mat_ld, mat_row): round-1 vs round-6 layout
 """
 import sys
 

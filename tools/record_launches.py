@@ -39,7 +39,7 @@ inline hipError_t rec_memset(void* p, int value, size_t bytes, hipStream_t strea
 #endif
 
 '''
-UNITS = ["capi", "capi_bm_f32", "capi_bm_bf16", "capi_bm_bf16hl", "capi_bm_f16", "capi_bm_wanpro", "capi_causal", "capi_causal_state"]
+UNITS = ["capi", "capi_bm_f32", "capi_bm_bf16", "capi_bm_bf16hl", "capi_bm_f16", "capi_bm_wanpro", "capi_causal", "capi_causal_gqa", "capi_causal_state"]
 CAUSAL_ENTRIES = ("mhla_causal_fwd_ws_bytes", "mhla_causal_bwd_ws_bytes", "mhla_causal_normgate_fusable", "mhla_causal_fwd", "mhla_causal_normgate_fwd",
                   "mhla_causal_bwd", "mhla_causal_varlen_fwd_ws_bytes", "mhla_causal_varlen_bwd_ws_bytes", "mhla_causal_varlen_normgate_fusable",
                   "mhla_causal_varlen_fwd", "mhla_causal_varlen_normgate_fwd", "mhla_causal_varlen_bwd")
