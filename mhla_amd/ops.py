@@ -138,9 +138,9 @@ def _strided_ok(t: torch.Tensor) -> bool:
     """Addressable in place by every kernel family: 16-byte aligned base and 16-byte row pieces (strides that are multiples of
     8 elements for 16-bit types, 4 for fp32) -- what the bf16 fast paths need, so a view never lands on a slower path or on a
     workspace-size mismatch because of its alignment."""
+    s = t.stride()   # (read once, as in _view: a block-mix call prepares three to five tensors)
     mult = 8 if t.element_size() == 2 else 4
-    return (t.dim() == 4 and t.stride(3) == 1 and all(s % mult == 0 for s in t.stride()[:3])
-            and t.data_ptr() % 16 == 0)
+    return len(s) == 4 and s[3] == 1 and not (s[0] % mult or s[1] % mult or s[2] % mult) and t.data_ptr() % 16 == 0
 
 
 def _prep(t: torch.Tensor) -> torch.Tensor:
@@ -192,6 +192,10 @@ def _rope_tables(cos: torch.Tensor, sin: torch.Tensor, N: int, D: int):
     if cos.shape != (N, D // 2) or sin.shape != (N, D // 2) or cos.dtype != torch.float32 or sin.dtype != torch.float32:
         raise ValueError(f"rope tables must be fp32 [N={N}, D/2={D // 2}]")
     return cos.contiguous(), sin.contiguous()
+
+
+def _wants_grad(*ts) -> bool:
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
 # Workspace sizes are pure functions of the problem: one ctypes round trip per distinct problem, not per call (the eager path of a
@@ -283,6 +287,68 @@ def _den_views(normalize, q_den, k_den, qv, kv):
     return qv, kv
 
 
+def _blocks(N: int, W: torch.Tensor, checked: bool = False):
+    """(M, S) of a call on N tokens with the mixing matrix W [M, M(, 1, 1)]: the blocks and the tokens of one.  `checked`: the node's
+    public wrapper has already refused an N that M does not divide (no second check)."""
+    M = W.shape[0]
+    return M, (N // M if checked or not N % M else _block_len(N, M))
+
+
+def _rope_args(cos: Optional[torch.Tensor], sin: Optional[torch.Tensor]):
+    """Optional rope tables as the C ABI takes them: (cos, sin, row stride); null pointers and 0 without tables."""
+    return (None, None, 0) if cos is None else (cos.data_ptr(), sin.data_ptr(), cos.stride(0))
+
+
+def _bm_launch(fn, head, ws, kept, prob, eps, flags):
+    """fn(*head, <tail>), checked; `fn`: one of the library's block-mix entry points.  They all end in this tail: the workspace and
+    its bytes; in a backward the workspace its forward kept (`kept`: a 1-tuple of the pointer or None; () in a forward); `prob`, the
+    problem (B, H, M, S, D, dtype code) as the size queries take it too; eps, flags, stream."""
+    rc = fn(*head, ws.data_ptr(), ws.numel() * 4, *kept, *prob, eps, flags, _stream())
+    if rc:
+        _lib.check(rc, fn.__name__)
+
+
+def _bm_fwd(lib, tok, den, normalize, Wf, out, index_ptr, prob, eps, flags):
+    """mhla_blockmix_fwd on prepared tensors (`tok` = (q, k, v), `den` = (q_den, k_den) or (None, None); `index_ptr`: the pointer
+    of block_index or None) into `out`.  Returns the workspace where the backward may read the forward's block summaries out of it
+    (the library keeps them there and the workspace is within KEEP_STATE_LIMIT_BYTES), otherwise None: the backward recomputes them."""
+    q, k, v = tok
+    fwd_bytes, _, keeps = _bm_plan(*prob, 0 if den[0] is None else 1, flags)
+    ws = _ws(fwd_bytes, q.device)
+    qv, kv = _view(q), _view(k)
+    _bm_launch(lib.mhla_blockmix_fwd, (qv, kv, _view(v), *_den_views(normalize, *den, qv, kv), Wf.data_ptr(), prob[2], _view(out),
+                                       index_ptr), ws, (), prob, eps, flags)
+    return ws if keeps and ws.numel() * 4 <= KEEP_STATE_LIMIT_BYTES else None
+
+
+def _bm_bwd(lib, tok, den, normalize, Wf, out, dout, grads, dW, index_ptr, fwd_ws, prob, eps, flags):
+    """mhla_blockmix_bwd on a node's saved tensors (`tok`, `den`, `index_ptr` as in `_bm_fwd`; `fwd_ws`: what `_bm_fwd` returned) into
+    `grads` = (dq, dk, dv, dq_den, dk_den) -- any [B, N, H, D] views, the last two None without `den` -- and dW fp32 [M, M]."""
+    q, k, v = tok
+    dq, dk, dv, dqd, dkd = grads
+    split = 0 if den[0] is None else 1
+    ws = _ws(_bm_plan(*prob, split, flags)[1], q.device)
+    qv, kv = _view(q), _view(k)
+    _bm_launch(lib.mhla_blockmix_bwd, (qv, kv, _view(v), *_den_views(normalize, *den, qv, kv), Wf.data_ptr(), prob[2], _view(out),
+                                       _view(dout), _view(dq), _view(dk), _view(dv), NULL_VIEW if dqd is None else _view(dqd),
+                                       NULL_VIEW if dkd is None else _view(dkd), dW.data_ptr(), index_ptr),
+               ws, (_ptr(fwd_ws),), prob, eps, flags)
+    _check_handover(lib, ws, *prob, split, flags)
+
+
+def _bm_grads(q, M, den=False):
+    """What a block-mix backward writes: (dq, dk, dv, dq_den, dk_den) like q and contiguous (the last two None without `den`), and
+    dW fp32 [M, M]."""
+    dq, dk, dv = q.new_empty(q.shape), q.new_empty(q.shape), q.new_empty(q.shape)
+    dW = torch.empty((M, M), dtype=torch.float32, device=q.device)
+    return (dq, dk, dv, torch.empty_like(dq) if den else None, torch.empty_like(dq) if den else None), dW
+
+
+def _w_grad(dW, w_shape, w_dtype):
+    """The library's fp32 [M, M] gradient as the gradient of the caller's W (its shape, its dtype)."""
+    return dW.reshape(w_shape).to(w_dtype)
+
+
 class _BlockMix(torch.autograd.Function):
     @staticmethod
     @_device_guard
@@ -290,8 +356,7 @@ class _BlockMix(torch.autograd.Function):
         lib = _lib.load()
         _require_gpu(q, k, v, W, q_den, k_den, block_index)
         B, N, H, D = q.shape
-        M = W.shape[0]
-        S = _block_len(N, M)
+        M, S = _blocks(N, W)
         split = q_den is not None
         if split and not normalize:
             raise ValueError("q_den/k_den given but normalize=False")
@@ -303,21 +368,11 @@ class _BlockMix(torch.autograd.Function):
         if split:
             q_den, k_den = _prep(q_den), _prep(k_den)
         Wf = _mix2d(W, M)
-        out = _alloc_like_tokens(B, N, H, D, q)
-        dt = _dtype_code(q)
-        fwd_bytes, _, keeps = _bm_plan(B, H, M, S, D, dt, int(split), flags)
-        ws = _ws(fwd_bytes, q.device)
-        qv, kv = _view(q), _view(k)
-        qd, kd = _den_views(normalize, q_den, k_den, qv, kv)
-        rc = lib.mhla_blockmix_fwd(qv, kv, _view(v), qd, kd, Wf.data_ptr(), M, _view(out), _ptr(block_index),
-                                   ws.data_ptr(), ws.numel() * 4, B, H, M, S, D, dt, float(eps), flags, _stream())
-        if rc:
-            _lib.check(rc, "mhla_blockmix_fwd")
-        # keep the forward's block summaries for the backward when they are the compact bf16 ones (fast path)
-        keep = keeps and ws.numel() * 4 <= KEEP_STATE_LIMIT_BYTES
-        ctx.save_for_backward(q, k, v, Wf, out, q_den if split else None, k_den if split else None, block_index,
-                              ws if keep else None)
-        ctx.cfg = (float(eps), bool(normalize), split, W.shape, W.dtype, flags)
+        out = q.new_empty((B, N, H, D))
+        prob, eps = (B, H, M, S, D, _dtype_code(q)), float(eps)
+        fwd_ws = _bm_fwd(lib, (q, k, v), (q_den, k_den), normalize, Wf, out, _ptr(block_index), prob, eps, flags)
+        ctx.save_for_backward(q, k, v, Wf, out, q_den, k_den, block_index, fwd_ws)
+        ctx.cfg = (prob, eps, bool(normalize), W.shape, W.dtype, flags)
         return out
 
     @staticmethod
@@ -325,32 +380,15 @@ class _BlockMix(torch.autograd.Function):
     def backward(ctx, dout):
         lib = _lib.load()
         q, k, v, Wf, out, q_den, k_den, block_index, fwd_ws = ctx.saved_tensors
-        eps, normalize, split, w_shape, w_dtype, flags = ctx.cfg
-        B, N, H, D = q.shape
-        M = Wf.shape[0]
-        S = N // M
+        prob, eps, normalize, w_shape, w_dtype, flags = ctx.cfg
         if dout.dtype != q.dtype:
             dout = dout.to(q.dtype)
         _check_like(q, "mhla_blockmix backward", dout=(dout, q.shape))
         dout = _prep(dout)
-        dq = _alloc_like_tokens(B, N, H, D, q)
-        dk = _alloc_like_tokens(B, N, H, D, q)
-        dv = _alloc_like_tokens(B, N, H, D, q)
-        dW = torch.empty((M, M), dtype=torch.float32, device=q.device)
-        dqd = dkd = None
-        if split:
-            dqd, dkd = torch.empty_like(dq), torch.empty_like(dq)
-        dt = _dtype_code(q)
-        ws = _ws(_bm_plan(B, H, M, S, D, dt, int(split), flags)[1], q.device)
-        qv, kv = _view(q), _view(k)
-        qd, kd = _den_views(normalize, q_den, k_den, qv, kv)
-        rc = lib.mhla_blockmix_bwd(qv, kv, _view(v), qd, kd, Wf.data_ptr(), M, _view(out), _view(dout),
-                                   _view(dq), _view(dk), _view(dv), _view_or_null(dqd), _view_or_null(dkd),
-                                   dW.data_ptr(), _ptr(block_index), ws.data_ptr(), ws.numel() * 4, _ptr(fwd_ws), B, H, M, S, D,
-                                   dt, eps, flags, _stream())
-        _lib.check(rc, "mhla_blockmix_bwd")
-        _check_handover(lib, ws, B, H, M, S, D, dt, int(split), flags)
-        return dq, dk, dv, dW.reshape(w_shape).to(w_dtype), dqd, dkd, None, None, None, None
+        grads, dW = _bm_grads(q, prob[2], q_den is not None)
+        _bm_bwd(lib, (q, k, v), (q_den, k_den), normalize, Wf, out, dout, grads, dW, _ptr(block_index), fwd_ws, prob, eps, flags)
+        dq, dk, dv, dqd, dkd = grads
+        return dq, dk, dv, _w_grad(dW, w_shape, w_dtype), dqd, dkd, None, None, None, None
 
 
 def mhla_blockmix(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, W: torch.Tensor, *, eps: float = 1e-6,
@@ -388,7 +426,7 @@ def mhla_blockmix(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, W: torch.Te
     if q.shape[-1] > 128:
         return _blockmix_wide_head(q, k, v, W, eps, q_den, k_den, normalize, block_index, relu_eps, force_generic, no_smalln, summaries)
     flags = _bm_flags(relu_eps, force_generic, no_smalln, summaries)
-    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, W, q_den, k_den))):
+    if not _wants_grad(q, k, v, W, q_den, k_den):
         flags |= _lib.FLAG_NO_BWD_STATE   # inference: the forward skips what only a backward would read
     if q.shape[0] == 0:   # empty batch: nothing to launch; keep the autograd graph connected (all gradients are zero)
         return torch.zeros_like(v) + 0 * (q.sum() + k.sum() + W.sum()).to(v.dtype)
@@ -472,20 +510,17 @@ class _BlockMixRope(torch.autograd.Function):
     def forward(ctx, q, k, v, W, cos, sin, eps, normalize, block_index):
         lib = _lib.load()
         B, N, H, D = q.shape
-        M = W.shape[0]
-        S = N // M
+        M, S = _blocks(N, W, checked=True)
         q, k, v = _prep(q.detach()), _prep(k.detach()), _prep(v.detach())
         Wf = _mix2d(W, M)
-        out = _alloc_like_tokens(B, N, H, D, q)
-        dt = _dtype_code(q)
-        ws = _ws(_bm_plan(B, H, M, S, D, dt, 0, 0)[0], q.device)
-        rc = lib.mhla_blockmix_rope_fwd(_view(q), _view(k), _view(v), int(bool(normalize)), Wf.data_ptr(), M, cos.data_ptr(),
-                                        sin.data_ptr(), cos.stride(0), _view(out), _ptr(block_index), ws.data_ptr(),
-                                        ws.numel() * 4, B, H, M, S, D, dt, float(eps), 0, _stream())
-        _lib.check(rc, "mhla_blockmix_rope_fwd")
+        out = q.new_empty((B, N, H, D))
+        prob, eps, normalize = (B, H, M, S, D, _dtype_code(q)), float(eps), int(bool(normalize))
+        ws = _ws(_bm_plan(*prob, 0, 0)[0], q.device)
+        _bm_launch(lib.mhla_blockmix_rope_fwd, (_view(q), _view(k), _view(v), normalize, Wf.data_ptr(), M, *_rope_args(cos, sin),
+                                                   _view(out), _ptr(block_index)), ws, (), prob, eps, 0)
         keep = any(ctx.needs_input_grad[:4]) and ws.numel() * 4 <= KEEP_STATE_LIMIT_BYTES   # KV, G, z, ksum, 1/n for the backward
         ctx.save_for_backward(q, k, v, Wf, out, cos, sin, block_index, ws if keep else None)
-        ctx.cfg = (float(eps), bool(normalize), W.shape, W.dtype)
+        ctx.cfg = (prob, eps, normalize, W.shape, W.dtype)
         return out
 
     @staticmethod
@@ -493,23 +528,15 @@ class _BlockMixRope(torch.autograd.Function):
     def backward(ctx, dout):
         lib = _lib.load()
         q, k, v, Wf, out, cos, sin, block_index, fwd_ws = ctx.saved_tensors
-        eps, normalize, w_shape, w_dtype = ctx.cfg
-        B, N, H, D = q.shape
-        M = Wf.shape[0]
-        S = N // M
+        prob, eps, normalize, w_shape, w_dtype = ctx.cfg
+        M = prob[2]
         dout = _prep(dout.to(q.dtype))
-        dq = _alloc_like_tokens(B, N, H, D, q)
-        dk = _alloc_like_tokens(B, N, H, D, q)
-        dv = _alloc_like_tokens(B, N, H, D, q)
-        dW = torch.empty((M, M), dtype=torch.float32, device=q.device)
-        dt = _dtype_code(q)
-        ws = _ws(_bm_plan(B, H, M, S, D, dt, 0, 0)[1], q.device)
-        rc = lib.mhla_blockmix_rope_bwd(_view(q), _view(k), _view(v), int(normalize), Wf.data_ptr(), M, cos.data_ptr(),
-                                        sin.data_ptr(), cos.stride(0), _view(out), _view(dout), _view(dq), _view(dk), _view(dv),
-                                        dW.data_ptr(), _ptr(block_index), ws.data_ptr(), ws.numel() * 4, _ptr(fwd_ws),
-                                        B, H, M, S, D, dt, eps, 0, _stream())
-        _lib.check(rc, "mhla_blockmix_rope_bwd")
-        return dq, dk, dv, dW.reshape(w_shape).to(w_dtype), None, None, None, None, None
+        (dq, dk, dv, _, _), dW = _bm_grads(q, M)
+        ws = _ws(_bm_plan(*prob, 0, 0)[1], q.device)
+        _bm_launch(lib.mhla_blockmix_rope_bwd, (_view(q), _view(k), _view(v), normalize, Wf.data_ptr(), M, *_rope_args(cos, sin),
+                                                   _view(out), _view(dout), _view(dq), _view(dk), _view(dv), dW.data_ptr(),
+                                                   _ptr(block_index)), ws, (_ptr(fwd_ws),), prob, eps, 0)
+        return dq, dk, dv, _w_grad(dW, w_shape, w_dtype), None, None, None, None, None
 
 
 def mhla_blockmix_rope(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, W: torch.Tensor, rope_cos: torch.Tensor,
@@ -531,11 +558,11 @@ def mhla_blockmix_rope(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, W: tor
     mhla_blockmix(q_rope, k_rope, v, W, q_den=q, k_den=k)."""
     _require_gpu(q, k, v, W, rope_cos, rope_sin, block_index)
     _, N, _, D = q.shape
-    _block_len(N, W.shape[0])
+    _blocks(N, W)   # (the one divisibility check of this call: the node does not repeat it)
     _check_like(q, "mhla_blockmix_rope", k=(k, q.shape), v=(v, q.shape))
     _check_block_index(block_index, N, q)
     cos, sin = _rope_tables(rope_cos, rope_sin, N, D)
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, W)) and (q.dtype != torch.float32 or D % 8):
+    if _wants_grad(q, k, v, W) and (q.dtype != torch.float32 or D % 8):
         raise RuntimeError("the backward of mhla_blockmix_rope needs fp32 tensors with D % 8 == 0; rotate in the host and call "
                            "mhla_blockmix(q_rope, k_rope, v, W, q_den=q, k_den=k) otherwise")
     return _BlockMixRope.apply(q, k, v, W, cos, sin, eps, normalize, block_index)
@@ -581,7 +608,8 @@ def _lepe_wgrad(dims, v, dy, geom, w_shape, w_dtype, b_dtype):
     ws = _ws(nbytes, v.device)
     rc = fn(v.data_ptr(), v.stride(0), v.stride(1), dy.data_ptr(), dy.stride(0), dy.stride(1), dwb.data_ptr(),
             ws.data_ptr(), ws.numel() * 4, v.shape[0], *geom, _dtype_code(v), _stream())
-    _lib.check(rc, f"mhla_lepe{dims}d_wgrad")
+    if rc:
+        _lib.check(rc, f"mhla_lepe{dims}d_wgrad")
     return dwb[:taps].t().reshape(w_shape).to(w_dtype), (dwb[taps].to(b_dtype) if b_dtype is not None else None)
 
 
@@ -642,6 +670,41 @@ def lepe3d(v: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
     return _Lepe.apply(v, weight, bias, add, 3, (F_, H_, W_, v.shape[2]))
 
 
+def _wan_tokens(fn, q, k, v, W, weights, rope_cos, rope_sin, norm_weight, gate, block_index, fp32_only=False):
+    """The front mhla_blockmix_wan and mhla_blockmix_wan_pro share, first half (`fn`: the caller's name, for the messages; `weights`:
+    its further differentiable tensors): the forward-only guard, the GPU requirement, the shapes, the agreement checks.  Returns q, k,
+    v detached and as the kernels address them, the problem (B, H, M, S, D, dtype code) and N."""
+    if _wants_grad(q, k, v, W, *weights, norm_weight, gate):
+        raise RuntimeError(f"{fn} is forward-only")
+    _require_gpu(q, k, v, W, *weights, rope_cos, rope_sin, norm_weight, gate, block_index)
+    if fp32_only and q.dtype != torch.float32:
+        raise TypeError(f"{fn} takes fp32 q, k, v (the host's .float())")
+    B, N, H, D = q.shape
+    M, S = _blocks(N, W)
+    _check_like(q, fn, k=(k, q.shape), v=(v, q.shape))
+    _check_block_index(block_index, N, q)
+    q, k, v = _prep(q.detach()), _prep(k.detach()), _prep(v.detach())
+    return q, k, v, (B, H, M, S, D, _dtype_code(q)), N
+
+
+def _wan_operands(q, prob, N, W, rope_cos, rope_sin, norm_weight, gate, out_dtype, gate_in):
+    """Second half of that front, in the order the storage is allocated: the optional rope tables, the gate (in `out_dtype`, which
+    the message calls `gate_in`), the norm weight (one that `_f32` has made already passes through as it is), W, the output and the
+    workspace, which both calls size by the fp32 plan.  Returns (cos, sin, gate, norm weight, Wf, out, ws)."""
+    B, H, M, S, D, _ = prob
+    cos = sin = None
+    if rope_cos is not None:
+        cos, sin = _rope_tables(rope_cos, rope_sin, N, D)
+    if gate is not None:
+        if gate.shape != (B, N, H, D) or gate.dtype != out_dtype:
+            raise ValueError(f"gate: [B, N, H, D] in {gate_in}")
+        gate = _prep(gate.detach())
+    nw = _f32(norm_weight)
+    Wf = _mix2d(W, M)
+    out = torch.empty((B, N, H, D), dtype=out_dtype, device=q.device)
+    return cos, sin, gate, nw, Wf, out, _ws(_bm_plan(B, H, M, S, D, _lib.F32, 0, 0)[0], q.device)
+
+
 @_device_guard
 def mhla_blockmix_wan(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, W: torch.Tensor, rope_cos: Optional[torch.Tensor],
                       rope_sin: Optional[torch.Tensor], norm_weight: Optional[torch.Tensor], norm_eps: float,
@@ -651,33 +714,11 @@ def mhla_blockmix_wan(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, W: torc
     (tables optional) and the per-head RMSNorm (x SiLU gate) of wan/mhla_utils.py:356-362 applied before the store.
     q, k, v: fp32 [B, N, H, D]; gate: [B, N, H, D] in `out_dtype` or None; returns [B, N, H, D] in `out_dtype`."""
     lib = _lib.load()
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, W, norm_weight, gate)):
-        raise RuntimeError("mhla_blockmix_wan is forward-only")
-    _require_gpu(q, k, v, W, rope_cos, rope_sin, norm_weight, gate, block_index)
-    if q.dtype != torch.float32:
-        raise TypeError("mhla_blockmix_wan takes fp32 q, k, v (the host's .float())")
-    B, N, H, D = q.shape
-    M = W.shape[0]
-    S = _block_len(N, M)
-    _check_like(q, "mhla_blockmix_wan", k=(k, q.shape), v=(v, q.shape))
-    _check_block_index(block_index, N, q)
-    q, k, v = _prep(q.detach()), _prep(k.detach()), _prep(v.detach())
-    cos = sin = None
-    if rope_cos is not None:
-        cos, sin = _rope_tables(rope_cos, rope_sin, N, D)
-    if gate is not None:
-        if gate.shape != (B, N, H, D) or gate.dtype != out_dtype:
-            raise ValueError("gate: [B, N, H, D] in out_dtype")
-        gate = _prep(gate.detach())
-    nw = _f32(norm_weight)
-    Wf = _mix2d(W, M)
-    out = torch.empty((B, N, H, D), dtype=out_dtype, device=q.device)
-    ws = _ws(_bm_plan(B, H, M, S, D, _lib.F32, 0, 0)[0], q.device)
-    rc = lib.mhla_blockmix_wan_fwd(_view(q), _view(k), _view(v), int(bool(normalize)), Wf.data_ptr(), M, _ptr(cos), _ptr(sin),
-                                   cos.stride(0) if cos is not None else 0, _ptr(nw), float(norm_eps), _view_or_null(gate), _view(out),
-                                   _DTYPES[out_dtype], _ptr(block_index), ws.data_ptr(), ws.numel() * 4,
-                                   B, H, M, S, D, _lib.F32, float(eps), 0, _stream())
-    _lib.check(rc, "mhla_blockmix_wan_fwd")
+    q, k, v, prob, N = _wan_tokens("mhla_blockmix_wan", q, k, v, W, (), rope_cos, rope_sin, norm_weight, gate, block_index, fp32_only=True)
+    cos, sin, gate, nw, Wf, out, ws = _wan_operands(q, prob, N, W, rope_cos, rope_sin, norm_weight, gate, out_dtype, "out_dtype")
+    _bm_launch(lib.mhla_blockmix_wan_fwd, (_view(q), _view(k), _view(v), int(bool(normalize)), Wf.data_ptr(), prob[2], *_rope_args(cos, sin),
+                                              _ptr(nw), float(norm_eps), _view_or_null(gate), _view(out), _DTYPES[out_dtype], _ptr(block_index)),
+               ws, (), prob, float(eps), 0)
     return out
 
 
@@ -699,17 +740,8 @@ def mhla_blockmix_wan_pro(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, wq:
     `mhla_blockmix_wan(qk_prologue(q), qk_prologue(k), v.float(), ...)` without the three fp32 tensors.  Forward only; returns
     [B, N, H, D] in the dtype of q."""
     lib = _lib.load()
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, W, wq, wk, norm_weight, gate)):
-        raise RuntimeError("mhla_blockmix_wan_pro is forward-only")
-    _require_gpu(q, k, v, W, wq, wk, rope_cos, rope_sin, norm_weight, gate, block_index)
-    B, N, H, D = q.shape
-    M = W.shape[0]
-    S = _block_len(N, M)
-    _check_like(q, "mhla_blockmix_wan_pro", k=(k, q.shape), v=(v, q.shape))
-    _check_block_index(block_index, N, q)
-    q, k, v = _prep(q.detach()), _prep(k.detach()), _prep(v.detach())
-    dt = _dtype_code(q)
-    C = H * D
+    q, k, v, prob, N = _wan_tokens("mhla_blockmix_wan_pro", q, k, v, W, (wq, wk), rope_cos, rope_sin, norm_weight, gate, block_index)
+    B, H, _, _, D, dt = prob
     wq, wk, nw = _f32(wq), _f32(wk), _f32(norm_weight)
     rq = rk = None
     if qk_norm:
@@ -720,22 +752,11 @@ def mhla_blockmix_wan_pro(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, wq:
         for x, r in ((q, rq), (k, rk)):
             if x.stride(0) != N * x.stride(1):
                 raise ValueError("q, k: batch stride must be N * token stride")
-            _lib.check(lib.mhla_rms_rstd(x.data_ptr(), x.stride(1), r.data_ptr(), B * N, C, float(qk_norm_eps), dt, _stream()), "mhla_rms_rstd")
-    cos = sin = None
-    if rope_cos is not None:
-        cos, sin = _rope_tables(rope_cos, rope_sin, N, D)
-    if gate is not None:
-        if gate.shape != (B, N, H, D) or gate.dtype != q.dtype:
-            raise ValueError("gate: [B, N, H, D] in the dtype of q")
-        gate = _prep(gate.detach())
-    Wf = _mix2d(W, M)
-    out = _alloc_like_tokens(B, N, H, D, q)
-    ws = _ws(_bm_plan(B, H, M, S, D, _lib.F32, 0, 0)[0], q.device)
-    rc = lib.mhla_blockmix_wan_pro_fwd(_view(q), _view(k), _view(v), _ptr(rq), _ptr(rk), _ptr(wq), _ptr(wk), int(bool(normalize)),
-                                       Wf.data_ptr(), M, _ptr(cos), _ptr(sin), cos.stride(0) if cos is not None else 0, _ptr(nw),
-                                       float(norm_eps), _view_or_null(gate), _view(out), dt, _ptr(block_index),
-                                       ws.data_ptr(), ws.numel() * 4, B, H, M, S, D, dt, float(eps), 0, _stream())
-    _lib.check(rc, "mhla_blockmix_wan_pro_fwd")
+            _lib.check(lib.mhla_rms_rstd(x.data_ptr(), x.stride(1), r.data_ptr(), B * N, H * D, float(qk_norm_eps), dt, _stream()), "mhla_rms_rstd")
+    cos, sin, gate, nw, Wf, out, ws = _wan_operands(q, prob, N, W, rope_cos, rope_sin, nw, gate, q.dtype, "the dtype of q")
+    _bm_launch(lib.mhla_blockmix_wan_pro_fwd, (_view(q), _view(k), _view(v), _ptr(rq), _ptr(rk), _ptr(wq), _ptr(wk), int(bool(normalize)),
+                                                  Wf.data_ptr(), prob[2], *_rope_args(cos, sin), _ptr(nw), float(norm_eps), _view_or_null(gate),
+                                                  _view(out), dt, _ptr(block_index)), ws, (), prob, float(eps), 0)
     return out
 
 
@@ -751,25 +772,19 @@ class _DitCore(torch.autograd.Function):
         lib = _lib.load()
         _require_gpu(qkv, W, lepe_w, lepe_b)
         B, N, _, H, D = qkv.shape
-        M, C, K = W.shape[0], H * D, lepe_w.shape[-1]
-        S = N // M
+        (M, S), C, K = _blocks(N, W, checked=True), H * D, lepe_w.shape[-1]
         qkv = qkv if (qkv.is_contiguous() and _strided_ok(qkv[:, :, 0])) else qkv.contiguous()
         q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
         Wf = _mix2d(W, M)
-        dt = _dtype_code(qkv)
-        attn = _alloc_like_tokens(B, N, H, D, qkv)
-        ws = _ws(_bm_plan(B, H, M, S, D, dt, 0, flags)[0], qkv.device)
-        qv, kv = _view(q), _view(k)
-        rc = lib.mhla_blockmix_fwd(qv, kv, _view(v), qv, kv, Wf.data_ptr(), M, _view(attn), None, ws.data_ptr(), ws.numel() * 4,
-                                   B, H, M, S, D, dt, float(eps), flags, _stream())
-        _lib.check(rc, "mhla_blockmix_fwd")
+        prob, eps = (B, H, M, S, D, _dtype_code(qkv)), float(eps)
+        attn = qkv.new_empty((B, N, H, D))
+        fwd_ws = _bm_fwd(lib, (q, k, v), (None, None), True, Wf, attn, None, prob, eps, flags)
         w_taps, b32 = _lepe_taps(lepe_w, lepe_b, C, K * K)
         y = torch.empty((B, N, C), dtype=qkv.dtype, device=qkv.device)
         v3 = v.reshape(B, N, C)          # view: H and D are adjacent in the packed buffer
         _lepe_conv(2, v3, w_taps, b32, attn, y, (pieces_len, block_len, C, K), False)
-        keep = _bm_plan(B, H, M, S, D, dt, 0, flags)[2] and ws.numel() * 4 <= KEEP_STATE_LIMIT_BYTES
-        ctx.save_for_backward(qkv, Wf, attn, w_taps, ws if keep else None)
-        ctx.cfg = (pieces_len, block_len, float(eps), flags, W.shape, W.dtype, lepe_w.shape, lepe_w.dtype,
+        ctx.save_for_backward(qkv, Wf, attn, w_taps, fwd_ws)
+        ctx.cfg = (prob, (pieces_len, block_len, C, K), eps, flags, W.shape, W.dtype, lepe_w.shape, lepe_w.dtype,
                    lepe_b.dtype if lepe_b is not None else None)
         return y
 
@@ -778,29 +793,20 @@ class _DitCore(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         qkv, Wf, attn, w_taps, fwd_ws = ctx.saved_tensors
-        pl, bl, eps, flags, w_shape, w_dtype, lw_shape, lw_dtype, lb_dtype = ctx.cfg
+        prob, geom, eps, flags, w_shape, w_dtype, lw_shape, lw_dtype, lb_dtype = ctx.cfg
         B, N, _, H, D = qkv.shape
-        M, C, K = Wf.shape[0], H * D, lw_shape[-1]
-        S = N // M
-        dt = _dtype_code(qkv)
+        M, C = prob[2], geom[2]
         dy = dy.to(qkv.dtype).contiguous()
-        dy4 = dy.reshape(B, N, H, D)
         q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
         dqkv = torch.empty_like(qkv)
-        dv_attn = _alloc_like_tokens(B, N, H, D, qkv)
+        dv_attn = qkv.new_empty((B, N, H, D))
         dW = torch.empty((M, M), dtype=torch.float32, device=qkv.device)
-        ws = _ws(_bm_plan(B, H, M, S, D, dt, 0, flags)[1], qkv.device)
-        qv, kv = _view(q), _view(k)
-        rc = lib.mhla_blockmix_bwd(qv, kv, _view(v), qv, kv, Wf.data_ptr(), M, _view(attn), _view(dy4),
-                                   _view(dqkv[:, :, 0]), _view(dqkv[:, :, 1]), _view(dv_attn), NULL_VIEW, NULL_VIEW,
-                                   dW.data_ptr(), None, ws.data_ptr(), ws.numel() * 4, _ptr(fwd_ws), B, H, M, S, D, dt, eps, flags, _stream())
-        _lib.check(rc, "mhla_blockmix_bwd")
-        _check_handover(lib, ws, B, H, M, S, D, dt, 0, flags)
+        _bm_bwd(lib, (q, k, v), (None, None), True, Wf, attn, dy.reshape(B, N, H, D), (dqkv[:, :, 0], dqkv[:, :, 1], dv_attn, None, None),
+                dW, None, fwd_ws, prob, eps, flags)
         # dv = operator part + LePE part (flipped-kernel correlation of dy), written into the V slice of the packed gradient
-        geom = (pl, bl, C, K)
         _lepe_conv(2, dy, w_taps, None, dv_attn, dqkv[:, :, 2].reshape(B, N, C), geom, True)
         dlw, dlb = _lepe_wgrad(2, v.reshape(B, N, C), dy, geom, lw_shape, lw_dtype, lb_dtype)
-        return dqkv, dW.reshape(w_shape).to(w_dtype), dlw, dlb, None, None, None, None
+        return dqkv, _w_grad(dW, w_shape, w_dtype), dlw, dlb, None, None, None, None
 
 
 def mhla_dit_core(qkv: torch.Tensor, W: torch.Tensor, lepe_weight: torch.Tensor, lepe_bias: Optional[torch.Tensor],
@@ -813,7 +819,7 @@ def mhla_dit_core(qkv: torch.Tensor, W: torch.Tensor, lepe_weight: torch.Tensor,
     if qkv.shape[1] % W.shape[0] or qkv.shape[1] != (pieces_len * block_len) ** 2:
         raise ValueError("token count does not match the block layout")
     flags = _bm_flags(relu_eps, False, False, summaries)
-    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (qkv, W, lepe_weight, lepe_bias))):
+    if not _wants_grad(qkv, W, lepe_weight, lepe_bias):
         flags |= _lib.FLAG_NO_BWD_STATE
     return _DitCore.apply(qkv, W, lepe_weight, lepe_bias, int(pieces_len), int(block_len), eps, flags)
 
@@ -830,7 +836,7 @@ class _FmapRotary(torch.autograd.Function):
         B, T, H, K = x.shape
         x = _prep(x)
         y = _alloc_like_tokens(B, T, H, K, x)
-        rc = lib.mhla_featmap_rotary(_view(x), NULL_VIEW, cos.data_ptr(), sin.data_ptr(), cos.stride(0), t_offset, _view(y),
+        rc = lib.mhla_featmap_rotary(_view(x), NULL_VIEW, *_rope_args(cos, sin), t_offset, _view(y),
                                      B, T, H, K, fmap, 0, _dtype_code(x), _stream())
         _lib.check(rc, "mhla_featmap_rotary")
         ctx.save_for_backward(x, cos, sin)
@@ -846,7 +852,7 @@ class _FmapRotary(torch.autograd.Function):
         B, T, H, K = x.shape
         dy = _prep(dy.to(x.dtype))
         dx = _alloc_like_tokens(B, T, H, K, x)
-        rc = lib.mhla_featmap_rotary(_view(dy), _view(x), cos.data_ptr(), sin.data_ptr(), cos.stride(0), t_offset, _view(dx),
+        rc = lib.mhla_featmap_rotary(_view(dy), _view(x), *_rope_args(cos, sin), t_offset, _view(dx),
                                      B, T, H, K, fmap, 1, _dtype_code(x), _stream())
         _lib.check(rc, "mhla_featmap_rotary (backward)")
         return dx, None, None, None, None
@@ -882,15 +888,14 @@ class _QkPrologue(torch.autograd.Function):
         w = _f32(weight)
         rope = cos is not None
         yr = torch.empty_like(y) if rope else None
-        ntok = cos.shape[0] if rope else 0
-        rc = lib.mhla_qk_prologue_rope(x2.data_ptr(), x2.stride(0), _ptr(w), y.data_ptr(), C,
-                                       yr.data_ptr() if rope else None, C, cos.data_ptr() if rope else None,
-                                       sin.data_ptr() if rope else None, cos.stride(0) if rope else 0, ntok,
-                                       int(head_dim) if rope else 0, rows, C, int(weight is not None), float(norm_eps),
+        head_dim = int(head_dim) if rope else 0
+        rc = lib.mhla_qk_prologue_rope(x2.data_ptr(), x2.stride(0), _ptr(w), y.data_ptr(), C, yr.data_ptr() if rope else None, C, *_rope_args(cos, sin),
+                                       cos.shape[0] if rope else 0, head_dim, rows, C, int(weight is not None), float(norm_eps),
                                        float(eps), _dtype_code(x2), _stream())
-        _lib.check(rc, "mhla_qk_prologue_rope")
+        if rc:
+            _lib.check(rc, "mhla_qk_prologue_rope")
         ctx.save_for_backward(x2, w, cos, sin)
-        ctx.cfg = (x.shape, float(norm_eps), int(head_dim) if rope else 0, weight.dtype if weight is not None else None)
+        ctx.cfg = (x.shape, float(norm_eps), head_dim, weight.dtype if weight is not None else None)
         if rope:
             return y.reshape(x.shape), yr.reshape(x.shape)
         return y.reshape(x.shape), None
@@ -911,12 +916,13 @@ class _QkPrologue(torch.autograd.Function):
         if w is not None:
             dwp = torch.empty((lib.mhla_qk_prologue_dw_rows(rows), C), dtype=torch.float32, device=x2.device)
         rope = dyr is not None
+        if not rope:   # no gradient arrived for the rotated output: the call is the one of a forward without tables
+            cos, sin, head_dim = None, None, 0
         rc = lib.mhla_qk_prologue_bwd(x2.data_ptr(), x2.stride(0), _ptr(w), _ptr(dy), C, dyr.data_ptr() if rope else None, C,
-                                      cos.data_ptr() if rope else None, sin.data_ptr() if rope else None,
-                                      cos.stride(0) if rope else 0, cos.shape[0] if rope else 0, head_dim if rope else 0,
-                                      dx.data_ptr(), C, _ptr(dwp), rows, C,
+                                      *_rope_args(cos, sin), cos.shape[0] if rope else 0, head_dim, dx.data_ptr(), C, _ptr(dwp), rows, C,
                                       int(w is not None), norm_eps, _dtype_code(x2), _stream())
-        _lib.check(rc, "mhla_qk_prologue_bwd")
+        if rc:
+            _lib.check(rc, "mhla_qk_prologue_bwd")
         dw = dwp.sum(0).to(w_dtype) if dwp is not None else None
         return dx.reshape(shape), dw, None, None, None, None, None
 
@@ -1127,10 +1133,6 @@ def _expand_kv(t: torch.Tensor, G: int) -> torch.Tensor:
     differentiable expand + reshape: autograd sums the G gradients of a head back onto it."""
     B, T, Hkv, D = t.shape
     return t[:, :, :, None, :].expand(B, T, Hkv, G, D).reshape(B, T, Hkv * G, D)
-
-
-def _wants_grad(*ts) -> bool:
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
 @_device_guard

@@ -1,6 +1,7 @@
-"""A stand-in for libmhla_hip.so that records the decode calls of `mhla_amd.ops` instead of launching them, so that the host layer
-(checks, slicing, marshalling) runs on CPU tensors, without a GPU.  Used by tools/record_decode_calls.py and
-tests/test_decode_calls_cpu.py.
+"""A stand-in for libmhla_hip.so that records the library calls of `mhla_amd.ops` instead of launching them, so that a host layer
+(checks, slicing, marshalling) runs on CPU tensors, without a GPU.  It began with the decode section and serves every section of
+`ops.py` whose nodes are Python: used by tools/record_decode_calls.py and tests/test_decode_calls_cpu.py (causal decode) and by
+tools/record_blockmix_calls.py and tests/test_blockmix_calls_cpu.py (block-mix operators, LePE, rotary and q / k prologues).
 
     with Session(ops, _lib) as s:
         s.name(q=q, k=k, v=v, mix=mix, S=state.S, P=state.P, Cur=state.Cur, pos=state.pos)
@@ -8,7 +9,9 @@ tests/test_decode_calls_cpu.py.
     s.calls   # [Call(name, args)], s.lines: the same as text
 
 Inside the `with`, `ops._require_gpu` and `ops._stream` are stubs and `_lib.load()` returns the recorder: every launching entry point
-is logged and returns 0, the `*_ws_bytes` queries (host arithmetic) go to the real library.  An argument is recorded by its C type:
+is logged and returns 0; the entry points that are host arithmetic (`*_ws_bytes`, `*_keeps_state`, `*_ok`, `*_dw_rows`, `*_fusable`,
+the two `describe` calls, `mhla_set_option`, `mhla_abi_version`, `mhla_build_flags`) go to the real library, and the text log
+(`lines`, not `calls`) shows each with its integer arguments and its result.  An argument is recorded by its C type:
 a view as ("view", base, element offset, sb, sn, sh), a pointer as ("ptr", base, byte offset), a workspace as ("ws", bytes), a null
 as ("null",), a scalar as itself.  `base` is the name a tensor was given with `name()`; storage allocated inside the call is named
 "new<n>" in order of allocation (a dispatch mode sees every allocation and keeps it alive until the call returns, so that no
@@ -42,6 +45,11 @@ class _Allocations(TorchDispatchMode):
         return out
 
 
+# entry points that launch nothing: answered by the real library
+_HOST_SUFFIXES = ("_ws_bytes", "_keeps_state", "_ok", "_dw_rows", "_fusable")
+_HOST_NAMES = ("mhla_describe_dispatch", "mhla_causal_describe_dispatch", "mhla_set_option", "mhla_abi_version", "mhla_build_flags")
+
+
 class _Recorder:
     """What `_lib.load()` returns inside a Session."""
 
@@ -51,8 +59,10 @@ class _Recorder:
     def __getattr__(self, name):
         if name.startswith("__") or name not in self._session.lib_mod.SIGNATURES:
             raise AttributeError(name)
-        if name.endswith("_ws_bytes") or name == "mhla_last_error":
+        if name == "mhla_last_error":
             return getattr(self._real, name)
+        if name.endswith(_HOST_SUFFIXES) or name in _HOST_NAMES:
+            return lambda *args: self._session._passed_through(name, args, getattr(self._real, name)(*args))
         return lambda *args: self._session._record(name, args)
 
 
@@ -130,6 +140,11 @@ class Session:
         self.calls.append(Call(name, tuple(out)))
         self.lines.append(f"  {name}({', '.join(map(repr, out))})")
         return 0
+
+    def _passed_through(self, name, args, result):
+        shown = ", ".join(repr(a) if isinstance(a, (int, float, bytes)) else "buffer" for a in args)
+        self.lines.append(f"  {name}({shown}) = {result!r}")
+        return result
 
     def call(self, label, fn, *args, state=None, catch=True, **kw):
         """Run one public call: its library calls, then its result (shape and base), or the exception's type and message, then

@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """Where the host time of an eager operator call goes (cProfile over many un-synchronised fwd+bwd calls of the C3 shape):
-python tools/host_overhead.py [iters] [--python-nodes] [--causal]
+python tools/host_overhead.py [iters] [--python-nodes] [--causal | --dit-core]
 --python-nodes: the autograd nodes of ops.py (ops.USE_NATIVE_NODES = False) instead of the C++ ones, where those are built.
---causal: the same loop on mhla_causal (B = 2, T = 512, H = 2, K = 64, V = 128, bf16) instead of mhla_blockmix."""
+--causal: the same loop on mhla_causal (B = 2, T = 512, H = 2, K = 64, V = 128, bf16) instead of mhla_blockmix.
+--dit-core: the same loop on mhla_dit_core at the DiT shape (packed qkv [32, 256, 3, 16, 72] bf16, M = 16, pieces_len = block_len = 4,
+a 3 x 3 LePE weight with bias): the node has no C++ twin, so this is what the DiT module pays on every call."""
 import argparse
 import cProfile
 import os
@@ -21,6 +23,7 @@ ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDe
 ap.add_argument("iters", nargs="?", type=int, default=300)
 ap.add_argument("--python-nodes", action="store_true")
 ap.add_argument("--causal", action="store_true")
+ap.add_argument("--dit-core", action="store_true")
 a = ap.parse_args()
 iters = a.iters
 if a.python_nodes:
@@ -33,6 +36,14 @@ if a.causal:
     W = mhla_amd.causal_mixing_init(T // 64).reshape(T // 64, T // 64).cuda().requires_grad_(True)
     do = torch.randn(B, T, H, V, generator=g).to(torch.bfloat16).cuda()
     op = mhla_amd.mhla_causal
+elif a.dit_core:
+    B, N, H, D, M = 32, 256, 16, 72, 16
+    qkv = (torch.rand(B, N, 3, H, D, generator=g) + 0.01).to(torch.bfloat16).cuda().requires_grad_(True)
+    W = block_distance_weights((4, 4), "linear").cuda().requires_grad_(True)
+    lepe_w = (0.1 * torch.randn(H * D, 1, 3, 3, generator=g)).cuda().requires_grad_(True)
+    lepe_b = (0.1 * torch.randn(H * D, generator=g)).cuda().requires_grad_(True)
+    do = torch.randn(B, N, H * D, generator=g).to(torch.bfloat16).cuda()
+    op = ops.mhla_dit_core
 else:
     B, N, H, D, M = 32, 256, 16, 72, 16
     mk = lambda: (torch.rand(B, N, H, D, generator=g) + 0.01).to(torch.bfloat16).cuda().requires_grad_(True)
@@ -40,11 +51,11 @@ else:
     W = block_distance_weights((4, 4), "linear").cuda().requires_grad_(True)
     do = torch.randn(B, N, H, D, generator=g).to(torch.bfloat16).cuda()
     op = mhla_amd.mhla_blockmix
-print(f"{op.__name__}, {'C++' if ops._native_nodes() else 'Python'} autograd nodes")
+print(f"{op.__name__}, {'C++' if ops._native_nodes() and not a.dit_core else 'Python'} autograd nodes")
 
 
 def step():
-    out = op(q, k, v, W)
+    out = op(qkv, W, lepe_w, lepe_b, 4, 4) if a.dit_core else op(q, k, v, W)
     out.backward(do)
 
 
