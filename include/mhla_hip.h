@@ -582,6 +582,58 @@ int mhla_causal_verify_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const f
                                   mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
                                   int dtype, void* stream);
 
+/* Slotted calls: steps, extends and prefills on CHOSEN ROWS of a state pool (added without a change of any existing signature or
+ * behaviour: MHLA_ABI_VERSION stays 9).  A pool is an ordinary ragged state with n_slots batch rows -- S [n_slots][Hkv][cap_chunks][K][V],
+ * P and Cur [n_slots][Hkv][K][V], pos_dev (and full_dev) int32 [n_slots] -- that outlives the calls; a server keeps every request in its
+ * row while the set of live requests changes from token to token, without concatenating or gathering states.  Each call below is its
+ * namesake (mhla_causal_step_ragged, _step_dev, _extend_ragged, _verify_ragged, _commit_ragged, _varlen_state_init) with a map after
+ * pos_dev: `slot_dev`, device int32 [B], and `n_slots`.  Call row b works on row slot_dev[b] of the pool: everything the call reads or
+ * writes of the STATE -- S, P, Cur, pos_dev, full_dev -- is addressed by slot_dev[b]; everything that belongs to the CALL -- q, k, v,
+ * gate, out, y, the workspace, ntok_dev, accept_dev -- stays addressed by b.  The calls that take q also take `Hkv` after `H`
+ * (Hkv = H: the ungrouped call; otherwise as the *_gqa forms above), so there are no separate grouped twins; the commit and the
+ * prefill touch no q and take the k/v head count as H, as their namesakes.
+ * Row b gets, bit for bit, what the namesake gives that row on a compact state holding copies of the chosen rows in call order: the
+ * same launches, tiles and order of every sum, the K split of the step chosen from the call's B H.  Rows of the pool the call does
+ * not name keep every bit of S, P, Cur, pos_dev and full_dev.  The map is the caller's contract: entries are distinct -- DUPLICATES ARE
+ * THE CALLER'S ERROR, rows that share a slot race on it.  An entry outside 0 .. n_slots - 1 (a caller's mark such as -1) never
+ * addresses anything: that call row is INACTIVE, its rows of out / y are written as zeros (the frozen / skipped behaviour of the
+ * namesake) and no state, position or flag is touched -- for mhla_causal_step_dev_slots a map rewritten in place between the
+ * replays of a captured graph is how requests join and leave.  mhla_causal_varlen_state_init_slots writes sequence s of the pack into
+ * row slot_dev[s]: the finished chunks of S, P and Cur of THOSE rows only (the namesake handed the pool would write P and Cur of every
+ * row); seq_len_dev stays indexed by s, pos_dev of the pool is the caller's to set.
+ * Checks, before any launch: slot_dev non-null and 4-byte aligned, n_slots > 0 (MHLA_EINVAL); then those of the namesake with B
+ * (n_seqs) counting call rows -- B*H <= 65535 as before, n_slots is not bounded by the grid.  The host values that vouch for device
+ * arrays (max_pos, any_boundary, max_end, max_later, any_close) are computed by the caller over the SELECTED rows.  Workspaces: the
+ * namesakes' functions (mhla_causal_step_ws_bytes, mhla_causal_extend_ragged_gqa_ws_bytes, mhla_causal_commit_ragged_ws_bytes) with the
+ * call's B -- they do not depend on the pool. */
+int mhla_causal_step_slots(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                           int32_t* pos_dev, const int32_t* slot_dev, int n_slots, int64_t max_pos, int any_boundary, mhla_mview out,
+                           mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv,
+                           int K, int V, int chunk, float scale, int dtype, void* stream);
+int mhla_causal_step_dev_slots(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                               float* Cur, int32_t* pos_dev, const int32_t* slot_dev, int n_slots, int32_t* full_dev, const void* rope_cos,
+                               const void* rope_sin, int64_t ld_tab, int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate,
+                               const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K,
+                               int V, int chunk, float scale, int dtype, void* stream);
+int mhla_causal_extend_slots(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                             float* Cur, int32_t* pos_dev, const int32_t* slot_dev, int n_slots, const int32_t* ntok_dev, int T,
+                             int64_t max_end, int max_later, int any_close, int left_padded, mhla_mview out, mhla_view gate,
+                             const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V,
+                             int chunk, float scale, int dtype, void* stream);
+int mhla_causal_verify_slots(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                             float* Cur, const int32_t* pos_dev, const int32_t* slot_dev, int n_slots, const int32_t* ntok_dev, int T,
+                             int64_t max_end, int max_later, int any_close, int left_padded, mhla_mview out, mhla_view gate,
+                             const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V,
+                             int chunk, float scale, int dtype, void* stream);
+int mhla_causal_commit_slots(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                             int32_t* pos_dev, const int32_t* slot_dev, int n_slots, const int32_t* ntok_dev, const int32_t* accept_dev, int T,
+                             int64_t max_end, int max_later, int any_close, int left_padded, void* ws, size_t ws_bytes, int B, int H, int K,
+                             int V, int chunk, int dtype, void* stream);
+int mhla_causal_varlen_state_init_slots(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                                        int n_seqs, const int32_t* seq_len_dev, const int32_t* slot_dev, int n_slots, int max_len, int T, int H,
+                                        int K, int V, int chunk, int n_chunks, const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev,
+                                        int dtype, void* stream);
+
 /* ---- prologue: q / k of the Wan host -------------------------------------- */
 
 /*

@@ -125,6 +125,25 @@ SIGNATURES = {
     "mhla_causal_verify_ragged_gqa": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                               c_int64, c_int, c_int, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int,
                                               c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    # slotted calls: the ragged namesakes on chosen rows of a state pool -- (slot_dev, n_slots) after pos_dev, Hkv after H where q is taken
+    "mhla_causal_step_slots": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                       c_int64, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
+                                       c_int, c_int, c_float, c_int, c_void_p]),
+    "mhla_causal_step_dev_slots": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, View, View, c_void_p, c_float, View, c_void_p,
+                                           c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "mhla_causal_extend_slots": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                         c_void_p, c_int, c_int64, c_int, c_int, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t,
+                                         c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "mhla_causal_verify_slots": (c_int, [View, View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                         c_void_p, c_int, c_int64, c_int, c_int, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t,
+                                         c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "mhla_causal_commit_slots": (c_int, [View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int,
+                                         c_int, c_void_p]),
+    "mhla_causal_varlen_state_init_slots": (c_int, [View, View, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                                    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                                    c_void_p]),
     "mhla_causal_fwd_gqa": (c_int, [View, View, View, c_void_p, c_int, View, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_int, c_float, c_int, c_uint, c_void_p]),
     "mhla_causal_normgate_fwd_gqa": (c_int, [View, View, View, c_void_p, c_int, View, View, c_void_p, c_float, View, c_void_p,

@@ -126,6 +126,9 @@ struct StateArgsDst : StateArgsVar {
     float* Sq;     // [nseq][H][cap][DX][DY]
     float* Cur;    // [nseq][H][DX][DY]
     int nseq, cap;
+    // mhla_causal_varlen_state_init_slots: Sq and Cur are a pool of n_slots rows, sequence s of the pack goes to row slot[s]
+    const int* slot;  // [nseq], 4-byte aligned, or null: row s itself
+    int n_slots;
 };
 
 template <int DT>
@@ -253,7 +256,12 @@ __global__ __launch_bounds__(NTHREADS) void k_bm_state(const A a) {
         const tab2_t d = {ld_tab1(a.dst, 2 * blk), ld_tab1(a.dst, 2 * blk + 1)};
         const bool whole = S == a.S;
         if ((unsigned)d.x >= (unsigned)a.nseq || (whole && (unsigned)d.y >= (unsigned)a.cap)) return;   // (workgroup-uniform)
-        const long sh = (long)d.x * a.H + h;
+        int row = d.x;
+        if (a.slot) {   // the state is a pool: sequence d.x of the pack lives in row slot[d.x] of it, none outside 0 .. n_slots - 1
+            row = ld_tab1(a.slot, d.x);
+            if ((unsigned)row >= (unsigned)a.n_slots) return;
+        }
+        const long sh = (long)row * a.H + h;
         ob = whole ? a.Sq + (sh * a.cap + d.y) * DX * DY : a.Cur + sh * DX * DY;
     } else {
         ob = a.out + ((long)bh * a.M + blk) * DX * DY;

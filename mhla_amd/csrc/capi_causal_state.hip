@@ -1,5 +1,5 @@
 // C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
-// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged, and the grouped-query forms mhla_causal_*_gqa of the ragged entry points; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged, the grouped-query forms mhla_causal_*_gqa of the ragged entry points, and their forms on chosen rows of a state pool, mhla_causal_*_slots; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
@@ -52,6 +52,17 @@ int cst_check_dev(const char* name, const void* p) {   // an int32 array on the 
     if (!p || ((uintptr_t)p) % 4) return fail(MHLA_EINVAL, "%s null or not 4-byte aligned", name);
     return MHLA_OK;
 }
+// the slot map of a slotted call (the *_slots entry points): call row b works on row map[b] of a state pool of n rows; map null:
+// the un-slotted namesake, row b itself
+struct Slots {
+    const int32_t* map = nullptr;
+    int n = 0;
+};
+int cst_check_slots(const int32_t* slot_dev, int n_slots) {
+    RC(cst_check_dev("slot_dev", slot_dev));
+    if (n_slots <= 0) return fail(MHLA_EINVAL, "n_slots=%d must be positive", n_slots);
+    return MHLA_OK;
+}
 int cst_check_mix(const float* mix, int ldmix, int64_t lastrow) {   // lastrow: the last row of mix the call reads, up to its diagonal
     if (!mix || ldmix < lastrow + 1)
         return fail(MHLA_EINVAL, "mix null or ldmix=%d < %lld (row %lld of mix is read)", ldmix, (long long)(lastrow + 1), (long long)lastrow);
@@ -74,10 +85,11 @@ int cst_roll(float* S, int cap, float* P, float* Cur, const float* mixrow, int n
     return launch(k_cs_roll<false>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll", r);
 }
 // the roll of a ragged state: each sequence for itself, by pos_dev (the position of the token its step just took)
-int cst_roll_ragged(float* S, int cap, float* P, float* Cur, const int32_t* pos_dev, const float* mix, int ldmix, int max_pos, int H, int BH,
-                    long E, hipStream_t st) {
-    const CsRollArgs r{S, P, Cur, nullptr, E, cap, 0, 0, pos_dev, mix, ldmix, max_pos, H};
-    return launch(k_cs_roll<true>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll_ragged", r);
+int cst_roll_ragged(float* S, int cap, float* P, float* Cur, const int32_t* pos_dev, Slots sl, const float* mix, int ldmix, int max_pos, int H,
+                    int BH, long E, hipStream_t st) {
+    const CsRollArgs r{S, P, Cur, nullptr, E, cap, 0, 0, pos_dev, mix, ldmix, max_pos, H, sl.map, sl.n};
+    return launch(sl.map ? k_cs_roll<true, false, true> : k_cs_roll<true>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st,
+                  "k_cs_roll_ragged", r);
 }
 int cst_zero_cur(float* Cur, int BH, long E, hipStream_t st) {
     hipError_t e = hipMemsetAsync(Cur, 0, (size_t)BH * E * 4, st);
@@ -111,11 +123,12 @@ int cst_xty(const mhla_view& k, const mhla_view& v, long tok0, long ntok, float*
 // the chunks of a pack (B = 1), each tile into its sequence's state: a whole chunk to S[seq][h][loc], a ragged one to Cur[seq][h]
 template <typename T>
 int cst_xty_pack(const mhla_view& k, const mhla_view& v, float* S, int cap, float* Cur, int n_seqs, int n_chunks, const int* tab, const int* dst,
-                 int T_, int H, int K, int V, hipStream_t st) {
+                 Slots sl, int T_, int H, int K, int V, hipStream_t st) {
     StateArgsDst a{};
     a.x = cv(k); a.y = cv(v);
     a.H = H; a.M = 0; a.S = CS; a.D = 64; a.DX = K; a.DY = V; a.T = T_; a.alpha = 1.f;
     a.tab = (const tab2_t*)tab; a.dst = dst; a.Sq = S; a.Cur = Cur; a.nseq = n_seqs; a.cap = cap;
+    a.slot = sl.map; a.n_slots = sl.n;
     const int strips = ((K + 63) / 64) * ((V + 63) / 64);
     return launch(k_bm_state<T, 4, 2, StateArgsDst>, dim3((unsigned)n_chunks, H, strips), dim3(NTHREADS), state_smem_floats<4>() * 4, st,
                   "k_bm_state<2,dst>", a);
@@ -176,7 +189,7 @@ int cx_rag_check(int T, int cap_chunks, const int32_t* pos_dev, const int32_t* n
 // Hkv < H (grouped-query heads): the launches that form or move state run over the B Hkv k/v heads, the two that compute rows
 // (k_cx_out, the finish) over the B H query heads
 int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
-                    float* Cur, int32_t* pos_dev, const int32_t* ntok_dev, int T, int64_t max_end, int max_later, int any_close,
+                    float* Cur, int32_t* pos_dev, Slots sl, const int32_t* ntok_dev, int T, int64_t max_end, int max_later, int any_close,
                     int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws,
                     size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream) {
     RC(cst_check(B, H, K, V, chunk, dtype));
@@ -193,7 +206,8 @@ int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float
     float* tiles = (float*)ws;
     float* stage = tiles + p.tiles;
     int* nval = (int*)(stage + p.stage);
-    const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0, dry ? 1 : 0};
+    const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0, dry ? 1 : 0, nullptr,
+                  sl.map, sl.n};
     const int kr = cst_rows((size_t)H, K, V);   // a one-token sequence: the step's K split for a batch of one
     // every launch but the last addresses by pos_dev; the last, which does not, advances it (dry: does not)
     DISPATCH_T(dtype, {
@@ -220,8 +234,9 @@ int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float
             }
         }
         CsFinishArgs f{stage, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, 1, dry ? nullptr : pos_dev};
-        f.nval = nval; f.left = left_padded ? 1 : 0;
-        RC(launch(k_cs_step_finish<ET, false, true>, dim3(BH, T), dim3(CST_THREADS), 0, st, "k_cs_step_finish_ragged", f));
+        f.nval = nval; f.left = left_padded ? 1 : 0; f.slot = sl.map; f.n_slots = sl.n;
+        RC(launch(sl.map ? k_cs_step_finish<ET, false, true, true> : k_cs_step_finish<ET, false, true>, dim3(BH, T), dim3(CST_THREADS), 0, st,
+                  "k_cs_step_finish_ragged", f));
     });
     return MHLA_OK;
 }
@@ -229,7 +244,7 @@ int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float
 // the ragged step chain (step, roll, finish); Hkv < H (grouped-query heads): step and roll run over the B Hkv k/v heads, the step
 // writing the partial sums of all B H query heads, which the finish reads as ever
 int cs_step_ragged_chain(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
-                         float* Cur, int32_t* pos_dev, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate,
+                         float* Cur, int32_t* pos_dev, Slots sl, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate,
                          const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V,
                          int chunk, float scale, int dtype, void* stream) {
     RC(cst_check(B, H, K, V, chunk, dtype));
@@ -250,18 +265,22 @@ int cs_step_ragged_chain(mhla_view q, mhla_view k, mhla_view v, const float* mix
     // step and roll address by pos_dev; the finish, which does not, advances it: last in the chain
     DISPATCH_T(dtype, {
         CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, Hkv, K, V, 0, 0, pos_dev, ldmix, (int)max_pos};
-        if (G == 1) RC(cst_step(k_cs_step<ET, true>, "k_cs_step_ragged", s, BH, st));
-        else        RC(cst_step(k_cs_step<ET, true, false, false, CST_GMAX>, "k_cs_step_ragged<gqa>", s, BH, st, G));
-        if (any_boundary) RC(cst_roll_ragged(S, cap_chunks, P, Cur, pos_dev, mix, ldmix, (int)max_pos, Hkv, B * Hkv, (long)K * V, st));
-        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit, pos_dev};
-        RC(launch(k_cs_step_finish<ET>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
+        s.slot = sl.map; s.n_slots = sl.n;
+        // (a slotted call: the kernels' SLOT instantiations; the un-slotted ones are the code they were)
+        if (G == 1) RC(cst_step(sl.map ? k_cs_step<ET, true, false, false, 1, true> : k_cs_step<ET, true>, "k_cs_step_ragged", s, BH, st));
+        else        RC(cst_step(sl.map ? k_cs_step<ET, true, false, false, CST_GMAX, true> : k_cs_step<ET, true, false, false, CST_GMAX>,
+                                "k_cs_step_ragged<gqa>", s, BH, st, G));
+        if (any_boundary) RC(cst_roll_ragged(S, cap_chunks, P, Cur, pos_dev, sl, mix, ldmix, (int)max_pos, Hkv, B * Hkv, (long)K * V, st));
+        CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit, pos_dev};
+        f.slot = sl.map; f.n_slots = sl.n;
+        RC(launch(sl.map ? k_cs_step_finish<ET, false, false, true> : k_cs_step_finish<ET>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish", f));
     });
     return MHLA_OK;
 }
 
 // the device-positioned step chain; Hkv < H as in cs_step_ragged_chain (the fused prologue: k once per k/v head, q per query head)
 int cs_step_dev_chain(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
-                      float* Cur, int32_t* pos_dev, int32_t* full_dev, const void* rope_cos, const void* rope_sin, int64_t ld_tab,
+                      float* Cur, int32_t* pos_dev, Slots sl, int32_t* full_dev, const void* rope_cos, const void* rope_sin, int64_t ld_tab,
                       int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                       mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale, int dtype,
                       void* stream) {
@@ -293,18 +312,86 @@ int cs_step_dev_chain(mhla_view q, mhla_view k, mhla_view v, const float* mix, i
     DISPATCH_T(dtype, {
         CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, Hkv, K, V, 0, 0, pos_dev, ldmix, max_pos,
                      rope_cos, rope_sin, (long)ld_tab, (int)tab_rows, feature_map};
+        s.slot = sl.map; s.n_slots = sl.n;
         if (G == 1) {
-            if (pro) RC(cst_step(k_cs_step<ET, true, true, true>, "k_cs_step_dev<pro>", s, BH, st));
-            else     RC(cst_step(k_cs_step<ET, true, true, false>, "k_cs_step_dev", s, BH, st));
+            if (pro) RC(cst_step(sl.map ? k_cs_step<ET, true, true, true, 1, true> : k_cs_step<ET, true, true, true>, "k_cs_step_dev<pro>", s, BH, st));
+            else     RC(cst_step(sl.map ? k_cs_step<ET, true, true, false, 1, true> : k_cs_step<ET, true, true, false>, "k_cs_step_dev", s, BH, st));
         } else {
-            if (pro) RC(cst_step(k_cs_step<ET, true, true, true, CST_GMAX>, "k_cs_step_dev<pro,gqa>", s, BH, st, G));
-            else     RC(cst_step(k_cs_step<ET, true, true, false, CST_GMAX>, "k_cs_step_dev<gqa>", s, BH, st, G));
+            if (pro) RC(cst_step(sl.map ? k_cs_step<ET, true, true, true, CST_GMAX, true> : k_cs_step<ET, true, true, true, CST_GMAX>,
+                                 "k_cs_step_dev<pro,gqa>", s, BH, st, G));
+            else     RC(cst_step(sl.map ? k_cs_step<ET, true, true, false, CST_GMAX, true> : k_cs_step<ET, true, true, false, CST_GMAX>,
+                                 "k_cs_step_dev<gqa>", s, BH, st, G));
         }
-        RC(cst_roll_ragged(S, cap_chunks, P, Cur, pos_dev, mix, ldmix, max_pos, Hkv, B * Hkv, (long)K * V, st));
-        const CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit, pos_dev, max_pos, full_dev};
-        RC(launch(k_cs_step_finish<ET, true>, dim3(BH), dim3(CST_THREADS), 0, st, "k_cs_step_finish_dev", f));
+        RC(cst_roll_ragged(S, cap_chunks, P, Cur, pos_dev, sl, mix, ldmix, max_pos, Hkv, B * Hkv, (long)K * V, st));
+        CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit, pos_dev, max_pos, full_dev};
+        f.slot = sl.map; f.n_slots = sl.n;
+        RC(launch(sl.map ? k_cs_step_finish<ET, true, false, true> : k_cs_step_finish<ET, true>, dim3(BH), dim3(CST_THREADS), 0, st,
+                  "k_cs_step_finish_dev", f));
     });
     return MHLA_OK;
+}
+
+// the pack prefill chain (the chunks' K^T V into their sequences' states, then every sequence's prefix mix); slotted: sequence s of the
+// pack into row sl.map[s] of the pool -- S, P and Cur of those rows only, seq_len_dev stays indexed by s
+int cs_pack_chain(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur, int n_seqs,
+                  const int32_t* seq_len_dev, Slots sl, int max_len, int T, int H, int K, int V, int chunk, int n_chunks,
+                  const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, int dtype, void* stream) {
+    RC(cst_check(1, H, K, V, chunk, dtype));
+    if (n_seqs <= 0) return fail(MHLA_EINVAL, "n_seqs=%d must be positive", n_seqs);
+    if ((size_t)n_seqs * H > 65535) return fail(MHLA_ENOTSUP, "n_seqs*H=%zu exceeds grid limit 65535", (size_t)n_seqs * H);
+    if (T <= 0 || n_chunks <= 0) return fail(MHLA_EINVAL, "T=%d n_chunks=%d must be positive (an all-empty pack is an all-zero state)", T, n_chunks);
+    CHECK_VIEW(k); CHECK_VIEW(v);
+    RC(cst_check_state(S, cap_chunks, P, Cur));
+    if (n_chunks < (T + chunk - 1) / chunk || n_chunks > T)
+        return fail(MHLA_EINVAL, "n_chunks=%d outside ceil(T / %d)=%d .. T=%d", n_chunks, chunk, (T + chunk - 1) / chunk, T);
+    if (max_len < 0 || max_len > T) return fail(MHLA_EINVAL, "max_len=%d outside 0 .. T=%d", max_len, T);
+    if ((max_len + chunk - 1) / chunk > cap_chunks)
+        return fail(MHLA_EINVAL, "max_len=%d tokens need %d chunks, the state holds %d", max_len, (max_len + chunk - 1) / chunk, cap_chunks);
+    // sequence s reads row len[s] / 64 of mix up to its diagonal unless its state is then full: the longest one's row covers all
+    RC(cst_check_mix(mix, ldmix, std::min(max_len / chunk, cap_chunks - 1)));
+    RC(cst_check_dev("seq_len_dev", seq_len_dev));
+    RC(cst_check_dev("chunk_dst_dev", chunk_dst_dev));
+    if (!chunk_tab_dev || ((uintptr_t)chunk_tab_dev) % 8) return fail(MHLA_EINVAL, "chunk_tab_dev null or not 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_T(dtype, { RC(cst_xty_pack<ET>(k, v, S, cap_chunks, Cur, n_seqs, n_chunks, chunk_tab_dev, chunk_dst_dev, sl, T, H, K, V, st)); });
+    const long E = (long)K * V;
+    const CsRollArgs r{S, P, Cur, nullptr, E, cap_chunks, 0, 0, seq_len_dev, mix, ldmix, max_len, H, sl.map, sl.n};
+    return launch(sl.map ? k_cs_roll<false, true, true> : k_cs_roll<false, true>, dim3((unsigned)((E / 4 + 63) / 64), n_seqs * H), dim3(64), 0, st,
+                  "k_cs_roll_pack", r);
+}
+
+// the commit chain: the state half of the ragged extend on the accepted tokens, no q and no rows (H: the k/v heads)
+int cx_commit_chain(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur, int32_t* pos_dev,
+                    Slots sl, const int32_t* ntok_dev, const int32_t* accept_dev, int T, int64_t max_end, int max_later, int any_close,
+                    int left_padded, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, int dtype, void* stream) {
+    RC(cst_check(B, H, K, V, chunk, dtype));
+    if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive", T);
+    if (T > 65535) return fail(MHLA_EINVAL, "T=%d exceeds 65535 tokens per call", T);
+    CHECK_VIEW(k); CHECK_VIEW(v);
+    RC(cst_check_state(S, cap_chunks, P, Cur));
+    RC(cst_check_dev("accept_dev", accept_dev));
+    RC(cx_rag_check(T, cap_chunks, pos_dev, ntok_dev, max_end, max_later, any_close, mix, ldmix));
+    RC(cst_check_ws(ws, ws_bytes, al4((size_t)B) * 4));
+    hipStream_t st = (hipStream_t)stream;
+    const int BH = B * H, strips = ((K + 63) / 64) * ((V + 63) / 64);
+    const long E = (long)K * V;
+    int* nval = (int*)ws;
+    const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0, 0, accept_dev, sl.map, sl.n};
+    // every launch but the last addresses by pos_dev; the last, which does not, advances it
+    DISPATCH_T(dtype, {
+        CxAccArgs c{};
+        c.x = cv(k); c.y = cv(v); c.H = H; c.DX = K; c.DY = V; c.rag = g; c.later = 0; c.S = S; c.Cur = Cur; c.nval = nval;
+        RC(launch(k_cx_xty_acc<ET, true>, dim3(1, BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+        if (any_close) {
+            c.later = 1;
+            RC(launch(k_cx_xty_acc<ET, true>, dim3(std::max(1, max_later), BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+            CxMixRagArgs m{};
+            m.m.S = S; m.m.ws = nullptr; m.m.P = P; m.m.mix = mix; m.m.E = E; m.m.ldmix = ldmix; m.m.cap = cap_chunks;
+            m.rag = g; m.H = H;
+            RC(launch(k_cx_mix_ragged, dim3((unsigned)((E / 4 + 63) / 64), BH, 1), dim3(64), 0, st, "k_cx_mix_ragged", m));
+        }
+    });
+    return launch(k_cx_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, "k_cx_advance", pos_dev, (const int*)nval, B, sl.map, sl.n);
 }
 
 }  // namespace
@@ -341,27 +428,17 @@ int mhla_causal_state_init(mhla_view k, mhla_view v, const float* mix, int ldmix
 int mhla_causal_varlen_state_init(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
                                   int n_seqs, const int32_t* seq_len_dev, int max_len, int T, int H, int K, int V, int chunk, int n_chunks,
                                   const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, int dtype, void* stream) {
-    RC(cst_check(1, H, K, V, chunk, dtype));
-    if (n_seqs <= 0) return fail(MHLA_EINVAL, "n_seqs=%d must be positive", n_seqs);
-    if ((size_t)n_seqs * H > 65535) return fail(MHLA_ENOTSUP, "n_seqs*H=%zu exceeds grid limit 65535", (size_t)n_seqs * H);
-    if (T <= 0 || n_chunks <= 0) return fail(MHLA_EINVAL, "T=%d n_chunks=%d must be positive (an all-empty pack is an all-zero state)", T, n_chunks);
-    CHECK_VIEW(k); CHECK_VIEW(v);
-    RC(cst_check_state(S, cap_chunks, P, Cur));
-    if (n_chunks < (T + chunk - 1) / chunk || n_chunks > T)
-        return fail(MHLA_EINVAL, "n_chunks=%d outside ceil(T / %d)=%d .. T=%d", n_chunks, chunk, (T + chunk - 1) / chunk, T);
-    if (max_len < 0 || max_len > T) return fail(MHLA_EINVAL, "max_len=%d outside 0 .. T=%d", max_len, T);
-    if ((max_len + chunk - 1) / chunk > cap_chunks)
-        return fail(MHLA_EINVAL, "max_len=%d tokens need %d chunks, the state holds %d", max_len, (max_len + chunk - 1) / chunk, cap_chunks);
-    // sequence s reads row len[s] / 64 of mix up to its diagonal unless its state is then full: the longest one's row covers all
-    RC(cst_check_mix(mix, ldmix, std::min(max_len / chunk, cap_chunks - 1)));
-    RC(cst_check_dev("seq_len_dev", seq_len_dev));
-    RC(cst_check_dev("chunk_dst_dev", chunk_dst_dev));
-    if (!chunk_tab_dev || ((uintptr_t)chunk_tab_dev) % 8) return fail(MHLA_EINVAL, "chunk_tab_dev null or not 8-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_T(dtype, { RC(cst_xty_pack<ET>(k, v, S, cap_chunks, Cur, n_seqs, n_chunks, chunk_tab_dev, chunk_dst_dev, T, H, K, V, st)); });
-    const long E = (long)K * V;
-    const CsRollArgs r{S, P, Cur, nullptr, E, cap_chunks, 0, 0, seq_len_dev, mix, ldmix, max_len, H};
-    return launch(k_cs_roll<false, true>, dim3((unsigned)((E / 4 + 63) / 64), n_seqs * H), dim3(64), 0, st, "k_cs_roll_pack", r);
+    return cs_pack_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, n_seqs, seq_len_dev, Slots{}, max_len, T, H, K, V, chunk, n_chunks, chunk_tab_dev,
+                         chunk_dst_dev, dtype, stream);
+}
+
+int mhla_causal_varlen_state_init_slots(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                                        int n_seqs, const int32_t* seq_len_dev, const int32_t* slot_dev, int n_slots, int max_len, int T, int H,
+                                        int K, int V, int chunk, int n_chunks, const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev,
+                                        int dtype, void* stream) {
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cs_pack_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, n_seqs, seq_len_dev, Slots{slot_dev, n_slots}, max_len, T, H, K, V, chunk, n_chunks,
+                         chunk_tab_dev, chunk_dst_dev, dtype, stream);
 }
 
 int mhla_causal_step(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
@@ -392,7 +469,7 @@ int mhla_causal_step_ragged(mhla_view q, mhla_view k, mhla_view v, const float* 
                             float* Cur, int32_t* pos_dev, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate,
                             const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V,
                             int chunk, float scale, int dtype, void* stream) {
-    return cs_step_ragged_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, max_pos, any_boundary, out, gate, norm_w, norm_eps, y, ws,
+    return cs_step_ragged_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, max_pos, any_boundary, out, gate, norm_w, norm_eps, y, ws,
                                 ws_bytes, B, H, H, K, V, chunk, scale, dtype, stream);
 }
 
@@ -400,7 +477,7 @@ int mhla_causal_step_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const flo
                                 float* Cur, int32_t* pos_dev, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate,
                                 const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K,
                                 int V, int chunk, float scale, int dtype, void* stream) {
-    return cs_step_ragged_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, max_pos, any_boundary, out, gate, norm_w, norm_eps, y, ws,
+    return cs_step_ragged_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, max_pos, any_boundary, out, gate, norm_w, norm_eps, y, ws,
                                 ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
@@ -409,7 +486,7 @@ int mhla_causal_step_dev(mhla_view q, mhla_view k, mhla_view v, const float* mix
                          int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                          mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                          void* stream) {
-    return cs_step_dev_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, full_dev, rope_cos, rope_sin, ld_tab, tab_rows, feature_map,
+    return cs_step_dev_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, full_dev, rope_cos, rope_sin, ld_tab, tab_rows, feature_map,
                              out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, H, K, V, chunk, scale, dtype, stream);
 }
 
@@ -418,7 +495,7 @@ int mhla_causal_step_dev_gqa(mhla_view q, mhla_view k, mhla_view v, const float*
                              int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                              mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
                              int dtype, void* stream) {
-    return cs_step_dev_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, full_dev, rope_cos, rope_sin, ld_tab, tab_rows, feature_map,
+    return cs_step_dev_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, full_dev, rope_cos, rope_sin, ld_tab, tab_rows, feature_map,
                              out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
@@ -500,7 +577,7 @@ int mhla_causal_extend_ragged(mhla_view q, mhla_view k, mhla_view v, const float
                               int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                               mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                               void* stream) {
-    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, ntok_dev, T, max_end, max_later, any_close, left_padded,
+    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, ntok_dev, T, max_end, max_later, any_close, left_padded,
                            out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, H, K, V, chunk, scale, dtype, stream);
 }
 
@@ -509,7 +586,7 @@ int mhla_causal_extend_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const f
                                   int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                                   mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
                                   int dtype, void* stream) {
-    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, ntok_dev, T, max_end, max_later, any_close, left_padded,
+    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, ntok_dev, T, max_end, max_later, any_close, left_padded,
                            out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
@@ -518,7 +595,7 @@ int mhla_causal_verify_ragged(mhla_view q, mhla_view k, mhla_view v, const float
                               int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                               mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                               void* stream) {
-    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), ntok_dev, T, max_end, max_later, any_close, left_padded, out, gate, norm_w,
+    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), Slots{}, ntok_dev, T, max_end, max_later, any_close, left_padded, out, gate, norm_w,
                            norm_eps, y, ws, ws_bytes, B, H, H, K, V, chunk, scale, dtype, stream);
 }
 
@@ -527,7 +604,7 @@ int mhla_causal_verify_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const f
                                   int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                                   mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
                                   int dtype, void* stream) {
-    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), ntok_dev, T, max_end, max_later,
+    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), Slots{}, ntok_dev, T, max_end, max_later,
                            any_close, left_padded, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
@@ -540,34 +617,58 @@ int mhla_causal_commit_ragged(mhla_view k, mhla_view v, const float* mix, int ld
                               int32_t* pos_dev, const int32_t* ntok_dev, const int32_t* accept_dev, int T, int64_t max_end,
                               int max_later, int any_close, int left_padded, void* ws, size_t ws_bytes, int B, int H, int K, int V,
                               int chunk, int dtype, void* stream) {
-    RC(cst_check(B, H, K, V, chunk, dtype));
-    if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive", T);
-    if (T > 65535) return fail(MHLA_EINVAL, "T=%d exceeds 65535 tokens per call", T);
-    CHECK_VIEW(k); CHECK_VIEW(v);
-    RC(cst_check_state(S, cap_chunks, P, Cur));
-    RC(cst_check_dev("accept_dev", accept_dev));
-    RC(cx_rag_check(T, cap_chunks, pos_dev, ntok_dev, max_end, max_later, any_close, mix, ldmix));
-    RC(cst_check_ws(ws, ws_bytes, al4((size_t)B) * 4));
-    hipStream_t st = (hipStream_t)stream;
-    const int BH = B * H, strips = ((K + 63) / 64) * ((V + 63) / 64);
-    const long E = (long)K * V;
-    int* nval = (int*)ws;
-    const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0, 0, accept_dev};
-    // every launch but the last addresses by pos_dev; the last, which does not, advances it
-    DISPATCH_T(dtype, {
-        CxAccArgs c{};
-        c.x = cv(k); c.y = cv(v); c.H = H; c.DX = K; c.DY = V; c.rag = g; c.later = 0; c.S = S; c.Cur = Cur; c.nval = nval;
-        RC(launch(k_cx_xty_acc<ET, true>, dim3(1, BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
-        if (any_close) {
-            c.later = 1;
-            RC(launch(k_cx_xty_acc<ET, true>, dim3(std::max(1, max_later), BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
-            CxMixRagArgs m{};
-            m.m.S = S; m.m.ws = nullptr; m.m.P = P; m.m.mix = mix; m.m.E = E; m.m.ldmix = ldmix; m.m.cap = cap_chunks;
-            m.rag = g; m.H = H;
-            RC(launch(k_cx_mix_ragged, dim3((unsigned)((E / 4 + 63) / 64), BH, 1), dim3(64), 0, st, "k_cx_mix_ragged", m));
-        }
-    });
-    return launch(k_cx_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, "k_cx_advance", pos_dev, (const int*)nval, B);
+    return cx_commit_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, ntok_dev, accept_dev, T, max_end, max_later, any_close,
+                           left_padded, ws, ws_bytes, B, H, K, V, chunk, dtype, stream);
+}
+
+// ---- slotted calls: the namesakes on chosen rows of a state pool (mhla_hip.h), each through its namesake's chain
+int mhla_causal_step_slots(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                           int32_t* pos_dev, const int32_t* slot_dev, int n_slots, int64_t max_pos, int any_boundary, mhla_mview out,
+                           mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv,
+                           int K, int V, int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cs_step_ragged_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots}, max_pos, any_boundary, out, gate,
+                                norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_step_dev_slots(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                               float* Cur, int32_t* pos_dev, const int32_t* slot_dev, int n_slots, int32_t* full_dev, const void* rope_cos,
+                               const void* rope_sin, int64_t ld_tab, int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate,
+                               const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K,
+                               int V, int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cs_step_dev_chain(q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots}, full_dev, rope_cos, rope_sin, ld_tab,
+                             tab_rows, feature_map, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_extend_slots(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                             float* Cur, int32_t* pos_dev, const int32_t* slot_dev, int n_slots, const int32_t* ntok_dev, int T,
+                             int64_t max_end, int max_later, int any_close, int left_padded, mhla_mview out, mhla_view gate,
+                             const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V,
+                             int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots}, ntok_dev, T, max_end, max_later,
+                           any_close, left_padded, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_verify_slots(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
+                             float* Cur, const int32_t* pos_dev, const int32_t* slot_dev, int n_slots, const int32_t* ntok_dev, int T,
+                             int64_t max_end, int max_later, int any_close, int left_padded, mhla_mview out, mhla_view gate,
+                             const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V,
+                             int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), Slots{slot_dev, n_slots}, ntok_dev, T,
+                           max_end, max_later, any_close, left_padded, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale,
+                           dtype, stream);
+}
+
+int mhla_causal_commit_slots(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
+                             int32_t* pos_dev, const int32_t* slot_dev, int n_slots, const int32_t* ntok_dev, const int32_t* accept_dev, int T,
+                             int64_t max_end, int max_later, int any_close, int left_padded, void* ws, size_t ws_bytes, int B, int H, int K,
+                             int V, int chunk, int dtype, void* stream) {
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cx_commit_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots}, ntok_dev, accept_dev, T, max_end, max_later,
+                           any_close, left_padded, ws, ws_bytes, B, H, K, V, chunk, dtype, stream);
 }
 
 }  // extern "C"

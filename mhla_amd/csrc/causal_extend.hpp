@@ -59,17 +59,24 @@ struct CxRag {
     int left;              // left-padded: sequence b's tokens are rows [T - n, T)
     int dry;               // verify: Cur, P and pos are not written (S rows at and beyond pos[b] / 64 still are)
     const int* acc;        // [B] or null; commit: sequence b takes the first min(acc[b], ntok[b]) tokens of its ntok[b]-token window
+    // slotted calls (cst_slot, causal_step.hpp): pos is the pool's [n_slots] and call row b reads pos[slot[b]]; ntok and acc stay the call's
+    const int* slot;       // [B] or null
+    int n_slots;
 };
 struct CxSeq {
     int n, i, r, a;        // tokens; chunk and fill of the open chunk; rows of the first segment
     int later;             // chunks touched after the first
     int iend;              // chunk open after the extension
     int shift;             // first token row inside [0, T)
+    int sb;                // the state's batch row: b, or slot[b] of a slotted call
     bool closes, full;     // the first segment closes chunk i; the state is full afterwards
 };
-// false: no token, or (defence only) entries outside what the host vouched for -- the caller returns at once
+// false: no token, an inactive row of a slotted call, or (defence only) entries outside what the host vouched for -- the caller
+// returns at once
 __device__ __forceinline__ bool cx_seq(const CxRag& g, int b, CxSeq& s) {
-    const int p = g.pos[b], w = g.ntok[b];
+    s.sb = cst_slot(g.slot, g.n_slots, b);
+    if (s.sb < 0) return false;
+    const int p = g.pos[s.sb], w = g.ntok[b];
     const int n = g.acc ? min(g.acc[b], w) : w;
     if (p < 0 || n < 1 || w > g.T || (long)p + n > (long)g.max_end) return false;
     s.n = n; s.i = p / CS; s.r = p - s.i * CS;
@@ -183,7 +190,7 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
     const int seg = blockIdx.x, bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H;
     const int hk = h / a.G;
-    const long bhk = (long)b * (a.H / a.G) + hk;   // the state's (b, k/v head); G = 1: bh
+    const long bhk = (long)b * (a.H / a.G) + hk;   // the call's (b, k/v head); G = 1: bh
     const int v0 = blockIdx.z * 64, vv = min(64, a.V - v0);
     long p0;
     int rv;
@@ -197,6 +204,7 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
         if (!a.later && h == 0 && blockIdx.z == 0 && tid == 0) a.nval[b] = ok ? s.n : 0;
         if (!ok || (a.later && seg >= s.later)) return;   // ahead of any LDS or further global traffic
         const long E = (long)a.K * a.V;
+        const long sbhk = (long)s.sb * (a.H / a.G) + hk;   // the state's (row, k/v head)
         if (a.later) {
             const int tok = s.a + seg * CS;
             p0 = s.shift + tok;
@@ -207,8 +215,8 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
         } else {
             p0 = s.shift;
             rv = s.a;
-            Pi = a.P + bhk * E;
-            Ci = a.Cur + bhk * E;
+            Pi = a.P + sbhk * E;
+            Ci = a.Cur + sbhk * E;
             mii = a.mdiag[(long)s.i * a.mstep];
             one = s.n == 1;
         }
@@ -309,12 +317,14 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_xty_acc(const CxAccArgs a) {
     const float* sb = nullptr;
     float* db = nullptr;
     [[maybe_unused]] bool one = false, zero_cur = false;
+    [[maybe_unused]] long sbh = bh;   // the state's (row, head)
     if constexpr (RAGGED) {
         CxSeq s;
         const bool ok = cx_seq(a.rag, b, s);
         if (a.nval && !a.later && h == 0 && blockIdx.z == 0 && tid == 0) a.nval[b] = ok ? s.n : 0;
         if (!ok) return;   // ahead of any LDS or further global traffic
         const long E = (long)a.DX * a.DY;
+        sbh = (long)s.sb * a.H + h;
         if (a.later) {
             const int seg = blockIdx.x, rest = s.n - s.a;
             if (!s.closes) return;
@@ -323,13 +333,13 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_xty_acc(const CxAccArgs a) {
             if (a.rag.dry && rows < CS) return;   // (the tail would go to Cur)
             if (!rows && !zero_cur) return;
             tok0 = s.shift + s.a + (long)seg * CS;
-            db = rows == CS ? a.S + ((long)bh * a.rag.cap + s.i + 1 + seg) * E : a.Cur + (long)bh * E;
+            db = rows == CS ? a.S + (sbh * a.rag.cap + s.i + 1 + seg) * E : a.Cur + sbh * E;
         } else {
             if (a.rag.dry && !s.closes) return;   // (the sum would go to Cur)
             rows = s.a;
             tok0 = s.shift;
-            sb = a.Cur + (long)bh * E;
-            db = s.closes ? a.S + ((long)bh * a.rag.cap + s.i) * E : a.Cur + (long)bh * E;
+            sb = a.Cur + sbh * E;
+            db = s.closes ? a.S + (sbh * a.rag.cap + s.i) * E : a.Cur + sbh * E;
             one = s.n == 1;
         }
     } else {
@@ -364,7 +374,7 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_xty_acc(const CxAccArgs a) {
                         else if (sb) val = sb[at] + val;
                         db[at] = val;
                     }
-                    if (zero_cur) a.Cur[(long)bh * a.DX * a.DY + at] = 0.f;
+                    if (zero_cur) a.Cur[sbh * a.DX * a.DY + at] = 0.f;
                 } else {
                     db[(long)row * a.DY + col] = sb[(long)row * a.DY + col] + acc[i][r];
                 }
@@ -386,9 +396,10 @@ struct CxMixArgs {
 };
 
 // P_c of the chunks c0 + u0 .. of one (b, h), elements e .. e + 3: ascending j with fmaf (k_cs_roll's sum).  `nws` of them go to the
-// workspace, whose stride per (b, h) is `ws_bh` tiles
-__device__ __forceinline__ void cx_mix_sums(const CxMixArgs& a, long bh, long e, int c0, int nws, int ws_bh, int nc, int cP) {
-    const float* Sb = a.S + bh * a.cap * a.E + e;
+// workspace, whose stride per (b, h) is `ws_bh` tiles.  bh: the call's (b, h), which owns the workspace; sbh: the state's (row, head),
+// another only in a slotted call
+__device__ __forceinline__ void cx_mix_sums(const CxMixArgs& a, long bh, long sbh, long e, int c0, int nws, int ws_bh, int nc, int cP) {
+    const float* Sb = a.S + sbh * a.cap * a.E + e;
     const int u0 = blockIdx.z * CX_MIX_NC, nu = min(CX_MIX_NC, nc - u0);
     f32x4 acc[CX_MIX_NC];
 #pragma unroll
@@ -430,17 +441,17 @@ __device__ __forceinline__ void cx_mix_sums(const CxMixArgs& a, long bh, long e,
     for (int u = 0; u < CX_MIX_NC; ++u) {
         if (u < nu) {
             if (u0 + u < nws) gst<f32x4>(a.ws + (bh * ws_bh + u0 + u) * a.E + e, acc[u]);
-            if (cbase + u == cP) gst<f32x4>(a.P + bh * a.E + e, acc[u]);
+            if (cbase + u == cP) gst<f32x4>(a.P + sbh * a.E + e, acc[u]);
         }
     }
-    if (cP < 0 && blockIdx.z == 0) gst<f32x4>(a.P + bh * a.E + e, f32x4{0.f, 0.f, 0.f, 0.f});
+    if (cP < 0 && blockIdx.z == 0) gst<f32x4>(a.P + sbh * a.E + e, f32x4{0.f, 0.f, 0.f, 0.f});
 }
 
 // grid (ceil(E / 4 / 64), B H, ceil(nc / 8)), one wave per workgroup: P_c = sum_{j < c} mix[c][j] S[j], ascending j (k_cs_roll's sum)
 __global__ __launch_bounds__(64) void k_cx_mix(const CxMixArgs a) {
     const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
     if (e >= a.E) return;   // (E % 4 == 0)
-    cx_mix_sums(a, blockIdx.y, e, a.c0, a.nws, a.nws, a.nc, a.cP);
+    cx_mix_sums(a, blockIdx.y, blockIdx.y, e, a.c0, a.nws, a.nws, a.nc, a.cP);
 }
 
 struct CxMixRagArgs {
@@ -456,24 +467,29 @@ __global__ __launch_bounds__(64) void k_cx_mix_ragged(const CxMixRagArgs a) {
     const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
     if (e >= a.m.E) return;   // (E % 4 == 0)
     const long bh = blockIdx.y;
+    const int b = (int)(bh / a.H);
     CxSeq s;
-    if (!cx_seq(a.rag, (int)(bh / a.H), s) || !s.closes) return;
+    if (!cx_seq(a.rag, b, s) || !s.closes) return;
+    const long sbh = bh + (long)(s.sb - b) * a.H;
     if (a.rag.dry) {   // the workspace tiles alone: no cP matches and none is negative
-        if (s.later) cx_mix_sums(a.m, bh, e, s.i + 1, s.later, a.rag.max_later, s.later, 0x7fffffff);
+        if (s.later) cx_mix_sums(a.m, bh, sbh, e, s.i + 1, s.later, a.rag.max_later, s.later, 0x7fffffff);
         return;
     }
     if (!a.m.ws) {     // chunk iend alone (every accumulator sums ascending j by itself: the group does not change its bits), or P = 0
-        cx_mix_sums(a.m, bh, e, s.iend, 0, 0, s.full ? 0 : 1, s.full ? -1 : s.iend);
+        cx_mix_sums(a.m, bh, sbh, e, s.iend, 0, 0, s.full ? 0 : 1, s.full ? -1 : s.iend);
         return;
     }
     const int nc = (s.full ? s.i + s.later : s.iend) - s.i;
-    cx_mix_sums(a.m, bh, e, s.i + 1, s.later, a.rag.max_later, nc, s.full ? -1 : s.iend);
+    cx_mix_sums(a.m, bh, sbh, e, s.i + 1, s.later, a.rag.max_later, nc, s.full ? -1 : s.iend);
 }
 
-// grid (ceil(B / 64)): the last launch of the commit chain, pos[b] += nval[b] (nval: what the first launch of the chain accepted)
-__global__ __launch_bounds__(64) void k_cx_advance(int* pos, const int* nval, int B) {
+// grid (ceil(B / 64)): the last launch of the commit chain, pos[b] += nval[b] (nval: what the first launch of the chain accepted);
+// a slotted call: the pool's pos[slot[b]], an inactive row none
+__global__ __launch_bounds__(64) void k_cx_advance(int* pos, const int* nval, int B, const int* slot, int n_slots) {
     const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b < B) pos[b] += nval[b];
+    if (b >= B) return;
+    const int sb = cst_slot(slot, n_slots, b);
+    if (sb >= 0) pos[sb] += nval[b];
 }
 
 }  // namespace mhla

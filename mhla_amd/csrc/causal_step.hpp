@@ -63,7 +63,28 @@ struct CsStepArgs {
     int tab_rows, fmap;    // tab_rows >= 64 cap (the host checked); feature map: 0 identity, 1 relu, 2 elu + 1
     // GMAX > 1 only: H counts the k/v heads (k, v, P, Cur and the grid), q and part have G H heads, head hk G + g in group hk
     int G;                 // 1 .. GMAX
+    // RAGGED only, slotted calls (cst_slot below): P, Cur and pos belong to a pool of n_slots rows, call row b uses row slot[b]
+    const int* slot;       // [B] or null: row b itself
+    int n_slots;
 };
+
+// Slotted calls (the mhla_causal_*_slots entry points): the state -- S, P, Cur, pos, full -- is a pool of n_slots batch rows, and
+// call row b works on row slot[b] of it; everything that belongs to the call (tokens, rows, workspace, ntok, accept, nval) stays
+// addressed by b.  The state row of call row b: b itself without a map (today's addressing, the same bits), slot[b] with one, or -1
+// where slot[b] is outside 0 .. n_slots - 1 -- such a row is INACTIVE: nothing of the pool is read or written for it and its rows
+// come out as zeros, the frozen / skipped branches that exist.  Workgroup-uniform: every workgroup serves one call row.
+__device__ __forceinline__ int cst_slot(const int* slot, int n_slots, int b) {
+    if (!slot) return b;
+    const int s = slot[b];
+    return (unsigned)s < (unsigned)n_slots ? s : -1;
+}
+// the step's kernels take "slotted" as a template parameter, so that the un-slotted instantiations are the code they were (measured:
+// profiles/causal_state_slots.md); the extend chain's kernels test the pointer at run time
+template <bool SLOT>
+__device__ __forceinline__ int cst_row(const int* slot, int n_slots, int b) {
+    if constexpr (SLOT) return cst_slot(slot, n_slots, b);
+    else return b;
+}
 
 // pos[b] as the ragged step addresses by it.  Defence only: the caller keeps the array equal to its host mirror, and then the clamp
 // changes nothing.  An array that disagrees with the mirror is a caller's error that gives wrong rows (another mix[i][i]); what the
@@ -95,8 +116,9 @@ constexpr int CST_GMAX = 8;       // query heads per k/v head the grouped step s
 
 // grid (ceil(V / 64), nsplit, B H); GMAX > 1 (grouped-query heads, a.H = Hkv): one accumulator per query head g < a.G of the group,
 // the loop over g fully unrolled and predicated by a.G alone (uniform over the launch)
-template <typename T, bool RAGGED = false, bool DEV = false, bool PRO = false, int GMAX = 1>
+template <typename T, bool RAGGED = false, bool DEV = false, bool PRO = false, int GMAX = 1, bool SLOT = false>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
+    static_assert(!SLOT || RAGGED, "a slot map goes with positions on the device");
     static_assert(!DEV || RAGGED, "DEV is the ragged step, bounded by the capacity");
     static_assert(!PRO || DEV, "the fused prologue goes with the device-positioned step");
     static_assert(GMAX == 1 || RAGGED, "grouped heads: the ragged and device-positioned steps only");
@@ -113,9 +135,15 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
     float mii;
     [[maybe_unused]] const T* cosr = nullptr;
     [[maybe_unused]] const T* sinr = nullptr;
+    long sbh = bh;   // the state's (row, head): the call's own without a slot map
+    [[maybe_unused]] int sb = b;
+    if constexpr (SLOT) {
+        sb = cst_slot(a.slot, a.n_slots, b);
+        sbh = (long)max(sb, 0) * a.H + h;
+    }
     if constexpr (DEV) {
-        int p = a.pos[b];
-        if (p < 0 || p > a.max_pos) {   // frozen: zeros as partial sums, the state untouched
+        int p = SLOT && sb < 0 ? -1 : a.pos[sb];
+        if (p < 0 || p > a.max_pos) {   // frozen (an inactive row of a slotted call included): zeros as partial sums, the state untouched
             live = false;
             p = 0;
         }
@@ -129,7 +157,8 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
             }
         }
     } else if constexpr (RAGGED) {
-        const long i = cst_pos(a.pos, b, a.max_pos) / CS;
+        if (SLOT && sb < 0) live = false;   // an inactive row of a slotted call: zeros as partial sums, the state untouched
+        const long i = SLOT && sb < 0 ? 0 : cst_pos(a.pos, sb, a.max_pos) / CS;
         mii = a.mix[i * a.ldmix + i];
     } else {
         mii = *a.mix;
@@ -139,7 +168,7 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
     for (int g = 0; g < GMAX; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (live) {
         const f32x4 vv = Io<T>::ld4(vb + col);
-        const long base = (long)bh * a.K * a.V + col;
+        const long base = sbh * a.K * a.V + col;
         constexpr int U = 4;   // rows in flight per thread: 2 U 16-byte loads
         for (int r0 = k0 + rg; r0 < k1; r0 += CST_RG * U) {
             f32x4 p[U], c[U];
@@ -213,6 +242,9 @@ struct CsFinishArgs {
     // WIN only (the ragged extend, causal_extend.hpp): sequence b's rows are nval[b] <= T of the T padded ones
     const int* nval;       // [B] tokens the chain accepted per sequence
     int left;              // the window is rows [T - nval[b], T) instead of [0, nval[b])
+    // slotted calls (cst_slot): advance and full are the pool's [n_slots], call row b moves entry slot[b]; an inactive row moves none
+    const int* slot;       // [B] or null
+    int n_slots;
 };
 
 // grid (B H, T tokens): o = scale * (partials in split order); y = o rsqrt(mean(o^2 over V) + neps) nw g sigmoid(g), from the fp32 o
@@ -220,7 +252,7 @@ struct CsFinishArgs {
 // its step wrote, so its row needs no branch here
 // WIN: a row outside its sequence's window is written as zeros (out and y) and reads nothing else; advance[b] += nval[b].  pos is
 // not read by any other thread of this launch: the window comes from nval, which an earlier launch of the chain wrote
-template <typename T, bool DEV = false, bool WIN = false>
+template <typename T, bool DEV = false, bool WIN = false, bool SLOT = false>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishArgs a) {
     static_assert(!(DEV && WIN), "the device-positioned step has one row per sequence");
     __shared__ float red[CST_THREADS / 64];
@@ -228,7 +260,10 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishAr
     const long tok = blockIdx.y;
     if constexpr (WIN) {
         const int n = a.nval[b], t0 = a.left ? (int)gridDim.y - n : 0;
-        if (a.advance && h == 0 && tok == 0 && tid == 0) a.advance[b] += n;   // (nothing in this launch reads it; null: a verify)
+        if (a.advance && h == 0 && tok == 0 && tid == 0) {   // (nothing in this launch reads it; null: a verify)
+            const int sb = cst_row<SLOT>(a.slot, a.n_slots, b);
+            if (!SLOT || sb >= 0) a.advance[sb] += n;
+        }
         if (tok < t0 || tok >= t0 + n) {
             T* ob = a.out.ptr ? (T*)a.out.ptr + b * a.out.sb + tok * a.out.sn + h * a.out.sh : nullptr;
             T* yb = a.y.ptr ? (T*)a.y.ptr + b * a.y.sb + tok * a.y.sn + h * a.y.sh : nullptr;
@@ -240,12 +275,18 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishAr
         }
     } else if constexpr (DEV) {
         if (h == 0 && tok == 0 && tid == 0) {
-            const int p = a.advance[b];
-            if (p < 0 || p > a.max_pos) a.full[b] = 1;
-            else a.advance[b] = p + 1;
+            const int sb = cst_row<SLOT>(a.slot, a.n_slots, b);
+            if (!SLOT || sb >= 0) {
+                const int p = a.advance[sb];
+                if (p < 0 || p > a.max_pos) a.full[sb] = 1;
+                else a.advance[sb] = p + 1;
+            }
         }
     } else {
-        if (a.advance && h == 0 && tok == 0 && tid == 0) a.advance[b] += 1;   // (nothing in this launch reads it)
+        if (a.advance && h == 0 && tok == 0 && tid == 0) {   // (nothing in this launch reads it)
+            const int sb = cst_row<SLOT>(a.slot, a.n_slots, b);
+            if (!SLOT || sb >= 0) a.advance[sb] += 1;
+        }
     }
     const float* pb = a.part + ((long)bh * gridDim.y + tok) * a.nsplit * a.V;
     T* ob = a.out.ptr ? (T*)a.out.ptr + b * a.out.sb + tok * a.out.sn + h * a.out.sh : nullptr;
@@ -313,6 +354,10 @@ struct CsRollArgs {
     const int* pos;        // [B]
     const float* mix;      // &mix[0][0]
     int ldmix, max_pos, H;
+    // slotted calls (cst_slot): S, P and Cur are the pool's, (b, h) works on row slot[b]; RAGGED reads the pool's pos[slot[b]], PACK
+    // the call's own pos[b] (the tokens of sequence b of the pack)
+    const int* slot;       // [B] or null
+    int n_slots;
 };
 
 // grid (ceil(E / 4 / 64), B H), one wave per workgroup: P = sum_{j < nj} mixrow[j] S[j], ascending j
@@ -321,16 +366,23 @@ struct CsRollArgs {
 // PACK: each (b, h) for itself, the prefix mix of a state whose finished chunks S[0 .. nj) were just written, nj = pos[b] / 64 --
 // no commit; P from row nj of mix, or P = 0 when nj == cap; Cur = 0 where the sequence has no open chunk (pos[b] % 64 == 0, an
 // empty sequence included: P = Cur = 0).  A pos[b] outside 0 .. max_pos leaves the sequence untouched (defence only, as RAGGED)
-template <bool RAGGED = false, bool PACK = false>
+template <bool RAGGED = false, bool PACK = false, bool SLOT = false>
 __global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
     static_assert(!(RAGGED && PACK), "one addressing mode");
     const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
     if (e >= a.E) return;   // (E % 4 == 0)
-    const long bh = blockIdx.y;
+    long bh = blockIdx.y;   // below: the state's (row, head)
     int nj = a.nj, commit = a.commit;
     const float* mixrow = a.mixrow;
+    [[maybe_unused]] int sb = 0;
+    if constexpr (RAGGED || PACK) {
+        const int b = (int)(bh / a.H);
+        sb = cst_row<SLOT>(a.slot, a.n_slots, b);
+        if (SLOT && sb < 0) return;   // an inactive row of a slotted call
+        if constexpr (SLOT) bh += (long)(sb - b) * a.H;
+    }
     if constexpr (PACK) {
-        const int p = a.pos[bh / a.H];
+        const int p = a.pos[blockIdx.y / a.H];
         if (p < 0 || p > a.max_pos) return;
         nj = p / CS;   // (<= cap: the host checked ceil(max_pos / 64) <= cap)
         commit = 0;
@@ -338,7 +390,7 @@ __global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
         if (p % CS == 0) gst<f32x4>(a.Cur + bh * a.E + e, f32x4{0.f, 0.f, 0.f, 0.f});
     }
     if constexpr (RAGGED) {
-        const int p = a.pos[bh / a.H];
+        const int p = a.pos[sb];
         if (p < 0 || p > a.max_pos || p % CS != CS - 1) return;   // (outside 0 .. max_pos: defence only, see cst_pos)
         nj = p / CS + 1;   // (<= cap: the host checked max_pos / 64 < cap)
         commit = 1;

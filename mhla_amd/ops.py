@@ -1462,6 +1462,7 @@ class CausalState:
         states = list(states)
         if not states or not all(isinstance(s, CausalState) for s in states):
             raise ValueError("CausalState.cat: a non-empty sequence of CausalState")
+        states = [s.compact() if isinstance(s, CausalStateView) else s for s in states]   # (a view: copies of its slots)
         a = states[0]
         for s in states[1:]:
             if tuple(s.S.shape[1:]) != tuple(a.S.shape[1:]) or s.chunk_size != a.chunk_size or s.S.device != a.S.device:
@@ -1477,10 +1478,206 @@ class CausalState:
             out._full = torch.cat([s.full for s in states])
         return out
 
+    # ---- a ragged state as a POOL of slots: requests stay in their batch row (slot) while the set of live ones changes
+    def at(self, slots) -> "CausalStateView":
+        """The batch rows `slots` of this ragged state (a pool of `B` slots), in that order, as a state of `len(slots)` sequences on the
+        SAME storage: nothing is copied, and every decode call that takes a state takes the view and reads and writes the pool
+        in place -- see `CausalStateView`.  slots: a sequence of distinct ints in 0 .. B - 1 (ValueError naming the offenders
+        otherwise), or an int32 tensor `[n]` on the state's device, which only `mhla_causal_step_dev` takes.  A uniform state is
+        refused: call `to_ragged()` first."""
+        return CausalStateView(self, slots)
+
+    def _pool_slots(self, fn: str, slots):
+        """What `reset` and `fork` check: a ragged state that is not stale, and `slots` as `at` takes a list."""
+        if self.lengths is None:
+            raise ValueError(f"{fn}: the state is uniform ({self!r}): a pool of slots is a ragged state, call to_ragged() first")
+        self._refuse_stale(fn)
+        return _slot_tuple(fn, slots, self.S.shape[0])
+
+    def _set_lengths(self, slots, values):
+        lengths = list(self.lengths)
+        for s, n in zip(slots, values):
+            lengths[s] = int(n)
+        self.lengths, self.seen = tuple(lengths), max(lengths)
+
+    def reset(self, slots) -> "CausalState":
+        """Empty the slots `slots` of a pool for new requests: P, Cur, pos, full and the host mirror of those rows become zero (plain
+        tensor operations, no kernel).  S needs no clearing: rows beyond a sequence's finished chunks are never read."""
+        slots = self._pool_slots("CausalState.reset", slots)
+        idx = torch.tensor(slots, dtype=torch.int64).to(self.S.device)
+        for t in (self.P, self.Cur, self.pos, self._full):
+            if t is not None:
+                t[idx] = 0
+        self._set_lengths(slots, (0,) * len(slots))
+        return self
+
+    def fork(self, src: int, dst: int) -> "CausalState":
+        """Copy slot `src` of a pool over slot `dst` (a shared prompt prefix, beams): the finished chunks of S, P, Cur, pos, full
+        and the host mirror -- plain tensor copies, no kernel.  Rows of S beyond the finished chunks are not copied: nothing reads
+        them."""
+        src, dst = self._pool_slots("CausalState.fork", (src, dst))
+        n = self.lengths[src]
+        self.S[dst, :, :n // 64] = self.S[src, :, :n // 64]
+        for t in (self.P, self.Cur, self.pos, self._full):
+            if t is not None:
+                t[dst] = t[src]
+        self._set_lengths((dst,), (n,))
+        return self
+
     def __repr__(self):
         B, H, cap, K, V = self.S.shape
         seen = f"seen={self.seen}" if self.lengths is None else f"lengths={self.lengths}"
         return f"CausalState(B={B}, H={H}, K={K}, V={V}, capacity_chunks={cap}, {seen}, device={self.S.device})"
+
+
+def _slot_tuple(fn, slots, n_slots):
+    """`slots` as a tuple of distinct ints in 0 .. n_slots - 1, at least one; ValueError naming the offenders otherwise."""
+    slots = list(slots)
+    bad = [s for s in slots if isinstance(s, bool) or not isinstance(s, int)]
+    if bad:
+        raise ValueError(f"{fn}: slots must be ints, got {bad}")
+    if not slots:
+        raise ValueError(f"{fn}: no slot given (at least one)")
+    out = [s for s in slots if not 0 <= s < n_slots]
+    if out:
+        raise ValueError(f"{fn}: slots {out} are outside 0 .. {n_slots - 1} (the pool has {n_slots})")
+    dup = sorted({s for s in slots if slots.count(s) > 1})
+    if dup:
+        raise ValueError(f"{fn}: slots {dup} are given more than once (rows of a call that share a slot would race)")
+    return tuple(slots)
+
+
+class CausalStateView(CausalState):
+    """`pool.at(slots)`: the rows `slots` of a ragged `CausalState` (the pool), in that order, as a state of B = len(slots) sequences.
+    It owns nothing: S, P, Cur, pos, full, the host mirror and `stale` are the pool's.  The decode calls -- `mhla_causal_step`,
+    `mhla_causal_step_dev`, `mhla_causal_extend` (with and without `counts`), `mhla_causal_verify`, `mhla_causal_commit` -- take it where
+    they take a state, and the pack prefill takes it as `into=`: row b of the call then reads and writes slot `slots[b]` of the pool
+    in place (the library's `*_slots` entry points), and gives bit for bit what the call gives on `view.compact()`, a compact state
+    holding copies of those slots.  Slots the view does not name keep every bit.  Nothing is gathered, scattered or concatenated.
+    slots as a sequence of ints: HOST-POSITIONED.  `lengths` is `tuple(pool.lengths[s] for s in slots)`; after a call the pool's
+    mirror has advanced at exactly those slots; the small device copy of the map is made once and kept on the view.
+    slots as an int32 tensor `[B]` on the pool's device: DEVICE-POSITIONED, for `mhla_causal_step_dev` alone (every other call
+    raises ValueError).  Its contents are never read by the host and may be rewritten in place between calls or replays of a captured
+    graph: an entry outside 0 .. n_slots - 1, -1 for instance, makes that row INACTIVE -- its row of the result is zeros and no slot,
+    position or flag is touched; entries that name a slot must be distinct (rows that share one race).  The step marks the POOL
+    stale, and `pool.sync()` refreshes it.
+    Not covered: `DecodeCache`, the fla layer and `hosts/gpt.py` build their states as before; a slot still reserves all
+    `capacity_chunks` chunks (no paging within a slot)."""
+
+    __slots__ = ("pool", "slots", "_map", "_mirror")
+
+    def __init__(self, pool: CausalState, slots):
+        self._mirror = (None, None)   # (the pool's lengths tuple the view's were last taken from, the view's lengths)
+        fn = "CausalState.at"
+        if isinstance(pool, CausalStateView):
+            raise ValueError(f"{fn}: a view of a view; take the slots from the pool")
+        if pool.lengths is None:
+            raise ValueError(f"{fn}: the state is uniform ({pool!r}): a pool of slots is a ragged state, call to_ragged() first")
+        self.pool = pool
+        if isinstance(slots, torch.Tensor):
+            if slots.dtype != torch.int32 or slots.dim() != 1 or slots.shape[0] < 1 or slots.device != pool.S.device or not slots.is_contiguous():
+                raise ValueError(f"{fn}: a slot map on the device is a contiguous int32 [B >= 1] tensor on {pool.S.device}, got "
+                                 f"{slots.dtype} {tuple(slots.shape)} on {slots.device}")
+            self.slots, self._map = None, slots
+        else:
+            self.slots, self._map = _slot_tuple(fn, slots, pool.S.shape[0]), None
+
+    S = property(lambda self: self.pool.S)
+    P = property(lambda self: self.pool.P)
+    Cur = property(lambda self: self.pool.Cur)
+    pos = property(lambda self: self.pool.pos)
+    chunk_size = property(lambda self: self.pool.chunk_size)
+    stale = property(lambda self: self.pool.stale, lambda self, x: setattr(self.pool, "stale", x))
+    _full = property(lambda self: self.pool._full, lambda self, x: setattr(self.pool, "_full", x))
+
+    @property
+    def rows(self) -> int:
+        """B: the sequences of a call on this view."""
+        return len(self.slots) if self.slots is not None else self._map.shape[0]
+
+    @property
+    def map(self) -> torch.Tensor:
+        """int32 [B] on the pool's device: slot of every row -- the caller's tensor, or the copy of the list made on first use."""
+        if self._map is None:
+            self._map = torch.tensor(self.slots, dtype=torch.int32).to(self.pool.S.device)
+        return self._map
+
+    @property
+    def lengths(self):
+        """The pool's host mirror at the view's slots (None for a map on the device, which the host never reads)."""
+        if self.slots is None:
+            return None
+        src = self.pool.lengths   # (a tuple, replaced whenever a length changes: its identity says whether the selection is current)
+        if self._mirror[0] is not src:
+            self._mirror = (src, tuple(src[s] for s in self.slots))
+        return self._mirror[1]
+
+    @lengths.setter
+    def lengths(self, values):
+        self.pool._set_lengths(self.slots, values)
+        self._mirror = (self.pool.lengths, tuple(values))
+
+    @property
+    def seen(self) -> int:
+        return self.pool.seen if self.slots is None else max(self.lengths)
+
+    @seen.setter
+    def seen(self, _):   # (the pool's `seen` follows its lengths: `_set_lengths`)
+        pass
+
+    def to_ragged(self) -> "CausalStateView":
+        return self
+
+    def sync(self) -> "CausalStateView":
+        self.pool.sync()
+        return self
+
+    def _host_slots(self, fn: str):
+        if self.slots is None:
+            raise ValueError(f"{fn}: the view's slot map lives on the device, which only mhla_causal_step_dev takes: make the view from "
+                             "a list of slots")
+        self.pool._refuse_stale(fn)
+
+    def compact(self) -> CausalState:
+        """A fresh ragged `CausalState` holding COPIES of the view's slots in call order (plain tensor operations): what a call on
+        the view is defined against."""
+        self._host_slots("CausalStateView.compact")
+        idx = self.map.to(torch.int64)
+        out = CausalState(self.S[idx], self.P[idx], self.Cur[idx], 0, self.chunk_size, lengths=self.lengths, pos=self.pos[idx])
+        if self.pool._full is not None:
+            out._full = self.pool._full[idx]
+        return out
+
+    clone = compact
+
+    def at(self, slots):
+        raise ValueError("CausalState.at: a view of a view; take the slots from the pool")
+
+    def reset(self, slots):
+        raise ValueError("CausalState.reset: slots are reset on the pool, not on a view of it")
+
+    def fork(self, src, dst):
+        raise ValueError("CausalState.fork: slots are forked on the pool, not on a view of it")
+
+    def _part(self, i, j) -> "_SlotPart":
+        return _SlotPart(self.pool, self.map[i:j])
+
+    def __repr__(self):
+        return f"CausalStateView(slots={self.slots if self.slots is not None else 'on the device'}, B={self.rows}, of {self.pool!r})"
+
+
+class _SlotPart:
+    """Rows [i, j) of a view, as a launch takes them: the pool's tensors and that piece of the map."""
+
+    __slots__ = ("S", "P", "Cur", "chunk_size", "map")
+
+    def __init__(self, pool, map_):
+        self.S, self.P, self.Cur, self.chunk_size, self.map = pool.S, pool.P, pool.Cur, pool.chunk_size, map_
+
+
+def _state_rows(state) -> int:
+    """The sequences a call on `state` has: its batch rows, or the rows a view selects."""
+    return state.rows if isinstance(state, CausalStateView) else state.S.shape[0]
 
 
 def _int_tuple(fn, name, xs, B, hi):
@@ -1510,22 +1707,27 @@ def _runs(lengths, nb):
 def _state_slice(state: CausalState, i, j) -> CausalState:
     """`state` for its sequences [i, j): views of S, P, Cur (what a launch reads of a state besides its sizes), or -- all of them,
     the usual case -- the state itself, with no views to build."""
-    if i == 0 and j == state.S.shape[0]:
+    if i == 0 and j == _state_rows(state):
         return state
+    if isinstance(state, CausalStateView):   # (the pool's tensors and that piece of the slot map)
+        return state._part(i, j)
     return CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], 0, 64)
 
 
 def _batch_slices(state: CausalState, nb, prepared=None, *along):
     """One launch addresses `nb` sequences (`_MAX_GRID_BH // H`; batches beyond that range: see mhla_blockmix).  Yields, for every
     batch slice [i, j) of at most `nb`: (`_state_slice`, `prepared.part(i, j)`, x[i:j] for every x of `along`).  B <= nb, the usual
-    case, is one launch chain on the objects themselves."""
-    B = state.S.shape[0]
+    case, is one launch chain on the objects themselves.  A view of a pool: its slot map is sliced with the tokens (`_state_slice`),
+    while the pool's `pos` and `full`, which the launches address through the map, pass whole."""
+    B = _state_rows(state)
     if B <= nb:
         yield (state, prepared) + along
         return
+    pooled = (state.pos, state._full) if isinstance(state, CausalStateView) else ()
     for i in range(0, B, nb):
         j = min(B, i + nb)
-        yield (_state_slice(state, i, j), prepared.part(i, j) if prepared is not None else None) + tuple(x[i:j] for x in along)
+        yield (_state_slice(state, i, j), prepared.part(i, j) if prepared is not None else None) + tuple(
+            x if any(x is t for t in pooled) else x[i:j] for x in along)
 
 
 def _run_slices(state: CausalState, lengths, nb):
@@ -1570,7 +1772,7 @@ def _causal_state_init(k, v, mix, state: CausalState):
 
 def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, chunk_size: int = 64,
                         scale: Optional[float] = None, *, summaries: str = "tf32", capacity_chunks: Optional[int] = None,
-                        lengths=None, left_padded: bool = False, cu_seqlens=None):
+                        lengths=None, left_padded: bool = False, cu_seqlens=None, into=None):
     """`(o, state)`: `o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries)` and the `CausalState`
     after these T tokens, from which `mhla_causal_step` continues one token at a time (T = 0: an empty state).  The state is
     built from k, v in exact fp32 products, independently of `summaries`; no autograd passes through it.
@@ -1581,7 +1783,11 @@ def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixin
     the ragged one of `mhla_causal_state(..., cu_seqlens=)`, one sequence of the pack per batch entry; one plan serves both.
     Grouped-query heads (k, v `[B, T, Hkv, .]`, H = G Hkv, G <= 8): `o` is `mhla_causal` on the un-repeated k, v -- bit for bit the
     output on k, v repeated G times per head, as the fla layer repeats them, without the copies; the state is built from the same
-    k, v and has Hkv heads (`CausalState`)."""
+    k, v and has Hkv heads (`CausalState`).
+    into (a host-positioned `CausalStateView`; with cu_seqlens only): the state half goes into the view's slots of its pool, as
+    `mhla_causal_state(..., into=)`, and the view is returned as `state`."""
+    if into is not None and cu_seqlens is None:
+        raise ValueError("mhla_causal_prefill: into= takes a pack (cu_seqlens=)")
     if q.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k: [B, T, H, K], v: [B, T, H, V]")
     if int(chunk_size) != 64:
@@ -1591,9 +1797,9 @@ def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixin
         _kv_group("mhla_causal_prefill", q.shape[2], k.shape[2])
     if cu_seqlens is not None:
         # every refusal of the state half first, so that nothing is launched for a call that is refused
-        plan = _causal_state_pack_args("mhla_causal_prefill", k, v, mixing_matrix, cu_seqlens, lengths, left_padded, capacity_chunks)[0]
+        plan = _causal_state_pack_args("mhla_causal_prefill", k, v, mixing_matrix, cu_seqlens, lengths, left_padded, capacity_chunks, into)[0]
         o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries, cu_seqlens=plan)
-        return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks, cu_seqlens=plan)
+        return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks, cu_seqlens=plan, into=into)
     if lengths is None:
         o = mhla_causal(q, k, v, mixing_matrix, chunk_size, scale, summaries=summaries)
         return o, mhla_causal_state(k, v, mixing_matrix, capacity_chunks=capacity_chunks)
@@ -1609,8 +1815,9 @@ def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixin
     return o, state
 
 
-def _causal_state_pack_args(fn, k, v, mixing_matrix, cu_seqlens, lengths, left_padded, capacity_chunks):
-    """The checks of a packed prefill state, all before the library is loaded or anything is launched; returns (plan, capacity)."""
+def _causal_state_pack_args(fn, k, v, mixing_matrix, cu_seqlens, lengths, left_padded, capacity_chunks, into=None):
+    """The checks of a packed prefill state, all before the library is loaded or anything is launched; returns (plan, capacity).
+    into: the view whose slots take the pack's sequences -- the capacity is then its pool's."""
     if k.dim() != 4 or v.dim() != 4:
         raise ValueError("k: [B, T, H, K], v: [B, T, H, V]")
     if lengths is not None or left_padded:
@@ -1619,10 +1826,22 @@ def _causal_state_pack_args(fn, k, v, mixing_matrix, cu_seqlens, lengths, left_p
     _check_like(k, fn, v=(v, (B, T, H, v.shape[-1])))
     plan = _causal_varlen_args(fn, k, mixing_matrix, cu_seqlens, 64)
     L = mixing_matrix.shape[0]
+    n_seqs = len(plan.cu) - 1
+    if into is not None:
+        if not isinstance(into, CausalStateView):
+            raise TypeError(f"{fn}: into must be a CausalStateView (pool.at(slots)), got {type(into).__name__}")
+        into._host_slots(fn)
+        if capacity_chunks is not None:
+            raise ValueError(f"{fn}: capacity_chunks={capacity_chunks} given together with into=: the capacity is the pool's "
+                             f"({into.capacity_chunks} chunks)")
+        if n_seqs != into.rows:
+            raise ValueError(f"{fn}: the pack holds {n_seqs} sequences, the view selects {into.rows} slots {into.slots}")
+        capacity_chunks = into.capacity_chunks
+        if tuple(into.S.shape[1:]) != (H, capacity_chunks, K, v.shape[-1]) or into.S.device != k.device:
+            raise ValueError(f"{fn}: into is {into!r}, the pack has H={H} K={K} V={v.shape[-1]} on {k.device}")
     cap = L if capacity_chunks is None else int(capacity_chunks)
     if not 0 < cap <= L:
         raise ValueError(f"capacity_chunks={cap} must be in 1 .. {L} (rows of mixing_matrix)")
-    n_seqs = len(plan.cu) - 1
     if n_seqs < 1:
         raise ValueError(f"{fn}: cu_seqlens holds no sequence")
     if n_seqs * H > _MAX_GRID_BH:
@@ -1638,20 +1857,24 @@ def _causal_state_pack_args(fn, k, v, mixing_matrix, cu_seqlens, lengths, left_p
 
 
 @_device_guard
-def _causal_state_init_pack(k, v, mix, state: CausalState, plan: CausalVarlenPlan):
-    """One launch chain of `mhla_causal_varlen_state_init`: the state of every sequence of the pack k, v into the ragged `state`."""
+def _causal_state_init_pack(k, v, mix, state: CausalState, plan: CausalVarlenPlan, seq_len: torch.Tensor):
+    """One launch chain of `mhla_causal_varlen_state_init`: the state of every sequence of the pack k, v into the ragged `state`;
+    `seq_len`: the sequences' lengths on the device (the state's `pos`).  A view: sequence s into slot s of the view, of its pool."""
     lib = _lib.load()
     _, T, H, K = k.shape
     k, v = _prep(k), _prep(v)
     mixf = _mix2d(mix)
-    rc = lib.mhla_causal_varlen_state_init(_view(k), _view(v), *_state_head(mixf, state), len(state.lengths), state.pos.data_ptr(),
-                                           max(state.lengths), T, H, K, v.shape[-1], state.chunk_size, plan.n_chunks,
-                                           plan.table.data_ptr(), plan.dst.data_ptr(), _dtype_code(k), _stream())
-    _lib.check(rc, "mhla_causal_varlen_state_init")
+    slot = getattr(state, "map", None)
+    name, where = (("mhla_causal_varlen_state_init", ()) if slot is None else
+                   ("mhla_causal_varlen_state_init_slots", (slot.data_ptr(), state.S.shape[0])))
+    rc = getattr(lib, name)(_view(k), _view(v), *_state_head(mixf, state), len(plan.lengths), seq_len.data_ptr(), *where,
+                            max(plan.lengths), T, H, K, v.shape[-1], state.chunk_size, plan.n_chunks,
+                            plan.table.data_ptr(), plan.dst.data_ptr(), _dtype_code(k), _stream())
+    _lib.check(rc, name)
 
 
 def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, *, lengths=None, left_padded: bool = False,
-                      capacity_chunks: Optional[int] = None, cu_seqlens=None) -> CausalState:
+                      capacity_chunks: Optional[int] = None, cu_seqlens=None, into=None) -> CausalState:
     """The `CausalState` after the T tokens of k `[B, T, H, K]`, v `[B, T, H, V]` (the state half of `mhla_causal_prefill`;
     chunk 64).  T = 0: an empty state.
     lengths (a list or a tensor of B ints in 0 .. T; a device tensor is read once, which synchronises): a padded batch -- the tokens
@@ -1660,19 +1883,41 @@ def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Ten
     cu_seqlens (a `CausalVarlenPlan`, a list or a tensor, as `mhla_causal` takes it; B = 1): a pack -- the ragged state of B =
     number of sequences, in `cu` order, empty ones included, bit for bit what every sequence prefilled alone gives, in ONE launch
     chain whatever their number (`mhla_causal_varlen_state_init`).  Excludes `lengths` / `left_padded` (ValueError); IndexError
-    names the sequences longer than `64 capacity_chunks` tokens; ValueError when sequences x heads exceed 65535."""
+    names the sequences longer than `64 capacity_chunks` tokens; ValueError when sequences x heads exceed 65535.
+    into (a host-positioned `CausalStateView`, `pool.at(slots)`; with cu_seqlens only): sequence s of the pack is prefilled into slot
+    `slots[s]` of the pool, in the same single launch chain (`mhla_causal_varlen_state_init_slots`), and the view is returned: those
+    slots -- finished chunks of S, P, Cur, pos, a cleared `full` flag and the host mirror -- then hold bit for bit what the call
+    without `into` returns, and every other slot keeps every bit.  The capacity is the pool's: `capacity_chunks` together with
+    `into` is a ValueError, as is a pack whose number of sequences is not the view's."""
+    if into is not None and cu_seqlens is None:
+        raise ValueError("mhla_causal_state: into= takes a pack (cu_seqlens=)")
     if cu_seqlens is not None:
-        plan, cap = _causal_state_pack_args("mhla_causal_state", k, v, mixing_matrix, cu_seqlens, lengths, left_padded, capacity_chunks)
+        plan, cap = _causal_state_pack_args("mhla_causal_state", k, v, mixing_matrix, cu_seqlens, lengths, left_padded, capacity_chunks, into)
         _, T, H, K = k.shape
         if T:
             _require_gpu(k, v, mixing_matrix, plan.table)
+        if into is not None:
+            pool = into.pool
+            with torch.no_grad():
+                seq_len = torch.tensor(plan.lengths, dtype=torch.int32).to(k.device)   # the one small copy of the call
+                idx = into.map.to(torch.int64)
+                if T:
+                    _causal_state_init_pack(k.detach(), v.detach(), mixing_matrix, into, plan, seq_len)
+                else:   # (an all-empty pack launches nothing: empty slots)
+                    pool.P[idx] = 0
+                    pool.Cur[idx] = 0
+                pool.pos[idx] = seq_len
+                if pool._full is not None:
+                    pool._full[idx] = 0
+            into.lengths = plan.lengths
+            return into
         with torch.no_grad():
             state = CausalState.empty(len(plan.lengths), H, K, v.shape[-1], cap, k.device, 64)
             # (the launch chain writes P and Cur of every sequence, the empty ones included: nothing to zero first)
             P, Cur = (state.P, state.Cur) if not T else (torch.empty_like(state.P), torch.empty_like(state.Cur))
             state = CausalState(state.S, P, Cur, 0, 64, lengths=plan.lengths)
             if T:
-                _causal_state_init_pack(k.detach(), v.detach(), mixing_matrix, state, plan)
+                _causal_state_init_pack(k.detach(), v.detach(), mixing_matrix, state, plan, state.pos)
         return state
     if k.dim() != 4 or v.dim() != 4:
         raise ValueError("k: [B, T, H, K], v: [B, T, H, V]")
@@ -1738,6 +1983,8 @@ def _decode_entry(fn, state, q, k, v, one_token, refuse_stale):
     `mhla_causal_step_dev`, which never reads it), the tensors' rank, the token count."""
     if not isinstance(state, CausalState):
         raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
+    if refuse_stale and isinstance(state, CausalStateView):   # (a slot map on the device: the device-positioned step alone)
+        state._host_slots(fn)
     if refuse_stale and state.stale:
         state._refuse_stale(fn)
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
@@ -1771,7 +2018,8 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
         raise ValueError(str(e)) from None
     if q.dtype not in _DTYPES:
         raise ValueError(f"{fn}: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
-    if tuple(state.S.shape) != (B, Hk, cap, K, V) or tuple(state.P.shape) != (B, Hk, K, V) or tuple(state.Cur.shape) != (B, Hk, K, V):
+    nrow = state.S.shape[0]   # the state's batch rows: B, or -- a view -- the slots of the pool, B of which the call selects
+    if _state_rows(state) != B or tuple(state.S.shape) != (nrow, Hk, cap, K, V) or tuple(state.P.shape) != (nrow, Hk, K, V) or tuple(state.Cur.shape) != (nrow, Hk, K, V):
         raise ValueError(f"{fn}: state is {state!r}, the {'token has' if T == 1 else 'tokens have'} B={B} H={H if Hk == H else Hk} K={K} V={V}"
                          + ("" if Hk == H else f" (k/v heads; q has {H})"))
     dev = q.device
@@ -1803,8 +2051,10 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
         raise ValueError(f"{fn}: gate / norm_weight given with epilogue=False")
     if not (state.S.is_contiguous() and state.P.is_contiguous() and state.Cur.is_contiguous()):
         raise ValueError(f"{fn}: state tensors must be contiguous")
-    if state.lengths is not None and (len(state.lengths) != B or state.pos is None or state.pos.device != dev or state.pos.dtype != torch.int32
-                                      or tuple(state.pos.shape) != (B,) or not state.pos.is_contiguous()):
+    # (a view whose slot map is on the device has no host lengths; its positions are the pool's all the same)
+    if (state.lengths is not None or isinstance(state, CausalStateView)) and (
+            (state.lengths is not None and len(state.lengths) != B) or state.pos is None or state.pos.device != dev
+            or state.pos.dtype != torch.int32 or tuple(state.pos.shape) != (nrow,) or not state.pos.is_contiguous()):
         raise ValueError(f"{fn}: a ragged state carries B={B} lengths and `pos`, a contiguous int32 [B] tensor on {dev}")
     # (nothing from here to the end of the call is recorded for autograd, with or without torch.no_grad(): grad mode is off or no
     # token tensor requires grad, both matrices are detached, and the launch reads and writes through raw pointers)
@@ -1814,6 +2064,11 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
     wf = norm_weight.detach().reshape(V).to(torch.float32).contiguous() if norm_weight is not None else None
     # (built without the generated `__new__`: one Python call less on a path that is bound by the host)
     return tuple.__new__(_Prepared, (q, k, v, gate, _mix2d(mixing_matrix), wf, pos, scale, want_y))
+
+
+# the entry point that runs a ragged call on chosen slots of a pool (a `CausalStateView`)
+_SLOT_CALLS = {"mhla_causal_step_ragged": "mhla_causal_step_slots", "mhla_causal_step_dev": "mhla_causal_step_dev_slots",
+               "mhla_causal_extend_ragged": "mhla_causal_extend_slots", "mhla_causal_verify_ragged": "mhla_causal_verify_slots"}
 
 
 @_device_guard
@@ -1826,6 +2081,10 @@ def _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, name, twin, state, mi
     lib = _lib.load()
     B, _, H, K = q.shape
     call, heads = _gqa_call(lib, name, H, k.shape[2]) if twin else (getattr(lib, name), (H,))
+    slot = getattr(state, "map", None)
+    if slot is not None:   # a view of a pool, or a batch slice of one: the slotted namesake -- the map after the positions, Hkv after H
+        name = _SLOT_CALLS[name]
+        call, heads, middle = getattr(lib, name), (H, k.shape[2]), (middle[0], slot.data_ptr(), state.S.shape[0], *middle[1:])
     ws = _ws(ws_bytes, q.device)
     # (the two optional arguments spelt out, not through `_view_or_null` / `_ptr`: two Python calls on a host-bound path)
     rc = call(_view(q), _view(k), _view(v), *_state_head(mixf, state), *middle, NULL_VIEW if want_y else _view(res),
@@ -1935,7 +2194,7 @@ def mhla_causal_step_dev(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixi
     fn = "mhla_causal_step_dev"
     _decode_entry(fn, state, q, k, v, True, False)   # (a stale mirror is what this call leaves: not refused)
     B, _, H, K = q.shape
-    if state.lengths is None:
+    if state.lengths is None and not isinstance(state, CausalStateView):   # (a view is of a ragged pool, whatever its map)
         raise ValueError(f"{fn}: the state is uniform ({state!r}); the positions must live on the device: pass state.to_ragged()")
     cap = state.capacity_chunks
     if mixing_matrix.dim() < 2 or mixing_matrix.shape[0] < cap or mixing_matrix.shape[1] < cap:
@@ -2091,6 +2350,9 @@ def _extend_counts(fn, prepared, state, counts, left_padded, res, norm_eps):
             else:
                 res[:, t0:t1].zero_()
         return res
+    if over and isinstance(state, CausalStateView):
+        raise ValueError(f"{fn}: {B} sequences x {T} tokens need a workspace beyond EXTEND_WS_CAP_BYTES={EXTEND_WS_CAP_BYTES}, and a view "
+                         "of a pool has no sequential fallback: extend fewer tokens or sequences per call")
     if over:
         res.zero_()
         step_t = _extend_step_t(1, H, K, V)
@@ -2152,7 +2414,8 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     prepared = _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue)
     pos = prepared.pos
     res = q.new_empty((B, T, H, V))
-    if state.lengths is not None and (k.shape[2] != H or any(n != state.lengths[0] for n in state.lengths)):
+    # (a view of a pool: always the ragged chain, which addresses through the slot map)
+    if state.lengths is not None and (k.shape[2] != H or any(n != state.lengths[0] for n in state.lengths) or isinstance(state, CausalStateView)):
         return _extend_counts(fn, prepared, state, (T,) * B, False, res, norm_eps)
     if k.shape[2] != H:   # grouped heads have no uniform kernels: the ragged chain on the same storage, its positions filled on the device
         rag = CausalState(state.S, state.P, state.Cur, 0, 64, lengths=(pos,) * B,
@@ -2175,12 +2438,14 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
 class CausalDraft:
     """What `mhla_causal_verify` hands to `mhla_causal_commit`: the draft's prepared `k`, `v` (REFERENCES to the tensors the verify
     read, or to their contiguous copies -- not copies of their own), `counts` (B ints), `left_padded`, and `lengths`, the state's
-    lengths when the draft was verified, which a commit holds the state to."""
+    lengths when the draft was verified, which a commit holds the state to; `view`, the `CausalStateView` the draft was verified on
+    (None: a state of its own), which a commit holds the state to as well -- the same pool and the same slots."""
 
-    __slots__ = ("k", "v", "counts", "left_padded", "lengths")
+    __slots__ = ("k", "v", "counts", "left_padded", "lengths", "view")
 
-    def __init__(self, k, v, counts, left_padded, lengths):
+    def __init__(self, k, v, counts, left_padded, lengths, view=None):
         self.k, self.v, self.counts, self.left_padded, self.lengths = k, v, tuple(counts), bool(left_padded), tuple(lengths)
+        self.view = view
 
     def __repr__(self):
         return f"CausalDraft(counts={self.counts}, left_padded={self.left_padded}, lengths={self.lengths})"
@@ -2207,7 +2472,7 @@ def mhla_causal_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     V = v.shape[-1]
     counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, (T,) * B if counts is None else counts, scale, gate,
                                        norm_weight, epilogue)
-    draft = CausalDraft(prepared.k, prepared.v, counts, left_padded, state.lengths)
+    draft = CausalDraft(prepared.k, prepared.v, counts, left_padded, state.lengths, state if isinstance(state, CausalStateView) else None)
     if not any(counts):
         return torch.zeros((B, T, H, V), dtype=q.dtype, device=q.device), draft
     slices = _ragged_slices(fn, state, counts, H, prepared.mixf)
@@ -2232,10 +2497,12 @@ def _causal_commit_ragged(k, v, mixf, state, pos, ntok, acc, plan, left_padded):
     dt = _dtype_code(k)
     max_end, max_later, any_close, _ = plan
     ws = _ws(lib.mhla_causal_commit_ragged_ws_bytes(B, dt), k.device)
-    rc = lib.mhla_causal_commit_ragged(_view(k), _view(v), *_state_head(mixf, state), pos.data_ptr(), ntok.data_ptr(), acc.data_ptr(), T,
-                                       max_end, max_later, int(any_close), int(bool(left_padded)), ws.data_ptr(), ws.numel() * 4, B, H, K, V,
-                                       state.chunk_size, dt, _stream())
-    _lib.check(rc, "mhla_causal_commit_ragged")
+    slot = getattr(state, "map", None)   # (a view of a pool, or a batch slice of one: the slotted namesake)
+    name, where = ("mhla_causal_commit_ragged", ()) if slot is None else ("mhla_causal_commit_slots", (slot.data_ptr(), state.S.shape[0]))
+    rc = getattr(lib, name)(_view(k), _view(v), *_state_head(mixf, state), pos.data_ptr(), *where, ntok.data_ptr(), acc.data_ptr(), T,
+                            max_end, max_later, int(any_close), int(bool(left_padded)), ws.data_ptr(), ws.numel() * 4, B, H, K, V,
+                            state.chunk_size, dt, _stream())
+    _lib.check(rc, name)
 
 
 def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: CausalState, accept) -> CausalState:
@@ -2251,9 +2518,15 @@ def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: C
         raise TypeError(f"{fn}: draft must be a CausalDraft (what mhla_causal_verify returns), got {type(draft).__name__}")
     if not isinstance(state, CausalState):
         raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
+    if isinstance(state, CausalStateView):
+        state._host_slots(fn)
     state._refuse_stale(fn)
     if state.lengths is None:
         raise ValueError(f"{fn}: the state is uniform ({state!r}); a draft is verified on, and committed to, a ragged state")
+    seen_on, given = ((x.pool, x.slots) if isinstance(x, CausalStateView) else None for x in (draft.view, state))
+    if seen_on != given:   # (pools compare by identity)
+        raise ValueError(f"{fn}: the draft was verified on {draft.view if draft.view is not None else 'a state of its own'!r}, "
+                         f"the commit is given {state!r}: pass the view (the same pool and slots) the verify took")
     B = len(draft.counts)
     accept = _int_tuple(fn, "accept", accept, B, draft.counts)
     if tuple(state.lengths) != draft.lengths:
@@ -2262,7 +2535,7 @@ def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: C
         return state
     k, v = draft.k, draft.v
     _, T, H, K = k.shape
-    if tuple(state.S.shape) != (B, H, state.capacity_chunks, K, v.shape[-1]) or state.S.device != k.device:
+    if _state_rows(state) != B or tuple(state.S.shape[1:]) != (H, state.capacity_chunks, K, v.shape[-1]) or state.S.device != k.device:
         raise ValueError(f"{fn}: state is {state!r}, the draft has B={B} H={H} K={K} V={v.shape[-1]} on {k.device}")
     if mixing_matrix.dim() < 2 or mixing_matrix.device != k.device:
         raise ValueError(f"{fn}: mixing_matrix must be [L, L(, 1, 1, 1, 1)] on {k.device}, got {tuple(mixing_matrix.shape)} on "

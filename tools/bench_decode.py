@@ -76,6 +76,16 @@ K = 128, V = 256, bf16, `summaries="tf32"`, plain and with the fused norm x gate
 identical runs), the kernels' device times, the workspace each path asks for and the peak of `torch.cuda.max_memory_allocated` over
 one call above what the inputs hold.
 
+`--slots`: the step on chosen slots of a state pool (`CausalState.at`) at the C5 head (H = 4, K = 128, V = 256, bf16, L = 128), B = 8 and
+32, lengths as for `--ragged`, non-boundary steps: (a) the un-slotted ragged step and device-positioned step on a compact state of B
+rows, (b) the same batch through a permuted view of a pool of 2 B slots (the host-positioned view for the step, a map on the device for
+the device-positioned step), (c) what a pool costs without views: `index_select` the live rows of S, P, Cur and pos into a fresh
+state, step it, `index_copy_` P, Cur and pos back (S does not change off a boundary: the cheapest honest form of it).  Alternating in
+one run, `--reps` times (at least four), `--steps` calls each (a quarter of them for (c)): wall time per call and, for (a) and (b), the
+device time of the library's kernels, each with median, min and max.  Positions and host mirror are put back before every call, for
+every variant, so that every call is the same step.  On a tree without `CausalState.at` the same command times (a) alone: the
+figure to hold the un-slotted path of a later tree against.
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -372,6 +382,95 @@ def graph_config(B, H, K, V, steps, reps):
            "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()},
            "replay_median_below_min_eager_ragged": statistics.median(wall["replay"]) < min(wall["ragged"]),
            "replay_pro_median_below_min_eager_ragged_pro": statistics.median(wall["replay_pro"]) < min(wall["ragged_pro"])}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def slots_config(B, H, K, V, steps, reps):
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    q, k, v = token(B, H, K, V, g)
+    i0 = 15
+    chunks = [i0 + (-2, -1, 1, 2)[b % 4] for b in range(B)]
+    lengths = tuple(c * 64 + (7 * b) % 63 for b, c in enumerate(chunks))
+    n_slots = 2 * B
+    slots = torch.randperm(n_slots, generator=g)[:B].tolist()
+
+    def make(rows, lens):
+        st = mhla_amd.CausalState.empty(rows, H, K, V, L, DEV)
+        st.S[:, :, :i0 + 3].normal_(0, 0.1)
+        st.P.normal_(0, 0.1)
+        st = mhla_amd.CausalState(st.S, st.P, st.Cur, lengths=lens)
+        st.full
+        return st
+
+    rag = make(B, lengths)
+    pos0 = torch.tensor(lengths, dtype=torch.int32, device=DEV)
+
+    def put_back(st, lens, pos):
+        st.lengths, st.seen, st.stale = lens, max(lens), False
+        st.pos.copy_(pos)
+
+    def compact_step():
+        put_back(rag, lengths, pos0)
+        mhla_amd.mhla_causal_step(q, k, v, mix, rag)
+
+    def compact_dev():
+        put_back(rag, lengths, pos0)
+        mhla_amd.mhla_causal_step_dev(q, k, v, mix, rag)
+
+    fns = {"compact_step": compact_step, "compact_dev": compact_dev}
+    states = [rag]
+    if hasattr(mhla_amd.CausalState, "at"):
+        pool_lengths = [0] * n_slots
+        for s_, n in zip(slots, lengths):
+            pool_lengths[s_] = n
+        pool_lengths = tuple(pool_lengths)
+        pool = make(n_slots, pool_lengths)
+        pool_pos0 = torch.tensor(pool_lengths, dtype=torch.int32, device=DEV)
+        idx = torch.tensor(slots, dtype=torch.int64, device=DEV)
+        view, dev_view = pool.at(slots), pool.at(idx.to(torch.int32))
+        states.append(pool)
+
+        def view_step():
+            put_back(pool, pool_lengths, pool_pos0)
+            mhla_amd.mhla_causal_step(q, k, v, mix, view)
+
+        def view_dev():
+            put_back(pool, pool_lengths, pool_pos0)
+            mhla_amd.mhla_causal_step_dev(q, k, v, mix, dev_view)
+
+        def gather_scatter():
+            put_back(pool, pool_lengths, pool_pos0)
+            live = mhla_amd.CausalState(pool.S.index_select(0, idx), pool.P.index_select(0, idx), pool.Cur.index_select(0, idx), lengths=lengths,
+                                        pos=pool.pos.index_select(0, idx))
+            mhla_amd.mhla_causal_step(q, k, v, mix, live)
+            pool.P.index_copy_(0, idx, live.P)
+            pool.Cur.index_copy_(0, idx, live.Cur)
+            pool.pos.index_copy_(0, idx, live.pos)
+
+        fns.update(view_step=view_step, view_dev=view_dev, gather_scatter=gather_scatter)
+    wall = {n: [] for n in fns}
+    dev = {n: [] for n in fns if n != "gather_scatter"}
+    kern = {}
+    with torch.no_grad():
+        for _ in range(max(4, reps)):
+            for n, fn in fns.items():
+                wall[n].append(batch_us(fn, max(10, steps // 4) if n == "gather_scatter" else steps))
+            for n in dev:
+                kern[n] = kernel_times(fns[n], iters=20)
+                dev[n].append(sum(kern[n].values()))
+            for st in states:
+                st.Cur.zero_()
+    med = {n: statistics.median(x) for n, x in wall.items()}
+    rec = {"slots": {"B": B, "H": H, "K": K, "V": V, "n_slots": n_slots, "slots": slots, "chunks": sorted(set(chunks))}, "steps_per_batch": steps,
+           "reps": max(4, reps), "wall_us": {n: spread(x) for n, x in wall.items()}, "device_us": {n: spread(x) for n, x in dev.items()},
+           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()}}
+    if "view_step" in fns:
+        rec["view_over_compact_device"] = {h: round(statistics.median(dev["view_" + h]) / statistics.median(dev["compact_" + h]), 3) for h in ("step", "dev")}
+        rec["view_over_compact_wall"] = {h: round(med["view_" + h] / med["compact_" + h], 3) for h in ("step", "dev")}
+        rec["gather_scatter_over_compact_wall"] = round(med["gather_scatter"] / med["compact_step"], 2)
+        rec["pool_MB"] = round(pool.nbytes / 2 ** 20, 1)
     print(json.dumps(rec), flush=True)
     return rec
 
@@ -736,8 +835,12 @@ if __name__ == "__main__":
     ap.add_argument("--speculative", action="store_true")
     ap.add_argument("--gqa", action="store_true")
     ap.add_argument("--gqa-prefill", action="store_true")
+    ap.add_argument("--slots", action="store_true")
     a = ap.parse_args()
-    if a.gqa_prefill:
+    if a.slots:
+        for B in (8, 32):
+            slots_config(B, 4, 128, 256, max(200, a.steps), a.reps)
+    elif a.gqa_prefill:
         for fused in (False, True):
             for Hkv in (8, 4, 2):
                 gqa_prefill_config(16, Hkv, 128, 256, 8192, fused, min(20, a.steps), a.reps)
