@@ -634,6 +634,55 @@ int mhla_causal_varlen_state_init_slots(mhla_view k, mhla_view v, const float* m
                                         int K, int V, int chunk, int n_chunks, const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev,
                                         int dtype, void* stream);
 
+/* Paged calls: the slotted calls above on a pool whose FINISHED CHUNKS ARE PAGES (added without a change of any existing signature or
+ * behaviour: MHLA_ABI_VERSION stays 9).  A dense pool reserves cap_chunks chunks of S per slot whatever the request's length; a paged
+ * pool keeps S as `pages`, fp32 [n_pages][Hkv][K][V], 16-byte aligned -- one page holds one chunk of one sequence, all k/v heads --
+ * and `table_dev`, device int32 [n_slots][cap_chunks], 4-byte aligned: chunk j of state row sb, head h lives at
+ * pages + ((int64)table_dev[sb * cap_chunks + j] * Hkv + h) * K * V.  An entry outside 0 .. n_pages - 1 means NO PAGE.  A finished
+ * chunk is never written again (the open chunk lives in Cur, its summary reaches S only when the chunk closes, and a verify writes
+ * only chunks at and beyond pos / 64), so rows may name the same page for a shared prefix: pages are the caller's to count and free.
+ * Each call is its *_slots namesake with `float* S` replaced by (pages, n_pages, table_dev); P, Cur, pos_dev, full_dev and the slot
+ * map keep their meaning, cap_chunks is the table's row length and remains the bound on positions.  Row b gets, bit for bit, what
+ * the namesake gives on the dense pool whose S[sb][h][j] holds the page's tile: the same launches, tiles, K split and order of
+ * every sum -- only the address of a chunk differs.
+ * Host-positioned calls (step, extend, verify, commit, varlen_state_init): the caller has given a page to every chunk that holds a
+ * token of the row afterwards, chunks 0 .. ceil(n_after / 64) - 1.  Defence only: no address is ever formed from an entry that
+ * is no page -- a write there is dropped (a step on a boundary then leaves that row's S, P and Cur as they are), a read there
+ * contributes no term.
+ * mhla_causal_step_dev_paged: row sb is LIVE iff 0 <= pos < 64 cap_chunks AND table_dev[sb][pos / 64] names a page; otherwise it
+ * takes the frozen branch of mhla_causal_step_dev unchanged (nothing of the pool touched, the row zeros, full_dev[sb] = 1).  Step,
+ * roll and finish each derive that from pos and the table alone; the boundary roll writes S[pos / 64] to the page that made the
+ * row live.  Like the slot map, the table may be rewritten in place between the replays of a captured graph.
+ * Checks, before any launch: pages non-null and 16-byte aligned, table_dev non-null and 4-byte aligned, n_pages > 0 (MHLA_EINVAL);
+ * then those of the namesake.  Workspaces: the namesakes' functions. */
+int mhla_causal_step_paged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages,
+                           const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev, int n_slots,
+                           int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y,
+                           void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream);
+int mhla_causal_step_dev_paged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages,
+                               const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev,
+                               int n_slots, int32_t* full_dev, const void* rope_cos, const void* rope_sin, int64_t ld_tab, int64_t tab_rows,
+                               int feature_map, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws,
+                               size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream);
+int mhla_causal_extend_paged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages,
+                             const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev,
+                             int n_slots, const int32_t* ntok_dev, int T, int64_t max_end, int max_later, int any_close, int left_padded,
+                             mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B,
+                             int H, int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream);
+int mhla_causal_verify_paged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages,
+                             const int32_t* table_dev, int cap_chunks, float* P, float* Cur, const int32_t* pos_dev, const int32_t* slot_dev,
+                             int n_slots, const int32_t* ntok_dev, int T, int64_t max_end, int max_later, int any_close, int left_padded,
+                             mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B,
+                             int H, int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream);
+int mhla_causal_commit_paged(mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages, const int32_t* table_dev,
+                             int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev, int n_slots,
+                             const int32_t* ntok_dev, const int32_t* accept_dev, int T, int64_t max_end, int max_later, int any_close,
+                             int left_padded, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, int dtype, void* stream);
+int mhla_causal_varlen_state_init_paged(mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages,
+                                        const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int n_seqs, const int32_t* seq_len_dev,
+                                        const int32_t* slot_dev, int n_slots, int max_len, int T, int H, int K, int V, int chunk, int n_chunks,
+                                        const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, int dtype, void* stream);
+
 /* ---- prologue: q / k of the Wan host -------------------------------------- */
 
 /*

@@ -179,6 +179,11 @@ SIGNATURES = {
     "mhla_rmsnorm_gate_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                       c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_int, c_void_p]),
 }
+# paged calls: each *_slots namesake with `float* S` (the argument after ldmix) replaced by (pages, n_pages, table_dev)
+for _name in ("step", "step_dev", "extend", "verify", "commit", "varlen_state_init"):
+    _res, _args = SIGNATURES[f"mhla_causal_{_name}_slots"]
+    _at = _args.index(c_int) + 1   # (ldmix is the first int of every one of them)
+    SIGNATURES[f"mhla_causal_{_name}_paged"] = (_res, _args[:_at] + [c_void_p, c_int, c_void_p] + _args[_at + 1:])
 
 _lib = None
 

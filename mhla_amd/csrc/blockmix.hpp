@@ -129,6 +129,10 @@ struct StateArgsDst : StateArgsVar {
     // mhla_causal_varlen_state_init_slots: Sq and Cur are a pool of n_slots rows, sequence s of the pack goes to row slot[s]
     const int* slot;  // [nseq], 4-byte aligned, or null: row s itself
     int n_slots;
+    // mhla_causal_varlen_state_init_paged: Sq is a pool of pages [n_pages][H][DX][DY]; chunk j of row r lives in page table[r cap + j],
+    // an entry outside 0 .. n_pages - 1 is no page and the tile is dropped (Cur stays dense per row)
+    const int* table; // [n_slots][cap], 4-byte aligned, or null: Sq is dense
+    int n_pages;
 };
 
 template <int DT>
@@ -262,7 +266,13 @@ __global__ __launch_bounds__(NTHREADS) void k_bm_state(const A a) {
             if ((unsigned)row >= (unsigned)a.n_slots) return;
         }
         const long sh = (long)row * a.H + h;
-        ob = whole ? a.Sq + (sh * a.cap + d.y) * DX * DY : a.Cur + sh * DX * DY;
+        if (whole && a.table) {   // the finished chunks are pages: the tile goes to the page the row's table names, nowhere without one
+            const int pg = ld_tab1(a.table + (long)row * a.cap, d.y);
+            if ((unsigned)pg >= (unsigned)a.n_pages) return;
+            ob = a.Sq + ((long)pg * a.H + h) * DX * DY;
+        } else {
+            ob = whole ? a.Sq + (sh * a.cap + d.y) * DX * DY : a.Cur + sh * DX * DY;
+        }
     } else {
         ob = a.out + ((long)bh * a.M + blk) * DX * DY;
     }

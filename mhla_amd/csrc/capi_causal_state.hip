@@ -1,5 +1,5 @@
 // C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
-// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged, the grouped-query forms mhla_causal_*_gqa of the ragged entry points, and their forms on chosen rows of a state pool, mhla_causal_*_slots; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged, the grouped-query forms mhla_causal_*_gqa of the ragged entry points, their forms on chosen rows of a state pool, mhla_causal_*_slots, and those on a pool whose finished chunks are pages, mhla_causal_*_paged; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
@@ -54,13 +54,23 @@ int cst_check_dev(const char* name, const void* p) {   // an int32 array on the 
 }
 // the slot map of a slotted call (the *_slots entry points): call row b works on row map[b] of a state pool of n rows; map null:
 // the un-slotted namesake, row b itself
+// a paged pool (the *_paged entry points) on top: the chains' `S` is then the pool of pages [n_pages][Hkv][K][V], and
+// table[map[b] cap_chunks + j] names the page of chunk j of call row b; table null: S is the dense array it was
 struct Slots {
     const int32_t* map = nullptr;
     int n = 0;
+    const int32_t* table = nullptr;
+    int n_pages = 0;
 };
 int cst_check_slots(const int32_t* slot_dev, int n_slots) {
     RC(cst_check_dev("slot_dev", slot_dev));
     if (n_slots <= 0) return fail(MHLA_EINVAL, "n_slots=%d must be positive", n_slots);
+    return MHLA_OK;
+}
+int cst_check_pages(const float* pages, int n_pages, const int32_t* table_dev) {
+    if (!pages || ((uintptr_t)pages) % 16) return fail(MHLA_EINVAL, "pages null or not 16-byte aligned");
+    RC(cst_check_dev("table_dev", table_dev));
+    if (n_pages <= 0) return fail(MHLA_EINVAL, "n_pages=%d must be positive", n_pages);
     return MHLA_OK;
 }
 int cst_check_mix(const float* mix, int ldmix, int64_t lastrow) {   // lastrow: the last row of mix the call reads, up to its diagonal
@@ -87,8 +97,8 @@ int cst_roll(float* S, int cap, float* P, float* Cur, const float* mixrow, int n
 // the roll of a ragged state: each sequence for itself, by pos_dev (the position of the token its step just took)
 int cst_roll_ragged(float* S, int cap, float* P, float* Cur, const int32_t* pos_dev, Slots sl, const float* mix, int ldmix, int max_pos, int H,
                     int BH, long E, hipStream_t st) {
-    const CsRollArgs r{S, P, Cur, nullptr, E, cap, 0, 0, pos_dev, mix, ldmix, max_pos, H, sl.map, sl.n};
-    return launch(sl.map ? k_cs_roll<true, false, true> : k_cs_roll<true>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st,
+    const CsRollArgs r{S, P, Cur, nullptr, E, cap, 0, 0, pos_dev, mix, ldmix, max_pos, H, sl.map, sl.n, sl.table, sl.n_pages};
+    return launch(sl.table ? k_cs_roll<true, false, true, true> : sl.map ? k_cs_roll<true, false, true> : k_cs_roll<true>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st,
                   "k_cs_roll_ragged", r);
 }
 int cst_zero_cur(float* Cur, int BH, long E, hipStream_t st) {
@@ -128,7 +138,7 @@ int cst_xty_pack(const mhla_view& k, const mhla_view& v, float* S, int cap, floa
     a.x = cv(k); a.y = cv(v);
     a.H = H; a.M = 0; a.S = CS; a.D = 64; a.DX = K; a.DY = V; a.T = T_; a.alpha = 1.f;
     a.tab = (const tab2_t*)tab; a.dst = dst; a.Sq = S; a.Cur = Cur; a.nseq = n_seqs; a.cap = cap;
-    a.slot = sl.map; a.n_slots = sl.n;
+    a.slot = sl.map; a.n_slots = sl.n; a.table = sl.table; a.n_pages = sl.n_pages;
     const int strips = ((K + 63) / 64) * ((V + 63) / 64);
     return launch(k_bm_state<T, 4, 2, StateArgsDst>, dim3((unsigned)n_chunks, H, strips), dim3(NTHREADS), state_smem_floats<4>() * 4, st,
                   "k_bm_state<2,dst>", a);
@@ -207,7 +217,7 @@ int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float
     float* stage = tiles + p.tiles;
     int* nval = (int*)(stage + p.stage);
     const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0, dry ? 1 : 0, nullptr,
-                  sl.map, sl.n};
+                  sl.map, sl.n, sl.table, sl.n_pages};
     const int kr = cst_rows((size_t)H, K, V);   // a one-token sequence: the step's K split for a batch of one
     // every launch but the last addresses by pos_dev; the last, which does not, advances it (dry: does not)
     DISPATCH_T(dtype, {
@@ -278,6 +288,12 @@ int cs_step_ragged_chain(mhla_view q, mhla_view k, mhla_view v, const float* mix
     return MHLA_OK;
 }
 
+// the device-positioned step's kernel: un-slotted, slotted, or slotted on a paged pool (each instantiation the code it was)
+template <typename ET, bool PRO, int GM>
+auto cs_dev_step_kernel(const Slots& sl) {
+    return sl.table ? k_cs_step<ET, true, true, PRO, GM, true, true> : sl.map ? k_cs_step<ET, true, true, PRO, GM, true> : k_cs_step<ET, true, true, PRO, GM>;
+}
+
 // the device-positioned step chain; Hkv < H as in cs_step_ragged_chain (the fused prologue: k once per k/v head, q per query head)
 int cs_step_dev_chain(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
                       float* Cur, int32_t* pos_dev, Slots sl, int32_t* full_dev, const void* rope_cos, const void* rope_sin, int64_t ld_tab,
@@ -312,20 +328,19 @@ int cs_step_dev_chain(mhla_view q, mhla_view k, mhla_view v, const float* mix, i
     DISPATCH_T(dtype, {
         CsStepArgs s{cv(q), cv(k), cv(v), mix, P, Cur, (float*)ws, Hkv, K, V, 0, 0, pos_dev, ldmix, max_pos,
                      rope_cos, rope_sin, (long)ld_tab, (int)tab_rows, feature_map};
-        s.slot = sl.map; s.n_slots = sl.n;
+        s.slot = sl.map; s.n_slots = sl.n; s.table = sl.table; s.tcap = cap_chunks; s.n_pages = sl.n_pages;
         if (G == 1) {
-            if (pro) RC(cst_step(sl.map ? k_cs_step<ET, true, true, true, 1, true> : k_cs_step<ET, true, true, true>, "k_cs_step_dev<pro>", s, BH, st));
-            else     RC(cst_step(sl.map ? k_cs_step<ET, true, true, false, 1, true> : k_cs_step<ET, true, true, false>, "k_cs_step_dev", s, BH, st));
+            if (pro) RC(cst_step(cs_dev_step_kernel<ET, true, 1>(sl), "k_cs_step_dev<pro>", s, BH, st));
+            else     RC(cst_step(cs_dev_step_kernel<ET, false, 1>(sl), "k_cs_step_dev", s, BH, st));
         } else {
-            if (pro) RC(cst_step(sl.map ? k_cs_step<ET, true, true, true, CST_GMAX, true> : k_cs_step<ET, true, true, true, CST_GMAX>,
-                                 "k_cs_step_dev<pro,gqa>", s, BH, st, G));
-            else     RC(cst_step(sl.map ? k_cs_step<ET, true, true, false, CST_GMAX, true> : k_cs_step<ET, true, true, false, CST_GMAX>,
-                                 "k_cs_step_dev<gqa>", s, BH, st, G));
+            if (pro) RC(cst_step(cs_dev_step_kernel<ET, true, CST_GMAX>(sl), "k_cs_step_dev<pro,gqa>", s, BH, st, G));
+            else     RC(cst_step(cs_dev_step_kernel<ET, false, CST_GMAX>(sl), "k_cs_step_dev<gqa>", s, BH, st, G));
         }
         RC(cst_roll_ragged(S, cap_chunks, P, Cur, pos_dev, sl, mix, ldmix, max_pos, Hkv, B * Hkv, (long)K * V, st));
         CsFinishArgs f{(const float*)ws, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, s.nsplit, pos_dev, max_pos, full_dev};
-        f.slot = sl.map; f.n_slots = sl.n;
-        RC(launch(sl.map ? k_cs_step_finish<ET, true, false, true> : k_cs_step_finish<ET, true>, dim3(BH), dim3(CST_THREADS), 0, st,
+        f.slot = sl.map; f.n_slots = sl.n; f.table = sl.table; f.tcap = cap_chunks; f.n_pages = sl.n_pages;
+        RC(launch(sl.table ? k_cs_step_finish<ET, true, false, true, true>
+                  : sl.map ? k_cs_step_finish<ET, true, false, true> : k_cs_step_finish<ET, true>, dim3(BH), dim3(CST_THREADS), 0, st,
                   "k_cs_step_finish_dev", f));
     });
     return MHLA_OK;
@@ -355,8 +370,8 @@ int cs_pack_chain(mhla_view k, mhla_view v, const float* mix, int ldmix, float* 
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype, { RC(cst_xty_pack<ET>(k, v, S, cap_chunks, Cur, n_seqs, n_chunks, chunk_tab_dev, chunk_dst_dev, sl, T, H, K, V, st)); });
     const long E = (long)K * V;
-    const CsRollArgs r{S, P, Cur, nullptr, E, cap_chunks, 0, 0, seq_len_dev, mix, ldmix, max_len, H, sl.map, sl.n};
-    return launch(sl.map ? k_cs_roll<false, true, true> : k_cs_roll<false, true>, dim3((unsigned)((E / 4 + 63) / 64), n_seqs * H), dim3(64), 0, st,
+    const CsRollArgs r{S, P, Cur, nullptr, E, cap_chunks, 0, 0, seq_len_dev, mix, ldmix, max_len, H, sl.map, sl.n, sl.table, sl.n_pages};
+    return launch(sl.table ? k_cs_roll<false, true, true, true> : sl.map ? k_cs_roll<false, true, true> : k_cs_roll<false, true>, dim3((unsigned)((E / 4 + 63) / 64), n_seqs * H), dim3(64), 0, st,
                   "k_cs_roll_pack", r);
 }
 
@@ -376,7 +391,8 @@ int cx_commit_chain(mhla_view k, mhla_view v, const float* mix, int ldmix, float
     const int BH = B * H, strips = ((K + 63) / 64) * ((V + 63) / 64);
     const long E = (long)K * V;
     int* nval = (int*)ws;
-    const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0, 0, accept_dev, sl.map, sl.n};
+    const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0, 0, accept_dev, sl.map, sl.n, sl.table,
+                  sl.n_pages};
     // every launch but the last addresses by pos_dev; the last, which does not, advances it
     DISPATCH_T(dtype, {
         CxAccArgs c{};
@@ -669,6 +685,73 @@ int mhla_causal_commit_slots(mhla_view k, mhla_view v, const float* mix, int ldm
     RC(cst_check_slots(slot_dev, n_slots));
     return cx_commit_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots}, ntok_dev, accept_dev, T, max_end, max_later,
                            any_close, left_padded, ws, ws_bytes, B, H, K, V, chunk, dtype, stream);
+}
+
+// ---- paged calls: the slotted calls on a pool whose finished chunks are pages named by a per-slot table (mhla_hip.h)
+int mhla_causal_step_paged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages,
+                           const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev, int n_slots,
+                           int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y,
+                           void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check_pages(pages, n_pages, table_dev));
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cs_step_ragged_chain(q, k, v, mix, ldmix, pages, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots, table_dev, n_pages}, max_pos,
+                                any_boundary, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_step_dev_paged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages,
+                               const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev,
+                               int n_slots, int32_t* full_dev, const void* rope_cos, const void* rope_sin, int64_t ld_tab, int64_t tab_rows,
+                               int feature_map, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws,
+                               size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check_pages(pages, n_pages, table_dev));
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cs_step_dev_chain(q, k, v, mix, ldmix, pages, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots, table_dev, n_pages}, full_dev,
+                             rope_cos, rope_sin, ld_tab, tab_rows, feature_map, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk,
+                             scale, dtype, stream);
+}
+
+int mhla_causal_extend_paged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages,
+                             const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev,
+                             int n_slots, const int32_t* ntok_dev, int T, int64_t max_end, int max_later, int any_close, int left_padded,
+                             mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B,
+                             int H, int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check_pages(pages, n_pages, table_dev));
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cx_ragged_chain(false, q, k, v, mix, ldmix, pages, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots, table_dev, n_pages}, ntok_dev,
+                           T, max_end, max_later, any_close, left_padded, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk,
+                           scale, dtype, stream);
+}
+
+int mhla_causal_verify_paged(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages,
+                             const int32_t* table_dev, int cap_chunks, float* P, float* Cur, const int32_t* pos_dev, const int32_t* slot_dev,
+                             int n_slots, const int32_t* ntok_dev, int T, int64_t max_end, int max_later, int any_close, int left_padded,
+                             mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B,
+                             int H, int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream) {
+    RC(cst_check_pages(pages, n_pages, table_dev));
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cx_ragged_chain(true, q, k, v, mix, ldmix, pages, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev),
+                           Slots{slot_dev, n_slots, table_dev, n_pages}, ntok_dev, T, max_end, max_later, any_close, left_padded, out, gate, norm_w,
+                           norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_commit_paged(mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages, const int32_t* table_dev,
+                             int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev, int n_slots,
+                             const int32_t* ntok_dev, const int32_t* accept_dev, int T, int64_t max_end, int max_later, int any_close,
+                             int left_padded, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, int dtype, void* stream) {
+    RC(cst_check_pages(pages, n_pages, table_dev));
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cx_commit_chain(k, v, mix, ldmix, pages, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots, table_dev, n_pages}, ntok_dev, accept_dev,
+                           T, max_end, max_later, any_close, left_padded, ws, ws_bytes, B, H, K, V, chunk, dtype, stream);
+}
+
+int mhla_causal_varlen_state_init_paged(mhla_view k, mhla_view v, const float* mix, int ldmix, float* pages, int n_pages,
+                                        const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int n_seqs, const int32_t* seq_len_dev,
+                                        const int32_t* slot_dev, int n_slots, int max_len, int T, int H, int K, int V, int chunk, int n_chunks,
+                                        const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, int dtype, void* stream) {
+    RC(cst_check_pages(pages, n_pages, table_dev));
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cs_pack_chain(k, v, mix, ldmix, pages, cap_chunks, P, Cur, n_seqs, seq_len_dev, Slots{slot_dev, n_slots, table_dev, n_pages}, max_len, T,
+                         H, K, V, chunk, n_chunks, chunk_tab_dev, chunk_dst_dev, dtype, stream);
 }
 
 }  // extern "C"

@@ -62,6 +62,9 @@ struct CxRag {
     // slotted calls (cst_slot, causal_step.hpp): pos is the pool's [n_slots] and call row b reads pos[slot[b]]; ntok and acc stay the call's
     const int* slot;       // [B] or null
     int n_slots;
+    // paged pools (cst_page, causal_step.hpp): S is a pool of pages and chunk j of state row sb lives in page table[sb cap + j]
+    const int* table;      // [n_slots][cap] or null: S is dense
+    int n_pages;
 };
 struct CxSeq {
     int n, i, r, a;        // tokens; chunk and fill of the open chunk; rows of the first segment
@@ -87,6 +90,14 @@ __device__ __forceinline__ bool cx_seq(const CxRag& g, int b, CxSeq& s) {
     s.full = s.iend >= g.cap;
     s.shift = g.left ? g.T - w : 0;
     return s.later <= g.max_later && (!s.closes || g.any_close);
+}
+
+// where chunk j of state row sb, head h (of H) lives: S[sb][h][j] of a dense state, or its page; null: the table names no page
+// for it (the host assigns every page a call can touch: defence only) and the caller drops the write
+__device__ __forceinline__ float* cx_chunk(float* S, const CxRag& g, int sb, int H, int h, int j, long E) {
+    if (!g.table) return S + (((long)sb * H + h) * g.cap + j) * E;
+    const long pg = cst_page(g.table, g.n_pages, (long)sb * g.cap + j);
+    return pg < 0 ? nullptr : S + (pg * H + h) * E;
 }
 
 struct CxOutArgs {
@@ -333,13 +344,18 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_xty_acc(const CxAccArgs a) {
             if (a.rag.dry && rows < CS) return;   // (the tail would go to Cur)
             if (!rows && !zero_cur) return;
             tok0 = s.shift + s.a + (long)seg * CS;
-            db = rows == CS ? a.S + (sbh * a.rag.cap + s.i + 1 + seg) * E : a.Cur + sbh * E;
+            db = rows == CS ? cx_chunk(a.S, a.rag, s.sb, a.H, h, s.i + 1 + seg, E) : a.Cur + sbh * E;
+            if (!db) {   // (no page)
+                if (!zero_cur) return;
+                rows = 0;
+            }
         } else {
             if (a.rag.dry && !s.closes) return;   // (the sum would go to Cur)
             rows = s.a;
             tok0 = s.shift;
             sb = a.Cur + sbh * E;
-            db = s.closes ? a.S + (sbh * a.rag.cap + s.i) * E : a.Cur + sbh * E;
+            db = s.closes ? cx_chunk(a.S, a.rag, s.sb, a.H, h, s.i, E) : a.Cur + sbh * E;
+            if (!db) return;   // (no page)
             one = s.n == 1;
         }
     } else {
@@ -397,9 +413,14 @@ struct CxMixArgs {
 
 // P_c of the chunks c0 + u0 .. of one (b, h), elements e .. e + 3: ascending j with fmaf (k_cs_roll's sum).  `nws` of them go to the
 // workspace, whose stride per (b, h) is `ws_bh` tiles.  bh: the call's (b, h), which owns the workspace; sbh: the state's (row, head),
-// another only in a slotted call
-__device__ __forceinline__ void cx_mix_sums(const CxMixArgs& a, long bh, long sbh, long e, int c0, int nws, int ws_bh, int nc, int cP) {
-    const float* Sb = a.S + sbh * a.cap * a.E + e;
+// another only in a slotted call.  PAGED: S[j] through `trow`, the state row's entries of the page table (n_pages pages of pg_floats floats,
+// this head's element e at `he` floats from a page's start): a group's eight entries are fetched ahead of its eight tile loads, a chunk without
+// a page contributes no term, and every other term keeps its place
+template <bool PAGED = false>
+__device__ __forceinline__ void cx_mix_sums(const CxMixArgs& a, long bh, long sbh, long e, int c0, int nws, int ws_bh, int nc, int cP,
+                                            [[maybe_unused]] const int* trow = nullptr, [[maybe_unused]] int n_pages = 0,
+                                            [[maybe_unused]] long pg_floats = 0, [[maybe_unused]] long he = 0) {
+    [[maybe_unused]] const float* Sb = PAGED ? nullptr : a.S + sbh * a.cap * a.E + e;
     const int u0 = blockIdx.z * CX_MIX_NC, nu = min(CX_MIX_NC, nc - u0);
     f32x4 acc[CX_MIX_NC];
 #pragma unroll
@@ -411,14 +432,26 @@ __device__ __forceinline__ void cx_mix_sums(const CxMixArgs& a, long bh, long sb
     int j0 = 0;
     for (; j0 + U <= jall; j0 += U) {
         f32x4 s[U];
+        [[maybe_unused]] long pg[U];
+        if constexpr (PAGED) {
 #pragma unroll
-        for (int w = 0; w < U; ++w) s[w] = gld<f32x4>(Sb + (long)(j0 + w) * a.E);
+            for (int w = 0; w < U; ++w) pg[w] = cst_page(trow, n_pages, j0 + w);
+#pragma unroll
+            for (int w = 0; w < U; ++w) {
+                s[w] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (pg[w] >= 0) s[w] = gld<f32x4>(a.S + pg[w] * pg_floats + he);
+            }
+        } else {
+#pragma unroll
+            for (int w = 0; w < U; ++w) s[w] = gld<f32x4>(Sb + (long)(j0 + w) * a.E);
+        }
 #pragma unroll
         for (int u = 0; u < CX_MIX_NC; ++u) {
             if (u < nu) {
                 const float* mr = a.mix + (long)(cbase + u) * a.ldmix + j0;
 #pragma unroll
                 for (int w = 0; w < U; ++w) {
+                    if (PAGED && pg[w] < 0) continue;
                     const float m = mr[w];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) acc[u][t] = fmaf(m, s[w][t], acc[u][t]);
@@ -427,7 +460,15 @@ __device__ __forceinline__ void cx_mix_sums(const CxMixArgs& a, long bh, long sb
         }
     }
     for (int j = j0; j < jend; ++j) {
-        const f32x4 s = gld<f32x4>(Sb + (long)j * a.E);
+        const float* src;
+        if constexpr (PAGED) {
+            const long pg = cst_page(trow, n_pages, j);
+            if (pg < 0) continue;
+            src = a.S + pg * pg_floats + he;
+        } else {
+            src = Sb + (long)j * a.E;
+        }
+        const f32x4 s = gld<f32x4>(src);
 #pragma unroll
         for (int u = 0; u < CX_MIX_NC; ++u) {
             if (u < nu && j < cbase + u) {
@@ -471,16 +512,21 @@ __global__ __launch_bounds__(64) void k_cx_mix_ragged(const CxMixRagArgs a) {
     CxSeq s;
     if (!cx_seq(a.rag, b, s) || !s.closes) return;
     const long sbh = bh + (long)(s.sb - b) * a.H;
+    int c0 = s.i + 1, nws = s.later, ws_bh = a.rag.max_later, nc, cP;
     if (a.rag.dry) {   // the workspace tiles alone: no cP matches and none is negative
-        if (s.later) cx_mix_sums(a.m, bh, sbh, e, s.i + 1, s.later, a.rag.max_later, s.later, 0x7fffffff);
-        return;
+        if (!s.later) return;
+        nc = s.later; cP = 0x7fffffff;
+    } else if (!a.m.ws) {     // chunk iend alone (every accumulator sums ascending j by itself: the group does not change its bits), or P = 0
+        c0 = s.iend; nws = 0; ws_bh = 0; nc = s.full ? 0 : 1; cP = s.full ? -1 : s.iend;
+    } else {
+        nc = (s.full ? s.i + s.later : s.iend) - s.i;
+        cP = s.full ? -1 : s.iend;
     }
-    if (!a.m.ws) {     // chunk iend alone (every accumulator sums ascending j by itself: the group does not change its bits), or P = 0
-        cx_mix_sums(a.m, bh, sbh, e, s.iend, 0, 0, s.full ? 0 : 1, s.full ? -1 : s.iend);
-        return;
-    }
-    const int nc = (s.full ? s.i + s.later : s.iend) - s.i;
-    cx_mix_sums(a.m, bh, sbh, e, s.i + 1, s.later, a.rag.max_later, nc, s.full ? -1 : s.iend);
+    if (a.rag.table)   // a paged pool: the same sums with every S[j] looked up in the row's table
+        cx_mix_sums<true>(a.m, bh, sbh, e, c0, nws, ws_bh, nc, cP, a.rag.table + (long)s.sb * a.rag.cap, a.rag.n_pages, (long)a.H * a.m.E,
+                          (bh - (long)b * a.H) * a.m.E + e);
+    else
+        cx_mix_sums(a.m, bh, sbh, e, c0, nws, ws_bh, nc, cP);
 }
 
 // grid (ceil(B / 64)): the last launch of the commit chain, pos[b] += nval[b] (nval: what the first launch of the chain accepted);

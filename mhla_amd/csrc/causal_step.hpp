@@ -66,6 +66,9 @@ struct CsStepArgs {
     // RAGGED only, slotted calls (cst_slot below): P, Cur and pos belong to a pool of n_slots rows, call row b uses row slot[b]
     const int* slot;       // [B] or null: row b itself
     int n_slots;
+    // PAGED only (DEV on a paged pool, cst_page below): the page table, its row length (the capacity in chunks) and the page count
+    const int* table;      // [n_slots][tcap]
+    int tcap, n_pages;
 };
 
 // Slotted calls (the mhla_causal_*_slots entry points): the state -- S, P, Cur, pos, full -- is a pool of n_slots batch rows, and
@@ -84,6 +87,18 @@ template <bool SLOT>
 __device__ __forceinline__ int cst_row(const int* slot, int n_slots, int b) {
     if constexpr (SLOT) return cst_slot(slot, n_slots, b);
     else return b;
+}
+
+// Paged pools (the mhla_causal_*_paged entry points): the finished chunks S[j] are not a dense [n_slots][H][cap] array but PAGES of
+// a pool [n_pages][H][K][V] -- one page holds one chunk of one sequence, all k/v heads -- and table[sb cap + j] names the page of
+// chunk j of state row sb.  A finished S[j] is never written again, so slots may share pages; P, Cur, pos and full stay dense per
+// slot.  An entry outside 0 .. n_pages - 1 is NO PAGE (-1 here): no address is ever formed from it, a write there is dropped and a
+// read contributes nothing.  The entry is workgroup-uniform and read through the constant address space, a scalar load, as
+// ld_tab1 (blockmix.hpp) reads the pack tables.  Tiling and the order of every sum do not depend on where a chunk lives: the
+// bits are those of the dense state that `compact()` gathers.
+__device__ __forceinline__ long cst_page(const int* table, int n_pages, long at) {
+    const int pg = *(const __attribute__((address_space(4))) int*)(table + at);
+    return (unsigned)pg < (unsigned)n_pages ? (long)pg : -1L;
 }
 
 // pos[b] as the ragged step addresses by it.  Defence only: the caller keeps the array equal to its host mirror, and then the clamp
@@ -116,9 +131,12 @@ constexpr int CST_GMAX = 8;       // query heads per k/v head the grouped step s
 
 // grid (ceil(V / 64), nsplit, B H); GMAX > 1 (grouped-query heads, a.H = Hkv): one accumulator per query head g < a.G of the group,
 // the loop over g fully unrolled and predicated by a.G alone (uniform over the launch)
-template <typename T, bool RAGGED = false, bool DEV = false, bool PRO = false, int GMAX = 1, bool SLOT = false>
+// PAGED (DEV on a paged pool): a sequence is live iff its position is inside the capacity AND the table names a page for chunk
+// pos / 64 -- the page its boundary roll will write; the step itself touches no page
+template <typename T, bool RAGGED = false, bool DEV = false, bool PRO = false, int GMAX = 1, bool SLOT = false, bool PAGED = false>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
     static_assert(!SLOT || RAGGED, "a slot map goes with positions on the device");
+    static_assert(!PAGED || (SLOT && DEV), "the step reads the page table only to tell a live sequence from a frozen one");
     static_assert(!DEV || RAGGED, "DEV is the ragged step, bounded by the capacity");
     static_assert(!PRO || DEV, "the fused prologue goes with the device-positioned step");
     static_assert(GMAX == 1 || RAGGED, "grouped heads: the ragged and device-positioned steps only");
@@ -143,6 +161,9 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
     }
     if constexpr (DEV) {
         int p = SLOT && sb < 0 ? -1 : a.pos[sb];
+        if constexpr (PAGED) {   // (no page for the open chunk: frozen, as a full state is)
+            if (p >= 0 && p <= a.max_pos && cst_page(a.table, a.n_pages, (long)sb * a.tcap + p / CS) < 0) p = -1;
+        }
         if (p < 0 || p > a.max_pos) {   // frozen (an inactive row of a slotted call included): zeros as partial sums, the state untouched
             live = false;
             p = 0;
@@ -245,6 +266,9 @@ struct CsFinishArgs {
     // slotted calls (cst_slot): advance and full are the pool's [n_slots], call row b moves entry slot[b]; an inactive row moves none
     const int* slot;       // [B] or null
     int n_slots;
+    // PAGED only (DEV on a paged pool): a position whose chunk has no page in the table stays as well, and full[b] = 1
+    const int* table;      // [n_slots][tcap]
+    int tcap, n_pages;
 };
 
 // grid (B H, T tokens): o = scale * (partials in split order); y = o rsqrt(mean(o^2 over V) + neps) nw g sigmoid(g), from the fp32 o
@@ -252,9 +276,10 @@ struct CsFinishArgs {
 // its step wrote, so its row needs no branch here
 // WIN: a row outside its sequence's window is written as zeros (out and y) and reads nothing else; advance[b] += nval[b].  pos is
 // not read by any other thread of this launch: the window comes from nval, which an earlier launch of the chain wrote
-template <typename T, bool DEV = false, bool WIN = false, bool SLOT = false>
+template <typename T, bool DEV = false, bool WIN = false, bool SLOT = false, bool PAGED = false>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishArgs a) {
     static_assert(!(DEV && WIN), "the device-positioned step has one row per sequence");
+    static_assert(!PAGED || (SLOT && DEV), "the finish reads the page table only to tell a live sequence from a frozen one");
     __shared__ float red[CST_THREADS / 64];
     const int tid = threadIdx.x, bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
     const long tok = blockIdx.y;
@@ -278,7 +303,9 @@ __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishAr
             const int sb = cst_row<SLOT>(a.slot, a.n_slots, b);
             if (!SLOT || sb >= 0) {
                 const int p = a.advance[sb];
-                if (p < 0 || p > a.max_pos) a.full[sb] = 1;
+                bool frozen = p < 0 || p > a.max_pos;
+                if constexpr (PAGED) frozen = frozen || cst_page(a.table, a.n_pages, (long)sb * a.tcap + p / CS) < 0;
+                if (frozen) a.full[sb] = 1;
                 else a.advance[sb] = p + 1;
             }
         }
@@ -358,6 +385,9 @@ struct CsRollArgs {
     // the call's own pos[b] (the tokens of sequence b of the pack)
     const int* slot;       // [B] or null
     int n_slots;
+    // PAGED only (cst_page): S is a pool of pages [n_pages][H][K][V] and chunk j of state row sb lives in page table[sb cap + j]
+    const int* table;      // [n_slots][cap]
+    int n_pages;
 };
 
 // grid (ceil(E / 4 / 64), B H), one wave per workgroup: P = sum_{j < nj} mixrow[j] S[j], ascending j
@@ -366,9 +396,13 @@ struct CsRollArgs {
 // PACK: each (b, h) for itself, the prefix mix of a state whose finished chunks S[0 .. nj) were just written, nj = pos[b] / 64 --
 // no commit; P from row nj of mix, or P = 0 when nj == cap; Cur = 0 where the sequence has no open chunk (pos[b] % 64 == 0, an
 // empty sequence included: P = Cur = 0).  A pos[b] outside 0 .. max_pos leaves the sequence untouched (defence only, as RAGGED)
-template <bool RAGGED = false, bool PACK = false, bool SLOT = false>
+// PAGED: every S[j] through the table, the group's eight entries fetched ahead of its eight tile loads; the same terms in the same
+// order.  A boundary whose chunk has no page leaves the sequence untouched: for the device-positioned step that sequence is frozen
+// (step and finish derive the same from pos and the table), for a host-positioned call it is defence only
+template <bool RAGGED = false, bool PACK = false, bool SLOT = false, bool PAGED = false>
 __global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
     static_assert(!(RAGGED && PACK), "one addressing mode");
+    static_assert(!PAGED || (SLOT && (RAGGED || PACK)), "a paged pool is addressed through a slot map");
     const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
     if (e >= a.E) return;   // (E % 4 == 0)
     long bh = blockIdx.y;   // below: the state's (row, head)
@@ -396,13 +430,29 @@ __global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
         commit = 1;
         mixrow = nj < a.cap ? a.mix + (long)nj * a.ldmix : nullptr;
     }
-    float* Sb = a.S + bh * a.cap * a.E + e;
+    [[maybe_unused]] float* Sb = nullptr;          // dense: S[0] of this (row, head)
+    [[maybe_unused]] const int* trow = nullptr;    // PAGED: this row's entries of the table
+    [[maybe_unused]] long he = 0;                  // PAGED: floats from a page's start to this head's element e
+    if constexpr (PAGED) {
+        trow = a.table + (long)sb * a.cap;
+        he = (long)(blockIdx.y % a.H) * a.E + e;
+    } else {
+        Sb = a.S + bh * a.cap * a.E + e;
+    }
     const long pe = bh * a.E + e;
     int n = nj;
     f32x4 last = {0.f, 0.f, 0.f, 0.f};
     if (commit) {
+        float* dst;
+        if constexpr (PAGED) {
+            const long pg = cst_page(trow, a.n_pages, nj - 1);
+            if (pg < 0) return;   // ahead of any write
+            dst = a.S + pg * a.H * a.E + he;
+        } else {
+            dst = Sb + (long)(nj - 1) * a.E;
+        }
         last = gld<f32x4>(a.Cur + pe);
-        gst<f32x4>(Sb + (long)(nj - 1) * a.E, last);
+        gst<f32x4>(dst, last);
         gst<f32x4>(a.Cur + pe, f32x4{0.f, 0.f, 0.f, 0.f});
         n = nj - 1;
     }
@@ -412,17 +462,37 @@ __global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
         int j = 0;
         for (; j + U <= n; j += U) {
             f32x4 s[U];
+            [[maybe_unused]] long pg[U];
+            if constexpr (PAGED) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) s[u] = gld<f32x4>(Sb + (long)(j + u) * a.E);
+                for (int u = 0; u < U; ++u) pg[u] = cst_page(trow, a.n_pages, j + u);
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    s[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (pg[u] >= 0) s[u] = gld<f32x4>(a.S + pg[u] * a.H * a.E + he);
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) s[u] = gld<f32x4>(Sb + (long)(j + u) * a.E);
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
+                if (PAGED && pg[u] < 0) continue;
                 const float w = mixrow[j + u];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) acc[t] = fmaf(w, s[u][t], acc[t]);
             }
         }
         for (; j < n; ++j) {
-            const f32x4 s = gld<f32x4>(Sb + (long)j * a.E);
+            const float* src;
+            if constexpr (PAGED) {
+                const long pg = cst_page(trow, a.n_pages, j);
+                if (pg < 0) continue;
+                src = a.S + pg * a.H * a.E + he;
+            } else {
+                src = Sb + (long)j * a.E;
+            }
+            const f32x4 s = gld<f32x4>(src);
             const float w = mixrow[j];
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[t] = fmaf(w, s[t], acc[t]);

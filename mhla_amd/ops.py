@@ -7,6 +7,7 @@ a ROCm device and the library must be built, otherwise these functions raise.
 from __future__ import annotations
 
 import functools
+import heapq
 import os
 import warnings
 from typing import NamedTuple, Optional
@@ -1378,6 +1379,7 @@ class CausalState:
     `[B, T, H, K]` with k, v `[B, T, Hkv, .]` and a state of Hkv heads, H = G Hkv, G <= 8."""
 
     __slots__ = ("S", "P", "Cur", "seen", "chunk_size", "lengths", "pos", "stale", "_full")
+    pages = None   # (a paged pool and its views hold the finished chunks as pages instead of S: `PagedCausalState`)
 
     def __init__(self, S: torch.Tensor, P: torch.Tensor, Cur: torch.Tensor, seen: int = 0, chunk_size: int = 64, *, lengths=None,
                  pos: Optional[torch.Tensor] = None):
@@ -1401,6 +1403,22 @@ class CausalState:
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
         return cls(z(B, H, capacity_chunks, K, V), z(B, H, K, V), z(B, H, K, V), 0, chunk_size)
 
+    # what the checks and launches read of a state's geometry, so that a pool whose finished chunks are pages (`PagedCausalState`),
+    # which has no dense S, answers them too
+    @property
+    def dims(self):
+        """(batch rows, k/v heads, capacity in chunks, K, V)."""
+        return tuple(self.S.shape)
+
+    @property
+    def device(self):
+        return self.S.device
+
+    @property
+    def _chunks(self) -> torch.Tensor:
+        """The tensor that holds the finished chunks: S, or the pages of a paged pool."""
+        return self.S
+
     @property
     def capacity_chunks(self) -> int:
         return self.S.shape[2]
@@ -1414,7 +1432,7 @@ class CausalState:
         """int32 [B] zeros on the state's device, created on first use: a device-positioned step sets `full[b] = 1` when it finds
         sequence b beyond the capacity (and leaves that sequence as it is); nothing but the caller clears it."""
         if self._full is None:
-            self._full = torch.zeros(self.S.shape[0], dtype=torch.int32, device=self.S.device)
+            self._full = torch.zeros(self.dims[0], dtype=torch.int32, device=self.device)
         return self._full
 
     def to_ragged(self) -> "CausalState":
@@ -1437,9 +1455,12 @@ class CausalState:
         self.lengths, self.seen, self.stale = tuple(int(n) for n in pos), max(int(n) for n in pos), False
         over = [b for b, f in enumerate(full) if f]
         if over:
-            raise IndexError(f"CausalState.sync: sequences {over} were stepped beyond the capacity of {self.capacity_chunks} chunks "
-                             f"({64 * self.capacity_chunks} tokens): their rows from there on are zeros (lengths={self.lengths})")
+            raise IndexError(f"{type(self).__name__}.sync: sequences {over} were stepped beyond the capacity of {self.capacity_chunks} chunks "
+                             f"({64 * self.capacity_chunks} tokens){self._sync_cause}: their rows from there on are zeros "
+                             f"(lengths={self.lengths})")
         return self
+
+    _sync_cause = ""   # (what else sets a `full` flag: a paged pool names a chunk without a page)
 
     def _refuse_stale(self, fn: str):
         if self.stale:
@@ -1462,6 +1483,8 @@ class CausalState:
         states = list(states)
         if not states or not all(isinstance(s, CausalState) for s in states):
             raise ValueError("CausalState.cat: a non-empty sequence of CausalState")
+        for s in states:
+            _refuse_paged_pool("CausalState.cat", s)
         states = [s.compact() if isinstance(s, CausalStateView) else s for s in states]   # (a view: copies of its slots)
         a = states[0]
         for s in states[1:]:
@@ -1492,7 +1515,7 @@ class CausalState:
         if self.lengths is None:
             raise ValueError(f"{fn}: the state is uniform ({self!r}): a pool of slots is a ragged state, call to_ragged() first")
         self._refuse_stale(fn)
-        return _slot_tuple(fn, slots, self.S.shape[0])
+        return _slot_tuple(fn, slots, self.dims[0])
 
     def _set_lengths(self, slots, values):
         lengths = list(self.lengths)
@@ -1561,10 +1584,10 @@ class CausalStateView(CausalState):
     graph: an entry outside 0 .. n_slots - 1, -1 for instance, makes that row INACTIVE -- its row of the result is zeros and no slot,
     position or flag is touched; entries that name a slot must be distinct (rows that share one race).  The step marks the POOL
     stale, and `pool.sync()` refreshes it.
-    Not covered: `DecodeCache`, the fla layer and `hosts/gpt.py` build their states as before; a slot still reserves all
-    `capacity_chunks` chunks (no paging within a slot)."""
+    Not covered: `DecodeCache`, the fla layer and `hosts/gpt.py` build their states as before; a slot of a dense pool reserves all
+    `capacity_chunks` chunks (`PagedCausalState`: a pool whose finished chunks are pages)."""
 
-    __slots__ = ("pool", "slots", "_map", "_mirror")
+    __slots__ = ("pool", "slots", "_map", "_mirror", "dims", "pages")
 
     def __init__(self, pool: CausalState, slots):
         self._mirror = (None, None)   # (the pool's lengths tuple the view's were last taken from, the view's lengths)
@@ -1573,16 +1596,19 @@ class CausalStateView(CausalState):
             raise ValueError(f"{fn}: a view of a view; take the slots from the pool")
         if pool.lengths is None:
             raise ValueError(f"{fn}: the state is uniform ({pool!r}): a pool of slots is a ragged state, call to_ragged() first")
-        self.pool = pool
+        self.pool, self.dims, self.pages = pool, pool.dims, pool.pages   # (neither changes while the pool lives: kept, not looked up per call)
         if isinstance(slots, torch.Tensor):
-            if slots.dtype != torch.int32 or slots.dim() != 1 or slots.shape[0] < 1 or slots.device != pool.S.device or not slots.is_contiguous():
-                raise ValueError(f"{fn}: a slot map on the device is a contiguous int32 [B >= 1] tensor on {pool.S.device}, got "
+            if slots.dtype != torch.int32 or slots.dim() != 1 or slots.shape[0] < 1 or slots.device != pool.device or not slots.is_contiguous():
+                raise ValueError(f"{fn}: a slot map on the device is a contiguous int32 [B >= 1] tensor on {pool.device}, got "
                                  f"{slots.dtype} {tuple(slots.shape)} on {slots.device}")
             self.slots, self._map = None, slots
         else:
-            self.slots, self._map = _slot_tuple(fn, slots, pool.S.shape[0]), None
+            self.slots, self._map = _slot_tuple(fn, slots, pool.dims[0]), None
 
     S = property(lambda self: self.pool.S)
+    capacity_chunks = property(lambda self: self.dims[2])
+    device = property(lambda self: self.pool.device)
+    _chunks = property(lambda self: self.pool._chunks)
     P = property(lambda self: self.pool.P)
     Cur = property(lambda self: self.pool.Cur)
     pos = property(lambda self: self.pool.pos)
@@ -1599,7 +1625,7 @@ class CausalStateView(CausalState):
     def map(self) -> torch.Tensor:
         """int32 [B] on the pool's device: slot of every row -- the caller's tensor, or the copy of the list made on first use."""
         if self._map is None:
-            self._map = torch.tensor(self.slots, dtype=torch.int32).to(self.pool.S.device)
+            self._map = torch.tensor(self.slots, dtype=torch.int32).to(self.pool.device)
         return self._map
 
     @property
@@ -1669,15 +1695,305 @@ class CausalStateView(CausalState):
 class _SlotPart:
     """Rows [i, j) of a view, as a launch takes them: the pool's tensors and that piece of the map."""
 
-    __slots__ = ("S", "P", "Cur", "chunk_size", "map")
+    __slots__ = ("S", "P", "Cur", "chunk_size", "map", "dims")
+    pages = None
 
     def __init__(self, pool, map_):
-        self.S, self.P, self.Cur, self.chunk_size, self.map = pool.S, pool.P, pool.Cur, pool.chunk_size, map_
+        self.S, self.P, self.Cur, self.chunk_size, self.map, self.dims = pool.S, pool.P, pool.Cur, pool.chunk_size, map_, pool.dims
 
 
 def _state_rows(state) -> int:
     """The sequences a call on `state` has: its batch rows, or the rows a view selects."""
     return state.rows if isinstance(state, CausalStateView) else state.S.shape[0]
+
+
+class PoolExhausted(RuntimeError):
+    """A call on a `PagedCausalState` needs more pages than the pool has free.  Raised before anything is changed."""
+
+
+def _page_table(fn, table, n_slots, n_pages):
+    """`table` as n_slots lists of equally many ints in -1 .. n_pages - 1 (-1: no page); ValueError naming the offenders otherwise."""
+    rows = [list(r) for r in (table.tolist() if isinstance(table, torch.Tensor) else table)]
+    if len(rows) != n_slots:
+        raise ValueError(f"{fn}: the table has {len(rows)} rows, the pool {n_slots} slots (one row of capacity_chunks entries per slot)")
+    cap = len(rows[0])
+    ragged = [s for s, r in enumerate(rows) if len(r) != cap]
+    if cap < 1 or ragged:
+        raise ValueError(f"{fn}: table rows {ragged or [0]} do not have the {cap} entries of row 0 (capacity_chunks >= 1 entries per slot)")
+    bad = sorted({repr(p) for r in rows for p in r if isinstance(p, bool) or not isinstance(p, int)})
+    if bad:
+        raise ValueError(f"{fn}: table entries must be ints, got [{', '.join(bad)}]")
+    out = sorted({p for r in rows for p in r if not -1 <= p < n_pages})
+    if out:
+        raise ValueError(f"{fn}: table entries {out} are outside -1 .. {n_pages - 1} (the pool has {n_pages} pages, -1 is no page)")
+    dup = sorted({p for r in rows for p in r if p >= 0 and r.count(p) > 1})
+    if dup:
+        raise ValueError(f"{fn}: pages {dup} are named more than once within one slot (two chunks of a sequence never share a page)")
+    return rows
+
+
+class PagedCausalState(CausalState):
+    """A pool of decode slots whose FINISHED CHUNKS ARE PAGES: `pages [n_pages, Hkv, K, V]` (fp32; one page holds K_j^T V_j of one chunk
+    of one sequence, all k/v heads) and, per slot, a page table of `capacity_chunks` entries -- `table` on the host (lists of ints, -1:
+    no page) and `table_dev` (int32 [n_slots, capacity_chunks]) for the kernels.  `P`, `Cur` `[n_slots, Hkv, K, V]`, `pos`, `full`,
+    `lengths` and `stale` are those of a dense ragged pool (`CausalState`); there is no dense `S` (None).  A dense pool reserves
+    `capacity_chunks` chunks per slot whatever the requests' lengths; this one costs memory for the tokens it holds, and slots share
+    finished pages by reference count (`refs`), so that `fork` copies no chunk.  Always ragged.
+    Calls go through `pool.at(slots)`, a `PagedStateView`, which every call that takes a `CausalStateView` takes (the library's
+    `*_paged` entry points); each gives bit for bit what the un-slotted call gives on `view.compact()`.  The pool itself is refused
+    where a state is expected.
+    Page rule: before its launch a host-positioned call (step, extend, verify, commit, pack prefill `into=`) gives a page to every
+    chunk that holds a token of the slot afterwards, chunks 0 .. ceil(n_after / 64) - 1, lowest free page first.  All or nothing:
+    `PoolExhausted` before anything changes when the free list is too short.  Changed rows of the table go to `table_dev` with a
+    stream-ordered copy (no synchronisation).  `mhla_causal_step_dev` never assigns: `reserve(slots, tokens)` applies the rule ahead
+    of it, and a sequence that reaches a chunk without a page is frozen like one at the capacity (`full`, `sync()`).
+    Not covered: `DecodeCache`, the fla layer and `hosts/gpt.py` keep states of their own; pages are never evicted or swapped."""
+
+    __slots__ = ("pages", "table", "table_dev", "refs", "free", "have")
+    _sync_cause = " or onto a chunk that has no page (pool.reserve(slots, tokens) assigns them)"
+
+    def __init__(self, pages: torch.Tensor, P: torch.Tensor, Cur: torch.Tensor, table, *, lengths=None, chunk_size: int = 64):
+        fn = "PagedCausalState"
+        if pages.dim() != 4 or P.dim() != 4 or tuple(P.shape[1:]) != tuple(pages.shape[1:]) or P.shape != Cur.shape:
+            raise ValueError(f"{fn}: pages [n_pages, Hkv, K, V] and P, Cur [n_slots, Hkv, K, V], got {tuple(pages.shape)}, {tuple(P.shape)}, "
+                             f"{tuple(Cur.shape)}")
+        if any(t.dtype != torch.float32 or t.device != pages.device or not t.is_contiguous() for t in (pages, P, Cur)):
+            raise ValueError(f"{fn}: pages, P and Cur must be contiguous float32 tensors on one device")
+        n_slots, n_pages = P.shape[0], pages.shape[0]
+        if min(n_slots, n_pages) < 1:
+            raise ValueError(f"{fn}: n_slots={n_slots} and n_pages={n_pages} must be positive")
+        rows = _page_table(fn, table, n_slots, n_pages)
+        lengths = _int_tuple(fn, "lengths", (0,) * n_slots if lengths is None else lengths, n_slots, None)
+        over = [s for s, n in enumerate(lengths) if n > 64 * len(rows[0])]
+        if over:
+            raise IndexError(f"{fn}: slots {over} (lengths {lengths}) exceed the capacity of {len(rows[0])} chunks")
+        bare = {s: [j for j in range(-(-n // 64)) if rows[s][j] < 0] for s, n in enumerate(lengths)}
+        bare = {s: js for s, js in bare.items() if js}
+        if bare:
+            raise ValueError(f"{fn}: slots {sorted(bare)} hold tokens in chunks that have no page: {bare} (lengths {lengths})")
+        self.S, self.P, self.Cur, self.chunk_size, self.pages = None, P, Cur, int(chunk_size), pages
+        self.lengths, self.seen, self.stale, self._full = lengths, max(lengths), False, None
+        self.pos = torch.tensor(lengths, dtype=torch.int32, device=pages.device)
+        self.table = rows
+        self.refs = [0] * n_pages
+        for r in rows:
+            for p in r:
+                if p >= 0:
+                    self.refs[p] += 1
+        self.free = [p for p in range(n_pages) if not self.refs[p]]   # (a heap: the lowest free page goes first)
+        self.have = [self._leading(r) for r in rows]   # per slot: its leading chunks that have pages -- the page rule's quick test
+        self.table_dev = torch.tensor(rows, dtype=torch.int32, device=pages.device)
+
+    @classmethod
+    def empty(cls, n_slots: int, Hkv: int, K: int, V: int, capacity_chunks: int, n_pages: int, device="cuda") -> "PagedCausalState":
+        if min(n_slots, Hkv, K, V, capacity_chunks, n_pages) <= 0:
+            raise ValueError(f"PagedCausalState.empty: non-positive size n_slots={n_slots} Hkv={Hkv} K={K} V={V} "
+                             f"capacity_chunks={capacity_chunks} n_pages={n_pages}")
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
+        return cls(z(n_pages, Hkv, K, V), z(n_slots, Hkv, K, V), z(n_slots, Hkv, K, V), [[-1] * capacity_chunks for _ in range(n_slots)])
+
+    dims = property(lambda self: (self.P.shape[0], self.P.shape[1], len(self.table[0]), self.P.shape[2], self.P.shape[3]))
+    capacity_chunks = property(lambda self: len(self.table[0]))
+    device = property(lambda self: self.pages.device)
+    _chunks = property(lambda self: self.pages)
+
+    @property
+    def nbytes(self) -> int:
+        return 4 * sum(t.numel() for t in (self.pages, self.P, self.Cur, self.pos, self._full, self.table_dev) if t is not None)
+
+    @property
+    def pages_free(self) -> int:
+        return len(self.free)
+
+    @property
+    def pages_used(self) -> int:
+        return len(self.refs) - len(self.free)
+
+    def at(self, slots) -> "PagedStateView":
+        """The slots `slots` of the pool as a state of `len(slots)` sequences on the same storage: `CausalState.at`, paged."""
+        return PagedStateView(self, slots)
+
+    def to_ragged(self) -> "PagedCausalState":
+        return self
+
+    def clone(self):
+        raise ValueError("PagedCausalState.clone: a paged pool is not copied as a whole; pool.at(slots).compact() copies slots")
+
+    # ---- pages
+    def _release(self, page: int):
+        self.refs[page] -= 1
+        if not self.refs[page]:
+            heapq.heappush(self.free, page)
+
+    @staticmethod
+    def _leading(row) -> int:
+        return next((j for j, p in enumerate(row) if p < 0), len(row))
+
+    def _push(self, slots):
+        """Rows `slots` of the host table, which changed, to `table_dev`: one small stream-ordered copy per row, no synchronisation."""
+        for s in slots:
+            self.have[s] = self._leading(self.table[s])
+            self.table_dev[s].copy_(torch.tensor(self.table[s], dtype=torch.int32), non_blocking=True)
+
+    def _assign(self, fn: str, slots, n_after, fresh: bool = False):
+        """The page rule for the slots `slots`: a page for every chunk 0 .. ceil(n_after[b] / 64) - 1 of slot b that has none.  fresh
+        (a prefill): the slot starts anew, its pages are released first (a shared one stays with its other holders).  All or nothing."""
+        have = self.have
+        if not fresh and all(n <= 64 * have[s] for s, n in zip(slots, n_after)):   # (the usual call: every page is there)
+            return
+        cap = self.capacity_chunks
+        want = [min(cap, -(-int(n) // 64)) for n in n_after]
+        released = 0
+        if fresh:
+            gone = [p for s in slots for p in self.table[s] if p >= 0]
+            released = sum(1 for p in set(gone) if self.refs[p] == gone.count(p))
+            missing = {s: list(range(w)) for s, w in zip(slots, want) if w}
+        else:
+            missing = {s: [j for j in range(w) if self.table[s][j] < 0] for s, w in zip(slots, want)}
+            missing = {s: js for s, js in missing.items() if js}
+        need = sum(len(js) for js in missing.values())
+        if need > len(self.free) + released:
+            raise PoolExhausted(f"{fn}: slots {sorted(missing)} need {need} more pages, the pool has {len(self.free) + released} free "
+                                f"(of {len(self.refs)}; pool.trim / pool.reset release pages)")
+        changed = set(missing)
+        if fresh:
+            for s in slots:
+                for j, p in enumerate(self.table[s]):
+                    if p >= 0:
+                        self._release(p)
+                        self.table[s][j] = -1
+                        changed.add(s)
+        for s, js in missing.items():
+            for j in js:
+                p = heapq.heappop(self.free)
+                self.refs[p] = 1
+                self.table[s][j] = p
+        if changed:
+            self._push(sorted(changed))
+
+    def reserve(self, slots, tokens) -> "PagedCausalState":
+        """Pages for the first `tokens` tokens (an int, or one per slot) of every slot of `slots`, by the page rule -- what a caller of
+        `mhla_causal_step_dev`, which never assigns pages, does ahead of the steps.  It reads the table alone, not the positions, so a
+        stale pool is fine.  IndexError beyond the capacity; `PoolExhausted` before anything changes."""
+        fn = "PagedCausalState.reserve"
+        slots = _slot_tuple(fn, slots, self.dims[0])
+        tokens = _int_tuple(fn, "tokens", (tokens,) * len(slots) if isinstance(tokens, int) else tokens, len(slots), None)
+        over = [s for s, n in zip(slots, tokens) if n > 64 * self.capacity_chunks]
+        if over:
+            raise IndexError(f"{fn}: slots {over} would hold more than the capacity of {self.capacity_chunks} chunks "
+                             f"({64 * self.capacity_chunks} tokens)")
+        self._assign(fn, slots, tokens)
+        return self
+
+    def trim(self, slots) -> "PagedCausalState":
+        """Release the pages of every slot of `slots` beyond its ceil(length / 64) chunks, for instance after a commit that accepted less
+        than was verified."""
+        slots = self._pool_slots("PagedCausalState.trim", slots)
+        changed = []
+        for s in slots:
+            for j in range(-(-self.lengths[s] // 64), self.capacity_chunks):
+                if self.table[s][j] >= 0:
+                    self._release(self.table[s][j])
+                    self.table[s][j] = -1
+                    changed.append(s)
+        self._push(sorted(set(changed)))
+        return self
+
+    def reset(self, slots) -> "PagedCausalState":
+        """Empty the slots `slots` for new requests: every page they hold is released (a shared one stays with its other holders), P,
+        Cur, pos, full and the host mirror of those rows become zero."""
+        slots = self._pool_slots("PagedCausalState.reset", slots)
+        self._set_lengths(slots, (0,) * len(slots))
+        self.trim(slots)
+        idx = torch.tensor(slots, dtype=torch.int64).to(self.device)
+        for t in (self.P, self.Cur, self.pos, self._full):
+            if t is not None:
+                t[idx] = 0
+        return self
+
+    def fork(self, src: int, dst: int) -> "PagedCausalState":
+        """Slot `dst` becomes a copy of slot `src` (a shared prompt prefix, beams) without copying a chunk: `dst`'s pages are released,
+        then it SHARES `src`'s pages of finished chunks (`length // 64` of them, reference count + 1); P, Cur, pos, full and the host
+        mirror are copied.  A finished chunk is never written again, so both go on independently."""
+        src, dst = self._pool_slots("PagedCausalState.fork", (src, dst))
+        n = self.lengths[src]
+        self._set_lengths((dst,), (0,))
+        self.trim((dst,))
+        for j in range(n // 64):
+            p = self.table[src][j]
+            self.refs[p] += 1
+            self.table[dst][j] = p
+        self._push((dst,))
+        for t in (self.P, self.Cur, self.pos, self._full):
+            if t is not None:
+                t[dst] = t[src]
+        self._set_lengths((dst,), (n,))
+        return self
+
+    def __repr__(self):
+        n_slots, H, cap, K, V = self.dims
+        return (f"PagedCausalState(n_slots={n_slots}, H={H}, K={K}, V={V}, capacity_chunks={cap}, pages={self.pages_used}/{len(self.refs)} used, "
+                f"lengths={self.lengths}, device={self.device})")
+
+
+class PagedStateView(CausalStateView):
+    """`paged_pool.at(slots)`: a `CausalStateView` of a `PagedCausalState`.  Everything said there holds; the finished chunks are read
+    and written through the pool's page table (the library's `*_paged` entry points), and `compact()` gathers them into an ordinary
+    dense ragged `CausalState` -- what every call on the view is defined against, bit for bit.  There is no dense `S`."""
+
+    __slots__ = ()
+
+    @property
+    def S(self):
+        raise AttributeError("a view of a PagedCausalState has no dense S: pool.pages and pool.table hold the finished chunks, "
+                             "view.compact() gathers them")
+
+    table_dev = property(lambda self: self.pool.table_dev)
+
+    def compact(self) -> CausalState:
+        """A fresh dense ragged `CausalState` holding COPIES of the view's slots in call order, each chunk gathered from its page
+        (zeros where the table names none): plain tensor operations."""
+        self._host_slots("PagedStateView.compact")
+        pool = self.pool
+        idx = self.map.to(torch.int64)
+        tab = torch.tensor([pool.table[s] for s in self.slots], dtype=torch.int64).to(pool.device)   # [B, cap]
+        S = pool.pages[tab.clamp_min(0)]   # [B, cap, H, K, V]
+        S[tab < 0] = 0
+        out = CausalState(S.permute(0, 2, 1, 3, 4).contiguous(), pool.P[idx], pool.Cur[idx], 0, self.chunk_size, lengths=self.lengths,
+                          pos=pool.pos[idx])
+        if pool._full is not None:
+            out._full = pool._full[idx]
+        return out
+
+    clone = compact
+
+    def _part(self, i, j) -> "_PagePart":
+        return _PagePart(self.pool, self.map[i:j])
+
+    def __repr__(self):
+        return f"PagedStateView(slots={self.slots if self.slots is not None else 'on the device'}, B={self.rows}, of {self.pool!r})"
+
+
+class _PagePart:
+    """Rows [i, j) of a view of a paged pool, as a launch takes them: the pool's tensors and that piece of the map."""
+
+    __slots__ = ("pages", "table_dev", "P", "Cur", "chunk_size", "map", "dims")
+
+    def __init__(self, pool, map_):
+        self.pages, self.table_dev, self.P, self.Cur = pool.pages, pool.table_dev, pool.P, pool.Cur
+        self.chunk_size, self.map, self.dims = pool.chunk_size, map_, pool.dims
+
+
+def _refuse_paged_pool(fn, state):
+    if isinstance(state, PagedCausalState):
+        raise TypeError(f"{fn}: a PagedCausalState is a pool, not a state: pass pool.at(slots), the view of the slots the call works on")
+
+
+def _assign_pages(fn, state, n_after, fresh=False):
+    """The page rule of a host-positioned call on a view of a paged pool (`PagedCausalState`): after every refusal, before the first
+    launch.  Any other state (`state.pages is None`, which the callers on a hot path test themselves): nothing."""
+    if state.pages is not None:
+        state.pool._assign(fn, state.slots, n_after, fresh)
 
 
 def _int_tuple(fn, name, xs, B, hi):
@@ -1739,7 +2055,16 @@ def _run_slices(state: CausalState, lengths, nb):
 def _state_head(mixf, state: CausalState):
     """The arguments every decode entry point of the library takes after its token views: the mixing matrix with its leading
     dimension, then S with the capacity, P, Cur."""
+    pages = state.pages
+    if pages is not None:   # a view of a paged pool, or a batch slice of one: (pages, n_pages, table_dev) where S stands
+        return (mixf.data_ptr(), mixf.shape[1], pages.data_ptr(), pages.shape[0], state.table_dev.data_ptr(), state.dims[2], state.P.data_ptr(),
+                state.Cur.data_ptr())
     return mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.S.shape[2], state.P.data_ptr(), state.Cur.data_ptr()
+
+
+def _pool_call(name: str, state) -> str:
+    """The entry point that runs the slotted call `name` (mhla_causal_*_slots) on `state`: itself, or its paged namesake."""
+    return name if state.pages is None else name[:-len("_slots")] + "_paged"
 
 
 @functools.lru_cache(maxsize=64)
@@ -1837,7 +2162,7 @@ def _causal_state_pack_args(fn, k, v, mixing_matrix, cu_seqlens, lengths, left_p
         if n_seqs != into.rows:
             raise ValueError(f"{fn}: the pack holds {n_seqs} sequences, the view selects {into.rows} slots {into.slots}")
         capacity_chunks = into.capacity_chunks
-        if tuple(into.S.shape[1:]) != (H, capacity_chunks, K, v.shape[-1]) or into.S.device != k.device:
+        if into.dims[1:] != (H, capacity_chunks, K, v.shape[-1]) or into.device != k.device:
             raise ValueError(f"{fn}: into is {into!r}, the pack has H={H} K={K} V={v.shape[-1]} on {k.device}")
     cap = L if capacity_chunks is None else int(capacity_chunks)
     if not 0 < cap <= L:
@@ -1866,7 +2191,7 @@ def _causal_state_init_pack(k, v, mix, state: CausalState, plan: CausalVarlenPla
     mixf = _mix2d(mix)
     slot = getattr(state, "map", None)
     name, where = (("mhla_causal_varlen_state_init", ()) if slot is None else
-                   ("mhla_causal_varlen_state_init_slots", (slot.data_ptr(), state.S.shape[0])))
+                   (_pool_call("mhla_causal_varlen_state_init_slots", state), (slot.data_ptr(), state.dims[0])))
     rc = getattr(lib, name)(_view(k), _view(v), *_state_head(mixf, state), len(plan.lengths), seq_len.data_ptr(), *where,
                             max(plan.lengths), T, H, K, v.shape[-1], state.chunk_size, plan.n_chunks,
                             plan.table.data_ptr(), plan.dst.data_ptr(), _dtype_code(k), _stream())
@@ -1901,6 +2226,7 @@ def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Ten
             with torch.no_grad():
                 seq_len = torch.tensor(plan.lengths, dtype=torch.int32).to(k.device)   # the one small copy of the call
                 idx = into.map.to(torch.int64)
+                _assign_pages("mhla_causal_state", into, plan.lengths, fresh=True)   # (a paged pool: before anything changes)
                 if T:
                     _causal_state_init_pack(k.detach(), v.detach(), mixing_matrix, into, plan, seq_len)
                 else:   # (an all-empty pack launches nothing: empty slots)
@@ -1983,6 +2309,8 @@ def _decode_entry(fn, state, q, k, v, one_token, refuse_stale):
     `mhla_causal_step_dev`, which never reads it), the tensors' rank, the token count."""
     if not isinstance(state, CausalState):
         raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
+    if isinstance(state, PagedCausalState):
+        _refuse_paged_pool(fn, state)
     if refuse_stale and isinstance(state, CausalStateView):   # (a slot map on the device: the device-positioned step alone)
         state._host_slots(fn)
     if refuse_stale and state.stale:
@@ -2018,12 +2346,13 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
         raise ValueError(str(e)) from None
     if q.dtype not in _DTYPES:
         raise ValueError(f"{fn}: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
-    nrow = state.S.shape[0]   # the state's batch rows: B, or -- a view -- the slots of the pool, B of which the call selects
-    if _state_rows(state) != B or tuple(state.S.shape) != (nrow, Hk, cap, K, V) or tuple(state.P.shape) != (nrow, Hk, K, V) or tuple(state.Cur.shape) != (nrow, Hk, K, V):
+    dims, chunks = state.dims, state._chunks
+    nrow = dims[0]   # the state's batch rows: B, or -- a view -- the slots of the pool, B of which the call selects
+    if _state_rows(state) != B or dims != (nrow, Hk, cap, K, V) or tuple(state.P.shape) != (nrow, Hk, K, V) or tuple(state.Cur.shape) != (nrow, Hk, K, V):
         raise ValueError(f"{fn}: state is {state!r}, the {'token has' if T == 1 else 'tokens have'} B={B} H={H if Hk == H else Hk} K={K} V={V}"
                          + ("" if Hk == H else f" (k/v heads; q has {H})"))
     dev = q.device
-    for name, t in (("state.S", state.S), ("state.P", state.P), ("state.Cur", state.Cur), ("mixing_matrix", mixing_matrix), ("norm_weight", norm_weight)):
+    for name, t in (("state.S", chunks), ("state.P", state.P), ("state.Cur", state.Cur), ("mixing_matrix", mixing_matrix), ("norm_weight", norm_weight)):
         if t is not None and t.device != dev:
             raise ValueError(f"{fn}: {name} is on {t.device}, expected {dev}")
     if norm_weight is not None and norm_weight.numel() != V:
@@ -2049,7 +2378,7 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
     want_y = bool(epilogue) if epilogue is not None else (gate is not None or norm_weight is not None)
     if not want_y and (gate is not None or norm_weight is not None):
         raise ValueError(f"{fn}: gate / norm_weight given with epilogue=False")
-    if not (state.S.is_contiguous() and state.P.is_contiguous() and state.Cur.is_contiguous()):
+    if not (chunks.is_contiguous() and state.P.is_contiguous() and state.Cur.is_contiguous()):
         raise ValueError(f"{fn}: state tensors must be contiguous")
     # (a view whose slot map is on the device has no host lengths; its positions are the pool's all the same)
     if (state.lengths is not None or isinstance(state, CausalStateView)) and (
@@ -2083,8 +2412,8 @@ def _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, name, twin, state, mi
     call, heads = _gqa_call(lib, name, H, k.shape[2]) if twin else (getattr(lib, name), (H,))
     slot = getattr(state, "map", None)
     if slot is not None:   # a view of a pool, or a batch slice of one: the slotted namesake -- the map after the positions, Hkv after H
-        name = _SLOT_CALLS[name]
-        call, heads, middle = getattr(lib, name), (H, k.shape[2]), (middle[0], slot.data_ptr(), state.S.shape[0], *middle[1:])
+        name = _pool_call(_SLOT_CALLS[name], state)
+        call, heads, middle = getattr(lib, name), (H, k.shape[2]), (middle[0], slot.data_ptr(), state.dims[0], *middle[1:])
     ws = _ws(ws_bytes, q.device)
     # (the two optional arguments spelt out, not through `_view_or_null` / `_ptr`: two Python calls on a host-bound path)
     rc = call(_view(q), _view(k), _view(v), *_state_head(mixf, state), *middle, NULL_VIEW if want_y else _view(res),
@@ -2156,6 +2485,8 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
         if cols < need:
             raise IndexError(f"mhla_causal_step: a sequence of lengths {part} closes its chunk: row {need - 1} of mixing_matrix is read, "
                              f"which has only {cols} columns")
+    if state.pages is not None:
+        _assign_pages("mhla_causal_step", state, [n + 1 for n in lengths])
     for part, p, pos_, lengths_, out in _batch_slices(state, nb, prepared, pos, lengths, res):
         _causal_step_ragged(*p, part, pos_, lengths_, out, norm_eps)
     if state.lengths is not None:
@@ -2363,6 +2694,8 @@ def _extend_counts(fn, prepared, state, counts, left_padded, res, norm_eps):
                 _extend_run(prepared, part, res, norm_eps, b, b + 1, p, t_lo, t_lo + n, step_t)
         state.pos += torch.tensor(counts, dtype=torch.int32).to(state.pos.device, non_blocking=False)
     else:
+        if state.pages is not None:
+            _assign_pages(fn, state, [p + n for p, n in zip(state.lengths, counts)])
         _ragged_chains("mhla_causal_extend_ragged", prepared, state, slices, counts, left_padded, res, norm_eps)
     state.lengths = tuple(p + n for p, n in zip(state.lengths, counts))
     state.seen = max(state.lengths)
@@ -2481,6 +2814,8 @@ def mhla_causal_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     if need > EXTEND_WS_CAP_BYTES:
         raise ValueError(f"{fn}: a draft of T={T} tokens for {B} sequences needs a workspace of {need} bytes, more than "
                          f"EXTEND_WS_CAP_BYTES={EXTEND_WS_CAP_BYTES}: verify fewer tokens or sequences per call")
+    if state.pages is not None:
+        _assign_pages(fn, state, [p + n for p, n in zip(state.lengths, counts)])   # (the draft's end)
     res = q.new_empty((B, T, H, V))
     _ragged_chains("mhla_causal_verify_ragged", prepared, state, slices, counts, left_padded, res, norm_eps)
     return res, draft
@@ -2498,7 +2833,8 @@ def _causal_commit_ragged(k, v, mixf, state, pos, ntok, acc, plan, left_padded):
     max_end, max_later, any_close, _ = plan
     ws = _ws(lib.mhla_causal_commit_ragged_ws_bytes(B, dt), k.device)
     slot = getattr(state, "map", None)   # (a view of a pool, or a batch slice of one: the slotted namesake)
-    name, where = ("mhla_causal_commit_ragged", ()) if slot is None else ("mhla_causal_commit_slots", (slot.data_ptr(), state.S.shape[0]))
+    name, where = (("mhla_causal_commit_ragged", ()) if slot is None else
+                   (_pool_call("mhla_causal_commit_slots", state), (slot.data_ptr(), state.dims[0])))
     rc = getattr(lib, name)(_view(k), _view(v), *_state_head(mixf, state), pos.data_ptr(), *where, ntok.data_ptr(), acc.data_ptr(), T,
                             max_end, max_later, int(any_close), int(bool(left_padded)), ws.data_ptr(), ws.numel() * 4, B, H, K, V,
                             state.chunk_size, dt, _stream())
@@ -2518,6 +2854,7 @@ def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: C
         raise TypeError(f"{fn}: draft must be a CausalDraft (what mhla_causal_verify returns), got {type(draft).__name__}")
     if not isinstance(state, CausalState):
         raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
+    _refuse_paged_pool(fn, state)
     if isinstance(state, CausalStateView):
         state._host_slots(fn)
     state._refuse_stale(fn)
@@ -2535,7 +2872,7 @@ def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: C
         return state
     k, v = draft.k, draft.v
     _, T, H, K = k.shape
-    if _state_rows(state) != B or tuple(state.S.shape[1:]) != (H, state.capacity_chunks, K, v.shape[-1]) or state.S.device != k.device:
+    if _state_rows(state) != B or state.dims[1:] != (H, state.capacity_chunks, K, v.shape[-1]) or state.device != k.device:
         raise ValueError(f"{fn}: state is {state!r}, the draft has B={B} H={H} K={K} V={v.shape[-1]} on {k.device}")
     if mixing_matrix.dim() < 2 or mixing_matrix.device != k.device:
         raise ValueError(f"{fn}: mixing_matrix must be [L, L(, 1, 1, 1, 1)] on {k.device}, got {tuple(mixing_matrix.shape)} on "
@@ -2547,6 +2884,8 @@ def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: C
         raise IndexError(f"{fn}: mixing_matrix has only {mixf.shape[0]} rows, fewer than the accepted tokens read (lengths "
                          f"{state.lengths}, accept {accept})")
     dev = k.device
+    if state.pages is not None:
+        _assign_pages(fn, state, [p + a for p, a in zip(state.lengths, accept)])
     both = torch.tensor((draft.counts, accept), dtype=torch.int32).to(dev)   # the one small copy of the call
     ntok, acc = both[0], both[1]
     for (_, _, plan), (part, _, k_, v_, pos, ntok_, acc_) in zip(slices, _batch_slices(state, slices[0][1], None, k, v, state.pos, ntok, acc)):

@@ -86,6 +86,16 @@ device time of the library's kernels, each with median, min and max.  Positions 
 every variant, so that every call is the same step.  On a tree without `CausalState.at` the same command times (a) alone: the
 figure to hold the un-slotted path of a later tree against.
 
+`--paged`: the step on a PAGED pool (`PagedCausalState`) beside the dense pool and the compact state, at the shape, batches and lengths of
+`--slots`, and at two places: "off" (the lengths of `--slots`, no sequence on a boundary) and "boundary" (every sequence at
+pos % 64 == 63, the one case in which a step reads S through the page table: its roll closes the chunk and mixes the finished ones).
+Variants, alternating in one run, `--reps` times, `--steps` calls each: (a) `compact_*`, the un-slotted step and device-positioned step
+on a compact state of B rows, (b) `view_*`, the same through a permuted view of a dense pool of 2 B slots, (c) `paged_*`, through the
+same view of a paged pool whose table is a random permutation of its pages (every page the steps touch assigned beforehand).  Wall and
+device time per call (median, min, max), the kernels' device times, and the bytes of the dense and the paged pool.  Positions and host
+mirror are put back before every call.  On a tree without `PagedCausalState` the same command times (a) and (b): the figures to hold
+the un-paged paths of a later tree against.
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -475,6 +485,79 @@ def slots_config(B, H, K, V, steps, reps):
     return rec
 
 
+def paged_config(B, H, K, V, steps, reps):
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    q, k, v = token(B, H, K, V, g)
+    i0 = 15
+    chunks = [i0 + (-2, -1, 1, 2)[b % 4] for b in range(B)]
+    places = {"off": tuple(c * 64 + (7 * b) % 63 for b, c in enumerate(chunks)), "boundary": tuple(c * 64 + 63 for c in chunks)}
+    n_slots = 2 * B
+    slots = torch.randperm(n_slots, generator=g)[:B].tolist()
+    idx = torch.tensor(slots, dtype=torch.int64, device=DEV)
+    held = i0 + 4   # chunks a slot holds pages for: every one a step here reads or closes, and the one it opens
+
+    def spread_over_pool(lens):
+        out = [0] * n_slots
+        for s_, n in zip(slots, lens):
+            out[s_] = n
+        return tuple(out)
+
+    def dense(rows):
+        st = mhla_amd.CausalState.empty(rows, H, K, V, L, DEV)
+        st.S[:, :, :held].normal_(0, 0.1)
+        st.P.normal_(0, 0.1)
+        st = mhla_amd.CausalState(st.S, st.P, st.Cur, lengths=(0,) * rows)
+        st.full
+        return st
+
+    rag, pool = dense(B), dense(n_slots)
+    states = {"compact": (rag, rag, rag, lambda lens: lens), "view": (pool, pool.at(slots), pool.at(idx.to(torch.int32)), spread_over_pool)}
+    nbytes = {"dense_pool_MB": round(pool.nbytes / 2 ** 20, 1)}
+    if hasattr(mhla_amd, "PagedCausalState"):
+        n_pages = n_slots * held
+        perm = torch.randperm(n_pages, generator=g).tolist()
+        table = [perm[s_ * held:(s_ + 1) * held] + [-1] * (L - held) for s_ in range(n_slots)]
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=DEV)
+        paged = mhla_amd.PagedCausalState(z(n_pages, H, K, V).normal_(0, 0.1), z(n_slots, H, K, V).normal_(0, 0.1), z(n_slots, H, K, V), table)
+        paged.full
+        states["paged"] = (paged, paged.at(slots), paged.at(idx.to(torch.int32)), spread_over_pool)
+        nbytes["paged_pool_MB"] = round(paged.nbytes / 2 ** 20, 1)
+    fns = {}
+    for place, lens in places.items():
+        for name, (st, host_view, dev_view, over) in states.items():
+            lens_ = over(lens)
+            pos0 = torch.tensor(lens_, dtype=torch.int32, device=DEV)
+
+            def step(st=st, view=host_view, lens_=lens_, pos0=pos0):
+                st.lengths, st.seen, st.stale = lens_, max(lens_), False
+                st.pos.copy_(pos0)
+                mhla_amd.mhla_causal_step(q, k, v, mix, view)
+
+            def dev(st=st, view=dev_view, lens_=lens_, pos0=pos0):
+                st.lengths, st.seen, st.stale = lens_, max(lens_), False
+                st.pos.copy_(pos0)
+                mhla_amd.mhla_causal_step_dev(q, k, v, mix, view)
+
+            fns[f"{name}_step@{place}"], fns[f"{name}_dev@{place}"] = step, dev
+    wall, devt, kern = {n: [] for n in fns}, {n: [] for n in fns}, {}
+    with torch.no_grad():
+        for _ in range(reps):
+            for n, fn in fns.items():
+                wall[n].append(batch_us(fn, steps))
+            for n, fn in fns.items():
+                kern[n] = kernel_times(fn, iters=20)
+                devt[n].append(sum(kern[n].values()))
+            for st, *_ in states.values():
+                st.Cur.zero_()
+    rec = {"paged": {"B": B, "H": H, "K": K, "V": V, "n_slots": n_slots, "slots": slots, "chunks": sorted(set(chunks)), "pages_per_slot": held},
+           "steps_per_batch": steps, "reps": reps, **nbytes, "wall_us": {n: spread(x) for n, x in wall.items()},
+           "device_us": {n: spread(x) for n, x in devt.items()},
+           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()}}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def launch_counts(fn):
     """{kernel: launches} of one call of `fn` (the library's per-launch hook)."""
     import ctypes
@@ -836,8 +919,12 @@ if __name__ == "__main__":
     ap.add_argument("--gqa", action="store_true")
     ap.add_argument("--gqa-prefill", action="store_true")
     ap.add_argument("--slots", action="store_true")
+    ap.add_argument("--paged", action="store_true")
     a = ap.parse_args()
-    if a.slots:
+    if a.paged:
+        for B in (8, 32):
+            paged_config(B, 4, 128, 256, max(200, a.steps), a.reps)
+    elif a.slots:
         for B in (8, 32):
             slots_config(B, 4, 128, 256, max(200, a.steps), a.reps)
     elif a.gqa_prefill:
