@@ -683,6 +683,45 @@ int mhla_causal_varlen_state_init_paged(mhla_view k, mhla_view v, const float* m
                                         const int32_t* slot_dev, int n_slots, int max_len, int T, int H, int K, int V, int chunk, int n_chunks,
                                         const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, int dtype, void* stream);
 
+/* h16 pages: the paged step, device-positioned step and pack prefill on a pool whose pages take 2 bytes an element (added without a
+ * change of any existing signature or behaviour: MHLA_ABI_VERSION stays 9).  A page is a payload, `pages_h16` _Float16
+ * [n_pages][Hkv][K][V], 16-byte aligned, and apart from it multipliers, `page_mult` float [n_pages][Hkv][K V / 64], 4-byte aligned:
+ * group g of a head is elements [64 g, 64 g + 64) of the head's flattened [K][V] chunk, its multiplier m the power of two
+ * 2^(floor(log2 max|x|) - 14) (exponent field clamped to 1 .. 240; the largest magnitude of the group by its bit pattern), its
+ * payload (_Float16)(x / m) rounded to nearest even; an element decodes as (float)payload * m, exact in fp32: 11 significand bits
+ * relative to the group's largest element, the precision of the forward's default chunk summaries.  Requires K V % 64 == 0.
+ * P, Cur, pos_dev, full_dev, the slot map and the table are those of the fp32 paged calls.  The contract:
+ *   pages    Cur of an open chunk depends on no page, so a chunk finishes with the fp32 values of the fp32 pool, bit for bit, and
+ *            the page written is the encoding of exactly those values.  A finished chunk is written, and so rounded, once.
+ *   readers  every prefix mix is the sum of the fp32 calls -- ascending j, fmaf -- over DECODED pages, the chunk a boundary just
+ *            committed included: P is a function of the pages alone, and a slot filled by the pack prefill holds the bits (payload,
+ *            multipliers, P, Cur) of one that reached the same tokens step by step.
+ *   no page  an entry outside 0 .. n_pages - 1 forms no address, of the multipliers as of the payload; pages, multipliers and slots
+ *            a call does not name keep every bit.
+ * Each call is its *_paged namesake with `float* pages` replaced by (pages_h16, page_mult).  The pack prefill stages the chunks'
+ * fp32 K^T V in a workspace before it encodes them: mhla_causal_varlen_state_init_paged_h16_ws_bytes gives the size that takes the
+ * whole pack in one pass (4 n_chunks H K V); any 16-byte aligned workspace that holds one chunk (4 H K V bytes) will do, the call
+ * then works through the chunk list in slices (MHLA_EINVAL below that).  Extend, verify and commit have no h16 form.
+ * Checks, before any launch: pages_h16 and page_mult non-null, 16-byte and 4-byte aligned, K V % 64 == 0 (MHLA_EINVAL); then those
+ * of the namesake. */
+int mhla_causal_step_paged_h16(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, void* pages_h16, float* page_mult, int n_pages,
+                               const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev,
+                               int n_slots, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate, const float* norm_w,
+                               float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk,
+                               float scale, int dtype, void* stream);
+int mhla_causal_step_dev_paged_h16(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, void* pages_h16, float* page_mult,
+                                   int n_pages, const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev,
+                                   const int32_t* slot_dev, int n_slots, int32_t* full_dev, const void* rope_cos, const void* rope_sin,
+                                   int64_t ld_tab, int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate, const float* norm_w,
+                                   float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk,
+                                   float scale, int dtype, void* stream);
+size_t mhla_causal_varlen_state_init_paged_h16_ws_bytes(int n_chunks, int H, int K, int V, int dtype);
+int mhla_causal_varlen_state_init_paged_h16(mhla_view k, mhla_view v, const float* mix, int ldmix, void* pages_h16, float* page_mult, int n_pages,
+                                            const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int n_seqs,
+                                            const int32_t* seq_len_dev, const int32_t* slot_dev, int n_slots, int max_len, int T, int H, int K,
+                                            int V, int chunk, int n_chunks, const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, void* ws,
+                                            size_t ws_bytes, int dtype, void* stream);
+
 /* ---- prologue: q / k of the Wan host -------------------------------------- */
 
 /*

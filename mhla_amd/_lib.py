@@ -184,6 +184,16 @@ for _name in ("step", "step_dev", "extend", "verify", "commit", "varlen_state_in
     _res, _args = SIGNATURES[f"mhla_causal_{_name}_slots"]
     _at = _args.index(c_int) + 1   # (ldmix is the first int of every one of them)
     SIGNATURES[f"mhla_causal_{_name}_paged"] = (_res, _args[:_at] + [c_void_p, c_int, c_void_p] + _args[_at + 1:])
+# h16 pages: the paged step, step_dev and pack prefill with `float* pages` replaced by (pages_h16, page_mult); the prefill takes a
+# workspace (ws, ws_bytes) ahead of dtype
+for _name in ("step", "step_dev", "varlen_state_init"):
+    _res, _args = SIGNATURES[f"mhla_causal_{_name}_paged"]
+    _at = _args.index(c_int) + 1
+    _args = _args[:_at] + [c_void_p, c_void_p] + _args[_at + 1:]
+    if _name == "varlen_state_init":
+        _args = _args[:-2] + [c_void_p, c_size_t] + _args[-2:]
+    SIGNATURES[f"mhla_causal_{_name}_paged_h16"] = (_res, _args)
+SIGNATURES["mhla_causal_varlen_state_init_paged_h16_ws_bytes"] = (c_size_t, [c_int] * 5)
 
 _lib = None
 

@@ -1,5 +1,5 @@
 // C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
-// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged, the grouped-query forms mhla_causal_*_gqa of the ragged entry points, their forms on chosen rows of a state pool, mhla_causal_*_slots, and those on a pool whose finished chunks are pages, mhla_causal_*_paged; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged, the grouped-query forms mhla_causal_*_gqa of the ragged entry points, their forms on chosen rows of a state pool, mhla_causal_*_slots, those on a pool whose finished chunks are pages, mhla_causal_*_paged, and the step, the device-positioned step and the pack prefill on a pool of 2-byte pages, mhla_causal_*_paged_h16; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
@@ -56,11 +56,14 @@ int cst_check_dev(const char* name, const void* p) {   // an int32 array on the 
 // the un-slotted namesake, row b itself
 // a paged pool (the *_paged entry points) on top: the chains' `S` is then the pool of pages [n_pages][Hkv][K][V], and
 // table[map[b] cap_chunks + j] names the page of chunk j of call row b; table null: S is the dense array it was
+// h16 pages (the *_paged_h16 entry points) on top of that: the chains' `S` is the pool's payload, _Float16 [n_pages][Hkv][K][V], and
+// mult its multipliers, float [n_pages][Hkv][K V / 64]; mult null: the pages are fp32
 struct Slots {
     const int32_t* map = nullptr;
     int n = 0;
     const int32_t* table = nullptr;
     int n_pages = 0;
+    float* mult = nullptr;
 };
 int cst_check_slots(const int32_t* slot_dev, int n_slots) {
     RC(cst_check_dev("slot_dev", slot_dev));
@@ -71,6 +74,13 @@ int cst_check_pages(const float* pages, int n_pages, const int32_t* table_dev) {
     if (!pages || ((uintptr_t)pages) % 16) return fail(MHLA_EINVAL, "pages null or not 16-byte aligned");
     RC(cst_check_dev("table_dev", table_dev));
     if (n_pages <= 0) return fail(MHLA_EINVAL, "n_pages=%d must be positive", n_pages);
+    return MHLA_OK;
+}
+int cst_check_pages_h16(const void* pages_h16, const float* page_mult, int K, int V) {
+    if (!pages_h16 || !page_mult) return fail(MHLA_EINVAL, "pages_h16 or page_mult null");
+    if (((uintptr_t)pages_h16) % 16 || ((uintptr_t)page_mult) % 4)
+        return fail(MHLA_EINVAL, "pages_h16 must be 16-byte aligned and page_mult 4-byte aligned");
+    if (((long)K * V) % CSH_GROUP) return fail(MHLA_EINVAL, "K=%d V=%d: h16 pages need K*V %% %d == 0 (one multiplier per %d elements)", K, V, CSH_GROUP, CSH_GROUP);
     return MHLA_OK;
 }
 int cst_check_mix(const float* mix, int ldmix, int64_t lastrow) {   // lastrow: the last row of mix the call reads, up to its diagonal
@@ -97,7 +107,9 @@ int cst_roll(float* S, int cap, float* P, float* Cur, const float* mixrow, int n
 // the roll of a ragged state: each sequence for itself, by pos_dev (the position of the token its step just took)
 int cst_roll_ragged(float* S, int cap, float* P, float* Cur, const int32_t* pos_dev, Slots sl, const float* mix, int ldmix, int max_pos, int H,
                     int BH, long E, hipStream_t st) {
-    const CsRollArgs r{S, P, Cur, nullptr, E, cap, 0, 0, pos_dev, mix, ldmix, max_pos, H, sl.map, sl.n, sl.table, sl.n_pages};
+    const CsRollArgs r{S, P, Cur, nullptr, E, cap, 0, 0, pos_dev, mix, ldmix, max_pos, H, sl.map, sl.n, sl.table, sl.n_pages, (_Float16*)S, sl.mult};
+    if (sl.mult)   // (h16 pages: 8 elements a lane)
+        return launch(k_cs_roll<true, false, true, true, PF_H16>, dim3((unsigned)((E / CSH_EPL + 63) / 64), BH), dim3(64), 0, st, "k_cs_roll_ragged<h16>", r);
     return launch(sl.table ? k_cs_roll<true, false, true, true> : sl.map ? k_cs_roll<true, false, true> : k_cs_roll<true>, dim3((unsigned)((E / 4 + 63) / 64), BH), dim3(64), 0, st,
                   "k_cs_roll_ragged", r);
 }
@@ -142,6 +154,19 @@ int cst_xty_pack(const mhla_view& k, const mhla_view& v, float* S, int cap, floa
     const int strips = ((K + 63) / 64) * ((V + 63) / 64);
     return launch(k_bm_state<T, 4, 2, StateArgsDst>, dim3((unsigned)n_chunks, H, strips), dim3(NTHREADS), state_smem_floats<4>() * 4, st,
                   "k_bm_state<2,dst>", a);
+}
+
+// h16 pages: the chunks [c0, c0 + n) of a pack's chunk list (B = 1), fp32, into the staging area [H][n][K][V] -- the tiles of
+// cst_xty_pack, each at its place in the list instead of its place in a state
+template <typename T>
+int cst_xty_stage(const mhla_view& k, const mhla_view& v, float* stage, int n, const int* tab, int T_, int H, int K, int V, hipStream_t st) {
+    StateArgsVar a{};
+    a.x = cv(k); a.y = cv(v);
+    a.out = stage; a.H = H; a.M = n; a.S = CS; a.D = 64; a.DX = K; a.DY = V; a.T = T_; a.alpha = 1.f;
+    a.tab = (const tab2_t*)tab;
+    const int strips = ((K + 63) / 64) * ((V + 63) / 64);
+    return launch(k_bm_state<T, 4, 2, StateArgsVar>, dim3((unsigned)n, H, strips), dim3(NTHREADS), state_smem_floats<4>() * 4, st,
+                  "k_bm_state<2,stage>", a);
 }
 
 // the extension's workspace, in floats: P_c of every chunk touched after the first, then the fp32 rows the epilogue reads
@@ -350,7 +375,7 @@ int cs_step_dev_chain(mhla_view q, mhla_view k, mhla_view v, const float* mix, i
 // pack into row sl.map[s] of the pool -- S, P and Cur of those rows only, seq_len_dev stays indexed by s
 int cs_pack_chain(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur, int n_seqs,
                   const int32_t* seq_len_dev, Slots sl, int max_len, int T, int H, int K, int V, int chunk, int n_chunks,
-                  const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, int dtype, void* stream) {
+                  const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, void* ws, size_t ws_bytes, int dtype, void* stream) {
     RC(cst_check(1, H, K, V, chunk, dtype));
     if (n_seqs <= 0) return fail(MHLA_EINVAL, "n_seqs=%d must be positive", n_seqs);
     if ((size_t)n_seqs * H > 65535) return fail(MHLA_ENOTSUP, "n_seqs*H=%zu exceeds grid limit 65535", (size_t)n_seqs * H);
@@ -368,9 +393,25 @@ int cs_pack_chain(mhla_view k, mhla_view v, const float* mix, int ldmix, float* 
     RC(cst_check_dev("chunk_dst_dev", chunk_dst_dev));
     if (!chunk_tab_dev || ((uintptr_t)chunk_tab_dev) % 8) return fail(MHLA_EINVAL, "chunk_tab_dev null or not 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    DISPATCH_T(dtype, { RC(cst_xty_pack<ET>(k, v, S, cap_chunks, Cur, n_seqs, n_chunks, chunk_tab_dev, chunk_dst_dev, sl, T, H, K, V, st)); });
     const long E = (long)K * V;
-    const CsRollArgs r{S, P, Cur, nullptr, E, cap_chunks, 0, 0, seq_len_dev, mix, ldmix, max_len, H, sl.map, sl.n, sl.table, sl.n_pages};
+    const CsRollArgs r{S, P, Cur, nullptr, E, cap_chunks, 0, 0, seq_len_dev, mix, ldmix, max_len, H, sl.map, sl.n, sl.table, sl.n_pages, (_Float16*)S, sl.mult};
+    if (sl.mult) {
+        // h16 pages: the chunks' fp32 K^T V staged in the workspace, then encoded into their pages (open chunks copied to Cur), over
+        // slices of the chunk list of as many chunks as the workspace holds; the roll once at the end
+        const size_t per = (size_t)H * E * 4;
+        RC(cst_check_ws(ws, ws_bytes, per));
+        const int fit = (int)std::min<size_t>((size_t)n_chunks, ws_bytes / per);
+        for (int c0 = 0; c0 < n_chunks; c0 += fit) {
+            const int n = std::min(fit, n_chunks - c0);
+            DISPATCH_T(dtype, { RC(cst_xty_stage<ET>(k, v, (float*)ws, n, chunk_tab_dev + 2 * c0, T, H, K, V, st)); });
+            const CsEncodeArgs en{(const float*)ws, chunk_tab_dev + 2 * c0, chunk_dst_dev + 2 * c0, (_Float16*)S, sl.mult, Cur, sl.map, sl.table, E,
+                                  n, H, n_seqs, cap_chunks, sl.n, sl.n_pages};
+            RC(launch(k_cs_page_encode, dim3((unsigned)n, H, (unsigned)((E / CSH_EPL + 63) / 64)), dim3(64), 0, st, "k_cs_page_encode", en));
+        }
+        return launch(k_cs_roll<false, true, true, true, PF_H16>, dim3((unsigned)((E / CSH_EPL + 63) / 64), n_seqs * H), dim3(64), 0, st,
+                      "k_cs_roll_pack<h16>", r);
+    }
+    DISPATCH_T(dtype, { RC(cst_xty_pack<ET>(k, v, S, cap_chunks, Cur, n_seqs, n_chunks, chunk_tab_dev, chunk_dst_dev, sl, T, H, K, V, st)); });
     return launch(sl.table ? k_cs_roll<false, true, true, true> : sl.map ? k_cs_roll<false, true, true> : k_cs_roll<false, true>, dim3((unsigned)((E / 4 + 63) / 64), n_seqs * H), dim3(64), 0, st,
                   "k_cs_roll_pack", r);
 }
@@ -445,7 +486,7 @@ int mhla_causal_varlen_state_init(mhla_view k, mhla_view v, const float* mix, in
                                   int n_seqs, const int32_t* seq_len_dev, int max_len, int T, int H, int K, int V, int chunk, int n_chunks,
                                   const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, int dtype, void* stream) {
     return cs_pack_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, n_seqs, seq_len_dev, Slots{}, max_len, T, H, K, V, chunk, n_chunks, chunk_tab_dev,
-                         chunk_dst_dev, dtype, stream);
+                         chunk_dst_dev, nullptr, 0, dtype, stream);
 }
 
 int mhla_causal_varlen_state_init_slots(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
@@ -454,7 +495,7 @@ int mhla_causal_varlen_state_init_slots(mhla_view k, mhla_view v, const float* m
                                         int dtype, void* stream) {
     RC(cst_check_slots(slot_dev, n_slots));
     return cs_pack_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, n_seqs, seq_len_dev, Slots{slot_dev, n_slots}, max_len, T, H, K, V, chunk, n_chunks,
-                         chunk_tab_dev, chunk_dst_dev, dtype, stream);
+                         chunk_tab_dev, chunk_dst_dev, nullptr, 0, dtype, stream);
 }
 
 int mhla_causal_step(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur,
@@ -751,7 +792,53 @@ int mhla_causal_varlen_state_init_paged(mhla_view k, mhla_view v, const float* m
     RC(cst_check_pages(pages, n_pages, table_dev));
     RC(cst_check_slots(slot_dev, n_slots));
     return cs_pack_chain(k, v, mix, ldmix, pages, cap_chunks, P, Cur, n_seqs, seq_len_dev, Slots{slot_dev, n_slots, table_dev, n_pages}, max_len, T,
-                         H, K, V, chunk, n_chunks, chunk_tab_dev, chunk_dst_dev, dtype, stream);
+                         H, K, V, chunk, n_chunks, chunk_tab_dev, chunk_dst_dev, nullptr, 0, dtype, stream);
+}
+
+// ---- h16 pages: the paged step, device-positioned step and pack prefill on a pool of 2-byte pages (mhla_hip.h), each through its
+// namesake's chain
+int mhla_causal_step_paged_h16(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, void* pages_h16, float* page_mult, int n_pages,
+                               const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev,
+                               int n_slots, int64_t max_pos, int any_boundary, mhla_mview out, mhla_view gate, const float* norm_w,
+                               float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk,
+                               float scale, int dtype, void* stream) {
+    RC(cst_check_pages_h16(pages_h16, page_mult, K, V));
+    RC(cst_check_pages((const float*)pages_h16, n_pages, table_dev));
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cs_step_ragged_chain(q, k, v, mix, ldmix, (float*)pages_h16, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots, table_dev, n_pages, page_mult},
+                                max_pos, any_boundary, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_step_dev_paged_h16(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, void* pages_h16, float* page_mult,
+                                   int n_pages, const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev,
+                                   const int32_t* slot_dev, int n_slots, int32_t* full_dev, const void* rope_cos, const void* rope_sin,
+                                   int64_t ld_tab, int64_t tab_rows, int feature_map, mhla_mview out, mhla_view gate, const float* norm_w,
+                                   float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk,
+                                   float scale, int dtype, void* stream) {
+    RC(cst_check_pages_h16(pages_h16, page_mult, K, V));
+    RC(cst_check_pages((const float*)pages_h16, n_pages, table_dev));
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cs_step_dev_chain(q, k, v, mix, ldmix, (float*)pages_h16, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots, table_dev, n_pages, page_mult},
+                             full_dev, rope_cos, rope_sin, ld_tab, tab_rows, feature_map, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K,
+                             V, chunk, scale, dtype, stream);
+}
+
+size_t mhla_causal_varlen_state_init_paged_h16_ws_bytes(int n_chunks, int H, int K, int V, int dtype) {
+    (void)dtype;
+    if (n_chunks <= 0 || H <= 0 || K <= 0 || V <= 0) return 0;
+    return (size_t)n_chunks * H * K * V * 4;
+}
+
+int mhla_causal_varlen_state_init_paged_h16(mhla_view k, mhla_view v, const float* mix, int ldmix, void* pages_h16, float* page_mult, int n_pages,
+                                            const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int n_seqs,
+                                            const int32_t* seq_len_dev, const int32_t* slot_dev, int n_slots, int max_len, int T, int H, int K,
+                                            int V, int chunk, int n_chunks, const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, void* ws,
+                                            size_t ws_bytes, int dtype, void* stream) {
+    RC(cst_check_pages_h16(pages_h16, page_mult, K, V));
+    RC(cst_check_pages((const float*)pages_h16, n_pages, table_dev));
+    RC(cst_check_slots(slot_dev, n_slots));
+    return cs_pack_chain(k, v, mix, ldmix, (float*)pages_h16, cap_chunks, P, Cur, n_seqs, seq_len_dev, Slots{slot_dev, n_slots, table_dev, n_pages, page_mult},
+                         max_len, T, H, K, V, chunk, n_chunks, chunk_tab_dev, chunk_dst_dev, ws, ws_bytes, dtype, stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 //                      workgroup) so that B H = 4 still fills the machine; per-split partial sums of o -> fp32 workspace
 //   k_cs_step_finish : partials summed in split order, scale, one rounding; optional RMSNorm x swish gate over the head's V channels
 //   k_cs_roll        : the chunk boundary (and the prefix mix of a prefilled state; PACK: of every sequence of a prefilled pack)
+//   k_cs_page_encode : h16 pages only -- the staged fp32 chunks of a pack prefill into their 2-byte pages
 // Ragged batches (every sequence at a position of its own): the same kernels, instantiated with RAGGED, read pos[b] from a device
 // int32 [B] array and derive i, r per (b, h) workgroup -- the step its mix[i][i], the roll whether this sequence is on a boundary
 // at all.  Tiling, K split, row walk and the order of every sum are the uniform ones, so equal positions give the uniform bits.
@@ -35,7 +36,8 @@
 // head count for that reason), at 1 / G of its state traffic.  The finish runs unchanged over the B H query heads.
 // Memory-bound (P and Cur read, Cur written: 12 K V bytes per (b, h) and token); plain fp32 FMA, no MFMA, no atomics: every
 // sum has a fixed order, so results repeat bit for bit.  The state is fp32 whatever the tensor dtype: Cur takes up to 64
-// rank-1 updates and P sums up to L chunks -- a 16-bit state would round at every token.
+// rank-1 updates and P sums up to L chunks -- a 16-bit state would round at every token.  (A FINISHED chunk is written once: the
+// h16 pages of a paged pool, below, round it once; P and Cur stay fp32.)
 #pragma once
 #include "common.hpp"
 #include "causal.hpp"   // CS, the chunk length
@@ -388,7 +390,143 @@ struct CsRollArgs {
     // PAGED only (cst_page): S is a pool of pages [n_pages][H][K][V] and chunk j of state row sb lives in page table[sb cap + j]
     const int* table;      // [n_slots][cap]
     int n_pages;
+    // FMT == PF_H16 only (h16 pages, below): the pool's payload [n_pages][H][K][V] and multipliers [n_pages][H][K V / 64]; S is unused
+    _Float16* pay;
+    float* mult;
 };
+
+// ---- h16 pages: a paged pool whose finished chunks take 2 bytes an element (the mhla_causal_*_paged_h16 entry points)
+// A page is a payload _Float16 [H][K][V] and, apart from it, multipliers float [H][K V / 64]: group g of a head is elements
+// [64 g, 64 g + 64) of the head's flattened [K][V] chunk (K V % 64 == 0: the host checked), stored as the h16 format of common.hpp --
+// m = h16_mult_from_max(largest magnitude of the group), payload = (_Float16)(x h16_inv(m)) rounded to nearest even, decoded as
+// (float)payload m, exact in fp32.  A finished chunk is written once, so it is rounded once; P and Cur stay fp32.
+// A lane holds CSH_EPL = 8 adjacent elements, one 16-byte piece of the payload (8-byte requests move at 0.54 - 0.70 of the 16-byte
+// rate, which would give back what the halved bytes gain: profiles/causal_state_h16.md), so a group is 8 adjacent lanes and a wave
+// covers 512 elements.  Encode and decode below are the only ones: every writer and every reader of a page goes through them.
+constexpr int PF_F32 = 0, PF_H16 = 1;   // page formats
+constexpr int CSH_GROUP = 64;           // elements per multiplier
+constexpr int CSH_EPL = 8;              // elements per lane
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+
+// x: this lane's 8 elements of a group whose other 56 the 7 neighbouring lanes hold (all 8 lanes of the group must call: the group's
+// largest magnitude is taken across them).  Magnitudes compare as bit patterns, so a NaN or an infinity orders above every finite
+// value -- the multiplier reads the exponent field alone.  Returns the payload piece; m: the group's multiplier, the same in all 8 lanes
+__device__ __forceinline__ f16x8 csh_encode(const f32x8 x, float& m) {
+    unsigned mx = 0u;
+#pragma unroll
+    for (int t = 0; t < CSH_EPL; ++t) mx = max(mx, __float_as_uint(x[t]) & 0x7fffffffu);
+#pragma unroll
+    for (int o = 1; o < CSH_GROUP / CSH_EPL; o <<= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
+    m = h16_mult_from_max(__uint_as_float(mx));
+    const float inv = h16_inv(m);
+    f16x8 p;
+#pragma unroll
+    for (int t = 0; t < CSH_EPL; ++t) p[t] = (_Float16)(x[t] * inv);   // (round to nearest even)
+    return p;
+}
+__device__ __forceinline__ f32x8 csh_decode(const f16x8 p, float m) {
+    f32x8 x;
+#pragma unroll
+    for (int t = 0; t < CSH_EPL; ++t) x[t] = (float)p[t] * m;
+    return x;
+}
+__device__ __forceinline__ f32x8 csh_ld8(const float* p) {
+    const f32x4 a = gld<f32x4>(p), b = gld<f32x4>(p + 4);
+    return f32x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+}
+__device__ __forceinline__ void csh_st8(float* p, const f32x8 x) {
+    gst<f32x4>(p, f32x4{x[0], x[1], x[2], x[3]});
+    gst<f32x4>(p + 4, f32x4{x[4], x[5], x[6], x[7]});
+}
+
+// the h16 roll: k_cs_roll<RAGGED or PACK, SLOT, PAGED, PF_H16>, grid (ceil(E / 8 / 64), B H), one wave per workgroup.  What RAGGED
+// and PACK derive per sequence is what the fp32 kernel derives.  The commit encodes Cur into the page (the multiplier from one lane
+// of the group, the payload from all) and zeroes Cur; the new P is the ascending fmaf sum over DECODED pages, the chunk just
+// committed included -- mixrow[n] * decode(encode(last)), not the fp32 `last` -- so that P is a function of the pages alone and a
+// slot that was prefilled and one that was stepped to the same tokens hold the same bits.  E % 64 == 0: whole groups leave together at
+// the `e >= E` test, every other return is uniform over the wave, so all 8 lanes of a group that stays reach the reduction.
+template <bool RAGGED, bool PACK>
+__device__ __forceinline__ void cs_roll_h16(const CsRollArgs& a) {
+    const long e = ((long)blockIdx.x * 64 + threadIdx.x) * CSH_EPL;
+    if (e >= a.E) return;
+    const int b = (int)(blockIdx.y / a.H), h = (int)(blockIdx.y - b * a.H);
+    const int sb = cst_slot(a.slot, a.n_slots, b);
+    if (sb < 0) return;   // an inactive row of a slotted call
+    const long pe = ((long)sb * a.H + h) * a.E + e;
+    int nj, commit;
+    if constexpr (PACK) {
+        const int p = a.pos[b];
+        if (p < 0 || p > a.max_pos) return;
+        nj = p / CS;
+        commit = 0;
+        if (p % CS == 0) csh_st8(a.Cur + pe, f32x8{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f});
+    } else {
+        static_assert(RAGGED, "the h16 roll is the ragged or the pack one");
+        const int p = a.pos[sb];
+        if (p < 0 || p > a.max_pos || p % CS != CS - 1) return;
+        nj = p / CS + 1;
+        commit = 1;
+    }
+    const float* mixrow = nj < a.cap ? a.mix + (long)nj * a.ldmix : nullptr;
+    const int* trow = a.table + (long)sb * a.cap;
+    const long G = a.E / CSH_GROUP;                        // multipliers per head
+    const long he = (long)h * a.E + e, hg = h * G + e / CSH_GROUP;   // from a page's start: this lane's payload piece, its group's multiplier
+    const long PE = (long)a.H * a.E, PG = a.H * G;         // elements, multipliers per page
+    int n = nj;
+    f32x8 last = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (commit) {
+        const long pg = cst_page(trow, a.n_pages, nj - 1);
+        if (pg < 0) return;   // ahead of any write
+        float m;
+        const f16x8 pay = csh_encode(csh_ld8(a.Cur + pe), m);
+        gst<f16x8>(a.pay + pg * PE + he, pay);
+        if ((threadIdx.x & (CSH_GROUP / CSH_EPL - 1)) == 0) a.mult[pg * PG + hg] = m;
+        csh_st8(a.Cur + pe, f32x8{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f});
+        last = csh_decode(pay, m);
+        n = nj - 1;
+    }
+    f32x8 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (mixrow) {
+        constexpr int U = 8;
+        int j = 0;
+        for (; j + U <= n; j += U) {
+            f16x8 s[U];
+            float m[U];
+            long pg[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) pg[u] = cst_page(trow, a.n_pages, j + u);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (pg[u] >= 0) {
+                    s[u] = gld<f16x8>(a.pay + pg[u] * PE + he);
+                    m[u] = a.mult[pg[u] * PG + hg];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (pg[u] < 0) continue;
+                const float w = mixrow[j + u];
+                const f32x8 d = csh_decode(s[u], m[u]);
+#pragma unroll
+                for (int t = 0; t < CSH_EPL; ++t) acc[t] = fmaf(w, d[t], acc[t]);
+            }
+        }
+        for (; j < n; ++j) {
+            const long pg = cst_page(trow, a.n_pages, j);
+            if (pg < 0) continue;
+            const f32x8 d = csh_decode(gld<f16x8>(a.pay + pg * PE + he), a.mult[pg * PG + hg]);
+            const float w = mixrow[j];
+#pragma unroll
+            for (int t = 0; t < CSH_EPL; ++t) acc[t] = fmaf(w, d[t], acc[t]);
+        }
+        if (commit) {
+            const float w = mixrow[n];
+#pragma unroll
+            for (int t = 0; t < CSH_EPL; ++t) acc[t] = fmaf(w, last[t], acc[t]);
+        }
+    }
+    csh_st8(a.P + pe, acc);
+}
 
 // grid (ceil(E / 4 / 64), B H), one wave per workgroup: P = sum_{j < nj} mixrow[j] S[j], ascending j
 // RAGGED: each (b, h) for itself -- not on a boundary (pos[b] % 64 != 63): nothing; else the commit with nj = i + 1 and the new P
@@ -399,10 +537,16 @@ struct CsRollArgs {
 // PAGED: every S[j] through the table, the group's eight entries fetched ahead of its eight tile loads; the same terms in the same
 // order.  A boundary whose chunk has no page leaves the sequence untouched: for the device-positioned step that sequence is frozen
 // (step and finish derive the same from pos and the table), for a host-positioned call it is defence only
-template <bool RAGGED = false, bool PACK = false, bool SLOT = false, bool PAGED = false>
+// FMT == PF_H16 (h16 pages): cs_roll_h16 above, grid (ceil(E / 8 / 64), B H); the fp32 instantiations are the code they were
+template <bool RAGGED = false, bool PACK = false, bool SLOT = false, bool PAGED = false, int FMT = PF_F32>
 __global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
     static_assert(!(RAGGED && PACK), "one addressing mode");
     static_assert(!PAGED || (SLOT && (RAGGED || PACK)), "a paged pool is addressed through a slot map");
+    static_assert(FMT == PF_F32 || PAGED, "a page format goes with a paged pool");
+    if constexpr (FMT == PF_H16) {
+        cs_roll_h16<RAGGED, PACK>(a);
+        return;
+    }
     const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
     if (e >= a.E) return;   // (E % 4 == 0)
     long bh = blockIdx.y;   // below: the state's (row, head)
@@ -504,6 +648,46 @@ __global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
         }
     }
     gst<f32x4>(a.P + pe, acc);
+}
+
+struct CsEncodeArgs {
+    const float* stage;    // [H][n][K V] fp32: K^T V of chunk c of this slice of the pack's chunk list, head h, at (h n + c) K V
+    const int* tab;        // [n][2] {first row, rows} of the slice's chunks (a chunk of 64 rows is a finished one)
+    const int* dst;        // [n][2] {sequence, index of the chunk within its sequence}
+    _Float16* pay;         // the pool: [n_pages][H][K][V]
+    float* mult;           //           [n_pages][H][K V / 64]
+    float* Cur;            //           [n_slots][H][K][V]
+    const int* slot;       // [nseq]
+    const int* table;      // [n_slots][cap]
+    long E;                // K V
+    int n, H, nseq, cap, n_slots, n_pages;
+};
+
+// The pack prefill into h16 slots: k_bm_state<2> leaves the fp32 K^T V of a slice of the pack's chunks in the call's workspace; this
+// moves each to its place.  grid (n, H, ceil(E / 8 / 64)), one wave per workgroup and 512 elements, as the h16 roll.  A finished chunk
+// is encoded into the page its sequence's table row names (none: dropped), an open one is copied to Cur of its sequence's slot -- the
+// destinations, and the entries that write nothing, of k_bm_state<2, StateArgsDst> (blockmix.hpp).
+__global__ __launch_bounds__(64) void k_cs_page_encode(const CsEncodeArgs a) {
+    const long e = ((long)blockIdx.z * 64 + threadIdx.x) * CSH_EPL;
+    if (e >= a.E) return;   // (E % 64 == 0: whole groups)
+    const int h = blockIdx.y, c = blockIdx.x;
+    const bool whole = ld_tab1(a.tab, 2 * c + 1) == CS;
+    const int seq = ld_tab1(a.dst, 2 * c), loc = ld_tab1(a.dst, 2 * c + 1);
+    if ((unsigned)seq >= (unsigned)a.nseq || (whole && (unsigned)loc >= (unsigned)a.cap)) return;   // (uniform over the wave, as all below)
+    const int row = ld_tab1(a.slot, seq);
+    if ((unsigned)row >= (unsigned)a.n_slots) return;
+    const f32x8 x = csh_ld8(a.stage + ((long)h * a.n + c) * a.E + e);
+    if (!whole) {
+        csh_st8(a.Cur + ((long)row * a.H + h) * a.E + e, x);
+        return;
+    }
+    const long pg = cst_page(a.table + (long)row * a.cap, a.n_pages, loc);
+    if (pg < 0) return;
+    float m;
+    const f16x8 pay = csh_encode(x, m);
+    const long G = a.E / CSH_GROUP;
+    gst<f16x8>(a.pay + (pg * a.H + h) * a.E + e, pay);
+    if ((threadIdx.x & (CSH_GROUP / CSH_EPL - 1)) == 0) a.mult[(pg * a.H + h) * G + e / CSH_GROUP] = m;
 }
 
 }  // namespace mhla

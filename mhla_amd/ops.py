@@ -1380,6 +1380,7 @@ class CausalState:
 
     __slots__ = ("S", "P", "Cur", "seen", "chunk_size", "lengths", "pos", "stale", "_full")
     pages = None   # (a paged pool and its views hold the finished chunks as pages instead of S: `PagedCausalState`)
+    page_mult = None   # (the multipliers of a paged pool of h16 pages: None for every other state)
 
     def __init__(self, S: torch.Tensor, P: torch.Tensor, Cur: torch.Tensor, seen: int = 0, chunk_size: int = 64, *, lengths=None,
                  pos: Optional[torch.Tensor] = None):
@@ -1696,7 +1697,7 @@ class _SlotPart:
     """Rows [i, j) of a view, as a launch takes them: the pool's tensors and that piece of the map."""
 
     __slots__ = ("S", "P", "Cur", "chunk_size", "map", "dims")
-    pages = None
+    pages = page_mult = None
 
     def __init__(self, pool, map_):
         self.S, self.P, self.Cur, self.chunk_size, self.map, self.dims = pool.S, pool.P, pool.Cur, pool.chunk_size, map_, pool.dims
@@ -1747,17 +1748,31 @@ class PagedCausalState(CausalState):
     `PoolExhausted` before anything changes when the free list is too short.  Changed rows of the table go to `table_dev` with a
     stream-ordered copy (no synchronisation).  `mhla_causal_step_dev` never assigns: `reserve(slots, tokens)` applies the rule ahead
     of it, and a sequence that reaches a chunk without a page is frozen like one at the capacity (`full`, `sync()`).
-    Not covered: `DecodeCache`, the fla layer and `hosts/gpt.py` keep states of their own; pages are never evicted or swapped."""
+    Not covered: `DecodeCache`, the fla layer and `hosts/gpt.py` keep states of their own; pages are never evicted or swapped.
+    Page format `"h16"` (`empty(..., page_format="h16")`, or a float16 `pages` together with `page_mult [n_pages, Hkv, K V / 64]`,
+    float32): a page takes 2 bytes an element -- an fp16 payload times one power-of-two multiplier per 64 adjacent elements of a
+    head's flattened `[K, V]` chunk (K V % 64 == 0), 11 significand bits relative to the group's largest element: the precision of
+    the forward's default chunk summaries -- so the pool holds 1.94 times the tokens in the same memory.  A finished chunk is written,
+    and so rounded, once; `P` and `Cur` stay fp32.  The chunk a sequence finishes with is the fp32 pool's, bit for bit, and its page
+    the encoding of it; every prefix mix sums DECODED pages, so `P` is a function of the pages alone and a prefilled slot holds
+    the bits of one stepped to the same tokens.  `mhla_causal_step`, `mhla_causal_step_dev` and the pack prefill `into=` take a view
+    of such a pool (the library's `*_paged_h16` entry points); `mhla_causal_extend`, `mhla_causal_verify` and `mhla_causal_commit`
+    raise NotImplementedError before anything is launched or any page assigned.  `compact()` decodes into the usual fp32 state.
+    The page rule, `reserve`, `fork`, `trim`, `reset` and `PoolExhausted` do not depend on the format."""
 
-    __slots__ = ("pages", "table", "table_dev", "refs", "free", "have")
+    __slots__ = ("pages", "page_mult", "table", "table_dev", "refs", "free", "have")
     _sync_cause = " or onto a chunk that has no page (pool.reserve(slots, tokens) assigns them)"
 
-    def __init__(self, pages: torch.Tensor, P: torch.Tensor, Cur: torch.Tensor, table, *, lengths=None, chunk_size: int = 64):
+    def __init__(self, pages: torch.Tensor, P: torch.Tensor, Cur: torch.Tensor, table, *, lengths=None, chunk_size: int = 64,
+                 page_mult: Optional[torch.Tensor] = None):
         fn = "PagedCausalState"
         if pages.dim() != 4 or P.dim() != 4 or tuple(P.shape[1:]) != tuple(pages.shape[1:]) or P.shape != Cur.shape:
             raise ValueError(f"{fn}: pages [n_pages, Hkv, K, V] and P, Cur [n_slots, Hkv, K, V], got {tuple(pages.shape)}, {tuple(P.shape)}, "
                              f"{tuple(Cur.shape)}")
-        if any(t.dtype != torch.float32 or t.device != pages.device or not t.is_contiguous() for t in (pages, P, Cur)):
+        h16 = page_mult is not None or pages.dtype == torch.float16
+        if h16:
+            self._check_h16(fn, pages, page_mult)
+        if any(t.dtype != torch.float32 or t.device != pages.device or not t.is_contiguous() for t in ((P, Cur) if h16 else (pages, P, Cur))):
             raise ValueError(f"{fn}: pages, P and Cur must be contiguous float32 tensors on one device")
         n_slots, n_pages = P.shape[0], pages.shape[0]
         if min(n_slots, n_pages) < 1:
@@ -1771,7 +1786,7 @@ class PagedCausalState(CausalState):
         bare = {s: js for s, js in bare.items() if js}
         if bare:
             raise ValueError(f"{fn}: slots {sorted(bare)} hold tokens in chunks that have no page: {bare} (lengths {lengths})")
-        self.S, self.P, self.Cur, self.chunk_size, self.pages = None, P, Cur, int(chunk_size), pages
+        self.S, self.P, self.Cur, self.chunk_size, self.pages, self.page_mult = None, P, Cur, int(chunk_size), pages, page_mult
         self.lengths, self.seen, self.stale, self._full = lengths, max(lengths), False, None
         self.pos = torch.tensor(lengths, dtype=torch.int32, device=pages.device)
         self.table = rows
@@ -1784,13 +1799,39 @@ class PagedCausalState(CausalState):
         self.have = [self._leading(r) for r in rows]   # per slot: its leading chunks that have pages -- the page rule's quick test
         self.table_dev = torch.tensor(rows, dtype=torch.int32, device=pages.device)
 
+    @staticmethod
+    def _check_h16(fn, pages, page_mult):
+        """h16 pages: a contiguous float16 payload with its multipliers, one per 64 elements of a head's chunk."""
+        n_pages, Hkv, K, V = pages.shape
+        if (K * V) % 64:
+            raise ValueError(f"{fn}: h16 pages need K V % 64 == 0 (one multiplier per 64 elements of a head's [K, V] chunk), got K={K} V={V}")
+        if pages.dtype != torch.float16 or page_mult is None or page_mult.dtype != torch.float32 or tuple(page_mult.shape) != (n_pages, Hkv, K * V // 64):
+            raise ValueError(f"{fn}: h16 pages are a float16 `pages` [n_pages, Hkv, K, V] together with a float32 `page_mult` "
+                             f"[n_pages, Hkv, K V / 64] = {(n_pages, Hkv, K * V // 64)}, got {pages.dtype} and "
+                             + ("no page_mult" if page_mult is None else f"{page_mult.dtype} {tuple(page_mult.shape)}"))
+        if page_mult.device != pages.device or not (pages.is_contiguous() and page_mult.is_contiguous()):
+            raise ValueError(f"{fn}: pages and page_mult must be contiguous tensors on one device")
+
     @classmethod
-    def empty(cls, n_slots: int, Hkv: int, K: int, V: int, capacity_chunks: int, n_pages: int, device="cuda") -> "PagedCausalState":
+    def empty(cls, n_slots: int, Hkv: int, K: int, V: int, capacity_chunks: int, n_pages: int, device="cuda",
+              page_format: str = "fp32") -> "PagedCausalState":
         if min(n_slots, Hkv, K, V, capacity_chunks, n_pages) <= 0:
             raise ValueError(f"PagedCausalState.empty: non-positive size n_slots={n_slots} Hkv={Hkv} K={K} V={V} "
                              f"capacity_chunks={capacity_chunks} n_pages={n_pages}")
+        if page_format not in ("fp32", "h16"):
+            raise ValueError(f"PagedCausalState.empty: page_format {page_format!r}: 'fp32' or 'h16'")
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
-        return cls(z(n_pages, Hkv, K, V), z(n_slots, Hkv, K, V), z(n_slots, Hkv, K, V), [[-1] * capacity_chunks for _ in range(n_slots)])
+        table = [[-1] * capacity_chunks for _ in range(n_slots)]
+        if page_format == "h16":
+            if (K * V) % 64:
+                raise ValueError(f"PagedCausalState.empty: h16 pages need K V % 64 == 0, got K={K} V={V}")
+            return cls(torch.zeros(n_pages, Hkv, K, V, dtype=torch.float16, device=device), z(n_slots, Hkv, K, V), z(n_slots, Hkv, K, V), table,
+                       page_mult=z(n_pages, Hkv, K * V // 64))
+        return cls(z(n_pages, Hkv, K, V), z(n_slots, Hkv, K, V), z(n_slots, Hkv, K, V), table)
+
+    @property
+    def page_format(self) -> str:
+        return "fp32" if self.page_mult is None else "h16"
 
     dims = property(lambda self: (self.P.shape[0], self.P.shape[1], len(self.table[0]), self.P.shape[2], self.P.shape[3]))
     capacity_chunks = property(lambda self: len(self.table[0]))
@@ -1799,7 +1840,8 @@ class PagedCausalState(CausalState):
 
     @property
     def nbytes(self) -> int:
-        return 4 * sum(t.numel() for t in (self.pages, self.P, self.Cur, self.pos, self._full, self.table_dev) if t is not None)
+        return sum(t.numel() * t.element_size()
+                   for t in (self.pages, self.page_mult, self.P, self.Cur, self.pos, self._full, self.table_dev) if t is not None)
 
     @property
     def pages_free(self) -> int:
@@ -1933,7 +1975,7 @@ class PagedCausalState(CausalState):
     def __repr__(self):
         n_slots, H, cap, K, V = self.dims
         return (f"PagedCausalState(n_slots={n_slots}, H={H}, K={K}, V={V}, capacity_chunks={cap}, pages={self.pages_used}/{len(self.refs)} used, "
-                f"lengths={self.lengths}, device={self.device})")
+                + ("" if self.page_mult is None else "page_format=h16, ") + f"lengths={self.lengths}, device={self.device})")
 
 
 class PagedStateView(CausalStateView):
@@ -1949,15 +1991,19 @@ class PagedStateView(CausalStateView):
                              "view.compact() gathers them")
 
     table_dev = property(lambda self: self.pool.table_dev)
+    page_mult = property(lambda self: self.pool.page_mult)
 
     def compact(self) -> CausalState:
         """A fresh dense ragged `CausalState` holding COPIES of the view's slots in call order, each chunk gathered from its page
-        (zeros where the table names none): plain tensor operations."""
+        (zeros where the table names none), h16 pages decoded (payload x multiplier, exact in fp32): plain tensor operations."""
         self._host_slots("PagedStateView.compact")
         pool = self.pool
         idx = self.map.to(torch.int64)
         tab = torch.tensor([pool.table[s] for s in self.slots], dtype=torch.int64).to(pool.device)   # [B, cap]
         S = pool.pages[tab.clamp_min(0)]   # [B, cap, H, K, V]
+        if pool.page_mult is not None:
+            m = pool.page_mult[tab.clamp_min(0)]   # [B, cap, H, K V / 64]
+            S = (S.float().reshape(*m.shape, 64) * m[..., None]).reshape(S.shape)
         S[tab < 0] = 0
         out = CausalState(S.permute(0, 2, 1, 3, 4).contiguous(), pool.P[idx], pool.Cur[idx], 0, self.chunk_size, lengths=self.lengths,
                           pos=pool.pos[idx])
@@ -1977,16 +2023,24 @@ class PagedStateView(CausalStateView):
 class _PagePart:
     """Rows [i, j) of a view of a paged pool, as a launch takes them: the pool's tensors and that piece of the map."""
 
-    __slots__ = ("pages", "table_dev", "P", "Cur", "chunk_size", "map", "dims")
+    __slots__ = ("pages", "page_mult", "table_dev", "P", "Cur", "chunk_size", "map", "dims")
 
     def __init__(self, pool, map_):
-        self.pages, self.table_dev, self.P, self.Cur = pool.pages, pool.table_dev, pool.P, pool.Cur
+        self.pages, self.page_mult, self.table_dev, self.P, self.Cur = pool.pages, pool.page_mult, pool.table_dev, pool.P, pool.Cur
         self.chunk_size, self.map, self.dims = pool.chunk_size, map_, pool.dims
 
 
 def _refuse_paged_pool(fn, state):
     if isinstance(state, PagedCausalState):
         raise TypeError(f"{fn}: a PagedCausalState is a pool, not a state: pass pool.at(slots), the view of the slots the call works on")
+
+
+def _refuse_h16(fn, state):
+    """What has no form on h16 pages, refused before anything is launched or any page is assigned: a verify uses the rows of S beyond
+    the finished chunks as scratch and reads them back, which rounded pages would change."""
+    if state.page_mult is not None:
+        raise NotImplementedError(f"{fn}: the pool's pages are h16 (page_format='h16'): mhla_causal_step, mhla_causal_step_dev and the pack "
+                                  "prefill (mhla_causal_state(..., into=view)) run on them; extend, verify and commit need an fp32 pool")
 
 
 def _assign_pages(fn, state, n_after, fresh=False):
@@ -2057,14 +2111,16 @@ def _state_head(mixf, state: CausalState):
     dimension, then S with the capacity, P, Cur."""
     pages = state.pages
     if pages is not None:   # a view of a paged pool, or a batch slice of one: (pages, n_pages, table_dev) where S stands
-        return (mixf.data_ptr(), mixf.shape[1], pages.data_ptr(), pages.shape[0], state.table_dev.data_ptr(), state.dims[2], state.P.data_ptr(),
-                state.Cur.data_ptr())
+        mult = state.page_mult   # (h16 pages: the multipliers follow the payload)
+        return (mixf.data_ptr(), mixf.shape[1], pages.data_ptr(), *(() if mult is None else (mult.data_ptr(),)), pages.shape[0],
+                state.table_dev.data_ptr(), state.dims[2], state.P.data_ptr(), state.Cur.data_ptr())
     return mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.S.shape[2], state.P.data_ptr(), state.Cur.data_ptr()
 
 
 def _pool_call(name: str, state) -> str:
-    """The entry point that runs the slotted call `name` (mhla_causal_*_slots) on `state`: itself, or its paged namesake."""
-    return name if state.pages is None else name[:-len("_slots")] + "_paged"
+    """The entry point that runs the slotted call `name` (mhla_causal_*_slots) on `state`: itself, its paged namesake, or that one's
+    form on h16 pages."""
+    return name if state.pages is None else name[:-len("_slots")] + ("_paged" if state.page_mult is None else "_paged_h16")
 
 
 @functools.lru_cache(maxsize=64)
@@ -2192,9 +2248,15 @@ def _causal_state_init_pack(k, v, mix, state: CausalState, plan: CausalVarlenPla
     slot = getattr(state, "map", None)
     name, where = (("mhla_causal_varlen_state_init", ()) if slot is None else
                    (_pool_call("mhla_causal_varlen_state_init_slots", state), (slot.data_ptr(), state.dims[0])))
+    ws = ()
+    if state.page_mult is not None:   # h16 pages: the chunks' fp32 K^T V are staged, in slices of the chunk list beyond the cap
+        V, dt = v.shape[-1], _dtype_code(k)
+        need = lib.mhla_causal_varlen_state_init_paged_h16_ws_bytes(plan.n_chunks, H, K, V, dt)
+        buf = _ws(min(need, max(EXTEND_WS_CAP_BYTES, lib.mhla_causal_varlen_state_init_paged_h16_ws_bytes(1, H, K, V, dt))), k.device)
+        ws = (buf.data_ptr(), buf.numel() * 4)
     rc = getattr(lib, name)(_view(k), _view(v), *_state_head(mixf, state), len(plan.lengths), seq_len.data_ptr(), *where,
                             max(plan.lengths), T, H, K, v.shape[-1], state.chunk_size, plan.n_chunks,
-                            plan.table.data_ptr(), plan.dst.data_ptr(), _dtype_code(k), _stream())
+                            plan.table.data_ptr(), plan.dst.data_ptr(), *ws, _dtype_code(k), _stream())
     _lib.check(rc, name)
 
 
@@ -2734,6 +2796,7 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     beyond `EXTEND_WS_CAP_BYTES` it runs window by window of whole chunks of tokens instead of sequence by sequence."""
     fn = "mhla_causal_extend"
     _decode_entry(fn, state, q, k, v, False, True)
+    _refuse_h16(fn, state)
     B, T, H, K = q.shape
     V = v.shape[-1]
     if counts is not None:
@@ -2801,6 +2864,7 @@ def mhla_causal_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     k and v (or to the contiguous copies the call made), not copies: the caller must not overwrite k, v before the commit."""
     fn = "mhla_causal_verify"
     _decode_entry(fn, state, q, k, v, False, True)
+    _refuse_h16(fn, state)
     B, T, H, K = q.shape
     V = v.shape[-1]
     counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, (T,) * B if counts is None else counts, scale, gate,
@@ -2855,6 +2919,7 @@ def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: C
     if not isinstance(state, CausalState):
         raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
     _refuse_paged_pool(fn, state)
+    _refuse_h16(fn, state)
     if isinstance(state, CausalStateView):
         state._host_slots(fn)
     state._refuse_stale(fn)

@@ -96,6 +96,13 @@ device time per call (median, min, max), the kernels' device times, and the byte
 mirror are put back before every call.  On a tree without `PagedCausalState` the same command times (a) and (b): the figures to hold
 the un-paged paths of a later tree against.
 
+`--paged-h16`: `--paged` at B = 4 and 32 with a fourth variant, (d) `h16_*`: the same view of a paged pool of h16 pages
+(`PagedCausalState(..., page_mult=)`: 2 bytes an element and one multiplier per 64, the same table) -- off a boundary, where the step
+reads P and Cur alone, and on one, where the roll encodes the closing chunk and mixes the decoded pages.  Then the PACK PREFILL into
+the slots (`mhla_causal_state(k, v, mix, cu_seqlens=plan, into=view)`, the B sequences at the "off" lengths, about 1000 tokens each)
+into the fp32 paged pool and into the h16 pool (state kernel into a staging area, `k_cs_page_encode`, roll): wall and device time per
+call, the kernels' device times, and the bytes of both pools.
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -485,7 +492,7 @@ def slots_config(B, H, K, V, steps, reps):
     return rec
 
 
-def paged_config(B, H, K, V, steps, reps):
+def paged_config(B, H, K, V, steps, reps, h16=False):
     g = torch.Generator().manual_seed(1)
     mix = causal_mixing_init(L).reshape(L, L).to(DEV)
     q, k, v = token(B, H, K, V, g)
@@ -523,6 +530,13 @@ def paged_config(B, H, K, V, steps, reps):
         paged.full
         states["paged"] = (paged, paged.at(slots), paged.at(idx.to(torch.int32)), spread_over_pool)
         nbytes["paged_pool_MB"] = round(paged.nbytes / 2 ** 20, 1)
+        if h16:   # the same table over 2-byte pages: a payload at the fp16 range's upper end, every multiplier 2^-17
+            pay = (z(n_pages, H, K, V).normal_(0, 0.1) * 2.0 ** 17).half()
+            hp = mhla_amd.PagedCausalState(pay, z(n_slots, H, K, V).normal_(0, 0.1), z(n_slots, H, K, V), table,
+                                           page_mult=torch.full((n_pages, H, K * V // 64), 2.0 ** -17, dtype=torch.float32, device=DEV))
+            hp.full
+            states["h16"] = (hp, hp.at(slots), hp.at(idx.to(torch.int32)), spread_over_pool)
+            nbytes["h16_pool_MB"] = round(hp.nbytes / 2 ** 20, 1)
     fns = {}
     for place, lens in places.items():
         for name, (st, host_view, dev_view, over) in states.items():
@@ -550,10 +564,39 @@ def paged_config(B, H, K, V, steps, reps):
                 devt[n].append(sum(kern[n].values()))
             for st, *_ in states.values():
                 st.Cur.zero_()
+    prefill = {}
+    if "h16" in states:   # last: a prefill starts its slots anew and takes the lowest free pages, which ends the random table
+        lens = places["off"]
+        cu = [0]
+        for n in lens:
+            cu.append(cu[-1] + n)
+        plan = mhla_amd.causal_varlen_plan(cu, DEV)
+        kc = torch.randn(1, cu[-1], H, K, generator=g).to(torch.bfloat16).to(DEV)
+        vc = torch.randn(1, cu[-1], H, V, generator=g).to(torch.bfloat16).to(DEV)
+        pf = {}
+        for name in ("paged", "h16"):
+            st, view = states[name][:2]
+
+            def fill(st=st, view=view):
+                st.stale = False
+                mhla_amd.mhla_causal_state(kc, vc, mix, cu_seqlens=plan, into=view)
+
+            pf[name] = fill
+        pw, pd, pk = {n: [] for n in pf}, {n: [] for n in pf}, {}
+        with torch.no_grad():
+            for _ in range(reps):
+                for n, fn in pf.items():
+                    pw[n].append(batch_us(fn, min(20, steps), warm=2))
+                for n, fn in pf.items():
+                    pk[n] = kernel_times(fn, iters=5)
+                    pd[n].append(sum(pk[n].values()))
+        prefill = {"prefill": {"tokens": cu[-1], "pack_chunks": plan.n_chunks, "wall_us": {n: spread(x) for n, x in pw.items()},
+                               "device_us": {n: spread(x) for n, x in pd.items()},
+                               "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in pk.items()}}}
     rec = {"paged": {"B": B, "H": H, "K": K, "V": V, "n_slots": n_slots, "slots": slots, "chunks": sorted(set(chunks)), "pages_per_slot": held},
            "steps_per_batch": steps, "reps": reps, **nbytes, "wall_us": {n: spread(x) for n, x in wall.items()},
            "device_us": {n: spread(x) for n, x in devt.items()},
-           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()}}
+           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()}, **prefill}
     print(json.dumps(rec), flush=True)
     return rec
 
@@ -920,8 +963,12 @@ if __name__ == "__main__":
     ap.add_argument("--gqa-prefill", action="store_true")
     ap.add_argument("--slots", action="store_true")
     ap.add_argument("--paged", action="store_true")
+    ap.add_argument("--paged-h16", action="store_true")
     a = ap.parse_args()
-    if a.paged:
+    if a.paged_h16:
+        for B in (4, 32):
+            paged_config(B, 4, 128, 256, max(200, a.steps), a.reps, h16=True)
+    elif a.paged:
         for B in (8, 32):
             paged_config(B, 4, 128, 256, max(200, a.steps), a.reps)
     elif a.slots:

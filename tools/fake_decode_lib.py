@@ -11,7 +11,9 @@ tools/record_blockmix_calls.py and tests/test_blockmix_calls_cpu.py (block-mix o
 Inside the `with`, `ops._require_gpu` and `ops._stream` are stubs and `_lib.load()` returns the recorder: every launching entry point
 is logged and returns 0 -- whatever `_lib.SIGNATURES` names, the slotted (`mhla_causal_*_slots`) and the paged calls among them
 (`mhla_causal_step_paged`, `mhla_causal_step_dev_paged`, `mhla_causal_extend_paged`, `mhla_causal_verify_paged`,
-`mhla_causal_commit_paged`, `mhla_causal_varlen_state_init_paged`: name `pages` and `table_dev` to see them in a call) --; the entry points that are host arithmetic (`*_ws_bytes`, `*_keeps_state`, `*_ok`, `*_dw_rows`, `*_fusable`,
+`mhla_causal_commit_paged`, `mhla_causal_varlen_state_init_paged`: name `pages` and `table_dev` to see them in a call; on h16 pages
+`mhla_causal_step_paged_h16`, `mhla_causal_step_dev_paged_h16` and `mhla_causal_varlen_state_init_paged_h16`, which take the payload
+and `page_mult` where those take `pages`, the prefill a workspace too) --; the entry points that are host arithmetic (`*_ws_bytes`, `*_keeps_state`, `*_ok`, `*_dw_rows`, `*_fusable`,
 the two `describe` calls, `mhla_set_option`, `mhla_abi_version`, `mhla_build_flags`) go to the real library, and the text log
 (`lines`, not `calls`) shows each with its integer arguments and its result.  An argument is recorded by its C type:
 a view as ("view", base, element offset, sb, sn, sh), a pointer as ("ptr", base, byte offset), a workspace as ("ws", bytes), a null
