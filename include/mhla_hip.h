@@ -683,6 +683,52 @@ int mhla_causal_varlen_state_init_paged(mhla_view k, mhla_view v, const float* m
                                         const int32_t* slot_dev, int n_slots, int max_len, int T, int H, int K, int V, int chunk, int n_chunks,
                                         const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, int dtype, void* stream);
 
+/* Packed new tokens: mhla_causal_extend_ragged, mhla_causal_verify_ragged and mhla_causal_commit_ragged on tokens that are NOT padded
+ * (added without a change of any existing signature or behaviour: MHLA_ABI_VERSION stays 9).  The new tokens of all B sequences are
+ * ONE run of n_tokens rows -- q, k, v, gate, out, y are [1][n_tokens][heads][K / V]; their batch stride sb is not used: pass 0 -- and
+ * sequence b's tokens are rows [off_dev[b], off_dev[b + 1]): off_dev is device int32 [B + 1], off_dev[0] = 0, non-decreasing,
+ * off_dev[B] = n_tokens; a sequence with no token (equal neighbours) keeps every bit of its state.  The layout of a scheduler step
+ * of continuous batching (and of mhla_causal_varlen_state_init): no padding row is allocated, staged or written.
+ * One entry point serves every kind of state, where the padded calls have one per kind:
+ *   Hkv          the k/v heads of k, v and the state; Hkv = H: ungrouped (the commit touches no q and takes Hkv alone)
+ *   slot_dev     device int32 [B], or NULL (n_slots unused): call row b works on row b of the state.  Non-null: on row slot_dev[b] of a
+ *                pool of n_slots rows, as the *_slots calls
+ *   table_dev    device int32 [n_slots][cap_chunks], or NULL (n_pages unused): `S` is the dense array [rows][Hkv][cap_chunks][K][V].
+ *                Non-null: `S` is the pool of fp32 pages [n_pages][Hkv][K][V], as `pages` of the *_paged calls
+ * Each runs its ragged namesake's chain -- the same launches (at most six; the commit at most four), tiles, K split and order of
+ * every sum, no atomics -- with w = off_dev[b + 1] - off_dev[b] where that reads ntok_dev[b] and off_dev[b] as the window's first
+ * row: sequence b's rows, its finished chunks, P, Cur and pos_dev[b] are BIT FOR BIT those of the padded call with ntok_dev[b] = w
+ * (one token: the bits of mhla_causal_step for a batch of one).  The fp32 rows are staged [H][n_tokens][V] and the last launch runs
+ * over (H, n_tokens): each workgroup finds its row's sequence by a binary search over off_dev, and the one of head 0 on a
+ * sequence's first row adds the sequence's tokens to pos_dev (the verify: does not).  accept_dev (commit): device int32 [B], the
+ * first min(accept_dev[b], w) rows of sequence b's window are taken.
+ * Host values that vouch for the arrays, as mhla_causal_extend_ragged's:
+ *   n_tokens     the rows of the pack, 1 .. 65535 (the last launch puts them on a grid dimension); takes T's place in every check
+ *   max_end, max_later, any_close   computed from pos_dev and the differences of off_dev (the commit: from the accepted counts)
+ * As a defence only, no content of the arrays addresses outside S, the matrix, the workspace or the token tensors: a sequence
+ * whose offsets decrease, whose window leaves [0, n_tokens), or which fails a test of mhla_causal_extend_ragged's defence is
+ * SKIPPED -- state and position untouched, its rows zeros -- and a row that belongs to no sequence is written as zeros.
+ * Workspace of extend and verify (mhla_causal_extend_packed_ws_bytes, pure host arithmetic, independent of dtype), in 4-byte words,
+ * each term rounded up to a multiple of 4:  B Hkv max_later K V  +  H n_tokens V  +  B; of the commit:
+ * mhla_causal_commit_ragged_ws_bytes(B).  MHLA_EINVAL before any launch, the message naming the value: off_dev null or misaligned;
+ * table_dev given with S misaligned or n_pages <= 0; slot_dev misaligned or given with n_slots <= 0; n_tokens outside 1 .. 65535;
+ * then what the ragged namesake checks (max_end, max_later, any_close, ldmix, the views, the state, the workspace, Hkv). */
+size_t mhla_causal_extend_packed_ws_bytes(int B, int n_tokens, int H, int Hkv, int K, int V, int max_later, int dtype);
+int mhla_causal_extend_packed(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int n_pages,
+                              const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev,
+                              int n_slots, const int32_t* off_dev, int n_tokens, int64_t max_end, int max_later, int any_close, mhla_mview out,
+                              mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H,
+                              int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream);
+int mhla_causal_verify_packed(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int n_pages,
+                              const int32_t* table_dev, int cap_chunks, float* P, float* Cur, const int32_t* pos_dev, const int32_t* slot_dev,
+                              int n_slots, const int32_t* off_dev, int n_tokens, int64_t max_end, int max_later, int any_close, mhla_mview out,
+                              mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H,
+                              int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream);
+int mhla_causal_commit_packed(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int n_pages, const int32_t* table_dev,
+                              int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev, int n_slots,
+                              const int32_t* off_dev, const int32_t* accept_dev, int n_tokens, int64_t max_end, int max_later, int any_close,
+                              void* ws, size_t ws_bytes, int B, int Hkv, int K, int V, int chunk, int dtype, void* stream);
+
 /* h16 pages: the paged step, device-positioned step and pack prefill on a pool whose pages take 2 bytes an element (added without a
  * change of any existing signature or behaviour: MHLA_ABI_VERSION stays 9).  A page is a payload, `pages_h16` _Float16
  * [n_pages][Hkv][K][V], 16-byte aligned, and apart from it multipliers, `page_mult` float [n_pages][Hkv][K V / 64], 4-byte aligned:

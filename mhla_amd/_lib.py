@@ -194,6 +194,16 @@ for _name in ("step", "step_dev", "varlen_state_init"):
         _args = _args[:-2] + [c_void_p, c_size_t] + _args[-2:]
     SIGNATURES[f"mhla_causal_{_name}_paged_h16"] = (_res, _args)
 SIGNATURES["mhla_causal_varlen_state_init_paged_h16_ws_bytes"] = (c_size_t, [c_int] * 5)
+# packed new tokens: one entry point for every kind of state -- (S or pages, n_pages, table_dev or null) after ldmix, (slot_dev or null,
+# n_slots) after pos_dev, then (off_dev, n_tokens) where the padded calls take (ntok_dev, T), no left_padded, Hkv after H
+_packed_state = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int]   # mix .. n_slots
+SIGNATURES["mhla_causal_extend_packed_ws_bytes"] = (c_size_t, [c_int] * 8)
+for _name in ("extend", "verify"):
+    SIGNATURES[f"mhla_causal_{_name}_packed"] = (c_int, [View, View, View] + _packed_state + [
+        c_void_p, c_int, c_int64, c_int, c_int, View, View, c_void_p, c_float, View, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int,
+        c_float, c_int, c_void_p])
+SIGNATURES["mhla_causal_commit_packed"] = (c_int, [View, View] + _packed_state + [
+    c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
 
 _lib = None
 

@@ -1,5 +1,5 @@
 // C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
-// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged, the grouped-query forms mhla_causal_*_gqa of the ragged entry points, their forms on chosen rows of a state pool, mhla_causal_*_slots, those on a pool whose finished chunks are pages, mhla_causal_*_paged, and the step, the device-positioned step and the pack prefill on a pool of 2-byte pages, mhla_causal_*_paged_h16; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged, the grouped-query forms mhla_causal_*_gqa of the ragged entry points, their forms on chosen rows of a state pool, mhla_causal_*_slots, those on a pool whose finished chunks are pages, mhla_causal_*_paged, the extend, verify and commit on packed new tokens, mhla_causal_*_packed, and the step, the device-positioned step and the pack prefill on a pool of 2-byte pages, mhla_causal_*_paged_h16; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
@@ -74,6 +74,16 @@ int cst_check_pages(const float* pages, int n_pages, const int32_t* table_dev) {
     if (!pages || ((uintptr_t)pages) % 16) return fail(MHLA_EINVAL, "pages null or not 16-byte aligned");
     RC(cst_check_dev("table_dev", table_dev));
     if (n_pages <= 0) return fail(MHLA_EINVAL, "n_pages=%d must be positive", n_pages);
+    return MHLA_OK;
+}
+// what a packed entry point checks of its nullable state arguments, and the Slots they make: off_dev is what makes the call packed,
+// so it is refused here, ahead of the chain (which takes a null off_dev for a padded call)
+int cst_packed_state(const float* S, int n_pages, const int32_t* table_dev, const int32_t* slot_dev, int n_slots, const int32_t* off_dev,
+                     Slots& sl) {
+    RC(cst_check_dev("off_dev", off_dev));
+    if (table_dev) RC(cst_check_pages(S, n_pages, table_dev));
+    if (slot_dev) RC(cst_check_slots(slot_dev, n_slots));
+    sl = Slots{slot_dev, slot_dev ? n_slots : 0, table_dev, table_dev ? n_pages : 0};
     return MHLA_OK;
 }
 int cst_check_pages_h16(const void* pages_h16, const float* page_mult, int K, int V) {
@@ -192,21 +202,24 @@ CxPlan cx_plan(int B, int T, int H, int K, int V, int64_t pos) {
 struct CxRagPlan {
     size_t tiles, stage, nval, total;
 };
-CxRagPlan cx_rag_plan(int B, int T, int H, int Hkv, int K, int V, int max_later) {   // (tiles per k/v head, rows per query head)
+// packed: T counts the tokens of the whole pack and the rows are [H][T][V], not [B H][T][V]
+CxRagPlan cx_rag_plan(int B, int T, int H, int Hkv, int K, int V, int max_later, bool packed = false) {   // (tiles per k/v head, rows per query head)
     CxRagPlan p{};
     p.tiles = al4((size_t)B * Hkv * max_later * K * V);
-    p.stage = al4((size_t)B * H * T * V);
+    p.stage = al4((size_t)(packed ? 1 : B) * H * T * V);
     p.nval = al4((size_t)B);
     p.total = p.tiles + p.stage + p.nval;
     return p;
 }
 
 // what the ragged entry points check of the host values that vouch for the device arrays, and of the rows of mix they let be read
-int cx_rag_check(int T, int cap_chunks, const int32_t* pos_dev, const int32_t* ntok_dev, int64_t max_end, int max_later, int any_close,
-                 const float* mix, int ldmix) {
+// (a packed call: off_dev where the padded one has ntok_dev, T the tokens of the pack)
+int cx_rag_check(int T, int cap_chunks, const int32_t* pos_dev, const int32_t* ntok_dev, const int32_t* off_dev, int64_t max_end, int max_later,
+                 int any_close, const float* mix, int ldmix) {
     if (cap_chunks > INT32_MAX / 64) return fail(MHLA_ENOTSUP, "cap_chunks=%d: positions beyond int32", cap_chunks);
     RC(cst_check_dev("pos_dev", pos_dev));
-    RC(cst_check_dev("ntok_dev", ntok_dev));
+    if (off_dev) RC(cst_check_dev("off_dev", off_dev));
+    else RC(cst_check_dev("ntok_dev", ntok_dev));
     if (max_end < 0) return fail(MHLA_EINVAL, "max_end=%lld is negative", (long long)max_end);
     if (max_end > (int64_t)64 * cap_chunks)
         return fail(MHLA_EINVAL, "max_end=%lld tokens need %lld chunks, the state holds %d", (long long)max_end, (long long)((max_end + 63) / 64), cap_chunks);
@@ -223,17 +236,20 @@ int cx_rag_check(int T, int cap_chunks, const int32_t* pos_dev, const int32_t* n
 // the ragged extend chain; dry (the verify): the same launches, nothing of the committed state -- Cur, P, pos_dev -- written
 // Hkv < H (grouped-query heads): the launches that form or move state run over the B Hkv k/v heads, the two that compute rows
 // (k_cx_out, the finish) over the B H query heads
+// off_dev (the packed entry points; ntok_dev null, left_padded 0): the tokens are ONE run of T rows, sequence b's [off_dev[b], off_dev[b + 1]),
+// the views come with sb = 0, the rows are staged [H][T][V] and the finish runs over (H, T)
 int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P,
-                    float* Cur, int32_t* pos_dev, Slots sl, const int32_t* ntok_dev, int T, int64_t max_end, int max_later, int any_close,
-                    int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws,
-                    size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream) {
+                    float* Cur, int32_t* pos_dev, Slots sl, const int32_t* ntok_dev, const int32_t* off_dev, int T, int64_t max_end,
+                    int max_later, int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
+                    mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale, int dtype,
+                    void* stream) {
     RC(cst_check(B, H, K, V, chunk, dtype));
     RC(cst_check_group(H, Hkv));
-    if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive", T);
-    if (T > 65535) return fail(MHLA_EINVAL, "T=%d exceeds 65535 tokens per call", T);   // (mhla_causal_extend answers MHLA_ENOTSUP here: kept, a caller may test the code)
+    if (T <= 0) return fail(MHLA_EINVAL, "%s=%d must be positive", off_dev ? "n_tokens" : "T", T);
+    if (T > 65535) return fail(MHLA_EINVAL, "%s=%d exceeds 65535 tokens per call", off_dev ? "n_tokens" : "T", T);   // (mhla_causal_extend answers MHLA_ENOTSUP here: kept, a caller may test the code)
     RC(cst_check_io(q, k, v, out, y, gate, norm_w, dtype, S, cap_chunks, P, Cur));
-    RC(cx_rag_check(T, cap_chunks, pos_dev, ntok_dev, max_end, max_later, any_close, mix, ldmix));
-    const CxRagPlan p = cx_rag_plan(B, T, H, Hkv, K, V, max_later);
+    RC(cx_rag_check(T, cap_chunks, pos_dev, ntok_dev, off_dev, max_end, max_later, any_close, mix, ldmix));
+    const CxRagPlan p = cx_rag_plan(B, T, H, Hkv, K, V, max_later, off_dev != nullptr);
     RC(cst_check_ws(ws, ws_bytes, p.total * 4));
     hipStream_t st = (hipStream_t)stream;
     const int BH = B * H, BHk = B * Hkv, nvt = (V + 63) / 64, strips = ((K + 63) / 64) * nvt;
@@ -242,8 +258,9 @@ int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float
     float* stage = tiles + p.tiles;
     int* nval = (int*)(stage + p.stage);
     const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0, dry ? 1 : 0, nullptr,
-                  sl.map, sl.n, sl.table, sl.n_pages};
+                  sl.map, sl.n, sl.table, sl.n_pages, off_dev};
     const int kr = cst_rows((size_t)H, K, V);   // a one-token sequence: the step's K split for a batch of one
+    const bool pk = off_dev != nullptr;   // (the kernels' PACKED instantiations; the padded ones are the code they were)
     // every launch but the last addresses by pos_dev; the last, which does not, advances it (dry: does not)
     DISPATCH_T(dtype, {
         CxOutArgs o{};
@@ -251,27 +268,35 @@ int cx_ragged_chain(bool dry, mhla_view q, mhla_view k, mhla_view v, const float
         o.stage = stage; o.H = H; o.K = K; o.V = V; o.T = T; o.scale = scale; o.mstep = (long)ldmix + 1;
         o.P = P; o.Cur = Cur; o.mdiag = mix; o.rag = g; o.later = 0; o.nval = nval; o.kr = kr; o.nsplit = (K + kr - 1) / kr;
         o.G = H / Hkv;
-        RC(launch(k_cx_out<ET, true>, dim3(1, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out_ragged", o));
+        RC(launch(pk ? k_cx_out<ET, true, true> : k_cx_out<ET, true>, dim3(1, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out_ragged", o));
         CxAccArgs c{};
         c.x = cv(k); c.y = cv(v); c.H = Hkv; c.DX = K; c.DY = V; c.rag = g; c.later = 0; c.S = S; c.Cur = Cur;
-        RC(launch(k_cx_xty_acc<ET, true>, dim3(1, BHk, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+        RC(launch(pk ? k_cx_xty_acc<ET, true, true> : k_cx_xty_acc<ET, true>, dim3(1, BHk, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
         if (any_close) {
             c.later = 1;
-            RC(launch(k_cx_xty_acc<ET, true>, dim3(std::max(1, max_later), BHk, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+            RC(launch(pk ? k_cx_xty_acc<ET, true, true> : k_cx_xty_acc<ET, true>, dim3(std::max(1, max_later), BHk, strips), dim3(NTHREADS), 0, st,
+                      "k_cx_xty_acc_ragged", c));
             CxMixRagArgs m{};
             m.m.S = S; m.m.ws = tiles; m.m.P = P; m.m.mix = mix; m.m.E = E; m.m.ldmix = ldmix; m.m.cap = cap_chunks;
             m.rag = g; m.H = Hkv;
             const int groups = (max_later + 1 + CX_MIX_NC - 1) / CX_MIX_NC;   // (the largest nc is max_later + 1)
-            RC(launch(k_cx_mix_ragged, dim3((unsigned)((E / 4 + 63) / 64), BHk, groups), dim3(64), 0, st, "k_cx_mix_ragged", m));
+            RC(launch(pk ? k_cx_mix_ragged<true> : k_cx_mix_ragged<>, dim3((unsigned)((E / 4 + 63) / 64), BHk, groups), dim3(64), 0, st, "k_cx_mix_ragged", m));
             if (max_later) {
                 o.P = tiles; o.Cur = nullptr; o.later = 1;
-                RC(launch(k_cx_out<ET, true>, dim3(max_later, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st, "k_cx_out_ragged", o));
+                RC(launch(pk ? k_cx_out<ET, true, true> : k_cx_out<ET, true>, dim3(max_later, BH, nvt), dim3(NTHREADS), CS_OUT_SMEM_FLOATS * 4, st,
+                          "k_cx_out_ragged", o));
             }
         }
         CsFinishArgs f{stage, cmv(out), cmv(y), cv(gate), norm_w, norm_eps, scale, H, V, 1, dry ? nullptr : pos_dev};
         f.nval = nval; f.left = left_padded ? 1 : 0; f.slot = sl.map; f.n_slots = sl.n;
-        RC(launch(sl.map ? k_cs_step_finish<ET, false, true, true> : k_cs_step_finish<ET, false, true>, dim3(BH, T), dim3(CST_THREADS), 0, st,
-                  "k_cs_step_finish_ragged", f));
+        if (pk) {
+            f.off = off_dev; f.nseq = B;
+            RC(launch(sl.map ? k_cs_step_finish<ET, false, true, true, false, true> : k_cs_step_finish<ET, false, true, false, false, true>,
+                      dim3(H, T), dim3(CST_THREADS), 0, st, "k_cs_step_finish_packed", f));
+        } else {
+            RC(launch(sl.map ? k_cs_step_finish<ET, false, true, true> : k_cs_step_finish<ET, false, true>, dim3(BH, T), dim3(CST_THREADS), 0, st,
+                      "k_cs_step_finish_ragged", f));
+        }
     });
     return MHLA_OK;
 }
@@ -416,36 +441,39 @@ int cs_pack_chain(mhla_view k, mhla_view v, const float* mix, int ldmix, float* 
                   "k_cs_roll_pack", r);
 }
 
-// the commit chain: the state half of the ragged extend on the accepted tokens, no q and no rows (H: the k/v heads)
+// the commit chain: the state half of the ragged extend on the accepted tokens, no q and no rows (H: the k/v heads); off_dev: as
+// cx_ragged_chain's
 int cx_commit_chain(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int cap_chunks, float* P, float* Cur, int32_t* pos_dev,
-                    Slots sl, const int32_t* ntok_dev, const int32_t* accept_dev, int T, int64_t max_end, int max_later, int any_close,
-                    int left_padded, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, int dtype, void* stream) {
+                    Slots sl, const int32_t* ntok_dev, const int32_t* off_dev, const int32_t* accept_dev, int T, int64_t max_end, int max_later,
+                    int any_close, int left_padded, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, int dtype, void* stream) {
     RC(cst_check(B, H, K, V, chunk, dtype));
-    if (T <= 0) return fail(MHLA_EINVAL, "T=%d must be positive", T);
-    if (T > 65535) return fail(MHLA_EINVAL, "T=%d exceeds 65535 tokens per call", T);
+    if (T <= 0) return fail(MHLA_EINVAL, "%s=%d must be positive", off_dev ? "n_tokens" : "T", T);
+    if (T > 65535) return fail(MHLA_EINVAL, "%s=%d exceeds 65535 tokens per call", off_dev ? "n_tokens" : "T", T);
     CHECK_VIEW(k); CHECK_VIEW(v);
     RC(cst_check_state(S, cap_chunks, P, Cur));
     RC(cst_check_dev("accept_dev", accept_dev));
-    RC(cx_rag_check(T, cap_chunks, pos_dev, ntok_dev, max_end, max_later, any_close, mix, ldmix));
+    RC(cx_rag_check(T, cap_chunks, pos_dev, ntok_dev, off_dev, max_end, max_later, any_close, mix, ldmix));
     RC(cst_check_ws(ws, ws_bytes, al4((size_t)B) * 4));
     hipStream_t st = (hipStream_t)stream;
     const int BH = B * H, strips = ((K + 63) / 64) * ((V + 63) / 64);
     const long E = (long)K * V;
     int* nval = (int*)ws;
+    const bool pk = off_dev != nullptr;
     const CxRag g{pos_dev, ntok_dev, T, cap_chunks, (int)max_end, max_later, any_close ? 1 : 0, left_padded ? 1 : 0, 0, accept_dev, sl.map, sl.n, sl.table,
-                  sl.n_pages};
+                  sl.n_pages, off_dev};
     // every launch but the last addresses by pos_dev; the last, which does not, advances it
     DISPATCH_T(dtype, {
         CxAccArgs c{};
         c.x = cv(k); c.y = cv(v); c.H = H; c.DX = K; c.DY = V; c.rag = g; c.later = 0; c.S = S; c.Cur = Cur; c.nval = nval;
-        RC(launch(k_cx_xty_acc<ET, true>, dim3(1, BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+        RC(launch(pk ? k_cx_xty_acc<ET, true, true> : k_cx_xty_acc<ET, true>, dim3(1, BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
         if (any_close) {
             c.later = 1;
-            RC(launch(k_cx_xty_acc<ET, true>, dim3(std::max(1, max_later), BH, strips), dim3(NTHREADS), 0, st, "k_cx_xty_acc_ragged", c));
+            RC(launch(pk ? k_cx_xty_acc<ET, true, true> : k_cx_xty_acc<ET, true>, dim3(std::max(1, max_later), BH, strips), dim3(NTHREADS), 0, st,
+                      "k_cx_xty_acc_ragged", c));
             CxMixRagArgs m{};
             m.m.S = S; m.m.ws = nullptr; m.m.P = P; m.m.mix = mix; m.m.E = E; m.m.ldmix = ldmix; m.m.cap = cap_chunks;
             m.rag = g; m.H = H;
-            RC(launch(k_cx_mix_ragged, dim3((unsigned)((E / 4 + 63) / 64), BH, 1), dim3(64), 0, st, "k_cx_mix_ragged", m));
+            RC(launch(pk ? k_cx_mix_ragged<true> : k_cx_mix_ragged<>, dim3((unsigned)((E / 4 + 63) / 64), BH, 1), dim3(64), 0, st, "k_cx_mix_ragged", m));
         }
     });
     return launch(k_cx_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, "k_cx_advance", pos_dev, (const int*)nval, B, sl.map, sl.n);
@@ -634,7 +662,7 @@ int mhla_causal_extend_ragged(mhla_view q, mhla_view k, mhla_view v, const float
                               int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                               mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                               void* stream) {
-    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, ntok_dev, T, max_end, max_later, any_close, left_padded,
+    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, ntok_dev, nullptr, T, max_end, max_later, any_close, left_padded,
                            out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, H, K, V, chunk, scale, dtype, stream);
 }
 
@@ -643,7 +671,7 @@ int mhla_causal_extend_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const f
                                   int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                                   mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
                                   int dtype, void* stream) {
-    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, ntok_dev, T, max_end, max_later, any_close, left_padded,
+    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, ntok_dev, nullptr, T, max_end, max_later, any_close, left_padded,
                            out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
@@ -652,7 +680,7 @@ int mhla_causal_verify_ragged(mhla_view q, mhla_view k, mhla_view v, const float
                               int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                               mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, float scale, int dtype,
                               void* stream) {
-    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), Slots{}, ntok_dev, T, max_end, max_later, any_close, left_padded, out, gate, norm_w,
+    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), Slots{}, ntok_dev, nullptr, T, max_end, max_later, any_close, left_padded, out, gate, norm_w,
                            norm_eps, y, ws, ws_bytes, B, H, H, K, V, chunk, scale, dtype, stream);
 }
 
@@ -661,7 +689,7 @@ int mhla_causal_verify_ragged_gqa(mhla_view q, mhla_view k, mhla_view v, const f
                                   int any_close, int left_padded, mhla_mview out, mhla_view gate, const float* norm_w, float norm_eps,
                                   mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V, int chunk, float scale,
                                   int dtype, void* stream) {
-    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), Slots{}, ntok_dev, T, max_end, max_later,
+    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), Slots{}, ntok_dev, nullptr, T, max_end, max_later,
                            any_close, left_padded, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
@@ -674,7 +702,7 @@ int mhla_causal_commit_ragged(mhla_view k, mhla_view v, const float* mix, int ld
                               int32_t* pos_dev, const int32_t* ntok_dev, const int32_t* accept_dev, int T, int64_t max_end,
                               int max_later, int any_close, int left_padded, void* ws, size_t ws_bytes, int B, int H, int K, int V,
                               int chunk, int dtype, void* stream) {
-    return cx_commit_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, ntok_dev, accept_dev, T, max_end, max_later, any_close,
+    return cx_commit_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{}, ntok_dev, nullptr, accept_dev, T, max_end, max_later, any_close,
                            left_padded, ws, ws_bytes, B, H, K, V, chunk, dtype, stream);
 }
 
@@ -704,7 +732,7 @@ int mhla_causal_extend_slots(mhla_view q, mhla_view k, mhla_view v, const float*
                              const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V,
                              int chunk, float scale, int dtype, void* stream) {
     RC(cst_check_slots(slot_dev, n_slots));
-    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots}, ntok_dev, T, max_end, max_later,
+    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots}, ntok_dev, nullptr, T, max_end, max_later,
                            any_close, left_padded, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
@@ -714,7 +742,7 @@ int mhla_causal_verify_slots(mhla_view q, mhla_view k, mhla_view v, const float*
                              const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H, int Hkv, int K, int V,
                              int chunk, float scale, int dtype, void* stream) {
     RC(cst_check_slots(slot_dev, n_slots));
-    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), Slots{slot_dev, n_slots}, ntok_dev, T,
+    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), Slots{slot_dev, n_slots}, ntok_dev, nullptr, T,
                            max_end, max_later, any_close, left_padded, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale,
                            dtype, stream);
 }
@@ -724,7 +752,7 @@ int mhla_causal_commit_slots(mhla_view k, mhla_view v, const float* mix, int ldm
                              int64_t max_end, int max_later, int any_close, int left_padded, void* ws, size_t ws_bytes, int B, int H, int K,
                              int V, int chunk, int dtype, void* stream) {
     RC(cst_check_slots(slot_dev, n_slots));
-    return cx_commit_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots}, ntok_dev, accept_dev, T, max_end, max_later,
+    return cx_commit_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots}, ntok_dev, nullptr, accept_dev, T, max_end, max_later,
                            any_close, left_padded, ws, ws_bytes, B, H, K, V, chunk, dtype, stream);
 }
 
@@ -759,7 +787,7 @@ int mhla_causal_extend_paged(mhla_view q, mhla_view k, mhla_view v, const float*
     RC(cst_check_pages(pages, n_pages, table_dev));
     RC(cst_check_slots(slot_dev, n_slots));
     return cx_ragged_chain(false, q, k, v, mix, ldmix, pages, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots, table_dev, n_pages}, ntok_dev,
-                           T, max_end, max_later, any_close, left_padded, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk,
+                           nullptr, T, max_end, max_later, any_close, left_padded, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk,
                            scale, dtype, stream);
 }
 
@@ -771,7 +799,7 @@ int mhla_causal_verify_paged(mhla_view q, mhla_view k, mhla_view v, const float*
     RC(cst_check_pages(pages, n_pages, table_dev));
     RC(cst_check_slots(slot_dev, n_slots));
     return cx_ragged_chain(true, q, k, v, mix, ldmix, pages, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev),
-                           Slots{slot_dev, n_slots, table_dev, n_pages}, ntok_dev, T, max_end, max_later, any_close, left_padded, out, gate, norm_w,
+                           Slots{slot_dev, n_slots, table_dev, n_pages}, ntok_dev, nullptr, T, max_end, max_later, any_close, left_padded, out, gate, norm_w,
                            norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
 }
 
@@ -781,7 +809,7 @@ int mhla_causal_commit_paged(mhla_view k, mhla_view v, const float* mix, int ldm
                              int left_padded, void* ws, size_t ws_bytes, int B, int H, int K, int V, int chunk, int dtype, void* stream) {
     RC(cst_check_pages(pages, n_pages, table_dev));
     RC(cst_check_slots(slot_dev, n_slots));
-    return cx_commit_chain(k, v, mix, ldmix, pages, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots, table_dev, n_pages}, ntok_dev, accept_dev,
+    return cx_commit_chain(k, v, mix, ldmix, pages, cap_chunks, P, Cur, pos_dev, Slots{slot_dev, n_slots, table_dev, n_pages}, ntok_dev, nullptr, accept_dev,
                            T, max_end, max_later, any_close, left_padded, ws, ws_bytes, B, H, K, V, chunk, dtype, stream);
 }
 
@@ -793,6 +821,46 @@ int mhla_causal_varlen_state_init_paged(mhla_view k, mhla_view v, const float* m
     RC(cst_check_slots(slot_dev, n_slots));
     return cs_pack_chain(k, v, mix, ldmix, pages, cap_chunks, P, Cur, n_seqs, seq_len_dev, Slots{slot_dev, n_slots, table_dev, n_pages}, max_len, T,
                          H, K, V, chunk, n_chunks, chunk_tab_dev, chunk_dst_dev, nullptr, 0, dtype, stream);
+}
+
+// ---- packed new tokens: the ragged extend, verify and commit on ONE run of tokens cut by off_dev (mhla_hip.h), each through its ragged
+// namesake's chain; one entry point serves every kind of state: slot_dev null -- row b itself, table_dev null -- `S` is the dense array
+size_t mhla_causal_extend_packed_ws_bytes(int B, int n_tokens, int H, int Hkv, int K, int V, int max_later, int dtype) {
+    (void)dtype;
+    if (B <= 0 || n_tokens <= 0 || H <= 0 || Hkv <= 0 || H % Hkv || K <= 0 || V <= 0 || max_later < 0) return 0;
+    return cx_rag_plan(B, n_tokens, H, Hkv, K, V, max_later, true).total * 4;
+}
+
+int mhla_causal_extend_packed(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int n_pages,
+                              const int32_t* table_dev, int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev,
+                              int n_slots, const int32_t* off_dev, int n_tokens, int64_t max_end, int max_later, int any_close, mhla_mview out,
+                              mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H,
+                              int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream) {
+    Slots sl{};
+    RC(cst_packed_state(S, n_pages, table_dev, slot_dev, n_slots, off_dev, sl));
+    return cx_ragged_chain(false, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, sl, nullptr, off_dev, n_tokens, max_end, max_later, any_close,
+                           0, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_verify_packed(mhla_view q, mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int n_pages,
+                              const int32_t* table_dev, int cap_chunks, float* P, float* Cur, const int32_t* pos_dev, const int32_t* slot_dev,
+                              int n_slots, const int32_t* off_dev, int n_tokens, int64_t max_end, int max_later, int any_close, mhla_mview out,
+                              mhla_view gate, const float* norm_w, float norm_eps, mhla_mview y, void* ws, size_t ws_bytes, int B, int H,
+                              int Hkv, int K, int V, int chunk, float scale, int dtype, void* stream) {
+    Slots sl{};
+    RC(cst_packed_state(S, n_pages, table_dev, slot_dev, n_slots, off_dev, sl));
+    return cx_ragged_chain(true, q, k, v, mix, ldmix, S, cap_chunks, P, Cur, const_cast<int32_t*>(pos_dev), sl, nullptr, off_dev, n_tokens, max_end,
+                           max_later, any_close, 0, out, gate, norm_w, norm_eps, y, ws, ws_bytes, B, H, Hkv, K, V, chunk, scale, dtype, stream);
+}
+
+int mhla_causal_commit_packed(mhla_view k, mhla_view v, const float* mix, int ldmix, float* S, int n_pages, const int32_t* table_dev,
+                              int cap_chunks, float* P, float* Cur, int32_t* pos_dev, const int32_t* slot_dev, int n_slots,
+                              const int32_t* off_dev, const int32_t* accept_dev, int n_tokens, int64_t max_end, int max_later, int any_close,
+                              void* ws, size_t ws_bytes, int B, int Hkv, int K, int V, int chunk, int dtype, void* stream) {
+    Slots sl{};
+    RC(cst_packed_state(S, n_pages, table_dev, slot_dev, n_slots, off_dev, sl));
+    return cx_commit_chain(k, v, mix, ldmix, S, cap_chunks, P, Cur, pos_dev, sl, nullptr, off_dev, accept_dev, n_tokens, max_end, max_later, any_close,
+                           0, ws, ws_bytes, B, Hkv, K, V, chunk, dtype, stream);
 }
 
 // ---- h16 pages: the paged step, device-positioned step and pack prefill on a pool of 2-byte pages (mhla_hip.h), each through its

@@ -42,6 +42,12 @@
 //   the P of the chunk open afterwards is formed), k_cx_advance: pos[b] += nval[b] -- the last, the only one not addressing by pos
 // (the middle two only when some sequence closes a chunk).  The same tiles and sums again: the state is the one the ragged extend
 // leaves after acc[b] tokens, bit for bit; one accepted token takes the step's fmaf.
+// Packed new tokens (CxRag::off; mhla_causal_{extend,verify,commit}_packed): the tokens of all sequences are ONE run of T rows and
+// sequence b's are [off[b], off[b + 1]) -- the three chains above with the token views' batch stride 0, w = off[b + 1] - off[b] where
+// cx_seq reads ntok[b] and shift = off[b]; the fp32 rows are staged [h][T][V] and the finish is k_cs_step_finish<WIN, PACKED> over
+// (H, T), which finds each row's sequence by a binary search over off.  The tiles, the K split and the order of every sum are the
+// padded chain's: the same bits per sequence.  Defence only: offsets that decrease or leave [0, T) skip the sequence.  PACKED is a
+// template parameter of cx_seq and of the three k_cx_* kernels that call it, so that the padded instantiations are the code they were.
 #pragma once
 #include "causal.hpp"
 #include "causal_step.hpp"
@@ -65,21 +71,37 @@ struct CxRag {
     // paged pools (cst_page, causal_step.hpp): S is a pool of pages and chunk j of state row sb lives in page table[sb cap + j]
     const int* table;      // [n_slots][cap] or null: S is dense
     int n_pages;
+    // packed new tokens (the mhla_causal_*_packed entry points): the tokens of all sequences are ONE run of T rows, sequence b's the rows
+    // [off[b], off[b + 1]) -- the token views come with sb = 0, ntok is unused and left is 0
+    const int* off;        // [B + 1] (the kernels' PACKED instantiations read it), or null: padded, [B][T]
 };
 struct CxSeq {
     int n, i, r, a;        // tokens; chunk and fill of the open chunk; rows of the first segment
     int later;             // chunks touched after the first
     int iend;              // chunk open after the extension
-    int shift;             // first token row inside [0, T)
+    int shift;             // first token row inside [0, T): of the sequence's padded rows, or -- packed -- of the pack
     int sb;                // the state's batch row: b, or slot[b] of a slotted call
     bool closes, full;     // the first segment closes chunk i; the state is full afterwards
 };
 // false: no token, an inactive row of a slotted call, or (defence only) entries outside what the host vouched for -- the caller
-// returns at once
+// returns at once.  PACKED (g.off set) is a template parameter of this and of the chain's kernels, not a run-time test of the pointer:
+// with the test compiled in, the padded k_cx_xty_acc became other code (60 SGPRs for 70; profiles/causal_extend_packed.md); as a
+// parameter the padded instantiations are the code they were
+template <bool PACKED = false>
 __device__ __forceinline__ bool cx_seq(const CxRag& g, int b, CxSeq& s) {
     s.sb = cst_slot(g.slot, g.n_slots, b);
     if (s.sb < 0) return false;
-    const int p = g.pos[s.sb], w = g.ntok[b];
+    const int p = g.pos[s.sb];
+    int w;
+    [[maybe_unused]] int first = 0;
+    if constexpr (PACKED) {   // workgroup-uniform entries read as cst_page reads the page table; a window that leaves [0, T) or offsets that decrease (w < 0, so n < 1): skipped
+        first = *(const __attribute__((address_space(4))) int*)(g.off + b);
+        const int end = *(const __attribute__((address_space(4))) int*)(g.off + b + 1);
+        if (first < 0 || end > g.T) return false;
+        w = end - first;
+    } else {
+        w = g.ntok[b];
+    }
     const int n = g.acc ? min(g.acc[b], w) : w;
     if (p < 0 || n < 1 || w > g.T || (long)p + n > (long)g.max_end) return false;
     s.n = n; s.i = p / CS; s.r = p - s.i * CS;
@@ -88,7 +110,8 @@ __device__ __forceinline__ bool cx_seq(const CxRag& g, int b, CxSeq& s) {
     s.iend = (p + n) / CS;
     s.closes = s.iend > s.i;
     s.full = s.iend >= g.cap;
-    s.shift = g.left ? g.T - w : 0;
+    if constexpr (PACKED) s.shift = first;
+    else s.shift = g.left ? g.T - w : 0;
     return s.later <= g.max_later && (!s.closes || g.any_close);
 }
 
@@ -103,7 +126,7 @@ __device__ __forceinline__ float* cx_chunk(float* S, const CxRag& g, int sb, int
 struct CxOutArgs {
     View q, k, v;          // [B][T][H][K / V]: the extension's tokens
     MView o;               // [B][T][H][V] rows, rounded once; ptr null: fp32 rows to `stage` instead
-    float* stage;          // [bh][T][V] fp32, NOT scaled (k_cs_step_finish scales, normalises and rounds)
+    float* stage;          // [bh][T][V] fp32, NOT scaled (k_cs_step_finish scales, normalises and rounds); packed (rag.off): [h][T][V]
     const float* P;        // prefix mix of this launch's segment 0
     long p_bh, p_seg;      // floats from one (b, h) / one segment to the next
     const float* Cur;      // [bh][K][V] the open chunk's K^T V before the segment (first segment), or null: zero
@@ -190,8 +213,9 @@ __device__ __forceinline__ void cx_one_token(const CxOutArgs& a, float* red, con
 
 // grid (segments, B H, ceil(V / 64)): k_cs_out on a run of <= 64 token rows of one chunk.  It only reads the state: with a.G > 1 the G
 // query heads of a group read the one state of their k/v head (causal_step.hpp), each with the tiles and sums of the ungrouped call
-template <typename T, bool RAGGED = false>
+template <typename T, bool RAGGED = false, bool PACKED = false>
 __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
+    static_assert(!PACKED || RAGGED, "a pack runs the ragged chain");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Qs = smem;                  // [64 c][66]
     float* Ks = Qs + CS * CS_LDX;      // [64 c'][66]
@@ -211,7 +235,7 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
     [[maybe_unused]] bool one = false;
     if constexpr (RAGGED) {
         CxSeq s;
-        const bool ok = cx_seq(a.rag, b, s);
+        const bool ok = cx_seq<PACKED>(a.rag, b, s);
         if (!a.later && h == 0 && blockIdx.z == 0 && tid == 0) a.nval[b] = ok ? s.n : 0;
         if (!ok || (a.later && seg >= s.later)) return;   // ahead of any LDS or further global traffic
         const long E = (long)a.K * a.V;
@@ -241,10 +265,12 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
     const T* qb = (const T*)a.q.ptr + b * a.q.sb + h * a.q.sh;
     const T* kb = (const T*)a.k.ptr + b * a.k.sb + hk * a.k.sh;
     const T* vb = (const T*)a.v.ptr + b * a.v.sb + hk * a.v.sh;
+    // the stage's rows of this (b, h): bh T ..; packed: the rows of head h are the pack's, h T .., and p0 counts from the pack's start
+    const long sbh = PACKED ? h : bh;
     if constexpr (RAGGED) {
         if (one) {
             cx_one_token<T>(a, smem, qb + p0 * a.q.sn, kb + p0 * a.k.sn, vb + p0 * a.v.sn, Pi, Ci, mii, v0,
-                            a.stage + ((long)bh * a.T + p0) * a.V + v0, tid);
+                            a.stage + (sbh * a.T + p0) * a.V + v0, tid);
             return;
         }
     }
@@ -287,7 +313,7 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
         T* ob = (T*)a.o.ptr + b * a.o.sb + h * a.o.sh;
         store_tile<T, 64>(ob + v0, a.o.sn, nullptr, p0, Os, CS_LDO, rv, vv, tid, NTHREADS);
     } else {
-        float* sb = a.stage + ((long)bh * a.T + p0) * a.V + v0;
+        float* sb = a.stage + (sbh * a.T + p0) * a.V + v0;
         for (int v = tid; v < rv * 16; v += NTHREADS) {
             const int r = v >> 4, c = (v & 15) * 4;
             if (c < vv) gst<f32x4>(sb + (long)r * a.V + c, *reinterpret_cast<const f32x4*>(Os + r * CS_LDO + c));
@@ -314,8 +340,9 @@ struct CxAccArgs {
 // closes, else Cur; one token: fmaf(k, v, Cur), the step's rank-1 update.  later = 1: K^T V alone (k_bm_state<2>'s tiles, loads and
 // kend: the same sums) of later segment blockIdx.x -- 64 rows -> S[i_b + 1 + s], fewer (the tail) -> Cur -- and segment 0's workgroups
 // write Cur = 0 for a sequence that closed its chunk and has no tail.  The two are separate launches: the first reads Cur.
-template <typename T, bool RAGGED = false>
+template <typename T, bool RAGGED = false, bool PACKED = false>
 __global__ __launch_bounds__(NTHREADS) void k_cx_xty_acc(const CxAccArgs a) {
+    static_assert(!PACKED || RAGGED, "a pack runs the ragged chain");
     constexpr int LD = ld_kmajor(64);
     __shared__ __attribute__((aligned(16))) float Xs[CS * LD];
     __shared__ __attribute__((aligned(16))) float Ys[CS * LD];
@@ -331,7 +358,7 @@ __global__ __launch_bounds__(NTHREADS) void k_cx_xty_acc(const CxAccArgs a) {
     [[maybe_unused]] long sbh = bh;   // the state's (row, head)
     if constexpr (RAGGED) {
         CxSeq s;
-        const bool ok = cx_seq(a.rag, b, s);
+        const bool ok = cx_seq<PACKED>(a.rag, b, s);
         if (a.nval && !a.later && h == 0 && blockIdx.z == 0 && tid == 0) a.nval[b] = ok ? s.n : 0;
         if (!ok) return;   // ahead of any LDS or further global traffic
         const long E = (long)a.DX * a.DY;
@@ -504,13 +531,14 @@ struct CxMixRagArgs {
 // grid (ceil(E / 4 / 64), B H, groups of the largest nc): each (b, h) for itself -- a sequence that closes no chunk returns; else
 // c0 = i_b + 1, its own later chunks to the workspace (stride rag.max_later), P of the chunk open afterwards to the state's P, or P = 0
 // where that sequence's state is then full
+template <bool PACKED = false>
 __global__ __launch_bounds__(64) void k_cx_mix_ragged(const CxMixRagArgs a) {
     const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
     if (e >= a.m.E) return;   // (E % 4 == 0)
     const long bh = blockIdx.y;
     const int b = (int)(bh / a.H);
     CxSeq s;
-    if (!cx_seq(a.rag, b, s) || !s.closes) return;
+    if (!cx_seq<PACKED>(a.rag, b, s) || !s.closes) return;
     const long sbh = bh + (long)(s.sb - b) * a.H;
     int c0 = s.i + 1, nws = s.later, ws_bh = a.rag.max_later, nc, cP;
     if (a.rag.dry) {   // the workspace tiles alone: no cP matches and none is negative

@@ -271,6 +271,9 @@ struct CsFinishArgs {
     // PAGED only (DEV on a paged pool): a position whose chunk has no page in the table stays as well, and full[b] = 1
     const int* table;      // [n_slots][tcap]
     int tcap, n_pages;
+    // PACKED only (WIN; the packed extend, causal_extend.hpp): the rows are ONE run of gridDim.y tokens, sequence b's [off[b], off[b + 1])
+    const int* off;        // [nseq + 1]
+    int nseq;
 };
 
 // grid (B H, T tokens): o = scale * (partials in split order); y = o rsqrt(mean(o^2 over V) + neps) nw g sigmoid(g), from the fp32 o
@@ -278,14 +281,45 @@ struct CsFinishArgs {
 // its step wrote, so its row needs no branch here
 // WIN: a row outside its sequence's window is written as zeros (out and y) and reads nothing else; advance[b] += nval[b].  pos is
 // not read by any other thread of this launch: the window comes from nval, which an earlier launch of the chain wrote
-template <typename T, bool DEV = false, bool WIN = false, bool SLOT = false, bool PAGED = false>
+// PACKED (with WIN), grid (H, tokens of the pack): part is [h][tokens][V] and out, y, gate come with sb = 0.  The workgroup finds the
+// sequence its row belongs to by a binary search over off (workgroup-uniform, read as cst_page reads the table; at most 17 halvings
+// for the 65535 sequences a grid holds); a row of a sequence the chain did not accept (nval[b] = 0), or -- defence only -- of no
+// sequence, is written as zeros; the workgroup of head 0 on the first row of sequence b advances its position
+template <typename T, bool DEV = false, bool WIN = false, bool SLOT = false, bool PAGED = false, bool PACKED = false>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishArgs a) {
     static_assert(!(DEV && WIN), "the device-positioned step has one row per sequence");
     static_assert(!PAGED || (SLOT && DEV), "the finish reads the page table only to tell a live sequence from a frozen one");
+    static_assert(!PACKED || WIN, "a pack is a set of windows");
     __shared__ float red[CST_THREADS / 64];
-    const int tid = threadIdx.x, bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
+    const int tid = threadIdx.x;
+    int bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
     const long tok = blockIdx.y;
-    if constexpr (WIN) {
+    if constexpr (PACKED) {
+        const auto off_at = [&](int i) { return *(const __attribute__((address_space(4))) int*)(a.off + i); };
+        h = bh;   // (bh stays the head: part's rows of a head are the pack's)
+        int lo = 0, hi = a.nseq;   // the last b with off[b] <= tok: empty sequences before it share its offset
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (off_at(mid) <= (int)tok) lo = mid;
+            else hi = mid;
+        }
+        b = lo;
+        const int first = off_at(b), n = a.nval[b];
+        if (a.advance && h == 0 && tok == first && tid == 0 && n > 0) {   // (nothing in this launch reads it; null: a verify)
+            const int sb = cst_row<SLOT>(a.slot, a.n_slots, b);
+            if (!SLOT || sb >= 0) a.advance[sb] += n;
+        }
+        if (tok < first || tok - first >= n) {
+            T* ob = a.out.ptr ? (T*)a.out.ptr + tok * a.out.sn + h * a.out.sh : nullptr;
+            T* yb = a.y.ptr ? (T*)a.y.ptr + tok * a.y.sn + h * a.y.sh : nullptr;
+            for (int c = tid; c < a.V; c += CST_THREADS) {
+                if (ob) cst_st1(ob + c, 0.f);
+                if (yb) cst_st1(yb + c, 0.f);
+            }
+            return;
+        }
+        b = 0;   // (the views of a pack have one batch row)
+    } else if constexpr (WIN) {
         const int n = a.nval[b], t0 = a.left ? (int)gridDim.y - n : 0;
         if (a.advance && h == 0 && tok == 0 && tid == 0) {   // (nothing in this launch reads it; null: a verify)
             const int sb = cst_row<SLOT>(a.slot, a.n_slots, b);

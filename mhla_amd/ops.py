@@ -1077,24 +1077,31 @@ def causal_varlen_plan(cu_seqlens, device=None, chunk_size: int = 64) -> CausalV
     """The `CausalVarlenPlan` of `cu_seqlens` (a sequence of ints or a 1-D integer tensor; reading a device tensor synchronises,
     once -- build the plan once per batch and pass it to every layer as `cu_seqlens=`).  ValueError unless cu_seqlens is 1-D,
     starts at 0 and never decreases; empty sequences are allowed.  `device` defaults to the tensor's."""
+    if isinstance(cu_seqlens, torch.Tensor) and device is None:
+        device = cu_seqlens.device
+    if int(chunk_size) <= 0:
+        _cu_host(cu_seqlens, False)   # (its refusals of the argument's form come first)
+        raise ValueError(f"chunk_size must be positive, got {chunk_size}")
+    return CausalVarlenPlan(_cu_host(cu_seqlens), device if device is not None else "cpu", chunk_size)
+
+
+def _cu_host(cu_seqlens, values=True):
+    """`cu_seqlens` (a sequence of ints or a 1-D integer tensor, read once) as a host tuple: ValueError unless it is 1-D and -- with
+    `values` -- starts at 0 and never decreases."""
     if isinstance(cu_seqlens, torch.Tensor):
         if cu_seqlens.dim() != 1 or cu_seqlens.is_floating_point() or cu_seqlens.is_complex():
             raise ValueError(f"cu_seqlens must be a 1-D integer tensor, got shape {tuple(cu_seqlens.shape)} of {cu_seqlens.dtype}")
-        if device is None:
-            device = cu_seqlens.device
         cu = cu_seqlens.tolist()
     else:
         cu = list(cu_seqlens)
         if any(isinstance(x, (list, tuple, torch.Tensor)) or int(x) != x for x in cu):
             raise ValueError(f"cu_seqlens must be a 1-D sequence of ints, got {cu_seqlens!r}")
     cu = tuple(int(x) for x in cu)
-    if int(chunk_size) <= 0:
-        raise ValueError(f"chunk_size must be positive, got {chunk_size}")
-    if len(cu) < 1 or cu[0] != 0:
+    if values and (len(cu) < 1 or cu[0] != 0):
         raise ValueError(f"cu_seqlens must start at 0, got {cu}")
-    if any(b < a for a, b in zip(cu, cu[1:])):
+    if values and any(b < a for a, b in zip(cu, cu[1:])):
         raise ValueError(f"cu_seqlens must be non-decreasing, got {cu}")
-    return CausalVarlenPlan(cu, device if device is not None else "cpu", chunk_size)
+    return cu
 
 
 def _causal_varlen_args(what, q, mixing_matrix, cu_seqlens, chunk_size) -> CausalVarlenPlan:
@@ -2366,7 +2373,7 @@ class _Prepared(NamedTuple):
         return self._replace(q=q, k=k, v=v, gate=gate, pos=self.pos if pos is None else pos)
 
 
-def _decode_entry(fn, state, q, k, v, one_token, refuse_stale):
+def _decode_entry(fn, state, q, k, v, one_token, refuse_stale, packed=False):
     """The first refusals of every decode call, in this order: the state's type, a stale host mirror (not for
     `mhla_causal_step_dev`, which never reads it), the tensors' rank, the token count."""
     if not isinstance(state, CausalState):
@@ -2383,11 +2390,11 @@ def _decode_entry(fn, state, q, k, v, one_token, refuse_stale):
     T = q.shape[1]
     if one_token and T != 1:
         raise ValueError(f"{fn} takes one token per call (T = 1), got T = {T}")
-    if T < 1:
+    if T < 1 and not packed:   # (a pack whose sequences are all empty has no row: nothing is launched)
         raise ValueError(f"{fn} takes at least one token per call, got T = {T}")
 
 
-def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=True) -> _Prepared:
+def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=True, seqs=None) -> _Prepared:
     """What `mhla_causal_step` and `mhla_causal_extend` (`fn`: the one called, for the messages) check after `_decode_entry`'s
     tests of the state's type, the tensors' rank and T, and the tensors they launch with.  The C ABI receives raw pointers, so
     everything is refused here, in an order callers rely on -- the head counts (k, v and the state may have Hkv heads that divide
@@ -2396,7 +2403,8 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
     or `state` is touched.  Returns a `_Prepared`; its position is that of the first token (of the furthest sequence
     of a ragged state, whose `seen` is `max(lengths)`: rows and capacity are checked against it).  `positioned=False`
     (`mhla_causal_step_dev`, which made its own check of the matrix against the capacity): the host position is neither read nor
-    checked -- a stale mirror is fine -- and the position returned is None."""
+    checked -- a stale mirror is fine -- and the position returned is None.  `seqs` (packed new tokens, `cu_seqlens=`): the
+    sequences the state must hold, where the tokens are one row [1, N, ...] and say nothing about it."""
     B, T, H, K = q.shape
     V = v.shape[-1]
     Hk = k.shape[2]   # grouped-query heads: k, v and the state have Hkv heads, q, gate and the rows H = G Hkv
@@ -2406,6 +2414,8 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
         _check_like(q, fn, k=(k, (B, T, Hk, K)), v=(v, (B, T, Hk, V)), gate=(gate, (B, T, H, V)))
     except TypeError as e:
         raise ValueError(str(e)) from None
+    if seqs is not None:
+        B = seqs
     if q.dtype not in _DTYPES:
         raise ValueError(f"{fn}: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
     dims, chunks = state.dims, state._chunks
@@ -2641,6 +2651,13 @@ def _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, scale, gate, norm
                          "device: pass state.to_ragged()")
     if len(state.lengths) != B:
         raise ValueError(f"{fn}: the state holds {len(state.lengths)} sequences, the tokens B={B}")
+    _counts_fit(fn, mixing_matrix, state, counts)
+    return counts, _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=False)
+
+
+def _counts_fit(fn, mixing_matrix, state, counts):
+    """The IndexErrors of a call with per-sequence counts, naming the sequences: every sequence's end within the rows of the mixing
+    matrix and the state's capacity."""
     if mixing_matrix.dim() < 2:
         raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
     L, cap = mixing_matrix.shape[0], state.capacity_chunks
@@ -2650,7 +2667,6 @@ def _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, scale, gate, norm
         if over:
             raise IndexError(f"{fn}: sequences {over} (lengths {tuple(state.lengths[b] for b in over)} + counts "
                              f"{tuple(counts[b] for b in over)}) need up to {max(need)} chunks but {what}")
-    return counts, _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=False)
 
 
 def _ragged_plan(lengths, counts, cap):
@@ -2696,6 +2712,138 @@ def _ragged_chains(fn, prepared, state, slices, counts, left_padded, res, norm_e
     # (`slices[0][1]`, the first slice's end, is the width `_ragged_slices` cut at)
     for (_, _, plan), (part, p, pos, ntok_, out) in zip(slices, _batch_slices(state, slices[0][1], prepared, state.pos, ntok, res)):
         _causal_extend_ragged(*p, part, pos, ntok_, plan, left_padded, out, norm_eps, fn)
+
+
+# ---- packed new tokens (`cu_seqlens=` of extend and verify, the draft's `cu` of a commit): the tokens of all sequences in one row
+_PACK_MAX_TOKENS = 65535   # tokens of one library call: its last launch puts them on a grid dimension
+
+
+def _packed_prepare(fn, q, k, v, mixing_matrix, state, cu_seqlens, counts, left_padded, scale, gate, norm_weight, epilogue):
+    """What a call with packed new tokens (`cu_seqlens=`) checks, in the order of `_counts_prepare`, before anything is launched or
+    `state` is touched; returns (cu as a tuple, every sequence's token count, what `_decode_prepare` returns)."""
+    if counts is not None or left_padded:
+        raise ValueError(f"{fn}: cu_seqlens (packed new tokens) excludes counts and left_padded, which place windows in padded tensors")
+    if q.shape[0] != 1:
+        raise ValueError(f"{fn}: cu_seqlens takes one packed row (B = 1), got B = {q.shape[0]}")
+    cu = _cu_host(cu_seqlens.cu if isinstance(cu_seqlens, CausalVarlenPlan) else cu_seqlens)   # (of a plan: its host `cu` alone)
+    if cu[-1] != q.shape[1]:
+        raise ValueError(f"{fn}: cu_seqlens ends at {cu[-1]}, the pack has N = {q.shape[1]} tokens")
+    if state.lengths is None:
+        raise ValueError(f"{fn}: cu_seqlens needs a ragged state and this one is uniform ({state!r}); the positions must live on the "
+                         "device: pass state.to_ragged()")
+    B = len(cu) - 1
+    if len(state.lengths) != B:
+        raise ValueError(f"{fn}: the state holds {len(state.lengths)} sequences, cu_seqlens has {len(cu)} entries ({B} sequences)")
+    counts = tuple(b - a for a, b in zip(cu, cu[1:]))
+    _counts_fit(fn, mixing_matrix, state, counts)
+    return cu, counts, _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=False, seqs=B)
+
+
+def _packed_slices(fn, state, cu, counts, H, mixf, ws_dims=None):
+    """The launch chains of one packed call, (first sequence, end, `_ragged_plan` of `counts`) each: the whole pack, or -- beyond
+    `_PACK_MAX_TOKENS`, one launch's (b, h) range (`_MAX_GRID_BH // H`) or, with `ws_dims` = (H, Hkv, K, V, dtype code) of a call
+    that computes rows, `EXTEND_WS_CAP_BYTES` -- consecutive runs of whole sequences, each as long as fits.  Sequences are
+    independent, so a cut changes no bit; there is no cut inside a sequence: one that alone exceeds a limit is a ValueError.  Then
+    `_ragged_slices`' check of the matrix's columns; all of it before the first launch."""
+    B, cap, nb = len(counts), state.capacity_chunks, max(1, _MAX_GRID_BH // H)
+    lib = _lib.load()
+
+    def fits(i, j, plan=None):
+        n = cu[j] - cu[i]
+        if j - i > nb or n > _PACK_MAX_TOKENS:
+            return False
+        if ws_dims is None or not n:
+            return True
+        Hq, Hk, K, V, dt = ws_dims
+        later = (plan or _ragged_plan(state.lengths[i:j], counts[i:j], cap))[1]
+        return lib.mhla_causal_extend_packed_ws_bytes(j - i, n, Hq, Hk, K, V, later, dt) <= EXTEND_WS_CAP_BYTES
+
+    whole = _ragged_plan(state.lengths, counts, cap)
+    slices, i = ([(0, B, whole)], B) if fits(0, B, whole) else ([], 0)   # (the usual call: one chain)
+    while i < B:
+        j = B
+        if not fits(i, B):
+            j = i + 1
+            if not fits(i, j):
+                raise ValueError(f"{fn}: sequence {i} alone brings {cu[j] - cu[i]} new tokens, more than one call takes ({_PACK_MAX_TOKENS} "
+                                 f"tokens, a workspace of EXTEND_WS_CAP_BYTES={EXTEND_WS_CAP_BYTES}): a pack is cut between sequences "
+                                 "only, pass the sequence in pieces")
+            while j < B and fits(i, j + 1):
+                j += 1
+        slices.append((i, j, _ragged_plan(state.lengths[i:j], counts[i:j], cap)))
+        i = j
+    for i, j, plan in slices:
+        if plan[0] and mixf.shape[1] < plan[3] + 1:
+            raise IndexError(f"{fn}: sequences {list(range(i, j))} (lengths {state.lengths[i:j]}, counts {counts[i:j]}): row {plan[3]} of "
+                             f"mixing_matrix is read, which has only {mixf.shape[1]} columns")
+    return slices
+
+
+def _packed_offsets(cu, slices, device, accept=None):
+    """The one small copy of a packed call: for every chain of `slices` its sequences' offsets from the chain's first token (j - i + 1
+    ints), one after the other, then -- a commit -- `accept`; returns (the device tensor, where each chain's offsets begin)."""
+    host, at = [], []
+    for i, j, _ in slices:
+        at.append(len(host))
+        host.extend(c - cu[i] for c in cu[i:j + 1])
+    if accept is not None:
+        host.extend(accept)
+    return torch.tensor(host, dtype=torch.int32).to(device), at
+
+
+def _packed_state_head(mixf, state, pos):
+    """What every packed entry point takes after its token views: the matrix, then `S` or the pages with (n_pages, table_dev) or
+    (0, null), the capacity, P, Cur, the positions, the slot map with the pool's rows or (null, 0)."""
+    pages, slot = state.pages, getattr(state, "map", None)
+    return (mixf.data_ptr(), mixf.shape[1],
+            *((state.S.data_ptr(), 0, None) if pages is None else (pages.data_ptr(), pages.shape[0], state.table_dev.data_ptr())),
+            state.dims[2] if slot is not None else state.S.shape[2], state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(),
+            *((None, 0) if slot is None else (slot.data_ptr(), state.dims[0])))
+
+
+def _view0(t: torch.Tensor) -> View:
+    """A tensor of a pack, [1, N, H, D], as the packed entry points take it: the batch stride 0."""
+    s = t.stride()
+    return View(t.data_ptr(), 0, s[1], s[2])
+
+
+@_device_guard
+def _causal_packed(q, k, v, gate, mixf, wf, _, scale, want_y, state, pos, off, B, plan, res, norm_eps, name):
+    """One launch chain of `mhla_causal_extend_packed` (`name`; or `mhla_causal_verify_packed`) on what `_decode_prepare` returned, cut
+    to the chain's tokens, for the B sequences `state` (a batch slice) holds: `pos` their device positions, `off` their B + 1 offsets
+    on the device, `plan` the host values of `_ragged_plan`; the rows into `res`."""
+    lib = _lib.load()
+    _, N, H, K = q.shape
+    Hk, V, dt = k.shape[2], v.shape[-1], _DTYPES[q.dtype]
+    max_end, max_later, any_close, _ = plan
+    ws = _ws(lib.mhla_causal_extend_packed_ws_bytes(B, N, H, Hk, K, V, max_later, dt), q.device)
+    rc = getattr(lib, name)(_view0(q), _view0(k), _view0(v), *_packed_state_head(mixf, state, pos), off.data_ptr(), N, max_end, max_later,
+                            int(any_close), NULL_VIEW if want_y else _view0(res), _view0(gate) if gate is not None else NULL_VIEW,
+                            wf.data_ptr() if wf is not None else None, float(norm_eps), _view0(res) if want_y else NULL_VIEW,
+                            ws.data_ptr(), ws.numel() * 4, B, H, Hk, K, V, state.chunk_size, float(scale), dt, _stream())
+    _lib.check(rc, name)
+
+
+def _packed_parts(state, slices):
+    """(`_state_slice`, its positions) of every chain of `slices`: a view's positions are the pool's, addressed through the map."""
+    pooled = isinstance(state, CausalStateView)
+    for i, j, _ in slices:
+        yield _state_slice(state, i, j), state.pos if pooled else state.pos[i:j]
+
+
+def _packed_chains(name, fn, prepared, state, cu, counts, res, norm_eps):
+    """The rows of a packed extend or verify (`name`: the entry point) into `res`: `_packed_slices`, the page rule, the one copy of
+    the offsets, then `_causal_packed` once per chain that has a token."""
+    H, Hk, K, V = prepared.q.shape[2], prepared.k.shape[2], prepared.q.shape[3], prepared.v.shape[-1]
+    slices = _packed_slices(fn, state, cu, counts, H, prepared.mixf, (H, Hk, K, V, _DTYPES[prepared.q.dtype]))
+    if state.pages is not None:
+        _assign_pages(fn, state, [p + n for p, n in zip(state.lengths, counts)])
+    off, at = _packed_offsets(cu, slices, res.device)
+    if len(slices) == 1:   # (the usual call: the objects themselves, no views to build)
+        return _causal_packed(*prepared, state, state.pos, off, len(counts), slices[0][2], res, norm_eps, name)
+    for (i, j, plan), a, (part, pos) in zip(slices, at, _packed_parts(state, slices)):
+        if plan[0]:   # (a chain whose sequences are all empty has no row and is left alone)
+            _causal_packed(*prepared.part(None, None, cu[i], cu[j]), part, pos, off[a:a + j - i + 1], j - i, plan, res[:, cu[i]:cu[j]], norm_eps, name)
 
 
 def _extend_run(prepared, part, res, norm_eps, i, j, p, t_lo, t_hi, step_t):
@@ -2766,7 +2914,8 @@ def _extend_counts(fn, prepared, state, counts, left_padded, res, norm_eps):
 
 def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
                        scale: Optional[float] = None, gate: Optional[torch.Tensor] = None, norm_weight: Optional[torch.Tensor] = None,
-                       norm_eps: float = 1e-5, epilogue: Optional[bool] = None, counts=None, left_padded: bool = False) -> torch.Tensor:
+                       norm_eps: float = 1e-5, epilogue: Optional[bool] = None, counts=None, left_padded: bool = False,
+                       cu_seqlens=None) -> torch.Tensor:
     """T >= 1 new tokens on an existing decode state in one call: q, k `[B, T, H, K]`, v (and `gate`) `[B, T, H, V]` of the tokens
     at positions `state.seen .. state.seen + T - 1`; returns those rows of `mhla_causal` over the whole sequence, `[B, T, H, V]`,
     updates `state` in place as T calls of `mhla_causal_step` would and adds T to `state.seen` -- the next turn of a
@@ -2793,12 +2942,34 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     per sequence but falls back to the uniform chain sequence by sequence (which cuts at chunk boundaries): the same rows and
     state within fp32 rounding, more launches.
     Grouped-query heads (k, v and the state on Hkv heads, as `mhla_causal_step`): always the ragged chain, on a uniform state too;
-    beyond `EXTEND_WS_CAP_BYTES` it runs window by window of whole chunks of tokens instead of sequence by sequence."""
+    beyond `EXTEND_WS_CAP_BYTES` it runs window by window of whole chunks of tokens instead of sequence by sequence.
+    cu_seqlens (B + 1 ints as a sequence, a 1-D tensor -- read once -- or a `CausalVarlenPlan`, of which only the host `cu` is used;
+    starts at 0, never decreases, ends at N; excludes `counts` and `left_padded`: ValueError): PACKED new tokens, the layout of a
+    scheduler step of continuous batching and of the pack prefill.  q, k are `[1, N, H, K]`, v (and `gate`) `[1, N, H(kv), V]`, the
+    state holds B sequences (ragged, not stale; a `CausalState`, or a view of a dense or an fp32 paged pool), and sequence b takes
+    tokens `[cu[b], cu[b + 1])` at its own position -- none (equal neighbours): its state keeps every bit.  Returns `[1, N, H, V]`.
+    No padding row is allocated, staged or written: the same ragged chain (at most six launches) with the fp32 rows staged
+    `[H, N, V]`; every sequence's rows and state are BIT FOR BIT those of the padded call with `counts=` the pack's lengths.  One
+    small host-to-device copy (the offsets).  Checks, IndexErrors and the page rule come before the first launch, in the order of
+    `counts=`; all sequences empty: nothing is launched, zeros are returned.  A pack beyond one call's 65535 tokens, one launch's
+    (b, h) range or `EXTEND_WS_CAP_BYTES` is cut BETWEEN sequences into consecutive chains (no bit changes); a single sequence
+    beyond the token bound or the cap is a ValueError -- there is no cut inside a sequence.  Not on h16 pages (NotImplementedError,
+    as the padded call)."""
     fn = "mhla_causal_extend"
-    _decode_entry(fn, state, q, k, v, False, True)
+    _decode_entry(fn, state, q, k, v, False, True, cu_seqlens is not None)
     _refuse_h16(fn, state)
     B, T, H, K = q.shape
     V = v.shape[-1]
+    if cu_seqlens is not None:
+        cu, counts, prepared = _packed_prepare(fn, q, k, v, mixing_matrix, state, cu_seqlens, counts, left_padded, scale, gate, norm_weight,
+                                               epilogue)
+        if not any(counts):
+            return torch.zeros((1, T, H, V), dtype=q.dtype, device=q.device)
+        res = q.new_empty((1, T, H, V))
+        _packed_chains("mhla_causal_extend_packed", fn, prepared, state, cu, counts, res, norm_eps)
+        state.lengths = tuple(p + n for p, n in zip(state.lengths, counts))
+        state.seen = max(state.lengths)
+        return res
     if counts is not None:
         counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, scale, gate, norm_weight, epilogue)
         if not any(counts):
@@ -2835,21 +3006,26 @@ class CausalDraft:
     """What `mhla_causal_verify` hands to `mhla_causal_commit`: the draft's prepared `k`, `v` (REFERENCES to the tensors the verify
     read, or to their contiguous copies -- not copies of their own), `counts` (B ints), `left_padded`, and `lengths`, the state's
     lengths when the draft was verified, which a commit holds the state to; `view`, the `CausalStateView` the draft was verified on
-    (None: a state of its own), which a commit holds the state to as well -- the same pool and the same slots."""
+    (None: a state of its own), which a commit holds the state to as well -- the same pool and the same slots; `cu`, the offsets of a
+    draft verified with `cu_seqlens=` (None: padded) -- k, v are then the pack `[1, N, Hkv, *]` and sequence b's window is rows
+    `[cu[b], cu[b + 1])`, `counts` their differences."""
 
-    __slots__ = ("k", "v", "counts", "left_padded", "lengths", "view")
+    __slots__ = ("k", "v", "counts", "left_padded", "lengths", "view", "cu")
 
-    def __init__(self, k, v, counts, left_padded, lengths, view=None):
+    def __init__(self, k, v, counts, left_padded, lengths, view=None, cu=None):
         self.k, self.v, self.counts, self.left_padded, self.lengths = k, v, tuple(counts), bool(left_padded), tuple(lengths)
         self.view = view
+        self.cu = None if cu is None else tuple(cu)
 
     def __repr__(self):
-        return f"CausalDraft(counts={self.counts}, left_padded={self.left_padded}, lengths={self.lengths})"
+        return (f"CausalDraft(counts={self.counts}, left_padded={self.left_padded}, lengths={self.lengths}"
+                + ("" if self.cu is None else ", packed") + ")")
 
 
 def mhla_causal_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
                        counts=None, left_padded: bool = False, scale: Optional[float] = None, gate: Optional[torch.Tensor] = None,
-                       norm_weight: Optional[torch.Tensor] = None, norm_eps: float = 1e-5, epilogue: Optional[bool] = None):
+                       norm_weight: Optional[torch.Tensor] = None, norm_eps: float = 1e-5, epilogue: Optional[bool] = None,
+                       cu_seqlens=None):
     """`(o, draft)`: the rows `mhla_causal_extend(q, k, v, mixing_matrix, state, counts=counts, left_padded=left_padded, ...)` would
     return, bit for bit, WITHOUT committing a token -- a draft of speculative, lookup or multi-token-prediction decoding to verify.
     `state` is untouched: `P`, `Cur`, `pos`, the finished chunks of `S`, `lengths` and `seen` are as before, so any call on it gives
@@ -2861,12 +3037,25 @@ def mhla_causal_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     launches at most; all counts 0: nothing is launched.  Batches beyond one launch's (b, h) range are sliced; a call whose workspace
     would exceed `EXTEND_WS_CAP_BYTES` raises ValueError (drafts are short: there is no sequential fallback).
     `draft` (a `CausalDraft`) is what `mhla_causal_commit` takes to advance the state by an accepted prefix.  It holds references to
-    k and v (or to the contiguous copies the call made), not copies: the caller must not overwrite k, v before the commit."""
+    k and v (or to the contiguous copies the call made), not copies: the caller must not overwrite k, v before the commit.
+    cu_seqlens: PACKED drafts, as `mhla_causal_extend(cu_seqlens=)` -- tokens `[1, N, ...]`, sequence b's draft rows
+    `[cu[b], cu[b + 1])`, rows `[1, N, H, V]`, bit for bit the padded verify's; the draft remembers the pack (`draft.cu`) and
+    `mhla_causal_commit` reads it from there, `accept[b]` the accepted prefix of sequence b's window.  A pack beyond one call's limits
+    is cut between sequences; a single sequence beyond them is a ValueError."""
     fn = "mhla_causal_verify"
-    _decode_entry(fn, state, q, k, v, False, True)
+    _decode_entry(fn, state, q, k, v, False, True, cu_seqlens is not None)
     _refuse_h16(fn, state)
     B, T, H, K = q.shape
     V = v.shape[-1]
+    if cu_seqlens is not None:
+        cu, counts, prepared = _packed_prepare(fn, q, k, v, mixing_matrix, state, cu_seqlens, counts, left_padded, scale, gate, norm_weight,
+                                               epilogue)
+        draft = CausalDraft(prepared.k, prepared.v, counts, False, state.lengths, state if isinstance(state, CausalStateView) else None, cu)
+        if not any(counts):
+            return torch.zeros((1, T, H, V), dtype=q.dtype, device=q.device), draft
+        res = q.new_empty((1, T, H, V))
+        _packed_chains("mhla_causal_verify_packed", fn, prepared, state, cu, counts, res, norm_eps)
+        return res, draft
     counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, (T,) * B if counts is None else counts, scale, gate,
                                        norm_weight, epilogue)
     draft = CausalDraft(prepared.k, prepared.v, counts, left_padded, state.lengths, state if isinstance(state, CausalStateView) else None)
@@ -2883,6 +3072,43 @@ def mhla_causal_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     res = q.new_empty((B, T, H, V))
     _ragged_chains("mhla_causal_verify_ragged", prepared, state, slices, counts, left_padded, res, norm_eps)
     return res, draft
+
+
+@_device_guard
+def _causal_commit_packed(k, v, mixf, state, pos, off, acc, B, plan):
+    """One launch chain of `mhla_causal_commit_packed` for the B sequences `state` (a batch slice) holds, on the chain's tokens of the
+    draft's pack: `pos` their device positions, which the chain advances, `off` / `acc` their B + 1 offsets and accepted counts on
+    the device, `plan` the host values of `_ragged_plan` for the accepted counts."""
+    lib = _lib.load()
+    _, N, H, K = k.shape
+    V, dt = v.shape[-1], _dtype_code(k)
+    max_end, max_later, any_close, _ = plan
+    ws = _ws(lib.mhla_causal_commit_ragged_ws_bytes(B, dt), k.device)
+    name = "mhla_causal_commit_packed"
+    rc = lib.mhla_causal_commit_packed(_view0(k), _view0(v), *_packed_state_head(mixf, state, pos), off.data_ptr(), acc.data_ptr(), N, max_end,
+                                       max_later, int(any_close), ws.data_ptr(), ws.numel() * 4, B, H, K, V, state.chunk_size, dt, _stream())
+    _lib.check(rc, name)
+
+
+def _commit_packed(fn, draft, mixf, state, accept):
+    """`mhla_causal_commit` of a draft verified with `cu_seqlens=`, after the checks both forms share: the rest of the padded form's,
+    the page rule, the one copy (offsets and `accept`), then one chain per slice of the pack."""
+    k, v, cu, B = draft.k, draft.v, draft.cu, len(draft.counts)
+    H = k.shape[2]
+    slices = _packed_slices(fn, state, cu, accept, H, mixf)
+    if any(plan[0] and mixf.shape[0] < plan[3] + 1 for _, _, plan in slices):
+        raise IndexError(f"{fn}: mixing_matrix has only {mixf.shape[0]} rows, fewer than the accepted tokens read (lengths "
+                         f"{state.lengths}, accept {accept})")
+    if state.pages is not None:
+        _assign_pages(fn, state, [p + a for p, a in zip(state.lengths, accept)])
+    off, at = _packed_offsets(cu, slices, k.device, accept)   # the one small copy of the call
+    acc = off[len(off) - B:]
+    for (i, j, plan), a, (part, pos) in zip(slices, at, _packed_parts(state, slices)):
+        if plan[0]:   # (a slice of which nothing was accepted is left alone)
+            _causal_commit_packed(k[:, cu[i]:cu[j]], v[:, cu[i]:cu[j]], mixf, part, pos, off[a:a + j - i + 1], acc[i:j], j - i, plan)
+    state.lengths = tuple(p + a for p, a in zip(state.lengths, accept))
+    state.seen = max(state.lengths)
+    return state
 
 
 @_device_guard
@@ -2944,6 +3170,8 @@ def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: C
                          f"{mixing_matrix.device}")
     _require_gpu(k, v, mixing_matrix)
     mixf = _mix2d(mixing_matrix)
+    if draft.cu is not None:
+        return _commit_packed(fn, draft, mixf, state, accept)
     slices = _ragged_slices(fn, state, accept, H, mixf)
     if any(plan[0] and mixf.shape[0] < plan[3] + 1 for _, _, plan in slices):
         raise IndexError(f"{fn}: mixing_matrix has only {mixf.shape[0]} rows, fewer than the accepted tokens read (lengths "

@@ -103,6 +103,19 @@ the slots (`mhla_causal_state(k, v, mix, cu_seqlens=plan, into=view)`, the B seq
 into the fp32 paged pool and into the h16 pool (state kernel into a staging area, `k_cs_page_encode`, roll): wall and device time per
 call, the kernels' device times, and the bytes of both pools.
 
+`--packed`: PACKED new tokens (`mhla_causal_extend(cu_seqlens=)`) beside the padded ragged call, at the C5 head (H = 4, K = 128,
+V = 256, bf16, L = 128), B = 8 and 32, on the mixed step of continuous batching: B - 1 decoders at positions of their own take ONE
+token each and the last sequence a 256-token slice of a prompt (from position 1000: it closes four chunks).  Variants, alternating
+in one run, `--reps` times, `--steps` calls each: `padded_extend` (`counts=`, tokens padded to [B, 256]), `padded_verify`,
+`ragged_step` (the single-token step of the same B sequences) -- the EXISTING paths, which the same command times on a tree
+without `cu_seqlens` too: the figures to hold them against --, then `packed_extend` ([1, B + 255] tokens), `padded_from_pack` (what a
+caller who holds a pack pays today: scatter the pack into zeroed padded tensors, the padded call, gather the rows back) and, at EQUAL
+tokens (every sequence 64 tokens from position 1000), `equal_padded` / `equal_packed`.  Wall and device time per call (median, min,
+max), the kernels' device times, launches per call, and the bytes of workspace and token tensors (q, k, v and the rows) of both
+layouts.  Positions and host mirror are put back before every call, for every variant.  `--packed --existing-only` times the existing
+paths alone on a tree that has `cu_seqlens` as well: the process then does exactly the work of the older tree's, which is what a
+comparison of the two builds needs (a process that also runs the packed variants differs in more than its library).
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -670,6 +683,104 @@ def mixed_config(H, K, V, steps, reps, slice_tokens=256):
     return rec
 
 
+def packed_config(B, H, K, V, steps, reps, slice_tokens=256, existing_only=False):
+    import inspect
+    has_packed = "cu_seqlens" in inspect.signature(mhla_amd.mhla_causal_extend).parameters and not existing_only
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    lengths = tuple((13 + b % 5) * 64 + 5 + (9 * b) % 50 for b in range(B - 1)) + (1000,)
+    counts = (1,) * (B - 1) + (slice_tokens,)
+    T, N = slice_tokens, B - 1 + slice_tokens
+    cu = [0]
+    for n in counts:
+        cu.append(cu[-1] + n)
+    mk = lambda rows, D: torch.randn(1, rows, H, D, generator=g).to(torch.bfloat16).to(DEV)
+    qp, kp, vp = mk(N, K), mk(N, K), mk(N, V)                        # the pack
+    q, k, v = (torch.zeros(B, T, H, t.shape[-1], dtype=t.dtype, device=DEV) for t in (qp, kp, vp))   # the same tokens, right-padded
+    rows = torch.cat([torch.arange(n) + b * T for b, n in enumerate(counts)]).to(DEV)   # row of the padded tensors of every pack row
+    for t, tp in ((q, qp), (k, kp), (v, vp)):
+        t.view(B * T, H, -1)[rows] = tp[0]
+    q1, k1, v1 = (t[:, :1].contiguous() for t in (q, k, v))         # one token per sequence
+    Te = 64                                                          # equal tokens: every sequence 64 from position 1000
+    qe, ke, ve = (torch.randn(B, Te, H, D, generator=g).to(torch.bfloat16).to(DEV) for D in (K, K, V))
+    qep, kep, vep = (t.reshape(1, B * Te, H, -1) for t in (qe, ke, ve))
+    cue = [b * Te for b in range(B + 1)]
+    st = mhla_amd.CausalState.empty(B, H, K, V, L, DEV)
+    st.S[:, :, :24].normal_(0, 0.1)
+    st.P.normal_(0, 0.1)
+    rag = mhla_amd.CausalState(st.S, st.P, st.Cur, lengths=lengths)
+    pos0 = torch.tensor(lengths, dtype=torch.int32, device=DEV)
+    pos_e = torch.full((B,), 1000, dtype=torch.int32, device=DEV)
+
+    def put_back(ls=lengths, p=pos0):
+        rag.lengths, rag.seen = tuple(ls), max(ls)
+        rag.pos.copy_(p)
+
+    def padded_extend():
+        put_back()
+        return mhla_amd.mhla_causal_extend(q, k, v, mix, rag, counts=counts)
+
+    def padded_verify():
+        put_back()
+        return mhla_amd.mhla_causal_verify(q, k, v, mix, rag, counts=counts)[0]
+
+    def ragged_step():
+        put_back()
+        return mhla_amd.mhla_causal_step(q1, k1, v1, mix, rag)
+
+    def equal_padded():
+        put_back((1000,) * B, pos_e)
+        return mhla_amd.mhla_causal_extend(qe, ke, ve, mix, rag, counts=(Te,) * B)
+
+    def packed_extend():
+        put_back()
+        return mhla_amd.mhla_causal_extend(qp, kp, vp, mix, rag, cu_seqlens=cu)
+
+    def padded_from_pack():
+        put_back()
+        pad = []
+        for tp in (qp, kp, vp):
+            t = torch.zeros(B * T, H, tp.shape[-1], dtype=tp.dtype, device=DEV)
+            t[rows] = tp[0]
+            pad.append(t.view(B, T, H, -1))
+        o = mhla_amd.mhla_causal_extend(*pad, mix, rag, counts=counts)
+        return o.view(B * T, H, V)[rows].unsqueeze(0)
+
+    def equal_packed():
+        put_back((1000,) * B, pos_e)
+        return mhla_amd.mhla_causal_extend(qep, kep, vep, mix, rag, cu_seqlens=cue)
+
+    fns = {"padded_extend": padded_extend, "padded_verify": padded_verify, "ragged_step": ragged_step, "equal_padded": equal_padded}
+    if has_packed:
+        fns.update(packed_extend=packed_extend, padded_from_pack=padded_from_pack, equal_packed=equal_packed)
+    wall = {n: [] for n in fns}
+    dev = {n: [] for n in fns}
+    kern = {}
+    with torch.no_grad():
+        for _ in range(reps):
+            for n, fn in fns.items():
+                wall[n].append(batch_us(fn, steps))
+            for n, fn in fns.items():
+                kern[n] = kernel_times(fn, iters=20)
+                dev[n].append(sum(kern[n].values()))
+            st.Cur.zero_()
+        launches = {n: launch_counts(fn) for n, fn in fns.items()}
+    lib = mhla_amd._lib.load()
+    later = max((p + n - 1) // 64 - p // 64 for p, n in zip(lengths, counts))
+    tok = lambda r: r * H * (2 * K + 2 * V) * 2   # q, k, v and the rows, bf16
+    nbytes = {"padded": {"workspace": lib.mhla_causal_extend_ragged_ws_bytes(B, T, H, K, V, later, 1), "tokens": tok(B * T)}}
+    if has_packed:
+        nbytes["packed"] = {"workspace": lib.mhla_causal_extend_packed_ws_bytes(B, N, H, H, K, V, later, 1), "tokens": tok(N)}
+    rec = {"packed": {"B": B, "H": H, "K": K, "V": V, "tokens": N, "padded_rows": B * T, "lengths": lengths, "counts": counts,
+                      "equal_tokens": Te, "tree_has_cu_seqlens": has_packed},
+           "steps_per_batch": steps, "reps": reps,
+           "wall_us": {n: spread(x) for n, x in wall.items()}, "device_us": {n: spread(x) for n, x in dev.items()},
+           "launches": {n: {"total": sum(c.values()), "by_kernel": c} for n, c in launches.items()},
+           "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()}, "bytes": nbytes}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def speculative_config(B, H, K, V, steps, reps, pos=2048, k=4):
     g = torch.Generator().manual_seed(1)
     mix = causal_mixing_init(L).reshape(L, L).to(DEV)
@@ -964,8 +1075,13 @@ if __name__ == "__main__":
     ap.add_argument("--slots", action="store_true")
     ap.add_argument("--paged", action="store_true")
     ap.add_argument("--paged-h16", action="store_true")
+    ap.add_argument("--packed", action="store_true")
+    ap.add_argument("--existing-only", action="store_true")
     a = ap.parse_args()
-    if a.paged_h16:
+    if a.packed:
+        for B in (8, 32):
+            packed_config(B, 4, 128, 256, max(100, a.steps), a.reps, existing_only=a.existing_only)
+    elif a.paged_h16:
         for B in (4, 32):
             paged_config(B, 4, 128, 256, max(200, a.steps), a.reps, h16=True)
     elif a.paged:
