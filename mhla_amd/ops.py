@@ -1693,21 +1693,8 @@ class CausalStateView(CausalState):
     def fork(self, src, dst):
         raise ValueError("CausalState.fork: slots are forked on the pool, not on a view of it")
 
-    def _part(self, i, j) -> "_SlotPart":
-        return _SlotPart(self.pool, self.map[i:j])
-
     def __repr__(self):
         return f"CausalStateView(slots={self.slots if self.slots is not None else 'on the device'}, B={self.rows}, of {self.pool!r})"
-
-
-class _SlotPart:
-    """Rows [i, j) of a view, as a launch takes them: the pool's tensors and that piece of the map."""
-
-    __slots__ = ("S", "P", "Cur", "chunk_size", "map", "dims")
-    pages = page_mult = None
-
-    def __init__(self, pool, map_):
-        self.S, self.P, self.Cur, self.chunk_size, self.map, self.dims = pool.S, pool.P, pool.Cur, pool.chunk_size, map_, pool.dims
 
 
 def _state_rows(state) -> int:
@@ -2020,21 +2007,8 @@ class PagedStateView(CausalStateView):
 
     clone = compact
 
-    def _part(self, i, j) -> "_PagePart":
-        return _PagePart(self.pool, self.map[i:j])
-
     def __repr__(self):
         return f"PagedStateView(slots={self.slots if self.slots is not None else 'on the device'}, B={self.rows}, of {self.pool!r})"
-
-
-class _PagePart:
-    """Rows [i, j) of a view of a paged pool, as a launch takes them: the pool's tensors and that piece of the map."""
-
-    __slots__ = ("pages", "page_mult", "table_dev", "P", "Cur", "chunk_size", "map", "dims")
-
-    def __init__(self, pool, map_):
-        self.pages, self.page_mult, self.table_dev, self.P, self.Cur = pool.pages, pool.page_mult, pool.table_dev, pool.P, pool.Cur
-        self.chunk_size, self.map, self.dims = pool.chunk_size, map_, pool.dims
 
 
 def _refuse_paged_pool(fn, state):
@@ -2050,11 +2024,12 @@ def _refuse_h16(fn, state):
                                   "prefill (mhla_causal_state(..., into=view)) run on them; extend, verify and commit need an fp32 pool")
 
 
-def _assign_pages(fn, state, n_after, fresh=False):
-    """The page rule of a host-positioned call on a view of a paged pool (`PagedCausalState`): after every refusal, before the first
-    launch.  Any other state (`state.pages is None`, which the callers on a hot path test themselves): nothing."""
+def _page_rule(fn, state, counts):
+    """The page rule of a host-positioned call that adds `counts[b]` tokens to sequence b of a view of a paged pool
+    (`PagedCausalState`): after every refusal, before the first launch.  Any other state (`state.pages is None`, which the callers
+    on a hot path test themselves): nothing."""
     if state.pages is not None:
-        state.pool._assign(fn, state.slots, n_after, fresh)
+        state.pool._assign(fn, state.slots, [p + n for p, n in zip(state.lengths, counts)])
 
 
 def _int_tuple(fn, name, xs, B, hi):
@@ -2081,53 +2056,95 @@ def _runs(lengths, nb):
         i = j
 
 
-def _state_slice(state: CausalState, i, j) -> CausalState:
-    """`state` for its sequences [i, j): views of S, P, Cur (what a launch reads of a state besides its sizes), or -- all of them,
-    the usual case -- the state itself, with no views to build."""
-    if i == 0 and j == _state_rows(state):
-        return state
-    if isinstance(state, CausalStateView):   # (the pool's tensors and that piece of the slot map)
-        return state._part(i, j)
-    return CausalState(state.S[i:j], state.P[i:j], state.Cur[i:j], 0, 64)
+class _StateRows:
+    """Rows [i, j) of a state as a launch takes them -- the one form for every kind.  A state of its own: views of S, P, Cur and no
+    slot map.  A view of a pool, dense or paged: the pool's tensors whole and that piece of the view's slot map."""
+
+    __slots__ = ("S", "pages", "page_mult", "table_dev", "P", "Cur", "chunk_size", "map", "dims")
+
+    def __init__(self, state, i, j):
+        pool = getattr(state, "pool", None)
+        self.chunk_size, self.dims = state.chunk_size, state.dims
+        if pool is None:
+            self.S, self.P, self.Cur, self.map = state.S[i:j], state.P[i:j], state.Cur[i:j], None
+            self.pages = self.page_mult = self.table_dev = None
+        else:
+            self.S, self.P, self.Cur, self.map = pool.S, pool.P, pool.Cur, state.map[i:j]
+            self.pages, self.page_mult, self.table_dev = pool.pages, pool.page_mult, getattr(pool, "table_dev", None)
+
+
+def _rows_of(state, i, j, *along):
+    """What one launch chain takes of a call's per-sequence objects when it serves sequences [i, j) only: (`_StateRows`, x[i:j] for
+    every x of `along`).  A view of a pool: its slot map is sliced with the tokens, while the pool's `pos` and `full`, which the
+    launches address through the map, pass whole."""
+    pooled = (state.pos, state._full) if isinstance(state, CausalStateView) else ()
+    return (_StateRows(state, i, j),) + tuple(x if any(x is t for t in pooled) else x[i:j] for x in along)
 
 
 def _batch_slices(state: CausalState, nb, prepared=None, *along):
     """One launch addresses `nb` sequences (`_MAX_GRID_BH // H`; batches beyond that range: see mhla_blockmix).  Yields, for every
-    batch slice [i, j) of at most `nb`: (`_state_slice`, `prepared.part(i, j)`, x[i:j] for every x of `along`).  B <= nb, the usual
-    case, is one launch chain on the objects themselves.  A view of a pool: its slot map is sliced with the tokens (`_state_slice`),
-    while the pool's `pos` and `full`, which the launches address through the map, pass whole."""
+    batch slice [i, j) of at most `nb`: (`_StateRows`, `prepared.part(i, j)`, x[i:j] for every x of `along`: `_rows_of`).  B <= nb,
+    the usual case, is one launch chain on the objects themselves."""
     B = _state_rows(state)
     if B <= nb:
         yield (state, prepared) + along
         return
-    pooled = (state.pos, state._full) if isinstance(state, CausalStateView) else ()
     for i in range(0, B, nb):
         j = min(B, i + nb)
-        yield (_state_slice(state, i, j), prepared.part(i, j) if prepared is not None else None) + tuple(
-            x if any(x is t for t in pooled) else x[i:j] for x in along)
+        rows = _rows_of(state, i, j, *along)
+        yield (rows[0], prepared.part(i, j) if prepared is not None else None) + rows[1:]
 
 
 def _run_slices(state: CausalState, lengths, nb):
-    """`_batch_slices` cut further where adjacent lengths differ: (i, j, the length, `_state_slice`) of every run of `_runs`."""
+    """`_batch_slices` cut further where adjacent lengths differ: (i, j, the length, the state's rows) of every run of `_runs`; a run
+    that is the whole batch: the state itself."""
     for i, j, n in _runs(lengths, nb):
-        yield i, j, n, _state_slice(state, i, j)
+        yield i, j, n, state if j - i == len(lengths) else _StateRows(state, i, j)
 
 
-def _state_head(mixf, state: CausalState):
-    """The arguments every decode entry point of the library takes after its token views: the mixing matrix with its leading
-    dimension, then S with the capacity, P, Cur."""
-    pages = state.pages
-    if pages is not None:   # a view of a paged pool, or a batch slice of one: (pages, n_pages, table_dev) where S stands
-        mult = state.page_mult   # (h16 pages: the multipliers follow the payload)
-        return (mixf.data_ptr(), mixf.shape[1], pages.data_ptr(), *(() if mult is None else (mult.data_ptr(),)), pages.shape[0],
-                state.table_dev.data_ptr(), state.dims[2], state.P.data_ptr(), state.Cur.data_ptr())
-    return mixf.data_ptr(), mixf.shape[1], state.S.data_ptr(), state.S.shape[2], state.P.data_ptr(), state.Cur.data_ptr()
+# The library's entry point for every kind of decode call (the key) by the kind of state: a state of its own, a view of a dense pool,
+# of a pool of fp32 pages, of a pool of h16 pages (None: there is none, and the call was refused on its way here).  Last, how the first
+# takes the heads: H alone (False), H alone with a grouped-query twin `_gqa` that takes H, Hkv (True: `_gqa_call` picks), or H, Hkv
+# like every entry point for a view (None).
+_ENTRY = {
+    "state_init": ("mhla_causal_state_init", None, None, None, False),
+    "prefill": ("mhla_causal_varlen_state_init", "mhla_causal_varlen_state_init_slots", "mhla_causal_varlen_state_init_paged",
+                "mhla_causal_varlen_state_init_paged_h16", False),
+    "step_uniform": ("mhla_causal_step", None, None, None, False),
+    "extend_uniform": ("mhla_causal_extend", None, None, None, False),
+    "step": ("mhla_causal_step_ragged", "mhla_causal_step_slots", "mhla_causal_step_paged", "mhla_causal_step_paged_h16", True),
+    "step_dev": ("mhla_causal_step_dev", "mhla_causal_step_dev_slots", "mhla_causal_step_dev_paged", "mhla_causal_step_dev_paged_h16", True),
+    "extend": ("mhla_causal_extend_ragged", "mhla_causal_extend_slots", "mhla_causal_extend_paged", None, True),
+    "verify": ("mhla_causal_verify_ragged", "mhla_causal_verify_slots", "mhla_causal_verify_paged", None, True),
+    "commit": ("mhla_causal_commit_ragged", "mhla_causal_commit_slots", "mhla_causal_commit_paged", None, False),
+    "extend_packed": ("mhla_causal_extend_packed", "mhla_causal_extend_packed", "mhla_causal_extend_packed", None, None),
+    "verify_packed": ("mhla_causal_verify_packed", "mhla_causal_verify_packed", "mhla_causal_verify_packed", None, None),
+    "commit_packed": ("mhla_causal_commit_packed", "mhla_causal_commit_packed", "mhla_causal_commit_packed", None, False),
+}
 
 
-def _pool_call(name: str, state) -> str:
-    """The entry point that runs the slotted call `name` (mhla_causal_*_slots) on `state`: itself, its paged namesake, or that one's
-    form on h16 pages."""
-    return name if state.pages is None else name[:-len("_slots")] + ("_paged" if state.page_mult is None else "_paged_h16")
+def _state_args(call, mixf, state, pos=(), packed=False):
+    """The one place that tells the kinds of state apart for the library: (the entry point of `call`, a key of `_ENTRY`, for this
+    state; how it takes the heads, `_ENTRY`'s last column; the state's part of its argument list, in its order).  `state`: a state,
+    a view, or `_StateRows` of either.  `pos`: what the entry point takes between Cur and the slot map, its positions last.
+    Padded:  mix, ldmix, S | pages, n_pages, table | pages, page_mult, n_pages, table; capacity, P, Cur, *pos; a view: slot map, n_slots.
+    Packed (one entry point for every kind): mix, ldmix, S, 0, null | pages, n_pages, table; capacity, P, Cur, *pos, slot map | null, n_slots | 0."""
+    row = _ENTRY[call]
+    slot = getattr(state, "map", None)
+    if slot is None:   # (a state of its own, the usual call, spelt out: this is on the path of every step)
+        S = state.S
+        if packed:
+            return row[0], None, (mixf.data_ptr(), mixf.shape[1], S.data_ptr(), 0, None, S.shape[2], state.P.data_ptr(), state.Cur.data_ptr(), *pos, None, 0)
+        return row[0], row[4], (mixf.data_ptr(), mixf.shape[1], S.data_ptr(), S.shape[2], state.P.data_ptr(), state.Cur.data_ptr(), *pos)
+    pages, mult = state.pages, state.page_mult
+    if pages is None:
+        name, chunks = row[1], (state.S.data_ptr(), 0, None) if packed else (state.S.data_ptr(),)
+    elif mult is None:
+        name, chunks = row[2], (pages.data_ptr(), pages.shape[0], state.table_dev.data_ptr())
+    else:   # (h16 pages: the multipliers follow the payload)
+        name, chunks = row[3], (pages.data_ptr(), mult.data_ptr(), pages.shape[0], state.table_dev.data_ptr())
+    dims = state.dims
+    return name, None, (mixf.data_ptr(), mixf.shape[1], *chunks, dims[2], state.P.data_ptr(), state.Cur.data_ptr(), *pos, slot.data_ptr(), dims[0])
 
 
 @functools.lru_cache(maxsize=64)
@@ -2153,9 +2170,9 @@ def _causal_state_init(k, v, mix, state: CausalState):
     B, T, H, K = k.shape
     k, v = _prep(k), _prep(v)
     mixf = _mix2d(mix)
-    rc = lib.mhla_causal_state_init(_view(k), _view(v), *_state_head(mixf, state), B, T, H, K, v.shape[-1], state.chunk_size,
-                                    _dtype_code(k), _stream())
-    _lib.check(rc, "mhla_causal_state_init")
+    name, _, head = _state_args("state_init", mixf, state)
+    rc = getattr(lib, name)(_view(k), _view(v), *head, B, T, H, K, v.shape[-1], state.chunk_size, _dtype_code(k), _stream())
+    _lib.check(rc, name)
 
 
 def mhla_causal_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, chunk_size: int = 64,
@@ -2252,17 +2269,14 @@ def _causal_state_init_pack(k, v, mix, state: CausalState, plan: CausalVarlenPla
     _, T, H, K = k.shape
     k, v = _prep(k), _prep(v)
     mixf = _mix2d(mix)
-    slot = getattr(state, "map", None)
-    name, where = (("mhla_causal_varlen_state_init", ()) if slot is None else
-                   (_pool_call("mhla_causal_varlen_state_init_slots", state), (slot.data_ptr(), state.dims[0])))
+    name, _, head = _state_args("prefill", mixf, state, (len(plan.lengths), seq_len.data_ptr()))
     ws = ()
     if state.page_mult is not None:   # h16 pages: the chunks' fp32 K^T V are staged, in slices of the chunk list beyond the cap
         V, dt = v.shape[-1], _dtype_code(k)
         need = lib.mhla_causal_varlen_state_init_paged_h16_ws_bytes(plan.n_chunks, H, K, V, dt)
         buf = _ws(min(need, max(EXTEND_WS_CAP_BYTES, lib.mhla_causal_varlen_state_init_paged_h16_ws_bytes(1, H, K, V, dt))), k.device)
         ws = (buf.data_ptr(), buf.numel() * 4)
-    rc = getattr(lib, name)(_view(k), _view(v), *_state_head(mixf, state), len(plan.lengths), seq_len.data_ptr(), *where,
-                            max(plan.lengths), T, H, K, v.shape[-1], state.chunk_size, plan.n_chunks,
+    rc = getattr(lib, name)(_view(k), _view(v), *head, max(plan.lengths), T, H, K, v.shape[-1], state.chunk_size, plan.n_chunks,
                             plan.table.data_ptr(), plan.dst.data_ptr(), *ws, _dtype_code(k), _stream())
     _lib.check(rc, name)
 
@@ -2295,7 +2309,8 @@ def mhla_causal_state(k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Ten
             with torch.no_grad():
                 seq_len = torch.tensor(plan.lengths, dtype=torch.int32).to(k.device)   # the one small copy of the call
                 idx = into.map.to(torch.int64)
-                _assign_pages("mhla_causal_state", into, plan.lengths, fresh=True)   # (a paged pool: before anything changes)
+                if into.pages is not None:   # (a paged pool: the slots start anew, their pages released first; before anything changes)
+                    pool._assign("mhla_causal_state", into.slots, plan.lengths, True)
                 if T:
                     _causal_state_init_pack(k.detach(), v.detach(), mixing_matrix, into, plan, seq_len)
                 else:   # (an all-empty pack launches nothing: empty slots)
@@ -2408,7 +2423,8 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
     B, T, H, K = q.shape
     V = v.shape[-1]
     Hk = k.shape[2]   # grouped-query heads: k, v and the state have Hkv heads, q, gate and the rows H = G Hkv
-    cap = state.capacity_chunks
+    dims = state.dims
+    nrow, cap = dims[0], dims[2]   # the state's batch rows (B, or -- a view -- the slots of the pool, B of which the call selects); its capacity
     _kv_group(fn, H, Hk)
     try:
         _check_like(q, fn, k=(k, (B, T, Hk, K)), v=(v, (B, T, Hk, V)), gate=(gate, (B, T, H, V)))
@@ -2418,9 +2434,8 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
         B = seqs
     if q.dtype not in _DTYPES:
         raise ValueError(f"{fn}: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
-    dims, chunks = state.dims, state._chunks
-    nrow = dims[0]   # the state's batch rows: B, or -- a view -- the slots of the pool, B of which the call selects
-    if _state_rows(state) != B or dims != (nrow, Hk, cap, K, V) or tuple(state.P.shape) != (nrow, Hk, K, V) or tuple(state.Cur.shape) != (nrow, Hk, K, V):
+    chunks = state._chunks
+    if (state.rows if isinstance(state, CausalStateView) else nrow) != B or dims != (nrow, Hk, cap, K, V) or tuple(state.P.shape) != (nrow, Hk, K, V) or tuple(state.Cur.shape) != (nrow, Hk, K, V):
         raise ValueError(f"{fn}: state is {state!r}, the {'token has' if T == 1 else 'tokens have'} B={B} H={H if Hk == H else Hk} K={K} V={V}"
                          + ("" if Hk == H else f" (k/v heads; q has {H})"))
     dev = q.device
@@ -2467,31 +2482,24 @@ def _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight,
     return tuple.__new__(_Prepared, (q, k, v, gate, _mix2d(mixing_matrix), wf, pos, scale, want_y))
 
 
-# the entry point that runs a ragged call on chosen slots of a pool (a `CausalStateView`)
-_SLOT_CALLS = {"mhla_causal_step_ragged": "mhla_causal_step_slots", "mhla_causal_step_dev": "mhla_causal_step_dev_slots",
-               "mhla_causal_extend_ragged": "mhla_causal_extend_slots", "mhla_causal_verify_ragged": "mhla_causal_verify_slots"}
-
-
 @_device_guard
-def _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, name, twin, state, middle, ws_bytes, res, norm_eps):
-    """The one library call of the decode entry points that compute rows: `name` on what `_decode_prepare` returned (the first
-    eight arguments; the guard finds its tensor at once), for the sequences `state` -- the batch or a slice of it -- holds.  All
-    of them take the token views and `_state_head`, then arguments of their own (`middle`), then one tail: the rows into `res` (through the norm x gate epilogue with `want_y`), a
-    workspace of `ws_bytes`, the sizes, scale, dtype and stream.  `twin`: the entry point has a grouped-query form, which
-    `_gqa_call` picks when k, v and the state have fewer heads than q."""
+def _launch_rows(q, k, v, gate, mixf, wf, scale, want_y, call, state, pos, middle, ws_bytes, res, norm_eps, B, packed=False):
+    """The one library call of the decode entry points that compute rows: `call` (a key of `_ENTRY`) on what `_decode_prepare`
+    returned (the first eight arguments; the guard finds its tensor at once), for the sequences `state` -- the batch or a slice of it
+    -- holds.  All of them take the token views and the state's part (`_state_args`, with the positions `pos`), then arguments of
+    their own (`middle`), then one tail: the rows into `res` (through the norm x gate epilogue with `want_y`), a workspace of
+    `ws_bytes`, the sizes (`B` sequences), scale, dtype and stream.  `packed`: the tokens are one row [1, N, ...] -- views with a zero
+    batch stride (`_view0`) and the packed form of the state's part; that is all the difference."""
     lib = _lib.load()
-    B, _, H, K = q.shape
-    call, heads = _gqa_call(lib, name, H, k.shape[2]) if twin else (getattr(lib, name), (H,))
-    slot = getattr(state, "map", None)
-    if slot is not None:   # a view of a pool, or a batch slice of one: the slotted namesake -- the map after the positions, Hkv after H
-        name = _pool_call(_SLOT_CALLS[name], state)
-        call, heads, middle = getattr(lib, name), (H, k.shape[2]), (middle[0], slot.data_ptr(), state.dims[0], *middle[1:])
+    _, _, H, K = q.shape
+    view = _view0 if packed else _view
+    name, twin, head = _state_args(call, mixf, state, pos, packed)
+    fn, heads = _gqa_call(lib, name, H, k.shape[2]) if twin else (getattr(lib, name), (H,) if twin is False else (H, k.shape[2]))
     ws = _ws(ws_bytes, q.device)
     # (the two optional arguments spelt out, not through `_view_or_null` / `_ptr`: two Python calls on a host-bound path)
-    rc = call(_view(q), _view(k), _view(v), *_state_head(mixf, state), *middle, NULL_VIEW if want_y else _view(res),
-              _view(gate) if gate is not None else NULL_VIEW, wf.data_ptr() if wf is not None else None, float(norm_eps),
-              _view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4, B, *heads, K, v.shape[-1], state.chunk_size,
-              float(scale), _DTYPES[q.dtype], _stream())
+    rc = fn(view(q), view(k), view(v), *head, *middle, NULL_VIEW if want_y else view(res), view(gate) if gate is not None else NULL_VIEW,
+            wf.data_ptr() if wf is not None else None, float(norm_eps), view(res) if want_y else NULL_VIEW, ws.data_ptr(), ws.numel() * 4,
+            B, *heads, K, v.shape[-1], state.chunk_size, float(scale), _DTYPES[q.dtype], _stream())
     _lib.check(rc, name)
 
 
@@ -2501,19 +2509,18 @@ def _causal_decode(q, k, v, gate, mixf, wf, pos, scale, want_y, state, res, norm
     B, T, H, K = q.shape
     V, dt = v.shape[-1], _DTYPES[q.dtype]
     if extend:
-        name, middle, ws_bytes = "mhla_causal_extend", (pos, T), _lib.load().mhla_causal_extend_ws_bytes(B, T, H, K, V, pos, dt)
+        call, middle, ws_bytes = "extend_uniform", (pos, T), _lib.load().mhla_causal_extend_ws_bytes(B, T, H, K, V, pos, dt)
     else:
-        name, middle, ws_bytes = "mhla_causal_step", (pos,), _step_ws_bytes(B, H, K, V, dt)
-    _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, name, False, state, middle, ws_bytes, res, norm_eps)
+        call, middle, ws_bytes = "step_uniform", (pos,), _step_ws_bytes(B, H, K, V, dt)
+    _launch_rows(q, k, v, gate, mixf, wf, scale, want_y, call, state, (), middle, ws_bytes, res, norm_eps, B)
 
 
 def _causal_step_ragged(q, k, v, gate, mixf, wf, _, scale, want_y, state, pos, lengths, res, norm_eps):
     """One launch chain of `mhla_causal_step_ragged` on what `_decode_prepare` returned, for the sequences `state` (a batch slice)
     holds: `pos` their device positions, which the chain advances, `lengths` the host mirror of the same numbers."""
     B, _, H, K = q.shape
-    _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, "mhla_causal_step_ragged", True, state,
-                   (pos.data_ptr(), max(lengths), int(any(n % 64 == 63 for n in lengths))),
-                   _step_ws_bytes(B, H, K, v.shape[-1], _DTYPES[q.dtype]), res, norm_eps)
+    _launch_rows(q, k, v, gate, mixf, wf, scale, want_y, "step", state, (pos.data_ptr(),),
+                 (max(lengths), int(any(n % 64 == 63 for n in lengths))), _step_ws_bytes(B, H, K, v.shape[-1], _DTYPES[q.dtype]), res, norm_eps, B)
 
 
 def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
@@ -2549,7 +2556,7 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
     nb = _MAX_GRID_BH // H
     # What the library checks per launch, for every slice before the first launch (a refusal after an earlier slice had run would
     # leave its device positions ahead of `lengths`): a slice with a sequence on a boundary needs the row after its furthest
-    # sequence's chunk, unless that chunk is the state's last.  (Not `_ragged_slices` with counts of one, which asks for less.)
+    # sequence's chunk, unless that chunk is the state's last.  (Not `_slices` with counts of one, which asks for less.)
     cols = prepared.mixf.shape[1]
     for i in range(0, B, nb):
         part = lengths[i:i + nb]
@@ -2557,8 +2564,8 @@ def mhla_causal_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_m
         if cols < need:
             raise IndexError(f"mhla_causal_step: a sequence of lengths {part} closes its chunk: row {need - 1} of mixing_matrix is read, "
                              f"which has only {cols} columns")
-    if state.pages is not None:
-        _assign_pages("mhla_causal_step", state, [n + 1 for n in lengths])
+    if state.pages is not None:   # (the page rule, `_page_rule`, on the lengths already at hand)
+        state.pool._assign("mhla_causal_step", state.slots, [n + 1 for n in lengths])
     for part, p, pos_, lengths_, out in _batch_slices(state, nb, prepared, pos, lengths, res):
         _causal_step_ragged(*p, part, pos_, lengths_, out, norm_eps)
     if state.lengths is not None:
@@ -2572,8 +2579,8 @@ def _causal_step_dev(q, k, v, gate, mixf, wf, _, scale, want_y, state, pos, full
     holds; `rotary`: the tables as the library takes them, (cos, sin, row stride, rows), nulls and zeros without.  Nothing here reads
     a position or synchronises: legal under stream capture."""
     B, _, H, K = q.shape
-    _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, "mhla_causal_step_dev", True, state,
-                   (pos.data_ptr(), full.data_ptr(), *rotary, fmap), _step_ws_bytes(B, H, K, v.shape[-1], _DTYPES[q.dtype]), res, norm_eps)
+    _launch_rows(q, k, v, gate, mixf, wf, scale, want_y, "step_dev", state, (pos.data_ptr(),), (full.data_ptr(), *rotary, fmap),
+                 _step_ws_bytes(B, H, K, v.shape[-1], _DTYPES[q.dtype]), res, norm_eps, B)
 
 
 def mhla_causal_step_dev(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing_matrix: torch.Tensor, state: CausalState, *,
@@ -2641,18 +2648,34 @@ def mhla_causal_step_dev(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixi
 EXTEND_WS_CAP_BYTES = 256 << 20
 
 
-def _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, scale, gate, norm_weight, epilogue):
-    """What a call with per-sequence `counts` (`mhla_causal_extend(counts=)`, `mhla_causal_verify`) checks, in the order callers rely
-    on, before anything is launched or `state` is touched; returns (counts as a tuple, what `_decode_prepare` returns)."""
-    B, T = q.shape[:2]
-    counts = _int_tuple(fn, "counts", counts, B, T)
+def _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, left_padded, cu_seqlens, scale, gate, norm_weight, epilogue):
+    """What a call with per-sequence token counts checks, in the order callers rely on, before anything is launched or `state` is
+    touched: the counts given (`mhla_causal_extend(counts=)`, `mhla_causal_verify`; padded tokens [B, T, ...]) or those of packed new
+    tokens (`cu_seqlens=`; one row [1, N, ...], which says nothing about the number of sequences).  Returns (cu as a tuple, or None
+    without `cu_seqlens`; every sequence's token count; what `_decode_prepare` returns)."""
+    if cu_seqlens is None:
+        cu, B = None, q.shape[0]
+        counts = _int_tuple(fn, "counts", counts, B, q.shape[1])
+    else:
+        if counts is not None or left_padded:
+            raise ValueError(f"{fn}: cu_seqlens (packed new tokens) excludes counts and left_padded, which place windows in padded tensors")
+        if q.shape[0] != 1:
+            raise ValueError(f"{fn}: cu_seqlens takes one packed row (B = 1), got B = {q.shape[0]}")
+        cu = _cu_host(cu_seqlens.cu if isinstance(cu_seqlens, CausalVarlenPlan) else cu_seqlens)   # (of a plan: its host `cu` alone)
+        if cu[-1] != q.shape[1]:
+            raise ValueError(f"{fn}: cu_seqlens ends at {cu[-1]}, the pack has N = {q.shape[1]} tokens")
+        B = len(cu) - 1
     if state.lengths is None:
-        raise ValueError(f"{fn}: counts needs a ragged state and this one is uniform ({state!r}); the positions must live on the "
-                         "device: pass state.to_ragged()")
+        raise ValueError(f"{fn}: {'counts' if cu is None else 'cu_seqlens'} needs a ragged state and this one is uniform ({state!r}); the "
+                         "positions must live on the device: pass state.to_ragged()")
     if len(state.lengths) != B:
-        raise ValueError(f"{fn}: the state holds {len(state.lengths)} sequences, the tokens B={B}")
+        raise ValueError(f"{fn}: the state holds {len(state.lengths)} sequences, "
+                         + (f"the tokens B={B}" if cu is None else f"cu_seqlens has {len(cu)} entries ({B} sequences)"))
+    if cu is not None:
+        counts = tuple([b - a for a, b in zip(cu, cu[1:])])
     _counts_fit(fn, mixing_matrix, state, counts)
-    return counts, _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=False)
+    return cu, counts, _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=False,
+                                       seqs=None if cu is None else B)
 
 
 def _counts_fit(fn, mixing_matrix, state, counts):
@@ -2662,6 +2685,8 @@ def _counts_fit(fn, mixing_matrix, state, counts):
         raise ValueError(f"mixing_matrix must be [L, L(, 1, 1, 1, 1)], got {tuple(mixing_matrix.shape)}")
     L, cap = mixing_matrix.shape[0], state.capacity_chunks
     need = [(p + n + 63) // 64 if n else 0 for p, n in zip(state.lengths, counts)]
+    if max(need, default=0) <= min(L, cap):   # (the usual call: no words to put together)
+        return
     for limit, what in ((L, f"mixing_matrix has only {L} rows"), (cap, f"the state holds only {cap}")):
         over = [b for b, c in enumerate(need) if c > limit]
         if over:
@@ -2675,76 +2700,43 @@ def _ragged_plan(lengths, counts, cap):
     live = [(p, n) for p, n in zip(lengths, counts) if n]
     if not live:
         return 0, 0, False, 0
-    max_end = max(p + n for p, n in live)
-    max_later = max((p + n - 1) // 64 - p // 64 for p, n in live)
-    any_close = any(p % 64 + n >= 64 for p, n in live)
+    # (lists, not generators: a handful of sequences, on the path of every extend, verify and commit)
+    max_end = max([p + n for p, n in live])
+    max_later = max([(p + n - 1) // 64 - p // 64 for p, n in live])
+    any_close = any([p % 64 + n >= 64 for p, n in live])
     return max_end, max_later, any_close, (min(max_end // 64, cap - 1) if any_close else (max_end - 1) // 64)
-
-
-def _ragged_slices(fn, state, counts, H, mixf):
-    """The batch slices of one ragged call, (first, end, `_ragged_plan`) each, after what the library checks per launch was checked
-    for every slice before the first launch (see mhla_causal_step)."""
-    B = len(counts)
-    nb = min(B, _MAX_GRID_BH // H)
-    slices = [(i, min(B, i + nb), _ragged_plan(state.lengths[i:i + nb], counts[i:i + nb], state.capacity_chunks)) for i in range(0, B, nb)]
-    for i, j, plan in slices:
-        if plan[0] and mixf.shape[1] < plan[3] + 1:
-            raise IndexError(f"{fn}: sequences {list(range(i, j))} (lengths {state.lengths[i:j]}, counts {counts[i:j]}): row {plan[3]} of "
-                             f"mixing_matrix is read, which has only {mixf.shape[1]} columns")
-    return slices
-
-
-def _causal_extend_ragged(q, k, v, gate, mixf, wf, _, scale, want_y, state, pos, ntok, plan, left_padded, res, norm_eps,
-                          fn="mhla_causal_extend_ragged"):
-    """One launch chain of `mhla_causal_extend_ragged` on what `_decode_prepare` returned, for the sequences `state` (a batch slice)
-    holds: `pos` their device positions, which the chain advances, `ntok` their token counts on the device, `plan` the host
-    values of `_ragged_plan`.  fn="mhla_causal_verify_ragged": the same arguments and rows, nothing committed."""
-    B, T, H, K = q.shape
-    max_end, max_later, any_close, _ = plan
-    ws_bytes = _extend_ragged_ws_bytes(_lib.load(), B, T, H, k.shape[2], K, v.shape[-1], max_later, _DTYPES[q.dtype])
-    _decode_launch(q, k, v, gate, mixf, wf, scale, want_y, fn, True, state,
-                   (pos.data_ptr(), ntok.data_ptr(), T, max_end, max_later, int(any_close), int(bool(left_padded))), ws_bytes, res, norm_eps)
-
-
-def _ragged_chains(fn, prepared, state, slices, counts, left_padded, res, norm_eps):
-    """`_causal_extend_ragged` (`fn`: the entry point, extend or verify) once per batch slice of `_ragged_slices`."""
-    ntok = torch.tensor(counts, dtype=torch.int32).to(res.device)   # the one small copy of the call
-    # (`slices[0][1]`, the first slice's end, is the width `_ragged_slices` cut at)
-    for (_, _, plan), (part, p, pos, ntok_, out) in zip(slices, _batch_slices(state, slices[0][1], prepared, state.pos, ntok, res)):
-        _causal_extend_ragged(*p, part, pos, ntok_, plan, left_padded, out, norm_eps, fn)
 
 
 # ---- packed new tokens (`cu_seqlens=` of extend and verify, the draft's `cu` of a commit): the tokens of all sequences in one row
 _PACK_MAX_TOKENS = 65535   # tokens of one library call: its last launch puts them on a grid dimension
 
 
-def _packed_prepare(fn, q, k, v, mixing_matrix, state, cu_seqlens, counts, left_padded, scale, gate, norm_weight, epilogue):
-    """What a call with packed new tokens (`cu_seqlens=`) checks, in the order of `_counts_prepare`, before anything is launched or
-    `state` is touched; returns (cu as a tuple, every sequence's token count, what `_decode_prepare` returns)."""
-    if counts is not None or left_padded:
-        raise ValueError(f"{fn}: cu_seqlens (packed new tokens) excludes counts and left_padded, which place windows in padded tensors")
-    if q.shape[0] != 1:
-        raise ValueError(f"{fn}: cu_seqlens takes one packed row (B = 1), got B = {q.shape[0]}")
-    cu = _cu_host(cu_seqlens.cu if isinstance(cu_seqlens, CausalVarlenPlan) else cu_seqlens)   # (of a plan: its host `cu` alone)
-    if cu[-1] != q.shape[1]:
-        raise ValueError(f"{fn}: cu_seqlens ends at {cu[-1]}, the pack has N = {q.shape[1]} tokens")
-    if state.lengths is None:
-        raise ValueError(f"{fn}: cu_seqlens needs a ragged state and this one is uniform ({state!r}); the positions must live on the "
-                         "device: pass state.to_ragged()")
-    B = len(cu) - 1
-    if len(state.lengths) != B:
-        raise ValueError(f"{fn}: the state holds {len(state.lengths)} sequences, cu_seqlens has {len(cu)} entries ({B} sequences)")
-    counts = tuple(b - a for a, b in zip(cu, cu[1:]))
-    _counts_fit(fn, mixing_matrix, state, counts)
-    return cu, counts, _decode_prepare(fn, q, k, v, mixing_matrix, state, scale, gate, norm_weight, epilogue, positioned=False, seqs=B)
+def _slices(fn, state, counts, H, mixf, cu=None, ws_dims=None, rows=False):
+    """The launch chains of one call with per-sequence `counts`, (first sequence, end, `_ragged_plan`) each, after what the library
+    checks per launch was checked for every one of them before the first launch (see mhla_causal_step): the columns of the matrix and
+    -- `rows`, a commit, whose `counts` are the accepted ones and have not been held against the matrix -- its rows.
+    Padded tokens: batch slices of one launch's (b, h) range, `_MAX_GRID_BH // H` sequences.  Packed (`cu`): `_packed_cut`."""
+    B, lengths = len(counts), state.lengths
+    if cu is None:
+        nb, cap = min(B, _MAX_GRID_BH // H), state.capacity_chunks
+        slices = [(i, min(B, i + nb), _ragged_plan(lengths[i:i + nb], counts[i:i + nb], cap)) for i in range(0, B, nb)]
+    else:
+        slices = _packed_cut(fn, state, cu, counts, H, ws_dims)
+    for i, j, plan in slices:
+        if plan[0] and mixf.shape[1] < plan[3] + 1:
+            raise IndexError(f"{fn}: sequences {list(range(i, j))} (lengths {lengths[i:j]}, counts {counts[i:j]}): row {plan[3]} of "
+                             f"mixing_matrix is read, which has only {mixf.shape[1]} columns")
+    if rows and any(plan[0] and mixf.shape[0] < plan[3] + 1 for _, _, plan in slices):
+        raise IndexError(f"{fn}: mixing_matrix has only {mixf.shape[0]} rows, fewer than the accepted tokens read (lengths "
+                         f"{lengths}, accept {counts})")
+    return slices
 
 
-def _packed_slices(fn, state, cu, counts, H, mixf, ws_dims=None):
-    """The launch chains of one packed call, (first sequence, end, `_ragged_plan` of `counts`) each: the whole pack, or -- beyond
-    `_PACK_MAX_TOKENS`, one launch's (b, h) range (`_MAX_GRID_BH // H`) or, with `ws_dims` = (H, Hkv, K, V, dtype code) of a call
-    that computes rows, `EXTEND_WS_CAP_BYTES` -- consecutive runs of whole sequences, each as long as fits.  Sequences are
-    independent, so a cut changes no bit; there is no cut inside a sequence: one that alone exceeds a limit is a ValueError.  Then
-    `_ragged_slices`' check of the matrix's columns; all of it before the first launch."""
+def _packed_cut(fn, state, cu, counts, H, ws_dims):
+    """Where a pack is cut: the whole pack, or -- beyond `_PACK_MAX_TOKENS`, one launch's (b, h) range (`_MAX_GRID_BH // H`) or, with
+    `ws_dims` = (H, Hkv, K, V, dtype code) of a call that computes rows, `EXTEND_WS_CAP_BYTES` -- consecutive runs of whole sequences,
+    each as long as fits.  Sequences are independent, so a cut changes no bit; there is no cut inside a sequence: one that alone
+    exceeds a limit is a ValueError."""
     B, cap, nb = len(counts), state.capacity_chunks, max(1, _MAX_GRID_BH // H)
     lib = _lib.load()
 
@@ -2772,11 +2764,29 @@ def _packed_slices(fn, state, cu, counts, H, mixf, ws_dims=None):
                 j += 1
         slices.append((i, j, _ragged_plan(state.lengths[i:j], counts[i:j], cap)))
         i = j
-    for i, j, plan in slices:
-        if plan[0] and mixf.shape[1] < plan[3] + 1:
-            raise IndexError(f"{fn}: sequences {list(range(i, j))} (lengths {state.lengths[i:j]}, counts {counts[i:j]}): row {plan[3]} of "
-                             f"mixing_matrix is read, which has only {mixf.shape[1]} columns")
     return slices
+
+
+def _causal_extend_ragged(q, k, v, gate, mixf, wf, _, scale, want_y, state, pos, ntok, plan, left_padded, res, norm_eps, call="extend"):
+    """One launch chain of `mhla_causal_extend_ragged` on what `_decode_prepare` returned, for the sequences `state` (a batch slice)
+    holds: `pos` their device positions, which the chain advances, `ntok` their token counts on the device, `plan` the host
+    values of `_ragged_plan`.  call="verify" (`mhla_causal_verify_ragged`): the same arguments and rows, nothing committed."""
+    B, T, H, K = q.shape
+    max_end, max_later, any_close, _ = plan
+    ws_bytes = _extend_ragged_ws_bytes(_lib.load(), B, T, H, k.shape[2], K, v.shape[-1], max_later, _DTYPES[q.dtype])
+    _launch_rows(q, k, v, gate, mixf, wf, scale, want_y, call, state, (pos.data_ptr(),),
+                 (ntok.data_ptr(), T, max_end, max_later, int(any_close), int(bool(left_padded))), ws_bytes, res, norm_eps, B)
+
+
+def _causal_packed(q, k, v, gate, mixf, wf, _, scale, want_y, state, pos, off, B, plan, res, norm_eps, call):
+    """One launch chain of `mhla_causal_extend_packed` (`call`: "extend_packed"; or "verify_packed") on what `_decode_prepare`
+    returned, cut to the chain's tokens, for the B sequences `state` (a batch slice) holds: `pos` their device positions, `off` their
+    B + 1 offsets on the device, `plan` the host values of `_ragged_plan`; the rows into `res`."""
+    _, N, H, K = q.shape
+    max_end, max_later, any_close, _ = plan
+    ws_bytes = _lib.load().mhla_causal_extend_packed_ws_bytes(B, N, H, k.shape[2], K, v.shape[-1], max_later, _DTYPES[q.dtype])
+    _launch_rows(q, k, v, gate, mixf, wf, scale, want_y, call, state, (pos.data_ptr(),), (off.data_ptr(), N, max_end, max_later, int(any_close)),
+                 ws_bytes, res, norm_eps, B, True)
 
 
 def _packed_offsets(cu, slices, device, accept=None):
@@ -2785,20 +2795,10 @@ def _packed_offsets(cu, slices, device, accept=None):
     host, at = [], []
     for i, j, _ in slices:
         at.append(len(host))
-        host.extend(c - cu[i] for c in cu[i:j + 1])
+        host.extend([c - cu[i] for c in cu[i:j + 1]])
     if accept is not None:
         host.extend(accept)
     return torch.tensor(host, dtype=torch.int32).to(device), at
-
-
-def _packed_state_head(mixf, state, pos):
-    """What every packed entry point takes after its token views: the matrix, then `S` or the pages with (n_pages, table_dev) or
-    (0, null), the capacity, P, Cur, the positions, the slot map with the pool's rows or (null, 0)."""
-    pages, slot = state.pages, getattr(state, "map", None)
-    return (mixf.data_ptr(), mixf.shape[1],
-            *((state.S.data_ptr(), 0, None) if pages is None else (pages.data_ptr(), pages.shape[0], state.table_dev.data_ptr())),
-            state.dims[2] if slot is not None else state.S.shape[2], state.P.data_ptr(), state.Cur.data_ptr(), pos.data_ptr(),
-            *((None, 0) if slot is None else (slot.data_ptr(), state.dims[0])))
 
 
 def _view0(t: torch.Tensor) -> View:
@@ -2807,43 +2807,43 @@ def _view0(t: torch.Tensor) -> View:
     return View(t.data_ptr(), 0, s[1], s[2])
 
 
-@_device_guard
-def _causal_packed(q, k, v, gate, mixf, wf, _, scale, want_y, state, pos, off, B, plan, res, norm_eps, name):
-    """One launch chain of `mhla_causal_extend_packed` (`name`; or `mhla_causal_verify_packed`) on what `_decode_prepare` returned, cut
-    to the chain's tokens, for the B sequences `state` (a batch slice) holds: `pos` their device positions, `off` their B + 1 offsets
-    on the device, `plan` the host values of `_ragged_plan`; the rows into `res`."""
-    lib = _lib.load()
-    _, N, H, K = q.shape
-    Hk, V, dt = k.shape[2], v.shape[-1], _DTYPES[q.dtype]
-    max_end, max_later, any_close, _ = plan
-    ws = _ws(lib.mhla_causal_extend_packed_ws_bytes(B, N, H, Hk, K, V, max_later, dt), q.device)
-    rc = getattr(lib, name)(_view0(q), _view0(k), _view0(v), *_packed_state_head(mixf, state, pos), off.data_ptr(), N, max_end, max_later,
-                            int(any_close), NULL_VIEW if want_y else _view0(res), _view0(gate) if gate is not None else NULL_VIEW,
-                            wf.data_ptr() if wf is not None else None, float(norm_eps), _view0(res) if want_y else NULL_VIEW,
-                            ws.data_ptr(), ws.numel() * 4, B, H, Hk, K, V, state.chunk_size, float(scale), dt, _stream())
-    _lib.check(rc, name)
+def _chains(state, slices, skip_empty=True):
+    """The one pairing of launch chains (`_slices`) with the state's rows, for extend, verify and commit, padded and packed: (the
+    chain's number, first sequence, end, plan, the state's rows, their positions: `_rows_of`) of every chain.  One chain, the usual
+    call: the state itself, no views built.  `skip_empty`: a chain none of whose sequences has a token is left out."""
+    if len(slices) == 1:
+        return ((0,) + slices[0] + (state, state.pos),)
+    return [(n, i, j, plan) + _rows_of(state, i, j, state.pos) for n, (i, j, plan) in enumerate(slices) if plan[0] or not skip_empty]
 
 
-def _packed_parts(state, slices):
-    """(`_state_slice`, its positions) of every chain of `slices`: a view's positions are the pool's, addressed through the map."""
-    pooled = isinstance(state, CausalStateView)
-    for i, j, _ in slices:
-        yield _state_slice(state, i, j), state.pos if pooled else state.pos[i:j]
-
-
-def _packed_chains(name, fn, prepared, state, cu, counts, res, norm_eps):
-    """The rows of a packed extend or verify (`name`: the entry point) into `res`: `_packed_slices`, the page rule, the one copy of
-    the offsets, then `_causal_packed` once per chain that has a token."""
-    H, Hk, K, V = prepared.q.shape[2], prepared.k.shape[2], prepared.q.shape[3], prepared.v.shape[-1]
-    slices = _packed_slices(fn, state, cu, counts, H, prepared.mixf, (H, Hk, K, V, _DTYPES[prepared.q.dtype]))
+def _rows_chains(call, fn, prepared, state, slices, counts, left_padded, res, norm_eps, cu=None):
+    """The rows of an extend or a verify (`call`: the key of `_ENTRY`) with per-sequence `counts` into `res`, one launch chain per
+    slice of `slices`: the page rule, the one copy (the counts; packed, `cu`: the offsets), then `_causal_extend_ragged` or
+    `_causal_packed` per chain.  Returns `res`."""
     if state.pages is not None:
-        _assign_pages(fn, state, [p + n for p, n in zip(state.lengths, counts)])
-    off, at = _packed_offsets(cu, slices, res.device)
-    if len(slices) == 1:   # (the usual call: the objects themselves, no views to build)
-        return _causal_packed(*prepared, state, state.pos, off, len(counts), slices[0][2], res, norm_eps, name)
-    for (i, j, plan), a, (part, pos) in zip(slices, at, _packed_parts(state, slices)):
-        if plan[0]:   # (a chain whose sequences are all empty has no row and is left alone)
-            _causal_packed(*prepared.part(None, None, cu[i], cu[j]), part, pos, off[a:a + j - i + 1], j - i, plan, res[:, cu[i]:cu[j]], norm_eps, name)
+        _page_rule(fn, state, counts)
+    if res is None:   # (a padded verify takes its rows after the page rule, every other call before it: the order of allocations stays)
+        res = prepared.q.new_empty(prepared.q.shape[:3] + prepared.v.shape[3:])
+    # the one small copy of the call: the counts, or the offsets of a pack
+    cnt, at = (torch.tensor(counts, dtype=torch.int32).to(res.device), None) if cu is None else _packed_offsets(cu, slices, res.device)
+    several = len(slices) > 1
+    p, c, out = prepared, cnt, res   # (one chain, the usual call: the caller's objects themselves)
+    for n, i, j, plan, rows, pos in _chains(state, slices, cu is not None):   # (a padded chain runs without a token too)
+        if cu is None:
+            if several:
+                p, c, out = prepared.part(i, j), cnt[i:j], res[i:j]
+            _causal_extend_ragged(*p, rows, pos, c, plan, left_padded, out, norm_eps, call)
+        else:
+            if several:
+                p, c, out = prepared.part(None, None, cu[i], cu[j]), cnt[at[n]:at[n] + j - i + 1], res[:, cu[i]:cu[j]]
+            _causal_packed(*p, rows, pos, c, j - i, plan, out, norm_eps, call)
+    return res
+
+
+def _advance(state, counts):
+    """The host mirror after every sequence took `counts[b]` tokens (the device positions were advanced by the launch chains)."""
+    lengths = tuple([p + n for p, n in zip(state.lengths, counts)])
+    state.lengths, state.seen = lengths, max(lengths)
 
 
 def _extend_run(prepared, part, res, norm_eps, i, j, p, t_lo, t_hi, step_t):
@@ -2870,7 +2870,7 @@ def _extend_counts(fn, prepared, state, counts, left_padded, res, norm_eps):
     B, T, H, K = prepared.q.shape
     V = prepared.v.shape[-1]
     Hk = prepared.k.shape[2]
-    slices = _ragged_slices(fn, state, counts, H, prepared.mixf)
+    slices = _slices(fn, state, counts, H, prepared.mixf)
     lib = _lib.load()
     dt = _DTYPES[prepared.q.dtype]
     over = any(_extend_ragged_ws_bytes(lib, j - i, T, H, Hk, K, V, plan[1], dt) > EXTEND_WS_CAP_BYTES for i, j, plan in slices)
@@ -2904,11 +2904,8 @@ def _extend_counts(fn, prepared, state, counts, left_padded, res, norm_eps):
                 _extend_run(prepared, part, res, norm_eps, b, b + 1, p, t_lo, t_lo + n, step_t)
         state.pos += torch.tensor(counts, dtype=torch.int32).to(state.pos.device, non_blocking=False)
     else:
-        if state.pages is not None:
-            _assign_pages(fn, state, [p + n for p, n in zip(state.lengths, counts)])
-        _ragged_chains("mhla_causal_extend_ragged", prepared, state, slices, counts, left_padded, res, norm_eps)
-    state.lengths = tuple(p + n for p, n in zip(state.lengths, counts))
-    state.seen = max(state.lengths)
+        _rows_chains("extend", fn, prepared, state, slices, counts, left_padded, res, norm_eps)
+    _advance(state, counts)
     return res
 
 
@@ -2957,24 +2954,22 @@ def mhla_causal_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     as the padded call)."""
     fn = "mhla_causal_extend"
     _decode_entry(fn, state, q, k, v, False, True, cu_seqlens is not None)
-    _refuse_h16(fn, state)
+    if state.page_mult is not None:
+        _refuse_h16(fn, state)
     B, T, H, K = q.shape
     V = v.shape[-1]
-    if cu_seqlens is not None:
-        cu, counts, prepared = _packed_prepare(fn, q, k, v, mixing_matrix, state, cu_seqlens, counts, left_padded, scale, gate, norm_weight,
+    if cu_seqlens is not None or counts is not None:
+        cu, counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, left_padded, cu_seqlens, scale, gate, norm_weight,
                                                epilogue)
         if not any(counts):
-            return torch.zeros((1, T, H, V), dtype=q.dtype, device=q.device)
-        res = q.new_empty((1, T, H, V))
-        _packed_chains("mhla_causal_extend_packed", fn, prepared, state, cu, counts, res, norm_eps)
-        state.lengths = tuple(p + n for p, n in zip(state.lengths, counts))
-        state.seen = max(state.lengths)
-        return res
-    if counts is not None:
-        counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, scale, gate, norm_weight, epilogue)
-        if not any(counts):
             return torch.zeros((B, T, H, V), dtype=q.dtype, device=q.device)
-        return _extend_counts(fn, prepared, state, counts, left_padded, q.new_empty((B, T, H, V)), norm_eps)
+        res = q.new_empty((B, T, H, V))
+        if cu is None:   # (padded: the three strategies of `_extend_counts`)
+            return _extend_counts(fn, prepared, state, counts, left_padded, res, norm_eps)
+        slices = _slices(fn, state, counts, H, prepared.mixf, cu, (H, k.shape[2], K, V, _DTYPES[prepared.q.dtype]))
+        _rows_chains("extend_packed", fn, prepared, state, slices, counts, False, res, norm_eps, cu)
+        _advance(state, counts)
+        return res
     if T == 1:
         return mhla_causal_step(q, k, v, mixing_matrix, state, scale=scale, gate=gate, norm_weight=norm_weight, norm_eps=norm_eps,
                                 epilogue=epilogue)
@@ -3044,89 +3039,43 @@ def mhla_causal_verify(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixing
     is cut between sequences; a single sequence beyond them is a ValueError."""
     fn = "mhla_causal_verify"
     _decode_entry(fn, state, q, k, v, False, True, cu_seqlens is not None)
-    _refuse_h16(fn, state)
+    if state.page_mult is not None:
+        _refuse_h16(fn, state)
     B, T, H, K = q.shape
     V = v.shape[-1]
-    if cu_seqlens is not None:
-        cu, counts, prepared = _packed_prepare(fn, q, k, v, mixing_matrix, state, cu_seqlens, counts, left_padded, scale, gate, norm_weight,
-                                               epilogue)
-        draft = CausalDraft(prepared.k, prepared.v, counts, False, state.lengths, state if isinstance(state, CausalStateView) else None, cu)
-        if not any(counts):
-            return torch.zeros((1, T, H, V), dtype=q.dtype, device=q.device), draft
-        res = q.new_empty((1, T, H, V))
-        _packed_chains("mhla_causal_verify_packed", fn, prepared, state, cu, counts, res, norm_eps)
-        return res, draft
-    counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, (T,) * B if counts is None else counts, scale, gate,
-                                       norm_weight, epilogue)
-    draft = CausalDraft(prepared.k, prepared.v, counts, left_padded, state.lengths, state if isinstance(state, CausalStateView) else None)
+    packed = cu_seqlens is not None
+    cu, counts, prepared = _counts_prepare(fn, q, k, v, mixing_matrix, state, (T,) * B if counts is None and not packed else counts, left_padded,
+                                           cu_seqlens, scale, gate, norm_weight, epilogue)
+    draft = CausalDraft(prepared.k, prepared.v, counts, left_padded, state.lengths, state if isinstance(state, CausalStateView) else None, cu)
     if not any(counts):
         return torch.zeros((B, T, H, V), dtype=q.dtype, device=q.device), draft
-    slices = _ragged_slices(fn, state, counts, H, prepared.mixf)
+    if packed:
+        slices = _slices(fn, state, counts, H, prepared.mixf, cu, (H, k.shape[2], K, V, _DTYPES[q.dtype]))
+        return _rows_chains("verify_packed", fn, prepared, state, slices, counts, False, q.new_empty((B, T, H, V)), norm_eps, cu), draft
+    slices = _slices(fn, state, counts, H, prepared.mixf)
     lib = _lib.load()
-    need = max(_extend_ragged_ws_bytes(lib, j - i, T, H, k.shape[2], K, V, plan[1], _DTYPES[q.dtype]) for i, j, plan in slices)
+    need = max([_extend_ragged_ws_bytes(lib, j - i, T, H, k.shape[2], K, V, plan[1], _DTYPES[q.dtype]) for i, j, plan in slices])
     if need > EXTEND_WS_CAP_BYTES:
         raise ValueError(f"{fn}: a draft of T={T} tokens for {B} sequences needs a workspace of {need} bytes, more than "
                          f"EXTEND_WS_CAP_BYTES={EXTEND_WS_CAP_BYTES}: verify fewer tokens or sequences per call")
-    if state.pages is not None:
-        _assign_pages(fn, state, [p + n for p, n in zip(state.lengths, counts)])   # (the draft's end)
-    res = q.new_empty((B, T, H, V))
-    _ragged_chains("mhla_causal_verify_ragged", prepared, state, slices, counts, left_padded, res, norm_eps)
-    return res, draft
+    return _rows_chains("verify", fn, prepared, state, slices, counts, left_padded, None, norm_eps), draft   # (None: the rows, taken after the page rule)
 
 
 @_device_guard
-def _causal_commit_packed(k, v, mixf, state, pos, off, acc, B, plan):
-    """One launch chain of `mhla_causal_commit_packed` for the B sequences `state` (a batch slice) holds, on the chain's tokens of the
-    draft's pack: `pos` their device positions, which the chain advances, `off` / `acc` their B + 1 offsets and accepted counts on
-    the device, `plan` the host values of `_ragged_plan` for the accepted counts."""
+def _launch_commit(k, v, mixf, state, pos, cnt, acc, B, plan, left_padded):
+    """The one library call of a commit, one launch chain for the B sequences `state` (a batch slice) holds: `pos` their device
+    positions, which the chain advances, `acc` the accepted counts on the device, `plan` the host values of `_ragged_plan` for them.
+    Padded (the draft's k, v [B, T, ...]): `cnt` the draft's counts on the device, and `left_padded`.  Packed (`left_padded` None;
+    k, v the chain's tokens of the draft's pack [1, N, ...]): `cnt` the sequences' B + 1 offsets, views with a zero batch stride."""
     lib = _lib.load()
-    _, N, H, K = k.shape
-    V, dt = v.shape[-1], _dtype_code(k)
+    _, T, H, K = k.shape
+    packed = left_padded is None
+    view, dt = _view0 if packed else _view, _dtype_code(k)
     max_end, max_later, any_close, _ = plan
     ws = _ws(lib.mhla_causal_commit_ragged_ws_bytes(B, dt), k.device)
-    name = "mhla_causal_commit_packed"
-    rc = lib.mhla_causal_commit_packed(_view0(k), _view0(v), *_packed_state_head(mixf, state, pos), off.data_ptr(), acc.data_ptr(), N, max_end,
-                                       max_later, int(any_close), ws.data_ptr(), ws.numel() * 4, B, H, K, V, state.chunk_size, dt, _stream())
-    _lib.check(rc, name)
-
-
-def _commit_packed(fn, draft, mixf, state, accept):
-    """`mhla_causal_commit` of a draft verified with `cu_seqlens=`, after the checks both forms share: the rest of the padded form's,
-    the page rule, the one copy (offsets and `accept`), then one chain per slice of the pack."""
-    k, v, cu, B = draft.k, draft.v, draft.cu, len(draft.counts)
-    H = k.shape[2]
-    slices = _packed_slices(fn, state, cu, accept, H, mixf)
-    if any(plan[0] and mixf.shape[0] < plan[3] + 1 for _, _, plan in slices):
-        raise IndexError(f"{fn}: mixing_matrix has only {mixf.shape[0]} rows, fewer than the accepted tokens read (lengths "
-                         f"{state.lengths}, accept {accept})")
-    if state.pages is not None:
-        _assign_pages(fn, state, [p + a for p, a in zip(state.lengths, accept)])
-    off, at = _packed_offsets(cu, slices, k.device, accept)   # the one small copy of the call
-    acc = off[len(off) - B:]
-    for (i, j, plan), a, (part, pos) in zip(slices, at, _packed_parts(state, slices)):
-        if plan[0]:   # (a slice of which nothing was accepted is left alone)
-            _causal_commit_packed(k[:, cu[i]:cu[j]], v[:, cu[i]:cu[j]], mixf, part, pos, off[a:a + j - i + 1], acc[i:j], j - i, plan)
-    state.lengths = tuple(p + a for p, a in zip(state.lengths, accept))
-    state.seen = max(state.lengths)
-    return state
-
-
-@_device_guard
-def _causal_commit_ragged(k, v, mixf, state, pos, ntok, acc, plan, left_padded):
-    """One launch chain of `mhla_causal_commit_ragged` for the sequences `state` (a batch slice) holds: `pos` their device positions,
-    which the chain advances, `ntok` / `acc` the draft's and the accepted counts on the device, `plan` the host values of
-    `_ragged_plan` for the accepted counts."""
-    lib = _lib.load()
-    B, T, H, K = k.shape
-    V = v.shape[-1]
-    dt = _dtype_code(k)
-    max_end, max_later, any_close, _ = plan
-    ws = _ws(lib.mhla_causal_commit_ragged_ws_bytes(B, dt), k.device)
-    slot = getattr(state, "map", None)   # (a view of a pool, or a batch slice of one: the slotted namesake)
-    name, where = (("mhla_causal_commit_ragged", ()) if slot is None else
-                   (_pool_call("mhla_causal_commit_slots", state), (slot.data_ptr(), state.dims[0])))
-    rc = getattr(lib, name)(_view(k), _view(v), *_state_head(mixf, state), pos.data_ptr(), *where, ntok.data_ptr(), acc.data_ptr(), T,
-                            max_end, max_later, int(any_close), int(bool(left_padded)), ws.data_ptr(), ws.numel() * 4, B, H, K, V,
+    name, _, head = _state_args("commit_packed" if packed else "commit", mixf, state, (pos.data_ptr(),), packed)
+    rc = getattr(lib, name)(view(k), view(v), *head, cnt.data_ptr(), acc.data_ptr(), T, max_end, max_later, int(any_close),
+                            *(() if packed else (int(bool(left_padded)),)), ws.data_ptr(), ws.numel() * 4, B, H, K, v.shape[-1],
                             state.chunk_size, dt, _stream())
     _lib.check(rc, name)
 
@@ -3144,11 +3093,14 @@ def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: C
         raise TypeError(f"{fn}: draft must be a CausalDraft (what mhla_causal_verify returns), got {type(draft).__name__}")
     if not isinstance(state, CausalState):
         raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
-    _refuse_paged_pool(fn, state)
-    _refuse_h16(fn, state)
+    if isinstance(state, PagedCausalState):
+        _refuse_paged_pool(fn, state)
+    if state.page_mult is not None:
+        _refuse_h16(fn, state)
     if isinstance(state, CausalStateView):
         state._host_slots(fn)
-    state._refuse_stale(fn)
+    if state.stale:
+        state._refuse_stale(fn)
     if state.lengths is None:
         raise ValueError(f"{fn}: the state is uniform ({state!r}); a draft is verified on, and committed to, a ragged state")
     seen_on, given = ((x.pool, x.slots) if isinstance(x, CausalStateView) else None for x in (draft.view, state))
@@ -3163,29 +3115,34 @@ def mhla_causal_commit(draft: CausalDraft, mixing_matrix: torch.Tensor, state: C
         return state
     k, v = draft.k, draft.v
     _, T, H, K = k.shape
-    if _state_rows(state) != B or state.dims[1:] != (H, state.capacity_chunks, K, v.shape[-1]) or state.device != k.device:
+    dims = state.dims
+    if (state.rows if isinstance(state, CausalStateView) else dims[0]) != B or dims[1:] != (H, dims[2], K, v.shape[-1]) or state.device != k.device:
         raise ValueError(f"{fn}: state is {state!r}, the draft has B={B} H={H} K={K} V={v.shape[-1]} on {k.device}")
     if mixing_matrix.dim() < 2 or mixing_matrix.device != k.device:
         raise ValueError(f"{fn}: mixing_matrix must be [L, L(, 1, 1, 1, 1)] on {k.device}, got {tuple(mixing_matrix.shape)} on "
                          f"{mixing_matrix.device}")
     _require_gpu(k, v, mixing_matrix)
     mixf = _mix2d(mixing_matrix)
-    if draft.cu is not None:
-        return _commit_packed(fn, draft, mixf, state, accept)
-    slices = _ragged_slices(fn, state, accept, H, mixf)
-    if any(plan[0] and mixf.shape[0] < plan[3] + 1 for _, _, plan in slices):
-        raise IndexError(f"{fn}: mixing_matrix has only {mixf.shape[0]} rows, fewer than the accepted tokens read (lengths "
-                         f"{state.lengths}, accept {accept})")
-    dev = k.device
+    cu = draft.cu
+    slices = _slices(fn, state, accept, H, mixf, cu, rows=True)
     if state.pages is not None:
-        _assign_pages(fn, state, [p + a for p, a in zip(state.lengths, accept)])
-    both = torch.tensor((draft.counts, accept), dtype=torch.int32).to(dev)   # the one small copy of the call
-    ntok, acc = both[0], both[1]
-    for (_, _, plan), (part, _, k_, v_, pos, ntok_, acc_) in zip(slices, _batch_slices(state, slices[0][1], None, k, v, state.pos, ntok, acc)):
-        if plan[0]:   # (a slice of which nothing was accepted is left alone)
-            _causal_commit_ragged(k_, v_, mixf, part, pos, ntok_, acc_, plan, draft.left_padded)
-    state.lengths = tuple(p + a for p, a in zip(state.lengths, accept))
-    state.seen = max(state.lengths)
+        _page_rule(fn, state, accept)
+    # the one small copy of the call: the draft's counts over `accept`, or the offsets of a pack followed by `accept`
+    if cu is None:
+        both = torch.tensor((draft.counts, accept), dtype=torch.int32).to(k.device)
+        cnt, acc = both[0], both[1]
+    else:
+        cnt, at = _packed_offsets(cu, slices, k.device, accept)
+        acc = cnt[len(cnt) - B:]
+    several, left = len(slices) > 1, draft.left_padded if cu is None else None
+    k_, v_, c, a = k, v, cnt, acc   # (one chain, the usual call: the caller's objects themselves)
+    for n, i, j, plan, rows, pos in _chains(state, slices):   # (a slice of which nothing was accepted is left alone)
+        if several and cu is None:
+            k_, v_, c, a = k[i:j], v[i:j], cnt[i:j], acc[i:j]
+        elif several:
+            k_, v_, c, a = k[:, cu[i]:cu[j]], v[:, cu[i]:cu[j]], cnt[at[n]:at[n] + j - i + 1], acc[i:j]
+        _launch_commit(k_, v_, mixf, rows, pos, c, a, j - i, plan, left)
+    _advance(state, accept)
     return state
 
 

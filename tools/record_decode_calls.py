@@ -1,14 +1,18 @@
 """The decode section of `mhla_amd/ops.py` (CausalState ... mhla_causal_commit) run on CPU tensors against a recording stand-in for
 the library (tools/fake_decode_lib.py): every library call with every argument, every public call's effect on the state's host
-mirror, every exception's type and message, and the signature and docstring hash of every public name of the section.  Two trees
-whose logs are byte-identical make the same calls in the same order and refuse the same things with the same words: the check
-of a refactor of that section (profiles/decode_host_refactor.md).
+mirror, every exception's type and message, and the signature and docstring hash of every public name of the section.  Plain
+states, views of a dense pool, of a pool of fp32 pages and of one of h16 pages (after every call on a view: the pool's mirror, its
+free pages and its table, host and device), a slot map on the device, the pack prefill `into=` a view, the pools' own methods, and
+packed new tokens (`cu_seqlens=`) as one chain and cut by each of the three limits.  Two trees whose logs are byte-identical make the
+same calls in the same order and refuse the same things with the same words: the check of a refactor of that section
+(profiles/decode_host_refactor.md, profiles/decode_host_refactor_pools.md).
 
     python tools/record_decode_calls.py [--tree DIR] [-o LOG]     the log (sha256 on stderr); DIR: another checkout to import
     python tools/record_decode_calls.py --raises                  also list the `raise` lines of the section no scenario reached
     python tools/record_decode_calls.py --counts                  Python function calls per public call (cProfile), no log
 """
 import argparse
+import contextlib
 import cProfile
 import hashlib
 import inspect
@@ -30,7 +34,7 @@ sys.path.insert(0, os.path.abspath(opt.tree))
 import torch  # noqa: E402
 
 import mhla_amd  # noqa: E402
-from mhla_amd import CausalState, _lib, ops  # noqa: E402
+from mhla_amd import CausalState, PagedCausalState, _lib, ops  # noqa: E402
 from mhla_amd import build as _build  # noqa: E402
 from fake_decode_lib import Session  # noqa: E402
 
@@ -38,7 +42,13 @@ _build.build(verbose=False)
 B, K, V, CAP = 3, 16, 24, 5
 PUBLIC = ("CausalState", "CausalState.empty", "CausalState.to_ragged", "CausalState.sync", "CausalState.clone", "CausalState.cat",
           "mhla_causal_prefill", "mhla_causal_state", "mhla_causal_step", "mhla_causal_step_dev", "mhla_causal_extend", "CausalDraft",
-          "mhla_causal_verify", "mhla_causal_commit")
+          "mhla_causal_verify", "mhla_causal_commit",
+          "CausalState.at", "CausalState.reset", "CausalState.fork", "CausalStateView", "CausalStateView.compact", "CausalStateView.sync",
+          "PagedCausalState", "PagedCausalState.empty", "PagedCausalState.at", "PagedCausalState.to_ragged", "PagedCausalState.clone",
+          "PagedCausalState.reserve", "PagedCausalState.trim", "PagedCausalState.reset", "PagedCausalState.fork", "PagedCausalState.sync",
+          "PagedStateView", "PagedStateView.compact", "PoolExhausted")
+# a pool of N_SLOTS slots, of which a view takes SLOTS in that order (slots 1 and 3 belong to others and must keep every bit)
+SLOTS, N_SLOTS, N_PAGES, OTHERS = (4, 0, 2), 5, 16, {1: 70, 3: 1}
 
 
 def rand(*shape, dtype=torch.float32, seed=0):
@@ -62,6 +72,185 @@ def name_all(s, state=None, **tensors):
     s.name(**tensors)
     if state is not None:
         s.name(S=state.S, P=state.P, Cur=state.Cur, pos=state.pos, full=state._full)
+
+
+def new_pool(kind, Hk, lengths=(6, 133, 127), slots=SLOTS, k_dim=K, n_pages=N_PAGES):
+    """(pool, pool.at(slots)) of one kind -- "dense", "paged" (fp32 pages) or "h16" --: the view's sequences hold `lengths`, the
+    slots of `OTHERS` theirs, every chunk that holds a token has its page.  slots: a tuple, or an int32 tensor (a map on the device)."""
+    host = [OTHERS.get(i, 0) for i in range(N_SLOTS)]
+    for i, n in zip(SLOTS, lengths):
+        host[i] = n
+    if kind == "dense":
+        e = CausalState.empty(N_SLOTS, Hk, k_dim, V, CAP, device="cpu")
+        pool = CausalState(e.S, e.P, e.Cur, 0, 64, lengths=host)
+    else:
+        pool = PagedCausalState.empty(N_SLOTS, Hk, k_dim, V, CAP, n_pages, "cpu", page_format="fp32" if kind == "paged" else "h16")
+        pool.reserve(range(N_SLOTS), host)
+        pool._set_lengths(range(N_SLOTS), host)
+        pool.pos.copy_(torch.tensor(host, dtype=torch.int32))
+    return pool, pool.at(slots)
+
+
+def name_pool(s, pool, view=None):
+    s.name(S=pool._chunks, P=pool.P, Cur=pool.Cur, pos=pool.pos, full=pool._full, slot=view.map if view is not None else None,
+           table=getattr(pool, "table_dev", None), mult=pool.page_mult)
+
+
+def pool_line(s, pool):
+    """The pool behind a view after a call: its host mirror and -- paged -- the free pages and the table, host and device."""
+    if pool is None:
+        return
+    pos = None if pool.pos is None else pool.pos.tolist()
+    line = f"  pool: seen={pool.seen} lengths={pool.lengths} stale={pool.stale} pos={pos} full={None if pool._full is None else pool._full.tolist()}"
+    if pool.pages is not None:
+        line += f" pages_free={pool.pages_free} free={sorted(pool.free)} refs={pool.refs} have={pool.have} table={pool.table} table_dev={pool.table_dev.tolist()}"
+    s.lines.append(line)
+
+
+@contextlib.contextmanager
+def lowered(**limits):
+    """Module globals of `ops` (the limits a call is cut by) set for the block."""
+    saved = {n: getattr(ops, n) for n in limits}
+    for n, x in limits.items():
+        setattr(ops, n, x)
+    try:
+        yield
+    finally:
+        for n, x in saved.items():
+            setattr(ops, n, x)
+
+
+def pool_scenarios(s, tag, dtype, H, Hk):
+    """Views of pools (dense, fp32 pages, h16 pages), the pack prefill `into=` them, and packed new tokens, in one configuration."""
+    mix, w = torch.rand(CAP, CAP, generator=torch.Generator().manual_seed(9)), torch.rand(V, generator=torch.Generator().manual_seed(8)) + 0.5
+    lengths = (6, 133, 127)
+
+    def run(label, fn, q, k, v, pool, view, **kw):
+        name_pool(s, pool, view)
+        s.name(mix=mix, w=w, q=q, k=k, v=v, gate=kw.get("gate"))
+        got = s.call(f"{tag} {label}", fn, q, k, v, mix, view, state=view, **kw)
+        pool_line(s, pool)
+        return got
+
+    def commit(label, draft, pool, st, accept):
+        got = s.call(f"{tag} {label}", mhla_amd.mhla_causal_commit, draft, mix, st, accept, state=st)
+        pool_line(s, pool)
+        return got
+
+    q, k, v, g = tokens(dtype, H, Hk, 1)
+    q5, k5, v5, g5 = tokens(dtype, H, Hk, 5)
+    for kind in ("dense", "paged", "h16"):
+        for at in (lengths, (63, 133, 127), (64, 133, 127)):   # (the last: the step opens a chunk, a paged pool gives it a page)
+            run(f"{kind} view: step at {at}", mhla_amd.mhla_causal_step, q, k, v, *new_pool(kind, Hk, at), gate=g, norm_weight=w)
+        pool, view = new_pool(kind, Hk)
+        pool.full
+        run(f"{kind} view: step_dev", mhla_amd.mhla_causal_step_dev, q, k, v, pool, view)
+        run(f"{kind} view: step after step_dev (stale)", mhla_amd.mhla_causal_step, q, k, v, pool, view)
+        s.call(f"{tag} {kind} view: sync", view.sync, state=view)
+        pool_line(s, pool)
+        if kind == "h16":
+            continue
+        run(f"{kind} view: extend T=5", mhla_amd.mhla_causal_extend, q5, k5, v5, *new_pool(kind, Hk), gate=g5)
+        run(f"{kind} view: extend T=1", mhla_amd.mhla_causal_extend, q, k, v, *new_pool(kind, Hk))
+        for counts, left in (((3, 0, 5), False), ((3, 0, 5), True), ((0, 0, 0), False)):
+            run(f"{kind} view: extend counts={counts} left_padded={left}", mhla_amd.mhla_causal_extend, q5, k5, v5, *new_pool(kind, Hk, (60, 133, 127)),
+                counts=counts, left_padded=left, norm_weight=w)
+        for counts, left, accept in (((3, 0, 5), False, (2, 0, 0)), ((3, 0, 5), True, (3, 0, 5)), (None, False, (0, 0, 0)), (None, False, torch.tensor([5, 1, 0]))):
+            pool, view = new_pool(kind, Hk, (60, 133, 127))
+            got = run(f"{kind} view: verify counts={counts} left_padded={left}", mhla_amd.mhla_causal_verify, q5, k5, v5, pool, view, counts=counts,
+                      left_padded=left, gate=g5)
+            commit(f"{kind} view: commit accept={accept}", got[1], pool, view, accept)
+    pool, _ = new_pool("dense", Hk)
+    dmap = torch.tensor([4, -1, 2], dtype=torch.int32)   # (an entry outside the pool: that row is inactive)
+    pool.full
+    run("dense view, slot map on the device: step_dev", mhla_amd.mhla_causal_step_dev, q, k, v, pool, pool.at(dmap), gate=g)
+
+    # ---- the pack prefill into a view
+    kp, vp = rand(1, 109, Hk, K, dtype=dtype, seed=5), rand(1, 109, Hk, V, dtype=dtype, seed=6)
+    for kind in ("dense", "paged", "h16"):
+        for label, k_, v_, cu in (("pack", kp, vp, [0, 6, 76, 109]), ("pack with an empty sequence", kp, vp, [0, 6, 6, 109]),
+                                  ("all-empty pack", kp[:, :0], vp[:, :0], [0, 0, 0, 0])):
+            pool, view = new_pool(kind, Hk)
+            pool.full
+            name_pool(s, pool, view)
+            s.name(k=kp, v=vp, mix=mix)
+            s.call(f"{tag} {kind} view: state {label} into=", mhla_amd.mhla_causal_state, k_, v_, mix, cu_seqlens=cu, into=view, state=view)
+            pool_line(s, pool)
+
+    # ---- packed new tokens
+    dt = ops._DTYPES[dtype]
+    packs = (((0, 3, 3, 73), (2, 0, 30)), ((0, 0, 0, 70), (0, 0, 70)))   # (cu, accept); sequence 1 is empty; of the second, the first two
+    ws = _lib.load().mhla_causal_extend_packed_ws_bytes(3, 73, H, Hk, K, V, ops._ragged_plan(lengths, (3, 0, 70), CAP)[1], dt)
+    cuts = (("one chain", {}), ("cut by _PACK_MAX_TOKENS", dict(_PACK_MAX_TOKENS=70)), ("cut by _MAX_GRID_BH", dict(_MAX_GRID_BH=2 * H)),
+            ("cut by EXTEND_WS_CAP_BYTES", dict(EXTEND_WS_CAP_BYTES=ws - 1)))
+    for kind in ("plain", "dense", "paged"):
+        fresh = lambda: (None, new_state(Hk, lengths)) if kind == "plain" else new_pool(kind, Hk)
+
+        def packed(label, fn, cu, pool, st, **kw):
+            n = cu[-1]
+            qn, kn, vn, gn = (rand(1, n, h, d, dtype=dtype, seed=20 + i) for i, (h, d) in enumerate(((H, K), (Hk, K), (Hk, V), (H, V))))
+            if pool is None:
+                name_all(s, st)
+            else:
+                name_pool(s, pool, st)
+            s.name(mix=mix, w=w, q=qn, k=kn, v=vn, gate=gn)
+            got = s.call(f"{tag} {kind}: {label} cu={cu}", fn, qn, kn, vn, mix, st, state=st, cu_seqlens=cu, gate=gn, **kw)
+            pool_line(s, pool)
+            return got
+
+        for what, limits in cuts:
+            for cu, accept in packs:
+                with lowered(**limits):
+                    packed(f"packed extend, {what}", mhla_amd.mhla_causal_extend, cu, *fresh(), norm_weight=w)
+                    pool, st = fresh()
+                    got = packed(f"packed verify, {what}", mhla_amd.mhla_causal_verify, cu, pool, st)
+                    if got is not None:
+                        commit(f"{kind}: packed commit accept={accept}, {what}", got[1], pool, st, accept)
+        packed("packed extend, all-empty pack", mhla_amd.mhla_causal_extend, (0, 0, 0, 0), *fresh())
+        pool, st = fresh()
+        got = packed("packed verify, all-empty pack", mhla_amd.mhla_causal_verify, (0, 0, 0, 0), pool, st)
+        commit(f"{kind}: packed commit of nothing", got[1], pool, st, (0, 0, 0))
+        pool, st = fresh()
+        got = packed("packed verify, every draft rejected", mhla_amd.mhla_causal_verify, packs[0][0], pool, st)
+        commit(f"{kind}: packed commit accept all zero", got[1], pool, st, (0, 0, 0))
+
+
+def pool_methods(s):
+    """The methods of the pools themselves, the free pages, the table and the host mirror after each."""
+    Hk = 2
+
+    def call(pool, label, fn, *a, **kw):
+        got = s.call(f"pool methods: {label}", fn, *a, **kw)
+        pool_line(s, pool)
+        return got
+
+    for kind in ("dense", "paged", "h16"):
+        pool, view = new_pool(kind, Hk, (70, 133, 127))
+        pool.full
+        name_pool(s, pool, view)
+        if kind != "dense":
+            call(pool, f"{kind} reserve", pool.reserve, (1, 3), 200)
+            call(pool, f"{kind} reserve per slot", pool.reserve, [4, 2], torch.tensor([320, 0]))
+            call(pool, f"{kind} trim", pool.trim, (1, 4))
+        call(pool, f"{kind} fork", pool.fork, 0, 3)
+        call(pool, f"{kind} fork onto a longer slot", pool.fork, 3, 1)
+        call(pool, f"{kind} reset", pool.reset, [0, 2])
+        if kind != "dense":
+            call(pool, f"{kind} trim after the reset", pool.trim, range(N_SLOTS))
+        for name in ("compact", "clone"):
+            got = call(pool, f"{kind} view.{name}", getattr(view, name))
+            s.lines.append(f"  {name}: S {tuple(got.S.shape)} {got.S.dtype} pos={got.pos.tolist()} full={got._full.tolist()}")
+        pool._full[1] = 1
+        pool.stale = True
+        call(pool, f"{kind} sync with a full flag", pool.sync)
+        call(pool, f"{kind} to_ragged is the pool", lambda: pool.to_ragged() is pool)
+        call(pool, f"{kind} view.to_ragged is the view", lambda: view.to_ragged() is view)
+        s.lines.append(f"  nbytes={pool.nbytes} dims={pool.dims} capacity_chunks={pool.capacity_chunks} view: rows={view.rows} dims={view.dims} "
+                       f"capacity_chunks={view.capacity_chunks} {view!r}")
+    st = new_state(Hk, (6, 133, 127))
+    dense, dview = new_pool("dense", Hk)
+    paged, pview = new_pool("paged", Hk)
+    call(None, "cat of a state and two views", lambda: _named_state(s, CausalState.cat([st, dview, pview])))
 
 
 def scenarios(s, tag, dtype, H, Hk):
@@ -310,6 +499,189 @@ def refusals(s):
     call("commit matrix columns", commit, ops.CausalDraft(k5, v5, (3, 0, 5), False, (6, 133, 127)), torch.rand(CAP, 2), st, (1, 0, 3))
     call("commit matrix rows", commit, ops.CausalDraft(k5, v5, (3, 0, 5), False, (6, 133, 127)), torch.rand(2, CAP), st, (1, 0, 3))
     call("commit dtype", commit, ops.CausalDraft(k5.double(), v5.double(), (3, 0, 5), False, (6, 133, 127)), mix, st, (1, 0, 3))
+    pool_refusals(s, call, H, Hk, mix)
+
+
+def pool_refusals(s, call, H, Hk, mix):
+    """The refusals of the pools, their views, the pack prefill `into=` and packed new tokens; after each on a paged view, the pool."""
+    q, k, v, g = tokens(torch.float32, H, Hk, 1)
+    q5, k5, v5, g5 = tokens(torch.float32, H, Hk, 5)
+    step, dev, extend, verify, commit = (mhla_amd.mhla_causal_step, mhla_amd.mhla_causal_step_dev, mhla_amd.mhla_causal_extend,
+                                         mhla_amd.mhla_causal_verify, mhla_amd.mhla_causal_commit)
+    draft5 = lambda lengths, view=None, cu=None: ops.CausalDraft(k5, v5, (3, 0, 5), False, lengths, view, cu)
+    # slots
+    dense, dview = new_pool("dense", Hk)
+    for label, slots in (("a bool", [0, True]), ("a float", [0, 1.0]), ("none", []), ("outside", [0, 5, -1]), ("twice", [1, 0, 1, 0])):
+        call(f"at: slots {label}", dense.at, slots)
+    call("at on a uniform state", new_state(Hk, seen=5).at, [0])
+    call("reset on a uniform state", new_state(Hk, seen=5).reset, [0])
+    call("fork on a stale pool", _stale(new_pool("dense", Hk)[0]).fork, 0, 1)
+    call("fork: slot outside", dense.fork, 0, 9)
+    call("a view of a view", ops.CausalStateView, dview, [0])
+    call("view.at", dview.at, [0])
+    call("view.reset", dview.reset, [0])
+    call("view.fork", dview.fork, 0, 1)
+    for label, t in (("int64", torch.tensor([0, 1])), ("rank", torch.zeros(1, 2, dtype=torch.int32)), ("empty", torch.zeros(0, dtype=torch.int32)),
+                     ("elsewhere", torch.zeros(2, dtype=torch.int32, device="meta")), ("strided", torch.zeros(4, dtype=torch.int32)[::2])):
+        call(f"at: a device map, {label}", dense.at, t)
+    # a slot map on the device goes to step_dev alone
+    for kind in ("dense", "paged"):
+        pool, _ = new_pool(kind, Hk)
+        onDev = pool.at(torch.tensor([4, 0, 2], dtype=torch.int32))
+        call(f"{kind} device map, step", step, q, k, v, mix, onDev, state=onDev)
+        call(f"{kind} device map, extend", extend, q5, k5, v5, mix, onDev, state=onDev)
+        call(f"{kind} device map, extend cu_seqlens", extend, q5[:1], k5[:1], v5[:1], mix, onDev, state=onDev, cu_seqlens=(0, 2, 2, 5))
+        call(f"{kind} device map, verify", verify, q5, k5, v5, mix, onDev, state=onDev)
+        call(f"{kind} device map, commit", commit, draft5((6, 133, 127), onDev), mix, onDev, (1, 0, 1), state=onDev)
+        call(f"{kind} device map, compact", onDev.compact)
+        call(f"{kind} device map, state into=", mhla_amd.mhla_causal_state, k5[:1], v5[:1], mix, cu_seqlens=(0, 2, 2, 5), into=onDev)
+        call(f"{kind} device map, cat", CausalState.cat, [onDev])
+        pool_line(s, pool)
+    # the paged pool's constructor
+    P_ = PagedCausalState
+    pg, sl, tab = (lambda n=4: torch.zeros(n, Hk, K, V)), (lambda n=2: torch.zeros(n, Hk, K, V)), [[-1] * CAP, [-1] * CAP]
+    call("paged: pages rank", P_, pg()[0], sl(), sl(), tab)
+    call("paged: P against pages", P_, pg(), torch.zeros(2, Hk, K, V + 1), sl(), tab)
+    call("paged: P against Cur", P_, pg(), sl(), sl(3), tab)
+    call("paged: dtype", P_, pg().double(), sl(), sl(), tab)
+    call("paged: contiguity", P_, pg(), torch.zeros(2, Hk, V, K).transpose(2, 3), torch.zeros(2, Hk, V, K).transpose(2, 3), tab)
+    call("paged: elsewhere", P_, pg(), sl().to("meta"), sl().to("meta"), tab)
+    call("paged: no slot", P_, pg(), sl(0), sl(0), [])
+    call("paged: no page", P_, pg(0), sl(), sl(), tab)
+    call("paged: table rows", P_, pg(), sl(), sl(), tab[:1])
+    call("paged: table of no entries", P_, pg(), sl(), sl(), [[], []])
+    call("paged: table rows of differing lengths", P_, pg(), sl(), sl(), torch.full((2, CAP), -1).tolist()[:1] + [[-1] * (CAP - 1)])
+    call("paged: table entries not ints", P_, pg(), sl(), sl(), [[0.5, True, -1, -1, -1], [-1] * CAP])
+    call("paged: table entries outside", P_, pg(), sl(), sl(), torch.tensor([[4, -2, -1, -1, -1], [0, -1, -1, -1, -1]]))
+    call("paged: a page twice in a slot", P_, pg(), sl(), sl(), [[1, 1, -1, 2, 2], [1, -1, -1, -1, -1]])
+    call("paged: lengths count", P_, pg(), sl(), sl(), tab, lengths=(1,))
+    call("paged: lengths beyond the capacity", P_, pg(), sl(), sl(), tab, lengths=(64 * CAP + 1, 0))
+    call("paged: tokens without a page", P_, pg(), sl(), sl(), [[0, -1, 1, -1, -1], [-1] * CAP], lengths=(130, 1))
+    h16, mult = (lambda kk=K: torch.zeros(4, Hk, kk, V, dtype=torch.float16)), torch.zeros(4, Hk, K * V // 64)
+    call("paged h16: K V % 64", P_, h16(3), torch.zeros(2, Hk, 3, V), torch.zeros(2, Hk, 3, V), tab, page_mult=mult)
+    call("paged h16: no page_mult", P_, h16(), sl(), sl(), tab)
+    call("paged h16: fp32 pages with a page_mult", P_, pg(), sl(), sl(), tab, page_mult=mult)
+    call("paged h16: page_mult dtype", P_, h16(), sl(), sl(), tab, page_mult=mult.double())
+    call("paged h16: page_mult shape", P_, h16(), sl(), sl(), tab, page_mult=mult[:, :, :-1])
+    call("paged h16: page_mult strided", P_, h16(), sl(), sl(), tab, page_mult=torch.zeros(4, Hk, K * V // 32)[..., ::2])
+    call("paged h16: page_mult elsewhere", P_, h16(), sl(), sl(), tab, page_mult=mult.to("meta"))
+    call("paged h16: P dtype", P_, h16(), sl().double(), sl().double(), tab, page_mult=mult)
+    call("paged.empty: size", P_.empty, 2, Hk, K, V, CAP, 0, "cpu")
+    call("paged.empty: page format", P_.empty, 2, Hk, K, V, CAP, 4, "cpu", page_format="bf16")
+    call("paged.empty: h16 K V % 64", P_.empty, 2, Hk, 3, V, CAP, 4, "cpu", page_format="h16")
+    # the paged pool's methods
+    paged, pview = new_pool("paged", Hk, n_pages=9)   # (every page is taken: 3 + 2 + 2 + 1 + 1)
+    call("paged.clone", paged.clone)
+    call("paged.reserve: slots", paged.reserve, [0, 0], 5)
+    call("paged.reserve: tokens count", paged.reserve, [0, 1], [5])
+    call("paged.reserve: tokens negative", paged.reserve, [0, 1], [5, -1])
+    call("paged.reserve: beyond the capacity", paged.reserve, [0, 1], 64 * CAP + 1)
+    call("paged.reserve: pool exhausted", paged.reserve, [4, 1], [64, 129])
+    pool_line(s, paged)
+    call("paged.trim on a stale pool", _stale(new_pool("paged", Hk)[0]).trim, [0])
+    call("paged.reset: slot outside", paged.reset, [5])
+    call("paged view.S", lambda: pview.S)
+    # a paged pool where a state is expected, and a full one
+    for label, fn, a in (("step", step, (q, k, v)), ("step_dev", dev, (q, k, v)), ("extend", extend, (q5, k5, v5)), ("verify", verify, (q5, k5, v5))):
+        call(f"the paged pool itself, {label}", fn, *a, mix, paged)
+    call("the paged pool itself, commit", commit, draft5(paged.lengths), mix, paged, (1, 0, 1))
+    call("the paged pool itself, cat", CausalState.cat, [paged])
+    full, fview = new_pool("paged", Hk, (64, 133, 127), n_pages=9)
+    call("pool exhausted, step", step, q, k, v, mix, fview, state=fview)
+    pool_line(s, full)
+    call("pool exhausted, extend", extend, q5, k5, v5, mix, fview, state=fview)
+    call("pool exhausted, extend counts", extend, q5, k5, v5, mix, fview, state=fview, counts=(1, 0, 2))
+    call("pool exhausted, extend cu_seqlens", extend, q5[:1], k5[:1], v5[:1], mix, fview, state=fview, cu_seqlens=(0, 2, 2, 5))
+    call("pool exhausted, verify", verify, q5, k5, v5, mix, fview, state=fview)
+    call("pool exhausted, verify cu_seqlens", verify, q5[:1], k5[:1], v5[:1], mix, fview, state=fview, cu_seqlens=(0, 2, 2, 5))
+    call("pool exhausted, commit", commit, draft5(fview.lengths, fview), mix, fview, (1, 0, 1), state=fview)
+    call("pool exhausted, commit of a pack", commit, draft5(fview.lengths, fview, (0, 3, 3, 8)), mix, fview, (1, 0, 1), state=fview)
+    k70, v70 = tokens(torch.float32, H, Hk, 70)[1:3]
+    call("pool exhausted, state into=", mhla_amd.mhla_causal_state, k70[:1], v70[:1], mix, cu_seqlens=(0, 1, 2, 70), into=full.at((1, 3, 4)))
+    pool_line(s, full)
+    # h16 pages: extend, verify and commit
+    hpool, hview = new_pool("h16", Hk)
+    call("h16 pages, extend", extend, q5, k5, v5, mix, hview, state=hview)
+    call("h16 pages, extend counts", extend, q5, k5, v5, mix, hview, state=hview, counts=(1, 0, 2))
+    call("h16 pages, extend cu_seqlens", extend, q5[:1], k5[:1], v5[:1], mix, hview, state=hview, cu_seqlens=(0, 2, 2, 5))
+    call("h16 pages, verify", verify, q5, k5, v5, mix, hview, state=hview)
+    call("h16 pages, verify cu_seqlens", verify, q5[:1], k5[:1], v5[:1], mix, hview, state=hview, cu_seqlens=(0, 2, 2, 5))
+    call("h16 pages, commit", commit, draft5(hview.lengths, hview), mix, hview, (1, 0, 1), state=hview)
+    pool_line(s, hpool)
+    # the pack prefill into a view
+    kp, vp, cu = k70[:1], v70[:1], (0, 6, 6, 70)
+    state_, prefill = mhla_amd.mhla_causal_state, mhla_amd.mhla_causal_prefill
+    call("state into= without a pack", state_, k70, v70, mix, into=dview)
+    call("prefill into= without a pack", prefill, tokens(torch.float32, H, Hk, 70)[0], k70, v70, mix, into=dview)
+    call("state into= a state", state_, kp, vp, mix, cu_seqlens=cu, into=new_state(Hk, (6, 133, 127)))
+    call("state into= the paged pool", state_, kp, vp, mix, cu_seqlens=cu, into=paged)
+    call("state into= a stale pool", state_, kp, vp, mix, cu_seqlens=cu, into=_stale(new_pool("dense", Hk)[0]).at(SLOTS))
+    call("state into= with a capacity", state_, kp, vp, mix, cu_seqlens=cu, into=dview, capacity_chunks=CAP)
+    call("state into= sequences against slots", state_, kp, vp, mix, cu_seqlens=(0, 6, 70), into=dview)
+    call("state into= heads", state_, kp, vp, mix, cu_seqlens=cu, into=new_pool("dense", H)[1])
+    call("state into= K", state_, kp, vp, mix, cu_seqlens=cu, into=new_pool("paged", Hk, k_dim=8)[1])
+    call("state into= beyond the capacity", state_, kp, vp, torch.rand(1, 1), cu_seqlens=cu, into=dview)
+    call("prefill into= sequences against slots", prefill, tokens(torch.float32, H, Hk, 70)[0][:1], kp, vp, mix, cu_seqlens=(0, 6, 70), into=dview)
+    # packed new tokens
+    qp, kp5, vp5 = q5[:1], k5[:1], v5[:1]
+    cu5 = (0, 2, 2, 5)
+    rag = lambda: new_state(Hk, (6, 133, 127))
+    for fn in (extend, verify):
+        n = fn.__name__
+        call(f"{n} cu_seqlens with counts", fn, qp, kp5, vp5, mix, rag(), cu_seqlens=cu5, counts=(2, 0, 3))
+        call(f"{n} cu_seqlens left-padded", fn, qp, kp5, vp5, mix, rag(), cu_seqlens=cu5, left_padded=True)
+        call(f"{n} cu_seqlens with B = 3", fn, q5, k5, v5, mix, rag(), cu_seqlens=cu5)
+        call(f"{n} cu_seqlens not from 0", fn, qp, kp5, vp5, mix, rag(), cu_seqlens=(1, 2, 2, 5))
+        call(f"{n} cu_seqlens decreasing", fn, qp, kp5, vp5, mix, rag(), cu_seqlens=torch.tensor([0, 3, 2, 5]))
+        call(f"{n} cu_seqlens rank", fn, qp, kp5, vp5, mix, rag(), cu_seqlens=torch.tensor([cu5]))
+        call(f"{n} cu_seqlens end", fn, qp, kp5, vp5, mix, rag(), cu_seqlens=(0, 2, 2, 4))
+        call(f"{n} cu_seqlens on a uniform state", fn, qp, kp5, vp5, mix, new_state(Hk, seen=5), cu_seqlens=cu5)
+        call(f"{n} cu_seqlens sequences", fn, qp, kp5, vp5, mix, rag(), cu_seqlens=(0, 2, 5))
+        call(f"{n} cu_seqlens on a view, sequences", fn, qp, kp5, vp5, mix, dview, cu_seqlens=(0, 2, 5))
+        call(f"{n} cu_seqlens matrix rank", fn, qp, kp5, vp5, torch.rand(CAP), rag(), cu_seqlens=cu5)
+        call(f"{n} cu_seqlens matrix rows", fn, qp, kp5, vp5, torch.rand(2, 2), rag(), cu_seqlens=cu5)
+        call(f"{n} cu_seqlens capacity", fn, qp, kp5, vp5, torch.rand(8, 8), new_state(Hk, (6, 133, 318)), cu_seqlens=cu5)
+        call(f"{n} cu_seqlens k shape", fn, qp, kp5[:, :4], vp5, mix, rag(), cu_seqlens=cu5)
+        call(f"{n} cu_seqlens T = 0 with tokens in cu", fn, qp[:, :0], kp5[:, :0], vp5[:, :0], mix, rag(), cu_seqlens=cu5)
+        call(f"{n} cu_seqlens matrix columns", fn, qp[:, :2], kp5[:, :2], vp5[:, :2], torch.rand(2, 2), new_state(Hk, (63, 127, 5)), cu_seqlens=(0, 1, 2, 2))
+        with lowered(_PACK_MAX_TOKENS=2):
+            call(f"{n} cu_seqlens: a sequence beyond the token bound", fn, qp, kp5, vp5, mix, rag(), cu_seqlens=cu5)
+        with lowered(EXTEND_WS_CAP_BYTES=1):
+            call(f"{n} cu_seqlens: a sequence beyond the workspace cap", fn, qp, kp5, vp5, mix, rag(), cu_seqlens=cu5)
+        with lowered(_MAX_GRID_BH=H - 1):
+            call(f"{n} cu_seqlens: a grid of less than one sequence", fn, qp, kp5, vp5, mix, rag(), cu_seqlens=cu5)
+    # a view has no sequential fallback (equal head counts: grouped heads fall back to windows of tokens first)
+    eq = tokens(torch.float32, H, H, 5)
+    with lowered(EXTEND_WS_CAP_BYTES=1):
+        for kind in ("dense", "paged"):
+            pool, view = new_pool(kind, H)
+            call(f"{kind} view: extend beyond the workspace cap", extend, *eq[:3], mix, view, state=view)
+            call(f"{kind} view: extend counts beyond the workspace cap", extend, *eq[:3], mix, view, state=view, counts=(3, 0, 5))
+            call(f"{kind} view: verify beyond the workspace cap", verify, *eq[:3], mix, view, state=view)
+            pool_line(s, pool)
+        gq = tokens(torch.float32, H, Hk, 5)
+        call("grouped heads: extend beyond the workspace cap", extend, *gq[:3], mix, rag(), counts=(3, 0, 5))
+    # the commit: a draft of another view, packed drafts
+    other, oview = new_pool("dense", Hk)
+    got = s.call("refusal: verify on a view", verify, q5, k5, v5, mix, dview, state=dview)
+    for label, st in (("the same slots of another pool", oview), ("other slots of the pool", dense.at((0, 4, 2))), ("a state of its own", rag()),
+                      ("the pool itself", dense)):
+        call(f"commit to {label}", commit, got[1], mix, st, (1, 0, 1))
+    call("commit of a state's draft to a view", commit, draft5((6, 133, 127)), mix, dview, (1, 0, 1))
+    call("commit to an equal view of the pool", commit, got[1], mix, dense.at(SLOTS), (1, 0, 1))
+    st = rag()
+    pack = lambda k_=k5[:1], v_=v5[:1]: ops.CausalDraft(torch.cat((k_, k_[:, :3]), 1), torch.cat((v_, v_[:, :3]), 1), (3, 0, 5), False, st.lengths, None, (0, 3, 3, 8))
+    call("commit of a pack: accept beyond the counts", commit, pack(), mix, st, (1, 1, 1))
+    call("commit of a pack: matrix columns", commit, pack(), torch.rand(CAP, 2), st, (1, 0, 3))
+    call("commit of a pack: matrix rows", commit, pack(), torch.rand(2, CAP), st, (1, 0, 3))
+    call("commit of a pack: state shape", commit, pack(), mix, new_state(H, (6, 133, 127)), (1, 0, 1))
+    with lowered(_PACK_MAX_TOKENS=4):
+        call("commit of a pack: a sequence beyond the token bound", commit, pack(), mix, st, (1, 0, 3))
+
+
+def _stale(pool):
+    pool.stale = True
+    return pool
 
 
 def record():
@@ -319,16 +691,23 @@ def record():
         for part in name.split("."):
             obj = getattr(obj, part)
         doc = hashlib.sha256((obj.__doc__ or "").encode()).hexdigest()
-        lines.append(f"{name}{inspect.signature(obj)} doc {doc}")
+        try:
+            sig = inspect.signature(obj)
+        except ValueError:   # (an exception class that takes what its base takes)
+            sig = f"({', '.join(c.__name__ for c in obj.__mro__[1:])})"
+        lines.append(f"{name}{sig} doc {doc}")
     with Session(ops, _lib) as s:
         for (H, Hk), dtype, limit in itertools.product(((4, 4), (4, 2)), (torch.float32, torch.bfloat16), (None, 2)):
             saved = ops._MAX_GRID_BH
             if limit:
                 ops._MAX_GRID_BH = limit * H
             try:
-                scenarios(s, f"[H={H} Hkv={Hk} {dtype} grid={'default' if limit is None else f'{limit}H'}]", dtype, H, Hk)
+                tag = f"[H={H} Hkv={Hk} {dtype} grid={'default' if limit is None else f'{limit}H'}]"
+                scenarios(s, tag, dtype, H, Hk)
+                pool_scenarios(s, tag, dtype, H, Hk)
             finally:
                 ops._MAX_GRID_BH = saved
+        pool_methods(s)
         refusals(s)
     return lines + s.lines
 
@@ -379,6 +758,33 @@ def count_calls():
                 st = new_state(Hk, (6, 133, 127))
                 return (ops.CausalDraft(k5, v5, (3, 0, 5), False, st.lengths), mix, st, (1, 0, 3)), {}
             measure(f"mhla_causal_commit {tag}", mhla_amd.mhla_causal_commit, commit_args)
+
+            # views of pools: the ragged step and the device-positioned step
+            for kind in ("dense", "paged", "h16"):
+                def view_args():
+                    pool, view = new_pool(kind, Hk)
+                    pool.full, view.map, view.lengths
+                    return (q, k, v, mix, view), {}
+                measure(f"mhla_causal_step {kind} view {tag}", mhla_amd.mhla_causal_step, view_args)
+                measure(f"mhla_causal_step_dev {kind} view {tag}", mhla_amd.mhla_causal_step_dev, view_args)
+
+            # packed new tokens
+            cu = (0, 3, 3, 8)
+            qp, kp, vp = (torch.cat((t[:1], t[:1, :3]), 1) for t in (q5, k5, v5))
+            for kind in ("plain", "dense"):
+                def state_():
+                    if kind == "plain":
+                        return new_state(Hk, (6, 133, 127))
+                    view = new_pool(kind, Hk)[1]
+                    view.map, view.lengths
+                    return view
+
+                def packed_commit_args():
+                    st = state_()
+                    return (ops.CausalDraft(kp, vp, (3, 0, 5), False, st.lengths, None if kind == "plain" else st, cu), mix, st, (1, 0, 3)), {}
+                measure(f"mhla_causal_extend cu_seqlens {kind} {tag}", mhla_amd.mhla_causal_extend, lambda: ((qp, kp, vp, mix, state_()), dict(cu_seqlens=cu)))
+                measure(f"mhla_causal_verify cu_seqlens {kind} {tag}", mhla_amd.mhla_causal_verify, lambda: ((qp, kp, vp, mix, state_()), dict(cu_seqlens=cu)))
+                measure(f"mhla_causal_commit of a pack {kind} {tag}", mhla_amd.mhla_causal_commit, packed_commit_args)
     return out
 
 
