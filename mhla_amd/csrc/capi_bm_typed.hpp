@@ -213,6 +213,14 @@ int bm_state(const BmPlan& p, const BmCall& c, const StateArgs& a) {
         }
         return not_built<ET, DT>(name, p.fmt);
     }
+    // (bf16 tensors under the relu prologue: relu(x) + eps is an fp32 value -- the instantiation that keeps its lo part; its row dots from G_i
+    // take the hi + lo form fp16 tensors have)
+    if constexpr (!S16 && std::is_same<ET, bf16_t>::value) {
+        if (a.relu) return with_fmt<ET, DT, S16>(p.fmt, name, [&]<int FMT>() {
+            constexpr int smem = (sf_packed(FMT) && TRANS && DT <= 4) ? sp::sp_state_rd_smem<DT, false>() : sp::sp_state_smem<DT>();
+            return launch(sp::k_sp_state<ET, DT, TRANS, SNT, FMT, sp::StateVar{.lo = true}>, g, dim3(SNT), smem, c.st, name, a);
+        });
+    }
     // (forward on h16 summaries without a split normaliser pair: the instantiation that has no third row stream)
     if constexpr (TRANS == 0 && bm_fmt_built<ET, DT, S16, SF_H16>()) {
         if (p.fmt == SF_H16 && !(c.normalize && c.split) && g_recut.load())
@@ -249,6 +257,12 @@ int sp_out(const BmPlan& p, const BmCall& c, const OutArgs& o, const char* name)
             if (p.fmt != SF_F32) return not_built<ET, DT>(name, p.fmt);
             return launch(sp::k_sp_out<ET, DT, TO, SF_F32, sp::OutVar{.rope = true}>, g, blk, sp::sp_out_smem<DT, SF_F32>(), c.st, name, o);
         }
+    }
+    // (bf16 tensors under the relu prologue: the instantiation that keeps the lo part of relu(q) + eps)
+    if constexpr (!EPI && !S16 && std::is_same<ET, bf16_t>::value) {
+        if (o.relu) return with_fmt<ET, DT, S16>(p.fmt, name, [&]<int FMT>() {
+            return launch(sp::k_sp_out<ET, DT, TO, FMT, sp::OutVar{.lo = true}>, g, blk, sp::sp_out_smem<DT, FMT>(), c.st, name, o);
+        });
     }
     // (16-bit tensors on h16 summaries, D <= 64, blocks of at most 64 tokens: the instantiation of one tile per wave)
     if constexpr (!EPI && bm_fmt_built<ET, DT, S16, SF_H16>() && DT <= 4) {
@@ -380,6 +394,9 @@ int bm_tok(const BmPlan& p, const BmCall& c, const TokArgs& t) {
         if constexpr (ONE_BUILT) RC((sp_dq<ET, DT, SF_H16, sp::DqVar{.wq = true, .one = true}>(p, c, t)));
     } else if (wq) RC((with_fmt<ET, DT, S16>(p.fmt, p.n_tok[0], [&]<int FMT>() { return sp_dq<ET, DT, FMT, sp::DqVar{.wq = true}>(p, c, t); })));
     else RC((with_fmt<ET, DT, S16>(p.fmt, p.n_tok[0], [&]<int FMT>() { return sp_dq<ET, DT, FMT>(p, c, t); })));
+    if constexpr (!S16 && std::is_same<ET, bf16_t>::value) {   // (the relu prologue on bf16 tensors: relu(k) + eps keeps its lo part)
+        if (c.relu()) return with_fmt<ET, DT, S16>(p.fmt, p.n_tok[1], [&]<int FMT>() { return sp_dkv<ET, DT, FMT, sp::DkvVar{.lo = true}>(p, c, t); });
+    }
     return with_fmt<ET, DT, S16>(p.fmt, p.n_tok[1], [&]<int FMT>() { return sp_dkv<ET, DT, FMT>(p, c, t); });
 }
 

@@ -16,7 +16,7 @@ constexpr int SP_OUT_T = 512;   // 8 waves share the staged G_i: twice the loads
 // clamped onto the block's last row and dropped) and no map look-ahead
 // ROPE (bf16 tensors): the launch has rotary tables -- the rotated q is an fp32 value and keeps its lo part, like fp32 / fp16 tensors and the
 // prologue's values do (without it the variant of calls without tables, where a bf16 q is its own hi part, is unchanged)
-struct OutVar { bool epi = false, pro = false, flat = false, one = false, rope = false; };   // pro: the q prologue on load (OutArgs::pro_*)
+struct OutVar { bool epi = false, pro = false, flat = false, one = false, rope = false, lo = false; };   // pro: the q prologue on load (OutArgs::pro_*)
 template <typename T, int DT, typename TO, int FMT, OutVar V = OutVar{}>
 #ifndef SP_OUT_EPI_WAVES
 #define SP_OUT_EPI_WAVES 2   // the fused-epilogue variant takes 142 VGPRs: one workgroup per CU without spills (157 us at C4) beats two with 28 spilled registers (163 us)
@@ -24,7 +24,7 @@ template <typename T, int DT, typename TO, int FMT, OutVar V = OutVar{}>
 __global__ __launch_bounds__(SP_OUT_T, V.epi ? SP_OUT_EPI_WAVES : 2) void k_sp_out(const OutArgs a) {
     constexpr bool EPI = V.epi, PRO = V.pro, FLAT = V.flat, ONE = V.one;
     constexpr int LD = mat_ld<DT>(), KST = Geo<DT>::KST, KP = KST * 32, TILE = KP * LD;
-    constexpr bool LO = !std::is_same<T, bf16_t>::value || PRO || V.rope;
+    constexpr bool LO = !std::is_same<T, bf16_t>::value || PRO || V.rope || V.lo;   // (lo: bf16 tensors under the relu prologue -- relu(q) + eps is no bf16 value)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     static_assert(!V.rope || (std::is_same<T, bf16_t>::value && sf_has_lo(FMT) && !PRO && !FLAT && !ONE), "the rotary flag marks the bf16 variant that keeps the lo part of the rotated q");
     static_assert(!FLAT || (FMT == SF_P24 && sizeof(T) == 2), "the flat tile list serves 16-bit tensors with 24-bit summaries");

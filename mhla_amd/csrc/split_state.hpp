@@ -40,7 +40,9 @@ static_assert(!SP_PAYLOAD_OPERANDS || 5 * sp_state_rd_smem<4, true>() <= 160 * 1
 // TS: the call may have a third token tensor (MODE 0: the split pair's k_den, MODE 1: the forward output).  false (MODE 0, picked by the
 // launch when the call has no split normaliser pair): no third row stream -- it was pointed at the key rows again and its values zeroed,
 // half as many requests again in the chunk loop -- and no registers for it
-struct StateVar { bool rope = false, pro = false, ts = true; };
+// LO (bf16 tensors under the relu prologue, MHLA_FLAG_RELU_EPS): relu(x) + eps is an fp32 value, not a bf16 one -- x keeps its lo part like
+// an fp16 tensor's (and the Kl tile holds it: the row dots take the hi + lo form of fp16 tensors, not the fp16 dO rows kept there)
+struct StateVar { bool rope = false, pro = false, ts = true, lo = false; };
 template <typename T, int DT, int MODE, int NT, int FMT, StateVar V = StateVar{}>
 __global__ __launch_bounds__(NT, NT == 512 ? 4 : (V.rope ? 2 : 3)) void k_sp_state(const StateArgs a) {
     constexpr bool ROPE = V.rope, PRO = V.pro, TS = V.ts;
@@ -50,13 +52,14 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (V.rope ? 2 : 3)) void k_sp_sta
     // stored output and its residual are not read, and the forward does not write the residual (capi_common.hpp bm_rowdots_from_g)
     constexpr bool RD = MODE == 1 && sf_packed(FMT) && sizeof(T) == 2 && DT <= 4 && !ROPE;
     constexpr bool THIRD = TS && !RD;   // a third row stream exists
-    constexpr bool PAYRD = RD && sp_payrd<T, DT, FMT>();   // the row dots on G_i's payload and fp16 dO rows (kept in the Kl tile)
+    static_assert(!V.lo || (std::is_same<T, bf16_t>::value && FMT != SF_BF16 && !PRO && !ROPE), "the lo flag marks the bf16 variant of the relu prologue");
+    constexpr bool PAYRD = RD && sp_payrd<T, DT, FMT>() && !V.lo;   // the row dots on G_i's payload and fp16 dO rows (kept in the Kl tile)
     constexpr bool TN = !RD || PAYRD;   // the token tiles in the conflict-free layout (Geo::LD, mat_row)
     constexpr int DW = Geo<DT>::DW, LD = TN ? Geo<DT>::LD : Geo<DT>::LDR, CGS = Geo<DT>::CGS, RPP = NT / CGS, IT = 32 / RPP, NWV = NT / 64,
                   RT = (DT + NWV - 1) / NWV, TILE = 32 * LD;
     static_assert(IT >= 1 && RPP * IT == 32, "a 32-row chunk must be whole staging passes");
     static_assert(RPP * DW * 4 <= 4 * 32 * LD * 2, "column-sum partials must fit in the tiles");
-    constexpr bool LO = !std::is_same<T, bf16_t>::value || PRO || (ROPE && sf_has_lo(FMT));   // the token operands carry a lo part (a rotated bf16 value is an fp32 one)
+    constexpr bool LO = !std::is_same<T, bf16_t>::value || PRO || V.lo || (ROPE && sf_has_lo(FMT));   // the token operands carry a lo part (a rotated bf16 value is an fp32 one)
     constexpr bool LOY = !std::is_same<T, bf16_t>::value || (MODE == 1 && sf_has_lo(FMT));   // ... and so does y = dO / n, unless the reduced-precision form was asked for
     constexpr int GLD = mat_ld<DT>(), GT = Geo<DT>::KST * 32 * GLD;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -299,7 +302,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (V.rope ? 2 : 3)) void k_sp_sta
                         }
                         const uint2 qr = *reinterpret_cast<const uint2*>(Kh + (tt * 16 + mat_row<TN>(nl)) * LD + ct * 16 + kg * 4);   // q[s][16 ct + 4 kg ..]: hi part
                         f32x4 q4 = {__uint_as_float(qr.x << 16), __uint_as_float(qr.x & 0xffff0000u), __uint_as_float(qr.y << 16), __uint_as_float(qr.y & 0xffff0000u)};
-                        if (LO) {   // (fp16 tensors: + lo part; bf16 values are their hi part)
+                        if (LO) {   // (fp16 tensors, and bf16 ones under the relu prologue: + lo part; stored bf16 values are their hi part)
                             const uint2 ql = *reinterpret_cast<const uint2*>(Kl + (tt * 16 + mat_row<TN>(nl)) * LD + ct * 16 + kg * 4);
                             q4 += f32x4{__uint_as_float(ql.x << 16), __uint_as_float(ql.x & 0xffff0000u), __uint_as_float(ql.y << 16), __uint_as_float(ql.y & 0xffff0000u)};
                         }

@@ -248,12 +248,12 @@ __global__ __launch_bounds__(NTHREADS, (DT <= 4 && V.wq) ? 4 : 2) void k_sp_bwd_
 
 // ROPE: k is the un-rotated tensor: it is rotated on its way into the dV product (KV was formed from the rotated keys), and
 // dK_rot is turned back before dksum is added
-struct DkvVar { bool rope = false; };
+struct DkvVar { bool rope = false, lo = false; };   // lo: bf16 tensors under the relu prologue (relu(k) + eps keeps its lo part)
 template <typename T, int DT, int FMT, DkvVar V = DkvVar{}>
 __global__ __launch_bounds__(NTHREADS, 2) void k_sp_bwd_dkv(const TokArgs a) {   // (a bound of 4 -- 128 VGPRs, four workgroups per CU at D <= 64 -- measured: C2 +-0, blocks of 256 tokens 85 -> 94 us)
     constexpr bool ROPE = V.rope;
     constexpr int LD = mat_ld<DT>(), DW = Geo<DT>::DW, KST = Geo<DT>::KST, TILE = KST * 32 * LD;
-    constexpr bool LO = !std::is_same<T, bf16_t>::value;
+    constexpr bool LO = !std::is_same<T, bf16_t>::value || V.lo;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u16* Gh = reinterpret_cast<u16*>(smem_raw);   // dKV_j [d1][d2]
     u16* Gl = Gh + TILE;                          // not allocated for bf16 summaries

@@ -25,6 +25,12 @@ DEV = "cuda"
 #    i.e. <= u max|x| when nothing averages (contraction length 1: the S = 1, M <= 4 corner cases of the fuzz tests reach
 #    0.8 u .. 1.7 u) and ~ u / sqrt(L) over a contraction of length L (BASELINE shapes, L >= 64: 0.2 u .. 0.8 u observed):
 #        max|got - want| <= (1 + K) u max|want|     (TOL_BF16SUM = 2 u for outputs, GTOL_BF16SUM = 3 u for gradients).
+#    With a mixing matrix that has NEGATIVE entries (the "signed" cases below) a single-bf16 intermediate that feeds the normaliser's
+#    signed sum is amplified by kappa_n = max (sum_j |W_ij| z_j + eps) / n_i, the cancellation in that sum:
+#        max|got - want| <= (1 + K kappa) u max|want|,   kappa = max(1, kappa_n) of the case from its fp64 reference (bm_tols_signed).
+#    Every other bound carries over to signed W unchanged: what the rounding of a stored summary costs is governed by kappa_G and
+#    kappa_dKV (mix_conditioning), and the signed cases keep both below 2.5 -- below the 1.9 .. 21.6 of the w="rand" cases the bounds
+#    already hold for; the normaliser's rows stay fp32 values (bf16 hi + lo in the matrix pipe): kappa_n x 2^-16 is negligible.
 UNIT_ROUNDOFF = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
 TOL = {torch.float32: 2e-4, torch.bfloat16: 2.0 ** -8 + 1e-3, torch.float16: 2.0 ** -11 + 1e-3}
 GTOL = dict(TOL)
@@ -83,11 +89,216 @@ def make_blockmix_inputs(B, H, M, S, D, dtype, seed=1234, w="linear", split=Fals
     return q, k, v, W, do, qd, kd
 
 
-def oracle_blockmix(q, k, v, W, do, qd, kd, eps, normalize):
-    f = lambda t: None if t is None else t.float()
-    out = orc.blockmix_fwd(f(q), f(k), f(v), W, eps, f(qd), f(kd), normalize)
-    grads = orc.blockmix_bwd(f(q), f(k), f(v), W, f(do), eps, f(qd), f(kd), normalize)
+def oracle_blockmix(q, k, v, W, do, qd, kd, eps, normalize, dtype=torch.float32):
+    """The oracle's operator and closed-form gradients on the given tensors, evaluated in `dtype` (fp32: the reference of the GPU
+    tests; fp64: what tests/test_blockmix_weights_cpu.py measures that reference against)."""
+    f = lambda t: None if t is None else t.to(dtype)
+    out = orc.blockmix_fwd(f(q), f(k), f(v), f(W), eps, f(qd), f(kd), normalize)
+    grads = orc.blockmix_bwd(f(q), f(k), f(v), f(W), f(do), eps, f(qd), f(kd), normalize)
     return out, grads
+
+
+# ---- mixing matrices with signs and with empty rows / columns, and an eps the results depend on -----------------------------------
+# make_blockmix_inputs draws W >= 0 without an empty row or column and every test passes eps = 1e-6 against normalisers in the
+# hundreds: a kernel family that drops eps, a mixing kernel that sizes a row multiplier from w instead of |w|, or a store skipped for
+# an all-zero row would pass.  The cases below (tests/test_gpu_blockmix_weights.py on the GPU; tests/test_blockmix_weights_cpu.py
+# shows without one that they are well conditioned and that the checks reject the errors they are meant for) use
+#  * "signed": W = I + R, R with a zero diagonal, entries uniform in [-1, 1], every row rescaled to an absolute sum of 0.5 -- the
+#    normaliser n_i[s] = z_i[s] + sum_j R_ij z_j[s] + eps stays positive (z > 0) and loses at most a factor kappa_n <= 4 to cancellation;
+#  * "sparse": unit diagonal + two further entries per row (uniform in [0.25, 1], seeded columns), then row M // 2 and column M // 3
+#    set to zero: that row's numerator is exactly 0 and its n exactly eps (out exactly 0), that column feeds nobody (dk, dv exactly 0);
+#  * "signed_full": 2 rand - 1, for normalize=False only (a normaliser with these weights crosses zero);
+#  * eps = visible_eps(): the power of two nearest to median(z) / 4, z the normaliser's product -- replacing it by 1e-6 moves every
+#    result by 0.1 .. 1.8 of its maximum.
+# Tolerances with these inputs: bm_tols() unchanged, but (1 + K kappa) u for summaries="bf16" with a signed W (bm_tols_signed; both
+# derived at the top of this file).
+MIX_KINDS = ("signed", "sparse")
+
+
+def make_mix_weights(kind, M, generator):
+    """A seeded [M, M] fp32 mixing matrix of one of the kinds above."""
+    if kind == "signed_full":
+        return 2 * torch.rand(M, M, generator=generator) - 1
+    if kind == "signed":
+        R = (2 * torch.rand(M, M, generator=generator) - 1).fill_diagonal_(0.0)
+        return torch.eye(M) + R * (0.5 / R.abs().sum(1, keepdim=True).clamp_min(1e-30))
+    if kind == "sparse":
+        assert M >= 3
+        W = torch.eye(M)
+        for i in range(M):   # two distinct columns other than i
+            others = torch.randperm(M - 1, generator=generator)[:2]
+            W[i, others + (others >= i).long()] = 0.25 + 0.75 * torch.rand(2, generator=generator)
+        W[M // 2, :] = 0.0
+        W[:, M // 3] = 0.0
+        return W
+    raise ValueError(kind)
+
+
+def _normaliser_product(q, k, M, q_den=None, k_den=None):
+    """z_j[s] = Q_j[s] . ksum_j of the normaliser's pair in fp64: [(B H), M, S]."""
+    qd, kd = (q, k) if q_den is None else (q_den, k_den)
+    qb, kb = orc._to_blocks(qd.double(), M), orc._to_blocks(kd.double(), M)
+    return torch.matmul(qb, kb.sum(-2).unsqueeze(-1)).squeeze(-1)
+
+
+def visible_eps(q, k, M, q_den=None, k_den=None):
+    """eps = 2^round(log2(median(z) / 4)): a power of two (exact in every format, whichever side of a product it is applied on) a
+    quarter of the typical normaliser product, so that a result computed without it, or with another one, is far outside any tolerance."""
+    import math
+    return 2.0 ** round(math.log2(_normaliser_product(q, k, M, q_den, k_den).median().item() / 4))
+
+
+def mix_conditioning(q, k, v, W, do, eps, q_den=None, k_den=None, normalize=True):
+    """How much cancellation a (signed) W puts into the three mixes of a case, from the fp64 reference on its tensors:
+      n_min     min n (the normaliser must stay positive);
+      kappa_n   max_{i,s} (sum_j |W_ij| z_j[s] + eps) / n_i[s]          (1 for W >= 0);
+      kappa_G   max_{bh,i} sum_j |W_ij| max|KV_j| / max|G_i|            (rows of W that are zero excluded: G_i is exactly 0);
+      kappa_dKV max_{bh,j} sum_i |W_ij| max|dG_i| / max|dKV_j|          (columns that are zero excluded)."""
+    M = W.shape[0]
+    Wd = W.double()
+    f = lambda t: None if t is None else t.double()
+    _, aux = orc.blockmix_fwd(f(q), f(k), f(v), Wd, eps, f(q_den), f(k_den), normalize, return_aux=True)
+    res = {}
+    if normalize:
+        res["n_min"] = aux["n"].min().item()
+        res["kappa_n"] = ((torch.einsum("ij,bjs->bis", Wd.abs(), aux["z"].abs()) + eps) / aux["n"]).max().item()
+        dP = orc._to_blocks(f(do), M) / aux["n"].unsqueeze(-1)
+    else:
+        res["n_min"], res["kappa_n"] = float("inf"), 1.0
+        dP = orc._to_blocks(f(do), M)
+    dG = torch.matmul(orc._to_blocks(f(q), M).transpose(-2, -1), dP)
+    amax = lambda t: t.abs().amax((-2, -1))                                        # [(B H), M]
+    rows, cols = Wd.abs().sum(1) > 0, Wd.abs().sum(0) > 0
+    res["kappa_G"] = ((amax(aux["kv"]) @ Wd.abs().t()) / amax(aux["g"]).clamp_min(1e-300))[:, rows].max().item()
+    dKV = torch.einsum("ij,bixy->bjxy", Wd, dG)
+    res["kappa_dKV"] = ((amax(dG) @ Wd.abs()) / amax(dKV).clamp_min(1e-300))[:, cols].max().item()
+    return res
+
+
+def bm_tols_signed(dtype, summaries, kappa_n):
+    """bm_tols() for a case whose W has negative entries: unchanged but for summaries="bf16", (1 + K max(1, kappa_n)) u there."""
+    if summaries == "bf16" and dtype == torch.bfloat16:
+        u, kappa = UNIT_ROUNDOFF[dtype], max(1.0, kappa_n)
+        return (1 + kappa) * u, (1 + 2 * kappa) * u, (1 + 2 * kappa) * u
+    return bm_tols(dtype, summaries)
+
+
+_BF, _HF, _F32 = torch.bfloat16, torch.float16, torch.float32
+_SN, _SNF, _FAST, _SP, _GEN = "small-sequence bf16", "small-sequence fp32", "bf16 fast path", "split-operand", "generic"
+# The rows tests/test_gpu_blockmix_weights.py runs with both W kinds and the visible eps:
+# (id, dtype, B, H, M, S, D, options, reaches); options: summaries / split (a separate normaliser pair) / gather (a random token
+# permutation as the gather map) / no_smalln / force_generic; reaches = (family, summary format, launches the forward's description
+# names, launches the backward's names) -- asserted through mhla_amd.describe_dispatch in tests/test_blockmix_weights_cpu.py.
+MIX_CASES = [
+    ("A1", _BF, 3, 2, 16, 16, 72, dict(summaries="split"), (_SN, "none (score tiles in LDS as bf16 hi + lo", ["k_sn_fwd<5,hl>"], ["k_sn_bwd<5,hl>"])),
+    ("A2", _BF, 3, 2, 16, 16, 72, dict(summaries="bf16"), (_SN, "none (score tiles as single bf16", ["k_sn_fwd<5>"], ["k_sn_bwd<5>"])),
+    ("A3", _BF, 2, 2, 9, 16, 64, dict(gather=True), (_SN, "none (score tiles in LDS as bf16 hi + lo", ["k_sn_fwd<4,hl>"], ["k_sn_bwd<4,hl>"])),
+    ("B1", _F32, 3, 2, 13, 16, 24, {}, (_SNF, "none", ["k_snf_fwd<4>"], ["k_snf_bwd<4>"])),
+    ("B2", _F32, 2, 2, 16, 16, 72, {}, (_SNF, "none", ["k_snf_fwd<5>"], ["k_snf_bwd<5>"])),
+    ("C1", _BF, 2, 3, 16, 32, 64, dict(summaries="bf16"), (_FAST, "bf16", ["k_fs_wz<0>"], ["k_fs_dw"])),
+    ("C2", _BF, 2, 3, 33, 20, 64, dict(summaries="bf16", gather=True), (_FAST, "bf16", ["k_fs_wz<0>"], ["k_fs_dw"])),
+    ("D1", _BF, 2, 3, 16, 32, 64, {}, (_SP, "h16", ["k_sp_mixh<0>"], ["k_sp_mixh<1,dw>"])),
+    ("D2", _HF, 2, 2, 40, 24, 64, {}, (_SP, "h16", ["k_sp_mixh<0>"], ["k_sp_mixh<1,dw>"])),
+    ("D3", _BF, 1, 2, 70, 16, 56, {}, (_SP, "h16", ["k_sp_mixh<0>"], ["k_sp_mixh<1,dw>"])),
+    ("D4", _BF, 2, 2, 16, 16, 64, dict(no_smalln=True), (_SP, "h16", ["k_sp_mixh<0>"], ["k_sp_mixh<1,dw>"])),
+    ("D5", _BF, 2, 2, 5, 37, 80, dict(split=True), (_SP, "h16", ["k_sp_mixh<0>", "k_wz<0>"], ["k_sp_mixh<1,dw>", "k_wz<1>", "k_dw"])),
+    ("E1", _BF, 4, 8, 130, 16, 64, {}, (_SP, "h16", ["k_sp_mixh2<0>"], ["k_sp_mixh2<1>", "k_sp_dwr<3,h16>"])),
+    ("E2", _BF, 1, 2, 130, 16, 64, {}, (_SP, "h16", ["k_sp_mixh<0>"], ["k_sp_mixh<1>", "k_sp_dwr<3,h16>"])),
+    ("E3", _BF, 1, 2, 200, 16, 64, {}, (_SP, "h16", ["k_sp_mixh<0>"], ["k_sp_mixh<1>", "k_sp_dwr<4,h16>"])),
+    ("F1", _BF, 2, 2, 40, 24, 64, dict(summaries="split"), (_SP, "p24", ["k_sp_mixr<0>"], ["k_sp_mixr<1,dw>"])),
+    ("F2", _HF, 1, 2, 5, 37, 80, dict(summaries="split", split=True), (_SP, "p24", ["k_sp_mixr<0>", "k_wz<0>"], ["k_sp_mixr<1,dw>", "k_wz<1>", "k_dw"])),
+    ("F3", _BF, 1, 2, 70, 8, 64, {}, (_SP, "p24", ["k_sp_mixr<0>"], ["k_sp_mixr<1,dw>"])),
+    ("G1", _F32, 1, 2, 70, 8, 64, {}, (_SP, "fp32 words", ["k_sp_mixr<0>"], ["k_sp_mixr<1,dw>"])),
+    ("G2", _F32, 1, 2, 150, 21, 128, dict(split=True, gather=True), (_SP, "p24", ["k_sp_mixr<0>", "k_wz<0>"], ["k_sp_mixr<1>", "k_wz<1>", "k_sp_dwt", "k_dw"])),
+    ("G3", _F32, 1, 2, 3, 33, 128, dict(split=True), (_SP, "p24", ["k_sp_mixr<0>", "k_wz<0>"], ["k_sp_mixr<1,dw>", "k_wz<1>", "k_dw"])),
+    ("H1", _BF, 1, 2, 200, 16, 64, dict(summaries="bf16"), (_SP, "bf16", ["k_s16_state<0>", "k_sp_mixr_dma<0>", "k_s16_out"], ["k_sp_mixr_dma<1>", "k_sp_dwr<4>"])),
+    ("H2", _BF, 2, 3, 77, 16, 64, dict(summaries="bf16"), (_SP, "bf16", ["k_s16_state<0>", "k_sp_mixr<0>", "k_wz<0>"], ["k_sp_mixr<1>", "k_wz<1>"])),
+    ("I1", _F32, 1, 2, 260, 8, 64, {}, (_SP, "fp32 words", ["k_sp_mix<0>", "k_wz<0>"], ["k_sp_mix<1>", "k_wz<1>", "k_sp_dw"])),
+    ("J1", _F32, 1, 2, 9, 20, 40, dict(force_generic=True), (_GEN, "fp32 words", ["k_mix<0,0>"], ["k_mix<1,0>"])),
+    ("J2", _F32, 2, 2, 5, 7, 12, {}, (_GEN, "fp32 words", ["k_mix<0,0>"], ["k_mix<1,0>"])),
+    # head dim above 128: ops._blockmix_wide_head's own normaliser and eps over un-normalised calls on 72-wide slices (what `reaches` describes)
+    ("K1", _F32, 1, 2, 6, 20, 136, {}, (_SP, "fp32 words", ["k_sp_mixr<0>"], ["k_sp_mixr<1,dw>"])),
+]
+MIX_CASE = {c[0]: c for c in MIX_CASES}
+# the relu(x) + eps prologue with eps = MIX_RELU_EPS on raw randn q, k: (id, dtype, B, H, M, S, D, options, reaches)
+MIX_RELU_EPS = 0.25
+MIX_RELU_CASES = [
+    ("R1", _F32, 2, 3, 16, 16, 72, {}, (_SNF, "none", ["k_snf_fwd<5>"], ["k_snf_bwd<5>"])),
+    ("R2", _BF, 2, 2, 16, 40, 72, {}, (_SP, "h16", ["k_sp_mixh<0>"], ["k_sp_mixh<1,dw>"])),
+    ("R3", _BF, 2, 2, 80, 16, 64, {}, (_SP, "h16", ["k_sp_mixh<0>"], ["k_sp_mixh<1,dw>"])),
+    # bf16 tensors on the other two summary formats: relu(x) + eps is no bf16 value, the token operands must keep its lo part there too
+    ("R4", _BF, 2, 2, 16, 24, 64, dict(summaries="split"), (_SP, "p24", ["k_sp_mixr<0>"], ["k_sp_mixr<1,dw>"])),
+    ("R5", _BF, 1, 2, 12, 24, 128, {}, (_SP, "fp32 words", ["k_sp_mixr<0>"], ["k_sp_mixr<1,dw>"])),
+]
+
+
+# Seeds are M * 1000 + S * 10 + D but for three rows whose "signed" inputs miss the conditions there (kappa_n = 4.5 at D4, 4.8 at G3;
+# J2's contraction over D = 12 and 7 tokens lets z vary tenfold between tokens, and n crosses zero): these take the smallest seed
+# 1, 2, 3, ... at which the conditions hold.  A choice of INPUTS by conditions on the fp64 reference -- no kernel result enters.
+MIX_SEEDS = {"D4": 1, "G3": 3, "J2": 4}
+
+
+def mix_case_seed(case):
+    return MIX_SEEDS.get(case[0], case[4] * 1000 + case[5] * 10 + case[6])
+
+
+def mix_case_per_block(case):
+    """Rows whose arithmetic keeps >= 16 significand bits in every summary element (fp32 tensors, summaries="split", the generic
+    kernels): their out, dq, dk, dv are held to the tolerance block by block as well (check_chunks with chunk = S)."""
+    return case[1] == torch.float32 or case[7].get("summaries") == "split" or bool(case[7].get("force_generic"))
+
+
+def make_mix_case(case, kind, eps=None):
+    """The tensors of a MIX_CASES row with a W of `kind`: q, k, v, do, qd, kd (block-major, rounded to the row's dtype), W, idx (the
+    gather map or None) and eps (given, or the visible one)."""
+    _, dtype, B, H, M, S, D, opt, _ = case
+    seed = mix_case_seed(case)
+    q, k, v, _, do, qd, kd = make_blockmix_inputs(B, H, M, S, D, dtype, seed, "rand", opt.get("split", False))
+    W = make_mix_weights(kind, M, torch.Generator().manual_seed(seed + 1))
+    idx = torch.randperm(M * S, generator=torch.Generator().manual_seed(seed + 2)).int() if opt.get("gather") else None
+    return dict(q=q, k=k, v=v, do=do, qd=qd, kd=kd, W=W, idx=idx, eps=visible_eps(q, k, M, qd, kd) if eps is None else eps)
+
+
+def mix_case_reference(t, normalize=True, dtype=torch.float32):
+    """The oracle on the tensors of make_mix_case(): out and the dict of gradients."""
+    return oracle_blockmix(t["q"], t["k"], t["v"], t["W"], t["do"], t["qd"], t["kd"], t["eps"], normalize, dtype)
+
+
+def make_mix_relu_case(case, kind):
+    """The tensors of a MIX_RELU_CASES row: RAW randn q, k (the kernels apply relu(x) + eps), v, do in the row's dtype, W of `kind`."""
+    _, dtype, B, H, M, S, D, _, _ = case
+    g = torch.Generator().manual_seed(mix_case_seed(case))
+    q, k, v, do = (torch.randn(B, M * S, H, D, generator=g).to(dtype) for _ in range(4))
+    W = make_mix_weights(kind, M, torch.Generator().manual_seed(mix_case_seed(case) + 1))
+    return dict(q=q, k=k, v=v, do=do, qd=None, kd=None, W=W, idx=None, eps=MIX_RELU_EPS)
+
+
+def mix_relu_reference(t, dtype=torch.float32, prologue=None, eps=None):
+    """The oracle on relu(q) + c, relu(k) + c with the normaliser's eps; dq, dk masked by x > 0 (the prologue's gradient).  c = eps =
+    the case's unless given: `prologue` / `eps` evaluate the operator with another constant on one side (what a kernel that takes
+    the two from different places would compute)."""
+    eps = t["eps"] if eps is None else eps
+    c = eps if prologue is None else prologue
+    qf, kf = torch.relu(t["q"].to(dtype)) + c, torch.relu(t["k"].to(dtype)) + c
+    out, g = oracle_blockmix(qf, kf, t["v"], t["W"], t["do"], None, None, eps, True, dtype)
+    g["dq"], g["dk"] = g["dq"] * (t["q"] > 0), g["dk"] * (t["k"] > 0)
+    return out, g
+
+
+def zero_rows_and_columns(W):
+    """(indices of the rows of W that are entirely zero, of the columns)."""
+    return (W == 0).all(1).nonzero().flatten().tolist(), (W == 0).all(0).nonzero().flatten().tolist()
+
+
+def check_dw_rows(got, want, W, tol):
+    """dW in two pieces, each normalised by its own maximum: the rows of W that are entirely zero (their n is eps alone: dW there is
+    several times the other rows' and would hide them under check()'s global maximum) and all other rows."""
+    zr, _ = zero_rows_and_columns(W)
+    if not zr:
+        return check("dW", got, want, tol)
+    rest = [i for i in range(W.shape[0]) if i not in zr]
+    check("dW (rows of W that are zero)", got[zr], want[zr], tol)
+    return check("dW (other rows)", got[rest], want[rest], tol)
 
 
 # The launch shapes of the rotary operator (tests/test_gpu_blockmix_rope.py holds the kernels to fp64 at them, tests/test_rope_ref_cpu.py
@@ -144,6 +355,33 @@ def rope_blockmix_fp64(q, k, v, W, do, cos, sin, perm=None, normalize=True, eps=
     out = torch.empty_like(o)
     out[:, rows] = o.detach()
     return out, t[0].grad, t[1].grad, t[2].grad, t[3].grad
+
+
+def mix_extra_checks(got, want, W, S, tols, per_block):
+    """What a case with a given W is held to beyond check(): `got`, `want`: name -> tensor, token tensors [B, M * S, H, D] in block-major
+    order.  Everything finite; the blocks whose row of W is zero have an exactly zero output, those whose column is zero exactly zero
+    dk, dv (and dk_den); with `per_block`, out / dq / dk / dv within their tolerance of every block's own maximum (check_chunks)."""
+    for name, g in got.items():
+        assert bool(torch.isfinite(g.float()).all()), f"{name}: not finite"
+    zr, zc = zero_rows_and_columns(W)
+    blocks = lambda t: t.reshape(t.shape[0], W.shape[0], S, *t.shape[2:])
+    assert not bool(blocks(got["out"])[:, zr].any()), f"out of blocks {zr} (rows of W that are zero) must be exactly zero"
+    for name in ("dk", "dv", "dk_den"):
+        if name in got:
+            assert not bool(blocks(got[name])[:, zc].any()), f"{name} of blocks {zc} (columns of W that are zero) must be exactly zero"
+    if per_block:
+        for name in ("out", "dq", "dk", "dv"):
+            check_chunks(name, got[name], want[name], tols[0] if name == "out" else tols[1], chunk=S)
+
+
+def make_mix_rope_case(case):
+    """make_rope_inputs of a ROPE_CASES row in fp32 with a "signed" W and the visible eps of its (un-rotated) normaliser pair:
+    (q, k, v, W, do, cos, sin, perm), eps."""
+    B, H, M, S, D, _, gather = case
+    q, k, v, _, do, cos, sin, perm = make_rope_inputs(B, H, M, S, D, torch.float32, seed=rope_case_seed(case), gather=gather)
+    W = make_mix_weights("signed", M, torch.Generator().manual_seed(rope_case_seed(case) + 1))
+    rows = slice(None) if perm is None else perm.long()
+    return (q, k, v, W, do, cos, sin, perm), visible_eps(q[:, rows], k[:, rows], M)
 
 
 def to_dev(*ts):

@@ -3,21 +3,33 @@ import pytest
 import torch
 
 from conftest import load_golden
-from gpu_util import poison, DEV, GTOL, TOL, DW_TOL, GTOL_BF16SUM, TOL_BF16SUM, bm_tols, check, make_blockmix_inputs, oracle_blockmix, to_dev
+from gpu_util import (poison, DEV, GTOL, TOL, DW_TOL, GTOL_BF16SUM, TOL_BF16SUM, bm_tols, bm_tols_signed, check, check_dw_rows, make_blockmix_inputs,
+                      mix_conditioning, mix_extra_checks, oracle_blockmix, to_dev)
 from oracle import mhla_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 
-def run_case(B, H, M, S, D, dtype, normalize=True, split=False, w="linear", idx=None, seed=1234, summaries="tf32", **opkw):
+def run_case(B, H, M, S, D, dtype, normalize=True, split=False, w="linear", idx=None, seed=1234, summaries="tf32", W=None, eps=1e-6,
+             per_block=False, **opkw):
     """One forward + backward through mhla_amd.mhla_blockmix against the oracle.  summaries="tf32" (the library's default: block
     summaries stored with 11 significand bits where the kernels have the 2-byte format, >= 16 elsewhere) and "split" (>= 16 bits
     everywhere): the reference's arithmetic on the given tensors, held to one final rounding + 1e-3 (1e-3 for the fp32-stored dW);
-    "bf16": the opt-in reduced-precision form (single-bf16 summaries / intermediates) at its (1 + K) u bounds."""
+    "bf16": the opt-in reduced-precision form (single-bf16 summaries / intermediates) at its (1 + K) u bounds.
+    W (a mixing matrix in place of the seeded one: gpu_util.make_mix_weights), eps and per_block (out, dq, dk, dv additionally held to
+    the tolerance block by block) serve tests/test_gpu_blockmix_weights.py: with a W given, dW is checked in two pieces (the rows of W
+    that are zero, the others), everything must be finite, a block whose row of W is zero must have an exactly zero output and one
+    whose column is zero exactly zero dk, dv, and a normalised "bf16" case with negative weights takes bm_tols_signed's bound.
+    Returns the results by name, in block-major token order."""
     import mhla_amd
     otol, gtol, wtol = bm_tols(dtype, summaries)
-    q, k, v, W, do, qd, kd = make_blockmix_inputs(B, H, M, S, D, dtype, seed, w, split)
-    want, wg = oracle_blockmix(q, k, v, W, do, qd, kd, 1e-6, normalize)
+    q, k, v, W0, do, qd, kd = make_blockmix_inputs(B, H, M, S, D, dtype, seed, w, split)
+    given = W is not None
+    if not given:
+        W = W0
+    elif normalize and bool((W < 0).any()):
+        otol, gtol, wtol = bm_tols_signed(dtype, summaries, mix_conditioning(q, k, v, W, do, eps, qd, kd)["kappa_n"])
+    want, wg = oracle_blockmix(q, k, v, W, do, qd, kd, eps, normalize)
     if idx is not None:   # scatter tokens so that block-major position p lives at row idx[p]
         def scat(t):
             if t is None:
@@ -32,7 +44,7 @@ def run_case(B, H, M, S, D, dtype, normalize=True, split=False, w="linear", idx=
         dqd.requires_grad_(True)
         dkd.requires_grad_(True)
     poison()
-    out = mhla_amd.mhla_blockmix(dq_, dk_, dv_, dW_, eps=1e-6, q_den=dqd, k_den=dkd, normalize=normalize,
+    out = mhla_amd.mhla_blockmix(dq_, dk_, dv_, dW_, eps=eps, q_den=dqd, k_den=dkd, normalize=normalize,
                                  block_index=None if idx is None else idx.to(DEV), summaries=summaries, **opkw)
     poison()
     out.backward(ddo)
@@ -44,11 +56,19 @@ def run_case(B, H, M, S, D, dtype, normalize=True, split=False, w="linear", idx=
     check("dq", gather(leaves[0].grad), wg["dq"], gtol)
     check("dk", gather(leaves[1].grad), wg["dk"], gtol)
     check("dv", gather(leaves[2].grad), wg["dv"], gtol)
-    # M == 1: the output does not depend on W (numerator and normaliser scale together), dW ~ 0
-    check("dW", leaves[3].grad, wg["dW"], wtol, atol=(1e9 if dtype != torch.float32 else 1e-3) if M == 1 else 0.0)
+    if given:
+        check_dw_rows(leaves[3].grad, wg["dW"], W, wtol)
+    else:
+        # M == 1: the output does not depend on W (numerator and normaliser scale together), dW ~ 0
+        check("dW", leaves[3].grad, wg["dW"], wtol, atol=(1e9 if dtype != torch.float32 else 1e-3) if M == 1 else 0.0)
+    got = {"out": gather(out.detach()), "dq": gather(leaves[0].grad), "dk": gather(leaves[1].grad), "dv": gather(leaves[2].grad), "dW": leaves[3].grad}
     if split and normalize:
         check("dq_den", gather(dqd.grad), wg["dq_den"], gtol)
         check("dk_den", gather(dkd.grad), wg["dk_den"], gtol)
+        got.update(dq_den=gather(dqd.grad), dk_den=gather(dkd.grad))
+    if given or per_block:
+        mix_extra_checks(got, dict(wg, out=want), W, S, (otol, gtol, wtol), per_block)
+    return got
 
 
 @pytest.mark.parametrize("tag", ["dit_a", "dit_b", "vit_a"])
