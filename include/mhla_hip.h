@@ -768,6 +768,37 @@ int mhla_causal_varlen_state_init_paged_h16(mhla_view k, mhla_view v, const floa
                                             int V, int chunk, int n_chunks, const int32_t* chunk_tab_dev, const int32_t* chunk_dst_dev, void* ws,
                                             size_t ws_bytes, int dtype, void* stream);
 
+/* Swap: the state of chosen slots of a paged pool OUT into one contiguous buffer (the blob) and back IN -- into other slots, other
+ * pages or another pool of the same Hkv, K, V and page format (added without a change of any existing signature or behaviour:
+ * MHLA_ABI_VERSION stays 9).  A finished page is immutable, so the state of a sequence -- its finished pages, P, Cur, pos, full --
+ * goes out and comes back with every bit intact: no arithmetic touches an element, an h16 page travels as payload and multipliers and
+ * is never decoded.  One entry point per direction serves both page formats: page_mult NULL means fp32 pages.
+ * The blob is a run of ITEMS, each starting on a 16-byte boundary, every item of a kind the same size:
+ *   n_seqs sequence items   P [Hkv][K][V] fp32 | Cur [Hkv][K][V] fp32 | pos, full as two int32, zeros up to 16 bytes
+ *   n_pages page items      fp32 pages: [Hkv][K][V] fp32;  h16 pages: _Float16 [Hkv][K][V] | float [Hkv][K V / 64] | zeros up to 16 bytes
+ * so items [i0, i1) are one contiguous byte range, and mhla_causal_swap_ws_bytes (pure host arithmetic; page_format 0: fp32, 1: h16;
+ * 0 for sizes it does not take) gives the size of a blob -- of one item with (1, 0) and (0, 1).
+ *   items_dev      device int32 [n_seqs + n_pages_moved]: the pool slot of every sequence item, then the pool page of every page item;
+ *                  slots distinct, pages distinct.  Which page of the blob holds which chunk of which sequence is the caller's record
+ *                  (and its page table's on the way in): a page that several sequences share is one item
+ *   i0, i1         the call moves the items [i0, i1) of that list, blob_at is the device address where item i0 begins (16-byte
+ *                  aligned): a blob that lives on the host is staged through a smaller device buffer in slices of whole items
+ *   full_dev       may be NULL: out, the flag reads as 0; in, the blob's flag is dropped
+ * mhla_causal_swap_out_paged reads the pool and writes every byte of its items, padding included; mhla_causal_swap_in_paged writes
+ * the pages, P, Cur, pos_dev and full_dev of the slots and pages the list names and nothing else.  As a defence only, an entry
+ * outside 0 .. n_slots - 1 (a sequence item) or 0 .. n_pages - 1 (a page item) forms no address and its item is skipped.
+ * One launch, stream-ordered, no synchronisation.  MHLA_EINVAL before any launch: non-positive Hkv, K, V, n_pages or n_slots;
+ * K V % 4 != 0; page_mult given with K V % 64 != 0; pages, P, Cur or blob_at null or not 16-byte aligned; page_mult (when given),
+ * pos_dev, full_dev (when given) or items_dev null or not 4-byte aligned; negative n_seqs or n_pages_moved; a range outside
+ * 0 <= i0 <= i1 <= n_seqs + n_pages_moved.  An empty range returns 0 without a launch. */
+size_t mhla_causal_swap_ws_bytes(int n_seqs, int n_pages, int Hkv, int K, int V, int page_format);
+int mhla_causal_swap_out_paged(const void* pages, const float* page_mult, int n_pages, const float* P, const float* Cur, const int32_t* pos_dev,
+                               const int32_t* full_dev, int n_slots, const int32_t* items_dev, int n_seqs, int n_pages_moved, int i0, int i1,
+                               void* blob_at, int Hkv, int K, int V, void* stream);
+int mhla_causal_swap_in_paged(void* pages, float* page_mult, int n_pages, float* P, float* Cur, int32_t* pos_dev, int32_t* full_dev, int n_slots,
+                              const int32_t* items_dev, int n_seqs, int n_pages_moved, int i0, int i1, const void* blob_at, int Hkv, int K, int V,
+                              void* stream);
+
 /* ---- prologue: q / k of the Wan host -------------------------------------- */
 
 /*

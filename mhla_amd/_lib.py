@@ -204,6 +204,12 @@ for _name in ("extend", "verify"):
         c_float, c_int, c_void_p])
 SIGNATURES["mhla_causal_commit_packed"] = (c_int, [View, View] + _packed_state + [
     c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
+# swap of a paged pool's slots: (pages, page_mult or null, n_pages, P, Cur, pos_dev, full_dev or null, n_slots), (items_dev, n_seqs,
+# n_pages_moved), the item range (i0, i1), the device address of item i0, Hkv, K, V, stream
+SIGNATURES["mhla_causal_swap_ws_bytes"] = (c_size_t, [c_int] * 6)
+for _name in ("out", "in"):
+    SIGNATURES[f"mhla_causal_swap_{_name}_paged"] = (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                             c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p])
 
 _lib = None
 

@@ -1,11 +1,12 @@
 // C ABI, causal operator: the decode state of a sequence, the single-token step and the extension by T tokens
-// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged, the grouped-query forms mhla_causal_*_gqa of the ragged entry points, their forms on chosen rows of a state pool, mhla_causal_*_slots, those on a pool whose finished chunks are pages, mhla_causal_*_paged, the extend, verify and commit on packed new tokens, mhla_causal_*_packed, and the step, the device-positioned step and the pack prefill on a pool of 2-byte pages, mhla_causal_*_paged_h16; kernels: causal_step.hpp, causal_extend.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
+// (mhla_causal_state_init, mhla_causal_varlen_state_init, mhla_causal_step, mhla_causal_step_ragged, mhla_causal_step_dev, mhla_causal_extend, mhla_causal_extend_ragged, mhla_causal_verify_ragged, mhla_causal_commit_ragged, the grouped-query forms mhla_causal_*_gqa of the ragged entry points, their forms on chosen rows of a state pool, mhla_causal_*_slots, those on a pool whose finished chunks are pages, mhla_causal_*_paged, the extend, verify and commit on packed new tokens, mhla_causal_*_packed, the step, the device-positioned step and the pack prefill on a pool of 2-byte pages, mhla_causal_*_paged_h16, and the swap of a paged pool's slots out into one buffer and back in, mhla_causal_swap_{out,in}_paged; kernels: causal_step.hpp, causal_extend.hpp, causal_swap.hpp).  The prefill state reuses the generic path's exact-fp32 chunk products (blockmix.hpp
 // k_bm_state<MODE 2>) written straight into the state's layout; the 16-bit pipeline's 11-bit summaries are never decoded.
 #include "capi_common.hpp"
 #include "blockmix.hpp"
 #include "causal.hpp"
 #include "causal_step.hpp"
 #include "causal_extend.hpp"
+#include "causal_swap.hpp"
 
 using namespace mhla;
 using namespace mhla::capi;
@@ -479,6 +480,39 @@ int cx_commit_chain(mhla_view k, mhla_view v, const float* mix, int ldmix, float
     return launch(k_cx_advance, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, "k_cx_advance", pos_dev, (const int*)nval, B, sl.map, sl.n);
 }
 
+// the two directions of a swap (OUT: pool -> blob): the checks, then one launch of k_cs_swap over the items [i0, i1), whose first
+// begins at `blob`.  mult null: fp32 pages
+template <bool OUT>
+int cs_swap(void* pages, float* mult, int n_pages, float* P, float* Cur, int32_t* pos_dev, int32_t* full_dev, int n_slots, const int32_t* items_dev,
+            int n_seqs, int n_moved, int i0, int i1, void* blob, int Hkv, int K, int V, void* stream) {
+    if (Hkv <= 0 || K <= 0 || V <= 0 || n_pages <= 0 || n_slots <= 0)
+        return fail(MHLA_EINVAL, "non-positive size Hkv=%d K=%d V=%d n_pages=%d n_slots=%d", Hkv, K, V, n_pages, n_slots);
+    if (((long)K * V) % 4) return fail(MHLA_EINVAL, "K=%d V=%d: K*V must be a multiple of 4 (16-byte pieces)", K, V);
+    if (mult && ((long)K * V) % CSH_GROUP) return fail(MHLA_EINVAL, "K=%d V=%d: h16 pages need K*V %% %d == 0 (one multiplier per %d elements)", K, V, CSH_GROUP, CSH_GROUP);
+    if (!pages || !P || !Cur || !blob) return fail(MHLA_EINVAL, "pages, P, Cur or the blob null");
+    if (((uintptr_t)pages | (uintptr_t)P | (uintptr_t)Cur | (uintptr_t)blob) % 16) return fail(MHLA_EINVAL, "pages, P, Cur and the blob must be 16-byte aligned");
+    if (mult) RC(cst_check_dev("page_mult", mult));
+    RC(cst_check_dev("pos_dev", pos_dev));
+    if (full_dev) RC(cst_check_dev("full_dev", full_dev));
+    RC(cst_check_dev("items_dev", items_dev));
+    if (n_seqs < 0 || n_moved < 0 || (long)n_seqs + n_moved > 0x7fffffffL) return fail(MHLA_EINVAL, "n_seqs=%d and n_pages_moved=%d must not be negative", n_seqs, n_moved);
+    if (i0 < 0 || i1 < i0 || i1 > n_seqs + n_moved)
+        return fail(MHLA_EINVAL, "items [%d, %d) are outside the list of %d sequences and %d pages", i0, i1, n_seqs, n_moved);
+    if (i0 == i1) return MHLA_OK;
+    const int fmt = mult ? PF_H16 : PF_F32;
+    const CsSwapLayout l = cs_swap_layout(Hkv, K, V, fmt);
+    const CsSwapArgs a{(char*)blob, items_dev, i0, i1, n_seqs, (char*)pages, mult, n_pages, P, Cur, pos_dev, full_dev, n_slots,
+                       l.state_pieces, l.pay_pieces, l.n_mult, l.n_mult_pad, l.seq_bytes, l.page_bytes};
+    // memory-bound: about 2048 workgroups at the most, the rest grid-strided -- x over the 16-byte pieces of an item, four to a lane of the
+    // smaller kind of item in the range (the four requests cs_swap_run keeps in flight; the larger kind takes more rounds), y over items
+    const long pieces = std::min(i0 < n_seqs ? l.state_pieces : l.pay_pieces, i1 > n_seqs ? l.pay_pieces : l.state_pieces);
+    const unsigned gx = (unsigned)std::min<long>((pieces + 1023) / 1024, 2048);
+    const unsigned gy = (unsigned)std::min<long>(i1 - i0, std::max<long>(1, 2048 / gx));
+    const hipStream_t st = (hipStream_t)stream;
+    if (mult) return launch(k_cs_swap<OUT, PF_H16>, dim3(gx, gy), dim3(256), 0, st, OUT ? "k_cs_swap<out,h16>" : "k_cs_swap<in,h16>", a);
+    return launch(k_cs_swap<OUT, PF_F32>, dim3(gx, gy), dim3(256), 0, st, OUT ? "k_cs_swap<out>" : "k_cs_swap<in>", a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -907,6 +941,28 @@ int mhla_causal_varlen_state_init_paged_h16(mhla_view k, mhla_view v, const floa
     RC(cst_check_slots(slot_dev, n_slots));
     return cs_pack_chain(k, v, mix, ldmix, (float*)pages_h16, cap_chunks, P, Cur, n_seqs, seq_len_dev, Slots{slot_dev, n_slots, table_dev, n_pages, page_mult},
                          max_len, T, H, K, V, chunk, n_chunks, chunk_tab_dev, chunk_dst_dev, ws, ws_bytes, dtype, stream);
+}
+
+// ---- swap: the state of chosen slots of a paged pool out into one contiguous blob and back in (mhla_hip.h; kernels: causal_swap.hpp)
+size_t mhla_causal_swap_ws_bytes(int n_seqs, int n_pages, int Hkv, int K, int V, int page_format) {
+    if (n_seqs < 0 || n_pages < 0 || Hkv <= 0 || K <= 0 || V <= 0 || ((long)K * V) % 4) return 0;
+    if (page_format != PF_F32 && (page_format != PF_H16 || ((long)K * V) % CSH_GROUP)) return 0;
+    const CsSwapLayout l = cs_swap_layout(Hkv, K, V, page_format);
+    return (size_t)n_seqs * l.seq_bytes + (size_t)n_pages * l.page_bytes;
+}
+
+int mhla_causal_swap_out_paged(const void* pages, const float* page_mult, int n_pages, const float* P, const float* Cur, const int32_t* pos_dev,
+                               const int32_t* full_dev, int n_slots, const int32_t* items_dev, int n_seqs, int n_pages_moved, int i0, int i1,
+                               void* blob_at, int Hkv, int K, int V, void* stream) {
+    return cs_swap<true>((void*)pages, (float*)page_mult, n_pages, (float*)P, (float*)Cur, (int32_t*)pos_dev, (int32_t*)full_dev, n_slots, items_dev, n_seqs,
+                         n_pages_moved, i0, i1, blob_at, Hkv, K, V, stream);
+}
+
+int mhla_causal_swap_in_paged(void* pages, float* page_mult, int n_pages, float* P, float* Cur, int32_t* pos_dev, int32_t* full_dev, int n_slots,
+                              const int32_t* items_dev, int n_seqs, int n_pages_moved, int i0, int i1, const void* blob_at, int Hkv, int K, int V,
+                              void* stream) {
+    return cs_swap<false>(pages, page_mult, n_pages, P, Cur, pos_dev, full_dev, n_slots, items_dev, n_seqs, n_pages_moved, i0, i1, (void*)blob_at, Hkv, K,
+                          V, stream);
 }
 
 }  // extern "C"

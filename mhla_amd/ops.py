@@ -1727,6 +1727,45 @@ def _page_table(fn, table, n_slots, n_pages):
     return rows
 
 
+class SwappedSlots:
+    """What `PagedCausalState.swap_out` returns and `swap_in` takes: the state of `n_seqs` sequences lifted out of a paged pool, in one
+    contiguous byte buffer (`buffer`, uint8, which it owns; the layout is the library's: mhla_hip.h, `mhla_causal_swap_ws_bytes`) --
+    per sequence P, Cur, pos and full, then every finished page once (an h16 page as payload and multipliers, never decoded).
+    `lengths`: tokens of every sequence; `page_format` and `dims` = (Hkv, K, V): what a pool must share to take it; `seq_pages`: per
+    sequence, the blob pages of its finished chunks 0, 1, ... -- sequences that shared a page in the pool name the same blob page;
+    `n_pages`, `nbytes`.  `host`: the buffer is host memory (pinned where a GPU is present), which a swap stages through the
+    device; otherwise it lives on the pool's device.  The kernels that fill a blob are stream-ordered and nothing synchronises: whoever
+    reads the bytes of a host blob (`buffer`, `to`) on another stream or from the host synchronises first."""
+
+    __slots__ = ("buffer", "lengths", "page_format", "dims", "seq_pages", "n_pages", "host")
+
+    def __init__(self, buffer, lengths, page_format, dims, seq_pages, n_pages, host):
+        self.buffer, self.lengths, self.page_format, self.dims = buffer, tuple(lengths), page_format, tuple(dims)
+        self.seq_pages, self.n_pages, self.host = tuple(tuple(r) for r in seq_pages), int(n_pages), bool(host)
+
+    n_seqs = property(lambda self: len(self.lengths))
+    nbytes = property(lambda self: self.buffer.numel())
+    device = property(lambda self: self.buffer.device)
+
+    @staticmethod
+    def _buffer(nbytes: int, device, host: bool) -> torch.Tensor:
+        if host:   # (pinned, so that the copies of a swap are asynchronous; a machine without a GPU -- a recorded session -- has nothing to pin for)
+            return torch.empty(nbytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+    def to(self, device) -> "SwappedSlots":
+        """A copy of the blob on `device` ("cpu": pinned host memory), stream-ordered on the current stream."""
+        device = torch.device(device)
+        buf = self._buffer(self.nbytes, device, device.type == "cpu")
+        buf.copy_(self.buffer, non_blocking=True)
+        return SwappedSlots(buf, self.lengths, self.page_format, self.dims, self.seq_pages, self.n_pages, device.type == "cpu")
+
+    def __repr__(self):
+        Hkv, K, V = self.dims
+        return (f"SwappedSlots(lengths={self.lengths}, n_pages={self.n_pages}, page_format={self.page_format}, Hkv={Hkv}, K={K}, V={V}, "
+                f"nbytes={self.nbytes}, {'host' if self.host else self.buffer.device})")
+
+
 class PagedCausalState(CausalState):
     """A pool of decode slots whose FINISHED CHUNKS ARE PAGES: `pages [n_pages, Hkv, K, V]` (fp32; one page holds K_j^T V_j of one chunk
     of one sequence, all k/v heads) and, per slot, a page table of `capacity_chunks` entries -- `table` on the host (lists of ints, -1:
@@ -1742,7 +1781,11 @@ class PagedCausalState(CausalState):
     `PoolExhausted` before anything changes when the free list is too short.  Changed rows of the table go to `table_dev` with a
     stream-ordered copy (no synchronisation).  `mhla_causal_step_dev` never assigns: `reserve(slots, tokens)` applies the rule ahead
     of it, and a sequence that reaches a chunk without a page is frozen like one at the capacity (`full`, `sync()`).
-    Not covered: `DecodeCache`, the fla layer and `hosts/gpt.py` keep states of their own; pages are never evicted or swapped.
+    Swapping: `swap_out(slots, device)` lifts the state of slots -- finished pages (a shared one once), P, Cur, pos, full -- into one
+    contiguous `SwappedSlots` blob, in pinned host memory (preemption) or on the device, and `swap_in(blob, slots)` puts it back bit
+    for bit into empty slots of this or another pool of the same Hkv, K, V and page format, by the page rule.  The pool never evicts on
+    its own: swapping is the caller's decision, and `PoolExhausted` is still raised before anything changes.
+    Not covered: `DecodeCache`, the fla layer and `hosts/gpt.py` keep states of their own; dense pools have no swap.
     Page format `"h16"` (`empty(..., page_format="h16")`, or a float16 `pages` together with `page_mult [n_pages, Hkv, K V / 64]`,
     float32): a page takes 2 bytes an element -- an fp16 payload times one power-of-two multiplier per 64 adjacent elements of a
     head's flattened `[K, V]` chunk (K V % 64 == 0), 11 significand bits relative to the group's largest element: the precision of
@@ -1966,6 +2009,85 @@ class PagedCausalState(CausalState):
         self._set_lengths((dst,), (n,))
         return self
 
+    # ---- swapping: the caller's decision, never the pool's
+    def swap_out(self, slots, device="cpu", release: bool = True) -> "SwappedSlots":
+        """Lift the state of the slots `slots` out of the pool into a `SwappedSlots` blob on `device`: "cpu" (pinned host memory:
+        preemption; staged through a device buffer of at most `SWAP_STAGE_CAP_BYTES` in slices of whole items) or the pool's own
+        device (also: None), for a migration into another pool or a compaction.  Per slot, in call order: its `length // 64` finished
+        pages -- a page that several of the slots share after a `fork` once --, P, Cur, pos and full.  Pages beyond the finished chunks
+        (the open chunk's, pages from `reserve`, a verify's scratch) are not saved: their content is outside the state's contract.
+        release=True: the slots are then emptied exactly as `reset` empties them (a page shared with a slot that stays loses one
+        reference); release=False: the pool keeps every bit -- a snapshot.  Everything is enqueued on the current stream and nothing
+        synchronises: synchronise before the host reads the bytes of a host blob.  The pool must be host-positioned and not stale."""
+        fn = "PagedCausalState.swap_out"
+        slots = self._pool_slots(fn, slots)
+        host = device is not None and torch.device(device).type == "cpu"
+        device = self.device if device is None else torch.device(device)
+        if not host and device != self.device and (device.index is not None or device.type != self.device.type):
+            raise ValueError(f"{fn}: device {device}: 'cpu' or the pool's device {self.device} (SwappedSlots.to(device) copies a blob anywhere)")
+        seq_pages, blob_page = [], {}   # (pool page -> blob page, in order of first use)
+        for s in slots:
+            seq_pages.append([blob_page.setdefault(self.table[s][j], len(blob_page)) for j in range(self.lengths[s] // 64)])
+        Hkv, K, V = self.dims[1], self.dims[3], self.dims[4]
+        nbytes = _swap_bytes(len(slots), len(blob_page), Hkv, K, V, self.page_format)
+        blob = SwappedSlots(SwappedSlots._buffer(nbytes, self.device, host), [self.lengths[s] for s in slots], self.page_format, (Hkv, K, V),
+                            seq_pages, len(blob_page), host)
+        _swap_launch("out", self, blob, list(slots) + list(blob_page))
+        if release:
+            self.reset(slots)
+        return blob
+
+    def swap_in(self, blob: "SwappedSlots", slots) -> "PagedCausalState":
+        """Put the sequences of `blob` into the EMPTY slots `slots` (as many as it has sequences; length 0 and no page in the table
+        row, ValueError naming the others) of this pool -- any pool with the blob's Hkv, K, V and page format (ValueError), whatever its
+        n_slots, n_pages and capacity (IndexError for a sequence beyond 64 capacity_chunks).  Page rule: every sequence gets
+        ceil(length / 64) pages, lowest free page first; a blob page that several sequences hold gets ONE pool page, its reference
+        count their number.  All or nothing: `PoolExhausted` before anything changes.  Then the changed table rows go to `table_dev`,
+        the scatter writes the finished pages, P, Cur, pos and full -- bit for bit what `swap_out` read -- and the host mirror follows.
+        A host blob is staged through the device in slices; a blob may be swapped in more than once (a `fork` across pools).  Stream-
+        ordered, no synchronisation."""
+        fn = "PagedCausalState.swap_in"
+        if not isinstance(blob, SwappedSlots):
+            raise TypeError(f"{fn}: blob must be the SwappedSlots of a swap_out, got {type(blob).__name__}")
+        slots = self._pool_slots(fn, slots)
+        if len(slots) != blob.n_seqs:
+            raise ValueError(f"{fn}: {len(slots)} slots for the {blob.n_seqs} sequences of the blob")
+        mine = (self.dims[1], self.dims[3], self.dims[4])
+        if blob.dims != mine or blob.page_format != self.page_format:
+            raise ValueError(f"{fn}: the blob holds (Hkv, K, V) = {blob.dims}, page_format={blob.page_format!r}; the pool "
+                             f"{mine}, page_format={self.page_format!r} (nothing is converted on the way)")
+        if not blob.host and blob.buffer.device != self.device:
+            raise ValueError(f"{fn}: the blob lives on {blob.buffer.device}, the pool on {self.device}: blob.to(device) copies it")
+        busy = [s for s in slots if self.lengths[s] or any(p >= 0 for p in self.table[s])]
+        if busy:
+            raise ValueError(f"{fn}: slots {busy} are not empty (length 0 and no page: pool.reset(slots) empties them)")
+        cap = self.capacity_chunks
+        over = [s for s, n in zip(slots, blob.lengths) if n > 64 * cap]
+        if over:
+            raise IndexError(f"{fn}: slots {over} would hold more than the capacity of {cap} chunks ({64 * cap} tokens; lengths {blob.lengths})")
+        need = blob.n_pages + sum(-(-n // 64) - n // 64 for n in blob.lengths)   # (shared pages once, and a page for every open chunk)
+        if need > len(self.free):
+            raise PoolExhausted(f"{fn}: slots {sorted(slots)} need {need} pages, the pool has {len(self.free)} free (of {len(self.refs)}; "
+                                "pool.trim / pool.reset release pages)")
+        placed = {}   # blob page -> pool page
+        for s, n, row in zip(slots, blob.lengths, blob.seq_pages):
+            for j in range(-(-n // 64)):
+                b = row[j] if j < len(row) else None   # (None: the open chunk's page, which holds nothing yet)
+                if b in placed:
+                    p = placed[b]
+                    self.refs[p] += 1
+                else:
+                    p = heapq.heappop(self.free)
+                    self.refs[p] = 1
+                    if b is not None:
+                        placed[b] = p
+                self.table[s][j] = p
+        self._push([s for s, n in zip(slots, blob.lengths) if n])
+        self.full   # (the scatter restores the flags)
+        _swap_launch("in", self, blob, list(slots) + [placed[b] for b in range(blob.n_pages)])
+        self._set_lengths(slots, blob.lengths)
+        return self
+
     def __repr__(self):
         n_slots, H, cap, K, V = self.dims
         return (f"PagedCausalState(n_slots={n_slots}, H={H}, K={K}, V={V}, capacity_chunks={cap}, pages={self.pages_used}/{len(self.refs)} used, "
@@ -2150,6 +2272,46 @@ def _state_args(call, mixf, state, pos=(), packed=False):
 @functools.lru_cache(maxsize=64)
 def _step_ws_bytes(B, H, K, V, dt):
     return _lib.load().mhla_causal_step_ws_bytes(B, H, K, V, dt)
+
+
+@functools.lru_cache(maxsize=64)
+def _swap_bytes(n_seqs, n_pages, Hkv, K, V, page_format):
+    """Bytes of a blob of `n_seqs` sequence items and `n_pages` page items: the library's layout (pure host arithmetic)."""
+    return _lib.load().mhla_causal_swap_ws_bytes(n_seqs, n_pages, Hkv, K, V, 1 if page_format == "h16" else 0)
+
+
+def _swap_launch(direction, pool, blob, items):
+    """Both directions of a swap ("out": pool -> blob, "in": blob -> pool): the one place that marshals a paged pool and an item list
+    (`items`: the pool slot of every sequence of the blob, then the pool page of every blob page) for mhla_causal_swap_{out,in}_paged.
+    The list goes to the device in one small copy.  A blob on the pool's device: one call on the whole list, on the blob itself.  A
+    host blob: the list is cut into slices of whole items whose bytes fit a device staging buffer of at most `SWAP_STAGE_CAP_BYTES`
+    (one item, where a single item is larger), reused across the slices -- stream order makes that safe --, each slice gathered into
+    the stage and copied to the blob, or copied to the stage and scattered; nothing synchronises."""
+    fn = getattr(_lib.load(), f"mhla_causal_swap_{direction}_paged")
+    Hkv, K, V = blob.dims
+    n_seqs, n_moved = blob.n_seqs, blob.n_pages
+    seq_b, page_b = (_swap_bytes(*n, Hkv, K, V, blob.page_format) for n in ((1, 0), (0, 1)))
+    at = lambda i: i * seq_b if i < n_seqs else n_seqs * seq_b + (i - n_seqs) * page_b   # where item i begins
+    items_dev = torch.tensor(items, dtype=torch.int32).to(pool.device)
+    head = (pool.pages.data_ptr(), _ptr(pool.page_mult), pool.pages.shape[0], pool.P.data_ptr(), pool.Cur.data_ptr(), pool.pos.data_ptr(),
+            _ptr(pool._full), pool.dims[0], items_dev.data_ptr(), n_seqs, n_moved)
+    what = f"mhla_causal_swap_{direction}_paged"
+    if not blob.host:
+        _lib.check(fn(*head, 0, len(items), blob.buffer.data_ptr(), Hkv, K, V, _stream()), what)
+        return
+    cuts = [0]
+    for i in range(1, len(items) + 1):   # (greedy: a slice grows while its bytes fit the cap, and holds at least one item)
+        if at(i) - at(cuts[-1]) > SWAP_STAGE_CAP_BYTES and i - 1 > cuts[-1]:
+            cuts.append(i - 1)
+    cuts.append(len(items))
+    stage = torch.empty(max(at(j) - at(i) for i, j in zip(cuts, cuts[1:])), dtype=torch.uint8, device=pool.device)
+    for i, j in zip(cuts, cuts[1:]):
+        piece, staged = blob.buffer[at(i):at(j)], stage[:at(j) - at(i)]
+        if direction == "in":
+            staged.copy_(piece, non_blocking=True)
+        _lib.check(fn(*head, i, j, stage.data_ptr(), Hkv, K, V, _stream()), what)
+        if direction == "out":
+            piece.copy_(staged, non_blocking=True)
 
 
 def _gqa_call(lib, name, H, Hkv):
@@ -2646,6 +2808,7 @@ def mhla_causal_step_dev(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mixi
 # Largest workspace one launch chain of `mhla_causal_extend` takes: a longer extension is cut into consecutive calls.  Per (b, h)
 # the chain needs 4 K V bytes per chunk touched after the first and 4 V bytes per token (mhla_hip.h).
 EXTEND_WS_CAP_BYTES = 256 << 20
+SWAP_STAGE_CAP_BYTES = EXTEND_WS_CAP_BYTES   # the device staging buffer of a swap to or from a host blob (`_swap_launch`)
 
 
 def _counts_prepare(fn, q, k, v, mixing_matrix, state, counts, left_padded, cu_seqlens, scale, gate, norm_weight, epilogue):

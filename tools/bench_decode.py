@@ -116,6 +116,16 @@ layouts.  Positions and host mirror are put back before every call, for every va
 paths alone on a tree that has `cu_seqlens` as well: the process then does exactly the work of the older tree's, which is what a
 comparison of the two builds needs (a process that also runs the packed variants differs in more than its library).
 
+`--swap`: `PagedCausalState.swap_out` / `swap_in` on the pools of `--paged` / `--paged-h16` (H = 4, K = 128, V = 256, 2 B slots, 19 pages a
+slot, a random table), the B sequences at the "off" lengths (about 1000 tokens, 13 .. 17 finished pages each), B = 4 and 32, fp32 and
+h16 pages.  Device blob: wall time per call (events around `--steps` calls, at most 100) and the device time of the swap kernel (the
+per-launch event hook), beside the torch expressions that move the same bytes -- `pages[idx]`, `P[idx]`, `Cur[idx]` (what `compact()`
+does) and the indexed assignments back -- and a plain device `copy_` of the blob's byte count: the session's copy rate.  Host blob:
+wall time of a swap out and of a swap in (after a `reset` of the target slots) with a synchronise, beside a pinned `copy_` of the
+same byte count in each direction, the link's ceiling.  GB/s counts the blob's bytes once.  Last, for context: the device time of
+the state half of a re-prefill of the same sequences (`mhla_causal_state(..., cu_seqlens=plan, into=view)`), a lower bound on what
+losing the state costs, since a real re-prefill runs the whole model.
+
 `--workload`: no timing, just a prefill and 192 real steps (three boundaries) at B = 1, H = 4, K = 128, V = 256 -- the program to put
 after `rocprofv3 --kernel-trace --stats -d <dir> --` for a trace of its own."""
 import argparse
@@ -614,6 +624,113 @@ def paged_config(B, H, K, V, steps, reps, h16=False):
     return rec
 
 
+def swap_config(B, H, K, V, steps, reps):
+    import time
+    g = torch.Generator().manual_seed(1)
+    mix = causal_mixing_init(L).reshape(L, L).to(DEV)
+    i0 = 15
+    chunks = [i0 + (-2, -1, 1, 2)[b % 4] for b in range(B)]
+    lens = tuple(c * 64 + (7 * b) % 63 for b, c in enumerate(chunks))   # the "off" lengths of --paged: about 1000 tokens each
+    n_slots, held = 2 * B, i0 + 4
+    slots = torch.randperm(n_slots, generator=g)[:B].tolist()
+    n_pages = n_slots * held
+    perm = torch.randperm(n_pages, generator=g).tolist()
+    table = [perm[s_ * held:(s_ + 1) * held] + [-1] * (L - held) for s_ in range(n_slots)]
+    lengths = [0] * n_slots
+    for s_, n in zip(slots, lens):
+        lengths[s_] = n
+    z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=DEV)
+
+    def make(fmt, filled=True):
+        tab, lng = (table, lengths) if filled else ([[-1] * L for _ in range(n_slots)], None)
+        if fmt == "h16":
+            pool = mhla_amd.PagedCausalState((z(n_pages, H, K, V).normal_(0, 0.1) * 2.0 ** 17).half(), z(n_slots, H, K, V).normal_(0, 0.1), z(n_slots, H, K, V), tab,
+                                             lengths=lng, page_mult=torch.full((n_pages, H, K * V // 64), 2.0 ** -17, dtype=torch.float32, device=DEV))
+        else:
+            pool = mhla_amd.PagedCausalState(z(n_pages, H, K, V).normal_(0, 0.1), z(n_slots, H, K, V).normal_(0, 0.1), z(n_slots, H, K, V), tab, lengths=lng)
+        pool.full
+        return pool
+
+    def wall_sync_us(fn, iters=5):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            fn()
+            torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / iters * 1e6
+
+    idx = torch.tensor(slots, dtype=torch.int64, device=DEV)
+    out = {}
+    for fmt in ("fp32", "h16"):
+        src, dst = make(fmt), make(fmt, filled=False)
+        blob = src.swap_out(slots, device=DEV, release=False)
+        pidx = torch.tensor([p for s_ in slots for p in src.table[s_][:src.lengths[s_] // 64]], dtype=torch.int64, device=DEV)
+        nbytes = blob.nbytes
+        flat = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+        pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        host_blob = src.swap_out(slots, release=False)
+        targets = list(range(B))
+
+        def torch_gather():   # the expressions of compact(): the same bytes into fresh tensors
+            got = [src.pages[pidx], src.P[idx], src.Cur[idx]]
+            if src.page_mult is not None:
+                got.append(src.page_mult[pidx])
+            return got
+
+        parts = torch_gather()
+        didx = torch.arange(len(pidx), device=DEV)
+
+        def torch_scatter():
+            dst.pages[didx] = parts[0]
+            dst.P[idx] = parts[1]
+            dst.Cur[idx] = parts[2]
+            if src.page_mult is not None:
+                dst.page_mult[didx] = parts[3]
+
+        def swap_in(b):
+            dst.reset(targets)
+            dst.swap_in(b, targets)
+
+        dev_fns = {"swap_out": lambda: src.swap_out(slots, device=DEV, release=False), "swap_in": lambda: swap_in(blob), "torch_gather": torch_gather,
+                   "torch_scatter": torch_scatter, "device_copy": lambda: flat.copy_(blob.buffer)}
+        host_fns = {"swap_out_host": lambda: src.swap_out(slots, release=False), "swap_in_host": lambda: swap_in(host_blob),
+                    "pinned_copy_d2h": lambda: pinned.copy_(flat, non_blocking=True), "pinned_copy_h2d": lambda: flat.copy_(pinned, non_blocking=True)}
+        wall, devt, host = {n: [] for n in dev_fns}, {"swap_out": [], "swap_in": []}, {n: [] for n in host_fns}
+        with torch.no_grad():
+            for _ in range(reps):
+                for n, fn in dev_fns.items():
+                    wall[n].append(batch_us(fn, steps))
+                for n in devt:
+                    devt[n].append(sum(kernel_times(dev_fns[n], iters=20).values()))
+                for n, fn in host_fns.items():
+                    host[n].append(wall_sync_us(fn))
+        gbs = lambda us: round(nbytes / statistics.median(us) / 1e3, 1)
+        out[fmt] = {"blob_MB": round(nbytes / 2 ** 20, 2), "pages_moved": blob.n_pages, "wall_us": {n: spread(x) for n, x in wall.items()},
+                    "device_us": {n: spread(x) for n, x in devt.items()}, "host_wall_us": {n: spread(x) for n, x in host.items()},
+                    "GBps": {**{f"{n}_device": gbs(x) for n, x in devt.items()}, **{f"{n}_wall": gbs(x) for n, x in wall.items()},
+                             **{n: gbs(x) for n, x in host.items()}}}
+    # what the alternative costs at the least: the state half of a re-prefill of the same sequences (a real one runs the whole model)
+    cu = [0]
+    for n in lens:
+        cu.append(cu[-1] + n)
+    plan = mhla_amd.causal_varlen_plan(cu, DEV)
+    kc = torch.randn(1, cu[-1], H, K, generator=g).to(torch.bfloat16).to(DEV)
+    vc = torch.randn(1, cu[-1], H, V, generator=g).to(torch.bfloat16).to(DEV)
+    pre = {}
+    with torch.no_grad():
+        for fmt in ("fp32", "h16"):
+            pool = make(fmt, filled=False)
+            view = pool.at(slots)
+            fill = lambda: mhla_amd.mhla_causal_state(kc, vc, mix, cu_seqlens=plan, into=view)
+            fill()
+            pre[fmt] = spread([sum(kernel_times(fill, iters=5).values()) for _ in range(reps)])
+    rec = {"swap": {"B": B, "H": H, "K": K, "V": V, "n_slots": n_slots, "tokens": cu[-1]}, "steps_per_batch": steps, "reps": reps, **out,
+           "reprefill_state_device_us": pre}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def launch_counts(fn):
     """{kernel: launches} of one call of `fn` (the library's per-launch hook)."""
     import ctypes
@@ -1077,8 +1194,12 @@ if __name__ == "__main__":
     ap.add_argument("--paged-h16", action="store_true")
     ap.add_argument("--packed", action="store_true")
     ap.add_argument("--existing-only", action="store_true")
+    ap.add_argument("--swap", action="store_true")
     a = ap.parse_args()
-    if a.packed:
+    if a.swap:
+        for B in (4, 32):
+            swap_config(B, 4, 128, 256, min(100, a.steps), a.reps)
+    elif a.packed:
         for B in (8, 32):
             packed_config(B, 4, 128, 256, max(100, a.steps), a.reps, existing_only=a.existing_only)
     elif a.paged_h16:
