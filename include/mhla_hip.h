@@ -839,6 +839,35 @@ int mhla_featmap_rotary(mhla_view x, mhla_view x_saved, const void* cos, const v
                         int64_t t_offset, mhla_mview y, int B, int T, int H, int K,
                         int feature_map, int backward, int dtype, void* stream);
 
+/*
+ * The same prologue for the NEW tokens of a decode call, q and k in ONE launch, at positions read from the decode state (added
+ * without a change of any existing signature or behaviour: MHLA_ABI_VERSION stays 9).  No host value depends on a position, so a
+ * captured graph can replay the call; `pos_dev` is read and never written -- enqueue the call ahead of the chain that advances it.
+ * Token layouts, as in the extend chain:
+ *   padded (off_dev NULL): q, yq [B][T][H][K], k, yk [B][T][Hkv][K] views.  Sequence b takes w = ntok_dev[b] rows (ntok_dev NULL: all
+ *     T), the window [0, w), or [T - w, T) with left_padded.
+ *   packed (off_dev: device int32 [B + 1]; ntok_dev NULL, left_padded 0): the tokens are one run of T rows, the views' batch stride is
+ *     unused, and row n belongs to the last b with off[b] <= n < off[b + 1]; empty sequences are skipped.
+ * Position: a row with index r inside its sequence's window sits at p = pos_dev[sb] + r, sb = b, or slot_dev[b] with a slot map
+ * (device int32 [B] of rows of a pool of n_slots; pos_dev is then the pool's [n_slots]; an entry outside 0 .. n_slots - 1 is an
+ * INACTIVE row, as in the slotted decode calls).
+ * Result: a row inside a window with 0 <= p < tab_rows holds the feature map followed by the rotary at table row p -- the fp32
+ * arithmetic of mhla_featmap_rotary, rounded where that call rounds: bit for bit its output on table rows gathered at the same
+ * positions.  Every other row -- outside every window, of an inactive slot entry, of a sequence whose offsets decrease or leave
+ * [0, T) (or whose count leaves 0 .. T), or with p outside the tables -- is written as zeros in both yq and yk.  Nothing read from the
+ * device arrays forms an address outside q, k, the tables or the outputs.
+ * yq may be q and yk may be k (in place); strided views work, q and k as slices of one fused projection included.  cos, sin:
+ * [tab_rows][K/2] in the tensor dtype, row stride ld_tab.  16-bit tensors move 16-byte pieces where every row of the views and the
+ * tables starts on 16 bytes and K % 16 == 0, 8-byte pieces otherwise: the same bits.
+ * MHLA_EINVAL before the launch: a non-positive size, K % 8 != 0, H % Hkv != 0, T outside 1 .. 65535, feature_map or dtype out of
+ * range, an invalid view, tables null or misaligned, ld_tab < K / 2 or not a multiple of 4, tab_rows <= 0, pos_dev null, any device
+ * array not 4-byte aligned, n_slots <= 0 with a slot map, off_dev together with ntok_dev or left_padded.
+ */
+int mhla_featmap_rotary_decode(mhla_view q, mhla_view k, const void* cos, const void* sin, int64_t ld_tab, int64_t tab_rows,
+                               const int32_t* pos_dev, const int32_t* slot_dev, int n_slots,
+                               const int32_t* ntok_dev, const int32_t* off_dev, int T, int left_padded,
+                               mhla_mview yq, mhla_mview yk, int B, int H, int Hkv, int K, int feature_map, int dtype, void* stream);
+
 /* ---- LePE: depthwise K x K convolution over V on the token layout --------- */
 
 /*

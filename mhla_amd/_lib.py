@@ -155,6 +155,9 @@ SIGNATURES = {
                                                     c_int, c_uint, c_void_p]),
     "mhla_featmap_rotary": (c_int, [View,View, c_void_p, c_void_p, c_int64, c_int64, View, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_void_p]),
+    # q, k, cos, sin, ld_tab, tab_rows, pos_dev, slot_dev, n_slots, ntok_dev, off_dev, T, left_padded, yq, yk, B, H, Hkv, K, feature_map, dtype, stream
+    "mhla_featmap_rotary_decode": (c_int, [View, View, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_int, c_int, View, View, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mhla_lepe2d": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                             c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mhla_lepe2d_wgrad_ws_bytes": (c_size_t, [c_int, c_int]),

@@ -1,5 +1,6 @@
 // C ABI, the operator's neighbours: per-head RMSNorm x gate, LePE depthwise convolutions, q/k prologues, feature map + rotary.
 #include "capi_common.hpp"
+#include "decode_prologue.hpp"
 #include "epilogue.hpp"
 #include "lepe.hpp"
 
@@ -253,6 +254,52 @@ int mhla_featmap_rotary(mhla_view x, mhla_view x_saved, const void* cos, const v
         if (backward) RC(launch(k_fmap_rotary<ET, true>, grid, dim3(256), 0, st, "k_fmap_rotary<bwd>", a));
         else          RC(launch(k_fmap_rotary<ET, false>, grid, dim3(256), 0, st, "k_fmap_rotary", a));
     });
+    return MHLA_OK;
+}
+
+int mhla_featmap_rotary_decode(mhla_view q, mhla_view k, const void* cos, const void* sin, int64_t ld_tab, int64_t tab_rows,
+                               const int32_t* pos_dev, const int32_t* slot_dev, int n_slots, const int32_t* ntok_dev,
+                               const int32_t* off_dev, int T, int left_padded, mhla_mview yq, mhla_mview yk, int B, int H, int Hkv,
+                               int K, int feature_map, int dtype, void* stream) {
+    if (B <= 0 || H <= 0 || Hkv <= 0 || K <= 0 || (K & 7)) return fail(MHLA_EINVAL, "B=%d H=%d Hkv=%d K=%d: need positive sizes and K %% 8 == 0", B, H, Hkv, K);
+    if (H % Hkv) return fail(MHLA_EINVAL, "H=%d is not a multiple of Hkv=%d", H, Hkv);
+    if (T < 1 || T > 65535) return fail(MHLA_EINVAL, "T=%d: 1 .. 65535 token rows", T);
+    if (feature_map < 0 || feature_map > 2) return fail(MHLA_EINVAL, "feature_map %d: 0 identity, 1 relu, 2 elu+1", feature_map);
+    if (dtype < 0 || dtype > 2) return fail(MHLA_EINVAL, "unknown dtype %d", dtype);
+    CHECK_VIEW(q); CHECK_VIEW(k); CHECK_VIEW(yq); CHECK_VIEW(yk);
+    const int esz = dtype == MHLA_F32 ? 4 : 2;
+    if (!cos || !sin || ld_tab < K / 2 || (ld_tab & 3) || (((uintptr_t)cos | (uintptr_t)sin) % (4 * esz)))
+        return fail(MHLA_EINVAL, "cos/sin tables: null, not %d-byte aligned, or ld_tab=%lld < K/2 = %d or not a multiple of 4", 4 * esz, (long long)ld_tab, K / 2);
+    if (tab_rows <= 0) return fail(MHLA_EINVAL, "tab_rows=%lld: the tables need a row", (long long)tab_rows);
+    if (!pos_dev || ((uintptr_t)pos_dev & 3)) return fail(MHLA_EINVAL, "pos_dev: null or not 4-byte aligned");
+    if (((uintptr_t)slot_dev | (uintptr_t)ntok_dev | (uintptr_t)off_dev) & 3) return fail(MHLA_EINVAL, "slot_dev / ntok_dev / off_dev: not 4-byte aligned");
+    if (slot_dev && n_slots <= 0) return fail(MHLA_EINVAL, "n_slots=%d with a slot map: the pool needs a slot", n_slots);
+    if (off_dev && (ntok_dev || left_padded)) return fail(MHLA_EINVAL, "off_dev (packed tokens) excludes ntok_dev and left_padded=%d, which place windows in padded tensors", left_padded);
+    const long rows = off_dev ? (long)T : (long)B * T;
+    if (rows > 0x7fffffffL) return fail(MHLA_ENOTSUP, "B T = %ld token rows exceed the grid limit", rows);
+    FrDecArgs a{cv(q), cv(k), cmv(yq), cmv(yk), cos, sin, (long)ld_tab, (long)tab_rows, pos_dev, slot_dev, n_slots, ntok_dev, off_dev,
+                T, left_padded ? 1 : 0, B, H, Hkv, K, feature_map};
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)rows);
+    // 16-bit tensors: 16-byte pieces (8 + 8 elements a thread) where every row of the views and the tables starts on 16 bytes and the
+    // half row is whole pieces; the bits do not depend on it (decode_prologue.hpp)
+    const bool wide = dtype != MHLA_F32 && K % 16 == 0 && !(ld_tab & 7) &&
+                      !((q.sb | q.sn | q.sh | k.sb | k.sn | k.sh | yq.sb | yq.sn | yq.sh | yk.sb | yk.sn | yk.sh) & 7) &&
+                      !(((uintptr_t)q.ptr | (uintptr_t)k.ptr | (uintptr_t)yq.ptr | (uintptr_t)yk.ptr | (uintptr_t)cos | (uintptr_t)sin) & 15);
+    if (dtype == MHLA_F32) {
+        if (off_dev) RC(launch(k_fr_decode<float, 4, true>, grid, dim3(256), 0, st, "k_fr_decode", a));
+        else         RC(launch(k_fr_decode<float, 4, false>, grid, dim3(256), 0, st, "k_fr_decode", a));
+    } else if (dtype == MHLA_BF16) {
+        if (wide) { if (off_dev) RC(launch(k_fr_decode<bf16_t, 8, true>, grid, dim3(256), 0, st, "k_fr_decode", a));
+                    else         RC(launch(k_fr_decode<bf16_t, 8, false>, grid, dim3(256), 0, st, "k_fr_decode", a)); }
+        else      { if (off_dev) RC(launch(k_fr_decode<bf16_t, 4, true>, grid, dim3(256), 0, st, "k_fr_decode", a));
+                    else         RC(launch(k_fr_decode<bf16_t, 4, false>, grid, dim3(256), 0, st, "k_fr_decode", a)); }
+    } else {
+        if (wide) { if (off_dev) RC(launch(k_fr_decode<f16_t, 8, true>, grid, dim3(256), 0, st, "k_fr_decode", a));
+                    else         RC(launch(k_fr_decode<f16_t, 8, false>, grid, dim3(256), 0, st, "k_fr_decode", a)); }
+        else      { if (off_dev) RC(launch(k_fr_decode<f16_t, 4, true>, grid, dim3(256), 0, st, "k_fr_decode", a));
+                    else         RC(launch(k_fr_decode<f16_t, 4, false>, grid, dim3(256), 0, st, "k_fr_decode", a)); }
+    }
     return MHLA_OK;
 }
 

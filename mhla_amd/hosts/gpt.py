@@ -6,12 +6,16 @@ Plumbing for step-level numbers; stock PyTorch besides the attention layer.  The
 BASELINE.json configs[4] sequence length, through the drop-in layer's `max_chunks`).  With `exact_decoding=True` the layers
 keep a decode state in a cache (`forward(..., cache=DecodeCache())`: prefill on the first call, one exact step per later
 token, one extension per later call of several tokens) and `generate` decodes greedily on top of it -- with `graph=True` by
-replaying one captured whole-model step per token (device-positioned steps: `DecodeCache(device_positions=True)`)."""
+replaying one captured whole-model step per token (device-positioned steps: `DecodeCache(device_positions=True)`).  With a
+`PagedDecodeCache` a forward is one scheduler step of continuous batching -- a pack of new tokens of the requests the cache's slots
+hold -- and `serve` runs requests to completion on top of it (`serve_schedule`: the policy, a pure function)."""
+import heapq
+
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..modules import MHLA, DecodeCache
+from ..modules import MHLA, DecodeCache, PagedDecodeCache
 from ..ops import causal_varlen_plan
 
 
@@ -101,7 +105,11 @@ class GPT_MHLA(nn.Module):
         state.  On a cache that holds a state it raises NotImplementedError.
         `speculative=True` (a cache that holds a state): `input_ids` are a draft to VERIFY -- the logits of the same call without
         the flag, but no layer's state and no token count moves; `cache.commit(accept)` then advances every layer by the first
-        `accept[b]` tokens of sequence b's window, `cache.discard()` by none.  Handed to every layer."""
+        `accept[b]` tokens of sequence b's window, `cache.discard()` by none.  Handed to every layer.
+        `cache` a `PagedDecodeCache`: one scheduler step of continuous batching.  `cache.schedule(slots, cu_seqlens)` declared which
+        request takes which rows of the pack, `input_ids` [1, N] is that pack, the logits are [1, N, vocab], and every layer has
+        advanced its pool's slots.  `cu_seqlens=` as an argument stays refused (the schedule carries it); `attention_mask`,
+        `token_counts` and `speculative` are refused by the layers."""
         if cache is not None and not self.exact_decoding:
             raise ValueError("GPT_MHLA.forward(cache=...) needs a model built with exact_decoding=True")
         # a model built with exact_decoding and isolate_sequences prefills a pack into an EMPTY DecodeCache(packed_prefill=True):
@@ -236,6 +244,105 @@ class GPT_MHLA(nn.Module):
             cache.commit(accept)
         ids = torch.tensor(out, dtype=torch.long, device=dev)
         return (ids, torch.stack([torch.stack(r) for r in kept])) if return_logits else ids
+
+
+    @torch.no_grad()
+    def serve(self, prompts, max_new_tokens, *, n_slots, n_pages, step_tokens=256, return_logits=False, cache=None):
+        """Greedy CONTINUOUS BATCHING of `prompts` (a list of 1-D id tensors or lists, any lengths) to `max_new_tokens` new ids each, no
+        EOS and no preemption, on a `PagedDecodeCache(n_slots, capacity of the mixing matrix, n_pages)`: every model call is one step
+        of `serve_schedule` (the policy; see there) -- the decoding requests' one token each beside slices of the prompts being
+        prefilled, packed, at most `step_tokens` tokens --, a finished request's slot is released at once and the next request
+        moves in.  The schedule depends on the lengths alone, so nothing is read back from the device between steps.  Returns the list
+        of every request's ids (1-D, `max_new_tokens` long); `return_logits=True`: `(ids, logits)`, per request the
+        `[max_new_tokens, vocab]` logits every id was picked from.  `cache`: an empty `PagedDecodeCache` of these sizes to run on (its
+        pools are reused; by default a new one is made); every slot is released again when `serve` returns."""
+        if not self.exact_decoding:
+            raise ValueError("GPT_MHLA.serve needs a model built with exact_decoding=True")
+        dev = self.embeddings.weight.device
+        prompts = [torch.as_tensor(p, dtype=torch.long).reshape(-1).to(dev) for p in prompts]
+        n = int(max_new_tokens)
+        cap = self.layers[0].attn.max_chunks
+        steps = serve_schedule([len(p) for p in prompts], n, n_slots, n_pages, cap, step_tokens)
+        if cache is None:
+            cache = PagedDecodeCache(n_slots, cap, n_pages, dev)
+        elif (cache.n_slots, cache.capacity_chunks, cache.n_pages) != (n_slots, cap, n_pages) or any(cache.lengths):
+            raise ValueError(f"GPT_MHLA.serve: cache is {cache!r}, expected an empty one of n_slots={n_slots}, capacity_chunks={cap}, n_pages={n_pages}")
+        fed = [0] * len(prompts)
+        ids, kept = [[] for _ in prompts], [[] for _ in prompts]
+        for slots, cu, kinds in steps:
+            pack = []
+            for (req, kind), a, b in zip(kinds, cu, cu[1:]):
+                pack.append(ids[req][-1] if kind == "decode" else prompts[req][fed[req]:fed[req] + b - a])
+                fed[req] += b - a
+            cache.schedule(slots, cu)
+            logits = self.forward(torch.cat(pack)[None], cache=cache)[0]
+            done = []
+            for (req, kind), slot, b in zip(kinds, slots, cu[1:]):
+                if kind != "prompt":   # (the request's last row of the step: its prompt ended here, or it decoded a token)
+                    ids[req].append(logits[b - 1].argmax(-1, keepdim=True))
+                    kept[req].append(logits[b - 1]) if return_logits else None
+                    if len(ids[req]) == n:
+                        done.append(slot)
+            if done:
+                cache.release(done)
+        empty = torch.zeros(0, dtype=torch.long, device=dev)
+        out = [torch.cat(r) if r else empty for r in ids]
+        return (out, [torch.stack(r) if r else None for r in kept]) if return_logits else out
+
+
+def serve_schedule(prompt_lens, max_new_tokens, n_slots, n_pages, capacity_chunks, step_tokens):
+    """The steps of `GPT_MHLA.serve`, a pure function of the lengths: a list of `(slots, cu, kinds)` -- what
+    `PagedDecodeCache.schedule(slots, cu)` takes, and per sequence of the pack `(request, kind)`, kind "prompt" (a slice of the prompt
+    that does not end it: no id), "first" (the slice that ends the prompt: the request's first id comes from its last row) or "decode"
+    (the id emitted last goes in, the next comes out).  A request is fed its prompt and its first `max_new_tokens - 1` ids.
+    Policy: admission is FIFO -- the oldest waiting request moves in when a slot is free and the pool can hold
+    ceil((prompt + max_new_tokens) / 64) pages for it beside those promised to the running requests, so no step can exhaust the
+    pool; no request overtakes it.  Within a step every decoding request takes its one token first, and what is left of
+    `step_tokens` goes to prompt slices in admission order (a request that gets none sits the step out).  A request that has its
+    `max_new_tokens` ids leaves after the step, and its slot and pages are free for the next step's admission.
+    ValueError: an empty prompt, a request beyond the capacity of 64 `capacity_chunks` tokens or beyond `n_pages` pages on its own,
+    `step_tokens < n_slots` (the decoding requests alone could exceed a step)."""
+    fn = "serve_schedule"
+    lens, n = [int(p) for p in prompt_lens], int(max_new_tokens)
+    if n < 1 or not lens:
+        return []
+    if min(int(n_slots), int(n_pages), int(capacity_chunks)) < 1 or step_tokens < n_slots:
+        raise ValueError(f"{fn}: n_slots={n_slots}, n_pages={n_pages}, capacity_chunks={capacity_chunks} must be positive and "
+                         f"step_tokens={step_tokens} at least n_slots (every decoding request takes a token of every step)")
+    need = [-(-(p + n) // 64) for p in lens]
+    bad = [r for r, p in enumerate(lens) if p < 1 or p + n - 1 > 64 * capacity_chunks or need[r] > n_pages]
+    if bad:
+        raise ValueError(f"{fn}: requests {bad} (prompts {[lens[r] for r in bad]} + {n} new tokens) are empty, exceed the capacity of "
+                         f"{64 * capacity_chunks} tokens or need more than the pool's {n_pages} pages")
+    waiting, free, pages = list(range(len(lens))), list(range(n_slots)), int(n_pages)
+    running, steps = [], []   # running: [request, slot, tokens fed, ids emitted] in admission order
+    while waiting or running:
+        while waiting and free and need[waiting[0]] <= pages:
+            r = waiting.pop(0)
+            pages -= need[r]
+            running.append([r, heapq.heappop(free), 0, 0])
+        budget = step_tokens - sum(1 for run in running if run[2] >= lens[run[0]])
+        slots, cu, kinds = [], [0], []
+        for decode in (True, False):
+            for run in running:
+                r, slot, fed, _ = run
+                if (fed >= lens[r]) != decode:
+                    continue
+                take = 1 if decode else min(budget, lens[r] - fed)
+                if not take:
+                    continue
+                budget -= 0 if decode else take
+                run[2] += take
+                run[3] += run[2] >= lens[r]
+                slots.append(slot)
+                cu.append(cu[-1] + take)
+                kinds.append((r, "decode" if decode else "first" if run[2] == lens[r] else "prompt"))
+        steps.append((tuple(slots), tuple(cu), tuple(kinds)))
+        for run in [run for run in running if run[3] == n]:
+            running.remove(run)
+            heapq.heappush(free, run[1])
+            pages += need[run[0]]
+    return steps
 
 
 def GPT_configs():

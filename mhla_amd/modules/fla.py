@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops import (CausalState, _mix2d, _runs, causal_varlen_plan, mhla_causal_prefill, featmap_rotary, mhla_causal, mhla_causal_commit, mhla_causal_extend, mhla_causal_normgate, mhla_causal_state, mhla_causal_step, mhla_causal_verify,
+from ..ops import (CausalState, PagedCausalState, _counts_fit, _cu_host, _mix2d, _runs, _slot_tuple, causal_varlen_plan, mhla_causal_prefill, featmap_rotary, featmap_rotary_decode, mhla_causal, mhla_causal_commit, mhla_causal_extend, mhla_causal_normgate, mhla_causal_state, mhla_causal_step, mhla_causal_verify,
                    mhla_causal_step_dev, naive_recurrent_mhla, rmsnorm_gate)
 from ..weights import causal_mixing_init
 
@@ -230,6 +230,123 @@ class DecodeCache:
         return self.states[layer_idx]
 
 
+class _PoolStep(NamedTuple):
+    """What `PagedDecodeCache.schedule` declared for the next model step."""
+    slots: Tuple[int, ...]               # the request (slot of every layer's pool) of every sequence of the pack
+    cu: Tuple[int, ...]                  # the pack's offsets, validated
+    counts: Tuple[int, ...]              # tokens per sequence
+    off_dev: torch.Tensor                # `cu` on the device (int32), uploaded once for all layers
+    map_dev: torch.Tensor                # `slots` on the device (int32), likewise
+    ran: set                             # the layers that have run the step
+
+
+class PagedDecodeCache:
+    """The cache of a model that serves requests by CONTINUOUS BATCHING (layers built with `exact_decoding=True`): one fp32-paged
+    `PagedCausalState` of `n_slots` slots, `capacity_chunks` chunks a slot and `n_pages` pages per layer -- created on the layer's
+    first call from its `(num_kv_heads with grouped_state, else num_heads; head_k_dim; head_v_dim)` --, and a request lives in the
+    same slot of every layer's pool.  A model step is a PACK of new tokens, `hidden_states [1, N, D]`:
+        cache.schedule(slots, cu_seqlens)   # request slots[b] takes rows cu[b] .. cu[b + 1] of the next pack (none: it sits the step out)
+        model(input_ids [1, N], cache=cache)
+    and every layer then runs `featmap_rotary_decode` (one launch: feature map and rotary of q and k at the positions its pool holds on
+    the device) and `mhla_causal_extend(cu_seqlens=)` on `pool.at(slots)` in place -- a decoding request's one token beside a slice of
+    a long prompt beside a fresh request, which is simply an empty slot.  `schedule` validates (ValueError, no state moves: distinct
+    slots in range; offsets from 0 that never decrease, one more than slots; their end is held against N when the model is called) and
+    uploads offsets and slot map ONCE for all layers.  Every layer runs exactly once between two `schedule` calls: a layer that runs
+    twice or without a schedule, and a `schedule` while only some layers have run the last one, are ValueErrors.
+    Every pool gets the same page-rule calls, so all layers' page tables are equal; what the operators refuse (`PoolExhausted`, the
+    IndexError of a slot beyond the capacity or the mixing matrix) is raised by layer 0 before anything of the step is launched.
+    `lengths`: tokens per slot (the host mirror of layer 0's pool); `pages_free`; `pool(i)`: layer i's pool (`swap_out` and the
+    like stay available there); `release(slots)` empties slots of every layer for new requests; `fork(src, dst)` copies a slot
+    (a shared prompt prefix) in every layer without copying a page.  h16 pages are refused: the extend has no form on them."""
+
+    def __init__(self, n_slots: int, capacity_chunks: int, n_pages: int, device="cuda", page_format: str = "fp32"):
+        if page_format != "fp32":
+            raise ValueError(f"PagedDecodeCache: page_format {page_format!r}: the layer step is an extend, which runs on fp32 pages only")
+        if min(int(n_slots), int(capacity_chunks), int(n_pages)) < 1:
+            raise ValueError(f"PagedDecodeCache: non-positive size n_slots={n_slots} capacity_chunks={capacity_chunks} n_pages={n_pages}")
+        self.n_slots, self.capacity_chunks, self.n_pages, self.device = int(n_slots), int(capacity_chunks), int(n_pages), torch.device(device)
+        self._pools, self._rotary, self._step = [], [], None
+
+    def schedule(self, slots, cu_seqlens) -> "PagedDecodeCache":
+        fn = "PagedDecodeCache.schedule"
+        slots = _slot_tuple(fn, slots, self.n_slots)
+        cu = _cu_host(cu_seqlens)
+        if len(cu) != len(slots) + 1:
+            raise ValueError(f"{fn}: cu_seqlens has {len(cu)} entries for {len(slots)} slots (one more than slots)")
+        last = self._step
+        if last is not None and last.ran and last.ran != set(range(len(self._pools))):
+            raise ValueError(f"{fn}: layers {sorted(set(range(len(self._pools))) - last.ran)} have not run the last scheduled step (every "
+                             "layer runs exactly once between two schedule calls)")
+        both = torch.tensor(cu + slots, dtype=torch.int32).to(self.device)   # (one small copy for the step, all layers)
+        self._step = _PoolStep(slots, cu, tuple(b - a for a, b in zip(cu, cu[1:])), both[:len(cu)], both[len(cu):], set())
+        return self
+
+    def _layer_step(self, layer_idx: int, n_tokens: int, dims):
+        """Layer `layer_idx`'s turn in the scheduled step (checked: a schedule, whose end is the pack's token count, and which this
+        layer has not run): (the step, the view of this layer's pool -- created on first use with `dims` = (heads, K, V))."""
+        fn, step = "MHLA.forward on a PagedDecodeCache", self._step
+        if step is None:
+            raise ValueError(f"{fn}: no step is scheduled: cache.schedule(slots, cu_seqlens) declares every model step")
+        if layer_idx in step.ran:
+            raise ValueError(f"{fn}: layer {layer_idx} has already run the scheduled step (every layer runs exactly once between two schedule calls)")
+        if step.cu[-1] != n_tokens:
+            raise ValueError(f"{fn}: the scheduled cu_seqlens ends at {step.cu[-1]}, the pack has N = {n_tokens} tokens")
+        while len(self._pools) <= layer_idx:
+            self._pools.append(None)
+            self._rotary.append(None)
+        if self._pools[layer_idx] is None:
+            self._pools[layer_idx] = PagedCausalState.empty(self.n_slots, *dims, self.capacity_chunks, self.n_pages, self.device)
+        view = self._pools[layer_idx].at(step.slots)
+        view._map = step.map_dev   # (the step's upload, not one per layer)
+        return step, view
+
+    def _tables(self, layer_idx: int, rotary, like):
+        """Layer `layer_idx`'s rotary tables of 64 x capacity rows in the dtype of `like`, built once and kept."""
+        kept = self._rotary[layer_idx]
+        if kept is None or kept[0].dtype != like.dtype or kept[0].device != like.device:
+            rows = 64 * self.capacity_chunks
+            cos, sin = rotary._tables(rows, like.device, like.dtype)
+            kept = self._rotary[layer_idx] = (cos[:rows], sin[:rows])
+        return kept
+
+    @property
+    def lengths(self) -> Tuple[int, ...]:
+        return self._pools[0].lengths if self._pools and self._pools[0] is not None else (0,) * self.n_slots
+
+    @property
+    def pages_free(self) -> int:
+        return self._pools[0].pages_free if self._pools and self._pools[0] is not None else self.n_pages
+
+    def pool(self, layer_idx: int) -> PagedCausalState:
+        return self._pools[layer_idx]
+
+    def release(self, slots) -> "PagedDecodeCache":
+        """`PagedCausalState.reset(slots)` on every layer's pool: the slots are empty, their pages free."""
+        slots = _slot_tuple("PagedDecodeCache.release", slots, self.n_slots)
+        for p in self._pools:
+            if p is not None:
+                p.reset(slots)
+        return self
+
+    def fork(self, src: int, dst: int) -> "PagedDecodeCache":
+        """`PagedCausalState.fork(src, dst)` on every layer's pool."""
+        _slot_tuple("PagedDecodeCache.fork", (src, dst), self.n_slots)
+        for p in self._pools:
+            if p is not None:
+                p.fork(src, dst)
+        return self
+
+    def __len__(self):
+        return sum(p is not None for p in self._pools)
+
+    def get_seq_length(self, layer_idx=0):
+        return max(self.lengths)
+
+    def __repr__(self):
+        return (f"PagedDecodeCache(n_slots={self.n_slots}, capacity_chunks={self.capacity_chunks}, n_pages={self.n_pages}, layers={len(self)}, "
+                f"lengths={self.lengths}, pages_free={self.pages_free})")
+
+
 def _elu1(x):
     return F.elu(x) + 1
 
@@ -309,6 +426,11 @@ class MHLA(nn.Module):
         of every sequence from one launch chain, rotary rows per sequence, and the cache counts the longest sequence; later calls
         are `[sequences, T', D]` on that state and read no mask.  `use_short_conv` there, and `cu_seqlens` on a cache that already
         holds a state, raise NotImplementedError.
+        With a `PagedDecodeCache` (recognised by its type alone; `exact_decoding` and `use_cache`, ValueError otherwise) a call is one
+        SCHEDULER STEP of continuous batching: `hidden_states [1, N, D]` is the pack `cache.schedule(slots, cu_seqlens)` declared, and
+        the layer runs one `featmap_rotary_decode` launch and one `mhla_causal_extend(cu_seqlens=)` on its pool's slots in place (see
+        `_pool_step`).  An `attention_mask` is a ValueError; `cu_seqlens`, `token_counts` or `speculative` as arguments,
+        `use_short_conv` and `head_k_dim % 8 != 0` raise NotImplementedError.
         `grouped_state` (not in the reference, default off: nothing changes; needs `exact_decoding`, ValueError otherwise): with
         `num_kv_heads < num_heads` every exact call -- the prefill's state, steps, extensions with or without `token_counts`,
         speculative verify / commit, device-positioned steps, the packed exact prefill -- keeps k and v un-repeated: feature map and
@@ -385,6 +507,8 @@ class MHLA(nn.Module):
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 past_key_values=None, use_cache: Optional[bool] = False, output_attentions: Optional[bool] = False,
                 **kwargs: Dict):
+        if isinstance(past_key_values, PagedDecodeCache):   # (recognised by the cache's type alone: nothing below changes)
+            return self._pool_step(hidden_states, attention_mask, past_key_values, use_cache, kwargs), None, past_key_values
         if self.exact_decoding and bool(use_cache) and getattr(past_key_values, "device_positions", False):
             if kwargs.get("speculative", False):
                 raise NotImplementedError("MHLA: speculative=True on a DecodeCache(device_positions=True) (a verify reads the host positions)")
@@ -711,6 +835,48 @@ class MHLA(nn.Module):
         else:
             o = self.g_norm(o, None).reshape(B, T, self.value_dim)
         return self.o_proj(o)
+
+    def _pool_step(self, hidden_states, attention_mask, cache, use_cache, kwargs):
+        """A scheduler step on a `PagedDecodeCache`: `hidden_states [1, N, D]` is the pack `cache.schedule(slots, cu_seqlens)` declared.
+        Projections (k, v left on `num_kv_heads` with `grouped_state`); ONE `featmap_rotary_decode` launch on this layer's
+        `pool.at(slots)` -- q and k in place, every row at the position its slot holds on the device, from the layer's tables of 64 x
+        capacity rows: no host position, no gathered table rows --; `mhla_causal_extend(cu_seqlens=)` on the same view (norm x gate as
+        `_decode` passes them; a fresh request is an empty slot, whose extend is the exact fp32 prefill); output gate and projection.
+        Everything the configuration cannot do is refused before anything runs, and what the extend would refuse (`PoolExhausted`,
+        the IndexError of a slot beyond the capacity or the mixing matrix) before this layer's first launch, its pages assigned by
+        the page rule the extend would apply."""
+        fn = "MHLA.forward on a PagedDecodeCache"
+        if not self.exact_decoding:
+            raise ValueError(f"{fn} needs a layer built with exact_decoding=True (the pool holds exact decode states)")
+        if not use_cache:
+            raise ValueError(f"{fn} needs use_cache=True: the call advances the pool")
+        if hidden_states.dim() != 3 or hidden_states.shape[0] != 1:
+            raise ValueError(f"{fn}: hidden_states is the step's pack [1, N, D], got {tuple(hidden_states.shape)}")
+        if attention_mask is not None:
+            raise ValueError(f"{fn}: no attention_mask: a pack has no padding")
+        given = [n for n in ("cu_seqlens", "token_counts") if kwargs.get(n, None) is not None] + (["speculative"] if kwargs.get("speculative", False) else [])
+        if given:
+            raise NotImplementedError(f"{fn}: {', '.join(given)} as an argument: cache.schedule(slots, cu_seqlens) carries the step's layout, "
+                                      "and speculative calls are not implemented on this cache")
+        if self.use_short_conv:
+            raise NotImplementedError(f"{fn}: use_short_conv (a convolution state per slot is not implemented)")
+        if self.head_k_dim % 8:
+            raise NotImplementedError(f"{fn} needs head_k_dim % 8 == 0 (the fused q / k prologue), got {self.head_k_dim}")
+        if self.layer_idx is None:
+            raise ValueError("MHLA(exact_decoding=True): the cache is indexed by layer_idx, which is None")
+        heads = self.num_kv_heads if self.grouped_state else self.num_heads
+        step, view = cache._layer_step(self.layer_idx, hidden_states.shape[1], (heads, self.head_k_dim, self.head_v_dim))
+        self.mixing_matrix.data = torch.clamp(self.mixing_matrix.data, 1e-5, 1).tril()   # (as every forward: layers/mhla.py:237)
+        _counts_fit("mhla_causal_extend", self.mixing_matrix, view, step.counts)
+        view.pool.reserve(step.slots, [p + n for p, n in zip(view.lengths, step.counts)])
+        q, k, v, _ = self._project(hidden_states, repeat=not self.grouped_state)
+        cos, sin = cache._tables(self.layer_idx, self.rotary, q)
+        q, k = featmap_rotary_decode(q, k, cos, sin, view, feature_map=self._fmap_name, off_dev=step.off_dev, inplace=True)
+        g, gn = self._fused_gate(hidden_states)
+        o = mhla_causal_extend(q, k, v, self.mixing_matrix, view, cu_seqlens=step.cu, gate=g, norm_weight=gn.weight if gn is not None else None,
+                               norm_eps=gn.eps if gn is not None else 1e-5, epilogue=gn is not None)
+        step.ran.add(self.layer_idx)
+        return self._gate_and_project(o.reshape(*hidden_states.shape[:2], self.value_dim) if gn is not None else o, hidden_states, gn is not None)
 
     def _device_positioned_entry(self, hidden_states, cache):
         """`DecodeCache(device_positions=True)`: what the configuration cannot do is refused on every call, the prefill included;

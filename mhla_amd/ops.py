@@ -874,6 +874,111 @@ def featmap_rotary(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, featur
     return _FmapRotary.apply(x, cos, sin, _FMAPS[feature_map], int(t_offset))
 
 
+@_device_guard
+def _fmrot_decode_launch(q, k, cos, sin, state, ntok, off, T, left_padded, yq, yk, B, fmap):
+    """The one library call of `featmap_rotary_decode`: the state gives `pos` and, a view of a pool, its slot map and slot count."""
+    view = _view if off is None else _view0
+    slot = state.map if isinstance(state, CausalStateView) else None
+    rc = _lib.load().mhla_featmap_rotary_decode(
+        view(q), view(k), cos.data_ptr(), sin.data_ptr(), cos.stride(0), cos.shape[0], state.pos.data_ptr(),
+        slot.data_ptr() if slot is not None else None, state.dims[0] if slot is not None else 0,
+        ntok.data_ptr() if ntok is not None else None, off.data_ptr() if off is not None else None, T, int(bool(left_padded)),
+        view(yq), view(yk), B, q.shape[2], k.shape[2], q.shape[3], fmap, _DTYPES[q.dtype], _stream())
+    _lib.check(rc, "mhla_featmap_rotary_decode")
+
+
+def featmap_rotary_decode(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, state: "CausalState", *,
+                          feature_map: Optional[str] = None, counts=None, left_padded: bool = False, cu_seqlens=None,
+                          off_dev: Optional[torch.Tensor] = None, inplace: bool = False):
+    """Feature map and rotary (`featmap_rotary`) of q AND k of a decode call's new tokens in ONE HIP launch, every row at the position
+    the decode state gives it: row r of sequence b's window sits at `state.pos[b] + r` (a view of a pool: at its slot's position).
+    The kernel reads the positions -- and the slot map -- on the device: no host position, no gathered table rows, nothing that a
+    captured graph could not replay; it never writes them, so call it ahead of the step / extend / verify that advances the state.
+    Returns `(q', k')`: bit for bit `featmap_rotary(x, cos.index_select(0, p), sin.index_select(0, p), feature_map)` at those
+    positions p; rows outside every window, of an inactive entry of a device slot map, or at a position beyond the tables are zeros.
+    q `[B, T, H, K]`, k `[B, T, Hkv, K]` (H a multiple of Hkv, K % 8 == 0; strided views -- slices of one fused projection -- are
+    addressed in place); cos, sin `[tab_rows, K/2]` in q's dtype, used as they are.  state: a ragged `CausalState` or any view of a
+    pool (dense, paged fp32, paged h16); only `pos` and the slot map are read, so a stale host mirror is fine.  A uniform state is a
+    ValueError: `state.to_ragged()` puts its positions on the device.
+    Token layouts, as `mhla_causal_extend` takes them: all T rows of every sequence (the default); `counts` (B ints in 0 .. T, rows
+    `[0, counts[b])`, or `[T - counts[b], T)` with `left_padded`); `cu_seqlens` (packed new tokens: q, k `[1, N, ...]`, sequence b's
+    rows `[cu[b], cu[b + 1])`; excludes `counts` and `left_padded`).  `counts` and `cu_seqlens` are validated as that call validates
+    them and go to the device in one small copy.  `off_dev`: the offsets of a pack as a device int32 `[B + 1]` tensor the caller has
+    validated and uploaded -- no host read, no copy (a cache uploads a step's offsets once for all layers); excludes the other two.
+    `inplace`: the results overwrite q and k (which must then be addressable in place).  Inference only."""
+    fn = "featmap_rotary_decode"
+    if not isinstance(state, CausalState):
+        raise TypeError(f"{fn}: state must be a CausalState, got {type(state).__name__}")
+    _refuse_paged_pool(fn, state)
+    if q.dim() != 4 or k.dim() != 4 or q.shape[-1] % 8 or q.shape[-1] < 8:
+        raise ValueError(f"{fn}: q [B, T, H, K], k [B, T, Hkv, K] with K % 8 == 0")
+    B, T, H, K = q.shape
+    Hkv = k.shape[2]
+    if tuple(k.shape) != (B, T, Hkv, K) or Hkv < 1 or H % Hkv or k.dtype != q.dtype or k.device != q.device:
+        raise ValueError(f"{fn}: k is {k.dtype} {tuple(k.shape)} on {k.device}, expected [B={B}, T={T}, Hkv, K={K}] like q ({q.dtype} on "
+                         f"{q.device}) with Hkv dividing H={H}")
+    if q.dtype not in _DTYPES:
+        raise ValueError(f"{fn}: unsupported dtype {q.dtype} (float32 / bfloat16 / float16)")
+    if feature_map not in _FMAPS:
+        raise ValueError(f"{fn}: feature_map {feature_map!r}: one of {sorted(f for f in _FMAPS if f)} or None")
+    if any(t.dim() != 2 or t.dtype != q.dtype or t.device != q.device or t.shape[1] != K // 2 or t.shape[0] < 1 for t in (cos, sin)) or cos.shape != sin.shape:
+        raise ValueError(f"{fn}: cos/sin: [tab_rows, K/2 = {K // 2}] tables in the dtype of q ({q.dtype}) on {q.device}")
+    if state.pos is None or (state.lengths is None and not isinstance(state, CausalStateView)):
+        raise ValueError(f"{fn}: the state is uniform ({state!r}) and has no positions on the device: pass state.to_ragged()")
+    if state.pos.device != q.device:
+        raise ValueError(f"{fn}: the state is on {state.pos.device}, q on {q.device}")
+    if _wants_grad(q, k):
+        raise ValueError(f"{fn} is inference only: call it under torch.no_grad() (an input requires grad)")
+    rows = _state_rows(state)
+    ntok = off = None
+    if off_dev is not None:
+        if counts is not None or cu_seqlens is not None or left_padded:
+            raise ValueError(f"{fn}: off_dev (offsets already on the device) excludes counts, cu_seqlens and left_padded")
+        if (not isinstance(off_dev, torch.Tensor) or off_dev.dtype != torch.int32 or off_dev.dim() != 1 or off_dev.shape[0] < 2
+                or off_dev.device != q.device or not off_dev.is_contiguous()):
+            raise ValueError(f"{fn}: off_dev is a contiguous int32 [sequences + 1] tensor on {q.device}")
+        if B != 1:
+            raise ValueError(f"{fn}: off_dev takes one packed row (B = 1), got B = {B}")
+        off, nseq = off_dev, off_dev.shape[0] - 1
+    elif cu_seqlens is not None:
+        if counts is not None or left_padded:
+            raise ValueError(f"{fn}: cu_seqlens (packed new tokens) excludes counts and left_padded, which place windows in padded tensors")
+        if B != 1:
+            raise ValueError(f"{fn}: cu_seqlens takes one packed row (B = 1), got B = {B}")
+        cu = _cu_host(cu_seqlens.cu if isinstance(cu_seqlens, CausalVarlenPlan) else cu_seqlens)
+        if cu[-1] != T:
+            raise ValueError(f"{fn}: cu_seqlens ends at {cu[-1]}, the pack has N = {T} tokens")
+        nseq = len(cu) - 1
+    else:
+        nseq = B
+        if counts is not None:
+            counts = _int_tuple(fn, "counts", counts, B, T)
+    if rows != nseq:
+        raise ValueError(f"{fn}: the state holds {rows} sequences, the tokens {nseq}")
+    if T > _PACK_MAX_TOKENS:
+        raise ValueError(f"{fn}: T = {T} token rows, one call takes {_PACK_MAX_TOKENS}")
+    _require_gpu(q, k, cos, sin)
+    if inplace:
+        if not (_step_view_ok(q) and _step_view_ok(k)):
+            raise ValueError(f"{fn}: inplace needs q and k addressable in place (last dim contiguous, strides multiples of 4 elements, "
+                             f"{4 * q.element_size()}-byte aligned)")
+        yq, yk = q, k
+    else:
+        q, k = (t if _step_view_ok(t) else t.contiguous() for t in (q, k))
+        yq, yk = torch.empty((B, T, H, K), dtype=q.dtype, device=q.device), torch.empty((B, T, Hkv, K), dtype=q.dtype, device=q.device)
+    if T == 0 or nseq == 0:   # (a pack whose sequences are all empty has no row)
+        return yq, yk
+    if cos.stride(1) != 1 or sin.stride(1) != 1 or cos.stride(0) != sin.stride(0) or cos.stride(0) % 4:
+        cos, sin = cos.contiguous(), sin.contiguous()
+    # the one small copy of the call: the counts, or the offsets of a pack (off_dev: none)
+    if off is None and cu_seqlens is not None:
+        off = torch.tensor(cu, dtype=torch.int32).to(q.device)
+    elif counts is not None:
+        ntok = torch.tensor(counts, dtype=torch.int32).to(q.device)
+    _fmrot_decode_launch(q, k, cos, sin, state, ntok, off, T, left_padded, yq, yk, nseq, _FMAPS[feature_map])
+    return yq, yk
+
+
 class _QkPrologue(torch.autograd.Function):
     @staticmethod
     @_device_guard
@@ -1592,8 +1697,9 @@ class CausalStateView(CausalState):
     graph: an entry outside 0 .. n_slots - 1, -1 for instance, makes that row INACTIVE -- its row of the result is zeros and no slot,
     position or flag is touched; entries that name a slot must be distinct (rows that share one race).  The step marks the POOL
     stale, and `pool.sync()` refreshes it.
-    Not covered: `DecodeCache`, the fla layer and `hosts/gpt.py` build their states as before; a slot of a dense pool reserves all
-    `capacity_chunks` chunks (`PagedCausalState`: a pool whose finished chunks are pages)."""
+    Not covered: `DecodeCache` builds its states as before (the fla layer and `hosts/gpt.py` run on a PAGED pool through
+    `modules.PagedDecodeCache`); a slot of a dense pool reserves all `capacity_chunks` chunks (`PagedCausalState`: a pool whose
+    finished chunks are pages)."""
 
     __slots__ = ("pool", "slots", "_map", "_mirror", "dims", "pages")
 
@@ -1785,7 +1891,8 @@ class PagedCausalState(CausalState):
     contiguous `SwappedSlots` blob, in pinned host memory (preemption) or on the device, and `swap_in(blob, slots)` puts it back bit
     for bit into empty slots of this or another pool of the same Hkv, K, V and page format, by the page rule.  The pool never evicts on
     its own: swapping is the caller's decision, and `PoolExhausted` is still raised before anything changes.
-    Not covered: `DecodeCache`, the fla layer and `hosts/gpt.py` keep states of their own; dense pools have no swap.
+    Through a model: `modules.PagedDecodeCache` holds one fp32 pool per layer, and the fla layer and `hosts/gpt.py` run packed scheduler
+    steps on it.  Not covered: `DecodeCache` keeps states of its own; dense pools have no swap.
     Page format `"h16"` (`empty(..., page_format="h16")`, or a float16 `pages` together with `page_mult [n_pages, Hkv, K V / 64]`,
     float32): a page takes 2 bytes an element -- an fp16 payload times one power-of-two multiplier per 64 adjacent elements of a
     head's flattened `[K, V]` chunk (K V % 64 == 0), 11 significand bits relative to the group's largest element: the precision of

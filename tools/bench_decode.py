@@ -116,6 +116,20 @@ layouts.  Positions and host mirror are put back before every call, for every va
 paths alone on a tree that has `cu_seqlens` as well: the process then does exactly the work of the older tree's, which is what a
 comparison of the two builds needs (a process that also runs the packed variants differs in more than its library).
 
+`--pool-layer`: a scheduler step of continuous batching through the fla LAYER on a `PagedDecodeCache` (a bf16 layer of the 340M shape:
+hidden 1024, 4 heads, K = 128, V = 256, 32 chunks), at two mixes -- `decode`: 32 requests x 1 token; `mixed`: 31 x 1 token + one
+256-token slice of a prompt (from position 1000: it closes four chunks) --, every sequence at a position of its own around 1000,
+positions and host mirrors put back before every call.  Three tables, alternating variants, `--reps` times, `--steps` calls each:
+the PROLOGUE alone, `featmap_rotary_decode` (one `k_fr_decode` launch reading positions and slot map on the device) against today's
+sequence for the same pack (position arithmetic with torch ops -- arange, searchsorted, adds --, two `index_select`s of the tables, two
+`k_fmap_rotary` launches): wall time from HIP events and the device time of the library's kernels from the per-launch hook (the torch
+kernels of today's path are in its wall time only); the whole LAYER step on the pool against the existing padded `DecodeCache` call
+with `token_counts` ([32, 1, D] / [32, 256, D]); and the HOST's share of a model step across 24 layers -- `schedule` once, then per
+layer the view of the pool, the capacity check and the page rule, timed with the host clock and no launch -- in the steady state
+and on a step in which every request opens a new chunk (a page and a table row pushed per request and layer): the figure a
+follow-up on one page table shared by all layers would rest on.  Also the prologue kernel on a pack of 32 x 512 tokens with its
+rows on and off 16-byte boundaries: 16-byte against 8-byte pieces.
+
 `--swap`: `PagedCausalState.swap_out` / `swap_in` on the pools of `--paged` / `--paged-h16` (H = 4, K = 128, V = 256, 2 B slots, 19 pages a
 slot, a random table), the B sequences at the "off" lengths (about 1000 tokens, 13 .. 17 finished pages each), B = 4 and 32, fp32 and
 h16 pages.  Device blob: wall time per call (events around `--steps` calls, at most 100) and the device time of the swap kernel (the
@@ -731,6 +745,143 @@ def swap_config(B, H, K, V, steps, reps):
     return rec
 
 
+def pool_layer_config(steps, reps, layers=24):
+    import time
+    from mhla_amd import modules, ops
+    B, D, H, K, V, CAP, SLICE = 32, 1024, 4, 128, 256, 32, 256
+    torch.manual_seed(1)
+    g = torch.Generator().manual_seed(1)
+    m = modules.MHLA(mode="chunk", hidden_size=D, num_heads=H, feature_map="relu", layer_idx=0, max_chunks=CAP, exact_decoding=True)
+    m = m.to(DEV).to(torch.bfloat16).eval()
+    lens = tuple(960 + (7 * b) % 63 for b in range(B - 1)) + (1000,)
+    slots = torch.randperm(2 * B, generator=g)[:B].tolist()
+    mixes = {"decode": (1,) * B, "mixed": (1,) * (B - 1) + (SLICE,)}
+    cos, sin = m.rotary._tables(64 * CAP, DEV, torch.bfloat16)
+    cos, sin = cos[:64 * CAP], sin[:64 * CAP]
+    rec = {"pool_layer": {"B": B, "hidden": D, "H": H, "K": K, "V": V, "capacity_chunks": CAP, "lengths": lens, "slots": slots},
+           "steps_per_batch": steps, "reps": reps}
+    with torch.no_grad():
+        for mix, counts in mixes.items():
+            cu = [0]
+            for n in counts:
+                cu.append(cu[-1] + n)
+            N, T = cu[-1], max(counts)
+            # ---- the states: a pool behind a PagedDecodeCache, a ragged state behind a DecodeCache, both at `lens`
+            cache = modules.PagedDecodeCache(2 * B, CAP, 2 * B * 21, DEV)
+            cache.schedule(slots, list(range(B + 1)))
+            m(torch.randn(1, B, D, generator=g).to(torch.bfloat16).to(DEV), past_key_values=cache, use_cache=True)   # (creates the pool)
+            pool = cache.pool(0)
+            pool.reserve(slots, [n + c for n, c in zip(lens, counts)])
+            pool.pages.normal_(0, 0.1)
+            pool.P.normal_(0, 0.1)
+            pool_lens = [0] * (2 * B)
+            for s_, n in zip(slots, lens):
+                pool_lens[s_] = n
+            pool_lens = tuple(pool_lens)
+            pool_pos = torch.tensor(pool_lens, dtype=torch.int32, device=DEV)
+            st = mhla_amd.CausalState.empty(B, H, K, V, CAP, DEV)
+            st.S.normal_(0, 0.1)
+            st.P.normal_(0, 0.1)
+            st = mhla_amd.CausalState(st.S, st.P, st.Cur, lengths=lens)
+            own = modules.DecodeCache()
+            own.update(recurrent_state=st, layer_idx=0, offset=max(lens))
+            st_pos = torch.tensor(lens, dtype=torch.int32, device=DEV)
+            x_pack = torch.randn(1, N, D, generator=g).to(torch.bfloat16).to(DEV)
+            x_pad = torch.randn(B, T, D, generator=g).to(torch.bfloat16).to(DEV)
+            q = torch.randn(1, N, H, K, generator=g).to(torch.bfloat16).to(DEV)
+            k = torch.randn(1, N, H, K, generator=g).to(torch.bfloat16).to(DEV)
+            view = pool.at(slots)
+            off = torch.tensor(cu, dtype=torch.int32, device=DEV)
+            cu_dev, map64 = off.long(), view.map.long()
+
+            def put_back():
+                pool.lengths, pool.seen = pool_lens, max(pool_lens)
+                pool.pos.copy_(pool_pos)
+                st.lengths, st.seen = lens, max(lens)
+                st.pos.copy_(st_pos)
+                own._seen[0] = max(lens)
+
+            def prologue_new():
+                mhla_amd.featmap_rotary_decode(q, k, cos, sin, view, feature_map="relu", off_dev=off)
+
+            def prologue_today():   # the layer's `_rotary_rows` + `_featmap_rotary` for a pack: positions with torch ops, gathered table rows
+                tpos = torch.arange(N, device=DEV)
+                seq = torch.searchsorted(cu_dev, tpos, right=True) - 1
+                p = pool.pos.long()[map64][seq] + tpos - cu_dev[seq]
+                c, s_ = cos.index_select(0, p), sin.index_select(0, p)
+                mhla_amd.featmap_rotary(q, c, s_, "relu"), mhla_amd.featmap_rotary(k, c, s_, "relu")
+
+            def layer_pool():
+                put_back()
+                cache.schedule(slots, cu)
+                m(x_pack, past_key_values=cache, use_cache=True)
+
+            def layer_padded():   # the existing DecodeCache call: padded [B, T, D], right-aligned windows
+                put_back()
+                m(x_pad, past_key_values=own, use_cache=True, token_counts=counts)
+
+            fns = {"prologue_k_fr_decode": prologue_new, "prologue_today": prologue_today, "layer_pool_step": layer_pool,
+                   "layer_padded_token_counts": layer_padded}
+            wall, devt, kern = {n: [] for n in fns}, {n: [] for n in fns}, {}
+            for _ in range(reps):
+                for n, fn in fns.items():
+                    wall[n].append(batch_us(fn, steps))
+                for n, fn in fns.items():
+                    kern[n] = kernel_times(fn, iters=20)
+                    devt[n].append(sum(kern[n].values()))
+            rec[mix] = {"tokens": N, "padded_rows": B * T, "wall_us": {n: spread(x) for n, x in wall.items()},
+                        "library_device_us": {n: spread(x) for n, x in devt.items()},
+                        "kernels_us": {n: {kn: round(us, 2) for kn, us in ks.items()} for n, ks in kern.items()}}
+        # ---- the prologue's piece width: a pack large enough to be bound by memory (32 x 512 tokens, q and k rotated in place), its rows
+        # on 16-byte boundaries (16-byte pieces) and 8 bytes off them (the 8-byte pieces of k_fmap_rotary); the bits are the same
+        NB = 32 * 512
+        big = torch.randn(1, NB, 2 * H * K + 8, generator=g).to(torch.bfloat16).to(DEV)
+        first = mhla_amd.CausalState.empty(32, 1, 8, 8, 1, DEV).to_ragged()
+        off_big = torch.arange(0, NB + 1, 512, dtype=torch.int32, device=DEV)
+        width = {}
+        for name, at in (("16_byte_pieces", 0), ("8_byte_pieces", 4)):
+            qv, kv = big[..., at:at + H * K].view(1, NB, H, K), big[..., at + H * K:at + 2 * H * K].view(1, NB, H, K)
+            fn = lambda qv=qv, kv=kv: mhla_amd.featmap_rotary_decode(qv, kv, cos, sin, first, feature_map="relu", off_dev=off_big, inplace=True)
+            width[name] = {"wall_us": spread([batch_us(fn, steps) for _ in range(reps)]),
+                           "device_us": spread([sum(kernel_times(fn, iters=20).values()) for _ in range(reps)])}
+        rec["piece_width"] = {"tokens": NB, "bytes_moved_MB": round(2 * 2 * NB * 2 * H * K / 2 ** 20, 1), **width}
+        # ---- the host's share of a model step: per layer the view, the capacity check and the page rule (no launch), `layers` pools
+        cache = modules.PagedDecodeCache(2 * B, CAP, 2 * B * 21, DEV)
+        dims = (1, 8, 8)   # (the host's work does not depend on the size of a page: small ones, 24 pools)
+        cache.schedule(slots, list(range(B + 1)))
+        for i in range(layers):
+            cache._layer_step(i, B, dims)
+            cache._step.ran.add(i)
+        host = {}
+        for place, at in (("steady", lens), ("every_request_opens_a_chunk", tuple(64 * (15 + b % 3) for b in range(B)))):
+            full = [0] * (2 * B)
+            for s_, n in zip(slots, at):
+                full[s_] = n
+            full = tuple(full)
+            for i in range(layers):
+                cache.pool(i).reserve(slots, list(at))
+            times = []
+            for _ in range(max(20, steps // 4)):
+                for i in range(layers):   # (put back: lengths, and the pages the last round assigned)
+                    pl = cache.pool(i)
+                    pl.lengths, pl.seen = full, max(full)
+                    pl.trim(slots)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                cache.schedule(slots, list(range(B + 1)))
+                for i in range(layers):
+                    step, view = cache._layer_step(i, B, dims)
+                    ops._counts_fit("bench", m.mixing_matrix, view, step.counts)
+                    view.pool.reserve(step.slots, [p + n for p, n in zip(view.lengths, step.counts)])
+                    step.ran.add(i)
+                times.append((time.perf_counter() - t0) * 1e6)
+                torch.cuda.synchronize()
+            host[place] = {"per_step_us": spread(times), "per_layer_us": round(statistics.median(times) / layers, 2)}
+        rec["host_share"] = {"layers": layers, "sequences": B, **host}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def launch_counts(fn):
     """{kernel: launches} of one call of `fn` (the library's per-launch hook)."""
     import ctypes
@@ -1195,8 +1346,11 @@ if __name__ == "__main__":
     ap.add_argument("--packed", action="store_true")
     ap.add_argument("--existing-only", action="store_true")
     ap.add_argument("--swap", action="store_true")
+    ap.add_argument("--pool-layer", action="store_true")
     a = ap.parse_args()
-    if a.swap:
+    if a.pool_layer:
+        pool_layer_config(max(100, a.steps), a.reps)
+    elif a.swap:
         for B in (4, 32):
             swap_config(B, 4, 128, 256, min(100, a.steps), a.reps)
     elif a.packed:
