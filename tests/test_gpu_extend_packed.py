@@ -3,24 +3,24 @@ mhla_causal_{extend,verify,commit}_packed -- against today's PADDED calls on the
 finished chunks, P, Cur, pos, lengths), and against the fp64 segment formula at the tolerances `check_step_rows` / `check_state`
 carry.  The sequences are `decode_util.TABLE` (8 sequences, 305 tokens, capacity 4, a 5 x 5 matrix), the drafts `SPEC_TABLE`; the
 shapes are the smallest at which the tiling branches differ.  On views of a dense and of an fp32 paged pool (slots permuted, one
-unused, every other byte poison) the reference is the same packed call on `view.compact()`."""
+unused, every other byte poison: `pool_util.fill_pool`) the reference is the same packed call on `view.compact()`, and nothing the
+call does not name changes a bit (`pool_util.check_untouched`)."""
 import functools
 
 import pytest
 import torch
 
 import mhla_amd
-from mhla_amd import CausalState, PagedCausalState
 from decode_util import (ACCEPT, COUNTS, DRAFTS, SPEC_CAP, SPEC_L, SPEC_T, TABLE, TABLE_CAP, check_state, check_step_rows, cpu_state,
                          extend_ragged_ref, one_sequence, packed_views, ragged_start, same_seq_state, table_inputs, unchanged)
 from gpu_util import DEV, launches, poison
+from pool_util import check_untouched, fill_pool, snapshot
 
 pytestmark = pytest.mark.gpu
 
 # (dtype, H, Hkv, K, V)
 SHAPES = [(torch.float32, 2, 2, 64, 64), (torch.bfloat16, 2, 2, 64, 64), (torch.float32, 2, 2, 40, 72), (torch.bfloat16, 4, 2, 64, 64)]
 IDS = ["fp32-K64V64", "bf16-K64V64", "fp32-K40V72", "bf16-G2"]
-NAN = float("nan")
 
 
 def _cu(counts):
@@ -155,52 +155,6 @@ def test_verify_then_commit_packed_equal_padded(shape):
     unchanged(st0, keep0)
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-def _dense_pool(start, slots, n_slots):
-    """A dense pool of `n_slots` rows, every byte NaN but for `slots`, which hold the sequences of `start` in that order."""
-    B, Hkv, cap, K, V = start.S.shape
-    nan = lambda *s: torch.full(s, NAN, dtype=torch.float32, device=DEV)
-    S, P, Cur = nan(n_slots, Hkv, cap, K, V), nan(n_slots, Hkv, K, V), nan(n_slots, Hkv, K, V)
-    host = [0] * n_slots
-    for b, s in enumerate(slots):
-        S[s], P[s], Cur[s], host[s] = start.S[b], start.P[b], start.Cur[b], start.lengths[b]
-    return CausalState(S, P, Cur, 0, 64, lengths=host)
-
-
-def _paged_pool(start, slots, n_slots, n_pages):
-    """The same as a paged pool: the finished chunks in pages handed out from the top, descending within a slot."""
-    B, Hkv, cap, K, V = start.S.shape
-    nan = lambda *s: torch.full(s, NAN, dtype=torch.float32, device=DEV)
-    rows, host, nxt = [[-1] * cap for _ in range(n_slots)], [0] * n_slots, n_pages - 1
-    for b, s in enumerate(slots):
-        host[s] = start.lengths[b]
-        for j in reversed(range(-(-host[s] // 64))):
-            rows[s][j], nxt = nxt, nxt - 1
-    pool = PagedCausalState(nan(n_pages, Hkv, K, V), nan(n_slots, Hkv, K, V), nan(n_slots, Hkv, K, V), rows, lengths=host)
-    for b, s in enumerate(slots):
-        for j in range(host[s] // 64):
-            pool.pages[rows[s][j]] = start.S[b, :, j]
-        pool.P[s], pool.Cur[s] = start.P[b], start.Cur[b]
-    return pool
-
-
-def _pool_rest(pool, unused):
-    """What a call on the view must not touch: the unused slot (P, Cur, pos, its dense S) and the pages no table row names."""
-    torch.cuda.synchronize()
-    out = [pool.P[unused].clone(), pool.Cur[unused].clone(), pool.pos[unused].clone()]
-    if pool.pages is None:
-        out.append(pool.S[unused].clone())
-    return out
-
-
-def _free_pages(pool):
-    named = {p for r in pool.table for p in r if p >= 0}
-    return [p for p in range(pool.pages.shape[0]) if p not in named]
-
-
 @pytest.mark.parametrize("kind", ["dense", "paged"])
 @pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[3]], ids=[IDS[1], IDS[3]])
 def test_the_same_three_on_views_of_a_pool(shape, kind):
@@ -212,12 +166,14 @@ def test_the_same_three_on_views_of_a_pool(shape, kind):
         slots = [s for s in reversed(range(B + 1)) if s != unused]
         slots = slots[1::2] + slots[0::2]   # (neither ascending nor descending)
         start = _start(shape, spec)
-        pool = _dense_pool(start, slots, B + 1) if kind == "dense" else _paged_pool(start, slots, B + 1, 4 * B)
+        # (pages handed out from the top of 4 B: every sequence's block below the one before it)
+        pages, top = {}, 4 * B
+        for s, n in zip(slots, start.lengths):
+            pages[s], top = list(range(top - -(-n // 64), top)), top - -(-n // 64)
+        pool = fill_pool(kind, start, slots, n_slots=B + 1, table=pages, n_pages=4 * B)
         view = pool.at(slots)
         assert view.lengths == start.lengths
-        ref = view.compact()
-        rest = _pool_rest(pool, unused)
-        pages0 = pool.pages.clone() if kind == "paged" else None
+        ref, before = view.compact(), snapshot(pool)
         if not spec:
             want = mhla_amd.mhla_causal_extend(q, k, v, md, ref, cu_seqlens=cu)
             got = mhla_amd.mhla_causal_extend(q, k, v, md, view, cu_seqlens=cu)
@@ -232,12 +188,8 @@ def test_the_same_three_on_views_of_a_pool(shape, kind):
         assert torch.equal(got, want), f"{kind} view, {'verify' if spec else 'extend'}: rows differ from the call on view.compact()"
         _same_states(f"{kind} view", view.compact(), ref, after)
         assert [pool.lengths[s] for s in slots] == after and pool.lengths[unused] == 0
-        for was, now in zip(rest, _pool_rest(pool, unused)):
-            assert torch.equal(_bits(was), _bits(now)), f"{kind} view: the unused slot {unused} changed"
-        if kind == "paged":
-            for p in _free_pages(pool):
-                assert torch.equal(_bits(pool.pages[p]), _bits(pages0[p])), f"page {p}, which no table row names, was written"
-            assert pool.table_dev.tolist() == pool.table
+        # the unused slot and every page but those the new tokens reach (to the draft's end, for a verify) keep every bit
+        check_untouched(f"{kind} view", pool, before, slots, reach=[p + n for p, n in table])
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)

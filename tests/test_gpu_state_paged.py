@@ -1,12 +1,11 @@
-"""Decode calls on a PAGED state pool (`PagedCausalState`, the library's mhla_causal_*_paged entry points): every call kind on the
-non-monotonic view [3, 0, 4] of a NaN-poisoned pool of 5 slots and 10 pages against the existing un-paged, un-slotted call on
-`view.compact()`, BIT FOR BIT (integer views, so the poison compares): the rows, the finished chunks read back through the page
-table, P, Cur and pos of the three slots, every bit of the slots the call does not name, and every bit of every page the call must
-not write -- the free ones, other slots', and the view's own finished chunks.  The pool is built through the explicit-table
-constructor from an un-paged pack prefill by plain tensor copies, with a SCRAMBLED table (pages interleaved across slots and
-descending within a slot: an identity mapping would hide a wrong index).  The shapes, tokens and lengths are those of
-test_gpu_state_slots.py.  One captured graph of a device-positioned step, with the slot map and the page table rewritten in place
-between replays, is held to the fp64 oracle of every request alone (the K split depends on B H: no bit equality there)."""
+"""What a PAGED state pool (`PagedCausalState`, the library's mhla_causal_*_paged entry points) has beyond the view contract it shares
+with a dense pool (test_gpu_state_slots.py: step, extend with counts, verify / commit and pack prefill on both kinds): the setup
+itself, an extend without counts, a fork that shares pages, the device-positioned step on a chunk without a page, and walks ten
+chunks deep -- every call on a view of a NaN-poisoned pool of 5 slots and 10 pages against the existing un-paged, un-slotted call on
+`view.compact()`, BIT FOR BIT (integer views, so the poison compares), with tests/pool_util.py's pool (`make_pool("paged", ...)`: built
+through the explicit-table constructor from an un-paged pack prefill by plain tensor copies, with a SCRAMBLED table) and checks
+(`check_pool`).  One captured graph of a device-positioned step, with the slot map and the page table rewritten in place between
+replays, is held to the fp64 oracle of every request alone (the K split depends on B H: no bit equality there)."""
 import pytest
 import torch
 
@@ -14,73 +13,9 @@ import mhla_amd
 from mhla_amd import CausalState, PagedCausalState
 from gpu_util import DEV
 from decode_util import check_state, check_step_rows, ragged_inputs
-from test_gpu_state_slots import (ACCEPT, CAP, CASES, COUNTS, IDS, L, LENGTHS, N_SLOTS, POISON, T, VIEW, bits, same_bits, tokens, windows)
+from pool_util import CAP, CASES, IDS, L, LENGTHS, N_PAGES, N_SLOTS, T, VIEW, check_pool, make_pool, same_bits, snapshot, tokens
 
 pytestmark = pytest.mark.gpu
-
-N_PAGES = 10
-# slot -> pages of its chunks 0, 1, ...: descending within a slot, interleaved across slots; pages 0, 1, 3, 8, 9 start free
-TABLE = {4: [7, 5, 2], 3: [6], 0: [4]}
-
-
-def make_pool(dtype, H, Hkv, K, V, slots=VIEW, lengths=LENGTHS, table=TABLE):
-    """A paged pool whose every byte is poison but for the slots `slots`, which hold what the existing (un-paged) pack prefill gives
-    for `lengths`: the finished chunks copied into the pages `table` names."""
-    hk, hv, *_, mix = tokens(dtype, H, Hkv, K, V)
-    cu = [0]
-    for n in lengths:
-        cu.append(cu[-1] + n)
-    src = mhla_amd.mhla_causal_state(hk[:, :cu[-1]], hv[:, :cu[-1]], mix, cu_seqlens=cu, capacity_chunks=CAP)
-    nan = lambda *s: torch.full(s, float("nan"), dtype=torch.float32, device=DEV)
-    rows = [[-1] * CAP for _ in range(N_SLOTS)]
-    host = [0] * N_SLOTS
-    for s, n in zip(slots, lengths):
-        host[s] = n
-        rows[s][:len(table[s])] = table[s]
-    pool = PagedCausalState(nan(N_PAGES, Hkv, K, V), nan(N_SLOTS, Hkv, K, V), nan(N_SLOTS, Hkv, K, V), rows, lengths=host)
-    assert pool.table_dev.tolist() == rows and pool.pages_used == sum(len(table[s]) for s in slots)
-    pool.pos.fill_(POISON)
-    for b, (s, n) in enumerate(zip(slots, lengths)):
-        for j in range(n // 64):
-            pool.pages[rows[s][j]] = src.S[b, :, j]
-        pool.P[s], pool.Cur[s], pool.pos[s] = src.P[b], src.Cur[b], n
-    pool.full   # (zeros: a flag is a finding)
-    return pool
-
-
-def snapshot(pool):
-    return tuple(t.clone() for t in (pool.pages, pool.P, pool.Cur, pool.pos, pool.full)) + ([list(r) for r in pool.table], pool.lengths)
-
-
-def check_pool(name, pool, before, ref, slots, lengths_after, touched=None, flagged=(), reach=None):
-    """Slots `slots` of the pool hold the bits of the compact state `ref` (finished chunks through the page table, P, Cur, pos);
-    every other slot, and of `slots` those not in `touched`, hold every bit they held `before` (`flagged`: but for their `full`
-    flag).  A page keeps every bit unless it holds a chunk a touched slot may write: from the chunk that was open `before` to the
-    last one its tokens reach (`reach`: tokens per slot; default `lengths_after`)."""
-    torch.cuda.synchronize()
-    touched = list(slots) if touched is None else touched
-    reach = lengths_after if reach is None else reach
-    assert pool.table_dev.tolist() == pool.table, f"{name}: the device table is not the host mirror"
-    writable = set()
-    for b, s in enumerate(slots):
-        n = lengths_after[b]
-        if s in touched:
-            for j in range(n // 64):
-                assert 0 <= pool.table[s][j] < N_PAGES, f"{name}: finished chunk {j} of slot {s} has no page"
-                same_bits(f"{name}: chunk {j} of slot {s} (page {pool.table[s][j]})", pool.pages[pool.table[s][j]], ref.S[b, :, j])
-            same_bits(f"{name}: P of slot {s}", pool.P[s], ref.P[b])
-            same_bits(f"{name}: Cur of slot {s}", pool.Cur[s], ref.Cur[b])
-            assert int(pool.pos[s]) == int(ref.pos[b]) == n, f"{name}: pos of slot {s} is {int(pool.pos[s])}, the compact state's {int(ref.pos[b])}, expected {n}"
-            writable.update(pool.table[s][j] for j in range(before[6][s] // 64, -(-reach[b] // 64)))
-    for s in range(N_SLOTS):
-        if s not in touched:
-            for part, now, was in zip(("P", "Cur", "pos", "full"), (pool.P, pool.Cur, pool.pos, pool.full), before[1:5]):
-                if part != "full" or s not in flagged:
-                    same_bits(f"{name}: {part} of slot {s}, which the call does not name or leaves alone", now[s], was[s])
-            assert pool.table[s] == before[5][s], f"{name}: the table row of slot {s}, which the call does not name"
-    for p in range(N_PAGES):
-        if p not in writable:
-            same_bits(f"{name}: page {p}, which the call must not write", pool.pages[p], before[0][p])
 
 
 def test_the_compact_state_of_a_view_is_the_prefill():
@@ -89,7 +24,7 @@ def test_the_compact_state_of_a_view_is_the_prefill():
     hk, hv, *_, mix = tokens(*shape)
     n = sum(LENGTHS)
     src = mhla_amd.mhla_causal_state(hk[:, :n], hv[:, :n], mix, cu_seqlens=[0, 63, 68, n], capacity_chunks=CAP)
-    pool = make_pool(*shape)
+    pool = make_pool("paged", shape)
     c = pool.at(VIEW).compact()
     assert type(c) is CausalState and c.lengths == LENGTHS and pool.nbytes < 4 * (N_PAGES + 2 * N_SLOTS + 1) * shape[2] * shape[3] * shape[4]
     same_bits("S[2][:2]", c.S[2, :, :2], src.S[2, :, :2])
@@ -100,47 +35,11 @@ def test_the_compact_state_of_a_view_is_the_prefill():
                                   hv[:, :1].expand(N_SLOTS, -1, -1, -1), mix, pool)
 
 
-@pytest.mark.parametrize("epilogue", [False, True], ids=["plain", "gate-norm"])
-@pytest.mark.parametrize("shape", CASES, ids=IDS)
-def test_step_on_a_paged_view_is_the_step_on_the_compact_state(shape, epilogue):
-    _, _, q, k, v, gate, w, mix = tokens(*shape)
-    kw = dict(gate=gate[:, :1], norm_weight=w) if epilogue else {}
-    pool = make_pool(*shape)
-    view = pool.at(VIEW)
-    assert view.lengths == LENGTHS
-    ref, before = view.compact(), snapshot(pool)
-    want = mhla_amd.mhla_causal_step(q[:, :1], k[:, :1], v[:, :1], mix, ref, **kw)
-    got = mhla_amd.mhla_causal_step(q[:, :1], k[:, :1], v[:, :1], mix, view, **kw)
-    same_bits("rows", got, want)
-    after = tuple(n + 1 for n in LENGTHS)
-    assert view.lengths == ref.lengths == after and tuple(pool.lengths[s] for s in VIEW) == after and pool.lengths[1] == pool.lengths[2] == 0
-    assert pool.table == before[5], "every chunk the step touches had its page"
-    check_pool("step", pool, before, ref, VIEW, after)
-
-
-@pytest.mark.parametrize("left", [False, True], ids=["right-padded", "left-padded"])
-@pytest.mark.parametrize("shape", CASES, ids=IDS)
-def test_extend_with_counts_on_a_paged_view(shape, left):
-    _, _, q, k, v, gate, w, mix = tokens(*shape)
-    q, k, v, gate = (windows(t, COUNTS, left) for t in (q, k, v, gate))
-    pool = make_pool(*shape)
-    view = pool.at(VIEW)
-    ref, before = view.compact(), snapshot(pool)
-    call = lambda st: mhla_amd.mhla_causal_extend(q, k, v, mix, st, counts=COUNTS, left_padded=left, gate=gate, norm_weight=w)
-    want = call(ref)
-    got = call(view)
-    same_bits("rows", got, want)
-    after = tuple(p + n for p, n in zip(LENGTHS, COUNTS))
-    assert view.lengths == ref.lengths == after
-    assert pool.table[0][:2] == [4, 0] and pool.pages_used == 6, "slot 0 grew into chunk 1: the lowest free page"
-    check_pool("extend", pool, before, ref, VIEW, after)
-
-
 @pytest.mark.parametrize("shape", CASES, ids=IDS)
 def test_extend_without_counts_on_a_paged_view(shape):
     """Every slot takes all T = 70 tokens: slot 4 mixes chunks 0 .. 2 through the table for its later segment, nine pages in use."""
     _, _, q, k, v, gate, w, mix = tokens(*shape)
-    pool = make_pool(*shape)
+    pool = make_pool("paged", shape)
     view = pool.at(VIEW)
     ref, before = view.compact(), snapshot(pool)
     call = lambda st: mhla_amd.mhla_causal_extend(q, k, v, mix, st, gate=gate, norm_weight=w)
@@ -152,58 +51,10 @@ def test_extend_without_counts_on_a_paged_view(shape):
     check_pool("extend", pool, before, ref, VIEW, after)
 
 
-@pytest.mark.parametrize("shape", CASES, ids=IDS)
-def test_verify_then_commit_on_a_paged_view(shape):
-    _, _, q, k, v, gate, w, mix = tokens(*shape)
-    q, k, v, gate = (windows(t, COUNTS, False) for t in (q, k, v, gate))
-    pool = make_pool(*shape)
-    view = pool.at(VIEW)
-    ref, before = view.compact(), snapshot(pool)
-    want, draft_ref = mhla_amd.mhla_causal_verify(q, k, v, mix, ref, counts=COUNTS, gate=gate, norm_weight=w)
-    got, draft = mhla_amd.mhla_causal_verify(q, k, v, mix, view, counts=COUNTS, gate=gate, norm_weight=w)
-    same_bits("rows", got, want)
-    assert draft.view is view and view.lengths == LENGTHS
-    ends = tuple(p + n for p, n in zip(LENGTHS, COUNTS))
-    # (only the finished chunks are specified after a verify: the header; the draft's pages are assigned)
-    assert pool.pages_used == 6
-    check_pool("verify", pool, before, ref, VIEW, LENGTHS, reach=ends)
-    mhla_amd.mhla_causal_commit(draft_ref, mix, ref, ACCEPT)
-    assert mhla_amd.mhla_causal_commit(draft, mix, view, ACCEPT) is view
-    after = tuple(p + a for p, a in zip(LENGTHS, ACCEPT))
-    assert view.lengths == ref.lengths == after
-    check_pool("commit", pool, before, ref, VIEW, after, reach=ends)
-    # slot 0 was verified to 75 tokens and accepted 38: the page of chunk 1 goes back
-    page = pool.table[0][1]
-    pool.trim(VIEW)
-    assert pool.table[0] == [4, -1, -1, -1] and pool.pages_used == 5 and page in pool.free and pool.table_dev.tolist() == pool.table
-
-
-@pytest.mark.parametrize("lengths", [(130, 0), (64, 70)], ids=["130+0", "64+70"])
-@pytest.mark.parametrize("shape", CASES, ids=IDS)
-def test_pack_prefill_into_paged_slots(shape, lengths):
-    hk, hv, *_, mix = tokens(*shape)
-    n, slots = sum(lengths), [4, 1]
-    cu = [0, lengths[0], n]
-    # (the pack: other tokens than those slot 4 was filled from)
-    k, v = hk[:, 10:10 + n], hv[:, 10:10 + n]
-    pool = make_pool(*shape)
-    before = snapshot(pool)
-    ref = mhla_amd.mhla_causal_state(k, v, mix, cu_seqlens=cu, capacity_chunks=CAP)
-    view = pool.at(slots)
-    assert mhla_amd.mhla_causal_state(k, v, mix, cu_seqlens=cu, into=view) is view
-    assert view.lengths == ref.lengths == lengths and pool.lengths == (5, lengths[1], 0, 63, lengths[0])
-    assert pool.pages_used == 2 + sum(-(-m // 64) for m in lengths), "slot 4 starts anew: its three pages went back first"
-    # (a prefill starts the slot anew: every chunk up to its length may be written)
-    start = list(before)
-    start[6] = tuple(0 if s in slots else m for s, m in enumerate(before[6]))
-    check_pool("pack prefill", pool, tuple(start), ref, slots, lengths)
-    assert pool.full.tolist() == [0] * N_SLOTS
-
-
 @pytest.mark.parametrize("shape", CASES[:2], ids=IDS[:2])
 def test_a_fork_shares_pages_and_both_go_on_alone(shape):
     _, _, q, k, v, gate, w, mix = tokens(*shape)
-    pool = make_pool(*shape)
+    pool = make_pool("paged", shape)
     used = pool.pages_used
     src_before = pool.at([4]).compact()
     pool.fork(4, 2)
@@ -235,7 +86,7 @@ def test_step_dev_freezes_a_slot_without_a_page_until_it_is_reserved(shape):
     _, _, q, k, v, gate, w, mix = tokens(*shape)
     step = lambda st: mhla_amd.mhla_causal_step_dev(q[:, :1], k[:, :1], v[:, :1], mix, st, gate=gate[:, :1], norm_weight=w)
     # slot 3 is at position 64: chunk 0 finished on page 6, no page for chunk 1
-    pool = make_pool(*shape, lengths=(64, 5, 129))   # (the pack of `tokens` holds 198 tokens)
+    pool = make_pool("paged", shape, lengths=(64, 5, 129))   # (the pack of `tokens` holds 198 tokens)
     dev_view = pool.at(torch.tensor(VIEW, dtype=torch.int32, device=DEV))
     ref, before = pool.at(VIEW).compact(), snapshot(pool)
     ref.pos[0] = -1   # (the reference freezes that row with the position the step knows)
@@ -244,7 +95,7 @@ def test_step_dev_freezes_a_slot_without_a_page_until_it_is_reserved(shape):
     same_bits("rows", got, want)
     assert float(got[0].float().abs().max()) == 0.0 and pool.stale
     check_pool("step_dev without a page", pool, before, ref, VIEW, (64, 6, 130), touched=[0, 4], flagged=[3])
-    assert pool.full.tolist() == [0, 0, 0, 1, 0] and pool.table == before[5], "step_dev assigns no page"
+    assert pool.full.tolist() == [0, 0, 0, 1, 0] and pool.table == before.table, "step_dev assigns no page"
     with pytest.raises(IndexError, match="no page"):
         pool.sync()
     # reserved, the flag cleared: the same call is the live step

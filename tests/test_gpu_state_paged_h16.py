@@ -1,12 +1,12 @@
 """Decode calls on a paged state pool of h16 pages (`PagedCausalState.empty(..., page_format="h16")`, the library's
 mhla_causal_*_paged_h16 entry points), held to the format's contract: a page is the ENCODING of the fp32 pool's page, bit for bit
-(integer views against the torch codec of tests/test_state_paged_h16_cpu.py); P is the ascending fmaf sum over DECODED pages, the
-chunk a boundary just committed included (the derived bound of an n-term fp32 fmaf chain, which a sum that adds the un-rounded chunk
-misses by orders of magnitude); a prefilled slot holds the bits of a stepped one; rows stay within the bound the 11-bit forward is
-held to, per chunk, against the fp64 operator on every request alone; and nothing a call does not name changes a bit -- payload,
-multipliers, slots, flags.  Shapes, tokens, VIEW = [3, 0, 4], LENGTHS = (63, 5, 130), the NaN poison and the scrambled table are
-those of test_gpu_state_slots.py and test_gpu_state_paged.py; what the rows' inputs may cost on their own is capped on the CPU
-(test_state_paged_h16_cpu.py: test_input_check_h16_pages_alone_stay_within_the_row_bound)."""
+(integer views against the torch codec of tests/pool_util.py, which tests/test_state_paged_h16_cpu.py checks); P is the ascending fmaf
+sum over DECODED pages, the chunk a boundary just committed included (the derived bound of an n-term fp32 fmaf chain, which a sum that
+adds the un-rounded chunk misses by orders of magnitude); a prefilled slot holds the bits of a stepped one; rows stay within the bound
+the 11-bit forward is held to, per chunk, against the fp64 operator on every request alone; and nothing a call does not name changes
+a bit -- payload, multipliers, slots, flags (`pool_util.check_untouched`).  Shapes, tokens, VIEW = [3, 0, 4], LENGTHS = (63, 5, 130),
+the NaN poison and the scrambled table are the pool family's (`pool_util.make_pool("paged" / "h16", ...)`); what the rows' inputs may
+cost on their own is capped on the CPU (test_state_paged_h16_cpu.py: test_input_check_h16_pages_alone_stay_within_the_row_bound)."""
 import functools
 
 import pytest
@@ -16,33 +16,13 @@ import mhla_amd
 from mhla_amd import PagedCausalState
 from gpu_util import CAUSAL_TOL, DEV, check, check_chunks
 from decode_util import ragged_inputs, signed_features
-from test_gpu_state_slots import CAP, CASES, IDS, L, LENGTHS, N_SLOTS, VIEW, same_bits, tokens
-from test_gpu_state_paged import N_PAGES, TABLE, make_pool
-from test_state_paged_h16_cpu import GROUP, ROW_EXTRA, cpu_tokens, decode, encode, gate_norm, rows_fp64, sequence
-import test_state_paged_h16_cpu as cpu
+from pool_util import (CAP, CASES, GROUP, IDS, L, LENGTHS, N_PAGES, N_SLOTS, NAN, ROW_EXTRA, TABLE, VIEW, check_untouched, decode, encode,
+                       gate_norm, make_pool, rows_fp64, same_bits, sequence, snapshot, tokens)
 
 pytestmark = pytest.mark.gpu
 
-assert (cpu.CASES, cpu.LENGTHS_GPU, cpu.L, cpu.T_STEPS) == (CASES, LENGTHS, L, 70), "the CPU input check uses these tests' cases"
-NAN = float("nan")
 # rows: the bound the 11-bit forward is held to (u + 1e-3: gpu_util.CAUSAL_TOL); fp32 tensors: the same rule, no final rounding
 ROW_TOL = {torch.float32: ROW_EXTRA, torch.bfloat16: CAUSAL_TOL[torch.bfloat16], torch.float16: CAUSAL_TOL[torch.float16]}
-
-
-def make_h16(shape, **kw):
-    """(the fp32 paged pool of test_gpu_state_paged.make_pool, an h16 pool of the same tokens and the same scrambled table): payload
-    and multipliers are the torch encoding of the fp32 pages, NaN in every page no slot names; P, Cur, pos are copies."""
-    src = make_pool(*shape, **kw)
-    pay, mult = encode(src.pages)
-    named = {p for r in src.table for p in r if p >= 0}
-    for p in range(N_PAGES):
-        if p not in named:
-            mult[p] = NAN
-    pool = PagedCausalState(pay, src.P.clone(), src.Cur.clone(), [list(r) for r in src.table], lengths=src.lengths, page_mult=mult)
-    pool.pos.copy_(src.pos)
-    pool.full
-    assert pool.page_format == "h16" and pool.pages_used == src.pages_used
-    return src, pool
 
 
 def empty_h16(H, K, V, n_slots=N_SLOTS, cap=CAP, n_pages=N_PAGES):
@@ -77,34 +57,6 @@ def p_is_the_sum_over_decoded_pages(name, pool, slot, mix, n):
     assert not bool(over.any()), f"{name}: P of slot {slot} is not the sum over its {n} decoded pages: {int(over.sum())} elements beyond the bound, worst {worst:.2e}"
 
 
-def snapshot(pool):
-    return tuple(t.clone() for t in (pool.pages, pool.page_mult, pool.P, pool.Cur, pool.pos, pool.full)) + ([list(r) for r in pool.table], pool.lengths)
-
-
-def check_isolation(name, pool, before, touched, reach, flagged=()):
-    """Every slot outside `touched` keeps every bit of P, Cur, pos and full and its table row; a page -- payload and multipliers
-    alike -- keeps every bit unless it holds a chunk a touched slot may write: from the chunk that was open `before` to the last one
-    its `reach` tokens touch (the `writable` rule of test_gpu_state_paged.check_pool).  `flagged`: slots whose `full` flag the call may
-    set.  The device table is the host's."""
-    torch.cuda.synchronize()
-    assert pool.table_dev.tolist() == pool.table, f"{name}: the device table is not the host mirror"
-    writable = set()
-    for s, n in zip(touched, reach):
-        writable.update(pool.table[s][j] for j in range(before[7][s] // 64, -(-n // 64)))
-    assert all(0 <= p < N_PAGES for p in writable), f"{name}: a chunk the call reaches has no page"
-    for s in range(N_SLOTS):
-        if s not in touched:
-            for part, now, was in zip(("P", "Cur", "pos", "full"), (pool.P, pool.Cur, pool.pos, pool.full), before[2:6]):
-                if part == "full" and s in flagged:
-                    continue
-                same_bits(f"{name}: {part} of slot {s}, which the call does not name", now[s], was[s])
-            assert pool.table[s] == before[6][s], f"{name}: the table row of slot {s}, which the call does not name"
-    for p in range(N_PAGES):
-        if p not in writable:
-            same_bits(f"{name}: payload of page {p}, which the call must not write", pool.pages[p], before[0][p])
-            same_bits(f"{name}: multipliers of page {p}, which the call must not write", pool.page_mult[p], before[1][p])
-
-
 def check_rows(name, got, want, m, dtype):
     """decode_util.check_step_rows at ROW_TOL: rows m .. of one request within the bound of its maximum, and chunk by chunk of its own chunks."""
     tol, ref = ROW_TOL[dtype], want[:, m:]
@@ -120,7 +72,7 @@ def check_rows(name, got, want, m, dtype):
 @pytest.mark.parametrize("shape", CASES, ids=IDS)
 def test_a_boundary_step_writes_the_encoded_page_and_mixes_decoded_pages(shape):
     _, _, q, k, v, _, _, mix = tokens(*shape)
-    src, pool = make_h16(shape)
+    src, pool = make_pool("paged", shape), make_pool("h16", shape)
     step = lambda view: mhla_amd.mhla_causal_step(q[:, :1], k[:, :1], v[:, :1], mix, view)
     step(src.at(VIEW))
     step(pool.at(VIEW))   # slot 3 crosses the boundary at 63 -> 64: chunk 0 goes to page 6
@@ -143,7 +95,7 @@ def test_a_pack_prefill_writes_the_encoded_pages(shape, lengths):
     n, slots = sum(lengths), [4, 1]
     cu = [0, lengths[0], n]
     kk, vv = hk[:, 10:10 + n], hv[:, 10:10 + n]
-    src, pool = make_h16(shape)
+    src, pool = make_pool("paged", shape), make_pool("h16", shape)
     before = snapshot(pool)
     mhla_amd.mhla_causal_state(kk, vv, mix, cu_seqlens=cu, into=src.at(slots))
     view = pool.at(slots)
@@ -159,9 +111,9 @@ def test_a_pack_prefill_writes_the_encoded_pages(shape, lengths):
             p_is_the_sum_over_decoded_pages("prefill", pool, s, mix, m // 64)
         else:
             assert float(pool.P[s].abs().max()) == 0.0
-    start = list(before)
-    start[7] = tuple(0 if s in slots else m for s, m in enumerate(before[7]))
-    check_isolation("pack prefill", pool, tuple(start), slots, lengths)
+    # (a prefill starts the slot anew: every chunk up to its length may be written)
+    start = before._replace(lengths=tuple(0 if s in slots else m for s, m in enumerate(before.lengths)))
+    check_untouched("pack prefill", pool, start, slots, lengths)
     assert pool.full.tolist() == [0] * N_SLOTS
 
 
@@ -213,8 +165,6 @@ def test_a_prefilled_slot_holds_the_bits_of_a_stepped_one(shape):
 @functools.lru_cache(maxsize=None)
 def row_reference(shape):
     """Per request (the exact fp64 rows [1, m + 70, H, V], the same through the gate x norm epilogue), once per shape."""
-    for a, b in zip(cpu_tokens(*shape), tokens(*shape)):
-        assert torch.equal(a, b.cpu()), "the CPU input check does not use these inputs"
     out = []
     for b in range(3):
         q, k, v, gate, w, mix, m = sequence(shape, b)
@@ -252,7 +202,7 @@ def test_seventy_steps_on_h16_pages_against_the_fp64_operator(shape, epilogue):
 @pytest.mark.parametrize("shape", CASES, ids=IDS)
 def test_a_step_changes_nothing_it_does_not_name(shape, call):
     _, _, q, k, v, gate, w, mix = tokens(*shape)
-    _, pool = make_h16(shape)
+    pool = make_pool("h16", shape)
     before = snapshot(pool)
     if call == "step":
         mhla_amd.mhla_causal_step(q[:, :1], k[:, :1], v[:, :1], mix, pool.at(VIEW), gate=gate[:, :1], norm_weight=w)
@@ -260,10 +210,11 @@ def test_a_step_changes_nothing_it_does_not_name(shape, call):
         mhla_amd.mhla_causal_step_dev(q[:, :1], k[:, :1], v[:, :1], mix, pool.at(torch.tensor(VIEW, dtype=torch.int32, device=DEV)),
                                       gate=gate[:, :1], norm_weight=w)
         assert pool.stale
-        pool.sync()
     after = tuple(m + 1 for m in LENGTHS)
-    assert tuple(pool.lengths[s] for s in VIEW) == after and pool.table == before[6]
-    check_isolation(call, pool, before, VIEW, after)
+    # (ahead of the sync, which reads pos back into the host lengths of EVERY slot, the unnamed ones' poison too)
+    check_untouched(call, pool, before, VIEW, after)
+    pool.sync()
+    assert tuple(pool.lengths[s] for s in VIEW) == after and pool.table == before.table
     assert pool.full.tolist() == [0] * N_SLOTS
 
 
@@ -273,7 +224,7 @@ def test_step_dev_freezes_a_slot_without_a_page_until_it_is_reserved(shape):
     _, _, q, k, v, gate, w, mix = tokens(*shape)
     step = lambda st: mhla_amd.mhla_causal_step_dev(q[:, :1], k[:, :1], v[:, :1], mix, st, gate=gate[:, :1], norm_weight=w)
     # slot 3 is at position 64: chunk 0 finished on page 6, no page for chunk 1
-    _, pool = make_h16(shape, lengths=(64, 5, 129))
+    pool = make_pool("h16", shape, lengths=(64, 5, 129))
     dev_view = pool.at(torch.tensor(VIEW, dtype=torch.int32, device=DEV))
     # (off a boundary a step reads P and Cur alone: its rows are, bit for bit, those of the step on the decoded compact state)
     ref, before = pool.at(VIEW).compact(), snapshot(pool)
@@ -282,8 +233,8 @@ def test_step_dev_freezes_a_slot_without_a_page_until_it_is_reserved(shape):
     got = step(dev_view)
     same_bits("rows", got, want)
     assert float(got[0].float().abs().max()) == 0.0 and pool.stale
-    check_isolation("step_dev without a page", pool, before, [0, 4], (6, 130), flagged=[3])
-    assert pool.full.tolist() == [0, 0, 0, 1, 0] and pool.table == before[6], "step_dev assigns no page"
+    check_untouched("step_dev without a page", pool, before, [0, 4], (6, 130), flagged=[3])
+    assert pool.full.tolist() == [0, 0, 0, 1, 0] and pool.table == before.table, "step_dev assigns no page"
     assert pool.pos.tolist()[0] == 6 and pool.pos.tolist()[3:] == [64, 130]
     with pytest.raises(IndexError, match="no page"):
         pool.sync()
@@ -296,7 +247,7 @@ def test_step_dev_freezes_a_slot_without_a_page_until_it_is_reserved(shape):
     same_bits("rows", got, want)
     assert float(got[0].float().abs().max()) > 0.0
     pool.sync()
-    check_isolation("step_dev after reserve", pool, before, VIEW, (65, 7, 131))
+    check_untouched("step_dev after reserve", pool, before, VIEW, (65, 7, 131))
     assert tuple(pool.lengths[s] for s in VIEW) == (65, 7, 131) and pool.full.tolist() == [0] * N_SLOTS
 
 
@@ -417,7 +368,7 @@ def test_ten_chunks_deep_the_unrolled_walk_reads_decoded_pages_through_the_table
 @pytest.mark.parametrize("shape", CASES[:2], ids=IDS[:2])
 def test_a_fork_shares_pages_and_both_hold_equal_bits_until_their_tokens_differ(shape):
     _, _, q, k, v, gate, w, mix = tokens(*shape)
-    _, pool = make_h16(shape)
+    pool = make_pool("h16", shape)
     used, pages, mult = pool.pages_used, pool.pages.clone(), pool.page_mult.clone()
     pool.fork(4, 2)
     assert pool.table[2] == [7, 5, -1, -1] and pool.refs[7] == pool.refs[5] == 2 and pool.refs[2] == 1, "the two finished chunks, by reference"

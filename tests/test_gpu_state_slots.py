@@ -1,11 +1,15 @@
-"""Decode calls on chosen slots of a state pool (`CausalState.at`, the library's mhla_causal_*_slots entry points): every call on
-the non-monotonic view [3, 0, 4] of a NaN-poisoned pool of 5 slots against the existing un-slotted call on `view.compact()`, BIT
-FOR BIT (integer views, so the poison compares): the rows, the finished chunks of S, P, Cur and pos of the three slots, and every
-bit of the slots the call does not name.  The pool is filled from an un-slotted pack prefill by plain tensor copies, so that no
-setup depends on what is tested.  One captured graph of a device-positioned step on a device map, rewritten in place while the
-graph is replayed, is held to the fp64 oracle of every request alone (the K split depends on B H: no bit equality with a batch
-of one there)."""
-import functools
+"""Decode calls on chosen slots of a state pool, DENSE (`CausalState.at`, the library's mhla_causal_*_slots entry points) and PAGED
+(`PagedCausalState`, mhla_causal_*_paged: 10 pages through a scrambled table): every call on the non-monotonic view [3, 0, 4] of a
+NaN-poisoned pool of 5 slots against the existing un-slotted, un-paged call on `view.compact()`, BIT FOR BIT (integer views, so the
+poison compares): the rows, the finished chunks (of S, or read back through the page table), P, Cur and pos of the three slots, every
+bit of the slots the call does not name, and every bit of every page the call must not write -- the free ones, other slots', and the
+view's own finished chunks.  The pools, their inputs and the checks are tests/pool_util.py's (`make_pool`, `tokens`, `check_pool`):
+filled from an un-slotted pack prefill by plain tensor copies, so that no setup depends on what is tested.  The view contract is
+written once for both kinds, what a paged pool adds to it (its page accounting) under `kind == "paged"`; the dense pool's own tests
+follow, the paged pool's own are in test_gpu_state_paged.py.  One captured graph of a device-positioned step on a device map,
+rewritten in place while the graph is replayed, is held to the fp64 oracle of every request alone (the K split depends on B H: no
+bit equality with a batch of one there)."""
+import itertools
 
 import pytest
 import torch
@@ -13,104 +17,29 @@ import torch
 import mhla_amd
 from mhla_amd import CausalState
 from gpu_util import DEV
-from decode_util import check_state, check_step_rows, ragged_inputs, signed_features
+from decode_util import check_state, check_step_rows, ragged_inputs
+from pool_util import (ACCEPT, CAP, CASES, COUNTS, IDS, L, LENGTHS, N_SLOTS, VIEW, check_pool, make_pool, same_bits, snapshot, tokens,
+                       windows)
 
 pytestmark = pytest.mark.gpu
 
-N_SLOTS, CAP, L = 5, 4, 4
-VIEW = [3, 0, 4]                  # call row -> slot: not monotonic
-LENGTHS = (63, 5, 130)            # on a chunk boundary, inside chunk 0, in chunk 2
-COUNTS, ACCEPT, T = (1, 70, 0), (1, 33, 0), 70
-POISON = 0x7FC00000               # pos of a slot nobody prefilled: a NaN's bits, outside every capacity
-
-# (dtype, H, Hkv, K, V)
-CASES = [(torch.float32, 2, 2, 64, 64), (torch.bfloat16, 2, 2, 64, 64), (torch.float32, 4, 2, 64, 64), (torch.bfloat16, 4, 2, 64, 64),
-         (torch.float32, 2, 2, 40, 72)]
-IDS = ["fp32", "bf16", "fp32-G2", "bf16-G2", "fp32-K40V72"]
+SHAPES = (CASES, IDS)
 
 
-def bits(t):
-    return t.view({4: torch.int32, 2: torch.int16}[t.element_size()]) if t.is_floating_point() else t
+def both_kinds(names, *axes):
+    """Parametrise a test over `names` and `kind`: the product of the axes [(values, ids), ...] on a dense pool, under the ids these cases
+    have always had, and on a paged pool, under the same ids with `-paged`."""
+    combos = list(itertools.product(*(list(zip(*axis)) for axis in axes)))
+    return pytest.mark.parametrize(names + ", kind", [pytest.param(*(v for v, _ in c), kind, id="-".join(i for _, i in c) + tail)
+                                                      for kind, tail in (("dense", ""), ("paged", "-paged")) for c in combos])
 
 
-def same_bits(name, a, b):
-    assert a.shape == b.shape and torch.equal(bits(a), bits(b)), f"{name}: bits differ"
-
-
-@functools.lru_cache(maxsize=None)
-def tokens(dtype, H, Hkv, K, V, B=3):
-    """One set per shape, shared by the cases and never written: the pack that fills the pool, T padded tokens per call row (NaN
-    outside the windows of COUNTS is put in by the cases that have windows), gate, norm weight, mix."""
-    g = torch.Generator().manual_seed(4321)
-    n = sum(LENGTHS)
-    hk, hv = signed_features(g, 1, n, Hkv, K).to(dtype), torch.randn(1, n, Hkv, V, generator=g).to(dtype)
-    q, k = signed_features(g, B, T, H, K).to(dtype), signed_features(g, B, T, Hkv, K).to(dtype)
-    v, gate = torch.randn(B, T, Hkv, V, generator=g).to(dtype), torch.randn(B, T, H, V, generator=g).to(dtype)
-    w = torch.rand(V, generator=g) + 0.5
-    mix = torch.tril(torch.rand(L, L, generator=g).clamp(1e-5, 1))
-    return tuple(t.to(DEV) for t in (hk, hv, q, k, v, gate, w, mix))
-
-
-def make_pool(dtype, H, Hkv, K, V, slots=VIEW, lengths=LENGTHS):
-    """A pool whose every byte is poison but for the slots `slots`, which hold what the existing pack prefill gives for `lengths`."""
-    hk, hv, *_, mix = tokens(dtype, H, Hkv, K, V)
-    cu = [0]
-    for n in lengths:
-        cu.append(cu[-1] + n)
-    src = mhla_amd.mhla_causal_state(hk[:, :cu[-1]], hv[:, :cu[-1]], mix, cu_seqlens=cu, capacity_chunks=CAP)
-    e = CausalState.empty(N_SLOTS, Hkv, K, V, CAP, DEV)
-    for t in (e.S, e.P, e.Cur):
-        t.fill_(float("nan"))
-    host = [0] * N_SLOTS
-    for s, n in zip(slots, lengths):
-        host[s] = n
-    pool = CausalState(e.S, e.P, e.Cur, 0, 64, lengths=host)
-    pool.pos.fill_(POISON)
-    for b, (s, n) in enumerate(zip(slots, lengths)):
-        pool.S[s, :, :n // 64] = src.S[b, :, :n // 64]
-        pool.P[s], pool.Cur[s], pool.pos[s] = src.P[b], src.Cur[b], n
-    pool.full   # (zeros: a flag is a finding)
-    return pool
-
-
-def snapshot(pool):
-    return tuple(t.clone() for t in (pool.S, pool.P, pool.Cur, pool.pos, pool.full))
-
-
-def check_pool(name, pool, before, ref, slots, lengths_after, touched=None, flagged=()):
-    """Slots `slots` of the pool hold the bits of the compact state `ref` (finished chunks of S, P, Cur, pos); every other slot, and
-    of `slots` those not in `touched`, hold every bit they held `before` (`flagged`: but for their `full` flag)."""
-    torch.cuda.synchronize()
-    touched = list(slots) if touched is None else touched
-    for b, s in enumerate(slots):
-        n = lengths_after[b]
-        if s in touched:
-            same_bits(f"{name}: S of slot {s}", pool.S[s, :, :n // 64], ref.S[b, :, :n // 64])
-            same_bits(f"{name}: P of slot {s}", pool.P[s], ref.P[b])
-            same_bits(f"{name}: Cur of slot {s}", pool.Cur[s], ref.Cur[b])
-            assert int(pool.pos[s]) == int(ref.pos[b]) == n, f"{name}: pos of slot {s} is {int(pool.pos[s])}, the compact state's {int(ref.pos[b])}, expected {n}"
-    for s in range(N_SLOTS):
-        if s not in touched:
-            for part, now, was in zip(("S", "P", "Cur", "pos", "full"), (pool.S, pool.P, pool.Cur, pool.pos, pool.full), before):
-                if part != "full" or s not in flagged:
-                    same_bits(f"{name}: {part} of slot {s}, which the call does not name or leaves alone", now[s], was[s])
-
-
-def windows(x, counts, left):
-    """x [B, T, ...] with NaN outside every row's window of counts[b] tokens."""
-    out = torch.full_like(x, float("nan"))
-    for b, n in enumerate(counts):
-        t0 = x.shape[1] - n if left else 0
-        out[b, t0:t0 + n] = x[b, t0:t0 + n]
-    return out
-
-
-@pytest.mark.parametrize("epilogue", [False, True], ids=["plain", "gate-norm"])
-@pytest.mark.parametrize("shape", CASES, ids=IDS)
-def test_step_on_a_view_is_the_step_on_the_compact_state(shape, epilogue):
+# ---- the view contract, on a dense and on a paged pool
+@both_kinds("shape, epilogue", SHAPES, ([False, True], ["plain", "gate-norm"]))
+def test_step_on_a_view_is_the_step_on_the_compact_state(shape, epilogue, kind):
     _, _, q, k, v, gate, w, mix = tokens(*shape)
     kw = dict(gate=gate[:, :1], norm_weight=w) if epilogue else {}
-    pool = make_pool(*shape)
+    pool = make_pool(kind, shape)
     view = pool.at(VIEW)
     assert view.lengths == LENGTHS
     ref, before = view.compact(), snapshot(pool)
@@ -119,15 +48,86 @@ def test_step_on_a_view_is_the_step_on_the_compact_state(shape, epilogue):
     same_bits("rows", got, want)
     after = tuple(n + 1 for n in LENGTHS)
     assert view.lengths == ref.lengths == after and tuple(pool.lengths[s] for s in VIEW) == after and pool.lengths[1] == pool.lengths[2] == 0
+    if kind == "paged":
+        assert pool.table == before.table, "every chunk the step touches had its page"
     check_pool("step", pool, before, ref, VIEW, after)
 
 
+@both_kinds("shape, left", SHAPES, ([False, True], ["right-padded", "left-padded"]))
+def test_extend_with_counts_on_a_view(shape, left, kind):
+    _, _, q, k, v, gate, w, mix = tokens(*shape)
+    q, k, v, gate = (windows(t, COUNTS, left) for t in (q, k, v, gate))
+    pool = make_pool(kind, shape)
+    view = pool.at(VIEW)
+    ref, before = view.compact(), snapshot(pool)
+    call = lambda st: mhla_amd.mhla_causal_extend(q, k, v, mix, st, counts=COUNTS, left_padded=left, gate=gate, norm_weight=w)
+    want = call(ref)
+    got = call(view)
+    same_bits("rows", got, want)
+    after = tuple(p + n for p, n in zip(LENGTHS, COUNTS))
+    assert view.lengths == ref.lengths == after
+    if kind == "paged":
+        assert pool.table[0][:2] == [4, 0] and pool.pages_used == 6, "slot 0 grew into chunk 1: the lowest free page"
+    check_pool("extend", pool, before, ref, VIEW, after)
+
+
+@both_kinds("shape", SHAPES)
+def test_verify_then_commit_on_a_view(shape, kind):
+    _, _, q, k, v, gate, w, mix = tokens(*shape)
+    q, k, v, gate = (windows(t, COUNTS, False) for t in (q, k, v, gate))
+    pool = make_pool(kind, shape)
+    view = pool.at(VIEW)
+    ref, before = view.compact(), snapshot(pool)
+    want, draft_ref = mhla_amd.mhla_causal_verify(q, k, v, mix, ref, counts=COUNTS, gate=gate, norm_weight=w)
+    got, draft = mhla_amd.mhla_causal_verify(q, k, v, mix, view, counts=COUNTS, gate=gate, norm_weight=w)
+    same_bits("rows", got, want)
+    assert draft.view is view and view.lengths == LENGTHS
+    ends = tuple(p + n for p, n in zip(LENGTHS, COUNTS))
+    # (only the finished chunks -- rows of S -- are specified after a verify: the header; on a paged pool the draft's pages are assigned,
+    # and `reach` names them; a dense pool has no pages and `reach` is not looked at)
+    if kind == "paged":
+        assert pool.pages_used == 6
+    check_pool("verify", pool, before, ref, VIEW, LENGTHS, reach=ends)
+    mhla_amd.mhla_causal_commit(draft_ref, mix, ref, ACCEPT)
+    assert mhla_amd.mhla_causal_commit(draft, mix, view, ACCEPT) is view
+    after = tuple(p + a for p, a in zip(LENGTHS, ACCEPT))
+    assert view.lengths == ref.lengths == after
+    check_pool("commit", pool, before, ref, VIEW, after, reach=ends)
+    if kind == "paged":
+        # slot 0 was verified to 75 tokens and accepted 38: the page of chunk 1 goes back
+        page = pool.table[0][1]
+        pool.trim(VIEW)
+        assert pool.table[0] == [4, -1, -1, -1] and pool.pages_used == 5 and page in pool.free and pool.table_dev.tolist() == pool.table
+
+
+@both_kinds("shape, lengths", SHAPES, ([(130, 0), (64, 70)], ["130+0", "64+70"]))
+def test_pack_prefill_into_slots(shape, lengths, kind):
+    hk, hv, *_, mix = tokens(*shape)
+    n, slots = sum(lengths), [4, 1]
+    cu = [0, lengths[0], n]
+    # (the pack: other tokens than those slot 4 was filled from)
+    k, v = hk[:, 10:10 + n], hv[:, 10:10 + n]
+    pool = make_pool(kind, shape)
+    before = snapshot(pool)
+    ref = mhla_amd.mhla_causal_state(k, v, mix, cu_seqlens=cu, capacity_chunks=CAP)
+    view = pool.at(slots)
+    assert mhla_amd.mhla_causal_state(k, v, mix, cu_seqlens=cu, into=view) is view
+    assert view.lengths == ref.lengths == lengths and pool.lengths == (5, lengths[1], 0, 63, lengths[0])
+    if kind == "paged":
+        assert pool.pages_used == 2 + sum(-(-m // 64) for m in lengths), "slot 4 starts anew: its three pages went back first"
+    # (a prefill starts the slot anew: every chunk up to its length may be written)
+    start = before._replace(lengths=tuple(0 if s in slots else m for s, m in enumerate(before.lengths)))
+    check_pool("pack prefill", pool, start, ref, slots, lengths)
+    assert pool.full.tolist() == [0] * N_SLOTS
+
+
+# ---- the dense pool's own
 @pytest.mark.parametrize("shape", CASES, ids=IDS)
 def test_step_dev_with_an_inactive_row_and_a_slot_at_capacity(shape):
     _, _, q, k, v, gate, w, mix = tokens(*shape)
     step = lambda st: mhla_amd.mhla_causal_step_dev(q[:, :1], k[:, :1], v[:, :1], mix, st, gate=gate[:, :1], norm_weight=w)
     # ---- map [3, -1, 4]: row 1 is zeros and touches no slot; the reference freezes that row with the position the step knows
-    pool = make_pool(*shape)
+    pool = make_pool("dense", shape)
     ref, before = pool.at(VIEW).compact(), snapshot(pool)
     ref.pos[1] = -1
     want = step(ref)
@@ -138,7 +138,7 @@ def test_step_dev_with_an_inactive_row_and_a_slot_at_capacity(shape):
     check_pool("step_dev", pool, before, ref, VIEW, (64, 5, 131), touched=[3, 4])
     assert pool.full.tolist() == [0] * N_SLOTS, "no flag: slot 0 was not named, the named slots are live"
     # ---- slot 3 at the capacity: full[3] = 1, the row zeros, the slot untouched
-    pool = make_pool(*shape)
+    pool = make_pool("dense", shape)
     pool.pos[3] = 64 * CAP
     ref, before = pool.at(VIEW).compact(), snapshot(pool)
     want = step(ref)
@@ -149,65 +149,10 @@ def test_step_dev_with_an_inactive_row_and_a_slot_at_capacity(shape):
     assert pool.full.tolist() == [0, 0, 0, 1, 0] and ref.full.tolist() == [1, 0, 0]
 
 
-@pytest.mark.parametrize("left", [False, True], ids=["right-padded", "left-padded"])
-@pytest.mark.parametrize("shape", CASES, ids=IDS)
-def test_extend_with_counts_on_a_view(shape, left):
-    _, _, q, k, v, gate, w, mix = tokens(*shape)
-    q, k, v, gate = (windows(t, COUNTS, left) for t in (q, k, v, gate))
-    pool = make_pool(*shape)
-    view = pool.at(VIEW)
-    ref, before = view.compact(), snapshot(pool)
-    call = lambda st: mhla_amd.mhla_causal_extend(q, k, v, mix, st, counts=COUNTS, left_padded=left, gate=gate, norm_weight=w)
-    want = call(ref)
-    got = call(view)
-    same_bits("rows", got, want)
-    after = tuple(p + n for p, n in zip(LENGTHS, COUNTS))
-    assert view.lengths == ref.lengths == after
-    check_pool("extend", pool, before, ref, VIEW, after)
-
-
-@pytest.mark.parametrize("shape", CASES, ids=IDS)
-def test_verify_then_commit_on_a_view(shape):
-    _, _, q, k, v, gate, w, mix = tokens(*shape)
-    q, k, v, gate = (windows(t, COUNTS, False) for t in (q, k, v, gate))
-    pool = make_pool(*shape)
-    view = pool.at(VIEW)
-    ref, before = view.compact(), snapshot(pool)
-    want, draft_ref = mhla_amd.mhla_causal_verify(q, k, v, mix, ref, counts=COUNTS, gate=gate, norm_weight=w)
-    got, draft = mhla_amd.mhla_causal_verify(q, k, v, mix, view, counts=COUNTS, gate=gate, norm_weight=w)
-    same_bits("rows", got, want)
-    assert draft.view is view and view.lengths == LENGTHS
-    # (only the finished rows of S are specified after a verify: the header)
-    check_pool("verify", pool, before, ref, VIEW, LENGTHS)
-    mhla_amd.mhla_causal_commit(draft_ref, mix, ref, ACCEPT)
-    assert mhla_amd.mhla_causal_commit(draft, mix, view, ACCEPT) is view
-    after = tuple(p + a for p, a in zip(LENGTHS, ACCEPT))
-    assert view.lengths == ref.lengths == after
-    check_pool("commit", pool, before, ref, VIEW, after)
-
-
-@pytest.mark.parametrize("lengths", [(130, 0), (64, 70)], ids=["130+0", "64+70"])
-@pytest.mark.parametrize("shape", CASES, ids=IDS)
-def test_pack_prefill_into_slots(shape, lengths):
-    hk, hv, *_, mix = tokens(*shape)
-    n, slots = sum(lengths), [4, 1]
-    cu = [0, lengths[0], n]
-    # (the pack: other tokens than those slot 4 was filled from)
-    k, v = hk[:, 10:10 + n], hv[:, 10:10 + n]
-    pool = make_pool(*shape)
-    before = snapshot(pool)
-    ref = mhla_amd.mhla_causal_state(k, v, mix, cu_seqlens=cu, capacity_chunks=CAP)
-    view = pool.at(slots)
-    assert mhla_amd.mhla_causal_state(k, v, mix, cu_seqlens=cu, into=view) is view
-    assert view.lengths == ref.lengths == lengths and pool.lengths == (5, lengths[1], 0, 63, lengths[0])
-    check_pool("pack prefill", pool, before, ref, slots, lengths)
-    assert pool.full.tolist() == [0] * N_SLOTS
-
-
 @pytest.mark.parametrize("shape", CASES[:2], ids=IDS[:2])
 def test_a_forked_slot_steps_like_its_source(shape):
     _, _, q, k, v, _, _, mix = tokens(*shape)
-    pool = make_pool(*shape)
+    pool = make_pool("dense", shape)
     pool.fork(3, 2)
     assert pool.lengths[2] == 63 and int(pool.pos[2]) == 63
     a = mhla_amd.mhla_causal_step(q[:1, :1], k[:1, :1], v[:1, :1], mix, pool.at([3]))

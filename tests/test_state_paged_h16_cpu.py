@@ -1,15 +1,15 @@
 """h16 pages of a paged state pool (`PagedCausalState.empty(..., page_format="h16")`), host side, no GPU.
-  * The REFERENCE CODEC: a torch restatement of the one encode / decode of causal_step.hpp (the exponent field through an int32 view,
-    as h16_mult_from_max reads it; the rounding is `.half()`), which tests/test_gpu_state_paged_h16.py holds the kernels to bit for bit.
+  * The REFERENCE CODEC (tests/pool_util.py: `encode`, `decode`): a torch restatement of the one encode / decode of causal_step.hpp
+    (the exponent field through an int32 view, as h16_mult_from_max reads it; the rounding is `.half()`), which
+    tests/test_gpu_state_paged_h16.py holds the kernels to bit for bit.
   * The host layer on tools/fake_decode_lib.py: what is allocated, that the page rule / fork / trim / reset give the tables of the
     fp32 pool for the same calls, that compact() decodes, the three refusals, K V % 64, and the `_h16` entry points with the
-    arguments the header names.
-  * The INPUT CHECK of the GPU row-parity test: with that test's very inputs (`cpu_tokens` restates test_gpu_state_slots.tokens
-    without the copy to the device; the GPU test asserts they are equal), decoding is emulated in fp64 with every finished chunk
+    arguments the header names.  The pool (`pool_util.host_pool`) is the one tests/test_state_swap_cpu.py uses.
+  * The INPUT CHECK of the GPU row-parity test: with that test's very inputs (`pool_util.tokens(..., device="cpu")`: the one generator,
+    without the copy to the device), decoding is emulated in fp64 with every finished chunk
     replaced by decode(encode(fp32(S_j))) and held to the exact fp64 operator chunk by chunk, at the part of the row bound that is
     left after the final rounding of a row (1e-3 of the chunk's maximum): what the page format itself costs, with nothing of the
     kernels in it.  Observed: profiles/causal_state_h16.md."""
-import functools
 import os
 import re
 import sys
@@ -19,36 +19,17 @@ import torch
 
 import mhla_amd
 from mhla_amd import CausalState, PagedCausalState, PagedStateView, PoolExhausted, _lib, ops
+from pool_util import (CAP, CASES, GROUP, HOST_DIMS, HOST_LENGTHS, HOST_ROWS, IDS, N_SLOTS, ROW_EXTRA, decode, encode, gate_norm, host_pool,
+                       host_state, rows_fp64, sequence)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from fake_decode_lib import Session  # noqa: E402
 
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # the reference codec
 # ---------------------------------------------------------------------------------------------------------------------------
-GROUP = 64
-
-
-def encode(x):
-    """x [..., K, V] fp32 -> (payload [..., K, V] fp16, multipliers [..., K V / 64] fp32): group g of a chunk is elements
-    [64 g, 64 g + 64) of the flattened [K, V]; its multiplier is 2^(e - 14) for the exponent field e of the group's largest magnitude
-    (compared as bit patterns; the field of the multiplier clamped to 1 .. 240), its payload half(x * 2^-(e - 14))."""
-    assert x.dtype == torch.float32 and (x.shape[-1] * x.shape[-2]) % GROUP == 0
-    g = x.contiguous().reshape(*x.shape[:-2], -1, GROUP)
-    mx = (g.view(torch.int32) & 0x7FFFFFFF).amax(-1)
-    e = (mx >> 23) & 0xFF
-    f = torch.where(e < 15, torch.ones_like(e), torch.where(e > 254, torch.full_like(e, 240), e - 14))
-    mult = (f << 23).view(torch.float32)
-    inv = (0x7F000000 - (f << 23)).view(torch.float32)   # 1 / mult, exact
-    return (g * inv[..., None]).half().reshape(x.shape), mult
-
-
-def decode(pay, mult):
-    """payload x multiplier, exact in fp32."""
-    return (pay.float().reshape(*mult.shape, GROUP) * mult[..., None]).reshape(pay.shape)
-
-
 def test_the_codec_keeps_eleven_bits_of_each_groups_maximum():
     g = torch.Generator().manual_seed(11)
     x = torch.randn(3, 2, 40, 72, generator=g) * torch.exp2(torch.randint(-40, 40, (3, 2, 1, 1), generator=g).float())
@@ -77,29 +58,14 @@ def test_the_codec_keeps_eleven_bits_of_each_groups_maximum():
 # ---------------------------------------------------------------------------------------------------------------------------
 # the host layer
 # ---------------------------------------------------------------------------------------------------------------------------
-N_SLOTS, H, K, V, CAP, N_PAGES = 5, 2, 8, 16, 4, 9
+(H, K, V, N_PAGES), LENGTHS, ROWS = HOST_DIMS, HOST_LENGTHS, HOST_ROWS   # (5, 0, 0, 63, 130) through [[4, ..], [], [], [6, ..], [7, 5, 2, -1]]
 E = K * V
-LENGTHS = (5, 0, 0, 63, 130)
-ROWS = [[4, -1, -1, -1], [-1] * 4, [-1] * 4, [6, -1, -1, -1], [7, 5, 2, -1]]
 NAMES = ("mhla_causal_step_paged_h16", "mhla_causal_step_dev_paged_h16", "mhla_causal_varlen_state_init_paged_h16")
-
-
-def new_pool(fmt="h16", lengths=LENGTHS, rows=ROWS):
-    z = lambda *s: torch.zeros(s)
-    kw = {}
-    pages = z(N_PAGES, H, K, V)
-    if fmt == "h16":
-        pages, kw = pages.half(), dict(page_mult=z(N_PAGES, H, E // GROUP))
-    return PagedCausalState(pages, z(N_SLOTS, H, K, V), z(N_SLOTS, H, K, V), [list(r) for r in rows], lengths=lengths, **kw)
 
 
 def toks(B, T=1):
     g = torch.Generator().manual_seed(5)
     return torch.randn(B, T, H, K, generator=g), torch.randn(B, T, H, K, generator=g), torch.randn(B, T, H, V, generator=g), torch.rand(CAP, CAP, generator=g)
-
-
-def host_state(pool):
-    return [list(r) for r in pool.table], list(pool.refs), sorted(pool.free), pool.lengths, pool.pos.tolist(), pool.table_dev.tolist()
 
 
 @pytest.fixture
@@ -146,7 +112,7 @@ def test_a_chunk_that_is_no_whole_number_of_groups_is_refused(no_library):
 
 
 def test_compact_decodes_the_pages(no_library):
-    pool = new_pool()
+    pool = host_pool()
     g = torch.Generator().manual_seed(1)
     chunks = torch.randn(N_PAGES, H, K, V, generator=g) * torch.exp2(torch.arange(N_PAGES).float() - 4)[:, None, None, None]
     pay, mult = encode(chunks)
@@ -170,7 +136,7 @@ def _build():
 
 def test_the_refusals_come_before_any_page_is_assigned():
     _build()
-    pool = new_pool()
+    pool = host_pool()
     view = pool.at([3, 0, 4])
     q, k, v, mix = toks(3, 70)
     before = host_state(pool)
@@ -185,7 +151,7 @@ def test_the_refusals_come_before_any_page_is_assigned():
             s.call("commit", mhla_amd.mhla_causal_commit, draft, mix, view, (1, 2, 1), catch=False)
     assert s.calls == [] and host_state(pool) == before and not pool.stale, "nothing launched, no page assigned, nothing moved"
     # the same calls on the fp32 pool are what they were
-    fp32 = new_pool("fp32")
+    fp32 = host_pool("fp32")
     with Session(ops, _lib) as s:
         s.call("extend", mhla_amd.mhla_causal_extend, q, k, v, mix, fp32.at([3, 0, 4]), counts=(3, 2, 70), catch=False)
     assert [c.name for c in s.calls] == ["mhla_causal_extend_paged"]
@@ -194,7 +160,7 @@ def test_the_refusals_come_before_any_page_is_assigned():
 def test_the_page_rule_and_the_counts_do_not_depend_on_the_format():
     """The same calls on an fp32 and on an h16 pool: tables, reference counts, free lists, lengths and positions agree after each."""
     _build()
-    pools = {fmt: new_pool(fmt) for fmt in ("fp32", "h16")}
+    pools = {fmt: host_pool(fmt) for fmt in ("fp32", "h16")}
     q, k, v, mix = toks(3)
     _, pk, pv, _ = toks(1, 134)
     dev_map = torch.tensor([3, -1, 4], dtype=torch.int32)
@@ -240,7 +206,7 @@ def _pointers(call):
 def test_a_view_of_an_h16_pool_makes_the_h16_call(entry, monkeypatch):
     _build()
     monkeypatch.setattr(ops, "_MAX_GRID_BH", 2 * H)   # (two slices: the map is cut with the tokens, the pool passes whole)
-    pool = new_pool()
+    pool = host_pool()
     view = pool.at(torch.tensor([3, 0, 4], dtype=torch.int32) if entry == "step_dev" else [3, 0, 4])
     q, k, v, mix = toks(3)
     fn = mhla_amd.mhla_causal_step if entry == "step" else mhla_amd.mhla_causal_step_dev
@@ -264,7 +230,7 @@ def test_a_view_of_an_h16_pool_makes_the_h16_call(entry, monkeypatch):
 
 def test_a_pack_prefill_into_an_h16_view_is_one_h16_call_with_a_workspace(monkeypatch):
     _build()
-    pool = new_pool()
+    pool = host_pool()
     view = pool.at([4, 1])
     _, k, v, mix = toks(1, 134)
     lib = _lib.load()
@@ -330,67 +296,10 @@ def test_the_entry_points_are_declared_exported_bound_and_check_their_pool():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the inputs of the GPU tests and the input check of the row parity
+# the input check of the row parity, on the inputs of the GPU tests (pool_util: tokens, sequence, rows_fp64, gate_norm)
 # ---------------------------------------------------------------------------------------------------------------------------
-L = 4
-LENGTHS_GPU = (63, 5, 130)
-T_STEPS = 70
-# (dtype, H, Hkv, K, V): test_gpu_state_slots.CASES, whose last shape has groups that straddle rows (V = 72)
-CASES = [(torch.float32, 2, 2, 64, 64), (torch.bfloat16, 2, 2, 64, 64), (torch.float32, 4, 2, 64, 64), (torch.bfloat16, 4, 2, 64, 64),
-         (torch.float32, 2, 2, 40, 72)]
-IDS = ["fp32", "bf16", "fp32-G2", "bf16-G2", "fp32-K40V72"]
-ROW_EXTRA = 1e-3   # the row bound beyond the final rounding of a row: CAUSAL_TOL[dtype] - u for 16-bit tensors, the whole bound for fp32
-
-
-@functools.lru_cache(maxsize=None)
-def cpu_tokens(dtype, H, Hkv, K, V, B=3):
-    """test_gpu_state_slots.tokens, draw for draw, left on the CPU (that one copies to the device, which this file has none of):
-    hk, hv (the pack that fills the pool), q, k, v, gate of T_STEPS tokens per call row, norm weight, mix."""
-    from decode_util import signed_features
-    g = torch.Generator().manual_seed(4321)
-    n = sum(LENGTHS_GPU)
-    hk, hv = signed_features(g, 1, n, Hkv, K).to(dtype), torch.randn(1, n, Hkv, V, generator=g).to(dtype)
-    q, k = signed_features(g, B, T_STEPS, H, K).to(dtype), signed_features(g, B, T_STEPS, Hkv, K).to(dtype)
-    v, gate = torch.randn(B, T_STEPS, Hkv, V, generator=g).to(dtype), torch.randn(B, T_STEPS, H, V, generator=g).to(dtype)
-    w = torch.rand(V, generator=g) + 0.5
-    mix = torch.tril(torch.rand(L, L, generator=g).clamp(1e-5, 1))
-    return hk, hv, q, k, v, gate, w, mix
-
-
-def sequence(case, b):
-    """Request b of the GPU tests alone, on the CPU in fp64: (q, k, v [1, m + T_STEPS, H, .] with k, v repeated to the query heads
-    and zeros as the queries of the m prefilled tokens, gate [1, T_STEPS, H, V], w, mix, m)."""
-    dtype, H, Hkv, K, V = case
-    hk, hv, q, k, v, gate, w, mix = cpu_tokens(*case)
-    t0, m = sum(LENGTHS_GPU[:b]), LENGTHS_GPU[b]
-    rep = lambda t: t.double().repeat_interleave(H // Hkv, dim=2)
-    kk = torch.cat([rep(hk[:, t0:t0 + m]), rep(k[b:b + 1])], dim=1)
-    vv = torch.cat([rep(hv[:, t0:t0 + m]), rep(v[b:b + 1])], dim=1)
-    qq = torch.cat([torch.zeros(1, m, H, K, dtype=torch.float64), q[b:b + 1].double()], dim=1)
-    return qq, kk, vv, gate[b:b + 1].double(), w.double(), mix.double(), m
-
-
-def rows_fp64(q, k, v, mix, store=None):
-    """The causal operator in fp64, [1, T, H, V]; `store`: what a finished chunk's K^T V [1, H, K, V] becomes before anything reads it."""
-    T, K = q.shape[1], q.shape[-1]
-    qh, kh, vh = (t.permute(0, 2, 1, 3) for t in (q, k, v))
-    S, out = [], []
-    for i in range(-(-T // 64)):
-        r = slice(64 * i, min(T, 64 * i + 64))
-        Q, Kc, Vc = qh[:, :, r], kh[:, :, r], vh[:, :, r]
-        P = sum((mix[i, j] * S[j] for j in range(i)), torch.zeros_like(Kc.transpose(-1, -2) @ Vc))
-        out.append(K ** -0.5 * (Q @ P + mix[i, i] * (torch.tril(Q @ Kc.transpose(-1, -2)) @ Vc)))
-        Sj = Kc.transpose(-1, -2) @ Vc
-        S.append(Sj if store is None else store(Sj))
-    return torch.cat(out, dim=2).permute(0, 2, 1, 3)
-
-
 def through_h16(S):
     return decode(*encode(S.float())).double()
-
-
-def gate_norm(o, gate, w, eps=1e-5):
-    return o * torch.rsqrt(o.square().mean(-1, keepdim=True) + eps) * w * gate * torch.sigmoid(gate)
 
 
 def row_chunks(m, n):

@@ -2,8 +2,8 @@
 the blob's size against the layout's arithmetic, the host bookkeeping of both directions against `reset` and the page rule, shared
 pages stored once, the library calls a swap makes (recorded by tools/fake_decode_lib.py on CPU tensors) -- one on a device blob, a
 tiling of the item list on a host blob --, every refusal before anything is launched or changed, and the checks of the two entry
-points that return before a launch.  The pools are those of test_state_paged_h16_cpu.py: lengths (63, 5, 130) at slots [3, 0, 4],
-a scrambled table."""
+points that return before a launch.  The pools are `pool_util.host_pool`, as in test_state_paged_h16_cpu.py: lengths (63, 5, 130) at
+slots [3, 0, 4], a scrambled table."""
 import os
 import re
 import sys
@@ -12,12 +12,13 @@ import pytest
 import torch
 
 from mhla_amd import PagedCausalState, PoolExhausted, SwappedSlots, _lib, ops
-from test_state_paged_h16_cpu import CAP, E, GROUP, H, K, LENGTHS, N_PAGES, N_SLOTS, ROWS, V, host_state, new_pool
+from pool_util import CAP, GROUP, HOST_DIMS, HOST_ROWS as ROWS, N_SLOTS, host_pool, host_state
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from fake_decode_lib import Session  # noqa: E402
 
+H, K, V, N_PAGES = HOST_DIMS
 FORMATS = ["fp32", "h16"]
 OUT, IN = "mhla_causal_swap_out_paged", "mhla_causal_swap_in_paged"
 EINVAL = -22
@@ -83,7 +84,7 @@ def test_the_blob_size_is_the_layouts_arithmetic(fmt, Hkv, K, V):
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_the_blob_reports_the_size_the_library_gives(fmt):
     _build()
-    blob, _ = swap_out(new_pool(fmt), [3, 0, 4], release=False)
+    blob, _ = swap_out(host_pool(fmt), [3, 0, 4], release=False)
     assert blob.nbytes == blob.buffer.numel() == 3 * seq_bytes(H, K, V) + 2 * page_bytes(H, K, V, fmt)
     assert blob.buffer.dtype == torch.uint8 and blob.buffer.is_contiguous() and blob.buffer.data_ptr() % 16 == 0
     assert blob.nbytes == _lib.load().mhla_causal_swap_ws_bytes(3, 2, H, K, V, FORMATS.index(fmt))
@@ -97,7 +98,7 @@ def test_the_blob_reports_the_size_the_library_gives(fmt):
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_swap_out_leaves_the_pool_as_reset_does(fmt):
     _build()
-    pool, twin = new_pool(fmt), new_pool(fmt)
+    pool, twin = host_pool(fmt), host_pool(fmt)
     blob, calls = swap_out(pool, [3, 4])
     twin.reset([3, 4])
     assert isinstance(blob, SwappedSlots) and blob.lengths == (63, 130) and blob.page_format == fmt and blob.dims == (H, K, V)
@@ -112,7 +113,7 @@ def test_swap_out_leaves_the_pool_as_reset_does(fmt):
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_release_false_leaves_every_host_field(fmt):
     _build()
-    pool = new_pool(fmt)
+    pool = host_pool(fmt)
     before = state(pool)
     blob, calls = swap_out(pool, [3, 0, 4], release=False)
     assert state(pool) == before and blob.lengths == (63, 5, 130) and blob.seq_pages == ((), (), (0, 1))
@@ -127,7 +128,7 @@ def _ranges(calls):
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_a_device_blob_is_one_call_on_the_named_pool(fmt, monkeypatch):
     _build()
-    pool = new_pool(fmt)
+    pool = host_pool(fmt)
     pool.full
     seen = []
     launch = ops._swap_launch
@@ -162,7 +163,7 @@ def test_a_host_blob_is_staged_in_slices_that_tile_the_item_list(fmt, cap, monke
     cap = {"one-byte": 1, "one-sequence": sb, "sequence-and-page": sb + pb}[cap]
     at = lambda i: i * sb if i < 3 else 3 * sb + (i - 3) * pb
     monkeypatch.setattr(ops, "SWAP_STAGE_CAP_BYTES", cap)
-    pool = new_pool(fmt)
+    pool = host_pool(fmt)
     blob, calls = swap_out(pool, [3, 0, 4], device="cpu")   # 3 sequences + 2 pages = 5 items
     target = PagedCausalState.empty(4, H, K, V, CAP, 7, "cpu", page_format=fmt)
     back = swap_in(target, blob, [1, 3, 0])
@@ -186,7 +187,7 @@ def test_a_host_blob_is_staged_in_slices_that_tile_the_item_list(fmt, cap, monke
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_a_shared_page_is_stored_once_and_placed_once(fmt):
     _build()
-    pool = new_pool(fmt).fork(4, 2)
+    pool = host_pool(fmt).fork(4, 2)
     assert pool.table[2] == [7, 5, -1, -1] and pool.refs[7] == pool.refs[5] == 2
     blob, _ = swap_out(pool, [4, 2])
     assert blob.n_pages == 2 and blob.seq_pages == ((0, 1), (0, 1)) and blob.lengths == (130, 130)
@@ -204,7 +205,7 @@ def test_a_shared_page_is_stored_once_and_placed_once(fmt):
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_swapping_out_one_holder_leaves_the_other(fmt):
     _build()
-    pool = new_pool(fmt).fork(4, 2)
+    pool = host_pool(fmt).fork(4, 2)
     blob, _ = swap_out(pool, [4])
     assert blob.n_pages == 2 and blob.seq_pages == ((0, 1),)
     assert pool.table[2] == [7, 5, -1, -1] and pool.refs[7] == pool.refs[5] == 1 and pool.lengths[2] == 130 and pool.pos.tolist()[2] == 130
@@ -223,7 +224,7 @@ def _refused(pool, exc, match, call):
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_swap_out_refusals_change_nothing(fmt):
     _build()
-    pool = new_pool(fmt)
+    pool = host_pool(fmt)
     for slots, what in (([3, 3], "more than once"), ([5], "outside 0"), ([-1], "outside 0"), ([], "no slot given"), ([1.0], "must be ints")):
         _refused(pool, ValueError, what, lambda: pool.swap_out(slots))
     _refused(pool, ValueError, "'cpu' or the pool's device", lambda: pool.swap_out([3], device="meta"))
@@ -234,9 +235,9 @@ def test_swap_out_refusals_change_nothing(fmt):
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_swap_in_refusals_change_nothing(fmt):
     _build()
-    src = new_pool(fmt)
+    src = host_pool(fmt)
     blob, _ = swap_out(src, [3, 4], release=False)
-    pool = new_pool(fmt)
+    pool = host_pool(fmt)
     for slots, what in (([1, 1], "more than once"), ([1, 5], "outside 0"), ([1, 2.0], "must be ints")):
         _refused(pool, ValueError, what, lambda: pool.swap_in(blob, slots))
     _refused(pool, ValueError, r"1 slots for the 2 sequences", lambda: pool.swap_in(blob, [1]))
@@ -265,8 +266,8 @@ def test_swap_in_refusals_change_nothing(fmt):
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_pool_exhausted_is_raised_before_anything_changes(fmt):
     _build()
-    blob, _ = swap_out(new_pool(fmt), [3, 4], release=False)   # needs 1 + 3 pages
-    pool = new_pool(fmt)                                       # 4 free of 9 ...
+    blob, _ = swap_out(host_pool(fmt), [3, 4], release=False)   # needs 1 + 3 pages
+    pool = host_pool(fmt)                                       # 4 free of 9 ...
     pool.reserve([0], 65)                                      # ... 3 free: one too few
     assert pool.pages_free == 3
     _refused(pool, PoolExhausted, r"need 4 pages, the pool has 3 free", lambda: pool.swap_in(blob, [1, 2]))
