@@ -21,13 +21,13 @@
 // chunks touched after the first, whether the first segment closes chunk i, whether the state is full afterwards.  The later
 // segments are a grid dimension sized by the batch maximum the host vouches for; a workgroup whose sequence has no such segment
 // (or no token at all) returns after those two loads, before any LDS or other global traffic.  Six launches, whatever B, ntok, pos:
-//   k_cx_out<RAGGED>     first segment (also: nval[b] = the tokens the chain accepts for b, which the finish reads instead of pos)
-//   k_cx_xty_acc<RAGGED> first segment: Cur, or S[i_b] where that sequence's chunk closes
-//   k_cx_xty_acc<RAGGED> later segments (src null): whole chunks -> S[i_b + 1 + s], the tail -> Cur, no tail -> Cur = 0.  A launch
+//   k_cx_out<.ragged>    first segment (also: nval[b] = the tokens the chain accepts for b, which the finish reads instead of pos)
+//   k_cx_xty_acc<.ragged> first segment: Cur, or S[i_b] where that sequence's chunk closes
+//   k_cx_xty_acc<.ragged> later segments (src null): whole chunks -> S[i_b + 1 + s], the tail -> Cur, no tail -> Cur = 0.  A launch
 //                        of its own: the one before READS Cur, this one WRITES it
 //   k_cx_mix_ragged      c0 = i_b + 1, nc and cP per sequence; workspace stride = the batch maximum of later chunks
-//   k_cx_out<RAGGED>     later segments, P from the workspace
-//   k_cs_step_finish<WIN> every row of [B][T]: rows of the window from the staged fp32 rows, rows outside it written as ZEROS;
+//   k_cx_out<.ragged>    later segments, P from the workspace
+//   k_cs_step_finish<.win> every row of [B][T]: rows of the window from the staged fp32 rows, rows outside it written as ZEROS;
 //                        pos[b] += nval[b] -- the last launch, the only one that does not address by pos
 // (the middle three only when the host says some sequence closes a chunk).  Tiling and the order of every sum are the uniform
 // chain's, so a sequence gets the bits mhla_causal_extend gives it alone in a batch of one; a sequence with ONE token gets the
@@ -38,21 +38,28 @@
 // call finishes them, and the later segments' prefix mixes are formed from them.  The rows are the ragged extend's, bit for bit.
 // Commit (CxRag::acc; mhla_causal_commit_ragged): the state half of the chain alone, on the first min(acc[b], ntok[b]) tokens of each
 // window (the window still placed by ntok[b]), no q and no output -- at most four launches:
-//   k_cx_xty_acc<RAGGED> first segment (also nval[b]), k_cx_xty_acc<RAGGED> later segments, k_cx_mix_ragged with no workspace (only
+//   k_cx_xty_acc<.ragged> first segment (also nval[b]), k_cx_xty_acc<.ragged> later segments, k_cx_mix_ragged with no workspace (only
 //   the P of the chunk open afterwards is formed), k_cx_advance: pos[b] += nval[b] -- the last, the only one not addressing by pos
 // (the middle two only when some sequence closes a chunk).  The same tiles and sums again: the state is the one the ragged extend
 // leaves after acc[b] tokens, bit for bit; one accepted token takes the step's fmaf.
 // Packed new tokens (CxRag::off; mhla_causal_{extend,verify,commit}_packed): the tokens of all sequences are ONE run of T rows and
 // sequence b's are [off[b], off[b + 1]) -- the three chains above with the token views' batch stride 0, w = off[b + 1] - off[b] where
-// cx_seq reads ntok[b] and shift = off[b]; the fp32 rows are staged [h][T][V] and the finish is k_cs_step_finish<WIN, PACKED> over
+// cx_seq reads ntok[b] and shift = off[b]; the fp32 rows are staged [h][T][V] and the finish is k_cs_step_finish<.win, .packed> over
 // (H, T), which finds each row's sequence by a binary search over off.  The tiles, the K split and the order of every sum are the
 // padded chain's: the same bits per sequence.  Defence only: offsets that decrease or leave [0, T) skip the sequence.  PACKED is a
-// template parameter of cx_seq and of the three k_cx_* kernels that call it, so that the padded instantiations are the code they were.
+// template parameter of cx_seq and (CxVar::packed) of the three k_cx_* kernels that call it, so that the padded instantiations are the code they were.
 #pragma once
 #include "causal.hpp"
 #include "causal_step.hpp"
 
 namespace mhla {
+
+// the variants of k_cx_out, k_cx_xty_acc and k_cx_mix_ragged, named at the launch site: CxVar{.ragged = true, .packed = true}
+struct CxVar {
+    bool ragged = false, packed = false;
+    constexpr bool operator==(const CxVar&) const = default;
+    constexpr bool valid() const { return !packed || ragged; }   // a pack runs the ragged chain
+};
 
 // RAGGED: what every kernel of the ragged chain derives its sequence's plan from
 struct CxRag {
@@ -213,9 +220,10 @@ __device__ __forceinline__ void cx_one_token(const CxOutArgs& a, float* red, con
 
 // grid (segments, B H, ceil(V / 64)): k_cs_out on a run of <= 64 token rows of one chunk.  It only reads the state: with a.G > 1 the G
 // query heads of a group read the one state of their k/v head (causal_step.hpp), each with the tiles and sums of the ungrouped call
-template <typename T, bool RAGGED = false, bool PACKED = false>
+template <typename T, CxVar VAR = CxVar{}>
 __global__ __launch_bounds__(NTHREADS) void k_cx_out(const CxOutArgs a) {
-    static_assert(!PACKED || RAGGED, "a pack runs the ragged chain");
+    static_assert(VAR.valid(), "no such extend: see CxVar::valid");
+    constexpr bool RAGGED = VAR.ragged, PACKED = VAR.packed;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Qs = smem;                  // [64 c][66]
     float* Ks = Qs + CS * CS_LDX;      // [64 c'][66]
@@ -340,9 +348,10 @@ struct CxAccArgs {
 // closes, else Cur; one token: fmaf(k, v, Cur), the step's rank-1 update.  later = 1: K^T V alone (k_bm_state<2>'s tiles, loads and
 // kend: the same sums) of later segment blockIdx.x -- 64 rows -> S[i_b + 1 + s], fewer (the tail) -> Cur -- and segment 0's workgroups
 // write Cur = 0 for a sequence that closed its chunk and has no tail.  The two are separate launches: the first reads Cur.
-template <typename T, bool RAGGED = false, bool PACKED = false>
+template <typename T, CxVar VAR = CxVar{}>
 __global__ __launch_bounds__(NTHREADS) void k_cx_xty_acc(const CxAccArgs a) {
-    static_assert(!PACKED || RAGGED, "a pack runs the ragged chain");
+    static_assert(VAR.valid(), "no such extend: see CxVar::valid");
+    constexpr bool RAGGED = VAR.ragged, PACKED = VAR.packed;
     constexpr int LD = ld_kmajor(64);
     __shared__ __attribute__((aligned(16))) float Xs[CS * LD];
     __shared__ __attribute__((aligned(16))) float Ys[CS * LD];
@@ -531,8 +540,10 @@ struct CxMixRagArgs {
 // grid (ceil(E / 4 / 64), B H, groups of the largest nc): each (b, h) for itself -- a sequence that closes no chunk returns; else
 // c0 = i_b + 1, its own later chunks to the workspace (stride rag.max_later), P of the chunk open afterwards to the state's P, or P = 0
 // where that sequence's state is then full
-template <bool PACKED = false>
+template <CxVar VAR = CxVar{.ragged = true}>
 __global__ __launch_bounds__(64) void k_cx_mix_ragged(const CxMixRagArgs a) {
+    static_assert(VAR.valid() && VAR.ragged, "the ragged mix: see CxVar::valid");
+    constexpr bool PACKED = VAR.packed;
     const long e = ((long)blockIdx.x * 64 + threadIdx.x) * 4;
     if (e >= a.m.E) return;   // (E % 4 == 0)
     const long bh = blockIdx.y;

@@ -135,13 +135,25 @@ constexpr int CST_GMAX = 8;       // query heads per k/v head the grouped step s
 // the loop over g fully unrolled and predicated by a.G alone (uniform over the launch)
 // PAGED (DEV on a paged pool): a sequence is live iff its position is inside the capacity AND the table names a page for chunk
 // pos / 64 -- the page its boundary roll will write; the step itself touches no page
-template <typename T, bool RAGGED = false, bool DEV = false, bool PRO = false, int GMAX = 1, bool SLOT = false, bool PAGED = false>
+// the step's variants, named at the launch site: StepVar{.ragged = true, .dev = true, .gmax = CST_GMAX}
+struct StepVar {
+    bool ragged = false, dev = false, pro = false;
+    int gmax = 1;
+    bool slot = false, paged = false;
+    constexpr bool operator==(const StepVar&) const = default;
+    constexpr bool valid() const {
+        return (!slot || ragged)              // a slot map goes with positions on the device
+               && (!paged || (slot && dev))   // the step reads the page table only to tell a live sequence from a frozen one
+               && (!dev || ragged)            // dev is the ragged step, bounded by the capacity
+               && (!pro || dev)               // the fused prologue goes with the device-positioned step
+               && (gmax == 1 || ragged);      // grouped heads: the ragged and device-positioned steps only
+    }
+};
+template <typename T, StepVar VAR = StepVar{}>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step(const CsStepArgs a) {
-    static_assert(!SLOT || RAGGED, "a slot map goes with positions on the device");
-    static_assert(!PAGED || (SLOT && DEV), "the step reads the page table only to tell a live sequence from a frozen one");
-    static_assert(!DEV || RAGGED, "DEV is the ragged step, bounded by the capacity");
-    static_assert(!PRO || DEV, "the fused prologue goes with the device-positioned step");
-    static_assert(GMAX == 1 || RAGGED, "grouped heads: the ragged and device-positioned steps only");
+    static_assert(VAR.valid(), "no such step: see StepVar::valid");
+    constexpr bool RAGGED = VAR.ragged, DEV = VAR.dev, PRO = VAR.pro, SLOT = VAR.slot, PAGED = VAR.paged;
+    constexpr int GMAX = VAR.gmax;
     __shared__ __attribute__((aligned(16))) float red[GMAX][CST_RG][CST_VT];
     const int tid = threadIdx.x, c4 = (tid & 15) * 4, rg = tid >> 4;
     const int bh = blockIdx.z, b = bh / a.H, h = bh - b * a.H;
@@ -285,11 +297,19 @@ struct CsFinishArgs {
 // sequence its row belongs to by a binary search over off (workgroup-uniform, read as cst_page reads the table; at most 17 halvings
 // for the 65535 sequences a grid holds); a row of a sequence the chain did not accept (nval[b] = 0), or -- defence only -- of no
 // sequence, is written as zeros; the workgroup of head 0 on the first row of sequence b advances its position
-template <typename T, bool DEV = false, bool WIN = false, bool SLOT = false, bool PAGED = false, bool PACKED = false>
+struct FinishVar {
+    bool dev = false, win = false, slot = false, paged = false, packed = false;
+    constexpr bool operator==(const FinishVar&) const = default;
+    constexpr bool valid() const {
+        return !(dev && win)                  // the device-positioned step has one row per sequence
+               && (!paged || (slot && dev))   // the finish reads the page table only to tell a live sequence from a frozen one
+               && (!packed || win);           // a pack is a set of windows
+    }
+};
+template <typename T, FinishVar VAR = FinishVar{}>
 __global__ __launch_bounds__(CST_THREADS) void k_cs_step_finish(const CsFinishArgs a) {
-    static_assert(!(DEV && WIN), "the device-positioned step has one row per sequence");
-    static_assert(!PAGED || (SLOT && DEV), "the finish reads the page table only to tell a live sequence from a frozen one");
-    static_assert(!PACKED || WIN, "a pack is a set of windows");
+    static_assert(VAR.valid(), "no such finish: see FinishVar::valid");
+    constexpr bool DEV = VAR.dev, WIN = VAR.win, SLOT = VAR.slot, PAGED = VAR.paged, PACKED = VAR.packed;
     __shared__ float red[CST_THREADS / 64];
     const int tid = threadIdx.x;
     int bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
@@ -473,7 +493,7 @@ __device__ __forceinline__ void csh_st8(float* p, const f32x8 x) {
     gst<f32x4>(p + 4, f32x4{x[4], x[5], x[6], x[7]});
 }
 
-// the h16 roll: k_cs_roll<RAGGED or PACK, SLOT, PAGED, PF_H16>, grid (ceil(E / 8 / 64), B H), one wave per workgroup.  What RAGGED
+// the h16 roll: k_cs_roll<RollVar{.ragged or .pack, .slot, .paged, .fmt = PF_H16}>, grid (ceil(E / 8 / 64), B H), one wave per workgroup.  What RAGGED
 // and PACK derive per sequence is what the fp32 kernel derives.  The commit encodes Cur into the page (the multiplier from one lane
 // of the group, the payload from all) and zeroes Cur; the new P is the ascending fmaf sum over DECODED pages, the chunk just
 // committed included -- mixrow[n] * decode(encode(last)), not the fp32 `last` -- so that P is a function of the pages alone and a
@@ -572,11 +592,21 @@ __device__ __forceinline__ void cs_roll_h16(const CsRollArgs& a) {
 // order.  A boundary whose chunk has no page leaves the sequence untouched: for the device-positioned step that sequence is frozen
 // (step and finish derive the same from pos and the table), for a host-positioned call it is defence only
 // FMT == PF_H16 (h16 pages): cs_roll_h16 above, grid (ceil(E / 8 / 64), B H); the fp32 instantiations are the code they were
-template <bool RAGGED = false, bool PACK = false, bool SLOT = false, bool PAGED = false, int FMT = PF_F32>
+struct RollVar {
+    bool ragged = false, pack = false, slot = false, paged = false;
+    int fmt = PF_F32;
+    constexpr bool operator==(const RollVar&) const = default;
+    constexpr bool valid() const {
+        return !(ragged && pack)                          // one addressing mode
+               && (!paged || (slot && (ragged || pack)))  // a paged pool is addressed through a slot map
+               && (fmt == PF_F32 || paged);               // a page format goes with a paged pool
+    }
+};
+template <RollVar VAR = RollVar{}>
 __global__ __launch_bounds__(64) void k_cs_roll(const CsRollArgs a) {
-    static_assert(!(RAGGED && PACK), "one addressing mode");
-    static_assert(!PAGED || (SLOT && (RAGGED || PACK)), "a paged pool is addressed through a slot map");
-    static_assert(FMT == PF_F32 || PAGED, "a page format goes with a paged pool");
+    static_assert(VAR.valid(), "no such roll: see RollVar::valid");
+    constexpr bool RAGGED = VAR.ragged, PACK = VAR.pack, SLOT = VAR.slot, PAGED = VAR.paged;
+    constexpr int FMT = VAR.fmt;
     if constexpr (FMT == PF_H16) {
         cs_roll_h16<RAGGED, PACK>(a);
         return;

@@ -7,8 +7,9 @@ layer must leave them identical):
                                                        # sections) with never-dereferenced aligned pointers
 Every launch is one line on stderr: name string, the kernel's own symbol (dladdr: the exact template instantiation), grid, block, dynamic
 LDS size, stream and a hash of the argument bytes; every call's return code and message and every size / capability query's answer too.
-In the two causal units (the operator: the twelve mhla_causal_* / mhla_causal_varlen_* calls and queries; the decode state: its six entry
-points and three size queries) hipMemsetAsync is a logger as well -- one MEMSET line -- so the launches behind a memset are recorded.
+In the two causal units (the operator: the twelve mhla_causal_* / mhla_causal_varlen_* calls and queries; the decode state: every launching
+entry point and size query of capi_causal_state.hip, DECODE_ENTRIES, and the decode prologue of capi_misc.hip) hipMemsetAsync is a logger as
+well -- one MEMSET line -- so the launches behind a memset are recorded.
 `diff` the logs of the two trees.  The argument hash covers struct padding: build with RECORD_ZERO_INIT=1 (host pass with
 -ftrivial-auto-var-init=zero, which reaches named locals only) to compare it."""
 import ctypes
@@ -39,12 +40,19 @@ inline hipError_t rec_memset(void* p, int value, size_t bytes, hipStream_t strea
 #endif
 
 '''
-UNITS = ["capi", "capi_bm_f32", "capi_bm_bf16", "capi_bm_bf16hl", "capi_bm_f16", "capi_bm_wanpro", "capi_causal", "capi_causal_gqa", "capi_causal_state"]
+UNITS = ["capi", "capi_bm_f32", "capi_bm_bf16", "capi_bm_bf16hl", "capi_bm_f16", "capi_bm_wanpro", "capi_causal", "capi_causal_gqa", "capi_causal_state", "capi_misc"]
 CAUSAL_ENTRIES = ("mhla_causal_fwd_ws_bytes", "mhla_causal_bwd_ws_bytes", "mhla_causal_normgate_fusable", "mhla_causal_fwd", "mhla_causal_normgate_fwd",
                   "mhla_causal_bwd", "mhla_causal_varlen_fwd_ws_bytes", "mhla_causal_varlen_bwd_ws_bytes", "mhla_causal_varlen_normgate_fusable",
                   "mhla_causal_varlen_fwd", "mhla_causal_varlen_normgate_fwd", "mhla_causal_varlen_bwd")
 DECODE_ENTRIES = ("mhla_causal_step_ws_bytes", "mhla_causal_state_init", "mhla_causal_step", "mhla_causal_step_ragged", "mhla_causal_step_dev",
-                  "mhla_causal_extend_ws_bytes", "mhla_causal_extend", "mhla_causal_extend_ragged_ws_bytes", "mhla_causal_extend_ragged")
+                  "mhla_causal_extend_ws_bytes", "mhla_causal_extend", "mhla_causal_extend_ragged_ws_bytes", "mhla_causal_extend_ragged",
+                  "mhla_causal_verify_ragged", "mhla_causal_commit_ragged_ws_bytes", "mhla_causal_commit_ragged", "mhla_causal_extend_ragged_gqa_ws_bytes",
+                  "mhla_causal_extend_packed_ws_bytes", "mhla_causal_varlen_state_init", "mhla_causal_varlen_state_init_slots",
+                  "mhla_causal_varlen_state_init_paged", "mhla_causal_varlen_state_init_paged_h16", "mhla_causal_varlen_state_init_paged_h16_ws_bytes",
+                  "mhla_causal_swap_ws_bytes", "mhla_causal_swap_out_paged", "mhla_causal_swap_in_paged", "mhla_featmap_rotary_decode") + tuple(
+    f"mhla_causal_{name}_{form}" for name, forms in (("step", ("ragged_gqa", "slots", "paged", "paged_h16")), ("step_dev", ("gqa", "slots", "paged", "paged_h16")),
+                                                     ("extend", ("ragged_gqa", "slots", "paged", "packed")), ("verify", ("ragged_gqa", "slots", "paged", "packed")),
+                                                     ("commit", ("slots", "paged", "packed"))) for form in forms)
 
 
 def build(tree, out):
@@ -194,8 +202,9 @@ def run_causal(lib, L):
 
 
 def run_decode(lib, L):
-    """The decode state: init, the three steps and the two extensions.  Every call is made from one dict of arguments; a variant
-    overrides some of them (a null or misaligned pointer, a short workspace, every ldmix from 0 to past the capacity)."""
+    """The decode state: init, the three steps and the two extensions, then (decode_forms) their forms, the commit, the pack prefill and
+    the swap.  Every call is made from one dict of arguments; a variant overrides some of them (a null or misaligned pointer, a short
+    workspace, every ldmix from 0 to past the capacity)."""
     call = Calls(lib)
     NV = L.NULL_VIEW
     for (B, H), K, Vd, dt, cap in itertools.product(((2, 2), (4, 64)), (64, 128, 100, 6), (64, 192), (L.F32, L.BF16, L.F16), (1, 3, 5)):
@@ -246,7 +255,103 @@ def run_decode(lib, L):
                     xws = lib.mhla_causal_extend_ragged_ws_bytes(B, T, H, K, Vd, later, dt)
                     call(f"EXTEND_RAGGED T={T} max_end={max_end} max_later={later} any_close={close} left={left} ws={xws}", "mhla_causal_extend_ragged",
                          a["q"], a["k"], a["v"], *state, a["pos_dev"], a["ntok_dev"], T, max_end, later, close, left, *epi, xws - a["short"], *dims)
+        decode_forms(call, lib, L, base, B, H, K, Vd, dt, cap)
     return call.n
+
+
+def decode_forms(call, lib, L, base, B, H, K, Vd, dt, cap):
+    """The forms of the ragged entry points at one (shape, dtype, capacity) -- grouped-query, slots, pages, h16 pages, packed tokens -- the
+    commit, the pack prefill and the swap, on a thinner grid of positions and token counts than the calls above.  A variant names the
+    forms it bears on: a null slot map is tried on the forms that take one."""
+    NV = L.NULL_VIEW
+    base = dict(base, Hkv=H, slot_dev=at(26), n_slots=B + 3, table_dev=at(27), pages=at(28), n_pages=B * cap + 2, page_mult=at(29), off_dev=at(30),
+                accept_dev=at(31), seq_len_dev=at(32), chunk_tab_dev=at(33), chunk_dst_dev=at(34), items_dev=at(35), blob=at(36), n_seqs=B, n_chunks=None)
+    POOLS, ALL = ("slots", "paged", "paged_h16", "packed"), ("gqa", "slots", "paged", "paged_h16", "packed", "init", "swap", "rotary")
+    variants = [("", {}, ALL), ("packed dense", dict(table_dev=None), ("packed",)), ("packed rows", dict(table_dev=None, slot_dev=None), ("packed", "rotary")),
+                ("packed pages, no slots", dict(slot_dev=None), ("packed",)), ("Hkv=H/2", dict(Hkv=max(1, H // 2)), ALL[:5] + ("rotary",))]
+    if H == 64:
+        variants += [("Hkv=3", dict(Hkv=3), ALL[:5] + ("rotary",)), ("Hkv=4", dict(Hkv=4), ALL[:5])]   # (Hkv not dividing H; G = 16 above the 8 a group holds)
+    if H == 2:   # (the variants on the smaller batch)
+        on = dict(slot_dev=POOLS + ("init", "rotary"), table_dev=POOLS[1:] + ("init",), pages=POOLS[1:] + ("init", "swap"), page_mult=("paged_h16", "init", "swap"),
+                  off_dev=("packed", "rotary"), accept_dev=ALL[1:5], seq_len_dev=("init",), chunk_tab_dev=("init",), chunk_dst_dev=("init",), items_dev=("swap",),
+                  blob=("swap",), S=("gqa", "slots", "packed", "init"), P=ALL[:7], Cur=ALL[:7], pos_dev=ALL, full_dev=ALL[:4] + ("swap",), ntok_dev=ALL[:3] + ("rotary",),
+                  ws=ALL[:6], mix=ALL[:6])
+        variants += [(f"{name}={'null' if o is None else 'off' + str(o)}", {name: None if o is None else base[name] + o}, kinds)
+                     for name, kinds in on.items() for o in ((None,) if name == "mix" else (None, 4) if name == "chunk_tab_dev" else (None, 8) if name in ("S", "P", "Cur", "pages", "blob", "ws") else (None, 2))]
+        variants += [(f"{name}=0", {name: 0}, kinds) for name, kinds in (("n_slots", POOLS + ("init", "swap", "rotary")), ("n_pages", POOLS[1:] + ("init", "swap")),
+                                                                        ("n_seqs", ("init", "swap")), ("n_chunks", ("init",)))]
+        variants += [("Hkv=3", dict(Hkv=3), ALL[:5] + ("rotary",)), ("no y", dict(y=NV, gate=NV, nw=None), ALL[:5]), ("no out", dict(out=NV), ALL[:5]),
+                     ("ws-1", dict(short=1), ALL[:6]), ("chunk=32", dict(chunk=32), ALL[:6]), ("ldmix=cap-1", dict(ld=cap - 1), ALL[:6])]
+    positions = sorted({-1, 0, 63, 64 * cap - 1, 64 * cap})
+    cs = at(16), at(17)
+    for vname, over, kinds in variants:
+        a = dict(base, **over)
+        Hkv = a["Hkv"]
+        say(f"FORMS {vname}")
+        q, k, v = a["q"], a["k"], a["v"]
+        ragged = (a["mix"], a["ld"], a["S"], cap, a["P"], a["Cur"], a["pos_dev"])
+        paged_at = lambda *pages: (a["mix"], a["ld"], *pages, a["n_pages"], a["table_dev"], cap, a["P"], a["Cur"])   # noqa: E731
+        slot = (a["slot_dev"], a["n_slots"])
+        states = dict(gqa=ragged, slots=ragged + slot, paged=paged_at(a["pages"]) + (a["pos_dev"],) + slot,
+                      paged_h16=paged_at(a["pages"], a["page_mult"]) + (a["pos_dev"],) + slot, packed=paged_at(a["S"] if a["table_dev"] is None else a["pages"]) + (a["pos_dev"],) + slot)
+        names = dict(gqa=("step_ragged_gqa", "step_dev_gqa", "extend_ragged_gqa", "verify_ragged_gqa", "commit_ragged"), slots=("step_slots", "step_dev_slots", "extend_slots", "verify_slots", "commit_slots"),
+                     paged=("step_paged", "step_dev_paged", "extend_paged", "verify_paged", "commit_paged"), paged_h16=("step_paged_h16", "step_dev_paged_h16", None, None, None),
+                     packed=(None, None, "extend_packed", "verify_packed", "commit_packed"))
+        epi = (a["out"], a["gate"], a["nw"], 1e-6, a["y"], a["ws"])
+        dims, step_ws = (B, H, Hkv, K, Vd, a["chunk"], 0.125, dt, 0x1000), lib.mhla_causal_step_ws_bytes(B, H, K, Vd, dt) - a["short"]
+        for kind in (kd for kd in ALL[:5] if kd in kinds):
+            state, (step, step_dev, extend, verify, commit) = states[kind], names[kind]
+            if step:
+                for pos, anyb in itertools.product(positions, (0, 1)):
+                    call(f"{step} max_pos={pos} any_boundary={anyb}", "mhla_causal_" + step, q, k, v, *state, pos, anyb, *epi, step_ws, *dims)
+                for fmap, cos, sin in ((0, None, None), (2, None, None), (1, *cs), (0, cs[0], None), (3, None, None)):
+                    call(f"{step_dev} fmap={fmap} rope={int(bool(cos))}{int(bool(sin))}", "mhla_causal_" + step_dev, q, k, v, *state, a["full_dev"], cos, sin, K // 2, 64 * cap, fmap,
+                         *epi, step_ws, *dims)
+            if not extend:
+                continue
+            pk = kind == "packed"
+            for T in (0, 1, 130, 65536):
+                most = (T + 62) // 64
+                for max_end, later, close, left in itertools.product((-1, 0, 65, 64 * cap, 64 * cap + 1), sorted({0, most, most + 1}), (0, 1), (0,) if pk else (0, 1)):
+                    if pk:
+                        xws, tok = lib.mhla_causal_extend_packed_ws_bytes(B, T, H, Hkv, K, Vd, later, dt), (a["off_dev"], T, max_end, later, close)
+                    else:
+                        xws, tok = lib.mhla_causal_extend_ragged_gqa_ws_bytes(B, T, H, Hkv, K, Vd, later, dt), (a["ntok_dev"], T, max_end, later, close, left)
+                    tag = f"T={T} max_end={max_end} max_later={later} any_close={close} left={left} ws={xws}"
+                    call(f"{extend} {tag}", "mhla_causal_" + extend, q, k, v, *state, *tok, *epi, xws - a["short"], *dims)
+                    call(f"{verify} {tag}", "mhla_causal_" + verify, q, k, v, *state, *tok, *epi, xws - a["short"], *dims)
+                    if kind == "gqa" and Hkv != H:
+                        continue   # (the commit has no grouped form of its own: it runs on the k/v heads)
+                    cws = lib.mhla_causal_commit_ragged_ws_bytes(B, dt)
+                    call(f"{commit} {tag} cws={cws}", "mhla_causal_" + commit, k, v, *state, tok[0], a["accept_dev"], *tok[1:], a["ws"], cws - a["short"],
+                         *((B, Hkv) if pk else (B, H)), K, Vd, a["chunk"], dt, 0x1000)
+        if "init" in kinds:   # the pack prefill: a pack of T tokens in n_chunks chunks (default: as few as hold them)
+            for T, max_len in ((0, 0), (1, 1), (130, 65), (130, 131), (64 * cap + 64, 64 * cap), (64 * cap + 64, 64 * cap + 1)):
+                for nc in ((a["n_chunks"],) if a["n_chunks"] is not None else sorted({(T + 63) // 64, (T + 63) // 64 + 1, (T + 63) // 64 - 1, T + 1})):
+                    tail = (max_len, T, H, K, Vd, a["chunk"], nc, a["chunk_tab_dev"], a["chunk_dst_dev"])
+                    seqs, dense = (a["n_seqs"], a["seq_len_dev"]), (a["mix"], a["ld"], a["S"], cap, a["P"], a["Cur"])
+                    tag = f"T={T} max_len={max_len} n_chunks={nc}"
+                    call(f"varlen_state_init {tag}", "mhla_causal_varlen_state_init", k, v, *dense, *seqs, *tail, dt, 0x1000)
+                    call(f"varlen_state_init_slots {tag}", "mhla_causal_varlen_state_init_slots", k, v, *dense, *seqs, *slot, *tail, dt, 0x1000)
+                    call(f"varlen_state_init_paged {tag}", "mhla_causal_varlen_state_init_paged", k, v, *paged_at(a["pages"]), *seqs, *slot, *tail, dt, 0x1000)
+                    for hws in sorted({lib.mhla_causal_varlen_state_init_paged_h16_ws_bytes(n_, H, K, Vd, dt) for n_ in (nc, 1, 2)}):
+                        call(f"varlen_state_init_paged_h16 {tag} ws={hws}", "mhla_causal_varlen_state_init_paged_h16", k, v, *paged_at(a["pages"], a["page_mult"]), *seqs, *slot,
+                             *tail, a["ws"], hws - a["short"], dt, 0x1000)
+        if "swap" in kinds:   # item ranges inside, empty and outside a list of n_seqs sequences and 3 pages; fp32 pages (no multipliers) and h16
+            n_seqs, moved = a["n_seqs"], 3
+            for mult, (i0, i1) in itertools.product((None, a["page_mult"]), ((0, n_seqs + moved), (0, 1), (n_seqs, n_seqs + 1), (1, n_seqs + 1), (2, 2), (-1, 1), (2, 1), (0, n_seqs + moved + 1))):
+                for fd in (a["full_dev"], None):
+                    say(f"SWAP ws={lib.mhla_causal_swap_ws_bytes(n_seqs, moved, Hkv, K, Vd, 0 if mult is None else 1)}")
+                    for d in ("out", "in"):
+                        call(f"swap_{d} mult={int(mult is not None)} full={int(fd is not None)} items=[{i0},{i1})", f"mhla_causal_swap_{d}_paged", a["pages"], mult, a["n_pages"], a["P"],
+                             a["Cur"], a["pos_dev"], fd, a["n_slots"], a["items_dev"], n_seqs, moved, i0, i1, a["blob"], Hkv, K, Vd, 0x1000)
+        if "rotary" in kinds:   # the decode prologue (capi_misc.hip): padded windows and packed tokens, with and without a slot map
+            yq, yk = L.View(at(37), 1 << 24, H * K, K), L.View(at(38), 1 << 24, Hkv * K, K)
+            for T, fmap, (ntok, off, left) in itertools.product((0, 1, 130), (0, 2, 3), ((a["ntok_dev"], None, 0), (a["ntok_dev"], None, 1), (None, None, 0), (None, a["off_dev"], 0),
+                                                                                       (a["ntok_dev"], a["off_dev"], 0), (None, a["off_dev"], 1))):
+                for cos, sin, ldt in ((*cs, K // 2), (cs[0], None, K // 2), (cs[0] + 8, cs[1], K // 2), (*cs, K // 2 + 2), (*cs, K // 2 + 4)):
+                    call(f"rotary_decode T={T} fmap={fmap} ntok={int(bool(ntok))} off={int(bool(off))} left={left} cos={cos and hex(cos)} sin={int(bool(sin))} ld_tab={ldt}",
+                         "mhla_featmap_rotary_decode", q, k, cos, sin, ldt, 64 * cap, a["pos_dev"], a["slot_dev"], a["n_slots"], ntok, off, T, left, yq, yk, B, H, Hkv, K, fmap, dt, 0x1000)
 
 
 if __name__ == "__main__":
